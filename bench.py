@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- headline benchmark: batched 64 KiB-block LZ4 decode on MI355X (BASELINE.json configs[1]).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--blocks B] [--dist D] [--no-extras]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--blocks B] [--dist D] [--no-extras] [--dump-outputs DIR]
 
 One "step" = one pass of the batched known-size decoder over the whole resident batch (2^20 blocks of
 64 KiB per GPU by default; every buffer is in HBM before the timed region starts).  For N > 1 the driver
@@ -80,7 +80,12 @@ def parse_args():
                          "built from separately allocated chunks whose placement the library measures: DESIGN.md 4.2)")
     ap.add_argument("--verify-budget", type=float, default=45.0,
                     help="seconds of host time for EACH full-corpus encoder check against the CPU reference (0 = skip)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (rank 0's shard) as DIR/<name>.npy: see dump_outputs()")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def relaunch_as_ranks(args):
@@ -165,6 +170,28 @@ class Workload:
     @property
     def algorithmic_bytes(self):           # sum(u_i + c_i + 8)
         return self.raw_bytes + self.comp_bytes + 8 * self.n
+
+
+DUMP_ROWS = 192      # decoded rows in the dump: 192 x 64 KiB as float32 = 48 MiB, so that with the per-block results it stays under 64 MB
+DUMP_LIMIT = 64_000_000
+
+
+def dump_outputs(out_dir, wl, seed):
+    """What the timed decode step hands its caller, as of its last run: the per-block result (compressed bytes consumed,
+    every block of the shard) and the decoded bytes of DUMP_ROWS blocks drawn with `seed` (row numbers ascending, saved
+    beside them), all as float32 / float64 .npy files.  Same arguments, same inputs, same files: two builds compare
+    output for output."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    rows = np.sort(np.random.default_rng(seed).choice(wl.n, size=min(DUMP_ROWS, wl.n), replace=False))
+    decoded = wl.back.index_select(0, torch.from_numpy(rows).to(wl.back.device))[:, :wl.batch.BLOCK].cpu().numpy()
+    arrays = {"decode_result": wl.used.cpu().numpy().astype(np.float32),
+              "decoded_sample_rows": rows.astype(np.float64),
+              "decoded_sample": decoded.astype(np.float32)}
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_LIMIT, "the output dump would exceed 64 MB"
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def cpu_model():
@@ -350,6 +377,8 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     ok = wl.verify()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, wl, seed)
 
     tmax = torch.tensor([elapsed], dtype=torch.float64)
     stats = torch.tensor([float(wl.algorithmic_bytes), float(wl.comp_bytes), float(ok)], dtype=torch.float64)

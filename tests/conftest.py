@@ -18,14 +18,6 @@ def oracle():
     return Oracle()
 
 
-@pytest.fixture(scope="session")
-def reference():
-    from oracle.oracle import Reference
-    if not Reference.available():
-        pytest.skip("oracle/_ref not built (reference checkout absent and no prebuilt .so)")
-    return Reference()
-
-
 # ---- forcing a block->hardware mapping (lz4hip_tuning_set) AND proving that it ran (lz4hip_dispatch_counts) --------
 _FAMILY = {"LZ4HIP_DECODER": (0, 1), "LZ4HIP_ENCODER": (2, 3), "LZ4HIP_HC": (4, 5)}   # (wave counter, lane counter)
 _KNOB = {"LZ4HIP_DECODER": "decoder", "LZ4HIP_ENCODER": "encoder", "LZ4HIP_HC": "hc"}

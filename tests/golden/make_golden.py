@@ -1,5 +1,6 @@
-"""Generates tests/golden/vectors.json from the REFERENCE's own C (oracle/_ref/libref_lz4.so, built in
-place from /root/reference/original by oracle/Makefile).  Run in the build container only:
+"""Generates tests/golden/vectors.json and tests/golden/ref_records.json from the REFERENCE's own C
+(oracle/_ref/libref_lz4.so and lz4demo, built in place from /root/reference/original by oracle/Makefile).
+Run in the build container only:
 
     python tests/golden/make_golden.py
 
@@ -11,13 +12,17 @@ streams are pinned here too via sha256 -- or given inline as hex.
 import hashlib
 import json
 import os
+import subprocess
 import sys
+import tempfile
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 from oracle.oracle import Oracle, Reference, compress_bound  # noqa: E402
+import ref_records as rr  # noqa: E402
 
 LOREM = (b"Lorem ipsum dolor sit amet, consectetur adipisicing elit, sed do eiusmod tempor incididunt ut "
          b"labore et dolore magna aliqua. Ut enim ad minim veniam, quis nostrud exercitation ullamco laboris "
@@ -83,6 +88,40 @@ def main():
     with open(path, "w") as f:
         json.dump(out, f, indent=1)
     print("wrote", path, len(synth), "synthetic +", len(inline), "inline vectors")
+    records(o, r)
+
+
+def records(o, r):
+    """The reference's answers to the calls of tests/ref_records.py, and what its CLI (oracle/_ref/lz4demo) writes and
+    reads back for the frames of tests/test_legacy_frame.py."""
+    out = dict(generator="tests/golden/make_golden.py", source="oracle/_ref/libref_lz4.so, oracle/_ref/lz4demo")
+    for section, walk in (("encoders", rr.encoders(r, o)), ("decoders", rr.decoders(r, o)), ("alignment", rr.alignment(r, o)),
+                          ("streams", rr.streams(r))):
+        out[section] = rr.summarise(walk)[0]
+    cli = os.path.join(ROOT, "oracle", "_ref", "lz4demo")
+    frames = {}
+    with tempfile.TemporaryDirectory() as tmp:
+        src, dst, back = (os.path.join(tmp, f) for f in ("in", "frame", "back"))
+        for n_bytes, dist, hc in sorted(set([rr.FRAME_PARSE_CASE] + rr.FRAME_INTEROP_CASES)):
+            data = rr.frame_sample(o, n_bytes, dist)
+            with open(src, "wb") as f:
+                f.write(data)
+            subprocess.run([cli, "-c1" if hc else "-c0", src, dst], check=True, capture_output=True, timeout=300)
+            with open(dst, "rb") as f:
+                frame = f.read()
+            rc = subprocess.run([cli, "-d", dst, back], capture_output=True, timeout=300).returncode
+            with open(back, "rb") as f:
+                decoded = f.read()
+            assert rc == 0 and decoded == data, ("the reference CLI does not read back its own frame", n_bytes, dist, hc)
+            frames[rr.frame_key(n_bytes, dist, hc)] = dict(len=len(frame), sha=rr.sha(frame), cli_decode_rc=rc,
+                                                           cli_decode_sha=rr.sha(decoded))
+    out["frames"] = frames
+    with open(rr.GOLDEN, "w") as f:       # one case per line
+        f.write("{\n" + ",\n".join(
+            json.dumps(k) + ": " + (json.dumps(v) if isinstance(v, str) else
+                                    "{\n" + ",\n".join(f" {json.dumps(g)}: {json.dumps(e)}" for g, e in v.items()) + "\n}")
+            for k, v in out.items()) + "\n}\n")
+    print("wrote", rr.GOLDEN, {k: len(v) for k, v in out.items() if isinstance(v, dict)})
 
 
 if __name__ == "__main__":
