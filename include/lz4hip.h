@@ -114,6 +114,63 @@ int lz4hip_decode_batch_host(const lz4hip_batch_t* b, int known_output_size);
 int lz4hip_encode_batch_host_multi(const lz4hip_batch_t* b, int mode, uint64_t device_mask);
 int lz4hip_decode_batch_host_multi(const lz4hip_batch_t* b, int known_output_size, uint64_t device_mask);
 
+/* ---- LZ4Stream buffers ---------------------------------------------------------------------------
+ * The wire format of lz4net's LZ4Stream (src/LZ4/LZ4Stream.cs:239-312): a run of chunks
+ *     varint(flags) varint(originalLength) [varint(compressedLength) if flags & 1] payload
+ * flags: 1 Compressed, 2 HighCompression.  A source of src_len bytes is cut into ceil(src_len / block_size) chunks (block_size is
+ * clamped to >= 16, like LZ4Stream); a chunk is stored raw when the encoder does not shrink it; an LZ4HC stream carries flag 2 on
+ * EVERY chunk, raw ones included, as the reference writes it.  Decoding skips empty chunks (original length 0) and stops at the
+ * first bad header.  Stream-level outcomes (lz4hip_stream_info_t.error): */
+#define LZ4HIP_STREAM_OK            0
+#define LZ4HIP_STREAM_END_OF_STREAM 1   /* truncated / corrupt header or payload  (EndOfStreamException) */
+#define LZ4HIP_STREAM_PASSES        2   /* compressed chunk with passes != 0      (NotSupportedException) */
+#define LZ4HIP_STREAM_CORRUPT_BLOCK 3   /* a chunk's LZ4 block failed to decode   (ArgumentException)     */
+#define LZ4HIP_STREAM_TABLE_FULL    4   /* more chunks than max_chunks; .chunks = the count needed        */
+typedef struct lz4hip_stream_info {
+    int64_t chunks, compressed_chunks;  /* non-empty chunks before the first header error (all of them, also when the table is full) */
+    int64_t decoded_bytes;              /* sum of their original lengths */
+    int64_t error_offset;               /* stream offset of the failing chunk's header (TABLE_FULL: of the first chunk that did not fit), -1 if none */
+    int32_t error, reserved;
+} lz4hip_stream_info_t;
+
+/* Bytes an encoded stream can take: len + n * (1 + 2 * varint_len(block_size)), n = ceil(len / block_size). */
+int64_t lz4hip_stream_bound(int64_t src_len, int32_t block_size);
+/* Device scratch (bytes) of the two device calls below; 0 for an empty source. */
+int64_t lz4hip_stream_encode_scratch_bytes(int64_t src_len, int32_t block_size);
+int64_t lz4hip_stream_decode_scratch_bytes(int64_t max_chunks);
+
+/* Device-resident streams: every pointer is device memory of the CURRENT device, the calls only enqueue kernels on `stream` (a
+ * hipStream_t, NULL = default stream), read no device value on the host and allocate nothing: scratch comes from the caller.  They
+ * return 0 or LZ4HIP_E_*.  The exceptions are those of lz4hip_encode_batch_device / lz4hip_decode_batch_device, which these calls
+ * run on the chunks: a stream encode whose chunk count reaches 49152 (fast) may build the lane encoder's table slab, an LZ4HC encode
+ * may allocate or grow its tables, and a decode of 16384 compressed chunks or more may run the lane decoder's probe and allocate its
+ * counters -- each once per device.
+ *
+ * Encode: writes the stream to dst (dst_cap >= lz4hip_stream_bound, else LZ4HIP_E_ARGUMENT) and its length to *dst_len (device).
+ * scratch_bytes must be >= lz4hip_stream_encode_scratch_bytes(src_len, block_size). */
+int lz4hip_stream_encode_device(const void* src, int64_t src_len, int32_t block_size, int mode,
+                                void* dst, int64_t dst_cap, int64_t* dst_len,
+                                void* scratch, int64_t scratch_bytes, void* stream);
+/* Decode is two calls; the caller reads *info back between them (one synchronisation) to learn the chunk counts and the output size.
+ * Index: walks the headers of src[0, src_len) into a table of max_chunks entries in scratch and writes *info (device).  When the
+ * stream has more non-empty chunks than max_chunks, info.error = LZ4HIP_STREAM_TABLE_FULL and info.chunks is the count needed.
+ * Decode: decodes what the index found, given the info it reported (host copy) and the same scratch and max_chunks: every chunk
+ * before the first header error is written to dst[0, decoded_bytes), and *info (device) is the index's, except that a corrupt
+ * block -- which always comes before the header error -- turns it into LZ4HIP_STREAM_CORRUPT_BLOCK at the FIRST such chunk's header.
+ * LZ4HIP_E_ARGUMENT for an info_host whose error is not OK / END_OF_STREAM / PASSES, or whose decoded_bytes exceed dst_cap. */
+int lz4hip_stream_index_device(const void* src, int64_t src_len, int64_t max_chunks, void* scratch, int64_t scratch_bytes,
+                               lz4hip_stream_info_t* info, void* stream);
+int lz4hip_stream_decode_device(const void* src, const lz4hip_stream_info_t* info_host, int64_t max_chunks,
+                                void* scratch, int64_t scratch_bytes, void* dst, int64_t dst_cap,
+                                lz4hip_stream_info_t* info, void* stream);
+
+/* Host-resident streams: stage the whole buffer through device memory (per-thread, grow-only, freed by lz4hip_release_workspaces),
+ * run the device calls above and synchronise.  Encode returns 0 or LZ4HIP_E_* (dst_cap >= lz4hip_stream_bound); *dst_len on the host.
+ * Decode returns info->error (0 or a positive LZ4HIP_STREAM_* code; the chunks before the error are in dst) or LZ4HIP_E_*; with
+ * dst_cap below the decoded size it returns LZ4HIP_E_ARGUMENT with info->decoded_bytes filled in (a size query: dst_cap = 0). */
+int lz4hip_stream_encode_host(const void* src, int64_t src_len, int32_t block_size, int mode, void* dst, int64_t dst_cap, int64_t* dst_len);
+int lz4hip_stream_decode_host(const void* src, int64_t src_len, void* dst, int64_t dst_cap, lz4hip_stream_info_t* info);
+
 /* ---- diagnostics ---------------------------------------------------------------------------------
  * Launch counters per kernel family since the library was loaded: which block->hardware mapping a call
  * actually used (the GPU tests assert these).  Copies min(n, LZ4HIP_K_COUNT) counters, returns LZ4HIP_K_COUNT. */

@@ -26,6 +26,15 @@ class Batch(C.Structure):
                 ("n_blocks", C.c_int64)]
 
 
+class StreamInfo(C.Structure):
+    """struct lz4hip_stream_info (include/lz4hip.h)."""
+    _fields_ = [("chunks", C.c_int64), ("compressed_chunks", C.c_int64), ("decoded_bytes", C.c_int64), ("error_offset", C.c_int64),
+                ("error", C.c_int32), ("reserved", C.c_int32)]
+
+
+STREAM_OK, STREAM_END_OF_STREAM, STREAM_PASSES, STREAM_CORRUPT_BLOCK, STREAM_TABLE_FULL = range(5)
+
+
 # every symbol include/lz4hip.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("lz4hip_codec_name", C.c_char_p, []),
@@ -53,6 +62,14 @@ SYMBOLS = [
     ("lz4hip_synth_device", C.c_int, [C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]),
     ("lz4hip_checksum_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
     ("lz4hip_compare_device", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]),
+    ("lz4hip_stream_bound", C.c_int64, [C.c_int64, C.c_int32]),
+    ("lz4hip_stream_encode_scratch_bytes", C.c_int64, [C.c_int64, C.c_int32]),
+    ("lz4hip_stream_decode_scratch_bytes", C.c_int64, [C.c_int64]),
+    ("lz4hip_stream_encode_device", C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    ("lz4hip_stream_index_device", C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    ("lz4hip_stream_decode_device", C.c_int, [C.c_void_p, C.POINTER(StreamInfo), C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    ("lz4hip_stream_encode_host", C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
+    ("lz4hip_stream_decode_host", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(StreamInfo)]),
 ]
 
 _lib = None

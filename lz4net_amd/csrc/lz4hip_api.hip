@@ -20,6 +20,7 @@
 #include "lz4hip_hc_nat.hpp"
 #include "lz4hip_hc_lcp.hpp"
 #include "lz4hip_synth.hpp"
+#include "lz4hip_stream.hpp"
 
 #include "../../include/lz4hip.h"
 
@@ -28,6 +29,7 @@
 #include <deque>
 #include <memory>
 #include <cstdlib>
+#include <cstddef>
 #include <cstring>
 #include <functional>
 #include <mutex>
@@ -1437,6 +1439,178 @@ int known_size_extent(const uint8_t* src, int osize)
     }
 }
 
+
+// ---- LZ4Stream buffers (lz4hip_stream.hpp) ----------------------------------------------------------------------------------
+// The framing kernels run around the batch paths above (launch_encode / launch_decode); scratch is the caller's, laid out here.
+static_assert(sizeof(StreamInfo) == sizeof(lz4hip_stream_info_t) && offsetof(StreamInfo, error) == offsetof(lz4hip_stream_info_t, error),
+              "StreamInfo must mirror lz4hip_stream_info_t");
+constexpr unsigned kStreamMaxGroups = 8192;                   // grid-stride kernels: at most 32 workgroups of 256 per CU
+
+int64_t stream_block(int32_t block_size) { return block_size < 16 ? 16 : block_size; }
+int64_t stream_chunks(int64_t len, int64_t block) { return len <= 0 ? 0 : (len - 1) / block + 1; }
+int64_t a256(int64_t v) { return (v + 255) / 256 * 256; }
+unsigned stream_grid(int64_t items)
+{
+    const int64_t g = (items + kStreamThreads - 1) / kStreamThreads;
+    return g < 1 ? 1u : (g > kStreamMaxGroups ? kStreamMaxGroups : (unsigned)g);
+}
+
+// the copy kernels: one workgroup per kCopySpan output bytes, at most kStreamMaxGroups (then each takes several spans)
+unsigned copy_grid(int64_t bytes)
+{
+    const int64_t g = (bytes + kCopySpan - 1) / kCopySpan;
+    return g < 1 ? 1u : (g > kStreamMaxGroups ? kStreamMaxGroups : (unsigned)g);
+}
+
+// encode scratch: the encoder's output (chunk k at k * block), chunk lengths, results, sizes / offsets, tile sums of the scan
+struct StreamEncodeScratch { int64_t comp, lens, result, offs, partial, total; };
+StreamEncodeScratch stream_encode_scratch(int64_t len, int64_t block)
+{
+    const int64_t n = stream_chunks(len, block), tiles = (n + kScanTile - 1) / kScanTile;
+    StreamEncodeScratch l;
+    int64_t at = 0;
+    l.comp = at;    at += a256(len);
+    l.lens = at;    at += a256(4 * n);
+    l.result = at;  at += a256(4 * n);
+    l.offs = at;    at += a256(8 * n);
+    l.partial = at; at += a256(8 * tiles);
+    l.total = n ? at : 0;
+    return l;
+}
+
+// decode scratch: the corrupt-block minimum, then the two tables of max_chunks entries
+int64_t stream_decode_scratch(int64_t max_chunks) { return 256 + 5 * a256(8 * max_chunks) + 4 * a256(4 * max_chunks); }
+StreamTables stream_tables(void* scratch, int64_t max_chunks)
+{
+    uint8_t* p = (uint8_t*)scratch;
+    StreamTables t;
+    t.max_chunks = max_chunks;
+    t.min_bad = (unsigned long long*)p; p += 256;
+    const int64_t w8 = a256(8 * max_chunks), w4 = a256(4 * max_chunks);
+    t.c_src_off = (int64_t*)p; p += w8;
+    t.c_dst_off = (int64_t*)p; p += w8;
+    t.c_hdr_off = (int64_t*)p; p += w8;
+    t.r_dst_off = (int64_t*)p; p += w8;
+    t.r_src_off = (int64_t*)p; p += w8;
+    t.c_src_len = (int32_t*)p; p += w4;
+    t.c_dst_cap = (int32_t*)p; p += w4;
+    t.c_result = (int32_t*)p; p += w4;
+    t.r_len = (int32_t*)p;
+    return t;
+}
+
+int64_t stream_bound(int64_t len, int32_t block_size)
+{
+    if (len <= 0) return 0;
+    const int64_t block = stream_block(block_size);
+    return len + stream_chunks(len, block) * (1 + 2 * varint_len((uint64_t)block));
+}
+
+int stream_encode(const void* src, int64_t src_len, int32_t block_size, int mode, void* dst, int64_t dst_cap, int64_t* dst_len,
+                  void* scratch, int64_t scratch_bytes, hipStream_t stream)
+{
+    if (src_len < 0 || !dst_len) return fail(LZ4HIP_E_ARGUMENT, "stream encode: src_len < 0 or dst_len is NULL");
+    if (mode != LZ4HIP_MODE_FAST && mode != LZ4HIP_MODE_HC) return fail(LZ4HIP_E_ARGUMENT, "mode must be LZ4HIP_MODE_FAST or LZ4HIP_MODE_HC");
+    const int64_t block = stream_block(block_size), n = stream_chunks(src_len, block);
+    if (n > 0x7FFFFFFF) return fail(LZ4HIP_E_ARGUMENT, "stream encode: more than 2^31 - 1 chunks");
+    if (dst_cap < stream_bound(src_len, block_size)) return fail(LZ4HIP_E_ARGUMENT, "stream encode: dst_cap < lz4hip_stream_bound");
+    const StreamEncodeScratch l = stream_encode_scratch(src_len, block);
+    if (scratch_bytes < l.total) return fail(LZ4HIP_E_ARGUMENT, "stream encode: scratch_bytes < lz4hip_stream_encode_scratch_bytes");
+    if (n == 0) { HIP_TRY(hipMemsetAsync(dst_len, 0, sizeof(int64_t), stream)); return 0; }
+    if (!src || !dst || !scratch) return fail(LZ4HIP_E_ARGUMENT, "stream encode: src, dst and scratch must be non-NULL");
+    uint8_t* const s = (uint8_t*)scratch;
+    int32_t* const lens = (int32_t*)(s + l.lens);
+    int32_t* const result = (int32_t*)(s + l.result);
+    int64_t* const offs = (int64_t*)(s + l.offs);
+    int64_t* const partial = (int64_t*)(s + l.partial);
+    hipLaunchKernelGGL(stream_lens_kernel, dim3(stream_grid(n)), dim3(kStreamThreads), 0, stream, lens, n, src_len, (int32_t)block);
+    HIP_TRY(hipGetLastError());
+    // FlushCurrentChunk: outputLength = inputLength per chunk; src_len_all = the block size, the upper bound LZ4HC picks its kernels from
+    lz4hip_batch_t b = {};
+    b.src = src; b.src_stride = block; b.src_len = lens;
+    b.dst = s + l.comp; b.dst_stride = block; b.dst_cap = lens;
+    b.src_len_all = (int32_t)block; b.result = result; b.n_blocks = n;
+    int rc = launch_encode(&b, mode, stream);
+    if (rc) return rc;
+    StreamEncodeArgs a;
+    a.src = (const uint8_t*)src; a.comp = s + l.comp; a.src_len = src_len; a.n = n; a.block = (int32_t)block;
+    a.hc_flag = mode == LZ4HIP_MODE_HC ? kChunkHighCompression : 0u; a.result = result; a.offs = offs;
+    hipLaunchKernelGGL(stream_sizes_kernel, dim3(stream_grid(n)), dim3(kStreamThreads), 0, stream, a);
+    const int64_t tiles = (n + kScanTile - 1) / kScanTile;
+    hipLaunchKernelGGL(stream_scan_reduce_kernel, dim3((unsigned)tiles), dim3(kStreamThreads), 0, stream, (const int64_t*)offs, n, partial);
+    hipLaunchKernelGGL(stream_scan_partials_kernel, dim3(1), dim3(kStreamThreads), 0, stream, partial, tiles, dst_len);
+    hipLaunchKernelGGL(stream_scan_apply_kernel, dim3((unsigned)tiles), dim3(kStreamThreads), 0, stream, offs, n, (const int64_t*)partial);
+    EncodeLayout layout = { a };
+    hipLaunchKernelGGL(stream_pack_kernel, dim3(copy_grid(stream_bound(src_len, block_size))), dim3(kStreamThreads), 0, stream,
+                       layout, (uint8_t*)dst, (const int64_t*)dst_len);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int stream_index(const void* src, int64_t src_len, int64_t max_chunks, void* scratch, int64_t scratch_bytes, lz4hip_stream_info_t* info,
+                 hipStream_t stream)
+{
+    if (src_len < 0 || max_chunks < 0 || !info || !scratch || (src_len > 0 && !src))
+        return fail(LZ4HIP_E_ARGUMENT, "stream index: negative size or NULL pointer");
+    if (scratch_bytes < stream_decode_scratch(max_chunks)) return fail(LZ4HIP_E_ARGUMENT, "stream index: scratch_bytes < lz4hip_stream_decode_scratch_bytes");
+    hipLaunchKernelGGL(stream_index_kernel, dim3(1), dim3(64), 0, stream, (const uint8_t*)src, src_len, stream_tables(scratch, max_chunks), (StreamInfo*)info);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int stream_decode(const void* src, const lz4hip_stream_info_t* info_host, int64_t max_chunks, void* scratch, int64_t scratch_bytes,
+                  void* dst, int64_t dst_cap, lz4hip_stream_info_t* info, hipStream_t stream)
+{
+    if (!info_host || !info || !scratch || max_chunks < 0) return fail(LZ4HIP_E_ARGUMENT, "stream decode: NULL pointer or max_chunks < 0");
+    const lz4hip_stream_info_t h = *info_host;
+    if (h.error != LZ4HIP_STREAM_OK && h.error != LZ4HIP_STREAM_END_OF_STREAM && h.error != LZ4HIP_STREAM_PASSES)
+        return fail(LZ4HIP_E_ARGUMENT, "stream decode: the index reported a table too small (or the info is not an index's)");
+    if (h.chunks < 0 || h.chunks > max_chunks || h.compressed_chunks < 0 || h.compressed_chunks > h.chunks || h.decoded_bytes < 0)
+        return fail(LZ4HIP_E_ARGUMENT, "stream decode: the info does not fit a table of max_chunks entries");
+    if (h.decoded_bytes > dst_cap) return fail(LZ4HIP_E_ARGUMENT, "stream decode: decoded_bytes > dst_cap");
+    if (h.chunks > 0 && (!src || !dst)) return fail(LZ4HIP_E_ARGUMENT, "stream decode: src and dst must be non-NULL");
+    if (scratch_bytes < stream_decode_scratch(max_chunks)) return fail(LZ4HIP_E_ARGUMENT, "stream decode: scratch_bytes < lz4hip_stream_decode_scratch_bytes");
+    if (h.compressed_chunks > 0x7FFFFFFF) return fail(LZ4HIP_E_ARGUMENT, "stream decode: more than 2^31 - 1 compressed chunks");
+    const StreamTables t = stream_tables(scratch, max_chunks);
+    StreamInfo from_index;
+    memcpy(&from_index, &h, sizeof from_index);
+    hipLaunchKernelGGL(stream_info_init_kernel, dim3(1), dim3(64), 0, stream, from_index, (StreamInfo*)info, t.min_bad);
+    HIP_TRY(hipGetLastError());
+    if (h.compressed_chunks > 0) {
+        // AcquireNextChunk: Decode(..., knownOutputLength: true) -- the compressed table IS the batch
+        lz4hip_batch_t b = {};
+        b.src = src; b.src_off = t.c_src_off; b.src_len = t.c_src_len;
+        b.dst = dst; b.dst_off = t.c_dst_off; b.dst_cap = t.c_dst_cap;
+        b.result = t.c_result; b.n_blocks = h.compressed_chunks;
+        int rc = launch_decode(&b, 1, stream);
+        if (rc) return rc;
+        hipLaunchKernelGGL(stream_check_kernel, dim3(stream_grid(h.compressed_chunks)), dim3(kStreamThreads), 0, stream, t, h.compressed_chunks);
+        HIP_TRY(hipGetLastError());
+    }
+    if (h.chunks > h.compressed_chunks) {
+        RawLayout layout = { (const uint8_t*)src, t, h.chunks - h.compressed_chunks };
+        hipLaunchKernelGGL(stream_raw_copy_kernel, dim3(copy_grid(h.decoded_bytes)), dim3(kStreamThreads), 0, stream,
+                           layout, (uint8_t*)dst, h.decoded_bytes);
+        HIP_TRY(hipGetLastError());
+    }
+    hipLaunchKernelGGL(stream_info_finish_kernel, dim3(1), dim3(64), 0, stream, (StreamInfo*)info, (const unsigned long long*)t.min_bad);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// The host pair stages the whole buffer in the calling thread's device scratch (HostContext: grow-only, freed by
+// lz4hip_release_workspaces) and runs the device path on the thread's first kernel stream.
+int stream_host_context(HostContext*& hc, hipStream_t& s)
+{
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    if (!(hc = host_context(dev))) return fail(LZ4HIP_E_DEVICE, "device index out of range");
+    int rc = hc->pipe.init();
+    if (rc) return rc;
+    s = hc->pipe.s_k[0];
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1729,6 +1903,105 @@ int lz4hip_compare_device(const void* a, int64_t a_stride, const void* b, int64_
     hipLaunchKernelGGL(compare_kernel, dim3((unsigned)((n_blocks + 3) / 4)), dim3(256), 0, (hipStream_t)stream, c);
     HIP_TRY(hipGetLastError());
     return 0;
+}
+
+int64_t lz4hip_stream_bound(int64_t src_len, int32_t block_size) { return stream_bound(src_len, block_size); }
+
+int64_t lz4hip_stream_encode_scratch_bytes(int64_t src_len, int32_t block_size)
+{
+    return src_len <= 0 ? 0 : stream_encode_scratch(src_len, stream_block(block_size)).total;
+}
+
+int64_t lz4hip_stream_decode_scratch_bytes(int64_t max_chunks) { return stream_decode_scratch(max_chunks < 0 ? 0 : max_chunks); }
+
+int lz4hip_stream_encode_device(const void* src, int64_t src_len, int32_t block_size, int mode, void* dst, int64_t dst_cap, int64_t* dst_len,
+                                void* scratch, int64_t scratch_bytes, void* stream)
+{
+    int rc = ensure_device();
+    if (rc) return rc;
+    return stream_encode(src, src_len, block_size, mode, dst, dst_cap, dst_len, scratch, scratch_bytes, (hipStream_t)stream);
+}
+
+int lz4hip_stream_index_device(const void* src, int64_t src_len, int64_t max_chunks, void* scratch, int64_t scratch_bytes,
+                               lz4hip_stream_info_t* info, void* stream)
+{
+    int rc = ensure_device();
+    if (rc) return rc;
+    return stream_index(src, src_len, max_chunks, scratch, scratch_bytes, info, (hipStream_t)stream);
+}
+
+int lz4hip_stream_decode_device(const void* src, const lz4hip_stream_info_t* info_host, int64_t max_chunks, void* scratch, int64_t scratch_bytes,
+                                void* dst, int64_t dst_cap, lz4hip_stream_info_t* info, void* stream)
+{
+    int rc = ensure_device();
+    if (rc) return rc;
+    return stream_decode(src, info_host, max_chunks, scratch, scratch_bytes, dst, dst_cap, info, (hipStream_t)stream);
+}
+
+int lz4hip_stream_encode_host(const void* src, int64_t src_len, int32_t block_size, int mode, void* dst, int64_t dst_cap, int64_t* dst_len)
+{
+    int rc = ensure_device();
+    if (rc) return rc;
+    if (src_len < 0 || !dst_len || (src_len > 0 && (!src || !dst))) return fail(LZ4HIP_E_ARGUMENT, "stream encode: negative size or NULL pointer");
+    const int64_t bound = stream_bound(src_len, block_size);
+    if (dst_cap < bound) return fail(LZ4HIP_E_ARGUMENT, "stream encode: dst_cap < lz4hip_stream_bound");
+    if (src_len == 0) { *dst_len = 0; return 0; }
+    HostContext* hc = nullptr;
+    hipStream_t s = nullptr;
+    if ((rc = stream_host_context(hc, s))) return rc;
+    // device image: [source | stream | scratch | length]
+    const int64_t scratch_bytes = lz4hip_stream_encode_scratch_bytes(src_len, block_size);
+    const int64_t out_at = a256(src_len), scratch_at = out_at + a256(bound), len_at = scratch_at + a256(scratch_bytes);
+    if ((rc = hc->scratch.reserve((size_t)(len_at + 256)))) return rc;
+    uint8_t* const d = (uint8_t*)hc->scratch.p;
+    HIP_TRY(hipMemcpyAsync(d, src, (size_t)src_len, hipMemcpyHostToDevice, s));
+    if ((rc = stream_encode(d, src_len, block_size, mode, d + out_at, bound, (int64_t*)(d + len_at), d + scratch_at, scratch_bytes, s))) return rc;
+    int64_t n = 0;
+    HIP_TRY(hipMemcpyAsync(&n, d + len_at, sizeof n, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    HIP_TRY(hipMemcpyAsync(dst, d + out_at, (size_t)n, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    *dst_len = n;
+    return 0;
+}
+
+int lz4hip_stream_decode_host(const void* src, int64_t src_len, void* dst, int64_t dst_cap, lz4hip_stream_info_t* info)
+{
+    int rc = ensure_device();
+    if (rc) return rc;
+    if (src_len < 0 || dst_cap < 0 || !info || (src_len > 0 && !src)) return fail(LZ4HIP_E_ARGUMENT, "stream decode: negative size or NULL pointer");
+    HostContext* hc = nullptr;
+    hipStream_t s = nullptr;
+    if ((rc = stream_host_context(hc, s))) return rc;
+    // device image: [source | info | output | table]; walked again after a table that was too small or an image that had to grow
+    int64_t max_chunks = (src_len + 4095) / 4096 + 16, out_bytes = dst_cap < 4 * src_len ? dst_cap : 4 * src_len;
+    lz4hip_stream_info_t h = {};
+    uint8_t* d = nullptr;
+    int64_t info_at = 0, out_at = 0, table_at = 0;
+    for (int attempt = 0;; attempt++) {
+        info_at = a256(src_len); out_at = info_at + 256; table_at = out_at + a256(out_bytes);
+        const int64_t table_bytes = stream_decode_scratch(max_chunks);
+        if ((rc = hc->scratch.reserve((size_t)(table_at + table_bytes)))) return rc;
+        d = (uint8_t*)hc->scratch.p;
+        if (src_len > 0) HIP_TRY(hipMemcpyAsync(d, src, (size_t)src_len, hipMemcpyHostToDevice, s));
+        if ((rc = stream_index(d, src_len, max_chunks, d + table_at, table_bytes, (lz4hip_stream_info_t*)(d + info_at), s))) return rc;
+        HIP_TRY(hipMemcpyAsync(&h, d + info_at, sizeof h, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        if (attempt >= 2) break;
+        if (h.error == LZ4HIP_STREAM_TABLE_FULL) { max_chunks = h.chunks; continue; }
+        if (h.decoded_bytes > dst_cap) break;
+        if (h.decoded_bytes > out_bytes) { out_bytes = h.decoded_bytes; continue; }
+        break;
+    }
+    *info = h;
+    if (h.error == LZ4HIP_STREAM_TABLE_FULL) return fail(LZ4HIP_E_DEVICE, "stream decode: the header walk did not settle");
+    if (h.decoded_bytes > dst_cap) return fail(LZ4HIP_E_ARGUMENT, "stream decode: dst_cap < decoded_bytes (reported in info->decoded_bytes)");
+    if ((rc = stream_decode(d, &h, max_chunks, d + table_at, stream_decode_scratch(max_chunks), d + out_at, out_bytes,
+                            (lz4hip_stream_info_t*)(d + info_at), s))) return rc;
+    HIP_TRY(hipMemcpyAsync(info, d + info_at, sizeof *info, hipMemcpyDeviceToHost, s));
+    if (h.decoded_bytes > 0) HIP_TRY(hipMemcpyAsync(dst, d + out_at, (size_t)h.decoded_bytes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return info->error;
 }
 
 }  // extern "C"

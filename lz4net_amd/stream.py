@@ -147,3 +147,87 @@ def decompress_stream(stream) -> bytes:
         if not (res == src_len).all():                       # Decode64: consumed != inputLength (Unsafe.cs:373-378)
             raise ArgumentException("LZ4 block is corrupted, or invalid length has been given.")
     return out.tobytes()
+
+
+# ---- device-resident streams (lz4hip_stream_* of include/lz4hip.h; kernels in csrc/lz4hip_stream.hpp) ------------------------------
+
+def _check_device_bytes(t, name):
+    import torch
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.uint8 or t.dim() != 1:
+        raise ArgumentException(f"{name} must be a 1-D uint8 CUDA tensor")
+    return t.contiguous()
+
+
+def compress_stream_device(t, block_size: int = DEFAULT_BLOCK_SIZE, high_compression: bool = False):
+    """compress_stream for a 1-D uint8 CUDA tensor, entirely on the device, on torch's current stream: the same bytes, returned as a
+    1-D uint8 CUDA tensor.  Waits for the device once, to learn the stream's length."""
+    import torch
+    t = _check_device_bytes(t, "t")
+    with torch.cuda.device(t.device):
+        return _compress_stream_device(t, max(16, int(block_size)), high_compression)
+
+
+def _compress_stream_device(t, block_size, high_compression):
+    import torch
+    L = _lib.lib()
+    n = t.numel()
+    if n == 0:
+        return torch.empty(0, dtype=torch.uint8, device=t.device)
+    out = torch.empty(L.lz4hip_stream_bound(n, block_size), dtype=torch.uint8, device=t.device)
+    scratch = torch.empty(L.lz4hip_stream_encode_scratch_bytes(n, block_size), dtype=torch.uint8, device=t.device)
+    out_len = torch.empty(1, dtype=torch.int64, device=t.device)
+    _lib.check(L.lz4hip_stream_encode_device(t.data_ptr(), n, block_size, _lib.MODE_HC if high_compression else _lib.MODE_FAST,
+                                             out.data_ptr(), out.numel(), out_len.data_ptr(), scratch.data_ptr(), scratch.numel(),
+                                             torch.cuda.current_stream(t.device).cuda_stream))
+    return out[:int(out_len.item())]
+
+
+def _stream_error(info):
+    """The exception parse_chunks / decompress_stream raise for an LZ4HIP_STREAM_* outcome, with the failing header's offset."""
+    if info.error == _lib.STREAM_END_OF_STREAM:
+        e = EndOfStreamException("truncated or corrupted stream")
+    elif info.error == _lib.STREAM_PASSES:
+        e = NotImplementedError("Chunks with multiple passes are not supported.")
+    elif info.error == _lib.STREAM_CORRUPT_BLOCK:
+        e = ArgumentException("LZ4 block is corrupted, or invalid length has been given.")
+    else:
+        e = _lib.Lz4HipError(f"stream decode: unexpected outcome {info.error}")
+    e.error_offset = int(info.error_offset)
+    return e
+
+
+def decompress_stream_device(t):
+    """decompress_stream for a 1-D uint8 CUDA tensor, on torch's current stream: the header walk, the block decode and the raw copies
+    run on the device; the host reads the walk's result once (to size the output) and the final outcome once."""
+    import torch
+    t = _check_device_bytes(t, "t")
+    with torch.cuda.device(t.device):
+        return _decompress_stream_device(t)
+
+
+def _decompress_stream_device(t):
+    import torch
+    L = _lib.lib()
+    dev = t.device
+    s = torch.cuda.current_stream(dev).cuda_stream
+    n = t.numel()
+    info_dev = torch.zeros(C.sizeof(_lib.StreamInfo), dtype=torch.uint8, device=dev)
+
+    def read_info():
+        return _lib.StreamInfo.from_buffer_copy(info_dev.cpu().numpy().tobytes())
+
+    max_chunks = (n + 4095) // 4096 + 16
+    for _ in range(2):
+        scratch = torch.empty(L.lz4hip_stream_decode_scratch_bytes(max_chunks), dtype=torch.uint8, device=dev)
+        _lib.check(L.lz4hip_stream_index_device(t.data_ptr(), n, max_chunks, scratch.data_ptr(), scratch.numel(), info_dev.data_ptr(), s))
+        info = read_info()
+        if info.error != _lib.STREAM_TABLE_FULL:
+            break
+        max_chunks = int(info.chunks)
+    out = torch.empty(int(info.decoded_bytes), dtype=torch.uint8, device=dev)
+    _lib.check(L.lz4hip_stream_decode_device(t.data_ptr(), C.byref(info), max_chunks, scratch.data_ptr(), scratch.numel(),
+                                             out.data_ptr(), out.numel(), info_dev.data_ptr(), s))
+    info = read_info()
+    if info.error != _lib.STREAM_OK:
+        raise _stream_error(info)
+    return out
