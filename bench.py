@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- headline benchmark: batched 64 KiB-block LZ4 decode on MI355X (BASELINE.json configs[1]).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--blocks B] [--dist D] [--no-extras] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--blocks B] [--dist D] [--dump-outputs DIR] [--full [--no-extras] [--no-cpu]]
 
 One "step" = one pass of the batched known-size decoder over the whole resident batch (2^20 blocks of
 64 KiB per GPU by default; every buffer is in HBM before the timed region starts).  For N > 1 the driver
@@ -13,6 +13,13 @@ Prints ONE JSON line (rank 0).  `value` = uncompressed GB/s of the decode step o
 launch stream vs the 8 TB/s HBM3E peak; `cpu_baseline` = the reference's own C (oracle/_ref, built
 from original/lz4.c) or, if absent, the CPU restatement, decoding a bounded sample of the same
 workload on this box's host cores.  `extras` carries the other distributions and the encoder rates.
+
+A plain run does what `value` and `ms_per_step` need and no more: it builds the batch (synthesis and the fast encode, whose
+time is `roofline_encode`), warms up, times the steps, checks the decoded batch (`verified`), writes --dump-outputs and
+prints the line; `cpu_baseline` and `roofline_hc` are null and `extras` holds the headline distribution alone.  --full
+adds everything else after the timed region: the CPU baseline, the every-block encoder checks against the CPU reference,
+both decoder mappings, the other distributions, LZ4HC, the batch-size sweep, the forced wavefront encoder, the measured
+HBM fill / copy and the host-pointer entry points (--no-extras / --no-cpu drop parts of it).
 """
 from __future__ import annotations
 
@@ -66,9 +73,12 @@ def parse_args():
     ap.add_argument("--blocks", type=int, default=1 << 20, help="64 KiB blocks PER GPU")
     ap.add_argument("--dist", type=int, default=2, help="headline distribution (0..3)")
     ap.add_argument("--seed", type=int, default=20260925)
-    ap.add_argument("--no-extras", action="store_true", help="skip the other distributions / encoder timings")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
-    ap.add_argument("--hc-only", action="store_true", help="of the extras run only the LZ4HC leg (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the CPU baseline, the encoder checks against the CPU reference and the extras "
+                         "(default: only what the headline needs)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the other distributions / encoder timings")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the cpu_baseline leg and the checks against the CPU reference")
+    ap.add_argument("--hc-only", action="store_true", help="with --full: of the extras run only the LZ4HC leg (profiling runs)")
     ap.add_argument("--hc-blocks", type=int, default=1 << 18, help="blocks for the LZ4HC extra (SURVEY 8d C4: 2^18; 0 = skip)")
     ap.add_argument("--decoder", choices=["auto", "lane", "wave"], default="auto",
                     help="block->hardware mapping of the decoder (auto = library default)")
@@ -85,6 +95,10 @@ def parse_args():
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if args.hc_only and not args.full:
+        ap.error("--hc-only selects among the legs of --full: give --full as well")
+    if not args.full:
+        args.no_extras = args.no_cpu = True      # a plain run: the headline alone
     return args
 
 
@@ -412,11 +426,10 @@ def main():
     # it in seconds, 2 048 otherwise; the raw blocks are the GPU batch's own first blocks (copied out here, wl is freed below)
     sample_blocks = min(16384 if (os.cpu_count() or 1) >= 32 else 2048, n)
     raw_sample = None
-    if rank == 0:
+    if rank == 0 and world == 1 and not args.no_cpu:
         k = min(64, n)
         gpu_sample = (wl.comp[:k].cpu().numpy(), wl.clen[:k].cpu().numpy())
-        if world == 1 and not args.no_cpu:
-            raw_sample = wl.raw[:sample_blocks].cpu().numpy()
+        raw_sample = wl.raw[:sample_blocks].cpu().numpy()
     head = {
         "decode_GBps": round(wl.raw_bytes / (sum(kernel_ms) / len(kernel_ms) / 1e3) / 1e9, 2),
         "encode_fast_GBps": round(wl.raw_bytes / (wl.encode_ms / 1e3) / 1e9, 2),
@@ -745,6 +758,7 @@ def main():
         "roofline_hc": side_roofline(hc_roof, "encode_hc", "lz4hip::hc_nat_chain_kernel + hc_lcp_fill_kernel + encode_hc_lcp_kernel (LZ4_compressHCCtx: chains and shared lengths of every position built up front, then one lane per block, convergent state machine without the insert loop)", hc_check),
         "cpu_baseline": cpu,
         "verified": all_ok,
+        "full": args.full,
         "csrc_sha": csrc_sha(), "library_build_id": lib_id,
         "extras": extras,
     }

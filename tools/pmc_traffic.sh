@@ -5,13 +5,14 @@
 # the hash matches); copy it to profiles/r04/ to commit it.  PMC_REPARSE=1: only re-evaluate the CSVs already there.
 # Usage: bash tools/pmc_traffic.sh [dist] [blocks] [hc_blocks]
 dist=${1:-2}; blocks=${2:-1048576}; hcb=${3:-262144}
+root=$(cd "$(dirname "$0")/.." && pwd)
 out=$GRAFT_REPO_ROOT/gpurun_out/pmc_traffic
 if [ -z "$PMC_REPARSE" ]; then
 rm -rf $out; mkdir -p $out; cd /tmp; export TMPDIR=/tmp
 i=0
 for pmc in "FETCH_SIZE" "WRITE_SIZE"; do
   i=$((i+1))
-  timeout 360 rocprofv3 --pmc $pmc -d $out/p$i -o pmc --output-format csv -- python $GRAFT_REPO_ROOT/bench.py --steps 2 --warmup 0 --no-cpu --hc-only --blocks $blocks --hc-blocks $hcb --dist $dist > $out/bench_$i.json 2>> $out/err.txt
+  timeout 360 rocprofv3 --pmc $pmc -d $out/p$i -o pmc --output-format csv -- python $root/bench.py --steps 2 --warmup 0 --full --no-cpu --hc-only --blocks $blocks --hc-blocks $hcb --dist $dist > $out/bench_$i.json 2>> $out/err.txt
 done
 fi
 cd ${GRAFT_REPO_ROOT:-.}

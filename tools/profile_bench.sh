@@ -15,7 +15,7 @@ out = sys.argv[1]
 rows = list(csv.DictReader(open(out + "/kernel_stats.csv")))
 with open(out + "/kernel_stats_summary.txt", "w") as f:
     f.write("rocprofv3 --kernel-trace --stats -- python bench.py --steps 5 --warmup 1 --no-extras --no-cpu\n")
-    f.write("(headline workload only, so that the per-kernel average IS the timed decode launch; the default bench.py adds the other distributions, the encoders and the CPU baseline after the timed region)\n")
+    f.write("(headline workload only, so that the per-kernel average IS the timed decode launch; bench.py --full adds the other distributions, LZ4HC and the CPU baseline after the timed region)\n")
     f.write("%-70s %8s %14s %14s %8s\n" % ("kernel", "calls", "total_ns", "avg_ns", "pct"))
     for r in rows:
         f.write("%-70s %8s %14s %14.0f %8s\n" % (r["Name"][:70], r["Calls"], r["TotalDurationNs"], float(r["AverageNs"]), r["Percentage"]))
