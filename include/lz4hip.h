@@ -171,6 +171,81 @@ int lz4hip_stream_decode_device(const void* src, const lz4hip_stream_info_t* inf
 int lz4hip_stream_encode_host(const void* src, int64_t src_len, int32_t block_size, int mode, void* dst, int64_t dst_cap, int64_t* dst_len);
 int lz4hip_stream_decode_host(const void* src, int64_t src_len, void* dst, int64_t dst_cap, lz4hip_stream_info_t* info);
 
+/* ---- wrapped messages ----------------------------------------------------------------------------
+ * The self-describing format of lz4net's LZ4Codec.Wrap / WrapHC / Unwrap (src/LZ4/LZ4Codec.cs:471-599), for many independent
+ * messages at once:  int32 originalLength, int32 payloadLength (both little-endian), payload.
+ * A batch of n messages is one buffer src of src_len bytes plus int64 offsets src_off[n + 1]: message i is
+ * src[src_off[i], src_off[i + 1]).  Wrap writes exactly this layout and Unwrap reads it: one call's output is the other's input.
+ *
+ * Wrap (as the reference): an empty message becomes 8 zero bytes; the encoder runs with outputLength = inputLength (fast or HC)
+ * and its output is used when 0 < r < inputLength; otherwise the message is stored raw with both fields = inputLength.
+ * result[i]: the payload size of a compressed message, 0 for one stored raw, LZ4HIP_E_ARGUMENT for offsets that decrease, fall
+ * outside [0, src_len] or give a length above INT32_MAX -- such a message takes 0 bytes of dst.  When offsets decrease, messages
+ * may overlap: their output is then unspecified, dst_off[n] may exceed dst_cap, and nothing past dst_cap is written.
+ *
+ * Unwrap (as the reference, with signed fields), per message, in this order:
+ *   fewer than 8 bytes                             LZ4HIP_WRAP_SIZE_INVALID   ("inputBuffer size is invalid")
+ *   payloadLength < 0 or > available - 8          LZ4HIP_WRAP_CORRUPT_HEADER ("inputBuffer size is invalid or has been corrupted";
+ *                                                  for a negative payloadLength the reference throws no ArgumentException but
+ *                                                  fails later, in the decoder's argument checks or the allocation)
+ *   payloadLength >= originalLength                the payload as it is (payloadLength bytes; also for a negative originalLength)
+ *   otherwise                                      a known-size decode of originalLength bytes; consumed != payloadLength is
+ *                                                  LZ4HIP_WRAP_CORRUPT_BLOCK ("LZ4 block is corrupted, or invalid length has been
+ *                                                  given.", Decode64, src/LZ4pn/LZ4Codec.Unsafe.cs:373-378)
+ * Bad offsets (as for Wrap) give the status LZ4HIP_E_ARGUMENT.  Every message with a valid header is decoded, not only those before
+ * the first failure.  A failed message's output range is unspecified (0 bytes for a header failure, originalLength for a corrupt
+ * block); no byte outside it is written.  info.first_error is the lowest failing index, header errors and corrupt blocks alike --
+ * what a sequential [Unwrap(w) for w in ...] raises first -- and info.error that message's status. */
+#define LZ4HIP_WRAP_OK             0
+#define LZ4HIP_WRAP_SIZE_INVALID   1   /* < 8 bytes                          */
+#define LZ4HIP_WRAP_CORRUPT_HEADER 2   /* payloadLength < 0 or past the end  */
+#define LZ4HIP_WRAP_CORRUPT_BLOCK  3   /* block did not decode exactly       */
+typedef struct lz4hip_unwrap_info {
+    int64_t messages, compressed;       /* n, and the messages that go through the block decoder */
+    int64_t decoded_bytes;              /* dst_off[n] */
+    int64_t first_error;                /* lowest failing message index, -1 if none */
+    int32_t error, reserved;            /* that message's status */
+} lz4hip_unwrap_info_t;
+
+/* src_len + 8 n: the exact worst case of a wrapped batch (every message stored raw). */
+int64_t lz4hip_wrap_bound(int64_t n, int64_t src_len);
+/* Device scratch (bytes) of the device calls below; the index and the decode of one batch share theirs. */
+int64_t lz4hip_wrap_scratch_bytes(int64_t n, int64_t src_len);
+int64_t lz4hip_unwrap_scratch_bytes(int64_t n);
+
+/* Device-resident batches: the contract of the lz4hip_stream_*_device calls -- device pointers of the CURRENT device, launch-only
+ * on `stream`, no device value read on the host, scratch from the caller, 0 or LZ4HIP_E_* returned -- with the first-use exceptions
+ * of lz4hip_encode_batch_device / lz4hip_decode_batch_device, which these calls run on the messages.
+ *
+ * Wrap: dst_cap >= lz4hip_wrap_bound(n, src_len), scratch_bytes >= lz4hip_wrap_scratch_bytes(n, src_len); writes dst_off[n + 1]
+ * (dst_off[n] = the total) and, if result is not NULL, result[n]. */
+int lz4hip_wrap_device(const void* src, int64_t src_len, const int64_t* src_off, int64_t n, int mode,
+                       void* dst, int64_t dst_cap, int64_t* dst_off, int32_t* result,
+                       void* scratch, int64_t scratch_bytes, void* stream);
+/* Unwrap is two calls; the caller reads *info back between them (one synchronisation) to size dst.
+ * Index: reads every header, writes dst_off[n + 1] (dst_off[n] = decoded_bytes), the header statuses status[n] and *info (device).
+ * Decode: given the index's info (host copy) and the same src, offsets, scratch, dst_off and status, decodes every message with a valid
+ * header into dst[dst_off[i], dst_off[i + 1]), adds LZ4HIP_WRAP_CORRUPT_BLOCK statuses and writes the final *info (device).
+ * LZ4HIP_E_ARGUMENT for an info_host whose decoded_bytes exceed dst_cap or that does not describe n messages. */
+int lz4hip_unwrap_index_device(const void* src, int64_t src_len, const int64_t* src_off, int64_t n,
+                               int64_t* dst_off, int32_t* status,
+                               void* scratch, int64_t scratch_bytes, lz4hip_unwrap_info_t* info, void* stream);
+int lz4hip_unwrap_decode_device(const void* src, int64_t src_len, const int64_t* src_off, int64_t n,
+                                const lz4hip_unwrap_info_t* info_host, void* scratch, int64_t scratch_bytes,
+                                void* dst, int64_t dst_cap, const int64_t* dst_off, int32_t* status,
+                                lz4hip_unwrap_info_t* info, void* stream);
+
+/* Host-resident batches (what a C# byte[][] caller binds): stage everything through device memory (per-thread, grow-only, freed by
+ * lz4hip_release_workspaces), run the device calls above and synchronise; every pointer is host memory.
+ * Wrap returns 0 or LZ4HIP_E_* (dst_cap >= lz4hip_wrap_bound).  Unwrap returns 0 when every message unwrapped, else info->error (a
+ * positive LZ4HIP_WRAP_* code, or LZ4HIP_E_ARGUMENT for bad offsets; dst, dst_off and status are filled in all the same) or
+ * LZ4HIP_E_*; with dst_cap below the decoded size it returns LZ4HIP_E_ARGUMENT with info->decoded_bytes, dst_off and status filled in
+ * (a size query: dst_cap = 0). */
+int lz4hip_wrap_host(const void* src, int64_t src_len, const int64_t* src_off, int64_t n, int mode,
+                     void* dst, int64_t dst_cap, int64_t* dst_off, int32_t* result);
+int lz4hip_unwrap_host(const void* src, int64_t src_len, const int64_t* src_off, int64_t n,
+                       void* dst, int64_t dst_cap, int64_t* dst_off, int32_t* status, lz4hip_unwrap_info_t* info);
+
 /* ---- diagnostics ---------------------------------------------------------------------------------
  * Launch counters per kernel family since the library was loaded: which block->hardware mapping a call
  * actually used (the GPU tests assert these).  Copies min(n, LZ4HIP_K_COUNT) counters, returns LZ4HIP_K_COUNT. */

@@ -35,6 +35,15 @@ class StreamInfo(C.Structure):
 STREAM_OK, STREAM_END_OF_STREAM, STREAM_PASSES, STREAM_CORRUPT_BLOCK, STREAM_TABLE_FULL = range(5)
 
 
+class UnwrapInfo(C.Structure):
+    """struct lz4hip_unwrap_info (include/lz4hip.h)."""
+    _fields_ = [("messages", C.c_int64), ("compressed", C.c_int64), ("decoded_bytes", C.c_int64), ("first_error", C.c_int64),
+                ("error", C.c_int32), ("reserved", C.c_int32)]
+
+
+WRAP_OK, WRAP_SIZE_INVALID, WRAP_CORRUPT_HEADER, WRAP_CORRUPT_BLOCK = range(4)
+
+
 # every symbol include/lz4hip.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("lz4hip_codec_name", C.c_char_p, []),
@@ -70,6 +79,18 @@ SYMBOLS = [
     ("lz4hip_stream_decode_device", C.c_int, [C.c_void_p, C.POINTER(StreamInfo), C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     ("lz4hip_stream_encode_host", C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
     ("lz4hip_stream_decode_host", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(StreamInfo)]),
+    ("lz4hip_wrap_bound", C.c_int64, [C.c_int64, C.c_int64]),
+    ("lz4hip_wrap_scratch_bytes", C.c_int64, [C.c_int64, C.c_int64]),
+    ("lz4hip_unwrap_scratch_bytes", C.c_int64, [C.c_int64]),
+    ("lz4hip_wrap_device", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_int64, C.c_void_p]),
+    ("lz4hip_unwrap_index_device", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                             C.c_void_p, C.c_void_p]),
+    ("lz4hip_unwrap_decode_device", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(UnwrapInfo), C.c_void_p, C.c_int64,
+                                              C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("lz4hip_wrap_host", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    ("lz4hip_unwrap_host", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                     C.POINTER(UnwrapInfo)]),
 ]
 
 _lib = None

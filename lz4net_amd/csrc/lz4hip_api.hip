@@ -21,6 +21,7 @@
 #include "lz4hip_hc_lcp.hpp"
 #include "lz4hip_synth.hpp"
 #include "lz4hip_stream.hpp"
+#include "lz4hip_wrap.hpp"
 
 #include "../../include/lz4hip.h"
 
@@ -1506,6 +1507,15 @@ int64_t stream_bound(int64_t len, int32_t block_size)
     return len + stream_chunks(len, block) * (1 + 2 * varint_len((uint64_t)block));
 }
 
+// exclusive scan of x[0, n) in place, n > 0; the sum goes to *total (device); partial holds ceil(n / kScanTile) tile sums
+void launch_scan(int64_t* x, int64_t n, int64_t* partial, int64_t* total, hipStream_t stream)
+{
+    const int64_t tiles = (n + kScanTile - 1) / kScanTile;
+    hipLaunchKernelGGL(stream_scan_reduce_kernel, dim3((unsigned)tiles), dim3(kStreamThreads), 0, stream, (const int64_t*)x, n, partial);
+    hipLaunchKernelGGL(stream_scan_partials_kernel, dim3(1), dim3(kStreamThreads), 0, stream, partial, tiles, total);
+    hipLaunchKernelGGL(stream_scan_apply_kernel, dim3((unsigned)tiles), dim3(kStreamThreads), 0, stream, x, n, (const int64_t*)partial);
+}
+
 int stream_encode(const void* src, int64_t src_len, int32_t block_size, int mode, void* dst, int64_t dst_cap, int64_t* dst_len,
                   void* scratch, int64_t scratch_bytes, hipStream_t stream)
 {
@@ -1536,10 +1546,7 @@ int stream_encode(const void* src, int64_t src_len, int32_t block_size, int mode
     a.src = (const uint8_t*)src; a.comp = s + l.comp; a.src_len = src_len; a.n = n; a.block = (int32_t)block;
     a.hc_flag = mode == LZ4HIP_MODE_HC ? kChunkHighCompression : 0u; a.result = result; a.offs = offs;
     hipLaunchKernelGGL(stream_sizes_kernel, dim3(stream_grid(n)), dim3(kStreamThreads), 0, stream, a);
-    const int64_t tiles = (n + kScanTile - 1) / kScanTile;
-    hipLaunchKernelGGL(stream_scan_reduce_kernel, dim3((unsigned)tiles), dim3(kStreamThreads), 0, stream, (const int64_t*)offs, n, partial);
-    hipLaunchKernelGGL(stream_scan_partials_kernel, dim3(1), dim3(kStreamThreads), 0, stream, partial, tiles, dst_len);
-    hipLaunchKernelGGL(stream_scan_apply_kernel, dim3((unsigned)tiles), dim3(kStreamThreads), 0, stream, offs, n, (const int64_t*)partial);
+    launch_scan(offs, n, partial, dst_len, stream);
     EncodeLayout layout = { a };
     hipLaunchKernelGGL(stream_pack_kernel, dim3(copy_grid(stream_bound(src_len, block_size))), dim3(kStreamThreads), 0, stream,
                        layout, (uint8_t*)dst, (const int64_t*)dst_len);
@@ -1608,6 +1615,147 @@ int stream_host_context(HostContext*& hc, hipStream_t& s)
     int rc = hc->pipe.init();
     if (rc) return rc;
     s = hc->pipe.s_k[0];
+    return 0;
+}
+
+// ---- wrapped messages (lz4hip_wrap.hpp) -------------------------------------------------------------------------------------
+// Framing kernels around launch_encode / launch_decode, the int64 scan and the copy routine of the stream path; scratch is the caller's.
+static_assert(sizeof(UnwrapInfo) == sizeof(lz4hip_unwrap_info_t) && offsetof(UnwrapInfo, error) == offsetof(lz4hip_unwrap_info_t, error),
+              "UnwrapInfo must mirror lz4hip_unwrap_info_t");
+static_assert(kWrapBadOffsets == LZ4HIP_E_ARGUMENT && kWrapSizeInvalid == LZ4HIP_WRAP_SIZE_INVALID &&
+              kWrapCorruptHeader == LZ4HIP_WRAP_CORRUPT_HEADER && kWrapCorruptBlock == LZ4HIP_WRAP_CORRUPT_BLOCK, "wrap statuses");
+
+int64_t scan_tiles(int64_t n) { return (n + kScanTile - 1) / kScanTile; }
+
+// wrap scratch: the encoder's output (message i at src_off[i]), its view of the offsets and lengths, its results, the scan's tile sums
+struct WrapScratch { int64_t comp, at, lens, enc, partial, total; };
+WrapScratch wrap_scratch(int64_t n, int64_t src_len)
+{
+    WrapScratch l;
+    int64_t at = 0;
+    l.comp = at;    at += a256(src_len);
+    l.at = at;      at += a256(8 * n);
+    l.lens = at;    at += a256(4 * n);
+    l.enc = at;     at += a256(4 * n);
+    l.partial = at; at += a256(8 * scan_tiles(n));
+    l.total = at;
+    return l;
+}
+
+// unwrap scratch: [min_bad, ncomp], the flags / table rows, the tile sums, then the table of up to n compressed messages
+int64_t unwrap_scratch(int64_t n) { return 256 + 4 * a256(8 * n) + a256(8 * scan_tiles(n)) + 4 * a256(4 * n); }
+UnwrapTables unwrap_tables(void* scratch, int64_t n)
+{
+    uint8_t* p = (uint8_t*)scratch;
+    UnwrapTables t;
+    const int64_t w8 = a256(8 * n), w4 = a256(4 * n);
+    t.n = n;
+    t.min_bad = (unsigned long long*)p;
+    t.ncomp = (int64_t*)(p + 8); p += 256;
+    t.cidx = (int64_t*)p; p += w8;
+    t.partial = (int64_t*)p; p += a256(8 * scan_tiles(n));
+    t.c_src_off = (int64_t*)p; p += w8;
+    t.c_dst_off = (int64_t*)p; p += w8;
+    t.c_msg = (int64_t*)p; p += w8;
+    t.c_src_len = (int32_t*)p; p += w4;
+    t.c_dst_cap = (int32_t*)p; p += w4;
+    t.c_result = (int32_t*)p; p += w4;
+    t.raw_len = (int32_t*)p;
+    return t;
+}
+
+int64_t wrap_bound(int64_t n, int64_t src_len) { return (src_len < 0 ? 0 : src_len) + kWrapHeader * (n < 0 ? 0 : n); }
+
+int wrap_encode(const void* src, int64_t src_len, const int64_t* src_off, int64_t n, int mode, void* dst, int64_t dst_cap, int64_t* dst_off,
+                int32_t* result, void* scratch, int64_t scratch_bytes, hipStream_t stream)
+{
+    if (src_len < 0 || n < 0 || !dst_off) return fail(LZ4HIP_E_ARGUMENT, "wrap: src_len < 0, n < 0 or dst_off is NULL");
+    if (mode != LZ4HIP_MODE_FAST && mode != LZ4HIP_MODE_HC) return fail(LZ4HIP_E_ARGUMENT, "mode must be LZ4HIP_MODE_FAST or LZ4HIP_MODE_HC");
+    if (n > 0x7FFFFFFF) return fail(LZ4HIP_E_ARGUMENT, "wrap: more than 2^31 - 1 messages");
+    if (dst_cap < wrap_bound(n, src_len)) return fail(LZ4HIP_E_ARGUMENT, "wrap: dst_cap < lz4hip_wrap_bound");
+    if (n == 0) { HIP_TRY(hipMemsetAsync(dst_off, 0, sizeof(int64_t), stream)); return 0; }
+    const WrapScratch l = wrap_scratch(n, src_len);
+    if (scratch_bytes < l.total) return fail(LZ4HIP_E_ARGUMENT, "wrap: scratch_bytes < lz4hip_wrap_scratch_bytes");
+    if ((src_len > 0 && !src) || !src_off || !dst || !scratch) return fail(LZ4HIP_E_ARGUMENT, "wrap: src, src_off, dst and scratch must be non-NULL");
+    uint8_t* const s = (uint8_t*)scratch;
+    int64_t* const at = (int64_t*)(s + l.at);
+    int32_t* const lens = (int32_t*)(s + l.lens);
+    int32_t* const enc = (int32_t*)(s + l.enc);
+    hipLaunchKernelGGL(wrap_lens_kernel, dim3(stream_grid(n)), dim3(kStreamThreads), 0, stream, src_off, n, src_len, at, lens);
+    HIP_TRY(hipGetLastError());
+    // Wrap: outputLength = inputLength per message, written at the message's own offset; src_len_all = 0 (no bound is known on the host)
+    lz4hip_batch_t b = {};
+    b.src = src; b.src_off = at; b.src_len = lens;
+    b.dst = s + l.comp; b.dst_off = at; b.dst_cap = lens;
+    b.src_len_all = 0; b.result = enc; b.n_blocks = n;
+    int rc = launch_encode(&b, mode, stream);
+    if (rc) return rc;
+    WrapArgs a;
+    a.src = (const uint8_t*)src; a.comp = s + l.comp; a.off = src_off; a.src_len = src_len; a.n = n; a.enc = enc; a.dst_off = dst_off;
+    hipLaunchKernelGGL(wrap_sizes_kernel, dim3(stream_grid(n)), dim3(kStreamThreads), 0, stream, a, result);
+    launch_scan(dst_off, n, (int64_t*)(s + l.partial), dst_off + n, stream);
+    WrapLayout layout = { a };
+    hipLaunchKernelGGL(wrap_pack_kernel, dim3(copy_grid(wrap_bound(n, src_len))), dim3(kStreamThreads), 0, stream, layout, (uint8_t*)dst, dst_cap);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int unwrap_index(const void* src, int64_t src_len, const int64_t* src_off, int64_t n, int64_t* dst_off, int32_t* status,
+                 void* scratch, int64_t scratch_bytes, lz4hip_unwrap_info_t* info, hipStream_t stream)
+{
+    if (src_len < 0 || n < 0 || !dst_off || !info || !scratch) return fail(LZ4HIP_E_ARGUMENT, "unwrap index: negative size or NULL pointer");
+    if (n > 0 && (!src_off || !status || (src_len > 0 && !src))) return fail(LZ4HIP_E_ARGUMENT, "unwrap index: NULL pointer");
+    if (scratch_bytes < unwrap_scratch(n)) return fail(LZ4HIP_E_ARGUMENT, "unwrap index: scratch_bytes < lz4hip_unwrap_scratch_bytes");
+    const UnwrapTables t = unwrap_tables(scratch, n);
+    HIP_TRY(hipMemsetAsync(scratch, 0xFF, 8, stream));                 // min_bad = none
+    HIP_TRY(hipMemsetAsync(t.ncomp, 0, 8, stream));
+    UnwrapArgs a = { (const uint8_t*)src, src_off, src_len, n, dst_off, status };
+    if (n == 0) {
+        HIP_TRY(hipMemsetAsync(dst_off, 0, sizeof(int64_t), stream));
+    } else {
+        hipLaunchKernelGGL(unwrap_index_kernel, dim3(stream_grid(n)), dim3(kStreamThreads), 0, stream, a, t);
+        launch_scan(dst_off, n, t.partial, dst_off + n, stream);
+        launch_scan(t.cidx, n, t.partial, t.ncomp, stream);
+        hipLaunchKernelGGL(unwrap_compact_kernel, dim3(stream_grid(n)), dim3(kStreamThreads), 0, stream, a, t);
+    }
+    hipLaunchKernelGGL(unwrap_info_kernel, dim3(1), dim3(64), 0, stream, a, t, (UnwrapInfo*)info);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int unwrap_decode(const void* src, int64_t src_len, const int64_t* src_off, int64_t n, const lz4hip_unwrap_info_t* info_host, void* scratch,
+                  int64_t scratch_bytes, void* dst, int64_t dst_cap, const int64_t* dst_off, int32_t* status, lz4hip_unwrap_info_t* info,
+                  hipStream_t stream)
+{
+    if (!info_host || !info || !scratch || !dst_off || src_len < 0 || n < 0) return fail(LZ4HIP_E_ARGUMENT, "unwrap decode: negative size or NULL pointer");
+    const lz4hip_unwrap_info_t h = *info_host;
+    if (h.messages != n || h.compressed < 0 || h.compressed > n || h.decoded_bytes < 0)
+        return fail(LZ4HIP_E_ARGUMENT, "unwrap decode: the info is not the index's of these n messages");
+    if (h.decoded_bytes > dst_cap) return fail(LZ4HIP_E_ARGUMENT, "unwrap decode: decoded_bytes > dst_cap");
+    if (n > 0 && (!src_off || !status || (src_len > 0 && !src))) return fail(LZ4HIP_E_ARGUMENT, "unwrap decode: NULL pointer");
+    if (h.decoded_bytes > 0 && !dst) return fail(LZ4HIP_E_ARGUMENT, "unwrap decode: dst is NULL");
+    if (scratch_bytes < unwrap_scratch(n)) return fail(LZ4HIP_E_ARGUMENT, "unwrap decode: scratch_bytes < lz4hip_unwrap_scratch_bytes");
+    if (h.compressed > 0x7FFFFFFF) return fail(LZ4HIP_E_ARGUMENT, "unwrap decode: more than 2^31 - 1 compressed messages");
+    const UnwrapTables t = unwrap_tables(scratch, n);
+    UnwrapArgs a = { (const uint8_t*)src, src_off, src_len, n, (int64_t*)dst_off, status };
+    if (h.compressed > 0) {
+        // Unwrap: Decode(..., outputLength, knownOutputLength: true) -- the compacted table IS the batch
+        lz4hip_batch_t b = {};
+        b.src = src; b.src_off = t.c_src_off; b.src_len = t.c_src_len;
+        b.dst = dst; b.dst_off = t.c_dst_off; b.dst_cap = t.c_dst_cap;
+        b.result = t.c_result; b.n_blocks = h.compressed;
+        int rc = launch_decode(&b, 1, stream);
+        if (rc) return rc;
+    }
+    if (n > h.compressed && h.decoded_bytes > 0) {
+        UnwrapRawLayout layout = { a, t };
+        hipLaunchKernelGGL(wrap_raw_copy_kernel, dim3(copy_grid(h.decoded_bytes)), dim3(kStreamThreads), 0, stream, layout, (uint8_t*)dst, h.decoded_bytes);
+        HIP_TRY(hipGetLastError());
+    }
+    if (h.compressed > 0)
+        hipLaunchKernelGGL(unwrap_check_kernel, dim3(stream_grid(h.compressed)), dim3(kStreamThreads), 0, stream, t, h.compressed, status);
+    hipLaunchKernelGGL(unwrap_info_kernel, dim3(1), dim3(64), 0, stream, a, t, (UnwrapInfo*)info);
+    HIP_TRY(hipGetLastError());
     return 0;
 }
 
@@ -1999,6 +2147,115 @@ int lz4hip_stream_decode_host(const void* src, int64_t src_len, void* dst, int64
     if ((rc = stream_decode(d, &h, max_chunks, d + table_at, stream_decode_scratch(max_chunks), d + out_at, out_bytes,
                             (lz4hip_stream_info_t*)(d + info_at), s))) return rc;
     HIP_TRY(hipMemcpyAsync(info, d + info_at, sizeof *info, hipMemcpyDeviceToHost, s));
+    if (h.decoded_bytes > 0) HIP_TRY(hipMemcpyAsync(dst, d + out_at, (size_t)h.decoded_bytes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return info->error;
+}
+
+int64_t lz4hip_wrap_bound(int64_t n, int64_t src_len) { return wrap_bound(n, src_len); }
+
+int64_t lz4hip_wrap_scratch_bytes(int64_t n, int64_t src_len) { return n <= 0 ? 0 : wrap_scratch(n, src_len < 0 ? 0 : src_len).total; }
+
+int64_t lz4hip_unwrap_scratch_bytes(int64_t n) { return unwrap_scratch(n < 0 ? 0 : n); }
+
+int lz4hip_wrap_device(const void* src, int64_t src_len, const int64_t* src_off, int64_t n, int mode, void* dst, int64_t dst_cap,
+                       int64_t* dst_off, int32_t* result, void* scratch, int64_t scratch_bytes, void* stream)
+{
+    int rc = ensure_device();
+    if (rc) return rc;
+    return wrap_encode(src, src_len, src_off, n, mode, dst, dst_cap, dst_off, result, scratch, scratch_bytes, (hipStream_t)stream);
+}
+
+int lz4hip_unwrap_index_device(const void* src, int64_t src_len, const int64_t* src_off, int64_t n, int64_t* dst_off, int32_t* status,
+                               void* scratch, int64_t scratch_bytes, lz4hip_unwrap_info_t* info, void* stream)
+{
+    int rc = ensure_device();
+    if (rc) return rc;
+    return unwrap_index(src, src_len, src_off, n, dst_off, status, scratch, scratch_bytes, info, (hipStream_t)stream);
+}
+
+int lz4hip_unwrap_decode_device(const void* src, int64_t src_len, const int64_t* src_off, int64_t n, const lz4hip_unwrap_info_t* info_host,
+                                void* scratch, int64_t scratch_bytes, void* dst, int64_t dst_cap, const int64_t* dst_off, int32_t* status,
+                                lz4hip_unwrap_info_t* info, void* stream)
+{
+    int rc = ensure_device();
+    if (rc) return rc;
+    return unwrap_decode(src, src_len, src_off, n, info_host, scratch, scratch_bytes, dst, dst_cap, dst_off, status, info, (hipStream_t)stream);
+}
+
+int lz4hip_wrap_host(const void* src, int64_t src_len, const int64_t* src_off, int64_t n, int mode, void* dst, int64_t dst_cap,
+                     int64_t* dst_off, int32_t* result)
+{
+    int rc = ensure_device();
+    if (rc) return rc;
+    if (src_len < 0 || n < 0 || !dst_off || (n > 0 && (!src_off || !dst)) || (src_len > 0 && !src))
+        return fail(LZ4HIP_E_ARGUMENT, "wrap: negative size or NULL pointer");
+    const int64_t bound = wrap_bound(n, src_len);
+    if (dst_cap < bound) return fail(LZ4HIP_E_ARGUMENT, "wrap: dst_cap < lz4hip_wrap_bound");
+    if (n == 0) { dst_off[0] = 0; return 0; }
+    HostContext* hc = nullptr;
+    hipStream_t s = nullptr;
+    if ((rc = stream_host_context(hc, s))) return rc;
+    // device image: [source | offsets | output | output offsets | results | scratch]
+    const int64_t scratch_bytes = lz4hip_wrap_scratch_bytes(n, src_len);
+    const int64_t off_at = a256(src_len), out_at = off_at + a256(8 * (n + 1)), doff_at = out_at + a256(bound),
+                  res_at = doff_at + a256(8 * (n + 1)), scratch_at = res_at + a256(4 * n);
+    if ((rc = hc->scratch.reserve((size_t)(scratch_at + scratch_bytes)))) return rc;
+    uint8_t* const d = (uint8_t*)hc->scratch.p;
+    if (src_len > 0) HIP_TRY(hipMemcpyAsync(d, src, (size_t)src_len, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d + off_at, src_off, (size_t)(8 * (n + 1)), hipMemcpyHostToDevice, s));
+    if ((rc = wrap_encode(d, src_len, (const int64_t*)(d + off_at), n, mode, d + out_at, bound, (int64_t*)(d + doff_at), (int32_t*)(d + res_at),
+                          d + scratch_at, scratch_bytes, s))) return rc;
+    HIP_TRY(hipMemcpyAsync(dst_off, d + doff_at, (size_t)(8 * (n + 1)), hipMemcpyDeviceToHost, s));
+    if (result) HIP_TRY(hipMemcpyAsync(result, d + res_at, (size_t)(4 * n), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    const int64_t total = dst_off[n] < dst_cap ? dst_off[n] : dst_cap;
+    if (total > 0) HIP_TRY(hipMemcpyAsync(dst, d + out_at, (size_t)total, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return 0;
+}
+
+int lz4hip_unwrap_host(const void* src, int64_t src_len, const int64_t* src_off, int64_t n, void* dst, int64_t dst_cap, int64_t* dst_off,
+                       int32_t* status, lz4hip_unwrap_info_t* info)
+{
+    int rc = ensure_device();
+    if (rc) return rc;
+    if (src_len < 0 || n < 0 || dst_cap < 0 || !dst_off || !info || (n > 0 && (!src_off || !status)) || (src_len > 0 && !src))
+        return fail(LZ4HIP_E_ARGUMENT, "unwrap: negative size or NULL pointer");
+    HostContext* hc = nullptr;
+    hipStream_t s = nullptr;
+    if ((rc = stream_host_context(hc, s))) return rc;
+    // device image: [source | offsets | output offsets | statuses | info | scratch | output]; staged again if the output had to grow
+    const int64_t scratch_bytes = unwrap_scratch(n);
+    const int64_t off_at = a256(src_len), doff_at = off_at + a256(8 * (n + 1)), st_at = doff_at + a256(8 * (n + 1)),
+                  info_at = st_at + a256(4 * n), scratch_at = info_at + 256, out_at = scratch_at + a256(scratch_bytes);
+    int64_t out_bytes = dst_cap < 4 * src_len ? dst_cap : 4 * src_len;
+    lz4hip_unwrap_info_t h = {};
+    uint8_t* d = nullptr;
+    for (int attempt = 0; attempt < 2; attempt++) {
+        if ((rc = hc->scratch.reserve((size_t)(out_at + out_bytes)))) return rc;
+        d = (uint8_t*)hc->scratch.p;
+        if (src_len > 0) HIP_TRY(hipMemcpyAsync(d, src, (size_t)src_len, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(d + off_at, src_off, (size_t)(8 * (n + 1)), hipMemcpyHostToDevice, s));
+        if ((rc = unwrap_index(d, src_len, (const int64_t*)(d + off_at), n, (int64_t*)(d + doff_at), (int32_t*)(d + st_at), d + scratch_at,
+                               scratch_bytes, (lz4hip_unwrap_info_t*)(d + info_at), s))) return rc;
+        HIP_TRY(hipMemcpyAsync(&h, d + info_at, sizeof h, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        if (h.decoded_bytes <= out_bytes || h.decoded_bytes > dst_cap) break;
+        out_bytes = h.decoded_bytes;
+    }
+    *info = h;
+    if (h.decoded_bytes > dst_cap || h.decoded_bytes > out_bytes) {
+        HIP_TRY(hipMemcpyAsync(dst_off, d + doff_at, (size_t)(8 * (n + 1)), hipMemcpyDeviceToHost, s));
+        if (n > 0) HIP_TRY(hipMemcpyAsync(status, d + st_at, (size_t)(4 * n), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        return fail(LZ4HIP_E_ARGUMENT, "unwrap: dst_cap < decoded_bytes (reported in info->decoded_bytes)");
+    }
+    if ((rc = unwrap_decode(d, src_len, (const int64_t*)(d + off_at), n, &h, d + scratch_at, scratch_bytes, d + out_at, out_bytes,
+                            (const int64_t*)(d + doff_at), (int32_t*)(d + st_at), (lz4hip_unwrap_info_t*)(d + info_at), s))) return rc;
+    HIP_TRY(hipMemcpyAsync(info, d + info_at, sizeof *info, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(dst_off, d + doff_at, (size_t)(8 * (n + 1)), hipMemcpyDeviceToHost, s));
+    if (n > 0) HIP_TRY(hipMemcpyAsync(status, d + st_at, (size_t)(4 * n), hipMemcpyDeviceToHost, s));
     if (h.decoded_bytes > 0) HIP_TRY(hipMemcpyAsync(dst, d + out_at, (size_t)h.decoded_bytes, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     return info->error;

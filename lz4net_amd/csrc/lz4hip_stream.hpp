@@ -217,6 +217,7 @@ template <class Layout>
 LZ4HIP_DEVICE void copy_piece(const Layout& L, CopyCursor<Layout>& c, uint8_t* dst, int64_t o, int64_t end)
 {
     c.seek(L, o);
+    if ((c.k < 0 || o >= c.s.pend) && o + 16 <= c.next) return;       // the whole piece lies between two segments: nothing to write
     if (c.k >= 0 && o >= c.s.pbegin && o + 16 <= c.s.pend && o + 16 <= end) {
         uint32_t w0, w1, w2, w3;
         wv::load_global16((uint64_t)(c.s.payload + (o - c.s.pbegin)), w0, w1, w2, w3);

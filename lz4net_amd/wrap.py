@@ -1,0 +1,161 @@
+"""Batches of wrapped messages (LZ4Codec.Wrap / WrapHC / Unwrap, src/LZ4/LZ4Codec.cs:471-599) on the device: the lz4hip_wrap_* /
+lz4hip_unwrap_* calls of include/lz4hip.h, kernels in csrc/lz4hip_wrap.hpp.
+
+A batch of n messages is one 1-D uint8 buffer plus int64 offsets[n + 1]: message i is buf[offsets[i]:offsets[i + 1]].  wrap_* returns
+the wrapped messages in that layout and unwrap_* reads it, so one's output is the other's input.  The bytes of each message are those
+of LZ4Codec.Wrap / WrapHC / Unwrap; errors raise the exceptions Unwrap raises, with the failing message's index in .message_index.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from .codec import _CORRUPT, ArgumentException
+
+_WRAP_INVALID = "inputBuffer size of inputLength is invalid"
+_MESSAGES = {
+    _lib.WRAP_SIZE_INVALID: "inputBuffer size is invalid",
+    _lib.WRAP_CORRUPT_HEADER: "inputBuffer size is invalid or has been corrupted",
+    _lib.WRAP_CORRUPT_BLOCK: _CORRUPT,
+    _lib.E_ARGUMENT: "offsets are invalid for the given buffer",
+}
+
+
+def unwrap_error(status: int, index: int) -> ArgumentException:
+    """The exception LZ4Codec.Unwrap raises for a message with this status (LZ4HIP_WRAP_*, or LZ4HIP_E_ARGUMENT for bad offsets)."""
+    e = ArgumentException(_MESSAGES.get(int(status), f"unwrap: unexpected status {int(status)}"))
+    e.message_index = int(index)
+    return e
+
+
+# ---- device-resident batches (torch CUDA tensors, torch's current stream) ------------------------------------------------------
+
+def _check_device(buf, offsets):
+    import torch
+    if not isinstance(buf, torch.Tensor) or not buf.is_cuda or buf.dtype != torch.uint8 or buf.dim() != 1:
+        raise ArgumentException("the buffer must be a 1-D uint8 CUDA tensor")
+    if not isinstance(offsets, torch.Tensor) or not offsets.is_cuda or offsets.dtype != torch.int64 or offsets.dim() != 1:
+        raise ArgumentException("offsets must be a 1-D int64 CUDA tensor")
+    if offsets.numel() < 1:
+        raise ArgumentException("offsets must hold n + 1 entries")
+    if offsets.device != buf.device:
+        raise ArgumentException("the buffer and the offsets must be on the same device")
+    return buf.contiguous(), offsets.contiguous()
+
+
+def wrap_device(src, offsets, high_compression: bool = False):
+    """[LZ4Codec.Wrap(m) for m in messages] (WrapHC with high_compression) for the messages src[offsets[i]:offsets[i + 1]] of a CUDA
+    tensor, on the device, on torch's current stream -> (packed, packed_offsets): packed_offsets[i] is where wrapped message i starts.
+    Waits for the device once, to learn the total."""
+    import torch
+    src, offsets = _check_device(src, offsets)
+    with torch.cuda.device(src.device):
+        L = _lib.lib()
+        dev = src.device
+        n = offsets.numel() - 1
+        bound = L.lz4hip_wrap_bound(n, src.numel())
+        out = torch.empty(bound, dtype=torch.uint8, device=dev)
+        out_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        result = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+        scratch = torch.empty(L.lz4hip_wrap_scratch_bytes(n, src.numel()), dtype=torch.uint8, device=dev)
+        _lib.check(L.lz4hip_wrap_device(src.data_ptr(), src.numel(), offsets.data_ptr(), n, _lib.MODE_HC if high_compression else _lib.MODE_FAST,
+                                        out.data_ptr(), bound, out_off.data_ptr(), result.data_ptr(), scratch.data_ptr(), scratch.numel(),
+                                        torch.cuda.current_stream(dev).cuda_stream))
+        lowest = result[:n].min().to(torch.int64).reshape(1) if n else torch.zeros(1, dtype=torch.int64, device=dev)
+        total, lowest = torch.cat([out_off[n:], lowest]).tolist()
+        if lowest < 0:
+            raise ArgumentException(_WRAP_INVALID)
+        return out[:total], out_off
+
+
+def unwrap_device(packed, offsets, check: bool = True):
+    """[LZ4Codec.Unwrap(w) for w in messages] for the wrapped messages packed[offsets[i]:offsets[i + 1]] of a CUDA tensor, on the device,
+    on torch's current stream -> (data, data_offsets).  Every message with a valid header is decoded; with check=True the first failing
+    message raises what Unwrap raises for it (ArgumentException, .message_index = its index), with check=False the per-message statuses
+    (LZ4HIP_WRAP_*, 0 = fine) come back as a third value instead.  Waits for the device twice: to size the output, and for the outcome."""
+    import torch
+    packed, offsets = _check_device(packed, offsets)
+    with torch.cuda.device(packed.device):
+        L = _lib.lib()
+        dev = packed.device
+        s = torch.cuda.current_stream(dev).cuda_stream
+        n = offsets.numel() - 1
+        out_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        status = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+        scratch = torch.empty(L.lz4hip_unwrap_scratch_bytes(n), dtype=torch.uint8, device=dev)
+        info_dev = torch.zeros(C.sizeof(_lib.UnwrapInfo), dtype=torch.uint8, device=dev)
+
+        def read_info():
+            return _lib.UnwrapInfo.from_buffer_copy(info_dev.cpu().numpy().tobytes())
+
+        _lib.check(L.lz4hip_unwrap_index_device(packed.data_ptr(), packed.numel(), offsets.data_ptr(), n, out_off.data_ptr(), status.data_ptr(),
+                                                scratch.data_ptr(), scratch.numel(), info_dev.data_ptr(), s))
+        info = read_info()
+        out = torch.empty(int(info.decoded_bytes), dtype=torch.uint8, device=dev)
+        _lib.check(L.lz4hip_unwrap_decode_device(packed.data_ptr(), packed.numel(), offsets.data_ptr(), n, C.byref(info), scratch.data_ptr(),
+                                                 scratch.numel(), out.data_ptr(), out.numel(), out_off.data_ptr(), status.data_ptr(),
+                                                 info_dev.data_ptr(), s))
+        info = read_info()
+        if not check:
+            return out, out_off, status[:n]
+        if info.first_error >= 0:
+            raise unwrap_error(info.error, info.first_error)
+        return out, out_off
+
+
+# ---- host-resident batches (numpy; the lz4hip_wrap_host / lz4hip_unwrap_host pair) -----------------------------------------------
+
+def _check_host(buf, offsets):
+    if isinstance(buf, (bytes, bytearray, memoryview)):
+        buf = np.frombuffer(buf, dtype=np.uint8)
+    if not isinstance(buf, np.ndarray) or buf.dtype != np.uint8 or buf.ndim != 1:
+        raise ArgumentException("the buffer must be a 1-D uint8 array")
+    if not isinstance(offsets, np.ndarray) or offsets.dtype != np.int64 or offsets.ndim != 1:
+        raise ArgumentException("offsets must be a 1-D int64 array")
+    if offsets.size < 1:
+        raise ArgumentException("offsets must hold n + 1 entries")
+    return np.ascontiguousarray(buf), np.ascontiguousarray(offsets)
+
+
+def wrap_host(src, offsets, high_compression: bool = False):
+    """wrap_device for host arrays, through lz4hip_wrap_host -> (packed, packed_offsets) as numpy arrays."""
+    src, offsets = _check_host(src, offsets)
+    L = _lib.lib()
+    n = offsets.size - 1
+    bound = L.lz4hip_wrap_bound(n, src.size)
+    out = np.empty(max(bound, 1), np.uint8)
+    out_off = np.empty(n + 1, np.int64)
+    result = np.empty(max(n, 1), np.int32)
+    _lib.check(L.lz4hip_wrap_host(src.ctypes.data, src.size, offsets.ctypes.data, n, _lib.MODE_HC if high_compression else _lib.MODE_FAST,
+                                  out.ctypes.data, bound, out_off.ctypes.data, result.ctypes.data))
+    if n and result[:n].min() < 0:
+        raise ArgumentException(_WRAP_INVALID)
+    return out[:int(out_off[n])], out_off
+
+
+def unwrap_host(packed, offsets, check: bool = True):
+    """unwrap_device for host arrays, through lz4hip_unwrap_host -> (data, data_offsets), or (data, data_offsets, status) with
+    check=False."""
+    packed, offsets = _check_host(packed, offsets)
+    L = _lib.lib()
+    n = offsets.size - 1
+    out_off = np.empty(n + 1, np.int64)
+    status = np.empty(max(n, 1), np.int32)
+    info = _lib.UnwrapInfo()
+    # a size query first (dst_cap = 0: LZ4HIP_E_ARGUMENT with decoded_bytes filled in), then the call that decodes
+    rc = L.lz4hip_unwrap_host(packed.ctypes.data, packed.size, offsets.ctypes.data, n, None, 0, out_off.ctypes.data, status.ctypes.data,
+                              C.byref(info))
+    out = np.empty(max(int(info.decoded_bytes), 1), np.uint8)
+    if info.decoded_bytes > 0:
+        rc = L.lz4hip_unwrap_host(packed.ctypes.data, packed.size, offsets.ctypes.data, n, out.ctypes.data, int(info.decoded_bytes),
+                                  out_off.ctypes.data, status.ctypes.data, C.byref(info))
+    if rc != info.error:                                              # (the outcome itself is info.error)
+        _lib.check(rc)
+    out = out[:int(info.decoded_bytes)]
+    if not check:
+        return out, out_off, status[:n]
+    if info.first_error >= 0:
+        raise unwrap_error(info.error, info.first_error)
+    return out, out_off
