@@ -116,22 +116,6 @@ int fail(int code, const std::string& what)
                         std::string(#expr) + ": " + hipGetErrorString(e_));                     \
     } while (0)
 
-// The library refuses to run anywhere but on the architecture its kernels were written for.
-int ensure_device()
-{
-    static thread_local int checked_device = -1;
-    int dev = -1;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return fail(LZ4HIP_E_DEVICE, std::string("no HIP device: ") + hipGetErrorString(e));
-    if (dev == checked_device) return 0;
-    hipDeviceProp_t prop;
-    HIP_TRY(hipGetDeviceProperties(&prop, dev));
-    if (std::string(prop.gcnArchName).rfind("gfx950", 0) != 0)
-        return fail(LZ4HIP_E_DEVICE, std::string("liblz4hip is built for gfx950 only, device is ") + prop.gcnArchName);
-    checked_device = dev;
-    return 0;
-}
-
 Batch to_device_batch(const lz4hip_batch_t& b)
 {
     Batch d;
@@ -179,7 +163,6 @@ struct HcWorkspace {
     hipEvent_t last = nullptr; bool busy = false;
     std::mutex mu;
 };
-HcWorkspace g_hc_ws[64], g_fast_ws[64];
 
 struct Lease {
     HcWorkspace* w = nullptr;
@@ -200,12 +183,9 @@ struct Lease {
 };
 
 // Takes the lock on the device's workspace and makes `stream` wait for its previous user.
-int lease_begin(HcWorkspace* pool, hipStream_t stream, Lease& l)
+int lease_begin(HcWorkspace& w, hipStream_t stream, Lease& l)
 {
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 64) return fail(LZ4HIP_E_DEVICE, "device index out of range");
-    l.w = &pool[dev];
+    l.w = &w;
     l.stream = stream;
     l.lock = std::unique_lock<std::mutex>(l.w->mu);
     if (!l.w->last) HIP_TRY(hipEventCreateWithFlags(&l.w->last, hipEventDisableTiming));
@@ -239,7 +219,7 @@ int lease_end(Lease& l, hipStream_t stream)
 // inside one contiguous 8 GiB allocation, 25-27 G spread out: profiles/r04/random_sectors_*.txt).  Where an allocation lands cannot be
 // asked for, but it can be MEASURED: a candidate set of chunks is built and timed with slab_probe_kernel (a few milliseconds); if it is
 // slower than a well spread slab, up to three more are built next to it and the fastest stays (fast_slab_reserve).
-// One-time work per device and slab size; protected by the g_fast_ws lease.
+// One-time work per device and slab size; protected by the device's fast_ws lease.
 struct FastSlab {
     std::vector<void*> chunks;
     unsigned tables_per_chunk = 0;   // a multiple of 64
@@ -257,7 +237,6 @@ struct FastSlab {
         groups = 0; tables_per_chunk = 0; probe = 0; tries = 0; failed_groups = 0; failed_free = 0;
     }
 };
-FastSlab g_fast_slab[64];
 constexpr int kFastSlabMaxChunks = 64;
 constexpr size_t kFastSlabCtlBytes = 256 + 8 * kFastSlabMaxChunks;
 
@@ -278,9 +257,8 @@ bool fast_slab_candidate(int n_chunks, size_t chunk_bytes, std::vector<void*>& o
 }
 
 // Makes the device's slab hold tables for `groups` wavefronts (nonzero return: could not be allocated; the lease stays valid).
-int fast_slab_reserve(Lease& l, int dev, int64_t groups)
+int fast_slab_reserve(Lease& l, FastSlab& fs, int64_t groups)
 {
-    FastSlab& fs = g_fast_slab[dev];
     if (fs.groups >= groups && fs.ctl) return 0;
     // (a smaller slab that is already there stays until the larger one is built: a failure leaves the old one in place)
     if (fs.failed_groups > 0 && groups >= fs.failed_groups) {            // this size failed before: not again (multi-GiB hipMallocs) unless memory has been freed since
@@ -400,7 +378,75 @@ struct HcPipe {
         ready = false;
     }
 };
-HcPipe g_hc_pipe[64];
+
+// Work counters of the persistent lane decoder: a small per-device ring of 256-byte slots, one per launch in flight.  A slot comes
+// back into use after 64 further launches on that device, possibly on another stream, so each slot carries an event that its
+// user records after the last kernel that reads it: the next user's stream waits for that event before it zeroes the slot, and
+// the slot's mutex is held from the zeroing to the record (a second host thread that draws the same slot waits for the
+// first one's record, not just for its launch).  GPU-side ordering only; a stream never waits unless 64 launches are in flight.
+struct CounterSlot { std::mutex mu; hipEvent_t done = nullptr; bool used = false; };
+struct CounterRing { void* mem = nullptr; CounterSlot slot[64]; std::atomic<unsigned> next{ 0 }; std::mutex mu; };
+
+// Everything the library keeps per device, shared by all its callers: facts and verdicts are kept for the life of the process once
+// they are known; device memory, streams and events until lz4hip_release_workspaces().
+constexpr int kMaxDevices = 64;
+static_assert(kMaxDevices <= 64, "device masks (lz4hip_*_multi) are 64-bit");
+struct DeviceState {
+    std::atomic<int> cus{ 0 };                  // multiprocessors (0: not known yet)
+    std::atomic<bool> gfx950{ false };          // ensure_device() has checked the architecture
+    HcWorkspace hc_ws, fast_ws;
+    FastSlab fast_slab;                         // under the fast_ws lease
+    HcPipe hc_pipe;                             // under the hc_ws lease
+    CounterRing counter_ring;
+    std::atomic<int> lds_drop{ 0 };             // lds_drop_confirmed(): 0 not probed yet, 1 confirmed, 2 not confirmed (or the probe could not run)
+    std::mutex lds_drop_mu;
+    std::atomic<int> lds_encode_five{ 0 }, lds_hc_lcp_fill{ 0 }, lds_encode_hc{ 0 };   // allow_dynamic_lds()
+    std::atomic<int> persist_per_cu{ 0 };       // residency of the persistent lane decoder (0: not known yet)
+};
+DeviceState g_device[kMaxDevices];
+
+// The current device's record (and ordinal), with its CU count known; a failed query is not kept.
+int current_device(DeviceState*& ds, int* dev_out = nullptr)
+{
+    int dev = -1;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return fail(LZ4HIP_E_DEVICE, std::string("no HIP device: ") + hipGetErrorString(e));
+    if (dev < 0 || dev >= kMaxDevices) return fail(LZ4HIP_E_DEVICE, "device index out of range");
+    ds = &g_device[dev];
+    if (ds->cus <= 0) {
+        int cus = 0;
+        HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+        if (cus <= 0) return fail(LZ4HIP_E_DEVICE, "device reports no multiprocessors");
+        ds->cus = cus;
+    }
+    if (dev_out) *dev_out = dev;
+    return 0;
+}
+
+// The library refuses to run anywhere but on the architecture its kernels were written for.
+int ensure_device()
+{
+    DeviceState* ds = nullptr;
+    int dev = -1, rc = current_device(ds, &dev);
+    if (rc || ds->gfx950) return rc;
+    hipDeviceProp_t prop;
+    HIP_TRY(hipGetDeviceProperties(&prop, dev));
+    if (std::string(prop.gcnArchName).rfind("gfx950", 0) != 0)
+        return fail(LZ4HIP_E_DEVICE, std::string("liblz4hip is built for gfx950 only, device is ") + prop.gcnArchName);
+    ds->gfx950 = true;
+    return 0;
+}
+
+// Lets `kernel` use `bytes` of dynamic LDS, asked once per device; `state`: 0 not asked yet, 1 allowed, 2 refused.  keep_refusal: a
+// refusal is kept (and taken off hipGetLastError) for a caller that falls back to a form without it; otherwise it is asked again next time.
+hipError_t allow_dynamic_lds(std::atomic<int>& state, const void* kernel, int bytes, bool keep_refusal)
+{
+    if (int st = state.load(std::memory_order_acquire)) return st == 1 ? hipSuccess : hipErrorInvalidValue;
+    const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e == hipSuccess) state.store(1, std::memory_order_release);
+    else if (keep_refusal) { (void)hipGetLastError(); state.store(2, std::memory_order_release); }
+    return e;
+}
 
 // Whether the wavefront-mapped fast encoder runs as workgroups of kEncodeBlocksPerGroup blocks (ten blocks per CU) instead of one-block workgroups
 // (nine per CU): whenever that saves a residency round -- 2 305 ... 2 560 blocks on 256 CUs, 16 384 (7 rounds instead of 8), every batch from 90 blocks
@@ -412,8 +458,9 @@ bool encoder_five_blocks_per_workgroup(int64_t n_blocks)
     const int k = knob(kKnobEncoderWg5);
     if (k == 1 || n_blocks < kEncodeBlocksPerGroup) return false;
     if (k == 2) return true;
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) return false;
+    DeviceState* ds = nullptr;
+    if (current_device(ds)) return false;
+    const int cus = ds->cus;
     const int64_t rounds9 = (n_blocks + 9 * cus - 1) / (9 * cus), rounds10 = (n_blocks + 10 * cus - 1) / (10 * cus);
     return rounds10 < rounds9;
 }
@@ -422,6 +469,10 @@ int launch_encode(const lz4hip_batch_t* b, int mode, hipStream_t stream)
 {
     if (b->n_blocks == 0) return 0;
     const Batch d = to_device_batch(*b);
+    DeviceState* ds = nullptr;
+    int rc = current_device(ds);
+    if (rc) return rc;
+    const int cus = ds->cus;
     if (mode == LZ4HIP_MODE_FAST) {
         // Two mappings (lz4hip_encode.hpp: one wavefront per block, table in LDS, 64 probes of the match search per
         // step; lz4hip_encode_lane.hpp: one lane per block, tables in a global slab).  The first is several times
@@ -439,19 +490,14 @@ int launch_encode(const lz4hip_batch_t* b, int mode, hipStream_t stream)
         unsigned slab_tpc = 0;
         int64_t groups = 0;
         if (pick != 'w') {
-            int dev = 0, cus = 0;
-            HIP_TRY(hipGetDevice(&dev));
-            HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
             int wpc = knob(kKnobEncoderWavesPerCu) > 0 ? knob(kKnobEncoderWavesPerCu) : kLaneEncodeWavesPerCu;
-            int rc = lease_begin(g_fast_ws, stream, lease);
-            if (rc) return rc;
+            if ((rc = lease_begin(ds->fast_ws, stream, lease))) return rc;
             // the slab holds one table per resident lane; if it cannot be had, halve the residency, and
             // in the end fall back to the wavefront mapping (which needs no workspace)
-            if (dev < 0 || dev >= 64) return fail(LZ4HIP_E_DEVICE, "device index out of range");
             for (; wpc >= 1; wpc /= 2) {
                 groups = (int64_t)cus * wpc;
                 if (groups > (d.n_blocks + 63) / 64) groups = (d.n_blocks + 63) / 64;
-                if (fast_slab_reserve(lease, dev, groups) == 0) { ws = g_fast_slab[dev].ctl; slab_tpc = g_fast_slab[dev].tables_per_chunk; break; }
+                if (fast_slab_reserve(lease, ds->fast_slab, groups) == 0) { ws = ds->fast_slab.ctl; slab_tpc = ds->fast_slab.tables_per_chunk; break; }
             }
             if (!ws) { lease.lock.unlock(); pick = 'w'; }
         }
@@ -466,20 +512,8 @@ int launch_encode(const lz4hip_batch_t* b, int mode, hipStream_t stream)
             // five tables are exactly 64 granules, two such workgroups fill the CU with TEN blocks (profiles/r06/wave_encoder_round_steps.txt).
             // 80 KiB of dynamic LDS has to be allowed per device first; where that is refused the one-block form runs.
             bool five = !first_version && encoder_five_blocks_per_workgroup(d.n_blocks);
-            if (five) {
-                static std::atomic<int> attr_state[64];                  // 0 not asked yet, 1 allowed, 2 refused
-                int dev5 = 0;
-                HIP_TRY(hipGetDevice(&dev5));
-                if (dev5 < 0 || dev5 >= 64) return fail(LZ4HIP_E_DEVICE, "device index out of range");
-                int st = attr_state[dev5].load(std::memory_order_acquire);
-                if (st == 0) {
-                    st = hipFuncSetAttribute((const void*)(encode_fast_kernel<2, kEncodeBlocksPerGroup>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                             kEncodeBlocksPerGroup * kFastTableBytes) == hipSuccess ? 1 : 2;
-                    if (st == 2) (void)hipGetLastError();
-                    attr_state[dev5].store(st, std::memory_order_release);
-                }
-                five = st == 1;
-            }
+            five = five && allow_dynamic_lds(ds->lds_encode_five, (const void*)(encode_fast_kernel<2, kEncodeBlocksPerGroup>),
+                                             kEncodeBlocksPerGroup * kFastTableBytes, true) == hipSuccess;
             if (five)
                 hipLaunchKernelGGL((encode_fast_kernel<2, kEncodeBlocksPerGroup>), dim3((unsigned)((d.n_blocks + kEncodeBlocksPerGroup - 1) / kEncodeBlocksPerGroup)),
                                    dim3(64 * kEncodeBlocksPerGroup), kEncodeBlocksPerGroup * kFastTableBytes, stream, d, pick == 'a' ? (int)kEncodeMayDefer : 0);
@@ -495,13 +529,9 @@ int launch_encode(const lz4hip_batch_t* b, int mode, hipStream_t stream)
                                (unsigned long long*)ws, (uint8_t* const*)((uint8_t*)ws + 256), slab_tpc, pick == 'a' ? 1 : 0);
             HIP_TRY(hipGetLastError());
             count_dispatch(LZ4HIP_K_ENCODE_LANE);
-            int rc = lease_end(lease, stream);
-            if (rc) return rc;
+            if ((rc = lease_end(lease, stream))) return rc;
         }
     } else if (mode == LZ4HIP_MODE_HC) {
-        int dev = 0, cus = 0;
-        HIP_TRY(hipGetDevice(&dev));
-        HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
         // 16-bit heads (64 KiB of LDS, two workgroups per CU) when every block is known to be <= 64 KiB:
         // uniform length, or per-block lengths with src_len_all carrying an upper bound (0 = unknown).
         const bool small = b->src_len_all > 0 && b->src_len_all <= 65536;
@@ -517,8 +547,7 @@ int launch_encode(const lz4hip_batch_t* b, int mode, hipStream_t stream)
         if (force == 1) lane_per_block = false;
         if (force == 2) lane_per_block = true;
         Lease lease;
-        int rc = lease_begin(g_hc_ws, stream, lease);
-        if (rc) return rc;
+        if ((rc = lease_begin(ds->hc_ws, stream, lease))) return rc;
         if (lane_per_block) {
             int hc_gen = knob(kKnobHcGen) ? knob(kKnobHcGen) : kHcLaneGeneration;
             if (hc_gen >= 3 && !small) hc_gen = 2;                    // lz4hip_hc_nat.hpp / lz4hip_hc_lcp.hpp are for blocks <= 64 KiB
@@ -563,14 +592,8 @@ int launch_encode(const lz4hip_batch_t* b, int mode, hipStream_t stream)
                 // stream, and the lane kernel of a sub-chunk starts on its own stream as soon as its tables are there -- next to the
                 // builders of the following ones and to the lane kernels of the earlier ones (each takes its share of the persistent
                 // grid).  Same tables, same bytes; the table memory is what one chunk needs, as before.
-                if (hc_gen == 4) {
-                    static std::atomic<bool> attr_set[64];            // once per device, not per launch
-                    if (!attr_set[dev].load(std::memory_order_acquire)) {
-                        HIP_TRY(hipFuncSetAttribute((const void*)hc_lcp_fill_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kHcLcpFillLdsBytes));
-                        attr_set[dev].store(true, std::memory_order_release);
-                    }
-                }
-                HcPipe& hp = g_hc_pipe[dev];
+                if (hc_gen == 4) HIP_TRY(allow_dynamic_lds(ds->lds_hc_lcp_fill, (const void*)hc_lcp_fill_kernel, kHcLcpFillLdsBytes, false));
+                HcPipe& hp = ds->hc_pipe;
                 if ((rc = hp.init())) return rc;
                 const size_t entry = hc_gen == 4 ? kHcLcpTableBytes : kHcNatChainBytes;
                 uint8_t* const tables = (uint8_t*)ws + kHcCounterBytes;
@@ -663,13 +686,7 @@ int launch_encode(const lz4hip_batch_t* b, int mode, hipStream_t stream)
         // first 8 bytes of the workspace: the work counter of the persistent grid
         lease.queued = true;
         HIP_TRY(hipMemsetAsync(ws, 0, 256, stream));
-        if (!small) {
-            static std::atomic<bool> attr_set[64];                    // once per device, not per launch
-            if (!attr_set[dev].load(std::memory_order_acquire)) {
-                HIP_TRY(hipFuncSetAttribute((const void*)encode_hc_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
-                attr_set[dev].store(true, std::memory_order_release);
-            }
-        }
+        if (!small) HIP_TRY(allow_dynamic_lds(ds->lds_encode_hc, (const void*)encode_hc_kernel, lds_bytes, false));
         hipLaunchKernelGGL(encode_hc_kernel, dim3((unsigned)groups), dim3(64), lds_bytes, stream, d,
                            (unsigned long long*)ws, (uint8_t*)ws + 256, lds_bytes);
         HIP_TRY(hipGetLastError());
@@ -686,26 +703,21 @@ int launch_encode(const lz4hip_batch_t* b, int mode, hipStream_t stream)
 // allocation is dropped.  That rule is CHECKED here, once per device, before the first lane-mapped decode (lds_drop_probe_kernel: every CU
 // full of workgroups of the decoder's LDS size issuing the decoder's kinds of out-of-range stores; ~1 ms); a device that does not confirm it --
 // or a caller that sets the knob decoder_wrapped_stores -- gets the instantiation whose ring rows are wrapped (POL bit 5), same bytes, ~2 % slower.
-std::atomic<int> g_lds_drop_state[64];       // 0 not probed yet, 1 confirmed, 2 not confirmed (or the probe could not run)
-std::mutex g_lds_drop_mu;
-bool lds_drop_confirmed(int dev)
+bool lds_drop_confirmed(DeviceState& ds)
 {
-    if (dev < 0 || dev >= 64) return false;
-    int st = g_lds_drop_state[dev].load(std::memory_order_acquire);
+    int st = ds.lds_drop.load(std::memory_order_acquire);
     if (st == 0) {
-        std::lock_guard<std::mutex> lk(g_lds_drop_mu);
-        st = g_lds_drop_state[dev].load(std::memory_order_acquire);
+        std::lock_guard<std::mutex> lk(ds.lds_drop_mu);
+        st = ds.lds_drop.load(std::memory_order_acquire);
         if (st == 0) {
             st = 2;
-            int cus = 0;
             unsigned* d = nullptr;
             unsigned h = ~0u;
             hipStream_t ps = nullptr;
-            if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0 &&
-                hipStreamCreateWithFlags(&ps, hipStreamNonBlocking) == hipSuccess && hipMalloc(&d, 256) == hipSuccess) {
+            if (hipStreamCreateWithFlags(&ps, hipStreamNonBlocking) == hipSuccess && hipMalloc(&d, 256) == hipSuccess) {
                 bool ok = hipMemsetAsync(d, 0, 256, ps) == hipSuccess;
                 if (ok) {
-                    hipLaunchKernelGGL(lds_drop_probe_kernel, dim3((unsigned)cus * 24u), dim3(64), 0, ps, d, 48);
+                    hipLaunchKernelGGL(lds_drop_probe_kernel, dim3((unsigned)ds.cus * 24u), dim3(64), 0, ps, d, 48);
                     ok = hipGetLastError() == hipSuccess && hipMemcpyAsync(&h, d, 4, hipMemcpyDeviceToHost, ps) == hipSuccess && hipStreamSynchronize(ps) == hipSuccess;
                 }
                 if (ok && h == 0u) st = 1;
@@ -713,20 +725,12 @@ bool lds_drop_confirmed(int dev)
             (void)hipGetLastError();
             if (d) (void)hipFree(d);
             if (ps) (void)hipStreamDestroy(ps);
-            g_lds_drop_state[dev].store(st, std::memory_order_release);
+            ds.lds_drop.store(st, std::memory_order_release);
         }
     }
     return st == 1;
 }
 
-// Work counters of the persistent lane decoder: a small per-device ring of 256-byte slots, one per launch in flight.  A slot comes
-// back into use after 64 further launches on that device, possibly on another stream, so each slot carries an event that its
-// user records after the last kernel that reads it: the next user's stream waits for that event before it zeroes the slot, and
-// the slot's mutex is held from the zeroing to the record (a second host thread that draws the same slot waits for the
-// first one's record, not just for its launch).  GPU-side ordering only; a stream never waits unless 64 launches are in flight.
-struct CounterSlot { std::mutex mu; hipEvent_t done = nullptr; bool used = false; };
-struct CounterRing { void* mem = nullptr; CounterSlot slot[64]; std::atomic<unsigned> next{ 0 }; std::mutex mu; };
-CounterRing g_counter_ring[64];
 struct CounterLease {
     CounterSlot* s = nullptr;
     std::unique_lock<std::mutex> lock;
@@ -734,10 +738,8 @@ struct CounterLease {
     // (also on error returns: whatever was queued on `stream` so far is what may still touch the slot)
     ~CounterLease() { if (s && lock.owns_lock() && s->done && hipEventRecord(s->done, stream) == hipSuccess) s->used = true; }
 };
-int decoder_counter(int dev, hipStream_t stream, unsigned long long** out, CounterLease& lease)
+int decoder_counter(CounterRing& r, hipStream_t stream, unsigned long long** out, CounterLease& lease)
 {
-    if (dev < 0 || dev >= 64) return fail(LZ4HIP_E_DEVICE, "device index out of range");
-    CounterRing& r = g_counter_ring[dev];
     void* mem = nullptr;
     unsigned k = 0;
     {
@@ -785,11 +787,11 @@ int launch_decode(const lz4hip_batch_t* b, int known, hipStream_t stream)
             // bit 4: input pieces are requested in the other iterations only, bit 5: sector input -- L holds a whole 64-byte sector
             // of the source and feeds the window one 32-byte half at a time)
             const int cfg = knob(kKnobDecoderRing) ? knob(kKnobDecoderRing) : kLane4Config;
-            int dev = 0, cus = 0;
-            HIP_TRY(hipGetDevice(&dev));
-            HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+            DeviceState* ds = nullptr;
+            if (int rc = current_device(ds)) return rc;
+            const int cus = ds->cus;
             // ring rows stored twice (out-of-range LDS stores dropped by the hardware) only where this device's probe confirmed the rule
-            const bool wrapped = knob(kKnobDecoderWrappedStores) != 0 || !lds_drop_confirmed(dev);
+            const bool wrapped = knob(kKnobDecoderWrappedStores) != 0 || !lds_drop_confirmed(*ds);
 #define LZ4HIP_LAUNCH_LANE4_POL(RING, PIECE, FLUSH, FS, FE, IE, POL)                                                                \
             do {                                                                                                                \
                 if (known) hipLaunchKernelGGL((decode_lane4_kernel<true, RING, PIECE, FLUSH, FS, FE, IE, POL>), dim3(grid), dim3(64), 0, stream, d, lane_filter);  \
@@ -813,12 +815,11 @@ int launch_decode(const lz4hip_batch_t* b, int known, hipStream_t stream)
                 constexpr int R_ = kLane4Config % 1000, P_ = (kLane4Config / 1000 & 2) ? 32 : 64, FU_ = (kLane4Config / 1000 & 1) ? 128 : 64,
                               FS_ = (kLane4Config / 1000 & 4) ? 1 : 2, FE_ = (kLane4Config / 1000 & 8) ? 2 : 1, IE_ = (kLane4Config / 1000 & 16) ? 2 : 1,
                               POL_ = (kLane4Config / 1000 & 32) ? 16 : 0;
-                static std::atomic<int> per_cu_cached[64];
-                int per_cu = dev >= 0 && dev < 64 ? per_cu_cached[dev].load(std::memory_order_relaxed) : 0;
+                int per_cu = ds->persist_per_cu.load(std::memory_order_relaxed);
                 if (per_cu <= 0) {
                     HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, decode_lane4_persistent_kernel<true, R_, P_, FU_, FS_, FE_, IE_, POL_>, 64, 0));
                     if (per_cu <= 0) per_cu = 1;
-                    if (dev >= 0 && dev < 64) per_cu_cached[dev].store(per_cu, std::memory_order_relaxed);
+                    ds->persist_per_cu.store(per_cu, std::memory_order_relaxed);
                 }
                 const int64_t capacity = (int64_t)per_cu * cus;
                 // 0: one block per lane only; 1: persistent only; 2: counted, one of the two
@@ -826,7 +827,7 @@ int launch_decode(const lz4hip_batch_t* b, int known, hipStream_t stream)
                 int mode = persist == 1 ? 1 : ((int64_t)grid <= capacity ? 0 : ((int64_t)grid < 3 * capacity ? 1 : (lane_filter == kAllBlocks ? 0 : 2)));
                 unsigned long long* counter = nullptr;
                 CounterLease counter_lease;                              // (its destructor records the slot's event behind the kernels queued below)
-                if (mode != 0) { int rc = decoder_counter(dev, stream, &counter, counter_lease); if (rc) return rc; }
+                if (mode != 0) { int rc = decoder_counter(ds->counter_ring, stream, &counter, counter_lease); if (rc) return rc; }
                 const unsigned* gate = mode == 2 ? (const unsigned*)(counter + 1) : nullptr;       // (the slot's second qword: the count)
                 const unsigned threshold = (unsigned)(d.n_blocks - d.n_blocks / 10);            // "nearly every block": 90 %
                 if (mode == 2) {
@@ -972,8 +973,8 @@ struct HostContext {
 // below) -- never a thread the library starts per call.
 HostContext* host_context(int dev, bool create = true)
 {
-    static thread_local HostContext* ctx[64] = {};
-    if (dev < 0 || dev >= 64) return nullptr;
+    static thread_local HostContext* ctx[kMaxDevices] = {};
+    if (dev < 0 || dev >= kMaxDevices) return nullptr;
     if (!ctx[dev] && create) ctx[dev] = new HostContext();   // lives as long as the thread (see ~Scratch)
     return ctx[dev];
 }
@@ -1327,7 +1328,7 @@ int run_host_batch_multi(const lz4hip_batch_t* hb, bool dst_len_is_result, uint6
     int visible = 0;
     if (hipGetDeviceCount(&visible) != hipSuccess || visible <= 0) return fail(LZ4HIP_E_DEVICE, "no HIP device");
     std::vector<int> devs;
-    for (int d = 0; d < visible && d < 64; d++)
+    for (int d = 0; d < visible && d < kMaxDevices; d++)
         if (device_mask == 0 || ((device_mask >> d) & 1ull)) devs.push_back(d);
     if (devs.empty()) return fail(LZ4HIP_E_ARGUMENT, "device_mask selects no visible device");
     const int logical = workers_on_one_device > 0 ? workers_on_one_device : knob(kKnobLogicalDevices);
@@ -1811,29 +1812,23 @@ int lz4hip_dispatch_counts(uint64_t* counts, int n)
 
 int lz4hip_release_workspaces(void)
 {
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 64) return fail(LZ4HIP_E_DEVICE, "device index out of range");
-    for (HcWorkspace* pool : { g_hc_ws, g_fast_ws }) {
-        HcWorkspace& w = pool[dev];
-        std::unique_lock<std::mutex> lock(w.mu);
-        if (pool == g_fast_ws && g_fast_slab[dev].ctl) {             // (the lane encoder's slab hangs off the same lease)
-            if (w.busy && w.last) HIP_TRY(hipEventSynchronize(w.last));
-            g_fast_slab[dev].release();
-            w.busy = false;
-        }
-        if (pool == g_hc_ws && g_hc_pipe[dev].ready) {               // (the sub-chunk pipeline's streams and events hang off the LZ4HC lease)
-            if (w.busy && w.last) HIP_TRY(hipEventSynchronize(w.last));
-            g_hc_pipe[dev].release();
-        }
-        if (!w.p) continue;
-        if (w.busy && w.last) HIP_TRY(hipEventSynchronize(w.last));
-        HIP_TRY(hipFree(w.p));
-        w.p = nullptr; w.cap = 0; w.busy = false;
+    DeviceState* ds = nullptr;
+    int dev = 0, rc = current_device(ds, &dev);
+    if (rc) return rc;
+    // each workspace after its last user, with what hangs off its lease: the LZ4HC sub-chunk pipeline's streams and events, the lane encoder's slab
+    for (HcWorkspace* w : { &ds->hc_ws, &ds->fast_ws }) {
+        std::lock_guard<std::mutex> lock(w->mu);
+        const bool pipe = w == &ds->hc_ws && ds->hc_pipe.ready, slab = w == &ds->fast_ws && ds->fast_slab.ctl;
+        if (!(pipe || slab || w->p)) continue;
+        if (w->busy && w->last) HIP_TRY(hipEventSynchronize(w->last));
+        if (pipe) ds->hc_pipe.release();
+        if (slab) ds->fast_slab.release();
+        if (w->p) HIP_TRY(hipFree(w->p));
+        w->p = nullptr; w->cap = 0; w->busy = false;
     }
     {
         // the persistent lane decoder's counter ring: every slot's last user must be done (slot by slot, under the slot's lock)
-        CounterRing& r = g_counter_ring[dev];
+        CounterRing& r = ds->counter_ring;
         std::lock_guard<std::mutex> lk(r.mu);
         if (r.mem) {
             for (CounterSlot& cs : r.slot) {
@@ -1859,7 +1854,7 @@ int lz4hip_release_workspaces(void)
         if (w->post([] {
                 int nd = 0;
                 if (hipGetDeviceCount(&nd) != hipSuccess) return;
-                for (int d = 0; d < nd && d < 64; d++)
+                for (int d = 0; d < nd && d < kMaxDevices; d++)
                     if (host_context(d, false) && hipSetDevice(d) == hipSuccess) release_host_context(d);
             })) continue;
         w->wait();
@@ -1884,17 +1879,17 @@ int lz4hip_tuning_get(const char* name)
     // read-only: what the placement of the current device's lane-encoder slab measured, in M steps per second (0: no slab yet or not measured),
     // and how many candidate placements were built
     if (name && (strcmp(name, "encoder_slab_rate") == 0 || strcmp(name, "encoder_slab_tried") == 0 || strcmp(name, "encoder_slab_chunks") == 0)) {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
-        std::lock_guard<std::mutex> lk(g_fast_ws[dev].mu);
-        return name[13] == 'r' ? (int)(g_fast_slab[dev].probe * 1000.0) : (name[13] == 't' ? g_fast_slab[dev].tries : (int)g_fast_slab[dev].chunks.size());
+        DeviceState* ds = nullptr;
+        if (current_device(ds)) return 0;
+        std::lock_guard<std::mutex> lk(ds->fast_ws.mu);
+        return name[13] == 'r' ? (int)(ds->fast_slab.probe * 1000.0) : (name[13] == 't' ? ds->fast_slab.tries : (int)ds->fast_slab.chunks.size());
     }
     // read-only: 1 if lane-mapped decodes on the current device store their ring rows twice (the device's probe confirmed that out-of-range LDS
     // stores are dropped, and the knob decoder_wrapped_stores is 0), 0 if they run the wrapped-row instantiation.  Runs the probe if it has not run yet.
     if (name && strcmp(name, "decoder_dual_store") == 0) {
-        int dev = 0;
-        if (ensure_device() || hipGetDevice(&dev) != hipSuccess) return 0;
-        return (lds_drop_confirmed(dev) && knob(kKnobDecoderWrappedStores) == 0) ? 1 : 0;
+        DeviceState* ds = nullptr;
+        if (ensure_device() || current_device(ds)) return 0;
+        return (lds_drop_confirmed(*ds) && knob(kKnobDecoderWrappedStores) == 0) ? 1 : 0;
     }
     for (int k = 0; name && k < kKnobCount; k++)
         if (strcmp(name, kKnobInfo[k].name) == 0) return g_knob[k].load(std::memory_order_relaxed);
@@ -1938,12 +1933,12 @@ int host_workers_for(const lz4hip_batch_t* b, int mode_is_hc)                  /
 int64_t encode_host_slice_blocks(const lz4hip_batch_t* b, int mode)
 {
     if (mode == LZ4HIP_MODE_HC) return kHcHostSliceBlocks;
-    int dev = 0, cus = 0;
-    if (!b || b->n_blocks < 4096 || hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) {
+    DeviceState* ds = nullptr;
+    if (!b || b->n_blocks < 4096 || current_device(ds)) {
         (void)hipGetLastError();
         return 0;
     }
-    const int64_t round = (int64_t)2 * kEncodeBlocksPerGroup * cus, slices = (b->n_blocks + round - 1) / round;
+    const int64_t round = (int64_t)2 * kEncodeBlocksPerGroup * ds->cus, slices = (b->n_blocks + round - 1) / round;
     return (b->n_blocks + slices - 1) / slices;
 }
 
@@ -1953,7 +1948,7 @@ int lz4hip_encode_batch_host(const lz4hip_batch_t* b, int mode)
     const int workers = mode == LZ4HIP_MODE_HC || knob(kKnobHostWorkers) <= 0 ? 1 : host_workers_for(b, 0);
     const int64_t slice = encode_host_slice_blocks(b, mode);
     int dev = 0;
-    if (workers > 1 && hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64)
+    if (workers > 1 && hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < kMaxDevices)
         return run_host_batch_multi(b, true, 1ull << dev, [mode](const lz4hip_batch_t* db, hipStream_t s) { return launch_encode(db, mode, s); }, slice, workers);
     return run_host_batch(b, true, [mode](const lz4hip_batch_t* db, hipStream_t s) { return launch_encode(db, mode, s); }, slice);
 }
@@ -1962,7 +1957,7 @@ int lz4hip_decode_batch_host(const lz4hip_batch_t* b, int known_output_size)
 {
     const int workers = host_workers_for(b, 0);
     int dev = 0;
-    if (workers > 1 && hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64)
+    if (workers > 1 && hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < kMaxDevices)
         return run_host_batch_multi(b, !known_output_size, 1ull << dev,
                                     [known_output_size](const lz4hip_batch_t* db, hipStream_t s) { return launch_decode(db, known_output_size, s); }, 0, workers);
     return run_host_batch(b, !known_output_size,
