@@ -1,6 +1,7 @@
 // HipLZ4Batch.cs -- batch entry points of liblz4hip.so for C# callers (source only: no .NET toolchain in
 // the build environment; the same calls are exercised through ctypes by lz4net_amd/stream.py,
-// lz4net_amd/legacy_frame.py and LZ4Codec.WrapMany/UnwrapMany in lz4net_amd/codec.py).
+// lz4net_amd/legacy_frame.py and LZ4Codec.WrapMany/UnwrapMany in lz4net_amd/codec.py; the lz4hip_streams_*_host
+// declarations below have never been compiled either, tests/test_streams_device.py calls the same symbols through ctypes).
 //
 // lz4net itself has no batch API: callers loop over LZ4Codec.Encode/Decode (LZ4Stream.FlushCurrentChunk /
 // AcquireNextChunk, src/LZ4/LZ4Stream.cs:239-312).  A GPU pays off per batch, so this is the call a
@@ -40,6 +41,28 @@ namespace LZ4hip
 
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
         private static extern unsafe int lz4hip_decode_batch_host_multi(Batch* b, int knownOutputSize, ulong deviceMask);
+
+        // Many LZ4Stream buffers per call (include/lz4hip.h, "batches of LZ4Stream buffers"): one buffer plus offsets[n + 1] in, the
+        // same layout out; every item becomes / is read as the stream LZ4Stream writes for it, the chunks of all items in one batch.
+        // struct lz4hip_streams_info, field for field
+        [StructLayout(LayoutKind.Sequential)]
+        public struct StreamsInfo
+        {
+            public long items, chunks, compressed_chunks, decoded_bytes, first_error, error_offset;
+            public int error, reserved;
+        }
+
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        private static extern long lz4hip_streams_bound(long n, long srcLen, int blockSize);
+
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        private static extern unsafe int lz4hip_streams_encode_host(byte* src, long srcLen, long* srcOff, long n, int blockSize, int mode,
+                                                                    byte* dst, long dstCap, long* dstOff);
+
+        // dstCap = 0 is a size query: LZ4HIP_E_ARGUMENT with info->decoded_bytes, dstOff, status and errorOffset filled in
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        private static extern unsafe int lz4hip_streams_decode_host(byte* src, long srcLen, long* srcOff, long n, byte* dst, long dstCap,
+                                                                    long* dstOff, int* status, long* errorOffset, StreamsInfo* info);
 
         /// <summary>Devices the batch calls shard over (bit d = HIP device d; 0 = every visible device).</summary>
         public static ulong DeviceMask = 0;

@@ -246,6 +246,75 @@ int lz4hip_wrap_host(const void* src, int64_t src_len, const int64_t* src_off, i
 int lz4hip_unwrap_host(const void* src, int64_t src_len, const int64_t* src_off, int64_t n,
                        void* dst, int64_t dst_cap, int64_t* dst_off, int32_t* status, lz4hip_unwrap_info_t* info);
 
+/* ---- batches of LZ4Stream buffers ----------------------------------------------------------------
+ * Many independent LZ4Stream buffers per call -- what a service holds: serialized objects, cache entries, log segments of one to a
+ * handful of chunks each -- in the layout of the wrapped-message calls: one buffer src of src_len bytes plus int64 offsets
+ * src_off[n + 1], item i is src[src_off[i], src_off[i + 1]).  Encode turns every item into the stream lz4hip_stream_encode_device
+ * writes for that item alone, byte for byte, and lays the streams back to back in dst with dst_off[n + 1]; decode reads exactly that
+ * layout: one call's output is the other's input.  Items may be longer than 2 GiB (chunks cannot).  The chunks of ALL items go
+ * through the block codecs as one batch, and on the way back every item's headers are walked by a wavefront of its own.
+ *
+ * Per item, decoding is what the one-stream calls do: every chunk before the item's first header error is decoded into
+ * dst[dst_off[i], dst_off[i + 1]); status[i] is an LZ4HIP_STREAM_* code and error_offset[i] the failing header's offset RELATIVE TO
+ * THE ITEM'S START (-1 if none); a corrupt block, which always comes before the header error, wins.  A failing item never disturbs
+ * another item's bytes or status, and no byte outside an item's range is written.  Offsets that decrease or fall outside
+ * [0, src_len] give that item the status LZ4HIP_E_ARGUMENT and 0 bytes; on encode such an item takes 0 bytes of dst (when offsets
+ * decrease, items may overlap: their output is then unspecified, dst_off[n] may exceed dst_cap, and nothing past dst_cap is written). */
+typedef struct lz4hip_streams_info {
+    int64_t items;                      /* n */
+    int64_t chunks, compressed_chunks;  /* non-empty chunks of all items before their header errors (TABLE_FULL: chunks = the count needed) */
+    int64_t decoded_bytes;              /* dst_off[n] */
+    int64_t first_error;                /* lowest failing item index, -1 if none: what a sequential loop over the items raises first */
+    int64_t error_offset;               /* that item's error_offset, -1 if none */
+    int32_t error, reserved;            /* that item's status, or LZ4HIP_STREAM_TABLE_FULL for the whole batch */
+} lz4hip_streams_info_t;
+
+/* src_len + (src_len / block_size + n) * (1 + 2 * varint_len(block_size)): covers every partition of src_len bytes into n items
+ * (sum of ceil(len_i / block_size) <= src_len / block_size + n).  block_size is clamped to >= 16. */
+int64_t lz4hip_streams_bound(int64_t n, int64_t src_len, int32_t block_size);
+/* Device scratch (bytes) of the device calls below; the index and the decode of one batch share theirs.  0 for an empty batch. */
+int64_t lz4hip_streams_encode_scratch_bytes(int64_t n, int64_t src_len, int32_t block_size);
+int64_t lz4hip_streams_decode_scratch_bytes(int64_t n, int64_t max_chunks);
+
+/* Device-resident batches: the contract of the lz4hip_stream_*_device and lz4hip_wrap_device calls -- device pointers of the CURRENT
+ * device, launch-only on `stream`, no device value read on the host, no allocation, scratch from the caller, 0 or LZ4HIP_E_*
+ * returned -- with the first-use exceptions of lz4hip_encode_batch_device / lz4hip_decode_batch_device, which these calls run on the
+ * chunks.  The offsets are device values, so the host sizes the chunk table by the bound src_len / block_size + n; entries past the
+ * real count are empty blocks.
+ *
+ * Encode: dst_cap >= lz4hip_streams_bound, scratch_bytes >= lz4hip_streams_encode_scratch_bytes; writes dst and dst_off[n + 1]
+ * (dst_off[n] = the total). */
+int lz4hip_streams_encode_device(const void* src, int64_t src_len, const int64_t* src_off, int64_t n, int32_t block_size, int mode,
+                                 void* dst, int64_t dst_cap, int64_t* dst_off,
+                                 void* scratch, int64_t scratch_bytes, void* stream);
+/* Decode is two calls; the caller reads *info back between them (one synchronisation) to size dst.
+ * Index: walks every item's headers (twice: to count, and to fill the tables), writes dst_off[n + 1] (dst_off[n] = decoded_bytes), the
+ * header statuses status[n], error_offset[n] and *info (device).  max_chunks is the table size for the WHOLE batch; when the items
+ * hold more non-empty chunks, info.error = LZ4HIP_STREAM_TABLE_FULL and info.chunks is the count needed.
+ * Decode: given the index's info (host copy) and the same src, offsets, max_chunks, scratch, dst_off, status and error_offset, decodes
+ * what the index found, turns the items with a corrupt block into LZ4HIP_STREAM_CORRUPT_BLOCK at the first such chunk's header and
+ * writes the final *info (device).  LZ4HIP_E_ARGUMENT for an info_host that reports TABLE_FULL, does not describe n items or whose
+ * decoded_bytes exceed dst_cap. */
+int lz4hip_streams_index_device(const void* src, int64_t src_len, const int64_t* src_off, int64_t n, int64_t max_chunks,
+                                int64_t* dst_off, int32_t* status, int64_t* error_offset,
+                                void* scratch, int64_t scratch_bytes, lz4hip_streams_info_t* info, void* stream);
+int lz4hip_streams_decode_device(const void* src, int64_t src_len, const int64_t* src_off, int64_t n,
+                                 const lz4hip_streams_info_t* info_host, int64_t max_chunks, void* scratch, int64_t scratch_bytes,
+                                 void* dst, int64_t dst_cap, const int64_t* dst_off, int32_t* status, int64_t* error_offset,
+                                 lz4hip_streams_info_t* info, void* stream);
+
+/* Host-resident batches (what a C# byte[][] caller binds): stage everything through device memory (per-thread, grow-only, freed by
+ * lz4hip_release_workspaces), run the device calls above and synchronise; every pointer is host memory.
+ * Encode returns 0 or LZ4HIP_E_* (dst_cap >= lz4hip_streams_bound; bad offsets, which the host can see here, are LZ4HIP_E_ARGUMENT).
+ * Decode returns 0 when every item decoded, else info->error (a positive LZ4HIP_STREAM_* code, or LZ4HIP_E_ARGUMENT for bad offsets;
+ * dst, dst_off, status and error_offset are filled in all the same) or LZ4HIP_E_*; with dst_cap below the decoded size it returns
+ * LZ4HIP_E_ARGUMENT with info->decoded_bytes, dst_off, status and error_offset filled in (a size query: dst_cap = 0). */
+int lz4hip_streams_encode_host(const void* src, int64_t src_len, const int64_t* src_off, int64_t n, int32_t block_size, int mode,
+                               void* dst, int64_t dst_cap, int64_t* dst_off);
+int lz4hip_streams_decode_host(const void* src, int64_t src_len, const int64_t* src_off, int64_t n,
+                               void* dst, int64_t dst_cap, int64_t* dst_off, int32_t* status, int64_t* error_offset,
+                               lz4hip_streams_info_t* info);
+
 /* ---- diagnostics ---------------------------------------------------------------------------------
  * Launch counters per kernel family since the library was loaded: which block->hardware mapping a call
  * actually used (the GPU tests assert these).  Copies min(n, LZ4HIP_K_COUNT) counters, returns LZ4HIP_K_COUNT. */

@@ -2,7 +2,8 @@
 
   lz4net_amd.LZ4Codec      host-side mirror of LZ4.LZ4Codec (src/LZ4/LZ4Codec.cs) over the C ABI
   lz4net_amd.batch         device-resident batches on torch tensors (+ round-robin multi-GPU sharding)
-  lz4net_amd.stream        LZ4Stream chunk framing with all chunks of a buffer in one GPU batch
+  lz4net_amd.stream        LZ4Stream chunk framing with all chunks of a buffer in one GPU batch; compress_streams_* / decompress_streams_*
+                           do the same for MANY buffers per call, the chunks of all of them in one batch (lz4hip_streams_*)
   lz4net_amd.wrap          batches of Wrap / WrapHC / Unwrap messages framed on the device (lz4hip_wrap_*)
   lz4net_amd._lib          ctypes binding of liblz4hip.so (include/lz4hip.h)
 

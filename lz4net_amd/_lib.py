@@ -44,6 +44,12 @@ class UnwrapInfo(C.Structure):
 WRAP_OK, WRAP_SIZE_INVALID, WRAP_CORRUPT_HEADER, WRAP_CORRUPT_BLOCK = range(4)
 
 
+class StreamsInfo(C.Structure):
+    """struct lz4hip_streams_info (include/lz4hip.h)."""
+    _fields_ = [("items", C.c_int64), ("chunks", C.c_int64), ("compressed_chunks", C.c_int64), ("decoded_bytes", C.c_int64),
+                ("first_error", C.c_int64), ("error_offset", C.c_int64), ("error", C.c_int32), ("reserved", C.c_int32)]
+
+
 # every symbol include/lz4hip.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("lz4hip_codec_name", C.c_char_p, []),
@@ -91,6 +97,18 @@ SYMBOLS = [
     ("lz4hip_wrap_host", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     ("lz4hip_unwrap_host", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                      C.POINTER(UnwrapInfo)]),
+    ("lz4hip_streams_bound", C.c_int64, [C.c_int64, C.c_int64, C.c_int32]),
+    ("lz4hip_streams_encode_scratch_bytes", C.c_int64, [C.c_int64, C.c_int64, C.c_int32]),
+    ("lz4hip_streams_decode_scratch_bytes", C.c_int64, [C.c_int64, C.c_int64]),
+    ("lz4hip_streams_encode_device", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int, C.c_void_p, C.c_int64, C.c_void_p,
+                                               C.c_void_p, C.c_int64, C.c_void_p]),
+    ("lz4hip_streams_index_device", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    ("lz4hip_streams_decode_device", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(StreamsInfo), C.c_int64, C.c_void_p, C.c_int64,
+                                               C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("lz4hip_streams_encode_host", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
+    ("lz4hip_streams_decode_host", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.POINTER(StreamsInfo)]),
 ]
 
 _lib = None

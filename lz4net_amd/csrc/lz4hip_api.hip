@@ -22,6 +22,7 @@
 #include "lz4hip_synth.hpp"
 #include "lz4hip_stream.hpp"
 #include "lz4hip_wrap.hpp"
+#include "lz4hip_streams.hpp"
 
 #include "../../include/lz4hip.h"
 
@@ -1760,6 +1761,200 @@ int unwrap_decode(const void* src, int64_t src_len, const int64_t* src_off, int6
     return 0;
 }
 
+// ---- batches of LZ4Stream buffers (lz4hip_streams.hpp) ------------------------------------------------------------------------
+// Many independent streams per call: the framing kernels of the one-stream path and its scan and copy routine, around ONE
+// launch_encode / launch_decode over the chunks of all items; scratch is the caller's.
+static_assert(sizeof(StreamsInfo) == sizeof(lz4hip_streams_info_t) && offsetof(StreamsInfo, error) == offsetof(lz4hip_streams_info_t, error) &&
+              offsetof(StreamsInfo, first_error) == offsetof(lz4hip_streams_info_t, first_error), "StreamsInfo must mirror lz4hip_streams_info_t");
+static_assert(kStreamsBadOffsets == LZ4HIP_E_ARGUMENT, "streams statuses");
+constexpr unsigned kStreamsMaxWalkGroups = 1u << 22;          // one wavefront per item; more items than this share wavefronts
+
+// the chunk table's size: the host does not know the offsets, only that sum ceil(len_i / block) <= src_len / block + n
+int64_t streams_chunk_cap(int64_t n, int64_t src_len, int64_t block) { return src_len / block + n; }
+
+int64_t streams_bound(int64_t n, int64_t src_len, int32_t block_size)
+{
+    if (n < 0) n = 0;
+    if (src_len < 0) src_len = 0;
+    const int64_t block = stream_block(block_size);
+    return src_len + streams_chunk_cap(n, src_len, block) * (1 + 2 * varint_len((uint64_t)block));
+}
+
+// encode scratch: the encoder's output (every chunk at its own source position), the items' first chunks, the chunk total, the chunk
+// table (position, length, result, size / offset + the total), the scans' tile sums
+struct StreamsEncodeScratch { int64_t comp, first, total_at, c_at, c_len, result, offs, partial, total; };
+StreamsEncodeScratch streams_encode_scratch(int64_t n, int64_t src_len, int64_t block)
+{
+    const int64_t cap = streams_chunk_cap(n, src_len, block);
+    StreamsEncodeScratch l;
+    int64_t at = 0;
+    l.comp = at;     at += a256(src_len);
+    l.first = at;    at += a256(8 * n);
+    l.total_at = at; at += 256;
+    l.c_at = at;     at += a256(8 * cap);
+    l.c_len = at;    at += a256(4 * cap);
+    l.result = at;   at += a256(4 * cap);
+    l.offs = at;     at += a256(8 * (cap + 1));
+    l.partial = at;  at += a256(8 * scan_tiles(cap));           // (cap >= n: both scans fit)
+    l.total = at;
+    return l;
+}
+
+// decode scratch: [lowest failing item, chunk total, compressed total], three per-item arrays, the scans' tile sums, then the two
+// tables of max_chunks entries (those of the one-stream path plus each compressed chunk's item)
+int64_t streams_decode_scratch(int64_t n, int64_t max_chunks)
+{
+    if (n <= 0) return 0;
+    return 256 + 3 * a256(8 * n) + a256(8 * scan_tiles(n)) + 5 * a256(8 * max_chunks) + 5 * a256(4 * max_chunks);
+}
+StreamsTables streams_tables(void* scratch, int64_t n, int64_t max_chunks)
+{
+    uint8_t* p = (uint8_t*)scratch;
+    StreamsTables t;
+    const int64_t n8 = a256(8 * n), w8 = a256(8 * max_chunks), w4 = a256(4 * max_chunks);
+    t.t.max_chunks = max_chunks;
+    t.t.min_bad = (unsigned long long*)p;
+    t.totals = (int64_t*)(p + 8); p += 256;
+    t.chunk_base = (int64_t*)p; p += n8;
+    t.comp_base = (int64_t*)p; p += n8;
+    t.item_bad = (unsigned long long*)p; p += n8;
+    t.partial = (int64_t*)p; p += a256(8 * scan_tiles(n));
+    t.t.c_src_off = (int64_t*)p; p += w8;
+    t.t.c_dst_off = (int64_t*)p; p += w8;
+    t.t.c_hdr_off = (int64_t*)p; p += w8;
+    t.t.r_dst_off = (int64_t*)p; p += w8;
+    t.t.r_src_off = (int64_t*)p; p += w8;
+    t.t.c_src_len = (int32_t*)p; p += w4;
+    t.t.c_dst_cap = (int32_t*)p; p += w4;
+    t.t.c_result = (int32_t*)p; p += w4;
+    t.t.r_len = (int32_t*)p; p += w4;
+    t.c_item = (int32_t*)p;
+    return t;
+}
+
+int streams_encode(const void* src, int64_t src_len, const int64_t* src_off, int64_t n, int32_t block_size, int mode, void* dst, int64_t dst_cap,
+                   int64_t* dst_off, void* scratch, int64_t scratch_bytes, hipStream_t stream)
+{
+    if (src_len < 0 || n < 0 || !dst_off) return fail(LZ4HIP_E_ARGUMENT, "streams encode: src_len < 0, n < 0 or dst_off is NULL");
+    if (mode != LZ4HIP_MODE_FAST && mode != LZ4HIP_MODE_HC) return fail(LZ4HIP_E_ARGUMENT, "mode must be LZ4HIP_MODE_FAST or LZ4HIP_MODE_HC");
+    const int64_t block = stream_block(block_size), cap = streams_chunk_cap(n, src_len, block);
+    if (n > 0x7FFFFFFF || cap > 0x7FFFFFFF) return fail(LZ4HIP_E_ARGUMENT, "streams encode: more than 2^31 - 1 items or chunks");
+    if (n > 0 && dst_cap < streams_bound(n, src_len, block_size)) return fail(LZ4HIP_E_ARGUMENT, "streams encode: dst_cap < lz4hip_streams_bound");
+    if (n == 0 || src_len == 0) { HIP_TRY(hipMemsetAsync(dst_off, 0, sizeof(int64_t) * (size_t)(n + 1), stream)); return 0; }
+    const StreamsEncodeScratch l = streams_encode_scratch(n, src_len, block);
+    if (scratch_bytes < l.total) return fail(LZ4HIP_E_ARGUMENT, "streams encode: scratch_bytes < lz4hip_streams_encode_scratch_bytes");
+    if (!src || !src_off || !dst || !scratch) return fail(LZ4HIP_E_ARGUMENT, "streams encode: src, src_off, dst and scratch must be non-NULL");
+    uint8_t* const s = (uint8_t*)scratch;
+    int64_t* const partial = (int64_t*)(s + l.partial);
+    StreamsEncodeArgs a;
+    a.src = (const uint8_t*)src; a.comp = s + l.comp; a.off = src_off; a.src_len = src_len; a.n = n; a.cap = cap; a.block = (int32_t)block;
+    a.hc_flag = mode == LZ4HIP_MODE_HC ? kChunkHighCompression : 0u;
+    a.first = (int64_t*)(s + l.first); a.total = (const int64_t*)(s + l.total_at);
+    a.c_at = (int64_t*)(s + l.c_at); a.c_len = (int32_t*)(s + l.c_len); a.result = (const int32_t*)(s + l.result); a.offs = (int64_t*)(s + l.offs);
+    hipLaunchKernelGGL(streams_counts_kernel, dim3(stream_grid(n)), dim3(kStreamThreads), 0, stream, a);
+    launch_scan(a.first, n, partial, (int64_t*)(s + l.total_at), stream);
+    hipLaunchKernelGGL(streams_chunks_kernel, dim3(stream_grid(cap)), dim3(kStreamThreads), 0, stream, a);
+    HIP_TRY(hipGetLastError());
+    // FlushCurrentChunk: outputLength = inputLength per chunk, written at the chunk's own source position; src_len_all = the block size,
+    // the upper bound LZ4HC picks its kernels from
+    lz4hip_batch_t b = {};
+    b.src = src; b.src_off = a.c_at; b.src_len = a.c_len;
+    b.dst = s + l.comp; b.dst_off = a.c_at; b.dst_cap = a.c_len;
+    b.src_len_all = (int32_t)block; b.result = (int32_t*)(s + l.result); b.n_blocks = cap;
+    int rc = launch_encode(&b, mode, stream);
+    if (rc) return rc;
+    hipLaunchKernelGGL(streams_sizes_kernel, dim3(stream_grid(cap)), dim3(kStreamThreads), 0, stream, a);
+    launch_scan(a.offs, cap, partial, a.offs + cap, stream);
+    hipLaunchKernelGGL(streams_offsets_kernel, dim3(stream_grid(n + 1)), dim3(kStreamThreads), 0, stream, a, dst_off);
+    StreamsEncodeLayout layout = { a };
+    hipLaunchKernelGGL(streams_pack_kernel, dim3(copy_grid(streams_bound(n, src_len, block_size))), dim3(kStreamThreads), 0, stream,
+                       layout, (uint8_t*)dst, dst_cap);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+__global__ void streams_empty_info_kernel(StreamsInfo* info)
+{
+    if (threadIdx.x != 0) return;
+    StreamsInfo r = {};
+    r.first_error = r.error_offset = -1;
+    *info = r;
+}
+
+int streams_index(const void* src, int64_t src_len, const int64_t* src_off, int64_t n, int64_t max_chunks, int64_t* dst_off, int32_t* status,
+                  int64_t* error_offset, void* scratch, int64_t scratch_bytes, lz4hip_streams_info_t* info, hipStream_t stream)
+{
+    if (src_len < 0 || n < 0 || max_chunks < 0 || !dst_off || !info) return fail(LZ4HIP_E_ARGUMENT, "streams index: negative size or NULL pointer");
+    if (n > 0x7FFFFFFF) return fail(LZ4HIP_E_ARGUMENT, "streams index: more than 2^31 - 1 items");
+    if (n > 0 && (!src_off || !status || !error_offset || !scratch || (src_len > 0 && !src))) return fail(LZ4HIP_E_ARGUMENT, "streams index: NULL pointer");
+    if (scratch_bytes < streams_decode_scratch(n, max_chunks)) return fail(LZ4HIP_E_ARGUMENT, "streams index: scratch_bytes < lz4hip_streams_decode_scratch_bytes");
+    if (n == 0) {
+        HIP_TRY(hipMemsetAsync(dst_off, 0, sizeof(int64_t), stream));
+        hipLaunchKernelGGL(streams_empty_info_kernel, dim3(1), dim3(64), 0, stream, (StreamsInfo*)info);
+        HIP_TRY(hipGetLastError());
+        return 0;
+    }
+    const StreamsTables t = streams_tables(scratch, n, max_chunks);
+    HIP_TRY(hipMemsetAsync(scratch, 0, 256, stream));
+    HIP_TRY(hipMemsetAsync(scratch, 0xFF, 8, stream));                 // min_bad = none
+    StreamsDecodeArgs a = { (const uint8_t*)src, src_off, src_len, n, dst_off, status, error_offset };
+    const unsigned walkers = n < (int64_t)kStreamsMaxWalkGroups ? (unsigned)n : kStreamsMaxWalkGroups;
+    hipLaunchKernelGGL(streams_walk_kernel<false>, dim3(walkers), dim3(64), 0, stream, a, t);
+    launch_scan(dst_off, n, t.partial, dst_off + n, stream);
+    launch_scan(t.chunk_base, n, t.partial, t.totals, stream);
+    launch_scan(t.comp_base, n, t.partial, t.totals + 1, stream);
+    hipLaunchKernelGGL(streams_walk_kernel<true>, dim3(walkers), dim3(64), 0, stream, a, t);
+    hipLaunchKernelGGL(streams_info_kernel, dim3(1), dim3(64), 0, stream, a, t, (StreamsInfo*)info);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int streams_decode(const void* src, int64_t src_len, const int64_t* src_off, int64_t n, const lz4hip_streams_info_t* info_host, int64_t max_chunks,
+                   void* scratch, int64_t scratch_bytes, void* dst, int64_t dst_cap, const int64_t* dst_off, int32_t* status, int64_t* error_offset,
+                   lz4hip_streams_info_t* info, hipStream_t stream)
+{
+    if (!info_host || !info || !dst_off || src_len < 0 || n < 0 || max_chunks < 0) return fail(LZ4HIP_E_ARGUMENT, "streams decode: negative size or NULL pointer");
+    const lz4hip_streams_info_t h = *info_host;
+    if (h.error == LZ4HIP_STREAM_TABLE_FULL) return fail(LZ4HIP_E_ARGUMENT, "streams decode: the index reported tables too small");
+    if (h.items != n || h.chunks < 0 || h.chunks > max_chunks || h.compressed_chunks < 0 || h.compressed_chunks > h.chunks || h.decoded_bytes < 0)
+        return fail(LZ4HIP_E_ARGUMENT, "streams decode: the info is not the index's of these n items and max_chunks entries");
+    if (h.decoded_bytes > dst_cap) return fail(LZ4HIP_E_ARGUMENT, "streams decode: decoded_bytes > dst_cap");
+    if (n > 0 && (!src_off || !status || !error_offset || !scratch || (src_len > 0 && !src))) return fail(LZ4HIP_E_ARGUMENT, "streams decode: NULL pointer");
+    if (h.decoded_bytes > 0 && !dst) return fail(LZ4HIP_E_ARGUMENT, "streams decode: dst is NULL");
+    if (scratch_bytes < streams_decode_scratch(n, max_chunks)) return fail(LZ4HIP_E_ARGUMENT, "streams decode: scratch_bytes < lz4hip_streams_decode_scratch_bytes");
+    if (h.compressed_chunks > 0x7FFFFFFF) return fail(LZ4HIP_E_ARGUMENT, "streams decode: more than 2^31 - 1 compressed chunks");
+    if (n == 0) {
+        hipLaunchKernelGGL(streams_empty_info_kernel, dim3(1), dim3(64), 0, stream, (StreamsInfo*)info);
+        HIP_TRY(hipGetLastError());
+        return 0;
+    }
+    const StreamsTables t = streams_tables(scratch, n, max_chunks);
+    StreamsDecodeArgs a = { (const uint8_t*)src, src_off, src_len, n, (int64_t*)dst_off, status, error_offset };
+    HIP_TRY(hipMemsetAsync(t.t.min_bad, 0xFF, 8, stream));
+    HIP_TRY(hipMemsetAsync(t.item_bad, 0xFF, (size_t)(8 * n), stream));
+    if (h.compressed_chunks > 0) {
+        // AcquireNextChunk: Decode(..., knownOutputLength: true) -- the compressed table of all items IS the batch
+        lz4hip_batch_t b = {};
+        b.src = src; b.src_off = t.t.c_src_off; b.src_len = t.t.c_src_len;
+        b.dst = dst; b.dst_off = t.t.c_dst_off; b.dst_cap = t.t.c_dst_cap;
+        b.result = t.t.c_result; b.n_blocks = h.compressed_chunks;
+        int rc = launch_decode(&b, 1, stream);
+        if (rc) return rc;
+        hipLaunchKernelGGL(streams_check_kernel, dim3(stream_grid(h.compressed_chunks)), dim3(kStreamThreads), 0, stream, t, h.compressed_chunks);
+        HIP_TRY(hipGetLastError());
+    }
+    if (h.chunks > h.compressed_chunks) {
+        RawLayout layout = { (const uint8_t*)src, t.t, h.chunks - h.compressed_chunks };
+        hipLaunchKernelGGL(stream_raw_copy_kernel, dim3(copy_grid(h.decoded_bytes)), dim3(kStreamThreads), 0, stream,
+                           layout, (uint8_t*)dst, h.decoded_bytes);
+        HIP_TRY(hipGetLastError());
+    }
+    hipLaunchKernelGGL(streams_finish_kernel, dim3(stream_grid(n)), dim3(kStreamThreads), 0, stream, a, t);
+    hipLaunchKernelGGL(streams_info_kernel, dim3(1), dim3(64), 0, stream, a, t, (StreamsInfo*)info);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2251,6 +2446,137 @@ int lz4hip_unwrap_host(const void* src, int64_t src_len, const int64_t* src_off,
     HIP_TRY(hipMemcpyAsync(info, d + info_at, sizeof *info, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(dst_off, d + doff_at, (size_t)(8 * (n + 1)), hipMemcpyDeviceToHost, s));
     if (n > 0) HIP_TRY(hipMemcpyAsync(status, d + st_at, (size_t)(4 * n), hipMemcpyDeviceToHost, s));
+    if (h.decoded_bytes > 0) HIP_TRY(hipMemcpyAsync(dst, d + out_at, (size_t)h.decoded_bytes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return info->error;
+}
+
+int64_t lz4hip_streams_bound(int64_t n, int64_t src_len, int32_t block_size) { return streams_bound(n, src_len, block_size); }
+
+int64_t lz4hip_streams_encode_scratch_bytes(int64_t n, int64_t src_len, int32_t block_size)
+{
+    return n <= 0 ? 0 : streams_encode_scratch(n, src_len < 0 ? 0 : src_len, stream_block(block_size)).total;
+}
+
+int64_t lz4hip_streams_decode_scratch_bytes(int64_t n, int64_t max_chunks) { return streams_decode_scratch(n, max_chunks < 0 ? 0 : max_chunks); }
+
+int lz4hip_streams_encode_device(const void* src, int64_t src_len, const int64_t* src_off, int64_t n, int32_t block_size, int mode,
+                                 void* dst, int64_t dst_cap, int64_t* dst_off, void* scratch, int64_t scratch_bytes, void* stream)
+{
+    int rc = ensure_device();
+    if (rc) return rc;
+    return streams_encode(src, src_len, src_off, n, block_size, mode, dst, dst_cap, dst_off, scratch, scratch_bytes, (hipStream_t)stream);
+}
+
+int lz4hip_streams_index_device(const void* src, int64_t src_len, const int64_t* src_off, int64_t n, int64_t max_chunks, int64_t* dst_off,
+                                int32_t* status, int64_t* error_offset, void* scratch, int64_t scratch_bytes, lz4hip_streams_info_t* info,
+                                void* stream)
+{
+    int rc = ensure_device();
+    if (rc) return rc;
+    return streams_index(src, src_len, src_off, n, max_chunks, dst_off, status, error_offset, scratch, scratch_bytes, info, (hipStream_t)stream);
+}
+
+int lz4hip_streams_decode_device(const void* src, int64_t src_len, const int64_t* src_off, int64_t n, const lz4hip_streams_info_t* info_host,
+                                 int64_t max_chunks, void* scratch, int64_t scratch_bytes, void* dst, int64_t dst_cap, const int64_t* dst_off,
+                                 int32_t* status, int64_t* error_offset, lz4hip_streams_info_t* info, void* stream)
+{
+    int rc = ensure_device();
+    if (rc) return rc;
+    return streams_decode(src, src_len, src_off, n, info_host, max_chunks, scratch, scratch_bytes, dst, dst_cap, dst_off, status, error_offset,
+                          info, (hipStream_t)stream);
+}
+
+int lz4hip_streams_encode_host(const void* src, int64_t src_len, const int64_t* src_off, int64_t n, int32_t block_size, int mode,
+                               void* dst, int64_t dst_cap, int64_t* dst_off)
+{
+    int rc = ensure_device();
+    if (rc) return rc;
+    if (src_len < 0 || n < 0 || !dst_off || (n > 0 && !src_off) || (src_len > 0 && n > 0 && (!src || !dst)))
+        return fail(LZ4HIP_E_ARGUMENT, "streams encode: negative size or NULL pointer");
+    // (the offsets are host memory here: bad ones are refused instead of encoded as empty items)
+    for (int64_t i = 0; i < n; i++)
+        if (src_off[i] < 0 || src_off[i + 1] < src_off[i] || src_off[i + 1] > src_len)
+            return fail(LZ4HIP_E_ARGUMENT, "streams encode: offsets decrease or fall outside [0, src_len]");
+    const int64_t bound = streams_bound(n, src_len, block_size);
+    if (n > 0 && dst_cap < bound) return fail(LZ4HIP_E_ARGUMENT, "streams encode: dst_cap < lz4hip_streams_bound");
+    if (n == 0 || src_len == 0) { for (int64_t i = 0; i <= n; i++) dst_off[i] = 0; return 0; }
+    HostContext* hc = nullptr;
+    hipStream_t s = nullptr;
+    if ((rc = stream_host_context(hc, s))) return rc;
+    // device image: [source | offsets | output | output offsets | scratch]
+    const int64_t scratch_bytes = lz4hip_streams_encode_scratch_bytes(n, src_len, block_size);
+    const int64_t off_at = a256(src_len), out_at = off_at + a256(8 * (n + 1)), doff_at = out_at + a256(bound), scratch_at = doff_at + a256(8 * (n + 1));
+    if ((rc = hc->scratch.reserve((size_t)(scratch_at + scratch_bytes)))) return rc;
+    uint8_t* const d = (uint8_t*)hc->scratch.p;
+    HIP_TRY(hipMemcpyAsync(d, src, (size_t)src_len, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d + off_at, src_off, (size_t)(8 * (n + 1)), hipMemcpyHostToDevice, s));
+    if ((rc = streams_encode(d, src_len, (const int64_t*)(d + off_at), n, block_size, mode, d + out_at, bound, (int64_t*)(d + doff_at),
+                             d + scratch_at, scratch_bytes, s))) return rc;
+    HIP_TRY(hipMemcpyAsync(dst_off, d + doff_at, (size_t)(8 * (n + 1)), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    const int64_t total = dst_off[n] < dst_cap ? dst_off[n] : dst_cap;
+    if (total > 0) HIP_TRY(hipMemcpyAsync(dst, d + out_at, (size_t)total, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return 0;
+}
+
+int lz4hip_streams_decode_host(const void* src, int64_t src_len, const int64_t* src_off, int64_t n, void* dst, int64_t dst_cap, int64_t* dst_off,
+                               int32_t* status, int64_t* error_offset, lz4hip_streams_info_t* info)
+{
+    int rc = ensure_device();
+    if (rc) return rc;
+    if (src_len < 0 || n < 0 || dst_cap < 0 || !dst_off || !info || (n > 0 && (!src_off || !status || !error_offset)) || (src_len > 0 && !src))
+        return fail(LZ4HIP_E_ARGUMENT, "streams decode: negative size or NULL pointer");
+    if (n == 0) {
+        lz4hip_streams_info_t r = {};
+        r.first_error = r.error_offset = -1;
+        *info = r;
+        dst_off[0] = 0;
+        return 0;
+    }
+    HostContext* hc = nullptr;
+    hipStream_t s = nullptr;
+    if ((rc = stream_host_context(hc, s))) return rc;
+    // device image: [source | offsets | output offsets | statuses | error offsets | info | output | tables]; indexed again after tables
+    // that were too small or an image that had to grow
+    const int64_t off_at = a256(src_len), doff_at = off_at + a256(8 * (n + 1)), st_at = doff_at + a256(8 * (n + 1)), eo_at = st_at + a256(4 * n),
+                  info_at = eo_at + a256(8 * n), out_at = info_at + 256;
+    int64_t max_chunks = src_len / 4096 + n + 16, out_bytes = dst_cap < 4 * src_len ? dst_cap : 4 * src_len, table_at = 0, table_bytes = 0;
+    lz4hip_streams_info_t h = {};
+    uint8_t* d = nullptr;
+    for (int attempt = 0;; attempt++) {
+        table_at = out_at + a256(out_bytes);
+        table_bytes = streams_decode_scratch(n, max_chunks);
+        if ((rc = hc->scratch.reserve((size_t)(table_at + table_bytes)))) return rc;
+        d = (uint8_t*)hc->scratch.p;
+        if (src_len > 0) HIP_TRY(hipMemcpyAsync(d, src, (size_t)src_len, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(d + off_at, src_off, (size_t)(8 * (n + 1)), hipMemcpyHostToDevice, s));
+        if ((rc = streams_index(d, src_len, (const int64_t*)(d + off_at), n, max_chunks, (int64_t*)(d + doff_at), (int32_t*)(d + st_at),
+                                (int64_t*)(d + eo_at), d + table_at, table_bytes, (lz4hip_streams_info_t*)(d + info_at), s))) return rc;
+        HIP_TRY(hipMemcpyAsync(&h, d + info_at, sizeof h, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        if (attempt >= 2) break;
+        if (h.error == LZ4HIP_STREAM_TABLE_FULL) { max_chunks = h.chunks; continue; }
+        if (h.decoded_bytes > dst_cap) break;
+        if (h.decoded_bytes > out_bytes) { out_bytes = h.decoded_bytes; continue; }
+        break;
+    }
+    *info = h;
+    if (h.error == LZ4HIP_STREAM_TABLE_FULL) return fail(LZ4HIP_E_DEVICE, "streams decode: the header walk did not settle");
+    if (h.decoded_bytes > dst_cap || h.decoded_bytes > out_bytes) {
+        HIP_TRY(hipMemcpyAsync(dst_off, d + doff_at, (size_t)(8 * (n + 1)), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(status, d + st_at, (size_t)(4 * n), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(error_offset, d + eo_at, (size_t)(8 * n), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        return fail(LZ4HIP_E_ARGUMENT, "streams decode: dst_cap < decoded_bytes (reported in info->decoded_bytes)");
+    }
+    if ((rc = streams_decode(d, src_len, (const int64_t*)(d + off_at), n, &h, max_chunks, d + table_at, table_bytes, d + out_at, out_bytes,
+                             (const int64_t*)(d + doff_at), (int32_t*)(d + st_at), (int64_t*)(d + eo_at), (lz4hip_streams_info_t*)(d + info_at), s))) return rc;
+    HIP_TRY(hipMemcpyAsync(info, d + info_at, sizeof *info, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(dst_off, d + doff_at, (size_t)(8 * (n + 1)), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(status, d + st_at, (size_t)(4 * n), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(error_offset, d + eo_at, (size_t)(8 * n), hipMemcpyDeviceToHost, s));
     if (h.decoded_bytes > 0) HIP_TRY(hipMemcpyAsync(dst, d + out_at, (size_t)h.decoded_bytes, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     return info->error;

@@ -283,63 +283,82 @@ struct StreamTables {
     unsigned long long* min_bad;                                       // header offset of the first corrupt block (decode)
 };
 
-// One wavefront walks the headers in stream order, exactly as stream.parse_chunks / TryReadVarInt do (src/LZ4/LZ4Stream.cs:180-218,
-// 274-312): per chunk ONE wavefront-wide load of the <= 30 header bytes at pos, the three varints' ends from a ballot of the
-// continuation bits (a varint ends at a clear bit or after 10 bytes: count >= 64), their values from one prefix sum of the lanes'
-// 7-bit groups, then a jump past the payload.  Empty chunks (original == 0) are skipped like AcquireNextChunk skips them.
+// One step of the header walk, exactly as stream.parse_chunks / TryReadVarInt do (src/LZ4/LZ4Stream.cs:180-218, 274-312): ONE
+// wavefront-wide load of the <= 30 header bytes at pos, the three varints' ends from a ballot of the continuation bits (a varint
+// ends at a clear bit or after 10 bytes: count >= 64), their values from one prefix sum of the lanes' 7-bit groups, and every
+// check in the order AcquireNextChunk applies them.  Called by all 64 lanes of a wavefront with the same arguments; the result is
+// the same in every lane.  err != kStreamOk: the other fields are not meaningful.
+struct ChunkHeader {
+    int err;
+    bool compressed;
+    int32_t original, clen;      // clen = original for a raw chunk: the payload's length either way
+    int64_t payload;             // offset of the payload; the next header is at payload + clen
+};
+
+LZ4HIP_DEVICE ChunkHeader stream_read_header(const uint8_t* src, int64_t src_len, int64_t pos, int lane)
+{
+    ChunkHeader h;
+    h.err = kStreamEndOfStream; h.compressed = false; h.original = h.clen = 0; h.payload = pos;
+    const int avail = src_len - pos < 30 ? (int)(src_len - pos) : 30;
+    const uint32_t b = lane < avail ? src[pos + lane] : 0u;
+    const uint64_t stop = wv::ballot(lane < avail && (b & 0x80u) == 0);
+    // a varint starting at lane s ends at the first stop at or after s, or at s + 9; it is complete iff that lane exists
+    auto vend = [&](int s) -> int {
+        const uint64_t m = s < 64 ? stop & (~0ull << s) : 0ull;
+        const int e = m ? __builtin_ctzll(m) : 64;
+        return e < s + 9 ? e : s + 9;
+    };
+    const int e1 = vend(0), e2 = vend(e1 + 1), e3 = vend(e2 + 1);
+    // the low 32 bits of each varint: lane i of a varint starting at s contributes (b & 0x7F) << 7 (i - s); the groups do not
+    // overlap, so a prefix sum adds them without carries and varint [s, e] = sum[e] - sum[s - 1]
+    const int s_mine = lane <= e1 ? 0 : (lane <= e2 ? e1 + 1 : e2 + 1);
+    const int sh = 7 * (lane - s_mine);
+    const uint32_t contrib = lane < avail && lane <= e3 && sh < 32 ? (b & 0x7Fu) << sh : 0u;
+    const uint32_t sum = wv::scan_add(contrib);
+    auto value = [&](int s, int e) -> uint32_t { return wv::readlane(sum, e) - (s > 0 ? wv::readlane(sum, s - 1) : 0u); };
+    // flags >> 2 != 0: a bit above bit 1 anywhere in the flags varint
+    const bool high = wv::any(lane <= e1 && lane < avail && ((lane == 0 ? (b & 0x7Cu) : (b & 0x7Fu)) != 0));
+    if (e1 >= avail || e2 >= avail) return h;                                  // inside a varint / missing chunk length
+    const uint32_t flags = value(0, e1);
+    h.compressed = (flags & kChunkCompressed) != 0;
+    if (h.compressed && e3 >= avail) return h;                                 // missing compressed length
+    h.original = (int32_t)value(e1 + 1, e2);
+    h.clen = h.compressed ? (int32_t)value(e2 + 1, e3) : h.original;
+    if (h.clen > h.original || h.clen < 0) return h;                           // corrupted chunk header
+    h.payload = pos + (h.compressed ? e3 : e2) + 1;
+    if (h.payload + h.clen > src_len) return h;                                // truncated payload
+    h.err = h.compressed && high ? kStreamPasses : kStreamOk;                  // multiple passes
+    return h;
+}
+
+// One wavefront walks the headers in stream order, one dependent global round trip per chunk: a header, then a jump past its
+// payload.  Empty chunks (original == 0) are skipped like AcquireNextChunk skips them.
 __global__ void __launch_bounds__(64) stream_index_kernel(const uint8_t* src, int64_t src_len, StreamTables t, StreamInfo* info)
 {
     const int lane = wv::lane();
     int64_t pos = 0, out = 0, chunks = 0, ncomp = 0, nraw = 0, err_off = -1;
     int err = kStreamOk;
     while (pos < src_len) {
-        const int avail = src_len - pos < 30 ? (int)(src_len - pos) : 30;
-        const uint32_t b = lane < avail ? src[pos + lane] : 0u;
-        const uint64_t stop = wv::ballot(lane < avail && (b & 0x80u) == 0);
-        // a varint starting at lane s ends at the first stop at or after s, or at s + 9; it is complete iff that lane exists
-        auto vend = [&](int s) -> int {
-            const uint64_t m = s < 64 ? stop & (~0ull << s) : 0ull;
-            const int e = m ? __builtin_ctzll(m) : 64;
-            return e < s + 9 ? e : s + 9;
-        };
-        const int e1 = vend(0), e2 = vend(e1 + 1), e3 = vend(e2 + 1);
-        // the low 32 bits of each varint: lane i of a varint starting at s contributes (b & 0x7F) << 7 (i - s); the groups do not
-        // overlap, so a prefix sum adds them without carries and varint [s, e] = sum[e] - sum[s - 1]
-        const int s_mine = lane <= e1 ? 0 : (lane <= e2 ? e1 + 1 : e2 + 1);
-        const int sh = 7 * (lane - s_mine);
-        const uint32_t contrib = lane < avail && lane <= e3 && sh < 32 ? (b & 0x7Fu) << sh : 0u;
-        const uint32_t sum = wv::scan_add(contrib);
-        auto value = [&](int s, int e) -> uint32_t { return wv::readlane(sum, e) - (s > 0 ? wv::readlane(sum, s - 1) : 0u); };
-        // flags >> 2 != 0: a bit above bit 1 anywhere in the flags varint
-        const bool high = wv::any(lane <= e1 && lane < avail && ((lane == 0 ? (b & 0x7Cu) : (b & 0x7Fu)) != 0));
-        if (e1 >= avail || e2 >= avail) { err = kStreamEndOfStream; break; }   // inside a varint / missing chunk length
-        const uint32_t flags = value(0, e1);
-        const bool compressed = (flags & kChunkCompressed) != 0;
-        if (compressed && e3 >= avail) { err = kStreamEndOfStream; break; }     // missing compressed length
-        const int32_t original = (int32_t)value(e1 + 1, e2);
-        const int32_t clen = compressed ? (int32_t)value(e2 + 1, e3) : original;
-        if (clen > original || clen < 0) { err = kStreamEndOfStream; break; }   // corrupted chunk header
-        const int64_t payload = pos + (compressed ? e3 : e2) + 1;
-        if (payload + clen > src_len) { err = kStreamEndOfStream; break; }     // truncated payload
-        if (compressed && high) { err = kStreamPasses; break; }                 // multiple passes
-        if (original != 0) {
+        const ChunkHeader h = stream_read_header(src, src_len, pos, lane);
+        if (h.err != kStreamOk) { err = h.err; break; }
+        if (h.original != 0) {
             if (chunks < t.max_chunks) {                                        // (ncomp + nraw == chunks: both lists fit)
                 if (lane == 0) {
-                    if (compressed) {
-                        t.c_src_off[ncomp] = payload; t.c_dst_off[ncomp] = out; t.c_hdr_off[ncomp] = pos;
-                        t.c_src_len[ncomp] = clen; t.c_dst_cap[ncomp] = original;
+                    if (h.compressed) {
+                        t.c_src_off[ncomp] = h.payload; t.c_dst_off[ncomp] = out; t.c_hdr_off[ncomp] = pos;
+                        t.c_src_len[ncomp] = h.clen; t.c_dst_cap[ncomp] = h.original;
                     } else {
-                        t.r_dst_off[nraw] = out; t.r_src_off[nraw] = payload; t.r_len[nraw] = original;
+                        t.r_dst_off[nraw] = out; t.r_src_off[nraw] = h.payload; t.r_len[nraw] = h.original;
                     }
                 }
             } else if (chunks == t.max_chunks) {
                 err_off = pos;                                                  // (TABLE_FULL: the first chunk that did not fit)
             }
-            if (compressed) ncomp++; else nraw++;
+            if (h.compressed) ncomp++; else nraw++;
             chunks++;
-            out += original;
+            out += h.original;
         }
-        pos = payload + clen;
+        pos = h.payload + h.clen;
     }
     // (a full table wins over a later header error: the caller grows the table to `chunks` and walks again)
     if (chunks > t.max_chunks) err = kStreamTableFull;

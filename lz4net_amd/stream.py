@@ -231,3 +231,160 @@ def _decompress_stream_device(t):
     if info.error != _lib.STREAM_OK:
         raise _stream_error(info)
     return out
+
+
+# ---- batches of streams (lz4hip_streams_* of include/lz4hip.h; kernels in csrc/lz4hip_streams.hpp) ---------------------------------
+# A batch of n streams is one 1-D uint8 buffer plus int64 offsets[n + 1]: item i is buf[offsets[i]:offsets[i + 1]].  compress_streams_*
+# returns the framed streams in that layout and decompress_streams_* reads it, so one's output is the other's input.
+
+_BAD_OFFSETS = "offsets are invalid for the given buffer"
+
+
+def _check_streams_device(buf, offsets):
+    import torch
+    if not isinstance(buf, torch.Tensor) or not buf.is_cuda or buf.dtype != torch.uint8 or buf.dim() != 1:
+        raise ArgumentException("the buffer must be a 1-D uint8 CUDA tensor")
+    if not isinstance(offsets, torch.Tensor) or not offsets.is_cuda or offsets.dtype != torch.int64 or offsets.dim() != 1:
+        raise ArgumentException("offsets must be a 1-D int64 CUDA tensor")
+    if offsets.numel() < 1:
+        raise ArgumentException("offsets must hold n + 1 entries")
+    if offsets.device != buf.device:
+        raise ArgumentException("the buffer and the offsets must be on the same device")
+    return buf.contiguous(), offsets.contiguous()
+
+
+def streams_error(status: int, index: int, error_offset: int = -1):
+    """The exception a sequential [decompress_stream(s) for s in ...] raises at an item with this status (LZ4HIP_STREAM_*, or
+    LZ4HIP_E_ARGUMENT for bad offsets), with the item's index in .item_index and the failing header's offset within it in .error_offset."""
+    if int(status) == _lib.E_ARGUMENT:
+        e = ArgumentException(_BAD_OFFSETS)
+        e.error_offset = -1
+    else:
+        e = _stream_error(_lib.StreamInfo(error=int(status), error_offset=int(error_offset)))
+    e.item_index = int(index)
+    return e
+
+
+def compress_streams_device(buf, offsets, block_size: int = DEFAULT_BLOCK_SIZE, high_compression: bool = False):
+    """[compress_stream(item) for item in items] for the items buf[offsets[i]:offsets[i + 1]] of a CUDA tensor, in one call on the
+    device, on torch's current stream -> (packed, packed_offsets): packed_offsets[i] is where item i's stream starts.  The chunks of
+    all items are one batch of the block encoder.  Waits for the device once, to learn the total."""
+    import torch
+    buf, offsets = _check_streams_device(buf, offsets)
+    block_size = max(16, int(block_size))
+    with torch.cuda.device(buf.device):
+        L = _lib.lib()
+        dev = buf.device
+        n = offsets.numel() - 1
+        bound = L.lz4hip_streams_bound(n, buf.numel(), block_size)
+        out = torch.empty(bound, dtype=torch.uint8, device=dev)
+        out_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        scratch = torch.empty(L.lz4hip_streams_encode_scratch_bytes(n, buf.numel(), block_size), dtype=torch.uint8, device=dev)
+        _lib.check(L.lz4hip_streams_encode_device(buf.data_ptr(), buf.numel(), offsets.data_ptr(), n, block_size,
+                                                  _lib.MODE_HC if high_compression else _lib.MODE_FAST, out.data_ptr(), bound,
+                                                  out_off.data_ptr(), scratch.data_ptr(), scratch.numel(),
+                                                  torch.cuda.current_stream(dev).cuda_stream))
+        bad = ((offsets[1:] < offsets[:-1]).any() | (offsets[0] < 0) | (offsets[-1] > buf.numel())).to(torch.int64).reshape(1)
+        total, bad = torch.cat([out_off[n:], bad]).tolist()
+        if bad:
+            raise ArgumentException(_BAD_OFFSETS)
+        return out[:total], out_off
+
+
+def decompress_streams_device(packed, offsets, check: bool = True):
+    """[decompress_stream(s) for s in streams] for the streams packed[offsets[i]:offsets[i + 1]] of a CUDA tensor, on the device, on
+    torch's current stream -> (data, data_offsets).  Every item's headers are walked by a wavefront of its own, the compressed chunks
+    of all items are one batch of the block decoder.  Every chunk before an item's first error is decoded; with check=True the first
+    failing item raises what decompress_stream raises for it (.item_index = its index, .error_offset = the failing header's offset
+    within the item), with check=False the per-item statuses (LZ4HIP_STREAM_*, 0 = fine; LZ4HIP_E_ARGUMENT for bad offsets) come back
+    as a third value instead.  Waits for the device twice: to size the output, and for the outcome."""
+    import torch
+    packed, offsets = _check_streams_device(packed, offsets)
+    with torch.cuda.device(packed.device):
+        L = _lib.lib()
+        dev = packed.device
+        s = torch.cuda.current_stream(dev).cuda_stream
+        n = offsets.numel() - 1
+        out_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        status = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+        err_off = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
+        info_dev = torch.zeros(C.sizeof(_lib.StreamsInfo), dtype=torch.uint8, device=dev)
+
+        def read_info():
+            return _lib.StreamsInfo.from_buffer_copy(info_dev.cpu().numpy().tobytes())
+
+        max_chunks = packed.numel() // 4096 + n + 16
+        for _ in range(2):
+            scratch = torch.empty(L.lz4hip_streams_decode_scratch_bytes(n, max_chunks), dtype=torch.uint8, device=dev)
+            _lib.check(L.lz4hip_streams_index_device(packed.data_ptr(), packed.numel(), offsets.data_ptr(), n, max_chunks, out_off.data_ptr(),
+                                                     status.data_ptr(), err_off.data_ptr(), scratch.data_ptr(), scratch.numel(),
+                                                     info_dev.data_ptr(), s))
+            info = read_info()
+            if info.error != _lib.STREAM_TABLE_FULL:
+                break
+            max_chunks = int(info.chunks)
+        out = torch.empty(int(info.decoded_bytes), dtype=torch.uint8, device=dev)
+        _lib.check(L.lz4hip_streams_decode_device(packed.data_ptr(), packed.numel(), offsets.data_ptr(), n, C.byref(info), max_chunks,
+                                                  scratch.data_ptr(), scratch.numel(), out.data_ptr(), out.numel(), out_off.data_ptr(),
+                                                  status.data_ptr(), err_off.data_ptr(), info_dev.data_ptr(), s))
+        info = read_info()
+        if not check:
+            return out, out_off, status[:n]
+        if info.first_error >= 0:
+            raise streams_error(info.error, info.first_error, info.error_offset)
+        return out, out_off
+
+
+def _check_streams_host(buf, offsets):
+    if isinstance(buf, (bytes, bytearray, memoryview)):
+        buf = np.frombuffer(buf, dtype=np.uint8)
+    if not isinstance(buf, np.ndarray) or buf.dtype != np.uint8 or buf.ndim != 1:
+        raise ArgumentException("the buffer must be a 1-D uint8 array")
+    if not isinstance(offsets, np.ndarray) or offsets.dtype != np.int64 or offsets.ndim != 1:
+        raise ArgumentException("offsets must be a 1-D int64 array")
+    if offsets.size < 1:
+        raise ArgumentException("offsets must hold n + 1 entries")
+    return np.ascontiguousarray(buf), np.ascontiguousarray(offsets)
+
+
+def compress_streams_host(buf, offsets, block_size: int = DEFAULT_BLOCK_SIZE, high_compression: bool = False):
+    """compress_streams_device for host arrays, through lz4hip_streams_encode_host -> (packed, packed_offsets) as numpy arrays."""
+    buf, offsets = _check_streams_host(buf, offsets)
+    block_size = max(16, int(block_size))
+    L = _lib.lib()
+    n = offsets.size - 1
+    if n and ((np.diff(offsets) < 0).any() or offsets[0] < 0 or offsets[-1] > buf.size):
+        raise ArgumentException(_BAD_OFFSETS)
+    bound = L.lz4hip_streams_bound(n, buf.size, block_size)
+    out = np.empty(max(bound, 1), np.uint8)
+    out_off = np.empty(n + 1, np.int64)
+    _lib.check(L.lz4hip_streams_encode_host(buf.ctypes.data, buf.size, offsets.ctypes.data, n, block_size,
+                                            _lib.MODE_HC if high_compression else _lib.MODE_FAST, out.ctypes.data, bound, out_off.ctypes.data))
+    return out[:int(out_off[n])], out_off
+
+
+def decompress_streams_host(packed, offsets, check: bool = True):
+    """decompress_streams_device for host arrays, through lz4hip_streams_decode_host -> (data, data_offsets), or (data, data_offsets,
+    status) with check=False."""
+    packed, offsets = _check_streams_host(packed, offsets)
+    L = _lib.lib()
+    n = offsets.size - 1
+    out_off = np.empty(n + 1, np.int64)
+    status = np.empty(max(n, 1), np.int32)
+    err_off = np.empty(max(n, 1), np.int64)
+    info = _lib.StreamsInfo()
+    # a size query first (dst_cap = 0: LZ4HIP_E_ARGUMENT with decoded_bytes filled in), then the call that decodes
+    rc = L.lz4hip_streams_decode_host(packed.ctypes.data, packed.size, offsets.ctypes.data, n, None, 0, out_off.ctypes.data, status.ctypes.data,
+                                      err_off.ctypes.data, C.byref(info))
+    out = np.empty(max(int(info.decoded_bytes), 1), np.uint8)
+    if info.decoded_bytes > 0:
+        rc = L.lz4hip_streams_decode_host(packed.ctypes.data, packed.size, offsets.ctypes.data, n, out.ctypes.data, int(info.decoded_bytes),
+                                          out_off.ctypes.data, status.ctypes.data, err_off.ctypes.data, C.byref(info))
+    if rc != info.error:                                              # (the outcome itself is info.error)
+        _lib.check(rc)
+    out = out[:int(info.decoded_bytes)]
+    if not check:
+        return out, out_off, status[:n]
+    if info.first_error >= 0:
+        raise streams_error(info.error, info.first_error, info.error_offset)
+    return out, out_off
