@@ -285,7 +285,8 @@ struct StreamTables {
 
 // One step of the header walk, exactly as stream.parse_chunks / TryReadVarInt do (src/LZ4/LZ4Stream.cs:180-218, 274-312): ONE
 // wavefront-wide load of the <= 30 header bytes at pos, the three varints' ends from a ballot of the continuation bits (a varint
-// ends at a clear bit or after 10 bytes: count >= 64), their values from one prefix sum of the lanes' 7-bit groups, and every
+// ends at a clear bit or after 10 bytes: count >= 64), the low 32 bits of their values (all the reference keeps of the lengths
+// and of the flags: it casts them to int) from one prefix sum of the lanes' 7-bit groups, and every
 // check in the order AcquireNextChunk applies them.  Called by all 64 lanes of a wavefront with the same arguments; the result is
 // the same in every lane.  err != kStreamOk: the other fields are not meaningful.
 struct ChunkHeader {
@@ -316,8 +317,6 @@ LZ4HIP_DEVICE ChunkHeader stream_read_header(const uint8_t* src, int64_t src_len
     const uint32_t contrib = lane < avail && lane <= e3 && sh < 32 ? (b & 0x7Fu) << sh : 0u;
     const uint32_t sum = wv::scan_add(contrib);
     auto value = [&](int s, int e) -> uint32_t { return wv::readlane(sum, e) - (s > 0 ? wv::readlane(sum, s - 1) : 0u); };
-    // flags >> 2 != 0: a bit above bit 1 anywhere in the flags varint
-    const bool high = wv::any(lane <= e1 && lane < avail && ((lane == 0 ? (b & 0x7Cu) : (b & 0x7Fu)) != 0));
     if (e1 >= avail || e2 >= avail) return h;                                  // inside a varint / missing chunk length
     const uint32_t flags = value(0, e1);
     h.compressed = (flags & kChunkCompressed) != 0;
@@ -327,7 +326,8 @@ LZ4HIP_DEVICE ChunkHeader stream_read_header(const uint8_t* src, int64_t src_len
     if (h.clen > h.original || h.clen < 0) return h;                           // corrupted chunk header
     h.payload = pos + (h.compressed ? e3 : e2) + 1;
     if (h.payload + h.clen > src_len) return h;                                // truncated payload
-    h.err = h.compressed && high ? kStreamPasses : kStreamOk;                  // multiple passes
+    // multiple passes: (int)flags >> 2 != 0 -- the reference casts the varint to an int-based enum, so only bits 2..31 of it count
+    h.err = h.compressed && (flags >> 2) != 0 ? kStreamPasses : kStreamOk;
     return h;
 }
 

@@ -52,7 +52,7 @@ def read_varint(buf, pos: int):
         result += (b & 0x7F) << count
         count += 7
         if (b & 0x80) == 0 or count >= 64:
-            return result, pos
+            return result & 0xFFFFFFFFFFFFFFFF, pos             # (a ulong: of a tenth byte only bit 0 survives its shift by 63)
 
 
 def _batch(src, src_off, src_len, dst, dst_off, dst_cap, result):
@@ -116,7 +116,7 @@ def parse_chunks(stream):
             raise EndOfStreamException("corrupted chunk header")
         if pos + clen > len(buf):
             raise EndOfStreamException("truncated chunk payload")
-        if compressed and (flags >> 2) != 0:
+        if compressed and ((flags & 0xFFFFFFFF) >> 2) != 0:      # (int)flags >> 2: bits 32..63 of the varint do not count
             raise NotImplementedError("Chunks with multiple passes are not supported.")
         chunks.append((compressed, original, pos, clen))
         pos += clen

@@ -153,3 +153,125 @@ def checksum(rows):
 def compare(a, b, lens):
     lens = np.array(lens, np.int32)
     return lib().emu_compare(_p(a), C.c_int64(a.shape[1]), _p(b), C.c_int64(b.shape[1]), _p(lens), C.c_int64(a.shape[0]))
+
+
+# ---- framing kernels (tests/simt/emu_framing.hpp): ctypes twins of the kernels' argument structs --------------------------------------
+_P, _I64, _I32, _U32 = C.c_void_p, C.c_int64, C.c_int32, C.c_uint32
+
+
+class StreamEncodeArgs(C.Structure):
+    _fields_ = [("src", _P), ("comp", _P), ("src_len", _I64), ("n", _I64), ("block", _I32), ("hc_flag", _U32), ("result", _P), ("offs", _P)]
+
+
+class StreamTables(C.Structure):
+    _fields_ = [("max_chunks", _I64), ("c_src_off", _P), ("c_dst_off", _P), ("c_hdr_off", _P), ("c_src_len", _P), ("c_dst_cap", _P),
+                ("c_result", _P), ("r_dst_off", _P), ("r_src_off", _P), ("r_len", _P), ("min_bad", _P)]
+
+
+class StreamInfo(C.Structure):
+    _fields_ = [("chunks", _I64), ("compressed_chunks", _I64), ("decoded_bytes", _I64), ("error_offset", _I64), ("error", _I32), ("reserved", _I32)]
+
+
+class WrapArgs(C.Structure):
+    _fields_ = [("src", _P), ("comp", _P), ("off", _P), ("src_len", _I64), ("n", _I64), ("enc", _P), ("dst_off", _P)]
+
+
+class UnwrapTables(C.Structure):
+    _fields_ = [("n", _I64), ("min_bad", _P), ("ncomp", _P), ("cidx", _P), ("partial", _P), ("c_src_off", _P), ("c_dst_off", _P), ("c_msg", _P),
+                ("c_src_len", _P), ("c_dst_cap", _P), ("c_result", _P), ("raw_len", _P)]
+
+
+class UnwrapArgs(C.Structure):
+    _fields_ = [("src", _P), ("off", _P), ("src_len", _I64), ("n", _I64), ("dst_off", _P), ("status", _P)]
+
+
+class UnwrapInfo(C.Structure):
+    _fields_ = [("messages", _I64), ("compressed", _I64), ("decoded_bytes", _I64), ("first_error", _I64), ("error", _I32), ("reserved", _I32)]
+
+
+class StreamsEncodeArgs(C.Structure):
+    _fields_ = [("src", _P), ("comp", _P), ("off", _P), ("src_len", _I64), ("n", _I64), ("cap", _I64), ("block", _I32), ("hc_flag", _U32),
+                ("first", _P), ("total", _P), ("c_at", _P), ("c_len", _P), ("result", _P), ("offs", _P)]
+
+
+class StreamsTables(C.Structure):
+    _fields_ = [("t", StreamTables), ("totals", _P), ("chunk_base", _P), ("comp_base", _P), ("item_bad", _P), ("partial", _P), ("c_item", _P)]
+
+
+class StreamsDecodeArgs(C.Structure):
+    _fields_ = [("src", _P), ("off", _P), ("src_len", _I64), ("n", _I64), ("dst_off", _P), ("status", _P), ("error_offset", _P)]
+
+
+class StreamsInfo(C.Structure):
+    _fields_ = [("items", _I64), ("chunks", _I64), ("compressed_chunks", _I64), ("decoded_bytes", _I64), ("first_error", _I64),
+                ("error_offset", _I64), ("error", _I32), ("reserved", _I32)]
+
+
+_FRAMING_STRUCTS = [StreamEncodeArgs, StreamTables, StreamInfo, WrapArgs, UnwrapTables, UnwrapArgs, UnwrapInfo, StreamsEncodeArgs,
+                    StreamsTables, StreamsDecodeArgs, StreamsInfo]
+_framing = None
+
+
+def framing():
+    """The library with the framing entry points typed; checks once that the ctypes twins above have the kernels' struct sizes."""
+    global _framing
+    if _framing is None:
+        L = lib()
+        L.emu_framing_sizeof.restype = C.c_int64
+        for i, s in enumerate(_FRAMING_STRUCTS):
+            assert L.emu_framing_sizeof(i) == C.sizeof(s), (s.__name__, L.emu_framing_sizeof(i), C.sizeof(s))
+        ptr, i64, i32 = C.c_void_p, C.c_int64, C.c_int
+        for name, args in {
+            "emu_scan": [ptr, i64, ptr, ptr],
+            "emu_stream_index": [ptr, i64, ptr, ptr],
+            "emu_copy_encode": [ptr, ptr, ptr, i32],
+            "emu_copy_raw": [ptr, ptr, i64, ptr, i64, i32],
+            "emu_copy_wrap": [ptr, ptr, i64, i32],
+            "emu_copy_unwrap_raw": [ptr, ptr, ptr, i64, i32],
+            "emu_copy_streams": [ptr, ptr, i64, i32],
+            "emu_streams_walk": [i32, ptr, ptr, i32],
+            "emu_stream_check": [ptr, i64, i32],
+            "emu_stream_encode": [ptr, ptr, ptr, ptr, ptr, i64, i32, i32],
+            "emu_stream_decode": [ptr, i64, ptr, ptr, ptr, ptr, ptr, ptr, i32, i32],
+            "emu_wrap": [ptr, ptr, ptr, ptr, ptr, ptr, i64, i64, i32, i32],
+            "emu_unwrap_index": [ptr, ptr, ptr, i32],
+            "emu_unwrap_decode": [ptr, ptr, ptr, ptr, ptr, ptr, ptr, i32, i32],
+            "emu_streams_plan": [ptr, ptr, i32],
+            "emu_streams_pack": [ptr, ptr, ptr, ptr, i64, i64, i32, i32],
+            "emu_streams_index": [ptr, ptr, ptr, i32],
+            "emu_streams_decode": [ptr, ptr, ptr, ptr, ptr, ptr, ptr, i32, i32],
+        }.items():
+            getattr(L, name).argtypes = args
+            getattr(L, name).restype = C.c_int if name in ("emu_stream_decode", "emu_streams_decode") else None
+        for name in ("emu_items_grid", "emu_copy_grid", "emu_walk_grid"):
+            getattr(L, name).argtypes = [i64]
+            getattr(L, name).restype = C.c_int
+        _framing = L
+    return _framing
+
+
+def scan_tile():
+    return int(framing().emu_framing_sizeof(100))
+
+
+def copy_span():
+    return int(framing().emu_framing_sizeof(101))
+
+
+def addr(a, offset=0):
+    """Address of element `offset` of a numpy array (the arrays must outlive the call they are passed to)."""
+    return a.ctypes.data + offset * a.itemsize
+
+
+def ref(s):
+    return C.addressof(s)
+
+
+def stream_tables(max_chunks, guard=4, fill=-77):
+    """StreamTables over fresh arrays of max_chunks + guard entries each, pre-filled; returns (struct, dict of the arrays)."""
+    m = max_chunks + guard
+    arrays = {k: np.full(m, fill, np.int64) for k in ("c_src_off", "c_dst_off", "c_hdr_off", "r_dst_off", "r_src_off")}
+    arrays.update({k: np.full(m, fill, np.int32) for k in ("c_src_len", "c_dst_cap", "c_result", "r_len")})
+    arrays["min_bad"] = np.full(1, 0xFFFFFFFFFFFFFFFF, np.uint64)
+    t = StreamTables(max_chunks=max_chunks, **{k: addr(v) for k, v in arrays.items()})
+    return t, arrays

@@ -1,6 +1,7 @@
 // emu_kernels.cpp -- TEST INFRASTRUCTURE ONLY.
 // Compiles the real kernel sources (lz4net_amd/csrc/*.hpp) against the SIMT emulator and exposes
-// them through a C ABI for tests/test_simt_emulation.py.  Built with g++, never shipped.
+// them through a C ABI for tests/test_simt_emulation.py and tests/test_simt_framing.py (the framing kernels: entry points in
+// emu_framing.hpp).  Built with g++, never shipped.
 #include "simt_wave.hpp"
 
 static unsigned long long g_iterations = 0;   // loop iterations of the lane decoders (all wavefronts), counted by lane 0
@@ -17,6 +18,9 @@ static unsigned long long g_stat[32];         // lane-iterations per state of th
 #include "lz4hip_encode.hpp"
 #include "lz4hip_encode_lane.hpp"
 #include "lz4hip_synth.hpp"
+#include "lz4hip_stream.hpp"
+#include "lz4hip_wrap.hpp"
+#include "lz4hip_streams.hpp"
 #ifdef LZ4HIP_HAVE_HC
 #include "lz4hip_hc.hpp"
 #include "lz4hip_hc_lane.hpp"
@@ -320,3 +324,5 @@ unsigned long long emu_steps() { return simt::rt().steps; }
 void emu_stats(unsigned long long* out, int reset) { for (int i = 0; i < 32; i++) { out[i] = g_stat[i]; if (reset) g_stat[i] = 0; } }
 unsigned long long emu_iterations(int reset) { const unsigned long long v = g_iterations; if (reset) g_iterations = 0; return v; }
 }
+
+#include "emu_framing.hpp"

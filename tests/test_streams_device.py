@@ -1,7 +1,9 @@
 """Batches of LZ4Stream buffers on the device (lz4hip_streams_* of include/lz4hip.h, lz4net_amd/stream.py compress_streams_* /
 decompress_streams_*).  CPU: the bound, the scratch sizes, the argument checks.  GPU: every item's bytes against a stream framed by
 the test from the oracle's blocks AND against the one-stream call on that item alone; round trips, foreign streams, per-item errors,
-guard bytes, the dispatch counters of one large batch, the host pair and a 1 GiB round trip.  Everything is exact equality."""
+guard bytes, the dispatch counters of one large batch, the host pair and a 1 GiB round trip.  Everything is exact equality.  The CPU
+twin of the GPU part -- the framing kernels themselves under the SIMT emulator, without the block codec -- lives in
+test_simt_framing.py."""
 import ctypes as C
 
 import numpy as np
@@ -12,7 +14,7 @@ from lz4net_amd import stream as st
 from lz4net_amd.codec import ArgumentException
 
 from conftest import ForcedMapping
-from test_stream_device import BLOCKS, KINDS, _bad_block, _nonminimal, _offsets, data_of, expected_stream, frame
+from test_stream_device import BLOCKS, KINDS, _bad_block, _nonminimal, _offsets, data_of, expected_stream, frame, wide_flags_streams
 
 
 def _varint_len(v):
@@ -229,6 +231,7 @@ def foreign_items(oracle):
     streams.append(frame([(st.FLAG_COMPRESSED, 5000, buf[:r]), (4, 3, b"abc")]))                 # a passes bit on a raw chunk
     streams.append(b"")
     streams.append(frame([(0, 0, b""), (0, 0, b"")]))                                            # nothing but empty chunks
+    streams += wide_flags_streams(oracle)                                                        # flags bits the reference drops
     return streams
 
 

@@ -1,7 +1,8 @@
 """Batches of wrapped messages on the device (lz4hip_wrap_* / lz4hip_unwrap_* of include/lz4hip.h, lz4net_amd/wrap.py).  CPU: the bound,
 the scratch sizes and the argument checks.  GPU: byte parity with messages wrapped HERE from the oracle's blocks, both mappings of
 each codec, round trips on a non-default torch stream, foreign messages, every failure kind in one batch, guard bytes, the host pair
-and a batch large enough for the lane decoder."""
+and a batch large enough for the lane decoder.  The CPU twin of the GPU part -- the framing kernels themselves under the SIMT
+emulator, without the block codec -- lives in test_simt_framing.py."""
 import ctypes as C
 import glob
 import os
