@@ -23,6 +23,7 @@
 #include "lz4hip_stream.hpp"
 #include "lz4hip_wrap.hpp"
 #include "lz4hip_streams.hpp"
+#include "lz4hip_framing.hpp"
 
 #include "../../include/lz4hip.h"
 
@@ -40,6 +41,7 @@
 #include <vector>
 
 using namespace lz4hip;
+using namespace lz4hip::framing;
 
 namespace {
 
@@ -1443,169 +1445,18 @@ int known_size_extent(const uint8_t* src, int osize)
 }
 
 
-// ---- LZ4Stream buffers (lz4hip_stream.hpp) ----------------------------------------------------------------------------------
-// The framing kernels run around the batch paths above (launch_encode / launch_decode); scratch is the caller's, laid out here.
-static_assert(sizeof(StreamInfo) == sizeof(lz4hip_stream_info_t) && offsetof(StreamInfo, error) == offsetof(lz4hip_stream_info_t, error),
-              "StreamInfo must mirror lz4hip_stream_info_t");
-constexpr unsigned kStreamMaxGroups = 8192;                   // grid-stride kernels: at most 32 workgroups of 256 per CU
-
-int64_t stream_block(int32_t block_size) { return block_size < 16 ? 16 : block_size; }
-int64_t stream_chunks(int64_t len, int64_t block) { return len <= 0 ? 0 : (len - 1) / block + 1; }
-int64_t a256(int64_t v) { return (v + 255) / 256 * 256; }
-unsigned stream_grid(int64_t items)
-{
-    const int64_t g = (items + kStreamThreads - 1) / kStreamThreads;
-    return g < 1 ? 1u : (g > kStreamMaxGroups ? kStreamMaxGroups : (unsigned)g);
-}
-
-// the copy kernels: one workgroup per kCopySpan output bytes, at most kStreamMaxGroups (then each takes several spans)
-unsigned copy_grid(int64_t bytes)
-{
-    const int64_t g = (bytes + kCopySpan - 1) / kCopySpan;
-    return g < 1 ? 1u : (g > kStreamMaxGroups ? kStreamMaxGroups : (unsigned)g);
-}
-
-// encode scratch: the encoder's output (chunk k at k * block), chunk lengths, results, sizes / offsets, tile sums of the scan
-struct StreamEncodeScratch { int64_t comp, lens, result, offs, partial, total; };
-StreamEncodeScratch stream_encode_scratch(int64_t len, int64_t block)
-{
-    const int64_t n = stream_chunks(len, block), tiles = (n + kScanTile - 1) / kScanTile;
-    StreamEncodeScratch l;
-    int64_t at = 0;
-    l.comp = at;    at += a256(len);
-    l.lens = at;    at += a256(4 * n);
-    l.result = at;  at += a256(4 * n);
-    l.offs = at;    at += a256(8 * n);
-    l.partial = at; at += a256(8 * tiles);
-    l.total = n ? at : 0;
-    return l;
-}
-
-// decode scratch: the corrupt-block minimum, then the two tables of max_chunks entries
-int64_t stream_decode_scratch(int64_t max_chunks) { return 256 + 5 * a256(8 * max_chunks) + 4 * a256(4 * max_chunks); }
-StreamTables stream_tables(void* scratch, int64_t max_chunks)
-{
-    uint8_t* p = (uint8_t*)scratch;
-    StreamTables t;
-    t.max_chunks = max_chunks;
-    t.min_bad = (unsigned long long*)p; p += 256;
-    const int64_t w8 = a256(8 * max_chunks), w4 = a256(4 * max_chunks);
-    t.c_src_off = (int64_t*)p; p += w8;
-    t.c_dst_off = (int64_t*)p; p += w8;
-    t.c_hdr_off = (int64_t*)p; p += w8;
-    t.r_dst_off = (int64_t*)p; p += w8;
-    t.r_src_off = (int64_t*)p; p += w8;
-    t.c_src_len = (int32_t*)p; p += w4;
-    t.c_dst_cap = (int32_t*)p; p += w4;
-    t.c_result = (int32_t*)p; p += w4;
-    t.r_len = (int32_t*)p;
-    return t;
-}
-
-int64_t stream_bound(int64_t len, int32_t block_size)
-{
-    if (len <= 0) return 0;
-    const int64_t block = stream_block(block_size);
-    return len + stream_chunks(len, block) * (1 + 2 * varint_len((uint64_t)block));
-}
-
-// exclusive scan of x[0, n) in place, n > 0; the sum goes to *total (device); partial holds ceil(n / kScanTile) tile sums
-void launch_scan(int64_t* x, int64_t n, int64_t* partial, int64_t* total, hipStream_t stream)
-{
-    const int64_t tiles = (n + kScanTile - 1) / kScanTile;
-    hipLaunchKernelGGL(stream_scan_reduce_kernel, dim3((unsigned)tiles), dim3(kStreamThreads), 0, stream, (const int64_t*)x, n, partial);
-    hipLaunchKernelGGL(stream_scan_partials_kernel, dim3(1), dim3(kStreamThreads), 0, stream, partial, tiles, total);
-    hipLaunchKernelGGL(stream_scan_apply_kernel, dim3((unsigned)tiles), dim3(kStreamThreads), 0, stream, x, n, (const int64_t*)partial);
-}
-
-int stream_encode(const void* src, int64_t src_len, int32_t block_size, int mode, void* dst, int64_t dst_cap, int64_t* dst_len,
-                  void* scratch, int64_t scratch_bytes, hipStream_t stream)
-{
-    if (src_len < 0 || !dst_len) return fail(LZ4HIP_E_ARGUMENT, "stream encode: src_len < 0 or dst_len is NULL");
-    if (mode != LZ4HIP_MODE_FAST && mode != LZ4HIP_MODE_HC) return fail(LZ4HIP_E_ARGUMENT, "mode must be LZ4HIP_MODE_FAST or LZ4HIP_MODE_HC");
-    const int64_t block = stream_block(block_size), n = stream_chunks(src_len, block);
-    if (n > 0x7FFFFFFF) return fail(LZ4HIP_E_ARGUMENT, "stream encode: more than 2^31 - 1 chunks");
-    if (dst_cap < stream_bound(src_len, block_size)) return fail(LZ4HIP_E_ARGUMENT, "stream encode: dst_cap < lz4hip_stream_bound");
-    const StreamEncodeScratch l = stream_encode_scratch(src_len, block);
-    if (scratch_bytes < l.total) return fail(LZ4HIP_E_ARGUMENT, "stream encode: scratch_bytes < lz4hip_stream_encode_scratch_bytes");
-    if (n == 0) { HIP_TRY(hipMemsetAsync(dst_len, 0, sizeof(int64_t), stream)); return 0; }
-    if (!src || !dst || !scratch) return fail(LZ4HIP_E_ARGUMENT, "stream encode: src, dst and scratch must be non-NULL");
-    uint8_t* const s = (uint8_t*)scratch;
-    int32_t* const lens = (int32_t*)(s + l.lens);
-    int32_t* const result = (int32_t*)(s + l.result);
-    int64_t* const offs = (int64_t*)(s + l.offs);
-    int64_t* const partial = (int64_t*)(s + l.partial);
-    hipLaunchKernelGGL(stream_lens_kernel, dim3(stream_grid(n)), dim3(kStreamThreads), 0, stream, lens, n, src_len, (int32_t)block);
-    HIP_TRY(hipGetLastError());
-    // FlushCurrentChunk: outputLength = inputLength per chunk; src_len_all = the block size, the upper bound LZ4HC picks its kernels from
-    lz4hip_batch_t b = {};
-    b.src = src; b.src_stride = block; b.src_len = lens;
-    b.dst = s + l.comp; b.dst_stride = block; b.dst_cap = lens;
-    b.src_len_all = (int32_t)block; b.result = result; b.n_blocks = n;
-    int rc = launch_encode(&b, mode, stream);
-    if (rc) return rc;
-    StreamEncodeArgs a;
-    a.src = (const uint8_t*)src; a.comp = s + l.comp; a.src_len = src_len; a.n = n; a.block = (int32_t)block;
-    a.hc_flag = mode == LZ4HIP_MODE_HC ? kChunkHighCompression : 0u; a.result = result; a.offs = offs;
-    hipLaunchKernelGGL(stream_sizes_kernel, dim3(stream_grid(n)), dim3(kStreamThreads), 0, stream, a);
-    launch_scan(offs, n, partial, dst_len, stream);
-    EncodeLayout layout = { a };
-    hipLaunchKernelGGL(stream_pack_kernel, dim3(copy_grid(stream_bound(src_len, block_size))), dim3(kStreamThreads), 0, stream,
-                       layout, (uint8_t*)dst, (const int64_t*)dst_len);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-int stream_index(const void* src, int64_t src_len, int64_t max_chunks, void* scratch, int64_t scratch_bytes, lz4hip_stream_info_t* info,
-                 hipStream_t stream)
-{
-    if (src_len < 0 || max_chunks < 0 || !info || !scratch || (src_len > 0 && !src))
-        return fail(LZ4HIP_E_ARGUMENT, "stream index: negative size or NULL pointer");
-    if (scratch_bytes < stream_decode_scratch(max_chunks)) return fail(LZ4HIP_E_ARGUMENT, "stream index: scratch_bytes < lz4hip_stream_decode_scratch_bytes");
-    hipLaunchKernelGGL(stream_index_kernel, dim3(1), dim3(64), 0, stream, (const uint8_t*)src, src_len, stream_tables(scratch, max_chunks), (StreamInfo*)info);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-int stream_decode(const void* src, const lz4hip_stream_info_t* info_host, int64_t max_chunks, void* scratch, int64_t scratch_bytes,
-                  void* dst, int64_t dst_cap, lz4hip_stream_info_t* info, hipStream_t stream)
-{
-    if (!info_host || !info || !scratch || max_chunks < 0) return fail(LZ4HIP_E_ARGUMENT, "stream decode: NULL pointer or max_chunks < 0");
-    const lz4hip_stream_info_t h = *info_host;
-    if (h.error != LZ4HIP_STREAM_OK && h.error != LZ4HIP_STREAM_END_OF_STREAM && h.error != LZ4HIP_STREAM_PASSES)
-        return fail(LZ4HIP_E_ARGUMENT, "stream decode: the index reported a table too small (or the info is not an index's)");
-    if (h.chunks < 0 || h.chunks > max_chunks || h.compressed_chunks < 0 || h.compressed_chunks > h.chunks || h.decoded_bytes < 0)
-        return fail(LZ4HIP_E_ARGUMENT, "stream decode: the info does not fit a table of max_chunks entries");
-    if (h.decoded_bytes > dst_cap) return fail(LZ4HIP_E_ARGUMENT, "stream decode: decoded_bytes > dst_cap");
-    if (h.chunks > 0 && (!src || !dst)) return fail(LZ4HIP_E_ARGUMENT, "stream decode: src and dst must be non-NULL");
-    if (scratch_bytes < stream_decode_scratch(max_chunks)) return fail(LZ4HIP_E_ARGUMENT, "stream decode: scratch_bytes < lz4hip_stream_decode_scratch_bytes");
-    if (h.compressed_chunks > 0x7FFFFFFF) return fail(LZ4HIP_E_ARGUMENT, "stream decode: more than 2^31 - 1 compressed chunks");
-    const StreamTables t = stream_tables(scratch, max_chunks);
-    StreamInfo from_index;
-    memcpy(&from_index, &h, sizeof from_index);
-    hipLaunchKernelGGL(stream_info_init_kernel, dim3(1), dim3(64), 0, stream, from_index, (StreamInfo*)info, t.min_bad);
-    HIP_TRY(hipGetLastError());
-    if (h.compressed_chunks > 0) {
-        // AcquireNextChunk: Decode(..., knownOutputLength: true) -- the compressed table IS the batch
-        lz4hip_batch_t b = {};
-        b.src = src; b.src_off = t.c_src_off; b.src_len = t.c_src_len;
-        b.dst = dst; b.dst_off = t.c_dst_off; b.dst_cap = t.c_dst_cap;
-        b.result = t.c_result; b.n_blocks = h.compressed_chunks;
-        int rc = launch_decode(&b, 1, stream);
-        if (rc) return rc;
-        hipLaunchKernelGGL(stream_check_kernel, dim3(stream_grid(h.compressed_chunks)), dim3(kStreamThreads), 0, stream, t, h.compressed_chunks);
-        HIP_TRY(hipGetLastError());
-    }
-    if (h.chunks > h.compressed_chunks) {
-        RawLayout layout = { (const uint8_t*)src, t, h.chunks - h.compressed_chunks };
-        hipLaunchKernelGGL(stream_raw_copy_kernel, dim3(copy_grid(h.decoded_bytes)), dim3(kStreamThreads), 0, stream,
-                           layout, (uint8_t*)dst, h.decoded_bytes);
-        HIP_TRY(hipGetLastError());
-    }
-    hipLaunchKernelGGL(stream_info_finish_kernel, dim3(1), dim3(64), 0, stream, (StreamInfo*)info, (const unsigned long long*)t.min_bad);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
+// ---- the framing paths (lz4hip_framing.hpp): LZ4Stream buffers, wrapped messages, batches of LZ4Stream buffers ----------------
+// The layouts and the kernel sequences live in that header, shared with the CPU emulator's tests; this is the device they run on here.
+struct HipBackend {
+    hipStream_t stream;
+    template <class... P, class... A>
+    void launch(void (*kernel)(P...), Grid grid, unsigned threads, A&&... a) { hipLaunchKernelGGL(kernel, dim3(grid.groups), dim3(threads), 0, stream, P(a)...); }
+    int fill(void* p, int byte, size_t bytes) { HIP_TRY(hipMemsetAsync(p, byte, bytes, stream)); return 0; }
+    int encode(const lz4hip_batch_t* b, int mode) { return launch_encode(b, mode, stream); }
+    int decode(const lz4hip_batch_t* b, int known) { return launch_decode(b, known, stream); }
+    int last_error() { HIP_TRY(hipGetLastError()); return 0; }
+    int fail(int code, const std::string& what) { return ::fail(code, what); }
+};
 
 // The host pair stages the whole buffer in the calling thread's device scratch (HostContext: grow-only, freed by
 // lz4hip_release_workspaces) and runs the device path on the thread's first kernel stream.
@@ -1617,341 +1468,6 @@ int stream_host_context(HostContext*& hc, hipStream_t& s)
     int rc = hc->pipe.init();
     if (rc) return rc;
     s = hc->pipe.s_k[0];
-    return 0;
-}
-
-// ---- wrapped messages (lz4hip_wrap.hpp) -------------------------------------------------------------------------------------
-// Framing kernels around launch_encode / launch_decode, the int64 scan and the copy routine of the stream path; scratch is the caller's.
-static_assert(sizeof(UnwrapInfo) == sizeof(lz4hip_unwrap_info_t) && offsetof(UnwrapInfo, error) == offsetof(lz4hip_unwrap_info_t, error),
-              "UnwrapInfo must mirror lz4hip_unwrap_info_t");
-static_assert(kWrapBadOffsets == LZ4HIP_E_ARGUMENT && kWrapSizeInvalid == LZ4HIP_WRAP_SIZE_INVALID &&
-              kWrapCorruptHeader == LZ4HIP_WRAP_CORRUPT_HEADER && kWrapCorruptBlock == LZ4HIP_WRAP_CORRUPT_BLOCK, "wrap statuses");
-
-int64_t scan_tiles(int64_t n) { return (n + kScanTile - 1) / kScanTile; }
-
-// wrap scratch: the encoder's output (message i at src_off[i]), its view of the offsets and lengths, its results, the scan's tile sums
-struct WrapScratch { int64_t comp, at, lens, enc, partial, total; };
-WrapScratch wrap_scratch(int64_t n, int64_t src_len)
-{
-    WrapScratch l;
-    int64_t at = 0;
-    l.comp = at;    at += a256(src_len);
-    l.at = at;      at += a256(8 * n);
-    l.lens = at;    at += a256(4 * n);
-    l.enc = at;     at += a256(4 * n);
-    l.partial = at; at += a256(8 * scan_tiles(n));
-    l.total = at;
-    return l;
-}
-
-// unwrap scratch: [min_bad, ncomp], the flags / table rows, the tile sums, then the table of up to n compressed messages
-int64_t unwrap_scratch(int64_t n) { return 256 + 4 * a256(8 * n) + a256(8 * scan_tiles(n)) + 4 * a256(4 * n); }
-UnwrapTables unwrap_tables(void* scratch, int64_t n)
-{
-    uint8_t* p = (uint8_t*)scratch;
-    UnwrapTables t;
-    const int64_t w8 = a256(8 * n), w4 = a256(4 * n);
-    t.n = n;
-    t.min_bad = (unsigned long long*)p;
-    t.ncomp = (int64_t*)(p + 8); p += 256;
-    t.cidx = (int64_t*)p; p += w8;
-    t.partial = (int64_t*)p; p += a256(8 * scan_tiles(n));
-    t.c_src_off = (int64_t*)p; p += w8;
-    t.c_dst_off = (int64_t*)p; p += w8;
-    t.c_msg = (int64_t*)p; p += w8;
-    t.c_src_len = (int32_t*)p; p += w4;
-    t.c_dst_cap = (int32_t*)p; p += w4;
-    t.c_result = (int32_t*)p; p += w4;
-    t.raw_len = (int32_t*)p;
-    return t;
-}
-
-int64_t wrap_bound(int64_t n, int64_t src_len) { return (src_len < 0 ? 0 : src_len) + kWrapHeader * (n < 0 ? 0 : n); }
-
-int wrap_encode(const void* src, int64_t src_len, const int64_t* src_off, int64_t n, int mode, void* dst, int64_t dst_cap, int64_t* dst_off,
-                int32_t* result, void* scratch, int64_t scratch_bytes, hipStream_t stream)
-{
-    if (src_len < 0 || n < 0 || !dst_off) return fail(LZ4HIP_E_ARGUMENT, "wrap: src_len < 0, n < 0 or dst_off is NULL");
-    if (mode != LZ4HIP_MODE_FAST && mode != LZ4HIP_MODE_HC) return fail(LZ4HIP_E_ARGUMENT, "mode must be LZ4HIP_MODE_FAST or LZ4HIP_MODE_HC");
-    if (n > 0x7FFFFFFF) return fail(LZ4HIP_E_ARGUMENT, "wrap: more than 2^31 - 1 messages");
-    if (dst_cap < wrap_bound(n, src_len)) return fail(LZ4HIP_E_ARGUMENT, "wrap: dst_cap < lz4hip_wrap_bound");
-    if (n == 0) { HIP_TRY(hipMemsetAsync(dst_off, 0, sizeof(int64_t), stream)); return 0; }
-    const WrapScratch l = wrap_scratch(n, src_len);
-    if (scratch_bytes < l.total) return fail(LZ4HIP_E_ARGUMENT, "wrap: scratch_bytes < lz4hip_wrap_scratch_bytes");
-    if ((src_len > 0 && !src) || !src_off || !dst || !scratch) return fail(LZ4HIP_E_ARGUMENT, "wrap: src, src_off, dst and scratch must be non-NULL");
-    uint8_t* const s = (uint8_t*)scratch;
-    int64_t* const at = (int64_t*)(s + l.at);
-    int32_t* const lens = (int32_t*)(s + l.lens);
-    int32_t* const enc = (int32_t*)(s + l.enc);
-    hipLaunchKernelGGL(wrap_lens_kernel, dim3(stream_grid(n)), dim3(kStreamThreads), 0, stream, src_off, n, src_len, at, lens);
-    HIP_TRY(hipGetLastError());
-    // Wrap: outputLength = inputLength per message, written at the message's own offset; src_len_all = 0 (no bound is known on the host)
-    lz4hip_batch_t b = {};
-    b.src = src; b.src_off = at; b.src_len = lens;
-    b.dst = s + l.comp; b.dst_off = at; b.dst_cap = lens;
-    b.src_len_all = 0; b.result = enc; b.n_blocks = n;
-    int rc = launch_encode(&b, mode, stream);
-    if (rc) return rc;
-    WrapArgs a;
-    a.src = (const uint8_t*)src; a.comp = s + l.comp; a.off = src_off; a.src_len = src_len; a.n = n; a.enc = enc; a.dst_off = dst_off;
-    hipLaunchKernelGGL(wrap_sizes_kernel, dim3(stream_grid(n)), dim3(kStreamThreads), 0, stream, a, result);
-    launch_scan(dst_off, n, (int64_t*)(s + l.partial), dst_off + n, stream);
-    WrapLayout layout = { a };
-    hipLaunchKernelGGL(wrap_pack_kernel, dim3(copy_grid(wrap_bound(n, src_len))), dim3(kStreamThreads), 0, stream, layout, (uint8_t*)dst, dst_cap);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-int unwrap_index(const void* src, int64_t src_len, const int64_t* src_off, int64_t n, int64_t* dst_off, int32_t* status,
-                 void* scratch, int64_t scratch_bytes, lz4hip_unwrap_info_t* info, hipStream_t stream)
-{
-    if (src_len < 0 || n < 0 || !dst_off || !info || !scratch) return fail(LZ4HIP_E_ARGUMENT, "unwrap index: negative size or NULL pointer");
-    if (n > 0 && (!src_off || !status || (src_len > 0 && !src))) return fail(LZ4HIP_E_ARGUMENT, "unwrap index: NULL pointer");
-    if (scratch_bytes < unwrap_scratch(n)) return fail(LZ4HIP_E_ARGUMENT, "unwrap index: scratch_bytes < lz4hip_unwrap_scratch_bytes");
-    const UnwrapTables t = unwrap_tables(scratch, n);
-    HIP_TRY(hipMemsetAsync(scratch, 0xFF, 8, stream));                 // min_bad = none
-    HIP_TRY(hipMemsetAsync(t.ncomp, 0, 8, stream));
-    UnwrapArgs a = { (const uint8_t*)src, src_off, src_len, n, dst_off, status };
-    if (n == 0) {
-        HIP_TRY(hipMemsetAsync(dst_off, 0, sizeof(int64_t), stream));
-    } else {
-        hipLaunchKernelGGL(unwrap_index_kernel, dim3(stream_grid(n)), dim3(kStreamThreads), 0, stream, a, t);
-        launch_scan(dst_off, n, t.partial, dst_off + n, stream);
-        launch_scan(t.cidx, n, t.partial, t.ncomp, stream);
-        hipLaunchKernelGGL(unwrap_compact_kernel, dim3(stream_grid(n)), dim3(kStreamThreads), 0, stream, a, t);
-    }
-    hipLaunchKernelGGL(unwrap_info_kernel, dim3(1), dim3(64), 0, stream, a, t, (UnwrapInfo*)info);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-int unwrap_decode(const void* src, int64_t src_len, const int64_t* src_off, int64_t n, const lz4hip_unwrap_info_t* info_host, void* scratch,
-                  int64_t scratch_bytes, void* dst, int64_t dst_cap, const int64_t* dst_off, int32_t* status, lz4hip_unwrap_info_t* info,
-                  hipStream_t stream)
-{
-    if (!info_host || !info || !scratch || !dst_off || src_len < 0 || n < 0) return fail(LZ4HIP_E_ARGUMENT, "unwrap decode: negative size or NULL pointer");
-    const lz4hip_unwrap_info_t h = *info_host;
-    if (h.messages != n || h.compressed < 0 || h.compressed > n || h.decoded_bytes < 0)
-        return fail(LZ4HIP_E_ARGUMENT, "unwrap decode: the info is not the index's of these n messages");
-    if (h.decoded_bytes > dst_cap) return fail(LZ4HIP_E_ARGUMENT, "unwrap decode: decoded_bytes > dst_cap");
-    if (n > 0 && (!src_off || !status || (src_len > 0 && !src))) return fail(LZ4HIP_E_ARGUMENT, "unwrap decode: NULL pointer");
-    if (h.decoded_bytes > 0 && !dst) return fail(LZ4HIP_E_ARGUMENT, "unwrap decode: dst is NULL");
-    if (scratch_bytes < unwrap_scratch(n)) return fail(LZ4HIP_E_ARGUMENT, "unwrap decode: scratch_bytes < lz4hip_unwrap_scratch_bytes");
-    if (h.compressed > 0x7FFFFFFF) return fail(LZ4HIP_E_ARGUMENT, "unwrap decode: more than 2^31 - 1 compressed messages");
-    const UnwrapTables t = unwrap_tables(scratch, n);
-    UnwrapArgs a = { (const uint8_t*)src, src_off, src_len, n, (int64_t*)dst_off, status };
-    if (h.compressed > 0) {
-        // Unwrap: Decode(..., outputLength, knownOutputLength: true) -- the compacted table IS the batch
-        lz4hip_batch_t b = {};
-        b.src = src; b.src_off = t.c_src_off; b.src_len = t.c_src_len;
-        b.dst = dst; b.dst_off = t.c_dst_off; b.dst_cap = t.c_dst_cap;
-        b.result = t.c_result; b.n_blocks = h.compressed;
-        int rc = launch_decode(&b, 1, stream);
-        if (rc) return rc;
-    }
-    if (n > h.compressed && h.decoded_bytes > 0) {
-        UnwrapRawLayout layout = { a, t };
-        hipLaunchKernelGGL(wrap_raw_copy_kernel, dim3(copy_grid(h.decoded_bytes)), dim3(kStreamThreads), 0, stream, layout, (uint8_t*)dst, h.decoded_bytes);
-        HIP_TRY(hipGetLastError());
-    }
-    if (h.compressed > 0)
-        hipLaunchKernelGGL(unwrap_check_kernel, dim3(stream_grid(h.compressed)), dim3(kStreamThreads), 0, stream, t, h.compressed, status);
-    hipLaunchKernelGGL(unwrap_info_kernel, dim3(1), dim3(64), 0, stream, a, t, (UnwrapInfo*)info);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-// ---- batches of LZ4Stream buffers (lz4hip_streams.hpp) ------------------------------------------------------------------------
-// Many independent streams per call: the framing kernels of the one-stream path and its scan and copy routine, around ONE
-// launch_encode / launch_decode over the chunks of all items; scratch is the caller's.
-static_assert(sizeof(StreamsInfo) == sizeof(lz4hip_streams_info_t) && offsetof(StreamsInfo, error) == offsetof(lz4hip_streams_info_t, error) &&
-              offsetof(StreamsInfo, first_error) == offsetof(lz4hip_streams_info_t, first_error), "StreamsInfo must mirror lz4hip_streams_info_t");
-static_assert(kStreamsBadOffsets == LZ4HIP_E_ARGUMENT, "streams statuses");
-constexpr unsigned kStreamsMaxWalkGroups = 1u << 22;          // one wavefront per item; more items than this share wavefronts
-
-// the chunk table's size: the host does not know the offsets, only that sum ceil(len_i / block) <= src_len / block + n
-int64_t streams_chunk_cap(int64_t n, int64_t src_len, int64_t block) { return src_len / block + n; }
-
-int64_t streams_bound(int64_t n, int64_t src_len, int32_t block_size)
-{
-    if (n < 0) n = 0;
-    if (src_len < 0) src_len = 0;
-    const int64_t block = stream_block(block_size);
-    return src_len + streams_chunk_cap(n, src_len, block) * (1 + 2 * varint_len((uint64_t)block));
-}
-
-// encode scratch: the encoder's output (every chunk at its own source position), the items' first chunks, the chunk total, the chunk
-// table (position, length, result, size / offset + the total), the scans' tile sums
-struct StreamsEncodeScratch { int64_t comp, first, total_at, c_at, c_len, result, offs, partial, total; };
-StreamsEncodeScratch streams_encode_scratch(int64_t n, int64_t src_len, int64_t block)
-{
-    const int64_t cap = streams_chunk_cap(n, src_len, block);
-    StreamsEncodeScratch l;
-    int64_t at = 0;
-    l.comp = at;     at += a256(src_len);
-    l.first = at;    at += a256(8 * n);
-    l.total_at = at; at += 256;
-    l.c_at = at;     at += a256(8 * cap);
-    l.c_len = at;    at += a256(4 * cap);
-    l.result = at;   at += a256(4 * cap);
-    l.offs = at;     at += a256(8 * (cap + 1));
-    l.partial = at;  at += a256(8 * scan_tiles(cap));           // (cap >= n: both scans fit)
-    l.total = at;
-    return l;
-}
-
-// decode scratch: [lowest failing item, chunk total, compressed total], three per-item arrays, the scans' tile sums, then the two
-// tables of max_chunks entries (those of the one-stream path plus each compressed chunk's item)
-int64_t streams_decode_scratch(int64_t n, int64_t max_chunks)
-{
-    if (n <= 0) return 0;
-    return 256 + 3 * a256(8 * n) + a256(8 * scan_tiles(n)) + 5 * a256(8 * max_chunks) + 5 * a256(4 * max_chunks);
-}
-StreamsTables streams_tables(void* scratch, int64_t n, int64_t max_chunks)
-{
-    uint8_t* p = (uint8_t*)scratch;
-    StreamsTables t;
-    const int64_t n8 = a256(8 * n), w8 = a256(8 * max_chunks), w4 = a256(4 * max_chunks);
-    t.t.max_chunks = max_chunks;
-    t.t.min_bad = (unsigned long long*)p;
-    t.totals = (int64_t*)(p + 8); p += 256;
-    t.chunk_base = (int64_t*)p; p += n8;
-    t.comp_base = (int64_t*)p; p += n8;
-    t.item_bad = (unsigned long long*)p; p += n8;
-    t.partial = (int64_t*)p; p += a256(8 * scan_tiles(n));
-    t.t.c_src_off = (int64_t*)p; p += w8;
-    t.t.c_dst_off = (int64_t*)p; p += w8;
-    t.t.c_hdr_off = (int64_t*)p; p += w8;
-    t.t.r_dst_off = (int64_t*)p; p += w8;
-    t.t.r_src_off = (int64_t*)p; p += w8;
-    t.t.c_src_len = (int32_t*)p; p += w4;
-    t.t.c_dst_cap = (int32_t*)p; p += w4;
-    t.t.c_result = (int32_t*)p; p += w4;
-    t.t.r_len = (int32_t*)p; p += w4;
-    t.c_item = (int32_t*)p;
-    return t;
-}
-
-int streams_encode(const void* src, int64_t src_len, const int64_t* src_off, int64_t n, int32_t block_size, int mode, void* dst, int64_t dst_cap,
-                   int64_t* dst_off, void* scratch, int64_t scratch_bytes, hipStream_t stream)
-{
-    if (src_len < 0 || n < 0 || !dst_off) return fail(LZ4HIP_E_ARGUMENT, "streams encode: src_len < 0, n < 0 or dst_off is NULL");
-    if (mode != LZ4HIP_MODE_FAST && mode != LZ4HIP_MODE_HC) return fail(LZ4HIP_E_ARGUMENT, "mode must be LZ4HIP_MODE_FAST or LZ4HIP_MODE_HC");
-    const int64_t block = stream_block(block_size), cap = streams_chunk_cap(n, src_len, block);
-    if (n > 0x7FFFFFFF || cap > 0x7FFFFFFF) return fail(LZ4HIP_E_ARGUMENT, "streams encode: more than 2^31 - 1 items or chunks");
-    if (n > 0 && dst_cap < streams_bound(n, src_len, block_size)) return fail(LZ4HIP_E_ARGUMENT, "streams encode: dst_cap < lz4hip_streams_bound");
-    if (n == 0 || src_len == 0) { HIP_TRY(hipMemsetAsync(dst_off, 0, sizeof(int64_t) * (size_t)(n + 1), stream)); return 0; }
-    const StreamsEncodeScratch l = streams_encode_scratch(n, src_len, block);
-    if (scratch_bytes < l.total) return fail(LZ4HIP_E_ARGUMENT, "streams encode: scratch_bytes < lz4hip_streams_encode_scratch_bytes");
-    if (!src || !src_off || !dst || !scratch) return fail(LZ4HIP_E_ARGUMENT, "streams encode: src, src_off, dst and scratch must be non-NULL");
-    uint8_t* const s = (uint8_t*)scratch;
-    int64_t* const partial = (int64_t*)(s + l.partial);
-    StreamsEncodeArgs a;
-    a.src = (const uint8_t*)src; a.comp = s + l.comp; a.off = src_off; a.src_len = src_len; a.n = n; a.cap = cap; a.block = (int32_t)block;
-    a.hc_flag = mode == LZ4HIP_MODE_HC ? kChunkHighCompression : 0u;
-    a.first = (int64_t*)(s + l.first); a.total = (const int64_t*)(s + l.total_at);
-    a.c_at = (int64_t*)(s + l.c_at); a.c_len = (int32_t*)(s + l.c_len); a.result = (const int32_t*)(s + l.result); a.offs = (int64_t*)(s + l.offs);
-    hipLaunchKernelGGL(streams_counts_kernel, dim3(stream_grid(n)), dim3(kStreamThreads), 0, stream, a);
-    launch_scan(a.first, n, partial, (int64_t*)(s + l.total_at), stream);
-    hipLaunchKernelGGL(streams_chunks_kernel, dim3(stream_grid(cap)), dim3(kStreamThreads), 0, stream, a);
-    HIP_TRY(hipGetLastError());
-    // FlushCurrentChunk: outputLength = inputLength per chunk, written at the chunk's own source position; src_len_all = the block size,
-    // the upper bound LZ4HC picks its kernels from
-    lz4hip_batch_t b = {};
-    b.src = src; b.src_off = a.c_at; b.src_len = a.c_len;
-    b.dst = s + l.comp; b.dst_off = a.c_at; b.dst_cap = a.c_len;
-    b.src_len_all = (int32_t)block; b.result = (int32_t*)(s + l.result); b.n_blocks = cap;
-    int rc = launch_encode(&b, mode, stream);
-    if (rc) return rc;
-    hipLaunchKernelGGL(streams_sizes_kernel, dim3(stream_grid(cap)), dim3(kStreamThreads), 0, stream, a);
-    launch_scan(a.offs, cap, partial, a.offs + cap, stream);
-    hipLaunchKernelGGL(streams_offsets_kernel, dim3(stream_grid(n + 1)), dim3(kStreamThreads), 0, stream, a, dst_off);
-    StreamsEncodeLayout layout = { a };
-    hipLaunchKernelGGL(streams_pack_kernel, dim3(copy_grid(streams_bound(n, src_len, block_size))), dim3(kStreamThreads), 0, stream,
-                       layout, (uint8_t*)dst, dst_cap);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-__global__ void streams_empty_info_kernel(StreamsInfo* info)
-{
-    if (threadIdx.x != 0) return;
-    StreamsInfo r = {};
-    r.first_error = r.error_offset = -1;
-    *info = r;
-}
-
-int streams_index(const void* src, int64_t src_len, const int64_t* src_off, int64_t n, int64_t max_chunks, int64_t* dst_off, int32_t* status,
-                  int64_t* error_offset, void* scratch, int64_t scratch_bytes, lz4hip_streams_info_t* info, hipStream_t stream)
-{
-    if (src_len < 0 || n < 0 || max_chunks < 0 || !dst_off || !info) return fail(LZ4HIP_E_ARGUMENT, "streams index: negative size or NULL pointer");
-    if (n > 0x7FFFFFFF) return fail(LZ4HIP_E_ARGUMENT, "streams index: more than 2^31 - 1 items");
-    if (n > 0 && (!src_off || !status || !error_offset || !scratch || (src_len > 0 && !src))) return fail(LZ4HIP_E_ARGUMENT, "streams index: NULL pointer");
-    if (scratch_bytes < streams_decode_scratch(n, max_chunks)) return fail(LZ4HIP_E_ARGUMENT, "streams index: scratch_bytes < lz4hip_streams_decode_scratch_bytes");
-    if (n == 0) {
-        HIP_TRY(hipMemsetAsync(dst_off, 0, sizeof(int64_t), stream));
-        hipLaunchKernelGGL(streams_empty_info_kernel, dim3(1), dim3(64), 0, stream, (StreamsInfo*)info);
-        HIP_TRY(hipGetLastError());
-        return 0;
-    }
-    const StreamsTables t = streams_tables(scratch, n, max_chunks);
-    HIP_TRY(hipMemsetAsync(scratch, 0, 256, stream));
-    HIP_TRY(hipMemsetAsync(scratch, 0xFF, 8, stream));                 // min_bad = none
-    StreamsDecodeArgs a = { (const uint8_t*)src, src_off, src_len, n, dst_off, status, error_offset };
-    const unsigned walkers = n < (int64_t)kStreamsMaxWalkGroups ? (unsigned)n : kStreamsMaxWalkGroups;
-    hipLaunchKernelGGL(streams_walk_kernel<false>, dim3(walkers), dim3(64), 0, stream, a, t);
-    launch_scan(dst_off, n, t.partial, dst_off + n, stream);
-    launch_scan(t.chunk_base, n, t.partial, t.totals, stream);
-    launch_scan(t.comp_base, n, t.partial, t.totals + 1, stream);
-    hipLaunchKernelGGL(streams_walk_kernel<true>, dim3(walkers), dim3(64), 0, stream, a, t);
-    hipLaunchKernelGGL(streams_info_kernel, dim3(1), dim3(64), 0, stream, a, t, (StreamsInfo*)info);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-int streams_decode(const void* src, int64_t src_len, const int64_t* src_off, int64_t n, const lz4hip_streams_info_t* info_host, int64_t max_chunks,
-                   void* scratch, int64_t scratch_bytes, void* dst, int64_t dst_cap, const int64_t* dst_off, int32_t* status, int64_t* error_offset,
-                   lz4hip_streams_info_t* info, hipStream_t stream)
-{
-    if (!info_host || !info || !dst_off || src_len < 0 || n < 0 || max_chunks < 0) return fail(LZ4HIP_E_ARGUMENT, "streams decode: negative size or NULL pointer");
-    const lz4hip_streams_info_t h = *info_host;
-    if (h.error == LZ4HIP_STREAM_TABLE_FULL) return fail(LZ4HIP_E_ARGUMENT, "streams decode: the index reported tables too small");
-    if (h.items != n || h.chunks < 0 || h.chunks > max_chunks || h.compressed_chunks < 0 || h.compressed_chunks > h.chunks || h.decoded_bytes < 0)
-        return fail(LZ4HIP_E_ARGUMENT, "streams decode: the info is not the index's of these n items and max_chunks entries");
-    if (h.decoded_bytes > dst_cap) return fail(LZ4HIP_E_ARGUMENT, "streams decode: decoded_bytes > dst_cap");
-    if (n > 0 && (!src_off || !status || !error_offset || !scratch || (src_len > 0 && !src))) return fail(LZ4HIP_E_ARGUMENT, "streams decode: NULL pointer");
-    if (h.decoded_bytes > 0 && !dst) return fail(LZ4HIP_E_ARGUMENT, "streams decode: dst is NULL");
-    if (scratch_bytes < streams_decode_scratch(n, max_chunks)) return fail(LZ4HIP_E_ARGUMENT, "streams decode: scratch_bytes < lz4hip_streams_decode_scratch_bytes");
-    if (h.compressed_chunks > 0x7FFFFFFF) return fail(LZ4HIP_E_ARGUMENT, "streams decode: more than 2^31 - 1 compressed chunks");
-    if (n == 0) {
-        hipLaunchKernelGGL(streams_empty_info_kernel, dim3(1), dim3(64), 0, stream, (StreamsInfo*)info);
-        HIP_TRY(hipGetLastError());
-        return 0;
-    }
-    const StreamsTables t = streams_tables(scratch, n, max_chunks);
-    StreamsDecodeArgs a = { (const uint8_t*)src, src_off, src_len, n, (int64_t*)dst_off, status, error_offset };
-    HIP_TRY(hipMemsetAsync(t.t.min_bad, 0xFF, 8, stream));
-    HIP_TRY(hipMemsetAsync(t.item_bad, 0xFF, (size_t)(8 * n), stream));
-    if (h.compressed_chunks > 0) {
-        // AcquireNextChunk: Decode(..., knownOutputLength: true) -- the compressed table of all items IS the batch
-        lz4hip_batch_t b = {};
-        b.src = src; b.src_off = t.t.c_src_off; b.src_len = t.t.c_src_len;
-        b.dst = dst; b.dst_off = t.t.c_dst_off; b.dst_cap = t.t.c_dst_cap;
-        b.result = t.t.c_result; b.n_blocks = h.compressed_chunks;
-        int rc = launch_decode(&b, 1, stream);
-        if (rc) return rc;
-        hipLaunchKernelGGL(streams_check_kernel, dim3(stream_grid(h.compressed_chunks)), dim3(kStreamThreads), 0, stream, t, h.compressed_chunks);
-        HIP_TRY(hipGetLastError());
-    }
-    if (h.chunks > h.compressed_chunks) {
-        RawLayout layout = { (const uint8_t*)src, t.t, h.chunks - h.compressed_chunks };
-        hipLaunchKernelGGL(stream_raw_copy_kernel, dim3(copy_grid(h.decoded_bytes)), dim3(kStreamThreads), 0, stream,
-                           layout, (uint8_t*)dst, h.decoded_bytes);
-        HIP_TRY(hipGetLastError());
-    }
-    hipLaunchKernelGGL(streams_finish_kernel, dim3(stream_grid(n)), dim3(kStreamThreads), 0, stream, a, t);
-    hipLaunchKernelGGL(streams_info_kernel, dim3(1), dim3(64), 0, stream, a, t, (StreamsInfo*)info);
-    HIP_TRY(hipGetLastError());
     return 0;
 }
 
@@ -2247,17 +1763,18 @@ int64_t lz4hip_stream_bound(int64_t src_len, int32_t block_size) { return stream
 
 int64_t lz4hip_stream_encode_scratch_bytes(int64_t src_len, int32_t block_size)
 {
-    return src_len <= 0 ? 0 : stream_encode_scratch(src_len, stream_block(block_size)).total;
+    return src_len <= 0 ? 0 : stream_encode_scratch(nullptr, src_len, stream_block(block_size)).bytes;
 }
 
-int64_t lz4hip_stream_decode_scratch_bytes(int64_t max_chunks) { return stream_decode_scratch(max_chunks < 0 ? 0 : max_chunks); }
+int64_t lz4hip_stream_decode_scratch_bytes(int64_t max_chunks) { return stream_decode_scratch_bytes(max_chunks < 0 ? 0 : max_chunks); }
 
 int lz4hip_stream_encode_device(const void* src, int64_t src_len, int32_t block_size, int mode, void* dst, int64_t dst_cap, int64_t* dst_len,
                                 void* scratch, int64_t scratch_bytes, void* stream)
 {
     int rc = ensure_device();
     if (rc) return rc;
-    return stream_encode(src, src_len, block_size, mode, dst, dst_cap, dst_len, scratch, scratch_bytes, (hipStream_t)stream);
+    HipBackend be = { (hipStream_t)stream };
+    return stream_encode(be, src, src_len, block_size, mode, dst, dst_cap, dst_len, scratch, scratch_bytes);
 }
 
 int lz4hip_stream_index_device(const void* src, int64_t src_len, int64_t max_chunks, void* scratch, int64_t scratch_bytes,
@@ -2265,7 +1782,8 @@ int lz4hip_stream_index_device(const void* src, int64_t src_len, int64_t max_chu
 {
     int rc = ensure_device();
     if (rc) return rc;
-    return stream_index(src, src_len, max_chunks, scratch, scratch_bytes, info, (hipStream_t)stream);
+    HipBackend be = { (hipStream_t)stream };
+    return stream_index(be, src, src_len, max_chunks, scratch, scratch_bytes, info);
 }
 
 int lz4hip_stream_decode_device(const void* src, const lz4hip_stream_info_t* info_host, int64_t max_chunks, void* scratch, int64_t scratch_bytes,
@@ -2273,7 +1791,8 @@ int lz4hip_stream_decode_device(const void* src, const lz4hip_stream_info_t* inf
 {
     int rc = ensure_device();
     if (rc) return rc;
-    return stream_decode(src, info_host, max_chunks, scratch, scratch_bytes, dst, dst_cap, info, (hipStream_t)stream);
+    HipBackend be = { (hipStream_t)stream };
+    return stream_decode(be, src, info_host, max_chunks, scratch, scratch_bytes, dst, dst_cap, info);
 }
 
 int lz4hip_stream_encode_host(const void* src, int64_t src_len, int32_t block_size, int mode, void* dst, int64_t dst_cap, int64_t* dst_len)
@@ -2289,11 +1808,14 @@ int lz4hip_stream_encode_host(const void* src, int64_t src_len, int32_t block_si
     if ((rc = stream_host_context(hc, s))) return rc;
     // device image: [source | stream | scratch | length]
     const int64_t scratch_bytes = lz4hip_stream_encode_scratch_bytes(src_len, block_size);
-    const int64_t out_at = a256(src_len), scratch_at = out_at + a256(bound), len_at = scratch_at + a256(scratch_bytes);
-    if ((rc = hc->scratch.reserve((size_t)(len_at + 256)))) return rc;
+    Carver image;
+    image.take(src_len);
+    const int64_t out_at = image.take(bound), scratch_at = image.take(scratch_bytes), len_at = image.take(256);
+    if ((rc = hc->scratch.reserve((size_t)image.at))) return rc;
     uint8_t* const d = (uint8_t*)hc->scratch.p;
     HIP_TRY(hipMemcpyAsync(d, src, (size_t)src_len, hipMemcpyHostToDevice, s));
-    if ((rc = stream_encode(d, src_len, block_size, mode, d + out_at, bound, (int64_t*)(d + len_at), d + scratch_at, scratch_bytes, s))) return rc;
+    HipBackend be = { s };
+    if ((rc = stream_encode(be, d, src_len, block_size, mode, d + out_at, bound, (int64_t*)(d + len_at), d + scratch_at, scratch_bytes))) return rc;
     int64_t n = 0;
     HIP_TRY(hipMemcpyAsync(&n, d + len_at, sizeof n, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
@@ -2316,13 +1838,16 @@ int lz4hip_stream_decode_host(const void* src, int64_t src_len, void* dst, int64
     lz4hip_stream_info_t h = {};
     uint8_t* d = nullptr;
     int64_t info_at = 0, out_at = 0, table_at = 0;
+    HipBackend be = { s };
     for (int attempt = 0;; attempt++) {
-        info_at = a256(src_len); out_at = info_at + 256; table_at = out_at + a256(out_bytes);
-        const int64_t table_bytes = stream_decode_scratch(max_chunks);
-        if ((rc = hc->scratch.reserve((size_t)(table_at + table_bytes)))) return rc;
+        const int64_t table_bytes = stream_decode_scratch_bytes(max_chunks);
+        Carver image;
+        image.take(src_len);
+        info_at = image.take(256); out_at = image.take(out_bytes); table_at = image.take(table_bytes);
+        if ((rc = hc->scratch.reserve((size_t)image.at))) return rc;
         d = (uint8_t*)hc->scratch.p;
         if (src_len > 0) HIP_TRY(hipMemcpyAsync(d, src, (size_t)src_len, hipMemcpyHostToDevice, s));
-        if ((rc = stream_index(d, src_len, max_chunks, d + table_at, table_bytes, (lz4hip_stream_info_t*)(d + info_at), s))) return rc;
+        if ((rc = stream_index(be, d, src_len, max_chunks, d + table_at, table_bytes, (lz4hip_stream_info_t*)(d + info_at)))) return rc;
         HIP_TRY(hipMemcpyAsync(&h, d + info_at, sizeof h, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
         if (attempt >= 2) break;
@@ -2334,8 +1859,8 @@ int lz4hip_stream_decode_host(const void* src, int64_t src_len, void* dst, int64
     *info = h;
     if (h.error == LZ4HIP_STREAM_TABLE_FULL) return fail(LZ4HIP_E_DEVICE, "stream decode: the header walk did not settle");
     if (h.decoded_bytes > dst_cap) return fail(LZ4HIP_E_ARGUMENT, "stream decode: dst_cap < decoded_bytes (reported in info->decoded_bytes)");
-    if ((rc = stream_decode(d, &h, max_chunks, d + table_at, stream_decode_scratch(max_chunks), d + out_at, out_bytes,
-                            (lz4hip_stream_info_t*)(d + info_at), s))) return rc;
+    if ((rc = stream_decode(be, d, &h, max_chunks, d + table_at, stream_decode_scratch_bytes(max_chunks), d + out_at, out_bytes,
+                            (lz4hip_stream_info_t*)(d + info_at)))) return rc;
     HIP_TRY(hipMemcpyAsync(info, d + info_at, sizeof *info, hipMemcpyDeviceToHost, s));
     if (h.decoded_bytes > 0) HIP_TRY(hipMemcpyAsync(dst, d + out_at, (size_t)h.decoded_bytes, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
@@ -2344,16 +1869,17 @@ int lz4hip_stream_decode_host(const void* src, int64_t src_len, void* dst, int64
 
 int64_t lz4hip_wrap_bound(int64_t n, int64_t src_len) { return wrap_bound(n, src_len); }
 
-int64_t lz4hip_wrap_scratch_bytes(int64_t n, int64_t src_len) { return n <= 0 ? 0 : wrap_scratch(n, src_len < 0 ? 0 : src_len).total; }
+int64_t lz4hip_wrap_scratch_bytes(int64_t n, int64_t src_len) { return n <= 0 ? 0 : wrap_scratch(nullptr, n, src_len < 0 ? 0 : src_len).bytes; }
 
-int64_t lz4hip_unwrap_scratch_bytes(int64_t n) { return unwrap_scratch(n < 0 ? 0 : n); }
+int64_t lz4hip_unwrap_scratch_bytes(int64_t n) { return unwrap_scratch_bytes(n < 0 ? 0 : n); }
 
 int lz4hip_wrap_device(const void* src, int64_t src_len, const int64_t* src_off, int64_t n, int mode, void* dst, int64_t dst_cap,
                        int64_t* dst_off, int32_t* result, void* scratch, int64_t scratch_bytes, void* stream)
 {
     int rc = ensure_device();
     if (rc) return rc;
-    return wrap_encode(src, src_len, src_off, n, mode, dst, dst_cap, dst_off, result, scratch, scratch_bytes, (hipStream_t)stream);
+    HipBackend be = { (hipStream_t)stream };
+    return wrap_encode(be, src, src_len, src_off, n, mode, dst, dst_cap, dst_off, result, scratch, scratch_bytes);
 }
 
 int lz4hip_unwrap_index_device(const void* src, int64_t src_len, const int64_t* src_off, int64_t n, int64_t* dst_off, int32_t* status,
@@ -2361,7 +1887,8 @@ int lz4hip_unwrap_index_device(const void* src, int64_t src_len, const int64_t* 
 {
     int rc = ensure_device();
     if (rc) return rc;
-    return unwrap_index(src, src_len, src_off, n, dst_off, status, scratch, scratch_bytes, info, (hipStream_t)stream);
+    HipBackend be = { (hipStream_t)stream };
+    return unwrap_index(be, src, src_len, src_off, n, dst_off, status, scratch, scratch_bytes, info);
 }
 
 int lz4hip_unwrap_decode_device(const void* src, int64_t src_len, const int64_t* src_off, int64_t n, const lz4hip_unwrap_info_t* info_host,
@@ -2370,7 +1897,8 @@ int lz4hip_unwrap_decode_device(const void* src, int64_t src_len, const int64_t*
 {
     int rc = ensure_device();
     if (rc) return rc;
-    return unwrap_decode(src, src_len, src_off, n, info_host, scratch, scratch_bytes, dst, dst_cap, dst_off, status, info, (hipStream_t)stream);
+    HipBackend be = { (hipStream_t)stream };
+    return unwrap_decode(be, src, src_len, src_off, n, info_host, scratch, scratch_bytes, dst, dst_cap, dst_off, status, info);
 }
 
 int lz4hip_wrap_host(const void* src, int64_t src_len, const int64_t* src_off, int64_t n, int mode, void* dst, int64_t dst_cap,
@@ -2388,14 +1916,17 @@ int lz4hip_wrap_host(const void* src, int64_t src_len, const int64_t* src_off, i
     if ((rc = stream_host_context(hc, s))) return rc;
     // device image: [source | offsets | output | output offsets | results | scratch]
     const int64_t scratch_bytes = lz4hip_wrap_scratch_bytes(n, src_len);
-    const int64_t off_at = a256(src_len), out_at = off_at + a256(8 * (n + 1)), doff_at = out_at + a256(bound),
-                  res_at = doff_at + a256(8 * (n + 1)), scratch_at = res_at + a256(4 * n);
-    if ((rc = hc->scratch.reserve((size_t)(scratch_at + scratch_bytes)))) return rc;
+    Carver image;
+    image.take(src_len);
+    const int64_t off_at = image.take(8 * (n + 1)), out_at = image.take(bound), doff_at = image.take(8 * (n + 1)), res_at = image.take(4 * n),
+                  scratch_at = image.take(scratch_bytes);
+    if ((rc = hc->scratch.reserve((size_t)image.at))) return rc;
     uint8_t* const d = (uint8_t*)hc->scratch.p;
     if (src_len > 0) HIP_TRY(hipMemcpyAsync(d, src, (size_t)src_len, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(d + off_at, src_off, (size_t)(8 * (n + 1)), hipMemcpyHostToDevice, s));
-    if ((rc = wrap_encode(d, src_len, (const int64_t*)(d + off_at), n, mode, d + out_at, bound, (int64_t*)(d + doff_at), (int32_t*)(d + res_at),
-                          d + scratch_at, scratch_bytes, s))) return rc;
+    HipBackend be = { s };
+    if ((rc = wrap_encode(be, d, src_len, (const int64_t*)(d + off_at), n, mode, d + out_at, bound, (int64_t*)(d + doff_at), (int32_t*)(d + res_at),
+                          d + scratch_at, scratch_bytes))) return rc;
     HIP_TRY(hipMemcpyAsync(dst_off, d + doff_at, (size_t)(8 * (n + 1)), hipMemcpyDeviceToHost, s));
     if (result) HIP_TRY(hipMemcpyAsync(result, d + res_at, (size_t)(4 * n), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
@@ -2416,9 +1947,12 @@ int lz4hip_unwrap_host(const void* src, int64_t src_len, const int64_t* src_off,
     hipStream_t s = nullptr;
     if ((rc = stream_host_context(hc, s))) return rc;
     // device image: [source | offsets | output offsets | statuses | info | scratch | output]; staged again if the output had to grow
-    const int64_t scratch_bytes = unwrap_scratch(n);
-    const int64_t off_at = a256(src_len), doff_at = off_at + a256(8 * (n + 1)), st_at = doff_at + a256(8 * (n + 1)),
-                  info_at = st_at + a256(4 * n), scratch_at = info_at + 256, out_at = scratch_at + a256(scratch_bytes);
+    const int64_t scratch_bytes = unwrap_scratch_bytes(n);
+    Carver image;
+    image.take(src_len);
+    const int64_t off_at = image.take(8 * (n + 1)), doff_at = image.take(8 * (n + 1)), st_at = image.take(4 * n), info_at = image.take(256),
+                  scratch_at = image.take(scratch_bytes), out_at = image.at;
+    HipBackend be = { s };
     int64_t out_bytes = dst_cap < 4 * src_len ? dst_cap : 4 * src_len;
     lz4hip_unwrap_info_t h = {};
     uint8_t* d = nullptr;
@@ -2427,8 +1961,8 @@ int lz4hip_unwrap_host(const void* src, int64_t src_len, const int64_t* src_off,
         d = (uint8_t*)hc->scratch.p;
         if (src_len > 0) HIP_TRY(hipMemcpyAsync(d, src, (size_t)src_len, hipMemcpyHostToDevice, s));
         HIP_TRY(hipMemcpyAsync(d + off_at, src_off, (size_t)(8 * (n + 1)), hipMemcpyHostToDevice, s));
-        if ((rc = unwrap_index(d, src_len, (const int64_t*)(d + off_at), n, (int64_t*)(d + doff_at), (int32_t*)(d + st_at), d + scratch_at,
-                               scratch_bytes, (lz4hip_unwrap_info_t*)(d + info_at), s))) return rc;
+        if ((rc = unwrap_index(be, d, src_len, (const int64_t*)(d + off_at), n, (int64_t*)(d + doff_at), (int32_t*)(d + st_at), d + scratch_at,
+                               scratch_bytes, (lz4hip_unwrap_info_t*)(d + info_at)))) return rc;
         HIP_TRY(hipMemcpyAsync(&h, d + info_at, sizeof h, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
         if (h.decoded_bytes <= out_bytes || h.decoded_bytes > dst_cap) break;
@@ -2441,8 +1975,8 @@ int lz4hip_unwrap_host(const void* src, int64_t src_len, const int64_t* src_off,
         HIP_TRY(hipStreamSynchronize(s));
         return fail(LZ4HIP_E_ARGUMENT, "unwrap: dst_cap < decoded_bytes (reported in info->decoded_bytes)");
     }
-    if ((rc = unwrap_decode(d, src_len, (const int64_t*)(d + off_at), n, &h, d + scratch_at, scratch_bytes, d + out_at, out_bytes,
-                            (const int64_t*)(d + doff_at), (int32_t*)(d + st_at), (lz4hip_unwrap_info_t*)(d + info_at), s))) return rc;
+    if ((rc = unwrap_decode(be, d, src_len, (const int64_t*)(d + off_at), n, &h, d + scratch_at, scratch_bytes, d + out_at, out_bytes,
+                            (const int64_t*)(d + doff_at), (int32_t*)(d + st_at), (lz4hip_unwrap_info_t*)(d + info_at)))) return rc;
     HIP_TRY(hipMemcpyAsync(info, d + info_at, sizeof *info, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(dst_off, d + doff_at, (size_t)(8 * (n + 1)), hipMemcpyDeviceToHost, s));
     if (n > 0) HIP_TRY(hipMemcpyAsync(status, d + st_at, (size_t)(4 * n), hipMemcpyDeviceToHost, s));
@@ -2455,17 +1989,18 @@ int64_t lz4hip_streams_bound(int64_t n, int64_t src_len, int32_t block_size) { r
 
 int64_t lz4hip_streams_encode_scratch_bytes(int64_t n, int64_t src_len, int32_t block_size)
 {
-    return n <= 0 ? 0 : streams_encode_scratch(n, src_len < 0 ? 0 : src_len, stream_block(block_size)).total;
+    return n <= 0 ? 0 : streams_encode_scratch(nullptr, n, src_len < 0 ? 0 : src_len, stream_block(block_size)).bytes;
 }
 
-int64_t lz4hip_streams_decode_scratch_bytes(int64_t n, int64_t max_chunks) { return streams_decode_scratch(n, max_chunks < 0 ? 0 : max_chunks); }
+int64_t lz4hip_streams_decode_scratch_bytes(int64_t n, int64_t max_chunks) { return streams_decode_scratch_bytes(n, max_chunks < 0 ? 0 : max_chunks); }
 
 int lz4hip_streams_encode_device(const void* src, int64_t src_len, const int64_t* src_off, int64_t n, int32_t block_size, int mode,
                                  void* dst, int64_t dst_cap, int64_t* dst_off, void* scratch, int64_t scratch_bytes, void* stream)
 {
     int rc = ensure_device();
     if (rc) return rc;
-    return streams_encode(src, src_len, src_off, n, block_size, mode, dst, dst_cap, dst_off, scratch, scratch_bytes, (hipStream_t)stream);
+    HipBackend be = { (hipStream_t)stream };
+    return streams_encode(be, src, src_len, src_off, n, block_size, mode, dst, dst_cap, dst_off, scratch, scratch_bytes);
 }
 
 int lz4hip_streams_index_device(const void* src, int64_t src_len, const int64_t* src_off, int64_t n, int64_t max_chunks, int64_t* dst_off,
@@ -2474,7 +2009,8 @@ int lz4hip_streams_index_device(const void* src, int64_t src_len, const int64_t*
 {
     int rc = ensure_device();
     if (rc) return rc;
-    return streams_index(src, src_len, src_off, n, max_chunks, dst_off, status, error_offset, scratch, scratch_bytes, info, (hipStream_t)stream);
+    HipBackend be = { (hipStream_t)stream };
+    return streams_index(be, src, src_len, src_off, n, max_chunks, dst_off, status, error_offset, scratch, scratch_bytes, info);
 }
 
 int lz4hip_streams_decode_device(const void* src, int64_t src_len, const int64_t* src_off, int64_t n, const lz4hip_streams_info_t* info_host,
@@ -2483,8 +2019,9 @@ int lz4hip_streams_decode_device(const void* src, int64_t src_len, const int64_t
 {
     int rc = ensure_device();
     if (rc) return rc;
-    return streams_decode(src, src_len, src_off, n, info_host, max_chunks, scratch, scratch_bytes, dst, dst_cap, dst_off, status, error_offset,
-                          info, (hipStream_t)stream);
+    HipBackend be = { (hipStream_t)stream };
+    return streams_decode(be, src, src_len, src_off, n, info_host, max_chunks, scratch, scratch_bytes, dst, dst_cap, dst_off, status, error_offset,
+                          info);
 }
 
 int lz4hip_streams_encode_host(const void* src, int64_t src_len, const int64_t* src_off, int64_t n, int32_t block_size, int mode,
@@ -2506,13 +2043,16 @@ int lz4hip_streams_encode_host(const void* src, int64_t src_len, const int64_t* 
     if ((rc = stream_host_context(hc, s))) return rc;
     // device image: [source | offsets | output | output offsets | scratch]
     const int64_t scratch_bytes = lz4hip_streams_encode_scratch_bytes(n, src_len, block_size);
-    const int64_t off_at = a256(src_len), out_at = off_at + a256(8 * (n + 1)), doff_at = out_at + a256(bound), scratch_at = doff_at + a256(8 * (n + 1));
-    if ((rc = hc->scratch.reserve((size_t)(scratch_at + scratch_bytes)))) return rc;
+    Carver image;
+    image.take(src_len);
+    const int64_t off_at = image.take(8 * (n + 1)), out_at = image.take(bound), doff_at = image.take(8 * (n + 1)), scratch_at = image.take(scratch_bytes);
+    if ((rc = hc->scratch.reserve((size_t)image.at))) return rc;
     uint8_t* const d = (uint8_t*)hc->scratch.p;
     HIP_TRY(hipMemcpyAsync(d, src, (size_t)src_len, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(d + off_at, src_off, (size_t)(8 * (n + 1)), hipMemcpyHostToDevice, s));
-    if ((rc = streams_encode(d, src_len, (const int64_t*)(d + off_at), n, block_size, mode, d + out_at, bound, (int64_t*)(d + doff_at),
-                             d + scratch_at, scratch_bytes, s))) return rc;
+    HipBackend be = { s };
+    if ((rc = streams_encode(be, d, src_len, (const int64_t*)(d + off_at), n, block_size, mode, d + out_at, bound, (int64_t*)(d + doff_at),
+                             d + scratch_at, scratch_bytes))) return rc;
     HIP_TRY(hipMemcpyAsync(dst_off, d + doff_at, (size_t)(8 * (n + 1)), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     const int64_t total = dst_off[n] < dst_cap ? dst_off[n] : dst_cap;
@@ -2540,20 +2080,25 @@ int lz4hip_streams_decode_host(const void* src, int64_t src_len, const int64_t* 
     if ((rc = stream_host_context(hc, s))) return rc;
     // device image: [source | offsets | output offsets | statuses | error offsets | info | output | tables]; indexed again after tables
     // that were too small or an image that had to grow
-    const int64_t off_at = a256(src_len), doff_at = off_at + a256(8 * (n + 1)), st_at = doff_at + a256(8 * (n + 1)), eo_at = st_at + a256(4 * n),
-                  info_at = eo_at + a256(8 * n), out_at = info_at + 256;
+    Carver image;
+    image.take(src_len);
+    const int64_t off_at = image.take(8 * (n + 1)), doff_at = image.take(8 * (n + 1)), st_at = image.take(4 * n), eo_at = image.take(8 * n),
+                  info_at = image.take(256), out_at = image.at;
+    HipBackend be = { s };
     int64_t max_chunks = src_len / 4096 + n + 16, out_bytes = dst_cap < 4 * src_len ? dst_cap : 4 * src_len, table_at = 0, table_bytes = 0;
     lz4hip_streams_info_t h = {};
     uint8_t* d = nullptr;
     for (int attempt = 0;; attempt++) {
-        table_at = out_at + a256(out_bytes);
-        table_bytes = streams_decode_scratch(n, max_chunks);
-        if ((rc = hc->scratch.reserve((size_t)(table_at + table_bytes)))) return rc;
+        table_bytes = streams_decode_scratch_bytes(n, max_chunks);
+        Carver tail = image;
+        tail.take(out_bytes);
+        table_at = tail.take(table_bytes);
+        if ((rc = hc->scratch.reserve((size_t)tail.at))) return rc;
         d = (uint8_t*)hc->scratch.p;
         if (src_len > 0) HIP_TRY(hipMemcpyAsync(d, src, (size_t)src_len, hipMemcpyHostToDevice, s));
         HIP_TRY(hipMemcpyAsync(d + off_at, src_off, (size_t)(8 * (n + 1)), hipMemcpyHostToDevice, s));
-        if ((rc = streams_index(d, src_len, (const int64_t*)(d + off_at), n, max_chunks, (int64_t*)(d + doff_at), (int32_t*)(d + st_at),
-                                (int64_t*)(d + eo_at), d + table_at, table_bytes, (lz4hip_streams_info_t*)(d + info_at), s))) return rc;
+        if ((rc = streams_index(be, d, src_len, (const int64_t*)(d + off_at), n, max_chunks, (int64_t*)(d + doff_at), (int32_t*)(d + st_at),
+                                (int64_t*)(d + eo_at), d + table_at, table_bytes, (lz4hip_streams_info_t*)(d + info_at)))) return rc;
         HIP_TRY(hipMemcpyAsync(&h, d + info_at, sizeof h, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
         if (attempt >= 2) break;
@@ -2571,8 +2116,8 @@ int lz4hip_streams_decode_host(const void* src, int64_t src_len, const int64_t* 
         HIP_TRY(hipStreamSynchronize(s));
         return fail(LZ4HIP_E_ARGUMENT, "streams decode: dst_cap < decoded_bytes (reported in info->decoded_bytes)");
     }
-    if ((rc = streams_decode(d, src_len, (const int64_t*)(d + off_at), n, &h, max_chunks, d + table_at, table_bytes, d + out_at, out_bytes,
-                             (const int64_t*)(d + doff_at), (int32_t*)(d + st_at), (int64_t*)(d + eo_at), (lz4hip_streams_info_t*)(d + info_at), s))) return rc;
+    if ((rc = streams_decode(be, d, src_len, (const int64_t*)(d + off_at), n, &h, max_chunks, d + table_at, table_bytes, d + out_at, out_bytes,
+                             (const int64_t*)(d + doff_at), (int32_t*)(d + st_at), (int64_t*)(d + eo_at), (lz4hip_streams_info_t*)(d + info_at)))) return rc;
     HIP_TRY(hipMemcpyAsync(info, d + info_at, sizeof *info, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(dst_off, d + doff_at, (size_t)(8 * (n + 1)), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(status, d + st_at, (size_t)(4 * n), hipMemcpyDeviceToHost, s));

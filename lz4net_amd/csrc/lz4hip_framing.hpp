@@ -1,0 +1,596 @@
+// lz4hip_framing.hpp -- host side of the framing paths (LZ4Stream buffers, wrapped messages, batches of LZ4Stream buffers): the scratch
+// layouts, the grids and the kernel sequences around the block codec, written ONCE for the library (lz4hip_api.hip, HipBackend) and for
+// the CPU emulator (tests/simt/emu_framing.hpp, EmuBackend).  Host code only: no kernel is defined here and nothing here calls the HIP
+// runtime or the emulator; everything that touches the device goes through the backend B, which has exactly
+//
+//     void launch(kernel, Grid, threads, args...)    the kernel on the call's stream, no dynamic LDS
+//     int  fill(p, byte, bytes)                      device bytes set to a value, in stream order
+//     int  encode(const lz4hip_batch_t*, mode)       the block encoder / decoder over a batch (launch_encode / launch_decode)
+//     int  decode(const lz4hip_batch_t*, known)
+//     int  last_error()                              0, or the failure of a launch since the last look
+//     int  fail(code, text)                          records the text, returns the code
+//
+// Each operation is a front (argument checks, the caller's scratch laid out into the kernels' argument structs) over a sequence
+// (*_run: structs in, launches out); the emulator's tests enter at either.
+#pragma once
+#include "lz4hip_stream.hpp"
+#include "lz4hip_wrap.hpp"
+#include "lz4hip_streams.hpp"
+
+#include "../../include/lz4hip.h"
+
+#include <cstddef>
+#include <cstring>
+
+namespace lz4hip {
+namespace framing {
+
+static_assert(sizeof(StreamInfo) == sizeof(lz4hip_stream_info_t) && offsetof(StreamInfo, error) == offsetof(lz4hip_stream_info_t, error),
+              "StreamInfo must mirror lz4hip_stream_info_t");
+static_assert(sizeof(UnwrapInfo) == sizeof(lz4hip_unwrap_info_t) && offsetof(UnwrapInfo, error) == offsetof(lz4hip_unwrap_info_t, error),
+              "UnwrapInfo must mirror lz4hip_unwrap_info_t");
+static_assert(kWrapBadOffsets == LZ4HIP_E_ARGUMENT && kWrapSizeInvalid == LZ4HIP_WRAP_SIZE_INVALID &&
+              kWrapCorruptHeader == LZ4HIP_WRAP_CORRUPT_HEADER && kWrapCorruptBlock == LZ4HIP_WRAP_CORRUPT_BLOCK, "wrap statuses");
+static_assert(sizeof(StreamsInfo) == sizeof(lz4hip_streams_info_t) && offsetof(StreamsInfo, error) == offsetof(lz4hip_streams_info_t, error) &&
+              offsetof(StreamsInfo, first_error) == offsetof(lz4hip_streams_info_t, first_error), "StreamsInfo must mirror lz4hip_streams_info_t");
+static_assert(kStreamsBadOffsets == LZ4HIP_E_ARGUMENT, "streams statuses");
+
+#define LZ4HIP_FRAMING_TRY(expr) do { if (int rc_ = (expr)) return rc_; } while (0)
+
+// ---- grids ---------------------------------------------------------------------------------------------------------------------
+// A launch's workgroups and the formula they came from: the emulator's tests replace each formula's answer by grids of 1 and 3.
+enum GridKind { kGridFixed, kGridItems, kGridCopy, kGridWalk };
+struct Grid { unsigned groups; GridKind kind; };
+
+constexpr unsigned kStreamMaxGroups = 8192;                   // grid-stride kernels: at most 32 workgroups of 256 per CU
+constexpr unsigned kStreamsMaxWalkGroups = 1u << 22;          // one wavefront per item; more items than this share wavefronts
+
+inline Grid fixed_grid(int64_t groups) { return { (unsigned)groups, kGridFixed }; }
+inline Grid stream_grid(int64_t items)
+{
+    const int64_t g = (items + kStreamThreads - 1) / kStreamThreads;
+    return { g < 1 ? 1u : (g > kStreamMaxGroups ? kStreamMaxGroups : (unsigned)g), kGridItems };
+}
+// the copy kernels: one workgroup per kCopySpan output bytes, at most kStreamMaxGroups (then each takes several spans)
+inline Grid copy_grid(int64_t bytes)
+{
+    const int64_t g = (bytes + kCopySpan - 1) / kCopySpan;
+    return { g < 1 ? 1u : (g > kStreamMaxGroups ? kStreamMaxGroups : (unsigned)g), kGridCopy };
+}
+inline Grid walk_grid(int64_t n) { return { n < (int64_t)kStreamsMaxWalkGroups ? (unsigned)n : kStreamsMaxWalkGroups, kGridWalk }; }
+
+// ---- sizes ---------------------------------------------------------------------------------------------------------------------
+inline int64_t stream_block(int32_t block_size) { return block_size < 16 ? 16 : block_size; }
+inline int64_t stream_chunks(int64_t len, int64_t block) { return len <= 0 ? 0 : (len - 1) / block + 1; }
+inline int64_t a256(int64_t v) { return (v + 255) / 256 * 256; }
+inline int64_t scan_tiles(int64_t n) { return (n + kScanTile - 1) / kScanTile; }
+
+inline int64_t stream_bound(int64_t len, int32_t block_size)
+{
+    if (len <= 0) return 0;
+    const int64_t block = stream_block(block_size);
+    return len + stream_chunks(len, block) * (1 + 2 * varint_len((uint64_t)block));
+}
+
+inline int64_t wrap_bound(int64_t n, int64_t src_len) { return (src_len < 0 ? 0 : src_len) + kWrapHeader * (n < 0 ? 0 : n); }
+
+// the chunk table's size: the host does not know the offsets, only that sum ceil(len_i / block) <= src_len / block + n
+inline int64_t streams_chunk_cap(int64_t n, int64_t src_len, int64_t block) { return src_len / block + n; }
+
+inline int64_t streams_bound(int64_t n, int64_t src_len, int32_t block_size)
+{
+    if (n < 0) n = 0;
+    if (src_len < 0) src_len = 0;
+    const int64_t block = stream_block(block_size);
+    return src_len + streams_chunk_cap(n, src_len, block) * (1 + 2 * varint_len((uint64_t)block));
+}
+
+// ---- scratch layouts -------------------------------------------------------------------------------------------------------------
+// Cuts a buffer into pieces that start at multiples of 256 bytes, in the order they are taken.  Every layout below is ONE walk of a
+// Carver: over the caller's scratch it yields the pointers, over no buffer at all (`*_bytes`) the size the caller must bring -- so a
+// piece cannot be added to one and forgotten in the other.  The *_host entry points cut their device images the same way.
+struct Carver {
+    uint8_t* base;
+    int64_t at;
+    explicit Carver(void* buffer = nullptr) : base((uint8_t*)buffer), at(0) {}
+    int64_t take(int64_t bytes) { const int64_t piece = at; at += a256(bytes); return piece; }    // the piece's offset
+    template <class T> T* take_as(int64_t bytes) { return (T*)((uintptr_t)base + (uintptr_t)take(bytes)); }
+};
+
+// stream encode: the encoder's output (chunk k at k * block), chunk lengths, results, sizes / offsets, tile sums of the scan
+struct StreamEncodeScratch { uint8_t* comp; int32_t* lens; int32_t* result; int64_t* offs; int64_t* partial; int64_t bytes; };
+inline StreamEncodeScratch stream_encode_scratch(void* scratch, int64_t len, int64_t block)
+{
+    const int64_t n = stream_chunks(len, block);
+    Carver c(scratch);
+    StreamEncodeScratch l;
+    l.comp = c.take_as<uint8_t>(len);
+    l.lens = c.take_as<int32_t>(4 * n);
+    l.result = c.take_as<int32_t>(4 * n);
+    l.offs = c.take_as<int64_t>(8 * n);
+    l.partial = c.take_as<int64_t>(8 * scan_tiles(n));
+    l.bytes = c.at;
+    return l;
+}
+
+// stream decode: the corrupt-block minimum, then the two tables of max_chunks entries
+inline StreamTables stream_tables(Carver& c, int64_t max_chunks)
+{
+    StreamTables t;
+    t.max_chunks = max_chunks;
+    t.min_bad = c.take_as<unsigned long long>(256);
+    t.c_src_off = c.take_as<int64_t>(8 * max_chunks);
+    t.c_dst_off = c.take_as<int64_t>(8 * max_chunks);
+    t.c_hdr_off = c.take_as<int64_t>(8 * max_chunks);
+    t.r_dst_off = c.take_as<int64_t>(8 * max_chunks);
+    t.r_src_off = c.take_as<int64_t>(8 * max_chunks);
+    t.c_src_len = c.take_as<int32_t>(4 * max_chunks);
+    t.c_dst_cap = c.take_as<int32_t>(4 * max_chunks);
+    t.c_result = c.take_as<int32_t>(4 * max_chunks);
+    t.r_len = c.take_as<int32_t>(4 * max_chunks);
+    return t;
+}
+inline int64_t stream_decode_scratch_bytes(int64_t max_chunks) { Carver c; stream_tables(c, max_chunks); return c.at; }
+
+// wrap: the encoder's output (message i at src_off[i]), its view of the offsets and lengths, its results, the scan's tile sums
+struct WrapScratch { uint8_t* comp; int64_t* at; int32_t* lens; int32_t* enc; int64_t* partial; int64_t bytes; };
+inline WrapScratch wrap_scratch(void* scratch, int64_t n, int64_t src_len)
+{
+    Carver c(scratch);
+    WrapScratch l;
+    l.comp = c.take_as<uint8_t>(src_len);
+    l.at = c.take_as<int64_t>(8 * n);
+    l.lens = c.take_as<int32_t>(4 * n);
+    l.enc = c.take_as<int32_t>(4 * n);
+    l.partial = c.take_as<int64_t>(8 * scan_tiles(n));
+    l.bytes = c.at;
+    return l;
+}
+
+// unwrap: [min_bad, ncomp], the flags / table rows, the tile sums, then the table of up to n compressed messages
+inline UnwrapTables unwrap_tables(Carver& c, int64_t n)
+{
+    UnwrapTables t;
+    t.n = n;
+    t.min_bad = c.take_as<unsigned long long>(256);
+    t.ncomp = (int64_t*)t.min_bad + 1;
+    t.cidx = c.take_as<int64_t>(8 * n);
+    t.partial = c.take_as<int64_t>(8 * scan_tiles(n));
+    t.c_src_off = c.take_as<int64_t>(8 * n);
+    t.c_dst_off = c.take_as<int64_t>(8 * n);
+    t.c_msg = c.take_as<int64_t>(8 * n);
+    t.c_src_len = c.take_as<int32_t>(4 * n);
+    t.c_dst_cap = c.take_as<int32_t>(4 * n);
+    t.c_result = c.take_as<int32_t>(4 * n);
+    t.raw_len = c.take_as<int32_t>(4 * n);
+    return t;
+}
+inline int64_t unwrap_scratch_bytes(int64_t n) { Carver c; unwrap_tables(c, n); return c.at; }
+
+// streams encode: the encoder's output (every chunk at its own source position), the items' first chunks, the chunk total, the chunk
+// table (position, length, result, size / offset + the total), the scans' tile sums
+struct StreamsEncodeScratch {
+    uint8_t* comp; int64_t* first; int64_t* total; int64_t* c_at; int32_t* c_len; int32_t* result; int64_t* offs; int64_t* partial; int64_t bytes;
+};
+inline StreamsEncodeScratch streams_encode_scratch(void* scratch, int64_t n, int64_t src_len, int64_t block)
+{
+    const int64_t cap = streams_chunk_cap(n, src_len, block);
+    Carver c(scratch);
+    StreamsEncodeScratch l;
+    l.comp = c.take_as<uint8_t>(src_len);
+    l.first = c.take_as<int64_t>(8 * n);
+    l.total = c.take_as<int64_t>(256);
+    l.c_at = c.take_as<int64_t>(8 * cap);
+    l.c_len = c.take_as<int32_t>(4 * cap);
+    l.result = c.take_as<int32_t>(4 * cap);
+    l.offs = c.take_as<int64_t>(8 * (cap + 1));
+    l.partial = c.take_as<int64_t>(8 * scan_tiles(cap));               // (cap >= n: both scans fit)
+    l.bytes = c.at;
+    return l;
+}
+
+// streams decode: [lowest failing item, chunk total, compressed total], three per-item arrays, the scans' tile sums, then the two
+// tables of max_chunks entries (those of the one-stream path plus each compressed chunk's item)
+inline StreamsTables streams_tables(Carver& c, int64_t n, int64_t max_chunks)
+{
+    StreamsTables t;
+    t.t.max_chunks = max_chunks;
+    t.t.min_bad = c.take_as<unsigned long long>(256);
+    t.totals = (int64_t*)t.t.min_bad + 1;
+    t.chunk_base = c.take_as<int64_t>(8 * n);
+    t.comp_base = c.take_as<int64_t>(8 * n);
+    t.item_bad = c.take_as<unsigned long long>(8 * n);
+    t.partial = c.take_as<int64_t>(8 * scan_tiles(n));
+    t.t.c_src_off = c.take_as<int64_t>(8 * max_chunks);
+    t.t.c_dst_off = c.take_as<int64_t>(8 * max_chunks);
+    t.t.c_hdr_off = c.take_as<int64_t>(8 * max_chunks);
+    t.t.r_dst_off = c.take_as<int64_t>(8 * max_chunks);
+    t.t.r_src_off = c.take_as<int64_t>(8 * max_chunks);
+    t.t.c_src_len = c.take_as<int32_t>(4 * max_chunks);
+    t.t.c_dst_cap = c.take_as<int32_t>(4 * max_chunks);
+    t.t.c_result = c.take_as<int32_t>(4 * max_chunks);
+    t.t.r_len = c.take_as<int32_t>(4 * max_chunks);
+    t.c_item = c.take_as<int32_t>(4 * max_chunks);
+    return t;
+}
+inline int64_t streams_decode_scratch_bytes(int64_t n, int64_t max_chunks)
+{
+    if (n <= 0) return 0;                                              // (no item: the calls touch no scratch)
+    Carver c;
+    streams_tables(c, n, max_chunks);
+    return c.at;
+}
+
+// ---- the scan --------------------------------------------------------------------------------------------------------------------
+// exclusive scan of x[0, n) in place, n > 0; the sum goes to *total (device); partial holds ceil(n / kScanTile) tile sums.  Reduce and
+// apply index their tile by blockIdx.x (no grid-stride loop): their grid is the tile count, whoever launches.
+template <class B>
+void launch_scan(B& be, int64_t* x, int64_t n, int64_t* partial, int64_t* total)
+{
+    const int64_t tiles = scan_tiles(n);
+    be.launch(stream_scan_reduce_kernel, fixed_grid(tiles), kStreamThreads, x, n, partial);
+    be.launch(stream_scan_partials_kernel, fixed_grid(1), kStreamThreads, partial, tiles, total);
+    be.launch(stream_scan_apply_kernel, fixed_grid(tiles), kStreamThreads, x, n, partial);
+}
+
+// ---- LZ4Stream buffers (lz4hip_stream.hpp) ------------------------------------------------------------------------------------------
+// a.comp and a.result are the block encoder's to write: chunk k at k * a.block
+template <class B>
+int stream_encode_run(B& be, const StreamEncodeArgs& a, int mode, int32_t* lens, int64_t* partial, uint8_t* dst, int64_t* dst_len)
+{
+    be.launch(stream_lens_kernel, stream_grid(a.n), kStreamThreads, lens, a.n, a.src_len, a.block);
+    LZ4HIP_FRAMING_TRY(be.last_error());
+    // FlushCurrentChunk: outputLength = inputLength per chunk; src_len_all = the block size, the upper bound LZ4HC picks its kernels from
+    lz4hip_batch_t b = {};
+    b.src = a.src; b.src_stride = a.block; b.src_len = lens;
+    b.dst = (void*)a.comp; b.dst_stride = a.block; b.dst_cap = lens;
+    b.src_len_all = a.block; b.result = (int32_t*)a.result; b.n_blocks = a.n;
+    LZ4HIP_FRAMING_TRY(be.encode(&b, mode));
+    be.launch(stream_sizes_kernel, stream_grid(a.n), kStreamThreads, a);
+    launch_scan(be, a.offs, a.n, partial, dst_len);
+    EncodeLayout layout = { a };
+    be.launch(stream_pack_kernel, copy_grid(stream_bound(a.src_len, a.block)), kStreamThreads, layout, dst, dst_len);
+    return be.last_error();
+}
+
+template <class B>
+int stream_encode(B& be, const void* src, int64_t src_len, int32_t block_size, int mode, void* dst, int64_t dst_cap, int64_t* dst_len,
+                  void* scratch, int64_t scratch_bytes)
+{
+    if (src_len < 0 || !dst_len) return be.fail(LZ4HIP_E_ARGUMENT, "stream encode: src_len < 0 or dst_len is NULL");
+    if (mode != LZ4HIP_MODE_FAST && mode != LZ4HIP_MODE_HC) return be.fail(LZ4HIP_E_ARGUMENT, "mode must be LZ4HIP_MODE_FAST or LZ4HIP_MODE_HC");
+    const int64_t block = stream_block(block_size), n = stream_chunks(src_len, block);
+    if (n > 0x7FFFFFFF) return be.fail(LZ4HIP_E_ARGUMENT, "stream encode: more than 2^31 - 1 chunks");
+    if (dst_cap < stream_bound(src_len, block_size)) return be.fail(LZ4HIP_E_ARGUMENT, "stream encode: dst_cap < lz4hip_stream_bound");
+    const StreamEncodeScratch l = stream_encode_scratch(scratch, src_len, block);
+    if (scratch_bytes < l.bytes) return be.fail(LZ4HIP_E_ARGUMENT, "stream encode: scratch_bytes < lz4hip_stream_encode_scratch_bytes");
+    if (n == 0) return be.fill(dst_len, 0, sizeof(int64_t));
+    if (!src || !dst || !scratch) return be.fail(LZ4HIP_E_ARGUMENT, "stream encode: src, dst and scratch must be non-NULL");
+    StreamEncodeArgs a;
+    a.src = (const uint8_t*)src; a.comp = l.comp; a.src_len = src_len; a.n = n; a.block = (int32_t)block;
+    a.hc_flag = mode == LZ4HIP_MODE_HC ? kChunkHighCompression : 0u; a.result = l.result; a.offs = l.offs;
+    return stream_encode_run(be, a, mode, l.lens, l.partial, (uint8_t*)dst, dst_len);
+}
+
+template <class B>
+int stream_index_run(B& be, const uint8_t* src, int64_t src_len, const StreamTables& t, StreamInfo* info)
+{
+    be.launch(stream_index_kernel, fixed_grid(1), 64, src, src_len, t, info);
+    return be.last_error();
+}
+
+template <class B>
+int stream_index(B& be, const void* src, int64_t src_len, int64_t max_chunks, void* scratch, int64_t scratch_bytes, lz4hip_stream_info_t* info)
+{
+    if (src_len < 0 || max_chunks < 0 || !info || !scratch || (src_len > 0 && !src))
+        return be.fail(LZ4HIP_E_ARGUMENT, "stream index: negative size or NULL pointer");
+    Carver c(scratch);
+    const StreamTables t = stream_tables(c, max_chunks);
+    if (scratch_bytes < c.at) return be.fail(LZ4HIP_E_ARGUMENT, "stream index: scratch_bytes < lz4hip_stream_decode_scratch_bytes");
+    return stream_index_run(be, (const uint8_t*)src, src_len, t, (StreamInfo*)info);
+}
+
+// h: what the index reported, read back by the host
+template <class B>
+int stream_decode_run(B& be, const uint8_t* src, const StreamInfo& h, const StreamTables& t, uint8_t* dst, StreamInfo* info)
+{
+    be.launch(stream_info_init_kernel, fixed_grid(1), 64, h, info, t.min_bad);
+    LZ4HIP_FRAMING_TRY(be.last_error());
+    if (h.compressed_chunks > 0) {
+        // AcquireNextChunk: Decode(..., knownOutputLength: true) -- the compressed table IS the batch
+        lz4hip_batch_t b = {};
+        b.src = src; b.src_off = t.c_src_off; b.src_len = t.c_src_len;
+        b.dst = dst; b.dst_off = t.c_dst_off; b.dst_cap = t.c_dst_cap;
+        b.result = t.c_result; b.n_blocks = h.compressed_chunks;
+        LZ4HIP_FRAMING_TRY(be.decode(&b, 1));
+        be.launch(stream_check_kernel, stream_grid(h.compressed_chunks), kStreamThreads, t, h.compressed_chunks);
+        LZ4HIP_FRAMING_TRY(be.last_error());
+    }
+    if (h.chunks > h.compressed_chunks) {
+        RawLayout layout = { src, t, h.chunks - h.compressed_chunks };
+        be.launch(stream_raw_copy_kernel, copy_grid(h.decoded_bytes), kStreamThreads, layout, dst, h.decoded_bytes);
+        LZ4HIP_FRAMING_TRY(be.last_error());
+    }
+    be.launch(stream_info_finish_kernel, fixed_grid(1), 64, info, t.min_bad);
+    return be.last_error();
+}
+
+template <class B>
+int stream_decode(B& be, const void* src, const lz4hip_stream_info_t* info_host, int64_t max_chunks, void* scratch, int64_t scratch_bytes,
+                  void* dst, int64_t dst_cap, lz4hip_stream_info_t* info)
+{
+    if (!info_host || !info || !scratch || max_chunks < 0) return be.fail(LZ4HIP_E_ARGUMENT, "stream decode: NULL pointer or max_chunks < 0");
+    const lz4hip_stream_info_t h = *info_host;
+    if (h.error != LZ4HIP_STREAM_OK && h.error != LZ4HIP_STREAM_END_OF_STREAM && h.error != LZ4HIP_STREAM_PASSES)
+        return be.fail(LZ4HIP_E_ARGUMENT, "stream decode: the index reported a table too small (or the info is not an index's)");
+    if (h.chunks < 0 || h.chunks > max_chunks || h.compressed_chunks < 0 || h.compressed_chunks > h.chunks || h.decoded_bytes < 0)
+        return be.fail(LZ4HIP_E_ARGUMENT, "stream decode: the info does not fit a table of max_chunks entries");
+    if (h.decoded_bytes > dst_cap) return be.fail(LZ4HIP_E_ARGUMENT, "stream decode: decoded_bytes > dst_cap");
+    if (h.chunks > 0 && (!src || !dst)) return be.fail(LZ4HIP_E_ARGUMENT, "stream decode: src and dst must be non-NULL");
+    Carver c(scratch);
+    const StreamTables t = stream_tables(c, max_chunks);
+    if (scratch_bytes < c.at) return be.fail(LZ4HIP_E_ARGUMENT, "stream decode: scratch_bytes < lz4hip_stream_decode_scratch_bytes");
+    if (h.compressed_chunks > 0x7FFFFFFF) return be.fail(LZ4HIP_E_ARGUMENT, "stream decode: more than 2^31 - 1 compressed chunks");
+    StreamInfo from_index;
+    memcpy(&from_index, &h, sizeof from_index);
+    return stream_decode_run(be, (const uint8_t*)src, from_index, t, (uint8_t*)dst, (StreamInfo*)info);
+}
+
+// ---- wrapped messages (lz4hip_wrap.hpp) ---------------------------------------------------------------------------------------------
+// a.comp and a.enc are the block encoder's to write: message i at a.off[i]
+template <class B>
+int wrap_encode_run(B& be, const WrapArgs& a, int mode, int64_t* at, int32_t* lens, int32_t* result, int64_t* partial, uint8_t* dst, int64_t dst_cap)
+{
+    be.launch(wrap_lens_kernel, stream_grid(a.n), kStreamThreads, a.off, a.n, a.src_len, at, lens);
+    LZ4HIP_FRAMING_TRY(be.last_error());
+    // Wrap: outputLength = inputLength per message, written at the message's own offset; src_len_all = 0 (no bound is known on the host)
+    lz4hip_batch_t b = {};
+    b.src = a.src; b.src_off = at; b.src_len = lens;
+    b.dst = (void*)a.comp; b.dst_off = at; b.dst_cap = lens;
+    b.src_len_all = 0; b.result = (int32_t*)a.enc; b.n_blocks = a.n;
+    LZ4HIP_FRAMING_TRY(be.encode(&b, mode));
+    be.launch(wrap_sizes_kernel, stream_grid(a.n), kStreamThreads, a, result);
+    launch_scan(be, a.dst_off, a.n, partial, a.dst_off + a.n);
+    WrapLayout layout = { a };
+    be.launch(wrap_pack_kernel, copy_grid(wrap_bound(a.n, a.src_len)), kStreamThreads, layout, dst, dst_cap);
+    return be.last_error();
+}
+
+template <class B>
+int wrap_encode(B& be, const void* src, int64_t src_len, const int64_t* src_off, int64_t n, int mode, void* dst, int64_t dst_cap, int64_t* dst_off,
+                int32_t* result, void* scratch, int64_t scratch_bytes)
+{
+    if (src_len < 0 || n < 0 || !dst_off) return be.fail(LZ4HIP_E_ARGUMENT, "wrap: src_len < 0, n < 0 or dst_off is NULL");
+    if (mode != LZ4HIP_MODE_FAST && mode != LZ4HIP_MODE_HC) return be.fail(LZ4HIP_E_ARGUMENT, "mode must be LZ4HIP_MODE_FAST or LZ4HIP_MODE_HC");
+    if (n > 0x7FFFFFFF) return be.fail(LZ4HIP_E_ARGUMENT, "wrap: more than 2^31 - 1 messages");
+    if (dst_cap < wrap_bound(n, src_len)) return be.fail(LZ4HIP_E_ARGUMENT, "wrap: dst_cap < lz4hip_wrap_bound");
+    if (n == 0) return be.fill(dst_off, 0, sizeof(int64_t));
+    const WrapScratch l = wrap_scratch(scratch, n, src_len);
+    if (scratch_bytes < l.bytes) return be.fail(LZ4HIP_E_ARGUMENT, "wrap: scratch_bytes < lz4hip_wrap_scratch_bytes");
+    if ((src_len > 0 && !src) || !src_off || !dst || !scratch) return be.fail(LZ4HIP_E_ARGUMENT, "wrap: src, src_off, dst and scratch must be non-NULL");
+    WrapArgs a;
+    a.src = (const uint8_t*)src; a.comp = l.comp; a.off = src_off; a.src_len = src_len; a.n = n; a.enc = l.enc; a.dst_off = dst_off;
+    return wrap_encode_run(be, a, mode, l.at, l.lens, result, l.partial, (uint8_t*)dst, dst_cap);
+}
+
+template <class B>
+int unwrap_index_run(B& be, const UnwrapArgs& a, const UnwrapTables& t, UnwrapInfo* info)
+{
+    LZ4HIP_FRAMING_TRY(be.fill(t.min_bad, 0xFF, 8));                   // min_bad = none
+    LZ4HIP_FRAMING_TRY(be.fill(t.ncomp, 0, 8));
+    if (a.n == 0) {
+        LZ4HIP_FRAMING_TRY(be.fill(a.dst_off, 0, sizeof(int64_t)));
+    } else {
+        be.launch(unwrap_index_kernel, stream_grid(a.n), kStreamThreads, a, t);
+        launch_scan(be, a.dst_off, a.n, t.partial, a.dst_off + a.n);
+        launch_scan(be, t.cidx, a.n, t.partial, t.ncomp);
+        be.launch(unwrap_compact_kernel, stream_grid(a.n), kStreamThreads, a, t);
+    }
+    be.launch(unwrap_info_kernel, fixed_grid(1), 64, a, t, info);
+    return be.last_error();
+}
+
+template <class B>
+int unwrap_index(B& be, const void* src, int64_t src_len, const int64_t* src_off, int64_t n, int64_t* dst_off, int32_t* status,
+                 void* scratch, int64_t scratch_bytes, lz4hip_unwrap_info_t* info)
+{
+    if (src_len < 0 || n < 0 || !dst_off || !info || !scratch) return be.fail(LZ4HIP_E_ARGUMENT, "unwrap index: negative size or NULL pointer");
+    if (n > 0 && (!src_off || !status || (src_len > 0 && !src))) return be.fail(LZ4HIP_E_ARGUMENT, "unwrap index: NULL pointer");
+    Carver c(scratch);
+    const UnwrapTables t = unwrap_tables(c, n);
+    if (scratch_bytes < c.at) return be.fail(LZ4HIP_E_ARGUMENT, "unwrap index: scratch_bytes < lz4hip_unwrap_scratch_bytes");
+    const UnwrapArgs a = { (const uint8_t*)src, src_off, src_len, n, dst_off, status };
+    return unwrap_index_run(be, a, t, (UnwrapInfo*)info);
+}
+
+// h: what the index reported, read back by the host; the tables are as the index left them
+template <class B>
+int unwrap_decode_run(B& be, const UnwrapArgs& a, const UnwrapTables& t, const UnwrapInfo& h, uint8_t* dst, UnwrapInfo* info)
+{
+    if (h.compressed > 0) {
+        // Unwrap: Decode(..., outputLength, knownOutputLength: true) -- the compacted table IS the batch
+        lz4hip_batch_t b = {};
+        b.src = a.src; b.src_off = t.c_src_off; b.src_len = t.c_src_len;
+        b.dst = dst; b.dst_off = t.c_dst_off; b.dst_cap = t.c_dst_cap;
+        b.result = t.c_result; b.n_blocks = h.compressed;
+        LZ4HIP_FRAMING_TRY(be.decode(&b, 1));
+    }
+    if (a.n > h.compressed && h.decoded_bytes > 0) {
+        UnwrapRawLayout layout = { a, t };
+        be.launch(wrap_raw_copy_kernel, copy_grid(h.decoded_bytes), kStreamThreads, layout, dst, h.decoded_bytes);
+        LZ4HIP_FRAMING_TRY(be.last_error());
+    }
+    if (h.compressed > 0) be.launch(unwrap_check_kernel, stream_grid(h.compressed), kStreamThreads, t, h.compressed, a.status);
+    be.launch(unwrap_info_kernel, fixed_grid(1), 64, a, t, info);
+    return be.last_error();
+}
+
+template <class B>
+int unwrap_decode(B& be, const void* src, int64_t src_len, const int64_t* src_off, int64_t n, const lz4hip_unwrap_info_t* info_host, void* scratch,
+                  int64_t scratch_bytes, void* dst, int64_t dst_cap, const int64_t* dst_off, int32_t* status, lz4hip_unwrap_info_t* info)
+{
+    if (!info_host || !info || !scratch || !dst_off || src_len < 0 || n < 0) return be.fail(LZ4HIP_E_ARGUMENT, "unwrap decode: negative size or NULL pointer");
+    const lz4hip_unwrap_info_t h = *info_host;
+    if (h.messages != n || h.compressed < 0 || h.compressed > n || h.decoded_bytes < 0)
+        return be.fail(LZ4HIP_E_ARGUMENT, "unwrap decode: the info is not the index's of these n messages");
+    if (h.decoded_bytes > dst_cap) return be.fail(LZ4HIP_E_ARGUMENT, "unwrap decode: decoded_bytes > dst_cap");
+    if (n > 0 && (!src_off || !status || (src_len > 0 && !src))) return be.fail(LZ4HIP_E_ARGUMENT, "unwrap decode: NULL pointer");
+    if (h.decoded_bytes > 0 && !dst) return be.fail(LZ4HIP_E_ARGUMENT, "unwrap decode: dst is NULL");
+    Carver c(scratch);
+    const UnwrapTables t = unwrap_tables(c, n);
+    if (scratch_bytes < c.at) return be.fail(LZ4HIP_E_ARGUMENT, "unwrap decode: scratch_bytes < lz4hip_unwrap_scratch_bytes");
+    if (h.compressed > 0x7FFFFFFF) return be.fail(LZ4HIP_E_ARGUMENT, "unwrap decode: more than 2^31 - 1 compressed messages");
+    const UnwrapArgs a = { (const uint8_t*)src, src_off, src_len, n, (int64_t*)dst_off, status };
+    UnwrapInfo from_index;
+    memcpy(&from_index, &h, sizeof from_index);
+    return unwrap_decode_run(be, a, t, from_index, (uint8_t*)dst, (UnwrapInfo*)info);
+}
+
+// ---- batches of LZ4Stream buffers (lz4hip_streams.hpp) --------------------------------------------------------------------------------
+// Many independent streams per call: the framing kernels of the one-stream path and its scan and copy routine, around ONE block
+// encoder / decoder call over the chunks of all items.  The encode sequence comes in two parts around the encoder: the chunk table
+// (a.first, *a.total, a.c_at, a.c_len), then -- a.comp and a.result written, every chunk at its own source position -- the pack.
+template <class B>
+int streams_encode_plan(B& be, const StreamsEncodeArgs& a, int64_t* partial)
+{
+    be.launch(streams_counts_kernel, stream_grid(a.n), kStreamThreads, a);
+    launch_scan(be, a.first, a.n, partial, (int64_t*)a.total);
+    be.launch(streams_chunks_kernel, stream_grid(a.cap), kStreamThreads, a);
+    return be.last_error();
+}
+
+template <class B>
+int streams_encode_pack(B& be, const StreamsEncodeArgs& a, int64_t* partial, int64_t* dst_off, uint8_t* dst, int64_t dst_cap)
+{
+    be.launch(streams_sizes_kernel, stream_grid(a.cap), kStreamThreads, a);
+    launch_scan(be, a.offs, a.cap, partial, a.offs + a.cap);
+    be.launch(streams_offsets_kernel, stream_grid(a.n + 1), kStreamThreads, a, dst_off);
+    StreamsEncodeLayout layout = { a };
+    be.launch(streams_pack_kernel, copy_grid(streams_bound(a.n, a.src_len, a.block)), kStreamThreads, layout, dst, dst_cap);
+    return be.last_error();
+}
+
+template <class B>
+int streams_encode(B& be, const void* src, int64_t src_len, const int64_t* src_off, int64_t n, int32_t block_size, int mode, void* dst,
+                   int64_t dst_cap, int64_t* dst_off, void* scratch, int64_t scratch_bytes)
+{
+    if (src_len < 0 || n < 0 || !dst_off) return be.fail(LZ4HIP_E_ARGUMENT, "streams encode: src_len < 0, n < 0 or dst_off is NULL");
+    if (mode != LZ4HIP_MODE_FAST && mode != LZ4HIP_MODE_HC) return be.fail(LZ4HIP_E_ARGUMENT, "mode must be LZ4HIP_MODE_FAST or LZ4HIP_MODE_HC");
+    const int64_t block = stream_block(block_size), cap = streams_chunk_cap(n, src_len, block);
+    if (n > 0x7FFFFFFF || cap > 0x7FFFFFFF) return be.fail(LZ4HIP_E_ARGUMENT, "streams encode: more than 2^31 - 1 items or chunks");
+    if (n > 0 && dst_cap < streams_bound(n, src_len, block_size)) return be.fail(LZ4HIP_E_ARGUMENT, "streams encode: dst_cap < lz4hip_streams_bound");
+    if (n == 0 || src_len == 0) return be.fill(dst_off, 0, sizeof(int64_t) * (size_t)(n + 1));
+    const StreamsEncodeScratch l = streams_encode_scratch(scratch, n, src_len, block);
+    if (scratch_bytes < l.bytes) return be.fail(LZ4HIP_E_ARGUMENT, "streams encode: scratch_bytes < lz4hip_streams_encode_scratch_bytes");
+    if (!src || !src_off || !dst || !scratch) return be.fail(LZ4HIP_E_ARGUMENT, "streams encode: src, src_off, dst and scratch must be non-NULL");
+    StreamsEncodeArgs a;
+    a.src = (const uint8_t*)src; a.comp = l.comp; a.off = src_off; a.src_len = src_len; a.n = n; a.cap = cap; a.block = (int32_t)block;
+    a.hc_flag = mode == LZ4HIP_MODE_HC ? kChunkHighCompression : 0u;
+    a.first = l.first; a.total = l.total; a.c_at = l.c_at; a.c_len = l.c_len; a.result = l.result; a.offs = l.offs;
+    LZ4HIP_FRAMING_TRY(streams_encode_plan(be, a, l.partial));
+    // FlushCurrentChunk: outputLength = inputLength per chunk, written at the chunk's own source position; src_len_all = the block size,
+    // the upper bound LZ4HC picks its kernels from
+    lz4hip_batch_t b = {};
+    b.src = src; b.src_off = a.c_at; b.src_len = a.c_len;
+    b.dst = l.comp; b.dst_off = a.c_at; b.dst_cap = a.c_len;
+    b.src_len_all = (int32_t)block; b.result = l.result; b.n_blocks = cap;
+    LZ4HIP_FRAMING_TRY(be.encode(&b, mode));
+    return streams_encode_pack(be, a, l.partial, dst_off, (uint8_t*)dst, dst_cap);
+}
+
+// no item: no table, nothing to walk
+template <class B>
+int streams_empty_info(B& be, StreamsInfo* info)
+{
+    be.launch(streams_empty_info_kernel, fixed_grid(1), 64, info);
+    return be.last_error();
+}
+
+template <class B>
+int streams_index_run(B& be, const StreamsDecodeArgs& a, const StreamsTables& t, StreamsInfo* info)
+{
+    LZ4HIP_FRAMING_TRY(be.fill(t.totals, 0, 16));
+    LZ4HIP_FRAMING_TRY(be.fill(t.t.min_bad, 0xFF, 8));                 // min_bad = none
+    be.launch(streams_walk_kernel<false>, walk_grid(a.n), 64, a, t);
+    launch_scan(be, a.dst_off, a.n, t.partial, a.dst_off + a.n);
+    launch_scan(be, t.chunk_base, a.n, t.partial, t.totals);
+    launch_scan(be, t.comp_base, a.n, t.partial, t.totals + 1);
+    be.launch(streams_walk_kernel<true>, walk_grid(a.n), 64, a, t);
+    be.launch(streams_info_kernel, fixed_grid(1), 64, a, t, info);
+    return be.last_error();
+}
+
+template <class B>
+int streams_index(B& be, const void* src, int64_t src_len, const int64_t* src_off, int64_t n, int64_t max_chunks, int64_t* dst_off, int32_t* status,
+                  int64_t* error_offset, void* scratch, int64_t scratch_bytes, lz4hip_streams_info_t* info)
+{
+    if (src_len < 0 || n < 0 || max_chunks < 0 || !dst_off || !info) return be.fail(LZ4HIP_E_ARGUMENT, "streams index: negative size or NULL pointer");
+    if (n > 0x7FFFFFFF) return be.fail(LZ4HIP_E_ARGUMENT, "streams index: more than 2^31 - 1 items");
+    if (n > 0 && (!src_off || !status || !error_offset || !scratch || (src_len > 0 && !src))) return be.fail(LZ4HIP_E_ARGUMENT, "streams index: NULL pointer");
+    if (scratch_bytes < streams_decode_scratch_bytes(n, max_chunks))
+        return be.fail(LZ4HIP_E_ARGUMENT, "streams index: scratch_bytes < lz4hip_streams_decode_scratch_bytes");
+    if (n == 0) {
+        LZ4HIP_FRAMING_TRY(be.fill(dst_off, 0, sizeof(int64_t)));
+        return streams_empty_info(be, (StreamsInfo*)info);
+    }
+    Carver c(scratch);
+    const StreamsTables t = streams_tables(c, n, max_chunks);
+    const StreamsDecodeArgs a = { (const uint8_t*)src, src_off, src_len, n, dst_off, status, error_offset };
+    return streams_index_run(be, a, t, (StreamsInfo*)info);
+}
+
+// h: what the index reported, read back by the host; the tables are as the index left them
+template <class B>
+int streams_decode_run(B& be, const StreamsDecodeArgs& a, const StreamsTables& t, const StreamsInfo& h, uint8_t* dst, StreamsInfo* info)
+{
+    LZ4HIP_FRAMING_TRY(be.fill(t.t.min_bad, 0xFF, 8));
+    LZ4HIP_FRAMING_TRY(be.fill(t.item_bad, 0xFF, (size_t)(8 * a.n)));
+    if (h.compressed_chunks > 0) {
+        // AcquireNextChunk: Decode(..., knownOutputLength: true) -- the compressed table of all items IS the batch
+        lz4hip_batch_t b = {};
+        b.src = a.src; b.src_off = t.t.c_src_off; b.src_len = t.t.c_src_len;
+        b.dst = dst; b.dst_off = t.t.c_dst_off; b.dst_cap = t.t.c_dst_cap;
+        b.result = t.t.c_result; b.n_blocks = h.compressed_chunks;
+        LZ4HIP_FRAMING_TRY(be.decode(&b, 1));
+        be.launch(streams_check_kernel, stream_grid(h.compressed_chunks), kStreamThreads, t, h.compressed_chunks);
+        LZ4HIP_FRAMING_TRY(be.last_error());
+    }
+    if (h.chunks > h.compressed_chunks) {
+        RawLayout layout = { a.src, t.t, h.chunks - h.compressed_chunks };
+        be.launch(stream_raw_copy_kernel, copy_grid(h.decoded_bytes), kStreamThreads, layout, dst, h.decoded_bytes);
+        LZ4HIP_FRAMING_TRY(be.last_error());
+    }
+    be.launch(streams_finish_kernel, stream_grid(a.n), kStreamThreads, a, t);
+    be.launch(streams_info_kernel, fixed_grid(1), 64, a, t, info);
+    return be.last_error();
+}
+
+template <class B>
+int streams_decode(B& be, const void* src, int64_t src_len, const int64_t* src_off, int64_t n, const lz4hip_streams_info_t* info_host,
+                   int64_t max_chunks, void* scratch, int64_t scratch_bytes, void* dst, int64_t dst_cap, const int64_t* dst_off, int32_t* status,
+                   int64_t* error_offset, lz4hip_streams_info_t* info)
+{
+    if (!info_host || !info || !dst_off || src_len < 0 || n < 0 || max_chunks < 0) return be.fail(LZ4HIP_E_ARGUMENT, "streams decode: negative size or NULL pointer");
+    const lz4hip_streams_info_t h = *info_host;
+    if (h.error == LZ4HIP_STREAM_TABLE_FULL) return be.fail(LZ4HIP_E_ARGUMENT, "streams decode: the index reported tables too small");
+    if (h.items != n || h.chunks < 0 || h.chunks > max_chunks || h.compressed_chunks < 0 || h.compressed_chunks > h.chunks || h.decoded_bytes < 0)
+        return be.fail(LZ4HIP_E_ARGUMENT, "streams decode: the info is not the index's of these n items and max_chunks entries");
+    if (h.decoded_bytes > dst_cap) return be.fail(LZ4HIP_E_ARGUMENT, "streams decode: decoded_bytes > dst_cap");
+    if (n > 0 && (!src_off || !status || !error_offset || !scratch || (src_len > 0 && !src))) return be.fail(LZ4HIP_E_ARGUMENT, "streams decode: NULL pointer");
+    if (h.decoded_bytes > 0 && !dst) return be.fail(LZ4HIP_E_ARGUMENT, "streams decode: dst is NULL");
+    if (scratch_bytes < streams_decode_scratch_bytes(n, max_chunks))
+        return be.fail(LZ4HIP_E_ARGUMENT, "streams decode: scratch_bytes < lz4hip_streams_decode_scratch_bytes");
+    if (h.compressed_chunks > 0x7FFFFFFF) return be.fail(LZ4HIP_E_ARGUMENT, "streams decode: more than 2^31 - 1 compressed chunks");
+    if (n == 0) return streams_empty_info(be, (StreamsInfo*)info);
+    Carver c(scratch);
+    const StreamsTables t = streams_tables(c, n, max_chunks);
+    const StreamsDecodeArgs a = { (const uint8_t*)src, src_off, src_len, n, (int64_t*)dst_off, status, error_offset };
+    StreamsInfo from_index;
+    memcpy(&from_index, &h, sizeof from_index);
+    return streams_decode_run(be, a, t, from_index, (uint8_t*)dst, (StreamsInfo*)info);
+}
+
+#undef LZ4HIP_FRAMING_TRY
+
+}  // namespace framing
+}  // namespace lz4hip

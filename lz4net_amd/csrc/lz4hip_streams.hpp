@@ -248,4 +248,13 @@ __global__ void __launch_bounds__(64) streams_info_kernel(StreamsDecodeArgs a, S
     *info = r;
 }
 
+// the info of a batch without items (no table to read it from)
+__global__ void streams_empty_info_kernel(StreamsInfo* info)
+{
+    if (threadIdx.x != 0) return;
+    StreamsInfo r = {};
+    r.first_error = r.error_offset = -1;
+    *info = r;
+}
+
 }  // namespace lz4hip

@@ -240,9 +240,21 @@ def framing():
             "emu_streams_pack": [ptr, ptr, ptr, ptr, i64, i64, i32, i32],
             "emu_streams_index": [ptr, ptr, ptr, i32],
             "emu_streams_decode": [ptr, ptr, ptr, ptr, ptr, ptr, ptr, i32, i32],
+            # the whole functions of lz4hip_framing.hpp: the library's arguments, then the codec's stand-in (results, bytes) and the grids
+            "emu_lib_stream_encode": [ptr, i64, i32, i32, ptr, i64, ptr, ptr, i64, ptr, ptr, i32, i32],
+            "emu_lib_stream_index": [ptr, i64, i64, ptr, i64, ptr],
+            "emu_lib_stream_decode": [ptr, ptr, i64, ptr, i64, ptr, i64, ptr, ptr, ptr, i32, i32],
+            "emu_lib_wrap": [ptr, i64, ptr, i64, i32, ptr, i64, ptr, ptr, ptr, i64, ptr, ptr, i32, i32],
+            "emu_lib_unwrap_index": [ptr, i64, ptr, i64, ptr, ptr, ptr, i64, ptr, i32],
+            "emu_lib_unwrap_decode": [ptr, i64, ptr, i64, ptr, ptr, i64, ptr, i64, ptr, ptr, ptr, ptr, ptr, i32, i32],
+            "emu_lib_streams_encode": [ptr, i64, ptr, i64, i32, i32, ptr, i64, ptr, ptr, i64, ptr, ptr, i32, i32],
+            "emu_lib_streams_index": [ptr, i64, ptr, i64, i64, ptr, ptr, ptr, ptr, i64, ptr, i32],
+            "emu_lib_streams_decode": [ptr, i64, ptr, i64, ptr, i64, ptr, i64, ptr, i64, ptr, ptr, ptr, ptr, ptr, ptr, i32, i32],
         }.items():
             getattr(L, name).argtypes = args
-            getattr(L, name).restype = C.c_int if name in ("emu_stream_decode", "emu_streams_decode") else None
+            getattr(L, name).restype = C.c_int if name in ("emu_stream_decode", "emu_streams_decode") or name.startswith("emu_lib_") else None
+        L.emu_scratch_bytes.argtypes = [i32, i64, i64, i64]
+        L.emu_scratch_bytes.restype = C.c_int64
         for name in ("emu_items_grid", "emu_copy_grid", "emu_walk_grid"):
             getattr(L, name).argtypes = [i64]
             getattr(L, name).restype = C.c_int

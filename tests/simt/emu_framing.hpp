@@ -1,61 +1,72 @@
 // emu_framing.hpp -- TEST INFRASTRUCTURE ONLY, included by emu_kernels.cpp.
 // C entry points that run the framing kernels (lz4hip_stream.hpp, lz4hip_wrap.hpp, lz4hip_streams.hpp) under the SIMT emulator
-// for tests/test_simt_framing.py: single kernels, and the kernel sequences of lz4hip_api.hip with the block codec step replaced
-// by arrays the test hands in.  The argument structs are passed by pointer; tests/emu_helpers.py mirrors them with ctypes and
-// checks the sizes against emu_framing_sizeof().  A grid argument of 0 means "the product's formula".
+// for tests/test_simt_framing.py: single kernels, and the library's own host code for the framing paths (lz4hip_framing.hpp: layouts,
+// grids and kernel sequences) over EmuBackend, with the block codec step replaced by arrays the test hands in.  The argument structs
+// are passed by pointer; tests/emu_helpers.py mirrors them with ctypes and checks the sizes against emu_framing_sizeof().  A grid
+// argument of 0 means "the library's formula".
 #pragma once
+#include "lz4hip_framing.hpp"
+
+#include <string>
+#include <tuple>
 
 namespace emu_framing {
 
 using namespace lz4hip;
+using namespace lz4hip::framing;
 
-constexpr size_t kScanLds = kStreamThreads * 8;
-constexpr unsigned kStreamMaxGroups = 8192;        // lz4hip_api.hip: "constexpr unsigned kStreamMaxGroups = 8192;"
+// a kernel and its arguments, as the closure simt::launch runs in every lane
+template <class... P>
+struct KernelCall {
+    void (*kernel)(P...);
+    std::tuple<P...> args;
+    void operator()() const { std::apply(kernel, args); }
+};
 
-// lz4hip_api.hip, stream_grid(): "const int64_t g = (items + kStreamThreads - 1) / kStreamThreads;
-//                                 return g < 1 ? 1u : (g > kStreamMaxGroups ? kStreamMaxGroups : (unsigned)g);"
-static unsigned items_grid(int64_t items, int grid)
-{
-    if (grid > 0) return (unsigned)grid;
-    const int64_t g = (items + kStreamThreads - 1) / kStreamThreads;
-    return g < 1 ? 1u : (g > kStreamMaxGroups ? kStreamMaxGroups : (unsigned)g);
-}
+// The device of lz4hip_framing.hpp's sequences, faked: the emulator's launcher, plain stores, and a block codec that hands out what
+// the test computed.
+struct EmuBackend {
+    int grid_items = 0, grid_copy = 0, grid_walk = 0;       // the test's grid for each formula; 0 = the formula's own
+    const int32_t* results = nullptr;                        // the block codec's stand-in: row j of a batch gets results[j] ...
+    const uint8_t* bytes = nullptr;                          // ... and its output bytes from here, at the row's own output offset
+    std::string error;
 
-// lz4hip_api.hip, copy_grid(): "const int64_t g = (bytes + kCopySpan - 1) / kCopySpan;
-//                               return g < 1 ? 1u : (g > kStreamMaxGroups ? kStreamMaxGroups : (unsigned)g);"
-// `bytes` is what the product passes there: the bound for the packs, decoded_bytes for the raw copies.
-static unsigned copy_grid(int64_t bytes, int grid)
-{
-    if (grid > 0) return (unsigned)grid;
-    const int64_t g = (bytes + kCopySpan - 1) / kCopySpan;
-    return g < 1 ? 1u : (g > kStreamMaxGroups ? kStreamMaxGroups : (unsigned)g);
-}
-
-// lz4hip_api.hip, streams_index(): "const unsigned walkers = n < (int64_t)kStreamsMaxWalkGroups ? (unsigned)n : kStreamsMaxWalkGroups;"
-// with "constexpr unsigned kStreamsMaxWalkGroups = 1u << 22;"
-static unsigned walk_grid(int64_t n, int grid)
-{
-    if (grid > 0) return (unsigned)grid;
-    return n < (int64_t)(1u << 22) ? (unsigned)n : (1u << 22);
-}
-
-// lz4hip_api.hip, launch_scan(): the three kernels, "dim3((unsigned)tiles)" / "dim3(1)" / "dim3((unsigned)tiles)".  Reduce and apply
-// index their tile by blockIdx.x (no grid-stride loop), so the scan has no grid parameter.
-static void scan(int64_t* x, int64_t n, int64_t* partial, int64_t* total)
-{
-    const int64_t tiles = (n + kScanTile - 1) / kScanTile;
-    simt::launch(dim3((unsigned)tiles), dim3(kStreamThreads), kScanLds, [=] { stream_scan_reduce_kernel(x, n, partial); });
-    simt::launch(dim3(1), dim3(kStreamThreads), kScanLds, [=] { stream_scan_partials_kernel(partial, tiles, total); });
-    simt::launch(dim3((unsigned)tiles), dim3(kStreamThreads), kScanLds, [=] { stream_scan_apply_kernel(x, n, partial); });
-}
-
-// the block decoder's stand-in: row j of the compressed table gets the caller's result and the caller's bytes
-static void fake_decode(const StreamTables& t, int64_t ncomp, const int32_t* results, const uint8_t* decoded, uint8_t* dst)
-{
-    for (int64_t j = 0; j < ncomp; j++) {
-        t.c_result[j] = results[j];
-        if (t.c_dst_cap[j] > 0) memcpy(dst + t.c_dst_off[j], decoded + t.c_dst_off[j], (size_t)t.c_dst_cap[j]);
+    // the emulator serves LZ4HIP_STATIC_LDS from its one LDS array: the scan kernels need their kStreamThreads * 8 bytes, the others do not mind
+    template <class... P, class... A>
+    void launch(void (*kernel)(P...), Grid grid, unsigned threads, A&&... a)
+    {
+        const int mine = grid.kind == kGridItems ? grid_items : (grid.kind == kGridCopy ? grid_copy : (grid.kind == kGridWalk ? grid_walk : 0));
+        simt::launch(dim3(mine > 0 ? (unsigned)mine : grid.groups), dim3(threads), kStreamThreads * 8, KernelCall<P...>{ kernel, std::tuple<P...>{ P(a)... } });
     }
+    int fill(void* p, int byte, size_t bytes) { memset(p, byte, bytes); return 0; }
+    // results == NULL: the test wrote the encoder's results and bytes in place before the call
+    int encode(const lz4hip_batch_t* b, int)
+    {
+        for (int64_t j = 0; results && j < b->n_blocks; j++) {
+            const int64_t at = b->dst_off ? b->dst_off[j] : j * b->dst_stride;
+            const int32_t r = results[j] < b->dst_cap[j] ? results[j] : b->dst_cap[j];
+            b->result[j] = results[j];
+            if (r > 0) memcpy((uint8_t*)b->dst + at, bytes + at, (size_t)r);
+        }
+        return 0;
+    }
+    int decode(const lz4hip_batch_t* b, int)
+    {
+        for (int64_t j = 0; j < b->n_blocks; j++) {
+            b->result[j] = results[j];
+            if (b->dst_cap[j] > 0) memcpy((uint8_t*)b->dst + b->dst_off[j], bytes + b->dst_off[j], (size_t)b->dst_cap[j]);
+        }
+        return 0;
+    }
+    int last_error() { return 0; }
+    int fail(int code, const char* what) { error = what; return code; }
+};
+
+inline EmuBackend backend(int grid_items, int grid_copy, int grid_walk = 0, const int32_t* results = nullptr, const uint8_t* bytes = nullptr)
+{
+    EmuBackend be;
+    be.grid_items = grid_items; be.grid_copy = grid_copy; be.grid_walk = grid_walk; be.results = results; be.bytes = bytes;
+    return be;
 }
 
 }  // namespace emu_framing
@@ -82,13 +93,17 @@ int64_t emu_framing_sizeof(int which)
     }
 }
 
-// the product's grid formulas, for the entries below that take an explicit grid
-int emu_items_grid(int64_t items) { return (int)emu_framing::items_grid(items, 0); }
-int emu_copy_grid(int64_t bytes) { return (int)emu_framing::copy_grid(bytes, 0); }
-int emu_walk_grid(int64_t n) { return (int)emu_framing::walk_grid(n, 0); }
+// the library's grid formulas, for the entries below that take an explicit grid
+int emu_items_grid(int64_t items) { return (int)framing::stream_grid(items).groups; }
+int emu_copy_grid(int64_t bytes) { return (int)framing::copy_grid(bytes).groups; }
+int emu_walk_grid(int64_t n) { return (int)framing::walk_grid(n).groups; }
 
 // ---- single kernels ----------------------------------------------------------------------------------------------------------
-void emu_scan(int64_t* x, int64_t n, int64_t* partial, int64_t* total) { emu_framing::scan(x, n, partial, total); }
+void emu_scan(int64_t* x, int64_t n, int64_t* partial, int64_t* total)
+{
+    emu_framing::EmuBackend be;
+    framing::launch_scan(be, x, n, partial, total);
+}
 
 void emu_stream_index(const uint8_t* src, int64_t src_len, const StreamTables* t, StreamInfo* info)
 {
@@ -130,7 +145,7 @@ void emu_streams_walk(int fill, const StreamsDecodeArgs* a, const StreamsTables*
 {
     const StreamsDecodeArgs aa = *a;
     const StreamsTables tt = *t;
-    const unsigned g = emu_framing::walk_grid(aa.n, grid);
+    const unsigned g = grid > 0 ? (unsigned)grid : framing::walk_grid(aa.n).groups;
     if (fill) simt::launch(dim3(g), dim3(64), 0, [=] { streams_walk_kernel<true>(aa, tt); });
     else      simt::launch(dim3(g), dim3(64), 0, [=] { streams_walk_kernel<false>(aa, tt); });
 }
@@ -138,158 +153,163 @@ void emu_streams_walk(int fill, const StreamsDecodeArgs* a, const StreamsTables*
 void emu_stream_check(const StreamTables* t, int64_t n, int grid)
 {
     const StreamTables tt = *t;
-    simt::launch(dim3(emu_framing::items_grid(n, grid)), dim3(kStreamThreads), 0, [=] { stream_check_kernel(tt, n); });
+    simt::launch(dim3(grid > 0 ? (unsigned)grid : framing::stream_grid(n).groups), dim3(kStreamThreads), 0, [=] { stream_check_kernel(tt, n); });
 }
 
-// ---- stream_encode of lz4hip_api.hip without launch_encode: a->result and a->comp are the test's ---------------------------------
+// ---- the sequences of lz4hip_framing.hpp over the test's own arrays ------------------------------------------------------------------
+// stream_encode without the block encoder: a->result and a->comp are the test's
 void emu_stream_encode(const StreamEncodeArgs* a, int32_t* lens, int64_t* partial, uint8_t* dst, int64_t* dst_len, int64_t bound,
                        int grid_items, int grid_copy)
 {
-    const StreamEncodeArgs aa = *a;
-    const unsigned gi = emu_framing::items_grid(aa.n, grid_items);
-    simt::launch(dim3(gi), dim3(kStreamThreads), 0, [=] { stream_lens_kernel(lens, aa.n, aa.src_len, aa.block); });
-    simt::launch(dim3(gi), dim3(kStreamThreads), 0, [=] { stream_sizes_kernel(aa); });
-    emu_framing::scan(aa.offs, aa.n, partial, dst_len);
-    EncodeLayout L = { aa };
-    simt::launch(dim3(emu_framing::copy_grid(bound, grid_copy)), dim3(kStreamThreads), 0, [=] { stream_pack_kernel(L, dst, dst_len); });
+    emu_framing::EmuBackend be = emu_framing::backend(grid_items, grid_copy);
+    framing::stream_encode_run(be, *a, LZ4HIP_MODE_FAST, lens, partial, dst, dst_len);
 }
 
-// ---- stream_index + stream_decode without launch_decode: results[j] / decoded stand for the decoder on row j ----------------------
-// Returns 0, or 1 when the index reported a full table (stream_decode refuses that info).
+// stream_index + stream_decode: results[j] / decoded stand for the block decoder on row j.  Returns 0, or 1 when the index reported a
+// full table (stream_decode refuses that info).
 int emu_stream_decode(const uint8_t* src, int64_t src_len, const StreamTables* t, const int32_t* results, const uint8_t* decoded,
                       uint8_t* dst, StreamInfo* index_info, StreamInfo* info, int grid_items, int grid_copy)
 {
-    const StreamTables tt = *t;
-    simt::launch(dim3(1), dim3(64), 0, [=] { stream_index_kernel(src, src_len, tt, index_info); });
-    const StreamInfo h = *index_info;
-    if (h.error == kStreamTableFull) return 1;
-    simt::launch(dim3(1), dim3(64), 0, [=] { stream_info_init_kernel(h, info, tt.min_bad); });
-    if (h.compressed_chunks > 0) {
-        emu_framing::fake_decode(tt, h.compressed_chunks, results, decoded, dst);
-        const int64_t nc = h.compressed_chunks;
-        simt::launch(dim3(emu_framing::items_grid(nc, grid_items)), dim3(kStreamThreads), 0, [=] { stream_check_kernel(tt, nc); });
-    }
-    if (h.chunks > h.compressed_chunks) {
-        RawLayout L = { src, tt, h.chunks - h.compressed_chunks };
-        const int64_t end = h.decoded_bytes;
-        simt::launch(dim3(emu_framing::copy_grid(end, grid_copy)), dim3(kStreamThreads), 0, [=] { stream_raw_copy_kernel(L, dst, end); });
-    }
-    simt::launch(dim3(1), dim3(64), 0, [=] { stream_info_finish_kernel(info, tt.min_bad); });
+    emu_framing::EmuBackend be = emu_framing::backend(grid_items, grid_copy, 0, results, decoded);
+    framing::stream_index_run(be, src, src_len, *t, index_info);
+    if (index_info->error == kStreamTableFull) return 1;
+    framing::stream_decode_run(be, src, *index_info, *t, dst, info);
     return 0;
 }
 
-// ---- wrap_encode without launch_encode: a->enc and a->comp are the test's -----------------------------------------------------------
+// wrap_encode without the block encoder: a->enc and a->comp are the test's
 void emu_wrap(const WrapArgs* a, int64_t* at, int32_t* lens, int32_t* result, int64_t* partial, uint8_t* dst, int64_t cap, int64_t bound,
               int grid_items, int grid_copy)
 {
-    const WrapArgs aa = *a;
-    const unsigned gi = emu_framing::items_grid(aa.n, grid_items);
-    simt::launch(dim3(gi), dim3(kStreamThreads), 0, [=] { wrap_lens_kernel(aa.off, aa.n, aa.src_len, at, lens); });
-    simt::launch(dim3(gi), dim3(kStreamThreads), 0, [=] { wrap_sizes_kernel(aa, result); });
-    emu_framing::scan(aa.dst_off, aa.n, partial, aa.dst_off + aa.n);
-    WrapLayout L = { aa };
-    simt::launch(dim3(emu_framing::copy_grid(bound, grid_copy)), dim3(kStreamThreads), 0, [=] { wrap_pack_kernel(L, dst, cap); });
+    emu_framing::EmuBackend be = emu_framing::backend(grid_items, grid_copy);
+    framing::wrap_encode_run(be, *a, LZ4HIP_MODE_FAST, at, lens, result, partial, dst, cap);
 }
 
-// ---- unwrap_index (n > 0) -------------------------------------------------------------------------------------------------------------
 void emu_unwrap_index(const UnwrapArgs* a, const UnwrapTables* t, UnwrapInfo* info, int grid_items)
 {
-    const UnwrapArgs aa = *a;
-    const UnwrapTables tt = *t;
-    *tt.min_bad = ~0ull;
-    *tt.ncomp = 0;
-    const unsigned gi = emu_framing::items_grid(aa.n, grid_items);
-    simt::launch(dim3(gi), dim3(kStreamThreads), 0, [=] { unwrap_index_kernel(aa, tt); });
-    emu_framing::scan(aa.dst_off, aa.n, tt.partial, aa.dst_off + aa.n);
-    emu_framing::scan(tt.cidx, aa.n, tt.partial, tt.ncomp);
-    simt::launch(dim3(gi), dim3(kStreamThreads), 0, [=] { unwrap_compact_kernel(aa, tt); });
-    simt::launch(dim3(1), dim3(64), 0, [=] { unwrap_info_kernel(aa, tt, info); });
+    emu_framing::EmuBackend be = emu_framing::backend(grid_items, 0);
+    framing::unwrap_index_run(be, *a, *t, info);
 }
 
-// ---- unwrap_decode without launch_decode, on the tables emu_unwrap_index left -------------------------------------------------------
+// unwrap_decode on the tables emu_unwrap_index left
 void emu_unwrap_decode(const UnwrapArgs* a, const UnwrapTables* t, const UnwrapInfo* index_info, const int32_t* results, const uint8_t* decoded,
                        uint8_t* dst, UnwrapInfo* info, int grid_items, int grid_copy)
 {
-    const UnwrapArgs aa = *a;
-    const UnwrapTables tt = *t;
-    const UnwrapInfo h = *index_info;
-    if (h.compressed > 0)
-        for (int64_t j = 0; j < h.compressed; j++) {
-            tt.c_result[j] = results[j];
-            if (tt.c_dst_cap[j] > 0) memcpy(dst + tt.c_dst_off[j], decoded + tt.c_dst_off[j], (size_t)tt.c_dst_cap[j]);
-        }
-    if (aa.n > h.compressed && h.decoded_bytes > 0) {
-        UnwrapRawLayout L = { aa, tt };
-        const int64_t end = h.decoded_bytes;
-        simt::launch(dim3(emu_framing::copy_grid(end, grid_copy)), dim3(kStreamThreads), 0, [=] { wrap_raw_copy_kernel(L, dst, end); });
-    }
-    if (h.compressed > 0) {
-        const int64_t nc = h.compressed;
-        int32_t* const status = aa.status;
-        simt::launch(dim3(emu_framing::items_grid(nc, grid_items)), dim3(kStreamThreads), 0, [=] { unwrap_check_kernel(tt, nc, status); });
-    }
-    simt::launch(dim3(1), dim3(64), 0, [=] { unwrap_info_kernel(aa, tt, info); });
+    emu_framing::EmuBackend be = emu_framing::backend(grid_items, grid_copy, 0, results, decoded);
+    framing::unwrap_decode_run(be, *a, *t, *index_info, dst, info);
 }
 
-// ---- streams_encode in two halves around launch_encode: the chunk table, then (a->result and a->comp filled by the test) the pack -----
+// streams_encode in its two parts: the chunk table, then (a->result and a->comp filled by the test) the pack
 void emu_streams_plan(const StreamsEncodeArgs* a, int64_t* partial, int grid_items)
 {
-    const StreamsEncodeArgs aa = *a;
-    simt::launch(dim3(emu_framing::items_grid(aa.n, grid_items)), dim3(kStreamThreads), 0, [=] { streams_counts_kernel(aa); });
-    emu_framing::scan(aa.first, aa.n, partial, (int64_t*)aa.total);
-    simt::launch(dim3(emu_framing::items_grid(aa.cap, grid_items)), dim3(kStreamThreads), 0, [=] { streams_chunks_kernel(aa); });
+    emu_framing::EmuBackend be = emu_framing::backend(grid_items, 0);
+    framing::streams_encode_plan(be, *a, partial);
 }
 
 void emu_streams_pack(const StreamsEncodeArgs* a, int64_t* partial, int64_t* dst_off, uint8_t* dst, int64_t cap, int64_t bound,
                       int grid_items, int grid_copy)
 {
-    const StreamsEncodeArgs aa = *a;
-    simt::launch(dim3(emu_framing::items_grid(aa.cap, grid_items)), dim3(kStreamThreads), 0, [=] { streams_sizes_kernel(aa); });
-    emu_framing::scan(aa.offs, aa.cap, partial, aa.offs + aa.cap);
-    simt::launch(dim3(emu_framing::items_grid(aa.n + 1, grid_items)), dim3(kStreamThreads), 0, [=] { streams_offsets_kernel(aa, dst_off); });
-    StreamsEncodeLayout L = { aa };
-    simt::launch(dim3(emu_framing::copy_grid(bound, grid_copy)), dim3(kStreamThreads), 0, [=] { streams_pack_kernel(L, dst, cap); });
+    emu_framing::EmuBackend be = emu_framing::backend(grid_items, grid_copy);
+    framing::streams_encode_pack(be, *a, partial, dst_off, dst, cap);
 }
 
-// ---- streams_index (n > 0); `head` is the first 256 bytes of the scratch: [min_bad, totals[0], totals[1], ...] --------------------------
 void emu_streams_index(const StreamsDecodeArgs* a, const StreamsTables* t, StreamsInfo* info, int grid_walk)
 {
-    const StreamsDecodeArgs aa = *a;
-    const StreamsTables tt = *t;
-    *tt.t.min_bad = ~0ull;
-    tt.totals[0] = tt.totals[1] = 0;
-    const unsigned g = emu_framing::walk_grid(aa.n, grid_walk);
-    simt::launch(dim3(g), dim3(64), 0, [=] { streams_walk_kernel<false>(aa, tt); });
-    emu_framing::scan(aa.dst_off, aa.n, tt.partial, aa.dst_off + aa.n);
-    emu_framing::scan(tt.chunk_base, aa.n, tt.partial, tt.totals);
-    emu_framing::scan(tt.comp_base, aa.n, tt.partial, tt.totals + 1);
-    simt::launch(dim3(g), dim3(64), 0, [=] { streams_walk_kernel<true>(aa, tt); });
-    simt::launch(dim3(1), dim3(64), 0, [=] { streams_info_kernel(aa, tt, info); });
+    emu_framing::EmuBackend be = emu_framing::backend(0, 0, grid_walk);
+    framing::streams_index_run(be, *a, *t, info);
 }
 
-// ---- streams_decode without launch_decode, on the tables emu_streams_index left; returns 1 for a full table ---------------------------
+// streams_decode on the tables emu_streams_index left; returns 1 for a full table
 int emu_streams_decode(const StreamsDecodeArgs* a, const StreamsTables* t, const StreamsInfo* index_info, const int32_t* results,
                        const uint8_t* decoded, uint8_t* dst, StreamsInfo* info, int grid_items, int grid_copy)
 {
-    const StreamsDecodeArgs aa = *a;
-    const StreamsTables tt = *t;
-    const StreamsInfo h = *index_info;
-    if (h.error == kStreamTableFull) return 1;
-    *tt.t.min_bad = ~0ull;
-    for (int64_t i = 0; i < aa.n; i++) tt.item_bad[i] = ~0ull;
-    if (h.compressed_chunks > 0) {
-        emu_framing::fake_decode(tt.t, h.compressed_chunks, results, decoded, dst);
-        const int64_t nc = h.compressed_chunks;
-        simt::launch(dim3(emu_framing::items_grid(nc, grid_items)), dim3(kStreamThreads), 0, [=] { streams_check_kernel(tt, nc); });
-    }
-    if (h.chunks > h.compressed_chunks) {
-        RawLayout L = { aa.src, tt.t, h.chunks - h.compressed_chunks };
-        const int64_t end = h.decoded_bytes;
-        simt::launch(dim3(emu_framing::copy_grid(end, grid_copy)), dim3(kStreamThreads), 0, [=] { stream_raw_copy_kernel(L, dst, end); });
-    }
-    simt::launch(dim3(emu_framing::items_grid(aa.n, grid_items)), dim3(kStreamThreads), 0, [=] { streams_finish_kernel(aa, tt); });
-    simt::launch(dim3(1), dim3(64), 0, [=] { streams_info_kernel(aa, tt, info); });
+    if (index_info->error == kStreamTableFull) return 1;
+    emu_framing::EmuBackend be = emu_framing::backend(grid_items, grid_copy, 0, results, decoded);
+    framing::streams_decode_run(be, *a, *t, *index_info, dst, info);
     return 0;
+}
+
+// ---- the whole functions of lz4hip_framing.hpp (front and sequence) on a scratch buffer the test brings -----------------------------
+// The library's argument lists, then the block codec's stand-in (results, bytes) and the grids.
+int64_t emu_scratch_bytes(int which, int64_t a, int64_t b, int64_t c)
+{
+    switch (which) {
+    case 0: return framing::stream_encode_scratch(nullptr, a, framing::stream_block((int32_t)b)).bytes;      // (src_len, block_size)
+    case 1: return framing::stream_decode_scratch_bytes(a);                                                   // (max_chunks)
+    case 2: return framing::wrap_scratch(nullptr, a, b).bytes;                                                // (n, src_len)
+    case 3: return framing::unwrap_scratch_bytes(a);                                                          // (n)
+    case 4: return framing::streams_encode_scratch(nullptr, a, b, framing::stream_block((int32_t)c)).bytes;  // (n, src_len, block_size)
+    case 5: return framing::streams_decode_scratch_bytes(a, b);                                               // (n, max_chunks)
+    default: return -1;
+    }
+}
+
+int emu_lib_stream_encode(const void* src, int64_t src_len, int32_t block_size, int mode, void* dst, int64_t dst_cap, int64_t* dst_len,
+                          void* scratch, int64_t scratch_bytes, const int32_t* results, const uint8_t* bytes, int grid_items, int grid_copy)
+{
+    emu_framing::EmuBackend be = emu_framing::backend(grid_items, grid_copy, 0, results, bytes);
+    return framing::stream_encode(be, src, src_len, block_size, mode, dst, dst_cap, dst_len, scratch, scratch_bytes);
+}
+
+int emu_lib_stream_index(const void* src, int64_t src_len, int64_t max_chunks, void* scratch, int64_t scratch_bytes, lz4hip_stream_info_t* info)
+{
+    emu_framing::EmuBackend be;
+    return framing::stream_index(be, src, src_len, max_chunks, scratch, scratch_bytes, info);
+}
+
+int emu_lib_stream_decode(const void* src, const lz4hip_stream_info_t* info_host, int64_t max_chunks, void* scratch, int64_t scratch_bytes,
+                          void* dst, int64_t dst_cap, lz4hip_stream_info_t* info, const int32_t* results, const uint8_t* bytes,
+                          int grid_items, int grid_copy)
+{
+    emu_framing::EmuBackend be = emu_framing::backend(grid_items, grid_copy, 0, results, bytes);
+    return framing::stream_decode(be, src, info_host, max_chunks, scratch, scratch_bytes, dst, dst_cap, info);
+}
+
+int emu_lib_wrap(const void* src, int64_t src_len, const int64_t* src_off, int64_t n, int mode, void* dst, int64_t dst_cap, int64_t* dst_off,
+                 int32_t* result, void* scratch, int64_t scratch_bytes, const int32_t* results, const uint8_t* bytes, int grid_items, int grid_copy)
+{
+    emu_framing::EmuBackend be = emu_framing::backend(grid_items, grid_copy, 0, results, bytes);
+    return framing::wrap_encode(be, src, src_len, src_off, n, mode, dst, dst_cap, dst_off, result, scratch, scratch_bytes);
+}
+
+int emu_lib_unwrap_index(const void* src, int64_t src_len, const int64_t* src_off, int64_t n, int64_t* dst_off, int32_t* status,
+                         void* scratch, int64_t scratch_bytes, lz4hip_unwrap_info_t* info, int grid_items)
+{
+    emu_framing::EmuBackend be = emu_framing::backend(grid_items, 0);
+    return framing::unwrap_index(be, src, src_len, src_off, n, dst_off, status, scratch, scratch_bytes, info);
+}
+
+int emu_lib_unwrap_decode(const void* src, int64_t src_len, const int64_t* src_off, int64_t n, const lz4hip_unwrap_info_t* info_host,
+                          void* scratch, int64_t scratch_bytes, void* dst, int64_t dst_cap, const int64_t* dst_off, int32_t* status,
+                          lz4hip_unwrap_info_t* info, const int32_t* results, const uint8_t* bytes, int grid_items, int grid_copy)
+{
+    emu_framing::EmuBackend be = emu_framing::backend(grid_items, grid_copy, 0, results, bytes);
+    return framing::unwrap_decode(be, src, src_len, src_off, n, info_host, scratch, scratch_bytes, dst, dst_cap, dst_off, status, info);
+}
+
+int emu_lib_streams_encode(const void* src, int64_t src_len, const int64_t* src_off, int64_t n, int32_t block_size, int mode, void* dst,
+                           int64_t dst_cap, int64_t* dst_off, void* scratch, int64_t scratch_bytes, const int32_t* results, const uint8_t* bytes,
+                           int grid_items, int grid_copy)
+{
+    emu_framing::EmuBackend be = emu_framing::backend(grid_items, grid_copy, 0, results, bytes);
+    return framing::streams_encode(be, src, src_len, src_off, n, block_size, mode, dst, dst_cap, dst_off, scratch, scratch_bytes);
+}
+
+int emu_lib_streams_index(const void* src, int64_t src_len, const int64_t* src_off, int64_t n, int64_t max_chunks, int64_t* dst_off,
+                          int32_t* status, int64_t* error_offset, void* scratch, int64_t scratch_bytes, lz4hip_streams_info_t* info, int grid_walk)
+{
+    emu_framing::EmuBackend be = emu_framing::backend(0, 0, grid_walk);
+    return framing::streams_index(be, src, src_len, src_off, n, max_chunks, dst_off, status, error_offset, scratch, scratch_bytes, info);
+}
+
+int emu_lib_streams_decode(const void* src, int64_t src_len, const int64_t* src_off, int64_t n, const lz4hip_streams_info_t* info_host,
+                           int64_t max_chunks, void* scratch, int64_t scratch_bytes, void* dst, int64_t dst_cap, const int64_t* dst_off,
+                           int32_t* status, int64_t* error_offset, lz4hip_streams_info_t* info, const int32_t* results, const uint8_t* bytes,
+                           int grid_items, int grid_copy)
+{
+    emu_framing::EmuBackend be = emu_framing::backend(grid_items, grid_copy, 0, results, bytes);
+    return framing::streams_decode(be, src, src_len, src_off, n, info_host, max_chunks, scratch, scratch_bytes, dst, dst_cap, dst_off, status,
+                                   error_offset, info);
 }
 
 }  // extern "C"

@@ -1,7 +1,7 @@
 // emu_kernels.cpp -- TEST INFRASTRUCTURE ONLY.
 // Compiles the real kernel sources (lz4net_amd/csrc/*.hpp) against the SIMT emulator and exposes
 // them through a C ABI for tests/test_simt_emulation.py and tests/test_simt_framing.py (the framing kernels: entry points in
-// emu_framing.hpp).  Built with g++, never shipped.
+// emu_framing.hpp, which run the library's own host code for those paths, lz4hip_framing.hpp).  Built with g++, never shipped.
 #include "simt_wave.hpp"
 
 static unsigned long long g_iterations = 0;   // loop iterations of the lane decoders (all wavefronts), counted by lane 0

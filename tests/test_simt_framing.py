@@ -1,6 +1,8 @@
 """The framing kernels (lz4net_amd/csrc/lz4hip_stream.hpp, lz4hip_wrap.hpp, lz4hip_streams.hpp) under the CPU SIMT emulator
 (tests/simt/emu_framing.hpp): the int64 scan, the position-driven copy routine behind its five layouts, the header reader, and the
-kernel sequences of lz4hip_api.hip with the block codec step replaced by arrays handed in here.  Every reference is plain Python /
+library's own host code for the framing paths (lz4net_amd/csrc/lz4hip_framing.hpp: scratch layouts, grids, kernel sequences), once
+from the kernels' argument structs over arrays made here and once whole, from the C ABI's arguments over a scratch buffer of exactly
+the size the library asks for, with the block codec step replaced by arrays handed in here.  Every reference is plain Python /
 numpy written from the wire formats (LZ4Stream: src/LZ4/LZ4Stream.cs:162-312, Wrap: src/LZ4/LZ4Codec.cs:471-599), never from the
 kernels.  Every output buffer has guard bytes on both sides and is pre-filled with a pattern; bytes that belong to no segment must
 still hold it.  Every case runs with a grid of one workgroup, a small odd grid and the product's grid formula.  The `-m gpu` tests
@@ -744,8 +746,51 @@ def test_header_fuzz(seed):
     check_streams_index(f"fuzz seed {seed}", streams)
 
 
-# ---- the kernel sequences of lz4hip_api.hip around a block codec that is the test's --------------------------------------------------
+# ---- the kernel sequences of lz4hip_framing.hpp around a block codec that is the test's ----------------------------------------------
 PIPE_BLOCKS = (16, 17, 127, 128, 4096)
+MODE_FAST, MODE_HC = 0, 1
+
+
+def lib_scratch(which, *args):
+    """(guarded buffer of exactly the bytes lz4hip_framing.hpp's size function `which` returns, address, size)"""
+    size = emu.framing().emu_scratch_bytes(which, *(list(args) + [0, 0])[:3])
+    buf, ptr = guarded(size)
+    return buf, ptr, size
+
+
+def untouched(buf):
+    return np.array_equal(buf, pattern(buf.size))
+
+
+def guards_intact(buf):
+    want = pattern(buf.size)
+    return np.array_equal(buf[:GUARD], want[:GUARD]) and np.array_equal(buf[-GUARD:], want[-GUARD:])
+
+
+def filled(n, dtype=np.int64):
+    return np.full(n, FILL, dtype)
+
+
+def lib_stream_encode(name, data, B, results, comp, hc, gi, gc, want):
+    """the whole stream_encode (front, layout, sequence) on a scratch buffer of exactly the size asked for, then on one a byte short"""
+    L = emu.framing()
+    n = -(-data.size // B)
+    bound = data.size + n * (1 + 2 * len(st.write_varint(B))) if data.size else 0
+    src = np.ascontiguousarray(np.concatenate([data, np.zeros(1, np.uint8)]))
+    res = np.array(list(results) + [0], np.int32)
+    for short in (0, 1):
+        scratch, sptr, size = lib_scratch(0, data.size, B)
+        dst_len = filled(3)
+        buf, ptr = guarded(bound)
+        rc = L.emu_lib_stream_encode(addr(src), data.size, B, MODE_HC if hc else MODE_FAST, ptr, bound, addr(dst_len, 1), sptr, size - short,
+                                     addr(res), addr(comp), gi, gc)
+        if short:
+            assert rc == E_ARGUMENT and untouched(buf) and untouched(scratch) and (dst_len == FILL).all(), (name, rc)
+            continue
+        assert rc == 0 and dst_len.tolist() == [FILL, len(want), FILL] and guards_intact(scratch), (name, rc, dst_len.tolist())
+        same(buf, ref_copy(bound, [(0, want)], len(want)), f"{name}: whole, grids {gi}, {gc}")
+        if data.size == 0:
+            assert size == 0 and untouched(buf), name                       # src_len == 0: *dst_len = 0 and nothing else
 
 
 def pipe_lengths(B):
@@ -785,6 +830,7 @@ def check_stream_encode(name, data, B, results, comp, hc, want):
             buf, total, bound = run_stream_encode(data, B, results, comp, hc, gi, gc)
             assert total == len(want) <= bound, (name, total, len(want))
             same(buf, ref_copy(bound, [(0, want)], len(want)), f"{name}: grids {gi}, {gc}")
+            lib_stream_encode(name, data, B, results, comp, hc, gi, gc, want)
 
 
 @pytest.mark.parametrize("B", PIPE_BLOCKS)
@@ -835,6 +881,37 @@ def run_stream_decode(stream, results, decoded, grid_items, grid_copy, spare=2):
     return index_info, info, buf, cap
 
 
+def lib_stream_decode(stream, results, decoded, grid_items, grid_copy, spare=2):
+    """run_stream_decode through the whole stream_index and stream_decode, tables in a scratch buffer of exactly the size asked for"""
+    L = emu.framing()
+    w = ref_walk(stream)
+    src = np.frombuffer(bytes(stream) + TAIL, np.uint8).copy()
+    mc = w["chunks"] + spare
+    res = np.array(list(results) + [0], np.int32)
+    dec = np.ascontiguousarray(np.concatenate([decoded, np.zeros(8, np.uint8)]))
+    cap = w["decoded_bytes"] + 24
+    for short in (1, 0):
+        scratch, sptr, size = lib_scratch(1, mc)
+        buf, ptr = guarded(cap)
+        index_info, info = emu.StreamInfo(chunks=FILL), emu.StreamInfo(chunks=FILL)
+        rc = L.emu_lib_stream_index(addr(src), len(stream), mc, sptr, size - short, ref(index_info))
+        if short:
+            good = emu.StreamInfo(chunks=w["chunks"], compressed_chunks=w["compressed_chunks"], decoded_bytes=w["decoded_bytes"], error_offset=-1)
+            rc2 = L.emu_lib_stream_decode(addr(src), ref(good), mc, sptr, size - 1, ptr, cap, ref(info), addr(res), addr(dec), grid_items, grid_copy)
+            assert rc == rc2 == E_ARGUMENT and index_info.chunks == info.chunks == FILL and untouched(scratch) and untouched(buf)
+            continue
+        assert rc == 0 and (index_info.error, index_info.error_offset, index_info.chunks) == (w["status"], w["error_offset"], w["chunks"])
+        assert L.emu_lib_stream_decode(addr(src), ref(index_info), mc, sptr, size, ptr, cap, ref(info), addr(res), addr(dec), grid_items, grid_copy) == 0
+        assert guards_intact(scratch)
+    return index_info, info, buf, cap
+
+
+def both_stream_decodes(*args):
+    """the sequences over the test's tables, then the whole functions over a scratch buffer: the same outcome is expected of both"""
+    yield run_stream_decode(*args)
+    yield lib_stream_decode(*args)
+
+
 @pytest.mark.parametrize("B", PIPE_BLOCKS)
 def test_pipeline_stream_decode(oracle, B):
     for size in pipe_lengths(B):
@@ -844,9 +921,9 @@ def test_pipeline_stream_decode(oracle, B):
         good = [r[3] for r in rows if r[0]]
         for gi in item_grids(len(good)):
             for gc in copy_grids(size):
-                _, info, buf, cap = run_stream_decode(stream, good, data, gi, gc)
-                assert (info.error, info.error_offset, info.chunks, info.decoded_bytes) == (OK, -1, len(rows), size), (B, size)
-                same(buf, ref_copy(cap, [(0, data)], size), f"block {B}, {size} bytes, grids {gi}, {gc}")
+                for _, info, buf, cap in both_stream_decodes(stream, good, data, gi, gc):
+                    assert (info.error, info.error_offset, info.chunks, info.decoded_bytes) == (OK, -1, len(rows), size), (B, size)
+                    same(buf, ref_copy(cap, [(0, data)], size), f"block {B}, {size} bytes, grids {gi}, {gc}")
 
 
 def test_pipeline_stream_decode_errors(oracle):
@@ -868,14 +945,14 @@ def test_pipeline_stream_decode_errors(oracle):
         for bad in ([1], [1, 2], [2, 1], list(range(len(comp_rows)))[::-1], [len(comp_rows) - 1], []):
             results = [r[3] - (1 if j in bad else 0) for j, r in enumerate(comp_rows)]
             for gi in (1, 3, 0):
-                index_info, info, buf, cap = run_stream_decode(stream, results, data, gi, 0)
-                if bad:
-                    want = (CORRUPT_BLOCK, hdr[min(bad)])
-                else:
-                    want = (w["status"], w["error_offset"])
-                assert (info.error, info.error_offset) == want, (tail, bad, gi, info.error, info.error_offset)
-                assert (info.chunks, info.compressed_chunks, info.decoded_bytes) == (w["chunks"], len(comp_rows), w["decoded_bytes"])
-                same(buf, ref_copy(cap, [(0, data[:w["decoded_bytes"]])], w["decoded_bytes"]), f"errors {tail} {bad} {gi}")
+                for index_info, info, buf, cap in both_stream_decodes(stream, results, data, gi, 0):
+                    if bad:
+                        want = (CORRUPT_BLOCK, hdr[min(bad)])
+                    else:
+                        want = (w["status"], w["error_offset"])
+                    assert (info.error, info.error_offset) == want, (tail, bad, gi, info.error, info.error_offset)
+                    assert (info.chunks, info.compressed_chunks, info.decoded_bytes) == (w["chunks"], len(comp_rows), w["decoded_bytes"])
+                    same(buf, ref_copy(cap, [(0, data[:w["decoded_bytes"]])], w["decoded_bytes"]), f"errors {tail} {bad} {gi}")
 
 
 def test_stream_check_kernel_takes_the_minimum():
@@ -917,6 +994,26 @@ def run_wrap(msgs, off, enc, comp, grid_items, grid_copy):
     L.emu_wrap(ref(a), addr(at), addr(lens), addr(result), addr(partial), ptr, bound, bound, grid_items, grid_copy)
     assert dst_off[n + 1] == FILL and at[n] == FILL and lens[n] == FILL and result[n] == FILL and partial[-1] == FILL
     return buf, bound, dst_off[:n + 1], at[:n], lens[:n], result[:n]
+
+
+def lib_wrap(msgs, off, enc, comp, grid_items, grid_copy, short=0):
+    """run_wrap through the whole wrap_encode: the encoder's results and bytes are handed in, the scratch has exactly the size asked for"""
+    L = emu.framing()
+    n = len(off) - 1
+    src = np.ascontiguousarray(np.concatenate(msgs + [np.zeros(1, np.uint8)]))
+    src_len = src.size - 1
+    bound = src_len + 8 * n
+    dst_off, result = filled(n + 2), filled(n + 1, np.int32)
+    e = np.array(list(enc) + [0], np.int32)
+    scratch, sptr, size = lib_scratch(2, n, src_len)
+    buf, ptr = guarded(bound)
+    rc = L.emu_lib_wrap(addr(src), src_len, addr(off), n, MODE_FAST, ptr, bound, addr(dst_off), addr(result), sptr, size - short, addr(e), addr(comp),
+                        grid_items, grid_copy)
+    if short:
+        assert rc == E_ARGUMENT and untouched(buf) and untouched(scratch) and (dst_off == FILL).all() and (result == FILL).all()
+        return None
+    assert rc == 0 and dst_off[n + 1] == FILL and result[n] == FILL and guards_intact(scratch)
+    return buf, bound, dst_off[:n + 1], result[:n]
 
 
 def test_pipeline_wrap(oracle):
@@ -962,6 +1059,10 @@ def test_pipeline_wrap(oracle):
                 what = f"wrap {variant}: grids {gi}, {gc}"
                 assert dst_off.tolist() == want_off and result.tolist() == want_result and at.tolist() == want_at and lens.tolist() == want_len, what
                 same(buf, ref_copy(bound, [(0, want)], len(want)), what)
+                buf, bound, dst_off, result = lib_wrap(msgs, off, enc, comp, gi, gc)
+                assert dst_off.tolist() == want_off and result.tolist() == want_result, what
+                same(buf, ref_copy(bound, [(0, want)], len(want)), what + ", whole")
+        lib_wrap(msgs, off, enc, comp, 0, 0, short=1)
 
 
 def ref_unwrap(m):
@@ -974,6 +1075,32 @@ def ref_unwrap(m):
     if payload >= original:
         return WRAP_OK, "raw", payload, payload
     return WRAP_OK, "comp", original, payload
+
+
+def lib_unwrap(src, off, src_len, n, results, decoded, total, grid_items, grid_copy):
+    """the whole unwrap_index and unwrap_decode on a scratch buffer of exactly the size asked for (and refused on one a byte short)
+    -> (index info, final info, output offsets, statuses after the index, final statuses, guarded output)"""
+    L = emu.framing()
+    res = np.array(list(results) + [0], np.int32)
+    for short in (1, 0):
+        scratch, sptr, size = lib_scratch(3, n)
+        dst_off, st_arr = filled(n + 2), filled(n + 1, np.int32)
+        buf, ptr = guarded(total + 24)
+        index_info, info = emu.UnwrapInfo(messages=FILL), emu.UnwrapInfo(messages=FILL)
+        rc = L.emu_lib_unwrap_index(addr(src), src_len, addr(off), n, addr(dst_off), addr(st_arr), sptr, size - short, ref(index_info), grid_items)
+        if short:
+            good = emu.UnwrapInfo(messages=n)
+            rc2 = L.emu_lib_unwrap_decode(addr(src), src_len, addr(off), n, ref(good), sptr, size - 1, ptr, total + 24, addr(dst_off), addr(st_arr),
+                                          ref(info), addr(res), addr(decoded), grid_items, grid_copy)
+            assert rc == rc2 == E_ARGUMENT and index_info.messages == info.messages == FILL
+            assert untouched(scratch) and untouched(buf) and (dst_off == FILL).all() and (st_arr == FILL).all()
+            continue
+        assert rc == 0
+        index_status = st_arr.copy()
+        assert L.emu_lib_unwrap_decode(addr(src), src_len, addr(off), n, ref(index_info), sptr, size, ptr, total + 24, addr(dst_off), addr(st_arr),
+                                       ref(info), addr(res), addr(decoded), grid_items, grid_copy) == 0
+        assert guards_intact(scratch)
+    return index_info, info, dst_off, index_status, st_arr, buf
 
 
 def test_pipeline_unwrap(oracle):
@@ -1068,6 +1195,15 @@ def test_pipeline_unwrap(oracle):
                 assert got == (n, len(comp), total, first, final_status[first] if first >= 0 else WRAP_OK), (what, got)
                 assert st_arr.tolist() == final_status + [FILL] and dst_off.tolist() == want_off + [FILL], what
                 same(buf, ref_copy(total + 24, segs, total), what)
+                index_info, info, dst_off, index_status, st_arr, buf = lib_unwrap(src, off, src_len, n, results, decoded, total, gi, gc)
+                first = min([k for k in range(n) if status[k] != WRAP_OK], default=-1)
+                got = (index_info.messages, index_info.compressed, index_info.decoded_bytes, index_info.first_error, index_info.error, index_info.reserved)
+                assert got == (n, len(comp), total, first, status[first] if first >= 0 else WRAP_OK, 0), (what, got)
+                first = min([k for k in range(n) if final_status[k] != WRAP_OK], default=-1)
+                got = (info.messages, info.compressed, info.decoded_bytes, info.first_error, info.error)
+                assert got == (n, len(comp), total, first, final_status[first] if first >= 0 else WRAP_OK), (what, got)
+                assert index_status.tolist() == status + [FILL] and st_arr.tolist() == final_status + [FILL] and dst_off.tolist() == want_off + [FILL], what
+                same(buf, ref_copy(total + 24, segs, total), what + ", whole")
 
 
 # -- batches of streams
@@ -1118,6 +1254,45 @@ def test_pipeline_streams_encode(oracle, B):
                 L.emu_streams_pack(ref(a), addr(partial), addr(dst_off), ptr, bound, bound, gi, gc)
                 assert dst_off.tolist() == want_off + [FILL] and offs[cap] == want_off[-1] and offs[cap + 1] == FILL and partial[-1] == FILL, what
                 same(out, ref_copy(bound, [(0, b"".join(want))], want_off[-1]), what)
+                # the whole streams_encode: the encoder's results in chunk order (the chunk table follows from the offsets and B), its
+                # bytes at each chunk's own position, the scratch of exactly the size asked for -- and refused on one a byte short
+                for short in (0, 1):
+                    scratch, sptr, size = lib_scratch(4, n, src_len, B)
+                    dst_off = filled(n + 2)
+                    out, ptr = guarded(bound)
+                    rc = L.emu_lib_streams_encode(addr(src), src_len, addr(off), n, B, MODE_HC if hc else MODE_FAST, ptr, bound, addr(dst_off), sptr,
+                                                  size - short, addr(res), addr(comp), gi, gc)
+                    if short:
+                        assert rc == E_ARGUMENT and untouched(out) and untouched(scratch) and (dst_off == FILL).all(), what
+                        continue
+                    assert rc == 0 and dst_off.tolist() == want_off + [FILL] and guards_intact(scratch), what
+                    same(out, ref_copy(bound, [(0, b"".join(want))], want_off[-1]), what + ", whole")
+
+
+def lib_streams_decode(src, off, n, max_chunks, results, decoded, total, grid_walk, grid_items, grid_copy):
+    """the whole streams_index and streams_decode on a scratch buffer of exactly the size asked for (and refused on one a byte short)"""
+    L = emu.framing()
+    src_len = src.size - len(TAIL)
+    res = np.array(list(results) + [0], np.int32)
+    for short in (1, 0):
+        scratch, sptr, size = lib_scratch(5, n, max_chunks)
+        dst_off, status, error_offset = filled(n + 2), filled(n + 1, np.int32), filled(n + 1)
+        buf, ptr = guarded(total + 24)
+        index_info, info = emu.StreamsInfo(items=FILL), emu.StreamsInfo(items=FILL)
+        rc = L.emu_lib_streams_index(addr(src), src_len, addr(off), n, max_chunks, addr(dst_off), addr(status), addr(error_offset), sptr, size - short,
+                                     ref(index_info), grid_walk)
+        if short:
+            good = emu.StreamsInfo(items=n)
+            rc2 = L.emu_lib_streams_decode(addr(src), src_len, addr(off), n, ref(good), max_chunks, sptr, size - 1, ptr, total + 24, addr(dst_off),
+                                           addr(status), addr(error_offset), ref(info), addr(res), addr(decoded), grid_items, grid_copy)
+            assert rc == rc2 == E_ARGUMENT and index_info.items == info.items == FILL and untouched(scratch) and untouched(buf)
+            assert (dst_off == FILL).all() and (status == FILL).all() and (error_offset == FILL).all()
+            continue
+        assert rc == 0
+        assert L.emu_lib_streams_decode(addr(src), src_len, addr(off), n, ref(index_info), max_chunks, sptr, size, ptr, total + 24, addr(dst_off),
+                                        addr(status), addr(error_offset), ref(info), addr(res), addr(decoded), grid_items, grid_copy) == 0
+        assert guards_intact(scratch)
+    return dict(index_info=index_info, info=info, dst_off=dst_off, status=status, error_offset=error_offset, buf=buf)
 
 
 def test_pipeline_streams_decode(oracle):
@@ -1172,5 +1347,58 @@ def test_pipeline_streams_decode(oracle):
                 assert got == (n, sum(w["chunks"] for w in walks), len(comp_rows), total, first, err_off[first], status[first]), (what, got)
                 assert r["status"].tolist() == status + [FILL] and r["error_offset"].tolist() == err_off + [FILL] and r["dst_off"].tolist() == want_off + [FILL], what
                 same(buf, ref_copy(total + 24, segs, total), what)
+                lr = lib_streams_decode(src, off, n, sum(w["chunks"] for w in walks) + 2, results, truth, total, gw, gi, gc)
+                info = lr["info"]
+                got = (info.items, info.chunks, info.compressed_chunks, info.decoded_bytes, info.first_error, info.error_offset, info.error)
+                assert got == (n, sum(w["chunks"] for w in walks), len(comp_rows), total, first, err_off[first], status[first]), (what, got)
+                assert lr["status"].tolist() == status + [FILL] and lr["error_offset"].tolist() == err_off + [FILL] and lr["dst_off"].tolist() == want_off + [FILL], what
+                same(lr["buf"], ref_copy(total + 24, segs, total), what + ", whole")
                 for i in range(n_good):                                         # every item in front of the failing ones decodes to its full size
                     assert sizes[i] == plain[i].size, (what, i)
+
+
+def test_whole_calls_without_items():
+    """n == 0 (and, for the encoders, src_len == 0) as the library's fronts handle them: the one offset (or all n + 1) set to 0, the info of
+    an empty batch, and not a byte of anything else -- destination, scratch, statuses"""
+    L = emu.framing()
+    src, off = np.zeros(8, np.uint8), np.zeros(4, np.int64)
+    res, comp = np.zeros(4, np.int32), np.zeros(8, np.uint8)
+
+    def fresh():
+        return guarded(4096) + guarded(64) + (filled(5), filled(3, np.int32), filled(3))
+
+    scratch, sptr, buf, ptr, dst_off, status, error_offset = fresh()
+    assert L.emu_lib_wrap(addr(src), 0, addr(off), 0, MODE_FAST, ptr, 64, addr(dst_off, 1), addr(status), sptr, 0, addr(res), addr(comp), 0, 0) == 0
+    assert dst_off.tolist() == [FILL, 0, FILL, FILL, FILL] and untouched(buf) and untouched(scratch) and (status == FILL).all()
+
+    for n, src_len in ((0, 0), (0, 8), (3, 0)):
+        scratch, sptr, buf, ptr, dst_off, status, error_offset = fresh()
+        assert L.emu_lib_streams_encode(addr(src), src_len, addr(off), n, 16, MODE_FAST, ptr, 64, addr(dst_off, 1), sptr, 0, addr(res), addr(comp), 0, 0) == 0
+        assert dst_off.tolist() == [FILL] + [0] * (n + 1) + [FILL] * (3 - n) and untouched(buf) and untouched(scratch), (n, src_len)
+
+    scratch, sptr, buf, ptr, dst_off, status, error_offset = fresh()
+    info = emu.UnwrapInfo(messages=FILL, compressed=FILL, decoded_bytes=FILL, first_error=FILL, error=FILL, reserved=FILL)
+    size = L.emu_scratch_bytes(3, 0, 0, 0)
+    assert size == 256 and L.emu_lib_unwrap_index(addr(src), 0, addr(off), 0, addr(dst_off, 1), addr(status), sptr, size, ref(info), 0) == 0
+    assert (info.messages, info.compressed, info.decoded_bytes, info.first_error, info.error, info.reserved) == (0, 0, 0, -1, WRAP_OK, 0)
+    assert dst_off.tolist() == [FILL, 0, FILL, FILL, FILL] and (status == FILL).all() and untouched(buf)
+    want = pattern(scratch.size)
+    want[GUARD:GUARD + 16] = np.frombuffer(struct.pack("<Qq", NONE64, 0), np.uint8)          # [min_bad = none, ncomp = 0]
+    same(scratch, want, "unwrap index of no messages: scratch")
+
+    empty = (0, 0, 0, 0, -1, -1, OK, 0)
+    for max_chunks in (0, 5):
+        scratch, sptr, buf, ptr, dst_off, status, error_offset = fresh()
+        info = emu.StreamsInfo(items=FILL, chunks=FILL, compressed_chunks=FILL, decoded_bytes=FILL, first_error=FILL, error_offset=FILL, error=FILL, reserved=FILL)
+        assert L.emu_scratch_bytes(5, 0, max_chunks, 0) == 0
+        assert L.emu_lib_streams_index(addr(src), 8, addr(off), 0, max_chunks, addr(dst_off, 1), addr(status), addr(error_offset), sptr, 0, ref(info), 0) == 0
+        got = (info.items, info.chunks, info.compressed_chunks, info.decoded_bytes, info.first_error, info.error_offset, info.error, info.reserved)
+        assert got == empty and dst_off.tolist() == [FILL, 0, FILL, FILL, FILL], got
+        assert untouched(scratch) and untouched(buf) and (status == FILL).all() and (error_offset == FILL).all()
+        final = emu.StreamsInfo(items=FILL, chunks=FILL, compressed_chunks=FILL, decoded_bytes=FILL, first_error=FILL, error_offset=FILL, error=FILL, reserved=FILL)
+        dst_off[:] = FILL
+        assert L.emu_lib_streams_decode(addr(src), 8, addr(off), 0, ref(info), max_chunks, sptr, 0, ptr, 64, addr(dst_off, 1), addr(status),
+                                        addr(error_offset), ref(final), addr(res), addr(comp), 0, 0) == 0
+        got = (final.items, final.chunks, final.compressed_chunks, final.decoded_bytes, final.first_error, final.error_offset, final.error, final.reserved)
+        assert got == empty and (dst_off == FILL).all(), got
+        assert untouched(scratch) and untouched(buf) and (status == FILL).all() and (error_offset == FILL).all()
