@@ -1449,6 +1449,7 @@ int known_size_extent(const uint8_t* src, int osize)
 // The layouts and the kernel sequences live in that header, shared with the CPU emulator's tests; this is the device they run on here.
 struct HipBackend {
     hipStream_t stream;
+    HostContext* host = nullptr;                                       // the host pair alone: whose scratch holds the staging image
     template <class... P, class... A>
     void launch(void (*kernel)(P...), Grid grid, unsigned threads, A&&... a) { hipLaunchKernelGGL(kernel, dim3(grid.groups), dim3(threads), 0, stream, P(a)...); }
     int fill(void* p, int byte, size_t bytes) { HIP_TRY(hipMemsetAsync(p, byte, bytes, stream)); return 0; }
@@ -1456,18 +1457,22 @@ struct HipBackend {
     int decode(const lz4hip_batch_t* b, int known) { return launch_decode(b, known, stream); }
     int last_error() { HIP_TRY(hipGetLastError()); return 0; }
     int fail(int code, const std::string& what) { return ::fail(code, what); }
+    int reserve(size_t bytes, uint8_t*& base) { int rc = host->scratch.reserve(bytes); base = (uint8_t*)host->scratch.p; return rc; }
+    int upload(void* dev, const void* from, size_t bytes) { HIP_TRY(hipMemcpyAsync(dev, from, bytes, hipMemcpyHostToDevice, stream)); return 0; }
+    int download(void* to, const void* dev, size_t bytes) { HIP_TRY(hipMemcpyAsync(to, dev, bytes, hipMemcpyDeviceToHost, stream)); return 0; }
+    int sync() { HIP_TRY(hipStreamSynchronize(stream)); return 0; }
 };
 
 // The host pair stages the whole buffer in the calling thread's device scratch (HostContext: grow-only, freed by
 // lz4hip_release_workspaces) and runs the device path on the thread's first kernel stream.
-int stream_host_context(HostContext*& hc, hipStream_t& s)
+int stream_host_context(HipBackend& be)
 {
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    if (!(hc = host_context(dev))) return fail(LZ4HIP_E_DEVICE, "device index out of range");
-    int rc = hc->pipe.init();
+    int rc = ensure_device(), dev = 0;
     if (rc) return rc;
-    s = hc->pipe.s_k[0];
+    HIP_TRY(hipGetDevice(&dev));
+    if (!(be.host = host_context(dev))) return fail(LZ4HIP_E_DEVICE, "device index out of range");
+    if ((rc = be.host->pipe.init())) return rc;
+    be.stream = be.host->pipe.s_k[0];
     return 0;
 }
 
@@ -1797,74 +1802,16 @@ int lz4hip_stream_decode_device(const void* src, const lz4hip_stream_info_t* inf
 
 int lz4hip_stream_encode_host(const void* src, int64_t src_len, int32_t block_size, int mode, void* dst, int64_t dst_cap, int64_t* dst_len)
 {
-    int rc = ensure_device();
-    if (rc) return rc;
-    if (src_len < 0 || !dst_len || (src_len > 0 && (!src || !dst))) return fail(LZ4HIP_E_ARGUMENT, "stream encode: negative size or NULL pointer");
-    const int64_t bound = stream_bound(src_len, block_size);
-    if (dst_cap < bound) return fail(LZ4HIP_E_ARGUMENT, "stream encode: dst_cap < lz4hip_stream_bound");
-    if (src_len == 0) { *dst_len = 0; return 0; }
-    HostContext* hc = nullptr;
-    hipStream_t s = nullptr;
-    if ((rc = stream_host_context(hc, s))) return rc;
-    // device image: [source | stream | scratch | length]
-    const int64_t scratch_bytes = lz4hip_stream_encode_scratch_bytes(src_len, block_size);
-    Carver image;
-    image.take(src_len);
-    const int64_t out_at = image.take(bound), scratch_at = image.take(scratch_bytes), len_at = image.take(256);
-    if ((rc = hc->scratch.reserve((size_t)image.at))) return rc;
-    uint8_t* const d = (uint8_t*)hc->scratch.p;
-    HIP_TRY(hipMemcpyAsync(d, src, (size_t)src_len, hipMemcpyHostToDevice, s));
-    HipBackend be = { s };
-    if ((rc = stream_encode(be, d, src_len, block_size, mode, d + out_at, bound, (int64_t*)(d + len_at), d + scratch_at, scratch_bytes))) return rc;
-    int64_t n = 0;
-    HIP_TRY(hipMemcpyAsync(&n, d + len_at, sizeof n, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    HIP_TRY(hipMemcpyAsync(dst, d + out_at, (size_t)n, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    *dst_len = n;
-    return 0;
+    HipBackend be = {};
+    if (int rc = stream_host_context(be)) return rc;
+    return stream_encode_host(be, src, src_len, block_size, mode, dst, dst_cap, dst_len);
 }
 
 int lz4hip_stream_decode_host(const void* src, int64_t src_len, void* dst, int64_t dst_cap, lz4hip_stream_info_t* info)
 {
-    int rc = ensure_device();
-    if (rc) return rc;
-    if (src_len < 0 || dst_cap < 0 || !info || (src_len > 0 && !src)) return fail(LZ4HIP_E_ARGUMENT, "stream decode: negative size or NULL pointer");
-    HostContext* hc = nullptr;
-    hipStream_t s = nullptr;
-    if ((rc = stream_host_context(hc, s))) return rc;
-    // device image: [source | info | output | table]; walked again after a table that was too small or an image that had to grow
-    int64_t max_chunks = (src_len + 4095) / 4096 + 16, out_bytes = dst_cap < 4 * src_len ? dst_cap : 4 * src_len;
-    lz4hip_stream_info_t h = {};
-    uint8_t* d = nullptr;
-    int64_t info_at = 0, out_at = 0, table_at = 0;
-    HipBackend be = { s };
-    for (int attempt = 0;; attempt++) {
-        const int64_t table_bytes = stream_decode_scratch_bytes(max_chunks);
-        Carver image;
-        image.take(src_len);
-        info_at = image.take(256); out_at = image.take(out_bytes); table_at = image.take(table_bytes);
-        if ((rc = hc->scratch.reserve((size_t)image.at))) return rc;
-        d = (uint8_t*)hc->scratch.p;
-        if (src_len > 0) HIP_TRY(hipMemcpyAsync(d, src, (size_t)src_len, hipMemcpyHostToDevice, s));
-        if ((rc = stream_index(be, d, src_len, max_chunks, d + table_at, table_bytes, (lz4hip_stream_info_t*)(d + info_at)))) return rc;
-        HIP_TRY(hipMemcpyAsync(&h, d + info_at, sizeof h, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        if (attempt >= 2) break;
-        if (h.error == LZ4HIP_STREAM_TABLE_FULL) { max_chunks = h.chunks; continue; }
-        if (h.decoded_bytes > dst_cap) break;
-        if (h.decoded_bytes > out_bytes) { out_bytes = h.decoded_bytes; continue; }
-        break;
-    }
-    *info = h;
-    if (h.error == LZ4HIP_STREAM_TABLE_FULL) return fail(LZ4HIP_E_DEVICE, "stream decode: the header walk did not settle");
-    if (h.decoded_bytes > dst_cap) return fail(LZ4HIP_E_ARGUMENT, "stream decode: dst_cap < decoded_bytes (reported in info->decoded_bytes)");
-    if ((rc = stream_decode(be, d, &h, max_chunks, d + table_at, stream_decode_scratch_bytes(max_chunks), d + out_at, out_bytes,
-                            (lz4hip_stream_info_t*)(d + info_at)))) return rc;
-    HIP_TRY(hipMemcpyAsync(info, d + info_at, sizeof *info, hipMemcpyDeviceToHost, s));
-    if (h.decoded_bytes > 0) HIP_TRY(hipMemcpyAsync(dst, d + out_at, (size_t)h.decoded_bytes, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return info->error;
+    HipBackend be = {};
+    if (int rc = stream_host_context(be)) return rc;
+    return stream_decode_host(be, src, src_len, dst, dst_cap, info);
 }
 
 int64_t lz4hip_wrap_bound(int64_t n, int64_t src_len) { return wrap_bound(n, src_len); }
@@ -1904,85 +1851,17 @@ int lz4hip_unwrap_decode_device(const void* src, int64_t src_len, const int64_t*
 int lz4hip_wrap_host(const void* src, int64_t src_len, const int64_t* src_off, int64_t n, int mode, void* dst, int64_t dst_cap,
                      int64_t* dst_off, int32_t* result)
 {
-    int rc = ensure_device();
-    if (rc) return rc;
-    if (src_len < 0 || n < 0 || !dst_off || (n > 0 && (!src_off || !dst)) || (src_len > 0 && !src))
-        return fail(LZ4HIP_E_ARGUMENT, "wrap: negative size or NULL pointer");
-    const int64_t bound = wrap_bound(n, src_len);
-    if (dst_cap < bound) return fail(LZ4HIP_E_ARGUMENT, "wrap: dst_cap < lz4hip_wrap_bound");
-    if (n == 0) { dst_off[0] = 0; return 0; }
-    HostContext* hc = nullptr;
-    hipStream_t s = nullptr;
-    if ((rc = stream_host_context(hc, s))) return rc;
-    // device image: [source | offsets | output | output offsets | results | scratch]
-    const int64_t scratch_bytes = lz4hip_wrap_scratch_bytes(n, src_len);
-    Carver image;
-    image.take(src_len);
-    const int64_t off_at = image.take(8 * (n + 1)), out_at = image.take(bound), doff_at = image.take(8 * (n + 1)), res_at = image.take(4 * n),
-                  scratch_at = image.take(scratch_bytes);
-    if ((rc = hc->scratch.reserve((size_t)image.at))) return rc;
-    uint8_t* const d = (uint8_t*)hc->scratch.p;
-    if (src_len > 0) HIP_TRY(hipMemcpyAsync(d, src, (size_t)src_len, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d + off_at, src_off, (size_t)(8 * (n + 1)), hipMemcpyHostToDevice, s));
-    HipBackend be = { s };
-    if ((rc = wrap_encode(be, d, src_len, (const int64_t*)(d + off_at), n, mode, d + out_at, bound, (int64_t*)(d + doff_at), (int32_t*)(d + res_at),
-                          d + scratch_at, scratch_bytes))) return rc;
-    HIP_TRY(hipMemcpyAsync(dst_off, d + doff_at, (size_t)(8 * (n + 1)), hipMemcpyDeviceToHost, s));
-    if (result) HIP_TRY(hipMemcpyAsync(result, d + res_at, (size_t)(4 * n), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    const int64_t total = dst_off[n] < dst_cap ? dst_off[n] : dst_cap;
-    if (total > 0) HIP_TRY(hipMemcpyAsync(dst, d + out_at, (size_t)total, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return 0;
+    HipBackend be = {};
+    if (int rc = stream_host_context(be)) return rc;
+    return wrap_host(be, src, src_len, src_off, n, mode, dst, dst_cap, dst_off, result);
 }
 
 int lz4hip_unwrap_host(const void* src, int64_t src_len, const int64_t* src_off, int64_t n, void* dst, int64_t dst_cap, int64_t* dst_off,
                        int32_t* status, lz4hip_unwrap_info_t* info)
 {
-    int rc = ensure_device();
-    if (rc) return rc;
-    if (src_len < 0 || n < 0 || dst_cap < 0 || !dst_off || !info || (n > 0 && (!src_off || !status)) || (src_len > 0 && !src))
-        return fail(LZ4HIP_E_ARGUMENT, "unwrap: negative size or NULL pointer");
-    HostContext* hc = nullptr;
-    hipStream_t s = nullptr;
-    if ((rc = stream_host_context(hc, s))) return rc;
-    // device image: [source | offsets | output offsets | statuses | info | scratch | output]; staged again if the output had to grow
-    const int64_t scratch_bytes = unwrap_scratch_bytes(n);
-    Carver image;
-    image.take(src_len);
-    const int64_t off_at = image.take(8 * (n + 1)), doff_at = image.take(8 * (n + 1)), st_at = image.take(4 * n), info_at = image.take(256),
-                  scratch_at = image.take(scratch_bytes), out_at = image.at;
-    HipBackend be = { s };
-    int64_t out_bytes = dst_cap < 4 * src_len ? dst_cap : 4 * src_len;
-    lz4hip_unwrap_info_t h = {};
-    uint8_t* d = nullptr;
-    for (int attempt = 0; attempt < 2; attempt++) {
-        if ((rc = hc->scratch.reserve((size_t)(out_at + out_bytes)))) return rc;
-        d = (uint8_t*)hc->scratch.p;
-        if (src_len > 0) HIP_TRY(hipMemcpyAsync(d, src, (size_t)src_len, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(d + off_at, src_off, (size_t)(8 * (n + 1)), hipMemcpyHostToDevice, s));
-        if ((rc = unwrap_index(be, d, src_len, (const int64_t*)(d + off_at), n, (int64_t*)(d + doff_at), (int32_t*)(d + st_at), d + scratch_at,
-                               scratch_bytes, (lz4hip_unwrap_info_t*)(d + info_at)))) return rc;
-        HIP_TRY(hipMemcpyAsync(&h, d + info_at, sizeof h, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        if (h.decoded_bytes <= out_bytes || h.decoded_bytes > dst_cap) break;
-        out_bytes = h.decoded_bytes;
-    }
-    *info = h;
-    if (h.decoded_bytes > dst_cap || h.decoded_bytes > out_bytes) {
-        HIP_TRY(hipMemcpyAsync(dst_off, d + doff_at, (size_t)(8 * (n + 1)), hipMemcpyDeviceToHost, s));
-        if (n > 0) HIP_TRY(hipMemcpyAsync(status, d + st_at, (size_t)(4 * n), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        return fail(LZ4HIP_E_ARGUMENT, "unwrap: dst_cap < decoded_bytes (reported in info->decoded_bytes)");
-    }
-    if ((rc = unwrap_decode(be, d, src_len, (const int64_t*)(d + off_at), n, &h, d + scratch_at, scratch_bytes, d + out_at, out_bytes,
-                            (const int64_t*)(d + doff_at), (int32_t*)(d + st_at), (lz4hip_unwrap_info_t*)(d + info_at)))) return rc;
-    HIP_TRY(hipMemcpyAsync(info, d + info_at, sizeof *info, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(dst_off, d + doff_at, (size_t)(8 * (n + 1)), hipMemcpyDeviceToHost, s));
-    if (n > 0) HIP_TRY(hipMemcpyAsync(status, d + st_at, (size_t)(4 * n), hipMemcpyDeviceToHost, s));
-    if (h.decoded_bytes > 0) HIP_TRY(hipMemcpyAsync(dst, d + out_at, (size_t)h.decoded_bytes, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return info->error;
+    HipBackend be = {};
+    if (int rc = stream_host_context(be)) return rc;
+    return unwrap_host(be, src, src_len, src_off, n, dst, dst_cap, dst_off, status, info);
 }
 
 int64_t lz4hip_streams_bound(int64_t n, int64_t src_len, int32_t block_size) { return streams_bound(n, src_len, block_size); }
@@ -2027,104 +1906,17 @@ int lz4hip_streams_decode_device(const void* src, int64_t src_len, const int64_t
 int lz4hip_streams_encode_host(const void* src, int64_t src_len, const int64_t* src_off, int64_t n, int32_t block_size, int mode,
                                void* dst, int64_t dst_cap, int64_t* dst_off)
 {
-    int rc = ensure_device();
-    if (rc) return rc;
-    if (src_len < 0 || n < 0 || !dst_off || (n > 0 && !src_off) || (src_len > 0 && n > 0 && (!src || !dst)))
-        return fail(LZ4HIP_E_ARGUMENT, "streams encode: negative size or NULL pointer");
-    // (the offsets are host memory here: bad ones are refused instead of encoded as empty items)
-    for (int64_t i = 0; i < n; i++)
-        if (src_off[i] < 0 || src_off[i + 1] < src_off[i] || src_off[i + 1] > src_len)
-            return fail(LZ4HIP_E_ARGUMENT, "streams encode: offsets decrease or fall outside [0, src_len]");
-    const int64_t bound = streams_bound(n, src_len, block_size);
-    if (n > 0 && dst_cap < bound) return fail(LZ4HIP_E_ARGUMENT, "streams encode: dst_cap < lz4hip_streams_bound");
-    if (n == 0 || src_len == 0) { for (int64_t i = 0; i <= n; i++) dst_off[i] = 0; return 0; }
-    HostContext* hc = nullptr;
-    hipStream_t s = nullptr;
-    if ((rc = stream_host_context(hc, s))) return rc;
-    // device image: [source | offsets | output | output offsets | scratch]
-    const int64_t scratch_bytes = lz4hip_streams_encode_scratch_bytes(n, src_len, block_size);
-    Carver image;
-    image.take(src_len);
-    const int64_t off_at = image.take(8 * (n + 1)), out_at = image.take(bound), doff_at = image.take(8 * (n + 1)), scratch_at = image.take(scratch_bytes);
-    if ((rc = hc->scratch.reserve((size_t)image.at))) return rc;
-    uint8_t* const d = (uint8_t*)hc->scratch.p;
-    HIP_TRY(hipMemcpyAsync(d, src, (size_t)src_len, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d + off_at, src_off, (size_t)(8 * (n + 1)), hipMemcpyHostToDevice, s));
-    HipBackend be = { s };
-    if ((rc = streams_encode(be, d, src_len, (const int64_t*)(d + off_at), n, block_size, mode, d + out_at, bound, (int64_t*)(d + doff_at),
-                             d + scratch_at, scratch_bytes))) return rc;
-    HIP_TRY(hipMemcpyAsync(dst_off, d + doff_at, (size_t)(8 * (n + 1)), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    const int64_t total = dst_off[n] < dst_cap ? dst_off[n] : dst_cap;
-    if (total > 0) HIP_TRY(hipMemcpyAsync(dst, d + out_at, (size_t)total, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return 0;
+    HipBackend be = {};
+    if (int rc = stream_host_context(be)) return rc;
+    return streams_encode_host(be, src, src_len, src_off, n, block_size, mode, dst, dst_cap, dst_off);
 }
 
 int lz4hip_streams_decode_host(const void* src, int64_t src_len, const int64_t* src_off, int64_t n, void* dst, int64_t dst_cap, int64_t* dst_off,
                                int32_t* status, int64_t* error_offset, lz4hip_streams_info_t* info)
 {
-    int rc = ensure_device();
-    if (rc) return rc;
-    if (src_len < 0 || n < 0 || dst_cap < 0 || !dst_off || !info || (n > 0 && (!src_off || !status || !error_offset)) || (src_len > 0 && !src))
-        return fail(LZ4HIP_E_ARGUMENT, "streams decode: negative size or NULL pointer");
-    if (n == 0) {
-        lz4hip_streams_info_t r = {};
-        r.first_error = r.error_offset = -1;
-        *info = r;
-        dst_off[0] = 0;
-        return 0;
-    }
-    HostContext* hc = nullptr;
-    hipStream_t s = nullptr;
-    if ((rc = stream_host_context(hc, s))) return rc;
-    // device image: [source | offsets | output offsets | statuses | error offsets | info | output | tables]; indexed again after tables
-    // that were too small or an image that had to grow
-    Carver image;
-    image.take(src_len);
-    const int64_t off_at = image.take(8 * (n + 1)), doff_at = image.take(8 * (n + 1)), st_at = image.take(4 * n), eo_at = image.take(8 * n),
-                  info_at = image.take(256), out_at = image.at;
-    HipBackend be = { s };
-    int64_t max_chunks = src_len / 4096 + n + 16, out_bytes = dst_cap < 4 * src_len ? dst_cap : 4 * src_len, table_at = 0, table_bytes = 0;
-    lz4hip_streams_info_t h = {};
-    uint8_t* d = nullptr;
-    for (int attempt = 0;; attempt++) {
-        table_bytes = streams_decode_scratch_bytes(n, max_chunks);
-        Carver tail = image;
-        tail.take(out_bytes);
-        table_at = tail.take(table_bytes);
-        if ((rc = hc->scratch.reserve((size_t)tail.at))) return rc;
-        d = (uint8_t*)hc->scratch.p;
-        if (src_len > 0) HIP_TRY(hipMemcpyAsync(d, src, (size_t)src_len, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(d + off_at, src_off, (size_t)(8 * (n + 1)), hipMemcpyHostToDevice, s));
-        if ((rc = streams_index(be, d, src_len, (const int64_t*)(d + off_at), n, max_chunks, (int64_t*)(d + doff_at), (int32_t*)(d + st_at),
-                                (int64_t*)(d + eo_at), d + table_at, table_bytes, (lz4hip_streams_info_t*)(d + info_at)))) return rc;
-        HIP_TRY(hipMemcpyAsync(&h, d + info_at, sizeof h, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        if (attempt >= 2) break;
-        if (h.error == LZ4HIP_STREAM_TABLE_FULL) { max_chunks = h.chunks; continue; }
-        if (h.decoded_bytes > dst_cap) break;
-        if (h.decoded_bytes > out_bytes) { out_bytes = h.decoded_bytes; continue; }
-        break;
-    }
-    *info = h;
-    if (h.error == LZ4HIP_STREAM_TABLE_FULL) return fail(LZ4HIP_E_DEVICE, "streams decode: the header walk did not settle");
-    if (h.decoded_bytes > dst_cap || h.decoded_bytes > out_bytes) {
-        HIP_TRY(hipMemcpyAsync(dst_off, d + doff_at, (size_t)(8 * (n + 1)), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(status, d + st_at, (size_t)(4 * n), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(error_offset, d + eo_at, (size_t)(8 * n), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        return fail(LZ4HIP_E_ARGUMENT, "streams decode: dst_cap < decoded_bytes (reported in info->decoded_bytes)");
-    }
-    if ((rc = streams_decode(be, d, src_len, (const int64_t*)(d + off_at), n, &h, max_chunks, d + table_at, table_bytes, d + out_at, out_bytes,
-                             (const int64_t*)(d + doff_at), (int32_t*)(d + st_at), (int64_t*)(d + eo_at), (lz4hip_streams_info_t*)(d + info_at)))) return rc;
-    HIP_TRY(hipMemcpyAsync(info, d + info_at, sizeof *info, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(dst_off, d + doff_at, (size_t)(8 * (n + 1)), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(status, d + st_at, (size_t)(4 * n), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(error_offset, d + eo_at, (size_t)(8 * n), hipMemcpyDeviceToHost, s));
-    if (h.decoded_bytes > 0) HIP_TRY(hipMemcpyAsync(dst, d + out_at, (size_t)h.decoded_bytes, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return info->error;
+    HipBackend be = {};
+    if (int rc = stream_host_context(be)) return rc;
+    return streams_decode_host(be, src, src_len, src_off, n, dst, dst_cap, dst_off, status, error_offset, info);
 }
 
 }  // extern "C"

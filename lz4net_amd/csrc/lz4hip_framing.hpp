@@ -10,6 +10,13 @@
 //     int  last_error()                              0, or the failure of a launch since the last look
 //     int  fail(code, text)                          records the text, returns the code
 //
+// and, for the host-pointer calls at the end (*_host) alone, the staging of caller memory in a device image:
+//
+//     int  reserve(bytes, base&)                     an image of at least `bytes` bytes; base may change whenever the image grows
+//     int  upload(dev, host, bytes)                  copies in stream order
+//     int  download(host, dev, bytes)
+//     int  sync()                                    waits for the stream
+//
 // Each operation is a front (argument checks, the caller's scratch laid out into the kernels' argument structs) over a sequence
 // (*_run: structs in, launches out); the emulator's tests enter at either.
 #pragma once
@@ -588,6 +595,261 @@ int streams_decode(B& be, const void* src, int64_t src_len, const int64_t* src_o
     StreamsInfo from_index;
     memcpy(&from_index, &h, sizeof from_index);
     return streams_decode_run(be, a, t, from_index, (uint8_t*)dst, (StreamsInfo*)info);
+}
+
+// ---- the host-pointer calls ------------------------------------------------------------------------------------------------------------
+// Each stages its arguments in ONE device image, runs the device path above on it and copies the results out.  An image is a Carver's
+// walk over no buffer -- its pieces are offsets, good for any base -- plus the base of the backend's reserve.  That base may move
+// whenever the image grows: a decoder that reserves again stages its source again, and keeps no pointer into the image across it.
+
+// a call's per-item arrays on the host and their pieces of the image
+struct Items { int64_t n; int64_t* dst_off; int64_t doff_at; int32_t* status; int64_t st_at; int64_t* error_offset; int64_t eo_at; };
+
+template <class B>
+struct Image {
+    B& be;
+    uint8_t* d = nullptr;
+    int64_t* i64(int64_t piece) const { return (int64_t*)(d + piece); }
+    int32_t* i32(int64_t piece) const { return (int32_t*)(d + piece); }
+    int reserve(int64_t bytes) { return be.reserve((size_t)bytes, d); }
+    int upload(int64_t piece, const void* host, int64_t bytes) { return be.upload(d + piece, host, (size_t)bytes); }
+    int download(void* host, int64_t piece, int64_t bytes) { return be.download(host, d + piece, (size_t)bytes); }
+    // the source, which is the image's first piece, and the n + 1 offsets of a call that has any
+    int upload_source(const void* src, int64_t src_len, const int64_t* src_off = nullptr, int64_t n = 0, int64_t off_at = -1)
+    {
+        if (src_len > 0) LZ4HIP_FRAMING_TRY(upload(0, src, src_len));
+        return off_at < 0 ? 0 : upload(off_at, src_off, 8 * (n + 1));
+    }
+    // the per-item arrays: n + 1 output offsets, then n statuses (wrap: results) and n error offsets where the caller has such an array
+    int download_items(const Items& it)
+    {
+        LZ4HIP_FRAMING_TRY(download(it.dst_off, it.doff_at, 8 * (it.n + 1)));
+        if (it.status && it.n > 0) LZ4HIP_FRAMING_TRY(download(it.status, it.st_at, 4 * it.n));
+        if (it.error_offset) LZ4HIP_FRAMING_TRY(download(it.error_offset, it.eo_at, 8 * it.n));
+        return 0;
+    }
+    // an encoder's output: the total has arrived on the host, the bytes follow
+    int download_encoded(void* dst, int64_t out_at, int64_t total)
+    {
+        if (total > 0) LZ4HIP_FRAMING_TRY(download(dst, out_at, total));
+        return be.sync();
+    }
+    // a decoder's results: the final info, the per-item arrays where there are any, the bytes
+    template <class Info>
+    int download_decoded(Info* info, int64_t info_at, void* dst, int64_t out_at, int64_t decoded_bytes, const Items* it = nullptr)
+    {
+        LZ4HIP_FRAMING_TRY(download(info, info_at, sizeof *info));
+        if (it) LZ4HIP_FRAMING_TRY(download_items(*it));
+        if (decoded_bytes > 0) LZ4HIP_FRAMING_TRY(download(dst, out_at, decoded_bytes));
+        return be.sync();
+    }
+};
+
+// The two LZ4Stream decoders index until their guesses hold.  `index` lays the image out for the current max_chunks and out_bytes,
+// stages the source, runs the index and queues the download of its info into h.  A full table is indexed again with the count it
+// reported, an output that has to grow with the size it reported: three passes at most, whatever they went on.  A size above dst_cap
+// ends the loop at once; the caller refuses it, as it does a table still full after the third pass.
+template <class B, class Info, class Index>
+int settle(B& be, int64_t dst_cap, int64_t& max_chunks, int64_t& out_bytes, const Info& h, Index index)
+{
+    for (int attempt = 0;; attempt++) {
+        LZ4HIP_FRAMING_TRY(index());
+        LZ4HIP_FRAMING_TRY(be.sync());
+        if (attempt >= 2) return 0;
+        if (h.error == LZ4HIP_STREAM_TABLE_FULL) max_chunks = h.chunks;
+        else if (h.decoded_bytes > dst_cap || h.decoded_bytes <= out_bytes) return 0;
+        else out_bytes = h.decoded_bytes;
+    }
+}
+
+inline int64_t guessed_output(int64_t src_len, int64_t dst_cap) { return dst_cap < 4 * src_len ? dst_cap : 4 * src_len; }
+
+template <class B>
+int stream_encode_host(B& be, const void* src, int64_t src_len, int32_t block_size, int mode, void* dst, int64_t dst_cap, int64_t* dst_len)
+{
+    if (src_len < 0 || !dst_len || (src_len > 0 && (!src || !dst))) return be.fail(LZ4HIP_E_ARGUMENT, "stream encode: negative size or NULL pointer");
+    const int64_t bound = stream_bound(src_len, block_size);
+    if (dst_cap < bound) return be.fail(LZ4HIP_E_ARGUMENT, "stream encode: dst_cap < lz4hip_stream_bound");
+    if (src_len == 0) { *dst_len = 0; return 0; }
+    // device image: [source | stream | scratch | length]
+    const int64_t scratch_bytes = stream_encode_scratch(nullptr, src_len, stream_block(block_size)).bytes;
+    Carver c;
+    c.take(src_len);
+    const int64_t out_at = c.take(bound), scratch_at = c.take(scratch_bytes), len_at = c.take(256);
+    Image<B> im = { be };
+    LZ4HIP_FRAMING_TRY(im.reserve(c.at));
+    LZ4HIP_FRAMING_TRY(im.upload_source(src, src_len));
+    LZ4HIP_FRAMING_TRY(stream_encode(be, im.d, src_len, block_size, mode, im.d + out_at, bound, im.i64(len_at), im.d + scratch_at, scratch_bytes));
+    int64_t total = 0;
+    LZ4HIP_FRAMING_TRY(im.download(&total, len_at, sizeof total));
+    LZ4HIP_FRAMING_TRY(be.sync());
+    LZ4HIP_FRAMING_TRY(im.download_encoded(dst, out_at, total));
+    *dst_len = total;
+    return 0;
+}
+
+// On dst_cap < decoded_bytes only *info is filled: there are no per-item arrays.
+template <class B>
+int stream_decode_host(B& be, const void* src, int64_t src_len, void* dst, int64_t dst_cap, lz4hip_stream_info_t* info)
+{
+    if (src_len < 0 || dst_cap < 0 || !info || (src_len > 0 && !src)) return be.fail(LZ4HIP_E_ARGUMENT, "stream decode: negative size or NULL pointer");
+    // device image: [source | info | output | table]
+    Image<B> im = { be };
+    int64_t max_chunks = (src_len + 4095) / 4096 + 16, out_bytes = guessed_output(src_len, dst_cap), info_at = 0, out_at = 0, table_at = 0, table_bytes = 0;
+    lz4hip_stream_info_t h = {};
+    LZ4HIP_FRAMING_TRY(settle(be, dst_cap, max_chunks, out_bytes, h, [&] {
+        table_bytes = stream_decode_scratch_bytes(max_chunks);
+        Carver c;
+        c.take(src_len);
+        info_at = c.take(256); out_at = c.take(out_bytes); table_at = c.take(table_bytes);
+        LZ4HIP_FRAMING_TRY(im.reserve(c.at));
+        LZ4HIP_FRAMING_TRY(im.upload_source(src, src_len));
+        LZ4HIP_FRAMING_TRY(stream_index(be, im.d, src_len, max_chunks, im.d + table_at, table_bytes, (lz4hip_stream_info_t*)(im.d + info_at)));
+        return im.download(&h, info_at, sizeof h);
+    }));
+    *info = h;
+    if (h.error == LZ4HIP_STREAM_TABLE_FULL) return be.fail(LZ4HIP_E_DEVICE, "stream decode: the header walk did not settle");
+    if (h.decoded_bytes > dst_cap) return be.fail(LZ4HIP_E_ARGUMENT, "stream decode: dst_cap < decoded_bytes (reported in info->decoded_bytes)");
+    LZ4HIP_FRAMING_TRY(stream_decode(be, im.d, &h, max_chunks, im.d + table_at, table_bytes, im.d + out_at, out_bytes,
+                                     (lz4hip_stream_info_t*)(im.d + info_at)));
+    LZ4HIP_FRAMING_TRY(im.download_decoded(info, info_at, dst, out_at, h.decoded_bytes));
+    return info->error;
+}
+
+template <class B>
+int wrap_host(B& be, const void* src, int64_t src_len, const int64_t* src_off, int64_t n, int mode, void* dst, int64_t dst_cap, int64_t* dst_off,
+              int32_t* result)
+{
+    if (src_len < 0 || n < 0 || !dst_off || (n > 0 && (!src_off || !dst)) || (src_len > 0 && !src))
+        return be.fail(LZ4HIP_E_ARGUMENT, "wrap: negative size or NULL pointer");
+    const int64_t bound = wrap_bound(n, src_len);
+    if (dst_cap < bound) return be.fail(LZ4HIP_E_ARGUMENT, "wrap: dst_cap < lz4hip_wrap_bound");
+    if (n == 0) { dst_off[0] = 0; return 0; }
+    // device image: [source | offsets | output | output offsets | results | scratch]
+    const int64_t scratch_bytes = wrap_scratch(nullptr, n, src_len).bytes;
+    Carver c;
+    c.take(src_len);
+    const int64_t off_at = c.take(8 * (n + 1)), out_at = c.take(bound), doff_at = c.take(8 * (n + 1)), res_at = c.take(4 * n),
+                  scratch_at = c.take(scratch_bytes);
+    Image<B> im = { be };
+    LZ4HIP_FRAMING_TRY(im.reserve(c.at));
+    LZ4HIP_FRAMING_TRY(im.upload_source(src, src_len, src_off, n, off_at));
+    LZ4HIP_FRAMING_TRY(wrap_encode(be, im.d, src_len, im.i64(off_at), n, mode, im.d + out_at, bound, im.i64(doff_at),
+                                   im.i32(res_at), im.d + scratch_at, scratch_bytes));
+    LZ4HIP_FRAMING_TRY(im.download_items({ n, dst_off, doff_at, result, res_at, nullptr, 0 }));
+    LZ4HIP_FRAMING_TRY(be.sync());
+    return im.download_encoded(dst, out_at, dst_off[n] < dst_cap ? dst_off[n] : dst_cap);
+}
+
+// No table to outgrow, so two passes: the guessed output, then the size the first one reported.  On dst_cap < decoded_bytes the index's
+// offsets and statuses are the caller's with the info: the Python wrappers' size query (dst_cap = 0) reads them.
+template <class B>
+int unwrap_host(B& be, const void* src, int64_t src_len, const int64_t* src_off, int64_t n, void* dst, int64_t dst_cap, int64_t* dst_off, int32_t* status,
+                lz4hip_unwrap_info_t* info)
+{
+    if (src_len < 0 || n < 0 || dst_cap < 0 || !dst_off || !info || (n > 0 && (!src_off || !status)) || (src_len > 0 && !src))
+        return be.fail(LZ4HIP_E_ARGUMENT, "unwrap: negative size or NULL pointer");
+    // device image: [source | offsets | output offsets | statuses | info | scratch | output], the output not rounded up
+    const int64_t scratch_bytes = unwrap_scratch_bytes(n);
+    Carver c;
+    c.take(src_len);
+    const int64_t off_at = c.take(8 * (n + 1)), doff_at = c.take(8 * (n + 1)), st_at = c.take(4 * n), info_at = c.take(256),
+                  scratch_at = c.take(scratch_bytes), out_at = c.at;
+    const Items items = { n, dst_off, doff_at, status, st_at, nullptr, 0 };
+    Image<B> im = { be };
+    int64_t out_bytes = guessed_output(src_len, dst_cap);
+    lz4hip_unwrap_info_t h = {};
+    for (int attempt = 0; attempt < 2; attempt++) {
+        LZ4HIP_FRAMING_TRY(im.reserve(out_at + out_bytes));
+        LZ4HIP_FRAMING_TRY(im.upload_source(src, src_len, src_off, n, off_at));
+        LZ4HIP_FRAMING_TRY(unwrap_index(be, im.d, src_len, im.i64(off_at), n, im.i64(doff_at),
+                                        im.i32(st_at), im.d + scratch_at, scratch_bytes, (lz4hip_unwrap_info_t*)(im.d + info_at)));
+        LZ4HIP_FRAMING_TRY(im.download(&h, info_at, sizeof h));
+        LZ4HIP_FRAMING_TRY(be.sync());
+        if (h.decoded_bytes <= out_bytes || h.decoded_bytes > dst_cap) break;
+        out_bytes = h.decoded_bytes;
+    }
+    *info = h;
+    if (h.decoded_bytes > dst_cap || h.decoded_bytes > out_bytes) {
+        LZ4HIP_FRAMING_TRY(im.download_items(items));
+        LZ4HIP_FRAMING_TRY(be.sync());
+        return be.fail(LZ4HIP_E_ARGUMENT, "unwrap: dst_cap < decoded_bytes (reported in info->decoded_bytes)");
+    }
+    LZ4HIP_FRAMING_TRY(unwrap_decode(be, im.d, src_len, im.i64(off_at), n, &h, im.d + scratch_at, scratch_bytes, im.d + out_at, out_bytes,
+                                     im.i64(doff_at), im.i32(st_at), (lz4hip_unwrap_info_t*)(im.d + info_at)));
+    LZ4HIP_FRAMING_TRY(im.download_decoded(info, info_at, dst, out_at, h.decoded_bytes, &items));
+    return info->error;
+}
+
+template <class B>
+int streams_encode_host(B& be, const void* src, int64_t src_len, const int64_t* src_off, int64_t n, int32_t block_size, int mode, void* dst,
+                        int64_t dst_cap, int64_t* dst_off)
+{
+    if (src_len < 0 || n < 0 || !dst_off || (n > 0 && !src_off) || (src_len > 0 && n > 0 && (!src || !dst)))
+        return be.fail(LZ4HIP_E_ARGUMENT, "streams encode: negative size or NULL pointer");
+    // (the offsets are host memory here: bad ones are refused instead of encoded as empty items)
+    for (int64_t i = 0; i < n; i++)
+        if (src_off[i] < 0 || src_off[i + 1] < src_off[i] || src_off[i + 1] > src_len)
+            return be.fail(LZ4HIP_E_ARGUMENT, "streams encode: offsets decrease or fall outside [0, src_len]");
+    const int64_t bound = streams_bound(n, src_len, block_size);
+    if (n > 0 && dst_cap < bound) return be.fail(LZ4HIP_E_ARGUMENT, "streams encode: dst_cap < lz4hip_streams_bound");
+    if (n == 0 || src_len == 0) { for (int64_t i = 0; i <= n; i++) dst_off[i] = 0; return 0; }
+    // device image: [source | offsets | output | output offsets | scratch]
+    const int64_t scratch_bytes = streams_encode_scratch(nullptr, n, src_len, stream_block(block_size)).bytes;
+    Carver c;
+    c.take(src_len);
+    const int64_t off_at = c.take(8 * (n + 1)), out_at = c.take(bound), doff_at = c.take(8 * (n + 1)), scratch_at = c.take(scratch_bytes);
+    Image<B> im = { be };
+    LZ4HIP_FRAMING_TRY(im.reserve(c.at));
+    LZ4HIP_FRAMING_TRY(im.upload_source(src, src_len, src_off, n, off_at));
+    LZ4HIP_FRAMING_TRY(streams_encode(be, im.d, src_len, im.i64(off_at), n, block_size, mode, im.d + out_at, bound,
+                                      im.i64(doff_at), im.d + scratch_at, scratch_bytes));
+    LZ4HIP_FRAMING_TRY(im.download_items({ n, dst_off, doff_at, nullptr, 0, nullptr, 0 }));
+    LZ4HIP_FRAMING_TRY(be.sync());
+    return im.download_encoded(dst, out_at, dst_off[n] < dst_cap ? dst_off[n] : dst_cap);
+}
+
+// On dst_cap < decoded_bytes the index's offsets, statuses and error offsets are the caller's with the info, as in unwrap_host.
+template <class B>
+int streams_decode_host(B& be, const void* src, int64_t src_len, const int64_t* src_off, int64_t n, void* dst, int64_t dst_cap, int64_t* dst_off,
+                        int32_t* status, int64_t* error_offset, lz4hip_streams_info_t* info)
+{
+    if (src_len < 0 || n < 0 || dst_cap < 0 || !dst_off || !info || (n > 0 && (!src_off || !status || !error_offset)) || (src_len > 0 && !src))
+        return be.fail(LZ4HIP_E_ARGUMENT, "streams decode: negative size or NULL pointer");
+    if (n == 0) { lz4hip_streams_info_t r = {}; r.first_error = r.error_offset = -1; *info = r; dst_off[0] = 0; return 0; }
+    // device image: [source | offsets | output offsets | statuses | error offsets | info | output | tables]
+    Carver head;
+    head.take(src_len);
+    const int64_t off_at = head.take(8 * (n + 1)), doff_at = head.take(8 * (n + 1)), st_at = head.take(4 * n), eo_at = head.take(8 * n),
+                  info_at = head.take(256), out_at = head.at;
+    const Items items = { n, dst_off, doff_at, status, st_at, error_offset, eo_at };
+    Image<B> im = { be };
+    int64_t max_chunks = src_len / 4096 + n + 16, out_bytes = guessed_output(src_len, dst_cap), table_at = 0, table_bytes = 0;
+    lz4hip_streams_info_t h = {};
+    LZ4HIP_FRAMING_TRY(settle(be, dst_cap, max_chunks, out_bytes, h, [&] {
+        table_bytes = streams_decode_scratch_bytes(n, max_chunks);
+        Carver c = head;
+        c.take(out_bytes);
+        table_at = c.take(table_bytes);
+        LZ4HIP_FRAMING_TRY(im.reserve(c.at));
+        LZ4HIP_FRAMING_TRY(im.upload_source(src, src_len, src_off, n, off_at));
+        LZ4HIP_FRAMING_TRY(streams_index(be, im.d, src_len, im.i64(off_at), n, max_chunks, im.i64(doff_at),
+                                         im.i32(st_at), im.i64(eo_at), im.d + table_at, table_bytes,
+                                         (lz4hip_streams_info_t*)(im.d + info_at)));
+        return im.download(&h, info_at, sizeof h);
+    }));
+    *info = h;
+    if (h.error == LZ4HIP_STREAM_TABLE_FULL) return be.fail(LZ4HIP_E_DEVICE, "streams decode: the header walk did not settle");
+    if (h.decoded_bytes > dst_cap || h.decoded_bytes > out_bytes) {
+        LZ4HIP_FRAMING_TRY(im.download_items(items));
+        LZ4HIP_FRAMING_TRY(be.sync());
+        return be.fail(LZ4HIP_E_ARGUMENT, "streams decode: dst_cap < decoded_bytes (reported in info->decoded_bytes)");
+    }
+    LZ4HIP_FRAMING_TRY(streams_decode(be, im.d, src_len, im.i64(off_at), n, &h, max_chunks, im.d + table_at, table_bytes, im.d + out_at,
+                                      out_bytes, im.i64(doff_at), im.i32(st_at), im.i64(eo_at),
+                                      (lz4hip_streams_info_t*)(im.d + info_at)));
+    LZ4HIP_FRAMING_TRY(im.download_decoded(info, info_at, dst, out_at, h.decoded_bytes, &items));
+    return info->error;
 }
 
 #undef LZ4HIP_FRAMING_TRY

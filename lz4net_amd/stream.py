@@ -240,7 +240,8 @@ def _decompress_stream_device(t):
 _BAD_OFFSETS = "offsets are invalid for the given buffer"
 
 
-def _check_streams_device(buf, offsets):
+def _check_device_batch(buf, offsets):
+    """a batch on the device: a 1-D uint8 CUDA tensor and its int64 offsets[n + 1] (wrap.py's batches are the same)"""
     import torch
     if not isinstance(buf, torch.Tensor) or not buf.is_cuda or buf.dtype != torch.uint8 or buf.dim() != 1:
         raise ArgumentException("the buffer must be a 1-D uint8 CUDA tensor")
@@ -270,7 +271,7 @@ def compress_streams_device(buf, offsets, block_size: int = DEFAULT_BLOCK_SIZE, 
     device, on torch's current stream -> (packed, packed_offsets): packed_offsets[i] is where item i's stream starts.  The chunks of
     all items are one batch of the block encoder.  Waits for the device once, to learn the total."""
     import torch
-    buf, offsets = _check_streams_device(buf, offsets)
+    buf, offsets = _check_device_batch(buf, offsets)
     block_size = max(16, int(block_size))
     with torch.cuda.device(buf.device):
         L = _lib.lib()
@@ -299,7 +300,7 @@ def decompress_streams_device(packed, offsets, check: bool = True):
     within the item), with check=False the per-item statuses (LZ4HIP_STREAM_*, 0 = fine; LZ4HIP_E_ARGUMENT for bad offsets) come back
     as a third value instead.  Waits for the device twice: to size the output, and for the outcome."""
     import torch
-    packed, offsets = _check_streams_device(packed, offsets)
+    packed, offsets = _check_device_batch(packed, offsets)
     with torch.cuda.device(packed.device):
         L = _lib.lib()
         dev = packed.device
@@ -335,7 +336,8 @@ def decompress_streams_device(packed, offsets, check: bool = True):
         return out, out_off
 
 
-def _check_streams_host(buf, offsets):
+def _check_host_batch(buf, offsets):
+    """the same batch in host memory; bytes-like buffers are taken as uint8 arrays"""
     if isinstance(buf, (bytes, bytearray, memoryview)):
         buf = np.frombuffer(buf, dtype=np.uint8)
     if not isinstance(buf, np.ndarray) or buf.dtype != np.uint8 or buf.ndim != 1:
@@ -349,7 +351,7 @@ def _check_streams_host(buf, offsets):
 
 def compress_streams_host(buf, offsets, block_size: int = DEFAULT_BLOCK_SIZE, high_compression: bool = False):
     """compress_streams_device for host arrays, through lz4hip_streams_encode_host -> (packed, packed_offsets) as numpy arrays."""
-    buf, offsets = _check_streams_host(buf, offsets)
+    buf, offsets = _check_host_batch(buf, offsets)
     block_size = max(16, int(block_size))
     L = _lib.lib()
     n = offsets.size - 1
@@ -366,7 +368,7 @@ def compress_streams_host(buf, offsets, block_size: int = DEFAULT_BLOCK_SIZE, hi
 def decompress_streams_host(packed, offsets, check: bool = True):
     """decompress_streams_device for host arrays, through lz4hip_streams_decode_host -> (data, data_offsets), or (data, data_offsets,
     status) with check=False."""
-    packed, offsets = _check_streams_host(packed, offsets)
+    packed, offsets = _check_host_batch(packed, offsets)
     L = _lib.lib()
     n = offsets.size - 1
     out_off = np.empty(n + 1, np.int64)

@@ -13,6 +13,7 @@ import numpy as np
 
 from . import _lib
 from .codec import _CORRUPT, ArgumentException
+from .stream import _check_device_batch, _check_host_batch
 
 _WRAP_INVALID = "inputBuffer size of inputLength is invalid"
 _MESSAGES = {
@@ -32,25 +33,12 @@ def unwrap_error(status: int, index: int) -> ArgumentException:
 
 # ---- device-resident batches (torch CUDA tensors, torch's current stream) ------------------------------------------------------
 
-def _check_device(buf, offsets):
-    import torch
-    if not isinstance(buf, torch.Tensor) or not buf.is_cuda or buf.dtype != torch.uint8 or buf.dim() != 1:
-        raise ArgumentException("the buffer must be a 1-D uint8 CUDA tensor")
-    if not isinstance(offsets, torch.Tensor) or not offsets.is_cuda or offsets.dtype != torch.int64 or offsets.dim() != 1:
-        raise ArgumentException("offsets must be a 1-D int64 CUDA tensor")
-    if offsets.numel() < 1:
-        raise ArgumentException("offsets must hold n + 1 entries")
-    if offsets.device != buf.device:
-        raise ArgumentException("the buffer and the offsets must be on the same device")
-    return buf.contiguous(), offsets.contiguous()
-
-
 def wrap_device(src, offsets, high_compression: bool = False):
     """[LZ4Codec.Wrap(m) for m in messages] (WrapHC with high_compression) for the messages src[offsets[i]:offsets[i + 1]] of a CUDA
     tensor, on the device, on torch's current stream -> (packed, packed_offsets): packed_offsets[i] is where wrapped message i starts.
     Waits for the device once, to learn the total."""
     import torch
-    src, offsets = _check_device(src, offsets)
+    src, offsets = _check_device_batch(src, offsets)
     with torch.cuda.device(src.device):
         L = _lib.lib()
         dev = src.device
@@ -76,7 +64,7 @@ def unwrap_device(packed, offsets, check: bool = True):
     message raises what Unwrap raises for it (ArgumentException, .message_index = its index), with check=False the per-message statuses
     (LZ4HIP_WRAP_*, 0 = fine) come back as a third value instead.  Waits for the device twice: to size the output, and for the outcome."""
     import torch
-    packed, offsets = _check_device(packed, offsets)
+    packed, offsets = _check_device_batch(packed, offsets)
     with torch.cuda.device(packed.device):
         L = _lib.lib()
         dev = packed.device
@@ -107,21 +95,9 @@ def unwrap_device(packed, offsets, check: bool = True):
 
 # ---- host-resident batches (numpy; the lz4hip_wrap_host / lz4hip_unwrap_host pair) -----------------------------------------------
 
-def _check_host(buf, offsets):
-    if isinstance(buf, (bytes, bytearray, memoryview)):
-        buf = np.frombuffer(buf, dtype=np.uint8)
-    if not isinstance(buf, np.ndarray) or buf.dtype != np.uint8 or buf.ndim != 1:
-        raise ArgumentException("the buffer must be a 1-D uint8 array")
-    if not isinstance(offsets, np.ndarray) or offsets.dtype != np.int64 or offsets.ndim != 1:
-        raise ArgumentException("offsets must be a 1-D int64 array")
-    if offsets.size < 1:
-        raise ArgumentException("offsets must hold n + 1 entries")
-    return np.ascontiguousarray(buf), np.ascontiguousarray(offsets)
-
-
 def wrap_host(src, offsets, high_compression: bool = False):
     """wrap_device for host arrays, through lz4hip_wrap_host -> (packed, packed_offsets) as numpy arrays."""
-    src, offsets = _check_host(src, offsets)
+    src, offsets = _check_host_batch(src, offsets)
     L = _lib.lib()
     n = offsets.size - 1
     bound = L.lz4hip_wrap_bound(n, src.size)
@@ -138,7 +114,7 @@ def wrap_host(src, offsets, high_compression: bool = False):
 def unwrap_host(packed, offsets, check: bool = True):
     """unwrap_device for host arrays, through lz4hip_unwrap_host -> (data, data_offsets), or (data, data_offsets, status) with
     check=False."""
-    packed, offsets = _check_host(packed, offsets)
+    packed, offsets = _check_host_batch(packed, offsets)
     L = _lib.lib()
     n = offsets.size - 1
     out_off = np.empty(n + 1, np.int64)

@@ -207,8 +207,16 @@ class StreamsInfo(C.Structure):
                 ("error_offset", _I64), ("error", _I32), ("reserved", _I32)]
 
 
+class HostRun(C.Structure):
+    """EmuHostRun: the emulated device of an emu_host_* call -- the block codec's stand-in and the grids in, the backend's counters,
+    the state of its guard bytes and the recorded failure text out"""
+    _fields_ = [("results", _P), ("bytes", _P), ("grid_items", _I32), ("grid_copy", _I32), ("grid_walk", _I32), ("intact", _I32),
+                ("reserves", _I64), ("moves", _I64), ("uploads", _I64), ("downloads", _I64), ("syncs", _I64), ("passes", _I64),
+                ("image_bytes", _I64), ("error", C.c_char * 160)]
+
+
 _FRAMING_STRUCTS = [StreamEncodeArgs, StreamTables, StreamInfo, WrapArgs, UnwrapTables, UnwrapArgs, UnwrapInfo, StreamsEncodeArgs,
-                    StreamsTables, StreamsDecodeArgs, StreamsInfo]
+                    StreamsTables, StreamsDecodeArgs, StreamsInfo, HostRun]
 _framing = None
 
 
@@ -250,9 +258,16 @@ def framing():
             "emu_lib_streams_encode": [ptr, i64, ptr, i64, i32, i32, ptr, i64, ptr, ptr, i64, ptr, ptr, i32, i32],
             "emu_lib_streams_index": [ptr, i64, ptr, i64, i64, ptr, ptr, ptr, ptr, i64, ptr, i32],
             "emu_lib_streams_decode": [ptr, i64, ptr, i64, ptr, i64, ptr, i64, ptr, i64, ptr, ptr, ptr, ptr, ptr, ptr, i32, i32],
+            # the host-pointer calls: the library's arguments, then a HostRun
+            "emu_host_stream_encode": [ptr, i64, i32, i32, ptr, i64, ptr, ptr],
+            "emu_host_stream_decode": [ptr, i64, ptr, i64, ptr, ptr],
+            "emu_host_wrap": [ptr, i64, ptr, i64, i32, ptr, i64, ptr, ptr, ptr],
+            "emu_host_unwrap": [ptr, i64, ptr, i64, ptr, i64, ptr, ptr, ptr, ptr],
+            "emu_host_streams_encode": [ptr, i64, ptr, i64, i32, i32, ptr, i64, ptr, ptr],
+            "emu_host_streams_decode": [ptr, i64, ptr, i64, ptr, i64, ptr, ptr, ptr, ptr, ptr],
         }.items():
             getattr(L, name).argtypes = args
-            getattr(L, name).restype = C.c_int if name in ("emu_stream_decode", "emu_streams_decode") or name.startswith("emu_lib_") else None
+            getattr(L, name).restype = C.c_int if name in ("emu_stream_decode", "emu_streams_decode") or name.startswith(("emu_lib_", "emu_host_")) else None
         L.emu_scratch_bytes.argtypes = [i32, i64, i64, i64]
         L.emu_scratch_bytes.restype = C.c_int64
         for name in ("emu_items_grid", "emu_copy_grid", "emu_walk_grid"):

@@ -1,14 +1,15 @@
 // emu_framing.hpp -- TEST INFRASTRUCTURE ONLY, included by emu_kernels.cpp.
 // C entry points that run the framing kernels (lz4hip_stream.hpp, lz4hip_wrap.hpp, lz4hip_streams.hpp) under the SIMT emulator
 // for tests/test_simt_framing.py: single kernels, and the library's own host code for the framing paths (lz4hip_framing.hpp: layouts,
-// grids and kernel sequences) over EmuBackend, with the block codec step replaced by arrays the test hands in.  The argument structs
-// are passed by pointer; tests/emu_helpers.py mirrors them with ctypes and checks the sizes against emu_framing_sizeof().  A grid
+// grids, kernel sequences and the staging of the host-pointer calls) over EmuBackend, with the block codec step replaced by arrays the
+// test hands in and the device image served from host memory.  The argument structs are passed by pointer; tests/emu_helpers.py mirrors them with ctypes and checks the sizes against emu_framing_sizeof().  A grid
 // argument of 0 means "the library's formula".
 #pragma once
 #include "lz4hip_framing.hpp"
 
 #include <string>
 #include <tuple>
+#include <vector>
 
 namespace emu_framing {
 
@@ -23,6 +24,8 @@ struct KernelCall {
     void operator()() const { std::apply(kernel, args); }
 };
 
+template <class K, class L> bool same_kernel(K k, L l) { return (void (*)())k == (void (*)())l; }
+
 // The device of lz4hip_framing.hpp's sequences, faked: the emulator's launcher, plain stores, and a block codec that hands out what
 // the test computed.
 struct EmuBackend {
@@ -35,6 +38,7 @@ struct EmuBackend {
     template <class... P, class... A>
     void launch(void (*kernel)(P...), Grid grid, unsigned threads, A&&... a)
     {
+        passes += same_kernel(kernel, stream_index_kernel) || same_kernel(kernel, unwrap_index_kernel) || same_kernel(kernel, streams_walk_kernel<false>);
         const int mine = grid.kind == kGridItems ? grid_items : (grid.kind == kGridCopy ? grid_copy : (grid.kind == kGridWalk ? grid_walk : 0));
         simt::launch(dim3(mine > 0 ? (unsigned)mine : grid.groups), dim3(threads), kStreamThreads * 8, KernelCall<P...>{ kernel, std::tuple<P...>{ P(a)... } });
     }
@@ -60,6 +64,47 @@ struct EmuBackend {
     }
     int last_error() { return 0; }
     int fail(int code, const char* what) { error = what; return code; }
+
+    // The staging image of the host-pointer calls: exactly the bytes asked for between guard bytes, at a multiple of 256 as a device
+    // allocation is.  A reserve that grows MOVES: the new block is a new allocation and the old one is filled with kStale and kept
+    // until the backend dies, so code that goes on using an old base reads kStale, and what it writes there shows in intact().
+    static constexpr size_t kGuard = 256;
+    static constexpr uint8_t kGuardByte = 0xC3, kFresh = 0xEE, kStale = 0xDD;
+    struct Block { std::vector<uint8_t> store; uint8_t* base; size_t bytes; };
+    std::vector<Block> blocks;
+    int64_t reserves = 0, moves = 0, uploads = 0, downloads = 0, syncs = 0, passes = 0;
+
+    int reserve(size_t bytes, uint8_t*& base)
+    {
+        reserves++;
+        if (blocks.empty() || bytes > blocks.back().bytes) {
+            if (!blocks.empty()) memset(blocks.back().base, kStale, blocks.back().bytes);
+            moves++;
+            blocks.emplace_back();
+            Block& b = blocks.back();
+            b.store.assign(bytes + 2 * kGuard + 256, kGuardByte);
+            b.base = (uint8_t*)(((uintptr_t)b.store.data() + kGuard + 255) / 256 * 256);
+            b.bytes = bytes;
+            memset(b.base, kFresh, bytes);
+        }
+        base = blocks.back().base;
+        return 0;
+    }
+    int upload(void* dev, const void* host, size_t bytes) { uploads++; memcpy(dev, host, bytes); return 0; }
+    int download(void* host, const void* dev, size_t bytes) { downloads++; memcpy(host, dev, bytes); return 0; }
+    int sync() { syncs++; return 0; }
+    // no byte outside any block's image was written, and none of a block that was given up
+    bool intact() const
+    {
+        for (size_t k = 0; k < blocks.size(); k++) {
+            const Block& b = blocks[k];
+            for (const uint8_t* p = b.store.data(); p < b.store.data() + b.store.size(); p++) {
+                const bool inside = p >= b.base && p < b.base + b.bytes;
+                if (inside ? (k + 1 < blocks.size() && *p != kStale) : *p != kGuardByte) return false;
+            }
+        }
+        return true;
+    }
 };
 
 inline EmuBackend backend(int grid_items, int grid_copy, int grid_walk = 0, const int32_t* results = nullptr, const uint8_t* bytes = nullptr)
@@ -70,6 +115,26 @@ inline EmuBackend backend(int grid_items, int grid_copy, int grid_walk = 0, cons
 }
 
 }  // namespace emu_framing
+
+// the host-pointer calls of lz4hip_framing.hpp (emu_host_*): what the emulated device is to do, and what it did
+struct EmuHostRun {
+    const int32_t* results; const uint8_t* bytes;            // the block codec's stand-in
+    int32_t grid_items, grid_copy, grid_walk, intact;        // intact: EmuBackend::intact() after the call
+    int64_t reserves, moves, uploads, downloads, syncs, passes, image_bytes;    // image_bytes: the last reserve's
+    char error[160];                                         // what fail() recorded
+};
+
+template <class Call>
+int emu_host_run(EmuHostRun* r, Call call)
+{
+    emu_framing::EmuBackend be = emu_framing::backend(r->grid_items, r->grid_copy, r->grid_walk, r->results, r->bytes);
+    const int rc = call(be);
+    r->intact = be.intact();
+    r->reserves = be.reserves; r->moves = be.moves; r->uploads = be.uploads; r->downloads = be.downloads; r->syncs = be.syncs; r->passes = be.passes;
+    r->image_bytes = be.blocks.empty() ? 0 : (int64_t)be.blocks.back().bytes;
+    snprintf(r->error, sizeof r->error, "%s", be.error.c_str());
+    return rc;
+}
 
 extern "C" {
 
@@ -87,6 +152,7 @@ int64_t emu_framing_sizeof(int which)
     case 8: return sizeof(StreamsTables);
     case 9: return sizeof(StreamsDecodeArgs);
     case 10: return sizeof(StreamsInfo);
+    case 11: return sizeof(EmuHostRun);
     case 100: return kScanTile;
     case 101: return kCopySpan;
     default: return -1;
@@ -310,6 +376,45 @@ int emu_lib_streams_decode(const void* src, int64_t src_len, const int64_t* src_
     emu_framing::EmuBackend be = emu_framing::backend(grid_items, grid_copy, 0, results, bytes);
     return framing::streams_decode(be, src, src_len, src_off, n, info_host, max_chunks, scratch, scratch_bytes, dst, dst_cap, dst_off, status,
                                    error_offset, info);
+}
+
+// ---- the host-pointer calls of lz4hip_framing.hpp: the library's argument lists, then an EmuHostRun ------------------------------------
+int emu_host_stream_encode(const void* src, int64_t src_len, int32_t block_size, int mode, void* dst, int64_t dst_cap, int64_t* dst_len, EmuHostRun* r)
+{
+    return emu_host_run(r, [&](emu_framing::EmuBackend& be) { return framing::stream_encode_host(be, src, src_len, block_size, mode, dst, dst_cap, dst_len); });
+}
+
+int emu_host_stream_decode(const void* src, int64_t src_len, void* dst, int64_t dst_cap, lz4hip_stream_info_t* info, EmuHostRun* r)
+{
+    return emu_host_run(r, [&](emu_framing::EmuBackend& be) { return framing::stream_decode_host(be, src, src_len, dst, dst_cap, info); });
+}
+
+int emu_host_wrap(const void* src, int64_t src_len, const int64_t* src_off, int64_t n, int mode, void* dst, int64_t dst_cap, int64_t* dst_off,
+                  int32_t* result, EmuHostRun* r)
+{
+    return emu_host_run(r, [&](emu_framing::EmuBackend& be) { return framing::wrap_host(be, src, src_len, src_off, n, mode, dst, dst_cap, dst_off, result); });
+}
+
+int emu_host_unwrap(const void* src, int64_t src_len, const int64_t* src_off, int64_t n, void* dst, int64_t dst_cap, int64_t* dst_off, int32_t* status,
+                    lz4hip_unwrap_info_t* info, EmuHostRun* r)
+{
+    return emu_host_run(r, [&](emu_framing::EmuBackend& be) { return framing::unwrap_host(be, src, src_len, src_off, n, dst, dst_cap, dst_off, status, info); });
+}
+
+int emu_host_streams_encode(const void* src, int64_t src_len, const int64_t* src_off, int64_t n, int32_t block_size, int mode, void* dst,
+                            int64_t dst_cap, int64_t* dst_off, EmuHostRun* r)
+{
+    return emu_host_run(r, [&](emu_framing::EmuBackend& be) {
+        return framing::streams_encode_host(be, src, src_len, src_off, n, block_size, mode, dst, dst_cap, dst_off);
+    });
+}
+
+int emu_host_streams_decode(const void* src, int64_t src_len, const int64_t* src_off, int64_t n, void* dst, int64_t dst_cap, int64_t* dst_off,
+                            int32_t* status, int64_t* error_offset, lz4hip_streams_info_t* info, EmuHostRun* r)
+{
+    return emu_host_run(r, [&](emu_framing::EmuBackend& be) {
+        return framing::streams_decode_host(be, src, src_len, src_off, n, dst, dst_cap, dst_off, status, error_offset, info);
+    });
 }
 
 }  // extern "C"

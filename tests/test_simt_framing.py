@@ -2,7 +2,8 @@
 (tests/simt/emu_framing.hpp): the int64 scan, the position-driven copy routine behind its five layouts, the header reader, and the
 library's own host code for the framing paths (lz4net_amd/csrc/lz4hip_framing.hpp: scratch layouts, grids, kernel sequences), once
 from the kernels' argument structs over arrays made here and once whole, from the C ABI's arguments over a scratch buffer of exactly
-the size the library asks for, with the block codec step replaced by arrays handed in here.  Every reference is plain Python /
+the size the library asks for, with the block codec step replaced by arrays handed in here; and the six host-pointer calls on top of
+them, over a device image in host memory (at the end of this file).  Every reference is plain Python /
 numpy written from the wire formats (LZ4Stream: src/LZ4/LZ4Stream.cs:162-312, Wrap: src/LZ4/LZ4Codec.cs:471-599), never from the
 kernels.  Every output buffer has guard bytes on both sides and is pre-filled with a pattern; bytes that belong to no segment must
 still hold it.  Every case runs with a grid of one workgroup, a small odd grid and the product's grid formula.  The `-m gpu` tests
@@ -1402,3 +1403,424 @@ def test_whole_calls_without_items():
         got = (final.items, final.chunks, final.compressed_chunks, final.decoded_bytes, final.first_error, final.error_offset, final.error, final.reserved)
         assert got == empty and (dst_off == FILL).all(), got
         assert untouched(scratch) and untouched(buf) and (status == FILL).all() and (error_offset == FILL).all()
+
+
+# ---- the host-pointer calls of lz4hip_framing.hpp (*_host) over a device image in host memory -----------------------------------------
+# Each call is compared with the device-path functions above (emu_lib_*) on the same input and the same faked codec arrays, and with
+# what the emulated backend counted: index passes, reserves and how many of them moved the image, copies in and out, waits.  The
+# backend's reserve moves whenever it grows and fills the block it gave up, so `intact` fails a call that wrote to a stale base and the
+# comparison one that read from it.
+def a256(v):
+    return -(-v // 256) * 256
+
+
+def host_run(results=None, codec_bytes=None, gi=0, gc=0, gw=0):
+    r = emu.HostRun(grid_items=gi, grid_copy=gc, grid_walk=gw)
+    r.keep = [np.array(list(results) + [0], np.int32) if results is not None else None, codec_bytes]
+    r.results = addr(r.keep[0]) if results is not None else None
+    r.bytes = addr(codec_bytes) if codec_bytes is not None else None
+    return r
+
+
+def counts(r):
+    return dict(passes=r.passes, reserves=r.reserves, moves=r.moves, uploads=r.uploads, downloads=r.downloads, syncs=r.syncs)
+
+
+def info_tuple(info):
+    return tuple(getattr(info, f[0]) for f in info._fields_)
+
+
+def poisoned(cls):
+    return cls(**{f[0]: FILL for f in cls._fields_})
+
+
+def forced_results(lens):
+    """results no encoder returns, of every kind: the rule is "compressed iff 0 < r < length" """
+    return [(ln // 2, 0, -1, ln, ln - 1, 1, ln + 1)[k % 7] for k, ln in enumerate(lens)]
+
+
+HOST_GRIDS = ((0, 0), (1, 1), (3, 3))
+
+
+@pytest.mark.parametrize("B,size", [(16, 0), (16, 1), (17, 1000), (128, 128 * 40 + 5), (4096, 70000)])
+def test_host_stream_encode(B, size):
+    L = emu.framing()
+    data = noise(size, B)
+    src = np.ascontiguousarray(np.concatenate([data, np.zeros(1, np.uint8)]))
+    n = -(-size // B)
+    bound = size + n * (1 + 2 * len(st.write_varint(B))) if size else 0
+    results = forced_results([min(B, size - k * B) for k in range(n)])
+    comp = noise(size + 16, 9)
+    for hc in (MODE_FAST, MODE_HC):
+        for gi, gc in HOST_GRIDS:
+            scratch, sptr, sbytes = lib_scratch(0, size, B)
+            want_len, want = filled(3), guarded(bound)
+            res = np.array(results + [0], np.int32)
+            assert L.emu_lib_stream_encode(addr(src), size, B, hc, want[1], bound, addr(want_len, 1), sptr, sbytes, addr(res), addr(comp), gi, gc) == 0
+            dst_len, (buf, ptr), r = filled(3), guarded(bound), host_run(results, comp, gi, gc)
+            assert L.emu_host_stream_encode(addr(src), size, B, hc, ptr, bound, addr(dst_len, 1), ref(r)) == 0 and r.intact
+            assert dst_len.tolist() == want_len.tolist() == [FILL, want_len[1], FILL]
+            same(buf, want[0], f"host stream encode {B} {size} {hc}")
+            if size == 0:                                                   # the short cut: *dst_len = 0 and no device at all
+                assert counts(r) == dict(passes=0, reserves=0, moves=0, uploads=0, downloads=0, syncs=0) and untouched(buf)
+                continue
+            assert counts(r) == dict(passes=0, reserves=1, moves=1, uploads=1, downloads=2, syncs=2)
+            assert r.image_bytes == a256(size) + a256(bound) + sbytes + 256
+
+
+def wrap_input(n, seed):
+    rng = np.random.default_rng(seed)
+    lens = [int(v) for v in rng.choice([0, 1, 7, 8, 40, 300, 5000], n)]
+    msgs = [noise(ln, k) for k, ln in enumerate(lens)]
+    off = np.zeros(n + 1, np.int64)
+    off[1:] = np.cumsum(lens)
+    src = np.ascontiguousarray(np.concatenate(msgs + [np.zeros(1, np.uint8)]))
+    return src, off, int(off[n]), lens
+
+
+@pytest.mark.parametrize("n", [1, 13, 300])
+def test_host_wrap(n):
+    L = emu.framing()
+    src, off, src_len, lens = wrap_input(n, n)
+    bound = src_len + 8 * n
+    enc, comp = forced_results(lens), noise(src_len + 16, 11)
+    for bad_offsets in (False, True):
+        if bad_offsets and n > 5:
+            off = off.copy()
+            off[3] = off[2] - 7
+            off[5] = src_len + 5
+        for gi, gc in HOST_GRIDS:
+            for with_result in (True, False):
+                scratch, sptr, sbytes = lib_scratch(2, n, src_len)
+                want_off, want_res, want = filled(n + 2), filled(n + 1, np.int32), guarded(bound)
+                e = np.array(enc + [0], np.int32)
+                assert L.emu_lib_wrap(addr(src), src_len, addr(off), n, MODE_FAST, want[1], bound, addr(want_off), addr(want_res), sptr, sbytes,
+                                      addr(e), addr(comp), gi, gc) == 0
+                dst_off, result, (buf, ptr), r = filled(n + 2), filled(n + 1, np.int32), guarded(bound), host_run(enc, comp, gi, gc)
+                assert L.emu_host_wrap(addr(src), src_len, addr(off), n, MODE_FAST, ptr, bound, addr(dst_off), addr(result) if with_result else None,
+                                       ref(r)) == 0 and r.intact
+                assert dst_off.tolist() == want_off.tolist() and dst_off[n + 1] == FILL
+                assert result.tolist() == want_res.tolist() if with_result else (result == FILL).all()
+                same(buf, want[0], f"host wrap {n} {bad_offsets}")
+                total = int(dst_off[n])
+                assert counts(r) == dict(passes=0, reserves=1, moves=1, uploads=1 + (src_len > 0), downloads=1 + with_result + (total > 0), syncs=2)
+                assert r.image_bytes == a256(src_len) + 2 * a256(8 * (n + 1)) + a256(bound) + a256(4 * n) + sbytes
+
+
+@pytest.mark.parametrize("B", [16, 128, 4096])
+def test_host_streams_encode(B):
+    L = emu.framing()
+    lens = [0, 0, 1, B - 1, 0, B, B + 1, 0, 5 * B + 3, 3 * B, 0]
+    n = len(lens)
+    items = [noise(ln, k) for k, ln in enumerate(lens)]
+    src = np.ascontiguousarray(np.concatenate(items + [np.zeros(1, np.uint8)]))
+    off = np.zeros(n + 1, np.int64)
+    off[1:] = np.cumsum(lens)
+    src_len = int(off[n])
+    cap = src_len // B + n
+    bound = src_len + cap * (1 + 2 * len(st.write_varint(B)))
+    chunk_lens = [min(B, ln - o) for ln in lens for o in range(0, ln, B)]
+    results = forced_results(chunk_lens) + [0] * (cap - len(chunk_lens))
+    comp = noise(src_len + 16, 12)
+    for hc in (MODE_FAST, MODE_HC):
+        for gi, gc in HOST_GRIDS:
+            scratch, sptr, sbytes = lib_scratch(4, n, src_len, B)
+            want_off, want = filled(n + 2), guarded(bound)
+            res = np.array(results + [0], np.int32)
+            assert L.emu_lib_streams_encode(addr(src), src_len, addr(off), n, B, hc, want[1], bound, addr(want_off), sptr, sbytes, addr(res), addr(comp), gi, gc) == 0
+            dst_off, (buf, ptr), r = filled(n + 2), guarded(bound), host_run(results, comp, gi, gc)
+            assert L.emu_host_streams_encode(addr(src), src_len, addr(off), n, B, hc, ptr, bound, addr(dst_off), ref(r)) == 0 and r.intact
+            assert dst_off.tolist() == want_off.tolist() and dst_off[n + 1] == FILL
+            same(buf, want[0], f"host streams encode {B} {hc}")
+            assert counts(r) == dict(passes=0, reserves=1, moves=1, uploads=2, downloads=2, syncs=2)
+            assert r.image_bytes == a256(src_len) + 2 * a256(8 * (n + 1)) + a256(bound) + sbytes
+
+
+# -- the decoders: every way the index settles.  A chunk or message (compressed, original size, payload bytes) decodes to `original`
+# bytes whatever its payload, the codec being the test's: any ratio, and any number of chunks per source byte.
+def decoder_chunks(kind):
+    """-> the chunks of one stream: few and modest / more than the table guess holds / larger than the output guess / both"""
+    if kind == "at once":
+        return [(1, 300, noise(100, 1)), (0, 90, noise(90, 2)), (1, 260, noise(70, 3)), (0, 1, noise(1, 4)), (1, 200, noise(199, 5))]
+    if kind == "table":
+        return [(k % 2, 4 if k % 2 else 3, noise(3, k)) for k in range(45)]
+    if kind == "output":
+        return [(1, 5000, noise(100, 6)), (0, 50, noise(50, 7)), (1, 9000, noise(20, 8))]
+    if kind == "both":
+        return [(1, 500 + k, noise(3, k)) for k in range(45)]
+    raise ValueError(kind)
+
+
+SETTLE = {"at once": 1, "table": 2, "output": 2, "both": 3}
+
+
+def stream_of(chunks):
+    return frame([(c, original, payload.tobytes()) for c, original, payload in chunks])
+
+
+def stream_image_bytes(src_len, out_bytes, max_chunks):
+    return a256(src_len) + 256 + a256(out_bytes) + emu.framing().emu_scratch_bytes(1, max_chunks, 0, 0)
+
+
+@pytest.mark.parametrize("kind", list(SETTLE))
+@pytest.mark.parametrize("outcome", ["good", "corrupt block", "bad header", "size query"])
+def test_host_stream_decode(kind, outcome):
+    L = emu.framing()
+    chunks = decoder_chunks(kind)
+    stream = stream_of(chunks) + (b"\x81" if outcome == "bad header" else b"")
+    w = ref_walk(stream)
+    assert w["chunks"] == len(chunks) and w["status"] == (EOS if outcome == "bad header" else OK)
+    src_len, total, passes = len(stream), w["decoded_bytes"], SETTLE[kind]
+    assert (w["chunks"] > (src_len + 4095) // 4096 + 16) == (kind in ("table", "both")) and (total > 4 * src_len) == (kind in ("output", "both"))
+    comp_rows = [r for r in w["rows"] if r[0]]
+    results = [r[3] - (1 if outcome == "corrupt block" and j in (1, 2) else 0) for j, r in enumerate(comp_rows)]
+    decoded = pattern(total + 8) ^ 0xFF
+    src = np.frombuffer(stream + TAIL, np.uint8).copy()
+    for gi, gc in HOST_GRIDS:
+        _, want_info, want, cap = lib_stream_decode(stream, results, decoded, gi, gc)
+        dec = np.ascontiguousarray(np.concatenate([decoded, np.zeros(8, np.uint8)]))
+        info, r = poisoned(emu.StreamInfo), host_run(results, dec, gi, gc)
+        what = f"host stream decode, {kind}, {outcome}: grids {gi}, {gc}"
+        if outcome == "size query":
+            # only *info is filled: the index's, with the size to bring.  A size above dst_cap ends the loop: no pass for the output.
+            passes = 2 if kind in ("table", "both") else 1
+            assert L.emu_host_stream_decode(addr(src), src_len, None, 0, ref(info), ref(r)) == E_ARGUMENT and r.intact, what
+            assert r.error == b"stream decode: dst_cap < decoded_bytes (reported in info->decoded_bytes)"
+            assert info_tuple(info) == (w["chunks"], len(comp_rows), total, -1, OK, 0), what
+            assert counts(r) == dict(passes=passes, reserves=passes, moves=passes, uploads=passes, downloads=passes, syncs=passes), (what, counts(r))
+            assert r.image_bytes == stream_image_bytes(src_len, 0, w["chunks"] if passes == 2 else (src_len + 4095) // 4096 + 16), what
+            continue
+        buf, ptr = guarded(cap)
+        rc = L.emu_host_stream_decode(addr(src), src_len, ptr, cap, ref(info), ref(r))
+        assert r.intact and info_tuple(info) == info_tuple(want_info) and rc == info.error, (what, rc, info_tuple(info))
+        assert info.error == {"good": OK, "corrupt block": CORRUPT_BLOCK, "bad header": EOS}[outcome], what
+        same(buf, want, what)
+        assert counts(r) == dict(passes=passes, reserves=passes, moves=passes, uploads=passes, downloads=passes + 2, syncs=passes + 1), (what, counts(r))
+        # the last pass: a table of exactly the reported count (or still the guess), an output of exactly the reported size (or the guess)
+        max_chunks = w["chunks"] if kind in ("table", "both") else (src_len + 4095) // 4096 + 16
+        assert r.image_bytes == stream_image_bytes(src_len, total if kind in ("output", "both") else min(cap, 4 * src_len), max_chunks), what
+
+
+def test_host_stream_decode_of_nothing():
+    """src_len == 0 is no short cut here: one index pass over no bytes, nothing uploaded, an info of zeros"""
+    L = emu.framing()
+    info, r, (buf, ptr) = poisoned(emu.StreamInfo), host_run([], np.zeros(8, np.uint8)), guarded(64)
+    assert L.emu_host_stream_decode(None, 0, ptr, 64, ref(info), ref(r)) == 0 and r.intact and untouched(buf)
+    assert info_tuple(info) == (0, 0, 0, -1, OK, 0)
+    assert counts(r) == dict(passes=1, reserves=1, moves=1, uploads=0, downloads=2, syncs=2)
+
+
+def unwrap_input(kind, outcome):
+    """-> (src, off, n, src_len, refs, results, total)"""
+    msgs = {"at once": [(300, 100), (90, 90), (0, 0), (260, 70), (1, 1), (200, 199)],
+            "output": [(5000, 100), (50, 50), (9000, 20), (0, 0)]}[kind]
+    wrapped = [header_wrap(original, payload) + noise(payload, k).tobytes() for k, (original, payload) in enumerate(msgs)]
+    if outcome == "bad header":
+        wrapped.insert(2, header_wrap(50, 60) + bytes(20))                  # a payload longer than the message
+        wrapped.insert(4, b"\x01\x02\x03")                                  # shorter than a header
+    n = len(wrapped)
+    off = np.zeros(n + 1, np.int64)
+    off[1:] = np.cumsum([len(m) for m in wrapped])
+    src = np.frombuffer(b"".join(wrapped) + bytes(16), np.uint8).copy()
+    refs = [ref_unwrap(np.frombuffer(m, np.uint8)) for m in wrapped]
+    comp = [k for k in range(n) if refs[k][1] == "comp"]
+    results = [refs[k][3] - (1 if outcome == "corrupt block" and j in (0, 2) else 0) for j, k in enumerate(comp)]
+    return src, off, n, int(off[n]), refs, results, sum(r[2] for r in refs)
+
+
+def unwrap_image_bytes(src_len, n, out_bytes):
+    return a256(src_len) + 2 * a256(8 * (n + 1)) + a256(4 * n) + 256 + emu.framing().emu_scratch_bytes(3, n, 0, 0) + out_bytes
+
+
+@pytest.mark.parametrize("kind", ["at once", "output"])
+@pytest.mark.parametrize("outcome", ["good", "corrupt block", "bad header", "size query"])
+def test_host_unwrap(kind, outcome):
+    L = emu.framing()
+    src, off, n, src_len, refs, results, total = unwrap_input(kind, outcome)
+    assert (total > 4 * src_len) == (kind == "output")
+    passes = 2 if kind == "output" else 1
+    decoded = pattern(total + 8) ^ 0xFF
+    for gi, gc in HOST_GRIDS:
+        want_index, want_info, want_off, index_status, want_status, want = lib_unwrap(src, off, src_len, n, results, decoded, total, gi, gc)
+        info, dst_off, status, r = poisoned(emu.UnwrapInfo), filled(n + 2), filled(n + 1, np.int32), host_run(results, decoded, gi, gc)
+        what = f"host unwrap, {kind}, {outcome}: grids {gi}, {gc}"
+        if outcome == "size query":
+            # the info, the offsets and the statuses of the index are the caller's; one pass, the size being above dst_cap
+            assert L.emu_host_unwrap(addr(src), src_len, addr(off), n, None, 0, addr(dst_off), addr(status), ref(info), ref(r)) == E_ARGUMENT and r.intact, what
+            assert r.error == b"unwrap: dst_cap < decoded_bytes (reported in info->decoded_bytes)"
+            assert info_tuple(info) == info_tuple(want_index) and info.decoded_bytes == total, what
+            assert dst_off.tolist() == want_off.tolist() and status.tolist() == index_status.tolist(), what
+            assert counts(r) == dict(passes=1, reserves=1, moves=1, uploads=2, downloads=3, syncs=2), (what, counts(r))
+            assert r.image_bytes == unwrap_image_bytes(src_len, n, 0), what
+            continue
+        buf, ptr = guarded(total + 24)
+        rc = L.emu_host_unwrap(addr(src), src_len, addr(off), n, ptr, total + 24, addr(dst_off), addr(status), ref(info), ref(r))
+        assert r.intact and info_tuple(info) == info_tuple(want_info) and rc == info.error, (what, rc, info_tuple(info))
+        assert info.error == {"good": WRAP_OK, "corrupt block": WRAP_CORRUPT_BLOCK, "bad header": WRAP_CORRUPT_HEADER}[outcome], what
+        assert dst_off.tolist() == want_off.tolist() and status.tolist() == want_status.tolist() and dst_off[n + 1] == FILL and status[n] == FILL, what
+        same(buf, want, what)
+        assert counts(r) == dict(passes=passes, reserves=passes, moves=passes, uploads=2 * passes, downloads=passes + 4, syncs=passes + 1), (what, counts(r))
+        assert r.image_bytes == unwrap_image_bytes(src_len, n, total if kind == "output" else min(total + 24, 4 * src_len)), what
+
+
+def test_host_unwrap_of_nothing():
+    """n == 0 is no short cut here: the one offset is staged, the index runs, dst_off[0] = 0 and the info of no messages come back"""
+    L = emu.framing()
+    info, dst_off, status, r, (buf, ptr) = poisoned(emu.UnwrapInfo), filled(3), filled(2, np.int32), host_run([], np.zeros(8, np.uint8)), guarded(64)
+    off = np.zeros(1, np.int64)
+    assert L.emu_host_unwrap(None, 0, addr(off), 0, ptr, 64, addr(dst_off, 1), addr(status), ref(info), ref(r)) == 0 and r.intact and untouched(buf)
+    assert info_tuple(info) == (0, 0, 0, -1, WRAP_OK, 0) and dst_off.tolist() == [FILL, 0, FILL] and (status == FILL).all()
+    assert counts(r) == dict(passes=0, reserves=1, moves=1, uploads=1, downloads=3, syncs=2)
+
+
+def streams_input(kind, outcome):
+    """-> (src with TAIL, off, n, walks): the chunks of decoder_chunks(kind) dealt to four items, an empty one between them"""
+    chunks = decoder_chunks(kind)
+    k = -(-len(chunks) // 4)
+    items = [stream_of(chunks[0:k]), b"", stream_of(chunks[k:2 * k]), stream_of(chunks[2 * k:3 * k]), stream_of(chunks[3 * k:])]
+    if outcome == "bad header":
+        items[2] += b"\x81"
+    n = len(items)
+    off = np.zeros(n + 1, np.int64)
+    off[1:] = np.cumsum([len(s) for s in items])
+    return np.frombuffer(b"".join(items) + TAIL, np.uint8).copy(), off, n, [ref_walk(s) for s in items]
+
+
+def streams_image_bytes(src_len, n, out_bytes, max_chunks):
+    return a256(src_len) + 2 * a256(8 * (n + 1)) + a256(4 * n) + a256(8 * n) + 256 + a256(out_bytes) + emu.framing().emu_scratch_bytes(5, n, max_chunks, 0)
+
+
+@pytest.mark.parametrize("kind", list(SETTLE))
+@pytest.mark.parametrize("outcome", ["good", "corrupt block", "bad header", "size query"])
+def test_host_streams_decode(kind, outcome):
+    L = emu.framing()
+    src, off, n, walks = streams_input(kind, outcome)
+    src_len, chunks, total, passes = int(off[n]), sum(w["chunks"] for w in walks), sum(w["decoded_bytes"] for w in walks), SETTLE[kind]
+    guess = src_len // 4096 + n + 16
+    assert (chunks > guess) == (kind in ("table", "both")) and (total > 4 * src_len) == (kind in ("output", "both"))
+    comp_rows = [r for w in walks for r in w["rows"] if r[0]]
+    results = [r[3] - (1 if outcome == "corrupt block" and j in (1, len(comp_rows) - 1) else 0) for j, r in enumerate(comp_rows)]
+    decoded = pattern(total + 8) ^ 0xFF
+    for gw, gi, gc in ((0, 0, 0), (1, 1, 1), (3, 3, 3)):
+        want = lib_streams_decode(src, off, n, chunks + 2, results, decoded, total, gw, gi, gc)
+        info, dst_off, status, error_offset = poisoned(emu.StreamsInfo), filled(n + 2), filled(n + 1, np.int32), filled(n + 1)
+        r = host_run(results, decoded, gi, gc, gw)
+        what = f"host streams decode, {kind}, {outcome}: grids {gw}, {gi}, {gc}"
+        if outcome == "size query":
+            # the info, the offsets, the statuses and the error offsets of the index are the caller's
+            passes = 2 if kind in ("table", "both") else 1
+            assert L.emu_host_streams_decode(addr(src), src_len, addr(off), n, None, 0, addr(dst_off), addr(status), addr(error_offset), ref(info),
+                                             ref(r)) == E_ARGUMENT and r.intact, what
+            assert r.error == b"streams decode: dst_cap < decoded_bytes (reported in info->decoded_bytes)"
+            assert info_tuple(info) == info_tuple(want["index_info"]) and info.decoded_bytes == total, what
+            assert dst_off.tolist() == want["dst_off"].tolist() and status.tolist() == want["status"].tolist(), what
+            assert error_offset.tolist() == want["error_offset"].tolist(), what
+            assert counts(r) == dict(passes=passes, reserves=passes, moves=passes, uploads=2 * passes, downloads=passes + 3, syncs=passes + 1), (what, counts(r))
+            assert r.image_bytes == streams_image_bytes(src_len, n, 0, chunks if passes == 2 else guess), what
+            continue
+        buf, ptr = guarded(total + 24)
+        rc = L.emu_host_streams_decode(addr(src), src_len, addr(off), n, ptr, total + 24, addr(dst_off), addr(status), addr(error_offset), ref(info), ref(r))
+        assert r.intact and info_tuple(info) == info_tuple(want["info"]) and rc == info.error, (what, rc, info_tuple(info))
+        assert info.error == {"good": OK, "corrupt block": CORRUPT_BLOCK, "bad header": EOS}[outcome], what
+        assert dst_off.tolist() == want["dst_off"].tolist() and status.tolist() == want["status"].tolist(), what
+        assert error_offset.tolist() == want["error_offset"].tolist() and dst_off[n + 1] == FILL and status[n] == FILL and error_offset[n] == FILL, what
+        same(buf, want["buf"], what)
+        assert counts(r) == dict(passes=passes, reserves=passes, moves=passes, uploads=2 * passes, downloads=passes + 5, syncs=passes + 1), (what, counts(r))
+        assert r.image_bytes == streams_image_bytes(src_len, n, total if kind in ("output", "both") else min(total + 24, 4 * src_len),
+                                                    chunks if kind in ("table", "both") else guess), what
+
+
+def test_host_argument_checks_and_short_cuts():
+    """every argument check of the six, by its message, with no device touched and nothing written (the mode is the device path's to
+    check: the source is staged by then, and still nothing is written); then the short cuts, which write the one thing they document
+    and nothing else"""
+    L = emu.framing()
+    src, off3 = np.zeros(64, np.uint8), np.array([0, 10, 20, 30], np.int64)
+    none = dict(passes=0, reserves=0, moves=0, uploads=0, downloads=0, syncs=0)
+    S, O = addr(src), addr(off3)
+
+    def fresh():
+        return guarded(4096) + (filled(6), filled(5, np.int32), filled(5), filled(3))
+
+    def refused(name, message, *args, uploads=0):
+        buf, ptr, dst_off, status, error_offset, dst_len = fresh()
+        info = {"emu_host_stream_decode": emu.StreamInfo, "emu_host_unwrap": emu.UnwrapInfo, "emu_host_streams_decode": emu.StreamsInfo}.get(name)
+        info = poisoned(info) if info else None
+        named = dict(dst=ptr, dst_off=addr(dst_off, 1), status=addr(status), error_offset=addr(error_offset), dst_len=addr(dst_len, 1),
+                     info=ref(info) if info else None)
+        r = host_run([], src)
+        rc = getattr(L, name)(*[named[a] if isinstance(a, str) else a for a in args], ref(r))
+        staged = dict(none, reserves=1, moves=1, uploads=uploads) if uploads else none
+        assert rc == E_ARGUMENT and r.error == message.encode() and counts(r) == staged and r.intact, (name, args, rc, r.error, counts(r))
+        assert untouched(buf) and all((a == FILL).all() for a in (dst_off, status, error_offset, dst_len)), (name, args)
+        assert info is None or all(v == FILL for v in info_tuple(info)), (name, args)
+
+    m = "stream encode: negative size or NULL pointer"
+    refused("emu_host_stream_encode", m, S, -1, 16, MODE_FAST, "dst", 4096, "dst_len")
+    refused("emu_host_stream_encode", m, S, 30, 16, MODE_FAST, "dst", 4096, None)
+    refused("emu_host_stream_encode", m, None, 30, 16, MODE_FAST, "dst", 4096, "dst_len")
+    refused("emu_host_stream_encode", m, S, 30, 16, MODE_FAST, None, 4096, "dst_len")
+    refused("emu_host_stream_encode", "stream encode: dst_cap < lz4hip_stream_bound", S, 30, 16, MODE_FAST, "dst", 30 + 2 * 3 - 1, "dst_len")
+    refused("emu_host_stream_encode", "mode must be LZ4HIP_MODE_FAST or LZ4HIP_MODE_HC", S, 30, 16, 7, "dst", 4096, "dst_len", uploads=1)
+    m = "stream decode: negative size or NULL pointer"
+    refused("emu_host_stream_decode", m, S, -1, "dst", 4096, "info")
+    refused("emu_host_stream_decode", m, S, 30, "dst", -1, "info")
+    refused("emu_host_stream_decode", m, S, 30, "dst", 4096, None)
+    refused("emu_host_stream_decode", m, None, 30, "dst", 4096, "info")
+    m = "wrap: negative size or NULL pointer"
+    refused("emu_host_wrap", m, S, -1, O, 3, MODE_FAST, "dst", 4096, "dst_off", "status")
+    refused("emu_host_wrap", m, S, 30, O, -1, MODE_FAST, "dst", 4096, "dst_off", "status")
+    refused("emu_host_wrap", m, S, 30, O, 3, MODE_FAST, "dst", 4096, None, "status")
+    refused("emu_host_wrap", m, S, 30, None, 3, MODE_FAST, "dst", 4096, "dst_off", "status")
+    refused("emu_host_wrap", m, S, 30, O, 3, MODE_FAST, None, 4096, "dst_off", "status")
+    refused("emu_host_wrap", m, None, 30, O, 3, MODE_FAST, "dst", 4096, "dst_off", "status")
+    refused("emu_host_wrap", "wrap: dst_cap < lz4hip_wrap_bound", S, 30, O, 3, MODE_FAST, "dst", 30 + 24 - 1, "dst_off", "status")
+    refused("emu_host_wrap", "mode must be LZ4HIP_MODE_FAST or LZ4HIP_MODE_HC", S, 30, O, 3, 7, "dst", 4096, "dst_off", "status", uploads=2)
+    m = "unwrap: negative size or NULL pointer"
+    refused("emu_host_unwrap", m, S, -1, O, 3, "dst", 4096, "dst_off", "status", "info")
+    refused("emu_host_unwrap", m, S, 30, O, -1, "dst", 4096, "dst_off", "status", "info")
+    refused("emu_host_unwrap", m, S, 30, O, 3, "dst", -1, "dst_off", "status", "info")
+    refused("emu_host_unwrap", m, S, 30, O, 3, "dst", 4096, None, "status", "info")
+    refused("emu_host_unwrap", m, S, 30, O, 3, "dst", 4096, "dst_off", "status", None)
+    refused("emu_host_unwrap", m, S, 30, None, 3, "dst", 4096, "dst_off", "status", "info")
+    refused("emu_host_unwrap", m, S, 30, O, 3, "dst", 4096, "dst_off", None, "info")
+    refused("emu_host_unwrap", m, None, 30, O, 3, "dst", 4096, "dst_off", "status", "info")
+    m = "streams encode: negative size or NULL pointer"
+    refused("emu_host_streams_encode", m, S, -1, O, 3, 16, MODE_FAST, "dst", 4096, "dst_off")
+    refused("emu_host_streams_encode", m, S, 30, O, -1, 16, MODE_FAST, "dst", 4096, "dst_off")
+    refused("emu_host_streams_encode", m, S, 30, O, 3, 16, MODE_FAST, "dst", 4096, None)
+    refused("emu_host_streams_encode", m, S, 30, None, 3, 16, MODE_FAST, "dst", 4096, "dst_off")
+    refused("emu_host_streams_encode", m, None, 30, O, 3, 16, MODE_FAST, "dst", 4096, "dst_off")
+    refused("emu_host_streams_encode", m, S, 30, O, 3, 16, MODE_FAST, None, 4096, "dst_off")
+    m = "streams encode: offsets decrease or fall outside [0, src_len]"
+    for bad in ([-1, 10, 20, 30], [0, 10, 9, 30], [0, 10, 20, 31]):
+        refused("emu_host_streams_encode", m, S, 30, addr(np.array(bad, np.int64)), 3, 16, MODE_FAST, "dst", 4096, "dst_off")
+    refused("emu_host_streams_encode", "streams encode: dst_cap < lz4hip_streams_bound", S, 30, O, 3, 16, MODE_FAST, "dst", 30 + 4 * 3 - 1, "dst_off")
+    refused("emu_host_streams_encode", "mode must be LZ4HIP_MODE_FAST or LZ4HIP_MODE_HC", S, 30, O, 3, 16, 7, "dst", 4096, "dst_off", uploads=2)
+    m = "streams decode: negative size or NULL pointer"
+    refused("emu_host_streams_decode", m, S, -1, O, 3, "dst", 4096, "dst_off", "status", "error_offset", "info")
+    refused("emu_host_streams_decode", m, S, 30, O, -1, "dst", 4096, "dst_off", "status", "error_offset", "info")
+    refused("emu_host_streams_decode", m, S, 30, O, 3, "dst", -1, "dst_off", "status", "error_offset", "info")
+    refused("emu_host_streams_decode", m, S, 30, O, 3, "dst", 4096, None, "status", "error_offset", "info")
+    refused("emu_host_streams_decode", m, S, 30, O, 3, "dst", 4096, "dst_off", "status", "error_offset", None)
+    refused("emu_host_streams_decode", m, S, 30, None, 3, "dst", 4096, "dst_off", "status", "error_offset", "info")
+    refused("emu_host_streams_decode", m, S, 30, O, 3, "dst", 4096, "dst_off", None, "error_offset", "info")
+    refused("emu_host_streams_decode", m, S, 30, O, 3, "dst", 4096, "dst_off", "status", None, "info")
+    refused("emu_host_streams_decode", m, None, 30, O, 3, "dst", 4096, "dst_off", "status", "error_offset", "info")
+
+    # the short cuts: no device, NULL buffers welcome
+    buf, ptr, dst_off, status, error_offset, dst_len = fresh()
+    r = host_run([], src)
+    assert L.emu_host_stream_encode(None, 0, 16, MODE_FAST, None, 0, addr(dst_len, 1), ref(r)) == 0 and dst_len.tolist() == [FILL, 0, FILL] and counts(r) == none
+    assert L.emu_host_wrap(None, 0, None, 0, MODE_FAST, None, 0, addr(dst_off, 1), None, ref(r)) == 0 and counts(r) == none
+    assert dst_off.tolist() == [FILL, 0] + [FILL] * 4
+    for n, src_len in ((0, 0), (0, 30), (3, 0)):
+        dst_off[:] = FILL
+        zeros = np.zeros(4, np.int64)
+        assert L.emu_host_streams_encode(None if src_len == 0 else S, src_len, addr(zeros) if n else None, n, 16, MODE_FAST, None, 4096, addr(dst_off, 1), ref(r)) == 0
+        assert dst_off.tolist() == [FILL] + [0] * (n + 1) + [FILL] * (4 - n) and counts(r) == none, (n, src_len)
+    dst_off[:] = FILL
+    info = poisoned(emu.StreamsInfo)
+    assert L.emu_host_streams_decode(S, 30, None, 0, None, 0, addr(dst_off, 1), None, None, ref(info), ref(r)) == 0 and counts(r) == none
+    assert info_tuple(info) == (0, 0, 0, 0, -1, -1, OK, 0) and dst_off.tolist() == [FILL, 0] + [FILL] * 4
+    assert untouched(buf) and (status == FILL).all() and (error_offset == FILL).all()
