@@ -24,6 +24,7 @@
 #include "lz4hip_wrap.hpp"
 #include "lz4hip_streams.hpp"
 #include "lz4hip_framing.hpp"
+#include "lz4hip_hostbatch.hpp"
 
 #include "../../include/lz4hip.h"
 
@@ -42,6 +43,8 @@
 
 using namespace lz4hip;
 using namespace lz4hip::framing;
+using lz4hip::hostbatch::kHostSlots;
+using lz4hip::hostbatch::kHcHostSliceBlocks;
 
 namespace {
 
@@ -102,7 +105,6 @@ constexpr int64_t kLaneEncodeMinBlocks = 49152;  // a lane needs 60 - 110 ms for
 constexpr int kLaneDecodeGeneration = 4;
 constexpr int kLane4Config = 59192;          // lane decoder: 192-byte ring, 32-byte input pieces out of whole 64-byte sectors, 128-byte flush units; iterations
                                               // alternate between flushing (two store instructions) and requesting input (four load instructions, one sector)
-constexpr int64_t kHcHostSliceBlocks = 16384;  // host-pointer LZ4HC batches: blocks per slice
 constexpr int kHcLaneGeneration = 4;           // blocks <= 64 KiB; larger ones: 2
 
 int fail(int code, const std::string& what)
@@ -456,6 +458,7 @@ hipError_t allow_dynamic_lds(std::atomic<int>& state, const void* kernel, int by
 // per CU up.  With the same number of rounds one block per workgroup is the better form (finer placement, nine wavefronts per CU disturb one another
 // less than ten): profiles/r06/wave_encoder_round_steps.txt.
 constexpr int kEncodeBlocksPerGroup = 5;
+static_assert(hostbatch::kHostEncodeBlocksPerCu == 2 * kEncodeBlocksPerGroup, "encode_host_slice_blocks: two workgroups per CU");
 bool encoder_five_blocks_per_workgroup(int64_t n_blocks)
 {
     const int k = knob(kKnobEncoderWg5);
@@ -916,8 +919,6 @@ int launch_decode(const lz4hip_batch_t* b, int known, hipStream_t stream)
     return 0;
 }
 
-size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
 // Pinned (page-locked) host staging, grow-only, per calling thread: two slots so that the host can fill / drain
 // one slice while the device works on the other.
 struct Pinned {
@@ -940,7 +941,6 @@ struct Pinned {
 // on DIFFERENT streams, so that a slice's kernels start as soon as its input has landed, next to those of the slices
 // before it -- a launch over a thousand blocks cannot fill the device and takes the same few milliseconds as one over
 // four thousand.
-constexpr int kHostSlots = 4;
 struct HostPipe {
     bool ready = false;
     int dev = -1;                // streams and events belong to a device: one set per (thread, device)
@@ -966,10 +966,74 @@ struct HostPipe {
 // Everything a calling thread needs to stage host batches through ONE device: scratch, pinned slots, pipeline.
 // Indexed by the device that is current when the call is made, so a thread may hipSetDevice() between calls
 // (and the multi-device entry points run one worker thread per device).
+// It is the stage of hostbatch::run_host_batch (lz4hip_hostbatch.hpp): copies in on one stream, copies out on another, the
+// kernels of a slot on the slot's own stream, events between them.
 struct HostContext {
     Scratch scratch;
-    Pinned pin_in[kHostSlots], pin_out[kHostSlots];
+    Pinned pinned_in[kHostSlots], pinned_out[kHostSlots];
     HostPipe pipe;
+    uint8_t* d_in[kHostSlots] = {};
+    uint8_t* d_out[kHostSlots] = {};
+
+    int fail(int code, const std::string& what) { return ::fail(code, what); }
+    int reserve(int slots, int64_t in_bytes, int64_t out_bytes)
+    {
+        int rc = scratch.reserve((size_t)slots * (size_t)(in_bytes + out_bytes));
+        if (rc) return rc;
+        for (int k = 0; k < slots; k++) {
+            if ((rc = pinned_in[k].reserve((size_t)in_bytes))) return rc;
+            if ((rc = pinned_out[k].reserve((size_t)out_bytes))) return rc;
+        }
+        if ((rc = pipe.init())) return rc;
+        for (int k = 0; k < slots; k++) {
+            d_in[k] = (uint8_t*)scratch.p + (size_t)k * (size_t)(in_bytes + out_bytes);
+            d_out[k] = d_in[k] + in_bytes;
+        }
+        return 0;
+    }
+    uint8_t* pin_in(int slot) { return (uint8_t*)pinned_in[slot].p; }
+    uint8_t* pin_out(int slot) { return (uint8_t*)pinned_out[slot].p; }
+    uint8_t* dev_in(int slot) { return d_in[slot]; }
+    uint8_t* dev_out(int slot) { return d_out[slot]; }
+    // whatever the caller queued on its stream before this call comes first
+    int begin()
+    {
+        HIP_TRY(hipEventRecord(pipe.e_start, hipStreamPerThread));
+        HIP_TRY(hipStreamWaitEvent(pipe.s_in, pipe.e_start, 0));
+        return 0;
+    }
+    // (the slot's previous kernels have finished: their slice has been drained)
+    int copy_in(int slot, int64_t offset, int64_t bytes)
+    {
+        HIP_TRY(hipMemcpyAsync(d_in[slot] + offset, pin_in(slot) + offset, (size_t)bytes, hipMemcpyHostToDevice, pipe.s_in));
+        return 0;
+    }
+    // on the slot's own stream, after its input has landed; the copies out wait for them
+    template <class Run>
+    int kernels(int slot, Run& run, const lz4hip_batch_t& db)
+    {
+        hipStream_t ks = pipe.s_k[slot];
+        HIP_TRY(hipEventRecord(pipe.e_in[slot], pipe.s_in));
+        HIP_TRY(hipStreamWaitEvent(ks, pipe.e_in[slot], 0));
+        if (int rc = run(&db, ks)) return rc;
+        HIP_TRY(hipEventRecord(pipe.e_k[slot], ks));
+        HIP_TRY(hipStreamWaitEvent(pipe.s_out, pipe.e_k[slot], 0));
+        return 0;
+    }
+    // (the slot's event is recorded behind each copy: it stands for the last one)
+    int copy_out(int slot, int64_t offset, int64_t bytes)
+    {
+        HIP_TRY(hipMemcpyAsync(pin_out(slot) + offset, d_out[slot] + offset, (size_t)bytes, hipMemcpyDeviceToHost, pipe.s_out));
+        HIP_TRY(hipEventRecord(pipe.e_out[slot], pipe.s_out));
+        return 0;
+    }
+    bool out_done(int slot) { return hipEventQuery(pipe.e_out[slot]) == hipSuccess; }
+    int wait_out(int slot) { HIP_TRY(hipEventSynchronize(pipe.e_out[slot])); return 0; }
+    void quiesce()
+    {
+        (void)hipStreamSynchronize(pipe.s_in); (void)hipStreamSynchronize(pipe.s_out);
+        for (int k = 0; k < kHostSlots; k++) (void)hipStreamSynchronize(pipe.s_k[k]);
+    }
 };
 // One per (thread, device), created on first use and kept for the life of the thread.  The threads that call this are
 // the callers' own (single-device entry points) and the library's PERSISTENT device workers (multi-device entry points,
@@ -985,7 +1049,7 @@ void release_host_context(int dev)
 {
     if (HostContext* hc = host_context(dev, false)) {
         hc->scratch.release();
-        for (int k = 0; k < kHostSlots; k++) { hc->pin_in[k].release(); hc->pin_out[k].release(); }
+        for (int k = 0; k < kHostSlots; k++) { hc->pinned_in[k].release(); hc->pinned_out[k].release(); }
     }
 }
 
@@ -1046,275 +1110,20 @@ DeviceWorker* device_worker(int logical)
     return g_worker[logical];
 }
 
-// ---- the row pool: gathers and scatters between caller memory and the pinned staging ------------------------------------
-// Plain memcpy of rows, ~10 GB/s per core -- and with six slices per batch the calling thread used to spend more time in them
-// than PCIe needs for the payload (round 3: 16 threads, started and joined per call: 24 GB/s for a 16 384-block decode).  Now
-// ONE persistent pool per process, started on first use: min(hardware threads / 4, 64) threads (knob host_threads), shared by
-// every caller -- the device workers of a multi-device call included: each of their jobs is cut into chunks that any pool
-// thread (and the submitting thread) may take, so eight devices share the pool instead of getting two threads each.
-struct RowJob {
-    std::function<void(int64_t)> f;
-    int64_t n = 0, chunk = 1;
-    std::atomic<int64_t> next{ 0 }, remaining{ 0 };
-    std::mutex m;
-    std::condition_variable done_cv;
-    bool exhausted() const { return next.load(std::memory_order_relaxed) >= n; }
-    // runs one chunk; false when none was left
-    bool work_one()
-    {
-        const int64_t lo = next.fetch_add(chunk, std::memory_order_relaxed);
-        if (lo >= n) return false;
-        const int64_t hi = lo + chunk < n ? lo + chunk : n;
-        for (int64_t i = lo; i < hi; i++) f(i);
-        if (remaining.fetch_sub(hi - lo, std::memory_order_acq_rel) == hi - lo) {
-            std::lock_guard<std::mutex> lk(m);
-            done_cv.notify_all();
-        }
-        return true;
-    }
-};
-struct RowPool {
-    std::mutex mu;
-    std::condition_variable cv;
-    std::deque<std::shared_ptr<RowJob>> q;                            // in priority order: gathers (they feed the pipeline) before scatters
-    unsigned started = 0;
-    void loop()
-    {
-        for (;;) {
-            std::shared_ptr<RowJob> j;
-            {
-                std::unique_lock<std::mutex> lk(mu);
-                for (;;) {
-                    while (!q.empty() && q.front()->exhausted()) q.pop_front();
-                    for (auto& c : q) if (!c->exhausted()) { j = c; break; }
-                    if (j) break;
-                    cv.wait(lk);
-                }
-            }
-            j->work_one();                                            // one chunk, then look again: a more urgent job may have arrived
-        }
-    }
-    unsigned want_threads()
-    {
-        if (knob(kKnobHostThreads) > 0) return (unsigned)knob(kKnobHostThreads);
-        // a quarter of the hardware threads, at least 8 where the host has them, at most 64 -- and never more than the host has
-        const unsigned hc = std::thread::hardware_concurrency() ? std::thread::hardware_concurrency() : 1u;
-        unsigned t = hc / 4;
-        t = t < 8 ? 8 : (t > 64 ? 64 : t);
-        return t > hc ? hc : t;
-    }
-    // queues the job and returns at once; wait() (which also works on it) before anything it touches is reused
-    std::shared_ptr<RowJob> submit(int64_t n, std::function<void(int64_t)> f, bool urgent)
-    {
-        const unsigned want = want_threads();
-        auto j = std::make_shared<RowJob>();
-        j->f = std::move(f); j->n = n;
-        j->chunk = n / ((int64_t)want * 4) > 0 ? n / ((int64_t)want * 4) : 1;
-        j->remaining.store(n);
-        {
-            std::lock_guard<std::mutex> lk(mu);
-            while (started + 1 < want) {                              // (the submitting thread works too)
-                try { std::thread(&RowPool::loop, this).detach(); }
-                catch (const std::system_error&) { break; }           // no more threads to be had: fewer helpers, same result
-                started++;
-            }
-            if (urgent) q.push_front(j); else q.push_back(j);
-        }
-        cv.notify_all();
-        return j;
-    }
-    void wait(const std::shared_ptr<RowJob>& j)
-    {
-        while (j->work_one()) {}
-        std::unique_lock<std::mutex> lk(j->m);
-        j->done_cv.wait(lk, [&] { return j->remaining.load(std::memory_order_acquire) == 0; });
-    }
-    void run(int64_t n, std::function<void(int64_t)> f) { wait(submit(n, std::move(f), true)); }
-};
-RowPool* row_pool()
-{
-    static RowPool* p = new RowPool();                               // never destroyed: its threads outlive main()
-    return p;
-}
-
-// f(i) for i in [0, n): on the calling thread for small jobs, on the row pool for large ones.
-template <class F>
-void for_rows(int64_t n, size_t bytes, F f)
-{
-    if (bytes < (4u << 20) || n < 2) { for (int64_t i = 0; i < n; i++) f(i); return; }
-    try { row_pool()->run(n, std::function<void(int64_t)>(f)); }
-    catch (const std::bad_alloc&) { for (int64_t i = 0; i < n; i++) f(i); }   // (idempotent copies: doing them again is harmless)
-}
-
-// Stage a host batch through device memory, run `run` on it, copy results (and dst payloads) back.
-// The batch is cut into slices; per slice: rows are gathered into pinned memory (host threads), ONE host-to-device copy,
-// the kernels, ONE device-to-host copy into pinned memory, rows scattered to the caller.  Copies in, kernels and copies
-// out run on their own streams over kHostSlots sets of buffers: slice k+1 travels in and slice k-1 out while slice k is
-// being processed (PCIe is full duplex), kernels of neighbouring slices overlap, and the host gathers / scatters next to
-// all that.
+// Stage a host batch through device memory, run `run` on it, copy results (and dst payloads) back: hostbatch::run_host_batch
+// (lz4hip_hostbatch.hpp: slices, images, gather and scatter, the order of it all) over the calling thread's context for the current device.
+// slice_hint > 0: blocks per slice wanted by the caller.
 template <class Run>
-// slice_hint > 0: blocks per slice wanted by the caller (LZ4HC: its lane kernels need ~0.35 s however few blocks a launch has, so
-// a batch goes in slices of up to 16384 blocks instead of ~2048).
 int run_host_batch(const lz4hip_batch_t* hb, bool dst_len_is_result, Run run, int64_t slice_hint = 0)
 {
     int rc = check_batch(hb);
     if (rc) return rc;
     if ((rc = ensure_device())) return rc;
-    const int64_t n = hb->n_blocks;
-    if (n == 0) return 0;
-
-    // tight device layout: per-block slots of the maximum length, 16-byte aligned
-    int64_t max_src = 0, max_dst = 0;
-    for (int64_t i = 0; i < n; i++) {
-        const int32_t sl = hb->src_len ? hb->src_len[i] : hb->src_len_all;
-        const int32_t dc = hb->dst_cap ? hb->dst_cap[i] : hb->dst_cap_all;
-        if (sl < 0) return fail(LZ4HIP_E_ARGUMENT, "negative source length");
-        max_src = sl > max_src ? sl : max_src;
-        max_dst = dc > max_dst ? dc : max_dst;
-    }
-    const size_t s_stride = align_up((size_t)max_src + 16, 16), d_stride = align_up((size_t)max_dst + 16, 16);
-    // slice size: a small batch goes in one piece; a large one in about 6 slices (knob host_slices; profiles/r02/host_slices_sweep.txt) of
-    // 32 MiB .. 512 MiB of rows each
-    const size_t row_bytes = s_stride + d_stride;
-    // slices: the kernels of a slice take milliseconds however few blocks it has (a 64 KiB block of short sequences needs 2.6 ms
-    // in the wavefront mapping), so small batches are cut less: 1 slice up to ~3 k blocks, 2 at 4 k, 6 from 12 k
-    // (profiles/r03/host_slices_by_batch_size.txt: 4 096 blocks 19.4 GB/s with 2 slices, 14.7-18.4 with 6-8)
-    const int auto_slices = (int)(n / 2048 < 1 ? 1 : (n / 2048 > 6 ? 6 : n / 2048));
-    const int want_slices = knob(kKnobHostSlices) > 0 ? knob(kKnobHostSlices) : auto_slices;
-    int64_t per_slice = (n + want_slices - 1) / want_slices;
-    int64_t lo = (int64_t)((32u << 20) / row_bytes), hi = (int64_t)((512u << 20) / row_bytes);
-    if (slice_hint > 0 && knob(kKnobHostSlices) <= 0 && max_src <= 65536) {
-        // (the hint is for the LZ4HC kernels of blocks <= 64 KiB; whatever the rows are, a slice stays below 4 GiB of staging)
-        const int64_t cap4g = (int64_t)((4ull << 30) / row_bytes);
-        const int64_t hinted = slice_hint < (hi > cap4g ? hi : cap4g) ? slice_hint : (hi > cap4g ? hi : cap4g);
-        per_slice = hinted; hi = hi > hinted ? hi : hinted;
-    }
-    per_slice = per_slice < lo ? lo : per_slice;
-    per_slice = per_slice > hi ? hi : per_slice;
-    per_slice = per_slice < 1 ? 1 : (per_slice > n ? n : per_slice);
-    const size_t m = (size_t)per_slice;
-    // The slice table (equal slices; a quarter slice at both ends -- less time before the first kernel and after the last one -- measured
-    // no gain: profiles/r06/host_tapered_slices_ab.txt, tools/ab/host_tapered_slices.patch).
-    std::vector<int64_t> bounds;
-    try {
-        for (int64_t at = 0; at < n; at += per_slice) bounds.push_back(at);
-        bounds.push_back(n);
-    } catch (const std::bad_alloc&) { return fail(LZ4HIP_E_MEMORY, "out of host memory"); }
-    const int64_t n_slices = (int64_t)bounds.size() - 1;
-    const int slots = n_slices < kHostSlots ? (int)n_slices : kHostSlots;
-    // device and pinned "in" image: [src slots | src_len | dst_cap];  "out" image: [dst slots | result]
-    const size_t in_lens = align_up(s_stride * m, 256), in_caps = in_lens + align_up(4 * m, 256), in_bytes = in_caps + align_up(4 * m, 256);
-    const size_t out_res = align_up(d_stride * m, 256), out_bytes = out_res + align_up(4 * m, 256);
     int dev_now = 0;
     HIP_TRY(hipGetDevice(&dev_now));
     HostContext* hc = host_context(dev_now);
     if (!hc) return fail(LZ4HIP_E_DEVICE, "device index out of range");
-    Scratch& g_scratch = hc->scratch;
-    Pinned* g_pin_in = hc->pin_in;
-    Pinned* g_pin_out = hc->pin_out;
-    if ((rc = g_scratch.reserve((size_t)slots * (in_bytes + out_bytes)))) return rc;
-    for (int k = 0; k < slots; k++) {
-        if ((rc = g_pin_in[k].reserve(in_bytes))) return rc;
-        if ((rc = g_pin_out[k].reserve(out_bytes))) return rc;
-    }
-    if ((rc = hc->pipe.init())) return rc;
-    HostPipe& pp = hc->pipe;
-    uint8_t* d_in[kHostSlots];
-    uint8_t* d_out[kHostSlots];
-    for (int k = 0; k < slots; k++) {
-        d_in[k] = (uint8_t*)g_scratch.p + (size_t)k * (in_bytes + out_bytes);
-        d_out[k] = d_in[k] + in_bytes;
-    }
-
-    auto src_row = [&](int64_t i) { return (const uint8_t*)hb->src + (hb->src_off ? hb->src_off[i] : i * hb->src_stride); };
-    auto src_len = [&](int64_t i) { return hb->src_len ? hb->src_len[i] : hb->src_len_all; };
-    auto dst_cap = [&](int64_t i) { return hb->dst_cap ? hb->dst_cap[i] : hb->dst_cap_all; };
-
-    // drain slice [first, first + cnt) from pinned slot `slot` into the caller's buffers
-    // The scatter of a slice runs on the row pool WITHOUT the calling thread waiting for it: that thread goes on gathering
-    // the next slice (round 3 did gather k+1 and scatter k-1 one after the other: ~23 of the 34 ms of a 16 384-block decode).
-    // A slot's pinned buffer is reused only after its scatter has finished.
-    std::shared_ptr<RowJob> scatter_job[kHostSlots];
-    auto scatter_wait = [&](int slot) {
-        if (scatter_job[slot]) { row_pool()->wait(scatter_job[slot]); scatter_job[slot].reset(); }
-    };
-    auto scatter = [&](int64_t first, int64_t cnt, int slot) {
-        const uint8_t* po = (const uint8_t*)g_pin_out[slot].p;
-        const int32_t* res = (const int32_t*)(po + out_res);
-        for (int64_t j = 0; j < cnt; j++) hb->result[first + j] = res[j];
-        auto row = [=](int64_t j) {
-            // bytes the caller gets back: the result for encoders / unknown-size decode, the full size for known-size decode
-            const int32_t cap = hb->dst_cap ? hb->dst_cap[first + j] : hb->dst_cap_all;
-            int64_t nbytes = dst_len_is_result ? res[j] : cap;
-            if (!dst_len_is_result && res[j] < 0) nbytes = 0;
-            if (nbytes > cap) nbytes = cap;
-            uint8_t* to = (uint8_t*)hb->dst + (hb->dst_off ? hb->dst_off[first + j] : (first + j) * hb->dst_stride);
-            if (nbytes > 0) memcpy(to, po + d_stride * (size_t)j, (size_t)nbytes);
-        };
-        if ((size_t)cnt * d_stride < (4u << 20) || cnt < 2) { for (int64_t j = 0; j < cnt; j++) row(j); return; }
-        try { scatter_job[slot] = row_pool()->submit(cnt, std::function<void(int64_t)>(row), false); }
-        catch (const std::bad_alloc&) { for (int64_t j = 0; j < cnt; j++) row(j); }
-    };
-#define PIPE_TRY(expr) do { if ((expr) != hipSuccess) { err = fail(LZ4HIP_E_DEVICE, #expr " failed"); } } while (0)
-
-    int err = 0;
-    int64_t drained = 0;                                             // slices [0, drained) are back in the caller's buffers
-    auto drain_one = [&]() {                                         // (blocking)
-        const int slot = (int)(drained % slots);
-        PIPE_TRY(hipEventSynchronize(pp.e_out[slot]));
-        if (!err) scatter(bounds[(size_t)drained], bounds[(size_t)drained + 1] - bounds[(size_t)drained], slot);
-        drained++;
-    };
-    // whatever the caller queued on its stream before this call comes first
-    PIPE_TRY(hipEventRecord(pp.e_start, hipStreamPerThread));
-    PIPE_TRY(hipStreamWaitEvent(pp.s_in, pp.e_start, 0));
-    int64_t slice = 0;
-    for (; slice < n_slices && !err; slice++) {
-        const int64_t first = bounds[(size_t)slice], cnt = bounds[(size_t)slice + 1] - first;
-        const int slot = (int)(slice % slots);
-        while (!err && drained + slots <= slice) drain_one();        // the slot's previous slice must be out of its buffers
-        scatter_wait(slot);                                          // ... and in the caller's
-        if (err) break;
-        uint8_t* pi = (uint8_t*)g_pin_in[slot].p;
-        int32_t* lens = (int32_t*)(pi + in_lens);
-        int32_t* caps = (int32_t*)(pi + in_caps);
-        for (int64_t j = 0; j < cnt; j++) { lens[j] = src_len(first + j); caps[j] = dst_cap(first + j); }
-        for_rows(cnt, (size_t)cnt * s_stride, [&, pi, first](int64_t j) {
-            const int32_t sl = src_len(first + j);
-            if (sl > 0) memcpy(pi + s_stride * (size_t)j, src_row(first + j), (size_t)sl);
-        });
-        // copy in (the slot's previous kernels have finished: their slice has been drained)
-        // (the rows the slice has, then its lengths and capacities: a short slice does not pay for a full one's image)
-        PIPE_TRY(hipMemcpyAsync(d_in[slot], pi, s_stride * (size_t)cnt, hipMemcpyHostToDevice, pp.s_in));
-        PIPE_TRY(hipMemcpyAsync(d_in[slot] + in_lens, pi + in_lens, in_bytes - in_lens, hipMemcpyHostToDevice, pp.s_in));
-        PIPE_TRY(hipEventRecord(pp.e_in[slot], pp.s_in));
-        // kernels, on the slot's own stream: after their input has landed
-        hipStream_t ks = pp.s_k[slot];
-        PIPE_TRY(hipStreamWaitEvent(ks, pp.e_in[slot], 0));
-        if (err) break;
-        lz4hip_batch_t db;
-        db.src = d_in[slot]; db.src_off = nullptr; db.src_stride = (int64_t)s_stride; db.src_len = (const int32_t*)(d_in[slot] + in_lens);
-        db.dst = d_out[slot]; db.dst_off = nullptr; db.dst_stride = (int64_t)d_stride; db.dst_cap = (const int32_t*)(d_in[slot] + in_caps);
-        db.dst_cap_all = 0; db.src_len_all = (int32_t)max_src;   /* upper-bound hint */ db.result = (int32_t*)(d_out[slot] + out_res); db.n_blocks = cnt;
-        if ((err = run(&db, ks))) break;
-        PIPE_TRY(hipEventRecord(pp.e_k[slot], ks));
-        // copy out: after the kernels
-        PIPE_TRY(hipStreamWaitEvent(pp.s_out, pp.e_k[slot], 0));
-        PIPE_TRY(hipMemcpyAsync(g_pin_out[slot].p, d_out[slot], d_stride * (size_t)cnt, hipMemcpyDeviceToHost, pp.s_out));
-        PIPE_TRY(hipMemcpyAsync((uint8_t*)g_pin_out[slot].p + out_res, d_out[slot] + out_res, out_bytes - out_res, hipMemcpyDeviceToHost, pp.s_out));
-        PIPE_TRY(hipEventRecord(pp.e_out[slot], pp.s_out));
-        if (err) break;
-        // slices that have already arrived are scattered while the later ones are in flight
-        while (!err && drained < slice && hipEventQuery(pp.e_out[drained % slots]) == hipSuccess) drain_one();
-    }
-    while (!err && drained < slice) drain_one();
-    for (int k = 0; k < kHostSlots; k++) scatter_wait(k);           // (also on error: the jobs read this frame's buffers)
-#undef PIPE_TRY
-    if (err) {
-        (void)hipStreamSynchronize(pp.s_in); (void)hipStreamSynchronize(pp.s_out);
-        for (int k = 0; k < kHostSlots; k++) (void)hipStreamSynchronize(pp.s_k[k]);
-    }
-    return err;
+    return hostbatch::run_host_batch(*hc, hb, dst_len_is_result, run, slice_hint, knob(kKnobHostSlices), knob(kKnobHostThreads));
 }
 
 // Host-resident batch sharded over the devices of `device_mask` (bit d = HIP device d; 0 = every visible device):
@@ -1344,31 +1153,8 @@ int run_host_batch_multi(const lz4hip_batch_t* hb, bool dst_len_is_result, uint6
     if (n == 0) return 0;
     const int nd = (int)devs.size();
 
-    struct Shard {
-        std::vector<int64_t> src_off, dst_off;
-        std::vector<int32_t> src_len, dst_cap, result;
-        lz4hip_batch_t b;
-        int rc = 0;
-        std::string err;
-    };
-    std::vector<Shard> shards((size_t)nd);
-    for (int k = 0; k < nd; k++) {
-        Shard& sh = shards[(size_t)k];
-        const int64_t cnt = n > k ? (n - k + nd - 1) / nd : 0;
-        sh.src_off.resize((size_t)cnt); sh.dst_off.resize((size_t)cnt);
-        sh.src_len.resize((size_t)cnt); sh.dst_cap.resize((size_t)cnt); sh.result.assign((size_t)cnt, 0);
-        for (int64_t j = 0; j < cnt; j++) {
-            const int64_t i = j * nd + k;
-            sh.src_off[(size_t)j] = hb->src_off ? hb->src_off[i] : i * hb->src_stride;
-            sh.dst_off[(size_t)j] = hb->dst_off ? hb->dst_off[i] : i * hb->dst_stride;
-            sh.src_len[(size_t)j] = hb->src_len ? hb->src_len[i] : hb->src_len_all;
-            sh.dst_cap[(size_t)j] = hb->dst_cap ? hb->dst_cap[i] : hb->dst_cap_all;
-        }
-        sh.b = *hb;
-        sh.b.src_off = sh.src_off.data(); sh.b.dst_off = sh.dst_off.data();
-        sh.b.src_len = sh.src_len.data(); sh.b.dst_cap = sh.dst_cap.data();
-        sh.b.result = sh.result.data(); sh.b.n_blocks = cnt;
-    }
+    using hostbatch::Shard;
+    std::vector<Shard> shards = hostbatch::shard_batch(hb, nd);
     if (nd == 1) {                                                   // one device: on the calling thread, with its own context
         int prev_dev = 0;
         HIP_TRY(hipGetDevice(&prev_dev));
@@ -1385,11 +1171,9 @@ int run_host_batch_multi(const lz4hip_batch_t* hb, bool dst_len_is_result, uint6
             w->busy.lock();
             Shard* sh = &shards[(size_t)k];
             const int phys = devs[(size_t)k];
-            const unsigned share = (unsigned)nd;
-            post_rc = w->post([sh, phys, share, dst_len_is_result, run, slice_hint] {
+            post_rc = w->post([sh, phys, dst_len_is_result, run, slice_hint] {
                 if (sh->b.n_blocks == 0) return;
                 if (hipSetDevice(phys) != hipSuccess) { sh->rc = LZ4HIP_E_DEVICE; sh->err = "hipSetDevice failed"; return; }
-                (void)share;
                 // nothing may be thrown across the worker's loop (a detached thread: std::terminate for the whole process)
                 try { sh->rc = run_host_batch(&sh->b, dst_len_is_result, run, slice_hint); }
                 catch (const std::bad_alloc&) { sh->rc = LZ4HIP_E_MEMORY; g_last_error = "out of host memory in a device worker"; }
@@ -1402,13 +1186,14 @@ int run_host_batch_multi(const lz4hip_batch_t* hb, bool dst_len_is_result, uint6
         for (int k = 0; k < posted; k++) { workers[(size_t)k]->wait(); workers[(size_t)k]->busy.unlock(); }
         if (post_rc) return post_rc;
     }
-    for (int k = 0; k < nd; k++) {
-        const Shard& sh = shards[(size_t)k];
-        if (sh.rc) return fail(sh.rc, "device " + std::to_string(devs[(size_t)k]) + ": " + sh.err);
-        for (int64_t j = 0; j < sh.b.n_blocks; j++) hb->result[j * nd + k] = sh.result[(size_t)j];
-    }
+    std::string text;
+    if ((rc = hostbatch::merge_shards(hb, shards, devs.data(), text))) return fail(rc, text);
     return 0;
 }
+
+// what a host-pointer call runs on each slice's device batch
+auto encoder_run(int mode) { return [mode](const lz4hip_batch_t* db, hipStream_t s) { return launch_encode(db, mode, s); }; }
+auto decoder_run(int known) { return [known](const lz4hip_batch_t* db, hipStream_t s) { return launch_decode(db, known, s); }; }
 
 int single(const char* src, int src_len, char* dst, int dst_cap, int kind /*0 fast,1 hc,2 dec known,3 dec unknown*/)
 {
@@ -1628,45 +1413,30 @@ int lz4hip_decode_batch_device(const lz4hip_batch_t* b, int known_output_size, v
     return launch_decode(b, known_output_size, (hipStream_t)stream);
 }
 
-// A single-device host-pointer batch of kHostWorkersMinBlocks blocks or more runs as TWO staging pipelines on the same device (the persistent
-// workers of the multi-device path, block i -> worker i mod 2): one pipeline's kernels and copies fill the gaps of the other's -- a 16 384-block
-// D2 decode 23.6 -> 33.5 GB/s on the driver's box of round 5/6 (profiles/r06/bench_driver_style_call1.json, host_pointer_batch_multi_device).
-// Knob host_workers: 1 = the calling thread's pipeline alone.
-constexpr int64_t kHostWorkersMinBlocks = 8192;
-int host_workers_for(const lz4hip_batch_t* b, int mode_is_hc)                  // (decode; fast encode only where the knob is set)
-{
-    if (!b || b->n_blocks < kHostWorkersMinBlocks || mode_is_hc) return 1;
-    const int k = knob(kKnobHostWorkers);
-    return k > 0 ? (k > 8 ? 8 : k) : 2;
-}
+// How many staging pipelines a single-device call runs as and the slices of an encode: lz4hip_hostbatch.hpp (host_workers_for,
+// encode_host_slice_blocks); here the knob and the device's CU count are fetched for them.
+int host_workers_for(const lz4hip_batch_t* b, int mode_is_hc) { return hostbatch::host_workers_for(b ? b->n_blocks : 0, mode_is_hc != 0, knob(kKnobHostWorkers)); }
 
-// Slices of a host-pointer FAST encode: the wavefront-mapped encoder holds ten blocks per CU (workgroups of five) and a slice's kernel time goes by
-// whole residency rounds -- 2 731 blocks (a sixth of 16 384) are 10.7 per CU = two rounds, 12.5 ms, where 2 560 blocks take 7.6 ms.  So a batch is cut
-// into the fewest EQUAL slices of at most one round each (16 384 blocks: 7 x 2 341), and it runs as ONE pipeline: the kernels are the bottleneck, a
-// second pipeline's slices only compete for the same ten places per CU (16 384 blocks 15.7-16.4 against 11.1-13.8 GB/s with two pipelines and 11.9-14.4
-// with round 5's six equal slices, three runs each on one box: profiles/r06/host_encode_one_pipeline_equal_round_slices.txt; earlier forms of the rule:
-// host_encode_slices_of_one_residency_round.txt, host_tapered_slices_ab.txt).
 int64_t encode_host_slice_blocks(const lz4hip_batch_t* b, int mode)
 {
-    if (mode == LZ4HIP_MODE_HC) return kHcHostSliceBlocks;
+    int cus = 0;
     DeviceState* ds = nullptr;
-    if (!b || b->n_blocks < 4096 || current_device(ds)) {
-        (void)hipGetLastError();
-        return 0;
+    if (mode != LZ4HIP_MODE_HC && b && b->n_blocks >= 4096) {
+        if (current_device(ds)) (void)hipGetLastError();
+        else cus = ds->cus;
     }
-    const int64_t round = (int64_t)2 * kEncodeBlocksPerGroup * ds->cus, slices = (b->n_blocks + round - 1) / round;
-    return (b->n_blocks + slices - 1) / slices;
+    return hostbatch::encode_host_slice_blocks(b ? b->n_blocks : 0, mode, cus);
 }
 
 int lz4hip_encode_batch_host(const lz4hip_batch_t* b, int mode)
 {
-    // (two pipelines only where the knob asks for them: see above)
+    // (two pipelines only where the knob asks for them: see host_workers_for)
     const int workers = mode == LZ4HIP_MODE_HC || knob(kKnobHostWorkers) <= 0 ? 1 : host_workers_for(b, 0);
     const int64_t slice = encode_host_slice_blocks(b, mode);
     int dev = 0;
     if (workers > 1 && hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < kMaxDevices)
-        return run_host_batch_multi(b, true, 1ull << dev, [mode](const lz4hip_batch_t* db, hipStream_t s) { return launch_encode(db, mode, s); }, slice, workers);
-    return run_host_batch(b, true, [mode](const lz4hip_batch_t* db, hipStream_t s) { return launch_encode(db, mode, s); }, slice);
+        return run_host_batch_multi(b, true, 1ull << dev, encoder_run(mode), slice, workers);
+    return run_host_batch(b, true, encoder_run(mode), slice);
 }
 
 int lz4hip_decode_batch_host(const lz4hip_batch_t* b, int known_output_size)
@@ -1674,23 +1444,18 @@ int lz4hip_decode_batch_host(const lz4hip_batch_t* b, int known_output_size)
     const int workers = host_workers_for(b, 0);
     int dev = 0;
     if (workers > 1 && hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < kMaxDevices)
-        return run_host_batch_multi(b, !known_output_size, 1ull << dev,
-                                    [known_output_size](const lz4hip_batch_t* db, hipStream_t s) { return launch_decode(db, known_output_size, s); }, 0, workers);
-    return run_host_batch(b, !known_output_size,
-                          [known_output_size](const lz4hip_batch_t* db, hipStream_t s) { return launch_decode(db, known_output_size, s); });
+        return run_host_batch_multi(b, !known_output_size, 1ull << dev, decoder_run(known_output_size), 0, workers);
+    return run_host_batch(b, !known_output_size, decoder_run(known_output_size));
 }
 
 int lz4hip_encode_batch_host_multi(const lz4hip_batch_t* b, int mode, uint64_t device_mask)
 {
-    return run_host_batch_multi(b, true, device_mask,
-                                [mode](const lz4hip_batch_t* db, hipStream_t s) { return launch_encode(db, mode, s); },
-                                mode == LZ4HIP_MODE_HC ? kHcHostSliceBlocks : 0);
+    return run_host_batch_multi(b, true, device_mask, encoder_run(mode), mode == LZ4HIP_MODE_HC ? kHcHostSliceBlocks : 0);
 }
 
 int lz4hip_decode_batch_host_multi(const lz4hip_batch_t* b, int known_output_size, uint64_t device_mask)
 {
-    return run_host_batch_multi(b, !known_output_size, device_mask,
-                                [known_output_size](const lz4hip_batch_t* db, hipStream_t s) { return launch_decode(db, known_output_size, s); });
+    return run_host_batch_multi(b, !known_output_size, device_mask, decoder_run(known_output_size));
 }
 
 int lz4hip_compress_limitedOutput(const char* source, char* dest, int isize, int maxOutputSize)

@@ -302,3 +302,33 @@ def stream_tables(max_chunks, guard=4, fill=-77):
     arrays["min_bad"] = np.full(1, 0xFFFFFFFFFFFFFFFF, np.uint64)
     t = StreamTables(max_chunks=max_chunks, **{k: addr(v) for k, v in arrays.items()})
     return t, arrays
+
+
+# ---- the host-pointer block batch calls (tests/simt/emu_hostbatch.hpp over lz4net_amd/csrc/lz4hip_hostbatch.hpp) -------------------------
+class HostBatch(C.Structure):
+    """EmuHostBatch: what an emu_host_batch call is to do (the block codec's stand-in, the knobs and limits, EmuStage's behaviour) and
+    what the stage saw (its log of 8-word records, the rows as the kernels found them staged, counters, violations, guard bytes)"""
+    _fields_ = [("results", _P), ("bytes", _P), ("bytes_stride", _I64), ("row0", _I64), ("decoder", _I32), ("fail_at", _I32), ("lag", _I32),
+                ("slices_knob", _I32), ("dst_len_is_result", _I32), ("pad", _I32), ("slice_hint", _I64), ("slice_floor", _I64),
+                ("slice_ceiling", _I64), ("hinted_ceiling", _I64), ("pool_floor", _I64), ("seen_src", _P), ("seen_stride", _I64),
+                ("seen_len", _P), ("seen_cap", _P), ("log", _P), ("log_cap", _I64), ("log_n", _I64), ("rows_seen", _I64),
+                ("kernel_calls", _I64), ("quiesces", _I64), ("reserves", _I64), ("violations", _I32), ("intact", _I32), ("error", C.c_char * 160)]
+
+
+_hostbatch = None
+
+
+def hostbatch():
+    """The library with the emu_host_* entry points typed."""
+    global _hostbatch
+    if _hostbatch is None:
+        L = lib()
+        L.emu_hostbatch_sizeof.restype = C.c_int64
+        assert L.emu_hostbatch_sizeof() == C.sizeof(HostBatch), (L.emu_hostbatch_sizeof(), C.sizeof(HostBatch))
+        ptr, i64, i32 = C.c_void_p, C.c_int64, C.c_int
+        L.emu_host_rule.argtypes, L.emu_host_rule.restype = [i32, i64, i64, i64], C.c_int64
+        L.emu_host_plan.argtypes, L.emu_host_plan.restype = [ptr, i32, i64, ptr, ptr, ptr], C.c_int
+        L.emu_host_batch.argtypes, L.emu_host_batch.restype = [ptr, ptr], C.c_int
+        L.emu_host_shards.argtypes, L.emu_host_shards.restype = [ptr, i32, ptr, C.c_uint, ptr, ptr, ptr], C.c_int
+        _hostbatch = L
+    return _hostbatch

@@ -1,7 +1,8 @@
 // emu_kernels.cpp -- TEST INFRASTRUCTURE ONLY.
 // Compiles the real kernel sources (lz4net_amd/csrc/*.hpp) against the SIMT emulator and exposes
 // them through a C ABI for tests/test_simt_emulation.py and tests/test_simt_framing.py (the framing kernels: entry points in
-// emu_framing.hpp, which run the library's own host code for those paths, lz4hip_framing.hpp).  Built with g++, never shipped.
+// emu_framing.hpp, which run the library's own host code for those paths, lz4hip_framing.hpp) and tests/test_simt_hostbatch.py (the
+// host-pointer block batch calls: emu_hostbatch.hpp over lz4hip_hostbatch.hpp).  Built with g++, never shipped.
 #include "simt_wave.hpp"
 
 static unsigned long long g_iterations = 0;   // loop iterations of the lane decoders (all wavefronts), counted by lane 0
@@ -326,3 +327,4 @@ unsigned long long emu_iterations(int reset) { const unsigned long long v = g_it
 }
 
 #include "emu_framing.hpp"
+#include "emu_hostbatch.hpp"
