@@ -42,6 +42,20 @@ namespace LZ4hip
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
         private static extern unsafe int lz4hip_decode_batch_host_multi(Batch* b, int knownOutputSize, ulong deviceMask);
 
+        // The decoded size of every block before an unknown-size decode (include/lz4hip.h, "the decoded sizes of a batch"): result,
+        // dstCap = max(result, 0) and dstOff[n + 1], their exclusive scan, are what lz4hip_decode_batch_host(b, 0) then takes.
+        // (Declaration only: not compiled or run by this repository's tests.)
+        // struct lz4hip_sizes_info, field for field
+        [StructLayout(LayoutKind.Sequential)]
+        public struct SizesInfo
+        {
+            public long blocks, decoded_bytes, first_error;
+            public int error, reserved;
+        }
+
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        private static extern unsafe int lz4hip_decoded_sizes_host(Batch* b, long* dstOff, int* dstCap, SizesInfo* info);
+
         // Many LZ4Stream buffers per call (include/lz4hip.h, "batches of LZ4Stream buffers"): one buffer plus offsets[n + 1] in, the
         // same layout out; every item becomes / is read as the stream LZ4Stream writes for it, the chunks of all items in one batch.
         // struct lz4hip_streams_info, field for field

@@ -315,6 +315,42 @@ int lz4hip_streams_decode_host(const void* src, int64_t src_len, const int64_t* 
                                void* dst, int64_t dst_cap, int64_t* dst_off, int32_t* status, int64_t* error_offset,
                                lz4hip_streams_info_t* info);
 
+/* ---- the decoded sizes of a batch, before decoding it ---------------------------------------------
+ * What a caller holding nothing but compressed blocks needs before an unknown-size decode: for block i, result[i] is what
+ * LZ4_uncompress_unknownOutputSize (original/lz4.c:916-1044) returns for it when maxOutputSize is too large ever to bind -- the bytes
+ * produced, or -(error position in the source) -- found by walking the block's tokens without writing a byte of output.  An empty
+ * block gives 0; a count above INT32_MAX, where the reference's int would have wrapped, and a negative length give LZ4HIP_E_ARGUMENT.
+ *
+ * For a block that obeys the format's end rules -- the last match starts at least 12 bytes before the end and the last 5 bytes are
+ * literals; every block an LZ4 encoder wrote does -- a following unknown-size decode with dst_cap = result[i] returns result[i].  A
+ * malformed block that walks to a size but breaks those rules then fails in the decoder with the reference's error, exactly as the
+ * reference would at that capacity.
+ *
+ * The call reads b->src, src_off / src_stride, src_len / src_len_all, result and n_blocks; the dst fields are ignored and may be NULL
+ * or 0.  It writes, each only where the pointer is not NULL: b->result[n]; dst_cap[n] = max(result[i], 0); dst_off[n + 1], the
+ * exclusive scan of dst_cap (a packed layout without padding, dst_off[n] = the total); *info.  The two arrays are laid out so that the
+ * second step is the existing call, unchanged:
+ *     lz4hip_batch_t d = *b;  d.dst = out;  d.dst_off = dst_off;  d.dst_cap = dst_cap;  lz4hip_decode_batch_device(&d, 0, stream);
+ * A block whose walk failed has capacity 0 there and fails again without writing a byte. */
+typedef struct lz4hip_sizes_info {
+    int64_t blocks;                     /* n */
+    int64_t decoded_bytes;              /* dst_off[n]: the sum of the non-negative results */
+    int64_t first_error;                /* lowest index with a negative result, -1 if none */
+    int32_t error, reserved;            /* that block's result, 0 if none */
+} lz4hip_sizes_info_t;
+
+/* Device scratch (bytes) of the device call; 0 for an empty batch, non-decreasing in n_blocks. */
+int64_t lz4hip_decoded_sizes_scratch_bytes(int64_t n_blocks);
+/* Device-resident batch: the contract of the other device calls -- device pointers of the CURRENT device, launch-only on `stream`, no
+ * device value read on the host, no allocation, scratch from the caller, 0 or LZ4HIP_E_* returned (arguments are checked first: a NULL
+ * batch, a negative n_blocks or too little scratch is LZ4HIP_E_ARGUMENT whatever the device). */
+int lz4hip_decoded_sizes_device(const lz4hip_batch_t* b, int64_t* dst_off, int32_t* dst_cap,
+                                void* scratch, int64_t scratch_bytes, lz4hip_sizes_info_t* info, void* stream);
+/* Host-resident batch: stages the blocks and their lengths through device memory (per-thread, grow-only, freed by
+ * lz4hip_release_workspaces), runs the device call and synchronises; only result, dst_off, dst_cap and info travel back.  Returns 0
+ * (block failures are in result and info) or LZ4HIP_E_*. */
+int lz4hip_decoded_sizes_host(const lz4hip_batch_t* b, int64_t* dst_off, int32_t* dst_cap, lz4hip_sizes_info_t* info);
+
 /* ---- diagnostics ---------------------------------------------------------------------------------
  * Launch counters per kernel family since the library was loaded: which block->hardware mapping a call
  * actually used (the GPU tests assert these).  Copies min(n, LZ4HIP_K_COUNT) counters, returns LZ4HIP_K_COUNT. */
@@ -378,6 +414,8 @@ int lz4hip_dispatch_counts(uint64_t* counts, int n);
  *                                 device before the first lane-mapped decode (a ~1 ms probe launch) and uses the instantiation that wraps its rows instead (same bytes,
  *                                 a few per cent slower) where the probe does not confirm it.  1 = always the wrapped-row instantiation (debuggers, trap-on-violation
  *                                 modes).  Read-only through lz4hip_tuning_get: "decoder_dual_store" = 1 if lane-mapped decodes on the current device store twice, else 0
+ *   "sizes_groups"               [LZ4HIP_SIZES_GROUPS]  lz4hip_decoded_sizes_*: wavefronts of the walk's grid (0 = one lane per block, one wavefront per
+ *                                 64 blocks; tests use a few so that every lane walks many blocks)
  *   "logical_devices"            [LZ4HIP_LOGICAL_DEVICES]  the *_multi entry points run this many device workers over the
  *                                 selected devices, wrapping around (0 = one per device): exercises the threaded path on one GPU
  * lz4hip_tuning_set returns the previous value (>= 0) or LZ4HIP_E_ARGUMENT; lz4hip_tuning_get the current value. */

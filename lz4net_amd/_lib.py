@@ -50,6 +50,11 @@ class StreamsInfo(C.Structure):
                 ("first_error", C.c_int64), ("error_offset", C.c_int64), ("error", C.c_int32), ("reserved", C.c_int32)]
 
 
+class SizesInfo(C.Structure):
+    """struct lz4hip_sizes_info (include/lz4hip.h)."""
+    _fields_ = [("blocks", C.c_int64), ("decoded_bytes", C.c_int64), ("first_error", C.c_int64), ("error", C.c_int32), ("reserved", C.c_int32)]
+
+
 # every symbol include/lz4hip.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("lz4hip_codec_name", C.c_char_p, []),
@@ -109,6 +114,9 @@ SYMBOLS = [
     ("lz4hip_streams_encode_host", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
     ("lz4hip_streams_decode_host", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                              C.POINTER(StreamsInfo)]),
+    ("lz4hip_decoded_sizes_scratch_bytes", C.c_int64, [C.c_int64]),
+    ("lz4hip_decoded_sizes_device", C.c_int, [C.POINTER(Batch), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    ("lz4hip_decoded_sizes_host", C.c_int, [C.POINTER(Batch), C.c_void_p, C.c_void_p, C.POINTER(SizesInfo)]),
 ]
 
 _lib = None

@@ -109,6 +109,64 @@ def count_mismatches(a: torch.Tensor, b: torch.Tensor, lens) -> int:
     return int(bad.item())
 
 
+# ---- sizing a batch before decoding it ---------------------------------------------------------------
+def _source(src, src_len, src_off):
+    """(n, lz4hip_batch_t without outputs, tensors to keep alive): rows of a 2-D tensor, or a 1-D buffer with int64 offsets."""
+    assert src.dtype == torch.uint8 and src.is_cuda and src.stride(-1) == 1
+    if src_off is None:
+        assert src.dim() == 2
+        n, stride = src.shape[0], src.stride(0)
+    else:
+        assert src.dim() == 1 and src_off.dtype == torch.int64 and src_off.is_cuda and src_off.is_contiguous()
+        n, stride = src_off.numel(), 0
+    sl, sl_all = _lens(src_len, n, src.device)
+    b = _lib.Batch(src=src.data_ptr(), src_off=_ptr(src_off), src_stride=stride, src_len=_ptr(sl), dst=None, dst_off=None,
+                   dst_stride=0, dst_cap=None, dst_cap_all=0, src_len_all=sl_all, result=None, n_blocks=n)
+    return n, b, (sl, src_off)
+
+
+def read_sizes_info(info: torch.Tensor) -> _lib.SizesInfo:
+    """The lz4hip_sizes_info_t a decoded_sizes call left on the device (synchronises)."""
+    return _lib.SizesInfo.from_buffer_copy(info.cpu().numpy().tobytes())
+
+
+def decoded_sizes(src: torch.Tensor, src_len, src_off: torch.Tensor | None = None, result: torch.Tensor | None = None):
+    """What an unknown-size decode of every block would produce, without decoding it (lz4hip_decoded_sizes_device): block i is row i
+    of a 2-D `src`, or src[src_off[i]:] of a 1-D one.  Returns (sizes, offsets, info), all on the device and not waited for:
+    sizes[i] = max(result[i], 0) (int32), offsets (int64, n + 1) their exclusive scan -- the dst_cap and dst_off of a packed decode --
+    and the lz4hip_sizes_info_t record as four int64 (read_sizes_info).  `result` (int32, n) receives the per-block results: bytes
+    produced, or -(error position), as LZ4_uncompress_unknownOutputSize with an unbounded output."""
+    n, b, keep = _source(src, src_len, src_off)
+    sizes = torch.empty(n, dtype=torch.int32, device=src.device)
+    offsets = torch.empty(n + 1, dtype=torch.int64, device=src.device)
+    info = torch.empty(4, dtype=torch.int64, device=src.device)
+    if result is not None:
+        assert result.dtype == torch.int32 and result.numel() == n and result.is_cuda and result.is_contiguous()
+        b.result = result.data_ptr()
+    need = _lib.lib().lz4hip_decoded_sizes_scratch_bytes(n)
+    scratch = torch.empty(max(need, 1), dtype=torch.uint8, device=src.device)
+    _lib.check(_lib.lib().lz4hip_decoded_sizes_device(C.byref(b), offsets.data_ptr(), sizes.data_ptr(), scratch.data_ptr(), need,
+                                                      info.data_ptr(), _stream()))
+    return sizes, offsets, info
+
+
+def decode_packed(src: torch.Tensor, src_len, src_off: torch.Tensor | None = None):
+    """Decode blocks of unknown size into a buffer of exactly the bytes they produce: the size query, ONE synchronisation to read its
+    info, then lz4hip_decode_batch_device (unknown size) on the offsets and capacities the query wrote.  Returns (dst, offsets,
+    results): block i is dst[offsets[i]:offsets[i + 1]] and results[i] its size, negative (and no byte written) for a corrupt one."""
+    n, b, keep = _source(src, src_len, src_off)
+    sizes, offsets, info = decoded_sizes(src, src_len, src_off)
+    total = read_sizes_info(info).decoded_bytes
+    dst = torch.empty(total, dtype=torch.uint8, device=src.device)
+    results = torch.empty(n, dtype=torch.int32, device=src.device)
+    if n == 0:
+        return dst, offsets, results
+    guard = dst if total > 0 else torch.empty(1, dtype=torch.uint8, device=src.device)      # (dst must be non-NULL even if nothing fits)
+    b.dst, b.dst_off, b.dst_cap, b.result = guard.data_ptr(), offsets.data_ptr(), sizes.data_ptr(), results.data_ptr()
+    _lib.check(_lib.lib().lz4hip_decode_batch_device(C.byref(b), 0, _stream()))
+    return dst, offsets, results
+
+
 # ---- round-robin sharding -------------------------------------------------------------------------
 def local_block_count(n_blocks: int, rank: int, world: int) -> int:
     """Blocks owned by `rank` when block i lives on rank i % world."""

@@ -59,7 +59,7 @@ void count_dispatch(int k) { g_dispatch[k].fetch_add(1, std::memory_order_relaxe
 // first time any knob is looked at; after that the launch paths read an atomic and never call getenv().
 // Mappings: 0 = automatic, 1 = one wavefront per block, 2 = one lane per block.
 enum Knob { kKnobDecoder = 0, kKnobEncoder, kKnobHc, kKnobEncoderWavesPerCu, kKnobHcWavesPerCu, kKnobHcGroups,
-            kKnobHostThreads, kKnobHostSlices, kKnobLogicalDevices, kKnobDecoderGen, kKnobDecoderRing, kKnobHcGen, kKnobHcCtrlEvery, kKnobHcCtrlLanes, kKnobHcSubChunks, kKnobDecoderPersist, kKnobDecoderGroups, kKnobEncoderSlabTries, kKnobEncoderWaveVersion, kKnobEncoderWg5, kKnobHostWorkers, kKnobDecoderWg4, kKnobDecoderWrappedStores, kKnobCount };
+            kKnobHostThreads, kKnobHostSlices, kKnobLogicalDevices, kKnobDecoderGen, kKnobDecoderRing, kKnobHcGen, kKnobHcCtrlEvery, kKnobHcCtrlLanes, kKnobHcSubChunks, kKnobDecoderPersist, kKnobDecoderGroups, kKnobEncoderSlabTries, kKnobEncoderWaveVersion, kKnobEncoderWg5, kKnobHostWorkers, kKnobDecoderWg4, kKnobDecoderWrappedStores, kKnobSizesGroups, kKnobCount };
 struct KnobInfo { const char* name; const char* env; bool mapping; };
 const KnobInfo kKnobInfo[kKnobCount] = {
     { "decoder", "LZ4HIP_DECODER", true }, { "encoder", "LZ4HIP_ENCODER", true }, { "hc", "LZ4HIP_HC", true },
@@ -80,6 +80,7 @@ const KnobInfo kKnobInfo[kKnobCount] = {
     { "host_workers", "LZ4HIP_HOST_WORKERS", false },                 // single-device host-pointer batches of >= 8192 blocks: staging pipelines (persistent worker threads) that share the device, each taking every k-th block (0 default = 2 for decode, 1 for the encoders; 1 = the calling thread's pipeline alone, rounds 2-5)
     { "decoder_wg4", "LZ4HIP_DECODER_WG4", false },                   // lane decoder, batches of at most one residency round: 0 default = workgroups of FOUR wavefronts (one per SIMD of a CU) while the batch has more than one wavefront per CU and at most one residency round; 1 = always workgroups of one wavefront (rounds 1-5); 2 = the four-wavefront form from four wavefronts on (tests); 3 = whatever the batch size (A/B runs)
     { "decoder_wrapped_stores", "LZ4HIP_DECODER_WRAPPED_STORES", false },   // lane decoder: 1 = the instantiation that WRAPS its ring rows (no LDS store outside the allocation) whatever the device's probe said; 0 default = what the probe allows (read-only twin: "decoder_dual_store")
+    { "sizes_groups", "LZ4HIP_SIZES_GROUPS", false },                 // lz4hip_decoded_sizes_*: wavefronts of the walk's grid (0 default = one wavefront per 64 blocks; tests: few wavefronts, many blocks per lane)
 };
 std::atomic<int> g_knob[kKnobCount];
 std::once_flag g_knob_once;
@@ -1682,6 +1683,29 @@ int lz4hip_streams_decode_host(const void* src, int64_t src_len, const int64_t* 
     HipBackend be = {};
     if (int rc = stream_host_context(be)) return rc;
     return streams_decode_host(be, src, src_len, src_off, n, dst, dst_cap, dst_off, status, error_offset, info);
+}
+
+int64_t lz4hip_decoded_sizes_scratch_bytes(int64_t n_blocks) { return sizes_scratch_bytes(n_blocks); }
+
+// (the arguments are checked before the device is looked for: a bad call is LZ4HIP_E_ARGUMENT on any machine)
+int lz4hip_decoded_sizes_device(const lz4hip_batch_t* b, int64_t* dst_off, int32_t* dst_cap, void* scratch, int64_t scratch_bytes,
+                                lz4hip_sizes_info_t* info, void* stream)
+{
+    if (!b) return fail(LZ4HIP_E_ARGUMENT, "decoded sizes: batch descriptor is NULL");
+    if (b->n_blocks < 0) return fail(LZ4HIP_E_ARGUMENT, "decoded sizes: n_blocks < 0");
+    if (scratch_bytes < sizes_scratch_bytes(b->n_blocks)) return fail(LZ4HIP_E_ARGUMENT, "decoded sizes: scratch_bytes < lz4hip_decoded_sizes_scratch_bytes");
+    if (b->n_blocks == 0 && !dst_off && !info) return 0;                // (nothing to write)
+    int rc = ensure_device();
+    if (rc) return rc;
+    HipBackend be = { (hipStream_t)stream };
+    return decoded_sizes(be, b, dst_off, dst_cap, scratch, scratch_bytes, info, knob(kKnobSizesGroups));
+}
+
+int lz4hip_decoded_sizes_host(const lz4hip_batch_t* b, int64_t* dst_off, int32_t* dst_cap, lz4hip_sizes_info_t* info)
+{
+    HipBackend be = {};
+    if (int rc = stream_host_context(be)) return rc;
+    return hostbatch::decoded_sizes_host(be, b, dst_off, dst_cap, info, knob(kKnobSizesGroups), knob(kKnobHostThreads));
 }
 
 }  // extern "C"

@@ -1,4 +1,5 @@
-// lz4hip_framing.hpp -- host side of the framing paths (LZ4Stream buffers, wrapped messages, batches of LZ4Stream buffers): the scratch
+// lz4hip_framing.hpp -- host side of the framing paths (LZ4Stream buffers, wrapped messages, batches of LZ4Stream buffers) and of the block
+// batch's size query (lz4hip_sizes.hpp): the scratch
 // layouts, the grids and the kernel sequences around the block codec, written ONCE for the library (lz4hip_api.hip, HipBackend) and for
 // the CPU emulator (tests/simt/emu_framing.hpp, EmuBackend).  Host code only: no kernel is defined here and nothing here calls the HIP
 // runtime or the emulator; everything that touches the device goes through the backend B, which has exactly
@@ -23,6 +24,7 @@
 #include "lz4hip_stream.hpp"
 #include "lz4hip_wrap.hpp"
 #include "lz4hip_streams.hpp"
+#include "lz4hip_sizes.hpp"
 
 #include "../../include/lz4hip.h"
 
@@ -41,6 +43,9 @@ static_assert(kWrapBadOffsets == LZ4HIP_E_ARGUMENT && kWrapSizeInvalid == LZ4HIP
 static_assert(sizeof(StreamsInfo) == sizeof(lz4hip_streams_info_t) && offsetof(StreamsInfo, error) == offsetof(lz4hip_streams_info_t, error) &&
               offsetof(StreamsInfo, first_error) == offsetof(lz4hip_streams_info_t, first_error), "StreamsInfo must mirror lz4hip_streams_info_t");
 static_assert(kStreamsBadOffsets == LZ4HIP_E_ARGUMENT, "streams statuses");
+static_assert(sizeof(SizesInfo) == sizeof(lz4hip_sizes_info_t) && offsetof(SizesInfo, first_error) == offsetof(lz4hip_sizes_info_t, first_error) &&
+              offsetof(SizesInfo, error) == offsetof(lz4hip_sizes_info_t, error), "SizesInfo must mirror lz4hip_sizes_info_t");
+static_assert(kSizesTooLarge == LZ4HIP_E_ARGUMENT, "sizes results");
 
 #define LZ4HIP_FRAMING_TRY(expr) do { if (int rc_ = (expr)) return rc_; } while (0)
 
@@ -65,6 +70,14 @@ inline Grid copy_grid(int64_t bytes)
     return { g < 1 ? 1u : (g > kStreamMaxGroups ? kStreamMaxGroups : (unsigned)g), kGridCopy };
 }
 inline Grid walk_grid(int64_t n) { return { n < (int64_t)kStreamsMaxWalkGroups ? (unsigned)n : kStreamsMaxWalkGroups, kGridWalk }; }
+// the size query: one lane per block in single-wavefront workgroups, at most kStreamsMaxWalkGroups of them (then a lane takes several
+// blocks); `groups` > 0 (the knob sizes_groups, the emulator's tests) replaces the formula's answer
+inline Grid sizes_grid(int64_t n, int groups)
+{
+    const int64_t g = (n + kSizesThreads - 1) / kSizesThreads;
+    if (groups > 0) return { (unsigned)groups, kGridFixed };
+    return { g < 1 ? 1u : (g > (int64_t)kStreamsMaxWalkGroups ? kStreamsMaxWalkGroups : (unsigned)g), kGridFixed };
+}
 
 // ---- sizes ---------------------------------------------------------------------------------------------------------------------
 inline int64_t stream_block(int32_t block_size) { return block_size < 16 ? 16 : block_size; }
@@ -595,6 +608,57 @@ int streams_decode(B& be, const void* src, int64_t src_len, const int64_t* src_o
     StreamsInfo from_index;
     memcpy(&from_index, &h, sizeof from_index);
     return streams_decode_run(be, a, t, from_index, (uint8_t*)dst, (StreamsInfo*)info);
+}
+
+// ---- the decoded sizes of a block batch (lz4hip_sizes.hpp) ----------------------------------------------------------------------------
+// scratch: the lowest failing index, then stand-ins for the outputs the caller left out (results, sizes / offsets), the scan's tile sums
+struct SizesScratch { unsigned long long* min_bad; int32_t* result; int64_t* offs; int64_t* partial; int64_t bytes; };
+inline SizesScratch sizes_scratch(void* scratch, int64_t n)
+{
+    Carver c(scratch);
+    SizesScratch l;
+    l.min_bad = c.take_as<unsigned long long>(256);
+    l.result = c.take_as<int32_t>(4 * n);
+    l.offs = c.take_as<int64_t>(8 * (n + 1));
+    l.partial = c.take_as<int64_t>(8 * scan_tiles(n));
+    l.bytes = c.at;
+    return l;
+}
+inline int64_t sizes_scratch_bytes(int64_t n) { return n <= 0 ? 0 : sizes_scratch(nullptr, n).bytes; }
+
+// a.n > 0; a.offs has n + 1 entries and receives the offsets, a.offs[n] the total
+template <class B>
+int decoded_sizes_run(B& be, const SizesArgs& a, int64_t* partial, SizesInfo* info, int groups)
+{
+    LZ4HIP_FRAMING_TRY(be.fill(a.min_bad, 0xFF, 8));                   // min_bad = none
+    be.launch(sizes_walk_kernel, sizes_grid(a.n, groups), kSizesThreads, a);
+    launch_scan(be, a.offs, a.n, partial, a.offs + a.n);
+    if (info) be.launch(sizes_info_kernel, fixed_grid(1), 64, a, info);
+    return be.last_error();
+}
+
+// reads b's src, src_off / src_stride, src_len / src_len_all, result and n_blocks; any of result, dst_off, dst_cap and info may be NULL
+template <class B>
+int decoded_sizes(B& be, const lz4hip_batch_t* b, int64_t* dst_off, int32_t* dst_cap, void* scratch, int64_t scratch_bytes,
+                  lz4hip_sizes_info_t* info, int groups = 0)
+{
+    if (!b) return be.fail(LZ4HIP_E_ARGUMENT, "decoded sizes: batch descriptor is NULL");
+    const int64_t n = b->n_blocks;
+    if (n < 0) return be.fail(LZ4HIP_E_ARGUMENT, "decoded sizes: n_blocks < 0");
+    if (n > 0x7FFFFFFF) return be.fail(LZ4HIP_E_ARGUMENT, "decoded sizes: more than 2^31 - 1 blocks");
+    if (scratch_bytes < sizes_scratch_bytes(n)) return be.fail(LZ4HIP_E_ARGUMENT, "decoded sizes: scratch_bytes < lz4hip_decoded_sizes_scratch_bytes");
+    if (n == 0) {
+        if (dst_off) LZ4HIP_FRAMING_TRY(be.fill(dst_off, 0, sizeof(int64_t)));
+        if (info) be.launch(sizes_empty_info_kernel, fixed_grid(1), 64, (SizesInfo*)info);
+        return be.last_error();
+    }
+    if (!b->src || !scratch) return be.fail(LZ4HIP_E_ARGUMENT, "decoded sizes: src and scratch must be non-NULL");
+    if (!b->src_len && b->src_len_all < 0) return be.fail(LZ4HIP_E_ARGUMENT, "decoded sizes: src_len_all < 0");
+    const SizesScratch l = sizes_scratch(scratch, n);
+    SizesArgs a;
+    a.src = (const uint8_t*)b->src; a.src_off = b->src_off; a.src_stride = b->src_stride; a.src_len = b->src_len; a.src_len_all = b->src_len_all;
+    a.n = n; a.result = b->result ? b->result : l.result; a.dst_cap = dst_cap; a.offs = dst_off ? dst_off : l.offs; a.min_bad = l.min_bad;
+    return decoded_sizes_run(be, a, l.partial, (SizesInfo*)info, groups);
 }
 
 // ---- the host-pointer calls ------------------------------------------------------------------------------------------------------------

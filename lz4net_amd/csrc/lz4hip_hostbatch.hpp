@@ -1,5 +1,5 @@
 // lz4hip_hostbatch.hpp -- host side of the host-pointer BLOCK batch calls (lz4hip_*_batch_host, *_host_multi and, through them, the seven
-// single-block calls): how a batch of caller rows is cut into slices, the two staging images of a slice, the gather and scatter of
+// single-block calls; lz4hip_decoded_sizes_host, decoded_sizes_host below, over the framing backend instead of the stage): how a batch of caller rows is cut into slices, the two staging images of a slice, the gather and scatter of
 // rows, the order in which slices travel through kHostSlots sets of buffers, and the round-robin shards of the multi-device form,
 // written ONCE for the library (lz4hip_api.hip, HostContext) and for the CPU tests (tests/simt/emu_hostbatch.hpp, EmuStage).  Host code
 // only: nothing here calls the HIP runtime; everything that touches a device goes through the stage S of run_host_batch, which has
@@ -353,6 +353,65 @@ int run_host_batch(Stage& st, const lz4hip_batch_t* hb, bool dst_len_is_result, 
     for (int k = 0; k < kHostSlots; k++) scatter_wait(k);           // (also on error: the jobs read the stage's images and the caller's batch)
     if (err) st.quiesce();
     return err;
+}
+
+// ---- the decoded sizes of a host-pointer batch ---------------------------------------------------------------------------------------
+// lz4hip_decoded_sizes_host: the rows are gathered back to back (the row work above), staged with their lengths in ONE device image of
+// the framing backend B, sized by the device call (framing::decoded_sizes), and only result, dst_off, dst_cap and info come back -- no
+// block payload travels in that direction.  Every row is needed before the offsets can be scanned, so there are no slices here.
+template <class B>
+int decoded_sizes_host(B& be, const lz4hip_batch_t* hb, int64_t* dst_off, int32_t* dst_cap, lz4hip_sizes_info_t* info, int groups, int threads_knob,
+                       const HostLimits& limits = HostLimits())
+{
+    if (!hb) return be.fail(LZ4HIP_E_ARGUMENT, "decoded sizes: batch descriptor is NULL");
+    const int64_t n = hb->n_blocks;
+    if (n < 0) return be.fail(LZ4HIP_E_ARGUMENT, "decoded sizes: n_blocks < 0");
+    if (n > 0x7FFFFFFF) return be.fail(LZ4HIP_E_ARGUMENT, "decoded sizes: more than 2^31 - 1 blocks");
+    if (n == 0) {
+        if (dst_off) dst_off[0] = 0;
+        if (info) { lz4hip_sizes_info_t r = {}; r.first_error = -1; *info = r; }
+        return 0;
+    }
+    if (!hb->src) return be.fail(LZ4HIP_E_ARGUMENT, "decoded sizes: src must be non-NULL");
+    std::vector<int64_t> at;
+    std::vector<int32_t> lens;
+    std::vector<uint8_t> rows;
+    int64_t total = 0;
+    try {
+        at.resize((size_t)n); lens.resize((size_t)n);
+        for (int64_t i = 0; i < n; i++) {
+            const int32_t sl = src_len(hb, i);
+            if (sl < 0) return be.fail(LZ4HIP_E_ARGUMENT, "negative source length");
+            at[(size_t)i] = total; lens[(size_t)i] = sl; total += sl;
+        }
+        rows.resize((size_t)total);
+    } catch (const std::bad_alloc&) { return be.fail(LZ4HIP_E_MEMORY, "decoded sizes: no host memory to gather the rows in"); }
+    uint8_t* const packed = rows.data();
+    const int64_t* const at_p = at.data();
+    const int32_t* const len_p = lens.data();
+    for_rows(n, total, limits, threads_knob, [=](int64_t i) {
+        if (len_p[i] > 0) memcpy(packed + at_p[i], src_row(hb, i), (size_t)len_p[i]);
+    });
+    // device image: [rows | offsets | lengths | results | sizes | output offsets | info | scratch]
+    const int64_t scratch_bytes = framing::sizes_scratch_bytes(n);
+    Carver c;
+    c.take(total);
+    const int64_t off_at = c.take(8 * n), len_at = c.take(4 * n), res_at = c.take(4 * n), cap_at = c.take(4 * n), doff_at = c.take(8 * (n + 1)),
+                  info_at = c.take(256), scratch_at = c.take(scratch_bytes);
+    framing::Image<B> im = { be };
+    if (int rc = im.reserve(c.at)) return rc;
+    if (int rc = im.upload_source(packed, total)) return rc;
+    if (int rc = im.upload(off_at, at_p, 8 * n)) return rc;
+    if (int rc = im.upload(len_at, len_p, 4 * n)) return rc;
+    lz4hip_batch_t db = {};
+    db.src = im.d; db.src_off = im.i64(off_at); db.src_len = im.i32(len_at); db.result = im.i32(res_at); db.n_blocks = n;
+    if (int rc = framing::decoded_sizes(be, &db, im.i64(doff_at), im.i32(cap_at), im.d + scratch_at, scratch_bytes,
+                                        (lz4hip_sizes_info_t*)(im.d + info_at), groups)) return rc;
+    if (hb->result) if (int rc = im.download(hb->result, res_at, 4 * n)) return rc;
+    if (dst_off) if (int rc = im.download(dst_off, doff_at, 8 * (n + 1))) return rc;
+    if (dst_cap) if (int rc = im.download(dst_cap, cap_at, 4 * n)) return rc;
+    if (info) if (int rc = im.download(info, info_at, sizeof *info)) return rc;
+    return be.sync();                                                  // (also what keeps the gathered rows alive until the upload has read them)
 }
 
 // ---- the shards of the multi-device form -----------------------------------------------------------------------------------------------
