@@ -78,6 +78,27 @@ namespace LZ4hip
         private static extern unsafe int lz4hip_streams_decode_host(byte* src, long srcLen, long* srcOff, long n, byte* dst, long dstCap,
                                                                     long* dstOff, int* status, long* errorOffset, StreamsInfo* info);
 
+        // Whole legacy frames of the reference's command-line tool per call (include/lz4hip.h, "legacy frames"): magic, then a size field
+        // and an LZ4 block per chunk; chunkSize 0 = the tool's 8 MiB.  (Declarations only: not compiled or run by this repository's tests,
+        // tests/test_gpu_frame_device.py calls the same symbols through ctypes.)
+        // struct lz4hip_frame_info, field for field
+        [StructLayout(LayoutKind.Sequential)]
+        public struct FrameInfo
+        {
+            public long chunks, decoded_bytes, good_bytes, error_offset;
+            public int error, reserved;
+        }
+
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        private static extern long lz4hip_frame_bound(long srcLen, int chunkSize);
+
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        private static extern unsafe int lz4hip_frame_encode_host(byte* src, long srcLen, int chunkSize, int mode, byte* dst, long dstCap, long* dstLen);
+
+        // returns info->error (LZ4HIP_FRAME_*); dstCap = 0 is a size query: LZ4HIP_E_ARGUMENT with *info filled in
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        private static extern unsafe int lz4hip_frame_decode_host(byte* src, long srcLen, int chunkSize, byte* dst, long dstCap, FrameInfo* info);
+
         /// <summary>Devices the batch calls shard over (bit d = HIP device d; 0 = every visible device).</summary>
         public static ulong DeviceMask = 0;
 

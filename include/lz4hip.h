@@ -351,6 +351,72 @@ int lz4hip_decoded_sizes_device(const lz4hip_batch_t* b, int64_t* dst_off, int32
  * (block failures are in result and info) or LZ4HIP_E_*. */
 int lz4hip_decoded_sizes_host(const lz4hip_batch_t* b, int64_t* dst_off, int32_t* dst_cap, lz4hip_sizes_info_t* info);
 
+/* ---- legacy frames ---------------------------------------------------------------------------------
+ * The frame of the demo command-line tool that ships with the reference (original/lz4demo.c:84-87, 167-317), the one format here that
+ * files from outside the lz4net world arrive in:
+ *     LE32 magic 0x184C2102   { LE32 compressedSize  payload }*
+ * The writer cuts a source of src_len bytes into ceil(src_len / chunk_size) chunks (8 MiB in the tool) and compresses each with
+ * LZ4_compress / LZ4_compressHC into an LZ4_compressBound buffer; an empty source is the 4 magic bytes alone.  The reader checks the
+ * magic, skips a size field that equals the magic (the header of an appended frame) and decodes every payload with
+ * LZ4_uncompress_unknownOutputSize(in, out, size, chunk_size); a negative result ends the read.  An empty chunk (size field 0) decodes
+ * to 0 bytes, as it does there.  chunk_size: 0 means 8 MiB, 1 .. 0x7E000000 (LZ4_MAX_INPUT_SIZE) is taken as given, anything else is
+ * LZ4HIP_E_ARGUMENT.  Frame-level outcomes (lz4hip_frame_info_t.error): */
+#define LZ4HIP_FRAME_OK            0
+#define LZ4HIP_FRAME_BAD_MAGIC     1   /* fewer than 4 bytes, or the first 4 are not the magic ("Unrecognized header") */
+#define LZ4HIP_FRAME_TRUNCATED     2   /* 1-3 bytes where a size field should be, or a payload that runs past the end   */
+#define LZ4HIP_FRAME_BAD_SIZE      3   /* a size field above the compressBound of chunk_size: more than the writer can produce
+                                          and than the reference reader's buffer holds; tested BEFORE the truncation rule */
+#define LZ4HIP_FRAME_CORRUPT_BLOCK 4   /* a chunk did not decode into <= chunk_size bytes ("Decoding Failed ! Corrupted input !") */
+#define LZ4HIP_FRAME_TABLE_FULL    5   /* more chunks than max_chunks; .chunks = the count needed */
+typedef struct lz4hip_frame_info {
+    int64_t chunks;         /* chunks before the first header error (all of them, also when the table is full) */
+    int64_t decoded_bytes;  /* dst_off[chunks]: the sum of the caps; the output buffer's size */
+    int64_t good_bytes;     /* what a sequential reader has written when it stops: dst_off[first bad chunk], decoded_bytes if none */
+    int64_t error_offset;   /* frame offset of the failing size field (BAD_MAGIC: 0; TABLE_FULL: of the first chunk that did not fit), -1 if none */
+    int32_t error, reserved;
+} lz4hip_frame_info_t;
+
+/* Bytes a frame can take: 4 + sum over the chunks of (4 + compressBound(len_k)); 4 for an empty source. */
+int64_t lz4hip_frame_bound(int64_t src_len, int32_t chunk_size);
+/* Device scratch (bytes) of the device calls below.  The encoder's includes one compressBound slot per chunk; an empty source still
+ * needs its few hundred bytes. */
+int64_t lz4hip_frame_encode_scratch_bytes(int64_t src_len, int32_t chunk_size);
+int64_t lz4hip_frame_decode_scratch_bytes(int64_t max_chunks);
+
+/* Device-resident frames: the contract of the LZ4Stream device calls -- device pointers of the CURRENT device, launch-only on `stream`
+ * (a hipStream_t, NULL = default stream), no device value read on the host, no allocation, scratch from the caller, 0 or LZ4HIP_E_*
+ * returned.  Arguments are checked first: LZ4HIP_E_ARGUMENT for them holds whatever the device.  The first-use exceptions of
+ * lz4hip_encode_batch_device / lz4hip_decode_batch_device, which these calls run on the chunks, apply.
+ *
+ * Encode: writes the frame to dst (dst_cap >= lz4hip_frame_bound, else LZ4HIP_E_ARGUMENT) and its length to *dst_len (device).  With
+ * a compressBound capacity the block encoder cannot fail, so there is no per-chunk failure. */
+int lz4hip_frame_encode_device(const void* src, int64_t src_len, int32_t chunk_size, int mode, void* dst, int64_t dst_cap,
+                               int64_t* dst_len, void* scratch, int64_t scratch_bytes, void* stream);
+/* Decode is two calls; the caller reads *info back between them (one synchronisation) to learn the chunk count and the output size.
+ * Index: walks the size fields of src[0, src_len) into a table of max_chunks rows in scratch, finds every chunk's decoded size without
+ * decoding it (as lz4hip_decoded_sizes_device does) and writes *info (device).  A chunk whose size walk fails or exceeds chunk_size
+ * -- the chunk the reference's reader fails on -- is a bad chunk: it takes 0 bytes of the output, so its neighbours pack around it,
+ * and turns the outcome into LZ4HIP_FRAME_CORRUPT_BLOCK at the LOWEST such chunk's size field; that always wins over the header
+ * error, which lies after every chunk in the table.  With more chunks than max_chunks, info.error = LZ4HIP_FRAME_TABLE_FULL and
+ * info.chunks is the count needed.
+ * Decode: given the info the index reported (host copy) and the same scratch and max_chunks, decodes every chunk before the first header
+ * error, bad ones excepted, into dst[0, decoded_bytes) -- exactly the decoded size, no slot per chunk -- and writes *info (device)
+ * again: a chunk that walked to a size but breaks the format's end rules fails in the decoder and is a bad chunk too.  A bad chunk
+ * never disturbs another chunk's bytes and no byte outside [0, decoded_bytes) is written.  LZ4HIP_E_ARGUMENT for an info_host with
+ * TABLE_FULL, counts that do not fit max_chunks, or decoded_bytes > dst_cap. */
+int lz4hip_frame_index_device(const void* src, int64_t src_len, int32_t chunk_size, int64_t max_chunks,
+                              void* scratch, int64_t scratch_bytes, lz4hip_frame_info_t* info, void* stream);
+int lz4hip_frame_decode_device(const void* src, const lz4hip_frame_info_t* info_host, int64_t max_chunks,
+                               void* scratch, int64_t scratch_bytes, void* dst, int64_t dst_cap,
+                               lz4hip_frame_info_t* info, void* stream);
+
+/* Host-resident frames: stage the whole buffer through device memory (per-thread, grow-only, freed by lz4hip_release_workspaces), run
+ * the device calls above and synchronise.  Encode returns 0 or LZ4HIP_E_* (dst_cap >= lz4hip_frame_bound); *dst_len on the host.
+ * Decode returns info->error (0 or a positive LZ4HIP_FRAME_* code, with dst[0, decoded_bytes) filled) or LZ4HIP_E_*; with dst_cap below
+ * the decoded size it returns LZ4HIP_E_ARGUMENT with *info filled in (a size query: dst_cap = 0). */
+int lz4hip_frame_encode_host(const void* src, int64_t src_len, int32_t chunk_size, int mode, void* dst, int64_t dst_cap, int64_t* dst_len);
+int lz4hip_frame_decode_host(const void* src, int64_t src_len, int32_t chunk_size, void* dst, int64_t dst_cap, lz4hip_frame_info_t* info);
+
 /* ---- diagnostics ---------------------------------------------------------------------------------
  * Launch counters per kernel family since the library was loaded: which block->hardware mapping a call
  * actually used (the GPU tests assert these).  Copies min(n, LZ4HIP_K_COUNT) counters, returns LZ4HIP_K_COUNT. */

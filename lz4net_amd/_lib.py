@@ -55,6 +55,15 @@ class SizesInfo(C.Structure):
     _fields_ = [("blocks", C.c_int64), ("decoded_bytes", C.c_int64), ("first_error", C.c_int64), ("error", C.c_int32), ("reserved", C.c_int32)]
 
 
+class FrameInfo(C.Structure):
+    """struct lz4hip_frame_info (include/lz4hip.h)."""
+    _fields_ = [("chunks", C.c_int64), ("decoded_bytes", C.c_int64), ("good_bytes", C.c_int64), ("error_offset", C.c_int64),
+                ("error", C.c_int32), ("reserved", C.c_int32)]
+
+
+FRAME_OK, FRAME_BAD_MAGIC, FRAME_TRUNCATED, FRAME_BAD_SIZE, FRAME_CORRUPT_BLOCK, FRAME_TABLE_FULL = range(6)
+
+
 # every symbol include/lz4hip.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("lz4hip_codec_name", C.c_char_p, []),
@@ -117,6 +126,14 @@ SYMBOLS = [
     ("lz4hip_decoded_sizes_scratch_bytes", C.c_int64, [C.c_int64]),
     ("lz4hip_decoded_sizes_device", C.c_int, [C.POINTER(Batch), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     ("lz4hip_decoded_sizes_host", C.c_int, [C.POINTER(Batch), C.c_void_p, C.c_void_p, C.POINTER(SizesInfo)]),
+    ("lz4hip_frame_bound", C.c_int64, [C.c_int64, C.c_int32]),
+    ("lz4hip_frame_encode_scratch_bytes", C.c_int64, [C.c_int64, C.c_int32]),
+    ("lz4hip_frame_decode_scratch_bytes", C.c_int64, [C.c_int64]),
+    ("lz4hip_frame_encode_device", C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    ("lz4hip_frame_index_device", C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    ("lz4hip_frame_decode_device", C.c_int, [C.c_void_p, C.POINTER(FrameInfo), C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    ("lz4hip_frame_encode_host", C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
+    ("lz4hip_frame_decode_host", C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.POINTER(FrameInfo)]),
 ]
 
 _lib = None

@@ -1708,4 +1708,59 @@ int lz4hip_decoded_sizes_host(const lz4hip_batch_t* b, int64_t* dst_off, int32_t
     return hostbatch::decoded_sizes_host(be, b, dst_off, dst_cap, info, knob(kKnobSizesGroups), knob(kKnobHostThreads));
 }
 
+int64_t lz4hip_frame_bound(int64_t src_len, int32_t chunk_size) { return frame_bound(src_len, chunk_size); }
+
+int64_t lz4hip_frame_encode_scratch_bytes(int64_t src_len, int32_t chunk_size)
+{
+    if (!frame_chunk_valid(chunk_size)) return fail(LZ4HIP_E_ARGUMENT, "frame encode: chunk_size must be 0 (8 MiB) or 1 .. 0x7E000000");
+    return frame_encode_scratch(nullptr, src_len < 0 ? 0 : src_len, frame_chunk(chunk_size)).bytes;
+}
+
+int64_t lz4hip_frame_decode_scratch_bytes(int64_t max_chunks) { return frame_decode_scratch_bytes(max_chunks < 0 ? 0 : max_chunks); }
+
+// (the arguments are checked before the device is looked for: a bad call is LZ4HIP_E_ARGUMENT on any machine)
+int lz4hip_frame_encode_device(const void* src, int64_t src_len, int32_t chunk_size, int mode, void* dst, int64_t dst_cap, int64_t* dst_len,
+                               void* scratch, int64_t scratch_bytes, void* stream)
+{
+    HipBackend be = { (hipStream_t)stream };
+    FrameEncodePlan p;
+    if (int rc = frame_encode_plan(be, src, src_len, chunk_size, mode, dst, dst_cap, dst_len, scratch, scratch_bytes, p)) return rc;
+    if (int rc = ensure_device()) return rc;
+    return frame_encode_run(be, p);
+}
+
+int lz4hip_frame_index_device(const void* src, int64_t src_len, int32_t chunk_size, int64_t max_chunks, void* scratch, int64_t scratch_bytes,
+                              lz4hip_frame_info_t* info, void* stream)
+{
+    HipBackend be = { (hipStream_t)stream };
+    FrameIndexPlan p;
+    if (int rc = frame_index_plan(be, src, src_len, chunk_size, max_chunks, scratch, scratch_bytes, info, knob(kKnobSizesGroups), p)) return rc;
+    if (int rc = ensure_device()) return rc;
+    return frame_index_run(be, p);
+}
+
+int lz4hip_frame_decode_device(const void* src, const lz4hip_frame_info_t* info_host, int64_t max_chunks, void* scratch, int64_t scratch_bytes,
+                               void* dst, int64_t dst_cap, lz4hip_frame_info_t* info, void* stream)
+{
+    HipBackend be = { (hipStream_t)stream };
+    FrameDecodePlan p;
+    if (int rc = frame_decode_plan(be, src, info_host, max_chunks, scratch, scratch_bytes, dst, dst_cap, info, p)) return rc;
+    if (int rc = ensure_device()) return rc;
+    return frame_decode_run(be, p);
+}
+
+int lz4hip_frame_encode_host(const void* src, int64_t src_len, int32_t chunk_size, int mode, void* dst, int64_t dst_cap, int64_t* dst_len)
+{
+    HipBackend be = {};
+    if (int rc = stream_host_context(be)) return rc;
+    return frame_encode_host(be, src, src_len, chunk_size, mode, dst, dst_cap, dst_len);
+}
+
+int lz4hip_frame_decode_host(const void* src, int64_t src_len, int32_t chunk_size, void* dst, int64_t dst_cap, lz4hip_frame_info_t* info)
+{
+    HipBackend be = {};
+    if (int rc = stream_host_context(be)) return rc;
+    return frame_decode_host(be, src, src_len, chunk_size, dst, dst_cap, info);
+}
+
 }  // extern "C"

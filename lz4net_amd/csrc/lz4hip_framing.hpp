@@ -1,5 +1,5 @@
-// lz4hip_framing.hpp -- host side of the framing paths (LZ4Stream buffers, wrapped messages, batches of LZ4Stream buffers) and of the block
-// batch's size query (lz4hip_sizes.hpp): the scratch
+// lz4hip_framing.hpp -- host side of the framing paths (LZ4Stream buffers, wrapped messages, batches of LZ4Stream buffers, legacy
+// frames) and of the block batch's size query (lz4hip_sizes.hpp): the scratch
 // layouts, the grids and the kernel sequences around the block codec, written ONCE for the library (lz4hip_api.hip, HipBackend) and for
 // the CPU emulator (tests/simt/emu_framing.hpp, EmuBackend).  Host code only: no kernel is defined here and nothing here calls the HIP
 // runtime or the emulator; everything that touches the device goes through the backend B, which has exactly
@@ -25,6 +25,7 @@
 #include "lz4hip_wrap.hpp"
 #include "lz4hip_streams.hpp"
 #include "lz4hip_sizes.hpp"
+#include "lz4hip_frame.hpp"
 
 #include "../../include/lz4hip.h"
 
@@ -46,6 +47,11 @@ static_assert(kStreamsBadOffsets == LZ4HIP_E_ARGUMENT, "streams statuses");
 static_assert(sizeof(SizesInfo) == sizeof(lz4hip_sizes_info_t) && offsetof(SizesInfo, first_error) == offsetof(lz4hip_sizes_info_t, first_error) &&
               offsetof(SizesInfo, error) == offsetof(lz4hip_sizes_info_t, error), "SizesInfo must mirror lz4hip_sizes_info_t");
 static_assert(kSizesTooLarge == LZ4HIP_E_ARGUMENT, "sizes results");
+static_assert(sizeof(FrameInfo) == sizeof(lz4hip_frame_info_t) && offsetof(FrameInfo, good_bytes) == offsetof(lz4hip_frame_info_t, good_bytes) &&
+              offsetof(FrameInfo, error) == offsetof(lz4hip_frame_info_t, error), "FrameInfo must mirror lz4hip_frame_info_t");
+static_assert(kFrameOk == LZ4HIP_FRAME_OK && kFrameBadMagic == LZ4HIP_FRAME_BAD_MAGIC && kFrameTruncated == LZ4HIP_FRAME_TRUNCATED &&
+              kFrameBadSize == LZ4HIP_FRAME_BAD_SIZE && kFrameCorruptBlock == LZ4HIP_FRAME_CORRUPT_BLOCK &&
+              kFrameTableFull == LZ4HIP_FRAME_TABLE_FULL, "frame statuses");
 
 #define LZ4HIP_FRAMING_TRY(expr) do { if (int rc_ = (expr)) return rc_; } while (0)
 
@@ -610,6 +616,216 @@ int streams_decode(B& be, const void* src, int64_t src_len, const int64_t* src_o
     return streams_decode_run(be, a, t, from_index, (uint8_t*)dst, (StreamsInfo*)info);
 }
 
+// ---- legacy frames (lz4hip_frame.hpp) ----------------------------------------------------------------------------------------------------
+inline bool frame_chunk_valid(int32_t chunk_size) { return chunk_size >= 0 && chunk_size <= kFrameMaxChunk; }
+inline int32_t frame_chunk(int32_t chunk_size) { return chunk_size == 0 ? kFrameDefaultChunk : chunk_size; }   // (of a valid chunk_size)
+
+// 4 + sum over the chunks of (4 + compressBound(len_k)): all chunks but the last are full
+inline int64_t frame_bound(int64_t src_len, int32_t chunk_size)
+{
+    if (!frame_chunk_valid(chunk_size)) return LZ4HIP_E_ARGUMENT;
+    if (src_len < 0) src_len = 0;
+    const int64_t chunk = frame_chunk(chunk_size), full = src_len / chunk, rest = src_len % chunk;
+    return kFrameField + full * (kFrameField + frame_block_bound((int32_t)chunk)) + (rest ? kFrameField + frame_block_bound((int32_t)rest) : 0);
+}
+
+// the encoder's slot per chunk: compressBound of the longest chunk there is
+inline int64_t frame_stride(int64_t src_len, int64_t chunk) { return frame_block_bound((int32_t)(src_len < chunk ? src_len : chunk)); }
+
+// frame encode: the encoder's output (chunk k at k * stride), chunk lengths, capacities, results, the n + 1 sizes / offsets, tile sums
+struct FrameEncodeScratch { uint8_t* comp; int32_t* lens; int32_t* caps; int32_t* result; int64_t* offs; int64_t* partial; int64_t bytes; };
+inline FrameEncodeScratch frame_encode_scratch(void* scratch, int64_t src_len, int64_t chunk)
+{
+    const int64_t n = stream_chunks(src_len, chunk);
+    Carver c(scratch);
+    FrameEncodeScratch l;
+    l.comp = c.take_as<uint8_t>(n * frame_stride(src_len, chunk));
+    l.lens = c.take_as<int32_t>(4 * n);
+    l.caps = c.take_as<int32_t>(4 * n);
+    l.result = c.take_as<int32_t>(4 * n);
+    l.offs = c.take_as<int64_t>(8 * (n + 1));
+    l.partial = c.take_as<int64_t>(8 * scan_tiles(n + 1));
+    l.bytes = c.at;
+    return l;
+}
+
+// frame decode: [the lowest bad chunk, what the walk found], then the table of max_chunks rows and the scan's tile sums
+inline FrameTables frame_tables(Carver& c, int64_t max_chunks)
+{
+    FrameTables t;
+    t.max_chunks = max_chunks;
+    t.min_bad = c.take_as<unsigned long long>(256);
+    t.walk = (int64_t*)t.min_bad + 1;
+    t.src_off = c.take_as<int64_t>(8 * max_chunks);
+    t.hdr_off = c.take_as<int64_t>(8 * max_chunks);
+    t.dst_off = c.take_as<int64_t>(8 * (max_chunks + 1));
+    t.src_len = c.take_as<int32_t>(4 * max_chunks);
+    t.dst_cap = c.take_as<int32_t>(4 * max_chunks);
+    t.result = c.take_as<int32_t>(4 * max_chunks);
+    t.partial = c.take_as<int64_t>(8 * scan_tiles(max_chunks));
+    return t;
+}
+inline int64_t frame_decode_scratch_bytes(int64_t max_chunks) { Carver c; frame_tables(c, max_chunks); return c.at; }
+
+// what a front hands its sequence
+struct FrameEncodePlan { FrameEncodeArgs a; int mode; int32_t* lens; int32_t* caps; int64_t* partial; uint8_t* dst; int64_t dst_cap; int64_t* dst_len; int64_t bound; };
+struct FrameIndexPlan { const uint8_t* src; int64_t src_len; int32_t chunk; FrameTables t; FrameInfo* info; int groups; };
+struct FrameDecodePlan { const uint8_t* src; FrameInfo h; FrameTables t; uint8_t* dst; FrameInfo* info; };
+
+// p.a.comp and p.a.result are the block encoder's to write: chunk k at k * p.a.stride.  An empty source is the scan of the magic's size alone.
+template <class B>
+int frame_encode_run(B& be, const FrameEncodePlan& p)
+{
+    const FrameEncodeArgs& a = p.a;
+    if (a.n > 0) {
+        be.launch(frame_lens_kernel, stream_grid(a.n), kStreamThreads, p.lens, p.caps, a.n, a.src_len, a.chunk);
+        LZ4HIP_FRAMING_TRY(be.last_error());
+        // compress_file: every chunk into a compressBound buffer; src_len_all = the chunk size, the upper bound LZ4HC picks its kernels from
+        lz4hip_batch_t b = {};
+        b.src = a.src; b.src_stride = a.chunk; b.src_len = p.lens;
+        b.dst = (void*)a.comp; b.dst_stride = a.stride; b.dst_cap = p.caps;
+        b.src_len_all = a.chunk; b.result = (int32_t*)a.result; b.n_blocks = a.n;
+        LZ4HIP_FRAMING_TRY(be.encode(&b, p.mode));
+    }
+    be.launch(frame_sizes_kernel, stream_grid(a.n + 1), kStreamThreads, a);
+    launch_scan(be, a.offs, a.n + 1, p.partial, p.dst_len);
+    FrameLayout layout = { a };
+    be.launch(frame_pack_kernel, copy_grid(p.bound), kStreamThreads, layout, p.dst, p.dst_len, p.dst_cap);
+    return be.last_error();
+}
+
+template <class B>
+int frame_encode_plan(B& be, const void* src, int64_t src_len, int32_t chunk_size, int mode, void* dst, int64_t dst_cap, int64_t* dst_len,
+                      void* scratch, int64_t scratch_bytes, FrameEncodePlan& p)
+{
+    if (src_len < 0 || !dst_len) return be.fail(LZ4HIP_E_ARGUMENT, "frame encode: src_len < 0 or dst_len is NULL");
+    if (!frame_chunk_valid(chunk_size)) return be.fail(LZ4HIP_E_ARGUMENT, "frame encode: chunk_size must be 0 (8 MiB) or 1 .. 0x7E000000");
+    if (mode != LZ4HIP_MODE_FAST && mode != LZ4HIP_MODE_HC) return be.fail(LZ4HIP_E_ARGUMENT, "mode must be LZ4HIP_MODE_FAST or LZ4HIP_MODE_HC");
+    const int64_t chunk = frame_chunk(chunk_size), n = stream_chunks(src_len, chunk);
+    if (n >= 0x7FFFFFFF) return be.fail(LZ4HIP_E_ARGUMENT, "frame encode: more than 2^31 - 2 chunks");
+    p.bound = frame_bound(src_len, chunk_size);
+    if (dst_cap < p.bound) return be.fail(LZ4HIP_E_ARGUMENT, "frame encode: dst_cap < lz4hip_frame_bound");
+    const FrameEncodeScratch l = frame_encode_scratch(scratch, src_len, chunk);
+    if (scratch_bytes < l.bytes) return be.fail(LZ4HIP_E_ARGUMENT, "frame encode: scratch_bytes < lz4hip_frame_encode_scratch_bytes");
+    if ((n > 0 && !src) || !dst || !scratch) return be.fail(LZ4HIP_E_ARGUMENT, "frame encode: src, dst and scratch must be non-NULL");
+    FrameEncodeArgs& a = p.a;
+    a.src = (const uint8_t*)src; a.comp = l.comp; a.src_len = src_len; a.n = n; a.stride = frame_stride(src_len, chunk); a.chunk = (int32_t)chunk;
+    a.result = l.result; a.offs = l.offs;
+    p.mode = mode; p.lens = l.lens; p.caps = l.caps; p.partial = l.partial; p.dst = (uint8_t*)dst; p.dst_cap = dst_cap; p.dst_len = dst_len;
+    return 0;
+}
+
+template <class B>
+int frame_encode(B& be, const void* src, int64_t src_len, int32_t chunk_size, int mode, void* dst, int64_t dst_cap, int64_t* dst_len,
+                 void* scratch, int64_t scratch_bytes)
+{
+    FrameEncodePlan p;
+    LZ4HIP_FRAMING_TRY(frame_encode_plan(be, src, src_len, chunk_size, mode, dst, dst_cap, dst_len, scratch, scratch_bytes, p));
+    return frame_encode_run(be, p);
+}
+
+// The rows past the walk's count must read as empty blocks: the two columns the size walk looks at are zeroed first.  It then runs over
+// ALL max_chunks rows (an empty row costs nothing and gives 0), so nothing is read on the host between the steps.
+template <class B>
+int frame_index_run(B& be, const FrameIndexPlan& p)
+{
+    const FrameTables& t = p.t;
+    LZ4HIP_FRAMING_TRY(be.fill(t.min_bad, 0xFF, 8));                   // min_bad = none
+    if (t.max_chunks > 0) {
+        LZ4HIP_FRAMING_TRY(be.fill(t.src_off, 0, (size_t)(8 * t.max_chunks)));
+        LZ4HIP_FRAMING_TRY(be.fill(t.src_len, 0, (size_t)(4 * t.max_chunks)));
+    }
+    be.launch(frame_walk_kernel, fixed_grid(1), 64, p.src, p.src_len, (int64_t)frame_block_bound(p.chunk), t);
+    LZ4HIP_FRAMING_TRY(be.last_error());
+    if (t.max_chunks > 0) {
+        SizesArgs a;
+        a.src = p.src; a.src_off = t.src_off; a.src_stride = 0; a.src_len = t.src_len; a.src_len_all = 0; a.n = t.max_chunks;
+        a.result = t.result; a.dst_cap = t.dst_cap; a.offs = t.dst_off; a.min_bad = t.min_bad;
+        be.launch(sizes_walk_kernel, sizes_grid(a.n, p.groups), kSizesThreads, a);
+        be.launch(frame_caps_kernel, stream_grid(t.max_chunks), kStreamThreads, t, p.chunk);
+        launch_scan(be, t.dst_off, t.max_chunks, t.partial, t.dst_off + t.max_chunks);
+    } else {
+        LZ4HIP_FRAMING_TRY(be.fill(t.dst_off, 0, sizeof(int64_t)));
+    }
+    be.launch(frame_info_kernel, fixed_grid(1), 64, t, p.info);
+    return be.last_error();
+}
+
+template <class B>
+int frame_index_plan(B& be, const void* src, int64_t src_len, int32_t chunk_size, int64_t max_chunks, void* scratch, int64_t scratch_bytes,
+                     lz4hip_frame_info_t* info, int groups, FrameIndexPlan& p)
+{
+    if (src_len < 0 || max_chunks < 0 || !info || !scratch || (src_len > 0 && !src))
+        return be.fail(LZ4HIP_E_ARGUMENT, "frame index: negative size or NULL pointer");
+    if (!frame_chunk_valid(chunk_size)) return be.fail(LZ4HIP_E_ARGUMENT, "frame index: chunk_size must be 0 (8 MiB) or 1 .. 0x7E000000");
+    if (max_chunks > 0x7FFFFFFF) return be.fail(LZ4HIP_E_ARGUMENT, "frame index: more than 2^31 - 1 table rows");
+    Carver c(scratch);
+    p.t = frame_tables(c, max_chunks);
+    if (scratch_bytes < c.at) return be.fail(LZ4HIP_E_ARGUMENT, "frame index: scratch_bytes < lz4hip_frame_decode_scratch_bytes");
+    p.src = (const uint8_t*)src; p.src_len = src_len; p.chunk = frame_chunk(chunk_size); p.info = (FrameInfo*)info; p.groups = groups;
+    return 0;
+}
+
+template <class B>
+int frame_index(B& be, const void* src, int64_t src_len, int32_t chunk_size, int64_t max_chunks, void* scratch, int64_t scratch_bytes,
+                lz4hip_frame_info_t* info, int groups = 0)
+{
+    FrameIndexPlan p;
+    LZ4HIP_FRAMING_TRY(frame_index_plan(be, src, src_len, chunk_size, max_chunks, scratch, scratch_bytes, info, groups, p));
+    return frame_index_run(be, p);
+}
+
+// p.h: what the index reported, read back by the host; the table is as the index left it.  A frame that decodes to nothing has only
+// capacities of 0 -- no chunk can write -- and keeps the walk's results for the check.
+template <class B>
+int frame_decode_run(B& be, const FrameDecodePlan& p)
+{
+    const FrameTables& t = p.t;
+    if (p.h.chunks > 0) {
+        if (p.h.decoded_bytes > 0) {
+            // decode_file: LZ4_uncompress_unknownOutputSize per chunk -- the table IS the batch, its capacities the sizes the walk found
+            lz4hip_batch_t b = {};
+            b.src = p.src; b.src_off = t.src_off; b.src_len = t.src_len;
+            b.dst = p.dst; b.dst_off = t.dst_off; b.dst_cap = t.dst_cap;
+            b.result = t.result; b.n_blocks = p.h.chunks;
+            LZ4HIP_FRAMING_TRY(be.decode(&b, 0));
+        }
+        be.launch(frame_check_kernel, stream_grid(p.h.chunks), kStreamThreads, t, p.h.chunks);
+        LZ4HIP_FRAMING_TRY(be.last_error());
+    }
+    be.launch(frame_info_kernel, fixed_grid(1), 64, t, p.info);
+    return be.last_error();
+}
+
+template <class B>
+int frame_decode_plan(B& be, const void* src, const lz4hip_frame_info_t* info_host, int64_t max_chunks, void* scratch, int64_t scratch_bytes,
+                      void* dst, int64_t dst_cap, lz4hip_frame_info_t* info, FrameDecodePlan& p)
+{
+    if (!info_host || !info || !scratch || max_chunks < 0) return be.fail(LZ4HIP_E_ARGUMENT, "frame decode: NULL pointer or max_chunks < 0");
+    const lz4hip_frame_info_t h = *info_host;
+    if (h.error < LZ4HIP_FRAME_OK || h.error >= LZ4HIP_FRAME_TABLE_FULL)
+        return be.fail(LZ4HIP_E_ARGUMENT, "frame decode: the index reported a table too small (or the info is not an index's)");
+    if (h.chunks < 0 || h.chunks > max_chunks || h.chunks > 0x7FFFFFFF || h.decoded_bytes < 0)
+        return be.fail(LZ4HIP_E_ARGUMENT, "frame decode: the info does not fit a table of max_chunks entries");
+    if (h.decoded_bytes > dst_cap) return be.fail(LZ4HIP_E_ARGUMENT, "frame decode: decoded_bytes > dst_cap");
+    if ((h.chunks > 0 && !src) || (h.decoded_bytes > 0 && !dst)) return be.fail(LZ4HIP_E_ARGUMENT, "frame decode: src and dst must be non-NULL");
+    Carver c(scratch);
+    p.t = frame_tables(c, max_chunks);
+    if (scratch_bytes < c.at) return be.fail(LZ4HIP_E_ARGUMENT, "frame decode: scratch_bytes < lz4hip_frame_decode_scratch_bytes");
+    p.src = (const uint8_t*)src; p.dst = (uint8_t*)dst; p.info = (FrameInfo*)info;
+    memcpy(&p.h, &h, sizeof p.h);
+    return 0;
+}
+
+template <class B>
+int frame_decode(B& be, const void* src, const lz4hip_frame_info_t* info_host, int64_t max_chunks, void* scratch, int64_t scratch_bytes,
+                 void* dst, int64_t dst_cap, lz4hip_frame_info_t* info)
+{
+    FrameDecodePlan p;
+    LZ4HIP_FRAMING_TRY(frame_decode_plan(be, src, info_host, max_chunks, scratch, scratch_bytes, dst, dst_cap, info, p));
+    return frame_decode_run(be, p);
+}
+
 // ---- the decoded sizes of a block batch (lz4hip_sizes.hpp) ----------------------------------------------------------------------------
 // scratch: the lowest failing index, then stand-ins for the outputs the caller left out (results, sizes / offsets), the scan's tile sums
 struct SizesScratch { unsigned long long* min_bad; int32_t* result; int64_t* offs; int64_t* partial; int64_t bytes; };
@@ -709,18 +925,18 @@ struct Image {
     }
 };
 
-// The two LZ4Stream decoders index until their guesses hold.  `index` lays the image out for the current max_chunks and out_bytes,
+// The LZ4Stream decoders and the legacy frame's (whose code for a full table is its own: `table_full`) index until their guesses hold.  `index` lays the image out for the current max_chunks and out_bytes,
 // stages the source, runs the index and queues the download of its info into h.  A full table is indexed again with the count it
 // reported, an output that has to grow with the size it reported: three passes at most, whatever they went on.  A size above dst_cap
 // ends the loop at once; the caller refuses it, as it does a table still full after the third pass.
 template <class B, class Info, class Index>
-int settle(B& be, int64_t dst_cap, int64_t& max_chunks, int64_t& out_bytes, const Info& h, Index index)
+int settle(B& be, int64_t dst_cap, int64_t& max_chunks, int64_t& out_bytes, const Info& h, Index index, int table_full = LZ4HIP_STREAM_TABLE_FULL)
 {
     for (int attempt = 0;; attempt++) {
         LZ4HIP_FRAMING_TRY(index());
         LZ4HIP_FRAMING_TRY(be.sync());
         if (attempt >= 2) return 0;
-        if (h.error == LZ4HIP_STREAM_TABLE_FULL) max_chunks = h.chunks;
+        if (h.error == table_full) max_chunks = h.chunks;
         else if (h.decoded_bytes > dst_cap || h.decoded_bytes <= out_bytes) return 0;
         else out_bytes = h.decoded_bytes;
     }
@@ -913,6 +1129,67 @@ int streams_decode_host(B& be, const void* src, int64_t src_len, const int64_t* 
                                       out_bytes, im.i64(doff_at), im.i32(st_at), im.i64(eo_at),
                                       (lz4hip_streams_info_t*)(im.d + info_at)));
     LZ4HIP_FRAMING_TRY(im.download_decoded(info, info_at, dst, out_at, h.decoded_bytes, &items));
+    return info->error;
+}
+
+template <class B>
+int frame_encode_host(B& be, const void* src, int64_t src_len, int32_t chunk_size, int mode, void* dst, int64_t dst_cap, int64_t* dst_len)
+{
+    if (src_len < 0 || !dst_len || !dst || (src_len > 0 && !src)) return be.fail(LZ4HIP_E_ARGUMENT, "frame encode: negative size or NULL pointer");
+    if (!frame_chunk_valid(chunk_size)) return be.fail(LZ4HIP_E_ARGUMENT, "frame encode: chunk_size must be 0 (8 MiB) or 1 .. 0x7E000000");
+    const int64_t bound = frame_bound(src_len, chunk_size);
+    if (dst_cap < bound) return be.fail(LZ4HIP_E_ARGUMENT, "frame encode: dst_cap < lz4hip_frame_bound");
+    // device image: [source | frame | scratch | length]
+    const int64_t scratch_bytes = frame_encode_scratch(nullptr, src_len, frame_chunk(chunk_size)).bytes;
+    Carver c;
+    c.take(src_len);
+    const int64_t out_at = c.take(bound), scratch_at = c.take(scratch_bytes), len_at = c.take(256);
+    Image<B> im = { be };
+    LZ4HIP_FRAMING_TRY(im.reserve(c.at));
+    LZ4HIP_FRAMING_TRY(im.upload_source(src, src_len));
+    LZ4HIP_FRAMING_TRY(frame_encode(be, im.d, src_len, chunk_size, mode, im.d + out_at, bound, im.i64(len_at), im.d + scratch_at, scratch_bytes));
+    int64_t total = 0;
+    LZ4HIP_FRAMING_TRY(im.download(&total, len_at, sizeof total));
+    LZ4HIP_FRAMING_TRY(be.sync());
+    LZ4HIP_FRAMING_TRY(im.download_encoded(dst, out_at, total));
+    *dst_len = total;
+    return 0;
+}
+
+// The index knows the decoded size, so the output's piece of the image is never too small for long: min(dst_cap, 4 * src_len) at first
+// -- all of it when the caller sized dst from a size query -- and exactly decoded_bytes on the pass after one that reported more.
+// That later pass follows stream_decode_host: the image may have moved, so the source is staged and the WHOLE index runs again (the
+// size field walk, the size walk, the scan) although the size is already known -- for a frame that shrank to less than a quarter, twice the
+// latency-bound walk.  Keeping the table across the move would save it.
+// On dst_cap < decoded_bytes only *info is filled.
+template <class B>
+int frame_decode_host(B& be, const void* src, int64_t src_len, int32_t chunk_size, void* dst, int64_t dst_cap, lz4hip_frame_info_t* info)
+{
+    if (src_len < 0 || dst_cap < 0 || !info || (src_len > 0 && !src)) return be.fail(LZ4HIP_E_ARGUMENT, "frame decode: negative size or NULL pointer");
+    if (!frame_chunk_valid(chunk_size)) return be.fail(LZ4HIP_E_ARGUMENT, "frame decode: chunk_size must be 0 (8 MiB) or 1 .. 0x7E000000");
+    // device image: [source | info | output | table]
+    Image<B> im = { be };
+    int64_t max_chunks = src_len / frame_chunk(chunk_size) + 16, out_bytes = guessed_output(src_len, dst_cap), info_at = 0, out_at = 0, table_at = 0,
+            table_bytes = 0;
+    lz4hip_frame_info_t h = {};
+    LZ4HIP_FRAMING_TRY(settle(be, dst_cap, max_chunks, out_bytes, h, [&] {
+        table_bytes = frame_decode_scratch_bytes(max_chunks);
+        Carver c;
+        c.take(src_len);
+        info_at = c.take(256); out_at = c.take(out_bytes); table_at = c.take(table_bytes);
+        LZ4HIP_FRAMING_TRY(im.reserve(c.at));
+        LZ4HIP_FRAMING_TRY(im.upload_source(src, src_len));
+        LZ4HIP_FRAMING_TRY(frame_index(be, im.d, src_len, chunk_size, max_chunks, im.d + table_at, table_bytes, (lz4hip_frame_info_t*)(im.d + info_at)));
+        return im.download(&h, info_at, sizeof h);
+    }, LZ4HIP_FRAME_TABLE_FULL));
+    *info = h;
+    if (h.error == LZ4HIP_FRAME_TABLE_FULL) return be.fail(LZ4HIP_E_DEVICE, "frame decode: the size field walk did not settle");
+    if (h.decoded_bytes > dst_cap || h.decoded_bytes > out_bytes)
+        return be.fail(LZ4HIP_E_ARGUMENT, "frame decode: dst_cap < decoded_bytes (reported in info->decoded_bytes)");
+    if (h.decoded_bytes > 0 && !dst) return be.fail(LZ4HIP_E_ARGUMENT, "frame decode: dst is NULL");
+    LZ4HIP_FRAMING_TRY(frame_decode(be, im.d, &h, max_chunks, im.d + table_at, table_bytes, im.d + out_at, out_bytes,
+                                    (lz4hip_frame_info_t*)(im.d + info_at)));
+    LZ4HIP_FRAMING_TRY(im.download_decoded(info, info_at, dst, out_at, h.decoded_bytes));
     return info->error;
 }
 

@@ -94,3 +94,123 @@ def decompress_frame(frame, chunk_size: int = CHUNK_SIZE) -> bytes:
     if (res < 0).any():
         raise ArgumentException("Decoding Failed ! Corrupted input !")
     return b"".join(out[int(dst_off[i]):int(dst_off[i]) + int(res[i])].tobytes() for i in range(n))
+
+
+# ---- whole frames on the device (lz4hip_frame_* of include/lz4hip.h; kernels in csrc/lz4hip_frame.hpp) ---------------------------------
+
+def _frame_error(status: int, error_offset: int = -1, frame_len: int = -1):
+    """The exception parse_frame / decompress_frame raise for an LZ4HIP_FRAME_* outcome, with the failing size field's offset in
+    .error_offset; frame_len tells a size field cut short from a payload cut short."""
+    status, error_offset = int(status), int(error_offset)
+    if status == _lib.FRAME_BAD_MAGIC:
+        e = ArgumentException("Unrecognized header : file cannot be decoded")
+    elif status == _lib.FRAME_TRUNCATED:
+        e = ArgumentException("truncated chunk header" if error_offset + 4 > frame_len else "truncated chunk payload")
+    elif status == _lib.FRAME_BAD_SIZE:
+        e = ArgumentException("chunk size exceeds what a chunk can compress to")
+    elif status == _lib.FRAME_CORRUPT_BLOCK:
+        e = ArgumentException("Decoding Failed ! Corrupted input !")
+    else:
+        e = _lib.Lz4HipError(f"frame decode: unexpected outcome {status}")
+    e.error_offset = int(error_offset)
+    return e
+
+
+def _check_chunk_size(chunk_size) -> int:
+    chunk_size = int(chunk_size)
+    if not 1 <= chunk_size <= 0x7E000000:
+        raise ArgumentException("chunk_size must be 1 .. 0x7E000000")
+    return chunk_size
+
+
+def compress_frame_device(t, high_compression: bool = False, chunk_size: int = CHUNK_SIZE):
+    """compress_frame for a 1-D uint8 CUDA tensor, entirely on the device, on torch's current stream: the same bytes, returned as a 1-D
+    uint8 CUDA tensor.  Waits for the device once, to learn the frame's length."""
+    import torch
+    from .stream import _check_device_bytes
+    t = _check_device_bytes(t, "t")
+    chunk_size = _check_chunk_size(chunk_size)
+    with torch.cuda.device(t.device):
+        L = _lib.lib()
+        n = t.numel()
+        out = torch.empty(L.lz4hip_frame_bound(n, chunk_size), dtype=torch.uint8, device=t.device)
+        scratch = torch.empty(L.lz4hip_frame_encode_scratch_bytes(n, chunk_size), dtype=torch.uint8, device=t.device)
+        out_len = torch.empty(1, dtype=torch.int64, device=t.device)
+        _lib.check(L.lz4hip_frame_encode_device(t.data_ptr(), n, chunk_size, _lib.MODE_HC if high_compression else _lib.MODE_FAST,
+                                                out.data_ptr(), out.numel(), out_len.data_ptr(), scratch.data_ptr(), scratch.numel(),
+                                                torch.cuda.current_stream(t.device).cuda_stream))
+        return out[:int(out_len.item())]
+
+
+def decompress_frame_device(t, chunk_size: int = CHUNK_SIZE):
+    """decompress_frame for a 1-D uint8 CUDA tensor, on torch's current stream: the size field walk, the size of every chunk and the block
+    decode run on the device, into a buffer of exactly the decoded size; the host reads the index's result once (to size the output)
+    and the final outcome once."""
+    import torch
+    from .stream import _check_device_bytes
+    t = _check_device_bytes(t, "t")
+    chunk_size = _check_chunk_size(chunk_size)
+    with torch.cuda.device(t.device):
+        L = _lib.lib()
+        dev = t.device
+        s = torch.cuda.current_stream(dev).cuda_stream
+        n = t.numel()
+        info_dev = torch.zeros(C.sizeof(_lib.FrameInfo), dtype=torch.uint8, device=dev)
+
+        def read_info():
+            return _lib.FrameInfo.from_buffer_copy(info_dev.cpu().numpy().tobytes())
+
+        max_chunks = n // chunk_size + 16
+        for _ in range(2):
+            scratch = torch.empty(L.lz4hip_frame_decode_scratch_bytes(max_chunks), dtype=torch.uint8, device=dev)
+            _lib.check(L.lz4hip_frame_index_device(t.data_ptr(), n, chunk_size, max_chunks, scratch.data_ptr(), scratch.numel(),
+                                                   info_dev.data_ptr(), s))
+            info = read_info()
+            if info.error != _lib.FRAME_TABLE_FULL:
+                break
+            max_chunks = int(info.chunks)
+        if info.error == _lib.FRAME_TABLE_FULL:
+            raise _lib.Lz4HipError("frame decode: the size field walk did not settle")
+        out = torch.empty(int(info.decoded_bytes), dtype=torch.uint8, device=dev)
+        _lib.check(L.lz4hip_frame_decode_device(t.data_ptr(), C.byref(info), max_chunks, scratch.data_ptr(), scratch.numel(),
+                                                out.data_ptr(), out.numel(), info_dev.data_ptr(), s))
+        info = read_info()
+        if info.error != _lib.FRAME_OK:
+            raise _frame_error(info.error, info.error_offset, n)
+        return out
+
+
+def _host_bytes(data):
+    if isinstance(data, np.ndarray):
+        return np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
+    return np.frombuffer(bytes(data), dtype=np.uint8)
+
+
+def compress_frame_host(data, high_compression: bool = False, chunk_size: int = CHUNK_SIZE) -> bytes:
+    """compress_frame through lz4hip_frame_encode_host: one staged call, the frame packed on the device."""
+    raw = _host_bytes(data)
+    chunk_size = _check_chunk_size(chunk_size)
+    L = _lib.lib()
+    bound = L.lz4hip_frame_bound(raw.size, chunk_size)
+    out = np.empty(bound, np.uint8)
+    out_len = C.c_int64(0)
+    _lib.check(L.lz4hip_frame_encode_host(raw.ctypes.data, raw.size, chunk_size, _lib.MODE_HC if high_compression else _lib.MODE_FAST,
+                                          out.ctypes.data, bound, C.byref(out_len)))
+    return out[:out_len.value].tobytes()
+
+
+def decompress_frame_host(frame, chunk_size: int = CHUNK_SIZE) -> bytes:
+    """decompress_frame through lz4hip_frame_decode_host: a size query (dst_cap = 0), then the call that decodes into exactly that size."""
+    buf = _host_bytes(frame)
+    chunk_size = _check_chunk_size(chunk_size)
+    L = _lib.lib()
+    info = _lib.FrameInfo()
+    rc = L.lz4hip_frame_decode_host(buf.ctypes.data, buf.size, chunk_size, None, 0, C.byref(info))
+    out = np.empty(max(int(info.decoded_bytes), 1), np.uint8)
+    if rc == _lib.E_ARGUMENT and info.decoded_bytes > 0:
+        rc = L.lz4hip_frame_decode_host(buf.ctypes.data, buf.size, chunk_size, out.ctypes.data, int(info.decoded_bytes), C.byref(info))
+    if rc != info.error:                                              # (the outcome itself is info.error)
+        _lib.check(rc)
+    if info.error != _lib.FRAME_OK:
+        raise _frame_error(info.error, info.error_offset, buf.size)
+    return out[:int(info.decoded_bytes)].tobytes()
