@@ -56,6 +56,28 @@ namespace LZ4hip
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
         private static extern unsafe int lz4hip_decoded_sizes_host(Batch* b, long* dstOff, int* dstCap, SizesInfo* info);
 
+        // A batch encoded into ONE buffer of exactly the bytes produced (include/lz4hip.h, "a block batch encoded into one packed buffer"):
+        // b's dst fields are ignored, b.dst_cap_all is the slot width (MaximumOutputLength of the longest block); dstOff[n + 1] and
+        // packedLen[n] come back in the layout lz4hip_decoded_sizes_host and an offsets-form decode batch read.  dstCap may be anything
+        // >= 0: info.written_blocks leading blocks fit, info.packed_bytes is what all of them need (dstCap = 0: a size query).
+        // roundBlocks = 0: one round; K > 0: rounds of K blocks through a ring of K slots of device scratch.
+        // (Declarations only: not compiled or run by this repository's tests, tests/test_gpu_encode_packed.py calls the same symbol
+        // through ctypes.)
+        // struct lz4hip_packed_info, field for field
+        [StructLayout(LayoutKind.Sequential)]
+        public struct PackedInfo
+        {
+            public long blocks, packed_bytes, written_blocks, first_failed;
+            public int error, reserved;
+        }
+
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        private static extern long lz4hip_encode_packed_scratch_bytes(long nBlocks, int slotBytes, long roundBlocks);
+
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        private static extern unsafe int lz4hip_encode_packed_host(Batch* b, int mode, long roundBlocks, byte* dst, long dstCap, long* dstOff,
+                                                                   int* packedLen, PackedInfo* info);
+
         // Many LZ4Stream buffers per call (include/lz4hip.h, "batches of LZ4Stream buffers"): one buffer plus offsets[n + 1] in, the
         // same layout out; every item becomes / is read as the stream LZ4Stream writes for it, the chunks of all items in one batch.
         // struct lz4hip_streams_info, field for field

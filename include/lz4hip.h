@@ -351,6 +351,60 @@ int lz4hip_decoded_sizes_device(const lz4hip_batch_t* b, int64_t* dst_off, int32
  * (block failures are in result and info) or LZ4HIP_E_*. */
 int lz4hip_decoded_sizes_host(const lz4hip_batch_t* b, int64_t* dst_off, int32_t* dst_cap, lz4hip_sizes_info_t* info);
 
+/* ---- a block batch encoded into one packed buffer ---------------------------------------------------
+ * The pack step the framed encoders end in, for the plain block batch: n blocks are compressed as lz4hip_encode_batch_device compresses
+ * them, but land back to back in ONE buffer -- block i at dst[dst_off[i], dst_off[i + 1]), no padding -- instead of one compressBound
+ * slot each.  The offsets and lengths written are exactly the src_off / src_len of the size query above and of an offsets-form decode
+ * batch: one call's output is the other's input.
+ *
+ * The source side of *b is read as the batch encoder reads it: src, src_off / src_stride, src_len / src_len_all (with its hint
+ * meaning) and n_blocks.  b->dst, dst_off and dst_stride are ignored and may be NULL or 0.  b->dst_cap_all must be > 0: it is the slot
+ * width, slot_bytes below, and the per-block output limit where b->dst_cap is NULL; with b->dst_cap given, block i's limit is
+ * min(dst_cap[i], dst_cap_all) -- LZ4_compress_limitedOutput semantics per block.  b->result[n], if not NULL, receives the raw
+ * per-block encoder results.
+ *
+ * The call writes dst_off[n + 1] (required): the exclusive scan of max(result[i], 0), dst_off[n] the total; packed_len[n] (optional):
+ * max(result[i], 0); the bytes; and *info.  A block that failed its limit (result 0) or its arguments (LZ4HIP_E_ARGUMENT: a negative
+ * length -- the call itself gives that result: such a length never reaches the block encoders, which do not check it) takes 0 bytes
+ * and its neighbours pack around it.
+ *
+ * dst_cap may be any value >= 0: it need not reach a bound.  The offsets are monotone, so block i is written iff
+ * dst_off[i + 1] <= dst_cap; info.written_blocks is the length of that prefix, the bytes of dst from dst_off[written_blocks] up to
+ * dst_cap are unspecified, and no byte at or past dst_cap is ever written.  dst_off, packed_len, result and info.packed_bytes are
+ * complete in either case: the encoders are deterministic, so a second call with dst_cap = packed_bytes fits, and dst_cap = 0 is a
+ * size query (dst may then be NULL).
+ *
+ * Rounds: round_blocks = 0 runs the batch as one round; round_blocks = K > 0 runs ceil(n / K) rounds of at most K blocks through ONE
+ * ring of min(K, n) slots, so the scratch -- the ring, a round's tables and a few hundred bytes -- does not grow with n once n > K.
+ * Each round is a normal batch encode of its rows: the wavefront / lane dispatch rules and the first-use exceptions of the batch
+ * encoder above (the lane encoder's table slab from 49152 blocks, the LZ4HC tables) apply to the ROUND's size, not to n. */
+typedef struct lz4hip_packed_info {
+    int64_t blocks;          /* n */
+    int64_t packed_bytes;    /* dst_off[n]: the bytes the whole batch needs, whatever dst_cap was */
+    int64_t written_blocks;  /* leading blocks that lie wholly inside dst_cap (n when all do) */
+    int64_t first_failed;    /* lowest index whose encoder result is <= 0, -1 if none */
+    int32_t error, reserved; /* that block's result (0 = did not fit its per-block limit, or LZ4HIP_E_ARGUMENT), 0 if none */
+} lz4hip_packed_info_t;
+
+/* Device scratch (bytes) of the device call; 0 for an empty batch, non-decreasing in n_blocks and the same for every
+ * n_blocks >= round_blocks > 0.  LZ4HIP_E_ARGUMENT for slot_bytes <= 0 or round_blocks < 0. */
+int64_t lz4hip_encode_packed_scratch_bytes(int64_t n_blocks, int32_t slot_bytes, int64_t round_blocks);
+/* Device-resident batch: the contract of the other device calls -- device pointers of the CURRENT device, launch-only on `stream`, no
+ * device value read on the host, no allocation beyond what the block encoder itself does on first use, scratch from the caller, 0 or
+ * LZ4HIP_E_* returned.  Arguments are checked first: a NULL batch or dst_off, a negative n_blocks, dst_cap or round_blocks,
+ * dst_cap_all <= 0, a bad mode, too little scratch or more than 2^31 - 1 blocks in a round is LZ4HIP_E_ARGUMENT whatever the device.
+ * An empty batch writes dst_off[0] = 0 and an info with first_failed = -1.  info may be NULL. */
+int lz4hip_encode_packed_device(const lz4hip_batch_t* b, int mode, int64_t round_blocks,
+                                void* dst, int64_t dst_cap, int64_t* dst_off, int32_t* packed_len,
+                                void* scratch, int64_t scratch_bytes, lz4hip_packed_info_t* info, void* stream);
+/* Host-resident batch: every pointer is host memory.  Gathers the rows, stages them with their lengths and limits through device
+ * memory (per-thread, grow-only, freed by lz4hip_release_workspaces), runs the device call, reads info and the per-block arrays back
+ * and copies only min(packed_bytes, dst_cap) bytes of output.  The arguments are checked as the device call checks them; info may
+ * be NULL.  Returns 0 (block failures are in result and info) or LZ4HIP_E_*. */
+int lz4hip_encode_packed_host(const lz4hip_batch_t* b, int mode, int64_t round_blocks,
+                              void* dst, int64_t dst_cap, int64_t* dst_off, int32_t* packed_len,
+                              lz4hip_packed_info_t* info);
+
 /* ---- legacy frames ---------------------------------------------------------------------------------
  * The frame of the demo command-line tool that ships with the reference (original/lz4demo.c:84-87, 167-317), the one format here that
  * files from outside the lz4net world arrive in:

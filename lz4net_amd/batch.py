@@ -167,6 +167,83 @@ def decode_packed(src: torch.Tensor, src_len, src_off: torch.Tensor | None = Non
     return dst, offsets, results
 
 
+# ---- encoding a batch into one packed buffer --------------------------------------------------------
+def read_packed_info(info: torch.Tensor) -> _lib.PackedInfo:
+    """The lz4hip_packed_info_t an encode_packed call left on the device (synchronises)."""
+    return _lib.PackedInfo.from_buffer_copy(info.cpu().numpy().tobytes())
+
+
+def compress_bound(n: int) -> int:
+    return n + n // 255 + 16
+
+
+def encode_packed_launch(src, src_len, src_off, hc, round_blocks, dst, slot_bytes, dst_cap=None, block_cap=None):
+    """One lz4hip_encode_packed_device call on torch's current stream, not waited for -> (offsets, lengths, results, info), all on the
+    device: int64 n + 1, int32 n, int32 n and the lz4hip_packed_info_t record as five int64 (read_packed_info).  dst_cap defaults to
+    dst.numel(); block_cap (int32, n) gives per-block output limits."""
+    n, b, keep = _source(src, src_len, src_off)
+    dev = src.device
+    offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    lengths = torch.empty(n, dtype=torch.int32, device=dev)
+    results = torch.empty(n, dtype=torch.int32, device=dev)
+    info = torch.empty(5, dtype=torch.int64, device=dev)
+    if block_cap is not None:
+        assert block_cap.dtype == torch.int32 and block_cap.numel() == n and block_cap.is_cuda and block_cap.is_contiguous()
+        b.dst_cap = block_cap.data_ptr()
+    b.dst_cap_all, b.result = slot_bytes, results.data_ptr()
+    if src.dim() == 2 and not isinstance(src_len, int):
+        b.src_len_all = src.shape[1]                # the hint: no block is longer than its row
+    need = _lib.check(_lib.lib().lz4hip_encode_packed_scratch_bytes(n, slot_bytes, round_blocks))
+    scratch = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+    cap = (0 if dst is None else dst.numel()) if dst_cap is None else dst_cap
+    _lib.check(_lib.lib().lz4hip_encode_packed_device(C.byref(b), _lib.MODE_HC if hc else _lib.MODE_FAST, round_blocks, _ptr(dst), cap,
+                                                      offsets.data_ptr(), lengths.data_ptr(), scratch.data_ptr(), need, info.data_ptr(), _stream()))
+    return offsets, lengths, results, info
+
+
+def encode_packed(src: torch.Tensor, src_len, src_off: torch.Tensor | None = None, hc: bool = False, round_blocks: int = 0,
+                  dst: torch.Tensor | None = None, slot_bytes: int | None = None):
+    """Compress a batch of blocks into ONE buffer of exactly the bytes they produce (lz4hip_encode_packed_device): block i is row i of
+    a 2-D `src`, or src[src_off[i]:] of a 1-D one.  Returns (dst_view, offsets, lengths, results, info): block i's compressed bytes are
+    dst_view[offsets[i]:offsets[i + 1]], lengths[i] = max(results[i], 0) their count, results the raw encoder results and info the
+    lz4hip_packed_info_t read back (ONE synchronisation).  decode_packed(dst_view, lengths, offsets[:-1]) is the way back.
+
+    round_blocks = K > 0 runs the batch in rounds of K blocks through a ring of K slots (device scratch that does not grow with the
+    batch).  slot_bytes, the slot width and per-block limit, defaults to compressBound of the longest block there can be: an int
+    src_len itself, the row width of a 2-D src; a 1-D src with a tensor of lengths must bring it.
+
+    dst=None: the first attempt allocates the size a compressor's caller expects to beat, as far as it is known without waiting for
+    the device: n * src_len for an int src_len; with a tensor of lengths the bytes `src` spans (n * row width, or src.numel() for a
+    1-D src) -- an upper bound of sum(src_len), and far more than that where most blocks are much shorter than their rows; bring
+    `dst` then.  Only
+    when not every block fits (info.written_blocks < n) is there a second call, into exactly info.packed_bytes bytes: that pass
+    ENCODES AGAIN, it does not reuse the first one's work.  With `dst` (1-D uint8) given there is never a second call: dst_view is
+    dst[:min(packed_bytes, dst.numel())], the blocks before info.written_blocks are in it, and offsets, lengths, results and
+    info.packed_bytes are complete."""
+    assert src.dtype == torch.uint8 and src.is_cuda
+    n = src.shape[0] if src_off is None else src_off.numel()
+    if slot_bytes is None:
+        if isinstance(src_len, int):
+            slot_bytes = compress_bound(src_len)
+        else:
+            assert src.dim() == 2, "a 1-D src with per-block lengths needs slot_bytes"
+            slot_bytes = compress_bound(src.shape[1])
+    slot_bytes = max(int(slot_bytes), 1)
+    given = dst is not None
+    if given:
+        assert dst.dtype == torch.uint8 and dst.is_cuda and dst.dim() == 1 and dst.is_contiguous()
+    else:
+        guess = n * src_len if isinstance(src_len, int) else (n * src.shape[1] if src.dim() == 2 else src.numel())
+        dst = torch.empty(max(guess, 0), dtype=torch.uint8, device=src.device)
+    offsets, lengths, results, info = encode_packed_launch(src, src_len, src_off, hc, round_blocks, dst, slot_bytes)
+    h = read_packed_info(info)
+    if not given and h.written_blocks < n:
+        dst = torch.empty(h.packed_bytes, dtype=torch.uint8, device=src.device)
+        offsets, lengths, results, info = encode_packed_launch(src, src_len, src_off, hc, round_blocks, dst, slot_bytes)
+        h = read_packed_info(info)
+    return dst[:min(h.packed_bytes, dst.numel())], offsets, lengths, results, h
+
+
 # ---- round-robin sharding -------------------------------------------------------------------------
 def local_block_count(n_blocks: int, rank: int, world: int) -> int:
     """Blocks owned by `rank` when block i lives on rank i % world."""

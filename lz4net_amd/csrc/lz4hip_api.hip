@@ -1708,6 +1708,30 @@ int lz4hip_decoded_sizes_host(const lz4hip_batch_t* b, int64_t* dst_off, int32_t
     return hostbatch::decoded_sizes_host(be, b, dst_off, dst_cap, info, knob(kKnobSizesGroups), knob(kKnobHostThreads));
 }
 
+int64_t lz4hip_encode_packed_scratch_bytes(int64_t n_blocks, int32_t slot_bytes, int64_t round_blocks)
+{
+    return encode_packed_scratch_bytes(n_blocks, slot_bytes, round_blocks);
+}
+
+// (the arguments are checked before the device is looked for: a bad call is LZ4HIP_E_ARGUMENT on any machine)
+int lz4hip_encode_packed_device(const lz4hip_batch_t* b, int mode, int64_t round_blocks, void* dst, int64_t dst_cap, int64_t* dst_off,
+                                int32_t* packed_len, void* scratch, int64_t scratch_bytes, lz4hip_packed_info_t* info, void* stream)
+{
+    HipBackend be = { (hipStream_t)stream };
+    PackedPlan p;
+    if (int rc = encode_packed_plan(be, b, mode, round_blocks, dst, dst_cap, dst_off, packed_len, scratch, scratch_bytes, info, p)) return rc;
+    if (int rc = ensure_device()) return rc;
+    return encode_packed_run(be, p);
+}
+
+int lz4hip_encode_packed_host(const lz4hip_batch_t* b, int mode, int64_t round_blocks, void* dst, int64_t dst_cap, int64_t* dst_off,
+                              int32_t* packed_len, lz4hip_packed_info_t* info)
+{
+    HipBackend be = {};
+    if (int rc = stream_host_context(be)) return rc;
+    return hostbatch::encode_packed_host(be, b, mode, round_blocks, dst, dst_cap, dst_off, packed_len, info, knob(kKnobHostThreads));
+}
+
 int64_t lz4hip_frame_bound(int64_t src_len, int32_t chunk_size) { return frame_bound(src_len, chunk_size); }
 
 int64_t lz4hip_frame_encode_scratch_bytes(int64_t src_len, int32_t chunk_size)

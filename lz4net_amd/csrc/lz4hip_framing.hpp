@@ -1,5 +1,5 @@
 // lz4hip_framing.hpp -- host side of the framing paths (LZ4Stream buffers, wrapped messages, batches of LZ4Stream buffers, legacy
-// frames) and of the block batch's size query (lz4hip_sizes.hpp): the scratch
+// frames), of the block batch's size query (lz4hip_sizes.hpp) and of its packed encode (lz4hip_packed.hpp): the scratch
 // layouts, the grids and the kernel sequences around the block codec, written ONCE for the library (lz4hip_api.hip, HipBackend) and for
 // the CPU emulator (tests/simt/emu_framing.hpp, EmuBackend).  Host code only: no kernel is defined here and nothing here calls the HIP
 // runtime or the emulator; everything that touches the device goes through the backend B, which has exactly
@@ -26,6 +26,7 @@
 #include "lz4hip_streams.hpp"
 #include "lz4hip_sizes.hpp"
 #include "lz4hip_frame.hpp"
+#include "lz4hip_packed.hpp"
 
 #include "../../include/lz4hip.h"
 
@@ -52,6 +53,9 @@ static_assert(sizeof(FrameInfo) == sizeof(lz4hip_frame_info_t) && offsetof(Frame
 static_assert(kFrameOk == LZ4HIP_FRAME_OK && kFrameBadMagic == LZ4HIP_FRAME_BAD_MAGIC && kFrameTruncated == LZ4HIP_FRAME_TRUNCATED &&
               kFrameBadSize == LZ4HIP_FRAME_BAD_SIZE && kFrameCorruptBlock == LZ4HIP_FRAME_CORRUPT_BLOCK &&
               kFrameTableFull == LZ4HIP_FRAME_TABLE_FULL, "frame statuses");
+static_assert(kPackedBadLength == LZ4HIP_E_ARGUMENT, "packed results");
+static_assert(sizeof(PackedInfo) == sizeof(lz4hip_packed_info_t) && offsetof(PackedInfo, first_failed) == offsetof(lz4hip_packed_info_t, first_failed) &&
+              offsetof(PackedInfo, error) == offsetof(lz4hip_packed_info_t, error), "PackedInfo must mirror lz4hip_packed_info_t");
 
 #define LZ4HIP_FRAMING_TRY(expr) do { if (int rc_ = (expr)) return rc_; } while (0)
 
@@ -875,6 +879,131 @@ int decoded_sizes(B& be, const lz4hip_batch_t* b, int64_t* dst_off, int32_t* dst
     a.src = (const uint8_t*)b->src; a.src_off = b->src_off; a.src_stride = b->src_stride; a.src_len = b->src_len; a.src_len_all = b->src_len_all;
     a.n = n; a.result = b->result ? b->result : l.result; a.dst_cap = dst_cap; a.offs = dst_off ? dst_off : l.offs; a.min_bad = l.min_bad;
     return decoded_sizes_run(be, a, l.partial, (SizesInfo*)info, groups);
+}
+
+// ---- a block batch encoded into one packed buffer (lz4hip_packed.hpp) -------------------------------------------------------------------
+// The batch runs in rounds of at most `round` blocks through ONE ring of `round` slots: the scratch is the ring, the round's limits and
+// results, the scan's tile sums and the state block, and does not grow with the batch once it has more blocks than a round.
+inline int64_t packed_slot(int32_t slot_bytes) { return ((int64_t)slot_bytes + 15) / 16 * 16; }
+// blocks per round: all of them for round_blocks = 0 (or more than there are)
+inline int64_t packed_round(int64_t n, int64_t round_blocks) { return round_blocks <= 0 || round_blocks > n ? n : round_blocks; }
+
+struct PackedScratch { uint8_t* ring; int32_t* caps; int32_t* lens; int32_t* result; int64_t* partial; int64_t* state; int64_t bytes; };
+inline PackedScratch packed_scratch(void* scratch, int64_t n, int32_t slot_bytes, int64_t round_blocks)
+{
+    const int64_t round = packed_round(n, round_blocks);
+    Carver c(scratch);
+    PackedScratch l;
+    l.ring = c.take_as<uint8_t>(round * packed_slot(slot_bytes));
+    l.caps = c.take_as<int32_t>(4 * round);
+    l.lens = c.take_as<int32_t>(4 * round);
+    l.result = c.take_as<int32_t>(4 * round);
+    l.partial = c.take_as<int64_t>(8 * scan_tiles(round));
+    l.state = c.take_as<int64_t>(kPackedStateBytes);
+    l.bytes = c.at;
+    return l;
+}
+// 0 for an empty batch; LZ4HIP_E_ARGUMENT for a slot width or a round the call refuses
+inline int64_t encode_packed_scratch_bytes(int64_t n, int32_t slot_bytes, int64_t round_blocks)
+{
+    if (n <= 0) return 0;
+    if (slot_bytes <= 0 || round_blocks < 0) return LZ4HIP_E_ARGUMENT;
+    return packed_scratch(nullptr, n, slot_bytes, round_blocks).bytes;
+}
+
+// what the front hands the sequence: b is the caller's descriptor (its source side and result are read)
+struct PackedPlan {
+    lz4hip_batch_t b; int mode; int64_t n, round, slot; int32_t limit; PackedScratch l;
+    uint8_t* dst; int64_t dst_cap; int64_t* dst_off; int32_t* packed_len; PackedInfo* info;
+};
+
+// Each round is a normal batch encode of its rows: the descriptor's array pointers are advanced here, on the host, its output is the
+// ring, its capacities the round's array in scratch and its lengths the round's sanitised copy there (the encoders do not check a
+// length's sign: a negative one would send their literal copy before the slot).  Rounds follow each other in stream order: a round's pack has read the ring
+// before the next round's encoder writes it.
+template <class B>
+int encode_packed_run(B& be, const PackedPlan& p)
+{
+    if (p.n == 0) {
+        LZ4HIP_FRAMING_TRY(be.fill(p.dst_off, 0, sizeof(int64_t)));
+        if (p.info) be.launch(packed_empty_info_kernel, fixed_grid(1), 64, p.info);
+        return be.last_error();
+    }
+    LZ4HIP_FRAMING_TRY(be.fill(p.l.state, 0, (size_t)kPackedStateBytes));
+    LZ4HIP_FRAMING_TRY(be.fill(p.l.state + kPackedBad, 0xFF, 8));      // the lowest failed index = none
+    const lz4hip_batch_t& b = p.b;
+    const Grid pack_grid = copy_grid(p.round * p.slot);
+    int32_t parity = 0;
+    for (int64_t first = 0; first < p.n; first += p.round, parity ^= 1) {
+        PackedRound a;
+        a.first = first; a.cnt = p.n - first < p.round ? p.n - first : p.round; a.slot = p.slot; a.limit = p.limit; a.parity = parity;
+        a.cap_in = b.dst_cap ? b.dst_cap + first : nullptr; a.caps = p.l.caps; a.result = b.result ? b.result + first : p.l.result;
+        a.len_in = b.src_len ? b.src_len + first : nullptr; a.lens_enc = p.l.lens;
+        a.ring = p.l.ring; a.offs = p.dst_off + first; a.lens = p.packed_len ? p.packed_len + first : nullptr; a.state = p.l.state;
+        be.launch(packed_caps_kernel, stream_grid(a.cnt), kStreamThreads, a);
+        LZ4HIP_FRAMING_TRY(be.last_error());
+        lz4hip_batch_t rb = {};
+        rb.src = b.src_off ? b.src : (const void*)((const uint8_t*)b.src + first * b.src_stride);
+        rb.src_off = b.src_off ? b.src_off + first : nullptr; rb.src_stride = b.src_stride;
+        rb.src_len = b.src_len ? p.l.lens : nullptr; rb.src_len_all = b.src_len_all;      // (no negative length reaches the encoder)
+        rb.dst = p.l.ring; rb.dst_stride = p.slot; rb.dst_cap = p.l.caps;
+        rb.result = a.result; rb.n_blocks = a.cnt;
+        LZ4HIP_FRAMING_TRY(be.encode(&rb, p.mode));
+        be.launch(packed_sizes_kernel, stream_grid(a.cnt), kStreamThreads, a);
+        launch_scan(be, a.offs, a.cnt, p.l.partial, p.l.state + kPackedTotal);
+        be.launch(packed_rebase_kernel, stream_grid(a.cnt), kStreamThreads, a);
+        PackedLayout layout = { a };
+        be.launch(packed_pack_kernel, pack_grid, kStreamThreads, layout, p.dst, p.dst_cap);
+        LZ4HIP_FRAMING_TRY(be.last_error());
+    }
+    if (p.info) be.launch(packed_info_kernel, fixed_grid(1), 64, (const int64_t*)p.dst_off, p.n, p.dst_cap, (const int64_t*)p.l.state, p.info);
+    return be.last_error();
+}
+
+// reads b's src, src_off / src_stride, src_len / src_len_all, dst_cap / dst_cap_all (the slot width), result and n_blocks; b's dst,
+// dst_off and dst_stride are ignored.  packed_len and info may be NULL.
+// what the device call and the host call check alike: everything but the scratch, which only the device call is handed
+template <class B>
+int encode_packed_check(B& be, const lz4hip_batch_t* b, int mode, int64_t round_blocks, const void* dst, int64_t dst_cap, const int64_t* dst_off)
+{
+    if (!b) return be.fail(LZ4HIP_E_ARGUMENT, "encode packed: batch descriptor is NULL");
+    const int64_t n = b->n_blocks;
+    if (n < 0) return be.fail(LZ4HIP_E_ARGUMENT, "encode packed: n_blocks < 0");
+    if (dst_cap < 0 || round_blocks < 0) return be.fail(LZ4HIP_E_ARGUMENT, "encode packed: dst_cap < 0 or round_blocks < 0");
+    if (b->dst_cap_all <= 0) return be.fail(LZ4HIP_E_ARGUMENT, "encode packed: dst_cap_all (the slot width) must be > 0");
+    if (mode != LZ4HIP_MODE_FAST && mode != LZ4HIP_MODE_HC) return be.fail(LZ4HIP_E_ARGUMENT, "mode must be LZ4HIP_MODE_FAST or LZ4HIP_MODE_HC");
+    if (!dst_off) return be.fail(LZ4HIP_E_ARGUMENT, "encode packed: dst_off is NULL");
+    if (packed_round(n, round_blocks) > 0x7FFFFFFF) return be.fail(LZ4HIP_E_ARGUMENT, "encode packed: more than 2^31 - 1 blocks in a round");
+    if (n > 0) {
+        if (!b->src || (dst_cap > 0 && !dst)) return be.fail(LZ4HIP_E_ARGUMENT, "encode packed: src and dst must be non-NULL");
+        if (!b->src_len && b->src_len_all < 0) return be.fail(LZ4HIP_E_ARGUMENT, "encode packed: src_len_all < 0");
+    }
+    return 0;
+}
+
+template <class B>
+int encode_packed_plan(B& be, const lz4hip_batch_t* b, int mode, int64_t round_blocks, void* dst, int64_t dst_cap, int64_t* dst_off,
+                       int32_t* packed_len, void* scratch, int64_t scratch_bytes, lz4hip_packed_info_t* info, PackedPlan& p)
+{
+    LZ4HIP_FRAMING_TRY(encode_packed_check(be, b, mode, round_blocks, dst, dst_cap, dst_off));
+    const int64_t n = b->n_blocks;
+    if (scratch_bytes < encode_packed_scratch_bytes(n, b->dst_cap_all, round_blocks))
+        return be.fail(LZ4HIP_E_ARGUMENT, "encode packed: scratch_bytes < lz4hip_encode_packed_scratch_bytes");
+    if (n > 0 && !scratch) return be.fail(LZ4HIP_E_ARGUMENT, "encode packed: scratch must be non-NULL");
+    p.n = n; p.round = packed_round(n, round_blocks);
+    p.b = *b; p.mode = mode; p.limit = b->dst_cap_all; p.slot = packed_slot(b->dst_cap_all);
+    p.l = packed_scratch(scratch, n, b->dst_cap_all, round_blocks);
+    p.dst = (uint8_t*)dst; p.dst_cap = dst_cap; p.dst_off = dst_off; p.packed_len = packed_len; p.info = (PackedInfo*)info;
+    return 0;
+}
+
+template <class B>
+int encode_packed(B& be, const lz4hip_batch_t* b, int mode, int64_t round_blocks, void* dst, int64_t dst_cap, int64_t* dst_off,
+                  int32_t* packed_len, void* scratch, int64_t scratch_bytes, lz4hip_packed_info_t* info)
+{
+    PackedPlan p;
+    LZ4HIP_FRAMING_TRY(encode_packed_plan(be, b, mode, round_blocks, dst, dst_cap, dst_off, packed_len, scratch, scratch_bytes, info, p));
+    return encode_packed_run(be, p);
 }
 
 // ---- the host-pointer calls ------------------------------------------------------------------------------------------------------------

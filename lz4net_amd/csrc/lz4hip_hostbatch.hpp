@@ -414,6 +414,73 @@ int decoded_sizes_host(B& be, const lz4hip_batch_t* hb, int64_t* dst_off, int32_
     return be.sync();                                                  // (also what keeps the gathered rows alive until the upload has read them)
 }
 
+// ---- a host-pointer batch encoded into one packed buffer ---------------------------------------------------------------------------------
+// lz4hip_encode_packed_host: the rows, strided or at offsets, are gathered back to back (the row work above, as decoded_sizes_host
+// does), staged with their offsets, lengths and limits in ONE device image of the framing backend B and encoded by the device call
+// (framing::encode_packed, whose argument checks run first: framing::encode_packed_check).  The info comes back first; then the
+// per-block arrays and only min(packed_bytes, dst_cap) bytes of output.  The image's output piece is min(dst_cap, the sum of the
+// per-block limits): no batch can take more, so a generous dst_cap costs no device memory.  A negative src_len[i] travels as it is --
+// the device sequence keeps it from the encoder and gives that block its LZ4HIP_E_ARGUMENT result -- and gathers no bytes.  info may
+// be NULL.
+template <class B>
+int encode_packed_host(B& be, const lz4hip_batch_t* hb, int mode, int64_t round_blocks, void* dst, int64_t dst_cap, int64_t* dst_off,
+                       int32_t* packed_len, lz4hip_packed_info_t* info, int threads_knob, const HostLimits& limits = HostLimits())
+{
+    if (int rc = framing::encode_packed_check(be, hb, mode, round_blocks, dst, dst_cap, dst_off)) return rc;
+    const int64_t n = hb->n_blocks;
+    lz4hip_packed_info_t h = {};
+    if (n == 0) {
+        dst_off[0] = 0;
+        h.first_failed = -1;
+        if (info) *info = h;
+        return 0;
+    }
+    std::vector<int64_t> at;
+    std::vector<int32_t> lens;
+    std::vector<uint8_t> rows;
+    int64_t total = 0, most = 0;
+    try {
+        at.resize((size_t)n); lens.resize((size_t)n);
+        for (int64_t i = 0; i < n; i++) {
+            const int32_t sl = src_len(hb, i), lim = hb->dst_cap && hb->dst_cap[i] < hb->dst_cap_all ? hb->dst_cap[i] : hb->dst_cap_all;
+            const int32_t cap = lim < 0 ? 0 : lim;
+            at[(size_t)i] = total; lens[(size_t)i] = sl; total += sl > 0 ? sl : 0; most += cap;
+        }
+        rows.resize((size_t)total);
+    } catch (const std::bad_alloc&) { return be.fail(LZ4HIP_E_MEMORY, "encode packed: no host memory to gather the rows in"); }
+    uint8_t* const packed = rows.data();
+    const int64_t* const at_p = at.data();
+    const int32_t* const len_p = lens.data();
+    for_rows(n, total, limits, threads_knob, [=](int64_t i) {
+        if (len_p[i] > 0) memcpy(packed + at_p[i], src_row(hb, i), (size_t)len_p[i]);
+    });
+    // device image: [rows | offsets | lengths | limits | results | lengths out | output offsets | info | scratch | output]
+    const int64_t out_bytes = dst_cap < most ? dst_cap : most;
+    const int64_t scratch_bytes = framing::encode_packed_scratch_bytes(n, hb->dst_cap_all, round_blocks);
+    Carver c;
+    c.take(total);
+    const int64_t off_at = c.take(8 * n), len_at = c.take(4 * n), cap_at = c.take(4 * n), res_at = c.take(4 * n), plen_at = c.take(4 * n),
+                  doff_at = c.take(8 * (n + 1)), info_at = c.take(256), scratch_at = c.take(scratch_bytes), out_at = c.take(out_bytes);
+    framing::Image<B> im = { be };
+    if (int rc = im.reserve(c.at)) return rc;
+    if (int rc = im.upload_source(packed, total)) return rc;
+    if (int rc = im.upload(off_at, at_p, 8 * n)) return rc;
+    if (int rc = im.upload(len_at, len_p, 4 * n)) return rc;
+    if (hb->dst_cap) if (int rc = im.upload(cap_at, hb->dst_cap, 4 * n)) return rc;
+    lz4hip_batch_t db = {};
+    db.src = im.d; db.src_off = im.i64(off_at); db.src_len = im.i32(len_at); db.src_len_all = hb->src_len_all;      /* upper-bound hint */
+    db.dst_cap = hb->dst_cap ? im.i32(cap_at) : nullptr; db.dst_cap_all = hb->dst_cap_all; db.result = im.i32(res_at); db.n_blocks = n;
+    if (int rc = framing::encode_packed(be, &db, mode, round_blocks, im.d + out_at, out_bytes, im.i64(doff_at), im.i32(plen_at), im.d + scratch_at,
+                                        scratch_bytes, (lz4hip_packed_info_t*)(im.d + info_at))) return rc;
+    if (int rc = im.download(&h, info_at, sizeof h)) return rc;
+    if (int rc = be.sync()) return rc;                                 // (also what keeps the gathered rows alive until the upload has read them)
+    if (info) *info = h;
+    if (hb->result) if (int rc = im.download(hb->result, res_at, 4 * n)) return rc;
+    if (int rc = im.download(dst_off, doff_at, 8 * (n + 1))) return rc;
+    if (packed_len) if (int rc = im.download(packed_len, plen_at, 4 * n)) return rc;
+    return im.download_encoded(dst, out_at, h.packed_bytes < out_bytes ? h.packed_bytes : out_bytes);
+}
+
 // ---- the shards of the multi-device form -----------------------------------------------------------------------------------------------
 // Block i belongs to shard i mod nd -- the partition of SURVEY.md 8e / BASELINE configs[4]: shard k holds blocks k, k + nd, ... as an
 // offset-addressed batch over the caller's buffers with lengths, capacities and results of its own (none at all when n <= k).
