@@ -405,6 +405,63 @@ int lz4hip_encode_packed_host(const lz4hip_batch_t* b, int mode, int64_t round_b
                               void* dst, int64_t dst_cap, int64_t* dst_off, int32_t* packed_len,
                               lz4hip_packed_info_t* info);
 
+/* ---- a block batch decoded into one packed buffer, without a size walk ---------------------------------
+ * The packed encode the other way, for blocks whose decoded sizes the caller does not know but for which it knows an UPPER BOUND per
+ * block: a frame's chunk size, a stream's block size, the row width the data was cut to.  The decoders then answer the size question
+ * themselves: a round of blocks is decoded into a ring of bound-sized slots, the produced sizes are scanned and the round is packed
+ * back to back into dst -- block i at dst[dst_off[i], dst_off[i + 1]).  No size query (lz4hip_decoded_sizes_device walks every
+ * block's tokens, which costs more than decoding it), no read-back between two calls, and no n * slot bytes of output.
+ *
+ * The source side of *b is read as the batch decoder reads it: src, src_off / src_stride, src_len / src_len_all and n_blocks.  b->dst,
+ * dst_off and dst_stride are ignored and may be NULL or 0.  b->dst_cap_all must be > 0: it is the slot width, slot_bytes below, and the
+ * per-block output limit where b->dst_cap is NULL; with b->dst_cap given, block i's limit is min(max(dst_cap[i], 0), dst_cap_all).
+ * b->result[n], if not NULL, receives the raw per-block results: result[i] is what lz4hip_decode_batch_device (known_output_size = 0)
+ * gives block i at that limit -- the bytes produced, or -(error position), the latter also for a block that would produce more than
+ * its limit: LZ4_uncompress_unknownOutputSize(src_i, slot, len_i, limit_i).  An empty block succeeds with 0.  A negative length gives
+ * LZ4HIP_E_ARGUMENT: the call itself produces that result, the decoders only ever see a sanitised copy of the lengths.
+ *
+ * The call writes dst_off[n + 1] (required): the exclusive scan of max(result[i], 0), dst_off[n] the total; decoded_len[n] (optional):
+ * max(result[i], 0); the bytes; and *info (optional).  A failed block -- result < 0; the packed encode's rule is <= 0, the one place
+ * the two differ -- takes 0 bytes and its neighbours pack around it.
+ *
+ * dst_cap may be any value >= 0.  Block i is written iff dst_off[i + 1] <= dst_cap; info.written_blocks is the length of that prefix,
+ * the bytes of dst from dst_off[written_blocks] up to dst_cap are unspecified, and no byte at or past dst_cap is ever written.
+ * dst_off, decoded_len, result and info.decoded_bytes are complete in either case: dst_cap = 0 is a size query at decode speed (dst may
+ * then be NULL), and a second call with dst_cap = decoded_bytes fits -- it decodes again.
+ *
+ * Rounds: round_blocks = 0 runs the batch as one round; round_blocks = K > 0 runs ceil(n / K) rounds of at most K blocks through ONE
+ * ring of min(K, n) slots of the slot width rounded up to 16 bytes, so the scratch does not grow with n once n > K.  Each round is a
+ * normal unknown-size batch decode of its rows into the ring (dst_stride = the slot): the wavefront / lane dispatch rules and the lane
+ * decoder's first-use probe apply to the ROUND's size, not to n.  Rounds do not overlap, so they bound memory and cost time (262 144
+ * blocks of 64 KiB: 25 ms in one round, 138 ms in rounds of 16 384), and a round of few large blocks leaves most of the
+ * device idle: see the frame call below. */
+typedef struct lz4hip_compact_info {
+    int64_t blocks;          /* n */
+    int64_t decoded_bytes;   /* dst_off[n]: the bytes the whole batch decodes to, whatever dst_cap was */
+    int64_t written_blocks;  /* leading blocks that lie wholly inside dst_cap (n when all do) */
+    int64_t first_failed;    /* lowest index with a NEGATIVE result, -1 if none */
+    int32_t error, reserved; /* that block's result, 0 if none */
+} lz4hip_compact_info_t;
+
+/* Device scratch (bytes) of the device call; 0 for an empty batch, non-decreasing in n_blocks and the same for every
+ * n_blocks >= round_blocks > 0.  LZ4HIP_E_ARGUMENT for slot_bytes <= 0 or round_blocks < 0. */
+int64_t lz4hip_decode_compact_scratch_bytes(int64_t n_blocks, int32_t slot_bytes, int64_t round_blocks);
+/* Device-resident batch: the contract of the other device calls -- device pointers of the CURRENT device, launch-only on `stream`, no
+ * device value read on the host, no allocation beyond what the block decoder itself does on first use, scratch from the caller, 0 or
+ * LZ4HIP_E_* returned.  Arguments are checked first: a NULL batch or dst_off, a negative n_blocks, dst_cap or round_blocks,
+ * dst_cap_all <= 0, too little scratch or more than 2^31 - 1 blocks in a round is LZ4HIP_E_ARGUMENT whatever the device.  An empty
+ * batch writes dst_off[0] = 0 and an info with first_failed = -1. */
+int lz4hip_decode_compact_device(const lz4hip_batch_t* b, int64_t round_blocks,
+                                 void* dst, int64_t dst_cap, int64_t* dst_off, int32_t* decoded_len,
+                                 void* scratch, int64_t scratch_bytes, lz4hip_compact_info_t* info, void* stream);
+/* Host-resident batch: every pointer is host memory.  Gathers the rows, stages them with their lengths and limits through device
+ * memory (per-thread, grow-only, freed by lz4hip_release_workspaces), runs the device call, reads info and the per-block arrays back
+ * and copies only min(decoded_bytes, dst_cap) bytes of output.  The arguments are checked as the device call checks them, before the
+ * device is looked for.  Returns 0 (block failures are in result and info) or LZ4HIP_E_*. */
+int lz4hip_decode_compact_host(const lz4hip_batch_t* b, int64_t round_blocks,
+                               void* dst, int64_t dst_cap, int64_t* dst_off, int32_t* decoded_len,
+                               lz4hip_compact_info_t* info);
+
 /* ---- legacy frames ---------------------------------------------------------------------------------
  * The frame of the demo command-line tool that ships with the reference (original/lz4demo.c:84-87, 167-317), the one format here that
  * files from outside the lz4net world arrive in:
@@ -463,6 +520,33 @@ int lz4hip_frame_index_device(const void* src, int64_t src_len, int32_t chunk_si
 int lz4hip_frame_decode_device(const void* src, const lz4hip_frame_info_t* info_host, int64_t max_chunks,
                                void* scratch, int64_t scratch_bytes, void* dst, int64_t dst_cap,
                                lz4hip_frame_info_t* info, void* stream);
+
+/* Decode in ONE call, with no value read on the host: the size field walk into a table of max_chunks rows, then
+ * lz4hip_decode_compact_device over all max_chunks rows -- slot and limit chunk_size; the rows past the frame's count are empty
+ * blocks -- straight into dst, then *info (device): chunks; decoded_bytes, the total; good_bytes, dst_off of the lowest chunk with a
+ * negative decoder result; and the error in the index's precedence: LZ4HIP_FRAME_TABLE_FULL, then LZ4HIP_FRAME_CORRUPT_BLOCK at the
+ * lowest bad chunk's size field, then the walk's header error.  A bad chunk takes 0 bytes and its neighbours pack around it.  dst_cap is
+ * any value >= 0 and clips as it does there: chunk k is written iff the offset after it is <= dst_cap, nothing at or past dst_cap is
+ * written, and decoded_bytes is complete either way (dst_cap = 0: a size query at decode speed).  On TABLE_FULL the contents of dst are
+ * unspecified: the caller grows the table to info.chunks and calls again.
+ *
+ * Every chunk gets chunk_size bytes of room, which is exactly the reference's reader (original/lz4demo.c:276-300:
+ * LZ4_uncompress_unknownOutputSize(in, out, size, chunk_size)).  The two-call path above decodes a chunk at the capacity its size walk
+ * found and is therefore STRICTER than that reader: a chunk that breaks the format's end rules without being cut short -- one whose
+ * last sequence is only legal because the output limit lies further on -- is a bad chunk there and decodes here as it does in the
+ * reference.
+ *
+ * round_chunks is lz4hip_decode_compact_device's round_blocks.  The ring of round_chunks = 0 is max_chunks slots of chunk_size bytes
+ * (rounded up to 16), which is large at 8 MiB chunks; rounds shrink it to round_chunks slots, but rounds do not overlap and a round
+ * of few large chunks leaves most of the device idle (one wavefront decodes one 8 MiB chunk): a 1 GiB frame of 8 MiB chunks took
+ * 230 ms in one round and 1.8 s in rounds of 16 on an MI355X.
+ * Scratch: lz4hip_frame_decode_compact_scratch_bytes, LZ4HIP_E_ARGUMENT for arguments the call refuses.  The arguments are checked
+ * first, whatever the device: negative sizes, a bad chunk_size, NULL src (with src_len > 0), scratch, info or dst (with dst_cap > 0),
+ * too little scratch. */
+int64_t lz4hip_frame_decode_compact_scratch_bytes(int32_t chunk_size, int64_t max_chunks, int64_t round_chunks);
+int lz4hip_frame_decode_compact_device(const void* src, int64_t src_len, int32_t chunk_size, int64_t max_chunks, int64_t round_chunks,
+                                       void* scratch, int64_t scratch_bytes, void* dst, int64_t dst_cap,
+                                       lz4hip_frame_info_t* info, void* stream);
 
 /* Host-resident frames: stage the whole buffer through device memory (per-thread, grow-only, freed by lz4hip_release_workspaces), run
  * the device calls above and synchronise.  Encode returns 0 or LZ4HIP_E_* (dst_cap >= lz4hip_frame_bound); *dst_len on the host.

@@ -61,6 +61,12 @@ class PackedInfo(C.Structure):
                 ("error", C.c_int32), ("reserved", C.c_int32)]
 
 
+class CompactInfo(C.Structure):
+    """struct lz4hip_compact_info (include/lz4hip.h)."""
+    _fields_ = [("blocks", C.c_int64), ("decoded_bytes", C.c_int64), ("written_blocks", C.c_int64), ("first_failed", C.c_int64),
+                ("error", C.c_int32), ("reserved", C.c_int32)]
+
+
 class FrameInfo(C.Structure):
     """struct lz4hip_frame_info (include/lz4hip.h)."""
     _fields_ = [("chunks", C.c_int64), ("decoded_bytes", C.c_int64), ("good_bytes", C.c_int64), ("error_offset", C.c_int64),
@@ -136,12 +142,19 @@ SYMBOLS = [
     ("lz4hip_encode_packed_device", C.c_int, [C.POINTER(Batch), C.c_int, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                               C.c_void_p, C.c_void_p]),
     ("lz4hip_encode_packed_host", C.c_int, [C.POINTER(Batch), C.c_int, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(PackedInfo)]),
+    ("lz4hip_decode_compact_scratch_bytes", C.c_int64, [C.c_int64, C.c_int32, C.c_int64]),
+    ("lz4hip_decode_compact_device", C.c_int, [C.POINTER(Batch), C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                               C.c_void_p, C.c_void_p]),
+    ("lz4hip_decode_compact_host", C.c_int, [C.POINTER(Batch), C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(CompactInfo)]),
     ("lz4hip_frame_bound", C.c_int64, [C.c_int64, C.c_int32]),
     ("lz4hip_frame_encode_scratch_bytes", C.c_int64, [C.c_int64, C.c_int32]),
     ("lz4hip_frame_decode_scratch_bytes", C.c_int64, [C.c_int64]),
     ("lz4hip_frame_encode_device", C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     ("lz4hip_frame_index_device", C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     ("lz4hip_frame_decode_device", C.c_int, [C.c_void_p, C.POINTER(FrameInfo), C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    ("lz4hip_frame_decode_compact_scratch_bytes", C.c_int64, [C.c_int32, C.c_int64, C.c_int64]),
+    ("lz4hip_frame_decode_compact_device", C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                                     C.c_void_p, C.c_void_p]),
     ("lz4hip_frame_encode_host", C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
     ("lz4hip_frame_decode_host", C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.POINTER(FrameInfo)]),
 ]

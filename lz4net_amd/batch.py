@@ -244,6 +244,72 @@ def encode_packed(src: torch.Tensor, src_len, src_off: torch.Tensor | None = Non
     return dst[:min(h.packed_bytes, dst.numel())], offsets, lengths, results, h
 
 
+# ---- decoding a batch into one packed buffer without a size walk --------------------------------------
+def read_compact_info(info: torch.Tensor) -> _lib.CompactInfo:
+    """The lz4hip_compact_info_t a decode_compact call left on the device (synchronises)."""
+    return _lib.CompactInfo.from_buffer_copy(info.cpu().numpy().tobytes())
+
+
+def decode_compact_launch(src, src_len, src_off, round_blocks, dst, slot_bytes, dst_cap=None, block_cap=None):
+    """One lz4hip_decode_compact_device call on torch's current stream, not waited for -> (offsets, lengths, results, info), all on the
+    device: int64 n + 1, int32 n, int32 n and the lz4hip_compact_info_t record as five int64 (read_compact_info).  dst_cap defaults to
+    dst.numel() (0 for dst=None: a size query); block_cap (int32, n) gives per-block output limits below slot_bytes."""
+    n, b, keep = _source(src, src_len, src_off)
+    dev = src.device
+    offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    lengths = torch.empty(n, dtype=torch.int32, device=dev)
+    results = torch.empty(n, dtype=torch.int32, device=dev)
+    info = torch.empty(5, dtype=torch.int64, device=dev)
+    if block_cap is not None:
+        assert block_cap.dtype == torch.int32 and block_cap.numel() == n and block_cap.is_cuda and block_cap.is_contiguous()
+        b.dst_cap = block_cap.data_ptr()
+    b.dst_cap_all, b.result = slot_bytes, results.data_ptr()
+    need = _lib.check(_lib.lib().lz4hip_decode_compact_scratch_bytes(n, slot_bytes, round_blocks))
+    scratch = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+    cap = (0 if dst is None else dst.numel()) if dst_cap is None else dst_cap
+    _lib.check(_lib.lib().lz4hip_decode_compact_device(C.byref(b), round_blocks, _ptr(dst), cap, offsets.data_ptr(), lengths.data_ptr(),
+                                                       scratch.data_ptr(), need, info.data_ptr(), _stream()))
+    return offsets, lengths, results, info
+
+
+COMPACT_GUESS = 4        # decode_compact's first output buffer: this many times the compressed bytes
+
+
+def decode_compact(src: torch.Tensor, src_len, src_off: torch.Tensor | None = None, slot_bytes: int = BLOCK, round_blocks: int = 0,
+                   dst: torch.Tensor | None = None):
+    """Decode blocks of unknown size, none longer than slot_bytes, into ONE buffer of exactly the bytes they produce without sizing
+    them first (lz4hip_decode_compact_device): block i is row i of a 2-D `src`, or src[src_off[i]:] of a 1-D one.  Returns (dst_view,
+    offsets, lengths, results, info): block i's bytes are dst_view[offsets[i]:offsets[i + 1]], lengths[i] = max(results[i], 0) their
+    count, results the raw decoder results (negative, and no byte taken, for a corrupt block or one that decodes to more than
+    slot_bytes) and info the lz4hip_compact_info_t read back (ONE synchronisation).
+
+    round_blocks = K > 0 runs the batch in rounds of K blocks through a ring of K slots of slot_bytes (device scratch that does not
+    grow with the batch); 0 takes n slots.
+
+    dst=None: the first attempt allocates a guess that needs no wait for the device: COMPACT_GUESS (4) times the compressed bytes as
+    far as they are known here -- n * src_len for an int src_len, else the bytes `src` spans -- capped at n * slot_bytes, which no
+    batch exceeds.  Only when not every block fits (info.written_blocks < n) is there a second call, into exactly info.decoded_bytes
+    bytes: that pass DECODES AGAIN, it does not reuse the first one's work.  With `dst` (1-D uint8) given there is never a second
+    call: dst_view is dst[:min(decoded_bytes, dst.numel())], the blocks before info.written_blocks are in it, and offsets, lengths,
+    results and info.decoded_bytes are complete."""
+    assert src.dtype == torch.uint8 and src.is_cuda
+    n = src.shape[0] if src_off is None else src_off.numel()
+    slot_bytes = max(int(slot_bytes), 1)
+    given = dst is not None
+    if given:
+        assert dst.dtype == torch.uint8 and dst.is_cuda and dst.dim() == 1 and dst.is_contiguous()
+    else:
+        compressed = n * src_len if isinstance(src_len, int) else src.numel()
+        dst = torch.empty(max(min(COMPACT_GUESS * compressed, n * slot_bytes), 0), dtype=torch.uint8, device=src.device)
+    offsets, lengths, results, info = decode_compact_launch(src, src_len, src_off, round_blocks, dst, slot_bytes)
+    h = read_compact_info(info)
+    if not given and h.written_blocks < n:
+        dst = torch.empty(h.decoded_bytes, dtype=torch.uint8, device=src.device)
+        offsets, lengths, results, info = decode_compact_launch(src, src_len, src_off, round_blocks, dst, slot_bytes)
+        h = read_compact_info(info)
+    return dst[:min(h.decoded_bytes, dst.numel())], offsets, lengths, results, h
+
+
 # ---- round-robin sharding -------------------------------------------------------------------------
 def local_block_count(n_blocks: int, rank: int, world: int) -> int:
     """Blocks owned by `rank` when block i lives on rank i % world."""

@@ -1732,6 +1732,31 @@ int lz4hip_encode_packed_host(const lz4hip_batch_t* b, int mode, int64_t round_b
     return hostbatch::encode_packed_host(be, b, mode, round_blocks, dst, dst_cap, dst_off, packed_len, info, knob(kKnobHostThreads));
 }
 
+int64_t lz4hip_decode_compact_scratch_bytes(int64_t n_blocks, int32_t slot_bytes, int64_t round_blocks)
+{
+    return decode_compact_scratch_bytes(n_blocks, slot_bytes, round_blocks);
+}
+
+// (the arguments are checked before the device is looked for: a bad call is LZ4HIP_E_ARGUMENT on any machine)
+int lz4hip_decode_compact_device(const lz4hip_batch_t* b, int64_t round_blocks, void* dst, int64_t dst_cap, int64_t* dst_off,
+                                 int32_t* decoded_len, void* scratch, int64_t scratch_bytes, lz4hip_compact_info_t* info, void* stream)
+{
+    HipBackend be = { (hipStream_t)stream };
+    PackedPlan p;
+    if (int rc = decode_compact_plan(be, b, round_blocks, dst, dst_cap, dst_off, decoded_len, scratch, scratch_bytes, info, p)) return rc;
+    if (int rc = ensure_device()) return rc;
+    return decode_compact_run(be, p);
+}
+
+int lz4hip_decode_compact_host(const lz4hip_batch_t* b, int64_t round_blocks, void* dst, int64_t dst_cap, int64_t* dst_off,
+                               int32_t* decoded_len, lz4hip_compact_info_t* info)
+{
+    HipBackend be = {};
+    if (int rc = decode_compact_check(be, b, round_blocks, dst, dst_cap, dst_off)) return rc;
+    if (int rc = stream_host_context(be)) return rc;
+    return hostbatch::decode_compact_host(be, b, round_blocks, dst, dst_cap, dst_off, decoded_len, info, knob(kKnobHostThreads));
+}
+
 int64_t lz4hip_frame_bound(int64_t src_len, int32_t chunk_size) { return frame_bound(src_len, chunk_size); }
 
 int64_t lz4hip_frame_encode_scratch_bytes(int64_t src_len, int32_t chunk_size)
@@ -1771,6 +1796,21 @@ int lz4hip_frame_decode_device(const void* src, const lz4hip_frame_info_t* info_
     if (int rc = frame_decode_plan(be, src, info_host, max_chunks, scratch, scratch_bytes, dst, dst_cap, info, p)) return rc;
     if (int rc = ensure_device()) return rc;
     return frame_decode_run(be, p);
+}
+
+int64_t lz4hip_frame_decode_compact_scratch_bytes(int32_t chunk_size, int64_t max_chunks, int64_t round_chunks)
+{
+    return frame_decode_compact_scratch_bytes(chunk_size, max_chunks, round_chunks);
+}
+
+int lz4hip_frame_decode_compact_device(const void* src, int64_t src_len, int32_t chunk_size, int64_t max_chunks, int64_t round_chunks,
+                                       void* scratch, int64_t scratch_bytes, void* dst, int64_t dst_cap, lz4hip_frame_info_t* info, void* stream)
+{
+    HipBackend be = { (hipStream_t)stream };
+    FrameCompactPlan p;
+    if (int rc = frame_decode_compact_plan(be, src, src_len, chunk_size, max_chunks, round_chunks, scratch, scratch_bytes, dst, dst_cap, info, p)) return rc;
+    if (int rc = ensure_device()) return rc;
+    return frame_decode_compact_run(be, p);
 }
 
 int lz4hip_frame_encode_host(const void* src, int64_t src_len, int32_t chunk_size, int mode, void* dst, int64_t dst_cap, int64_t* dst_len)

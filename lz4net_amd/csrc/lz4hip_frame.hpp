@@ -181,10 +181,9 @@ __global__ void __launch_bounds__(kStreamThreads) frame_check_kernel(FrameTables
 // The record, from the table as it stands: after the index, and again after the decode's check.  Every chunk in the table lies before
 // the walk's header error (if any), so a bad chunk comes first; a frame with more chunks than rows is LZ4HIP_FRAME_TABLE_FULL whatever
 // its chunks hold (the caller grows the table to `chunks` and indexes again).
-__global__ void __launch_bounds__(64) frame_info_kernel(FrameTables t, FrameInfo* info)
+// (`bad`: the lowest bad chunk, ~0 for none -- the two-call path keeps it in the table, the one-call path of lz4hip_compact.hpp elsewhere)
+LZ4HIP_DEVICE FrameInfo frame_info_of(const FrameTables& t, unsigned long long bad)
 {
-    if (threadIdx.x != 0) return;
-    const unsigned long long bad = *t.min_bad;
     FrameInfo r;
     r.chunks = t.walk[0];
     r.decoded_bytes = r.good_bytes = t.dst_off[t.max_chunks];
@@ -199,7 +198,13 @@ __global__ void __launch_bounds__(64) frame_info_kernel(FrameTables t, FrameInfo
         r.error_offset = t.hdr_off[bad];
         r.good_bytes = t.dst_off[bad];
     }
-    *info = r;
+    return r;
+}
+
+__global__ void __launch_bounds__(64) frame_info_kernel(FrameTables t, FrameInfo* info)
+{
+    if (threadIdx.x != 0) return;
+    *info = frame_info_of(t, *t.min_bad);
 }
 
 }  // namespace lz4hip

@@ -1,5 +1,6 @@
 // lz4hip_framing.hpp -- host side of the framing paths (LZ4Stream buffers, wrapped messages, batches of LZ4Stream buffers, legacy
-// frames), of the block batch's size query (lz4hip_sizes.hpp) and of its packed encode (lz4hip_packed.hpp): the scratch
+// frames), of the block batch's size query (lz4hip_sizes.hpp), of its packed encode (lz4hip_packed.hpp) and of its compact decode
+// (lz4hip_compact.hpp): the scratch
 // layouts, the grids and the kernel sequences around the block codec, written ONCE for the library (lz4hip_api.hip, HipBackend) and for
 // the CPU emulator (tests/simt/emu_framing.hpp, EmuBackend).  Host code only: no kernel is defined here and nothing here calls the HIP
 // runtime or the emulator; everything that touches the device goes through the backend B, which has exactly
@@ -27,6 +28,7 @@
 #include "lz4hip_sizes.hpp"
 #include "lz4hip_frame.hpp"
 #include "lz4hip_packed.hpp"
+#include "lz4hip_compact.hpp"
 
 #include "../../include/lz4hip.h"
 
@@ -56,6 +58,12 @@ static_assert(kFrameOk == LZ4HIP_FRAME_OK && kFrameBadMagic == LZ4HIP_FRAME_BAD_
 static_assert(kPackedBadLength == LZ4HIP_E_ARGUMENT, "packed results");
 static_assert(sizeof(PackedInfo) == sizeof(lz4hip_packed_info_t) && offsetof(PackedInfo, first_failed) == offsetof(lz4hip_packed_info_t, first_failed) &&
               offsetof(PackedInfo, error) == offsetof(lz4hip_packed_info_t, error), "PackedInfo must mirror lz4hip_packed_info_t");
+// (the compact decode's record is written by the packed encode's info kernels)
+static_assert(sizeof(PackedInfo) == sizeof(lz4hip_compact_info_t) && offsetof(PackedInfo, blocks) == offsetof(lz4hip_compact_info_t, blocks) &&
+              offsetof(PackedInfo, packed_bytes) == offsetof(lz4hip_compact_info_t, decoded_bytes) &&
+              offsetof(PackedInfo, written_blocks) == offsetof(lz4hip_compact_info_t, written_blocks) &&
+              offsetof(PackedInfo, first_failed) == offsetof(lz4hip_compact_info_t, first_failed) &&
+              offsetof(PackedInfo, error) == offsetof(lz4hip_compact_info_t, error), "PackedInfo must mirror lz4hip_compact_info_t");
 
 #define LZ4HIP_FRAMING_TRY(expr) do { if (int rc_ = (expr)) return rc_; } while (0)
 
@@ -917,12 +925,14 @@ struct PackedPlan {
     uint8_t* dst; int64_t dst_cap; int64_t* dst_off; int32_t* packed_len; PackedInfo* info;
 };
 
-// Each round is a normal batch encode of its rows: the descriptor's array pointers are advanced here, on the host, its output is the
+// The rounds, for the packed encode and for the compact decode (lz4hip_compact.hpp) alike: `codec` runs the block encoder or decoder over
+// a round's descriptor, `sizes` is the kernel that turns its results into sizes under the codec's failure rule.
+// Each round is a normal batch encode (decode) of its rows: the descriptor's array pointers are advanced here, on the host, its output is the
 // ring, its capacities the round's array in scratch and its lengths the round's sanitised copy there (the encoders do not check a
 // length's sign: a negative one would send their literal copy before the slot).  Rounds follow each other in stream order: a round's pack has read the ring
 // before the next round's encoder writes it.
-template <class B>
-int encode_packed_run(B& be, const PackedPlan& p)
+template <class B, class Codec>
+int packed_rounds_run(B& be, const PackedPlan& p, Codec codec, void (*sizes)(PackedRound))
 {
     if (p.n == 0) {
         LZ4HIP_FRAMING_TRY(be.fill(p.dst_off, 0, sizeof(int64_t)));
@@ -948,8 +958,8 @@ int encode_packed_run(B& be, const PackedPlan& p)
         rb.src_len = b.src_len ? p.l.lens : nullptr; rb.src_len_all = b.src_len_all;      // (no negative length reaches the encoder)
         rb.dst = p.l.ring; rb.dst_stride = p.slot; rb.dst_cap = p.l.caps;
         rb.result = a.result; rb.n_blocks = a.cnt;
-        LZ4HIP_FRAMING_TRY(be.encode(&rb, p.mode));
-        be.launch(packed_sizes_kernel, stream_grid(a.cnt), kStreamThreads, a);
+        LZ4HIP_FRAMING_TRY(codec(&rb));
+        be.launch(sizes, stream_grid(a.cnt), kStreamThreads, a);
         launch_scan(be, a.offs, a.cnt, p.l.partial, p.l.state + kPackedTotal);
         be.launch(packed_rebase_kernel, stream_grid(a.cnt), kStreamThreads, a);
         PackedLayout layout = { a };
@@ -958,6 +968,12 @@ int encode_packed_run(B& be, const PackedPlan& p)
     }
     if (p.info) be.launch(packed_info_kernel, fixed_grid(1), 64, (const int64_t*)p.dst_off, p.n, p.dst_cap, (const int64_t*)p.l.state, p.info);
     return be.last_error();
+}
+
+template <class B>
+int encode_packed_run(B& be, const PackedPlan& p)
+{
+    return packed_rounds_run(be, p, [&](const lz4hip_batch_t* rb) { return be.encode(rb, p.mode); }, packed_sizes_kernel);
 }
 
 // reads b's src, src_off / src_stride, src_len / src_len_all, dst_cap / dst_cap_all (the slot width), result and n_blocks; b's dst,
@@ -1004,6 +1020,138 @@ int encode_packed(B& be, const lz4hip_batch_t* b, int mode, int64_t round_blocks
     PackedPlan p;
     LZ4HIP_FRAMING_TRY(encode_packed_plan(be, b, mode, round_blocks, dst, dst_cap, dst_off, packed_len, scratch, scratch_bytes, info, p));
     return encode_packed_run(be, p);
+}
+
+// ---- a block batch decoded into one packed buffer (lz4hip_compact.hpp) -------------------------------------------------------------------
+// The packed encode the other way: the same rounds through the same ring, tables and state block (packed_scratch), the block decoder
+// (unknown size) in the encoder's place and compact_sizes_kernel, whose failure rule is result < 0, in packed_sizes_kernel's.  The plan
+// is a PackedPlan whose mode is not looked at and whose packed_len is the caller's decoded_len.
+// 0 for an empty batch; LZ4HIP_E_ARGUMENT for a slot width or a round the call refuses
+inline int64_t decode_compact_scratch_bytes(int64_t n, int32_t slot_bytes, int64_t round_blocks)
+{
+    return encode_packed_scratch_bytes(n, slot_bytes, round_blocks);
+}
+
+// Each round is a normal unknown-size batch decode of its rows into the ring, dst_stride the slot: the decoders' dispatch rules see
+// the round's size.  They are handed the round's sanitised lengths, never the caller's.
+template <class B>
+int decode_compact_run(B& be, const PackedPlan& p)
+{
+    return packed_rounds_run(be, p, [&](const lz4hip_batch_t* rb) { return be.decode(rb, 0); }, compact_sizes_kernel);
+}
+
+// reads b's src, src_off / src_stride, src_len / src_len_all, dst_cap / dst_cap_all (the slot width), result and n_blocks; b's dst,
+// dst_off and dst_stride are ignored.  decoded_len and info may be NULL.
+// what the device call and the host call check alike: everything but the scratch, which only the device call is handed
+template <class B>
+int decode_compact_check(B& be, const lz4hip_batch_t* b, int64_t round_blocks, const void* dst, int64_t dst_cap, const int64_t* dst_off)
+{
+    if (!b) return be.fail(LZ4HIP_E_ARGUMENT, "decode compact: batch descriptor is NULL");
+    const int64_t n = b->n_blocks;
+    if (n < 0) return be.fail(LZ4HIP_E_ARGUMENT, "decode compact: n_blocks < 0");
+    if (dst_cap < 0 || round_blocks < 0) return be.fail(LZ4HIP_E_ARGUMENT, "decode compact: dst_cap < 0 or round_blocks < 0");
+    if (b->dst_cap_all <= 0) return be.fail(LZ4HIP_E_ARGUMENT, "decode compact: dst_cap_all (the slot width) must be > 0");
+    if (!dst_off) return be.fail(LZ4HIP_E_ARGUMENT, "decode compact: dst_off is NULL");
+    if (packed_round(n, round_blocks) > 0x7FFFFFFF) return be.fail(LZ4HIP_E_ARGUMENT, "decode compact: more than 2^31 - 1 blocks in a round");
+    if (n > 0) {
+        if (!b->src || (dst_cap > 0 && !dst)) return be.fail(LZ4HIP_E_ARGUMENT, "decode compact: src and dst must be non-NULL");
+        if (!b->src_len && b->src_len_all < 0) return be.fail(LZ4HIP_E_ARGUMENT, "decode compact: src_len_all < 0");
+    }
+    return 0;
+}
+
+template <class B>
+int decode_compact_plan(B& be, const lz4hip_batch_t* b, int64_t round_blocks, void* dst, int64_t dst_cap, int64_t* dst_off,
+                        int32_t* decoded_len, void* scratch, int64_t scratch_bytes, lz4hip_compact_info_t* info, PackedPlan& p)
+{
+    LZ4HIP_FRAMING_TRY(decode_compact_check(be, b, round_blocks, dst, dst_cap, dst_off));
+    const int64_t n = b->n_blocks;
+    if (scratch_bytes < decode_compact_scratch_bytes(n, b->dst_cap_all, round_blocks))
+        return be.fail(LZ4HIP_E_ARGUMENT, "decode compact: scratch_bytes < lz4hip_decode_compact_scratch_bytes");
+    if (n > 0 && !scratch) return be.fail(LZ4HIP_E_ARGUMENT, "decode compact: scratch must be non-NULL");
+    p.n = n; p.round = packed_round(n, round_blocks);
+    p.b = *b; p.mode = 0; p.limit = b->dst_cap_all; p.slot = packed_slot(b->dst_cap_all);
+    p.l = packed_scratch(scratch, n, b->dst_cap_all, round_blocks);
+    p.dst = (uint8_t*)dst; p.dst_cap = dst_cap; p.dst_off = dst_off; p.packed_len = decoded_len; p.info = (PackedInfo*)info;
+    return 0;
+}
+
+template <class B>
+int decode_compact(B& be, const lz4hip_batch_t* b, int64_t round_blocks, void* dst, int64_t dst_cap, int64_t* dst_off,
+                   int32_t* decoded_len, void* scratch, int64_t scratch_bytes, lz4hip_compact_info_t* info)
+{
+    PackedPlan p;
+    LZ4HIP_FRAMING_TRY(decode_compact_plan(be, b, round_blocks, dst, dst_cap, dst_off, decoded_len, scratch, scratch_bytes, info, p));
+    return decode_compact_run(be, p);
+}
+
+// ---- a legacy frame decoded in one call (lz4hip_compact.hpp) -------------------------------------------------------------------------------
+// The size field walk, then the compact decode over ALL max_chunks rows of the table -- slot and limit chunk_size, as the reference's
+// reader gives every chunk (original/lz4demo.c:276-300); the rows past the walk's count are empty blocks, which decode to nothing --
+// straight into dst, then the record.  Nothing is read on the host between the steps.
+// scratch: the index's table (its dst_off column receives the offsets, its result column the decoder's results), then the compact
+// decode's scratch for max_chunks rows
+struct FrameCompactScratch { FrameTables t; void* compact; int64_t compact_bytes; int64_t bytes; };
+inline FrameCompactScratch frame_compact_scratch(void* scratch, int32_t chunk, int64_t max_chunks, int64_t round_chunks)
+{
+    Carver c(scratch);
+    FrameCompactScratch l;
+    l.t = frame_tables(c, max_chunks);
+    l.compact = c.take_as<uint8_t>(0);
+    l.compact_bytes = packed_scratch(nullptr, max_chunks, chunk, round_chunks).bytes;
+    l.bytes = c.at + l.compact_bytes;
+    return l;
+}
+inline int64_t frame_decode_compact_scratch_bytes(int32_t chunk_size, int64_t max_chunks, int64_t round_chunks)
+{
+    if (!frame_chunk_valid(chunk_size) || max_chunks < 0 || round_chunks < 0) return LZ4HIP_E_ARGUMENT;
+    return frame_compact_scratch(nullptr, frame_chunk(chunk_size), max_chunks, round_chunks).bytes;
+}
+
+struct FrameCompactPlan { const uint8_t* src; int64_t src_len; int32_t chunk; FrameTables t; PackedPlan decode; FrameInfo* info; };
+
+template <class B>
+int frame_decode_compact_run(B& be, const FrameCompactPlan& p)
+{
+    const FrameTables& t = p.t;
+    if (t.max_chunks > 0) {
+        LZ4HIP_FRAMING_TRY(be.fill(t.src_off, 0, (size_t)(8 * t.max_chunks)));
+        LZ4HIP_FRAMING_TRY(be.fill(t.src_len, 0, (size_t)(4 * t.max_chunks)));
+    }
+    be.launch(frame_walk_kernel, fixed_grid(1), 64, p.src, p.src_len, (int64_t)frame_block_bound(p.chunk), t);
+    LZ4HIP_FRAMING_TRY(be.last_error());
+    LZ4HIP_FRAMING_TRY(decode_compact_run(be, p.decode));
+    if (t.max_chunks == 0) LZ4HIP_FRAMING_TRY(be.fill(p.decode.l.state + kPackedBad, 0xFF, 8));   // (no row: the decode left its state block alone)
+    be.launch(frame_compact_info_kernel, fixed_grid(1), 64, t, (const int64_t*)(p.decode.l.state + kPackedBad), p.info);
+    return be.last_error();
+}
+
+template <class B>
+int frame_decode_compact_plan(B& be, const void* src, int64_t src_len, int32_t chunk_size, int64_t max_chunks, int64_t round_chunks, void* scratch,
+                              int64_t scratch_bytes, void* dst, int64_t dst_cap, lz4hip_frame_info_t* info, FrameCompactPlan& p)
+{
+    if (src_len < 0 || max_chunks < 0 || round_chunks < 0 || dst_cap < 0 || !info || !scratch || (src_len > 0 && !src) || (dst_cap > 0 && !dst))
+        return be.fail(LZ4HIP_E_ARGUMENT, "frame decode compact: negative size or NULL pointer");
+    if (!frame_chunk_valid(chunk_size)) return be.fail(LZ4HIP_E_ARGUMENT, "frame decode compact: chunk_size must be 0 (8 MiB) or 1 .. 0x7E000000");
+    if (packed_round(max_chunks, round_chunks) > 0x7FFFFFFF) return be.fail(LZ4HIP_E_ARGUMENT, "frame decode compact: more than 2^31 - 1 table rows in a round");
+    p.chunk = frame_chunk(chunk_size);
+    const FrameCompactScratch l = frame_compact_scratch(scratch, p.chunk, max_chunks, round_chunks);
+    if (scratch_bytes < l.bytes) return be.fail(LZ4HIP_E_ARGUMENT, "frame decode compact: scratch_bytes < lz4hip_frame_decode_compact_scratch_bytes");
+    p.src = (const uint8_t*)src; p.src_len = src_len; p.t = l.t; p.info = (FrameInfo*)info;
+    // the table IS the batch: every row at its offset in the frame (an empty frame's rows are all empty: any address will do for them)
+    lz4hip_batch_t b = {};
+    b.src = src ? src : scratch; b.src_off = l.t.src_off; b.src_len = l.t.src_len;
+    b.dst_cap_all = p.chunk; b.result = l.t.result; b.n_blocks = max_chunks;
+    return decode_compact_plan(be, &b, round_chunks, dst, dst_cap, l.t.dst_off, nullptr, l.compact, l.compact_bytes, nullptr, p.decode);
+}
+
+template <class B>
+int frame_decode_compact(B& be, const void* src, int64_t src_len, int32_t chunk_size, int64_t max_chunks, int64_t round_chunks, void* scratch,
+                         int64_t scratch_bytes, void* dst, int64_t dst_cap, lz4hip_frame_info_t* info)
+{
+    FrameCompactPlan p;
+    LZ4HIP_FRAMING_TRY(frame_decode_compact_plan(be, src, src_len, chunk_size, max_chunks, round_chunks, scratch, scratch_bytes, dst, dst_cap, info, p));
+    return frame_decode_compact_run(be, p);
 }
 
 // ---- the host-pointer calls ------------------------------------------------------------------------------------------------------------

@@ -414,27 +414,21 @@ int decoded_sizes_host(B& be, const lz4hip_batch_t* hb, int64_t* dst_off, int32_
     return be.sync();                                                  // (also what keeps the gathered rows alive until the upload has read them)
 }
 
-// ---- a host-pointer batch encoded into one packed buffer ---------------------------------------------------------------------------------
-// lz4hip_encode_packed_host: the rows, strided or at offsets, are gathered back to back (the row work above, as decoded_sizes_host
-// does), staged with their offsets, lengths and limits in ONE device image of the framing backend B and encoded by the device call
-// (framing::encode_packed, whose argument checks run first: framing::encode_packed_check).  The info comes back first; then the
-// per-block arrays and only min(packed_bytes, dst_cap) bytes of output.  The image's output piece is min(dst_cap, the sum of the
-// per-block limits): no batch can take more, so a generous dst_cap costs no device memory.  A negative src_len[i] travels as it is --
-// the device sequence keeps it from the encoder and gives that block its LZ4HIP_E_ARGUMENT result -- and gathers no bytes.  info may
-// be NULL.
-template <class B>
-int encode_packed_host(B& be, const lz4hip_batch_t* hb, int mode, int64_t round_blocks, void* dst, int64_t dst_cap, int64_t* dst_off,
-                       int32_t* packed_len, lz4hip_packed_info_t* info, int threads_knob, const HostLimits& limits = HostLimits())
+// ---- a host-pointer batch encoded into, or decoded into, one packed buffer -------------------------------------------------------------------
+// lz4hip_encode_packed_host and lz4hip_decode_compact_host: the rows, strided or at offsets, are gathered back to back, once (the row work
+// above, as decoded_sizes_host does), staged with their offsets, lengths and limits in ONE device image of the framing backend B and
+// run through the device call (`device`: framing::encode_packed or framing::decode_compact on the image's batch, output, offsets, lengths,
+// scratch and info).  The info comes back first; then the per-block arrays and only min(the bytes the batch took, dst_cap) bytes of
+// output.  The image's output piece is min(dst_cap, the sum of the per-block limits): no batch can take more, so a generous dst_cap
+// costs no device memory.  A negative src_len[i] travels as it is -- the device sequence keeps it from the block codec and gives that
+// block its LZ4HIP_E_ARGUMENT result -- and gathers no bytes.  The batch has passed the call's argument checks and is not empty.
+// `total`: the info's count of those bytes.
+template <class B, class Info, class Device>
+int packed_host_run(B& be, const lz4hip_batch_t* hb, int64_t scratch_bytes, void* dst, int64_t dst_cap, int64_t* dst_off, int32_t* out_len,
+                    Info* info, int64_t Info::*total_bytes, const char* no_memory, int threads_knob, const HostLimits& limits, Device device)
 {
-    if (int rc = framing::encode_packed_check(be, hb, mode, round_blocks, dst, dst_cap, dst_off)) return rc;
     const int64_t n = hb->n_blocks;
-    lz4hip_packed_info_t h = {};
-    if (n == 0) {
-        dst_off[0] = 0;
-        h.first_failed = -1;
-        if (info) *info = h;
-        return 0;
-    }
+    Info h = {};
     std::vector<int64_t> at;
     std::vector<int32_t> lens;
     std::vector<uint8_t> rows;
@@ -447,7 +441,7 @@ int encode_packed_host(B& be, const lz4hip_batch_t* hb, int mode, int64_t round_
             at[(size_t)i] = total; lens[(size_t)i] = sl; total += sl > 0 ? sl : 0; most += cap;
         }
         rows.resize((size_t)total);
-    } catch (const std::bad_alloc&) { return be.fail(LZ4HIP_E_MEMORY, "encode packed: no host memory to gather the rows in"); }
+    } catch (const std::bad_alloc&) { return be.fail(LZ4HIP_E_MEMORY, no_memory); }
     uint8_t* const packed = rows.data();
     const int64_t* const at_p = at.data();
     const int32_t* const len_p = lens.data();
@@ -456,7 +450,6 @@ int encode_packed_host(B& be, const lz4hip_batch_t* hb, int mode, int64_t round_
     });
     // device image: [rows | offsets | lengths | limits | results | lengths out | output offsets | info | scratch | output]
     const int64_t out_bytes = dst_cap < most ? dst_cap : most;
-    const int64_t scratch_bytes = framing::encode_packed_scratch_bytes(n, hb->dst_cap_all, round_blocks);
     Carver c;
     c.take(total);
     const int64_t off_at = c.take(8 * n), len_at = c.take(4 * n), cap_at = c.take(4 * n), res_at = c.take(4 * n), plen_at = c.take(4 * n),
@@ -470,15 +463,57 @@ int encode_packed_host(B& be, const lz4hip_batch_t* hb, int mode, int64_t round_
     lz4hip_batch_t db = {};
     db.src = im.d; db.src_off = im.i64(off_at); db.src_len = im.i32(len_at); db.src_len_all = hb->src_len_all;      /* upper-bound hint */
     db.dst_cap = hb->dst_cap ? im.i32(cap_at) : nullptr; db.dst_cap_all = hb->dst_cap_all; db.result = im.i32(res_at); db.n_blocks = n;
-    if (int rc = framing::encode_packed(be, &db, mode, round_blocks, im.d + out_at, out_bytes, im.i64(doff_at), im.i32(plen_at), im.d + scratch_at,
-                                        scratch_bytes, (lz4hip_packed_info_t*)(im.d + info_at))) return rc;
+    if (int rc = device(&db, im.d + out_at, out_bytes, im.i64(doff_at), im.i32(plen_at), im.d + scratch_at, (Info*)(im.d + info_at))) return rc;
     if (int rc = im.download(&h, info_at, sizeof h)) return rc;
     if (int rc = be.sync()) return rc;                                 // (also what keeps the gathered rows alive until the upload has read them)
     if (info) *info = h;
     if (hb->result) if (int rc = im.download(hb->result, res_at, 4 * n)) return rc;
     if (int rc = im.download(dst_off, doff_at, 8 * (n + 1))) return rc;
-    if (packed_len) if (int rc = im.download(packed_len, plen_at, 4 * n)) return rc;
-    return im.download_encoded(dst, out_at, h.packed_bytes < out_bytes ? h.packed_bytes : out_bytes);
+    if (out_len) if (int rc = im.download(out_len, plen_at, 4 * n)) return rc;
+    return im.download_encoded(dst, out_at, h.*total_bytes < out_bytes ? h.*total_bytes : out_bytes);
+}
+
+// the argument checks are the device call's and run first (framing::encode_packed_check); info may be NULL
+template <class B>
+int encode_packed_host(B& be, const lz4hip_batch_t* hb, int mode, int64_t round_blocks, void* dst, int64_t dst_cap, int64_t* dst_off,
+                       int32_t* packed_len, lz4hip_packed_info_t* info, int threads_knob, const HostLimits& limits = HostLimits())
+{
+    if (int rc = framing::encode_packed_check(be, hb, mode, round_blocks, dst, dst_cap, dst_off)) return rc;
+    if (hb->n_blocks == 0) {
+        lz4hip_packed_info_t h = {};
+        dst_off[0] = 0;
+        h.first_failed = -1;
+        if (info) *info = h;
+        return 0;
+    }
+    const int64_t scratch_bytes = framing::encode_packed_scratch_bytes(hb->n_blocks, hb->dst_cap_all, round_blocks);
+    return packed_host_run(be, hb, scratch_bytes, dst, dst_cap, dst_off, packed_len, info, &lz4hip_packed_info_t::packed_bytes,
+                           "encode packed: no host memory to gather the rows in", threads_knob, limits,
+                           [&](const lz4hip_batch_t* db, uint8_t* out, int64_t out_bytes, int64_t* doff, int32_t* plen, uint8_t* scratch, lz4hip_packed_info_t* dinfo) {
+                               return framing::encode_packed(be, db, mode, round_blocks, out, out_bytes, doff, plen, scratch, scratch_bytes, dinfo);
+                           });
+}
+
+// lz4hip_decode_compact_host.  The caller has run the device call's argument checks (framing::decode_compact_check) before it looked
+// for a device; info may be NULL.
+template <class B>
+int decode_compact_host(B& be, const lz4hip_batch_t* hb, int64_t round_blocks, void* dst, int64_t dst_cap, int64_t* dst_off,
+                        int32_t* decoded_len, lz4hip_compact_info_t* info, int threads_knob, const HostLimits& limits = HostLimits())
+{
+    if (int rc = framing::decode_compact_check(be, hb, round_blocks, dst, dst_cap, dst_off)) return rc;
+    if (hb->n_blocks == 0) {
+        lz4hip_compact_info_t h = {};
+        dst_off[0] = 0;
+        h.first_failed = -1;
+        if (info) *info = h;
+        return 0;
+    }
+    const int64_t scratch_bytes = framing::decode_compact_scratch_bytes(hb->n_blocks, hb->dst_cap_all, round_blocks);
+    return packed_host_run(be, hb, scratch_bytes, dst, dst_cap, dst_off, decoded_len, info, &lz4hip_compact_info_t::decoded_bytes,
+                           "decode compact: no host memory to gather the rows in", threads_knob, limits,
+                           [&](const lz4hip_batch_t* db, uint8_t* out, int64_t out_bytes, int64_t* doff, int32_t* dlen, uint8_t* scratch, lz4hip_compact_info_t* dinfo) {
+                               return framing::decode_compact(be, db, round_blocks, out, out_bytes, doff, dlen, scratch, scratch_bytes, dinfo);
+                           });
 }
 
 // ---- the shards of the multi-device form -----------------------------------------------------------------------------------------------

@@ -180,6 +180,47 @@ def decompress_frame_device(t, chunk_size: int = CHUNK_SIZE):
         return out
 
 
+def decompress_frame_compact_device(t, chunk_size: int = CHUNK_SIZE, round_chunks: int = 0):
+    """decompress_frame for a 1-D uint8 CUDA tensor through lz4hip_frame_decode_compact_device, on torch's current stream: ONE call walks
+    the size fields, decodes every chunk with chunk_size bytes of room -- as the reference's reader does, so a chunk the two-call path of
+    decompress_frame_device refuses for breaking the format's end rules at its own size decodes here as it does there -- and packs the
+    chunks back to back; no chunk is sized before it is decoded.  The table is sized as decompress_frame_device sizes it.  The output
+    buffer is a guess the host can make without waiting: four times the frame, at most chunk_size per chunk the frame can hold; the
+    host reads the outcome once, and only a frame with more chunks than the table or more bytes than the guess is decoded again, into
+    the count and the size that record gave.  round_chunks = K > 0 decodes K chunks at a time through a ring of K chunk_size slots instead
+    of one slot per table row: less scratch, but the rounds do not overlap."""
+    import torch
+    from .stream import _check_device_bytes
+    t = _check_device_bytes(t, "t")
+    chunk_size = _check_chunk_size(chunk_size)
+    with torch.cuda.device(t.device):
+        L = _lib.lib()
+        dev = t.device
+        s = torch.cuda.current_stream(dev).cuda_stream
+        n = t.numel()
+        info_dev = torch.zeros(C.sizeof(_lib.FrameInfo), dtype=torch.uint8, device=dev)
+        max_chunks = n // chunk_size + 16
+        out_bytes = min(4 * n, min(max_chunks, n // 4) * chunk_size)           # (a chunk takes at least its 4-byte size field)
+        for _ in range(3):
+            need = _lib.check(L.lz4hip_frame_decode_compact_scratch_bytes(chunk_size, max_chunks, round_chunks))
+            scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+            out = torch.empty(out_bytes, dtype=torch.uint8, device=dev)
+            _lib.check(L.lz4hip_frame_decode_compact_device(t.data_ptr(), n, chunk_size, max_chunks, round_chunks, scratch.data_ptr(), need,
+                                                            out.data_ptr(), out_bytes, info_dev.data_ptr(), s))
+            info = _lib.FrameInfo.from_buffer_copy(info_dev.cpu().numpy().tobytes())
+            if info.error == _lib.FRAME_TABLE_FULL:
+                max_chunks = int(info.chunks)
+            elif info.decoded_bytes > out_bytes:
+                out_bytes = int(info.decoded_bytes)
+            else:
+                break
+        if info.error == _lib.FRAME_TABLE_FULL or info.decoded_bytes > out_bytes:
+            raise _lib.Lz4HipError("frame decode: the size field walk did not settle")
+        if info.error != _lib.FRAME_OK:
+            raise _frame_error(info.error, info.error_offset, n)
+        return out[:int(info.decoded_bytes)]
+
+
 def _host_bytes(data):
     if isinstance(data, np.ndarray):
         return np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
