@@ -164,6 +164,31 @@ int lz4hip_stream_decode_device(const void* src, const lz4hip_stream_info_t* inf
                                 void* scratch, int64_t scratch_bytes, void* dst, int64_t dst_cap,
                                 lz4hip_stream_info_t* info, void* stream);
 
+/* Decode in ONE call, with no value read on the host, into a buffer the caller already owns (a tensor of known shape, a cache page,
+ * an arena): the contract of lz4hip_frame_decode_compact_device.  The arguments are checked first, whatever the device --
+ * LZ4HIP_E_ARGUMENT for a negative size, NULL src with src_len > 0, NULL dst with dst_cap > 0, NULL info or scratch, too little
+ * scratch, more than 2^31 - 1 table rows -- and after that the call is launch-only on `stream`: nothing is read back and nothing is
+ * allocated, with the first-use exceptions of lz4hip_decode_batch_device.  written_bytes may be NULL; dst_cap is any value >= 0, and
+ * the call's cost follows the device-side end of the output, not dst_cap.
+ *
+ * The headers carry every chunk's decoded size, so the index already lays the output out: the index runs as above, the block decoder
+ * (known size) runs ONCE over all max_chunks rows of the table -- the rows past the stream's count are empty blocks -- and writes
+ * straight to dst.  With dst_cap >= the decoded size every output is what the two calls above write with the same max_chunks, byte
+ * for byte: dst[0, decoded_bytes) and *info, and *written_bytes (device) = decoded_bytes.  Otherwise the output is clipped at a chunk
+ * boundary: a chunk is written iff its end offset is <= dst_cap, *written_bytes is the end of the last such chunk (0 if none), no byte
+ * at or past it is written and the chunks that do not fit are not decoded; info.chunks, compressed_chunks and decoded_bytes are
+ * complete all the same, so dst_cap = 0 is a size query in one call.  A corrupt block is found only in a chunk that was written:
+ * *info is the index's, turned into LZ4HIP_STREAM_CORRUPT_BLOCK by the first corrupt block among the written chunks.  On
+ * LZ4HIP_STREAM_TABLE_FULL *info is the index's (chunks = the count needed), nothing is written to dst and *written_bytes = 0.
+ *
+ * max_chunks: size the table to the stream.  The decoder's choice between its wavefront and lane mappings goes by the table size, not
+ * by the stream's real chunk count: a table of 16 384 rows or more around 1 024 chunks of 1 MiB takes the lane mapping for them.
+ * scratch_bytes must be >= lz4hip_stream_decode_into_scratch_bytes(max_chunks). */
+int64_t lz4hip_stream_decode_into_scratch_bytes(int64_t max_chunks);
+int lz4hip_stream_decode_into_device(const void* src, int64_t src_len, int64_t max_chunks,
+                                     void* scratch, int64_t scratch_bytes, void* dst, int64_t dst_cap,
+                                     lz4hip_stream_info_t* info, int64_t* written_bytes, void* stream);
+
 /* Host-resident streams: stage the whole buffer through device memory (per-thread, grow-only, freed by lz4hip_release_workspaces),
  * run the device calls above and synchronise.  Encode returns 0 or LZ4HIP_E_* (dst_cap >= lz4hip_stream_bound); *dst_len on the host.
  * Decode returns info->error (0 or a positive LZ4HIP_STREAM_* code; the chunks before the error are in dst) or LZ4HIP_E_*; with
@@ -235,6 +260,20 @@ int lz4hip_unwrap_decode_device(const void* src, int64_t src_len, const int64_t*
                                 void* dst, int64_t dst_cap, const int64_t* dst_off, int32_t* status,
                                 lz4hip_unwrap_info_t* info, void* stream);
 
+/* Unwrap in ONE call, with no value read on the host, into a buffer the caller already owns: lz4hip_stream_decode_into_device for
+ * wrapped messages, with its contract and argument checks (n > 0 also needs src_off and status).  The index runs as above, the block
+ * decoder (known size) runs once over all n rows of the table and writes straight to dst.  With dst_cap >= the decoded size dst,
+ * dst_off, status and *info are what the two calls above write, byte for byte, and *written_messages (device, may be NULL) = n.
+ * Otherwise message i is written iff dst_off[i + 1] <= dst_cap: *written_messages is the length of that prefix, no byte at or past
+ * dst_off[*written_messages] is written and the other messages are not decoded; dst_off, the header statuses and
+ * info.decoded_bytes are complete all the same (dst_cap = 0: a size query in one call), and a corrupt block is found only in a
+ * message that was written.  scratch_bytes must be >= lz4hip_unwrap_into_scratch_bytes(n). */
+int64_t lz4hip_unwrap_into_scratch_bytes(int64_t n);
+int lz4hip_unwrap_into_device(const void* src, int64_t src_len, const int64_t* src_off, int64_t n,
+                              void* scratch, int64_t scratch_bytes, void* dst, int64_t dst_cap,
+                              int64_t* dst_off, int32_t* status,
+                              lz4hip_unwrap_info_t* info, int64_t* written_messages, void* stream);
+
 /* Host-resident batches (what a C# byte[][] caller binds): stage everything through device memory (per-thread, grow-only, freed by
  * lz4hip_release_workspaces), run the device calls above and synchronise; every pointer is host memory.
  * Wrap returns 0 or LZ4HIP_E_* (dst_cap >= lz4hip_wrap_bound).  Unwrap returns 0 when every message unwrapped, else info->error (a
@@ -302,6 +341,23 @@ int lz4hip_streams_decode_device(const void* src, int64_t src_len, const int64_t
                                  const lz4hip_streams_info_t* info_host, int64_t max_chunks, void* scratch, int64_t scratch_bytes,
                                  void* dst, int64_t dst_cap, const int64_t* dst_off, int32_t* status, int64_t* error_offset,
                                  lz4hip_streams_info_t* info, void* stream);
+
+/* Decode in ONE call, with no value read on the host, into a buffer the caller already owns: lz4hip_stream_decode_into_device for a
+ * batch of streams, with its contract and argument checks (n > 0 also needs src_off, status, error_offset and scratch; more than
+ * 2^31 - 1 items or table rows are refused).  The index runs as above, the block decoder (known size) runs once over all max_chunks
+ * rows of the table -- size it to the batch: the decoder's choice of mapping goes by the table size -- and writes straight to dst.
+ * With dst_cap >= the decoded size dst, dst_off, status, error_offset and *info are what the two calls above write with the same
+ * max_chunks, byte for byte, and *written_items (device, may be NULL) = n.  Otherwise item i is written iff dst_off[i + 1] <= dst_cap:
+ * *written_items is the length of that prefix, no byte at or past dst_off[*written_items] is written and the other items' chunks are
+ * not decoded; dst_off, the header statuses, error_offset and info.decoded_bytes are complete all the same (dst_cap = 0: a size
+ * query in one call), and a corrupt block is found only in an item that was written.  On LZ4HIP_STREAM_TABLE_FULL *info, dst_off,
+ * status and error_offset are the index's, nothing is written to dst and *written_items = 0.
+ * scratch_bytes must be >= lz4hip_streams_decode_into_scratch_bytes(n, max_chunks), which is 0 for an empty batch. */
+int64_t lz4hip_streams_decode_into_scratch_bytes(int64_t n, int64_t max_chunks);
+int lz4hip_streams_decode_into_device(const void* src, int64_t src_len, const int64_t* src_off, int64_t n, int64_t max_chunks,
+                                      void* scratch, int64_t scratch_bytes, void* dst, int64_t dst_cap,
+                                      int64_t* dst_off, int32_t* status, int64_t* error_offset,
+                                      lz4hip_streams_info_t* info, int64_t* written_items, void* stream);
 
 /* Host-resident batches (what a C# byte[][] caller binds): stage everything through device memory (per-thread, grow-only, freed by
  * lz4hip_release_workspaces), run the device calls above and synchronise; every pointer is host memory.

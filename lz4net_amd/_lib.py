@@ -109,6 +109,9 @@ SYMBOLS = [
     ("lz4hip_stream_encode_device", C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     ("lz4hip_stream_index_device", C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     ("lz4hip_stream_decode_device", C.c_int, [C.c_void_p, C.POINTER(StreamInfo), C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    ("lz4hip_stream_decode_into_scratch_bytes", C.c_int64, [C.c_int64]),
+    ("lz4hip_stream_decode_into_device", C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                                   C.c_void_p]),
     ("lz4hip_stream_encode_host", C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
     ("lz4hip_stream_decode_host", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(StreamInfo)]),
     ("lz4hip_wrap_bound", C.c_int64, [C.c_int64, C.c_int64]),
@@ -120,6 +123,9 @@ SYMBOLS = [
                                              C.c_void_p, C.c_void_p]),
     ("lz4hip_unwrap_decode_device", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(UnwrapInfo), C.c_void_p, C.c_int64,
                                               C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("lz4hip_unwrap_into_scratch_bytes", C.c_int64, [C.c_int64]),
+    ("lz4hip_unwrap_into_device", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("lz4hip_wrap_host", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     ("lz4hip_unwrap_host", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                      C.POINTER(UnwrapInfo)]),
@@ -132,6 +138,9 @@ SYMBOLS = [
                                               C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     ("lz4hip_streams_decode_device", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(StreamsInfo), C.c_int64, C.c_void_p, C.c_int64,
                                                C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("lz4hip_streams_decode_into_scratch_bytes", C.c_int64, [C.c_int64, C.c_int64]),
+    ("lz4hip_streams_decode_into_device", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("lz4hip_streams_encode_host", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
     ("lz4hip_streams_decode_host", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                              C.POINTER(StreamsInfo)]),

@@ -1566,6 +1566,18 @@ int lz4hip_stream_decode_device(const void* src, const lz4hip_stream_info_t* inf
     return stream_decode(be, src, info_host, max_chunks, scratch, scratch_bytes, dst, dst_cap, info);
 }
 
+int64_t lz4hip_stream_decode_into_scratch_bytes(int64_t max_chunks) { return stream_decode_into_scratch_bytes(max_chunks < 0 ? 0 : max_chunks); }
+
+int lz4hip_stream_decode_into_device(const void* src, int64_t src_len, int64_t max_chunks, void* scratch, int64_t scratch_bytes, void* dst,
+                                     int64_t dst_cap, lz4hip_stream_info_t* info, int64_t* written_bytes, void* stream)
+{
+    HipBackend be = { (hipStream_t)stream };
+    StreamIntoPlan p;
+    if (int rc = stream_decode_into_plan(be, src, src_len, max_chunks, scratch, scratch_bytes, dst, dst_cap, info, written_bytes, p)) return rc;
+    if (int rc = ensure_device()) return rc;
+    return stream_decode_into_run(be, p);
+}
+
 int lz4hip_stream_encode_host(const void* src, int64_t src_len, int32_t block_size, int mode, void* dst, int64_t dst_cap, int64_t* dst_len)
 {
     HipBackend be = {};
@@ -1612,6 +1624,19 @@ int lz4hip_unwrap_decode_device(const void* src, int64_t src_len, const int64_t*
     if (rc) return rc;
     HipBackend be = { (hipStream_t)stream };
     return unwrap_decode(be, src, src_len, src_off, n, info_host, scratch, scratch_bytes, dst, dst_cap, dst_off, status, info);
+}
+
+int64_t lz4hip_unwrap_into_scratch_bytes(int64_t n) { return unwrap_into_scratch_bytes(n < 0 ? 0 : n); }
+
+int lz4hip_unwrap_into_device(const void* src, int64_t src_len, const int64_t* src_off, int64_t n, void* scratch, int64_t scratch_bytes, void* dst,
+                              int64_t dst_cap, int64_t* dst_off, int32_t* status, lz4hip_unwrap_info_t* info, int64_t* written_messages,
+                              void* stream)
+{
+    HipBackend be = { (hipStream_t)stream };
+    UnwrapIntoPlan p;
+    if (int rc = unwrap_into_plan(be, src, src_len, src_off, n, scratch, scratch_bytes, dst, dst_cap, dst_off, status, info, written_messages, p)) return rc;
+    if (int rc = ensure_device()) return rc;
+    return unwrap_into_run(be, p);
 }
 
 int lz4hip_wrap_host(const void* src, int64_t src_len, const int64_t* src_off, int64_t n, int mode, void* dst, int64_t dst_cap,
@@ -1667,6 +1692,23 @@ int lz4hip_streams_decode_device(const void* src, int64_t src_len, const int64_t
     HipBackend be = { (hipStream_t)stream };
     return streams_decode(be, src, src_len, src_off, n, info_host, max_chunks, scratch, scratch_bytes, dst, dst_cap, dst_off, status, error_offset,
                           info);
+}
+
+int64_t lz4hip_streams_decode_into_scratch_bytes(int64_t n, int64_t max_chunks)
+{
+    return streams_decode_into_scratch_bytes(n, max_chunks < 0 ? 0 : max_chunks);
+}
+
+int lz4hip_streams_decode_into_device(const void* src, int64_t src_len, const int64_t* src_off, int64_t n, int64_t max_chunks, void* scratch,
+                                      int64_t scratch_bytes, void* dst, int64_t dst_cap, int64_t* dst_off, int32_t* status,
+                                      int64_t* error_offset, lz4hip_streams_info_t* info, int64_t* written_items, void* stream)
+{
+    HipBackend be = { (hipStream_t)stream };
+    StreamsIntoPlan p;
+    if (int rc = streams_decode_into_plan(be, src, src_len, src_off, n, max_chunks, scratch, scratch_bytes, dst, dst_cap, dst_off, status,
+                                          error_offset, info, written_items, p)) return rc;
+    if (int rc = ensure_device()) return rc;
+    return streams_decode_into_run(be, p);
 }
 
 int lz4hip_streams_encode_host(const void* src, int64_t src_len, const int64_t* src_off, int64_t n, int32_t block_size, int mode,

@@ -374,6 +374,81 @@ int stream_decode(B& be, const void* src, const lz4hip_stream_info_t* info_host,
     return stream_decode_run(be, (const uint8_t*)src, from_index, t, (uint8_t*)dst, (StreamInfo*)info);
 }
 
+// The one-call decode: the index's tables, then the decoder's own copy of the length and capacity columns.  The stand-in for a
+// written_bytes the caller left out is the second qword of the tables' first piece.
+struct StreamIntoScratch { StreamTables t; int32_t* s_src_len; int32_t* s_dst_cap; int64_t bytes; };
+inline StreamIntoScratch stream_into_scratch(void* scratch, int64_t max_chunks)
+{
+    Carver c(scratch);
+    StreamIntoScratch l;
+    l.t = stream_tables(c, max_chunks);
+    l.s_src_len = c.take_as<int32_t>(4 * max_chunks);
+    l.s_dst_cap = c.take_as<int32_t>(4 * max_chunks);
+    l.bytes = c.at;
+    return l;
+}
+inline int64_t stream_decode_into_scratch_bytes(int64_t max_chunks) { return stream_into_scratch(nullptr, max_chunks).bytes; }
+
+// `any`: an address for the rows of a decoder call that has no source or no output (all of them empty then)
+struct StreamIntoPlan { const uint8_t* src; int64_t src_len; StreamClip clip; uint8_t* dst; StreamInfo* info; uint8_t* any; };
+
+// The index as it is, then everything the two-call decode does, over ALL max_chunks rows and with the counts and the output's end taken
+// from the device.  The offset columns the decoder reads are zeroed first: a row past the count is an empty block at offset 0.
+template <class B>
+int stream_decode_into_run(B& be, const StreamIntoPlan& p)
+{
+    const StreamTables& t = p.clip.t;
+    LZ4HIP_FRAMING_TRY(be.fill(p.clip.written, 0, 8));
+    LZ4HIP_FRAMING_TRY(be.fill(t.min_bad, 0xFF, 8));                   // min_bad = none
+    if (t.max_chunks > 0) {
+        LZ4HIP_FRAMING_TRY(be.fill(t.c_src_off, 0, (size_t)(8 * t.max_chunks)));
+        LZ4HIP_FRAMING_TRY(be.fill(t.c_dst_off, 0, (size_t)(8 * t.max_chunks)));
+    }
+    LZ4HIP_FRAMING_TRY(stream_index_run(be, p.src, p.src_len, t, p.info));
+    if (t.max_chunks > 0) {
+        be.launch(stream_clip_kernel, stream_grid(t.max_chunks), kStreamThreads, p.clip, (const StreamInfo*)p.info);
+        LZ4HIP_FRAMING_TRY(be.last_error());
+        // AcquireNextChunk: Decode(..., knownOutputLength: true) -- the whole compressed table IS the batch
+        lz4hip_batch_t b = {};
+        b.src = p.src ? p.src : p.any; b.src_off = t.c_src_off; b.src_len = p.clip.s_src_len;
+        b.dst = p.dst ? p.dst : p.any; b.dst_off = t.c_dst_off; b.dst_cap = p.clip.s_dst_cap;
+        b.result = t.c_result; b.n_blocks = t.max_chunks;
+        LZ4HIP_FRAMING_TRY(be.decode(&b, 1));
+        const int64_t* counts = &p.info->chunks;
+        be.launch(stream_check_into_kernel, stream_grid(t.max_chunks), kStreamThreads, t, (const int32_t*)p.clip.s_dst_cap, counts);
+        RawLayout layout = { p.src, t, 0 };
+        const int64_t most = p.src_len < p.clip.dst_cap / 255 ? p.src_len * 255 : p.clip.dst_cap;   // (an LZ4 block grows 255 times at most)
+        be.launch(stream_raw_copy_into_kernel, copy_grid(most), kStreamThreads, layout, p.dst, counts, (const int64_t*)p.clip.written);
+        LZ4HIP_FRAMING_TRY(be.last_error());
+    }
+    be.launch(stream_info_finish_kernel, fixed_grid(1), 64, p.info, (const unsigned long long*)t.min_bad);
+    return be.last_error();
+}
+
+template <class B>
+int stream_decode_into_plan(B& be, const void* src, int64_t src_len, int64_t max_chunks, void* scratch, int64_t scratch_bytes, void* dst,
+                            int64_t dst_cap, lz4hip_stream_info_t* info, int64_t* written_bytes, StreamIntoPlan& p)
+{
+    if (src_len < 0 || max_chunks < 0 || dst_cap < 0 || !info || !scratch || (src_len > 0 && !src) || (dst_cap > 0 && !dst))
+        return be.fail(LZ4HIP_E_ARGUMENT, "stream decode into: negative size or NULL pointer");
+    if (max_chunks > 0x7FFFFFFF) return be.fail(LZ4HIP_E_ARGUMENT, "stream decode into: more than 2^31 - 1 table rows");
+    const StreamIntoScratch l = stream_into_scratch(scratch, max_chunks);
+    if (scratch_bytes < l.bytes) return be.fail(LZ4HIP_E_ARGUMENT, "stream decode into: scratch_bytes < lz4hip_stream_decode_into_scratch_bytes");
+    p.src = (const uint8_t*)src; p.src_len = src_len; p.dst = (uint8_t*)dst; p.info = (StreamInfo*)info; p.any = (uint8_t*)scratch;
+    p.clip.t = l.t; p.clip.s_src_len = l.s_src_len; p.clip.s_dst_cap = l.s_dst_cap; p.clip.dst_cap = dst_cap;
+    p.clip.written = written_bytes ? (unsigned long long*)written_bytes : l.t.min_bad + 1;
+    return 0;
+}
+
+template <class B>
+int stream_decode_into(B& be, const void* src, int64_t src_len, int64_t max_chunks, void* scratch, int64_t scratch_bytes, void* dst,
+                       int64_t dst_cap, lz4hip_stream_info_t* info, int64_t* written_bytes)
+{
+    StreamIntoPlan p;
+    LZ4HIP_FRAMING_TRY(stream_decode_into_plan(be, src, src_len, max_chunks, scratch, scratch_bytes, dst, dst_cap, info, written_bytes, p));
+    return stream_decode_into_run(be, p);
+}
+
 // ---- wrapped messages (lz4hip_wrap.hpp) ---------------------------------------------------------------------------------------------
 // a.comp and a.enc are the block encoder's to write: message i at a.off[i]
 template <class B>
@@ -482,6 +557,80 @@ int unwrap_decode(B& be, const void* src, int64_t src_len, const int64_t* src_of
     UnwrapInfo from_index;
     memcpy(&from_index, &h, sizeof from_index);
     return unwrap_decode_run(be, a, t, from_index, (uint8_t*)dst, (UnwrapInfo*)info);
+}
+
+// The one-call unwrap: the index's tables, then the decoder's own copy of the length and capacity columns.  The prefix's end, and the
+// stand-in for a written_messages the caller left out, are the third and fourth qword of the tables' first piece.
+struct UnwrapIntoScratch { UnwrapTables t; int32_t* s_src_len; int32_t* s_dst_cap; int64_t bytes; };
+inline UnwrapIntoScratch unwrap_into_scratch(void* scratch, int64_t n)
+{
+    Carver c(scratch);
+    UnwrapIntoScratch l;
+    l.t = unwrap_tables(c, n);
+    l.s_src_len = c.take_as<int32_t>(4 * n);
+    l.s_dst_cap = c.take_as<int32_t>(4 * n);
+    l.bytes = c.at;
+    return l;
+}
+inline int64_t unwrap_into_scratch_bytes(int64_t n) { return unwrap_into_scratch(nullptr, n).bytes; }
+
+struct UnwrapIntoPlan { UnwrapArgs a; UnwrapClip clip; uint8_t* dst; UnwrapInfo* info; uint8_t* any; };
+
+// The index as it is, then the two-call decode's steps over ALL n rows of the table, the count and the output's end taken from the device
+template <class B>
+int unwrap_into_run(B& be, const UnwrapIntoPlan& p)
+{
+    const UnwrapArgs& a = p.a;
+    const UnwrapTables& t = p.clip.t;
+    LZ4HIP_FRAMING_TRY(be.fill(p.clip.written_messages, 0, 8));
+    LZ4HIP_FRAMING_TRY(be.fill(p.clip.written_end, 0, 8));
+    if (a.n > 0) {
+        LZ4HIP_FRAMING_TRY(be.fill(t.c_src_off, 0, (size_t)(8 * a.n)));
+        LZ4HIP_FRAMING_TRY(be.fill(t.c_dst_off, 0, (size_t)(8 * a.n)));
+    }
+    LZ4HIP_FRAMING_TRY(unwrap_index_run(be, a, t, p.info));
+    if (a.n == 0) return 0;
+    be.launch(unwrap_clip_kernel, stream_grid(a.n), kStreamThreads, a, p.clip);
+    LZ4HIP_FRAMING_TRY(be.last_error());
+    // Unwrap: Decode(..., outputLength, knownOutputLength: true) -- the whole table IS the batch
+    lz4hip_batch_t b = {};
+    b.src = a.src ? a.src : p.any; b.src_off = t.c_src_off; b.src_len = p.clip.s_src_len;
+    b.dst = p.dst ? p.dst : p.any; b.dst_off = t.c_dst_off; b.dst_cap = p.clip.s_dst_cap;
+    b.result = t.c_result; b.n_blocks = a.n;
+    LZ4HIP_FRAMING_TRY(be.decode(&b, 1));
+    UnwrapRawLayout layout = { a, t };
+    const int64_t most = a.src_len < p.clip.dst_cap / 255 ? a.src_len * 255 : p.clip.dst_cap;     // (an LZ4 block grows 255 times at most)
+    be.launch(wrap_raw_copy_into_kernel, copy_grid(most), kStreamThreads, layout, p.dst, (const int64_t*)p.clip.written_end);
+    be.launch(unwrap_check_into_kernel, stream_grid(a.n), kStreamThreads, t, (const int32_t*)p.clip.s_dst_cap, a.status);
+    be.launch(unwrap_info_kernel, fixed_grid(1), 64, a, t, p.info);
+    return be.last_error();
+}
+
+template <class B>
+int unwrap_into_plan(B& be, const void* src, int64_t src_len, const int64_t* src_off, int64_t n, void* scratch, int64_t scratch_bytes, void* dst,
+                     int64_t dst_cap, int64_t* dst_off, int32_t* status, lz4hip_unwrap_info_t* info, int64_t* written_messages, UnwrapIntoPlan& p)
+{
+    if (src_len < 0 || n < 0 || dst_cap < 0 || !dst_off || !info || !scratch || (dst_cap > 0 && !dst))
+        return be.fail(LZ4HIP_E_ARGUMENT, "unwrap into: negative size or NULL pointer");
+    if (n > 0x7FFFFFFF) return be.fail(LZ4HIP_E_ARGUMENT, "unwrap into: more than 2^31 - 1 messages");
+    if (n > 0 && (!src_off || !status || (src_len > 0 && !src))) return be.fail(LZ4HIP_E_ARGUMENT, "unwrap into: NULL pointer");
+    const UnwrapIntoScratch l = unwrap_into_scratch(scratch, n);
+    if (scratch_bytes < l.bytes) return be.fail(LZ4HIP_E_ARGUMENT, "unwrap into: scratch_bytes < lz4hip_unwrap_into_scratch_bytes");
+    p.a = { (const uint8_t*)src, src_off, src_len, n, dst_off, status };
+    p.dst = (uint8_t*)dst; p.info = (UnwrapInfo*)info; p.any = (uint8_t*)scratch;
+    p.clip.t = l.t; p.clip.s_src_len = l.s_src_len; p.clip.s_dst_cap = l.s_dst_cap; p.clip.dst_cap = dst_cap;
+    p.clip.written_end = (int64_t*)l.t.min_bad + 2;
+    p.clip.written_messages = written_messages ? written_messages : (int64_t*)l.t.min_bad + 3;
+    return 0;
+}
+
+template <class B>
+int unwrap_into(B& be, const void* src, int64_t src_len, const int64_t* src_off, int64_t n, void* scratch, int64_t scratch_bytes, void* dst,
+                int64_t dst_cap, int64_t* dst_off, int32_t* status, lz4hip_unwrap_info_t* info, int64_t* written_messages)
+{
+    UnwrapIntoPlan p;
+    LZ4HIP_FRAMING_TRY(unwrap_into_plan(be, src, src_len, src_off, n, scratch, scratch_bytes, dst, dst_cap, dst_off, status, info, written_messages, p));
+    return unwrap_into_run(be, p);
 }
 
 // ---- batches of LZ4Stream buffers (lz4hip_streams.hpp) --------------------------------------------------------------------------------
@@ -626,6 +775,100 @@ int streams_decode(B& be, const void* src, int64_t src_len, const int64_t* src_o
     StreamsInfo from_index;
     memcpy(&from_index, &h, sizeof from_index);
     return streams_decode_run(be, a, t, from_index, (uint8_t*)dst, (StreamsInfo*)info);
+}
+
+// The one-call decode: the index's tables, then the decoder's own copy of the length and capacity columns.  The prefix's end, and the
+// stand-in for a written_items the caller left out, are the fourth and fifth qword of the tables' first piece.
+struct StreamsIntoScratch { StreamsTables t; int32_t* s_src_len; int32_t* s_dst_cap; int64_t bytes; };
+inline StreamsIntoScratch streams_into_scratch(void* scratch, int64_t n, int64_t max_chunks)
+{
+    Carver c(scratch);
+    StreamsIntoScratch l;
+    l.t = streams_tables(c, n, max_chunks);
+    l.s_src_len = c.take_as<int32_t>(4 * max_chunks);
+    l.s_dst_cap = c.take_as<int32_t>(4 * max_chunks);
+    l.bytes = c.at;
+    return l;
+}
+inline int64_t streams_decode_into_scratch_bytes(int64_t n, int64_t max_chunks)
+{
+    return n <= 0 ? 0 : streams_into_scratch(nullptr, n, max_chunks).bytes;       // (no item: the call touches no scratch)
+}
+
+// a.n == 0: only a.dst_off, info and written are looked at
+struct StreamsIntoPlan { StreamsDecodeArgs a; StreamsClip clip; uint8_t* dst; StreamsInfo* info; int64_t* written; uint8_t* any; };
+
+// The index as it is, then the two-call decode's steps over ALL max_chunks rows, the counts and the output's end taken from the device
+template <class B>
+int streams_decode_into_run(B& be, const StreamsIntoPlan& p)
+{
+    const StreamsDecodeArgs& a = p.a;
+    if (a.n == 0) {
+        LZ4HIP_FRAMING_TRY(be.fill(a.dst_off, 0, sizeof(int64_t)));
+        if (p.written) LZ4HIP_FRAMING_TRY(be.fill(p.written, 0, 8));
+        return streams_empty_info(be, p.info);
+    }
+    const StreamsTables& t = p.clip.t;
+    const int64_t rows = t.t.max_chunks;
+    LZ4HIP_FRAMING_TRY(be.fill(p.clip.written_items, 0, 8));
+    LZ4HIP_FRAMING_TRY(be.fill(p.clip.written_end, 0, 8));
+    if (rows > 0) {
+        LZ4HIP_FRAMING_TRY(be.fill(t.t.c_src_off, 0, (size_t)(8 * rows)));
+        LZ4HIP_FRAMING_TRY(be.fill(t.t.c_dst_off, 0, (size_t)(8 * rows)));
+    }
+    LZ4HIP_FRAMING_TRY(streams_index_run(be, a, t, p.info));
+    LZ4HIP_FRAMING_TRY(be.fill(t.t.min_bad, 0xFF, 8));
+    LZ4HIP_FRAMING_TRY(be.fill(t.item_bad, 0xFF, (size_t)(8 * a.n)));
+    be.launch(streams_clip_kernel, stream_grid(rows > a.n ? rows : a.n), kStreamThreads, a, p.clip);
+    LZ4HIP_FRAMING_TRY(be.last_error());
+    if (rows > 0) {
+        // AcquireNextChunk: Decode(..., knownOutputLength: true) -- the whole compressed table of all items IS the batch
+        lz4hip_batch_t b = {};
+        b.src = a.src ? a.src : p.any; b.src_off = t.t.c_src_off; b.src_len = p.clip.s_src_len;
+        b.dst = p.dst ? p.dst : p.any; b.dst_off = t.t.c_dst_off; b.dst_cap = p.clip.s_dst_cap;
+        b.result = t.t.c_result; b.n_blocks = rows;
+        LZ4HIP_FRAMING_TRY(be.decode(&b, 1));
+        be.launch(streams_check_into_kernel, stream_grid(rows), kStreamThreads, t, (const int32_t*)p.clip.s_dst_cap);
+        RawLayout layout = { a.src, t.t, 0 };
+        const int64_t most = a.src_len < p.clip.dst_cap / 255 ? a.src_len * 255 : p.clip.dst_cap;   // (an LZ4 block grows 255 times at most)
+        be.launch(stream_raw_copy_into_kernel, copy_grid(most), kStreamThreads, layout, p.dst, (const int64_t*)t.totals, (const int64_t*)p.clip.written_end);
+        LZ4HIP_FRAMING_TRY(be.last_error());
+    }
+    be.launch(streams_finish_kernel, stream_grid(a.n), kStreamThreads, a, t);
+    be.launch(streams_info_kernel, fixed_grid(1), 64, a, t, p.info);
+    return be.last_error();
+}
+
+template <class B>
+int streams_decode_into_plan(B& be, const void* src, int64_t src_len, const int64_t* src_off, int64_t n, int64_t max_chunks, void* scratch,
+                             int64_t scratch_bytes, void* dst, int64_t dst_cap, int64_t* dst_off, int32_t* status, int64_t* error_offset,
+                             lz4hip_streams_info_t* info, int64_t* written_items, StreamsIntoPlan& p)
+{
+    if (src_len < 0 || n < 0 || max_chunks < 0 || dst_cap < 0 || !dst_off || !info || (dst_cap > 0 && !dst))
+        return be.fail(LZ4HIP_E_ARGUMENT, "streams decode into: negative size or NULL pointer");
+    if (n > 0x7FFFFFFF || max_chunks > 0x7FFFFFFF) return be.fail(LZ4HIP_E_ARGUMENT, "streams decode into: more than 2^31 - 1 items or table rows");
+    if (n > 0 && (!src_off || !status || !error_offset || !scratch || (src_len > 0 && !src))) return be.fail(LZ4HIP_E_ARGUMENT, "streams decode into: NULL pointer");
+    if (scratch_bytes < streams_decode_into_scratch_bytes(n, max_chunks))
+        return be.fail(LZ4HIP_E_ARGUMENT, "streams decode into: scratch_bytes < lz4hip_streams_decode_into_scratch_bytes");
+    p.a = { (const uint8_t*)src, src_off, src_len, n, dst_off, status, error_offset };
+    p.dst = (uint8_t*)dst; p.info = (StreamsInfo*)info; p.written = written_items; p.any = (uint8_t*)scratch;
+    if (n == 0) return 0;
+    const StreamsIntoScratch l = streams_into_scratch(scratch, n, max_chunks);
+    p.clip.t = l.t; p.clip.s_src_len = l.s_src_len; p.clip.s_dst_cap = l.s_dst_cap; p.clip.dst_cap = dst_cap;
+    p.clip.written_end = (int64_t*)l.t.t.min_bad + 3;
+    p.clip.written_items = written_items ? written_items : (int64_t*)l.t.t.min_bad + 4;
+    return 0;
+}
+
+template <class B>
+int streams_decode_into(B& be, const void* src, int64_t src_len, const int64_t* src_off, int64_t n, int64_t max_chunks, void* scratch,
+                        int64_t scratch_bytes, void* dst, int64_t dst_cap, int64_t* dst_off, int32_t* status, int64_t* error_offset,
+                        lz4hip_streams_info_t* info, int64_t* written_items)
+{
+    StreamsIntoPlan p;
+    LZ4HIP_FRAMING_TRY(streams_decode_into_plan(be, src, src_len, src_off, n, max_chunks, scratch, scratch_bytes, dst, dst_cap, dst_off, status,
+                                                error_offset, info, written_items, p));
+    return streams_decode_into_run(be, p);
 }
 
 // ---- legacy frames (lz4hip_frame.hpp) ----------------------------------------------------------------------------------------------------

@@ -413,4 +413,69 @@ __global__ void __launch_bounds__(64) stream_info_finish_kernel(StreamInfo* info
     if (threadIdx.x == 0 && *min_bad != ~0ull) { info->error = kStreamCorruptBlock; info->error_offset = (int64_t)*min_bad; }
 }
 
+// ---- decode in one call, into a buffer of any capacity ------------------------------------------------------------------------
+// Nothing of the index is read on the host: the decoder runs over ALL max_chunks rows of the compressed table, and what the two-call
+// decode took from the host's copy of the info -- the counts, the end of the output -- these kernels read on the device.  The output
+// offsets are monotone, so the chunks that fit dst_cap are a prefix of the stream; the decoder is handed a copy of the length and
+// capacity columns in which every other row (past the count, clipped, or all of them on TABLE_FULL) is an empty block of capacity 0.
+// The table's own columns stay: the check compares against them.
+struct StreamClip {
+    StreamTables t;
+    int32_t* s_src_len; int32_t* s_dst_cap;                            // the decoder's columns, max_chunks rows
+    int64_t dst_cap;
+    unsigned long long* written;                                       // end of the last chunk that fits, 0 before the launch
+};
+
+// `counts`: [non-empty chunks, compressed chunks] as the index left them (a StreamInfo's first fields); `full`: TABLE_FULL
+LZ4HIP_DEVICE void stream_clip_counts(const int64_t* counts, bool full, int64_t max_chunks, int64_t& ncomp, int64_t& nraw)
+{
+    ncomp = full ? 0 : counts[1];
+    nraw = full ? 0 : counts[0] - counts[1];
+    if (ncomp > max_chunks) ncomp = max_chunks;                        // (never, for an index's counts: no row outside the table is read)
+    if (nraw > max_chunks) nraw = max_chunks;
+    if (ncomp < 0) ncomp = 0;
+    if (nraw < 0) nraw = 0;
+}
+
+__global__ void __launch_bounds__(kStreamThreads) stream_clip_kernel(StreamClip c, const StreamInfo* info)
+{
+    int64_t ncomp, nraw;
+    stream_clip_counts(&info->chunks, info->error == kStreamTableFull, c.t.max_chunks, ncomp, nraw);
+    for (int64_t i = (int64_t)blockIdx.x * kStreamThreads + threadIdx.x; i < c.t.max_chunks; i += (int64_t)gridDim.x * kStreamThreads) {
+        // the last row of either table that fits speaks for its table (the offsets do not decrease): two atomics a call at most
+        int32_t len = 0, cap = 0;
+        if (i < ncomp) {
+            const int64_t end = c.t.c_dst_off[i] + c.t.c_dst_cap[i];
+            if (end <= c.dst_cap) {
+                len = c.t.c_src_len[i]; cap = c.t.c_dst_cap[i];
+                if (i + 1 == ncomp || c.t.c_dst_off[i + 1] + c.t.c_dst_cap[i + 1] > c.dst_cap) atomicMax(c.written, (unsigned long long)end);
+            }
+        }
+        c.s_src_len[i] = len;
+        c.s_dst_cap[i] = cap;
+        if (i < nraw) {
+            const int64_t end = c.t.r_dst_off[i] + c.t.r_len[i];
+            if (end <= c.dst_cap && (i + 1 == nraw || c.t.r_dst_off[i + 1] + c.t.r_len[i + 1] > c.dst_cap)) atomicMax(c.written, (unsigned long long)end);
+        }
+    }
+}
+
+// the raw chunks that start before *end: a chunk that does not fit starts at *end or later, so the copy clips at a chunk boundary
+__global__ void __launch_bounds__(kStreamThreads) stream_raw_copy_into_kernel(RawLayout L, uint8_t* dst, const int64_t* counts, const int64_t* end)
+{
+    const int64_t to = *end;
+    int64_t ncomp;
+    stream_clip_counts(counts, to <= 0, L.t.max_chunks, ncomp, L.n);
+    if (L.n > 0) copy_spans(L, dst, to);
+}
+
+// stream_check_kernel over the rows the decoder was given (a chunk in the table has original > 0: capacity 0 means clipped)
+__global__ void __launch_bounds__(kStreamThreads) stream_check_into_kernel(StreamTables t, const int32_t* s_dst_cap, const int64_t* counts)
+{
+    int64_t ncomp, nraw;
+    stream_clip_counts(counts, false, t.max_chunks, ncomp, nraw);
+    for (int64_t i = (int64_t)blockIdx.x * kStreamThreads + threadIdx.x; i < ncomp; i += (int64_t)gridDim.x * kStreamThreads)
+        if (s_dst_cap[i] != 0 && t.c_result[i] != t.c_src_len[i]) atomicMin(t.min_bad, (unsigned long long)t.c_hdr_off[i]);
+}
+
 }  // namespace lz4hip

@@ -248,6 +248,45 @@ __global__ void __launch_bounds__(64) streams_info_kernel(StreamsDecodeArgs a, S
     *info = r;
 }
 
+// ---- decode in one call, into a buffer of any capacity (see lz4hip_stream.hpp) ---------------------------------------------------
+// The items that fit dst_cap are a prefix of the batch: item i is written iff dst_off[i + 1] <= dst_cap.
+struct StreamsClip {
+    StreamsTables t;
+    int32_t* s_src_len; int32_t* s_dst_cap;                            // the decoder's columns, max_chunks rows
+    int64_t dst_cap;
+    int64_t* written_items; int64_t* written_end;                      // the prefix's length and dst_off[that]; both 0 before the launch
+};
+
+__global__ void __launch_bounds__(kStreamThreads) streams_clip_kernel(StreamsDecodeArgs a, StreamsClip c)
+{
+    const int64_t rows = c.t.t.max_chunks, most = rows > a.n ? rows : a.n;
+    const bool full = c.t.totals[0] > rows;
+    int64_t ncomp, nraw;
+    stream_clip_counts(c.t.totals, full, rows, ncomp, nraw);
+    for (int64_t i = (int64_t)blockIdx.x * kStreamThreads + threadIdx.x; i < most; i += (int64_t)gridDim.x * kStreamThreads) {
+        if (i < rows) {
+            int32_t len = 0, cap = 0;
+            if (i < ncomp && a.dst_off[c.t.c_item[i] + 1] <= c.dst_cap) { len = c.t.t.c_src_len[i]; cap = c.t.t.c_dst_cap[i]; }
+            c.s_src_len[i] = len;
+            c.s_dst_cap[i] = cap;
+        }
+        // the last item that fits: the offsets do not decrease, so there is one such item at most
+        if (!full && i < a.n && a.dst_off[i + 1] <= c.dst_cap && (i + 1 == a.n || a.dst_off[i + 2] > c.dst_cap)) {
+            *c.written_items = i + 1;
+            *c.written_end = a.dst_off[i + 1];
+        }
+    }
+}
+
+// streams_check_kernel over the rows the decoder was given
+__global__ void __launch_bounds__(kStreamThreads) streams_check_into_kernel(StreamsTables t, const int32_t* s_dst_cap)
+{
+    int64_t ncomp, nraw;
+    stream_clip_counts(t.totals, t.totals[0] > t.t.max_chunks, t.t.max_chunks, ncomp, nraw);
+    for (int64_t j = (int64_t)blockIdx.x * kStreamThreads + threadIdx.x; j < ncomp; j += (int64_t)gridDim.x * kStreamThreads)
+        if (s_dst_cap[j] != 0 && t.t.c_result[j] != t.t.c_src_len[j]) atomicMin(&t.item_bad[t.c_item[j]], (unsigned long long)t.t.c_hdr_off[j]);
+}
+
 // the info of a batch without items (no table to read it from)
 __global__ void streams_empty_info_kernel(StreamsInfo* info)
 {

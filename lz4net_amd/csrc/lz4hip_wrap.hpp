@@ -232,6 +232,53 @@ __global__ void __launch_bounds__(kStreamThreads) unwrap_check_kernel(UnwrapTabl
         }
 }
 
+// ---- unwrap in one call, into a buffer of any capacity (see lz4hip_stream.hpp) ---------------------------------------------------
+// The messages that fit dst_cap are a prefix of the batch: message i is written iff dst_off[i + 1] <= dst_cap.  The decoder runs over
+// all n rows of the table with a copy of its length and capacity columns in which the rows past the count and the clipped ones are
+// empty blocks of capacity 0 (a compressed message decodes to at least one byte: capacity 0 means "not given to the decoder").
+struct UnwrapClip {
+    UnwrapTables t;
+    int32_t* s_src_len; int32_t* s_dst_cap;                            // the decoder's columns, n rows
+    int64_t dst_cap;
+    int64_t* written_messages; int64_t* written_end;                   // the prefix's length and dst_off[that]; both 0 before the launch
+};
+
+__global__ void __launch_bounds__(kStreamThreads) unwrap_clip_kernel(UnwrapArgs a, UnwrapClip c)
+{
+    int64_t ncomp = *c.t.ncomp;
+    if (ncomp > a.n) ncomp = a.n;
+    for (int64_t i = (int64_t)blockIdx.x * kStreamThreads + threadIdx.x; i < a.n; i += (int64_t)gridDim.x * kStreamThreads) {
+        int32_t len = 0, cap = 0;
+        if (i < ncomp && a.dst_off[c.t.c_msg[i] + 1] <= c.dst_cap) { len = c.t.c_src_len[i]; cap = c.t.c_dst_cap[i]; }
+        c.s_src_len[i] = len;
+        c.s_dst_cap[i] = cap;
+        // the last message that fits: the offsets do not decrease, so there is one such message at most
+        if (a.dst_off[i + 1] <= c.dst_cap && (i + 1 == a.n || a.dst_off[i + 2] > c.dst_cap)) {
+            *c.written_messages = i + 1;
+            *c.written_end = a.dst_off[i + 1];
+        }
+    }
+}
+
+// a message that does not fit starts at *end or later, so the copy clips at a message boundary
+__global__ void __launch_bounds__(kStreamThreads) wrap_raw_copy_into_kernel(UnwrapRawLayout L, uint8_t* dst, const int64_t* end)
+{
+    const int64_t to = *end;
+    if (to > 0) copy_spans(L, dst, to);
+}
+
+// unwrap_check_kernel over the rows the decoder was given
+__global__ void __launch_bounds__(kStreamThreads) unwrap_check_into_kernel(UnwrapTables t, const int32_t* s_dst_cap, int32_t* status)
+{
+    int64_t ncomp = *t.ncomp;
+    if (ncomp > t.n) ncomp = t.n;
+    for (int64_t j = (int64_t)blockIdx.x * kStreamThreads + threadIdx.x; j < ncomp; j += (int64_t)gridDim.x * kStreamThreads)
+        if (s_dst_cap[j] != 0 && t.c_result[j] != t.c_src_len[j]) {
+            status[t.c_msg[j]] = kWrapCorruptBlock;
+            atomicMin(t.min_bad, (unsigned long long)t.c_msg[j]);
+        }
+}
+
 // info from the tables: the counts, and the lowest failing message with its status (what a sequential Unwrap loop raises first)
 __global__ void __launch_bounds__(64) unwrap_info_kernel(UnwrapArgs a, UnwrapTables t, UnwrapInfo* info)
 {

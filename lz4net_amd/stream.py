@@ -233,6 +233,61 @@ def _decompress_stream_device(t):
     return out
 
 
+def _check_out(out, like):
+    import torch
+    if not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != torch.uint8 or out.dim() != 1 or not out.is_contiguous():
+        raise ArgumentException("out must be a contiguous 1-D uint8 CUDA tensor")
+    if out.device != like.device:
+        raise ArgumentException("out must be on the source's device")
+    return out
+
+
+def _read_info(info, cls):
+    """the one place that waits for the device: the info record a *_into call left there, as its ctypes struct"""
+    return cls.from_buffer_copy(info.cpu().numpy().tobytes())
+
+
+def decompress_stream_into(t, out, max_chunks=None, block_size: int = DEFAULT_BLOCK_SIZE):
+    """decompress_stream for a 1-D uint8 CUDA tensor, into a tensor the caller already owns, in ONE device call on torch's current
+    stream, without waiting for the device -> (info, written): device tensors holding the lz4hip_stream_info_t record (read it with
+    read_stream_info, check it with check_stream_into) and the int64 count of bytes written.  The output is clipped at a chunk boundary
+    when `out` is too small; info.decoded_bytes is the size needed all the same.  max_chunks is the chunk table's size: by default
+    out.numel() // max(16, block_size) + 16, which holds anything compress_stream_device wrote into `out`'s size with that block size."""
+    import torch
+    t = _check_device_bytes(t, "t")
+    out = _check_out(out, t)
+    if max_chunks is None:
+        max_chunks = out.numel() // max(16, int(block_size)) + 16
+    with torch.cuda.device(t.device):
+        L = _lib.lib()
+        dev = t.device
+        info = torch.zeros(C.sizeof(_lib.StreamInfo), dtype=torch.uint8, device=dev)
+        written = torch.zeros(1, dtype=torch.int64, device=dev)
+        scratch = torch.empty(L.lz4hip_stream_decode_into_scratch_bytes(max_chunks), dtype=torch.uint8, device=dev)
+        _lib.check(L.lz4hip_stream_decode_into_device(t.data_ptr(), t.numel(), max_chunks, scratch.data_ptr(), scratch.numel(), out.data_ptr(),
+                                                      out.numel(), info.data_ptr(), written.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+        return info, written
+
+
+def read_stream_info(info):
+    """the lz4hip_stream_info_t a decompress_stream_into call left on the device (waits for the device)"""
+    return _read_info(info, _lib.StreamInfo)
+
+
+def check_stream_into(info, written):
+    """Waits for a decompress_stream_into call and raises what decompress_stream_device raises for its outcome (.error_offset = the
+    failing header's offset), an Lz4HipError naming the chunk count for a table that was too small, an ArgumentException when `out` was
+    too small for the stream.  Returns the info record."""
+    h = read_stream_info(info)
+    if h.error == _lib.STREAM_TABLE_FULL:
+        raise _lib.Lz4HipError(f"stream decode: the chunk table is too small, the stream has {h.chunks} chunks (max_chunks)")
+    if h.error != _lib.STREAM_OK:
+        raise _stream_error(h)
+    if int(written.item()) < h.decoded_bytes:
+        raise ArgumentException(f"out is too small: the stream decodes to {h.decoded_bytes} bytes")
+    return h
+
+
 # ---- batches of streams (lz4hip_streams_* of include/lz4hip.h; kernels in csrc/lz4hip_streams.hpp) ---------------------------------
 # A batch of n streams is one 1-D uint8 buffer plus int64 offsets[n + 1]: item i is buf[offsets[i]:offsets[i + 1]].  compress_streams_*
 # returns the framed streams in that layout and decompress_streams_* reads it, so one's output is the other's input.
@@ -334,6 +389,53 @@ def decompress_streams_device(packed, offsets, check: bool = True):
         if info.first_error >= 0:
             raise streams_error(info.error, info.first_error, info.error_offset)
         return out, out_off
+
+
+def decompress_streams_into(packed, offsets, out, max_chunks=None, block_size: int = DEFAULT_BLOCK_SIZE):
+    """decompress_streams_device into a tensor the caller already owns, in ONE device call on torch's current stream, without waiting
+    for the device -> (out_off, status, error_offset, info, written_items), all device tensors: item i is out[out_off[i]:out_off[i + 1]],
+    status and error_offset are per item, info holds the lz4hip_streams_info_t record (read_streams_info, check_streams_into) and
+    written_items the int64 count of leading items that fit `out`; the others are not written, and out_off and info.decoded_bytes are
+    complete all the same.  max_chunks is the chunk table's size for the whole batch: by default out.numel() // block + n + 16."""
+    import torch
+    packed, offsets = _check_device_batch(packed, offsets)
+    out = _check_out(out, packed)
+    n = offsets.numel() - 1
+    if max_chunks is None:
+        max_chunks = out.numel() // max(16, int(block_size)) + n + 16
+    with torch.cuda.device(packed.device):
+        L = _lib.lib()
+        dev = packed.device
+        out_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        status = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+        err_off = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
+        info = torch.zeros(C.sizeof(_lib.StreamsInfo), dtype=torch.uint8, device=dev)
+        written = torch.zeros(1, dtype=torch.int64, device=dev)
+        scratch = torch.empty(L.lz4hip_streams_decode_into_scratch_bytes(n, max_chunks), dtype=torch.uint8, device=dev)
+        _lib.check(L.lz4hip_streams_decode_into_device(packed.data_ptr(), packed.numel(), offsets.data_ptr(), n, max_chunks, scratch.data_ptr(),
+                                                       scratch.numel(), out.data_ptr(), out.numel(), out_off.data_ptr(), status.data_ptr(),
+                                                       err_off.data_ptr(), info.data_ptr(), written.data_ptr(),
+                                                       torch.cuda.current_stream(dev).cuda_stream))
+        return out_off, status[:n], err_off[:n], info, written
+
+
+def read_streams_info(info):
+    """the lz4hip_streams_info_t a decompress_streams_into call left on the device (waits for the device)"""
+    return _read_info(info, _lib.StreamsInfo)
+
+
+def check_streams_into(info, written_items):
+    """Waits for a decompress_streams_into call and raises what decompress_streams_device(check=True) raises for its outcome
+    (.item_index, .error_offset), an Lz4HipError naming the chunk count for a table that was too small, an ArgumentException when
+    `out` was too small for the batch.  Returns the info record."""
+    h = read_streams_info(info)
+    if h.error == _lib.STREAM_TABLE_FULL:
+        raise _lib.Lz4HipError(f"streams decode: the chunk table is too small, the batch has {h.chunks} chunks (max_chunks)")
+    if h.first_error >= 0:
+        raise streams_error(h.error, h.first_error, h.error_offset)
+    if int(written_items.item()) < h.items:
+        raise ArgumentException(f"out is too small: the batch decodes to {h.decoded_bytes} bytes")
+    return h
 
 
 def _check_host_batch(buf, offsets):

@@ -13,7 +13,7 @@ import numpy as np
 
 from . import _lib
 from .codec import _CORRUPT, ArgumentException
-from .stream import _check_device_batch, _check_host_batch
+from .stream import _check_device_batch, _check_host_batch, _check_out, _read_info
 
 _WRAP_INVALID = "inputBuffer size of inputLength is invalid"
 _MESSAGES = {
@@ -91,6 +91,45 @@ def unwrap_device(packed, offsets, check: bool = True):
         if info.first_error >= 0:
             raise unwrap_error(info.error, info.first_error)
         return out, out_off
+
+
+def unwrap_into(packed, offsets, out):
+    """unwrap_device into a tensor the caller already owns, in ONE device call on torch's current stream, without waiting for the
+    device -> (out_off, status, info, written_messages), all device tensors: message i is out[out_off[i]:out_off[i + 1]], status is
+    per message, info holds the lz4hip_unwrap_info_t record (read_unwrap_info, check_unwrap_into) and written_messages the int64 count
+    of leading messages that fit `out`; the others are not written, and out_off and info.decoded_bytes are complete all the same."""
+    import torch
+    packed, offsets = _check_device_batch(packed, offsets)
+    out = _check_out(out, packed)
+    with torch.cuda.device(packed.device):
+        L = _lib.lib()
+        dev = packed.device
+        n = offsets.numel() - 1
+        out_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        status = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+        info = torch.zeros(C.sizeof(_lib.UnwrapInfo), dtype=torch.uint8, device=dev)
+        written = torch.zeros(1, dtype=torch.int64, device=dev)
+        scratch = torch.empty(L.lz4hip_unwrap_into_scratch_bytes(n), dtype=torch.uint8, device=dev)
+        _lib.check(L.lz4hip_unwrap_into_device(packed.data_ptr(), packed.numel(), offsets.data_ptr(), n, scratch.data_ptr(), scratch.numel(),
+                                               out.data_ptr(), out.numel(), out_off.data_ptr(), status.data_ptr(), info.data_ptr(),
+                                               written.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+        return out_off, status[:n], info, written
+
+
+def read_unwrap_info(info):
+    """the lz4hip_unwrap_info_t an unwrap_into call left on the device (waits for the device)"""
+    return _read_info(info, _lib.UnwrapInfo)
+
+
+def check_unwrap_into(info, written_messages):
+    """Waits for an unwrap_into call and raises what unwrap_device(check=True) raises for its outcome (.message_index), an
+    ArgumentException when `out` was too small for the batch.  Returns the info record."""
+    h = read_unwrap_info(info)
+    if h.first_error >= 0:
+        raise unwrap_error(h.error, h.first_error)
+    if int(written_messages.item()) < h.messages:
+        raise ArgumentException(f"out is too small: the batch unwraps to {h.decoded_bytes} bytes")
+    return h
 
 
 # ---- host-resident batches (numpy; the lz4hip_wrap_host / lz4hip_unwrap_host pair) -----------------------------------------------
