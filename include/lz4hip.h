@@ -189,6 +189,21 @@ int lz4hip_stream_decode_into_device(const void* src, int64_t src_len, int64_t m
                                      void* scratch, int64_t scratch_bytes, void* dst, int64_t dst_cap,
                                      lz4hip_stream_info_t* info, int64_t* written_bytes, void* stream);
 
+/* The chunk directory of ONE stream, for a stream that is decoded more than once or in parts: the index's header walk (one wavefront,
+ * one dependent round trip per chunk -- latency-bound by design, and the point is that it runs once per stream) with its result
+ * kept.  The arguments are checked first, whatever the device; then the call is launch-only on `stream` and takes no scratch: it writes
+ * straight to the caller's device arrays hdr_off and out_off of max_chunks + 1 entries each.  For every non-empty chunk k before the
+ * first header error hdr_off[k] is the offset of its header and out_off[k] its decoded offset; the closing entry hdr_off[chunks] is
+ * the offset at which the walk ended (src_len for a clean stream, else error_offset) and out_off[chunks] = decoded_bytes.  *info
+ * (device) is what lz4hip_stream_index_device reports, with its stop rules and error codes.  With more chunks than max_chunks
+ * info.error = LZ4HIP_STREAM_TABLE_FULL and info.chunks is the count needed: entries [0, max_chunks) are valid and the closing entry is
+ * not written.
+ * A stream is the concatenation of its chunks and each chunk a valid one-chunk stream: src[hdr_off[k], hdr_off[k + 1]) is chunk k plus
+ * the empty chunks' headers behind it, an item of lz4hip_streams_decode_spans_into_device, in which every chunk's header is read by a
+ * wavefront of its own.  Chunks k0 .. k1 as such spans decode to bytes [out_off[k0], out_off[k1 + 1]) of the stream. */
+int lz4hip_stream_directory_device(const void* src, int64_t src_len, int64_t max_chunks,
+                                   int64_t* hdr_off, int64_t* out_off, lz4hip_stream_info_t* info, void* stream);
+
 /* Host-resident streams: stage the whole buffer through device memory (per-thread, grow-only, freed by lz4hip_release_workspaces),
  * run the device calls above and synchronise.  Encode returns 0 or LZ4HIP_E_* (dst_cap >= lz4hip_stream_bound); *dst_len on the host.
  * Decode returns info->error (0 or a positive LZ4HIP_STREAM_* code; the chunks before the error are in dst) or LZ4HIP_E_*; with
@@ -274,6 +289,26 @@ int lz4hip_unwrap_into_device(const void* src, int64_t src_len, const int64_t* s
                               int64_t* dst_off, int32_t* status,
                               lz4hip_unwrap_info_t* info, int64_t* written_messages, void* stream);
 
+/* Unwrap CHOSEN messages of an arena in one call: lz4hip_unwrap_into_device with m spans in the place of n consecutive messages.
+ * Message j of the call is src[src_begin[j], src_end[j]) (device arrays of m entries); the spans may come in any order, repeat,
+ * overlap and leave holes -- the source is only read -- so the cost follows m, not the arena.  Everything else is the contract of
+ * lz4hip_unwrap_into_device with m for n: the argument checks (m > 0 also needs src_begin, src_end and status), launch-only, scratch
+ * of lz4hip_unwrap_into_scratch_bytes(m); dst_off[m + 1] and status[m] are indexed by CALL position, info.first_error is the lowest
+ * failing call position, and dst_cap clips a prefix in call order (message j is written iff dst_off[j + 1] <= dst_cap; dst_cap = 0
+ * is the size query).  A span with begin < 0, end < begin, end > src_len or longer than INT32_MAX gets LZ4HIP_E_ARGUMENT and 0 bytes,
+ * as bad offsets do.  With src_begin = src_off and src_end = src_off + 1 every output is what lz4hip_unwrap_into_device writes, byte
+ * for byte.  With repeats the decoded size has no bound in src_len: size dst from the size query. */
+int lz4hip_unwrap_spans_into_device(const void* src, int64_t src_len, const int64_t* src_begin, const int64_t* src_end, int64_t m,
+                                    void* scratch, int64_t scratch_bytes, void* dst, int64_t dst_cap,
+                                    int64_t* dst_off, int32_t* status,
+                                    lz4hip_unwrap_info_t* info, int64_t* written_messages, void* stream);
+/* The spans of chosen entries, for callers with nothing to index a device array with: begin[j] = src_off[sel[j]], end[j] =
+ * src_off[sel[j] + 1]; a sel[j] outside [0, n) gives begin[j] = end[j] = -1, which the span calls (this one and
+ * lz4hip_streams_decode_spans_into_device) answer with LZ4HIP_E_ARGUMENT for that item.  The arguments are checked first (n, m >= 0;
+ * m > 0 needs sel, src_begin and src_end, and src_off unless n = 0); then one launch on `stream`, no scratch. */
+int lz4hip_spans_select_device(const int64_t* src_off, int64_t n, const int64_t* sel, int64_t m,
+                               int64_t* src_begin, int64_t* src_end, void* stream);
+
 /* Host-resident batches (what a C# byte[][] caller binds): stage everything through device memory (per-thread, grow-only, freed by
  * lz4hip_release_workspaces), run the device calls above and synchronise; every pointer is host memory.
  * Wrap returns 0 or LZ4HIP_E_* (dst_cap >= lz4hip_wrap_bound).  Unwrap returns 0 when every message unwrapped, else info->error (a
@@ -358,6 +393,21 @@ int lz4hip_streams_decode_into_device(const void* src, int64_t src_len, const in
                                       void* scratch, int64_t scratch_bytes, void* dst, int64_t dst_cap,
                                       int64_t* dst_off, int32_t* status, int64_t* error_offset,
                                       lz4hip_streams_info_t* info, int64_t* written_items, void* stream);
+
+/* Decode CHOSEN items of an arena in one call: lz4hip_streams_decode_into_device with m spans in the place of n consecutive items.
+ * Item j of the call is src[src_begin[j], src_end[j]) (device arrays of m entries; lz4hip_spans_select_device makes them from
+ * offsets and indices, lz4hip_stream_directory_device from one stream's chunks); the spans may come in any order, repeat, overlap and
+ * leave holes.  Everything else is the contract of lz4hip_streams_decode_into_device with m for n: the argument checks (m > 0 also
+ * needs src_begin, src_end, status, error_offset and scratch), launch-only, scratch of lz4hip_streams_decode_into_scratch_bytes(m,
+ * max_chunks); dst_off[m + 1], status[m] and error_offset[m] are indexed by CALL position, error_offset is relative to src_begin[j],
+ * info.first_error is the lowest failing call position, and dst_cap clips a prefix in call order.  max_chunks counts the chunks of
+ * the chosen items with multiplicity; LZ4HIP_STREAM_TABLE_FULL works as above.  A span with begin < 0, end < begin or end > src_len
+ * gets LZ4HIP_E_ARGUMENT and 0 bytes.  With src_begin = src_off and src_end = src_off + 1 every output is what
+ * lz4hip_streams_decode_into_device writes, byte for byte. */
+int lz4hip_streams_decode_spans_into_device(const void* src, int64_t src_len, const int64_t* src_begin, const int64_t* src_end, int64_t m,
+                                            int64_t max_chunks, void* scratch, int64_t scratch_bytes, void* dst, int64_t dst_cap,
+                                            int64_t* dst_off, int32_t* status, int64_t* error_offset,
+                                            lz4hip_streams_info_t* info, int64_t* written_items, void* stream);
 
 /* Host-resident batches (what a C# byte[][] caller binds): stage everything through device memory (per-thread, grow-only, freed by
  * lz4hip_release_workspaces), run the device calls above and synchronise; every pointer is host memory.

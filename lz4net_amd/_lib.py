@@ -112,6 +112,7 @@ SYMBOLS = [
     ("lz4hip_stream_decode_into_scratch_bytes", C.c_int64, [C.c_int64]),
     ("lz4hip_stream_decode_into_device", C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                                    C.c_void_p]),
+    ("lz4hip_stream_directory_device", C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("lz4hip_stream_encode_host", C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
     ("lz4hip_stream_decode_host", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(StreamInfo)]),
     ("lz4hip_wrap_bound", C.c_int64, [C.c_int64, C.c_int64]),
@@ -126,6 +127,9 @@ SYMBOLS = [
     ("lz4hip_unwrap_into_scratch_bytes", C.c_int64, [C.c_int64]),
     ("lz4hip_unwrap_into_device", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("lz4hip_unwrap_spans_into_device", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("lz4hip_spans_select_device", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("lz4hip_wrap_host", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     ("lz4hip_unwrap_host", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                      C.POINTER(UnwrapInfo)]),
@@ -141,6 +145,8 @@ SYMBOLS = [
     ("lz4hip_streams_decode_into_scratch_bytes", C.c_int64, [C.c_int64, C.c_int64]),
     ("lz4hip_streams_decode_into_device", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("lz4hip_streams_decode_spans_into_device", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64,
+                                                          C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("lz4hip_streams_encode_host", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
     ("lz4hip_streams_decode_host", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                              C.POINTER(StreamsInfo)]),

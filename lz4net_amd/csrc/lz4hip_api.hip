@@ -1578,6 +1578,15 @@ int lz4hip_stream_decode_into_device(const void* src, int64_t src_len, int64_t m
     return stream_decode_into_run(be, p);
 }
 
+int lz4hip_stream_directory_device(const void* src, int64_t src_len, int64_t max_chunks, int64_t* hdr_off, int64_t* out_off,
+                                   lz4hip_stream_info_t* info, void* stream)
+{
+    HipBackend be = { (hipStream_t)stream };
+    if (int rc = stream_directory_check(be, src, src_len, max_chunks, hdr_off, out_off, info)) return rc;
+    if (int rc = ensure_device()) return rc;
+    return stream_directory_run(be, src, src_len, max_chunks, hdr_off, out_off, info);
+}
+
 int lz4hip_stream_encode_host(const void* src, int64_t src_len, int32_t block_size, int mode, void* dst, int64_t dst_cap, int64_t* dst_len)
 {
     HipBackend be = {};
@@ -1637,6 +1646,26 @@ int lz4hip_unwrap_into_device(const void* src, int64_t src_len, const int64_t* s
     if (int rc = unwrap_into_plan(be, src, src_len, src_off, n, scratch, scratch_bytes, dst, dst_cap, dst_off, status, info, written_messages, p)) return rc;
     if (int rc = ensure_device()) return rc;
     return unwrap_into_run(be, p);
+}
+
+int lz4hip_unwrap_spans_into_device(const void* src, int64_t src_len, const int64_t* src_begin, const int64_t* src_end, int64_t m, void* scratch,
+                                    int64_t scratch_bytes, void* dst, int64_t dst_cap, int64_t* dst_off, int32_t* status,
+                                    lz4hip_unwrap_info_t* info, int64_t* written_messages, void* stream)
+{
+    HipBackend be = { (hipStream_t)stream };
+    UnwrapIntoPlan p;
+    if (int rc = unwrap_spans_into_plan(be, src, src_len, src_begin, src_end, m, scratch, scratch_bytes, dst, dst_cap, dst_off, status, info,
+                                        written_messages, p)) return rc;
+    if (int rc = ensure_device()) return rc;
+    return unwrap_into_run(be, p);
+}
+
+int lz4hip_spans_select_device(const int64_t* src_off, int64_t n, const int64_t* sel, int64_t m, int64_t* src_begin, int64_t* src_end, void* stream)
+{
+    HipBackend be = { (hipStream_t)stream };
+    if (int rc = spans_select_check(be, src_off, n, sel, m, src_begin, src_end)) return rc;
+    if (int rc = ensure_device()) return rc;
+    return spans_select_run(be, src_off, n, sel, m, src_begin, src_end);
 }
 
 int lz4hip_wrap_host(const void* src, int64_t src_len, const int64_t* src_off, int64_t n, int mode, void* dst, int64_t dst_cap,
@@ -1707,6 +1736,19 @@ int lz4hip_streams_decode_into_device(const void* src, int64_t src_len, const in
     StreamsIntoPlan p;
     if (int rc = streams_decode_into_plan(be, src, src_len, src_off, n, max_chunks, scratch, scratch_bytes, dst, dst_cap, dst_off, status,
                                           error_offset, info, written_items, p)) return rc;
+    if (int rc = ensure_device()) return rc;
+    return streams_decode_into_run(be, p);
+}
+
+int lz4hip_streams_decode_spans_into_device(const void* src, int64_t src_len, const int64_t* src_begin, const int64_t* src_end, int64_t m,
+                                            int64_t max_chunks, void* scratch, int64_t scratch_bytes, void* dst, int64_t dst_cap,
+                                            int64_t* dst_off, int32_t* status, int64_t* error_offset, lz4hip_streams_info_t* info,
+                                            int64_t* written_items, void* stream)
+{
+    HipBackend be = { (hipStream_t)stream };
+    StreamsIntoPlan p;
+    if (int rc = streams_decode_spans_into_plan(be, src, src_len, src_begin, src_end, m, max_chunks, scratch, scratch_bytes, dst, dst_cap, dst_off,
+                                                status, error_offset, info, written_items, p)) return rc;
     if (int rc = ensure_device()) return rc;
     return streams_decode_into_run(be, p);
 }

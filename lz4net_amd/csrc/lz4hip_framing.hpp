@@ -328,6 +328,30 @@ int stream_index(B& be, const void* src, int64_t src_len, int64_t max_chunks, vo
     return stream_index_run(be, (const uint8_t*)src, src_len, t, (StreamInfo*)info);
 }
 
+// The walk of the index, kept in the caller's own arrays of max_chunks + 1 entries each (no scratch): see stream_directory_kernel
+template <class B>
+int stream_directory_check(B& be, const void* src, int64_t src_len, int64_t max_chunks, const int64_t* hdr_off, const int64_t* out_off,
+                           const lz4hip_stream_info_t* info)
+{
+    if (src_len < 0 || max_chunks < 0 || !hdr_off || !out_off || !info || (src_len > 0 && !src))
+        return be.fail(LZ4HIP_E_ARGUMENT, "stream directory: negative size or NULL pointer");
+    return 0;
+}
+
+template <class B>
+int stream_directory_run(B& be, const void* src, int64_t src_len, int64_t max_chunks, int64_t* hdr_off, int64_t* out_off, lz4hip_stream_info_t* info)
+{
+    be.launch(stream_directory_kernel, fixed_grid(1), 64, (const uint8_t*)src, src_len, max_chunks, hdr_off, out_off, (StreamInfo*)info);
+    return be.last_error();
+}
+
+template <class B>
+int stream_directory(B& be, const void* src, int64_t src_len, int64_t max_chunks, int64_t* hdr_off, int64_t* out_off, lz4hip_stream_info_t* info)
+{
+    LZ4HIP_FRAMING_TRY(stream_directory_check(be, src, src_len, max_chunks, hdr_off, out_off, info));
+    return stream_directory_run(be, src, src_len, max_chunks, hdr_off, out_off, info);
+}
+
 // h: what the index reported, read back by the host
 template <class B>
 int stream_decode_run(B& be, const uint8_t* src, const StreamInfo& h, const StreamTables& t, uint8_t* dst, StreamInfo* info)
@@ -486,15 +510,17 @@ int wrap_encode(B& be, const void* src, int64_t src_len, const int64_t* src_off,
     return wrap_encode_run(be, a, mode, l.at, l.lens, result, l.partial, (uint8_t*)dst, dst_cap);
 }
 
+// `end`: NULL for consecutive messages (a.off has n + 1 entries), else the n ends of the spans that begin at a.off[i]
 template <class B>
-int unwrap_index_run(B& be, const UnwrapArgs& a, const UnwrapTables& t, UnwrapInfo* info)
+int unwrap_index_run(B& be, const UnwrapArgs& a, const UnwrapTables& t, UnwrapInfo* info, const int64_t* end = nullptr)
 {
     LZ4HIP_FRAMING_TRY(be.fill(t.min_bad, 0xFF, 8));                   // min_bad = none
     LZ4HIP_FRAMING_TRY(be.fill(t.ncomp, 0, 8));
     if (a.n == 0) {
         LZ4HIP_FRAMING_TRY(be.fill(a.dst_off, 0, sizeof(int64_t)));
     } else {
-        be.launch(unwrap_index_kernel, stream_grid(a.n), kStreamThreads, a, t);
+        if (end) be.launch(unwrap_index_spans_kernel, stream_grid(a.n), kStreamThreads, a, t, end);
+        else be.launch(unwrap_index_kernel, stream_grid(a.n), kStreamThreads, a, t);
         launch_scan(be, a.dst_off, a.n, t.partial, a.dst_off + a.n);
         launch_scan(be, t.cidx, a.n, t.partial, t.ncomp);
         be.launch(unwrap_compact_kernel, stream_grid(a.n), kStreamThreads, a, t);
@@ -574,9 +600,11 @@ inline UnwrapIntoScratch unwrap_into_scratch(void* scratch, int64_t n)
 }
 inline int64_t unwrap_into_scratch_bytes(int64_t n) { return unwrap_into_scratch(nullptr, n).bytes; }
 
-struct UnwrapIntoPlan { UnwrapArgs a; UnwrapClip clip; uint8_t* dst; UnwrapInfo* info; uint8_t* any; };
+// `end`: NULL for consecutive messages, else the span form's ends (a.off holds the begins)
+struct UnwrapIntoPlan { UnwrapArgs a; UnwrapClip clip; uint8_t* dst; UnwrapInfo* info; uint8_t* any; const int64_t* end = nullptr; };
 
-// The index as it is, then the two-call decode's steps over ALL n rows of the table, the count and the output's end taken from the device
+// The index as it is, then the two-call decode's steps over ALL n rows of the table, the count and the output's end taken from the device.
+// Consecutive messages and spans are this one sequence: only the index kernel and the raw copy's grid know the difference.
 template <class B>
 int unwrap_into_run(B& be, const UnwrapIntoPlan& p)
 {
@@ -588,7 +616,7 @@ int unwrap_into_run(B& be, const UnwrapIntoPlan& p)
         LZ4HIP_FRAMING_TRY(be.fill(t.c_src_off, 0, (size_t)(8 * a.n)));
         LZ4HIP_FRAMING_TRY(be.fill(t.c_dst_off, 0, (size_t)(8 * a.n)));
     }
-    LZ4HIP_FRAMING_TRY(unwrap_index_run(be, a, t, p.info));
+    LZ4HIP_FRAMING_TRY(unwrap_index_run(be, a, t, p.info, p.end));
     if (a.n == 0) return 0;
     be.launch(unwrap_clip_kernel, stream_grid(a.n), kStreamThreads, a, p.clip);
     LZ4HIP_FRAMING_TRY(be.last_error());
@@ -599,7 +627,8 @@ int unwrap_into_run(B& be, const UnwrapIntoPlan& p)
     b.result = t.c_result; b.n_blocks = a.n;
     LZ4HIP_FRAMING_TRY(be.decode(&b, 1));
     UnwrapRawLayout layout = { a, t };
-    const int64_t most = a.src_len < p.clip.dst_cap / 255 ? a.src_len * 255 : p.clip.dst_cap;     // (an LZ4 block grows 255 times at most)
+    // (an LZ4 block grows 255 times at most; spans may repeat, so their output has no bound in src_len)
+    const int64_t most = !p.end && a.src_len < p.clip.dst_cap / 255 ? a.src_len * 255 : p.clip.dst_cap;
     be.launch(wrap_raw_copy_into_kernel, copy_grid(most), kStreamThreads, layout, p.dst, (const int64_t*)p.clip.written_end);
     be.launch(unwrap_check_into_kernel, stream_grid(a.n), kStreamThreads, t, (const int32_t*)p.clip.s_dst_cap, a.status);
     be.launch(unwrap_info_kernel, fixed_grid(1), 64, a, t, p.info);
@@ -631,6 +660,53 @@ int unwrap_into(B& be, const void* src, int64_t src_len, const int64_t* src_off,
     UnwrapIntoPlan p;
     LZ4HIP_FRAMING_TRY(unwrap_into_plan(be, src, src_len, src_off, n, scratch, scratch_bytes, dst, dst_cap, dst_off, status, info, written_messages, p));
     return unwrap_into_run(be, p);
+}
+
+// The span form: message j is src[src_begin[j], src_end[j]); everything else is unwrap_into's, with m in the place of n
+template <class B>
+int unwrap_spans_into_plan(B& be, const void* src, int64_t src_len, const int64_t* src_begin, const int64_t* src_end, int64_t m, void* scratch,
+                           int64_t scratch_bytes, void* dst, int64_t dst_cap, int64_t* dst_off, int32_t* status, lz4hip_unwrap_info_t* info,
+                           int64_t* written_messages, UnwrapIntoPlan& p)
+{
+    if (m > 0 && !src_end) return be.fail(LZ4HIP_E_ARGUMENT, "unwrap spans into: NULL pointer");
+    LZ4HIP_FRAMING_TRY(unwrap_into_plan(be, src, src_len, src_begin, m, scratch, scratch_bytes, dst, dst_cap, dst_off, status, info, written_messages, p));
+    p.end = m > 0 ? src_end : nullptr;
+    return 0;
+}
+
+template <class B>
+int unwrap_spans_into(B& be, const void* src, int64_t src_len, const int64_t* src_begin, const int64_t* src_end, int64_t m, void* scratch,
+                      int64_t scratch_bytes, void* dst, int64_t dst_cap, int64_t* dst_off, int32_t* status, lz4hip_unwrap_info_t* info,
+                      int64_t* written_messages)
+{
+    UnwrapIntoPlan p;
+    LZ4HIP_FRAMING_TRY(unwrap_spans_into_plan(be, src, src_len, src_begin, src_end, m, scratch, scratch_bytes, dst, dst_cap, dst_off, status, info,
+                                              written_messages, p));
+    return unwrap_into_run(be, p);
+}
+
+// begin[j] = src_off[sel[j]], end[j] = src_off[sel[j] + 1], or (-1, -1) for a sel[j] outside [0, n): one launch, no scratch
+template <class B>
+int spans_select_check(B& be, const int64_t* src_off, int64_t n, const int64_t* sel, int64_t m, const int64_t* src_begin, const int64_t* src_end)
+{
+    if (n < 0 || m < 0) return be.fail(LZ4HIP_E_ARGUMENT, "spans select: n < 0 or m < 0");
+    if (m > 0 && (!sel || !src_begin || !src_end || (n > 0 && !src_off))) return be.fail(LZ4HIP_E_ARGUMENT, "spans select: NULL pointer");
+    return 0;
+}
+
+template <class B>
+int spans_select_run(B& be, const int64_t* src_off, int64_t n, const int64_t* sel, int64_t m, int64_t* src_begin, int64_t* src_end)
+{
+    if (m == 0) return 0;
+    be.launch(spans_select_kernel, stream_grid(m), kStreamThreads, src_off, n, sel, m, src_begin, src_end);
+    return be.last_error();
+}
+
+template <class B>
+int spans_select(B& be, const int64_t* src_off, int64_t n, const int64_t* sel, int64_t m, int64_t* src_begin, int64_t* src_end)
+{
+    LZ4HIP_FRAMING_TRY(spans_select_check(be, src_off, n, sel, m, src_begin, src_end));
+    return spans_select_run(be, src_off, n, sel, m, src_begin, src_end);
 }
 
 // ---- batches of LZ4Stream buffers (lz4hip_streams.hpp) --------------------------------------------------------------------------------
@@ -693,16 +769,19 @@ int streams_empty_info(B& be, StreamsInfo* info)
     return be.last_error();
 }
 
+// `end`: NULL for consecutive items (a.off has n + 1 entries), else the n ends of the spans that begin at a.off[i]
 template <class B>
-int streams_index_run(B& be, const StreamsDecodeArgs& a, const StreamsTables& t, StreamsInfo* info)
+int streams_index_run(B& be, const StreamsDecodeArgs& a, const StreamsTables& t, StreamsInfo* info, const int64_t* end = nullptr)
 {
     LZ4HIP_FRAMING_TRY(be.fill(t.totals, 0, 16));
     LZ4HIP_FRAMING_TRY(be.fill(t.t.min_bad, 0xFF, 8));                 // min_bad = none
-    be.launch(streams_walk_kernel<false>, walk_grid(a.n), 64, a, t);
+    if (end) be.launch(streams_walk_spans_kernel<false>, walk_grid(a.n), 64, a, t, end);
+    else be.launch(streams_walk_kernel<false>, walk_grid(a.n), 64, a, t);
     launch_scan(be, a.dst_off, a.n, t.partial, a.dst_off + a.n);
     launch_scan(be, t.chunk_base, a.n, t.partial, t.totals);
     launch_scan(be, t.comp_base, a.n, t.partial, t.totals + 1);
-    be.launch(streams_walk_kernel<true>, walk_grid(a.n), 64, a, t);
+    if (end) be.launch(streams_walk_spans_kernel<true>, walk_grid(a.n), 64, a, t, end);
+    else be.launch(streams_walk_kernel<true>, walk_grid(a.n), 64, a, t);
     be.launch(streams_info_kernel, fixed_grid(1), 64, a, t, info);
     return be.last_error();
 }
@@ -795,10 +874,14 @@ inline int64_t streams_decode_into_scratch_bytes(int64_t n, int64_t max_chunks)
     return n <= 0 ? 0 : streams_into_scratch(nullptr, n, max_chunks).bytes;       // (no item: the call touches no scratch)
 }
 
-// a.n == 0: only a.dst_off, info and written are looked at
-struct StreamsIntoPlan { StreamsDecodeArgs a; StreamsClip clip; uint8_t* dst; StreamsInfo* info; int64_t* written; uint8_t* any; };
+// a.n == 0: only a.dst_off, info and written are looked at.  `end`: NULL for consecutive items, else the span form's ends (a.off holds
+// the begins)
+struct StreamsIntoPlan {
+    StreamsDecodeArgs a; StreamsClip clip; uint8_t* dst; StreamsInfo* info; int64_t* written; uint8_t* any; const int64_t* end = nullptr;
+};
 
-// The index as it is, then the two-call decode's steps over ALL max_chunks rows, the counts and the output's end taken from the device
+// The index as it is, then the two-call decode's steps over ALL max_chunks rows, the counts and the output's end taken from the device.
+// Consecutive items and spans are this one sequence: only the walk kernels and the raw copy's grid know the difference.
 template <class B>
 int streams_decode_into_run(B& be, const StreamsIntoPlan& p)
 {
@@ -816,7 +899,7 @@ int streams_decode_into_run(B& be, const StreamsIntoPlan& p)
         LZ4HIP_FRAMING_TRY(be.fill(t.t.c_src_off, 0, (size_t)(8 * rows)));
         LZ4HIP_FRAMING_TRY(be.fill(t.t.c_dst_off, 0, (size_t)(8 * rows)));
     }
-    LZ4HIP_FRAMING_TRY(streams_index_run(be, a, t, p.info));
+    LZ4HIP_FRAMING_TRY(streams_index_run(be, a, t, p.info, p.end));
     LZ4HIP_FRAMING_TRY(be.fill(t.t.min_bad, 0xFF, 8));
     LZ4HIP_FRAMING_TRY(be.fill(t.item_bad, 0xFF, (size_t)(8 * a.n)));
     be.launch(streams_clip_kernel, stream_grid(rows > a.n ? rows : a.n), kStreamThreads, a, p.clip);
@@ -830,7 +913,8 @@ int streams_decode_into_run(B& be, const StreamsIntoPlan& p)
         LZ4HIP_FRAMING_TRY(be.decode(&b, 1));
         be.launch(streams_check_into_kernel, stream_grid(rows), kStreamThreads, t, (const int32_t*)p.clip.s_dst_cap);
         RawLayout layout = { a.src, t.t, 0 };
-        const int64_t most = a.src_len < p.clip.dst_cap / 255 ? a.src_len * 255 : p.clip.dst_cap;   // (an LZ4 block grows 255 times at most)
+        // (an LZ4 block grows 255 times at most; spans may repeat, so their output has no bound in src_len)
+        const int64_t most = !p.end && a.src_len < p.clip.dst_cap / 255 ? a.src_len * 255 : p.clip.dst_cap;
         be.launch(stream_raw_copy_into_kernel, copy_grid(most), kStreamThreads, layout, p.dst, (const int64_t*)t.totals, (const int64_t*)p.clip.written_end);
         LZ4HIP_FRAMING_TRY(be.last_error());
     }
@@ -868,6 +952,30 @@ int streams_decode_into(B& be, const void* src, int64_t src_len, const int64_t* 
     StreamsIntoPlan p;
     LZ4HIP_FRAMING_TRY(streams_decode_into_plan(be, src, src_len, src_off, n, max_chunks, scratch, scratch_bytes, dst, dst_cap, dst_off, status,
                                                 error_offset, info, written_items, p));
+    return streams_decode_into_run(be, p);
+}
+
+// The span form: item j is src[src_begin[j], src_end[j]); everything else is streams_decode_into's, with m in the place of n
+template <class B>
+int streams_decode_spans_into_plan(B& be, const void* src, int64_t src_len, const int64_t* src_begin, const int64_t* src_end, int64_t m,
+                                   int64_t max_chunks, void* scratch, int64_t scratch_bytes, void* dst, int64_t dst_cap, int64_t* dst_off,
+                                   int32_t* status, int64_t* error_offset, lz4hip_streams_info_t* info, int64_t* written_items, StreamsIntoPlan& p)
+{
+    if (m > 0 && !src_end) return be.fail(LZ4HIP_E_ARGUMENT, "streams decode spans into: NULL pointer");
+    LZ4HIP_FRAMING_TRY(streams_decode_into_plan(be, src, src_len, src_begin, m, max_chunks, scratch, scratch_bytes, dst, dst_cap, dst_off, status,
+                                                error_offset, info, written_items, p));
+    p.end = m > 0 ? src_end : nullptr;
+    return 0;
+}
+
+template <class B>
+int streams_decode_spans_into(B& be, const void* src, int64_t src_len, const int64_t* src_begin, const int64_t* src_end, int64_t m,
+                              int64_t max_chunks, void* scratch, int64_t scratch_bytes, void* dst, int64_t dst_cap, int64_t* dst_off,
+                              int32_t* status, int64_t* error_offset, lz4hip_streams_info_t* info, int64_t* written_items)
+{
+    StreamsIntoPlan p;
+    LZ4HIP_FRAMING_TRY(streams_decode_spans_into_plan(be, src, src_len, src_begin, src_end, m, max_chunks, scratch, scratch_bytes, dst, dst_cap,
+                                                      dst_off, status, error_offset, info, written_items, p));
     return streams_decode_into_run(be, p);
 }
 

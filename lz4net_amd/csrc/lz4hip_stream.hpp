@@ -12,6 +12,7 @@
 //   decode: stream_index_kernel (ONE wavefront walks the headers, one dependent global round trip per chunk, and writes the
 //           compressed and the raw chunks to two separate tables) -> [launch_decode on the compressed table] ->
 //           stream_raw_copy_kernel (same copy routine as the pack) -> stream_check_kernel (the first corrupt block in stream order)
+//   directory: stream_directory_kernel (the index's walk, writing every chunk's header and output offset to the caller's arrays)
 //
 // Every kernel here is launch-only work on the caller's stream over caller scratch.
 #pragma once
@@ -364,6 +365,43 @@ __global__ void __launch_bounds__(64) stream_index_kernel(const uint8_t* src, in
     if (chunks > t.max_chunks) err = kStreamTableFull;
     else if (err != kStreamOk) err_off = pos;
     if (lane == 0) {
+        StreamInfo r;
+        r.chunks = chunks; r.compressed_chunks = ncomp; r.decoded_bytes = out; r.error_offset = err_off; r.error = err; r.reserved = 0;
+        *info = r;
+    }
+}
+
+// The same walk, kept: the directory of a stream that is decoded more than once, or in parts.  hdr_off[k] is the header offset of
+// non-empty chunk k and out_off[k] its decoded offset; the closing entry (hdr_off[chunks], out_off[chunks]) is where the walk ended
+// (src_len, or the header error's offset) and the decoded size.  Both arrays have max_chunks + 1 entries.  src[hdr_off[k],
+// hdr_off[k + 1]) is chunk k and the empty chunks behind it: a one-chunk stream, an item of the batch decoder's span form
+// (lz4hip_streams.hpp).  The stop rules, the error codes and *info are stream_index_kernel's; on TABLE_FULL the entries [0, max_chunks)
+// are valid and no closing entry is written.
+__global__ void __launch_bounds__(64) stream_directory_kernel(const uint8_t* src, int64_t src_len, int64_t max_chunks, int64_t* hdr_off,
+                                                              int64_t* out_off, StreamInfo* info)
+{
+    const int lane = wv::lane();
+    int64_t pos = 0, out = 0, chunks = 0, ncomp = 0, err_off = -1;
+    int err = kStreamOk;
+    while (pos < src_len) {
+        const ChunkHeader h = stream_read_header(src, src_len, pos, lane);
+        if (h.err != kStreamOk) { err = h.err; break; }
+        if (h.original != 0) {
+            if (chunks < max_chunks) {
+                if (lane == 0) { hdr_off[chunks] = pos; out_off[chunks] = out; }
+            } else if (chunks == max_chunks) {
+                err_off = pos;                                                  // (TABLE_FULL: the first chunk that did not fit)
+            }
+            if (h.compressed) ncomp++;
+            chunks++;
+            out += h.original;
+        }
+        pos = h.payload + h.clen;
+    }
+    if (chunks > max_chunks) err = kStreamTableFull;
+    else if (err != kStreamOk) err_off = pos;
+    if (lane == 0) {
+        if (chunks <= max_chunks) { hdr_off[chunks] = pos; out_off[chunks] = out; }
         StreamInfo r;
         r.chunks = chunks; r.compressed_chunks = ncomp; r.decoded_bytes = out; r.error_offset = err_off; r.error = err; r.reserved = 0;
         *info = r;

@@ -15,6 +15,8 @@
 //   decode: [launch_decode, known size, on the compressed table of all items] -> stream_raw_copy_kernel (RawLayout over the raw table
 //           of all items) -> streams_check_kernel (per item, the header offset of its first corrupt block) -> streams_finish_kernel
 //           (final statuses, lowest failing item) -> streams_info_kernel
+//   spans:  chosen items of an arena, [begin[j], end[j]) in any order: the walk alone reads an item's end, so the span form is the same
+//           sequence behind streams_walk_spans_kernel<false / true>
 //
 // Every kernel here is launch-only work on the caller's stream over caller scratch.
 #pragma once
@@ -30,16 +32,21 @@ struct StreamsInfo {
     int32_t error, reserved;
 };
 
-// item i of the batch: false (and an empty item at 0) for offsets that decrease or fall outside [0, src_len]
-LZ4HIP_DEVICE bool streams_item(const int64_t* off, int64_t i, int64_t src_len, int64_t& at, int64_t& len)
+// the item src[a, b): false (and an empty item at 0) for bounds that decrease or fall outside [0, src_len]
+LZ4HIP_DEVICE bool streams_span(int64_t a, int64_t b, int64_t src_len, int64_t& at, int64_t& len)
 {
-    const int64_t a = off[i], b = off[i + 1];
     at = 0;
     len = 0;
     if (a < 0 || b < a || b > src_len) return false;
     at = a;
     len = b - a;
     return true;
+}
+
+// item i of the batch: the span [off[i], off[i + 1])
+LZ4HIP_DEVICE bool streams_item(const int64_t* off, int64_t i, int64_t src_len, int64_t& at, int64_t& len)
+{
+    return streams_span(off[i], off[i + 1], src_len, at, len);
 }
 
 // ---- encode ----------------------------------------------------------------------------------------------------------------
@@ -168,14 +175,15 @@ struct StreamsDecodeArgs {
 
 // One wavefront per item walks its headers like stream_index_kernel walks a lone stream.  The count pass (kFill = false) leaves the
 // item's three counts, its header status and the failing header's offset; the fill pass, after the scans, writes the tables.
+// Item i is src[a.off[i], end[i]): the walk is the only step that reads an item's end, everything after it reads the tables.
 template <bool kFill>
-__global__ void __launch_bounds__(64) streams_walk_kernel(StreamsDecodeArgs a, StreamsTables t)
+LZ4HIP_DEVICE void streams_walk_items(const StreamsDecodeArgs& a, const StreamsTables& t, const int64_t* end)
 {
     const int lane = wv::lane();
     if (kFill && t.totals[0] > t.t.max_chunks) return;                 // (TABLE_FULL: the caller grows the tables and indexes again)
     for (int64_t i = blockIdx.x; i < a.n; i += gridDim.x) {
         int64_t at, len;
-        const bool valid = streams_item(a.off, i, a.src_len, at, len);
+        const bool valid = streams_span(a.off[i], end[i], a.src_len, at, len);
         const uint8_t* const src = a.src + at;
         int64_t pos = 0, out = 0, ncomp = 0, nraw = 0;
         int64_t out_base = 0, comp_base = 0, raw_base = 0;
@@ -210,6 +218,20 @@ __global__ void __launch_bounds__(64) streams_walk_kernel(StreamsDecodeArgs a, S
             if (st != kStreamOk) atomicMin(t.t.min_bad, (unsigned long long)i);
         }
     }
+}
+
+// consecutive items: a.off has n + 1 entries and item i ends where item i + 1 begins
+template <bool kFill>
+__global__ void __launch_bounds__(64) streams_walk_kernel(StreamsDecodeArgs a, StreamsTables t)
+{
+    streams_walk_items<kFill>(a, t, a.off + 1);
+}
+
+// chosen items: a.off holds the n begins and `end` the n ends, in any order, with repeats, overlaps and holes
+template <bool kFill>
+__global__ void __launch_bounds__(64) streams_walk_spans_kernel(StreamsDecodeArgs a, StreamsTables t, const int64_t* end)
+{
+    streams_walk_items<kFill>(a, t, end);
 }
 
 // Decode64's check (src/LZ4pn/LZ4Codec.Unsafe.cs:373-378) per chunk; per item, the corrupt block FIRST in its stream

@@ -15,6 +15,8 @@
 //           the arrays of a lz4hip_batch_t) -> unwrap_info_kernel
 //   decode: [launch_decode, known size, on the compacted table] -> wrap_raw_copy_kernel (copy_spans over UnwrapRawLayout) ->
 //           unwrap_check_kernel (consumed != payloadLength: corrupt block) -> unwrap_info_kernel
+//   spans:  chosen messages of an arena, [begin[j], end[j]) in any order: the index alone reads a message's end, so the span form is
+//           the same sequence behind unwrap_index_spans_kernel; spans_select_kernel makes the spans from offsets and indices
 //
 // Every kernel here is launch-only work on the caller's stream over caller scratch.
 #pragma once
@@ -33,16 +35,21 @@ struct UnwrapInfo {
     int32_t error, reserved;
 };
 
-// message i of the batch: false for offsets that decrease, fall outside [0, src_len] or give a length above INT32_MAX
-LZ4HIP_DEVICE bool wrap_message(const int64_t* off, int64_t i, int64_t src_len, int64_t& at, int32_t& len)
+// the message src[a, b): false for bounds that decrease, fall outside [0, src_len] or give a length above INT32_MAX
+LZ4HIP_DEVICE bool wrap_span(int64_t a, int64_t b, int64_t src_len, int64_t& at, int32_t& len)
 {
-    const int64_t a = off[i], b = off[i + 1];
     at = 0;
     len = 0;
     if (a < 0 || b < a || b > src_len || b - a > 0x7FFFFFFF) return false;
     at = a;
     len = (int32_t)(b - a);
     return true;
+}
+
+// message i of the batch: the span [off[i], off[i + 1])
+LZ4HIP_DEVICE bool wrap_message(const int64_t* off, int64_t i, int64_t src_len, int64_t& at, int32_t& len)
+{
+    return wrap_span(off[i], off[i + 1], src_len, at, len);
 }
 
 LZ4HIP_DEVICE int32_t load_le32(const uint8_t* p)
@@ -159,14 +166,16 @@ struct UnwrapArgs {
 
 // Unwrap's checks in its order (src/LZ4/LZ4Codec.cs:574-599), with signed fields: < 8 bytes, payloadLength past the end (or negative),
 // payloadLength >= originalLength: the payload as it is, else a known-size decode of originalLength bytes.
-__global__ void __launch_bounds__(kStreamThreads) unwrap_index_kernel(UnwrapArgs a, UnwrapTables t)
+// Message i is src[a.off[i], end[i]): the index is the only step that reads a message's end, everything after it reads a.off[i] as
+// the message's begin, a.dst_off and the tables.
+LZ4HIP_DEVICE void unwrap_index_items(const UnwrapArgs& a, const UnwrapTables& t, const int64_t* end)
 {
     for (int64_t i = (int64_t)blockIdx.x * kStreamThreads + threadIdx.x; i < a.n; i += (int64_t)gridDim.x * kStreamThreads) {
         int64_t at;
         int32_t len;
         int32_t st = kWrapOk, raw = 0;
         int64_t size = 0, comp = 0;
-        if (!wrap_message(a.off, i, a.src_len, at, len)) {
+        if (!wrap_span(a.off[i], end[i], a.src_len, at, len)) {
             st = kWrapBadOffsets;
         } else if (len < kWrapHeader) {
             st = kWrapSizeInvalid;
@@ -182,6 +191,18 @@ __global__ void __launch_bounds__(kStreamThreads) unwrap_index_kernel(UnwrapArgs
         t.raw_len[i] = raw;
         if (st != kWrapOk) atomicMin(t.min_bad, (unsigned long long)i);
     }
+}
+
+// consecutive messages: a.off has n + 1 entries and message i ends where message i + 1 begins
+__global__ void __launch_bounds__(kStreamThreads) unwrap_index_kernel(UnwrapArgs a, UnwrapTables t)
+{
+    unwrap_index_items(a, t, a.off + 1);
+}
+
+// chosen messages: a.off holds the n begins and `end` the n ends, in any order, with repeats, overlaps and holes
+__global__ void __launch_bounds__(kStreamThreads) unwrap_index_spans_kernel(UnwrapArgs a, UnwrapTables t, const int64_t* end)
+{
+    unwrap_index_items(a, t, end);
 }
 
 // after both scans: the compressed messages, in message order, into the table
@@ -292,6 +313,20 @@ __global__ void __launch_bounds__(64) unwrap_info_kernel(UnwrapArgs a, UnwrapTab
     r.error = bad == ~0ull ? kWrapOk : a.status[bad];
     r.reserved = 0;
     *info = r;
+}
+
+// ---- spans of chosen items ----------------------------------------------------------------------------------------------------
+// begin[j] = off[sel[j]], end[j] = off[sel[j] + 1] for the span forms of the one-call decodes (wrapped messages and LZ4Stream buffers
+// alike); a sel[j] outside [0, n) gives (-1, -1), which those calls answer with a bad-offsets status for item j alone.
+__global__ void __launch_bounds__(kStreamThreads) spans_select_kernel(const int64_t* off, int64_t n, const int64_t* sel, int64_t m,
+                                                                      int64_t* begin, int64_t* end)
+{
+    for (int64_t j = (int64_t)blockIdx.x * kStreamThreads + threadIdx.x; j < m; j += (int64_t)gridDim.x * kStreamThreads) {
+        const int64_t i = sel[j];
+        const bool inside = i >= 0 && i < n;
+        begin[j] = inside ? off[i] : -1;
+        end[j] = inside ? off[i + 1] : -1;
+    }
 }
 
 }  // namespace lz4hip

@@ -309,6 +309,21 @@ def _check_device_batch(buf, offsets):
     return buf.contiguous(), offsets.contiguous()
 
 
+def _check_device_spans(buf, begin, end):
+    """chosen items of an arena on the device: a 1-D uint8 CUDA tensor and the int64 begin[m], end[m] of its spans"""
+    import torch
+    if not isinstance(buf, torch.Tensor) or not buf.is_cuda or buf.dtype != torch.uint8 or buf.dim() != 1:
+        raise ArgumentException("the buffer must be a 1-D uint8 CUDA tensor")
+    for t in (begin, end):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.int64 or t.dim() != 1:
+            raise ArgumentException("begin and end must be 1-D int64 CUDA tensors")
+        if t.device != buf.device:
+            raise ArgumentException("the buffer and the spans must be on the same device")
+    if begin.numel() != end.numel():
+        raise ArgumentException("begin and end must have the same length")
+    return buf.contiguous(), begin.contiguous(), end.contiguous()
+
+
 def streams_error(status: int, index: int, error_offset: int = -1):
     """The exception a sequential [decompress_stream(s) for s in ...] raises at an item with this status (LZ4HIP_STREAM_*, or
     LZ4HIP_E_ARGUMENT for bad offsets), with the item's index in .item_index and the failing header's offset within it in .error_offset."""
@@ -417,6 +432,85 @@ def decompress_streams_into(packed, offsets, out, max_chunks=None, block_size: i
                                                        err_off.data_ptr(), info.data_ptr(), written.data_ptr(),
                                                        torch.cuda.current_stream(dev).cuda_stream))
         return out_off, status[:n], err_off[:n], info, written
+
+
+def decompress_streams_spans_into(packed, begin, end, out, max_chunks=None, block_size: int = DEFAULT_BLOCK_SIZE):
+    """decompress_streams_into for CHOSEN items of an arena: item j of the call is packed[begin[j]:end[j]] (int64 CUDA tensors of m
+    entries, from wrap.select_spans, a stream_directory or the caller's own index; any order, repeats, overlaps and holes), in ONE
+    device call whose cost follows m -> (out_off, status, error_offset, info, written_items) as decompress_streams_into returns them,
+    indexed by position in the call; check_streams_into reads them.  max_chunks counts the chunks of the chosen items, repeats
+    included: by default out.numel() // block + m + 16."""
+    import torch
+    packed, begin, end = _check_device_spans(packed, begin, end)
+    out = _check_out(out, packed)
+    m = begin.numel()
+    if max_chunks is None:
+        max_chunks = out.numel() // max(16, int(block_size)) + m + 16
+    with torch.cuda.device(packed.device):
+        L = _lib.lib()
+        dev = packed.device
+        out_off = torch.empty(m + 1, dtype=torch.int64, device=dev)
+        status = torch.empty(max(m, 1), dtype=torch.int32, device=dev)
+        err_off = torch.empty(max(m, 1), dtype=torch.int64, device=dev)
+        info = torch.zeros(C.sizeof(_lib.StreamsInfo), dtype=torch.uint8, device=dev)
+        written = torch.zeros(1, dtype=torch.int64, device=dev)
+        scratch = torch.empty(L.lz4hip_streams_decode_into_scratch_bytes(m, max_chunks), dtype=torch.uint8, device=dev)
+        _lib.check(L.lz4hip_streams_decode_spans_into_device(packed.data_ptr(), packed.numel(), begin.data_ptr(), end.data_ptr(), m, max_chunks,
+                                                             scratch.data_ptr(), scratch.numel(), out.data_ptr(), out.numel(),
+                                                             out_off.data_ptr(), status.data_ptr(), err_off.data_ptr(), info.data_ptr(),
+                                                             written.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+        return out_off, status[:m], err_off[:m], info, written
+
+
+def stream_directory(t, max_chunks=None, block_size: int = DEFAULT_BLOCK_SIZE):
+    """The chunk directory of ONE LZ4Stream buffer (a 1-D uint8 CUDA tensor), to keep beside a stream that is decoded more than once
+    or in parts -> (hdr_off, out_off, out_off_host): device int64 tensors of chunks + 1 entries -- chunk k's header is at hdr_off[k]
+    and its bytes are [out_off[k], out_off[k + 1]) of the plain text; the closing entries are the stream's length and its decoded size
+    -- and a host copy of out_off as a numpy array.  t[hdr_off[k]:hdr_off[k + 1]] is a one-chunk item for
+    decompress_streams_spans_into.  This is the once-per-stream step: the serial header walk, and it waits for the device (twice when
+    the default table of t.numel() // block + 16 chunks was too small).  A header error raises what decompress_stream_device raises."""
+    import torch
+    t = _check_device_bytes(t, "t")
+    if max_chunks is None:
+        max_chunks = t.numel() // max(16, int(block_size)) + 16
+    with torch.cuda.device(t.device):
+        L = _lib.lib()
+        dev = t.device
+        info_dev = torch.zeros(C.sizeof(_lib.StreamInfo), dtype=torch.uint8, device=dev)
+        for _ in range(2):
+            hdr_off = torch.empty(max_chunks + 1, dtype=torch.int64, device=dev)
+            out_off = torch.empty(max_chunks + 1, dtype=torch.int64, device=dev)
+            _lib.check(L.lz4hip_stream_directory_device(t.data_ptr(), t.numel(), max_chunks, hdr_off.data_ptr(), out_off.data_ptr(),
+                                                        info_dev.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+            info = _read_info(info_dev, _lib.StreamInfo)
+            if info.error != _lib.STREAM_TABLE_FULL:
+                break
+            max_chunks = int(info.chunks)
+        if info.error != _lib.STREAM_OK:
+            raise _stream_error(info)
+        k = int(info.chunks) + 1
+        return hdr_off[:k], out_off[:k], out_off[:k].cpu().numpy()
+
+
+def decompress_stream_range(t, directory, start: int, length: int):
+    """Bytes [start, start + length) of the plain text of the LZ4Stream buffer t, given its stream_directory: decodes the chunks that
+    cover the range -- whole chunks, as one-chunk spans in one decompress_streams_spans_into call into a chunk-aligned buffer -- and
+    returns the length-byte view of it.  Waits for the device once, for the outcome."""
+    import torch
+    t = _check_device_bytes(t, "t")
+    hdr_off, out_off, host = directory
+    start, length = int(start), int(length)
+    total = int(host[-1])
+    if start < 0 or length < 0 or start + length > total:
+        raise ArgumentException(f"the range is outside the stream's {total} decoded bytes")
+    if length == 0:
+        return torch.empty(0, dtype=torch.uint8, device=t.device)
+    k0 = int(np.searchsorted(host, start, side="right")) - 1            # the chunk that holds `start`, and the one that holds the last byte
+    k1 = int(np.searchsorted(host, start + length - 1, side="right")) - 1
+    out = torch.empty(int(host[k1 + 1] - host[k0]), dtype=torch.uint8, device=t.device)
+    res = decompress_streams_spans_into(t, hdr_off[k0:k1 + 1], hdr_off[k0 + 1:k1 + 2], out, max_chunks=k1 - k0 + 1)
+    check_streams_into(res[3], res[4])
+    return out[start - int(host[k0]):start - int(host[k0]) + length]
 
 
 def read_streams_info(info):

@@ -13,7 +13,7 @@ import numpy as np
 
 from . import _lib
 from .codec import _CORRUPT, ArgumentException
-from .stream import _check_device_batch, _check_host_batch, _check_out, _read_info
+from .stream import _check_device_batch, _check_device_spans, _check_host_batch, _check_out, _read_info
 
 _WRAP_INVALID = "inputBuffer size of inputLength is invalid"
 _MESSAGES = {
@@ -114,6 +114,53 @@ def unwrap_into(packed, offsets, out):
                                                out.data_ptr(), out.numel(), out_off.data_ptr(), status.data_ptr(), info.data_ptr(),
                                                written.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
         return out_off, status[:n], info, written
+
+
+def select_spans(offsets, sel):
+    """The spans of chosen entries of an arena, on the device, on torch's current stream, without waiting for it -> (begin, end):
+    begin[j] = offsets[sel[j]], end[j] = offsets[sel[j] + 1] for the int64 CUDA tensors offsets[n + 1] and sel[m]; a sel[j] outside
+    [0, n) gives (-1, -1), which unwrap_spans_into and stream.decompress_streams_spans_into answer with the bad-offsets status for that
+    item.  (Through the library's kernel: what a C or C# caller, who has no torch to index with, calls.)"""
+    import torch
+    for name, t in (("offsets", offsets), ("sel", sel)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.int64 or t.dim() != 1:
+            raise ArgumentException(f"{name} must be a 1-D int64 CUDA tensor")
+    if offsets.numel() < 1:
+        raise ArgumentException("offsets must hold n + 1 entries")
+    if sel.device != offsets.device:
+        raise ArgumentException("offsets and sel must be on the same device")
+    offsets, sel = offsets.contiguous(), sel.contiguous()
+    with torch.cuda.device(offsets.device):
+        dev = offsets.device
+        m = sel.numel()
+        begin = torch.empty(m, dtype=torch.int64, device=dev)
+        end = torch.empty(m, dtype=torch.int64, device=dev)
+        _lib.check(_lib.lib().lz4hip_spans_select_device(offsets.data_ptr(), offsets.numel() - 1, sel.data_ptr(), m, begin.data_ptr(),
+                                                         end.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+        return begin, end
+
+
+def unwrap_spans_into(packed, begin, end, out):
+    """unwrap_into for CHOSEN messages of an arena: message j of the call is packed[begin[j]:end[j]] (int64 CUDA tensors of m entries,
+    from select_spans or the caller's own index; any order, repeats, overlaps and holes), in ONE device call whose cost follows m ->
+    (out_off, status, info, written_messages) as unwrap_into returns them, indexed by position in the call; check_unwrap_into reads
+    them.  A span outside the buffer gets the bad-offsets status and no bytes."""
+    import torch
+    packed, begin, end = _check_device_spans(packed, begin, end)
+    out = _check_out(out, packed)
+    with torch.cuda.device(packed.device):
+        L = _lib.lib()
+        dev = packed.device
+        m = begin.numel()
+        out_off = torch.empty(m + 1, dtype=torch.int64, device=dev)
+        status = torch.empty(max(m, 1), dtype=torch.int32, device=dev)
+        info = torch.zeros(C.sizeof(_lib.UnwrapInfo), dtype=torch.uint8, device=dev)
+        written = torch.zeros(1, dtype=torch.int64, device=dev)
+        scratch = torch.empty(L.lz4hip_unwrap_into_scratch_bytes(m), dtype=torch.uint8, device=dev)
+        _lib.check(L.lz4hip_unwrap_spans_into_device(packed.data_ptr(), packed.numel(), begin.data_ptr(), end.data_ptr(), m, scratch.data_ptr(),
+                                                     scratch.numel(), out.data_ptr(), out.numel(), out_off.data_ptr(), status.data_ptr(),
+                                                     info.data_ptr(), written.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+        return out_off, status[:m], info, written
 
 
 def read_unwrap_info(info):
