@@ -569,8 +569,8 @@ int lz4hip_decode_compact_host(const lz4hip_batch_t* b, int64_t round_blocks,
                                lz4hip_compact_info_t* info);
 
 /* ---- legacy frames ---------------------------------------------------------------------------------
- * The frame of the demo command-line tool that ships with the reference (original/lz4demo.c:84-87, 167-317), the one format here that
- * files from outside the lz4net world arrive in:
+ * The frame of the demo command-line tool that ships with the reference (original/lz4demo.c:84-87, 167-317): the format files
+ * written by that tool (and by lz4 before r120) arrive in; files from current tools use the LZ4 frame further down:
  *     LE32 magic 0x184C2102   { LE32 compressedSize  payload }*
  * The writer cuts a source of src_len bytes into ceil(src_len / chunk_size) chunks (8 MiB in the tool) and compresses each with
  * LZ4_compress / LZ4_compressHC into an LZ4_compressBound buffer; an empty source is the 4 magic bytes alone.  The reader checks the
@@ -660,6 +660,87 @@ int lz4hip_frame_decode_compact_device(const void* src, int64_t src_len, int32_t
  * the decoded size it returns LZ4HIP_E_ARGUMENT with *info filled in (a size query: dst_cap = 0). */
 int lz4hip_frame_encode_host(const void* src, int64_t src_len, int32_t chunk_size, int mode, void* dst, int64_t dst_cap, int64_t* dst_len);
 int lz4hip_frame_decode_host(const void* src, int64_t src_len, int32_t chunk_size, void* dst, int64_t dst_cap, lz4hip_frame_info_t* info);
+
+/* ---- xxHash32 of rows, and LZ4 frames (magic 0x184D2204) on the device ---------------------------------------------------------------
+ * lz4hip_xxh32_rows_device: XXH32 with `seed` of n_rows rows of device bytes, row i at data + (off ? off[i] : i * stride) with length
+ * len ? len[i] : len_all (a negative length counts as 0), one uint32 per row into sums (device).  Four lanes per row, sixteen rows
+ * per wavefront; a single long row runs at the latency of its four chains, whatever the device.  Launch-only on `stream`; no byte
+ * outside a row is read.  0 or LZ4HIP_E_*; the arguments are checked before the device is looked for. */
+int lz4hip_xxh32_rows_device(const void* data, const int64_t* off, int64_t stride, const int32_t* len, int64_t len_all, uint32_t seed,
+                             uint32_t* sums, int64_t n_rows, void* stream);
+
+/* The LZ4 frame format (LZ4 Frame format v1.6.x): what `lz4`, LZ4F_compressFrame, K4os.Compression.LZ4.Streams and python-lz4 write.
+ *     LE32 0x184D2204  FLG  BD  [LE64 contentSize]  HC   { LE32 blockSize  data  [LE32 xxh32(data)] }*   LE32 0   [LE32 xxh32(content)]
+ * The contract is that of the lz4hip_frame_*_device calls: device pointers of the current device, launch-only on the caller's stream,
+ * no device value read on the host, no allocation, scratch from the caller (the *_scratch_bytes queries), arguments checked before the
+ * device is looked for, 0 or LZ4HIP_E_* returned.
+ *
+ * Encode flags: */
+#define LZ4HIP_LZ4F_BLOCK_CHECKSUM   1u   /* FLG.4: xxh32 of every block's stored bytes                                      */
+#define LZ4HIP_LZ4F_CONTENT_CHECKSUM 2u   /* FLG.2: xxh32 of the whole source -- ONE row of the checksum kernel, serial work */
+#define LZ4HIP_LZ4F_CONTENT_SIZE     4u   /* FLG.3: the source's length in the descriptor (omitted for an empty source)      */
+/* Decode flags: which of the checksums the frame carries are verified */
+#define LZ4HIP_LZ4F_VERIFY_BLOCKS    1u
+#define LZ4HIP_LZ4F_VERIFY_CONTENT   2u   /* one serial row over dst[0, decoded_bytes): only when all of it was written and no block is bad */
+/* Outcomes (lz4hip_lz4f_info_t.error).  Precedence, as a sequential reader meets them: TABLE_FULL; a descriptor error (no block is
+ * walked then); the lowest bad block (BLOCK_CHECKSUM_ERROR / CORRUPT_BLOCK, at its size field); the walk's error (TRUNCATED /
+ * BAD_BLOCK_SIZE: it lies after every tabled block); CONTENT_SIZE_ERROR; CONTENT_CHECKSUM_ERROR. */
+#define LZ4HIP_LZ4F_OK                     0
+#define LZ4HIP_LZ4F_BAD_MAGIC              1   /* fewer than 4 bytes, or neither the frame magic nor a skippable one */
+#define LZ4HIP_LZ4F_BAD_HEADER             2   /* version, a reserved bit, or a block size id below 4 */
+#define LZ4HIP_LZ4F_HEADER_CHECKSUM        3
+#define LZ4HIP_LZ4F_UNSUPPORTED_LINKED     4   /* FLG.5 clear: linked blocks decode only in order, each against the 64 KiB before it */
+#define LZ4HIP_LZ4F_UNSUPPORTED_DICT       5   /* FLG.0 set */
+#define LZ4HIP_LZ4F_SLOT_TOO_SMALL         6   /* the frame's block maximum exceeds slot_bytes: call again with .block_max */
+#define LZ4HIP_LZ4F_TRUNCATED              7   /* the frame ends inside the descriptor, a size field, data, a checksum, or before its EndMark */
+#define LZ4HIP_LZ4F_BAD_BLOCK_SIZE         8   /* a size field above the frame's block maximum (tested before the truncation rule) */
+#define LZ4HIP_LZ4F_CORRUPT_BLOCK          9   /* a block did not decode into <= the frame's block maximum */
+#define LZ4HIP_LZ4F_BLOCK_CHECKSUM_ERROR   10
+#define LZ4HIP_LZ4F_CONTENT_SIZE_ERROR     11
+#define LZ4HIP_LZ4F_CONTENT_CHECKSUM_ERROR 12
+#define LZ4HIP_LZ4F_TABLE_FULL             13  /* more blocks than max_blocks; .blocks = the count needed */
+#define LZ4HIP_LZ4F_KIND_FRAME     0
+#define LZ4HIP_LZ4F_KIND_SKIPPABLE 1           /* magic 0x184D2A50 .. 0x184D2A5F: frame_bytes = 8 + its size, no output */
+typedef struct lz4hip_lz4f_info {
+    int64_t blocks;          /* data blocks in the frame */
+    int64_t decoded_bytes;   /* bytes of all good blocks: the size dst needs (a bad block takes 0 bytes, its neighbours pack around it) */
+    int64_t good_bytes;      /* what a sequential reader had written when it stopped */
+    int64_t error_offset;    /* where in the frame the outcome was met, -1 for none */
+    int64_t content_size;    /* the descriptor's, -1 if absent */
+    int64_t frame_bytes;     /* everything up to and including the content checksum: an appended frame starts there (meaningful without a walk error) */
+    int32_t error;           /* LZ4HIP_LZ4F_* */
+    int32_t kind;            /* LZ4HIP_LZ4F_KIND_* */
+    int32_t block_max;       /* the frame's block maximum in bytes (0: the descriptor did not parse) */
+    int32_t flg, bd;         /* the descriptor's bytes */
+    int32_t checks;          /* bits 0-1: block checksums, bits 2-3: content checksum; 0 absent, 1 verified, 2 present but not checked */
+} lz4hip_lz4f_info_t;
+
+/* Upper bound of a frame of src_len bytes (every block stored raw); LZ4HIP_E_ARGUMENT for a block_size_id other than 0, 4 .. 7 or an
+ * unknown flag.  block_size_id: 4 = 64 KiB, 5 = 256 KiB, 6 = 1 MiB, 7 = 4 MiB; 0 means 4, the format library's default. */
+int64_t lz4hip_lz4f_bound(int64_t src_len, int block_size_id, unsigned flags);
+int64_t lz4hip_lz4f_encode_scratch_bytes(int64_t src_len, int block_size_id);
+/* slot_bytes: the caller's bound on the frame's block maximum (it sizes the ring): 65536, 262144, 1048576, 4194304, or 0 = 4194304;
+ * max_blocks >= 1 table rows; round_blocks as in lz4hip_decode_compact_device (0: one round) */
+int64_t lz4hip_lz4f_decode_scratch_bytes(int32_t slot_bytes, int64_t max_blocks, int64_t round_blocks);
+
+/* Encode one frame: independent blocks, no dictionary, a block that does not shrink stored raw (the format library's rule: the block
+ * encoder gets length - 1 bytes of room).  mode: LZ4HIP_MODE_FAST or LZ4HIP_MODE_HC, the same format either way.  dst_cap >=
+ * lz4hip_lz4f_bound; the frame's length goes to *dst_len (device).  The bytes differ from liblz4's (another parse), the descriptor's
+ * do not; every conforming reader reads them. */
+int lz4hip_lz4f_encode_device(const void* src, int64_t src_len, int block_size_id, int mode, unsigned flags, void* dst, int64_t dst_cap,
+                              int64_t* dst_len, void* scratch, int64_t scratch_bytes, void* stream);
+/* Decode ONE frame (or skip one skippable frame) at src in one call: the walk over the size fields (one wavefront, one dependent load
+ * per block), the block checksums, the compact decode of every block through a ring of slot_bytes slots -- a raw block is copied from
+ * the source -- packed back to back into dst and clipped at dst_cap (any value >= 0; 0 is a size query), the content size and the
+ * content checksum.  *info (device) receives the record.  Appended frames are the caller's loop over info.frame_bytes.  One wavefront
+ * decodes one block: a frame of 4 MiB blocks decodes like the legacy frame's 8 MiB chunks. */
+int lz4hip_lz4f_decode_device(const void* src, int64_t src_len, int32_t slot_bytes, int64_t max_blocks, int64_t round_blocks, unsigned flags,
+                              void* scratch, int64_t scratch_bytes, void* dst, int64_t dst_cap, lz4hip_lz4f_info_t* info, void* stream);
+/* Host-pointer forms, staged like lz4hip_frame_*_host.  Encode returns 0 or LZ4HIP_E_*; *dst_len on the host.  Decode returns
+ * info->error (0 or a positive LZ4HIP_LZ4F_* code, with dst[0, decoded_bytes) filled) or LZ4HIP_E_*; with dst_cap below the decoded
+ * size only *info is filled and LZ4HIP_E_ARGUMENT returned (dst_cap = 0: a size query). */
+int lz4hip_lz4f_encode_host(const void* src, int64_t src_len, int block_size_id, int mode, unsigned flags, void* dst, int64_t dst_cap, int64_t* dst_len);
+int lz4hip_lz4f_decode_host(const void* src, int64_t src_len, unsigned flags, void* dst, int64_t dst_cap, lz4hip_lz4f_info_t* info);
 
 /* ---- diagnostics ---------------------------------------------------------------------------------
  * Launch counters per kernel family since the library was loaded: which block->hardware mapping a call

@@ -5,6 +5,8 @@
   lz4net_amd.stream        LZ4Stream chunk framing with all chunks of a buffer in one GPU batch; compress_streams_* / decompress_streams_*
                            do the same for MANY buffers per call, the chunks of all of them in one batch (lz4hip_streams_*)
   lz4net_amd.wrap          batches of Wrap / WrapHC / Unwrap messages framed on the device (lz4hip_wrap_*)
+  lz4net_amd.lz4_frame     LZ4 frames (magic 0x184D2204, what every current lz4 tool reads and writes) encoded and decoded on the
+                           device in one call (lz4hip_lz4f_*), and XXH32 of rows of device bytes
   lz4net_amd._lib          ctypes binding of liblz4hip.so (include/lz4hip.h)
 
 The codec itself is hand-written HIP (lz4net_amd/csrc); Python only moves pointers.

@@ -76,6 +76,22 @@ class FrameInfo(C.Structure):
 FRAME_OK, FRAME_BAD_MAGIC, FRAME_TRUNCATED, FRAME_BAD_SIZE, FRAME_CORRUPT_BLOCK, FRAME_TABLE_FULL = range(6)
 
 
+class Lz4fInfo(C.Structure):
+    """struct lz4hip_lz4f_info (include/lz4hip.h)."""
+    _fields_ = [("blocks", C.c_int64), ("decoded_bytes", C.c_int64), ("good_bytes", C.c_int64), ("error_offset", C.c_int64),
+                ("content_size", C.c_int64), ("frame_bytes", C.c_int64), ("error", C.c_int32), ("kind", C.c_int32), ("block_max", C.c_int32),
+                ("flg", C.c_int32), ("bd", C.c_int32), ("checks", C.c_int32)]
+
+
+(LZ4F_OK, LZ4F_BAD_MAGIC, LZ4F_BAD_HEADER, LZ4F_HEADER_CHECKSUM, LZ4F_UNSUPPORTED_LINKED, LZ4F_UNSUPPORTED_DICT, LZ4F_SLOT_TOO_SMALL,
+ LZ4F_TRUNCATED, LZ4F_BAD_BLOCK_SIZE, LZ4F_CORRUPT_BLOCK, LZ4F_BLOCK_CHECKSUM_ERROR, LZ4F_CONTENT_SIZE_ERROR, LZ4F_CONTENT_CHECKSUM_ERROR,
+ LZ4F_TABLE_FULL) = range(14)
+LZ4F_BLOCK_CHECKSUM, LZ4F_CONTENT_CHECKSUM, LZ4F_CONTENT_SIZE = 1, 2, 4
+LZ4F_VERIFY_BLOCKS, LZ4F_VERIFY_CONTENT = 1, 2
+LZ4F_KIND_FRAME, LZ4F_KIND_SKIPPABLE = 0, 1
+LZ4F_CHECK_ABSENT, LZ4F_CHECK_VERIFIED, LZ4F_CHECK_SKIPPED = 0, 1, 2
+
+
 # every symbol include/lz4hip.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("lz4hip_codec_name", C.c_char_p, []),
@@ -172,6 +188,16 @@ SYMBOLS = [
                                                      C.c_void_p, C.c_void_p]),
     ("lz4hip_frame_encode_host", C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
     ("lz4hip_frame_decode_host", C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.POINTER(FrameInfo)]),
+    ("lz4hip_xxh32_rows_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_uint32, C.c_void_p, C.c_int64, C.c_void_p]),
+    ("lz4hip_lz4f_bound", C.c_int64, [C.c_int64, C.c_int, C.c_uint]),
+    ("lz4hip_lz4f_encode_scratch_bytes", C.c_int64, [C.c_int64, C.c_int]),
+    ("lz4hip_lz4f_decode_scratch_bytes", C.c_int64, [C.c_int32, C.c_int64, C.c_int64]),
+    ("lz4hip_lz4f_encode_device", C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_uint, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
+                                            C.c_void_p]),
+    ("lz4hip_lz4f_decode_device", C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_uint, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                            C.c_void_p, C.c_void_p]),
+    ("lz4hip_lz4f_encode_host", C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_uint, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
+    ("lz4hip_lz4f_decode_host", C.c_int, [C.c_void_p, C.c_int64, C.c_uint, C.c_void_p, C.c_int64, C.POINTER(Lz4fInfo)]),
 ]
 
 _lib = None

@@ -1911,4 +1911,63 @@ int lz4hip_frame_decode_host(const void* src, int64_t src_len, int32_t chunk_siz
     return frame_decode_host(be, src, src_len, chunk_size, dst, dst_cap, info);
 }
 
+// (the arguments are checked before the device is looked for: a bad call is LZ4HIP_E_ARGUMENT on any machine)
+int lz4hip_xxh32_rows_device(const void* data, const int64_t* off, int64_t stride, const int32_t* len, int64_t len_all, uint32_t seed,
+                             uint32_t* sums, int64_t n_rows, void* stream)
+{
+    HipBackend be = { (hipStream_t)stream };
+    if (int rc = xxh32_rows_check(be, data, off, stride, len, len_all, sums, n_rows)) return rc;
+    if (n_rows == 0) return 0;
+    if (int rc = ensure_device()) return rc;
+    const XxhRows rows = { (const uint8_t*)data, off, stride, len, nullptr, len_all, seed, sums, n_rows };
+    return xxh32_rows_run(be, rows);
+}
+
+int64_t lz4hip_lz4f_bound(int64_t src_len, int block_size_id, unsigned flags) { return lz4f_bound(src_len, block_size_id, flags); }
+
+int64_t lz4hip_lz4f_encode_scratch_bytes(int64_t src_len, int block_size_id)
+{
+    if (!lz4f_id_valid(block_size_id)) return fail(LZ4HIP_E_ARGUMENT, "lz4f encode: block_size_id must be 0 (64 KiB) or 4 .. 7");
+    return lz4f_encode_scratch(nullptr, src_len < 0 ? 0 : src_len, lz4f_block_bytes(lz4f_id(block_size_id))).bytes;
+}
+
+int64_t lz4hip_lz4f_decode_scratch_bytes(int32_t slot_bytes, int64_t max_blocks, int64_t round_blocks)
+{
+    return lz4f_decode_scratch_bytes(slot_bytes, max_blocks, round_blocks);
+}
+
+int lz4hip_lz4f_encode_device(const void* src, int64_t src_len, int block_size_id, int mode, unsigned flags, void* dst, int64_t dst_cap,
+                              int64_t* dst_len, void* scratch, int64_t scratch_bytes, void* stream)
+{
+    HipBackend be = { (hipStream_t)stream };
+    Lz4fEncodePlan p;
+    if (int rc = lz4f_encode_plan(be, src, src_len, block_size_id, mode, flags, dst, dst_cap, dst_len, scratch, scratch_bytes, p)) return rc;
+    if (int rc = ensure_device()) return rc;
+    return lz4f_encode_run(be, p);
+}
+
+int lz4hip_lz4f_decode_device(const void* src, int64_t src_len, int32_t slot_bytes, int64_t max_blocks, int64_t round_blocks, unsigned flags,
+                              void* scratch, int64_t scratch_bytes, void* dst, int64_t dst_cap, lz4hip_lz4f_info_t* info, void* stream)
+{
+    HipBackend be = { (hipStream_t)stream };
+    Lz4fDecodePlan p;
+    if (int rc = lz4f_decode_plan(be, src, src_len, slot_bytes, max_blocks, round_blocks, flags, scratch, scratch_bytes, dst, dst_cap, info, p)) return rc;
+    if (int rc = ensure_device()) return rc;
+    return lz4f_decode_run(be, p);
+}
+
+int lz4hip_lz4f_encode_host(const void* src, int64_t src_len, int block_size_id, int mode, unsigned flags, void* dst, int64_t dst_cap, int64_t* dst_len)
+{
+    HipBackend be = {};
+    if (int rc = stream_host_context(be)) return rc;
+    return lz4f_encode_host(be, src, src_len, block_size_id, mode, flags, dst, dst_cap, dst_len);
+}
+
+int lz4hip_lz4f_decode_host(const void* src, int64_t src_len, unsigned flags, void* dst, int64_t dst_cap, lz4hip_lz4f_info_t* info)
+{
+    HipBackend be = {};
+    if (int rc = stream_host_context(be)) return rc;
+    return lz4f_decode_host(be, src, src_len, flags, dst, dst_cap, info);
+}
+
 }  // extern "C"

@@ -1,5 +1,5 @@
 // lz4hip_framing.hpp -- host side of the framing paths (LZ4Stream buffers, wrapped messages, batches of LZ4Stream buffers, legacy
-// frames), of the block batch's size query (lz4hip_sizes.hpp), of its packed encode (lz4hip_packed.hpp) and of its compact decode
+// frames, LZ4 frames), of the block batch's size query (lz4hip_sizes.hpp), of its packed encode (lz4hip_packed.hpp) and of its compact decode
 // (lz4hip_compact.hpp): the scratch
 // layouts, the grids and the kernel sequences around the block codec, written ONCE for the library (lz4hip_api.hip, HipBackend) and for
 // the CPU emulator (tests/simt/emu_framing.hpp, EmuBackend).  Host code only: no kernel is defined here and nothing here calls the HIP
@@ -29,6 +29,7 @@
 #include "lz4hip_frame.hpp"
 #include "lz4hip_packed.hpp"
 #include "lz4hip_compact.hpp"
+#include "lz4hip_lz4f.hpp"
 
 #include "../../include/lz4hip.h"
 
@@ -1505,6 +1506,286 @@ int frame_decode_compact(B& be, const void* src, int64_t src_len, int32_t chunk_
     return frame_decode_compact_run(be, p);
 }
 
+// ---- xxHash32 of rows, and LZ4 frames (lz4hip_lz4f.hpp) ----------------------------------------------------------------------------------
+static_assert(kLz4fBlockChecksum == LZ4HIP_LZ4F_BLOCK_CHECKSUM && kLz4fContentChecksum == LZ4HIP_LZ4F_CONTENT_CHECKSUM &&
+              kLz4fContentSize == LZ4HIP_LZ4F_CONTENT_SIZE && kLz4fVerifyBlocks == LZ4HIP_LZ4F_VERIFY_BLOCKS &&
+              kLz4fVerifyContent == LZ4HIP_LZ4F_VERIFY_CONTENT && kLz4fKindSkippable == LZ4HIP_LZ4F_KIND_SKIPPABLE, "lz4f flags");
+static_assert(kLz4fOk == LZ4HIP_LZ4F_OK && kLz4fBadMagic == LZ4HIP_LZ4F_BAD_MAGIC && kLz4fBadHeader == LZ4HIP_LZ4F_BAD_HEADER &&
+              kLz4fHeaderChecksum == LZ4HIP_LZ4F_HEADER_CHECKSUM && kLz4fUnsupportedLinked == LZ4HIP_LZ4F_UNSUPPORTED_LINKED &&
+              kLz4fUnsupportedDict == LZ4HIP_LZ4F_UNSUPPORTED_DICT && kLz4fSlotTooSmall == LZ4HIP_LZ4F_SLOT_TOO_SMALL &&
+              kLz4fTruncated == LZ4HIP_LZ4F_TRUNCATED && kLz4fBadBlockSize == LZ4HIP_LZ4F_BAD_BLOCK_SIZE &&
+              kLz4fCorruptBlock == LZ4HIP_LZ4F_CORRUPT_BLOCK && kLz4fBlockChecksumError == LZ4HIP_LZ4F_BLOCK_CHECKSUM_ERROR &&
+              kLz4fContentSizeError == LZ4HIP_LZ4F_CONTENT_SIZE_ERROR && kLz4fContentChecksumError == LZ4HIP_LZ4F_CONTENT_CHECKSUM_ERROR &&
+              kLz4fTableFull == LZ4HIP_LZ4F_TABLE_FULL, "lz4f statuses");
+static_assert(sizeof(Lz4fInfo) == sizeof(lz4hip_lz4f_info_t) && offsetof(Lz4fInfo, frame_bytes) == offsetof(lz4hip_lz4f_info_t, frame_bytes) &&
+              offsetof(Lz4fInfo, error) == offsetof(lz4hip_lz4f_info_t, error) && offsetof(Lz4fInfo, checks) == offsetof(lz4hip_lz4f_info_t, checks),
+              "Lz4fInfo must mirror lz4hip_lz4f_info_t");
+
+// sixteen rows per wavefront, four wavefronts per workgroup; more rows than the grid holds share wavefronts
+inline Grid xxh_grid(int64_t n)
+{
+    const int64_t rows = kXxhRowsPerWave * (kXxhThreads / 64), g = (n + rows - 1) / rows;
+    return { g < 1 ? 1u : (g > kStreamMaxGroups ? kStreamMaxGroups : (unsigned)g), kGridItems };
+}
+
+template <class B>
+int xxh32_rows_run(B& be, const XxhRows& rows)
+{
+    if (rows.n <= 0) return 0;
+    be.launch(xxh32_rows_kernel, xxh_grid(rows.n), kXxhThreads, rows);
+    return be.last_error();
+}
+
+template <class B>
+int xxh32_rows_check(B& be, const void* data, const int64_t* off, int64_t stride, const int32_t* len, int64_t len_all, const uint32_t* sums, int64_t n)
+{
+    if (n < 0) return be.fail(LZ4HIP_E_ARGUMENT, "xxh32 rows: n_rows < 0");
+    if (n > 0 && !sums) return be.fail(LZ4HIP_E_ARGUMENT, "xxh32 rows: sums is NULL");
+    if (n > 0 && !data && (len || len_all > 0)) return be.fail(LZ4HIP_E_ARGUMENT, "xxh32 rows: data is NULL");
+    return 0;
+}
+
+inline bool lz4f_id_valid(int block_size_id) { return block_size_id == 0 || (block_size_id >= 4 && block_size_id <= 7); }
+inline int lz4f_id(int block_size_id) { return block_size_id == 0 ? 4 : block_size_id; }                        // (of a valid id)
+constexpr unsigned kLz4fEncodeFlags = kLz4fBlockChecksum | kLz4fContentChecksum | kLz4fContentSize;
+// an empty source carries no content size: 0 means "unknown" to the format library, which writes none
+inline unsigned lz4f_flags(int64_t src_len, unsigned flags) { return src_len > 0 ? flags : flags & ~kLz4fContentSize; }
+inline int32_t lz4f_head_len(unsigned flags) { return 7 + ((flags & kLz4fContentSize) ? 8 : 0); }
+
+// the descriptor, every block stored raw behind its size field (and before its checksum), the EndMark and the content checksum
+inline int64_t lz4f_bound(int64_t src_len, int block_size_id, unsigned flags)
+{
+    if (!lz4f_id_valid(block_size_id) || (flags & ~kLz4fEncodeFlags)) return LZ4HIP_E_ARGUMENT;
+    if (src_len < 0) src_len = 0;
+    flags = lz4f_flags(src_len, flags);
+    const int64_t n = stream_chunks(src_len, lz4f_block_bytes(lz4f_id(block_size_id)));
+    return lz4f_head_len(flags) + src_len + n * (4 + ((flags & kLz4fBlockChecksum) ? 4 : 0)) + 4 + ((flags & kLz4fContentChecksum) ? 4 : 0);
+}
+
+// the encoder's slot per block: a block is given one byte less than its length
+inline int64_t lz4f_stride(int64_t src_len, int64_t block) { return src_len < block ? src_len : block; }
+
+// lz4f encode: the encoder's output (block k at k * stride), block lengths, capacities, results, the checksum rows, the n + 1 checksums,
+// the descriptor, the n + 2 sizes / offsets, tile sums
+struct Lz4fEncodeScratch {
+    uint8_t* comp; int32_t* lens; int32_t* caps; int32_t* result; int64_t* row_off; int32_t* row_len; uint32_t* sums; uint8_t* head; int64_t* offs;
+    int64_t* partial; int64_t bytes;
+};
+inline Lz4fEncodeScratch lz4f_encode_scratch(void* scratch, int64_t src_len, int64_t block)
+{
+    const int64_t n = stream_chunks(src_len, block);
+    Carver c(scratch);
+    Lz4fEncodeScratch l;
+    l.comp = c.take_as<uint8_t>(n * lz4f_stride(src_len, block));
+    l.lens = c.take_as<int32_t>(4 * n);
+    l.caps = c.take_as<int32_t>(4 * n);
+    l.result = c.take_as<int32_t>(4 * n);
+    l.row_off = c.take_as<int64_t>(8 * n);
+    l.row_len = c.take_as<int32_t>(4 * n);
+    l.sums = c.take_as<uint32_t>(4 * (n + 1));
+    l.head = c.take_as<uint8_t>(kLz4fHeadMax);
+    l.offs = c.take_as<int64_t>(8 * (n + 2));
+    l.partial = c.take_as<int64_t>(8 * scan_tiles(n + 2));
+    l.bytes = c.at;
+    return l;
+}
+
+struct Lz4fEncodePlan {
+    Lz4fEncodeArgs a; int mode; int32_t* lens; int32_t* caps; int64_t* row_off; int32_t* row_len; int64_t* partial; uint8_t* dst; int64_t dst_cap;
+    int64_t* dst_len; int64_t bound;
+};
+
+// p.a.comp and p.a.result are the block encoder's to write: block k at k * p.a.stride.  An empty source is a descriptor and an EndMark.
+template <class B>
+int lz4f_encode_run(B& be, const Lz4fEncodePlan& p)
+{
+    const Lz4fEncodeArgs& a = p.a;
+    if (a.n > 0) {
+        be.launch(lz4f_lens_kernel, stream_grid(a.n), kStreamThreads, p.lens, p.caps, a.n, a.src_len, a.block);
+        LZ4HIP_FRAMING_TRY(be.last_error());
+        lz4hip_batch_t b = {};
+        b.src = a.src; b.src_stride = a.block; b.src_len = p.lens;
+        b.dst = (void*)a.comp; b.dst_stride = a.stride; b.dst_cap = p.caps;
+        b.src_len_all = a.block; b.result = (int32_t*)a.result; b.n_blocks = a.n;
+        LZ4HIP_FRAMING_TRY(be.encode(&b, p.mode));
+        if (a.flags & kLz4fBlockChecksum) {
+            be.launch(lz4f_rows_kernel, stream_grid(a.n), kStreamThreads, a, p.row_off, p.row_len);
+            const XxhRows rows = { a.src, p.row_off, 0, p.row_len, nullptr, 0, 0u, a.sums, a.n };
+            LZ4HIP_FRAMING_TRY(xxh32_rows_run(be, rows));
+        }
+    }
+    if (a.flags & kLz4fContentChecksum) {
+        const XxhRows content = { a.src, nullptr, 0, nullptr, nullptr, a.src_len, 0u, a.sums + a.n, 1 };
+        LZ4HIP_FRAMING_TRY(xxh32_rows_run(be, content));
+    }
+    be.launch(lz4f_head_kernel, fixed_grid(1), 64, a);
+    be.launch(lz4f_sizes_kernel, stream_grid(a.n + 2), kStreamThreads, a);
+    launch_scan(be, a.offs, a.n + 2, p.partial, p.dst_len);
+    Lz4fLayout layout = { a };
+    be.launch(lz4f_pack_kernel, copy_grid(p.bound), kStreamThreads, layout, p.dst, p.dst_len, p.dst_cap);
+    return be.last_error();
+}
+
+template <class B>
+int lz4f_encode_plan(B& be, const void* src, int64_t src_len, int block_size_id, int mode, unsigned flags, void* dst, int64_t dst_cap, int64_t* dst_len,
+                     void* scratch, int64_t scratch_bytes, Lz4fEncodePlan& p)
+{
+    if (src_len < 0 || !dst_len) return be.fail(LZ4HIP_E_ARGUMENT, "lz4f encode: src_len < 0 or dst_len is NULL");
+    if (!lz4f_id_valid(block_size_id)) return be.fail(LZ4HIP_E_ARGUMENT, "lz4f encode: block_size_id must be 0 (64 KiB) or 4 .. 7");
+    if (flags & ~kLz4fEncodeFlags) return be.fail(LZ4HIP_E_ARGUMENT, "lz4f encode: unknown flag");
+    if (mode != LZ4HIP_MODE_FAST && mode != LZ4HIP_MODE_HC) return be.fail(LZ4HIP_E_ARGUMENT, "mode must be LZ4HIP_MODE_FAST or LZ4HIP_MODE_HC");
+    const int id = lz4f_id(block_size_id);
+    const int64_t block = lz4f_block_bytes(id), n = stream_chunks(src_len, block);
+    if (n >= 0x7FFFFFFF) return be.fail(LZ4HIP_E_ARGUMENT, "lz4f encode: more than 2^31 - 2 blocks");
+    p.bound = lz4f_bound(src_len, block_size_id, flags);
+    if (dst_cap < p.bound) return be.fail(LZ4HIP_E_ARGUMENT, "lz4f encode: dst_cap < lz4hip_lz4f_bound");
+    const Lz4fEncodeScratch l = lz4f_encode_scratch(scratch, src_len, block);
+    if (scratch_bytes < l.bytes) return be.fail(LZ4HIP_E_ARGUMENT, "lz4f encode: scratch_bytes < lz4hip_lz4f_encode_scratch_bytes");
+    if ((n > 0 && !src) || !dst || !scratch) return be.fail(LZ4HIP_E_ARGUMENT, "lz4f encode: src, dst and scratch must be non-NULL");
+    Lz4fEncodeArgs& a = p.a;
+    a.src = (const uint8_t*)src; a.comp = l.comp; a.src_len = src_len; a.n = n; a.stride = lz4f_stride(src_len, block); a.block = (int32_t)block;
+    a.block_id = id; a.flags = lz4f_flags(src_len, flags); a.head_len = lz4f_head_len(a.flags);
+    a.result = l.result; a.sums = l.sums; a.head = l.head; a.offs = l.offs;
+    p.mode = mode; p.lens = l.lens; p.caps = l.caps; p.row_off = l.row_off; p.row_len = l.row_len; p.partial = l.partial;
+    p.dst = (uint8_t*)dst; p.dst_cap = dst_cap; p.dst_len = dst_len;
+    return 0;
+}
+
+template <class B>
+int lz4f_encode(B& be, const void* src, int64_t src_len, int block_size_id, int mode, unsigned flags, void* dst, int64_t dst_cap, int64_t* dst_len,
+                void* scratch, int64_t scratch_bytes)
+{
+    Lz4fEncodePlan p;
+    LZ4HIP_FRAMING_TRY(lz4f_encode_plan(be, src, src_len, block_size_id, mode, flags, dst, dst_cap, dst_len, scratch, scratch_bytes, p));
+    return lz4f_encode_run(be, p);
+}
+
+// lz4f decode: the table of max_blocks rows (the n + 1 checksums and what the walk found with it), then the compact decode's scratch for
+// max_blocks rows of slot_bytes
+inline bool lz4f_slot_valid(int32_t slot_bytes) { return slot_bytes == 0 || slot_bytes == 65536 || slot_bytes == 262144 || slot_bytes == 1048576 || slot_bytes == 4194304; }
+inline int32_t lz4f_slot(int32_t slot_bytes) { return slot_bytes == 0 ? 4194304 : slot_bytes; }                    // (of a valid slot_bytes)
+constexpr unsigned kLz4fDecodeFlags = kLz4fVerifyBlocks | kLz4fVerifyContent;
+
+inline Lz4fTables lz4f_tables(Carver& c, int64_t max_blocks)
+{
+    Lz4fTables t;
+    t.max_blocks = max_blocks;
+    t.walk = c.take_as<int64_t>(8 * kLz4fWalkSlots);
+    t.src_off = c.take_as<int64_t>(8 * max_blocks);
+    t.hdr_off = c.take_as<int64_t>(8 * max_blocks);
+    t.dst_off = c.take_as<int64_t>(8 * (max_blocks + 1));
+    t.stored = c.take_as<int32_t>(4 * max_blocks);
+    t.dec_len = c.take_as<int32_t>(4 * max_blocks);
+    t.sum_len = c.take_as<int32_t>(4 * max_blocks);
+    t.result = c.take_as<int32_t>(4 * max_blocks);
+    t.sums = c.take_as<uint32_t>(4 * (max_blocks + 1));
+    t.row = c.take_as<uint8_t>(max_blocks);
+    return t;
+}
+struct Lz4fDecodeScratch { Lz4fTables t; PackedScratch l; int64_t bytes; };
+inline Lz4fDecodeScratch lz4f_decode_scratch(void* scratch, int32_t slot, int64_t max_blocks, int64_t round_blocks)
+{
+    Carver c(scratch);
+    Lz4fDecodeScratch d;
+    d.t = lz4f_tables(c, max_blocks);
+    d.l = packed_scratch(c.take_as<uint8_t>(0), max_blocks, slot, round_blocks);
+    d.bytes = c.at + d.l.bytes;
+    return d;
+}
+inline int64_t lz4f_decode_scratch_bytes(int32_t slot_bytes, int64_t max_blocks, int64_t round_blocks)
+{
+    if (!lz4f_slot_valid(slot_bytes) || max_blocks < 1 || round_blocks < 0) return LZ4HIP_E_ARGUMENT;
+    return lz4f_decode_scratch(nullptr, lz4f_slot(slot_bytes), max_blocks, round_blocks).bytes;
+}
+
+struct Lz4fDecodePlan {
+    const uint8_t* src; int64_t src_len; int32_t slot_bytes; unsigned flags; Lz4fTables t; PackedScratch l; int64_t round, slot;
+    uint8_t* dst; int64_t dst_cap; Lz4fInfo* info;
+};
+
+// The walk, the block checksums, then packed_rounds_run's rounds over ALL max_blocks rows of the table with the twin sizes step and pack
+// layout (the rows past the walk's count are empty blocks, which decode to nothing), the record, the content checksum.  Nothing is
+// read on the host between the steps.  The decoders are handed the table's dec_len column through the round's sanitised copy: a raw
+// row and a row with a bad checksum arrive as empty blocks.
+template <class B>
+int lz4f_decode_run(B& be, const Lz4fDecodePlan& p)
+{
+    const Lz4fTables& t = p.t;
+    const int64_t n = t.max_blocks;
+    LZ4HIP_FRAMING_TRY(be.fill(t.src_off, 0, (size_t)(8 * n)));
+    LZ4HIP_FRAMING_TRY(be.fill(t.stored, 0, (size_t)(4 * n)));
+    LZ4HIP_FRAMING_TRY(be.fill(t.dec_len, 0, (size_t)(4 * n)));
+    LZ4HIP_FRAMING_TRY(be.fill(t.sum_len, 0, (size_t)(4 * n)));
+    LZ4HIP_FRAMING_TRY(be.fill(t.row, 0, (size_t)n));
+    be.launch(lz4f_walk_kernel, fixed_grid(1), 64, p.src, p.src_len, p.slot_bytes, t);
+    LZ4HIP_FRAMING_TRY(be.last_error());
+    if (p.flags & kLz4fVerifyBlocks) {
+        const XxhRows rows = { p.src, t.src_off, 0, t.sum_len, nullptr, 0, 0u, t.sums, n };
+        LZ4HIP_FRAMING_TRY(xxh32_rows_run(be, rows));
+        be.launch(lz4f_verify_kernel, stream_grid(n), kStreamThreads, p.src, t);
+    }
+    LZ4HIP_FRAMING_TRY(be.fill(p.l.state, 0, (size_t)kPackedStateBytes));
+    LZ4HIP_FRAMING_TRY(be.fill(p.l.state + kPackedBad, 0xFF, 8));      // the lowest bad block = none
+    const Grid pack_grid = copy_grid(p.round * p.slot);
+    int32_t parity = 0;
+    for (int64_t first = 0; first < n; first += p.round, parity ^= 1) {
+        PackedRound a;
+        a.first = first; a.cnt = n - first < p.round ? n - first : p.round; a.slot = p.slot; a.limit = p.slot_bytes; a.parity = parity;
+        a.cap_in = nullptr; a.caps = p.l.caps; a.result = t.result + first;
+        a.len_in = t.dec_len + first; a.lens_enc = p.l.lens;
+        a.ring = p.l.ring; a.offs = t.dst_off + first; a.lens = nullptr; a.state = p.l.state;
+        be.launch(packed_caps_kernel, stream_grid(a.cnt), kStreamThreads, a);
+        LZ4HIP_FRAMING_TRY(be.last_error());
+        lz4hip_batch_t rb = {};
+        rb.src = p.src; rb.src_off = t.src_off + first; rb.src_len = p.l.lens;
+        rb.dst = p.l.ring; rb.dst_stride = p.slot; rb.dst_cap = p.l.caps;
+        rb.result = a.result; rb.n_blocks = a.cnt;
+        LZ4HIP_FRAMING_TRY(be.decode(&rb, 0));
+        const Lz4fRound r = { a, p.src, t.src_off + first, t.stored + first, t.row + first, t.walk };
+        be.launch(lz4f_round_sizes_kernel, stream_grid(a.cnt), kStreamThreads, r);
+        launch_scan(be, a.offs, a.cnt, p.l.partial, p.l.state + kPackedTotal);
+        be.launch(packed_rebase_kernel, stream_grid(a.cnt), kStreamThreads, a);
+        Lz4fRoundLayout layout = { r };
+        be.launch(lz4f_round_pack_kernel, pack_grid, kStreamThreads, layout, p.dst, p.dst_cap);
+        LZ4HIP_FRAMING_TRY(be.last_error());
+    }
+    be.launch(lz4f_info_kernel, fixed_grid(1), 64, t, (const int64_t*)(p.l.state + kPackedBad), p.flags, p.dst_cap, p.info);
+    if (p.flags & kLz4fVerifyContent) {
+        const XxhRows content = { p.dst, nullptr, 0, nullptr, t.walk + kLz4fWalkContentLen, 0, 0u, t.sums + n, 1 };
+        LZ4HIP_FRAMING_TRY(xxh32_rows_run(be, content));
+        be.launch(lz4f_final_kernel, fixed_grid(1), 64, p.src, t, p.info);
+    }
+    return be.last_error();
+}
+
+template <class B>
+int lz4f_decode_plan(B& be, const void* src, int64_t src_len, int32_t slot_bytes, int64_t max_blocks, int64_t round_blocks, unsigned flags,
+                     void* scratch, int64_t scratch_bytes, void* dst, int64_t dst_cap, lz4hip_lz4f_info_t* info, Lz4fDecodePlan& p)
+{
+    if (src_len < 0 || max_blocks < 1 || round_blocks < 0 || dst_cap < 0 || !info || !scratch || (src_len > 0 && !src) || (dst_cap > 0 && !dst))
+        return be.fail(LZ4HIP_E_ARGUMENT, "lz4f decode: negative size, max_blocks < 1 or NULL pointer");
+    if (!lz4f_slot_valid(slot_bytes)) return be.fail(LZ4HIP_E_ARGUMENT, "lz4f decode: slot_bytes must be 0 (4 MiB), 65536, 262144, 1048576 or 4194304");
+    if (flags & ~kLz4fDecodeFlags) return be.fail(LZ4HIP_E_ARGUMENT, "lz4f decode: unknown flag");
+    if (packed_round(max_blocks, round_blocks) > 0x7FFFFFFF) return be.fail(LZ4HIP_E_ARGUMENT, "lz4f decode: more than 2^31 - 1 table rows in a round");
+    p.slot_bytes = lz4f_slot(slot_bytes);
+    const Lz4fDecodeScratch d = lz4f_decode_scratch(scratch, p.slot_bytes, max_blocks, round_blocks);
+    if (scratch_bytes < d.bytes) return be.fail(LZ4HIP_E_ARGUMENT, "lz4f decode: scratch_bytes < lz4hip_lz4f_decode_scratch_bytes");
+    // (an empty source's rows are all empty: any address will do for them)
+    p.src = src ? (const uint8_t*)src : (const uint8_t*)scratch; p.src_len = src_len; p.flags = flags; p.t = d.t; p.l = d.l;
+    p.round = packed_round(max_blocks, round_blocks); p.slot = packed_slot(p.slot_bytes);
+    p.dst = (uint8_t*)dst; p.dst_cap = dst_cap; p.info = (Lz4fInfo*)info;
+    return 0;
+}
+
+template <class B>
+int lz4f_decode(B& be, const void* src, int64_t src_len, int32_t slot_bytes, int64_t max_blocks, int64_t round_blocks, unsigned flags, void* scratch,
+                int64_t scratch_bytes, void* dst, int64_t dst_cap, lz4hip_lz4f_info_t* info)
+{
+    Lz4fDecodePlan p;
+    LZ4HIP_FRAMING_TRY(lz4f_decode_plan(be, src, src_len, slot_bytes, max_blocks, round_blocks, flags, scratch, scratch_bytes, dst, dst_cap, info, p));
+    return lz4f_decode_run(be, p);
+}
+
 // ---- the host-pointer calls ------------------------------------------------------------------------------------------------------------
 // Each stages its arguments in ONE device image, runs the device path above on it and copies the results out.  An image is a Carver's
 // walk over no buffer -- its pieces are offsets, good for any base -- plus the base of the backend's reserve.  That base may move
@@ -1818,6 +2099,78 @@ int frame_decode_host(B& be, const void* src, int64_t src_len, int32_t chunk_siz
     LZ4HIP_FRAMING_TRY(frame_decode(be, im.d, &h, max_chunks, im.d + table_at, table_bytes, im.d + out_at, out_bytes,
                                     (lz4hip_frame_info_t*)(im.d + info_at)));
     LZ4HIP_FRAMING_TRY(im.download_decoded(info, info_at, dst, out_at, h.decoded_bytes));
+    return info->error;
+}
+
+// The LZ4 frame's encoder staged the way frame_encode_host stages the legacy frame's.
+template <class B>
+int lz4f_encode_host(B& be, const void* src, int64_t src_len, int block_size_id, int mode, unsigned flags, void* dst, int64_t dst_cap, int64_t* dst_len)
+{
+    if (src_len < 0 || !dst_len || !dst || (src_len > 0 && !src)) return be.fail(LZ4HIP_E_ARGUMENT, "lz4f encode: negative size or NULL pointer");
+    if (!lz4f_id_valid(block_size_id) || (flags & ~kLz4fEncodeFlags)) return be.fail(LZ4HIP_E_ARGUMENT, "lz4f encode: block_size_id must be 0 or 4 .. 7, flags known");
+    const int64_t bound = lz4f_bound(src_len, block_size_id, flags);
+    if (dst_cap < bound) return be.fail(LZ4HIP_E_ARGUMENT, "lz4f encode: dst_cap < lz4hip_lz4f_bound");
+    // device image: [source | frame | scratch | length]
+    const int64_t scratch_bytes = lz4f_encode_scratch(nullptr, src_len, lz4f_block_bytes(lz4f_id(block_size_id))).bytes;
+    Carver c;
+    c.take(src_len);
+    const int64_t out_at = c.take(bound), scratch_at = c.take(scratch_bytes), len_at = c.take(256);
+    Image<B> im = { be };
+    LZ4HIP_FRAMING_TRY(im.reserve(c.at));
+    LZ4HIP_FRAMING_TRY(im.upload_source(src, src_len));
+    LZ4HIP_FRAMING_TRY(lz4f_encode(be, im.d, src_len, block_size_id, mode, flags, im.d + out_at, bound, im.i64(len_at), im.d + scratch_at, scratch_bytes));
+    int64_t total = 0;
+    LZ4HIP_FRAMING_TRY(im.download(&total, len_at, sizeof total));
+    LZ4HIP_FRAMING_TRY(be.sync());
+    LZ4HIP_FRAMING_TRY(im.download_encoded(dst, out_at, total));
+    *dst_len = total;
+    return 0;
+}
+
+// The descriptor lies in host memory here: the block maximum sizes the slot, the content size (or four times the frame) the output's
+// piece of the image and the table.  A table that was too small or an output that has to grow is decoded again with what the record
+// reported, three passes at most.  On dst_cap < decoded_bytes only *info is filled (a size query: dst_cap = 0).
+template <class B>
+int lz4f_decode_host(B& be, const void* src, int64_t src_len, unsigned flags, void* dst, int64_t dst_cap, lz4hip_lz4f_info_t* info)
+{
+    if (src_len < 0 || dst_cap < 0 || !info || (src_len > 0 && !src)) return be.fail(LZ4HIP_E_ARGUMENT, "lz4f decode: negative size or NULL pointer");
+    if (flags & ~kLz4fDecodeFlags) return be.fail(LZ4HIP_E_ARGUMENT, "lz4f decode: unknown flag");
+    const uint8_t* s = (const uint8_t*)src;
+    const int id = src_len >= 6 ? (s[5] >> 4) & 7 : 4;
+    const int32_t slot = lz4f_block_bytes(id < 4 ? 4 : id);
+    int64_t known = -1;
+    if (src_len >= 14 && (s[4] & 0x08)) memcpy(&known, s + 6, 8);
+    int64_t out_bytes = known >= 0 && known <= 255 * src_len ? known : guessed_output(src_len, dst_cap);
+    if (out_bytes > dst_cap) out_bytes = dst_cap;
+    int64_t max_blocks = (known >= 0 && known <= 255 * src_len ? known : src_len) / slot + 16;
+    // device image: [source | info | output | scratch]
+    Image<B> im = { be };
+    lz4hip_lz4f_info_t h = {};
+    int64_t info_at = 0, out_at = 0;
+    for (int attempt = 0;; attempt++) {
+        const int64_t scratch_bytes = lz4f_decode_scratch_bytes(slot, max_blocks, 0);
+        Carver c;
+        c.take(src_len);
+        info_at = c.take(256); out_at = c.take(out_bytes);
+        const int64_t scratch_at = c.take(scratch_bytes);
+        LZ4HIP_FRAMING_TRY(im.reserve(c.at));
+        LZ4HIP_FRAMING_TRY(im.upload_source(src, src_len));
+        LZ4HIP_FRAMING_TRY(lz4f_decode(be, im.d, src_len, slot, max_blocks, 0, flags, im.d + scratch_at, scratch_bytes, im.d + out_at, out_bytes,
+                                       (lz4hip_lz4f_info_t*)(im.d + info_at)));
+        LZ4HIP_FRAMING_TRY(im.download(&h, info_at, sizeof h));
+        LZ4HIP_FRAMING_TRY(be.sync());
+        if (attempt >= 2) break;
+        if (h.error == LZ4HIP_LZ4F_TABLE_FULL) max_blocks = h.blocks;
+        else if (h.decoded_bytes > dst_cap || h.decoded_bytes <= out_bytes) break;
+        else out_bytes = h.decoded_bytes;
+    }
+    *info = h;
+    if (h.error == LZ4HIP_LZ4F_TABLE_FULL) return be.fail(LZ4HIP_E_DEVICE, "lz4f decode: the size field walk did not settle");
+    if (h.decoded_bytes > dst_cap || h.decoded_bytes > out_bytes)
+        return be.fail(LZ4HIP_E_ARGUMENT, "lz4f decode: dst_cap < decoded_bytes (reported in info->decoded_bytes)");
+    if (h.decoded_bytes > 0 && !dst) return be.fail(LZ4HIP_E_ARGUMENT, "lz4f decode: dst is NULL");
+    if (h.decoded_bytes > 0) LZ4HIP_FRAMING_TRY(im.download(dst, out_at, h.decoded_bytes));
+    LZ4HIP_FRAMING_TRY(be.sync());
     return info->error;
 }
 

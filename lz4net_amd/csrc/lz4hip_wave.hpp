@@ -70,6 +70,12 @@ LZ4HIP_DEVICE uint32_t scan_add(uint32_t x)
     return x;
 }
 
+// Exchange inside each group of four consecutive lanes (DPP quad_perm, no LDS): lane i receives v from lane i ^ 1 / i ^ 2.  All four
+// lanes of the quad must be active.  (LZ4HIP_WAVE_QUAD: a wave API without these two gets them from shuffle(), lz4hip_lz4f.hpp.)
+#define LZ4HIP_WAVE_QUAD 1
+LZ4HIP_DEVICE uint32_t quad_xor1(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0xB1, 0xF, 0xF, false); }   // quad_perm:[1,0,3,2]
+LZ4HIP_DEVICE uint32_t quad_xor2(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x4E, 0xF, 0xF, false); }   // quad_perm:[2,3,0,1]
+
 // Arbitrary cross-lane gather (ds_bpermute_b32): lane i receives v from lane idx_i.
 LZ4HIP_DEVICE uint32_t shuffle(uint32_t v, int src_lane) { return (uint32_t)__builtin_amdgcn_ds_bpermute(src_lane << 2, (int)v); }
 

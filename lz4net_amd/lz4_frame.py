@@ -1,0 +1,257 @@
+"""The LZ4 frame format (magic 0x184D2204, LZ4 Frame format v1.6.x): what every `lz4` tool since r120, LZ4F_compressFrame,
+K4os.Compression.LZ4.Streams and python-lz4 write and read.
+
+    LE32 0x184D2204   FLG  BD  [LE64 contentSize if FLG.3]  [LE32 dictID if FLG.0]  HC
+    { LE32 blockSize (bit 31: stored raw)  data  [LE32 xxh32(data) if FLG.4] }*
+    LE32 0 (EndMark)   [LE32 xxh32(content) if FLG.2]
+
+The blocks are the block format the library encodes and decodes anyway; the framing, the xxHash32 checksums and the packing run on
+the device (lz4hip_lz4f_* of include/lz4hip.h).  Frames written here hold independent blocks and no dictionary; frames with linked
+blocks (FLG.5 clear) or a dictionary ID are refused with a clear message, not decoded wrongly.  Skippable frames (magic 0x184D2A50 ..
+0x184D2A5F) are skipped, appended frames decoded one after the other."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from .codec import ArgumentException
+
+MAGIC = 0x184D2204
+SKIPPABLE_MAGIC = 0x184D2A50
+BLOCK_SIZES = {65536: 4, 262144: 5, 1048576: 6, 4194304: 7}
+HEADER_PEEK = 19                                                       # magic + FLG + BD + content size + dictID + HC
+
+_TEXT = {
+    _lib.LZ4F_BAD_MAGIC: "not an LZ4 frame: unknown magic number",
+    _lib.LZ4F_BAD_HEADER: "frame descriptor: wrong version, reserved bit set or invalid block size",
+    _lib.LZ4F_HEADER_CHECKSUM: "frame descriptor: header checksum mismatch",
+    _lib.LZ4F_UNSUPPORTED_LINKED: "frames with linked blocks are not supported: their blocks decode only in order",
+    _lib.LZ4F_UNSUPPORTED_DICT: "frames with a dictionary ID are not supported",
+    _lib.LZ4F_SLOT_TOO_SMALL: "the frame's block maximum exceeds the slot it was given",
+    _lib.LZ4F_TRUNCATED: "truncated frame",
+    _lib.LZ4F_BAD_BLOCK_SIZE: "block size exceeds the frame's block maximum",
+    _lib.LZ4F_CORRUPT_BLOCK: "Decoding Failed ! Corrupted input !",
+    _lib.LZ4F_BLOCK_CHECKSUM_ERROR: "block checksum mismatch",
+    _lib.LZ4F_CONTENT_SIZE_ERROR: "decoded size differs from the frame's content size",
+    _lib.LZ4F_CONTENT_CHECKSUM_ERROR: "content checksum mismatch",
+}
+
+
+def _frame_error(status: int, error_offset: int = -1):
+    """The exception the decoders raise for an LZ4HIP_LZ4F_* outcome, with where it was met in .error_offset and the code in .status."""
+    status = int(status)
+    e = ArgumentException(_TEXT[status]) if status in _TEXT else _lib.Lz4HipError(f"lz4 frame decode: unexpected outcome {status}")
+    e.error_offset, e.status = int(error_offset), status
+    return e
+
+
+def _xxh32_small(data: bytes) -> int:
+    """XXH32 (seed 0) of fewer than 16 bytes: the descriptor's HC byte"""
+    P1, P2, P3, P4, P5, M = 2654435761, 2246822519, 3266489917, 668265263, 374761393, 0xFFFFFFFF
+    assert len(data) < 16
+    h = (P5 + len(data)) & M
+    i = 0
+    while i + 4 <= len(data):
+        h = (h + int.from_bytes(data[i:i + 4], "little") * P3) & M
+        h = (((h << 17) | (h >> 15)) & M) * P4 & M
+        i += 4
+    for b in data[i:]:
+        h = (h + b * P5) & M
+        h = (((h << 11) | (h >> 21)) & M) * P1 & M
+    h ^= h >> 15
+    h = h * P2 & M
+    h ^= h >> 13
+    h = h * P3 & M
+    return h ^ (h >> 16)
+
+
+def parse_header(data) -> dict:
+    """The start of a frame -> {"kind": "frame" | "skippable", "header_bytes", and for a frame "flg", "bd", "block_max", "independent",
+    "block_checksum", "content_checksum", "content_size" (None if absent), "dict_id" (None if absent); for a skippable frame "size"}.
+    Raises ArgumentException as the device walk would (magic, version, reserved bits, block size id, truncation, HC)."""
+    data = bytes(data)
+    if len(data) < 4:
+        raise _frame_error(_lib.LZ4F_BAD_MAGIC, 0)
+    magic = int.from_bytes(data[:4], "little")
+    if magic & 0xFFFFFFF0 == SKIPPABLE_MAGIC:
+        if len(data) < 8:
+            raise _frame_error(_lib.LZ4F_TRUNCATED, 4)
+        return {"kind": "skippable", "size": int.from_bytes(data[4:8], "little"), "header_bytes": 8}
+    if magic != MAGIC:
+        raise _frame_error(_lib.LZ4F_BAD_MAGIC, 0)
+    if len(data) < 7:
+        raise _frame_error(_lib.LZ4F_TRUNCATED, 4)
+    flg, bd = data[4], data[5]
+    dlen = 3 + (8 if flg & 0x08 else 0) + (4 if flg & 0x01 else 0)
+    if (flg >> 6) != 1 or flg & 0x02 or bd & 0x8F or ((bd >> 4) & 7) < 4:
+        raise _frame_error(_lib.LZ4F_BAD_HEADER, 4)
+    if 4 + dlen > len(data):
+        raise _frame_error(_lib.LZ4F_TRUNCATED, 4)
+    if data[4 + dlen - 1] != (_xxh32_small(data[4:4 + dlen - 1]) >> 8) & 0xFF:
+        raise _frame_error(_lib.LZ4F_HEADER_CHECKSUM, 4 + dlen - 1)
+    at = 6
+    content_size = dict_id = None
+    if flg & 0x08:
+        content_size = int.from_bytes(data[at:at + 8], "little")
+        at += 8
+    if flg & 0x01:
+        dict_id = int.from_bytes(data[at:at + 4], "little")
+    return {"kind": "frame", "flg": flg, "bd": bd, "block_max": 1 << (8 + 2 * ((bd >> 4) & 7)), "independent": bool(flg & 0x20),
+            "block_checksum": bool(flg & 0x10), "content_checksum": bool(flg & 0x04), "content_size": content_size, "dict_id": dict_id,
+            "header_bytes": 4 + dlen}
+
+
+def _block_id(block_size) -> int:
+    if int(block_size) not in BLOCK_SIZES:
+        raise ArgumentException("block_size must be 65536, 262144, 1048576 or 4194304")
+    return BLOCK_SIZES[int(block_size)]
+
+
+def _encode_flags(block_checksum, content_checksum, content_size) -> int:
+    return ((_lib.LZ4F_BLOCK_CHECKSUM if block_checksum else 0) | (_lib.LZ4F_CONTENT_CHECKSUM if content_checksum else 0) |
+            (_lib.LZ4F_CONTENT_SIZE if content_size else 0))
+
+
+def compress_frame_device(t, block_size: int = 65536, high_compression: bool = False, block_checksum: bool = False,
+                          content_checksum: bool = False, content_size: bool = True):
+    """One LZ4 frame of a 1-D uint8 CUDA tensor, entirely on the device, on torch's current stream, returned as a 1-D uint8 CUDA tensor:
+    independent blocks of block_size bytes, a block that does not shrink stored raw.  The content checksum is ONE serial row of the
+    checksum kernel over the whole source.  Waits for the device once, to learn the frame's length."""
+    import torch
+    from .stream import _check_device_bytes
+    t = _check_device_bytes(t, "t")
+    bid, flags = _block_id(block_size), _encode_flags(block_checksum, content_checksum, content_size)
+    with torch.cuda.device(t.device):
+        L = _lib.lib()
+        n = t.numel()
+        out = torch.empty(L.lz4hip_lz4f_bound(n, bid, flags), dtype=torch.uint8, device=t.device)
+        scratch = torch.empty(max(L.lz4hip_lz4f_encode_scratch_bytes(n, bid), 1), dtype=torch.uint8, device=t.device)
+        out_len = torch.empty(1, dtype=torch.int64, device=t.device)
+        _lib.check(L.lz4hip_lz4f_encode_device(t.data_ptr(), n, bid, _lib.MODE_HC if high_compression else _lib.MODE_FAST, flags,
+                                               out.data_ptr(), out.numel(), out_len.data_ptr(), scratch.data_ptr(), scratch.numel(),
+                                               torch.cuda.current_stream(t.device).cuda_stream))
+        return out[:int(out_len.item())]
+
+
+def decompress_frame_device(t, verify: bool = True, round_blocks: int = 0):
+    """The content of the LZ4 frames in a 1-D uint8 CUDA tensor -- appended frames one after the other, skippable frames skipped -- as a
+    1-D uint8 CUDA tensor, decoded on the device on torch's current stream.  Per frame the host reads the first 19 bytes back (the block
+    maximum sizes the decoder's slots, the content size the output and the table), calls lz4hip_lz4f_decode_device once and reads its
+    record; only a frame without a content size whose output outgrows the guess, or with more blocks than the table, is decoded again.
+    verify=True checks whatever checksums the frame carries, as every reader of this format does; verify=False skips both.  The
+    content checksum is ONE row of the checksum kernel -- four serial chains over the whole output, bound by their latency whatever the
+    device (DESIGN.md 7 records the measured single-row rate, or says that it has not been measured yet) -- so verify=False is worth it for large frames whose
+    integrity is known.  round_blocks = K > 0 decodes K blocks at a time through a ring of K slots.  Raises ArgumentException with the
+    outcome's text."""
+    import torch
+    from .stream import _check_device_bytes
+    t = _check_device_bytes(t, "t")
+    flags = (_lib.LZ4F_VERIFY_BLOCKS | _lib.LZ4F_VERIFY_CONTENT) if verify else 0
+    with torch.cuda.device(t.device):
+        L = _lib.lib()
+        dev = t.device
+        s = torch.cuda.current_stream(dev).cuda_stream
+        info_dev = torch.zeros(C.sizeof(_lib.Lz4fInfo), dtype=torch.uint8, device=dev)
+        parts, pos, n = [], 0, t.numel()
+        if n == 0:
+            raise _frame_error(_lib.LZ4F_BAD_MAGIC, 0)
+        while pos < n:
+            try:
+                head = parse_header(t[pos:pos + HEADER_PEEK].cpu().numpy().tobytes())
+            except ArgumentException as e:
+                e.error_offset += pos
+                raise
+            if head["kind"] == "skippable":
+                if pos + 8 + head["size"] > n:
+                    raise _frame_error(_lib.LZ4F_TRUNCATED, pos + 4)
+                pos += 8 + head["size"]
+                continue
+            rest = n - pos
+            known = head["content_size"]
+            out_bytes = known if known is not None and known <= 255 * rest else 4 * rest
+            max_blocks = (out_bytes if known is not None else rest) // head["block_max"] + 16
+            for _ in range(3):
+                need = _lib.check(L.lz4hip_lz4f_decode_scratch_bytes(head["block_max"], max_blocks, round_blocks))
+                scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+                out = torch.empty(out_bytes, dtype=torch.uint8, device=dev)
+                _lib.check(L.lz4hip_lz4f_decode_device(t.data_ptr() + pos, rest, head["block_max"], max_blocks, round_blocks, flags, scratch.data_ptr(),
+                                                       need, out.data_ptr(), out_bytes, info_dev.data_ptr(), s))
+                info = _lib.Lz4fInfo.from_buffer_copy(info_dev.cpu().numpy().tobytes())
+                if info.error == _lib.LZ4F_TABLE_FULL:
+                    max_blocks = int(info.blocks)
+                elif info.decoded_bytes > out_bytes:
+                    out_bytes = int(info.decoded_bytes)
+                else:
+                    break
+            if info.error == _lib.LZ4F_TABLE_FULL or info.decoded_bytes > out_bytes:
+                raise _lib.Lz4HipError("lz4 frame decode: the size field walk did not settle")
+            if info.error != _lib.LZ4F_OK:
+                raise _frame_error(info.error, pos + info.error_offset if info.error_offset >= 0 else -1)
+            parts.append(out[:int(info.decoded_bytes)])
+            pos += int(info.frame_bytes)
+        if not parts:                                                 # (skippable frames only)
+            return torch.empty(0, dtype=torch.uint8, device=dev)
+        return parts[0] if len(parts) == 1 else torch.cat(parts)
+
+
+def _host_bytes(data):
+    if isinstance(data, np.ndarray):
+        return np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
+    return np.frombuffer(bytes(data), dtype=np.uint8)
+
+
+def compress_frame_host(data, block_size: int = 65536, high_compression: bool = False, block_checksum: bool = False,
+                        content_checksum: bool = False, content_size: bool = True) -> bytes:
+    """compress_frame_device for host bytes, through lz4hip_lz4f_encode_host: one staged call, the frame packed on the device."""
+    raw = _host_bytes(data)
+    bid, flags = _block_id(block_size), _encode_flags(block_checksum, content_checksum, content_size)
+    L = _lib.lib()
+    bound = L.lz4hip_lz4f_bound(raw.size, bid, flags)
+    out = np.empty(bound, np.uint8)
+    out_len = C.c_int64(0)
+    _lib.check(L.lz4hip_lz4f_encode_host(raw.ctypes.data, raw.size, bid, _lib.MODE_HC if high_compression else _lib.MODE_FAST, flags,
+                                         out.ctypes.data, bound, C.byref(out_len)))
+    return out[:out_len.value].tobytes()
+
+
+def decompress_frame_host(frame, verify: bool = True) -> bytes:
+    """decompress_frame_device for host bytes, through lz4hip_lz4f_decode_host: per frame a size query (dst_cap = 0), then the call that
+    decodes into exactly that size.  Appended frames follow each other; skippable frames are skipped."""
+    buf = _host_bytes(frame)
+    flags = (_lib.LZ4F_VERIFY_BLOCKS | _lib.LZ4F_VERIFY_CONTENT) if verify else 0
+    L = _lib.lib()
+    parts, pos = [], 0
+    if buf.size == 0:
+        raise _frame_error(_lib.LZ4F_BAD_MAGIC, 0)
+    while pos < buf.size:
+        info = _lib.Lz4fInfo()
+        at, rest = buf.ctypes.data + pos, buf.size - pos
+        rc = L.lz4hip_lz4f_decode_host(at, rest, flags, None, 0, C.byref(info))
+        out = np.empty(max(int(info.decoded_bytes), 1), np.uint8)
+        if rc == _lib.E_ARGUMENT and info.decoded_bytes > 0:
+            rc = L.lz4hip_lz4f_decode_host(at, rest, flags, out.ctypes.data, int(info.decoded_bytes), C.byref(info))
+        if rc != info.error:                                          # (the outcome itself is info.error)
+            _lib.check(rc)
+        if info.error != _lib.LZ4F_OK:
+            raise _frame_error(info.error, pos + info.error_offset if info.error_offset >= 0 else -1)
+        parts.append(out[:int(info.decoded_bytes)].tobytes())
+        pos += int(info.frame_bytes)
+    return b"".join(parts)
+
+
+def xxh32_rows_device(data, off, lens, seed: int = 0):
+    """XXH32 of rows of a 1-D uint8 CUDA tensor on torch's current stream: row i is data[off[i] : off[i] + lens[i]] (off: int64 CUDA
+    tensor, lens: int32 CUDA tensor).  Returns the hashes as an int32 CUDA tensor of uint32 bit patterns; launch-only."""
+    import torch
+    from .stream import _check_device_bytes
+    data = _check_device_bytes(data, "data")
+    if off.dtype != torch.int64 or lens.dtype != torch.int32 or off.numel() != lens.numel() or not (off.is_cuda and lens.is_cuda):
+        raise ArgumentException("off must be an int64 and lens an int32 CUDA tensor of the same length")
+    with torch.cuda.device(data.device):
+        n = off.numel()
+        sums = torch.empty(n, dtype=torch.int32, device=data.device)
+        _lib.check(_lib.lib().lz4hip_xxh32_rows_device(data.data_ptr(), off.contiguous().data_ptr(), 0, lens.contiguous().data_ptr(), 0,
+                                                       seed & 0xFFFFFFFF, sums.data_ptr(), n, torch.cuda.current_stream(data.device).cuda_stream))
+        return sums
