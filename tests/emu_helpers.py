@@ -1,30 +1,17 @@
-"""ctypes front-end for tests/simt/libsimt_kernels.so (TEST INFRASTRUCTURE): runs the real kernel
-sources under the CPU SIMT emulator.  Same call shapes as the GPU batch API so tests can share code."""
+"""ctypes front-end for tests/simt/libsimt_kernels.so and the LZ4Stream / Wrap entry points of tests/simt/libsimt_framing.so (TEST
+INFRASTRUCTURE): runs the real kernel sources under the CPU SIMT emulator.  Same call shapes as the GPU batch API so tests can share code."""
 import ctypes as C
-import os
-import sys
 
 import numpy as np
 
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "simt"))
-from build_emu import build  # noqa: E402
+import emu_lib
+from emu_lib import I32 as _I32, I64 as _I64, P as _P, U32 as _U32
 
-_lib = None
-_starved = None
 _use_starved = False
 
 
 def lib():
-    global _lib, _starved
-    if _use_starved:
-        if _starved is None:
-            _starved = C.CDLL(build(starved=True))
-        return _starved
-    if _lib is None:
-        _lib = C.CDLL(build())
-        _lib.emu_compare.restype = C.c_ulonglong
-        _lib.emu_steps.restype = C.c_ulonglong
-    return _lib
+    return emu_lib.kernels(_use_starved)
 
 
 class starved_flush:
@@ -155,10 +142,7 @@ def compare(a, b, lens):
     return lib().emu_compare(_p(a), C.c_int64(a.shape[1]), _p(b), C.c_int64(b.shape[1]), _p(lens), C.c_int64(a.shape[0]))
 
 
-# ---- framing kernels (tests/simt/emu_framing.hpp): ctypes twins of the kernels' argument structs --------------------------------------
-_P, _I64, _I32, _U32 = C.c_void_p, C.c_int64, C.c_int32, C.c_uint32
-
-
+# ---- framing kernels (tests/simt/emu_stream.inc): ctypes twins of the kernels' argument structs --------------------------------------
 class StreamEncodeArgs(C.Structure):
     _fields_ = [("src", _P), ("comp", _P), ("src_len", _I64), ("n", _I64), ("block", _I32), ("hc_flag", _U32), ("result", _P), ("offs", _P)]
 
@@ -207,13 +191,7 @@ class StreamsInfo(C.Structure):
                 ("error_offset", _I64), ("error", _I32), ("reserved", _I32)]
 
 
-class HostRun(C.Structure):
-    """EmuHostRun: the emulated device of an emu_host_* call -- the block codec's stand-in and the grids in, the backend's counters,
-    the state of its guard bytes and the recorded failure text out"""
-    _fields_ = [("results", _P), ("bytes", _P), ("grid_items", _I32), ("grid_copy", _I32), ("grid_walk", _I32), ("intact", _I32),
-                ("reserves", _I64), ("moves", _I64), ("uploads", _I64), ("downloads", _I64), ("syncs", _I64), ("passes", _I64),
-                ("image_bytes", _I64), ("error", C.c_char * 160)]
-
+HostRun = emu_lib.EmuHostRun
 
 _FRAMING_STRUCTS = [StreamEncodeArgs, StreamTables, StreamInfo, WrapArgs, UnwrapTables, UnwrapArgs, UnwrapInfo, StreamsEncodeArgs,
                     StreamsTables, StreamsDecodeArgs, StreamsInfo, HostRun]
@@ -224,54 +202,52 @@ def framing():
     """The library with the framing entry points typed; checks once that the ctypes twins above have the kernels' struct sizes."""
     global _framing
     if _framing is None:
-        L = lib()
-        L.emu_framing_sizeof.restype = C.c_int64
+        L = emu_lib.framing()
         for i, s in enumerate(_FRAMING_STRUCTS):
             assert L.emu_framing_sizeof(i) == C.sizeof(s), (s.__name__, L.emu_framing_sizeof(i), C.sizeof(s))
-        ptr, i64, i32 = C.c_void_p, C.c_int64, C.c_int
         for name, args in {
-            "emu_scan": [ptr, i64, ptr, ptr],
-            "emu_stream_index": [ptr, i64, ptr, ptr],
-            "emu_copy_encode": [ptr, ptr, ptr, i32],
-            "emu_copy_raw": [ptr, ptr, i64, ptr, i64, i32],
-            "emu_copy_wrap": [ptr, ptr, i64, i32],
-            "emu_copy_unwrap_raw": [ptr, ptr, ptr, i64, i32],
-            "emu_copy_streams": [ptr, ptr, i64, i32],
-            "emu_streams_walk": [i32, ptr, ptr, i32],
-            "emu_stream_check": [ptr, i64, i32],
-            "emu_stream_encode": [ptr, ptr, ptr, ptr, ptr, i64, i32, i32],
-            "emu_stream_decode": [ptr, i64, ptr, ptr, ptr, ptr, ptr, ptr, i32, i32],
-            "emu_wrap": [ptr, ptr, ptr, ptr, ptr, ptr, i64, i64, i32, i32],
-            "emu_unwrap_index": [ptr, ptr, ptr, i32],
-            "emu_unwrap_decode": [ptr, ptr, ptr, ptr, ptr, ptr, ptr, i32, i32],
-            "emu_streams_plan": [ptr, ptr, i32],
-            "emu_streams_pack": [ptr, ptr, ptr, ptr, i64, i64, i32, i32],
-            "emu_streams_index": [ptr, ptr, ptr, i32],
-            "emu_streams_decode": [ptr, ptr, ptr, ptr, ptr, ptr, ptr, i32, i32],
+            "emu_scan": [_P, _I64, _P, _P],
+            "emu_stream_index": [_P, _I64, _P, _P],
+            "emu_copy_encode": [_P, _P, _P, _I32],
+            "emu_copy_raw": [_P, _P, _I64, _P, _I64, _I32],
+            "emu_copy_wrap": [_P, _P, _I64, _I32],
+            "emu_copy_unwrap_raw": [_P, _P, _P, _I64, _I32],
+            "emu_copy_streams": [_P, _P, _I64, _I32],
+            "emu_streams_walk": [_I32, _P, _P, _I32],
+            "emu_stream_check": [_P, _I64, _I32],
+            "emu_stream_encode": [_P, _P, _P, _P, _P, _I64, _I32, _I32],
+            "emu_stream_decode": [_P, _I64, _P, _P, _P, _P, _P, _P, _I32, _I32],
+            "emu_wrap": [_P, _P, _P, _P, _P, _P, _I64, _I64, _I32, _I32],
+            "emu_unwrap_index": [_P, _P, _P, _I32],
+            "emu_unwrap_decode": [_P, _P, _P, _P, _P, _P, _P, _I32, _I32],
+            "emu_streams_plan": [_P, _P, _I32],
+            "emu_streams_pack": [_P, _P, _P, _P, _I64, _I64, _I32, _I32],
+            "emu_streams_index": [_P, _P, _P, _I32],
+            "emu_streams_decode": [_P, _P, _P, _P, _P, _P, _P, _I32, _I32],
             # the whole functions of lz4hip_framing.hpp: the library's arguments, then the codec's stand-in (results, bytes) and the grids
-            "emu_lib_stream_encode": [ptr, i64, i32, i32, ptr, i64, ptr, ptr, i64, ptr, ptr, i32, i32],
-            "emu_lib_stream_index": [ptr, i64, i64, ptr, i64, ptr],
-            "emu_lib_stream_decode": [ptr, ptr, i64, ptr, i64, ptr, i64, ptr, ptr, ptr, i32, i32],
-            "emu_lib_wrap": [ptr, i64, ptr, i64, i32, ptr, i64, ptr, ptr, ptr, i64, ptr, ptr, i32, i32],
-            "emu_lib_unwrap_index": [ptr, i64, ptr, i64, ptr, ptr, ptr, i64, ptr, i32],
-            "emu_lib_unwrap_decode": [ptr, i64, ptr, i64, ptr, ptr, i64, ptr, i64, ptr, ptr, ptr, ptr, ptr, i32, i32],
-            "emu_lib_streams_encode": [ptr, i64, ptr, i64, i32, i32, ptr, i64, ptr, ptr, i64, ptr, ptr, i32, i32],
-            "emu_lib_streams_index": [ptr, i64, ptr, i64, i64, ptr, ptr, ptr, ptr, i64, ptr, i32],
-            "emu_lib_streams_decode": [ptr, i64, ptr, i64, ptr, i64, ptr, i64, ptr, i64, ptr, ptr, ptr, ptr, ptr, ptr, i32, i32],
+            "emu_lib_stream_encode": [_P, _I64, _I32, _I32, _P, _I64, _P, _P, _I64, _P, _P, _I32, _I32],
+            "emu_lib_stream_index": [_P, _I64, _I64, _P, _I64, _P],
+            "emu_lib_stream_decode": [_P, _P, _I64, _P, _I64, _P, _I64, _P, _P, _P, _I32, _I32],
+            "emu_lib_wrap": [_P, _I64, _P, _I64, _I32, _P, _I64, _P, _P, _P, _I64, _P, _P, _I32, _I32],
+            "emu_lib_unwrap_index": [_P, _I64, _P, _I64, _P, _P, _P, _I64, _P, _I32],
+            "emu_lib_unwrap_decode": [_P, _I64, _P, _I64, _P, _P, _I64, _P, _I64, _P, _P, _P, _P, _P, _I32, _I32],
+            "emu_lib_streams_encode": [_P, _I64, _P, _I64, _I32, _I32, _P, _I64, _P, _P, _I64, _P, _P, _I32, _I32],
+            "emu_lib_streams_index": [_P, _I64, _P, _I64, _I64, _P, _P, _P, _P, _I64, _P, _I32],
+            "emu_lib_streams_decode": [_P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _P, _P, _P, _P, _P, _I32, _I32],
             # the host-pointer calls: the library's arguments, then a HostRun
-            "emu_host_stream_encode": [ptr, i64, i32, i32, ptr, i64, ptr, ptr],
-            "emu_host_stream_decode": [ptr, i64, ptr, i64, ptr, ptr],
-            "emu_host_wrap": [ptr, i64, ptr, i64, i32, ptr, i64, ptr, ptr, ptr],
-            "emu_host_unwrap": [ptr, i64, ptr, i64, ptr, i64, ptr, ptr, ptr, ptr],
-            "emu_host_streams_encode": [ptr, i64, ptr, i64, i32, i32, ptr, i64, ptr, ptr],
-            "emu_host_streams_decode": [ptr, i64, ptr, i64, ptr, i64, ptr, ptr, ptr, ptr, ptr],
+            "emu_host_stream_encode": [_P, _I64, _I32, _I32, _P, _I64, _P, _P],
+            "emu_host_stream_decode": [_P, _I64, _P, _I64, _P, _P],
+            "emu_host_wrap": [_P, _I64, _P, _I64, _I32, _P, _I64, _P, _P, _P],
+            "emu_host_unwrap": [_P, _I64, _P, _I64, _P, _I64, _P, _P, _P, _P],
+            "emu_host_streams_encode": [_P, _I64, _P, _I64, _I32, _I32, _P, _I64, _P, _P],
+            "emu_host_streams_decode": [_P, _I64, _P, _I64, _P, _I64, _P, _P, _P, _P, _P],
         }.items():
             getattr(L, name).argtypes = args
             getattr(L, name).restype = C.c_int if name in ("emu_stream_decode", "emu_streams_decode") or name.startswith(("emu_lib_", "emu_host_")) else None
-        L.emu_scratch_bytes.argtypes = [i32, i64, i64, i64]
+        L.emu_scratch_bytes.argtypes = [_I32, _I64, _I64, _I64]
         L.emu_scratch_bytes.restype = C.c_int64
         for name in ("emu_items_grid", "emu_copy_grid", "emu_walk_grid"):
-            getattr(L, name).argtypes = [i64]
+            getattr(L, name).argtypes = [_I64]
             getattr(L, name).restype = C.c_int
         _framing = L
     return _framing
@@ -325,10 +301,9 @@ def hostbatch():
         L = lib()
         L.emu_hostbatch_sizeof.restype = C.c_int64
         assert L.emu_hostbatch_sizeof() == C.sizeof(HostBatch), (L.emu_hostbatch_sizeof(), C.sizeof(HostBatch))
-        ptr, i64, i32 = C.c_void_p, C.c_int64, C.c_int
-        L.emu_host_rule.argtypes, L.emu_host_rule.restype = [i32, i64, i64, i64], C.c_int64
-        L.emu_host_plan.argtypes, L.emu_host_plan.restype = [ptr, i32, i64, ptr, ptr, ptr], C.c_int
-        L.emu_host_batch.argtypes, L.emu_host_batch.restype = [ptr, ptr], C.c_int
-        L.emu_host_shards.argtypes, L.emu_host_shards.restype = [ptr, i32, ptr, C.c_uint, ptr, ptr, ptr], C.c_int
+        L.emu_host_rule.argtypes, L.emu_host_rule.restype = [_I32, _I64, _I64, _I64], C.c_int64
+        L.emu_host_plan.argtypes, L.emu_host_plan.restype = [_P, _I32, _I64, _P, _P, _P], C.c_int
+        L.emu_host_batch.argtypes, L.emu_host_batch.restype = [_P, _P], C.c_int
+        L.emu_host_shards.argtypes, L.emu_host_shards.restype = [_P, _I32, _P, C.c_uint, _P, _P, _P], C.c_int
         _hostbatch = L
     return _hostbatch

@@ -1,5 +1,7 @@
-"""Builds tests/simt/libsimt_kernels.so (TEST INFRASTRUCTURE): the real kernel sources compiled with
-g++ against the SIMT emulator.  Rebuilt when any kernel header or emulator file is newer."""
+"""Builds the emulator libraries (TEST INFRASTRUCTURE): the real kernel sources and the library's own host code compiled with g++
+against the SIMT emulator.  libsimt_kernels.so holds the block codec kernels and the host-pointer block batch calls
+(emu_kernels.cpp), libsimt_framing.so everything on the framing side (emu_framing.cpp and its parts, emu_*.inc).  Each is rebuilt
+when a kernel header or an emulator file is newer."""
 import glob
 import os
 import subprocess
@@ -7,7 +9,23 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 CSRC = os.path.join(ROOT, "lz4net_amd", "csrc")
+AB = os.path.join(ROOT, "tools", "ab")
 SO = os.path.join(HERE, "libsimt_kernels.so")
+FRAMING_SO = os.path.join(HERE, "libsimt_framing.so")
+
+
+def _files(*patterns):
+    return [f for p in patterns for f in glob.glob(p)]
+
+
+def _build(so, source, deps, flags):
+    deps = deps + [os.path.join(HERE, source)]
+    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
+        tmp = "%s.%d.tmp" % (so, os.getpid())                               # (test processes that start together never load a half-written file)
+        subprocess.run(["g++", "-O2", "-g", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unused", "-Wno-parentheses", "-Wno-unknown-pragmas",
+                        "-I" + HERE, "-I" + CSRC, *flags, "-o", tmp, os.path.join(HERE, source)], check=True)
+        os.replace(tmp, so)
+    return so
 
 
 def build(starved: bool = False) -> str:
@@ -15,14 +33,13 @@ def build(starved: bool = False) -> str:
     lanes miss flush rounds again and again and run their rings full (and its cooperative staging
     load to 2 pieces per round, so that lanes run out of input) -- the rare states of the lane decoder (a lane that
     cannot append, a far-match chunk fetched but not consumed) become the common ones."""
-    so = SO.replace(".so", "_starved.so") if starved else SO
-    deps = glob.glob(os.path.join(ROOT, "tools", "ab", "*.hpp")) + glob.glob(os.path.join(CSRC, "*.hpp")) + glob.glob(os.path.join(CSRC, "*.inc")) + glob.glob(os.path.join(HERE, "*.hpp")) + \
-        [os.path.join(HERE, "emu_kernels.cpp")]
-    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        flags = ["-DLZ4HIP_HAVE_HC", "-DLZ4HIP_TUNING_BUILD"] if os.path.exists(os.path.join(CSRC, "lz4hip_hc.hpp")) else []
-        if starved:
-            flags += ["-DLZ4HIP_DEC_FLUSH_RECS=4", "-DLZ4HIP_DEC_LOAD_PIECES=2", "-DLZ4HIP_DEC3_FLUSH_RECS=4", "-DLZ4HIP_DEC3_LOAD_PIECES=2", "-DLZ4HIP_DEC4_FLUSH_RECS=2"]
-        subprocess.run(["g++", "-O2", "-g", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unused", "-Wno-parentheses", "-Wno-unknown-pragmas",
-                        "-I" + HERE, "-I" + CSRC, "-I" + os.path.join(ROOT, "tools", "ab"), *flags, "-o", so, os.path.join(HERE, "emu_kernels.cpp")],
-                       check=True)
-    return so
+    flags = ["-I" + AB] + (["-DLZ4HIP_HAVE_HC", "-DLZ4HIP_TUNING_BUILD"] if os.path.exists(os.path.join(CSRC, "lz4hip_hc.hpp")) else [])
+    if starved:
+        flags += ["-DLZ4HIP_DEC_FLUSH_RECS=4", "-DLZ4HIP_DEC_LOAD_PIECES=2", "-DLZ4HIP_DEC3_FLUSH_RECS=4", "-DLZ4HIP_DEC3_LOAD_PIECES=2", "-DLZ4HIP_DEC4_FLUSH_RECS=2"]
+    deps = _files(os.path.join(AB, "*.hpp"), os.path.join(CSRC, "*.hpp"), os.path.join(CSRC, "*.inc"), os.path.join(HERE, "*.hpp"))
+    return _build(SO.replace(".so", "_starved.so") if starved else SO, "emu_kernels.cpp", deps, flags)
+
+
+def build_framing() -> str:
+    deps = _files(os.path.join(CSRC, "*.hpp"), os.path.join(CSRC, "*.inc"), os.path.join(HERE, "*.hpp"), os.path.join(HERE, "*.inc"))
+    return _build(FRAMING_SO, "emu_framing.cpp", deps, ["-pthread"])

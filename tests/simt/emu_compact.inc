@@ -1,18 +1,10 @@
-// emu_compact.cpp -- TEST INFRASTRUCTURE ONLY.
+// emu_compact.inc -- TEST INFRASTRUCTURE ONLY, a part of emu_framing.cpp.
 // The compact decode of a block batch (lz4net_amd/csrc/lz4hip_compact.hpp) and the legacy frame's one-call decode on top of it under the
 // SIMT emulator, for tests/test_simt_compact.py: the real kernels, the library's own fronts and launch sequences (lz4hip_framing.hpp:
 // decode_compact, frame_decode_compact and their _plan / _run halves) and its host-pointer call (lz4hip_hostbatch.hpp:
 // decode_compact_host) over the emulated device of emu_framing.hpp.  The block decoder is a stand-in keyed by GLOBAL block index: the
 // sequence hands the decoder one round's rows at a time, so the backend counts the rows it has been given.  Results and bytes are the
-// test's, computed with the oracle.  Built with g++ by build_emu_compact.py into a library of its own, never shipped.
-#include "simt_wave.hpp"
-
-#include "lz4hip_common.hpp"
-
-using namespace lz4hip;
-
-#include "emu_framing.hpp"
-#include "lz4hip_hostbatch.hpp"
+// test's, computed with the oracle.  The size field walks are the counters' passes.
 
 // what the emulated device is to do, and what it did
 struct CompactEmuRun {
@@ -24,29 +16,17 @@ struct CompactEmuRun {
     const int64_t* src_at;
     const int32_t* src_len;      // per global block: the length the decoder must see (0 where the caller's is negative)
     int64_t n;
-    int32_t grid, intact;        // grid > 0 replaces every formula's answer; intact: EmuBackend::intact() after a host call
+    int32_t grid, pad;           // grid > 0 replaces the item and copy formulas' answers
     int64_t calls, max_rows, shape_errors;                               // decoder calls, the most rows in one, rows or descriptors that were not as promised
-    int64_t reserves, moves, uploads, downloads, syncs, last_download, image_bytes;   // last_download: the bytes of the last download
-    int64_t walks;                                                       // size field walks
-    char error[160];
+    EmuCounters counters;
 };
 
 namespace {
 
-constexpr uint8_t kJunk = 0xBD;  // what a decoder may leave inside its capacity
-
-struct CompactBackend : emu_framing::EmuBackend {
+struct CompactBackend : EmuBackend {
     CompactEmuRun* r = nullptr;
-    int64_t done = 0, last_download = 0, walks = 0;
+    int64_t done = 0;
 
-    template <class... P, class... A>
-    void launch(void (*kernel)(P...), framing::Grid grid, unsigned threads, A&&... a)
-    {
-        walks += emu_framing::same_kernel(kernel, frame_walk_kernel);
-        const int mine = grid.kind == framing::kGridItems || grid.kind == framing::kGridCopy ? r->grid : 0;
-        simt::launch(dim3(mine > 0 ? (unsigned)mine : grid.groups), dim3(threads), kStreamThreads * 8,
-                     emu_framing::KernelCall<P...>{ kernel, std::tuple<P...>{ P(a)... } });
-    }
     // LZ4_uncompress_unknownOutputSize per row at the row's capacity: the oracle's result and, inside the capacity and nowhere else, its
     // bytes; what lies between them and the capacity is junk, as after a decoder that failed or stopped short
     int decode(const lz4hip_batch_t* b, int known)
@@ -71,17 +51,13 @@ struct CompactBackend : emu_framing::EmuBackend {
         done += b->n_blocks;
         return 0;
     }
-    int download(void* host, const void* dev, size_t bytes) { last_download = (int64_t)bytes; return EmuBackend::download(host, dev, bytes); }
 };
 
-int finish(const CompactBackend& be, int rc, CompactEmuRun* r)
+CompactBackend backend_of(CompactEmuRun* r)
 {
-    r->intact = be.intact();
-    r->reserves = be.reserves; r->moves = be.moves; r->uploads = be.uploads; r->downloads = be.downloads; r->syncs = be.syncs;
-    r->last_download = be.last_download; r->walks = be.walks;
-    r->image_bytes = be.blocks.empty() ? 0 : (int64_t)be.blocks.back().bytes;
-    snprintf(r->error, sizeof r->error, "%s", be.error.c_str());
-    return rc;
+    CompactBackend be = backend<CompactBackend>(r->grid, r->grid);
+    be.r = r;
+    return be;
 }
 
 }  // namespace
@@ -119,29 +95,26 @@ void emu_frame_compact_tables(void* scratch, int32_t chunk_size, int64_t max_chu
 int emu_decode_compact(const lz4hip_batch_t* b, int64_t round_blocks, void* dst, int64_t dst_cap, int64_t* dst_off, int32_t* decoded_len,
                        void* scratch, int64_t scratch_bytes, lz4hip_compact_info_t* info, CompactEmuRun* r)
 {
-    CompactBackend be;
-    be.r = r;
-    return finish(be, framing::decode_compact(be, b, round_blocks, dst, dst_cap, dst_off, decoded_len, scratch, scratch_bytes, info), r);
+    CompactBackend be = backend_of(r);
+    return finish(be, framing::decode_compact(be, b, round_blocks, dst, dst_cap, dst_off, decoded_len, scratch, scratch_bytes, info), &r->counters);
 }
 
 // hostbatch::decode_compact_host over the emulated image; pool_floor < 0: the library's limit for gathering on the row pool
 int emu_decode_compact_host(const lz4hip_batch_t* b, int64_t round_blocks, void* dst, int64_t dst_cap, int64_t* dst_off, int32_t* decoded_len,
                             lz4hip_compact_info_t* info, int64_t pool_floor, CompactEmuRun* r)
 {
-    CompactBackend be;
-    be.r = r;
+    CompactBackend be = backend_of(r);
     hostbatch::HostLimits limits;
     if (pool_floor >= 0) limits.pool_floor = pool_floor;
-    return finish(be, hostbatch::decode_compact_host(be, b, round_blocks, dst, dst_cap, dst_off, decoded_len, info, 2, limits), r);
+    return finish(be, hostbatch::decode_compact_host(be, b, round_blocks, dst, dst_cap, dst_off, decoded_len, info, 2, limits), &r->counters);
 }
 
 // framing::frame_decode_compact, front and sequence: block g of the run record is row g of the table
 int emu_frame_decode_compact(const void* src, int64_t src_len, int32_t chunk_size, int64_t max_chunks, int64_t round_chunks, void* scratch,
                              int64_t scratch_bytes, void* dst, int64_t dst_cap, lz4hip_frame_info_t* info, CompactEmuRun* r)
 {
-    CompactBackend be;
-    be.r = r;
-    return finish(be, framing::frame_decode_compact(be, src, src_len, chunk_size, max_chunks, round_chunks, scratch, scratch_bytes, dst, dst_cap, info), r);
+    CompactBackend be = backend_of(r);
+    return finish(be, framing::frame_decode_compact(be, src, src_len, chunk_size, max_chunks, round_chunks, scratch, scratch_bytes, dst, dst_cap, info), &r->counters);
 }
 
 }  // extern "C"

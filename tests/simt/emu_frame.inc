@@ -1,44 +1,18 @@
-// emu_frame.cpp -- TEST INFRASTRUCTURE ONLY.
+// emu_frame.inc -- TEST INFRASTRUCTURE ONLY, a part of emu_framing.cpp.
 // The legacy frame path (lz4net_amd/csrc/lz4hip_frame.hpp) under the SIMT emulator, for tests/test_simt_frame.py: the real kernels, the
 // library's own fronts and launch sequences (lz4hip_framing.hpp: frame_encode / frame_index / frame_decode and their _plan / _run
 // halves) and its host-pointer calls (frame_encode_host / frame_decode_host) over the emulated device of emu_framing.hpp with its moving
-// image.  The block codec is EmuBackend's stand-in: results and bytes the test computed with the oracle.  Built with g++ by
-// build_emu_frame.py into a library of its own, never shipped.
-#include "simt_wave.hpp"
-
-#include "lz4hip_common.hpp"
-
-using namespace lz4hip;
-
-#include "emu_framing.hpp"
+// image.  The block codec is EmuBackend's stand-in: results and bytes the test computed with the oracle.
 
 namespace {
 
-// EmuBackend with the LDS the size walk's workgroup has on the device (the scan kernels need less), the test's grids, and a count of
-// the size field walks
-struct FrameBackend : emu_framing::EmuBackend {
-    template <class... P, class... A>
-    void launch(void (*kernel)(P...), framing::Grid grid, unsigned threads, A&&... a)
-    {
-        passes += emu_framing::same_kernel(kernel, frame_walk_kernel);
-        const int mine = grid.kind == framing::kGridItems ? grid_items : (grid.kind == framing::kGridCopy ? grid_copy : 0);
-        simt::launch(dim3(mine > 0 ? (unsigned)mine : grid.groups), dim3(threads), kSizesLdsBytes,
-                     emu_framing::KernelCall<P...>{ kernel, std::tuple<P...>{ P(a)... } });
-    }
-};
-
-// `grid` > 0 replaces every formula's answer: the item kernels', the copy kernels' and the size walk's
-FrameBackend frame_backend(int grid, const int32_t* results, const uint8_t* bytes)
+// EmuBackend with the LDS the size walk's workgroup has on the device; `grid` > 0 replaces every formula's answer: the item kernels',
+// the copy kernels' and (handed to the front) the size walk's
+EmuBackend frame_backend(int grid, const int32_t* results, const uint8_t* bytes)
 {
-    FrameBackend be;
-    be.grid_items = be.grid_copy = grid; be.results = results; be.bytes = bytes;
+    EmuBackend be = backend(grid, grid, 0, results, bytes);
+    be.lds_bytes = kSizesLdsBytes;
     return be;
-}
-
-int finish(const FrameBackend& be, int rc, char* error, int error_bytes)
-{
-    if (error) snprintf(error, (size_t)error_bytes, "%s", be.error.c_str());
-    return rc;
 }
 
 }  // namespace
@@ -73,14 +47,14 @@ void emu_frame_tables(void* scratch, int64_t max_chunks, FrameTables* t)
 int emu_frame_encode(const void* src, int64_t src_len, int32_t chunk_size, int mode, void* dst, int64_t dst_cap, int64_t* dst_len, void* scratch,
                      int64_t scratch_bytes, const int32_t* results, const uint8_t* bytes, int grid, char* error, int error_bytes)
 {
-    FrameBackend be = frame_backend(grid, results, bytes);
+    EmuBackend be = frame_backend(grid, results, bytes);
     return finish(be, framing::frame_encode(be, src, src_len, chunk_size, mode, dst, dst_cap, dst_len, scratch, scratch_bytes), error, error_bytes);
 }
 
 int emu_frame_index(const void* src, int64_t src_len, int32_t chunk_size, int64_t max_chunks, void* scratch, int64_t scratch_bytes,
                     lz4hip_frame_info_t* info, int grid, char* error, int error_bytes)
 {
-    FrameBackend be = frame_backend(grid, nullptr, nullptr);
+    EmuBackend be = frame_backend(grid, nullptr, nullptr);
     return finish(be, framing::frame_index(be, src, src_len, chunk_size, max_chunks, scratch, scratch_bytes, info, grid), error, error_bytes);
 }
 
@@ -88,14 +62,14 @@ int emu_frame_index(const void* src, int64_t src_len, int32_t chunk_size, int64_
 int emu_frame_decode(const void* src, const lz4hip_frame_info_t* info_host, int64_t max_chunks, void* scratch, int64_t scratch_bytes, void* dst,
                      int64_t dst_cap, lz4hip_frame_info_t* info, const int32_t* results, const uint8_t* bytes, int grid, char* error, int error_bytes)
 {
-    FrameBackend be = frame_backend(grid, results, bytes);
+    EmuBackend be = frame_backend(grid, results, bytes);
     return finish(be, framing::frame_decode(be, src, info_host, max_chunks, scratch, scratch_bytes, dst, dst_cap, info), error, error_bytes);
 }
 
 // ---- the sequences alone, over a table the test laid out (emu_frame_tables) --------------------------------------------------------------
 int emu_frame_index_run(const uint8_t* src, int64_t src_len, int32_t chunk, const FrameTables* t, FrameInfo* info, int grid)
 {
-    FrameBackend be = frame_backend(grid, nullptr, nullptr);
+    EmuBackend be = frame_backend(grid, nullptr, nullptr);
     const framing::FrameIndexPlan p = { src, src_len, chunk, *t, info, grid };
     return framing::frame_index_run(be, p);
 }
@@ -103,7 +77,7 @@ int emu_frame_index_run(const uint8_t* src, int64_t src_len, int32_t chunk, cons
 int emu_frame_decode_run(const uint8_t* src, const FrameInfo* index_info, const FrameTables* t, uint8_t* dst, FrameInfo* info, const int32_t* results,
                          const uint8_t* bytes, int grid)
 {
-    FrameBackend be = frame_backend(grid, results, bytes);
+    EmuBackend be = frame_backend(grid, results, bytes);
     const framing::FrameDecodePlan p = { src, *index_info, *t, dst, info };
     return framing::frame_decode_run(be, p);
 }
@@ -111,24 +85,14 @@ int emu_frame_decode_run(const uint8_t* src, const FrameInfo* index_info, const 
 // ---- the host-pointer calls: the library's argument lists, then an EmuHostRun (grid_items: the grid of every formula) ---------------------
 int emu_host_frame_encode(const void* src, int64_t src_len, int32_t chunk_size, int mode, void* dst, int64_t dst_cap, int64_t* dst_len, EmuHostRun* r)
 {
-    FrameBackend be = frame_backend(r->grid_items, r->results, r->bytes);
-    const int rc = framing::frame_encode_host(be, src, src_len, chunk_size, mode, dst, dst_cap, dst_len);
-    r->intact = be.intact();
-    r->reserves = be.reserves; r->moves = be.moves; r->uploads = be.uploads; r->downloads = be.downloads; r->syncs = be.syncs; r->passes = be.passes;
-    r->image_bytes = be.blocks.empty() ? 0 : (int64_t)be.blocks.back().bytes;
-    snprintf(r->error, sizeof r->error, "%s", be.error.c_str());
-    return rc;
+    EmuBackend be = frame_backend(r->grid_items, r->results, r->bytes);
+    return finish(be, framing::frame_encode_host(be, src, src_len, chunk_size, mode, dst, dst_cap, dst_len), &r->counters);
 }
 
 int emu_host_frame_decode(const void* src, int64_t src_len, int32_t chunk_size, void* dst, int64_t dst_cap, lz4hip_frame_info_t* info, EmuHostRun* r)
 {
-    FrameBackend be = frame_backend(r->grid_items, r->results, r->bytes);
-    const int rc = framing::frame_decode_host(be, src, src_len, chunk_size, dst, dst_cap, info);
-    r->intact = be.intact();
-    r->reserves = be.reserves; r->moves = be.moves; r->uploads = be.uploads; r->downloads = be.downloads; r->syncs = be.syncs; r->passes = be.passes;
-    r->image_bytes = be.blocks.empty() ? 0 : (int64_t)be.blocks.back().bytes;
-    snprintf(r->error, sizeof r->error, "%s", be.error.c_str());
-    return rc;
+    EmuBackend be = frame_backend(r->grid_items, r->results, r->bytes);
+    return finish(be, framing::frame_decode_host(be, src, src_len, chunk_size, dst, dst_cap, info), &r->counters);
 }
 
 }  // extern "C"

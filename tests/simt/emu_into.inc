@@ -1,17 +1,9 @@
-// emu_into.cpp -- TEST INFRASTRUCTURE ONLY.
+// emu_into.inc -- TEST INFRASTRUCTURE ONLY, a part of emu_framing.cpp.
 // The one-call decodes of an LZ4Stream buffer, of a batch of them and of wrapped messages (lz4net_amd/csrc/lz4hip_framing.hpp:
 // stream_decode_into, streams_decode_into, unwrap_into -- fronts and sequences -- over the clip, check and copy kernels of
 // lz4hip_stream.hpp, lz4hip_streams.hpp and lz4hip_wrap.hpp) under the SIMT emulator, for tests/test_simt_into.py.  The block decoder
 // is a stand-in fed the test's results and bytes; it also VERIFIES what it is handed: one known-size call over the whole table, every
 // row past the count and every clipped row an empty block of capacity 0, every other row with its own offsets, length and capacity.
-// Built with g++ by build_emu_into.py into a library of its own, never shipped.
-#include "simt_wave.hpp"
-
-#include "lz4hip_common.hpp"
-
-using namespace lz4hip;
-
-#include "emu_framing.hpp"
 
 // what the emulated device is to do, and what it did
 struct IntoEmuRun {
@@ -24,12 +16,12 @@ struct IntoEmuRun {
     int64_t rows, count;         // the table's size; the rows the index fills (0 on TABLE_FULL)
     int32_t grid_items, grid_copy, grid_walk, pad;   // > 0 replaces the formula's answer
     int64_t calls, shape_errors, decoded_rows;       // decoder calls, rows or descriptors that were not as promised, rows given bytes
-    char error[160];
+    EmuCounters counters;
 };
 
 namespace {
 
-struct IntoBackend : emu_framing::EmuBackend {
+struct IntoBackend : EmuBackend {
     IntoEmuRun* r = nullptr;
 
     // a (0, 0) row gets -1 and not a byte, as the known-size decoders answer it
@@ -58,15 +50,9 @@ struct IntoBackend : emu_framing::EmuBackend {
 
 IntoBackend backend_of(IntoEmuRun* r)
 {
-    IntoBackend be;
-    be.r = r; be.grid_items = r->grid_items; be.grid_copy = r->grid_copy; be.grid_walk = r->grid_walk;
+    IntoBackend be = backend<IntoBackend>(r->grid_items, r->grid_copy, r->grid_walk);
+    be.r = r;
     return be;
-}
-
-int finish(const IntoBackend& be, int rc, IntoEmuRun* r)
-{
-    snprintf(r->error, sizeof r->error, "%s", be.error.c_str());
-    return rc;
 }
 
 }  // namespace
@@ -102,7 +88,7 @@ int emu_stream_decode_into(const void* src, int64_t src_len, int64_t max_chunks,
                            lz4hip_stream_info_t* info, int64_t* written_bytes, IntoEmuRun* r)
 {
     IntoBackend be = backend_of(r);
-    return finish(be, framing::stream_decode_into(be, src, src_len, max_chunks, scratch, scratch_bytes, dst, dst_cap, info, written_bytes), r);
+    return finish(be, framing::stream_decode_into(be, src, src_len, max_chunks, scratch, scratch_bytes, dst, dst_cap, info, written_bytes), &r->counters);
 }
 
 int emu_streams_decode_into(const void* src, int64_t src_len, const int64_t* src_off, int64_t n, int64_t max_chunks, void* scratch,
@@ -111,14 +97,14 @@ int emu_streams_decode_into(const void* src, int64_t src_len, const int64_t* src
 {
     IntoBackend be = backend_of(r);
     return finish(be, framing::streams_decode_into(be, src, src_len, src_off, n, max_chunks, scratch, scratch_bytes, dst, dst_cap, dst_off, status,
-                                                   error_offset, info, written_items), r);
+                                                   error_offset, info, written_items), &r->counters);
 }
 
 int emu_unwrap_into(const void* src, int64_t src_len, const int64_t* src_off, int64_t n, void* scratch, int64_t scratch_bytes, void* dst,
                     int64_t dst_cap, int64_t* dst_off, int32_t* status, lz4hip_unwrap_info_t* info, int64_t* written_messages, IntoEmuRun* r)
 {
     IntoBackend be = backend_of(r);
-    return finish(be, framing::unwrap_into(be, src, src_len, src_off, n, scratch, scratch_bytes, dst, dst_cap, dst_off, status, info, written_messages), r);
+    return finish(be, framing::unwrap_into(be, src, src_len, src_off, n, scratch, scratch_bytes, dst, dst_cap, dst_off, status, info, written_messages), &r->counters);
 }
 
 }  // extern "C"

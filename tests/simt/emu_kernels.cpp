@@ -1,8 +1,8 @@
 // emu_kernels.cpp -- TEST INFRASTRUCTURE ONLY.
 // Compiles the real kernel sources (lz4net_amd/csrc/*.hpp) against the SIMT emulator and exposes
-// them through a C ABI for tests/test_simt_emulation.py and tests/test_simt_framing.py (the framing kernels: entry points in
-// emu_framing.hpp, which run the library's own host code for those paths, lz4hip_framing.hpp) and tests/test_simt_hostbatch.py (the
-// host-pointer block batch calls: emu_hostbatch.hpp over lz4hip_hostbatch.hpp).  Built with g++, never shipped.
+// them through a C ABI for tests/test_simt_emulation.py and tests/test_simt_hostbatch.py (the host-pointer block batch calls:
+// emu_hostbatch.hpp over lz4hip_hostbatch.hpp, which may run the real decode_kernel).  The framing side is libsimt_framing.so
+// (emu_framing.cpp).  Built with g++ by build_emu.py, never shipped.
 #include "simt_wave.hpp"
 
 static unsigned long long g_iterations = 0;   // loop iterations of the lane decoders (all wavefronts), counted by lane 0
@@ -19,9 +19,6 @@ static unsigned long long g_stat[32];         // lane-iterations per state of th
 #include "lz4hip_encode.hpp"
 #include "lz4hip_encode_lane.hpp"
 #include "lz4hip_synth.hpp"
-#include "lz4hip_stream.hpp"
-#include "lz4hip_wrap.hpp"
-#include "lz4hip_streams.hpp"
 #ifdef LZ4HIP_HAVE_HC
 #include "lz4hip_hc.hpp"
 #include "lz4hip_hc_lane.hpp"
@@ -326,5 +323,4 @@ void emu_stats(unsigned long long* out, int reset) { for (int i = 0; i < 32; i++
 unsigned long long emu_iterations(int reset) { const unsigned long long v = g_iterations; if (reset) g_iterations = 0; return v; }
 }
 
-#include "emu_framing.hpp"
 #include "emu_hostbatch.hpp"

@@ -1,18 +1,9 @@
-// emu_packed.cpp -- TEST INFRASTRUCTURE ONLY.
+// emu_packed.inc -- TEST INFRASTRUCTURE ONLY, a part of emu_framing.cpp.
 // The packed encode of a block batch (lz4net_amd/csrc/lz4hip_packed.hpp) under the SIMT emulator, for tests/test_simt_packed.py: the real
 // kernels, the library's own front and launch sequence (lz4hip_framing.hpp: encode_packed and its _plan / _run halves) and its
 // host-pointer call (lz4hip_hostbatch.hpp: encode_packed_host) over the emulated device of emu_framing.hpp.  The block codec is a
 // stand-in keyed by GLOBAL block index: the sequence hands the encoder one round's rows at a time, so the backend counts the rows it
-// has been given.  Results and bytes are the test's, computed with the oracle.  Built with g++ by build_emu_packed.py into a library of
-// its own, never shipped.
-#include "simt_wave.hpp"
-
-#include "lz4hip_common.hpp"
-
-using namespace lz4hip;
-
-#include "emu_framing.hpp"
-#include "lz4hip_hostbatch.hpp"
+// has been given.  Results and bytes are the test's, computed with the oracle.
 
 // what the emulated device is to do, and what it did
 struct PackedEmuRun {
@@ -23,27 +14,17 @@ struct PackedEmuRun {
     const int64_t* src_at;
     const uint8_t* bad_len;      // per global block: 1 where the caller's length is negative (the encoder must see an empty block there), or NULL
     int64_t n;
-    int32_t grid, intact;        // grid > 0 replaces every formula's answer; intact: EmuBackend::intact() after a host call
+    int32_t grid, pad;           // grid > 0 replaces the item and copy formulas' answers
     int64_t calls, max_rows, shape_errors;                               // encoder calls, the most rows in one, rows or descriptors that were not as promised
-    int64_t reserves, moves, uploads, downloads, syncs, last_download, image_bytes;   // last_download: the bytes of the last download
-    char error[160];
+    EmuCounters counters;
 };
 
 namespace {
 
-constexpr uint8_t kJunk = 0xBD;  // what a limited encoder may leave inside its capacity
-
-struct PackedBackend : emu_framing::EmuBackend {
+struct PackedBackend : EmuBackend {
     PackedEmuRun* r = nullptr;
-    int64_t done = 0, last_download = 0;
+    int64_t done = 0;
 
-    template <class... P, class... A>
-    void launch(void (*kernel)(P...), framing::Grid grid, unsigned threads, A&&... a)
-    {
-        const int mine = grid.kind == framing::kGridItems || grid.kind == framing::kGridCopy ? r->grid : 0;
-        simt::launch(dim3(mine > 0 ? (unsigned)mine : grid.groups), dim3(threads), kStreamThreads * 8,
-                     emu_framing::KernelCall<P...>{ kernel, std::tuple<P...>{ P(a)... } });
-    }
     // LZ4_compress_limitedOutput per row: the oracle's bytes where they fit the row's capacity, else 0 and junk inside the capacity
     int encode(const lz4hip_batch_t* b, int)
     {
@@ -72,17 +53,13 @@ struct PackedBackend : emu_framing::EmuBackend {
         done += b->n_blocks;
         return 0;
     }
-    int download(void* host, const void* dev, size_t bytes) { last_download = (int64_t)bytes; return EmuBackend::download(host, dev, bytes); }
 };
 
-int finish(const PackedBackend& be, int rc, PackedEmuRun* r)
+PackedBackend backend_of(PackedEmuRun* r)
 {
-    r->intact = be.intact();
-    r->reserves = be.reserves; r->moves = be.moves; r->uploads = be.uploads; r->downloads = be.downloads; r->syncs = be.syncs;
-    r->last_download = be.last_download;
-    r->image_bytes = be.blocks.empty() ? 0 : (int64_t)be.blocks.back().bytes;
-    snprintf(r->error, sizeof r->error, "%s", be.error.c_str());
-    return rc;
+    PackedBackend be = backend<PackedBackend>(r->grid, r->grid);
+    be.r = r;
+    return be;
 }
 
 }  // namespace
@@ -108,20 +85,18 @@ int emu_packed_copy_grid(int64_t bytes) { return (int)framing::copy_grid(bytes).
 int emu_encode_packed(const lz4hip_batch_t* b, int mode, int64_t round_blocks, void* dst, int64_t dst_cap, int64_t* dst_off, int32_t* packed_len,
                       void* scratch, int64_t scratch_bytes, lz4hip_packed_info_t* info, PackedEmuRun* r)
 {
-    PackedBackend be;
-    be.r = r;
-    return finish(be, framing::encode_packed(be, b, mode, round_blocks, dst, dst_cap, dst_off, packed_len, scratch, scratch_bytes, info), r);
+    PackedBackend be = backend_of(r);
+    return finish(be, framing::encode_packed(be, b, mode, round_blocks, dst, dst_cap, dst_off, packed_len, scratch, scratch_bytes, info), &r->counters);
 }
 
 // hostbatch::encode_packed_host over the emulated image; pool_floor < 0: the library's limit for gathering on the row pool
 int emu_encode_packed_host(const lz4hip_batch_t* b, int mode, int64_t round_blocks, void* dst, int64_t dst_cap, int64_t* dst_off, int32_t* packed_len,
                            lz4hip_packed_info_t* info, int64_t pool_floor, PackedEmuRun* r)
 {
-    PackedBackend be;
-    be.r = r;
+    PackedBackend be = backend_of(r);
     hostbatch::HostLimits limits;
     if (pool_floor >= 0) limits.pool_floor = pool_floor;
-    return finish(be, hostbatch::encode_packed_host(be, b, mode, round_blocks, dst, dst_cap, dst_off, packed_len, info, 2, limits), r);
+    return finish(be, hostbatch::encode_packed_host(be, b, mode, round_blocks, dst, dst_cap, dst_off, packed_len, info, 2, limits), &r->counters);
 }
 
 }  // extern "C"

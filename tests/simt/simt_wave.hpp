@@ -85,6 +85,19 @@ inline uint32_t shuffle(uint32_t v, int src_lane)
     return (uint32_t)w[src_lane & 63].slot[p];
 }
 
+// the quad exchanges of lz4hip_wave.hpp (DPP quad_perm): lane i receives v from lane i ^ 1 / i ^ 2, and that lane must take part
+#define LZ4HIP_WAVE_QUAD 1
+inline uint32_t quad_xor(uint32_t v, int x, int site)
+{
+    unsigned p, tag;
+    const simt::Lane* w = simt::exchange(v, site, &p, &tag);
+    const int from = lane() ^ x;
+    if (from >= simt::wave_width(simt::rt().cur) || !simt::took_part(w[from], p, tag)) simt::die("wv::quad_xor() with an inactive lane in the quad", from);
+    return (uint32_t)w[from].slot[p];
+}
+inline uint32_t quad_xor1(uint32_t v) { return quad_xor(v, 1, 160); }
+inline uint32_t quad_xor2(uint32_t v) { return quad_xor(v, 2, 161); }
+
 inline uint64_t ballot(bool pred)
 {
     unsigned p, tag;

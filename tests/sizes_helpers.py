@@ -1,17 +1,14 @@
 """TEST INFRASTRUCTURE for the size query of a block batch (lz4hip_decoded_sizes_*): the corpora of tests/test_decoded_sizes.py (CPU,
 under the SIMT emulator) and tests/test_gpu_decoded_sizes.py (the device), what the reference returns for every block of them, and
-the ctypes front of tests/simt/libsimt_sizes.so."""
+the ctypes front of the size query's entry points in tests/simt/libsimt_framing.so."""
 import ctypes as C
 import functools
-import os
-import sys
 
 import numpy as np
 
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "simt"))
-from build_emu_sizes import build  # noqa: E402
-
-from lz4net_amd._lib import Batch, SizesInfo  # noqa: E402
+import emu_lib
+from emu_lib import EmuHostRun
+from lz4net_amd._lib import Batch, SizesInfo
 
 E_ARGUMENT = -2000000002
 FUZZ_SEED, FUZZ_BLOCKS = 20261017, 20480
@@ -177,15 +174,9 @@ def expected(results):
 
 
 # ---- the emulator ---------------------------------------------------------------------------------------------------------------
-class EmuHostRun(C.Structure):
-    _fields_ = [("results", C.c_void_p), ("bytes", C.c_void_p), ("grid_items", C.c_int32), ("grid_copy", C.c_int32), ("grid_walk", C.c_int32),
-                ("intact", C.c_int32), ("reserves", C.c_int64), ("moves", C.c_int64), ("uploads", C.c_int64), ("downloads", C.c_int64),
-                ("syncs", C.c_int64), ("passes", C.c_int64), ("image_bytes", C.c_int64), ("error", C.c_char * 160)]
-
-
 @functools.lru_cache(maxsize=None)
 def emu():
-    lib = C.CDLL(build())
+    lib = emu_lib.framing()
     lib.emu_sizes_window.restype = C.c_int64
     lib.emu_sizes_scratch_bytes.restype = C.c_int64
     lib.emu_sizes_scratch_bytes.argtypes = [C.c_int64]

@@ -1,6 +1,6 @@
 """CPU-only: the LZ4 frame path against the format library.  The frames of tests/golden/lz4f_frames.json were written by liblz4's
 LZ4F_compressFrame (tests/golden/make_lz4f_golden.py) and are read here by the test-side twin (tests/lz4f_ref.py) and by the emulator
-path (the library's kernels and sequences, tests/simt/emu_lz4f.cpp); these tests never skip.  Where liblz4 is installed (found with
+path (the library's kernels and sequences, tests/simt/emu_lz4f.inc); these tests never skip.  Where liblz4 is installed (found with
 ctypes.util.find_library; nothing is downloaded) fresh frames at levels 0 and 9 and every block size id go the same way, the emulator
 path's frames go through LZ4F_decompress, which must consume every byte, and the descriptors are compared; those tests, and only those,
 skip where the library is absent."""

@@ -1,41 +1,36 @@
 """CPU-only: the compact decode of a block batch (lz4net_amd/csrc/lz4hip_compact.hpp and its host code in lz4hip_framing.hpp and
-lz4hip_hostbatch.hpp) and the legacy frame's one-call decode on top of it, under the SIMT emulator (tests/simt/emu_compact.cpp): the
+lz4hip_hostbatch.hpp) and the legacy frame's one-call decode on top of it, under the SIMT emulator (tests/simt/emu_compact.inc): the
 real kernels, the library's fronts, launch sequences and host-pointer call, with the block decoder replaced by a stand-in keyed by
 global block index that writes, into the slot and never past the block's limit, what the oracle's LZ4_uncompress_unknownOutputSize
 gives for the block at that limit.  Every case runs with the library's grids and with grids forced to 1 and 3 workgroups."""
 import ctypes as C
 import functools
-import os
-import sys
 
 import numpy as np
 import pytest
 
+import emu_lib
 import test_simt_frame as tf
+from emu_lib import I32 as _I32, I64 as _I64, P as _P
 from lz4net_amd._lib import Batch, CompactInfo, FrameInfo
-
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "simt"))
-from build_emu_compact import build  # noqa: E402
 
 E_ARGUMENT = -2000000002
 GRIDS = (0, 1, 3)
 GUARD = 0x5A
 SMALL = (0, 1, 12, 13, 64)
 SLOT = 70000                                    # the decoded size of the longest block: the slot width of most cases
-_P, _I64, _I32 = C.c_void_p, C.c_int64, C.c_int32
 Guarded = tf.Guarded
 
 
 class CompactEmuRun(C.Structure):
+    _anonymous_ = ("counters",)
     _fields_ = [("results", _P), ("limits", _P), ("at", _P), ("bytes", _P), ("src", _P), ("src_at", _P), ("src_len", _P), ("n", _I64),
-                ("grid", _I32), ("intact", _I32), ("calls", _I64), ("max_rows", _I64), ("shape_errors", _I64),
-                ("reserves", _I64), ("moves", _I64), ("uploads", _I64), ("downloads", _I64), ("syncs", _I64), ("last_download", _I64),
-                ("image_bytes", _I64), ("walks", _I64), ("error", C.c_char * 160)]
+                ("grid", _I32), ("pad", _I32), ("calls", _I64), ("max_rows", _I64), ("shape_errors", _I64), ("counters", emu_lib.EmuCounters)]
 
 
 @functools.lru_cache(maxsize=None)
 def emu():
-    L = C.CDLL(build())
+    L = emu_lib.framing()
     L.emu_compact_sizeof.restype = _I64
     assert L.emu_compact_sizeof(0) == L.emu_compact_sizeof(3) == C.sizeof(CompactInfo) and L.emu_compact_sizeof(1) == C.sizeof(CompactEmuRun)
     assert L.emu_compact_sizeof(2) == C.sizeof(Batch) and L.emu_compact_sizeof(4) == C.sizeof(tf.FrameTables) and L.emu_compact_sizeof(5) == C.sizeof(FrameInfo)
@@ -516,7 +511,7 @@ def run_frame(oracle, frame, chunk, max_chunks=None, k=0, grid=0, dst_cap=None):
     rc = emu().emu_frame_decode_compact(src.ctypes.data if a.size else None, a.size, chunk, m, k, scratch.ptr, scratch.n, dst.ptr, dst_cap,
                                         C.addressof(info), C.addressof(r))
     assert rc == 0, r.error
-    assert dst.intact() and scratch.intact() and r.shape_errors == 0 and r.walks == 1
+    assert dst.intact() and scratch.intact() and r.shape_errors == 0 and r.passes == 1
     assert (r.calls, r.max_rows) == rounds_of(m, k), "the decode runs over all max_chunks rows"
     if len(chunks) > m:
         assert tf.info_tuple(info) == (len(chunks), total, total if all(x >= 0 for x in rets[:m]) else tf.info_tuple(info)[2], chunks[m][0] - 4, TABLE_FULL)
@@ -624,7 +619,7 @@ def test_frame_argument_checks():
     def call(src=buf.ptr, src_len=100, chunk=4096, m=4, k=0, scratch=buf.ptr, scratch_n=need, dst=buf.ptr, dst_cap=100, info_ptr=C.addressof(info)):
         r = CompactEmuRun()
         rc = L.emu_frame_decode_compact(src, src_len, chunk, m, k, scratch, scratch_n, dst, dst_cap, info_ptr, C.addressof(r))
-        assert r.walks == 0 or rc == 0
+        assert r.passes == 0 or rc == 0
         return rc
 
     for kw in (dict(src_len=-1), dict(m=-1), dict(k=-1), dict(dst_cap=-1), dict(info_ptr=None), dict(scratch=None), dict(src=None), dict(dst=None),

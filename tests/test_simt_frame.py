@@ -1,31 +1,27 @@
 """CPU-only: the legacy frame path (lz4net_amd/csrc/lz4hip_frame.hpp and its host code in lz4hip_framing.hpp) under the SIMT emulator
-(tests/simt/emu_frame.cpp): the real kernels, the library's fronts, launch sequences and host-pointer calls, with the block codec
+(tests/simt/emu_frame.inc): the real kernels, the library's fronts, launch sequences and host-pointer calls, with the block codec
 replaced by results and bytes computed here with the oracle.  Every case runs with the library's grids and with grids forced to 1 and 3
 workgroups.  The reference reader is modelled by `reader`: parse_frame's walk plus LZ4_uncompress_unknownOutputSize(in, out, size,
 chunk_size) per chunk."""
 import ctypes as C
 import functools
-import os
 import random
-import sys
 
 import numpy as np
 import pytest
 
+import emu_lib
 import ref_records as rr
 import sizes_helpers as sh
 from lz4net_amd import legacy_frame as lf
+from emu_lib import I32 as _I32, I64 as _I64, P as _P
 from lz4net_amd._lib import FrameInfo
-
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "simt"))
-from build_emu_frame import build  # noqa: E402
 
 E_ARGUMENT = -2000000002
 OK, BAD_MAGIC, TRUNCATED, BAD_SIZE, CORRUPT_BLOCK, TABLE_FULL = range(6)
 MAGIC = lf.MAGIC.to_bytes(4, "little")
 GRIDS = (0, 1, 3)
 GUARD = 0x5A
-_P, _I64, _I32 = C.c_void_p, C.c_int64, C.c_int32
 
 
 class FrameTables(C.Structure):
@@ -35,7 +31,7 @@ class FrameTables(C.Structure):
 
 @functools.lru_cache(maxsize=None)
 def emu():
-    L = C.CDLL(build())
+    L = emu_lib.framing()
     L.emu_frame_sizeof.restype = _I64
     assert L.emu_frame_sizeof(0) == C.sizeof(FrameTables) and L.emu_frame_sizeof(1) == C.sizeof(FrameInfo)
     assert L.emu_frame_sizeof(2) == C.sizeof(sh.EmuHostRun)

@@ -1,5 +1,5 @@
 """The framing kernels (lz4net_amd/csrc/lz4hip_stream.hpp, lz4hip_wrap.hpp, lz4hip_streams.hpp) under the CPU SIMT emulator
-(tests/simt/emu_framing.hpp): the int64 scan, the position-driven copy routine behind its five layouts, the header reader, and the
+(tests/simt/emu_stream.inc): the int64 scan, the position-driven copy routine behind its five layouts, the header reader, and the
 library's own host code for the framing paths (lz4net_amd/csrc/lz4hip_framing.hpp: scratch layouts, grids, kernel sequences), once
 from the kernels' argument structs over arrays made here and once whole, from the C ABI's arguments over a scratch buffer of exactly
 the size the library asks for, with the block codec step replaced by arrays handed in here; and the six host-pointer calls on top of

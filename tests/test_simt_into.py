@@ -1,5 +1,5 @@
 """CPU-only: the one-call decodes of an LZ4Stream buffer, of a batch of them and of wrapped messages (lz4hip_framing.hpp:
-stream_decode_into, streams_decode_into, unwrap_into) under the SIMT emulator (tests/simt/emu_into.cpp): the real clip, check, copy and
+stream_decode_into, streams_decode_into, unwrap_into) under the SIMT emulator (tests/simt/emu_into.inc): the real clip, check, copy and
 info kernels, the library's fronts and sequences, on a scratch buffer of exactly the size asked for between guard bytes.  The block
 decoder is a stand-in fed the oracle's results and bytes that verifies what it is handed: ONE known-size call over the whole table,
 every row past the count and every clipped row as (0, 0), every other row with its own offsets, length and capacity.  Every case runs
@@ -9,37 +9,34 @@ without: the good parts are held against the plain bytes the oracle compressed, 
 tests/test_gpu_decode_into.py repeats the cases against the host paths.)"""
 import ctypes as C
 import functools
-import os
-import sys
 
 import numpy as np
 import pytest
 
 import emu_helpers as emu
+import emu_lib
 import test_simt_framing as fr
 from emu_helpers import addr, ref
+from emu_lib import I32 as _I32, I64 as _I64, P as _P
 from lz4net_amd._lib import StreamInfo, StreamsInfo, UnwrapInfo
 from test_stream_device import expected_stream, frame
-
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "simt"))
-from build_emu_into import build  # noqa: E402
 
 OK, EOS, PASSES, CORRUPT_BLOCK, TABLE_FULL = 0, 1, 2, 3, 4
 E_ARGUMENT = -2000000002
 GRIDS = (0, 1, 3)
 GUARD, FILL = 64, 0xA5
-_P, _I64, _I32 = C.c_void_p, C.c_int64, C.c_int32
 
 
 class IntoEmuRun(C.Structure):
+    _anonymous_ = ("counters",)
     _fields_ = [("results", _P), ("bytes", _P), ("src_off", _P), ("dst_off", _P), ("len", _P), ("cap", _P), ("rows", _I64), ("count", _I64),
                 ("grid_items", _I32), ("grid_copy", _I32), ("grid_walk", _I32), ("pad", _I32), ("calls", _I64), ("shape_errors", _I64),
-                ("decoded_rows", _I64), ("error", C.c_char * 160)]
+                ("decoded_rows", _I64), ("counters", emu_lib.EmuCounters)]
 
 
 @functools.lru_cache(maxsize=None)
 def lib():
-    L = C.CDLL(build())
+    L = emu_lib.framing()
     L.emu_into_sizeof.restype = _I64
     assert [L.emu_into_sizeof(i) for i in range(4)] == [C.sizeof(s) for s in (IntoEmuRun, StreamInfo, StreamsInfo, UnwrapInfo)]
     L.emu_into_scratch_bytes.argtypes, L.emu_into_scratch_bytes.restype = [C.c_int, _I64, _I64], _I64

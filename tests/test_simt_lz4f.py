@@ -1,38 +1,34 @@
 """CPU-only: the xxHash32 row kernel and the LZ4 frame path (lz4net_amd/csrc/lz4hip_lz4f.hpp and its host code in lz4hip_framing.hpp)
-under the SIMT emulator (tests/simt/emu_lz4f.cpp): the real kernels, the library's fronts, launch sequences and host-pointer calls, with
+under the SIMT emulator (tests/simt/emu_lz4f.inc): the real kernels, the library's fronts, launch sequences and host-pointer calls, with
 the block codec replaced by results and bytes computed here with the oracle.  The reference is the test-side twin tests/lz4f_ref.py: a
 from-the-spec xxh32, a frame writer and a frame reader over the oracle's block codec."""
 import ctypes as C
 import functools
 import mmap
-import os
-import sys
 
 import numpy as np
 import pytest
 
+import emu_lib
 import lz4f_ref as ref
+from emu_lib import I32 as _I32, I64 as _I64, P as _P, U32 as _U32
 from lz4net_amd._lib import Lz4fInfo
-
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "simt"))
-from build_emu_lz4f import build  # noqa: E402
 
 E_ARGUMENT = -2000000002
 GUARD = 0x5A
-_P, _I64, _I32, _U32 = C.c_void_p, C.c_int64, C.c_int32, C.c_uint32
 LENGTHS = (0, 1, 3, 4, 5, 15, 16, 17, 31, 32, 33, 63, 64, 65, 127, 128, 129, 1023, 1024, 1025)
 INFO_FIELDS = [f for f, _ in Lz4fInfo._fields_]
 
 
 class EmuRun(C.Structure):
+    _anonymous_ = ("counters",)
     _fields_ = [("enc_results", _P), ("enc_bytes", _P), ("enc_len", _P), ("dec_results", _P), ("dec_len", _P), ("dec_at", _P), ("dec_bytes", _P), ("dec_rows", _I64),
-                ("grid", _I32), ("intact", _I32), ("calls", _I64), ("shape_errors", _I64), ("reserves", _I64), ("moves", _I64), ("uploads", _I64),
-                ("downloads", _I64), ("syncs", _I64), ("error", C.c_char * 160)]
+                ("grid", _I32), ("pad", _I32), ("calls", _I64), ("shape_errors", _I64), ("counters", emu_lib.EmuCounters)]
 
 
 @functools.lru_cache(maxsize=None)
 def emu():
-    L = C.CDLL(build())
+    L = emu_lib.framing()
     L.emu_lz4f_sizeof.restype = _I64
     assert L.emu_lz4f_sizeof(0) == C.sizeof(Lz4fInfo) == L.emu_lz4f_sizeof(2) and L.emu_lz4f_sizeof(1) == C.sizeof(EmuRun)
     L.emu_xxh32_serial.argtypes, L.emu_xxh32_serial.restype = [_P, _I64, _U32], _U32

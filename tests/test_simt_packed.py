@@ -1,39 +1,34 @@
 """CPU-only: the packed encode of a block batch (lz4net_amd/csrc/lz4hip_packed.hpp and its host code in lz4hip_framing.hpp and
-lz4hip_hostbatch.hpp) under the SIMT emulator (tests/simt/emu_packed.cpp): the real kernels, the library's front, launch sequence and
+lz4hip_hostbatch.hpp) under the SIMT emulator (tests/simt/emu_packed.inc): the real kernels, the library's front, launch sequence and
 host-pointer call, with the block encoder replaced by a stand-in keyed by global block index that hands out what the oracle's
 LZ4_compress / LZ4_compressHC wrote for the block -- or 0 and junk where that does not fit the block's limit, as a limited encoder
 may.  Every case runs with the library's grids and with grids forced to 1 and 3 workgroups."""
 import ctypes as C
 import functools
-import os
-import sys
 
 import numpy as np
 import pytest
 
+import emu_lib
+from emu_lib import I32 as _I32, I64 as _I64, P as _P
 from lz4net_amd._lib import Batch, PackedInfo
-
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "simt"))
-from build_emu_packed import build  # noqa: E402
 
 E_ARGUMENT = -2000000002
 GRIDS = (0, 1, 3)
 GUARD = 0x5A
 SMALL = (0, 1, 12, 13, 64)
 SLOT = 70000 + 70000 // 255 + 16                # compressBound of the longest block
-_P, _I64, _I32 = C.c_void_p, C.c_int64, C.c_int32
 
 
 class PackedEmuRun(C.Structure):
-    _fields_ = [("sizes", _P), ("at", _P), ("bytes", _P), ("src", _P), ("src_at", _P), ("bad_len", _P), ("n", _I64), ("grid", _I32), ("intact", _I32),
-                ("calls", _I64), ("max_rows", _I64), ("shape_errors", _I64),
-                ("reserves", _I64), ("moves", _I64), ("uploads", _I64), ("downloads", _I64), ("syncs", _I64), ("last_download", _I64),
-                ("image_bytes", _I64), ("error", C.c_char * 160)]
+    _anonymous_ = ("counters",)
+    _fields_ = [("sizes", _P), ("at", _P), ("bytes", _P), ("src", _P), ("src_at", _P), ("bad_len", _P), ("n", _I64), ("grid", _I32), ("pad", _I32),
+                ("calls", _I64), ("max_rows", _I64), ("shape_errors", _I64), ("counters", emu_lib.EmuCounters)]
 
 
 @functools.lru_cache(maxsize=None)
 def emu():
-    L = C.CDLL(build())
+    L = emu_lib.framing()
     L.emu_packed_sizeof.restype = _I64
     assert L.emu_packed_sizeof(0) == C.sizeof(PackedInfo) and L.emu_packed_sizeof(1) == C.sizeof(PackedEmuRun)
     assert L.emu_packed_sizeof(2) == C.sizeof(Batch)

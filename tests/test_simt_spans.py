@@ -1,41 +1,32 @@
 """CPU-only: the span forms of the one-call decodes (lz4hip_framing.hpp: unwrap_spans_into, streams_decode_spans_into), the selection
-kernel (spans_select) and the chunk directory of one stream (stream_directory) under the SIMT emulator (tests/simt/emu_spans.cpp): the
+kernel (spans_select) and the chunk directory of one stream (stream_directory) under the SIMT emulator (tests/simt/emu_spans.inc): the
 real index, walk, clip, check, copy and info kernels, the library's fronts and sequences, on a scratch buffer of exactly the size asked
-for between guard bytes, with the library's grids and with grids of 1 and 3.  The block decoder is emu_into.cpp's stand-in, which
+for between guard bytes, with the library's grids and with grids of 1 and 3.  The block decoder is emu_into.inc's stand-in, which
 verifies the table it is handed row by row; it hands out each item's own plain bytes, so what a call leaves in dst is held against the
-items' sources.  The identity cases run the consecutive entry points of emu_into.cpp and the span entry points on the same arena in
+items' sources.  The identity cases run the consecutive entry points of emu_into.inc and the span entry points on the same arena in
 the same library and compare every output byte for byte."""
 import ctypes as C
 import functools
-import os
-import sys
 
 import numpy as np
 
 import emu_helpers as emu
 import test_simt_framing as fr
+import test_simt_into as into
 from emu_helpers import addr, ref
+from emu_lib import I64 as _I64, P as _P
 from lz4net_amd import stream as st
 from lz4net_amd._lib import StreamInfo, StreamsInfo, UnwrapInfo
-from test_simt_into import FILL, GRIDS, Buf, IntoEmuRun, info_bytes, run_record
+from test_simt_into import FILL, GRIDS, Buf, info_bytes, run_record
 from test_stream_device import expected_stream, frame
-
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "simt"))
-from build_emu_spans import build  # noqa: E402
 
 OK, EOS, PASSES, CORRUPT_BLOCK, TABLE_FULL = 0, 1, 2, 3, 4
 E_ARGUMENT = -2000000002
-_P, _I64, _I32 = C.c_void_p, C.c_int64, C.c_int32
 
 
 @functools.lru_cache(maxsize=None)
 def lib():
-    L = C.CDLL(build())
-    L.emu_into_sizeof.restype = _I64
-    assert [L.emu_into_sizeof(i) for i in range(4)] == [C.sizeof(s) for s in (IntoEmuRun, StreamInfo, StreamsInfo, UnwrapInfo)]
-    L.emu_into_scratch_bytes.argtypes, L.emu_into_scratch_bytes.restype = [C.c_int, _I64, _I64], _I64
-    L.emu_streams_decode_into.argtypes = [_P, _I64, _P, _I64, _I64, _P, _I64, _P, _I64, _P, _P, _P, _P, _P, _P]
-    L.emu_unwrap_into.argtypes = [_P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _P, _P, _P, _P]
+    L = into.lib()                                                         # the consecutive forms, typed and their records checked
     L.emu_streams_decode_spans_into.argtypes = [_P, _I64, _P, _P, _I64, _I64, _P, _I64, _P, _I64, _P, _P, _P, _P, _P, _P]
     L.emu_unwrap_spans_into.argtypes = [_P, _I64, _P, _P, _I64, _P, _I64, _P, _I64, _P, _P, _P, _P, _P]
     L.emu_spans_select.argtypes = [_P, _I64, _P, _I64, _P, _P, C.c_int]
