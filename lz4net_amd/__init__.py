@@ -7,6 +7,8 @@
   lz4net_amd.wrap          batches of Wrap / WrapHC / Unwrap messages framed on the device (lz4hip_wrap_*)
   lz4net_amd.lz4_frame     LZ4 frames (magic 0x184D2204, what every current lz4 tool reads and writes) encoded and decoded on the
                            device in one call (lz4hip_lz4f_*), and XXH32 of rows of device bytes
+  lz4net_amd._plumbing     what those modules do around every library call, once: argument checks, the per-call device context,
+                           reading a record back, the retry loop, the host size query
   lz4net_amd._lib          ctypes binding of liblz4hip.so (include/lz4hip.h)
 
 The codec itself is hand-written HIP (lz4net_amd/csrc); Python only moves pointers.

@@ -16,7 +16,8 @@ import ctypes as C
 
 import torch
 
-from . import _lib
+from . import _lib, _plumbing as _p
+from ._plumbing import compress_bound
 
 BLOCK = 65536
 BOUND = BLOCK + BLOCK // 255 + 16          # MaximumOutputLength(65536) = 65809
@@ -127,7 +128,7 @@ def _source(src, src_len, src_off):
 
 def read_sizes_info(info: torch.Tensor) -> _lib.SizesInfo:
     """The lz4hip_sizes_info_t a decoded_sizes call left on the device (synchronises)."""
-    return _lib.SizesInfo.from_buffer_copy(info.cpu().numpy().tobytes())
+    return _p.read_record(info, _lib.SizesInfo)
 
 
 def decoded_sizes(src: torch.Tensor, src_len, src_off: torch.Tensor | None = None, result: torch.Tensor | None = None):
@@ -167,14 +168,48 @@ def decode_packed(src: torch.Tensor, src_len, src_off: torch.Tensor | None = Non
     return dst, offsets, results
 
 
+# ---- a batch into one packed buffer: what encode_packed and decode_compact share ---------------------------------------------------
+def _launch_packed(name, lead, n, b, device, round_blocks, dst, slot_bytes, dst_cap, block_cap):
+    """encode_packed_launch and decode_compact_launch: lz4hip_<name>_scratch_bytes, then lz4hip_<name>_device on the sources in `b`;
+    `lead` holds the scalar arguments the call takes between the batch and round_blocks."""
+    offsets = torch.empty(n + 1, dtype=torch.int64, device=device)
+    lengths = torch.empty(n, dtype=torch.int32, device=device)
+    results = torch.empty(n, dtype=torch.int32, device=device)
+    info = torch.empty(5, dtype=torch.int64, device=device)
+    if block_cap is not None:
+        assert block_cap.dtype == torch.int32 and block_cap.numel() == n and block_cap.is_cuda and block_cap.is_contiguous()
+        b.dst_cap = block_cap.data_ptr()
+    b.dst_cap_all, b.result = slot_bytes, results.data_ptr()
+    need = _lib.check(getattr(_lib.lib(), f"lz4hip_{name}_scratch_bytes")(n, slot_bytes, round_blocks))
+    scratch = torch.empty(max(need, 1), dtype=torch.uint8, device=device)
+    cap = (0 if dst is None else dst.numel()) if dst_cap is None else dst_cap
+    _lib.check(getattr(_lib.lib(), f"lz4hip_{name}_device")(C.byref(b), *lead, round_blocks, _ptr(dst), cap, offsets.data_ptr(), lengths.data_ptr(),
+                                                            scratch.data_ptr(), need, info.data_ptr(), _stream()))
+    return offsets, lengths, results, info
+
+
+def _two_tries(launch, read, total, n, dst, guess, device):
+    """encode_packed and decode_compact: launch(dst) into the caller's `dst`, or into `guess` bytes and, only when not every block
+    fit, once more into exactly the bytes the first try's record named in its field `total` -> (dst_view, offsets, lengths, results,
+    record).  One wait for the device per try."""
+    given = dst is not None
+    if given:
+        assert dst.dtype == torch.uint8 and dst.is_cuda and dst.dim() == 1 and dst.is_contiguous()
+    else:
+        dst = torch.empty(max(guess, 0), dtype=torch.uint8, device=device)
+    offsets, lengths, results, info = launch(dst)
+    h = read(info)
+    if not given and h.written_blocks < n:
+        dst = torch.empty(getattr(h, total), dtype=torch.uint8, device=device)
+        offsets, lengths, results, info = launch(dst)
+        h = read(info)
+    return dst[:min(getattr(h, total), dst.numel())], offsets, lengths, results, h
+
+
 # ---- encoding a batch into one packed buffer --------------------------------------------------------
 def read_packed_info(info: torch.Tensor) -> _lib.PackedInfo:
     """The lz4hip_packed_info_t an encode_packed call left on the device (synchronises)."""
-    return _lib.PackedInfo.from_buffer_copy(info.cpu().numpy().tobytes())
-
-
-def compress_bound(n: int) -> int:
-    return n + n // 255 + 16
+    return _p.read_record(info, _lib.PackedInfo)
 
 
 def encode_packed_launch(src, src_len, src_off, hc, round_blocks, dst, slot_bytes, dst_cap=None, block_cap=None):
@@ -182,23 +217,9 @@ def encode_packed_launch(src, src_len, src_off, hc, round_blocks, dst, slot_byte
     device: int64 n + 1, int32 n, int32 n and the lz4hip_packed_info_t record as five int64 (read_packed_info).  dst_cap defaults to
     dst.numel(); block_cap (int32, n) gives per-block output limits."""
     n, b, keep = _source(src, src_len, src_off)
-    dev = src.device
-    offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
-    lengths = torch.empty(n, dtype=torch.int32, device=dev)
-    results = torch.empty(n, dtype=torch.int32, device=dev)
-    info = torch.empty(5, dtype=torch.int64, device=dev)
-    if block_cap is not None:
-        assert block_cap.dtype == torch.int32 and block_cap.numel() == n and block_cap.is_cuda and block_cap.is_contiguous()
-        b.dst_cap = block_cap.data_ptr()
-    b.dst_cap_all, b.result = slot_bytes, results.data_ptr()
     if src.dim() == 2 and not isinstance(src_len, int):
         b.src_len_all = src.shape[1]                # the hint: no block is longer than its row
-    need = _lib.check(_lib.lib().lz4hip_encode_packed_scratch_bytes(n, slot_bytes, round_blocks))
-    scratch = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
-    cap = (0 if dst is None else dst.numel()) if dst_cap is None else dst_cap
-    _lib.check(_lib.lib().lz4hip_encode_packed_device(C.byref(b), _lib.MODE_HC if hc else _lib.MODE_FAST, round_blocks, _ptr(dst), cap,
-                                                      offsets.data_ptr(), lengths.data_ptr(), scratch.data_ptr(), need, info.data_ptr(), _stream()))
-    return offsets, lengths, results, info
+    return _launch_packed("encode_packed", (_p.mode(hc),), n, b, src.device, round_blocks, dst, slot_bytes, dst_cap, block_cap)
 
 
 def encode_packed(src: torch.Tensor, src_len, src_off: torch.Tensor | None = None, hc: bool = False, round_blocks: int = 0,
@@ -229,25 +250,15 @@ def encode_packed(src: torch.Tensor, src_len, src_off: torch.Tensor | None = Non
             assert src.dim() == 2, "a 1-D src with per-block lengths needs slot_bytes"
             slot_bytes = compress_bound(src.shape[1])
     slot_bytes = max(int(slot_bytes), 1)
-    given = dst is not None
-    if given:
-        assert dst.dtype == torch.uint8 and dst.is_cuda and dst.dim() == 1 and dst.is_contiguous()
-    else:
-        guess = n * src_len if isinstance(src_len, int) else (n * src.shape[1] if src.dim() == 2 else src.numel())
-        dst = torch.empty(max(guess, 0), dtype=torch.uint8, device=src.device)
-    offsets, lengths, results, info = encode_packed_launch(src, src_len, src_off, hc, round_blocks, dst, slot_bytes)
-    h = read_packed_info(info)
-    if not given and h.written_blocks < n:
-        dst = torch.empty(h.packed_bytes, dtype=torch.uint8, device=src.device)
-        offsets, lengths, results, info = encode_packed_launch(src, src_len, src_off, hc, round_blocks, dst, slot_bytes)
-        h = read_packed_info(info)
-    return dst[:min(h.packed_bytes, dst.numel())], offsets, lengths, results, h
+    guess = n * src_len if isinstance(src_len, int) else (n * src.shape[1] if src.dim() == 2 else src.numel())
+    return _two_tries(lambda dst: encode_packed_launch(src, src_len, src_off, hc, round_blocks, dst, slot_bytes), read_packed_info,
+                      "packed_bytes", n, dst, guess, src.device)
 
 
 # ---- decoding a batch into one packed buffer without a size walk --------------------------------------
 def read_compact_info(info: torch.Tensor) -> _lib.CompactInfo:
     """The lz4hip_compact_info_t a decode_compact call left on the device (synchronises)."""
-    return _lib.CompactInfo.from_buffer_copy(info.cpu().numpy().tobytes())
+    return _p.read_record(info, _lib.CompactInfo)
 
 
 def decode_compact_launch(src, src_len, src_off, round_blocks, dst, slot_bytes, dst_cap=None, block_cap=None):
@@ -255,21 +266,7 @@ def decode_compact_launch(src, src_len, src_off, round_blocks, dst, slot_bytes, 
     device: int64 n + 1, int32 n, int32 n and the lz4hip_compact_info_t record as five int64 (read_compact_info).  dst_cap defaults to
     dst.numel() (0 for dst=None: a size query); block_cap (int32, n) gives per-block output limits below slot_bytes."""
     n, b, keep = _source(src, src_len, src_off)
-    dev = src.device
-    offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
-    lengths = torch.empty(n, dtype=torch.int32, device=dev)
-    results = torch.empty(n, dtype=torch.int32, device=dev)
-    info = torch.empty(5, dtype=torch.int64, device=dev)
-    if block_cap is not None:
-        assert block_cap.dtype == torch.int32 and block_cap.numel() == n and block_cap.is_cuda and block_cap.is_contiguous()
-        b.dst_cap = block_cap.data_ptr()
-    b.dst_cap_all, b.result = slot_bytes, results.data_ptr()
-    need = _lib.check(_lib.lib().lz4hip_decode_compact_scratch_bytes(n, slot_bytes, round_blocks))
-    scratch = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
-    cap = (0 if dst is None else dst.numel()) if dst_cap is None else dst_cap
-    _lib.check(_lib.lib().lz4hip_decode_compact_device(C.byref(b), round_blocks, _ptr(dst), cap, offsets.data_ptr(), lengths.data_ptr(),
-                                                       scratch.data_ptr(), need, info.data_ptr(), _stream()))
-    return offsets, lengths, results, info
+    return _launch_packed("decode_compact", (), n, b, src.device, round_blocks, dst, slot_bytes, dst_cap, block_cap)
 
 
 COMPACT_GUESS = 4        # decode_compact's first output buffer: this many times the compressed bytes
@@ -295,19 +292,9 @@ def decode_compact(src: torch.Tensor, src_len, src_off: torch.Tensor | None = No
     assert src.dtype == torch.uint8 and src.is_cuda
     n = src.shape[0] if src_off is None else src_off.numel()
     slot_bytes = max(int(slot_bytes), 1)
-    given = dst is not None
-    if given:
-        assert dst.dtype == torch.uint8 and dst.is_cuda and dst.dim() == 1 and dst.is_contiguous()
-    else:
-        compressed = n * src_len if isinstance(src_len, int) else src.numel()
-        dst = torch.empty(max(min(COMPACT_GUESS * compressed, n * slot_bytes), 0), dtype=torch.uint8, device=src.device)
-    offsets, lengths, results, info = decode_compact_launch(src, src_len, src_off, round_blocks, dst, slot_bytes)
-    h = read_compact_info(info)
-    if not given and h.written_blocks < n:
-        dst = torch.empty(h.decoded_bytes, dtype=torch.uint8, device=src.device)
-        offsets, lengths, results, info = decode_compact_launch(src, src_len, src_off, round_blocks, dst, slot_bytes)
-        h = read_compact_info(info)
-    return dst[:min(h.decoded_bytes, dst.numel())], offsets, lengths, results, h
+    compressed = n * src_len if isinstance(src_len, int) else src.numel()
+    return _two_tries(lambda dst: decode_compact_launch(src, src_len, src_off, round_blocks, dst, slot_bytes), read_compact_info,
+                      "decoded_bytes", n, dst, min(COMPACT_GUESS * compressed, n * slot_bytes), src.device)
 
 
 # ---- round-robin sharding -------------------------------------------------------------------------

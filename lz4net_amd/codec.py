@@ -15,6 +15,8 @@ The C# source of the real shim is bindings/csharp/HipLZ4Service.cs (cannot be co
 """
 from __future__ import annotations
 
+import ctypes as C
+
 import numpy as np
 
 from . import _lib
@@ -30,6 +32,9 @@ class ArgumentNullException(ArgumentException):
 
 class InvalidOperationException(RuntimeError):
     pass
+
+
+from . import _plumbing as _p  # noqa: E402  (below the exceptions: _plumbing raises them)
 
 
 _CORRUPT = "LZ4 block is corrupted, or invalid length has been given."
@@ -237,9 +242,6 @@ class LZ4Codec(metaclass=_LZ4CodecMeta):
     @classmethod
     def WrapMany(cls, messages, high_compression: bool = False) -> list:
         """[Wrap(m) for m in messages] with every message compressed in one lz4hip_encode_batch_host call."""
-        import ctypes as C
-        from . import _lib
-        from .stream import _batch
         bufs = [bytes(_as_bytes(m, "inputBuffer")) for m in messages]
         idx = [i for i, m in enumerate(bufs) if len(m) > 0]
         out = [bytes(8)] * len(bufs)                                 # empty message -> 8 zero bytes (:497-498)
@@ -250,8 +252,8 @@ class LZ4Codec(metaclass=_LZ4CodecMeta):
         raw = np.frombuffer(b"".join(bufs[i] for i in idx), dtype=np.uint8)
         comp = np.zeros(raw.size, dtype=np.uint8)                    # outputLength = inputLength per message
         res = np.zeros(len(idx), dtype=np.int32)
-        b = _batch(raw, offs, lens, comp, offs, lens, res)
-        _lib.check(_lib.lib().lz4hip_encode_batch_host(C.byref(b), _lib.MODE_HC if high_compression else _lib.MODE_FAST))
+        b = _p.host_blocks(raw, offs, lens, comp, offs, lens, res)
+        _lib.check(_lib.lib().lz4hip_encode_batch_host(C.byref(b), _p.mode(high_compression)))
         for j, i in enumerate(idx):
             ln, n, o = int(lens[j]), int(res[j]), int(offs[j])
             if n >= ln or n <= 0:                                    # stored raw (:527-533)
@@ -263,9 +265,6 @@ class LZ4Codec(metaclass=_LZ4CodecMeta):
     @classmethod
     def UnwrapMany(cls, wrapped) -> list:
         """[Unwrap(w) for w in wrapped] with every compressed message decoded in one lz4hip_decode_batch_host call."""
-        import ctypes as C
-        from . import _lib
-        from .stream import _batch
         bufs = [bytes(_as_bytes(w, "inputBuffer")) for w in wrapped]
         out, todo = [None] * len(bufs), []
         for i, w in enumerate(bufs):
@@ -287,7 +286,7 @@ class LZ4Codec(metaclass=_LZ4CodecMeta):
             dst_off = np.concatenate(([0], np.cumsum(dst_len[:-1], dtype=np.int64))).astype(np.int64)
             dst = np.zeros(int(dst_len.astype(np.int64).sum()), dtype=np.uint8)
             res = np.zeros(len(todo), dtype=np.int32)
-            b = _batch(src, src_off, src_len, dst, dst_off, dst_len, res)
+            b = _p.host_blocks(src, src_off, src_len, dst, dst_off, dst_len, res)
             _lib.check(_lib.lib().lz4hip_decode_batch_host(C.byref(b), 1))
             if not (res == src_len).all():                           # Decode64: consumed != inputLength (Unsafe.cs:373-378)
                 raise ArgumentException("LZ4 block is corrupted, or invalid length has been given.")

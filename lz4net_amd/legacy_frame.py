@@ -20,16 +20,14 @@ import ctypes as C
 
 import numpy as np
 
-from . import _lib
+from . import _lib, _plumbing as _p
 from .codec import ArgumentException
-from .stream import _batch
 
 MAGIC = 0x184C2102
 CHUNK_SIZE = 8 << 20
 
 
-def _bound(n: int) -> int:
-    return n + n // 255 + 16                                       # LZ4_compressBound, original/lz4.h:85-86
+_bound = _p.compress_bound
 
 
 def compress_frame(data, high_compression: bool = False, chunk_size: int = CHUNK_SIZE) -> bytes:
@@ -45,8 +43,8 @@ def compress_frame(data, high_compression: bool = False, chunk_size: int = CHUNK
     dst_off = np.concatenate(([0], np.cumsum(caps[:-1], dtype=np.int64))).astype(np.int64)
     comp = np.zeros(int(caps.astype(np.int64).sum()), dtype=np.uint8)
     res = np.zeros(n, dtype=np.int32)
-    b = _batch(raw, offs, lens, comp, dst_off, caps, res)
-    _lib.check(_lib.lib().lz4hip_encode_batch_host(C.byref(b), _lib.MODE_HC if high_compression else _lib.MODE_FAST))
+    b = _p.host_blocks(raw, offs, lens, comp, dst_off, caps, res)
+    _lib.check(_lib.lib().lz4hip_encode_batch_host(C.byref(b), _p.mode(high_compression)))
     for i in range(n):
         size = int(res[i])
         if size <= 0:                                              # cannot happen with a compressBound-sized buffer
@@ -89,7 +87,7 @@ def decompress_frame(frame, chunk_size: int = CHUNK_SIZE) -> bytes:
     caps = np.full(n, chunk_size, dtype=np.int32)
     out = np.zeros(n * chunk_size, dtype=np.uint8)
     res = np.zeros(n, dtype=np.int32)
-    b = _batch(data, src_off, src_len, out, dst_off, caps, res)
+    b = _p.host_blocks(data, src_off, src_len, out, dst_off, caps, res)
     _lib.check(_lib.lib().lz4hip_decode_batch_host(C.byref(b), 0))
     if (res < 0).any():
         raise ArgumentException("Decoding Failed ! Corrupted input !")
@@ -126,19 +124,15 @@ def _check_chunk_size(chunk_size) -> int:
 def compress_frame_device(t, high_compression: bool = False, chunk_size: int = CHUNK_SIZE):
     """compress_frame for a 1-D uint8 CUDA tensor, entirely on the device, on torch's current stream: the same bytes, returned as a 1-D
     uint8 CUDA tensor.  Waits for the device once, to learn the frame's length."""
-    import torch
-    from .stream import _check_device_bytes
-    t = _check_device_bytes(t, "t")
+    t = _p.check_device_bytes(t, "t")
     chunk_size = _check_chunk_size(chunk_size)
-    with torch.cuda.device(t.device):
-        L = _lib.lib()
+    with _p.DeviceCall(t) as d:
         n = t.numel()
-        out = torch.empty(L.lz4hip_frame_bound(n, chunk_size), dtype=torch.uint8, device=t.device)
-        scratch = torch.empty(L.lz4hip_frame_encode_scratch_bytes(n, chunk_size), dtype=torch.uint8, device=t.device)
-        out_len = torch.empty(1, dtype=torch.int64, device=t.device)
-        _lib.check(L.lz4hip_frame_encode_device(t.data_ptr(), n, chunk_size, _lib.MODE_HC if high_compression else _lib.MODE_FAST,
-                                                out.data_ptr(), out.numel(), out_len.data_ptr(), scratch.data_ptr(), scratch.numel(),
-                                                torch.cuda.current_stream(t.device).cuda_stream))
+        out = d.u8(d.lib.lz4hip_frame_bound(n, chunk_size))
+        scratch = d.u8(d.lib.lz4hip_frame_encode_scratch_bytes(n, chunk_size))
+        out_len = d.i64(1)
+        _lib.check(d.lib.lz4hip_frame_encode_device(t.data_ptr(), n, chunk_size, _p.mode(high_compression), out.data_ptr(), out.numel(),
+                                                    out_len.data_ptr(), scratch.data_ptr(), scratch.numel(), d.stream))
         return out[:int(out_len.item())]
 
 
@@ -146,35 +140,26 @@ def decompress_frame_device(t, chunk_size: int = CHUNK_SIZE):
     """decompress_frame for a 1-D uint8 CUDA tensor, on torch's current stream: the size field walk, the size of every chunk and the block
     decode run on the device, into a buffer of exactly the decoded size; the host reads the index's result once (to size the output)
     and the final outcome once."""
-    import torch
-    from .stream import _check_device_bytes
-    t = _check_device_bytes(t, "t")
+    t = _p.check_device_bytes(t, "t")
     chunk_size = _check_chunk_size(chunk_size)
-    with torch.cuda.device(t.device):
-        L = _lib.lib()
-        dev = t.device
-        s = torch.cuda.current_stream(dev).cuda_stream
+    with _p.DeviceCall(t) as d:
         n = t.numel()
-        info_dev = torch.zeros(C.sizeof(_lib.FrameInfo), dtype=torch.uint8, device=dev)
+        info_dev = d.record(_lib.FrameInfo)
 
-        def read_info():
-            return _lib.FrameInfo.from_buffer_copy(info_dev.cpu().numpy().tobytes())
+        def index(max_chunks):
+            scratch = d.u8(d.lib.lz4hip_frame_decode_scratch_bytes(max_chunks))
+            _lib.check(d.lib.lz4hip_frame_index_device(t.data_ptr(), n, chunk_size, max_chunks, scratch.data_ptr(), scratch.numel(),
+                                                       info_dev.data_ptr(), d.stream))
+            info = _p.read_record(info_dev, _lib.FrameInfo)
+            return (scratch, info), (int(info.chunks) if info.error == _lib.FRAME_TABLE_FULL else None)
 
-        max_chunks = n // chunk_size + 16
-        for _ in range(2):
-            scratch = torch.empty(L.lz4hip_frame_decode_scratch_bytes(max_chunks), dtype=torch.uint8, device=dev)
-            _lib.check(L.lz4hip_frame_index_device(t.data_ptr(), n, chunk_size, max_chunks, scratch.data_ptr(), scratch.numel(),
-                                                   info_dev.data_ptr(), s))
-            info = read_info()
-            if info.error != _lib.FRAME_TABLE_FULL:
-                break
-            max_chunks = int(info.chunks)
+        (scratch, info), max_chunks = _p.settle(2, n // chunk_size + 16, index)
         if info.error == _lib.FRAME_TABLE_FULL:
             raise _lib.Lz4HipError("frame decode: the size field walk did not settle")
-        out = torch.empty(int(info.decoded_bytes), dtype=torch.uint8, device=dev)
-        _lib.check(L.lz4hip_frame_decode_device(t.data_ptr(), C.byref(info), max_chunks, scratch.data_ptr(), scratch.numel(),
-                                                out.data_ptr(), out.numel(), info_dev.data_ptr(), s))
-        info = read_info()
+        out = d.u8(int(info.decoded_bytes))
+        _lib.check(d.lib.lz4hip_frame_decode_device(t.data_ptr(), C.byref(info), max_chunks, scratch.data_ptr(), scratch.numel(),
+                                                    out.data_ptr(), out.numel(), info_dev.data_ptr(), d.stream))
+        info = _p.read_record(info_dev, _lib.FrameInfo)
         if info.error != _lib.FRAME_OK:
             raise _frame_error(info.error, info.error_offset, n)
         return out
@@ -189,31 +174,24 @@ def decompress_frame_compact_device(t, chunk_size: int = CHUNK_SIZE, round_chunk
     host reads the outcome once, and only a frame with more chunks than the table or more bytes than the guess is decoded again, into
     the count and the size that record gave.  round_chunks = K > 0 decodes K chunks at a time through a ring of K chunk_size slots instead
     of one slot per table row: less scratch, but the rounds do not overlap."""
-    import torch
-    from .stream import _check_device_bytes
-    t = _check_device_bytes(t, "t")
+    t = _p.check_device_bytes(t, "t")
     chunk_size = _check_chunk_size(chunk_size)
-    with torch.cuda.device(t.device):
-        L = _lib.lib()
-        dev = t.device
-        s = torch.cuda.current_stream(dev).cuda_stream
+    with _p.DeviceCall(t) as d:
         n = t.numel()
-        info_dev = torch.zeros(C.sizeof(_lib.FrameInfo), dtype=torch.uint8, device=dev)
+        info_dev = d.record(_lib.FrameInfo)
+
+        def decode(guess):
+            max_chunks, out_bytes = guess
+            need = _lib.check(d.lib.lz4hip_frame_decode_compact_scratch_bytes(chunk_size, max_chunks, round_chunks))
+            scratch, out = d.u8(need), d.u8(out_bytes)
+            _lib.check(d.lib.lz4hip_frame_decode_compact_device(t.data_ptr(), n, chunk_size, max_chunks, round_chunks, scratch.data_ptr(), need,
+                                                                out.data_ptr(), out_bytes, info_dev.data_ptr(), d.stream))
+            info = _p.read_record(info_dev, _lib.FrameInfo)
+            return (out, info), _p.table_or_output(info, "chunks", _lib.FRAME_TABLE_FULL, guess)
+
         max_chunks = n // chunk_size + 16
         out_bytes = min(4 * n, min(max_chunks, n // 4) * chunk_size)           # (a chunk takes at least its 4-byte size field)
-        for _ in range(3):
-            need = _lib.check(L.lz4hip_frame_decode_compact_scratch_bytes(chunk_size, max_chunks, round_chunks))
-            scratch = torch.empty(need, dtype=torch.uint8, device=dev)
-            out = torch.empty(out_bytes, dtype=torch.uint8, device=dev)
-            _lib.check(L.lz4hip_frame_decode_compact_device(t.data_ptr(), n, chunk_size, max_chunks, round_chunks, scratch.data_ptr(), need,
-                                                            out.data_ptr(), out_bytes, info_dev.data_ptr(), s))
-            info = _lib.FrameInfo.from_buffer_copy(info_dev.cpu().numpy().tobytes())
-            if info.error == _lib.FRAME_TABLE_FULL:
-                max_chunks = int(info.chunks)
-            elif info.decoded_bytes > out_bytes:
-                out_bytes = int(info.decoded_bytes)
-            else:
-                break
+        (out, info), (max_chunks, out_bytes) = _p.settle(3, (max_chunks, out_bytes), decode)
         if info.error == _lib.FRAME_TABLE_FULL or info.decoded_bytes > out_bytes:
             raise _lib.Lz4HipError("frame decode: the size field walk did not settle")
         if info.error != _lib.FRAME_OK:
@@ -221,37 +199,27 @@ def decompress_frame_compact_device(t, chunk_size: int = CHUNK_SIZE, round_chunk
         return out[:int(info.decoded_bytes)]
 
 
-def _host_bytes(data):
-    if isinstance(data, np.ndarray):
-        return np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
-    return np.frombuffer(bytes(data), dtype=np.uint8)
-
-
 def compress_frame_host(data, high_compression: bool = False, chunk_size: int = CHUNK_SIZE) -> bytes:
     """compress_frame through lz4hip_frame_encode_host: one staged call, the frame packed on the device."""
-    raw = _host_bytes(data)
+    raw = _p.host_bytes(data)
     chunk_size = _check_chunk_size(chunk_size)
     L = _lib.lib()
     bound = L.lz4hip_frame_bound(raw.size, chunk_size)
     out = np.empty(bound, np.uint8)
     out_len = C.c_int64(0)
-    _lib.check(L.lz4hip_frame_encode_host(raw.ctypes.data, raw.size, chunk_size, _lib.MODE_HC if high_compression else _lib.MODE_FAST,
-                                          out.ctypes.data, bound, C.byref(out_len)))
+    _lib.check(L.lz4hip_frame_encode_host(raw.ctypes.data, raw.size, chunk_size, _p.mode(high_compression), out.ctypes.data, bound,
+                                          C.byref(out_len)))
     return out[:out_len.value].tobytes()
 
 
 def decompress_frame_host(frame, chunk_size: int = CHUNK_SIZE) -> bytes:
     """decompress_frame through lz4hip_frame_decode_host: a size query (dst_cap = 0), then the call that decodes into exactly that size."""
-    buf = _host_bytes(frame)
+    buf = _p.host_bytes(frame)
     chunk_size = _check_chunk_size(chunk_size)
     L = _lib.lib()
     info = _lib.FrameInfo()
-    rc = L.lz4hip_frame_decode_host(buf.ctypes.data, buf.size, chunk_size, None, 0, C.byref(info))
-    out = np.empty(max(int(info.decoded_bytes), 1), np.uint8)
-    if rc == _lib.E_ARGUMENT and info.decoded_bytes > 0:
-        rc = L.lz4hip_frame_decode_host(buf.ctypes.data, buf.size, chunk_size, out.ctypes.data, int(info.decoded_bytes), C.byref(info))
-    if rc != info.error:                                              # (the outcome itself is info.error)
-        _lib.check(rc)
+    out = _p.sized_decode_host(lambda dst, dst_cap: L.lz4hip_frame_decode_host(buf.ctypes.data, buf.size, chunk_size, dst, dst_cap, C.byref(info)),
+                               info, after_e_argument_only=True)
     if info.error != _lib.FRAME_OK:
         raise _frame_error(info.error, info.error_offset, buf.size)
-    return out[:int(info.decoded_bytes)].tobytes()
+    return out.tobytes()

@@ -15,7 +15,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _lib
+from . import _lib, _plumbing as _p
 from .codec import ArgumentException
 
 MAGIC = 0x184D2204
@@ -114,24 +114,24 @@ def _encode_flags(block_checksum, content_checksum, content_size) -> int:
             (_lib.LZ4F_CONTENT_SIZE if content_size else 0))
 
 
+def _verify_flags(verify) -> int:
+    return (_lib.LZ4F_VERIFY_BLOCKS | _lib.LZ4F_VERIFY_CONTENT) if verify else 0
+
+
 def compress_frame_device(t, block_size: int = 65536, high_compression: bool = False, block_checksum: bool = False,
                           content_checksum: bool = False, content_size: bool = True):
     """One LZ4 frame of a 1-D uint8 CUDA tensor, entirely on the device, on torch's current stream, returned as a 1-D uint8 CUDA tensor:
     independent blocks of block_size bytes, a block that does not shrink stored raw.  The content checksum is ONE serial row of the
     checksum kernel over the whole source.  Waits for the device once, to learn the frame's length."""
-    import torch
-    from .stream import _check_device_bytes
-    t = _check_device_bytes(t, "t")
+    t = _p.check_device_bytes(t, "t")
     bid, flags = _block_id(block_size), _encode_flags(block_checksum, content_checksum, content_size)
-    with torch.cuda.device(t.device):
-        L = _lib.lib()
+    with _p.DeviceCall(t) as d:
         n = t.numel()
-        out = torch.empty(L.lz4hip_lz4f_bound(n, bid, flags), dtype=torch.uint8, device=t.device)
-        scratch = torch.empty(max(L.lz4hip_lz4f_encode_scratch_bytes(n, bid), 1), dtype=torch.uint8, device=t.device)
-        out_len = torch.empty(1, dtype=torch.int64, device=t.device)
-        _lib.check(L.lz4hip_lz4f_encode_device(t.data_ptr(), n, bid, _lib.MODE_HC if high_compression else _lib.MODE_FAST, flags,
-                                               out.data_ptr(), out.numel(), out_len.data_ptr(), scratch.data_ptr(), scratch.numel(),
-                                               torch.cuda.current_stream(t.device).cuda_stream))
+        out = d.u8(d.lib.lz4hip_lz4f_bound(n, bid, flags))
+        scratch = d.u8(max(d.lib.lz4hip_lz4f_encode_scratch_bytes(n, bid), 1))
+        out_len = d.i64(1)
+        _lib.check(d.lib.lz4hip_lz4f_encode_device(t.data_ptr(), n, bid, _p.mode(high_compression), flags, out.data_ptr(), out.numel(),
+                                                   out_len.data_ptr(), scratch.data_ptr(), scratch.numel(), d.stream))
         return out[:int(out_len.item())]
 
 
@@ -146,14 +146,10 @@ def decompress_frame_device(t, verify: bool = True, round_blocks: int = 0):
     integrity is known.  round_blocks = K > 0 decodes K blocks at a time through a ring of K slots.  Raises ArgumentException with the
     outcome's text."""
     import torch
-    from .stream import _check_device_bytes
-    t = _check_device_bytes(t, "t")
-    flags = (_lib.LZ4F_VERIFY_BLOCKS | _lib.LZ4F_VERIFY_CONTENT) if verify else 0
-    with torch.cuda.device(t.device):
-        L = _lib.lib()
-        dev = t.device
-        s = torch.cuda.current_stream(dev).cuda_stream
-        info_dev = torch.zeros(C.sizeof(_lib.Lz4fInfo), dtype=torch.uint8, device=dev)
+    t = _p.check_device_bytes(t, "t")
+    flags = _verify_flags(verify)
+    with _p.DeviceCall(t) as d:
+        info_dev = d.record(_lib.Lz4fInfo)
         parts, pos, n = [], 0, t.numel()
         if n == 0:
             raise _frame_error(_lib.LZ4F_BAD_MAGIC, 0)
@@ -169,22 +165,20 @@ def decompress_frame_device(t, verify: bool = True, round_blocks: int = 0):
                 pos += 8 + head["size"]
                 continue
             rest = n - pos
+
+            def decode(guess):
+                max_blocks, out_bytes = guess
+                need = _lib.check(d.lib.lz4hip_lz4f_decode_scratch_bytes(head["block_max"], max_blocks, round_blocks))
+                scratch, out = d.u8(need), d.u8(out_bytes)
+                _lib.check(d.lib.lz4hip_lz4f_decode_device(t.data_ptr() + pos, rest, head["block_max"], max_blocks, round_blocks, flags,
+                                                           scratch.data_ptr(), need, out.data_ptr(), out_bytes, info_dev.data_ptr(), d.stream))
+                info = _p.read_record(info_dev, _lib.Lz4fInfo)
+                return (out, info), _p.table_or_output(info, "blocks", _lib.LZ4F_TABLE_FULL, guess)
+
             known = head["content_size"]
             out_bytes = known if known is not None and known <= 255 * rest else 4 * rest
             max_blocks = (out_bytes if known is not None else rest) // head["block_max"] + 16
-            for _ in range(3):
-                need = _lib.check(L.lz4hip_lz4f_decode_scratch_bytes(head["block_max"], max_blocks, round_blocks))
-                scratch = torch.empty(need, dtype=torch.uint8, device=dev)
-                out = torch.empty(out_bytes, dtype=torch.uint8, device=dev)
-                _lib.check(L.lz4hip_lz4f_decode_device(t.data_ptr() + pos, rest, head["block_max"], max_blocks, round_blocks, flags, scratch.data_ptr(),
-                                                       need, out.data_ptr(), out_bytes, info_dev.data_ptr(), s))
-                info = _lib.Lz4fInfo.from_buffer_copy(info_dev.cpu().numpy().tobytes())
-                if info.error == _lib.LZ4F_TABLE_FULL:
-                    max_blocks = int(info.blocks)
-                elif info.decoded_bytes > out_bytes:
-                    out_bytes = int(info.decoded_bytes)
-                else:
-                    break
+            (out, info), (max_blocks, out_bytes) = _p.settle(3, (max_blocks, out_bytes), decode)
             if info.error == _lib.LZ4F_TABLE_FULL or info.decoded_bytes > out_bytes:
                 raise _lib.Lz4HipError("lz4 frame decode: the size field walk did not settle")
             if info.error != _lib.LZ4F_OK:
@@ -192,35 +186,29 @@ def decompress_frame_device(t, verify: bool = True, round_blocks: int = 0):
             parts.append(out[:int(info.decoded_bytes)])
             pos += int(info.frame_bytes)
         if not parts:                                                 # (skippable frames only)
-            return torch.empty(0, dtype=torch.uint8, device=dev)
+            return d.u8(0)
         return parts[0] if len(parts) == 1 else torch.cat(parts)
-
-
-def _host_bytes(data):
-    if isinstance(data, np.ndarray):
-        return np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
-    return np.frombuffer(bytes(data), dtype=np.uint8)
 
 
 def compress_frame_host(data, block_size: int = 65536, high_compression: bool = False, block_checksum: bool = False,
                         content_checksum: bool = False, content_size: bool = True) -> bytes:
     """compress_frame_device for host bytes, through lz4hip_lz4f_encode_host: one staged call, the frame packed on the device."""
-    raw = _host_bytes(data)
+    raw = _p.host_bytes(data)
     bid, flags = _block_id(block_size), _encode_flags(block_checksum, content_checksum, content_size)
     L = _lib.lib()
     bound = L.lz4hip_lz4f_bound(raw.size, bid, flags)
     out = np.empty(bound, np.uint8)
     out_len = C.c_int64(0)
-    _lib.check(L.lz4hip_lz4f_encode_host(raw.ctypes.data, raw.size, bid, _lib.MODE_HC if high_compression else _lib.MODE_FAST, flags,
-                                         out.ctypes.data, bound, C.byref(out_len)))
+    _lib.check(L.lz4hip_lz4f_encode_host(raw.ctypes.data, raw.size, bid, _p.mode(high_compression), flags, out.ctypes.data, bound,
+                                         C.byref(out_len)))
     return out[:out_len.value].tobytes()
 
 
 def decompress_frame_host(frame, verify: bool = True) -> bytes:
     """decompress_frame_device for host bytes, through lz4hip_lz4f_decode_host: per frame a size query (dst_cap = 0), then the call that
     decodes into exactly that size.  Appended frames follow each other; skippable frames are skipped."""
-    buf = _host_bytes(frame)
-    flags = (_lib.LZ4F_VERIFY_BLOCKS | _lib.LZ4F_VERIFY_CONTENT) if verify else 0
+    buf = _p.host_bytes(frame)
+    flags = _verify_flags(verify)
     L = _lib.lib()
     parts, pos = [], 0
     if buf.size == 0:
@@ -228,15 +216,11 @@ def decompress_frame_host(frame, verify: bool = True) -> bytes:
     while pos < buf.size:
         info = _lib.Lz4fInfo()
         at, rest = buf.ctypes.data + pos, buf.size - pos
-        rc = L.lz4hip_lz4f_decode_host(at, rest, flags, None, 0, C.byref(info))
-        out = np.empty(max(int(info.decoded_bytes), 1), np.uint8)
-        if rc == _lib.E_ARGUMENT and info.decoded_bytes > 0:
-            rc = L.lz4hip_lz4f_decode_host(at, rest, flags, out.ctypes.data, int(info.decoded_bytes), C.byref(info))
-        if rc != info.error:                                          # (the outcome itself is info.error)
-            _lib.check(rc)
+        out = _p.sized_decode_host(lambda dst, dst_cap: L.lz4hip_lz4f_decode_host(at, rest, flags, dst, dst_cap, C.byref(info)), info,
+                                   after_e_argument_only=True)
         if info.error != _lib.LZ4F_OK:
             raise _frame_error(info.error, pos + info.error_offset if info.error_offset >= 0 else -1)
-        parts.append(out[:int(info.decoded_bytes)].tobytes())
+        parts.append(out.tobytes())
         pos += int(info.frame_bytes)
     return b"".join(parts)
 
@@ -245,13 +229,12 @@ def xxh32_rows_device(data, off, lens, seed: int = 0):
     """XXH32 of rows of a 1-D uint8 CUDA tensor on torch's current stream: row i is data[off[i] : off[i] + lens[i]] (off: int64 CUDA
     tensor, lens: int32 CUDA tensor).  Returns the hashes as an int32 CUDA tensor of uint32 bit patterns; launch-only."""
     import torch
-    from .stream import _check_device_bytes
-    data = _check_device_bytes(data, "data")
+    data = _p.check_device_bytes(data, "data")
     if off.dtype != torch.int64 or lens.dtype != torch.int32 or off.numel() != lens.numel() or not (off.is_cuda and lens.is_cuda):
         raise ArgumentException("off must be an int64 and lens an int32 CUDA tensor of the same length")
-    with torch.cuda.device(data.device):
+    with _p.DeviceCall(data) as d:
         n = off.numel()
-        sums = torch.empty(n, dtype=torch.int32, device=data.device)
-        _lib.check(_lib.lib().lz4hip_xxh32_rows_device(data.data_ptr(), off.contiguous().data_ptr(), 0, lens.contiguous().data_ptr(), 0,
-                                                       seed & 0xFFFFFFFF, sums.data_ptr(), n, torch.cuda.current_stream(data.device).cuda_stream))
+        sums = d.i32(n)
+        _lib.check(d.lib.lz4hip_xxh32_rows_device(data.data_ptr(), off.contiguous().data_ptr(), 0, lens.contiguous().data_ptr(), 0,
+                                                  seed & 0xFFFFFFFF, sums.data_ptr(), n, d.stream))
         return sums

@@ -18,7 +18,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _lib
+from . import _lib, _plumbing as _p
 from .codec import ArgumentException
 
 FLAG_COMPRESSED, FLAG_HIGH_COMPRESSION = 1, 2
@@ -55,13 +55,6 @@ def read_varint(buf, pos: int):
             return result & 0xFFFFFFFFFFFFFFFF, pos             # (a ulong: of a tenth byte only bit 0 survives its shift by 63)
 
 
-def _batch(src, src_off, src_len, dst, dst_off, dst_cap, result):
-    n = len(src_len)
-    return _lib.Batch(src=src.ctypes.data, src_off=src_off.ctypes.data, src_stride=0, src_len=src_len.ctypes.data,
-                      dst=dst.ctypes.data, dst_off=dst_off.ctypes.data, dst_stride=0, dst_cap=dst_cap.ctypes.data,
-                      dst_cap_all=0, src_len_all=0, result=result.ctypes.data, n_blocks=n)
-
-
 def compress_stream(data, block_size: int = DEFAULT_BLOCK_SIZE, high_compression: bool = False) -> bytes:
     """LZ4Stream(Compress).Write(data) + Close(): every chunk of `data` encoded in one GPU batch."""
     block_size = max(16, int(block_size))
@@ -73,8 +66,8 @@ def compress_stream(data, block_size: int = DEFAULT_BLOCK_SIZE, high_compression
     lens = np.minimum(block_size, raw.size - offs).astype(np.int32)
     comp = np.zeros(raw.size, dtype=np.uint8)                  # outputLength = inputLength per chunk, packed at the same offsets
     res = np.zeros(n, dtype=np.int32)
-    b = _batch(raw, offs, lens, comp, offs, lens, res)
-    _lib.check(_lib.lib().lz4hip_encode_batch_host(C.byref(b), _lib.MODE_HC if high_compression else _lib.MODE_FAST))
+    b = _p.host_blocks(raw, offs, lens, comp, offs, lens, res)
+    _lib.check(_lib.lib().lz4hip_encode_batch_host(C.byref(b), _p.mode(high_compression)))
     out = bytearray()
     for i in range(n):
         o, ln, cl = int(offs[i]), int(lens[i]), int(res[i])
@@ -142,7 +135,7 @@ def decompress_stream(stream) -> bytes:
         dst_off = np.array([out_off[i] for i in idx], dtype=np.int64)
         dst_len = np.array([chunks[i][1] for i in idx], dtype=np.int32)
         res = np.zeros(len(idx), dtype=np.int32)
-        b = _batch(data, src_off, src_len, out, dst_off, dst_len, res)
+        b = _p.host_blocks(data, src_off, src_len, out, dst_off, dst_len, res)
         _lib.check(_lib.lib().lz4hip_decode_batch_host(C.byref(b), 1))
         if not (res == src_len).all():                       # Decode64: consumed != inputLength (Unsafe.cs:373-378)
             raise ArgumentException("LZ4 block is corrupted, or invalid length has been given.")
@@ -151,35 +144,21 @@ def decompress_stream(stream) -> bytes:
 
 # ---- device-resident streams (lz4hip_stream_* of include/lz4hip.h; kernels in csrc/lz4hip_stream.hpp) ------------------------------
 
-def _check_device_bytes(t, name):
-    import torch
-    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.uint8 or t.dim() != 1:
-        raise ArgumentException(f"{name} must be a 1-D uint8 CUDA tensor")
-    return t.contiguous()
-
-
 def compress_stream_device(t, block_size: int = DEFAULT_BLOCK_SIZE, high_compression: bool = False):
     """compress_stream for a 1-D uint8 CUDA tensor, entirely on the device, on torch's current stream: the same bytes, returned as a
     1-D uint8 CUDA tensor.  Waits for the device once, to learn the stream's length."""
-    import torch
-    t = _check_device_bytes(t, "t")
-    with torch.cuda.device(t.device):
-        return _compress_stream_device(t, max(16, int(block_size)), high_compression)
-
-
-def _compress_stream_device(t, block_size, high_compression):
-    import torch
-    L = _lib.lib()
-    n = t.numel()
-    if n == 0:
-        return torch.empty(0, dtype=torch.uint8, device=t.device)
-    out = torch.empty(L.lz4hip_stream_bound(n, block_size), dtype=torch.uint8, device=t.device)
-    scratch = torch.empty(L.lz4hip_stream_encode_scratch_bytes(n, block_size), dtype=torch.uint8, device=t.device)
-    out_len = torch.empty(1, dtype=torch.int64, device=t.device)
-    _lib.check(L.lz4hip_stream_encode_device(t.data_ptr(), n, block_size, _lib.MODE_HC if high_compression else _lib.MODE_FAST,
-                                             out.data_ptr(), out.numel(), out_len.data_ptr(), scratch.data_ptr(), scratch.numel(),
-                                             torch.cuda.current_stream(t.device).cuda_stream))
-    return out[:int(out_len.item())]
+    t = _p.check_device_bytes(t, "t")
+    block_size = max(16, int(block_size))
+    with _p.DeviceCall(t) as d:
+        n = t.numel()
+        if n == 0:
+            return d.u8(0)
+        out = d.u8(d.lib.lz4hip_stream_bound(n, block_size))
+        scratch = d.u8(d.lib.lz4hip_stream_encode_scratch_bytes(n, block_size))
+        out_len = d.i64(1)
+        _lib.check(d.lib.lz4hip_stream_encode_device(t.data_ptr(), n, block_size, _p.mode(high_compression), out.data_ptr(), out.numel(),
+                                                     out_len.data_ptr(), scratch.data_ptr(), scratch.numel(), d.stream))
+        return out[:int(out_len.item())]
 
 
 def _stream_error(info):
@@ -196,55 +175,34 @@ def _stream_error(info):
     return e
 
 
+def _table_full(info):
+    """the next table size for _p.settle: the chunk count a walk reported when its table was too small, else None"""
+    return int(info.chunks) if info.error == _lib.STREAM_TABLE_FULL else None
+
+
 def decompress_stream_device(t):
     """decompress_stream for a 1-D uint8 CUDA tensor, on torch's current stream: the header walk, the block decode and the raw copies
     run on the device; the host reads the walk's result once (to size the output) and the final outcome once."""
-    import torch
-    t = _check_device_bytes(t, "t")
-    with torch.cuda.device(t.device):
-        return _decompress_stream_device(t)
+    t = _p.check_device_bytes(t, "t")
+    with _p.DeviceCall(t) as d:
+        n = t.numel()
+        info_dev = d.record(_lib.StreamInfo)
 
+        def index(max_chunks):
+            scratch = d.u8(d.lib.lz4hip_stream_decode_scratch_bytes(max_chunks))
+            _lib.check(d.lib.lz4hip_stream_index_device(t.data_ptr(), n, max_chunks, scratch.data_ptr(), scratch.numel(), info_dev.data_ptr(),
+                                                        d.stream))
+            info = _p.read_record(info_dev, _lib.StreamInfo)
+            return (scratch, info), _table_full(info)
 
-def _decompress_stream_device(t):
-    import torch
-    L = _lib.lib()
-    dev = t.device
-    s = torch.cuda.current_stream(dev).cuda_stream
-    n = t.numel()
-    info_dev = torch.zeros(C.sizeof(_lib.StreamInfo), dtype=torch.uint8, device=dev)
-
-    def read_info():
-        return _lib.StreamInfo.from_buffer_copy(info_dev.cpu().numpy().tobytes())
-
-    max_chunks = (n + 4095) // 4096 + 16
-    for _ in range(2):
-        scratch = torch.empty(L.lz4hip_stream_decode_scratch_bytes(max_chunks), dtype=torch.uint8, device=dev)
-        _lib.check(L.lz4hip_stream_index_device(t.data_ptr(), n, max_chunks, scratch.data_ptr(), scratch.numel(), info_dev.data_ptr(), s))
-        info = read_info()
-        if info.error != _lib.STREAM_TABLE_FULL:
-            break
-        max_chunks = int(info.chunks)
-    out = torch.empty(int(info.decoded_bytes), dtype=torch.uint8, device=dev)
-    _lib.check(L.lz4hip_stream_decode_device(t.data_ptr(), C.byref(info), max_chunks, scratch.data_ptr(), scratch.numel(),
-                                             out.data_ptr(), out.numel(), info_dev.data_ptr(), s))
-    info = read_info()
-    if info.error != _lib.STREAM_OK:
-        raise _stream_error(info)
-    return out
-
-
-def _check_out(out, like):
-    import torch
-    if not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != torch.uint8 or out.dim() != 1 or not out.is_contiguous():
-        raise ArgumentException("out must be a contiguous 1-D uint8 CUDA tensor")
-    if out.device != like.device:
-        raise ArgumentException("out must be on the source's device")
-    return out
-
-
-def _read_info(info, cls):
-    """the one place that waits for the device: the info record a *_into call left there, as its ctypes struct"""
-    return cls.from_buffer_copy(info.cpu().numpy().tobytes())
+        (scratch, info), max_chunks = _p.settle(2, (n + 4095) // 4096 + 16, index)      # (a table still too small: the decode's outcome says so)
+        out = d.u8(int(info.decoded_bytes))
+        _lib.check(d.lib.lz4hip_stream_decode_device(t.data_ptr(), C.byref(info), max_chunks, scratch.data_ptr(), scratch.numel(),
+                                                     out.data_ptr(), out.numel(), info_dev.data_ptr(), d.stream))
+        info = _p.read_record(info_dev, _lib.StreamInfo)
+        if info.error != _lib.STREAM_OK:
+            raise _stream_error(info)
+        return out
 
 
 def decompress_stream_into(t, out, max_chunks=None, block_size: int = DEFAULT_BLOCK_SIZE):
@@ -253,25 +211,21 @@ def decompress_stream_into(t, out, max_chunks=None, block_size: int = DEFAULT_BL
     read_stream_info, check it with check_stream_into) and the int64 count of bytes written.  The output is clipped at a chunk boundary
     when `out` is too small; info.decoded_bytes is the size needed all the same.  max_chunks is the chunk table's size: by default
     out.numel() // max(16, block_size) + 16, which holds anything compress_stream_device wrote into `out`'s size with that block size."""
-    import torch
-    t = _check_device_bytes(t, "t")
-    out = _check_out(out, t)
+    t = _p.check_device_bytes(t, "t")
+    out = _p.check_out(out, t)
     if max_chunks is None:
         max_chunks = out.numel() // max(16, int(block_size)) + 16
-    with torch.cuda.device(t.device):
-        L = _lib.lib()
-        dev = t.device
-        info = torch.zeros(C.sizeof(_lib.StreamInfo), dtype=torch.uint8, device=dev)
-        written = torch.zeros(1, dtype=torch.int64, device=dev)
-        scratch = torch.empty(L.lz4hip_stream_decode_into_scratch_bytes(max_chunks), dtype=torch.uint8, device=dev)
-        _lib.check(L.lz4hip_stream_decode_into_device(t.data_ptr(), t.numel(), max_chunks, scratch.data_ptr(), scratch.numel(), out.data_ptr(),
-                                                      out.numel(), info.data_ptr(), written.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+    with _p.DeviceCall(t) as d:
+        info, written = d.record(_lib.StreamInfo), d.i64(1, zero=True)
+        scratch = d.u8(d.lib.lz4hip_stream_decode_into_scratch_bytes(max_chunks))
+        _lib.check(d.lib.lz4hip_stream_decode_into_device(t.data_ptr(), t.numel(), max_chunks, scratch.data_ptr(), scratch.numel(), out.data_ptr(),
+                                                          out.numel(), info.data_ptr(), written.data_ptr(), d.stream))
         return info, written
 
 
 def read_stream_info(info):
     """the lz4hip_stream_info_t a decompress_stream_into call left on the device (waits for the device)"""
-    return _read_info(info, _lib.StreamInfo)
+    return _p.read_record(info, _lib.StreamInfo)
 
 
 def check_stream_into(info, written):
@@ -292,43 +246,11 @@ def check_stream_into(info, written):
 # A batch of n streams is one 1-D uint8 buffer plus int64 offsets[n + 1]: item i is buf[offsets[i]:offsets[i + 1]].  compress_streams_*
 # returns the framed streams in that layout and decompress_streams_* reads it, so one's output is the other's input.
 
-_BAD_OFFSETS = "offsets are invalid for the given buffer"
-
-
-def _check_device_batch(buf, offsets):
-    """a batch on the device: a 1-D uint8 CUDA tensor and its int64 offsets[n + 1] (wrap.py's batches are the same)"""
-    import torch
-    if not isinstance(buf, torch.Tensor) or not buf.is_cuda or buf.dtype != torch.uint8 or buf.dim() != 1:
-        raise ArgumentException("the buffer must be a 1-D uint8 CUDA tensor")
-    if not isinstance(offsets, torch.Tensor) or not offsets.is_cuda or offsets.dtype != torch.int64 or offsets.dim() != 1:
-        raise ArgumentException("offsets must be a 1-D int64 CUDA tensor")
-    if offsets.numel() < 1:
-        raise ArgumentException("offsets must hold n + 1 entries")
-    if offsets.device != buf.device:
-        raise ArgumentException("the buffer and the offsets must be on the same device")
-    return buf.contiguous(), offsets.contiguous()
-
-
-def _check_device_spans(buf, begin, end):
-    """chosen items of an arena on the device: a 1-D uint8 CUDA tensor and the int64 begin[m], end[m] of its spans"""
-    import torch
-    if not isinstance(buf, torch.Tensor) or not buf.is_cuda or buf.dtype != torch.uint8 or buf.dim() != 1:
-        raise ArgumentException("the buffer must be a 1-D uint8 CUDA tensor")
-    for t in (begin, end):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.int64 or t.dim() != 1:
-            raise ArgumentException("begin and end must be 1-D int64 CUDA tensors")
-        if t.device != buf.device:
-            raise ArgumentException("the buffer and the spans must be on the same device")
-    if begin.numel() != end.numel():
-        raise ArgumentException("begin and end must have the same length")
-    return buf.contiguous(), begin.contiguous(), end.contiguous()
-
-
 def streams_error(status: int, index: int, error_offset: int = -1):
     """The exception a sequential [decompress_stream(s) for s in ...] raises at an item with this status (LZ4HIP_STREAM_*, or
     LZ4HIP_E_ARGUMENT for bad offsets), with the item's index in .item_index and the failing header's offset within it in .error_offset."""
     if int(status) == _lib.E_ARGUMENT:
-        e = ArgumentException(_BAD_OFFSETS)
+        e = ArgumentException(_p.BAD_OFFSETS)
         e.error_offset = -1
     else:
         e = _stream_error(_lib.StreamInfo(error=int(status), error_offset=int(error_offset)))
@@ -341,24 +263,19 @@ def compress_streams_device(buf, offsets, block_size: int = DEFAULT_BLOCK_SIZE, 
     device, on torch's current stream -> (packed, packed_offsets): packed_offsets[i] is where item i's stream starts.  The chunks of
     all items are one batch of the block encoder.  Waits for the device once, to learn the total."""
     import torch
-    buf, offsets = _check_device_batch(buf, offsets)
+    buf, offsets = _p.check_device_batch(buf, offsets)
     block_size = max(16, int(block_size))
-    with torch.cuda.device(buf.device):
-        L = _lib.lib()
-        dev = buf.device
+    with _p.DeviceCall(buf) as d:
         n = offsets.numel() - 1
-        bound = L.lz4hip_streams_bound(n, buf.numel(), block_size)
-        out = torch.empty(bound, dtype=torch.uint8, device=dev)
-        out_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
-        scratch = torch.empty(L.lz4hip_streams_encode_scratch_bytes(n, buf.numel(), block_size), dtype=torch.uint8, device=dev)
-        _lib.check(L.lz4hip_streams_encode_device(buf.data_ptr(), buf.numel(), offsets.data_ptr(), n, block_size,
-                                                  _lib.MODE_HC if high_compression else _lib.MODE_FAST, out.data_ptr(), bound,
-                                                  out_off.data_ptr(), scratch.data_ptr(), scratch.numel(),
-                                                  torch.cuda.current_stream(dev).cuda_stream))
+        bound = d.lib.lz4hip_streams_bound(n, buf.numel(), block_size)
+        out, out_off = d.u8(bound), d.i64(n + 1)
+        scratch = d.u8(d.lib.lz4hip_streams_encode_scratch_bytes(n, buf.numel(), block_size))
+        _lib.check(d.lib.lz4hip_streams_encode_device(buf.data_ptr(), buf.numel(), offsets.data_ptr(), n, block_size, _p.mode(high_compression),
+                                                      out.data_ptr(), bound, out_off.data_ptr(), scratch.data_ptr(), scratch.numel(), d.stream))
         bad = ((offsets[1:] < offsets[:-1]).any() | (offsets[0] < 0) | (offsets[-1] > buf.numel())).to(torch.int64).reshape(1)
         total, bad = torch.cat([out_off[n:], bad]).tolist()
         if bad:
-            raise ArgumentException(_BAD_OFFSETS)
+            raise ArgumentException(_p.BAD_OFFSETS)
         return out[:total], out_off
 
 
@@ -369,41 +286,49 @@ def decompress_streams_device(packed, offsets, check: bool = True):
     failing item raises what decompress_stream raises for it (.item_index = its index, .error_offset = the failing header's offset
     within the item), with check=False the per-item statuses (LZ4HIP_STREAM_*, 0 = fine; LZ4HIP_E_ARGUMENT for bad offsets) come back
     as a third value instead.  Waits for the device twice: to size the output, and for the outcome."""
-    import torch
-    packed, offsets = _check_device_batch(packed, offsets)
-    with torch.cuda.device(packed.device):
-        L = _lib.lib()
-        dev = packed.device
-        s = torch.cuda.current_stream(dev).cuda_stream
+    packed, offsets = _p.check_device_batch(packed, offsets)
+    with _p.DeviceCall(packed) as d:
         n = offsets.numel() - 1
-        out_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
-        status = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
-        err_off = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
-        info_dev = torch.zeros(C.sizeof(_lib.StreamsInfo), dtype=torch.uint8, device=dev)
+        out_off, status = d.items(n)
+        err_off = d.i64(max(n, 1))
+        info_dev = d.record(_lib.StreamsInfo)
 
-        def read_info():
-            return _lib.StreamsInfo.from_buffer_copy(info_dev.cpu().numpy().tobytes())
+        def index(max_chunks):
+            scratch = d.u8(d.lib.lz4hip_streams_decode_scratch_bytes(n, max_chunks))
+            _lib.check(d.lib.lz4hip_streams_index_device(packed.data_ptr(), packed.numel(), offsets.data_ptr(), n, max_chunks, out_off.data_ptr(),
+                                                         status.data_ptr(), err_off.data_ptr(), scratch.data_ptr(), scratch.numel(),
+                                                         info_dev.data_ptr(), d.stream))
+            info = _p.read_record(info_dev, _lib.StreamsInfo)
+            return (scratch, info), _table_full(info)
 
-        max_chunks = packed.numel() // 4096 + n + 16
-        for _ in range(2):
-            scratch = torch.empty(L.lz4hip_streams_decode_scratch_bytes(n, max_chunks), dtype=torch.uint8, device=dev)
-            _lib.check(L.lz4hip_streams_index_device(packed.data_ptr(), packed.numel(), offsets.data_ptr(), n, max_chunks, out_off.data_ptr(),
-                                                     status.data_ptr(), err_off.data_ptr(), scratch.data_ptr(), scratch.numel(),
-                                                     info_dev.data_ptr(), s))
-            info = read_info()
-            if info.error != _lib.STREAM_TABLE_FULL:
-                break
-            max_chunks = int(info.chunks)
-        out = torch.empty(int(info.decoded_bytes), dtype=torch.uint8, device=dev)
-        _lib.check(L.lz4hip_streams_decode_device(packed.data_ptr(), packed.numel(), offsets.data_ptr(), n, C.byref(info), max_chunks,
-                                                  scratch.data_ptr(), scratch.numel(), out.data_ptr(), out.numel(), out_off.data_ptr(),
-                                                  status.data_ptr(), err_off.data_ptr(), info_dev.data_ptr(), s))
-        info = read_info()
+        (scratch, info), max_chunks = _p.settle(2, packed.numel() // 4096 + n + 16, index)  # (a table still too small: the decode's outcome says so)
+        out = d.u8(int(info.decoded_bytes))
+        _lib.check(d.lib.lz4hip_streams_decode_device(packed.data_ptr(), packed.numel(), offsets.data_ptr(), n, C.byref(info), max_chunks,
+                                                      scratch.data_ptr(), scratch.numel(), out.data_ptr(), out.numel(), out_off.data_ptr(),
+                                                      status.data_ptr(), err_off.data_ptr(), info_dev.data_ptr(), d.stream))
+        info = _p.read_record(info_dev, _lib.StreamsInfo)
         if not check:
             return out, out_off, status[:n]
         if info.first_error >= 0:
             raise streams_error(info.error, info.first_error, info.error_offset)
         return out, out_off
+
+
+def _streams_into(entry, packed, where, n, out, max_chunks, block_size):
+    """decompress_streams_into and decompress_streams_spans_into: the library call `entry` over the n items that the tensors `where`
+    locate in `packed` (offsets; or begin and end)"""
+    out = _p.check_out(out, packed)
+    if max_chunks is None:
+        max_chunks = out.numel() // max(16, int(block_size)) + n + 16
+    with _p.DeviceCall(packed) as d:
+        out_off, status = d.items(n)
+        err_off = d.i64(max(n, 1))
+        info, written = d.record(_lib.StreamsInfo), d.i64(1, zero=True)
+        scratch = d.u8(d.lib.lz4hip_streams_decode_into_scratch_bytes(n, max_chunks))
+        _lib.check(getattr(d.lib, entry)(packed.data_ptr(), packed.numel(), *(w.data_ptr() for w in where), n, max_chunks, scratch.data_ptr(),
+                                         scratch.numel(), out.data_ptr(), out.numel(), out_off.data_ptr(), status.data_ptr(),
+                                         err_off.data_ptr(), info.data_ptr(), written.data_ptr(), d.stream))
+        return out_off, status[:n], err_off[:n], info, written
 
 
 def decompress_streams_into(packed, offsets, out, max_chunks=None, block_size: int = DEFAULT_BLOCK_SIZE):
@@ -412,26 +337,8 @@ def decompress_streams_into(packed, offsets, out, max_chunks=None, block_size: i
     status and error_offset are per item, info holds the lz4hip_streams_info_t record (read_streams_info, check_streams_into) and
     written_items the int64 count of leading items that fit `out`; the others are not written, and out_off and info.decoded_bytes are
     complete all the same.  max_chunks is the chunk table's size for the whole batch: by default out.numel() // block + n + 16."""
-    import torch
-    packed, offsets = _check_device_batch(packed, offsets)
-    out = _check_out(out, packed)
-    n = offsets.numel() - 1
-    if max_chunks is None:
-        max_chunks = out.numel() // max(16, int(block_size)) + n + 16
-    with torch.cuda.device(packed.device):
-        L = _lib.lib()
-        dev = packed.device
-        out_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
-        status = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
-        err_off = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
-        info = torch.zeros(C.sizeof(_lib.StreamsInfo), dtype=torch.uint8, device=dev)
-        written = torch.zeros(1, dtype=torch.int64, device=dev)
-        scratch = torch.empty(L.lz4hip_streams_decode_into_scratch_bytes(n, max_chunks), dtype=torch.uint8, device=dev)
-        _lib.check(L.lz4hip_streams_decode_into_device(packed.data_ptr(), packed.numel(), offsets.data_ptr(), n, max_chunks, scratch.data_ptr(),
-                                                       scratch.numel(), out.data_ptr(), out.numel(), out_off.data_ptr(), status.data_ptr(),
-                                                       err_off.data_ptr(), info.data_ptr(), written.data_ptr(),
-                                                       torch.cuda.current_stream(dev).cuda_stream))
-        return out_off, status[:n], err_off[:n], info, written
+    packed, offsets = _p.check_device_batch(packed, offsets)
+    return _streams_into("lz4hip_streams_decode_into_device", packed, (offsets,), offsets.numel() - 1, out, max_chunks, block_size)
 
 
 def decompress_streams_spans_into(packed, begin, end, out, max_chunks=None, block_size: int = DEFAULT_BLOCK_SIZE):
@@ -440,26 +347,8 @@ def decompress_streams_spans_into(packed, begin, end, out, max_chunks=None, bloc
     device call whose cost follows m -> (out_off, status, error_offset, info, written_items) as decompress_streams_into returns them,
     indexed by position in the call; check_streams_into reads them.  max_chunks counts the chunks of the chosen items, repeats
     included: by default out.numel() // block + m + 16."""
-    import torch
-    packed, begin, end = _check_device_spans(packed, begin, end)
-    out = _check_out(out, packed)
-    m = begin.numel()
-    if max_chunks is None:
-        max_chunks = out.numel() // max(16, int(block_size)) + m + 16
-    with torch.cuda.device(packed.device):
-        L = _lib.lib()
-        dev = packed.device
-        out_off = torch.empty(m + 1, dtype=torch.int64, device=dev)
-        status = torch.empty(max(m, 1), dtype=torch.int32, device=dev)
-        err_off = torch.empty(max(m, 1), dtype=torch.int64, device=dev)
-        info = torch.zeros(C.sizeof(_lib.StreamsInfo), dtype=torch.uint8, device=dev)
-        written = torch.zeros(1, dtype=torch.int64, device=dev)
-        scratch = torch.empty(L.lz4hip_streams_decode_into_scratch_bytes(m, max_chunks), dtype=torch.uint8, device=dev)
-        _lib.check(L.lz4hip_streams_decode_spans_into_device(packed.data_ptr(), packed.numel(), begin.data_ptr(), end.data_ptr(), m, max_chunks,
-                                                             scratch.data_ptr(), scratch.numel(), out.data_ptr(), out.numel(),
-                                                             out_off.data_ptr(), status.data_ptr(), err_off.data_ptr(), info.data_ptr(),
-                                                             written.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
-        return out_off, status[:m], err_off[:m], info, written
+    packed, begin, end = _p.check_device_spans(packed, begin, end)
+    return _streams_into("lz4hip_streams_decode_spans_into_device", packed, (begin, end), begin.numel(), out, max_chunks, block_size)
 
 
 def stream_directory(t, max_chunks=None, block_size: int = DEFAULT_BLOCK_SIZE):
@@ -469,24 +358,21 @@ def stream_directory(t, max_chunks=None, block_size: int = DEFAULT_BLOCK_SIZE):
     -- and a host copy of out_off as a numpy array.  t[hdr_off[k]:hdr_off[k + 1]] is a one-chunk item for
     decompress_streams_spans_into.  This is the once-per-stream step: the serial header walk, and it waits for the device (twice when
     the default table of t.numel() // block + 16 chunks was too small).  A header error raises what decompress_stream_device raises."""
-    import torch
-    t = _check_device_bytes(t, "t")
+    t = _p.check_device_bytes(t, "t")
     if max_chunks is None:
         max_chunks = t.numel() // max(16, int(block_size)) + 16
-    with torch.cuda.device(t.device):
-        L = _lib.lib()
-        dev = t.device
-        info_dev = torch.zeros(C.sizeof(_lib.StreamInfo), dtype=torch.uint8, device=dev)
-        for _ in range(2):
-            hdr_off = torch.empty(max_chunks + 1, dtype=torch.int64, device=dev)
-            out_off = torch.empty(max_chunks + 1, dtype=torch.int64, device=dev)
-            _lib.check(L.lz4hip_stream_directory_device(t.data_ptr(), t.numel(), max_chunks, hdr_off.data_ptr(), out_off.data_ptr(),
-                                                        info_dev.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
-            info = _read_info(info_dev, _lib.StreamInfo)
-            if info.error != _lib.STREAM_TABLE_FULL:
-                break
-            max_chunks = int(info.chunks)
-        if info.error != _lib.STREAM_OK:
+    with _p.DeviceCall(t) as d:
+        info_dev = d.record(_lib.StreamInfo)
+
+        def walk(max_chunks):
+            hdr_off, out_off = d.i64(max_chunks + 1), d.i64(max_chunks + 1)
+            _lib.check(d.lib.lz4hip_stream_directory_device(t.data_ptr(), t.numel(), max_chunks, hdr_off.data_ptr(), out_off.data_ptr(),
+                                                            info_dev.data_ptr(), d.stream))
+            info = _p.read_record(info_dev, _lib.StreamInfo)
+            return (hdr_off, out_off, info), _table_full(info)
+
+        (hdr_off, out_off, info), _ = _p.settle(2, max_chunks, walk)
+        if info.error != _lib.STREAM_OK:                               # (a table still too small is one of them)
             raise _stream_error(info)
         k = int(info.chunks) + 1
         return hdr_off[:k], out_off[:k], out_off[:k].cpu().numpy()
@@ -497,7 +383,7 @@ def decompress_stream_range(t, directory, start: int, length: int):
     cover the range -- whole chunks, as one-chunk spans in one decompress_streams_spans_into call into a chunk-aligned buffer -- and
     returns the length-byte view of it.  Waits for the device once, for the outcome."""
     import torch
-    t = _check_device_bytes(t, "t")
+    t = _p.check_device_bytes(t, "t")
     hdr_off, out_off, host = directory
     start, length = int(start), int(length)
     total = int(host[-1])
@@ -515,7 +401,7 @@ def decompress_stream_range(t, directory, start: int, length: int):
 
 def read_streams_info(info):
     """the lz4hip_streams_info_t a decompress_streams_into call left on the device (waits for the device)"""
-    return _read_info(info, _lib.StreamsInfo)
+    return _p.read_record(info, _lib.StreamsInfo)
 
 
 def check_streams_into(info, written_items):
@@ -532,55 +418,35 @@ def check_streams_into(info, written_items):
     return h
 
 
-def _check_host_batch(buf, offsets):
-    """the same batch in host memory; bytes-like buffers are taken as uint8 arrays"""
-    if isinstance(buf, (bytes, bytearray, memoryview)):
-        buf = np.frombuffer(buf, dtype=np.uint8)
-    if not isinstance(buf, np.ndarray) or buf.dtype != np.uint8 or buf.ndim != 1:
-        raise ArgumentException("the buffer must be a 1-D uint8 array")
-    if not isinstance(offsets, np.ndarray) or offsets.dtype != np.int64 or offsets.ndim != 1:
-        raise ArgumentException("offsets must be a 1-D int64 array")
-    if offsets.size < 1:
-        raise ArgumentException("offsets must hold n + 1 entries")
-    return np.ascontiguousarray(buf), np.ascontiguousarray(offsets)
-
-
 def compress_streams_host(buf, offsets, block_size: int = DEFAULT_BLOCK_SIZE, high_compression: bool = False):
     """compress_streams_device for host arrays, through lz4hip_streams_encode_host -> (packed, packed_offsets) as numpy arrays."""
-    buf, offsets = _check_host_batch(buf, offsets)
+    buf, offsets = _p.check_host_batch(buf, offsets)
     block_size = max(16, int(block_size))
     L = _lib.lib()
     n = offsets.size - 1
     if n and ((np.diff(offsets) < 0).any() or offsets[0] < 0 or offsets[-1] > buf.size):
-        raise ArgumentException(_BAD_OFFSETS)
+        raise ArgumentException(_p.BAD_OFFSETS)
     bound = L.lz4hip_streams_bound(n, buf.size, block_size)
     out = np.empty(max(bound, 1), np.uint8)
     out_off = np.empty(n + 1, np.int64)
-    _lib.check(L.lz4hip_streams_encode_host(buf.ctypes.data, buf.size, offsets.ctypes.data, n, block_size,
-                                            _lib.MODE_HC if high_compression else _lib.MODE_FAST, out.ctypes.data, bound, out_off.ctypes.data))
+    _lib.check(L.lz4hip_streams_encode_host(buf.ctypes.data, buf.size, offsets.ctypes.data, n, block_size, _p.mode(high_compression),
+                                            out.ctypes.data, bound, out_off.ctypes.data))
     return out[:int(out_off[n])], out_off
 
 
 def decompress_streams_host(packed, offsets, check: bool = True):
     """decompress_streams_device for host arrays, through lz4hip_streams_decode_host -> (data, data_offsets), or (data, data_offsets,
     status) with check=False."""
-    packed, offsets = _check_host_batch(packed, offsets)
+    packed, offsets = _p.check_host_batch(packed, offsets)
     L = _lib.lib()
     n = offsets.size - 1
     out_off = np.empty(n + 1, np.int64)
     status = np.empty(max(n, 1), np.int32)
     err_off = np.empty(max(n, 1), np.int64)
     info = _lib.StreamsInfo()
-    # a size query first (dst_cap = 0: LZ4HIP_E_ARGUMENT with decoded_bytes filled in), then the call that decodes
-    rc = L.lz4hip_streams_decode_host(packed.ctypes.data, packed.size, offsets.ctypes.data, n, None, 0, out_off.ctypes.data, status.ctypes.data,
-                                      err_off.ctypes.data, C.byref(info))
-    out = np.empty(max(int(info.decoded_bytes), 1), np.uint8)
-    if info.decoded_bytes > 0:
-        rc = L.lz4hip_streams_decode_host(packed.ctypes.data, packed.size, offsets.ctypes.data, n, out.ctypes.data, int(info.decoded_bytes),
-                                          out_off.ctypes.data, status.ctypes.data, err_off.ctypes.data, C.byref(info))
-    if rc != info.error:                                              # (the outcome itself is info.error)
-        _lib.check(rc)
-    out = out[:int(info.decoded_bytes)]
+    out = _p.sized_decode_host(lambda dst, dst_cap: L.lz4hip_streams_decode_host(
+        packed.ctypes.data, packed.size, offsets.ctypes.data, n, dst, dst_cap, out_off.ctypes.data, status.ctypes.data, err_off.ctypes.data,
+        C.byref(info)), info)
     if not check:
         return out, out_off, status[:n]
     if info.first_error >= 0:

@@ -20,6 +20,65 @@ def test_exports_match_header():
         assert hasattr(L, name), name
 
 
+def _header():
+    """include/lz4hip.h without its comments"""
+    text = open(os.path.join(ROOT, "include", "lz4hip.h")).read()
+    return re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+
+
+def _c_class(decl: str):
+    """A C type as the ABI passes it: "pointer", or (bits, signed)."""
+    if "*" in decl:
+        return "pointer"
+    words = [w for w in decl.split() if w != "const"]
+    return {("int",): (32, True), ("int32_t",): (32, True), ("unsigned",): (32, False), ("unsigned", "int"): (32, False),
+            ("uint32_t",): (32, False), ("int64_t",): (64, True), ("uint64_t",): (64, False)}[tuple(words)]
+
+
+def _ctypes_class(t):
+    if t in (C.c_void_p, C.c_char_p) or issubclass(t, C._Pointer):
+        return "pointer"
+    return 8 * C.sizeof(t), t(-1).value < 0
+
+
+def test_constants_match_header():
+    from lz4net_amd import _lib
+    defines = re.findall(r"^[ \t]*#[ \t]*define[ \t]+LZ4HIP_(\w+)[ \t]+(\S[^\n]*)$", _header(), re.M)
+    assert len(defines) >= 48, len(defines)
+    for name, value in defines:
+        value = int(value.strip().strip("()").rstrip("uU"), 0)
+        assert getattr(_lib, name, None) == value, (name, value, getattr(_lib, name, None))
+
+
+def test_structs_match_header():
+    from lz4net_amd import _lib
+    structs = re.findall(r"typedef\s+struct\s+lz4hip_(\w+)\s*\{(.*?)\}\s*lz4hip_(\w+)_t\s*;", _header(), re.S)
+    assert len(structs) >= 9, len(structs)
+    for tag, body, alias in structs:
+        assert tag == alias
+        want = []
+        for decl in filter(None, (d.strip() for d in body.split(";"))):
+            ctype, first = re.fullmatch(r"(.*?[\s\*])(\w+(?:\s*,\s*\w+)*)", decl, re.S).groups()
+            want += [(name.strip(), _c_class(ctype)) for name in first.split(",")]
+        cls = getattr(_lib, "".join(part.capitalize() for part in tag.split("_")))
+        assert issubclass(cls, C.Structure) and f"struct lz4hip_{tag} " in cls.__doc__
+        assert [(name, _ctypes_class(t)) for name, t in cls._fields_] == want, tag
+
+
+def test_prototypes_match_header():
+    from lz4net_amd import _lib
+    text = re.sub(r"typedef\s+struct.*?\}\s*\w+\s*;", " ", _header(), flags=re.S)
+    text = re.sub(r"^[ \t]*#[^\n]*$|extern\s+\"C\"\s*\{", " ", text, flags=re.M)
+    protos = re.findall(r"([\w\s\*]+?)\b(lz4hip_\w+)\s*\(([^()]*)\)\s*;", text)
+    bound = {name: (restype, argtypes) for name, restype, argtypes in _lib.SYMBOLS}
+    assert len(protos) >= 86 and {name for _, name, _ in protos} == set(bound)
+    for ret, name, args in protos:
+        args = [] if args.strip() == "void" else [re.fullmatch(r"(.*?[\s\*])\w+", a.strip(), re.S).group(1) for a in args.split(",")]
+        restype, argtypes = bound[name]
+        assert _ctypes_class(restype) == _c_class(ret), name
+        assert [_ctypes_class(t) for t in argtypes] == [_c_class(a) for a in args], name
+
+
 def test_host_logic_without_gpu():
     from lz4net_amd import LZ4Codec, _lib
     from lz4net_amd.codec import ArgumentException, ArgumentNullException
