@@ -1,15 +1,41 @@
 """TEST INFRASTRUCTURE: the two emulator libraries of tests/simt/build_emu.py, each built and loaded once for every test file, the
-ctypes aliases the tests type their entry points with, and the twins of the records every framing run record shares
-(tests/simt/emu_framing.hpp: EmuCounters, EmuHostRun)."""
+ctypes aliases the tests type their entry points with, the twins of the records every framing run record shares
+(tests/simt/emu_framing.hpp: EmuCounters, EmuHostRun), and what every emulator test file shares: the argument error, the forced grids
+and the guarded buffer."""
 import ctypes as C
 import functools
 import os
 import sys
 
+import numpy as np
+
+from lz4net_amd._lib import E_ARGUMENT  # noqa: F401  (the tests take it from here)
+
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "simt"))
 from build_emu import build, build_framing  # noqa: E402
 
 P, I64, I32, U32 = C.c_void_p, C.c_int64, C.c_int32, C.c_uint32
+GRIDS = (0, 1, 3)                               # the library's own grids, and grids forced to 1 and 3 workgroups
+GUARD = 0x5A
+
+
+def u8(b):
+    return np.frombuffer(bytes(b), np.uint8).copy()
+
+
+class Guarded:
+    """`nbytes` bytes at a multiple of 256 between guard bytes"""
+
+    def __init__(self, nbytes, fill=GUARD):
+        self.n = max(int(nbytes), 0)
+        self.store = np.full(self.n + 768, GUARD, np.uint8)
+        self.lead = (-self.store.ctypes.data) % 256 + 256
+        self.a = self.store[self.lead:self.lead + self.n]
+        self.a[:] = fill
+        self.ptr = self.store.ctypes.data + self.lead
+
+    def intact(self):
+        return bool((self.store[:self.lead] == GUARD).all() and (self.store[self.lead + self.n:] == GUARD).all())
 
 
 class EmuCounters(C.Structure):

@@ -1,5 +1,6 @@
-"""numpy front-end over the HOST-pointer batch entry points of liblz4hip.so, used by the -m gpu tests.
-Everything goes through the C ABI (include/lz4hip.h)."""
+"""What the -m gpu tests share: a numpy front-end over the HOST-pointer batch entry points of liblz4hip.so (everything goes through the
+C ABI, include/lz4hip.h), and device buffers -- bytes up and down, an output between guard bytes, a forced decoder mapping.  torch is
+imported inside the functions, so that the files are collected on a machine without a device."""
 import ctypes as C
 
 import numpy as np
@@ -50,3 +51,62 @@ def decode(comps, out_sizes, known=True, src_lens=None, canary=64, device_mask=N
     else:
         _lib.check(_lib.lib().lz4hip_decode_batch_host_multi(C.byref(b), 1 if known else 0, device_mask))
     return res, dst
+
+
+# ---- device buffers ------------------------------------------------------------------------------------------------------------------
+GUARD, FILL = 64, 0xA5
+
+
+def dev(b):
+    import torch
+    return torch.from_numpy(np.frombuffer(bytes(b), np.uint8).copy()).cuda()
+
+
+def host(t):
+    return t.cpu().numpy().tobytes()
+
+
+def i64(values):
+    import torch
+    return torch.tensor(list(values), dtype=torch.int64, device="cuda")
+
+
+def synth_bytes(dist, n_bytes, seed):
+    from lz4net_amd import batch
+    rows = batch.synth(dist, seed, 0, (n_bytes + 4095) // 4096, length=4096)
+    return rows.reshape(-1)[:n_bytes]
+
+
+def s0():
+    import torch
+    return torch.cuda.current_stream().cuda_stream
+
+
+def guarded(cap):
+    """cap bytes between GUARD bytes of FILL on either side"""
+    import torch
+    return torch.full((cap + 2 * GUARD,), FILL, dtype=torch.uint8, device="cuda")
+
+
+def intact_from(raw, written, dst_cap):
+    return raw[:GUARD] == bytes([FILL]) * GUARD and raw[GUARD + written:] == bytes([FILL]) * (dst_cap - written + GUARD)
+
+
+class mapping_ran:
+    """with mapping_ran("lane"): the decoder is forced to that mapping, and lz4hip_dispatch_counts proves that it ran and the other did not"""
+
+    def __init__(self, mapping):
+        self.mapping = mapping
+        self.knobs = _lib.tuning(decoder="wave") if mapping == "wave" else _lib.tuning(decoder="lane", decoder_groups=1)
+
+    def __enter__(self):
+        self.before = _lib.dispatch_counts()
+        self.knobs.__enter__()
+
+    def __exit__(self, *exc):
+        self.knobs.__exit__(*exc)
+        if exc[0] is None:
+            after = _lib.dispatch_counts()
+            mine, other = (_lib.K_DECODE_WAVE, _lib.K_DECODE_LANE) if self.mapping == "wave" else (_lib.K_DECODE_LANE, _lib.K_DECODE_WAVE)
+            assert after[mine] > self.before[mine] and after[other] == self.before[other], self.mapping
+        return False

@@ -7,10 +7,9 @@ import functools
 import numpy as np
 
 import emu_lib
-from emu_lib import EmuHostRun
+from emu_lib import E_ARGUMENT, GUARD, EmuHostRun  # noqa: F401  (E_ARGUMENT: the tests take it from here)
 from lz4net_amd._lib import Batch, SizesInfo
 
-E_ARGUMENT = -2000000002
 FUZZ_SEED, FUZZ_BLOCKS = 20261017, 20480
 
 
@@ -187,9 +186,6 @@ def emu():
 
 def _p(a):
     return None if a is None else a.ctypes.data
-
-
-GUARD = 0x5A
 
 
 class Outputs:

@@ -7,21 +7,13 @@ import numpy as np
 import pytest
 
 import ref_records as rr
+from gpu_helpers import dev, host
 from lz4net_amd import _lib, legacy_frame as lf
 
 pytestmark = pytest.mark.gpu
 
 FRAMES = rr.load()["frames"]
 MAGIC = lf.MAGIC.to_bytes(4, "little")
-
-
-def dev(b):
-    import torch
-    return torch.from_numpy(np.frombuffer(bytes(b), np.uint8).copy()).cuda()
-
-
-def host(t):
-    return t.cpu().numpy().tobytes()
 
 
 @pytest.mark.parametrize("hc", [False, True])

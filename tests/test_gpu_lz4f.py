@@ -12,35 +12,15 @@ import numpy as np
 import pytest
 
 import lz4f_ref as ref
+from gpu_helpers import dev, host
+from lz4f_cases import LENGTHS, emu_encode, flip, mixed, sample
 from lz4net_amd import _lib, batch, lz4_frame as lz
 from lz4net_amd.codec import ArgumentException
 
 pytestmark = pytest.mark.gpu
 
-LENGTHS = (0, 1, 3, 4, 5, 15, 16, 17, 31, 32, 33, 63, 64, 65, 127, 128, 129, 1023, 1024, 1025)
 with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "lz4f_frames.json")) as _f:
     FRAMES = json.load(_f)["frames"]
-
-
-def dev(b):
-    import torch
-    return torch.from_numpy(np.frombuffer(bytes(b), np.uint8).copy()).cuda()
-
-
-def host(t):
-    return t.cpu().numpy().tobytes()
-
-
-def sample(oracle, dist, n):
-    if dist == 0:
-        return bytes(n)
-    if dist == 1:
-        return np.random.default_rng(n).integers(0, 256, n, dtype=np.uint8).tobytes()
-    return oracle.gen(dist, 5, 0, (n + 65535) // 65536 or 1).reshape(-1)[:n].tobytes()
-
-
-def mixed(oracle, block=65536):
-    return sample(oracle, 1, block) + sample(oracle, 2, block) + sample(oracle, 0, block) + sample(oracle, 3, block) + sample(oracle, 1, 5)
 
 
 def hashes(rows, lead=0, seed=0):
@@ -123,7 +103,6 @@ def test_round_trips_source_lengths(oracle, n):
 
 @pytest.mark.parametrize("block_size", [65536, 262144, 1048576, 4194304])
 def test_block_sizes_mixed_blocks_and_the_emulator_path_s_bytes(oracle, block_size):
-    from test_simt_lz4f import emu_encode
     src = mixed(oracle)
     hc = block_size == 262144
     frame = host(lz.compress_frame_device(dev(src), block_size=block_size, high_compression=hc, block_checksum=True, content_checksum=True))
@@ -158,12 +137,6 @@ def check_against_twin(oracle, frame, **kw):
     assert got == want, {f: (got[f], want[f]) for f in got if got[f] != want[f]}
     assert raw[:len(out)] == out and raw[len(out):] == b"\xA7" * (len(raw) - len(out))
     return want
-
-
-def flip(frame, at, x=0x01):
-    b = bytearray(frame)
-    b[at] ^= x
-    return bytes(b)
 
 
 def test_every_outcome_once(oracle):

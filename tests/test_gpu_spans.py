@@ -9,67 +9,14 @@ import functools
 import numpy as np
 import pytest
 
-from lz4net_amd import _lib, batch, stream as st, wrap
+from gpu_helpers import FILL, GUARD, dev, guarded, host, i64, intact_from, mapping_ran, s0, synth_bytes
+from lz4net_amd import _lib, stream as st, wrap
 from lz4net_amd.codec import ArgumentException
 
 pytestmark = pytest.mark.gpu
 
-GUARD, FILL = 64, 0xA5
 SPARE = 37
 CORRUPT = [0x0F, 0xFF, 0xFF]                                             # no literal, a match 65 535 bytes back: before the output
-
-
-def host(t):
-    return t.cpu().numpy().tobytes()
-
-
-def dev(b):
-    import torch
-    return torch.from_numpy(np.frombuffer(bytes(b), np.uint8).copy()).cuda()
-
-
-def i64(values):
-    import torch
-    return torch.tensor(list(values), dtype=torch.int64, device="cuda")
-
-
-def synth_bytes(dist, n_bytes, seed):
-    rows = batch.synth(dist, seed, 0, (n_bytes + 4095) // 4096, length=4096)
-    return rows.reshape(-1)[:n_bytes]
-
-
-def s0():
-    import torch
-    return torch.cuda.current_stream().cuda_stream
-
-
-def guarded(cap):
-    import torch
-    return torch.full((cap + 2 * GUARD,), FILL, dtype=torch.uint8, device="cuda")
-
-
-def intact_from(raw, written, dst_cap):
-    return raw[:GUARD] == bytes([FILL]) * GUARD and raw[GUARD + written:] == bytes([FILL]) * (dst_cap - written + GUARD)
-
-
-class mapping_ran:
-    """with mapping_ran("lane"): the decoder is forced to that mapping, and lz4hip_dispatch_counts proves that it ran and the other did not"""
-
-    def __init__(self, mapping):
-        self.mapping = mapping
-        self.knobs = _lib.tuning(decoder="wave") if mapping == "wave" else _lib.tuning(decoder="lane", decoder_groups=1)
-
-    def __enter__(self):
-        self.before = _lib.dispatch_counts()
-        self.knobs.__enter__()
-
-    def __exit__(self, *exc):
-        self.knobs.__exit__(*exc)
-        if exc[0] is None:
-            after = _lib.dispatch_counts()
-            mine, other = (_lib.K_DECODE_WAVE, _lib.K_DECODE_LANE) if self.mapping == "wave" else (_lib.K_DECODE_LANE, _lib.K_DECODE_WAVE)
-            assert after[mine] > self.before[mine] and after[other] == self.before[other], self.mapping
-        return False
 
 
 def mixed_source(sizes, seed):

@@ -12,8 +12,8 @@ import pytest
 
 import lz4f_lib
 import lz4f_ref as ref
+from lz4f_cases import check_decode, emu_encode, mixed, sample
 from lz4net_amd import lz4_frame
-from test_simt_lz4f import check_decode, emu_encode, mixed, sample
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "lz4f_frames.json")
 with open(GOLDEN) as _f:

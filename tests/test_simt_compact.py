@@ -10,16 +10,12 @@ import numpy as np
 import pytest
 
 import emu_lib
-import test_simt_frame as tf
-from emu_lib import I32 as _I32, I64 as _I64, P as _P
+import frame_cases as fc
+from block_cases import SMALL, BlockCase, check_sentinels, expect_info, lengths_of, rounds_of, sentinels
+from emu_lib import E_ARGUMENT, GRIDS, Guarded, I32 as _I32, I64 as _I64, P as _P, u8
 from lz4net_amd._lib import Batch, CompactInfo, FrameInfo
 
-E_ARGUMENT = -2000000002
-GRIDS = (0, 1, 3)
-GUARD = 0x5A
-SMALL = (0, 1, 12, 13, 64)
 SLOT = 70000                                    # the decoded size of the longest block: the slot width of most cases
-Guarded = tf.Guarded
 
 
 class CompactEmuRun(C.Structure):
@@ -33,7 +29,7 @@ def emu():
     L = emu_lib.framing()
     L.emu_compact_sizeof.restype = _I64
     assert L.emu_compact_sizeof(0) == L.emu_compact_sizeof(3) == C.sizeof(CompactInfo) and L.emu_compact_sizeof(1) == C.sizeof(CompactEmuRun)
-    assert L.emu_compact_sizeof(2) == C.sizeof(Batch) and L.emu_compact_sizeof(4) == C.sizeof(tf.FrameTables) and L.emu_compact_sizeof(5) == C.sizeof(FrameInfo)
+    assert L.emu_compact_sizeof(2) == C.sizeof(Batch) and L.emu_compact_sizeof(4) == C.sizeof(fc.FrameTables) and L.emu_compact_sizeof(5) == C.sizeof(FrameInfo)
     L.emu_compact_scratch_bytes.argtypes, L.emu_compact_scratch_bytes.restype = [_I64, _I32, _I64], _I64
     L.emu_frame_compact_scratch_bytes.argtypes, L.emu_frame_compact_scratch_bytes.restype = [_I32, _I64, _I64], _I64
     L.emu_frame_compact_tables.argtypes, L.emu_frame_compact_tables.restype = [_P, _I32, _I64, _I64, _P], None
@@ -76,65 +72,23 @@ def decoded(key, which, limit):
     return int(r), out[:max(r, 0)].copy()
 
 
-def lengths_of(n):
-    """mixed decoded lengths: mostly the short ones, the long ones at the ends and around the round boundaries, ONE block of 70 000"""
-    lens = [SMALL[(i * 7 + i // 5) % len(SMALL)] for i in range(n)]
-    for i, length in ((0, 65536), (n - 1, 4096), (2, 70000), (63, 4096), (64, 65536), (255, 4096), (256, 4096), (999, 65536), (1000, 4096),
-                      (4095, 4096), (4096, 65536)):
-        if 0 <= i < n and (length != 70000 or n > 2):
-            lens[i] = length
-    if n == 1:
-        lens[0] = 70000
-    return lens
-
-
-class Case:
+class Case(BlockCase):
     """n blocks in one of the two source layouts.  bad: indices that hold a block the decoder fails on; neg: indices whose length is
     handed over negative; slot: dst_cap_all"""
 
     def __init__(self, n, layout, lens=None, bad=(), neg=(), slot=SLOT, pick=None):
-        self.n, self.slot = n, slot
+        self.slot = slot
         lens = lengths_of(n) if lens is None else list(lens)
         self.keys = [(length, (i if pick is None else pick) % len(pool()[length])) for i, length in enumerate(lens)]
         for j, i in enumerate(sorted(bad)):
             self.keys[i] = ("bad", j % 3)
         self.comp = [pool()[key][which] for key, which in self.keys]
         self.neg = set(neg)
-        self.src_len = np.array([-(c.size + 1) if i in self.neg else c.size for i, c in enumerate(self.comp)] + [0], np.int32)
+        src_len = [-(c.size + 1) if i in self.neg else c.size for i, c in enumerate(self.comp)]
+        self.lay_out(self.comp, src_len, layout, src_len_all=0, dst_cap_all=slot)
         self.seen_len = np.maximum(self.src_len, 0)                   # what the decoder must be handed
         self.src_at = np.concatenate(([0], np.cumsum([c.size for c in self.comp], dtype=np.int64))).astype(np.int64)
         self.flat = np.concatenate(self.comp + [np.zeros(1, np.uint8)])
-        longest = max([c.size for c in self.comp] + [1])
-        if layout == "strided":
-            self.stride = longest + 7
-            self.src = np.full(max(n, 1) * self.stride + 16, 0x77, np.uint8)
-            for i, c in enumerate(self.comp):
-                self.src[i * self.stride:i * self.stride + c.size] = c
-            self.src_off = None
-        else:
-            # rows in reverse order with gaps: offsets that do not increase
-            self.stride = 0
-            self.src_off = np.zeros(n + 1, np.int64)
-            at = 3
-            for i in reversed(range(n)):
-                self.src_off[i] = at
-                at += self.comp[i].size + (i % 5)
-            self.src = np.full(at + 16, 0x77, np.uint8)
-            for i, c in enumerate(self.comp):
-                self.src[self.src_off[i]:self.src_off[i] + c.size] = c
-
-    def batch(self, caps=None, result=None, uniform_len=None):
-        b = Batch()
-        b.src, b.src_stride = self.src.ctypes.data, self.stride
-        b.src_off = None if self.src_off is None else self.src_off.ctypes.data
-        b.src_len = None if uniform_len is not None else self.src_len.ctypes.data
-        b.src_len_all = uniform_len if uniform_len is not None else 0
-        b.dst, b.dst_off, b.dst_stride = None, None, 0
-        b.dst_cap = None if caps is None else caps.ctypes.data
-        b.dst_cap_all = self.slot
-        b.result = None if result is None else result.ctypes.data
-        b.n_blocks = self.n
-        return b
 
     def expect(self, caps=None):
         """(results, lengths, offsets, bytes per block, limits) as the contract states them"""
@@ -166,26 +120,15 @@ def info_tuple(i):
     return (i.blocks, i.decoded_bytes, i.written_blocks, i.first_failed, i.error)
 
 
-def expect_info(n, res, offs, dst_cap):
-    bad = [i for i in range(n) if res[i] < 0]
-    written = max(w for w in range(n + 1) if offs[w] <= dst_cap)
-    return (n, int(offs[n]), written, bad[0] if bad else -1, int(res[bad[0]]) if bad else 0)
-
-
-def rounds_of(n, k):
-    k = n if k <= 0 or k > n else k
-    return (0, 0) if n == 0 else ((n + k - 1) // k, k)
-
-
 def check_outputs(case, caps, dst, dst_cap, dst_off, dlen, result, info, want_result, want_len):
     n = case.n
     res_want, len_want, off_want, outs, _ = case.expect(caps)
     total = int(off_want[n])
-    assert dst_off[0] == -77 and dst_off[n + 2] == -77 and dlen[0] == -77 and dlen[n + 1] == -77 and result[0] == -77 and result[n + 1] == -77
+    check_sentinels(n, dst_off, dlen, result)
     assert (dst_off[1:n + 2] == off_want).all(), "the offsets are complete whatever dst_cap is"
     assert not want_len or (dlen[1:n + 1] == len_want).all()
     assert not want_result or (result[1:n + 1] == res_want).all()
-    want = expect_info(n, res_want, off_want, dst_cap)
+    want = expect_info(n, res_want, off_want, dst_cap, failed=lambda r: r < 0)
     assert info_tuple(info) == want
     w = want[2]
     plain = np.concatenate([outs[i] for i in range(w)] + [np.zeros(0, np.uint8)])
@@ -202,10 +145,7 @@ def run(case, k=0, grid=0, dst_cap=None, caps=None, want_result=True, want_len=T
     dst_cap = total if dst_cap is None else dst_cap
     dst = Guarded(dst_cap, fill=0xA7)
     scratch = Guarded(emu().emu_compact_scratch_bytes(n, case.slot, k) - scratch_short)
-    dst_off = np.full(n + 3, -77, np.int64)
-    dlen = np.full(n + 2, -77, np.int32)
-    result = np.full(n + 2, -77, np.int32)
-    info = CompactInfo(-7, -7, -7, -7, -7, -7)
+    dst_off, dlen, result, info = sentinels(n, CompactInfo)
     b = case.batch(caps, result[1:] if want_result else None)
     r = case.run_record(grid, caps)
     rc = emu().emu_decode_compact(C.addressof(b), k, dst.ptr, dst_cap, dst_off.ctypes.data + 8, dlen.ctypes.data + 4 if want_len else None,
@@ -422,10 +362,7 @@ def run_host(case, k=0, grid=0, dst_cap=None, caps=None, want_result=True, want_
     total = int(case.expect(caps)[2][n])
     dst_cap = total if dst_cap is None else dst_cap
     dst = Guarded(dst_cap, fill=0xA7)
-    dst_off = np.full(n + 3, -77, np.int64)
-    dlen = np.full(n + 2, -77, np.int32)
-    result = np.full(n + 2, -77, np.int32)
-    info = CompactInfo(-7, -7, -7, -7, -7, -7)
+    dst_off, dlen, result, info = sentinels(n, CompactInfo)
     b = case.batch(caps, result[1:] if want_result else None)
     r = case.run_record(grid, caps)
     rc = emu().emu_decode_compact_host(C.addressof(b), k, dst.ptr, dst_cap, dst_off.ctypes.data + 8, dlen.ctypes.data + 4 if want_len else None,
@@ -479,16 +416,16 @@ def test_host_call_image_is_not_sized_by_a_generous_dst_cap():
 
 
 # ---- the legacy frame in one call ---------------------------------------------------------------------------------------------------------
-TABLE_FULL, CORRUPT_BLOCK = tf.TABLE_FULL, tf.CORRUPT_BLOCK
+TABLE_FULL, CORRUPT_BLOCK = fc.TABLE_FULL, fc.CORRUPT_BLOCK
 
 
 def run_frame(oracle, frame, chunk, max_chunks=None, k=0, grid=0, dst_cap=None):
-    """frame_decode_compact under the emulator against the reference's reader (tf.reader: the size field walk, then
+    """frame_decode_compact under the emulator against the reference's reader (frame_cases.reader: the size field walk, then
     LZ4_uncompress_unknownOutputSize(in, out, size, chunk) per chunk) -> (info, dst)"""
-    chunks, rets, outs, offs, want = tf.reader(oracle, frame, chunk)
+    chunks, rets, outs, offs, want = fc.reader(oracle, frame, chunk)
     m = len(chunks) + 3 if max_chunks is None else max_chunks
     rows = min(len(chunks), m)
-    a = tf.u8(frame)
+    a = u8(frame)
     src = np.concatenate([a, np.full(64, 0xEE, np.uint8)])
     results = np.zeros(m + 1, np.int32)
     results[:rows] = rets[:rows]
@@ -514,10 +451,10 @@ def run_frame(oracle, frame, chunk, max_chunks=None, k=0, grid=0, dst_cap=None):
     assert dst.intact() and scratch.intact() and r.shape_errors == 0 and r.passes == 1
     assert (r.calls, r.max_rows) == rounds_of(m, k), "the decode runs over all max_chunks rows"
     if len(chunks) > m:
-        assert tf.info_tuple(info) == (len(chunks), total, total if all(x >= 0 for x in rets[:m]) else tf.info_tuple(info)[2], chunks[m][0] - 4, TABLE_FULL)
+        assert fc.info_tuple(info) == (len(chunks), total, total if all(x >= 0 for x in rets[:m]) else fc.info_tuple(info)[2], chunks[m][0] - 4, TABLE_FULL)
         return info, dst
-    assert tf.info_tuple(info) == want
-    t = tf.FrameTables()
+    assert fc.info_tuple(info) == want
+    t = fc.FrameTables()
     emu().emu_frame_compact_tables(scratch.ptr, chunk, m, k, C.addressof(t))
     dst_off = np.ctypeslib.as_array(C.cast(t.dst_off, C.POINTER(C.c_int64)), shape=(m + 1,))
     assert (dst_off == at).all() and (dst_off[:rows + 1] == offs[:rows + 1]).all()
@@ -531,41 +468,41 @@ def run_frame(oracle, frame, chunk, max_chunks=None, k=0, grid=0, dst_cap=None):
 @pytest.mark.parametrize("grid", GRIDS)
 def test_frames_equal_the_reference_reader(oracle, grid):
     for chunk, n in ((4096, 0), (4096, 4095), (4096, 3 * 4096 - 9), (17, 200 * 17 - 5), (65536, 65537)):
-        frame = tf.make_frame(oracle, tf.sample(oracle, n), chunk)
-        assert len(tf.walk(frame, chunk)[0]) == (n + chunk - 1) // chunk
+        frame = fc.make_frame(oracle, fc.sample(oracle, n), chunk)
+        assert len(fc.walk(frame, chunk)[0]) == (n + chunk - 1) // chunk
         for k in sorted({0, 1, 2, 7} if n < 3000 or chunk > 17 else {0, 7, 64, 199, 200}):
             info, dst = run_frame(oracle, frame, chunk, k=k, grid=grid)
-            assert info.error == tf.OK and bytes(dst.a) == bytes(tf.sample(oracle, n))
+            assert info.error == fc.OK and bytes(dst.a) == bytes(fc.sample(oracle, n))
 
 
 @pytest.mark.parametrize("grid", GRIDS)
 def test_frame_header_cases(oracle, grid):
     chunk = 4096
-    frame = tf.make_frame(oracle, tf.sample(oracle, 3 * chunk + 7), chunk)
+    frame = fc.make_frame(oracle, fc.sample(oracle, 3 * chunk + 7), chunk)
     for k in (0, 2):
-        for f, err in ((frame + frame, tf.OK), (tf.MAGIC + frame, tf.OK), (frame + tf.MAGIC, tf.OK),                 # appended frames
-                       (frame + b"\x01\x02", tf.TRUNCATED), (frame[:-3], tf.TRUNCATED),                             # a truncated tail
-                       (frame + (tf.bound(chunk) + 1).to_bytes(4, "little") + b"\x00" * 8, tf.BAD_SIZE),             # a bad size field
-                       (b"\x00" + frame[1:], tf.BAD_MAGIC), (b"", tf.BAD_MAGIC), (frame[:4], tf.OK)):
+        for f, err in ((frame + frame, fc.OK), (fc.MAGIC + frame, fc.OK), (frame + fc.MAGIC, fc.OK),                 # appended frames
+                       (frame + b"\x01\x02", fc.TRUNCATED), (frame[:-3], fc.TRUNCATED),                             # a truncated tail
+                       (frame + (fc.bound(chunk) + 1).to_bytes(4, "little") + b"\x00" * 8, fc.BAD_SIZE),             # a bad size field
+                       (b"\x00" + frame[1:], fc.BAD_MAGIC), (b"", fc.BAD_MAGIC), (frame[:4], fc.OK)):
             info, dst = run_frame(oracle, f, chunk, k=k, grid=grid)
             assert info.error == err, (f[:8], err)
         # dst_cap: nothing at or past it is written, the record is complete
         total = 3 * chunk + 7
         for dst_cap in (0, 1, chunk, chunk + 1, total - 1, total + 100):
             info, dst = run_frame(oracle, frame, chunk, k=k, grid=grid, dst_cap=dst_cap)
-            assert (info.decoded_bytes, info.good_bytes, info.error) == (total, total, tf.OK)
+            assert (info.decoded_bytes, info.good_bytes, info.error) == (total, total, fc.OK)
 
 
 @pytest.mark.parametrize("grid", GRIDS)
 def test_frame_table_too_small(oracle, grid):
     chunk = 4096
-    frame = tf.make_frame(oracle, tf.sample(oracle, 5 * chunk + 7), chunk)
-    chunks = tf.walk(frame, chunk)[0]
+    frame = fc.make_frame(oracle, fc.sample(oracle, 5 * chunk + 7), chunk)
+    chunks = fc.walk(frame, chunk)[0]
     for m in (0, 1, 5):
         info, dst = run_frame(oracle, frame, chunk, max_chunks=m, k=2, grid=grid)
         assert (info.error, info.chunks, info.error_offset) == (TABLE_FULL, 6, chunks[m][0] - 4)
     info, dst = run_frame(oracle, frame, chunk, max_chunks=6, k=2, grid=grid)
-    assert info.error == tf.OK
+    assert info.error == fc.OK
 
 
 @pytest.mark.parametrize("grid", GRIDS)
@@ -573,16 +510,16 @@ def test_frame_corrupt_chunks(oracle, grid):
     """a corrupt chunk first, last and in the middle: it takes 0 bytes, its neighbours pack around it, and the lowest one is the outcome,
     ahead of the header error behind it"""
     chunk = 4096
-    data = tf.sample(oracle, 9 * chunk)
-    a = tf.u8(data)
+    data = fc.sample(oracle, 9 * chunk)
+    a = u8(data)
     comps = [bytes(oracle.compress(a[i * chunk:(i + 1) * chunk])) for i in range(9)]
     for bad in ((0,), (8,), (4,), (0, 4, 8)):
         parts = [b"\xFF\xFF\xFF" + c[3:] if i in bad else c for i, c in enumerate(comps)]
-        frame = tf.MAGIC + b"".join(len(c).to_bytes(4, "little") + c for c in parts) + b"\x01\x02"
+        frame = fc.MAGIC + b"".join(len(c).to_bytes(4, "little") + c for c in parts) + b"\x01\x02"
         for k in (0, 4, 5):
             info, dst = run_frame(oracle, frame, chunk, k=k, grid=grid)
             field = 4 + sum(4 + len(c) for c in parts[:bad[0]])
-            assert tf.info_tuple(info) == (9, (9 - len(bad)) * chunk, bad[0] * chunk, field, CORRUPT_BLOCK)
+            assert fc.info_tuple(info) == (9, (9 - len(bad)) * chunk, bad[0] * chunk, field, CORRUPT_BLOCK)
             assert bytes(dst.a) == b"".join(data[i * chunk:(i + 1) * chunk] for i in range(9) if i not in bad)
 
 
@@ -592,18 +529,18 @@ def test_frame_chunk_that_only_decodes_with_room(oracle, grid):
     decodes at the walked size, fails it; with chunk_size bytes of room -- the reference's reader -- it decodes.  The expected bytes are
     the oracle's at that capacity."""
     chunk = 4096
-    data = tf.sample(oracle, 2 * chunk)
-    a = tf.u8(data)
+    data = fc.sample(oracle, 2 * chunk)
+    a = u8(data)
     odd = bytes([0x10, 0x30, 1, 0, 0x50, 1, 2, 3, 4, 5])
     parts = [bytes(oracle.compress(a[:chunk])), odd, bytes(oracle.compress(a[chunk:]))]
-    frame = tf.MAGIC + b"".join(len(c).to_bytes(4, "little") + c for c in parts)
-    r, out = oracle.uncompress_unknown_raw(tf.u8(odd), len(odd), chunk)
-    assert r == 10 and oracle.uncompress_unknown_raw(tf.u8(odd), len(odd), 10)[0] < 0
-    ix = tf.Index(frame, chunk, 5, grid)
-    assert ix.info.error == tf.OK and ix.decode(oracle)[1].error == CORRUPT_BLOCK, "the two-call path rejects the chunk"
+    frame = fc.MAGIC + b"".join(len(c).to_bytes(4, "little") + c for c in parts)
+    r, out = oracle.uncompress_unknown_raw(u8(odd), len(odd), chunk)
+    assert r == 10 and oracle.uncompress_unknown_raw(u8(odd), len(odd), 10)[0] < 0
+    ix = fc.Index(frame, chunk, 5, grid)
+    assert ix.info.error == fc.OK and ix.decode(oracle)[1].error == CORRUPT_BLOCK, "the two-call path rejects the chunk"
     for k in (0, 2):
         info, dst = run_frame(oracle, frame, chunk, k=k, grid=grid)
-        assert tf.info_tuple(info) == (3, 2 * chunk + 10, 2 * chunk + 10, -1, tf.OK)
+        assert fc.info_tuple(info) == (3, 2 * chunk + 10, 2 * chunk + 10, -1, fc.OK)
         assert bytes(dst.a) == data[:chunk] + bytes(out[:10]) + data[chunk:]
 
 

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import emu_helpers as emu
+from emu_lib import E_ARGUMENT
 from oracle.oracle import compress_bound
 
 SIZES = (0, 1, 12, 13, 14, 64, 65, 300, 4096, 20000, 65535, 65536)
@@ -274,7 +275,7 @@ def test_encode_hc_nat_bit_exact(oracle, kind):
         assert np.array_equal(dst[i, :res[i]], want), (i, a.size)
     # a block > 64 KiB is refused by these kernels (the library launches lz4hip_hc_conv.hpp for such batches)
     res, dst = emu.encode([oracle.gen(2, 3, 0, 2).reshape(-1)[:70000].copy(), blocks[10]], hc=True, groups=1, **{kind: True})
-    assert res[0] == -2000000002 and res[1] == len(oracle.compress(blocks[10], hc=True))
+    assert res[0] == E_ARGUMENT and res[1] == len(oracle.compress(blocks[10], hc=True))
 
 
 @PRECOMPUTED

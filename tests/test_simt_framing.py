@@ -15,19 +15,15 @@ import pytest
 
 import emu_helpers as emu
 from emu_helpers import addr, ref
+from emu_lib import E_ARGUMENT
+from framing_cases import (CORRUPT_BLOCK, EOS, OK, PASSES, TABLE_FULL, TAIL, WRAP_CORRUPT_BLOCK, WRAP_CORRUPT_HEADER, WRAP_OK, header_stream, header_wrap,
+                           mixed, noise, pattern, ref_unwrap, ref_walk)
 from lz4net_amd import stream as st
-from test_stream_device import expected_stream, frame
+from stream_cases import expected_stream, frame
 
-OK, EOS, PASSES, CORRUPT_BLOCK, TABLE_FULL = 0, 1, 2, 3, 4          # LZ4HIP_STREAM_* (include/lz4hip.h)
-WRAP_OK, WRAP_SIZE_INVALID, WRAP_CORRUPT_HEADER, WRAP_CORRUPT_BLOCK = 0, 1, 2, 3
-E_ARGUMENT = -2000000002
 GUARD = 64
 SPAN = 65536                                                            # kCopySpan (checked in test_constants)
 NONE64 = 0xFFFFFFFFFFFFFFFF
-
-
-def pattern(n):
-    return ((np.arange(n, dtype=np.int64) * 131 + 17) & 0xFF).astype(np.uint8)
 
 
 def guarded(size):
@@ -117,23 +113,6 @@ def check_copy(name, case, ends=None, grids=None):
             buf, ptr = guarded(total)
             run(ptr, end, grid)
             same(buf, want, f"{name}: end {end} of {total}, grid {grid}")
-
-
-def header_stream(flags, original, clen=None):
-    return st.write_varint(flags) + st.write_varint(original) + (st.write_varint(clen) if flags & 1 else b"")
-
-
-def header_wrap(original, payload):
-    return struct.pack("<ii", original, payload)
-
-
-RNG = np.random.default_rng(20240607)
-NOISE = RNG.integers(0, 256, 1 << 18, dtype=np.uint8)
-
-
-def noise(n, salt=0):
-    o = (salt * 7919) % (NOISE.size - n - 1) if n < NOISE.size else 0
-    return NOISE[o:o + n].copy() if n <= NOISE.size else np.resize(NOISE, n)
 
 
 # -- RawLayout: (gap before, length, source residue) per segment; gaps, zero lengths, any source alignment
@@ -425,65 +404,6 @@ def test_copy_streams_layout():
 
 
 # ---- the header reader ------------------------------------------------------------------------------------------------------------
-# The reference walk, written to the rules of LZ4Stream.cs: TryReadVarInt sums (b & 0x7F) << count into a ulong (modulo 2^64; the
-# tenth byte's shift is 63, so only its bit 0 survives) and stops at a clear continuation bit or after ten bytes (:167-187);
-# AcquireNextChunk casts the lengths to int and the flags to an int-based enum, and tests (int)flags >> 2 (:274-312).
-MASK64 = (1 << 64) - 1
-
-
-def cs_varint(buf, pos):
-    """-> (value, new pos); value None: clean end of data, "eos": the data ends inside the varint"""
-    result = count = 0
-    while True:
-        if pos >= len(buf):
-            return (None if count == 0 else "eos"), pos
-        b = buf[pos]
-        pos += 1
-        result = (result + ((b & 0x7F) << count)) & MASK64
-        count += 7
-        if (b & 0x80) == 0 or count >= 64:
-            return result, pos
-
-
-def s32(v):
-    v &= 0xFFFFFFFF
-    return v - (1 << 32) if v >= 1 << 31 else v
-
-
-def ref_walk(buf, max_chunks=None):
-    """-> dict: rows [(compressed, header offset, payload offset, payload length, original, output offset)] of the non-empty
-    chunks, status, error_offset, chunks, compressed_chunks, decoded_bytes -- what lz4hip_stream_index_device documents."""
-    buf = bytes(buf)
-    pos, out, rows, status = 0, 0, [], OK
-    while pos < len(buf):
-        flags, p = cs_varint(buf, pos)
-        original, p = cs_varint(buf, p) if flags != "eos" else ("eos", p)
-        bad = flags == "eos" or original in (None, "eos")
-        compressed = (not bad) and (flags & 1) != 0
-        clen = original
-        if compressed:
-            clen, p = cs_varint(buf, p)
-            bad = clen in (None, "eos")
-        if not bad:
-            original, clen = s32(original), s32(clen)
-            bad = clen > original or clen < 0 or p + clen > len(buf)
-        if bad:
-            status = EOS
-            break
-        if compressed and (s32(flags) >> 2) != 0:
-            status = PASSES
-            break
-        if original != 0:
-            rows.append((compressed, pos, p, clen, original, out))
-            out += original
-        pos = p + clen
-    w = dict(rows=rows, status=status, error_offset=pos if status != OK else -1, chunks=len(rows),
-             compressed_chunks=sum(1 for r in rows if r[0]), decoded_bytes=out)
-    if max_chunks is not None and len(rows) > max_chunks:                 # a full table wins over a later header error
-        w.update(status=TABLE_FULL, error_offset=rows[max_chunks][1])
-    return w
-
-
 def host_outcome(buf):
     """stream.parse_chunks as (status, non-empty chunks)"""
     try:
@@ -495,7 +415,6 @@ def host_outcome(buf):
     return OK, [c for c in chunks if c[1] != 0]
 
 
-TAIL = frame([(0, 3, b"abc")] * 12)                                       # behind every buffer: bytes that parse as more chunks
 FILL = -77
 
 
@@ -798,15 +717,6 @@ def pipe_lengths(B):
     return [0, 1, B - 1, B, B + 1, 5 * B + 3]
 
 
-def mixed(oracle, size, salt):
-    """compressible and incompressible stretches"""
-    if size == 0:
-        return np.zeros(0, np.uint8)
-    a = oracle.gen(2, 21 + salt, 3, -(-size // 65536)).reshape(-1)[:size].copy()
-    a[size // 3:size // 2] = noise(size // 2 - size // 3, salt)
-    return a
-
-
 def run_stream_encode(data, B, results, comp, hc, grid_items, grid_copy):
     L = emu.framing()
     n = -(-data.size // B)
@@ -1064,18 +974,6 @@ def test_pipeline_wrap(oracle):
                 assert dst_off.tolist() == want_off and result.tolist() == want_result, what
                 same(buf, ref_copy(bound, [(0, want)], len(want)), what + ", whole")
         lib_wrap(msgs, off, enc, comp, 0, 0, short=1)
-
-
-def ref_unwrap(m):
-    """Unwrap's checks in its order with signed fields -> (status, "raw" / "comp" / None, output size, payload length)"""
-    if len(m) < 8:
-        return WRAP_SIZE_INVALID, None, 0, 0
-    original, payload = struct.unpack("<ii", bytes(m[:8]))
-    if payload < 0 or payload > len(m) - 8:
-        return WRAP_CORRUPT_HEADER, None, 0, 0
-    if payload >= original:
-        return WRAP_OK, "raw", payload, payload
-    return WRAP_OK, "comp", original, payload
 
 
 def lib_unwrap(src, off, src_len, n, results, decoded, total, grid_items, grid_copy):

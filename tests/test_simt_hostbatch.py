@@ -14,9 +14,8 @@ import pytest
 
 import emu_helpers as emu
 from emu_helpers import addr, ref
-from lz4net_amd._lib import Batch
+from lz4net_amd._lib import E_ARGUMENT, E_DEVICE, Batch
 
-E_DEVICE, E_ARGUMENT = -2000000001, -2000000002
 GUARD = 64
 UNTOUCHED = -12345678
 COPY_IN, KERNELS, COPY_OUT, OUT_DONE, WAIT_OUT, QUIESCE = 2, 3, 4, 5, 6, 8          # EmuStage::Kind

@@ -7,64 +7,17 @@ with the library's grids and with grids of 1 and 3; with a capacity that holds e
 pair's from the same emulator, byte for byte.  (stream.decompress_stream and LZ4Codec.Unwrap decode on the device, which this suite does
 without: the good parts are held against the plain bytes the oracle compressed, which is what those two return for them;
 tests/test_gpu_decode_into.py repeats the cases against the host paths.)"""
-import ctypes as C
-import functools
-
 import numpy as np
 import pytest
 
 import emu_helpers as emu
-import emu_lib
-import test_simt_framing as fr
+import framing_cases as fr
 from emu_helpers import addr, ref
-from emu_lib import I32 as _I32, I64 as _I64, P as _P
+from emu_lib import E_ARGUMENT, GRIDS
+from framing_cases import CORRUPT_BLOCK, EOS, OK, PASSES, TABLE_FULL
+from into_cases import FILL, Buf, info_bytes, lib, run_record
 from lz4net_amd._lib import StreamInfo, StreamsInfo, UnwrapInfo
-from test_stream_device import expected_stream, frame
-
-OK, EOS, PASSES, CORRUPT_BLOCK, TABLE_FULL = 0, 1, 2, 3, 4
-E_ARGUMENT = -2000000002
-GRIDS = (0, 1, 3)
-GUARD, FILL = 64, 0xA5
-
-
-class IntoEmuRun(C.Structure):
-    _anonymous_ = ("counters",)
-    _fields_ = [("results", _P), ("bytes", _P), ("src_off", _P), ("dst_off", _P), ("len", _P), ("cap", _P), ("rows", _I64), ("count", _I64),
-                ("grid_items", _I32), ("grid_copy", _I32), ("grid_walk", _I32), ("pad", _I32), ("calls", _I64), ("shape_errors", _I64),
-                ("decoded_rows", _I64), ("counters", emu_lib.EmuCounters)]
-
-
-@functools.lru_cache(maxsize=None)
-def lib():
-    L = emu_lib.framing()
-    L.emu_into_sizeof.restype = _I64
-    assert [L.emu_into_sizeof(i) for i in range(4)] == [C.sizeof(s) for s in (IntoEmuRun, StreamInfo, StreamsInfo, UnwrapInfo)]
-    L.emu_into_scratch_bytes.argtypes, L.emu_into_scratch_bytes.restype = [C.c_int, _I64, _I64], _I64
-    L.emu_stream_decode_into.argtypes = [_P, _I64, _I64, _P, _I64, _P, _I64, _P, _P, _P]
-    L.emu_streams_decode_into.argtypes = [_P, _I64, _P, _I64, _I64, _P, _I64, _P, _I64, _P, _P, _P, _P, _P, _P]
-    L.emu_unwrap_into.argtypes = [_P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _P, _P, _P, _P]
-    return L
-
-
-class Buf:
-    """`size` bytes of `fill` between guard bytes of the same value"""
-
-    def __init__(self, size, fill=FILL):
-        self.whole = np.full(size + 2 * GUARD, fill, np.uint8)
-        self.a, self.ptr, self.size, self.fill = self.whole[GUARD:GUARD + size], addr(self.whole, GUARD), size, fill
-
-    def guards_intact(self):
-        return bool((self.whole[:GUARD] == self.fill).all() and (self.whole[GUARD + self.size:] == self.fill).all())
-
-
-def run_record(results, truth, src_off, dst_off, lens, caps, rows, count, grid):
-    keep = (np.array(list(results) + [0], np.int32), np.ascontiguousarray(np.concatenate([truth, np.zeros(8, np.uint8)])),
-            np.array(list(src_off) + [0], np.int64), np.array(list(dst_off) + [0], np.int64), np.array(list(lens) + [0], np.int32),
-            np.array(list(caps) + [0], np.int32))
-    r = IntoEmuRun(rows=rows, count=count, grid_items=grid, grid_copy=grid, grid_walk=grid)
-    r.results, r.bytes, r.src_off, r.dst_off, r.len, r.cap = (addr(a) for a in keep)
-    return r, keep
-
+from stream_cases import expected_stream, frame
 
 def cap_values(ends, total):
     """0, 1, the start and the end of each given chunk (item, message), total - 1, total, total + 4096"""
@@ -72,10 +25,6 @@ def cap_values(ends, total):
     for start, end in ends:
         caps |= {start, end}
     return sorted(caps)
-
-
-def info_bytes(info):
-    return bytes(memoryview(info))
 
 
 # ---- one stream ------------------------------------------------------------------------------------------------------------------

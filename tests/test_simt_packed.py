@@ -10,13 +10,10 @@ import numpy as np
 import pytest
 
 import emu_lib
-from emu_lib import I32 as _I32, I64 as _I64, P as _P
+from block_cases import SMALL, BlockCase, check_sentinels, expect_info, lengths_of, rounds_of, sentinels
+from emu_lib import E_ARGUMENT, GRIDS, Guarded, I32 as _I32, I64 as _I64, P as _P
 from lz4net_amd._lib import Batch, PackedInfo
 
-E_ARGUMENT = -2000000002
-GRIDS = (0, 1, 3)
-GUARD = 0x5A
-SMALL = (0, 1, 12, 13, 64)
 SLOT = 70000 + 70000 // 255 + 16                # compressBound of the longest block
 
 
@@ -37,21 +34,6 @@ def emu():
     L.emu_encode_packed.argtypes = [_P, C.c_int, _I64, _P, _I64, _P, _P, _P, _I64, _P, _P]
     L.emu_encode_packed_host.argtypes = [_P, C.c_int, _I64, _P, _I64, _P, _P, _P, _I64, _P]
     return L
-
-
-class Guarded:
-    """`nbytes` bytes at a multiple of 256 between guard bytes"""
-
-    def __init__(self, nbytes, fill=GUARD):
-        self.n = max(int(nbytes), 0)
-        self.store = np.full(self.n + 768, GUARD, np.uint8)
-        self.lead = (-self.store.ctypes.data) % 256 + 256
-        self.a = self.store[self.lead:self.lead + self.n]
-        self.a[:] = fill
-        self.ptr = self.store.ctypes.data + self.lead
-
-    def intact(self):
-        return bool((self.store[:self.lead] == GUARD).all() and (self.store[self.lead + self.n:] == GUARD).all())
 
 
 # ---- the blocks and what the reference's encoders write for them ------------------------------------------------------------------
@@ -75,23 +57,11 @@ def pool():
     return out
 
 
-def lengths_of(n):
-    """mixed lengths: mostly the short ones, the long ones at the ends and around the round boundaries, ONE block of 70 000"""
-    lens = [SMALL[(i * 7 + i // 5) % len(SMALL)] for i in range(n)]
-    for i, length in ((0, 65536), (n - 1, 4096), (2, 70000), (63, 4096), (64, 65536), (255, 4096), (256, 4096), (999, 65536), (1000, 4096),
-                      (4095, 4096), (4096, 65536)):
-        if 0 <= i < n and (length != 70000 or n > 2):
-            lens[i] = length
-    if n == 1:
-        lens[0] = 70000
-    return lens
-
-
-class Case:
+class Case(BlockCase):
     """n blocks in one of the two source layouts, and the stand-in's tables for them"""
 
     def __init__(self, n, layout, hc=False, lens=None):
-        self.n, self.hc = n, hc
+        self.hc = hc
         self.lens = lengths_of(n) if lens is None else list(lens)
         picks = [pool()[abs(length)][i % len(pool()[abs(length)])] for i, length in enumerate(self.lens)]
         self.raw = [p[0] for p in picks]
@@ -101,39 +71,8 @@ class Case:
         self.bytes = np.concatenate(self.enc + [np.zeros(1, np.uint8)])
         self.src_at = np.concatenate(([0], np.cumsum([r.size for r in self.raw], dtype=np.int64))).astype(np.int64)
         self.flat = np.concatenate(self.raw + [np.zeros(1, np.uint8)])
-        self.src_len = np.array(self.lens + [0], np.int32)
+        self.lay_out(self.raw, self.lens, layout, src_len_all=70000, dst_cap_all=SLOT)
         self.bad_len = (self.src_len < 0).astype(np.uint8)      # the stand-in must see an empty block there, never the negative length
-        longest = max([abs(x) for x in self.lens] + [1])
-        if layout == "strided":
-            self.stride = longest + 7
-            self.src = np.full(max(n, 1) * self.stride + 16, 0x77, np.uint8)
-            for i, r in enumerate(self.raw):
-                self.src[i * self.stride:i * self.stride + r.size] = r
-            self.src_off = None
-        else:
-            # rows in reverse order with gaps: offsets that do not increase
-            self.stride = 0
-            self.src_off = np.zeros(n + 1, np.int64)
-            at = 3
-            for i in reversed(range(n)):
-                self.src_off[i] = at
-                at += self.raw[i].size + (i % 5)
-            self.src = np.full(at + 16, 0x77, np.uint8)
-            for i, r in enumerate(self.raw):
-                self.src[self.src_off[i]:self.src_off[i] + r.size] = r
-
-    def batch(self, caps=None, result=None, uniform_len=None):
-        b = Batch()
-        b.src, b.src_stride = self.src.ctypes.data, self.stride
-        b.src_off = None if self.src_off is None else self.src_off.ctypes.data
-        b.src_len = None if uniform_len is not None else self.src_len.ctypes.data
-        b.src_len_all = uniform_len if uniform_len is not None else 70000
-        b.dst, b.dst_off, b.dst_stride = None, None, 0
-        b.dst_cap = None if caps is None else caps.ctypes.data
-        b.dst_cap_all = SLOT
-        b.result = None if result is None else result.ctypes.data
-        b.n_blocks = self.n
-        return b
 
     def expect(self, caps=None):
         """(results, lengths, offsets) as the contract states them"""
@@ -158,17 +97,6 @@ def info_tuple(i):
     return (i.blocks, i.packed_bytes, i.written_blocks, i.first_failed, i.error)
 
 
-def expect_info(n, res, offs, dst_cap):
-    bad = [i for i in range(n) if res[i] <= 0]
-    written = max(w for w in range(n + 1) if offs[w] <= dst_cap)
-    return (n, int(offs[n]), written, bad[0] if bad else -1, int(res[bad[0]]) if bad else 0)
-
-
-def rounds_of(n, k):
-    k = n if k <= 0 or k > n else k
-    return (0, 0) if n == 0 else ((n + k - 1) // k, k)
-
-
 def run(case, k=0, grid=0, dst_cap=None, caps=None, want_result=True, want_len=True, scratch_short=0):
     """encode_packed under the emulator -> (rc, dst, info, run record); checks everything the contract promises on the way"""
     n = case.n
@@ -177,16 +105,13 @@ def run(case, k=0, grid=0, dst_cap=None, caps=None, want_result=True, want_len=T
     dst_cap = total if dst_cap is None else dst_cap
     dst = Guarded(dst_cap, fill=0xA7)
     scratch = Guarded(emu().emu_packed_scratch_bytes(n, SLOT, k) - scratch_short)
-    dst_off = np.full(n + 3, -77, np.int64)
-    plen = np.full(n + 2, -77, np.int32)
-    result = np.full(n + 2, -77, np.int32)
-    info = PackedInfo(-7, -7, -7, -7, -7, -7)
+    dst_off, plen, result, info = sentinels(n, PackedInfo)
     b = case.batch(caps, result[1:] if want_result else None)
     r = case.run_record(grid)
     rc = emu().emu_encode_packed(C.addressof(b), int(case.hc), k, dst.ptr, dst_cap, dst_off.ctypes.data + 8, plen.ctypes.data + 4 if want_len else None,
                                  scratch.ptr, scratch.n, C.addressof(info), C.addressof(r))
     assert dst.intact() and scratch.intact(), "a byte outside dst (at or past dst_cap) or outside the scratch was written"
-    assert dst_off[0] == -77 and dst_off[n + 2] == -77 and plen[0] == -77 and plen[n + 1] == -77 and result[0] == -77 and result[n + 1] == -77
+    check_sentinels(n, dst_off, plen, result)
     if rc != 0:
         return rc, dst, info, r
     assert r.shape_errors == 0, "the encoder was handed a row or a descriptor that is not the batch's"
@@ -196,7 +121,7 @@ def run(case, k=0, grid=0, dst_cap=None, caps=None, want_result=True, want_len=T
         assert (plen[1:n + 1] == len_want).all()
     if want_result:
         assert (result[1:n + 1] == res_want).all()
-    want = expect_info(n, res_want, off_want, dst_cap)
+    want = expect_info(n, res_want, off_want, dst_cap, failed=lambda r: r <= 0)
     assert info_tuple(info) == want
     w = want[2]
     packed = np.concatenate([case.enc[i][:len_want[i]] for i in range(w)] + [np.zeros(0, np.uint8)])
@@ -379,21 +304,18 @@ def run_host(case, k=0, grid=0, dst_cap=None, caps=None, want_result=True, want_
     total = int(off_want[n])
     dst_cap = total if dst_cap is None else dst_cap
     dst = Guarded(dst_cap, fill=0xA7)
-    dst_off = np.full(n + 3, -77, np.int64)
-    plen = np.full(n + 2, -77, np.int32)
-    result = np.full(n + 2, -77, np.int32)
-    info = PackedInfo(-7, -7, -7, -7, -7, -7)
+    dst_off, plen, result, info = sentinels(n, PackedInfo)
     b = case.batch(caps, result[1:] if want_result else None)
     r = case.run_record(grid)
     rc = emu().emu_encode_packed_host(C.addressof(b), int(case.hc), k, dst.ptr, dst_cap, dst_off.ctypes.data + 8, plen.ctypes.data + 4 if want_len else None,
                                       C.addressof(info), pool_floor, C.addressof(r))
     assert rc == 0, r.error
     assert dst.intact() and r.intact == 1 and r.shape_errors == 0
-    assert dst_off[0] == -77 and dst_off[n + 2] == -77 and plen[0] == -77 and plen[n + 1] == -77 and result[0] == -77 and result[n + 1] == -77
+    check_sentinels(n, dst_off, plen, result)
     assert (dst_off[1:n + 2] == off_want).all()
     assert not want_len or (plen[1:n + 1] == len_want).all()
     assert not want_result or (result[1:n + 1] == res_want).all()
-    want = expect_info(n, res_want, off_want, dst_cap)
+    want = expect_info(n, res_want, off_want, dst_cap, failed=lambda r: r <= 0)
     assert info_tuple(info) == want
     w = want[2]
     packed = np.concatenate([case.enc[i][:len_want[i]] for i in range(w)] + [np.zeros(0, np.uint8)])

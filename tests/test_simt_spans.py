@@ -11,17 +11,16 @@ import functools
 import numpy as np
 
 import emu_helpers as emu
-import test_simt_framing as fr
-import test_simt_into as into
+import framing_cases as fr
+import into_cases as into
 from emu_helpers import addr, ref
-from emu_lib import I64 as _I64, P as _P
+from emu_lib import E_ARGUMENT, GRIDS, I64 as _I64, P as _P
+from framing_cases import CORRUPT_BLOCK, EOS, OK, PASSES, TABLE_FULL
+from into_cases import FILL, Buf, info_bytes, run_record
 from lz4net_amd import stream as st
 from lz4net_amd._lib import StreamInfo, StreamsInfo, UnwrapInfo
-from test_simt_into import FILL, GRIDS, Buf, info_bytes, run_record
-from test_stream_device import expected_stream, frame
+from stream_cases import expected_stream, frame
 
-OK, EOS, PASSES, CORRUPT_BLOCK, TABLE_FULL = 0, 1, 2, 3, 4
-E_ARGUMENT = -2000000002
 
 
 @functools.lru_cache(maxsize=None)

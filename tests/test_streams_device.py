@@ -14,7 +14,7 @@ from lz4net_amd import stream as st
 from lz4net_amd.codec import ArgumentException
 
 from conftest import ForcedMapping
-from test_stream_device import BLOCKS, KINDS, _bad_block, _nonminimal, _offsets, data_of, expected_stream, frame, wide_flags_streams
+from stream_cases import BLOCKS, KINDS, _bad_block, _nonminimal, _offsets, data_of, expected_stream, frame, wide_flags_streams
 
 
 def _varint_len(v):
