@@ -121,6 +121,37 @@ namespace LZ4hip
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
         private static extern unsafe int lz4hip_frame_decode_host(byte* src, long srcLen, int chunkSize, byte* dst, long dstCap, FrameInfo* info);
 
+        // Many LZ4 frames (magic 0x184D2204) per call (include/lz4hip.h, "batches of LZ4 frames"): one buffer plus offsets[n + 1], one
+        // frame per item.  (Declarations only: not compiled or run by this repository's tests, tests/test_gpu_lz4f_batch.py calls the
+        // same symbols through ctypes.)
+        // struct lz4hip_lz4f_info and struct lz4hip_lz4f_batch_info, field for field
+        [StructLayout(LayoutKind.Sequential)]
+        public struct Lz4fInfo
+        {
+            public long blocks, decoded_bytes, good_bytes, error_offset, content_size, frame_bytes;
+            public int error, kind, block_max, flg, bd, checks;
+        }
+
+        [StructLayout(LayoutKind.Sequential)]
+        public struct Lz4fBatchInfo
+        {
+            public long items, blocks, decoded_bytes, first_error, error_offset;
+            public int error, reserved;
+        }
+
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        private static extern long lz4hip_lz4f_batch_bound(long n, long srcLen, int blockSizeId, uint flags);
+
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        private static extern unsafe int lz4hip_lz4f_batch_encode_host(byte* src, long srcLen, long* srcOff, long n, int blockSizeId, int mode, uint flags,
+                                                                       byte* dst, long dstCap, long* dstOff);
+
+        // returns 0, the first failing item's LZ4HIP_LZ4F_* code, or LZ4HIP_E_*; dstCap = 0 is a size query: LZ4HIP_E_ARGUMENT with dstOff,
+        // itemInfo and *info filled in
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        private static extern unsafe int lz4hip_lz4f_batch_decode_host(byte* src, long srcLen, long* srcOff, long n, uint flags, byte* dst, long dstCap,
+                                                                       long* dstOff, Lz4fInfo* itemInfo, Lz4fBatchInfo* info);
+
         /// <summary>Devices the batch calls shard over (bit d = HIP device d; 0 = every visible device).</summary>
         public static ulong DeviceMask = 0;
 

@@ -742,6 +742,63 @@ int lz4hip_lz4f_decode_device(const void* src, int64_t src_len, int32_t slot_byt
 int lz4hip_lz4f_encode_host(const void* src, int64_t src_len, int block_size_id, int mode, unsigned flags, void* dst, int64_t dst_cap, int64_t* dst_len);
 int lz4hip_lz4f_decode_host(const void* src, int64_t src_len, unsigned flags, void* dst, int64_t dst_cap, lz4hip_lz4f_info_t* info);
 
+/* ---- batches of LZ4 frames ---------------------------------------------------------------------------
+ * Many independent frames per call, in the layout of the lz4hip_streams_* and lz4hip_wrap_* calls: one buffer src of src_len bytes plus
+ * device offsets src_off[n + 1]; item i is src[src_off[i], src_off[i + 1]); outputs lie back to back in dst with dst_off[n + 1] (device),
+ * so one call's output is the other's input.  The contract is that of lz4hip_lz4f_*_device: device pointers of the current device,
+ * launch-only on the caller's stream, no device value read on the host, no allocation, scratch from the caller (the *_scratch_bytes
+ * queries), arguments checked before the device is looked for, 0 or LZ4HIP_E_* returned.
+ *
+ * Out of scope: frames with linked blocks or a dictionary (the item's outcome says so); following appended frames inside one item (an
+ * item is ONE frame, what lies behind it is left alone and shows only in frame_bytes); span forms (chosen items of an arena); a block
+ * decoder for large blocks -- one wavefront still decodes one block.
+ *
+ * Encode: every item becomes the frame lz4hip_lz4f_encode_device writes for that item alone with the same block_size_id, mode and
+ * flags, byte for byte (an empty item's frame carries no content size).  The offsets are device values, so the block table is sized by
+ * the bound src_len / block + n; ONE block encoder call runs over the blocks of all items, the block checksums are rows of one
+ * checksum launch and the n content checksums n rows of another.  dst_cap >= lz4hip_lz4f_batch_bound.  An item whose offsets decrease
+ * or leave [0, src_len] takes 0 bytes, as in lz4hip_streams_encode_device. */
+int64_t lz4hip_lz4f_batch_bound(int64_t n, int64_t src_len, int block_size_id, unsigned flags);
+int64_t lz4hip_lz4f_batch_encode_scratch_bytes(int64_t n, int64_t src_len, int block_size_id);
+int lz4hip_lz4f_batch_encode_device(const void* src, int64_t src_len, const int64_t* src_off, int64_t n, int block_size_id, int mode, unsigned flags,
+                                    void* dst, int64_t dst_cap, int64_t* dst_off, void* scratch, int64_t scratch_bytes, void* stream);
+
+/* Decode: ONE frame per item.  item_info[n] (device) receives one lz4hip_lz4f_info_t per item, and dst[dst_off[i], dst_off[i + 1]) its
+ * bytes: what lz4hip_lz4f_decode_device gives for that item alone with a table and a dst_cap that hold it, every field, offsets relative
+ * to the item's start -- a skippable item (kind, 0 bytes), UNSUPPORTED_LINKED, UNSUPPORTED_DICT and SLOT_TOO_SMALL as the ITEM's outcome,
+ * trailing bytes behind frame_bytes left alone.  A failing item never disturbs another item's bytes or record; an item whose offsets
+ * decrease or leave [0, src_len] gets error = LZ4HIP_E_ARGUMENT and 0 bytes.  The walks run one wavefront per item, the content
+ * checksums as n rows of one checksum launch.
+ * max_blocks sizes the table for the WHOLE batch and slot_bytes bounds every item's block maximum; the block decoder picks its mapping
+ * by the rows it is handed, so size max_blocks to the batch (a table many times too large decodes a small batch with the mapping of a
+ * large one).  With more blocks than max_blocks: info.error = LZ4HIP_LZ4F_TABLE_FULL, info.blocks = the count needed, every item's
+ * error is TABLE_FULL and nothing is written to dst.
+ * dst_cap clips by position, as in the one-frame call (0 is a size query): nothing at or past dst_cap is written, *written_items
+ * (device) = the prefix of items that lie wholly inside dst_cap, the content checksum of an item not wholly written is "present but not
+ * checked", dst_off and decoded_bytes are complete all the same. */
+typedef struct lz4hip_lz4f_batch_info {
+    int64_t items;
+    int64_t blocks;          /* data blocks of all items: the rows the table needs */
+    int64_t decoded_bytes;   /* dst_off[n]: the size dst needs */
+    int64_t first_error;     /* the lowest failing item (what a sequential loop over the items raises first), -1 if none */
+    int64_t error_offset;    /* that item's error_offset, relative to the item's start; -1 if none */
+    int32_t error;           /* that item's error, LZ4HIP_LZ4F_TABLE_FULL for a table that is too small, 0 if no item failed */
+    int32_t reserved;
+} lz4hip_lz4f_batch_info_t;
+int64_t lz4hip_lz4f_batch_decode_scratch_bytes(int64_t n, int32_t slot_bytes, int64_t max_blocks, int64_t round_blocks);
+int lz4hip_lz4f_batch_decode_device(const void* src, int64_t src_len, const int64_t* src_off, int64_t n, int32_t slot_bytes, int64_t max_blocks,
+                                    int64_t round_blocks, unsigned flags, void* scratch, int64_t scratch_bytes, void* dst, int64_t dst_cap,
+                                    int64_t* dst_off, lz4hip_lz4f_info_t* item_info, lz4hip_lz4f_batch_info_t* info, int64_t* written_items,
+                                    void* stream);
+/* Host-pointer forms, staged like lz4hip_streams_*_host: one device image, results out; offsets that decrease or leave [0, src_len] are
+ * refused.  Encode returns 0 or LZ4HIP_E_*.  Decode sizes its slots by the largest block maximum among the items' descriptors and
+ * returns 0, the first failing item's code (dst, dst_off, item_info and info filled), or LZ4HIP_E_*; with dst_cap below the decoded size
+ * it returns LZ4HIP_E_ARGUMENT with dst_off, item_info and info filled in (dst_cap = 0: a size query). */
+int lz4hip_lz4f_batch_encode_host(const void* src, int64_t src_len, const int64_t* src_off, int64_t n, int block_size_id, int mode, unsigned flags,
+                                  void* dst, int64_t dst_cap, int64_t* dst_off);
+int lz4hip_lz4f_batch_decode_host(const void* src, int64_t src_len, const int64_t* src_off, int64_t n, unsigned flags, void* dst, int64_t dst_cap,
+                                  int64_t* dst_off, lz4hip_lz4f_info_t* item_info, lz4hip_lz4f_batch_info_t* info);
+
 /* ---- diagnostics ---------------------------------------------------------------------------------
  * Launch counters per kernel family since the library was loaded: which block->hardware mapping a call
  * actually used (the GPU tests assert these).  Copies min(n, LZ4HIP_K_COUNT) counters, returns LZ4HIP_K_COUNT. */

@@ -6,7 +6,8 @@
                            do the same for MANY buffers per call, the chunks of all of them in one batch (lz4hip_streams_*)
   lz4net_amd.wrap          batches of Wrap / WrapHC / Unwrap messages framed on the device (lz4hip_wrap_*)
   lz4net_amd.lz4_frame     LZ4 frames (magic 0x184D2204, what every current lz4 tool reads and writes) encoded and decoded on the
-                           device in one call (lz4hip_lz4f_*), and XXH32 of rows of device bytes
+                           device in one call (lz4hip_lz4f_*), and XXH32 of rows of device bytes; compress_frames_* / decompress_frames_*
+                           do the same for MANY frames per call, one frame per item (lz4hip_lz4f_batch_*)
   lz4net_amd._plumbing     what those modules do around every library call, once: argument checks, the per-call device context,
                            reading a record back, the retry loop, the host size query
   lz4net_amd._lib          ctypes binding of liblz4hip.so (include/lz4hip.h)

@@ -83,6 +83,12 @@ class Lz4fInfo(C.Structure):
                 ("flg", C.c_int32), ("bd", C.c_int32), ("checks", C.c_int32)]
 
 
+class Lz4fBatchInfo(C.Structure):
+    """struct lz4hip_lz4f_batch_info (include/lz4hip.h)."""
+    _fields_ = [("items", C.c_int64), ("blocks", C.c_int64), ("decoded_bytes", C.c_int64), ("first_error", C.c_int64), ("error_offset", C.c_int64),
+                ("error", C.c_int32), ("reserved", C.c_int32)]
+
+
 (LZ4F_OK, LZ4F_BAD_MAGIC, LZ4F_BAD_HEADER, LZ4F_HEADER_CHECKSUM, LZ4F_UNSUPPORTED_LINKED, LZ4F_UNSUPPORTED_DICT, LZ4F_SLOT_TOO_SMALL,
  LZ4F_TRUNCATED, LZ4F_BAD_BLOCK_SIZE, LZ4F_CORRUPT_BLOCK, LZ4F_BLOCK_CHECKSUM_ERROR, LZ4F_CONTENT_SIZE_ERROR, LZ4F_CONTENT_CHECKSUM_ERROR,
  LZ4F_TABLE_FULL) = range(14)
@@ -198,6 +204,16 @@ SYMBOLS = [
                                             C.c_void_p, C.c_void_p]),
     ("lz4hip_lz4f_encode_host", C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_uint, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
     ("lz4hip_lz4f_decode_host", C.c_int, [C.c_void_p, C.c_int64, C.c_uint, C.c_void_p, C.c_int64, C.POINTER(Lz4fInfo)]),
+    ("lz4hip_lz4f_batch_bound", C.c_int64, [C.c_int64, C.c_int64, C.c_int, C.c_uint]),
+    ("lz4hip_lz4f_batch_encode_scratch_bytes", C.c_int64, [C.c_int64, C.c_int64, C.c_int]),
+    ("lz4hip_lz4f_batch_encode_device", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_uint, C.c_void_p, C.c_int64, C.c_void_p,
+                                                  C.c_void_p, C.c_int64, C.c_void_p]),
+    ("lz4hip_lz4f_batch_decode_scratch_bytes", C.c_int64, [C.c_int64, C.c_int32, C.c_int64, C.c_int64]),
+    ("lz4hip_lz4f_batch_decode_device", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_uint, C.c_void_p, C.c_int64,
+                                                  C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("lz4hip_lz4f_batch_encode_host", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_uint, C.c_void_p, C.c_int64, C.c_void_p]),
+    ("lz4hip_lz4f_batch_decode_host", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_uint, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                                C.POINTER(Lz4fBatchInfo)]),
 ]
 
 _lib = None

@@ -1970,4 +1970,56 @@ int lz4hip_lz4f_decode_host(const void* src, int64_t src_len, unsigned flags, vo
     return lz4f_decode_host(be, src, src_len, flags, dst, dst_cap, info);
 }
 
+int64_t lz4hip_lz4f_batch_bound(int64_t n, int64_t src_len, int block_size_id, unsigned flags) { return lz4f_batch_bound(n, src_len, block_size_id, flags); }
+
+int64_t lz4hip_lz4f_batch_encode_scratch_bytes(int64_t n, int64_t src_len, int block_size_id)
+{
+    if (!lz4f_id_valid(block_size_id)) return fail(LZ4HIP_E_ARGUMENT, "lz4f batch encode: block_size_id must be 0 (64 KiB) or 4 .. 7");
+    return n <= 0 ? 0 : lz4f_batch_encode_scratch(nullptr, n, src_len < 0 ? 0 : src_len, lz4f_block_bytes(lz4f_id(block_size_id))).bytes;
+}
+
+int64_t lz4hip_lz4f_batch_decode_scratch_bytes(int64_t n, int32_t slot_bytes, int64_t max_blocks, int64_t round_blocks)
+{
+    return lz4f_batch_decode_scratch_bytes(n, slot_bytes, max_blocks, round_blocks);
+}
+
+int lz4hip_lz4f_batch_encode_device(const void* src, int64_t src_len, const int64_t* src_off, int64_t n, int block_size_id, int mode, unsigned flags,
+                                    void* dst, int64_t dst_cap, int64_t* dst_off, void* scratch, int64_t scratch_bytes, void* stream)
+{
+    HipBackend be = { (hipStream_t)stream };
+    Lz4fBatchEncodePlan p;
+    if (int rc = lz4f_batch_encode_plan(be, src, src_len, src_off, n, block_size_id, mode, flags, dst, dst_cap, dst_off, scratch, scratch_bytes, p)) return rc;
+    if (int rc = ensure_device()) return rc;
+    return lz4f_batch_encode_run(be, p);
+}
+
+int lz4hip_lz4f_batch_decode_device(const void* src, int64_t src_len, const int64_t* src_off, int64_t n, int32_t slot_bytes, int64_t max_blocks,
+                                    int64_t round_blocks, unsigned flags, void* scratch, int64_t scratch_bytes, void* dst, int64_t dst_cap,
+                                    int64_t* dst_off, lz4hip_lz4f_info_t* item_info, lz4hip_lz4f_batch_info_t* info, int64_t* written_items,
+                                    void* stream)
+{
+    HipBackend be = { (hipStream_t)stream };
+    Lz4fBatchDecodePlan p;
+    if (int rc = lz4f_batch_decode_plan(be, src, src_len, src_off, n, slot_bytes, max_blocks, round_blocks, flags, scratch, scratch_bytes, dst, dst_cap,
+                                        dst_off, item_info, info, written_items, p)) return rc;
+    if (int rc = ensure_device()) return rc;
+    return lz4f_batch_decode_run(be, p);
+}
+
+int lz4hip_lz4f_batch_encode_host(const void* src, int64_t src_len, const int64_t* src_off, int64_t n, int block_size_id, int mode, unsigned flags,
+                                  void* dst, int64_t dst_cap, int64_t* dst_off)
+{
+    HipBackend be = {};
+    if (int rc = stream_host_context(be)) return rc;
+    return lz4f_batch_encode_host(be, src, src_len, src_off, n, block_size_id, mode, flags, dst, dst_cap, dst_off);
+}
+
+int lz4hip_lz4f_batch_decode_host(const void* src, int64_t src_len, const int64_t* src_off, int64_t n, unsigned flags, void* dst, int64_t dst_cap,
+                                  int64_t* dst_off, lz4hip_lz4f_info_t* item_info, lz4hip_lz4f_batch_info_t* info)
+{
+    HipBackend be = {};
+    if (int rc = stream_host_context(be)) return rc;
+    return lz4f_batch_decode_host(be, src, src_len, src_off, n, flags, dst, dst_cap, dst_off, item_info, info);
+}
+
 }  // extern "C"

@@ -1,5 +1,5 @@
 // lz4hip_framing.hpp -- host side of the framing paths (LZ4Stream buffers, wrapped messages, batches of LZ4Stream buffers, legacy
-// frames, LZ4 frames), of the block batch's size query (lz4hip_sizes.hpp), of its packed encode (lz4hip_packed.hpp) and of its compact decode
+// frames, LZ4 frames and batches of them), of the block batch's size query (lz4hip_sizes.hpp), of its packed encode (lz4hip_packed.hpp) and of its compact decode
 // (lz4hip_compact.hpp): the scratch
 // layouts, the grids and the kernel sequences around the block codec, written ONCE for the library (lz4hip_api.hip, HipBackend) and for
 // the CPU emulator (tests/simt/emu_framing.hpp, EmuBackend).  Host code only: no kernel is defined here and nothing here calls the HIP
@@ -30,6 +30,7 @@
 #include "lz4hip_packed.hpp"
 #include "lz4hip_compact.hpp"
 #include "lz4hip_lz4f.hpp"
+#include "lz4hip_lz4f_batch.hpp"
 
 #include "../../include/lz4hip.h"
 
@@ -1786,6 +1787,288 @@ int lz4f_decode(B& be, const void* src, int64_t src_len, int32_t slot_bytes, int
     return lz4f_decode_run(be, p);
 }
 
+// ---- batches of LZ4 frames (lz4hip_lz4f_batch.hpp) --------------------------------------------------------------------------------------
+// Many independent frames per call: the one-frame path's kernels, scan, copy routine and row checksums around ONE block encoder call
+// over the blocks of all items, and around the compact decode's rounds over the rows of all items.
+static_assert(sizeof(Lz4fBatchInfo) == sizeof(lz4hip_lz4f_batch_info_t) && offsetof(Lz4fBatchInfo, first_error) == offsetof(lz4hip_lz4f_batch_info_t, first_error) &&
+              offsetof(Lz4fBatchInfo, error) == offsetof(lz4hip_lz4f_batch_info_t, error), "Lz4fBatchInfo must mirror lz4hip_lz4f_batch_info_t");
+static_assert(kLz4fBatchBadOffsets == LZ4HIP_E_ARGUMENT, "lz4f batch statuses");
+
+// the block table's rows: the host does not know the offsets, only that sum ceil(len_i / block) <= src_len / block + n
+inline int64_t lz4f_batch_cap(int64_t n, int64_t src_len, int64_t block) { return src_len / block + n; }
+
+// n descriptors, EndMarks and content checksums, and every row of the block table stored raw behind its size field
+inline int64_t lz4f_batch_bound(int64_t n, int64_t src_len, int block_size_id, unsigned flags)
+{
+    if (!lz4f_id_valid(block_size_id) || (flags & ~kLz4fEncodeFlags)) return LZ4HIP_E_ARGUMENT;
+    if (n < 0) n = 0;
+    if (src_len < 0) src_len = 0;
+    const int64_t cap = lz4f_batch_cap(n, src_len, lz4f_block_bytes(lz4f_id(block_size_id)));
+    return n * (lz4f_head_len(flags) + 4 + ((flags & kLz4fContentChecksum) ? 4 : 0)) + src_len + cap * (4 + ((flags & kLz4fBlockChecksum) ? 4 : 0));
+}
+
+// lz4f batch encode: the encoder's output (every block at its own source position), the items' spans and first blocks, the block total,
+// the block table (position, length, capacity, result, checksum row), the cap + n checksums, the n descriptors, the segments' items and
+// sizes / offsets + the total, the scans' tile sums
+struct Lz4fBatchEncodeScratch {
+    uint8_t* comp; int64_t* item_at; int64_t* item_len; int64_t* first; int64_t* total; int64_t* c_at; int32_t* c_len; int32_t* c_cap; int32_t* result;
+    int64_t* row_off; int32_t* row_len; uint32_t* sums; uint8_t* head; int32_t* seg_item; int64_t* offs; int64_t* partial; int64_t bytes;
+};
+inline Lz4fBatchEncodeScratch lz4f_batch_encode_scratch(void* scratch, int64_t n, int64_t src_len, int64_t block)
+{
+    const int64_t cap = lz4f_batch_cap(n, src_len, block), segs = cap + 2 * n;
+    Carver c(scratch);
+    Lz4fBatchEncodeScratch l;
+    l.comp = c.take_as<uint8_t>(src_len);
+    l.item_at = c.take_as<int64_t>(8 * n);
+    l.item_len = c.take_as<int64_t>(8 * n);
+    l.first = c.take_as<int64_t>(8 * n);
+    l.total = c.take_as<int64_t>(256);
+    l.c_at = c.take_as<int64_t>(8 * cap);
+    l.c_len = c.take_as<int32_t>(4 * cap);
+    l.c_cap = c.take_as<int32_t>(4 * cap);
+    l.result = c.take_as<int32_t>(4 * cap);
+    l.row_off = c.take_as<int64_t>(8 * cap);
+    l.row_len = c.take_as<int32_t>(4 * cap);
+    l.sums = c.take_as<uint32_t>(4 * (cap + n));
+    l.head = c.take_as<uint8_t>(kLz4fHeadMax * n);
+    l.seg_item = c.take_as<int32_t>(4 * segs);
+    l.offs = c.take_as<int64_t>(8 * (segs + 1));
+    l.partial = c.take_as<int64_t>(8 * scan_tiles(segs));              // (segs >= n: both scans fit)
+    l.bytes = c.at;
+    return l;
+}
+
+struct Lz4fBatchEncodePlan {
+    Lz4fBatchEncodeArgs a; int mode; int32_t* result; int64_t* row_off; int32_t* row_len; int64_t* partial; uint8_t* dst; int64_t dst_cap; int64_t* dst_off;
+    int64_t bound;
+};
+
+// a.comp and a.result are the block encoder's to write, every block at its own source position.  Rows past the blocks' count are
+// empty blocks, which read and write nothing.
+template <class B>
+int lz4f_batch_encode_run(B& be, const Lz4fBatchEncodePlan& p)
+{
+    const Lz4fBatchEncodeArgs& a = p.a;
+    if (a.n == 0) return be.fill(p.dst_off, 0, sizeof(int64_t));
+    const int64_t segs = a.cap + 2 * a.n;
+    be.launch(lz4f_batch_counts_kernel, stream_grid(a.n), kStreamThreads, a);
+    launch_scan(be, a.first, a.n, p.partial, (int64_t*)a.total);
+    be.launch(lz4f_batch_blocks_kernel, stream_grid(a.cap), kStreamThreads, a);
+    LZ4HIP_FRAMING_TRY(be.last_error());
+    lz4hip_batch_t b = {};
+    b.src = a.src; b.src_off = a.c_at; b.src_len = a.c_len;
+    b.dst = (void*)a.comp; b.dst_off = a.c_at; b.dst_cap = a.c_cap;
+    b.src_len_all = a.block; b.result = p.result; b.n_blocks = a.cap;
+    LZ4HIP_FRAMING_TRY(be.encode(&b, p.mode));
+    if (a.flags & kLz4fBlockChecksum) {
+        be.launch(lz4f_batch_rows_kernel, stream_grid(a.cap), kStreamThreads, a, p.row_off, p.row_len);
+        const XxhRows rows = { a.src, p.row_off, 0, p.row_len, nullptr, 0, 0u, a.sums, a.cap };
+        LZ4HIP_FRAMING_TRY(xxh32_rows_run(be, rows));
+    }
+    if (a.flags & kLz4fContentChecksum) {
+        const XxhRows content = { a.src, a.item_at, 0, nullptr, a.item_len, 0, 0u, a.sums + a.cap, a.n };
+        LZ4HIP_FRAMING_TRY(xxh32_rows_run(be, content));
+    }
+    be.launch(lz4f_batch_head_kernel, stream_grid(a.n), kStreamThreads, a);
+    be.launch(lz4f_batch_sizes_kernel, stream_grid(segs), kStreamThreads, a);
+    launch_scan(be, a.offs, segs, p.partial, a.offs + segs);
+    be.launch(lz4f_batch_offsets_kernel, stream_grid(a.n + 1), kStreamThreads, a, p.dst_off);
+    Lz4fBatchLayout layout = { a };
+    be.launch(lz4f_batch_pack_kernel, copy_grid(p.bound), kStreamThreads, layout, p.dst, p.dst_cap);
+    return be.last_error();
+}
+
+template <class B>
+int lz4f_batch_encode_plan(B& be, const void* src, int64_t src_len, const int64_t* src_off, int64_t n, int block_size_id, int mode, unsigned flags,
+                           void* dst, int64_t dst_cap, int64_t* dst_off, void* scratch, int64_t scratch_bytes, Lz4fBatchEncodePlan& p)
+{
+    if (src_len < 0 || n < 0 || !dst_off) return be.fail(LZ4HIP_E_ARGUMENT, "lz4f batch encode: src_len < 0, n < 0 or dst_off is NULL");
+    if (!lz4f_id_valid(block_size_id)) return be.fail(LZ4HIP_E_ARGUMENT, "lz4f batch encode: block_size_id must be 0 (64 KiB) or 4 .. 7");
+    if (flags & ~kLz4fEncodeFlags) return be.fail(LZ4HIP_E_ARGUMENT, "lz4f batch encode: unknown flag");
+    if (mode != LZ4HIP_MODE_FAST && mode != LZ4HIP_MODE_HC) return be.fail(LZ4HIP_E_ARGUMENT, "mode must be LZ4HIP_MODE_FAST or LZ4HIP_MODE_HC");
+    const int id = lz4f_id(block_size_id);
+    const int64_t block = lz4f_block_bytes(id), cap = lz4f_batch_cap(n, src_len, block);
+    if (n > 0x3FFFFFFF || cap > 0x3FFFFFFF) return be.fail(LZ4HIP_E_ARGUMENT, "lz4f batch encode: more than 2^30 - 1 items or blocks");
+    p.bound = lz4f_batch_bound(n, src_len, block_size_id, flags);
+    if (n > 0 && dst_cap < p.bound) return be.fail(LZ4HIP_E_ARGUMENT, "lz4f batch encode: dst_cap < lz4hip_lz4f_batch_bound");
+    const Lz4fBatchEncodeScratch l = lz4f_batch_encode_scratch(scratch, n, src_len, block);
+    if (n > 0 && scratch_bytes < l.bytes) return be.fail(LZ4HIP_E_ARGUMENT, "lz4f batch encode: scratch_bytes < lz4hip_lz4f_batch_encode_scratch_bytes");
+    if (n > 0 && ((src_len > 0 && !src) || !src_off || !dst || !scratch))
+        return be.fail(LZ4HIP_E_ARGUMENT, "lz4f batch encode: src, src_off, dst and scratch must be non-NULL");
+    Lz4fBatchEncodeArgs& a = p.a;
+    // (an empty source's items are all empty: any address will do for them)
+    a.src = src ? (const uint8_t*)src : (const uint8_t*)scratch; a.comp = l.comp; a.off = src_off; a.src_len = src_len; a.n = n; a.cap = cap;
+    a.block = (int32_t)block; a.block_id = id; a.flags = flags;
+    a.item_at = l.item_at; a.item_len = l.item_len; a.first = l.first; a.total = l.total; a.c_at = l.c_at; a.c_len = l.c_len; a.c_cap = l.c_cap;
+    a.result = l.result; a.sums = l.sums; a.head = l.head; a.seg_item = l.seg_item; a.offs = l.offs;
+    p.mode = mode; p.result = l.result; p.row_off = l.row_off; p.row_len = l.row_len; p.partial = l.partial;
+    p.dst = (uint8_t*)dst; p.dst_cap = dst_cap; p.dst_off = dst_off;
+    return 0;
+}
+
+template <class B>
+int lz4f_batch_encode(B& be, const void* src, int64_t src_len, const int64_t* src_off, int64_t n, int block_size_id, int mode, unsigned flags, void* dst,
+                      int64_t dst_cap, int64_t* dst_off, void* scratch, int64_t scratch_bytes)
+{
+    Lz4fBatchEncodePlan p;
+    LZ4HIP_FRAMING_TRY(lz4f_batch_encode_plan(be, src, src_len, src_off, n, block_size_id, mode, flags, dst, dst_cap, dst_off, scratch, scratch_bytes, p));
+    return lz4f_batch_encode_run(be, p);
+}
+
+// lz4f batch decode: what is kept per item (the walk's records, spans, first rows, lowest bad rows, content rows), the totals, the
+// scan's tile sums, the table of max_blocks rows, then the compact decode's scratch for max_blocks rows of slot_bytes
+inline Lz4fBatchTables lz4f_batch_tables(Carver& c, int64_t n, int64_t max_blocks)
+{
+    Lz4fBatchTables t;
+    t.max_blocks = max_blocks; t.n = n;
+    t.total = c.take_as<int64_t>(256);
+    t.min_bad = (unsigned long long*)t.total + 1;
+    t.walk = c.take_as<int64_t>(8 * kLz4fWalkSlots * n);
+    t.item_at = c.take_as<int64_t>(8 * n);
+    t.base = c.take_as<int64_t>(8 * n);
+    t.item_bad = c.take_as<unsigned long long>(8 * n);
+    t.content_off = c.take_as<int64_t>(8 * n);
+    t.content_len = c.take_as<int64_t>(8 * n);
+    t.content_sums = c.take_as<uint32_t>(4 * n);
+    t.src_off = c.take_as<int64_t>(8 * max_blocks);
+    t.hdr_off = c.take_as<int64_t>(8 * max_blocks);
+    t.dst_off = c.take_as<int64_t>(8 * (max_blocks + 1));
+    t.stored = c.take_as<int32_t>(4 * max_blocks);
+    t.dec_len = c.take_as<int32_t>(4 * max_blocks);
+    t.sum_len = c.take_as<int32_t>(4 * max_blocks);
+    t.result = c.take_as<int32_t>(4 * max_blocks);
+    t.item = c.take_as<int32_t>(4 * max_blocks);
+    t.sums = c.take_as<uint32_t>(4 * max_blocks);
+    t.row = c.take_as<uint8_t>(max_blocks);
+    return t;
+}
+struct Lz4fBatchDecodeScratch { Lz4fBatchTables t; int64_t* partial; PackedScratch l; int64_t bytes; };
+inline Lz4fBatchDecodeScratch lz4f_batch_decode_scratch(void* scratch, int64_t n, int32_t slot, int64_t max_blocks, int64_t round_blocks)
+{
+    Carver c(scratch);
+    Lz4fBatchDecodeScratch d;
+    d.t = lz4f_batch_tables(c, n, max_blocks);
+    d.partial = c.take_as<int64_t>(8 * scan_tiles(n));
+    d.l = packed_scratch(c.take_as<uint8_t>(0), max_blocks, slot, round_blocks);
+    d.bytes = c.at + d.l.bytes;
+    return d;
+}
+inline int64_t lz4f_batch_decode_scratch_bytes(int64_t n, int32_t slot_bytes, int64_t max_blocks, int64_t round_blocks)
+{
+    if (n < 0 || !lz4f_slot_valid(slot_bytes) || max_blocks < 1 || round_blocks < 0) return LZ4HIP_E_ARGUMENT;
+    return lz4f_batch_decode_scratch(nullptr, n, lz4f_slot(slot_bytes), max_blocks, round_blocks).bytes;
+}
+
+struct Lz4fBatchDecodePlan {
+    Lz4fBatchDecodeArgs a; Lz4fBatchTables t; int64_t* partial; PackedScratch l; int64_t round, slot; uint8_t* dst; Lz4fBatchInfo* info;
+};
+
+// The two walks around their scan, the block checksums, then lz4f_decode_run's rounds over ALL max_blocks rows of the table with the
+// batch's sizes step and pack layout, the items' records, their content checksums as n rows of one launch, the batch's record.
+// Nothing is read on the host between the steps.
+template <class B>
+int lz4f_batch_decode_run(B& be, const Lz4fBatchDecodePlan& p)
+{
+    const Lz4fBatchDecodeArgs& a = p.a;
+    const Lz4fBatchTables& t = p.t;
+    const int64_t m = t.max_blocks;
+    LZ4HIP_FRAMING_TRY(be.fill(a.written_items, 0, sizeof(int64_t)));
+    if (a.n == 0) {
+        LZ4HIP_FRAMING_TRY(be.fill(a.dst_off, 0, sizeof(int64_t)));
+        be.launch(lz4f_batch_empty_record_kernel, fixed_grid(1), 64, p.info);
+        return be.last_error();
+    }
+    LZ4HIP_FRAMING_TRY(be.fill(t.src_off, 0, (size_t)(8 * m)));
+    LZ4HIP_FRAMING_TRY(be.fill(t.stored, 0, (size_t)(4 * m)));
+    LZ4HIP_FRAMING_TRY(be.fill(t.dec_len, 0, (size_t)(4 * m)));
+    LZ4HIP_FRAMING_TRY(be.fill(t.sum_len, 0, (size_t)(4 * m)));
+    LZ4HIP_FRAMING_TRY(be.fill(t.item, 0, (size_t)(4 * m)));
+    LZ4HIP_FRAMING_TRY(be.fill(t.row, 0, (size_t)m));
+    LZ4HIP_FRAMING_TRY(be.fill(t.total, 0, 8));
+    LZ4HIP_FRAMING_TRY(be.fill(t.min_bad, 0xFF, 8));                   // the lowest failing item = none
+    LZ4HIP_FRAMING_TRY(be.fill(t.item_bad, 0xFF, (size_t)(8 * a.n)));  // every item's lowest bad row = none
+    be.launch(lz4f_batch_walk_kernel<false>, walk_grid(a.n), 64, a, t);
+    launch_scan(be, t.base, a.n, p.partial, t.total);
+    be.launch(lz4f_batch_walk_kernel<true>, walk_grid(a.n), 64, a, t);
+    LZ4HIP_FRAMING_TRY(be.last_error());
+    if (a.flags & kLz4fVerifyBlocks) {
+        const XxhRows rows = { a.src, t.src_off, 0, t.sum_len, nullptr, 0, 0u, t.sums, m };
+        LZ4HIP_FRAMING_TRY(xxh32_rows_run(be, rows));
+        be.launch(lz4f_batch_verify_kernel, stream_grid(m), kStreamThreads, a.src, t);
+    }
+    LZ4HIP_FRAMING_TRY(be.fill(p.l.state, 0, (size_t)kPackedStateBytes));
+    LZ4HIP_FRAMING_TRY(be.fill(p.l.state + kPackedBad, 0xFF, 8));
+    const Grid pack_grid = copy_grid(p.round * p.slot);
+    int32_t parity = 0;
+    for (int64_t first = 0; first < m; first += p.round, parity ^= 1) {
+        PackedRound r;
+        r.first = first; r.cnt = m - first < p.round ? m - first : p.round; r.slot = p.slot; r.limit = a.slot_bytes; r.parity = parity;
+        r.cap_in = nullptr; r.caps = p.l.caps; r.result = t.result + first;
+        r.len_in = t.dec_len + first; r.lens_enc = p.l.lens;
+        r.ring = p.l.ring; r.offs = t.dst_off + first; r.lens = nullptr; r.state = p.l.state;
+        be.launch(packed_caps_kernel, stream_grid(r.cnt), kStreamThreads, r);
+        LZ4HIP_FRAMING_TRY(be.last_error());
+        lz4hip_batch_t rb = {};
+        rb.src = a.src; rb.src_off = t.src_off + first; rb.src_len = p.l.lens;
+        rb.dst = p.l.ring; rb.dst_stride = p.slot; rb.dst_cap = p.l.caps;
+        rb.result = r.result; rb.n_blocks = r.cnt;
+        LZ4HIP_FRAMING_TRY(be.decode(&rb, 0));
+        const Lz4fBatchRound br = { r, a.src, t.src_off + first, t.stored + first, t.row + first, t.item + first, t.walk, t.item_bad };
+        be.launch(lz4f_batch_round_sizes_kernel, stream_grid(r.cnt), kStreamThreads, br);
+        launch_scan(be, r.offs, r.cnt, p.l.partial, p.l.state + kPackedTotal);
+        be.launch(packed_rebase_kernel, stream_grid(r.cnt), kStreamThreads, r);
+        Lz4fBatchRoundLayout layout = { br };
+        be.launch(lz4f_batch_round_pack_kernel, pack_grid, kStreamThreads, layout, p.dst, a.dst_cap);
+        LZ4HIP_FRAMING_TRY(be.last_error());
+    }
+    be.launch(lz4f_batch_offsets_out_kernel, stream_grid(a.n + 1), kStreamThreads, a, t);
+    be.launch(lz4f_batch_info_kernel, stream_grid(a.n), kStreamThreads, a, t);
+    if (a.flags & kLz4fVerifyContent) {
+        const XxhRows content = { p.dst, t.content_off, 0, nullptr, t.content_len, 0, 0u, t.content_sums, a.n };
+        LZ4HIP_FRAMING_TRY(xxh32_rows_run(be, content));
+        be.launch(lz4f_batch_final_kernel, stream_grid(a.n), kStreamThreads, a, t);
+    }
+    be.launch(lz4f_batch_record_kernel, fixed_grid(1), 64, a, t, p.info);
+    return be.last_error();
+}
+
+template <class B>
+int lz4f_batch_decode_plan(B& be, const void* src, int64_t src_len, const int64_t* src_off, int64_t n, int32_t slot_bytes, int64_t max_blocks,
+                           int64_t round_blocks, unsigned flags, void* scratch, int64_t scratch_bytes, void* dst, int64_t dst_cap, int64_t* dst_off,
+                           lz4hip_lz4f_info_t* item_info, lz4hip_lz4f_batch_info_t* info, int64_t* written_items, Lz4fBatchDecodePlan& p)
+{
+    if (src_len < 0 || n < 0 || max_blocks < 1 || round_blocks < 0 || dst_cap < 0 || !dst_off || !info || !written_items || (dst_cap > 0 && !dst))
+        return be.fail(LZ4HIP_E_ARGUMENT, "lz4f batch decode: negative size, max_blocks < 1 or NULL pointer");
+    if (n > 0 && (!src_off || !item_info || !scratch || (src_len > 0 && !src))) return be.fail(LZ4HIP_E_ARGUMENT, "lz4f batch decode: NULL pointer");
+    if (n > 0x7FFFFFFF) return be.fail(LZ4HIP_E_ARGUMENT, "lz4f batch decode: more than 2^31 - 1 items");
+    if (!lz4f_slot_valid(slot_bytes)) return be.fail(LZ4HIP_E_ARGUMENT, "lz4f batch decode: slot_bytes must be 0 (4 MiB), 65536, 262144, 1048576 or 4194304");
+    if (flags & ~kLz4fDecodeFlags) return be.fail(LZ4HIP_E_ARGUMENT, "lz4f batch decode: unknown flag");
+    if (packed_round(max_blocks, round_blocks) > 0x7FFFFFFF) return be.fail(LZ4HIP_E_ARGUMENT, "lz4f batch decode: more than 2^31 - 1 table rows in a round");
+    const int32_t slot = lz4f_slot(slot_bytes);
+    const Lz4fBatchDecodeScratch d = lz4f_batch_decode_scratch(scratch, n, slot, max_blocks, round_blocks);
+    if (n > 0 && scratch_bytes < d.bytes) return be.fail(LZ4HIP_E_ARGUMENT, "lz4f batch decode: scratch_bytes < lz4hip_lz4f_batch_decode_scratch_bytes");
+    Lz4fBatchDecodeArgs& a = p.a;
+    // (an empty source's rows are all empty: any address will do for them)
+    a.src = src ? (const uint8_t*)src : (const uint8_t*)scratch; a.off = src_off; a.src_len = src_len; a.n = n; a.slot_bytes = slot; a.flags = flags;
+    a.dst_cap = dst_cap; a.dst_off = dst_off; a.item_info = (Lz4fInfo*)item_info; a.written_items = written_items;
+    p.t = d.t; p.partial = d.partial; p.l = d.l; p.round = packed_round(max_blocks, round_blocks); p.slot = packed_slot(slot);
+    p.dst = (uint8_t*)dst; p.info = (Lz4fBatchInfo*)info;
+    return 0;
+}
+
+template <class B>
+int lz4f_batch_decode(B& be, const void* src, int64_t src_len, const int64_t* src_off, int64_t n, int32_t slot_bytes, int64_t max_blocks, int64_t round_blocks,
+                      unsigned flags, void* scratch, int64_t scratch_bytes, void* dst, int64_t dst_cap, int64_t* dst_off, lz4hip_lz4f_info_t* item_info,
+                      lz4hip_lz4f_batch_info_t* info, int64_t* written_items)
+{
+    Lz4fBatchDecodePlan p;
+    LZ4HIP_FRAMING_TRY(lz4f_batch_decode_plan(be, src, src_len, src_off, n, slot_bytes, max_blocks, round_blocks, flags, scratch, scratch_bytes, dst, dst_cap,
+                                              dst_off, item_info, info, written_items, p));
+    return lz4f_batch_decode_run(be, p);
+}
+
+
 // ---- the host-pointer calls ------------------------------------------------------------------------------------------------------------
 // Each stages its arguments in ONE device image, runs the device path above on it and copies the results out.  An image is a Carver's
 // walk over no buffer -- its pieces are offsets, good for any base -- plus the base of the backend's reserve.  That base may move
@@ -2169,6 +2452,98 @@ int lz4f_decode_host(B& be, const void* src, int64_t src_len, unsigned flags, vo
     if (h.decoded_bytes > dst_cap || h.decoded_bytes > out_bytes)
         return be.fail(LZ4HIP_E_ARGUMENT, "lz4f decode: dst_cap < decoded_bytes (reported in info->decoded_bytes)");
     if (h.decoded_bytes > 0 && !dst) return be.fail(LZ4HIP_E_ARGUMENT, "lz4f decode: dst is NULL");
+    if (h.decoded_bytes > 0) LZ4HIP_FRAMING_TRY(im.download(dst, out_at, h.decoded_bytes));
+    LZ4HIP_FRAMING_TRY(be.sync());
+    return info->error;
+}
+
+// A batch of frames staged the way streams_encode_host stages a batch of streams; the offsets are host memory here, so bad ones are
+// refused instead of encoded as items of no bytes.
+template <class B>
+int lz4f_batch_encode_host(B& be, const void* src, int64_t src_len, const int64_t* src_off, int64_t n, int block_size_id, int mode, unsigned flags,
+                           void* dst, int64_t dst_cap, int64_t* dst_off)
+{
+    if (src_len < 0 || n < 0 || !dst_off || (n > 0 && (!src_off || !dst)) || (src_len > 0 && n > 0 && !src))
+        return be.fail(LZ4HIP_E_ARGUMENT, "lz4f batch encode: negative size or NULL pointer");
+    if (!lz4f_id_valid(block_size_id) || (flags & ~kLz4fEncodeFlags)) return be.fail(LZ4HIP_E_ARGUMENT, "lz4f batch encode: block_size_id must be 0 or 4 .. 7, flags known");
+    if (mode != LZ4HIP_MODE_FAST && mode != LZ4HIP_MODE_HC) return be.fail(LZ4HIP_E_ARGUMENT, "mode must be LZ4HIP_MODE_FAST or LZ4HIP_MODE_HC");
+    for (int64_t i = 0; i < n; i++)
+        if (src_off[i] < 0 || src_off[i + 1] < src_off[i] || src_off[i + 1] > src_len)
+            return be.fail(LZ4HIP_E_ARGUMENT, "lz4f batch encode: offsets decrease or fall outside [0, src_len]");
+    const int64_t bound = lz4f_batch_bound(n, src_len, block_size_id, flags);
+    if (n > 0 && dst_cap < bound) return be.fail(LZ4HIP_E_ARGUMENT, "lz4f batch encode: dst_cap < lz4hip_lz4f_batch_bound");
+    if (n == 0) { dst_off[0] = 0; return 0; }
+    // device image: [source | offsets | output | output offsets | scratch]
+    const int64_t scratch_bytes = lz4f_batch_encode_scratch(nullptr, n, src_len, lz4f_block_bytes(lz4f_id(block_size_id))).bytes;
+    Carver c;
+    c.take(src_len);
+    const int64_t off_at = c.take(8 * (n + 1)), out_at = c.take(bound), doff_at = c.take(8 * (n + 1)), scratch_at = c.take(scratch_bytes);
+    Image<B> im = { be };
+    LZ4HIP_FRAMING_TRY(im.reserve(c.at));
+    LZ4HIP_FRAMING_TRY(im.upload_source(src, src_len, src_off, n, off_at));
+    LZ4HIP_FRAMING_TRY(lz4f_batch_encode(be, im.d, src_len, im.i64(off_at), n, block_size_id, mode, flags, im.d + out_at, bound, im.i64(doff_at),
+                                         im.d + scratch_at, scratch_bytes));
+    LZ4HIP_FRAMING_TRY(im.download_items({ n, dst_off, doff_at, nullptr, 0, nullptr, 0 }));
+    LZ4HIP_FRAMING_TRY(be.sync());
+    return im.download_encoded(dst, out_at, dst_off[n] < dst_cap ? dst_off[n] : dst_cap);
+}
+
+// The descriptors lie in host memory here: the largest block maximum among them sizes the slots.  The table and the output's piece of
+// the image start as guesses; a table that was too small or an output that has to grow is decoded again with what the record reported,
+// three passes at most.  The rounds are bounded (a ring of 256 MiB, at least 64 slots), so the image does not grow with the table.
+// On dst_cap < decoded_bytes the offsets and the items' records are the caller's with the info (a size query: dst_cap = 0).
+template <class B>
+int lz4f_batch_decode_host(B& be, const void* src, int64_t src_len, const int64_t* src_off, int64_t n, unsigned flags, void* dst, int64_t dst_cap,
+                           int64_t* dst_off, lz4hip_lz4f_info_t* item_info, lz4hip_lz4f_batch_info_t* info)
+{
+    if (src_len < 0 || n < 0 || dst_cap < 0 || !dst_off || !info || (n > 0 && (!src_off || !item_info)) || (src_len > 0 && n > 0 && !src))
+        return be.fail(LZ4HIP_E_ARGUMENT, "lz4f batch decode: negative size or NULL pointer");
+    if (flags & ~kLz4fDecodeFlags) return be.fail(LZ4HIP_E_ARGUMENT, "lz4f batch decode: unknown flag");
+    if (n == 0) { lz4hip_lz4f_batch_info_t r = {}; r.first_error = r.error_offset = -1; *info = r; dst_off[0] = 0; return 0; }
+    const uint8_t* s = (const uint8_t*)src;
+    int id = 4;
+    for (int64_t i = 0; i < n; i++) {
+        if (src_off[i] < 0 || src_off[i + 1] < src_off[i] || src_off[i + 1] > src_len)
+            return be.fail(LZ4HIP_E_ARGUMENT, "lz4f batch decode: offsets decrease or fall outside [0, src_len]");
+        const uint8_t* f = s + src_off[i];
+        if (src_off[i + 1] - src_off[i] >= 6 && f[0] == 0x04 && f[1] == 0x22 && f[2] == 0x4D && f[3] == 0x18 && ((f[5] >> 4) & 7) > id) id = (f[5] >> 4) & 7;
+    }
+    const int32_t slot = lz4f_block_bytes(id);
+    const int64_t round_blocks = ((int64_t)1 << 28) / slot;
+    // device image: [source | offsets | output offsets | records | info | written | output | scratch]
+    Carver head;
+    head.take(src_len);
+    const int64_t off_at = head.take(8 * (n + 1)), doff_at = head.take(8 * (n + 1)), rec_at = head.take((int64_t)sizeof(lz4hip_lz4f_info_t) * n),
+                  info_at = head.take(256), written_at = head.take(256), out_at = head.at;
+    Image<B> im = { be };
+    int64_t max_blocks = src_len / 4096 + n + 16, out_bytes = guessed_output(src_len, dst_cap);
+    lz4hip_lz4f_batch_info_t h = {};
+    for (int attempt = 0;; attempt++) {
+        const int64_t scratch_bytes = lz4f_batch_decode_scratch_bytes(n, slot, max_blocks, round_blocks);
+        Carver c = head;
+        c.take(out_bytes);
+        const int64_t scratch_at = c.take(scratch_bytes);
+        LZ4HIP_FRAMING_TRY(im.reserve(c.at));
+        LZ4HIP_FRAMING_TRY(im.upload_source(src, src_len, src_off, n, off_at));
+        LZ4HIP_FRAMING_TRY(lz4f_batch_decode(be, im.d, src_len, im.i64(off_at), n, slot, max_blocks, round_blocks, flags, im.d + scratch_at, scratch_bytes,
+                                             im.d + out_at, out_bytes, im.i64(doff_at), (lz4hip_lz4f_info_t*)(im.d + rec_at),
+                                             (lz4hip_lz4f_batch_info_t*)(im.d + info_at), im.i64(written_at)));
+        LZ4HIP_FRAMING_TRY(im.download(&h, info_at, sizeof h));
+        LZ4HIP_FRAMING_TRY(be.sync());
+        if (attempt >= 2) break;
+        if (h.error == LZ4HIP_LZ4F_TABLE_FULL) max_blocks = h.blocks;
+        else if (h.decoded_bytes > dst_cap || h.decoded_bytes <= out_bytes) break;
+        else out_bytes = h.decoded_bytes;
+    }
+    *info = h;
+    if (h.error == LZ4HIP_LZ4F_TABLE_FULL) return be.fail(LZ4HIP_E_DEVICE, "lz4f batch decode: the size field walks did not settle");
+    LZ4HIP_FRAMING_TRY(im.download(dst_off, doff_at, 8 * (n + 1)));
+    LZ4HIP_FRAMING_TRY(im.download(item_info, rec_at, (int64_t)sizeof(lz4hip_lz4f_info_t) * n));
+    if (h.decoded_bytes > dst_cap || h.decoded_bytes > out_bytes) {
+        LZ4HIP_FRAMING_TRY(be.sync());
+        return be.fail(LZ4HIP_E_ARGUMENT, "lz4f batch decode: dst_cap < decoded_bytes (reported in info->decoded_bytes)");
+    }
+    if (h.decoded_bytes > 0 && !dst) return be.fail(LZ4HIP_E_ARGUMENT, "lz4f batch decode: dst is NULL");
     if (h.decoded_bytes > 0) LZ4HIP_FRAMING_TRY(im.download(dst, out_at, h.decoded_bytes));
     LZ4HIP_FRAMING_TRY(be.sync());
     return info->error;

@@ -359,15 +359,24 @@ struct Lz4fTables {
     int64_t* walk;                                                     // kLz4fWalk* slots
 };
 
-// One wavefront; every lane runs the same walk on the same (wave-uniform) position and lane 0 writes.  The descriptor's checks come in
+// what one walk found: the kLz4fWalk* slots before they are stored
+struct Lz4fWalk {
+    int64_t pos, blocks, err_off, content_size, trailer;
+    int err, kind, flg, bd;
+    int32_t block_max;
+};
+
+// The walk over ONE frame at src[0, src_len), by every lane of a wavefront on the same (wave-uniform) position; it writes nothing itself:
+// row(k, pos, size, raw, sum_bytes) is called for data block k, whose size field lies at pos.  lz4f_walk_kernel and the batch's walk
+// (lz4hip_lz4f_batch.hpp) are this walk with their own rows.  The descriptor's checks come in
 // the order a sequential reader applies them: version, reserved bits and block size id; the descriptor's length against the frame's;
 // HC; then what this decoder does not take (a dictionary ID, linked blocks, a block maximum above the caller's slot).  With a
 // descriptor error no block is walked.  Per size field: the EndMark (and the content checksum behind it), the size against the
 // frame's block maximum, then the data and its checksum against the end of the frame.
-__global__ void __launch_bounds__(64) lz4f_walk_kernel(const uint8_t* src, int64_t src_len, int32_t slot_bytes, Lz4fTables t)
+template <class Row>
+LZ4HIP_DEVICE Lz4fWalk lz4f_walk_frame(const uint8_t* src, int64_t src_len, int32_t slot_bytes, Row row)
 {
-    const int lane = wv::lane();
-    int64_t pos = 0, blocks = 0, err_off = -1, full_off = -1, content_size = -1, trailer = -1;
+    int64_t pos = 0, blocks = 0, err_off = -1, content_size = -1, trailer = -1;
     int err = kLz4fOk, kind = kLz4fKindFrame, flg = 0, bd = 0;
     int32_t block_max = 0;
     const uint32_t magic = src_len >= 4 ? wv::uniform(load_u32(src)) : 0u;
@@ -411,26 +420,43 @@ __global__ void __launch_bounds__(64) lz4f_walk_kernel(const uint8_t* src, int64
             const int64_t size = (int64_t)(field & ~kLz4fRawBit);
             if (size > block_max) { err = kLz4fBadBlockSize; err_off = pos; break; }
             if (pos + 4 + size + sum_bytes > src_len) { err = kLz4fTruncated; err_off = pos; break; }
-            if (blocks < t.max_blocks) {
-                if (lane == 0) {
-                    const bool raw = (field & kLz4fRawBit) != 0;
-                    t.src_off[blocks] = pos + 4; t.hdr_off[blocks] = pos; t.stored[blocks] = (int32_t)size;
-                    t.dec_len[blocks] = raw ? 0 : (int32_t)size; t.sum_len[blocks] = sum_bytes ? (int32_t)size : 0;
-                    t.row[blocks] = raw ? kLz4fRowRaw : 0;
-                }
-            } else if (blocks == t.max_blocks) {
-                full_off = pos;
-            }
+            row(blocks, pos, (int32_t)size, (field & kLz4fRawBit) != 0, (int32_t)sum_bytes);
             blocks++;
             pos += 4 + size + sum_bytes;
         }
     }
-    if (lane == 0) {
-        int64_t* w = t.walk;
-        w[kLz4fWalkBlocks] = blocks; w[kLz4fWalkError] = err; w[kLz4fWalkErrorOff] = err_off; w[kLz4fWalkFullOff] = full_off;
-        w[kLz4fWalkFlg] = flg; w[kLz4fWalkBd] = bd; w[kLz4fWalkContentSize] = content_size; w[kLz4fWalkFrameBytes] = pos;
-        w[kLz4fWalkKind] = kind; w[kLz4fWalkTrailer] = trailer; w[kLz4fWalkBlockMax] = block_max; w[kLz4fWalkContentLen] = 0;
-    }
+    Lz4fWalk r;
+    r.pos = pos; r.blocks = blocks; r.err_off = err_off; r.content_size = content_size; r.trailer = trailer;
+    r.err = err; r.kind = kind; r.flg = flg; r.bd = bd; r.block_max = block_max;
+    return r;
+}
+
+// the walk's record in its slots; full_off: the size field of the first block that did not fit the table, -1 if all did
+LZ4HIP_DEVICE void lz4f_walk_store(int64_t* w, const Lz4fWalk& r, int64_t full_off)
+{
+    w[kLz4fWalkBlocks] = r.blocks; w[kLz4fWalkError] = r.err; w[kLz4fWalkErrorOff] = r.err_off; w[kLz4fWalkFullOff] = full_off;
+    w[kLz4fWalkFlg] = r.flg; w[kLz4fWalkBd] = r.bd; w[kLz4fWalkContentSize] = r.content_size; w[kLz4fWalkFrameBytes] = r.pos;
+    w[kLz4fWalkKind] = r.kind; w[kLz4fWalkTrailer] = r.trailer; w[kLz4fWalkBlockMax] = r.block_max; w[kLz4fWalkContentLen] = 0;
+}
+
+// One wavefront; every lane runs the same walk on the same (wave-uniform) position and lane 0 writes: row k of the table for block k
+// while the table has rows, the record at the end.
+__global__ void __launch_bounds__(64) lz4f_walk_kernel(const uint8_t* src, int64_t src_len, int32_t slot_bytes, Lz4fTables t)
+{
+    const int lane = wv::lane();
+    int64_t full_off = -1;
+    const Lz4fWalk r = lz4f_walk_frame(src, src_len, slot_bytes, [&](int64_t k, int64_t pos, int32_t size, bool raw, int32_t sum_bytes) {
+        if (k < t.max_blocks) {
+            if (lane == 0) {
+                t.src_off[k] = pos + 4; t.hdr_off[k] = pos; t.stored[k] = size;
+                t.dec_len[k] = raw ? 0 : size; t.sum_len[k] = sum_bytes ? size : 0;
+                t.row[k] = raw ? kLz4fRowRaw : 0;
+            }
+        } else if (k == t.max_blocks) {
+            full_off = pos;
+        }
+    });
+    if (lane == 0) lz4f_walk_store(t.walk, r, full_off);
 }
 
 // after xxh32_rows_kernel over the rows' stored bytes: a row whose checksum does not match is a bad block, and the decoder is handed an

@@ -8,7 +8,11 @@ K4os.Compression.LZ4.Streams and python-lz4 write and read.
 The blocks are the block format the library encodes and decodes anyway; the framing, the xxHash32 checksums and the packing run on
 the device (lz4hip_lz4f_* of include/lz4hip.h).  Frames written here hold independent blocks and no dictionary; frames with linked
 blocks (FLG.5 clear) or a dictionary ID are refused with a clear message, not decoded wrongly.  Skippable frames (magic 0x184D2A50 ..
-0x184D2A5F) are skipped, appended frames decoded one after the other."""
+0x184D2A5F) are skipped, appended frames decoded one after the other.
+
+Many frames at once -- the buffers of an Arrow IPC stream, the record batches of a Kafka log, a service's pickled messages -- go
+through the batch calls (lz4hip_lz4f_batch_*): compress_frames_device / decompress_frames_device and their host forms take one buffer
+and int64 offsets[n + 1], as the batches of stream.py and wrap.py do, and treat every item as ONE frame."""
 from __future__ import annotations
 
 import ctypes as C
@@ -238,3 +242,116 @@ def xxh32_rows_device(data, off, lens, seed: int = 0):
         _lib.check(d.lib.lz4hip_xxh32_rows_device(data.data_ptr(), off.contiguous().data_ptr(), 0, lens.contiguous().data_ptr(), 0,
                                                   seed & 0xFFFFFFFF, sums.data_ptr(), n, d.stream))
         return sums
+
+
+# ---- batches of frames: one buffer, offsets[n + 1], one frame per item ---------------------------------------------------------------------
+
+def _item_error(batch):
+    """the exception of the first failing item of a batch record (lz4hip_lz4f_batch_info_t), with the item's index in .item"""
+    i = int(batch.first_error)
+    if batch.error == _lib.E_ARGUMENT:
+        e = ArgumentException(_p.BAD_OFFSETS)
+        e.error_offset, e.status = -1, int(batch.error)
+    else:
+        e = _frame_error(batch.error, batch.error_offset)
+    e.item = i
+    return e
+
+
+def compress_frames_device(t, offsets, block_size: int = 65536, high_compression: bool = False, block_checksum: bool = False,
+                           content_checksum: bool = False, content_size: bool = True):
+    """[compress_frame_device(item) for item in items] for the items t[offsets[i]:offsets[i + 1]] of a 1-D uint8 CUDA tensor, in one
+    call on the device, on torch's current stream -> (frames, frame_offsets): item i's frame is frames[frame_offsets[i]:
+    frame_offsets[i + 1]], byte for byte the frame of that item alone.  The blocks of all items are one batch of the block encoder,
+    the block checksums rows of one checksum launch, the n content checksums n rows of another.  Waits for the device once, to learn
+    the total."""
+    import torch
+    t, offsets = _p.check_device_batch(t, offsets)
+    bid, flags = _block_id(block_size), _encode_flags(block_checksum, content_checksum, content_size)
+    with _p.DeviceCall(t) as d:
+        n = offsets.numel() - 1
+        bound = d.lib.lz4hip_lz4f_batch_bound(n, t.numel(), bid, flags)
+        out, out_off = d.u8(bound), d.i64(n + 1)
+        scratch = d.u8(max(d.lib.lz4hip_lz4f_batch_encode_scratch_bytes(n, t.numel(), bid), 1))
+        _lib.check(d.lib.lz4hip_lz4f_batch_encode_device(t.data_ptr(), t.numel(), offsets.data_ptr(), n, bid, _p.mode(high_compression), flags,
+                                                         out.data_ptr(), bound, out_off.data_ptr(), scratch.data_ptr(), scratch.numel(), d.stream))
+        bad = ((offsets[1:] < offsets[:-1]).any() | (offsets[0] < 0) | (offsets[-1] > t.numel())).to(torch.int64).reshape(1)
+        total, bad = torch.cat([out_off[n:], bad]).tolist()
+        if bad:
+            raise ArgumentException(_p.BAD_OFFSETS)
+        return out[:total], out_off
+
+
+def decompress_frames_device(t, offsets, slot_bytes: int = 65536, verify: bool = True, round_blocks: int = 0, max_blocks=None):
+    """[decompress_frame_device(item) for item in items] for items of ONE frame each, t[offsets[i]:offsets[i + 1]] of a 1-D uint8 CUDA
+    tensor, in one call on the device, on torch's current stream -> (data, data_offsets).  Every item's size fields are walked by a
+    wavefront of its own, the blocks of all items are one table of the block decoder, the content checksums n rows of one launch.
+    slot_bytes bounds every item's block maximum (65536, 262144, 1048576 or 4194304): an item with larger blocks fails with "the frame's
+    block maximum exceeds the slot".  max_blocks is the table's size for the whole batch (default: a guess from the bytes); a table
+    that was too small, or an output that outgrew the guess of four times the input, is decoded once more from the record.  A skippable
+    item gives no bytes; what lies behind an item's frame is left alone.  round_blocks = K > 0 decodes K blocks at a time through a
+    ring of K slots instead of one slot per table row.  Raises the first failing item's ArgumentException, its index in .item."""
+    t, offsets = _p.check_device_batch(t, offsets)
+    flags = _verify_flags(verify)
+    if int(slot_bytes) not in BLOCK_SIZES:
+        raise ArgumentException("slot_bytes must be 65536, 262144, 1048576 or 4194304")
+    with _p.DeviceCall(t) as d:
+        n = offsets.numel() - 1
+        out_off, items_dev = d.i64(n + 1), d.u8(C.sizeof(_lib.Lz4fInfo) * max(n, 1), zero=True)
+        info_dev, written = d.record(_lib.Lz4fBatchInfo), d.i64(1, zero=True)
+
+        def decode(guess):
+            rows, out_bytes = guess
+            need = _lib.check(d.lib.lz4hip_lz4f_batch_decode_scratch_bytes(n, slot_bytes, rows, round_blocks))
+            scratch, out = d.u8(max(need, 1)), d.u8(out_bytes)
+            _lib.check(d.lib.lz4hip_lz4f_batch_decode_device(t.data_ptr(), t.numel(), offsets.data_ptr(), n, slot_bytes, rows, round_blocks, flags,
+                                                             scratch.data_ptr(), need, out.data_ptr(), out_bytes, out_off.data_ptr(),
+                                                             items_dev.data_ptr(), info_dev.data_ptr(), written.data_ptr(), d.stream))
+            info = _p.read_record(info_dev, _lib.Lz4fBatchInfo)
+            return (out, info), _p.table_or_output(info, "blocks", _lib.LZ4F_TABLE_FULL, guess)
+
+        rows = int(max_blocks) if max_blocks is not None else t.numel() // 16384 + n + 16
+        (out, info), (rows, out_bytes) = _p.settle(3, (rows, 4 * t.numel()), decode)
+        if info.error == _lib.LZ4F_TABLE_FULL or info.decoded_bytes > out_bytes:
+            raise _lib.Lz4HipError("lz4 frame batch decode: the size field walks did not settle")
+        if info.first_error >= 0:
+            raise _item_error(info)
+        return out[:int(info.decoded_bytes)], out_off
+
+
+def compress_frames_host(buf, offsets, block_size: int = 65536, high_compression: bool = False, block_checksum: bool = False,
+                         content_checksum: bool = False, content_size: bool = True):
+    """compress_frames_device for host arrays, through lz4hip_lz4f_batch_encode_host -> (frames, frame_offsets) as numpy arrays."""
+    buf, offsets = _p.check_host_batch(buf, offsets)
+    bid, flags = _block_id(block_size), _encode_flags(block_checksum, content_checksum, content_size)
+    n = offsets.size - 1
+    if n and ((np.diff(offsets) < 0).any() or offsets[0] < 0 or offsets[-1] > buf.size):
+        raise ArgumentException(_p.BAD_OFFSETS)
+    L = _lib.lib()
+    bound = L.lz4hip_lz4f_batch_bound(n, buf.size, bid, flags)
+    out = np.empty(max(bound, 1), np.uint8)
+    out_off = np.empty(n + 1, np.int64)
+    _lib.check(L.lz4hip_lz4f_batch_encode_host(buf.ctypes.data, buf.size, offsets.ctypes.data, n, bid, _p.mode(high_compression), flags,
+                                               out.ctypes.data, bound, out_off.ctypes.data))
+    return out[:int(out_off[n])], out_off
+
+
+def decompress_frames_host(packed, offsets, verify: bool = True):
+    """decompress_frames_device for host arrays, through lz4hip_lz4f_batch_decode_host: a size query (dst_cap = 0), then the call that
+    decodes into exactly that size -> (data, data_offsets) as numpy arrays.  The slots take the largest block maximum among the items'
+    descriptors.  Raises the first failing item's ArgumentException, its index in .item."""
+    packed, offsets = _p.check_host_batch(packed, offsets)
+    n = offsets.size - 1
+    if n and ((np.diff(offsets) < 0).any() or offsets[0] < 0 or offsets[-1] > packed.size):
+        raise ArgumentException(_p.BAD_OFFSETS)
+    flags = _verify_flags(verify)
+    L = _lib.lib()
+    out_off = np.zeros(n + 1, np.int64)
+    items = (_lib.Lz4fInfo * max(n, 1))()
+    info = _lib.Lz4fBatchInfo()
+    out = _p.sized_decode_host(lambda dst, dst_cap: L.lz4hip_lz4f_batch_decode_host(
+        packed.ctypes.data, packed.size, offsets.ctypes.data, n, flags, dst, dst_cap, out_off.ctypes.data, items, C.byref(info)), info,
+        after_e_argument_only=True)
+    if info.first_error >= 0:
+        raise _item_error(info)
+    return out, out_off
