@@ -146,6 +146,11 @@ namespace LZ4hip
         private static extern unsafe int lz4hip_lz4f_batch_encode_host(byte* src, long srcLen, long* srcOff, long n, int blockSizeId, int mode, uint flags,
                                                                        byte* dst, long dstCap, long* dstOff);
 
+        /// <summary>Decode flags of lz4hip_lz4f_batch_decode_host (LZ4HIP_LZ4F_VERIFY_BLOCKS, _VERIFY_CONTENT, _ACCEPT_LINKED).
+        /// Lz4fAcceptLinked decodes items whose blocks are linked (LZ4F_compressFrame's default above one block) instead of failing
+        /// them with UNSUPPORTED_LINKED; each such item is one serial chain on ONE wavefront, so it pays only in batches of many items.</summary>
+        public const uint Lz4fVerifyBlocks = 1, Lz4fVerifyContent = 2, Lz4fAcceptLinked = 8;
+
         // returns 0, the first failing item's LZ4HIP_LZ4F_* code, or LZ4HIP_E_*; dstCap = 0 is a size query: LZ4HIP_E_ARGUMENT with dstOff,
         // itemInfo and *info filled in
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]

@@ -682,6 +682,28 @@ int lz4hip_xxh32_rows_device(const void* data, const int64_t* off, int64_t strid
 /* Decode flags: which of the checksums the frame carries are verified */
 #define LZ4HIP_LZ4F_VERIFY_BLOCKS    1u
 #define LZ4HIP_LZ4F_VERIFY_CONTENT   2u   /* one serial row over dst[0, decoded_bytes): only when all of it was written and no block is bad */
+/* ... and an opt-in of the four decode calls (lz4hip_lz4f_decode_* and lz4hip_lz4f_batch_decode_*): frames whose blocks are LINKED
+ * (FLG.5 clear -- the default of LZ4F_compressFrame, python-lz4 and Arrow's LZ4_FRAME codec for content above one block) are decoded
+ * instead of refused with UNSUPPORTED_LINKED.  Without the flag every call is what it was; dictionaries stay refused either way.
+ * COST: a linked frame is ONE serial chain and runs on ONE wavefront, so one large linked frame decodes far slower than on a host core
+ * (INTEGRATION.md 4 has a lone wavefront's figures).  The flag pays only in batches of many items, one wavefront each.  With it:
+ *  - an independent frame or item takes the path it always took: the same bytes, the same record;
+ *  - a linked one yields what a sequential reader (LZ4F_decompress) yields.  A match may start anywhere in the bytes of the SAME frame
+ *    already produced, earlier blocks (stored-raw ones included) up to 65 535 back, never before the frame's first output byte
+ *    whatever dst holds there: that is a corrupt block;
+ *  - the first bad block ends a linked item, as it ends a sequential read.  A block known bad before the layout -- a checksum mismatch
+ *    under VERIFY_BLOCKS, a size walk that fails, a size above the frame's block maximum -- takes 0 bytes and so does every block of
+ *    the item behind it: BLOCK_CHECKSUM_ERROR or CORRUPT_BLOCK at that block's size field, good_bytes what lay before it.  A block
+ *    that walks to a size but that the decoder then refuses (a match that starts before the frame; the end rules broken at its own
+ *    size, the caveat of the two-call legacy frame path above) KEEPS its place: CORRUPT_BLOCK at its size field, good_bytes the
+ *    item's bytes before it, the item's blocks behind it not touched, the item's bytes from good_bytes on unspecified.  No other item's
+ *    bytes or record are disturbed.  Such a block is only found when it is reached: not behind the dst_cap clip, so not in a size query;
+ *  - dst_cap clips a linked item at a BLOCK boundary: its blocks that lie wholly inside dst_cap are written, the first one that does
+ *    not and those behind it are not (an independent item keeps the byte-exact clip).  Nothing at or past dst_cap is written; offsets,
+ *    sizes and decoded_bytes are complete either way, dst_cap = 0 is the size query, written_items and "present but not checked" are
+ *    as ever; VERIFY_CONTENT covers linked items;
+ *  - the *_decode_scratch_bytes values include one more int32 per table row, flag or no flag. */
+#define LZ4HIP_LZ4F_ACCEPT_LINKED    8u   /* (4u is not a decode flag and stays refused as an unknown one, as callers have pinned it) */
 /* Outcomes (lz4hip_lz4f_info_t.error).  Precedence, as a sequential reader meets them: TABLE_FULL; a descriptor error (no block is
  * walked then); the lowest bad block (BLOCK_CHECKSUM_ERROR / CORRUPT_BLOCK, at its size field); the walk's error (TRUNCATED /
  * BAD_BLOCK_SIZE: it lies after every tabled block); CONTENT_SIZE_ERROR; CONTENT_CHECKSUM_ERROR. */
@@ -689,7 +711,7 @@ int lz4hip_xxh32_rows_device(const void* data, const int64_t* off, int64_t strid
 #define LZ4HIP_LZ4F_BAD_MAGIC              1   /* fewer than 4 bytes, or neither the frame magic nor a skippable one */
 #define LZ4HIP_LZ4F_BAD_HEADER             2   /* version, a reserved bit, or a block size id below 4 */
 #define LZ4HIP_LZ4F_HEADER_CHECKSUM        3
-#define LZ4HIP_LZ4F_UNSUPPORTED_LINKED     4   /* FLG.5 clear: linked blocks decode only in order, each against the 64 KiB before it */
+#define LZ4HIP_LZ4F_UNSUPPORTED_LINKED     4   /* FLG.5 clear: linked blocks decode only in order, each against the 64 KiB before it (LZ4HIP_LZ4F_ACCEPT_LINKED takes them) */
 #define LZ4HIP_LZ4F_UNSUPPORTED_DICT       5   /* FLG.0 set */
 #define LZ4HIP_LZ4F_SLOT_TOO_SMALL         6   /* the frame's block maximum exceeds slot_bytes: call again with .block_max */
 #define LZ4HIP_LZ4F_TRUNCATED              7   /* the frame ends inside the descriptor, a size field, data, a checksum, or before its EndMark */
@@ -749,7 +771,8 @@ int lz4hip_lz4f_decode_host(const void* src, int64_t src_len, unsigned flags, vo
  * launch-only on the caller's stream, no device value read on the host, no allocation, scratch from the caller (the *_scratch_bytes
  * queries), arguments checked before the device is looked for, 0 or LZ4HIP_E_* returned.
  *
- * Out of scope: frames with linked blocks or a dictionary (the item's outcome says so); following appended frames inside one item (an
+ * Out of scope: frames with a dictionary (the item's outcome says so; frames with linked blocks are the caller's choice:
+ * LZ4HIP_LZ4F_ACCEPT_LINKED); following appended frames inside one item (an
  * item is ONE frame, what lies behind it is left alone and shows only in frame_bytes); span forms (chosen items of an arena); a block
  * decoder for large blocks -- one wavefront still decodes one block.
  *
@@ -765,7 +788,7 @@ int lz4hip_lz4f_batch_encode_device(const void* src, int64_t src_len, const int6
 
 /* Decode: ONE frame per item.  item_info[n] (device) receives one lz4hip_lz4f_info_t per item, and dst[dst_off[i], dst_off[i + 1]) its
  * bytes: what lz4hip_lz4f_decode_device gives for that item alone with a table and a dst_cap that hold it, every field, offsets relative
- * to the item's start -- a skippable item (kind, 0 bytes), UNSUPPORTED_LINKED, UNSUPPORTED_DICT and SLOT_TOO_SMALL as the ITEM's outcome,
+ * to the item's start -- a skippable item (kind, 0 bytes), UNSUPPORTED_LINKED (without LZ4HIP_LZ4F_ACCEPT_LINKED), UNSUPPORTED_DICT and SLOT_TOO_SMALL as the ITEM's outcome,
  * trailing bytes behind frame_bytes left alone.  A failing item never disturbs another item's bytes or record; an item whose offsets
  * decrease or leave [0, src_len] gets error = LZ4HIP_E_ARGUMENT and 0 bytes.  The walks run one wavefront per item, the content
  * checksums as n rows of one checksum launch.

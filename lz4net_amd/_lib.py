@@ -93,7 +93,7 @@ class Lz4fBatchInfo(C.Structure):
  LZ4F_TRUNCATED, LZ4F_BAD_BLOCK_SIZE, LZ4F_CORRUPT_BLOCK, LZ4F_BLOCK_CHECKSUM_ERROR, LZ4F_CONTENT_SIZE_ERROR, LZ4F_CONTENT_CHECKSUM_ERROR,
  LZ4F_TABLE_FULL) = range(14)
 LZ4F_BLOCK_CHECKSUM, LZ4F_CONTENT_CHECKSUM, LZ4F_CONTENT_SIZE = 1, 2, 4
-LZ4F_VERIFY_BLOCKS, LZ4F_VERIFY_CONTENT = 1, 2
+LZ4F_VERIFY_BLOCKS, LZ4F_VERIFY_CONTENT, LZ4F_ACCEPT_LINKED = 1, 2, 8
 LZ4F_KIND_FRAME, LZ4F_KIND_SKIPPABLE = 0, 1
 LZ4F_CHECK_ABSENT, LZ4F_CHECK_VERIFIED, LZ4F_CHECK_SKIPPED = 0, 1, 2
 

@@ -149,8 +149,11 @@ constexpr int kWaveRingBytes = 4096;     // LDS mirror of a wavefront's most rec
 constexpr int kWaveBurstRecBytes = 1024; // ... followed by the burst's sequence records (at most 64 x 8 bytes)
 constexpr int kWaveLdsBytes = kWaveRingBytes + kWaveBurstRecBytes;
 
-template <bool KNOWN>
-LZ4HIP_DEVICE int decode_block(const uint8_t* src, int src_len, uint8_t* dst, int out_size, unsigned char* ring)
+// HISTORY: the `history` bytes before dst exist and a match may start in them (a linked block of an LZ4 frame: lz4hip_lz4f_linked.hpp).
+// Only the general path knows them: the burst and the short path leave a source before the block to it, as they leave an error, it
+// reads dst at indices below 0, and the LDS mirror never holds bytes before the block.  Without HISTORY the argument is not looked at.
+template <bool KNOWN, bool HISTORY = false>
+LZ4HIP_DEVICE int decode_block(const uint8_t* src, int src_len, uint8_t* dst, int out_size, unsigned char* ring, int history = 0)
 {
     const int lane = wv::lane();
     const int iend = src_len, oend = out_size;
@@ -351,7 +354,7 @@ LZ4HIP_DEVICE int decode_block(const uint8_t* src, int src_len, uint8_t* dst, in
         const int off = (int)(win.peek(p) | (win.peek(p + 1) << 8));
         p += 2;
         const int ref = lit_end - off;
-        if (ref < 0) return -p;
+        if (ref < (HISTORY ? -history : 0)) return -p;
         int ml = (int)(token & 15);
         if (ml == 15) {
             if (KNOWN) {

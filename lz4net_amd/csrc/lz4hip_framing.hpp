@@ -31,6 +31,7 @@
 #include "lz4hip_compact.hpp"
 #include "lz4hip_lz4f.hpp"
 #include "lz4hip_lz4f_batch.hpp"
+#include "lz4hip_lz4f_linked.hpp"
 
 #include "../../include/lz4hip.h"
 
@@ -1510,7 +1511,8 @@ int frame_decode_compact(B& be, const void* src, int64_t src_len, int32_t chunk_
 // ---- xxHash32 of rows, and LZ4 frames (lz4hip_lz4f.hpp) ----------------------------------------------------------------------------------
 static_assert(kLz4fBlockChecksum == LZ4HIP_LZ4F_BLOCK_CHECKSUM && kLz4fContentChecksum == LZ4HIP_LZ4F_CONTENT_CHECKSUM &&
               kLz4fContentSize == LZ4HIP_LZ4F_CONTENT_SIZE && kLz4fVerifyBlocks == LZ4HIP_LZ4F_VERIFY_BLOCKS &&
-              kLz4fVerifyContent == LZ4HIP_LZ4F_VERIFY_CONTENT && kLz4fKindSkippable == LZ4HIP_LZ4F_KIND_SKIPPABLE, "lz4f flags");
+              kLz4fVerifyContent == LZ4HIP_LZ4F_VERIFY_CONTENT && kLz4fAcceptLinked == LZ4HIP_LZ4F_ACCEPT_LINKED &&
+              kLz4fKindSkippable == LZ4HIP_LZ4F_KIND_SKIPPABLE, "lz4f flags");
 static_assert(kLz4fOk == LZ4HIP_LZ4F_OK && kLz4fBadMagic == LZ4HIP_LZ4F_BAD_MAGIC && kLz4fBadHeader == LZ4HIP_LZ4F_BAD_HEADER &&
               kLz4fHeaderChecksum == LZ4HIP_LZ4F_HEADER_CHECKSUM && kLz4fUnsupportedLinked == LZ4HIP_LZ4F_UNSUPPORTED_LINKED &&
               kLz4fUnsupportedDict == LZ4HIP_LZ4F_UNSUPPORTED_DICT && kLz4fSlotTooSmall == LZ4HIP_LZ4F_SLOT_TOO_SMALL &&
@@ -1665,7 +1667,36 @@ int lz4f_encode(B& be, const void* src, int64_t src_len, int block_size_id, int 
 // max_blocks rows of slot_bytes
 inline bool lz4f_slot_valid(int32_t slot_bytes) { return slot_bytes == 0 || slot_bytes == 65536 || slot_bytes == 262144 || slot_bytes == 1048576 || slot_bytes == 4194304; }
 inline int32_t lz4f_slot(int32_t slot_bytes) { return slot_bytes == 0 ? 4194304 : slot_bytes; }                    // (of a valid slot_bytes)
-constexpr unsigned kLz4fDecodeFlags = kLz4fVerifyBlocks | kLz4fVerifyContent;
+constexpr unsigned kLz4fDecodeFlags = kLz4fVerifyBlocks | kLz4fVerifyContent | kLz4fAcceptLinked;
+
+// ---- frames with linked blocks (lz4hip_lz4f_linked.hpp), for both decode sequences below ------------------------------------------------
+// one lane per table row in single-wavefront workgroups; one wavefront per item in workgroups of kWaveDecodeWavesPerGroup: more rows
+// or items than the grid holds share lanes and wavefronts
+inline Grid lz4f_linked_rows_grid(int64_t rows)
+{
+    const int64_t g = (rows + kSizesThreads - 1) / kSizesThreads;
+    return { g < 1 ? 1u : (g > (int64_t)kStreamsMaxWalkGroups ? kStreamsMaxWalkGroups : (unsigned)g), kGridItems };
+}
+inline Grid lz4f_linked_items_grid(int64_t n)
+{
+    const int64_t g = (n + kWaveDecodeWavesPerGroup - 1) / kWaveDecodeWavesPerGroup;
+    return { g < 1 ? 1u : (g > (int64_t)kStreamsMaxWalkGroups ? kStreamsMaxWalkGroups : (unsigned)g), kGridWalk };
+}
+// before the rounds (and after the block checksums and the fill of the lowest bad rows): every linked row's size, every linked item's plan
+template <class B>
+int lz4f_linked_plan_run(B& be, const Lz4fLinked& a)
+{
+    be.launch(lz4f_linked_sizes_kernel, lz4f_linked_rows_grid(a.max_blocks), kSizesThreads, a);
+    be.launch(lz4f_linked_plan_kernel, stream_grid(a.n), kStreamThreads, a);
+    return be.last_error();
+}
+// after the last round, before the records: the linked items, one wavefront each
+template <class B>
+int lz4f_linked_decode_run(B& be, const Lz4fLinked& a)
+{
+    be.launch(lz4f_linked_decode_kernel, lz4f_linked_items_grid(a.n), 64 * kWaveDecodeWavesPerGroup, a);
+    return be.last_error();
+}
 
 inline Lz4fTables lz4f_tables(Carver& c, int64_t max_blocks)
 {
@@ -1681,6 +1712,7 @@ inline Lz4fTables lz4f_tables(Carver& c, int64_t max_blocks)
     t.result = c.take_as<int32_t>(4 * max_blocks);
     t.sums = c.take_as<uint32_t>(4 * (max_blocks + 1));
     t.row = c.take_as<uint8_t>(max_blocks);
+    t.plan = c.take_as<int32_t>(4 * max_blocks);
     return t;
 }
 struct Lz4fDecodeScratch { Lz4fTables t; PackedScratch l; int64_t bytes; };
@@ -1707,7 +1739,8 @@ struct Lz4fDecodePlan {
 // The walk, the block checksums, then packed_rounds_run's rounds over ALL max_blocks rows of the table with the twin sizes step and pack
 // layout (the rows past the walk's count are empty blocks, which decode to nothing), the record, the content checksum.  Nothing is
 // read on the host between the steps.  The decoders are handed the table's dec_len column through the round's sanitised copy: a raw
-// row and a row with a bad checksum arrive as empty blocks.
+// row and a row with a bad checksum arrive as empty blocks, and so does every row of a frame with linked blocks, which a caller who
+// accepts them (kLz4fAcceptLinked) gets sized before the rounds and decoded after them, as the batch of one item.
 template <class B>
 int lz4f_decode_run(B& be, const Lz4fDecodePlan& p)
 {
@@ -1718,7 +1751,7 @@ int lz4f_decode_run(B& be, const Lz4fDecodePlan& p)
     LZ4HIP_FRAMING_TRY(be.fill(t.dec_len, 0, (size_t)(4 * n)));
     LZ4HIP_FRAMING_TRY(be.fill(t.sum_len, 0, (size_t)(4 * n)));
     LZ4HIP_FRAMING_TRY(be.fill(t.row, 0, (size_t)n));
-    be.launch(lz4f_walk_kernel, fixed_grid(1), 64, p.src, p.src_len, p.slot_bytes, t);
+    be.launch(lz4f_walk_kernel, fixed_grid(1), 64, p.src, p.src_len, p.slot_bytes, p.flags, t);
     LZ4HIP_FRAMING_TRY(be.last_error());
     if (p.flags & kLz4fVerifyBlocks) {
         const XxhRows rows = { p.src, t.src_off, 0, t.sum_len, nullptr, 0, 0u, t.sums, n };
@@ -1727,6 +1760,9 @@ int lz4f_decode_run(B& be, const Lz4fDecodePlan& p)
     }
     LZ4HIP_FRAMING_TRY(be.fill(p.l.state, 0, (size_t)kPackedStateBytes));
     LZ4HIP_FRAMING_TRY(be.fill(p.l.state + kPackedBad, 0xFF, 8));      // the lowest bad block = none
+    const Lz4fLinked linked = { p.src, p.dst, p.dst_cap, 1, n, t.walk, nullptr, nullptr, t.src_off, t.stored, t.dst_off, t.row, t.plan,
+                                (unsigned long long*)(p.l.state + kPackedBad) };
+    if (p.flags & kLz4fAcceptLinked) LZ4HIP_FRAMING_TRY(lz4f_linked_plan_run(be, linked));
     const Grid pack_grid = copy_grid(p.round * p.slot);
     int32_t parity = 0;
     for (int64_t first = 0; first < n; first += p.round, parity ^= 1) {
@@ -1742,7 +1778,7 @@ int lz4f_decode_run(B& be, const Lz4fDecodePlan& p)
         rb.dst = p.l.ring; rb.dst_stride = p.slot; rb.dst_cap = p.l.caps;
         rb.result = a.result; rb.n_blocks = a.cnt;
         LZ4HIP_FRAMING_TRY(be.decode(&rb, 0));
-        const Lz4fRound r = { a, p.src, t.src_off + first, t.stored + first, t.row + first, t.walk };
+        const Lz4fRound r = { a, p.src, t.src_off + first, t.stored + first, t.row + first, t.walk, t.plan + first };
         be.launch(lz4f_round_sizes_kernel, stream_grid(a.cnt), kStreamThreads, r);
         launch_scan(be, a.offs, a.cnt, p.l.partial, p.l.state + kPackedTotal);
         be.launch(packed_rebase_kernel, stream_grid(a.cnt), kStreamThreads, a);
@@ -1750,6 +1786,7 @@ int lz4f_decode_run(B& be, const Lz4fDecodePlan& p)
         be.launch(lz4f_round_pack_kernel, pack_grid, kStreamThreads, layout, p.dst, p.dst_cap);
         LZ4HIP_FRAMING_TRY(be.last_error());
     }
+    if (p.flags & kLz4fAcceptLinked) LZ4HIP_FRAMING_TRY(lz4f_linked_decode_run(be, linked));
     be.launch(lz4f_info_kernel, fixed_grid(1), 64, t, (const int64_t*)(p.l.state + kPackedBad), p.flags, p.dst_cap, p.info);
     if (p.flags & kLz4fVerifyContent) {
         const XxhRows content = { p.dst, nullptr, 0, nullptr, t.walk + kLz4fWalkContentLen, 0, 0u, t.sums + n, 1 };
@@ -1941,6 +1978,7 @@ inline Lz4fBatchTables lz4f_batch_tables(Carver& c, int64_t n, int64_t max_block
     t.item = c.take_as<int32_t>(4 * max_blocks);
     t.sums = c.take_as<uint32_t>(4 * max_blocks);
     t.row = c.take_as<uint8_t>(max_blocks);
+    t.plan = c.take_as<int32_t>(4 * max_blocks);
     return t;
 }
 struct Lz4fBatchDecodeScratch { Lz4fBatchTables t; int64_t* partial; PackedScratch l; int64_t bytes; };
@@ -1966,6 +2004,7 @@ struct Lz4fBatchDecodePlan {
 
 // The two walks around their scan, the block checksums, then lz4f_decode_run's rounds over ALL max_blocks rows of the table with the
 // batch's sizes step and pack layout, the items' records, their content checksums as n rows of one launch, the batch's record.
+// With kLz4fAcceptLinked the linked items' rows are sized before the rounds and decoded after them (lz4hip_lz4f_linked.hpp).
 // Nothing is read on the host between the steps.
 template <class B>
 int lz4f_batch_decode_run(B& be, const Lz4fBatchDecodePlan& p)
@@ -1999,6 +2038,8 @@ int lz4f_batch_decode_run(B& be, const Lz4fBatchDecodePlan& p)
     }
     LZ4HIP_FRAMING_TRY(be.fill(p.l.state, 0, (size_t)kPackedStateBytes));
     LZ4HIP_FRAMING_TRY(be.fill(p.l.state + kPackedBad, 0xFF, 8));
+    const Lz4fLinked linked = { a.src, p.dst, a.dst_cap, a.n, m, t.walk, t.base, t.total, t.src_off, t.stored, t.dst_off, t.row, t.plan, t.item_bad };
+    if (a.flags & kLz4fAcceptLinked) LZ4HIP_FRAMING_TRY(lz4f_linked_plan_run(be, linked));
     const Grid pack_grid = copy_grid(p.round * p.slot);
     int32_t parity = 0;
     for (int64_t first = 0; first < m; first += p.round, parity ^= 1) {
@@ -2014,7 +2055,7 @@ int lz4f_batch_decode_run(B& be, const Lz4fBatchDecodePlan& p)
         rb.dst = p.l.ring; rb.dst_stride = p.slot; rb.dst_cap = p.l.caps;
         rb.result = r.result; rb.n_blocks = r.cnt;
         LZ4HIP_FRAMING_TRY(be.decode(&rb, 0));
-        const Lz4fBatchRound br = { r, a.src, t.src_off + first, t.stored + first, t.row + first, t.item + first, t.walk, t.item_bad };
+        const Lz4fBatchRound br = { r, a.src, t.src_off + first, t.stored + first, t.row + first, t.item + first, t.walk, t.item_bad, t.plan + first };
         be.launch(lz4f_batch_round_sizes_kernel, stream_grid(r.cnt), kStreamThreads, br);
         launch_scan(be, r.offs, r.cnt, p.l.partial, p.l.state + kPackedTotal);
         be.launch(packed_rebase_kernel, stream_grid(r.cnt), kStreamThreads, r);
@@ -2022,6 +2063,7 @@ int lz4f_batch_decode_run(B& be, const Lz4fBatchDecodePlan& p)
         be.launch(lz4f_batch_round_pack_kernel, pack_grid, kStreamThreads, layout, p.dst, a.dst_cap);
         LZ4HIP_FRAMING_TRY(be.last_error());
     }
+    if (a.flags & kLz4fAcceptLinked) LZ4HIP_FRAMING_TRY(lz4f_linked_decode_run(be, linked));
     be.launch(lz4f_batch_offsets_out_kernel, stream_grid(a.n + 1), kStreamThreads, a, t);
     be.launch(lz4f_batch_info_kernel, stream_grid(a.n), kStreamThreads, a, t);
     if (a.flags & kLz4fVerifyContent) {

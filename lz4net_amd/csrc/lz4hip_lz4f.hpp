@@ -22,9 +22,10 @@
 //             its payload the SOURCE, not the ring; the decoder sees it as an empty row -> lz4f_info_kernel -> [xxh32_rows_kernel, one
 //             row over the output] -> lz4f_final_kernel
 //
-// The encoder's blocks are always independent (FLG.5) and use no dictionary; the decoder refuses linked blocks -- each decodes only
-// against the 64 KiB before it, in order, so there is nothing to batch -- and dictionaries.  Every kernel here is launch-only work on the caller's stream over
-// caller scratch.
+// The encoder's blocks are always independent (FLG.5) and use no dictionary; the decoder refuses dictionaries, and linked blocks unless
+// the caller accepts them (kLz4fAcceptLinked): each decodes only against the 64 KiB before it, in order, so a linked frame is one
+// serial chain -- lz4hip_lz4f_linked.hpp runs it on one wavefront, after the rounds, which see its rows as holes.  Every kernel here
+// is launch-only work on the caller's stream over caller scratch.
 #pragma once
 #include "lz4hip_packed.hpp"
 
@@ -331,9 +332,12 @@ constexpr int kLz4fOk = 0, kLz4fBadMagic = 1, kLz4fBadHeader = 2, kLz4fHeaderChe
               kLz4fSlotTooSmall = 6, kLz4fTruncated = 7, kLz4fBadBlockSize = 8, kLz4fCorruptBlock = 9, kLz4fBlockChecksumError = 10,
               kLz4fContentSizeError = 11, kLz4fContentChecksumError = 12, kLz4fTableFull = 13;
 constexpr unsigned kLz4fVerifyBlocks = 1, kLz4fVerifyContent = 2;       // LZ4HIP_LZ4F_VERIFY_* (include/lz4hip.h)
+constexpr unsigned kLz4fAcceptLinked = 8;                               // LZ4HIP_LZ4F_ACCEPT_LINKED
 constexpr int kLz4fKindFrame = 0, kLz4fKindSkippable = 1;
 constexpr int kLz4fCheckAbsent = 0, kLz4fCheckVerified = 1, kLz4fCheckSkipped = 2;   // info.checks: bits 0-1 the blocks', bits 2-3 the content's
 constexpr uint8_t kLz4fRowRaw = 1, kLz4fRowBadSum = 2;
+// a row of a frame with linked blocks: the rounds see a hole of its planned size; a dead one lies at or behind its item's first bad block
+constexpr uint8_t kLz4fRowLinked = 4, kLz4fRowDead = 8;
 
 // Device twin of lz4hip_lz4f_info_t (include/lz4hip.h; the API checks that the layouts agree).
 struct Lz4fInfo {
@@ -357,6 +361,7 @@ struct Lz4fTables {
     uint32_t* sums;                                                    // max_blocks block checksums as computed, then the content's
     uint8_t* row;                                                      // kLz4fRow* bits
     int64_t* walk;                                                     // kLz4fWalk* slots
+    int32_t* plan;                                                     // a linked row's size, known before the rounds (lz4hip_lz4f_linked.hpp)
 };
 
 // what one walk found: the kLz4fWalk* slots before they are stored
@@ -366,15 +371,20 @@ struct Lz4fWalk {
     int32_t block_max;
 };
 
+// A row as the walk leaves it: its bits, and the length the ring decoder is handed -- 0 for a raw row and for a linked one, which it
+// sees as empty rows
+LZ4HIP_DEVICE uint8_t lz4f_row_bits(bool raw, bool linked) { return (uint8_t)((raw ? kLz4fRowRaw : 0) | (linked ? kLz4fRowLinked : 0)); }
+LZ4HIP_DEVICE int32_t lz4f_row_dec_len(uint8_t bits, int32_t size) { return bits ? 0 : size; }
+
 // The walk over ONE frame at src[0, src_len), by every lane of a wavefront on the same (wave-uniform) position; it writes nothing itself:
-// row(k, pos, size, raw, sum_bytes) is called for data block k, whose size field lies at pos.  lz4f_walk_kernel and the batch's walk
+// row(k, pos, size, bits, sum_bytes) is called for data block k, whose size field lies at pos (bits: lz4f_row_bits).  lz4f_walk_kernel and the batch's walk
 // (lz4hip_lz4f_batch.hpp) are this walk with their own rows.  The descriptor's checks come in
 // the order a sequential reader applies them: version, reserved bits and block size id; the descriptor's length against the frame's;
-// HC; then what this decoder does not take (a dictionary ID, linked blocks, a block maximum above the caller's slot).  With a
-// descriptor error no block is walked.  Per size field: the EndMark (and the content checksum behind it), the size against the
-// frame's block maximum, then the data and its checksum against the end of the frame.
+// HC; then what this decoder does not take (a dictionary ID, linked blocks unless `flags` has kLz4fAcceptLinked, a block maximum above
+// the caller's slot).  With a descriptor error no block is walked.  Per size field: the EndMark (and the content checksum behind it),
+// the size against the frame's block maximum, then the data and its checksum against the end of the frame.
 template <class Row>
-LZ4HIP_DEVICE Lz4fWalk lz4f_walk_frame(const uint8_t* src, int64_t src_len, int32_t slot_bytes, Row row)
+LZ4HIP_DEVICE Lz4fWalk lz4f_walk_frame(const uint8_t* src, int64_t src_len, int32_t slot_bytes, unsigned flags, Row row)
 {
     int64_t pos = 0, blocks = 0, err_off = -1, content_size = -1, trailer = -1;
     int err = kLz4fOk, kind = kLz4fKindFrame, flg = 0, bd = 0;
@@ -400,7 +410,7 @@ LZ4HIP_DEVICE Lz4fWalk lz4f_walk_frame(const uint8_t* src, int64_t src_len, int3
             block_max = lz4f_block_bytes(id);
             if (flg & 0x08) content_size = (int64_t)wv::uniform(load_u64(src + 6));
             if (flg & 0x01) { err = kLz4fUnsupportedDict; err_off = 4; }
-            else if (!(flg & 0x20)) { err = kLz4fUnsupportedLinked; err_off = 4; }
+            else if (!(flg & 0x20) && !(flags & kLz4fAcceptLinked)) { err = kLz4fUnsupportedLinked; err_off = 4; }
             else if (block_max > slot_bytes) { err = kLz4fSlotTooSmall; err_off = 5; }
             pos = 4 + dlen;
         }
@@ -420,7 +430,7 @@ LZ4HIP_DEVICE Lz4fWalk lz4f_walk_frame(const uint8_t* src, int64_t src_len, int3
             const int64_t size = (int64_t)(field & ~kLz4fRawBit);
             if (size > block_max) { err = kLz4fBadBlockSize; err_off = pos; break; }
             if (pos + 4 + size + sum_bytes > src_len) { err = kLz4fTruncated; err_off = pos; break; }
-            row(blocks, pos, (int32_t)size, (field & kLz4fRawBit) != 0, (int32_t)sum_bytes);
+            row(blocks, pos, (int32_t)size, lz4f_row_bits((field & kLz4fRawBit) != 0, !(flg & 0x20)), (int32_t)sum_bytes);
             blocks++;
             pos += 4 + size + sum_bytes;
         }
@@ -441,16 +451,16 @@ LZ4HIP_DEVICE void lz4f_walk_store(int64_t* w, const Lz4fWalk& r, int64_t full_o
 
 // One wavefront; every lane runs the same walk on the same (wave-uniform) position and lane 0 writes: row k of the table for block k
 // while the table has rows, the record at the end.
-__global__ void __launch_bounds__(64) lz4f_walk_kernel(const uint8_t* src, int64_t src_len, int32_t slot_bytes, Lz4fTables t)
+__global__ void __launch_bounds__(64) lz4f_walk_kernel(const uint8_t* src, int64_t src_len, int32_t slot_bytes, unsigned flags, Lz4fTables t)
 {
     const int lane = wv::lane();
     int64_t full_off = -1;
-    const Lz4fWalk r = lz4f_walk_frame(src, src_len, slot_bytes, [&](int64_t k, int64_t pos, int32_t size, bool raw, int32_t sum_bytes) {
+    const Lz4fWalk r = lz4f_walk_frame(src, src_len, slot_bytes, flags, [&](int64_t k, int64_t pos, int32_t size, uint8_t bits, int32_t sum_bytes) {
         if (k < t.max_blocks) {
             if (lane == 0) {
                 t.src_off[k] = pos + 4; t.hdr_off[k] = pos; t.stored[k] = size;
-                t.dec_len[k] = raw ? 0 : size; t.sum_len[k] = sum_bytes ? size : 0;
-                t.row[k] = raw ? kLz4fRowRaw : 0;
+                t.dec_len[k] = lz4f_row_dec_len(bits, size); t.sum_len[k] = sum_bytes ? size : 0;
+                t.row[k] = bits;
             }
         } else if (k == t.max_blocks) {
             full_off = pos;
@@ -476,13 +486,16 @@ struct Lz4fRound {
     const uint8_t* src;
     const int64_t* src_off; const int32_t* stored; const uint8_t* row;
     const int64_t* walk;
+    const int32_t* plan;
 };
 
 // The bytes row k of the round takes, or -1 for a bad block: a row with a bad checksum; a raw row its stored size; a compressed row the
-// decoder's result, if it is one and within the FRAME's block maximum (it fits the slot either way).
+// decoder's result, if it is one and within the FRAME's block maximum (it fits the slot either way).  A linked row takes its planned
+// size (0 for a dead one; its item's bad block is the plan's to report).
 LZ4HIP_DEVICE int32_t lz4f_row_bytes(const Lz4fRound& r, int64_t k)
 {
     const uint8_t bits = r.row[k];
+    if (bits & kLz4fRowLinked) return r.plan[k];
     if (bits & kLz4fRowBadSum) return -1;
     if (bits & kLz4fRowRaw) return r.stored[k];
     const int32_t res = r.a.result[k];
@@ -499,7 +512,8 @@ __global__ void __launch_bounds__(kStreamThreads) lz4f_round_sizes_kernel(Lz4fRo
     }
 }
 
-// PackedLayout's twin: a raw row's payload lies in the source
+// PackedLayout's twin: a raw row's payload lies in the source; a linked row has none (its bytes up to the next row's start are the
+// linked decode's to write)
 struct Lz4fRoundLayout {
     Lz4fRound r;
     LZ4HIP_DEVICE int64_t count() const { return r.a.cnt; }
@@ -507,7 +521,7 @@ struct Lz4fRoundLayout {
     LZ4HIP_DEVICE CopySeg seg(int64_t k) const
     {
         CopySeg s;
-        const int32_t len = lz4f_row_bytes(r, k);
+        const int32_t len = (r.row[k] & kLz4fRowLinked) ? 0 : lz4f_row_bytes(r, k);
         s.start = s.pbegin = r.a.offs[k];
         s.pend = s.start + (len < 0 ? 0 : len);
         s.payload = (r.row[k] & kLz4fRowRaw) ? r.src + r.src_off[k] : r.a.ring + k * r.a.slot;

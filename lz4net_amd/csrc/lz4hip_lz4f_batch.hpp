@@ -16,7 +16,8 @@
 //           rows at the item's base with absolute source offsets and the item's index) -> [xxh32_rows_kernel over all rows +
 //           lz4f_batch_verify_kernel] -> the compact decode's rounds over ALL max_blocks rows (packed_caps_kernel, the block decoder,
 //           lz4f_batch_round_sizes_kernel, the scan, packed_rebase_kernel, lz4f_batch_round_pack_kernel): a round may begin and end in
-//           the middle of an item; the lowest bad row is kept PER ITEM -> lz4f_batch_offsets_out_kernel (dst_off) ->
+//           the middle of an item; the lowest bad row is kept PER ITEM -> [the linked items, each on one wavefront:
+//           lz4hip_lz4f_linked.hpp, which also sizes their rows before the rounds] -> lz4f_batch_offsets_out_kernel (dst_off) ->
 //           lz4f_batch_info_kernel (one thread per item: lz4f_info_kernel's precedence, the item's content row) -> xxh32_rows_kernel
 //           (n rows of the output) -> lz4f_batch_final_kernel -> lz4f_batch_record_kernel
 //
@@ -290,6 +291,7 @@ struct Lz4fBatchTables {
     unsigned long long* min_bad;                                       // the lowest failing item (~0: none)
     int64_t* content_off; int64_t* content_len;                        // the n rows of the content checksums in the output
     uint32_t* content_sums;
+    int32_t* plan;                                                     // a linked row's size, known before the rounds (lz4hip_lz4f_linked.hpp)
 };
 
 struct Lz4fBatchDecodeArgs {
@@ -320,12 +322,12 @@ __global__ void __launch_bounds__(64) lz4f_batch_walk_kernel(Lz4fBatchDecodeArgs
         const int64_t base = kFill ? t.base[i] : 0;
         Lz4fWalk r;
         if (valid) {
-            r = lz4f_walk_frame(a.src + at, len, a.slot_bytes, [&](int64_t k, int64_t pos, int32_t size, bool raw, int32_t sum_bytes) {
+            r = lz4f_walk_frame(a.src + at, len, a.slot_bytes, a.flags, [&](int64_t k, int64_t pos, int32_t size, uint8_t bits, int32_t sum_bytes) {
                 if (kFill && lane == 0 && base + k < t.max_blocks) {
                     const int64_t j = base + k;
                     t.src_off[j] = at + pos + 4; t.hdr_off[j] = pos; t.stored[j] = size;
-                    t.dec_len[j] = raw ? 0 : size; t.sum_len[j] = sum_bytes ? size : 0;
-                    t.row[j] = raw ? kLz4fRowRaw : 0; t.item[j] = (int32_t)i;
+                    t.dec_len[j] = lz4f_row_dec_len(bits, size); t.sum_len[j] = sum_bytes ? size : 0;
+                    t.row[j] = bits; t.item[j] = (int32_t)i;
                 }
             });
         } else {
@@ -357,12 +359,14 @@ struct Lz4fBatchRound {
     const int64_t* src_off; const int32_t* stored; const uint8_t* row; const int32_t* item;
     const int64_t* walk;
     unsigned long long* item_bad;
+    const int32_t* plan;
 };
 
 // lz4f_row_bytes with the block maximum of the ROW's item
 LZ4HIP_DEVICE int32_t lz4f_batch_row_bytes(const Lz4fBatchRound& r, int64_t k)
 {
     const uint8_t bits = r.row[k];
+    if (bits & kLz4fRowLinked) return r.plan[k];
     if (bits & kLz4fRowBadSum) return -1;
     if (bits & kLz4fRowRaw) return r.stored[k];
     const int32_t res = r.a.result[k];
@@ -386,7 +390,7 @@ struct Lz4fBatchRoundLayout {
     LZ4HIP_DEVICE CopySeg seg(int64_t k) const
     {
         CopySeg s;
-        const int32_t len = lz4f_batch_row_bytes(r, k);
+        const int32_t len = (r.row[k] & kLz4fRowLinked) ? 0 : lz4f_batch_row_bytes(r, k);   // (a linked row is a hole: Lz4fRoundLayout)
         s.start = s.pbegin = r.a.offs[k];
         s.pend = s.start + (len < 0 ? 0 : len);
         s.payload = (r.row[k] & kLz4fRowRaw) ? r.src + r.src_off[k] : r.a.ring + k * r.a.slot;

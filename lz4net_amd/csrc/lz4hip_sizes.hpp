@@ -94,8 +94,10 @@ struct SizesWindow {
     }
 };
 
-// the walk of one block; every lane has a block of its own (no collective operations: lanes finish when they finish)
-LZ4HIP_DEVICE int32_t decoded_size_block(const uint8_t* src, int64_t iend, uint32_t* col)
+// the walk of one block; every lane has a block of its own (no collective operations: lanes finish when they finish).  `history`: bytes
+// of output that exist before the block and that its matches may reach into -- 0 for a block that stands alone; the linked blocks of
+// an LZ4 frame (lz4hip_lz4f_linked.hpp) are sized with the format's 65 535, and their decoder checks the real history
+LZ4HIP_DEVICE int32_t decoded_size_block(const uint8_t* src, int64_t iend, uint32_t* col, int32_t history = 0)
 {
     if (iend == 0) return 0;
     if (iend < 0) return kSizesTooLarge;
@@ -133,7 +135,7 @@ LZ4HIP_DEVICE int32_t decoded_size_block(const uint8_t* src, int64_t iend, uint3
         if (token < 0x20u) o4 = t4 >> (8 * (1 + (int)ll));
         else { win.need(ip, 4); o4 = win.peek4(ip); }
         ip += 2;
-        if ((int64_t)(o4 & 0xFFFFu) > produced) return (int32_t)-ip;
+        if ((int64_t)(o4 & 0xFFFFu) > produced + history) return (int32_t)-ip;
         // ---- match length ----
         int64_t ml = token & 15u;
         if (ml == 15) {

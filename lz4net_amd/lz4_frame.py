@@ -6,9 +6,10 @@ K4os.Compression.LZ4.Streams and python-lz4 write and read.
     LE32 0 (EndMark)   [LE32 xxh32(content) if FLG.2]
 
 The blocks are the block format the library encodes and decodes anyway; the framing, the xxHash32 checksums and the packing run on
-the device (lz4hip_lz4f_* of include/lz4hip.h).  Frames written here hold independent blocks and no dictionary; frames with linked
-blocks (FLG.5 clear) or a dictionary ID are refused with a clear message, not decoded wrongly.  Skippable frames (magic 0x184D2A50 ..
-0x184D2A5F) are skipped, appended frames decoded one after the other.
+the device (lz4hip_lz4f_* of include/lz4hip.h).  Frames written here hold independent blocks and no dictionary; frames with a
+dictionary ID are refused with a clear message, not decoded wrongly, and so are frames with linked blocks (FLG.5 clear) unless the
+caller passes accept_linked=True.  Skippable frames (magic 0x184D2A50 .. 0x184D2A5F) are skipped, appended frames decoded one after
+the other.
 
 Many frames at once -- the buffers of an Arrow IPC stream, the record batches of a Kafka log, a service's pickled messages -- go
 through the batch calls (lz4hip_lz4f_batch_*): compress_frames_device / decompress_frames_device and their host forms take one buffer
@@ -118,8 +119,8 @@ def _encode_flags(block_checksum, content_checksum, content_size) -> int:
             (_lib.LZ4F_CONTENT_SIZE if content_size else 0))
 
 
-def _verify_flags(verify) -> int:
-    return (_lib.LZ4F_VERIFY_BLOCKS | _lib.LZ4F_VERIFY_CONTENT) if verify else 0
+def _decode_flags(verify, accept_linked) -> int:
+    return ((_lib.LZ4F_VERIFY_BLOCKS | _lib.LZ4F_VERIFY_CONTENT) if verify else 0) | (_lib.LZ4F_ACCEPT_LINKED if accept_linked else 0)
 
 
 def compress_frame_device(t, block_size: int = 65536, high_compression: bool = False, block_checksum: bool = False,
@@ -139,7 +140,7 @@ def compress_frame_device(t, block_size: int = 65536, high_compression: bool = F
         return out[:int(out_len.item())]
 
 
-def decompress_frame_device(t, verify: bool = True, round_blocks: int = 0):
+def decompress_frame_device(t, verify: bool = True, round_blocks: int = 0, accept_linked: bool = False):
     """The content of the LZ4 frames in a 1-D uint8 CUDA tensor -- appended frames one after the other, skippable frames skipped -- as a
     1-D uint8 CUDA tensor, decoded on the device on torch's current stream.  Per frame the host reads the first 19 bytes back (the block
     maximum sizes the decoder's slots, the content size the output and the table), calls lz4hip_lz4f_decode_device once and reads its
@@ -147,11 +148,13 @@ def decompress_frame_device(t, verify: bool = True, round_blocks: int = 0):
     verify=True checks whatever checksums the frame carries, as every reader of this format does; verify=False skips both.  The
     content checksum is ONE row of the checksum kernel -- four serial chains over the whole output, bound by their latency whatever the
     device (DESIGN.md 7 records the measured single-row rate, or says that it has not been measured yet) -- so verify=False is worth it for large frames whose
-    integrity is known.  round_blocks = K > 0 decodes K blocks at a time through a ring of K slots.  Raises ArgumentException with the
-    outcome's text."""
+    integrity is known.  round_blocks = K > 0 decodes K blocks at a time through a ring of K slots.  accept_linked=True decodes frames
+    with linked blocks (LZ4HIP_LZ4F_ACCEPT_LINKED) instead of refusing them: such a frame is one serial chain on ONE wavefront, far
+    slower for one large frame than a host core -- it pays in decompress_frames_device, many frames at once.  Raises ArgumentException
+    with the outcome's text."""
     import torch
     t = _p.check_device_bytes(t, "t")
-    flags = _verify_flags(verify)
+    flags = _decode_flags(verify, accept_linked)
     with _p.DeviceCall(t) as d:
         info_dev = d.record(_lib.Lz4fInfo)
         parts, pos, n = [], 0, t.numel()
@@ -208,11 +211,12 @@ def compress_frame_host(data, block_size: int = 65536, high_compression: bool = 
     return out[:out_len.value].tobytes()
 
 
-def decompress_frame_host(frame, verify: bool = True) -> bytes:
+def decompress_frame_host(frame, verify: bool = True, accept_linked: bool = False) -> bytes:
     """decompress_frame_device for host bytes, through lz4hip_lz4f_decode_host: per frame a size query (dst_cap = 0), then the call that
-    decodes into exactly that size.  Appended frames follow each other; skippable frames are skipped."""
+    decodes into exactly that size.  Appended frames follow each other; skippable frames are skipped.  accept_linked as in
+    decompress_frame_device."""
     buf = _p.host_bytes(frame)
-    flags = _verify_flags(verify)
+    flags = _decode_flags(verify, accept_linked)
     L = _lib.lib()
     parts, pos = [], 0
     if buf.size == 0:
@@ -282,7 +286,8 @@ def compress_frames_device(t, offsets, block_size: int = 65536, high_compression
         return out[:total], out_off
 
 
-def decompress_frames_device(t, offsets, slot_bytes: int = 65536, verify: bool = True, round_blocks: int = 0, max_blocks=None):
+def decompress_frames_device(t, offsets, slot_bytes: int = 65536, verify: bool = True, round_blocks: int = 0, max_blocks=None,
+                             accept_linked: bool = False):
     """[decompress_frame_device(item) for item in items] for items of ONE frame each, t[offsets[i]:offsets[i + 1]] of a 1-D uint8 CUDA
     tensor, in one call on the device, on torch's current stream -> (data, data_offsets).  Every item's size fields are walked by a
     wavefront of its own, the blocks of all items are one table of the block decoder, the content checksums n rows of one launch.
@@ -290,9 +295,12 @@ def decompress_frames_device(t, offsets, slot_bytes: int = 65536, verify: bool =
     block maximum exceeds the slot".  max_blocks is the table's size for the whole batch (default: a guess from the bytes); a table
     that was too small, or an output that outgrew the guess of four times the input, is decoded once more from the record.  A skippable
     item gives no bytes; what lies behind an item's frame is left alone.  round_blocks = K > 0 decodes K blocks at a time through a
-    ring of K slots instead of one slot per table row.  Raises the first failing item's ArgumentException, its index in .item."""
+    ring of K slots instead of one slot per table row.  accept_linked=True decodes items whose blocks are linked (the default of
+    LZ4F_compressFrame, python-lz4 and Arrow's LZ4_FRAME codec above one block) instead of failing them: each such item is decoded in
+    order by ONE wavefront, so the flag pays in batches of many items.  Raises the first failing item's ArgumentException, its index in
+    .item."""
     t, offsets = _p.check_device_batch(t, offsets)
-    flags = _verify_flags(verify)
+    flags = _decode_flags(verify, accept_linked)
     if int(slot_bytes) not in BLOCK_SIZES:
         raise ArgumentException("slot_bytes must be 65536, 262144, 1048576 or 4194304")
     with _p.DeviceCall(t) as d:
@@ -336,15 +344,15 @@ def compress_frames_host(buf, offsets, block_size: int = 65536, high_compression
     return out[:int(out_off[n])], out_off
 
 
-def decompress_frames_host(packed, offsets, verify: bool = True):
+def decompress_frames_host(packed, offsets, verify: bool = True, accept_linked: bool = False):
     """decompress_frames_device for host arrays, through lz4hip_lz4f_batch_decode_host: a size query (dst_cap = 0), then the call that
     decodes into exactly that size -> (data, data_offsets) as numpy arrays.  The slots take the largest block maximum among the items'
-    descriptors.  Raises the first failing item's ArgumentException, its index in .item."""
+    descriptors.  accept_linked as in decompress_frames_device.  Raises the first failing item's ArgumentException, its index in .item."""
     packed, offsets = _p.check_host_batch(packed, offsets)
     n = offsets.size - 1
     if n and ((np.diff(offsets) < 0).any() or offsets[0] < 0 or offsets[-1] > packed.size):
         raise ArgumentException(_p.BAD_OFFSETS)
-    flags = _verify_flags(verify)
+    flags = _decode_flags(verify, accept_linked)
     L = _lib.lib()
     out_off = np.zeros(n + 1, np.int64)
     items = (_lib.Lz4fInfo * max(n, 1))()

@@ -16,6 +16,20 @@ each for D2 and D3, with no checksums and with both.  Yardsticks, all existing c
            compressBound stride
 
     python tools/lz4f_batch_rate.py --case small [--reps 5] [--loop-items 256] [--out profiles/lz4f_batch/small.json]
+
+  linked  frames with LINKED blocks through the decode flag LZ4HIP_LZ4F_ACCEPT_LINKED: 4 096 frames of 256 KiB content in 64 KiB blocks
+          (16 384 frames of 64 KiB would fit one block each, and such a frame cannot be linked), and 262 144 independent frames of 4 KiB
+          as the all-independent control.  The linked frames are this library's own frames with the descriptor's FLG.5 cleared and HC
+          recomputed -- valid linked frames whose matches happen not to reach back -- and, where liblz4 is found, LZ4F_compressFrame's,
+          whose matches do.  Timed, decode only, taking turns:
+            linked_flagged_ms            the flagged call on the linked batch        (liblz4_linked_flagged_ms: on liblz4's frames)
+            independent_unflagged_ms     the unflagged call on the same content as independent frames
+            control_flagged_ms / control_unflagged_ms    either call on the control: the flag must cost an independent batch nothing
+            linked_size_query_ms - linked_refused_ms     the size pre-pass plus the plan alone, as a DIFFERENCE: the flagged call at
+                                         dst_cap = 0 (walk, size pre-pass, plan, empty rounds, records; no block is decoded) minus the
+                                         unflagged call on the linked batch (every item refused: walk, empty rounds, records)
+          --unflagged-only times the unflagged rows alone, which a library from before the flag can run too: the parent's build beside
+          this one in the same session (LZ4HIP_KEEP_LIBRARY over a copied library) is the check that the unflagged path is what it was.
 """
 import argparse
 import ctypes as C
@@ -30,9 +44,10 @@ import torch  # noqa: E402
 from lz4net_amd import _lib, batch, lz4_frame as lz  # noqa: E402
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--case", choices=("small", "large"), required=True)
+ap.add_argument("--case", choices=("small", "large", "linked"), required=True)
+ap.add_argument("--unflagged-only", action="store_true", help="--case linked: only the rows that do not pass the flag")
 ap.add_argument("--reps", type=int, default=5)
-ap.add_argument("--items", type=int, default=0, help="items of the case (default: 16384 small, 1024 large)")
+ap.add_argument("--items", type=int, default=0, help="items of the case (default: 16384 small, 1024 large, 4096 linked)")
 ap.add_argument("--loop-items", type=int, default=256)
 ap.add_argument("--dists", default="2,3")
 ap.add_argument("--out", default="")
@@ -40,8 +55,8 @@ args = ap.parse_args()
 L = _lib.lib()
 if L.lz4hip_device_count() <= 0:
     sys.exit("lz4f_batch_rate: no gfx950 device: nothing is measured without one")
-ITEM = 65536 if args.case == "small" else 1 << 20
-N = args.items or (16384 if args.case == "small" else 1024)
+ITEM = {"small": 65536, "large": 1 << 20, "linked": 262144}[args.case]
+N = args.items or {"small": 16384, "large": 1024, "linked": 4096}[args.case]
 BLOCK = 65536
 out_path = args.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "lz4f_batch", args.case + ".json")
 
@@ -88,6 +103,117 @@ s = torch.cuda.current_stream().cuda_stream
 results = {"_note": "every yardstick is timed in the SAME library and run as the batch calls; `loop` is wall time over --loop-items items and "
                     "its *_extrapolated_ms figures are per-item time times the item count, not measurements of the whole loop",
            "_library": L.lz4hip_build_id().decode(), "case": args.case, "items": N, "item_bytes": ITEM}
+
+
+# ---- the linked case ---------------------------------------------------------------------------------------------------------------------
+def encode_frames(data, n, item, eflags):
+    """this library's frames of the n items of `item` bytes -> (frames, offsets)"""
+    total = n * item
+    off = torch.arange(n + 1, dtype=torch.int64, device="cuda") * item
+    bound = L.lz4hip_lz4f_batch_bound(n, total, 4, eflags)
+    enc_out, enc_off, enc_scratch = u8(bound), i64(n + 1), u8(L.lz4hip_lz4f_batch_encode_scratch_bytes(n, total, 4))
+    _lib.check(L.lz4hip_lz4f_batch_encode_device(data.data_ptr(), total, off.data_ptr(), n, 4, _lib.MODE_FAST, eflags, enc_out.data_ptr(), bound,
+                                                 enc_off.data_ptr(), enc_scratch.data_ptr(), enc_scratch.numel(), s))
+    return enc_out[:int(enc_off[n])].clone(), enc_off.clone()
+
+
+def relinked(frames, frame_off, n, item, eflags):
+    """the same frames with FLG.5 cleared and HC recomputed (every item has the same descriptor: the same size)"""
+    out = frames.clone()
+    flg = int(frames[4]) & ~0x20
+    head = bytes([flg, int(frames[5])]) + (item.to_bytes(8, "little") if eflags & _lib.LZ4F_CONTENT_SIZE else b"")
+    at = frame_off[:n]
+    out[at + 4] = flg
+    out[at + 4 + len(head)] = (lz._xxh32_small(head) >> 8) & 0xFF
+    return out
+
+
+def liblz4_frames(data, n, item):
+    """LZ4F_compressFrame's linked frames of the items, or None where liblz4 is not found"""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import lz4f_lib
+    if lz4f_lib.load() is None:
+        return None
+    host = data.cpu().numpy()
+    parts = [lz4f_lib.compress_frame(host[i * item:(i + 1) * item].tobytes(), 4, 0, False, False, True, linked=True) for i in range(n)]
+    assert all(not p[4] & 0x20 for p in parts)
+    lens = torch.tensor([0] + [len(p) for p in parts], dtype=torch.int64)
+    import numpy as np
+    return torch.from_numpy(np.frombuffer(b"".join(parts), np.uint8).copy()).cuda(), torch.cumsum(lens, 0).cuda()
+
+
+def decoder(frames, frame_off, n, rows, flags, cap, out, scratch):
+    """the bare batch decode call over preallocated buffers (the calls of one label share `out` and `scratch`: they take turns)
+    -> (the call, a reader of its record)"""
+    out_off, recs, info_dev, written = i64(n + 1), u8(C.sizeof(_lib.Lz4fInfo) * n), u8(256), i64(1)
+    need = _lib.check(L.lz4hip_lz4f_batch_decode_scratch_bytes(n, 65536, rows, 0))
+    assert need <= scratch.numel()
+    call = lambda: _lib.check(L.lz4hip_lz4f_batch_decode_device(  # noqa: E731
+        frames.data_ptr(), frames.numel(), frame_off.data_ptr(), n, 65536, rows, 0, flags, scratch.data_ptr(), need, out.data_ptr(), cap, out_off.data_ptr(),
+        recs.data_ptr(), info_dev.data_ptr(), written.data_ptr(), s))
+    record = lambda: _lib.Lz4fBatchInfo.from_buffer_copy(info_dev.cpu().numpy().tobytes()[:C.sizeof(_lib.Lz4fBatchInfo)])  # noqa: E731
+    return call, record
+
+
+def linked_case():
+    small_item, small_n = 4096, N * ITEM // 4096
+    accept = 0 if args.unflagged_only else _lib.LZ4F_ACCEPT_LINKED
+    results.update(control_items=small_n, control_item_bytes=small_item, unflagged_only=bool(args.unflagged_only))
+    for dist in [int(x) for x in args.dists.split(",") if x]:
+        total = N * ITEM
+        data = batch.synth(dist, 7, 0, total // batch.BLOCK).reshape(-1)
+        rows = total // BLOCK
+        for label, eflags, vflags in (("plain", 0, 0), ("both_checksums", _lib.LZ4F_BLOCK_CHECKSUM | _lib.LZ4F_CONTENT_CHECKSUM, 3)):
+            eflags |= _lib.LZ4F_CONTENT_SIZE
+            r = results[f"D{dist}/{label}"] = {"content_bytes": total, "blocks": rows}
+            frames, frame_off = encode_frames(data, N, ITEM, eflags)
+            linked = relinked(frames, frame_off, N, ITEM, eflags)
+            control, control_off = encode_frames(data, small_n, small_item, eflags)
+            fns = {}
+            out = u8(total)
+            scratch = u8(max(L.lz4hip_lz4f_batch_decode_scratch_bytes(N, 65536, rows, 0), L.lz4hip_lz4f_batch_decode_scratch_bytes(small_n, 65536, small_n, 0)))
+
+            def add(name, fr, fo, n, nrows, flags, want_error, cap=None):
+                call, record = decoder(fr, fo, n, nrows, flags, total if cap is None else cap, out, scratch)
+                out.zero_()
+                call()
+                h = record()
+                if want_error == 0:
+                    assert (h.error, h.first_error, h.blocks, h.decoded_bytes) == (0, -1, nrows, total), (name, h.error, h.first_error, h.blocks, h.decoded_bytes)
+                    assert cap is not None or torch.equal(out, data), name
+                else:
+                    assert h.error == want_error and h.first_error == 0 and h.decoded_bytes == 0, (name, h.error, h.decoded_bytes)
+                fns[name] = call
+
+            add("independent_unflagged_ms", frames, frame_off, N, rows, vflags, 0)
+            add("control_unflagged_ms", control, control_off, small_n, small_n, vflags, 0)
+            add("linked_refused_ms", linked, frame_off, N, rows, vflags, _lib.LZ4F_UNSUPPORTED_LINKED)
+            if accept:
+                add("linked_flagged_ms", linked, frame_off, N, rows, vflags | accept, 0)
+                add("control_flagged_ms", control, control_off, small_n, small_n, vflags | accept, 0)
+                add("linked_size_query_ms", linked, frame_off, N, rows, vflags | accept, 0, cap=0)
+                theirs = liblz4_frames(data, N, ITEM) if label == "plain" else None
+                if theirs is not None:
+                    r["liblz4_frames_bytes"] = theirs[0].numel()
+                    add("liblz4_linked_flagged_ms", theirs[0], theirs[1], N, rows, vflags | accept, 0)
+            r["frames_bytes"] = frames.numel()
+            r.update(event_ms(fns))
+            if accept:
+                r["prepass_plus_plan_ms_by_difference"] = r["linked_size_query_ms"] - r["linked_refused_ms"]
+            for name in [k for k in r if k.endswith("flagged_ms")]:
+                r[name.replace("_ms", "_GBps")] = total / r[name] / 1e6
+            print(json.dumps({f"D{dist}/{label}": r}), flush=True)
+            del frames, linked, control, fns, out, scratch
+        del data
+
+
+if args.case == "linked":
+    linked_case()
+    os.makedirs(os.path.dirname(out_path), exist_ok=True)
+    with open(out_path, "w") as f:
+        json.dump(results, f, indent=1)
+    sys.exit(0)
+
 for dist in [int(x) for x in args.dists.split(",") if x]:
     total = N * ITEM
     data = batch.synth(dist, 7, 0, total // batch.BLOCK).reshape(-1)
