@@ -26,6 +26,17 @@
 //     (tools/lds_out_of_range.hip), so the rows of an append go to `row` and to `row - ring size` (ds_write2st64_b32: two rows per
 //     instruction) and the three instructions per row address that a ring of 48 rows cost are gone: -19 of ~305 vector-ALU instructions per
 //     iteration.  Worth nothing while the request ceiling held (round 4), +2.5 % behind the sector input.
+// THE ORDER OF AN ITERATION is set by what a wavefront ALONE on its SIMD cannot hide (every batch of up to one residency round, 65 536 blocks, runs
+// that way): a clock read per section (tools/dec_lane_sections.hip, profiles/decode_last_round/lone_wave_sections.txt) found no wait for memory
+// at B1 at all, but the cooperative flush -- three DEPENDENT LDS round trips in a row: record out, record in, ring rows in -- and the near-match
+// rows read right before their use.  So the flush runs in stages with independent work between them, and every LDS read is asked for at the top:
+//     T2a owners write their flush records, fl += unit | T2b helpers ask for their record (LDS operations of a wavefront complete in order: the read
+//     needs no wait behind the write) | T1c' near-match rows asked for | T1a window refill | T1b cursor view | T1c rows rotated | T3 chunk size
+//     T2c helpers ask for their ring rows | T4 parse ahead | T2d flush stores | T5 far fetch | T6 | B1 ..
+// Every lane reads "its" record slot and ring rows whether it helps or not (a lane mask decides at the store): no branch in T2b / T2c.  Two orders
+// are kept: the flush stores stay in front of T5, whose far fetch may only read what an EARLIER store instruction of this wavefront has written
+// (fl counts a unit from T2a on, but nothing between T2a and T2d reads memory through it), and nothing appends to the ring (B3 / B4) before the
+// helpers have read it (the wave-level fence behind T2d).  Vector-memory instructions per iteration, and their order, are unchanged (kVm).
 // Everything else is generation 3's design: dword-interleaved output ring, appends by DS_MSKOR_B32 + v_perm_b32, cooperative
 // flush (four lanes per 64-byte line, or eight per 128-byte unit), far matches fetched from the lane's own output one and a
 // half iterations ahead, parse-ahead of one sequence, a byte-wise parser behind one wave-level branch, hand-counted vmcnt.
@@ -45,10 +56,16 @@
 // Section markers for the per-section instruction table of the compiled kernel (tools/isa_lane4_table.py builds with
 // -DLZ4HIP_SECTION_MARKERS: each marker becomes a comment line in the assembly listing; volatile asm statements -- most of this kernel's
 // selects, loads and stores -- keep their order relative to the markers).  Nothing in product builds.
+// tools/dec_lane_sections.hip defines LZ4HIP_SECTION itself (a clock read per marker, accumulated in registers that LZ4HIP_SECTION_BEGIN declares
+// and LZ4HIP_SECTION_END writes out): where a lone wavefront's cycles go.
 #ifdef LZ4HIP_SECTION_MARKERS
 #define LZ4HIP_SECTION(name) asm volatile("; @@SECTION " name)
-#else
+#elif !defined(LZ4HIP_SECTION)
 #define LZ4HIP_SECTION(name) ((void)0)
+#endif
+#ifndef LZ4HIP_SECTION_BEGIN
+#define LZ4HIP_SECTION_BEGIN() ((void)0)
+#define LZ4HIP_SECTION_END(lane) ((void)0)
 #endif
 
 namespace lz4hip {
@@ -179,6 +196,7 @@ LZ4HIP_DEVICE int lane4_decode_block(unsigned char* lds, int lane, bool active, 
         if (!act || (!KNOWN && iend == 0)) { done = 1; final_seen = 1; }   // lz4.c:946 returns -(0)
     };
     start_block(active);
+    LZ4HIP_SECTION_BEGIN();
 
     // Append the low n_ bytes of the data dwords at op: rotated to the byte phase of op (one v_perm_b32 per dword), the
     // first dword merged into the ring under a byte mask, the others stored whole.
@@ -237,8 +255,66 @@ LZ4HIP_DEVICE int lane4_decode_block(unsigned char* lds, int lane, bool active, 
         constexpr int kVm = (FLUSH ? FS : 0) + 1 + (INPUT ? NL : 0);
         LZ4HIP_ITERATION_HOOK(lane);
         // ================================ TOP ================================
+        // ---- (T2a) flush, stage 1 of 4: the lanes that have a finished unit leave a record for their helpers.  The flush is three DEPENDENT
+        //      LDS round trips (record out, record in, ring rows in) in front of its stores; a wavefront alone on its SIMD has nobody to hide
+        //      them behind, so the stages (T2a .. T2d) stand apart, with independent work between one's LDS reads and the next one's use of them ----
+        LZ4HIP_SECTION("T2a flush records");
+        bool go = false;                                             // wave-uniform: some lane flushes in this iteration
+        int cnt = 0;
+        wv::mask_t f_act_m[FS];                                      // per store instruction: this lane is a helper of a record ...
+        Aligned16 f_rec[FS];                                         // ... the record (T2b) ...
+        uint64_t f_g[FS];                                            // ... and where its 16 bytes go, and the bytes (T2c)
+        uint32_t f_q[FS][4];
+        if constexpr (FLUSH) {
+            const bool need = (done == 0) & (op - fl >= FU);
+            const uint64_t needy = wv::ballot(need);
+            const int cnt_all = wv::popc64(needy);
+            go = cnt_all != 0;
+            bool mine = false;
+            if (go) {
+                cnt = cnt_all < kFlushRecs ? cnt_all : kFlushRecs;
+                const int frank = wv::rank_below(needy);
+                mine = need & (frank < kFlushRecs);
+                if (mine) {
+                    const uint64_t dp = (uint64_t)dst;
+                    // ring address of the unit: fl is a multiple of 4, so it starts floor((op - fl) / 4) rows before oa's row
+                    *frec(frank) = Aligned16{ { ring_add(oa, kRingBytes - ((((uint32_t)(op - fl)) << 6) & ~0xFFu) * (uint32_t)WAVES), (uint32_t)fl, (uint32_t)dp, (uint32_t)(dp >> 32) } };
+                }
+                // the unit counts as stored from here on: what reads fl below (room, the far fetch's test in T5, the end of the block) comes behind
+                // the store instructions of T2d in program order, and nothing appends to the ring before the helpers have read it (B3 / B4)
+                fl += mine ? FU : 0;
+            }
+            LZ4HIP_STAT(3, need); LZ4HIP_STAT(4, need & !mine);
+        }
+        LZ4HIP_SECTION("T2b record read");
+        // ---- (T2b) flush, stage 2: FU / 16 helper lanes per record ask for it, right behind the owners' writes (LDS operations of a wavefront
+        //      complete in issue order; the fence is for the compiler); the window and the chunk size stand between here and its use in T2c.
+        //      EVERY lane reads the record slot it would help with -- always inside the wavefront's records -- and only the lane mask says
+        //      whether what it read is a record of this iteration: no branch, and nothing to merge behind one ----
+        if constexpr (FLUSH) {
+            if (go) wv::mem_sync();
+#pragma unroll
+            for (int s = 0; s < FS; s++) {
+                const int idx = s * RECS_PER_STORE + lane / HPR;
+                f_act_m[s] = wv::cond(idx < cnt);
+                f_rec[s] = *frec(idx);
+            }
+        }
         // ---- (T1) the input window: take the next piece in once the cursor has left the current one; the 16 bytes at the
-        //      cursor; the 16 bytes at the source of the current near match ----
+        //      cursor; the 16 bytes at the source of the current near match (its ring rows are asked for first: they depend on nothing
+        //      the window does, and the window's selects cover their way back) ----
+        LZ4HIP_SECTION("T1c near-match reads");
+        const uint32_t offn = kind == kK4Near ? (uint32_t)off : 4u;  // (any other kind: some valid row)
+        uint32_t r0, r1, r2, r3, r4;
+        {
+            // row of output byte op - off: (op >> 2) - ((off - (op & 3) + 3) >> 2) rows back from oa
+            const uint32_t back = (((offn + 3u - ((uint32_t)op & 3u)) << 6) & ~0xFFu) * (uint32_t)WAVES;
+            uint32_t sa;
+            if (RPOW2) sa = (oa - back) & (kRingBytes - 1u);
+            else { const uint32_t t = oa - back, u = t + kRingBytes; sa = u < t ? u : t; }
+            r0 = L4_RING(sa); r1 = L4_RING(ring_add(sa, kRow)); r2 = L4_RING(ring_add(sa, 2 * kRow));
+            r3 = L4_RING(ring_add(sa, 3 * kRow)); r4 = L4_RING(ring_add(sa, 4 * kRow));
+        }
         LZ4HIP_SECTION("T1a window refill");
         int d = ip + skew - wb;                                      // byte offset of the cursor in W: 0 .. 16 + P (+ 16 while a piece is awaited)
         {
@@ -293,62 +369,10 @@ LZ4HIP_DEVICE int lane4_decode_block(unsigned char* lds, int lane, bool active, 
         LZ4HIP_SECTION("T1c near-match source rows");
         uint32_t v0, v1, v2, v3;
         {
-            // row of output byte op - off: (op >> 2) - ((off - (op & 3) + 3) >> 2) rows back from oa
-            const uint32_t offn = kind == kK4Near ? (uint32_t)off : 4u;        // (any other kind: some valid row)
-            const uint32_t back = (((offn + 3u - ((uint32_t)op & 3u)) << 6) & ~0xFFu) * (uint32_t)WAVES;
-            uint32_t sa;
-            if (RPOW2) sa = (oa - back) & (kRingBytes - 1u);
-            else { const uint32_t t = oa - back, u = t + kRingBytes; sa = u < t ? u : t; }
-            const uint32_t r0 = L4_RING(sa), r1 = L4_RING(ring_add(sa, kRow)), r2 = L4_RING(ring_add(sa, 2 * kRow)),
-                           r3 = L4_RING(ring_add(sa, 3 * kRow)), r4 = L4_RING(ring_add(sa, 4 * kRow));
             const uint32_t sr = L4_PHASE_SEL((uint32_t)op - offn);
             v0 = wv::perm(r1, r0, sr); v1 = wv::perm(r2, r1, sr); v2 = wv::perm(r3, r2, sr); v3 = wv::perm(r4, r3, sr);
         }
 
-        LZ4HIP_SECTION("T2 cooperative flush");
-        // ---- (T2) flush finished output, FU bytes at a time, FU / 16 lanes per unit: ALWAYS FS store instructions ----
-        if constexpr (FLUSH) {
-            const bool need = (done == 0) & (op - fl >= FU);
-            const uint64_t needy = wv::ballot(need);
-            const int cnt_all = wv::popc64(needy);
-            const bool go = cnt_all != 0;                            // wave-uniform
-            int cnt = 0;
-            bool mine = false;
-            if (go) {
-                cnt = cnt_all < kFlushRecs ? cnt_all : kFlushRecs;
-                const int frank = wv::rank_below(needy);
-                mine = need & (frank < kFlushRecs);
-                if (mine) {
-                    const uint64_t dp = (uint64_t)dst;
-                    // ring address of the unit: fl is a multiple of 4, so it starts floor((op - fl) / 4) rows before oa's row
-                    *frec(frank) = Aligned16{ { ring_add(oa, kRingBytes - ((((uint32_t)(op - fl)) << 6) & ~0xFFu) * (uint32_t)WAVES), (uint32_t)fl, (uint32_t)dp, (uint32_t)(dp >> 32) } };
-                }
-                wv::mem_sync();
-            }
-            const int sub = lane % HPR;
-#pragma unroll
-            for (int base = 0; base < FS * RECS_PER_STORE; base += RECS_PER_STORE) {
-                const int idx = base + lane / HPR;
-                const bool act = idx < cnt;
-                const wv::mask_t act_m = wv::cond(idx < cnt);
-                uint64_t g = 0;
-                uint32_t q0 = 0, q1 = 0, q2 = 0, q3 = 0;
-                if (act) {
-                    const Aligned16 r = *frec(idx);
-                    g = ((uint64_t)r.w[2] | ((uint64_t)r.w[3] << 32)) + (uint64_t)(r.w[1] + 16u * (uint32_t)sub);
-                    // the owner's lane bits are in r.w[0]; this helper takes rows 4*sub .. 4*sub+3 of the unit
-                    const uint32_t b0 = ring_add(r.w[0], 4u * kRow * (uint32_t)sub);
-                    if (kLineNoWrap) { q0 = L4_RING(b0); q1 = L4_RING(b0 + kRow); q2 = L4_RING(b0 + 2 * kRow); q3 = L4_RING(b0 + 3 * kRow); }   // (immediate offsets)
-                    else { q0 = L4_RING(b0); q1 = L4_RING(ring_add(b0, kRow)); q2 = L4_RING(ring_add(b0, 2 * kRow)); q3 = L4_RING(ring_add(b0, 3 * kRow)); }
-                }
-                wv::vm_store16_mask(act_m, g, q0, q1, q2, q3);
-            }
-            LZ4HIP_STAT(3, need); LZ4HIP_STAT(4, need & !mine);
-            if (go) {
-                wv::mem_sync();                                      // records and ring rows are free to be overwritten again
-                fl += mine ? FU : 0;
-            }
-        }
         LZ4HIP_SECTION("T3 chunk size");
         // ---- (T3) size of this iteration's chunk of the current copy (appended at the bottom) ----
         const bool room = op - fl <= R - 46;                         // this iteration's appends (<= 16 + 11 bytes + 19 of overshoot) stay clear of unflushed output
@@ -361,6 +385,22 @@ LZ4HIP_DEVICE int lane4_decode_block(unsigned char* lds, int lane, bool active, 
         LZ4HIP_STAT(8, (done == 0) & (rem > 0) & (kind == kK4Far) & (gready == 0)); LZ4HIP_STAT(9, (done == 0) & (rem > n));
         const int rem_after = rem - n;
         const int op_end = op + rem;                                 // where the current copy ends = where the parsed-ahead sequence's literals go
+
+        LZ4HIP_SECTION("T2c ring rows");
+        // ---- (T2c) flush, stage 3: each helper asks for its four ring rows of the unit (a lane that helps nobody for its own row 0, which
+        //      the masked store then leaves behind); the parse stands between here and the stores ----
+        if constexpr (FLUSH) {
+            const int sub = lane % HPR;
+#pragma unroll
+            for (int s = 0; s < FS; s++) {
+                const Aligned16 r = f_rec[s];
+                f_g[s] = ((uint64_t)r.w[2] | ((uint64_t)r.w[3] << 32)) + (uint64_t)(r.w[1] + 16u * (uint32_t)sub);
+                // the owner's lane bits are in r.w[0]; this helper takes rows 4*sub .. 4*sub+3 of the unit
+                const uint32_t b0 = wv::sel(f_act_m[s], ring_add(r.w[0], 4u * kRow * (uint32_t)sub), lane4);
+                if (kLineNoWrap) { f_q[s][0] = L4_RING(b0); f_q[s][1] = L4_RING(b0 + kRow); f_q[s][2] = L4_RING(b0 + 2 * kRow); f_q[s][3] = L4_RING(b0 + 3 * kRow); }   // (immediate offsets)
+                else { f_q[s][0] = L4_RING(b0); f_q[s][1] = L4_RING(ring_add(b0, kRow)); f_q[s][2] = L4_RING(ring_add(b0, 2 * kRow)); f_q[s][3] = L4_RING(ring_add(b0, 3 * kRow)); }
+            }
+        }
 
         LZ4HIP_SECTION("T4 parse ahead");
         // ---- (T4) parse ahead: the next sequence's header (needs only the cursor) ----
@@ -460,6 +500,15 @@ LZ4HIP_DEVICE int lane4_decode_block(unsigned char* lds, int lane, bool active, 
             }
             LZ4HIP_SECTION("T4 parse ahead");
             pv = 1;
+        }
+
+        LZ4HIP_SECTION("T2d flush stores");
+        // ---- (T2d) flush, stage 4: FU bytes per record leave, 16 per helper: ALWAYS FS store instructions, and always in front of T5 -- a far
+        //      fetch may only read what a store instruction issued EARLIER by this wavefront has written ----
+        if constexpr (FLUSH) {
+#pragma unroll
+            for (int s = 0; s < FS; s++) wv::vm_store16_mask(f_act_m[s], f_g[s], f_q[s][0], f_q[s][1], f_q[s][2], f_q[s][3]);
+            if (go) wv::mem_sync();                                  // records and ring rows are free to be overwritten again
         }
 
         LZ4HIP_SECTION("T5 far fetch");
@@ -589,6 +638,7 @@ LZ4HIP_DEVICE int lane4_decode_block(unsigned char* lds, int lane, bool active, 
             }
         }
     }
+    LZ4HIP_SECTION_END(lane);
     return result;
 #undef L4_RING
 #undef L4_PHASE_SEL
