@@ -21,8 +21,12 @@
 //  counter (vmcnt) covers loads AND stores, so a gather from global memory waits for every store issued before it --
 //  the write acknowledgement of the previous sequence, ~0.5 us -- while the ring's gather is an LDS access and the
 //  stores to HBM are never waited for.  Matches that reach further back, and everything after a long copy until the
-//  ring has filled up again, gather from global memory.  16 KiB of LDS per workgroup of four wavefronts leaves the
-//  residency where the registers put it.
+//  ring has filled up again, gather from global memory -- and so does a source among the ring's oldest bytes, whose
+//  slots the sequence itself is about to take: the one-sequence paths read and store with nothing in between that orders
+//  one lane's read against another lane's store, so the general path serves from the ring what starts less than
+//  4 096 - (its literals + match) bytes back and the short path what starts less than 4 096 - 20 bytes back (a burst reads
+//  before a collective and stores behind it, and serves all 4 096).  16 KiB of LDS per workgroup of four wavefronts leaves
+//  the residency where the registers put it.
 //
 // Return values are the reference's: known-size decode returns the number of source bytes consumed
 // or -(position of the error in the source); unknown-size decode returns bytes produced or
@@ -37,6 +41,9 @@
 #endif
 #ifndef LZ4HIP_STAT_ADD
 #define LZ4HIP_STAT_ADD(slot, n) ((void)0)
+#endif
+#ifndef LZ4HIP_STAT_PATH
+#define LZ4HIP_STAT_PATH(slot, cond) ((void)0)   /* slots 26 .. 34, which path a sequence took: only a build whose counter array has them defines it (tests/simt/emu_kernels.cpp) */
 #endif
 // Section timers of the wavefront decoder (tools/dec_wave_sections.hip defines these to s_memtime accumulators; nothing in product builds).
 #ifndef LZ4HIP_DEC_T0
@@ -84,6 +91,7 @@ struct SrcWindow {
             w0 = (nb == base + 256) ? w1 : fetch(nb + o);
             w1 = fetch(nb + 256 + o);
             base = nb;
+            LZ4HIP_STAT_PATH(33, wv::lane() == 0);
             wv::wait_vector_memory();                                // (once per 256 bytes of input: see wait_vector_memory)
         }
     }
@@ -137,6 +145,7 @@ LZ4HIP_DEVICE void wave_match_copy(uint8_t* dst, int pos, int off, int n)
         // Keep it in registers and only store (a run of zeros or of a short pattern becomes a fill, not a copy).
         if (dist == 1024 && left >= 1024) {
             const Vec16 v = load_v16(dst + cur - 1024 + lane * 16);
+            LZ4HIP_STAT_PATH(32, lane == 0);
             for (; left >= 1024; left -= 1024, cur += 1024)              // (explicit 16-byte global stores: the compiler splits this one into dwords otherwise)
                 wv::store_global16((uint64_t)(dst + cur + lane * 16), v.w[0], v.w[1], v.w[2], v.w[3]);
             wv::mem_sync();
@@ -146,6 +155,7 @@ LZ4HIP_DEVICE void wave_match_copy(uint8_t* dst, int pos, int off, int n)
 
 struct alignas(8) BurstRec { uint32_t x, y; };   // a burst's sequence: token lane | literals << 8 | offset << 16; first output byte
 constexpr int kWaveRingBytes = 4096;     // LDS mirror of a wavefront's most recent output (power of two)
+constexpr int kWaveRingShortServed = kWaveRingBytes - (2 + kMinMatch + 14);   // ... of which the short path serves all but what its longest sequence overwrites
 constexpr int kWaveBurstRecBytes = 1024; // ... followed by the burst's sequence records (at most 64 x 8 bytes)
 constexpr int kWaveLdsBytes = kWaveRingBytes + kWaveBurstRecBytes;
 
@@ -278,8 +288,8 @@ LZ4HIP_DEVICE int decode_block(const uint8_t* src, int src_len, uint8_t* dst, in
             }
             if (burst_done) { LZ4HIP_DEC_T(0); continue; }
             LZ4HIP_DEC_T(1);
-            LZ4HIP_STAT(23, lane == 0);
-            burst_fail = burst_fail < 5 ? burst_fail + 1 : 5;       // no run of short sequences here: back off, 1, 2, 4 .. 32 sequences
+            LZ4HIP_STAT(23, lane == 0); LZ4HIP_STAT_PATH(34, lane == 0 && tok_m != 0ull);      // 34: a source lay behind the mirror (or before the block)
+            burst_fail = burst_fail < 5 ? burst_fail + 1 : 5;       // no run of short sequences here: back off, 1, 2, 4 .. 16 sequences
             burst_skip = 1 << burst_fail >> 1;
             if (burst_skip < 1) burst_skip = 1;
         }
@@ -297,7 +307,10 @@ LZ4HIP_DEVICE int decode_block(const uint8_t* src, int src_len, uint8_t* dst, in
                 const int t_off = (int)((t5 >> (8 + 8 * tll)) & 0xFFFFu);
                 if (t_off >= t_ml + tll && t_off <= t_lit_end) {
                     const int t_ref = t_lit_end - t_off;
-                    const int ring_lo = op - kWaveRingBytes > ring_from ? op - kWaveRingBytes : ring_from;
+                    // (the mirror serves what it is sure to hold AFTER this step, which stores at most 2 + 18 bytes: the slots of older bytes
+                    //  are the ones this step's store takes, and nothing orders a lane's read against another lane's store.  Such a source
+                    //  comes from memory.  A constant, not this sequence's own length: no instruction more than without it.)
+                    const int ring_lo = op - kWaveRingShortServed > ring_from ? op - kWaveRingShortServed : ring_from;
                     const int sidx = t_ref + lane - tll;             // source of this lane's match byte (lanes >= tll)
                     const uint32_t lit = (uint32_t)(t5 >> 8) >> lane8;             // lanes < tll: their literal
                     // (two copies of the store on purpose: the one behind the LDS gather must not inherit the global
@@ -312,7 +325,7 @@ LZ4HIP_DEVICE int decode_block(const uint8_t* src, int src_len, uint8_t* dst, in
                         if (lane < tll + t_ml) { dst[op + lane] = (uint8_t)v; ring[(op + lane) & (kWaveRingBytes - 1)] = (uint8_t)v; }
                     }
                     wv::mem_sync();
-                    LZ4HIP_STAT(24, lane == 0);
+                    LZ4HIP_STAT(24, lane == 0); LZ4HIP_STAT_PATH(26, lane == 0 && t_ref >= ring_lo); LZ4HIP_STAT_PATH(27, lane == 0 && t_ref < ring_lo);
                     ip += 3 + tll; op = t_lit_end + t_ml;
                     LZ4HIP_DEC_T(2);
                     continue;
@@ -380,11 +393,13 @@ LZ4HIP_DEVICE int decode_block(const uint8_t* src, int src_len, uint8_t* dst, in
             const int sidx = ref + jj;                       // source index in dst
             const int from_lit = sidx - op;                  // >= 0: the byte is one of THIS sequence's literals
             const uint32_t via_lit = wv::shuffle(lit_byte, from_lit < 0 ? 0 : from_lit);
-            const int ring_lo = op - kWaveRingBytes > ring_from ? op - kWaveRingBytes : ring_from;
+            const int ring_lo = match_end - kWaveRingBytes > ring_from ? match_end - kWaveRingBytes : ring_from;   // (as in the short path: what the mirror holds after this step)
             uint32_t v = lit_byte;
             if (in_match) v = from_lit >= 0 ? via_lit : (sidx >= ring_lo ? (uint32_t)ring[sidx & (kWaveRingBytes - 1)] : (uint32_t)dst[sidx]);
             if (lane < ll || in_match) { dst[op + lane] = (uint8_t)v; ring[(op + lane) & (kWaveRingBytes - 1)] = (uint8_t)v; }
+            LZ4HIP_STAT_PATH(28, in_match && from_lit >= 0); LZ4HIP_STAT_PATH(29, in_match && from_lit < 0 && sidx >= ring_lo); LZ4HIP_STAT_PATH(30, in_match && from_lit < 0 && sidx < ring_lo);
         } else {
+            LZ4HIP_STAT_PATH(31, lane == 0);
             ring_from = match_end;                           // the long copies below bypass the ring
             if (ll > 0) {
                 if (short_lit) { if (lane < ll) dst[op + lane] = (uint8_t)lit_byte; }

@@ -33,7 +33,7 @@ def _length_bytes(n):
     return bytes(out)
 
 
-def emit(seqs, tail):
+def emit(seqs, tail, min_tail=TAIL):
     """the LZ4 block of the sequences (literals, offset, match length >= 4) and the last literals; returns (block, bytes it decodes to)"""
     b, out = bytearray(), bytearray()
     for lit, off, ml in seqs:
@@ -48,7 +48,7 @@ def emit(seqs, tail):
         out += lit
         for _ in range(ml):
             out.append(out[-off])
-    assert len(tail) >= TAIL
+    assert len(tail) >= min_tail
     b.append(min(len(tail), 15) << 4)
     if len(tail) >= 15:
         b += _length_bytes(len(tail))

@@ -7,9 +7,10 @@
 
 static unsigned long long g_iterations = 0;   // loop iterations of the lane decoders (all wavefronts), counted by lane 0
 #define LZ4HIP_ITERATION_HOOK(lane) do { if ((lane) == 0) g_iterations++; } while (0)
-static unsigned long long g_stat[32];         // lane-iterations per state of the fourth-generation lane decoder (tools/emu_decoder_stats.py)
+static unsigned long long g_stat[40];         // lane-iterations per state of the fourth-generation lane decoder (tools/emu_decoder_stats.py); 20 .. 34: paths of the wavefront decoder (tests/wave_decode_cases.py)
 #define LZ4HIP_STAT(slot, cond) do { if (cond) g_stat[slot]++; } while (0)
 #define LZ4HIP_STAT_ADD(slot, n) do { g_stat[slot] += (unsigned long long)(n); } while (0)
+#define LZ4HIP_STAT_PATH(slot, cond) LZ4HIP_STAT(slot, cond)
 
 #include "lz4hip_common.hpp"
 #include "lz4hip_decode.hpp"
@@ -319,7 +320,7 @@ unsigned long long emu_compare(const uint8_t* x, int64_t xs, const uint8_t* y, i
 }
 
 unsigned long long emu_steps() { return simt::rt().steps; }
-void emu_stats(unsigned long long* out, int reset) { for (int i = 0; i < 32; i++) { out[i] = g_stat[i]; if (reset) g_stat[i] = 0; } }
+void emu_stats(unsigned long long* out, int reset) { for (int i = 0; i < 40; i++) { out[i] = g_stat[i]; if (reset) g_stat[i] = 0; } }
 unsigned long long emu_iterations(int reset) { const unsigned long long v = g_iterations; if (reset) g_iterations = 0; return v; }
 }
 

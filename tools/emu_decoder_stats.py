@@ -23,7 +23,7 @@ comps = [o.compress(b) for b in blocks]
 nseq = None
 for cfg in cfgs:
     lib = emu.lib()
-    st = (C.c_ulonglong * 32)()
+    st = (C.c_ulonglong * 40)()
     lib.emu_stats(st, 1)
     lib.emu_iterations.restype = C.c_ulonglong
     lib.emu_iterations(1)

@@ -21,7 +21,7 @@ nblk = int(sys.argv[2]) if len(sys.argv) > 2 else 64
 o = Oracle()
 blocks = [o.gen(dist, 99, i, 1)[0] for i in range(nblk)]
 lib = emu.lib()
-st = (C.c_ulonglong * 32)()
+st = (C.c_ulonglong * 40)()
 lib.emu_stats(st, 1)
 res, dst = emu.encode(blocks, hc=True, lcp=True, groups=1)
 for i, b in enumerate(blocks):
