@@ -37,6 +37,7 @@
 
 #include <cstddef>
 #include <cstring>
+#include <string>
 
 namespace lz4hip {
 namespace framing {
@@ -1279,22 +1280,26 @@ struct PackedPlan {
     uint8_t* dst; int64_t dst_cap; int64_t* dst_off; int32_t* packed_len; PackedInfo* info;
 };
 
-// The rounds, for the packed encode and for the compact decode (lz4hip_compact.hpp) alike: `codec` runs the block encoder or decoder over
-// a round's descriptor, `sizes` is the kernel that turns its results into sizes under the codec's failure rule.
+// The state block before the first round; what may mark a lowest failed index ahead of the rounds (the linked plan of lz4hip_lz4f_linked.hpp)
+// comes after it.
+template <class B>
+int packed_state_init(B& be, const PackedScratch& l)
+{
+    LZ4HIP_FRAMING_TRY(be.fill(l.state, 0, (size_t)kPackedStateBytes));
+    return be.fill(l.state + kPackedBad, 0xFF, 8);                      // the lowest failed index = none
+}
+
+// The rounds, written ONCE for the packed encode, the compact decode (lz4hip_compact.hpp) and the decodes of LZ4 frames (lz4hip_lz4f.hpp,
+// lz4hip_lz4f_batch.hpp): `codec` runs the block encoder or decoder over a round's descriptor, `sizes` launches the step that turns its
+// results into sizes under the caller's failure rule, `pack` the copy of the round's rows out of the ring.  p.b says where the rows lie:
+// the caller's descriptor, or a table's columns dressed as one.
 // Each round is a normal batch encode (decode) of its rows: the descriptor's array pointers are advanced here, on the host, its output is the
 // ring, its capacities the round's array in scratch and its lengths the round's sanitised copy there (the encoders do not check a
 // length's sign: a negative one would send their literal copy before the slot).  Rounds follow each other in stream order: a round's pack has read the ring
 // before the next round's encoder writes it.
-template <class B, class Codec>
-int packed_rounds_run(B& be, const PackedPlan& p, Codec codec, void (*sizes)(PackedRound))
+template <class B, class Codec, class Sizes, class Pack>
+int packed_rounds(B& be, const PackedPlan& p, Codec codec, Sizes sizes, Pack pack)
 {
-    if (p.n == 0) {
-        LZ4HIP_FRAMING_TRY(be.fill(p.dst_off, 0, sizeof(int64_t)));
-        if (p.info) be.launch(packed_empty_info_kernel, fixed_grid(1), 64, p.info);
-        return be.last_error();
-    }
-    LZ4HIP_FRAMING_TRY(be.fill(p.l.state, 0, (size_t)kPackedStateBytes));
-    LZ4HIP_FRAMING_TRY(be.fill(p.l.state + kPackedBad, 0xFF, 8));      // the lowest failed index = none
     const lz4hip_batch_t& b = p.b;
     const Grid pack_grid = copy_grid(p.round * p.slot);
     int32_t parity = 0;
@@ -1313,13 +1318,28 @@ int packed_rounds_run(B& be, const PackedPlan& p, Codec codec, void (*sizes)(Pac
         rb.dst = p.l.ring; rb.dst_stride = p.slot; rb.dst_cap = p.l.caps;
         rb.result = a.result; rb.n_blocks = a.cnt;
         LZ4HIP_FRAMING_TRY(codec(&rb));
-        be.launch(sizes, stream_grid(a.cnt), kStreamThreads, a);
+        sizes(a, stream_grid(a.cnt));
         launch_scan(be, a.offs, a.cnt, p.l.partial, p.l.state + kPackedTotal);
         be.launch(packed_rebase_kernel, stream_grid(a.cnt), kStreamThreads, a);
-        PackedLayout layout = { a };
-        be.launch(packed_pack_kernel, pack_grid, kStreamThreads, layout, p.dst, p.dst_cap);
+        pack(a, pack_grid);
         LZ4HIP_FRAMING_TRY(be.last_error());
     }
+    return 0;
+}
+
+// a block batch through the rounds: the empty batch, the state block, the rounds with the sizes kernel of the codec's failure rule and
+// PackedLayout, the record
+template <class B, class Codec>
+int packed_rounds_run(B& be, const PackedPlan& p, Codec codec, void (*sizes)(PackedRound))
+{
+    if (p.n == 0) {
+        LZ4HIP_FRAMING_TRY(be.fill(p.dst_off, 0, sizeof(int64_t)));
+        if (p.info) be.launch(packed_empty_info_kernel, fixed_grid(1), 64, p.info);
+        return be.last_error();
+    }
+    LZ4HIP_FRAMING_TRY(packed_state_init(be, p.l));
+    LZ4HIP_FRAMING_TRY(packed_rounds(be, p, codec, [&](const PackedRound& a, Grid grid) { be.launch(sizes, grid, kStreamThreads, a); },
+                                     [&](const PackedRound& a, Grid grid) { be.launch(packed_pack_kernel, grid, kStreamThreads, PackedLayout{ a }, p.dst, p.dst_cap); }));
     if (p.info) be.launch(packed_info_kernel, fixed_grid(1), 64, (const int64_t*)p.dst_off, p.n, p.dst_cap, (const int64_t*)p.l.state, p.info);
     return be.last_error();
 }
@@ -1332,22 +1352,51 @@ int encode_packed_run(B& be, const PackedPlan& p)
 
 // reads b's src, src_off / src_stride, src_len / src_len_all, dst_cap / dst_cap_all (the slot width), result and n_blocks; b's dst,
 // dst_off and dst_stride are ignored.  packed_len and info may be NULL.
-// what the device call and the host call check alike: everything but the scratch, which only the device call is handed
+// What the device call and the host call check alike, for the packed encode (`what` = "encode packed") and the compact decode ("decode
+// compact", whose mode is LZ4HIP_MODE_FAST: it has none): everything but the scratch, which only the device call is handed
+template <class B>
+int packed_check(B& be, const char* what, const lz4hip_batch_t* b, int mode, int64_t round_blocks, const void* dst, int64_t dst_cap, const int64_t* dst_off)
+{
+    const auto fail = [&](const char* text) { return be.fail(LZ4HIP_E_ARGUMENT, (std::string(what) + ": " + text).c_str()); };
+    if (!b) return fail("batch descriptor is NULL");
+    const int64_t n = b->n_blocks;
+    if (n < 0) return fail("n_blocks < 0");
+    if (dst_cap < 0 || round_blocks < 0) return fail("dst_cap < 0 or round_blocks < 0");
+    if (b->dst_cap_all <= 0) return fail("dst_cap_all (the slot width) must be > 0");
+    if (mode != LZ4HIP_MODE_FAST && mode != LZ4HIP_MODE_HC) return be.fail(LZ4HIP_E_ARGUMENT, "mode must be LZ4HIP_MODE_FAST or LZ4HIP_MODE_HC");
+    if (!dst_off) return fail("dst_off is NULL");
+    if (packed_round(n, round_blocks) > 0x7FFFFFFF) return fail("more than 2^31 - 1 blocks in a round");
+    if (n > 0) {
+        if (!b->src || (dst_cap > 0 && !dst)) return fail("src and dst must be non-NULL");
+        if (!b->src_len && b->src_len_all < 0) return fail("src_len_all < 0");
+    }
+    return 0;
+}
+
 template <class B>
 int encode_packed_check(B& be, const lz4hip_batch_t* b, int mode, int64_t round_blocks, const void* dst, int64_t dst_cap, const int64_t* dst_off)
 {
-    if (!b) return be.fail(LZ4HIP_E_ARGUMENT, "encode packed: batch descriptor is NULL");
+    return packed_check(be, "encode packed", b, mode, round_blocks, dst, dst_cap, dst_off);
+}
+
+// `lens`: the caller's packed_len or decoded_len.  The scratch query's name in the failure text is the public one: lz4hip_<what, with
+// underscores>_scratch_bytes.
+template <class B>
+int packed_plan(B& be, const char* what, const lz4hip_batch_t* b, int mode, int64_t round_blocks, void* dst, int64_t dst_cap, int64_t* dst_off,
+                int32_t* lens, void* scratch, int64_t scratch_bytes, PackedInfo* info, PackedPlan& p)
+{
+    LZ4HIP_FRAMING_TRY(packed_check(be, what, b, mode, round_blocks, dst, dst_cap, dst_off));
     const int64_t n = b->n_blocks;
-    if (n < 0) return be.fail(LZ4HIP_E_ARGUMENT, "encode packed: n_blocks < 0");
-    if (dst_cap < 0 || round_blocks < 0) return be.fail(LZ4HIP_E_ARGUMENT, "encode packed: dst_cap < 0 or round_blocks < 0");
-    if (b->dst_cap_all <= 0) return be.fail(LZ4HIP_E_ARGUMENT, "encode packed: dst_cap_all (the slot width) must be > 0");
-    if (mode != LZ4HIP_MODE_FAST && mode != LZ4HIP_MODE_HC) return be.fail(LZ4HIP_E_ARGUMENT, "mode must be LZ4HIP_MODE_FAST or LZ4HIP_MODE_HC");
-    if (!dst_off) return be.fail(LZ4HIP_E_ARGUMENT, "encode packed: dst_off is NULL");
-    if (packed_round(n, round_blocks) > 0x7FFFFFFF) return be.fail(LZ4HIP_E_ARGUMENT, "encode packed: more than 2^31 - 1 blocks in a round");
-    if (n > 0) {
-        if (!b->src || (dst_cap > 0 && !dst)) return be.fail(LZ4HIP_E_ARGUMENT, "encode packed: src and dst must be non-NULL");
-        if (!b->src_len && b->src_len_all < 0) return be.fail(LZ4HIP_E_ARGUMENT, "encode packed: src_len_all < 0");
+    if (scratch_bytes < encode_packed_scratch_bytes(n, b->dst_cap_all, round_blocks)) {
+        std::string query = what;
+        for (char& ch : query) ch = ch == ' ' ? '_' : ch;
+        return be.fail(LZ4HIP_E_ARGUMENT, (std::string(what) + ": scratch_bytes < lz4hip_" + query + "_scratch_bytes").c_str());
     }
+    if (n > 0 && !scratch) return be.fail(LZ4HIP_E_ARGUMENT, (std::string(what) + ": scratch must be non-NULL").c_str());
+    p.n = n; p.round = packed_round(n, round_blocks);
+    p.b = *b; p.mode = mode; p.limit = b->dst_cap_all; p.slot = packed_slot(b->dst_cap_all);
+    p.l = packed_scratch(scratch, n, b->dst_cap_all, round_blocks);
+    p.dst = (uint8_t*)dst; p.dst_cap = dst_cap; p.dst_off = dst_off; p.packed_len = lens; p.info = info;
     return 0;
 }
 
@@ -1355,16 +1404,7 @@ template <class B>
 int encode_packed_plan(B& be, const lz4hip_batch_t* b, int mode, int64_t round_blocks, void* dst, int64_t dst_cap, int64_t* dst_off,
                        int32_t* packed_len, void* scratch, int64_t scratch_bytes, lz4hip_packed_info_t* info, PackedPlan& p)
 {
-    LZ4HIP_FRAMING_TRY(encode_packed_check(be, b, mode, round_blocks, dst, dst_cap, dst_off));
-    const int64_t n = b->n_blocks;
-    if (scratch_bytes < encode_packed_scratch_bytes(n, b->dst_cap_all, round_blocks))
-        return be.fail(LZ4HIP_E_ARGUMENT, "encode packed: scratch_bytes < lz4hip_encode_packed_scratch_bytes");
-    if (n > 0 && !scratch) return be.fail(LZ4HIP_E_ARGUMENT, "encode packed: scratch must be non-NULL");
-    p.n = n; p.round = packed_round(n, round_blocks);
-    p.b = *b; p.mode = mode; p.limit = b->dst_cap_all; p.slot = packed_slot(b->dst_cap_all);
-    p.l = packed_scratch(scratch, n, b->dst_cap_all, round_blocks);
-    p.dst = (uint8_t*)dst; p.dst_cap = dst_cap; p.dst_off = dst_off; p.packed_len = packed_len; p.info = (PackedInfo*)info;
-    return 0;
+    return packed_plan(be, "encode packed", b, mode, round_blocks, dst, dst_cap, dst_off, packed_len, scratch, scratch_bytes, (PackedInfo*)info, p);
 }
 
 template <class B>
@@ -1394,40 +1434,18 @@ int decode_compact_run(B& be, const PackedPlan& p)
     return packed_rounds_run(be, p, [&](const lz4hip_batch_t* rb) { return be.decode(rb, 0); }, compact_sizes_kernel);
 }
 
-// reads b's src, src_off / src_stride, src_len / src_len_all, dst_cap / dst_cap_all (the slot width), result and n_blocks; b's dst,
-// dst_off and dst_stride are ignored.  decoded_len and info may be NULL.
-// what the device call and the host call check alike: everything but the scratch, which only the device call is handed
+// The packed encode's check and plan (packed_check, packed_plan) under this call's name; decoded_len and info may be NULL.
 template <class B>
 int decode_compact_check(B& be, const lz4hip_batch_t* b, int64_t round_blocks, const void* dst, int64_t dst_cap, const int64_t* dst_off)
 {
-    if (!b) return be.fail(LZ4HIP_E_ARGUMENT, "decode compact: batch descriptor is NULL");
-    const int64_t n = b->n_blocks;
-    if (n < 0) return be.fail(LZ4HIP_E_ARGUMENT, "decode compact: n_blocks < 0");
-    if (dst_cap < 0 || round_blocks < 0) return be.fail(LZ4HIP_E_ARGUMENT, "decode compact: dst_cap < 0 or round_blocks < 0");
-    if (b->dst_cap_all <= 0) return be.fail(LZ4HIP_E_ARGUMENT, "decode compact: dst_cap_all (the slot width) must be > 0");
-    if (!dst_off) return be.fail(LZ4HIP_E_ARGUMENT, "decode compact: dst_off is NULL");
-    if (packed_round(n, round_blocks) > 0x7FFFFFFF) return be.fail(LZ4HIP_E_ARGUMENT, "decode compact: more than 2^31 - 1 blocks in a round");
-    if (n > 0) {
-        if (!b->src || (dst_cap > 0 && !dst)) return be.fail(LZ4HIP_E_ARGUMENT, "decode compact: src and dst must be non-NULL");
-        if (!b->src_len && b->src_len_all < 0) return be.fail(LZ4HIP_E_ARGUMENT, "decode compact: src_len_all < 0");
-    }
-    return 0;
+    return packed_check(be, "decode compact", b, LZ4HIP_MODE_FAST, round_blocks, dst, dst_cap, dst_off);
 }
 
 template <class B>
 int decode_compact_plan(B& be, const lz4hip_batch_t* b, int64_t round_blocks, void* dst, int64_t dst_cap, int64_t* dst_off,
                         int32_t* decoded_len, void* scratch, int64_t scratch_bytes, lz4hip_compact_info_t* info, PackedPlan& p)
 {
-    LZ4HIP_FRAMING_TRY(decode_compact_check(be, b, round_blocks, dst, dst_cap, dst_off));
-    const int64_t n = b->n_blocks;
-    if (scratch_bytes < decode_compact_scratch_bytes(n, b->dst_cap_all, round_blocks))
-        return be.fail(LZ4HIP_E_ARGUMENT, "decode compact: scratch_bytes < lz4hip_decode_compact_scratch_bytes");
-    if (n > 0 && !scratch) return be.fail(LZ4HIP_E_ARGUMENT, "decode compact: scratch must be non-NULL");
-    p.n = n; p.round = packed_round(n, round_blocks);
-    p.b = *b; p.mode = 0; p.limit = b->dst_cap_all; p.slot = packed_slot(b->dst_cap_all);
-    p.l = packed_scratch(scratch, n, b->dst_cap_all, round_blocks);
-    p.dst = (uint8_t*)dst; p.dst_cap = dst_cap; p.dst_off = dst_off; p.packed_len = decoded_len; p.info = (PackedInfo*)info;
-    return 0;
+    return packed_plan(be, "decode compact", b, LZ4HIP_MODE_FAST, round_blocks, dst, dst_cap, dst_off, decoded_len, scratch, scratch_bytes, (PackedInfo*)info, p);
 }
 
 template <class B>
@@ -1698,11 +1716,13 @@ int lz4f_linked_decode_run(B& be, const Lz4fLinked& a)
     return be.last_error();
 }
 
-inline Lz4fTables lz4f_tables(Carver& c, int64_t max_blocks)
+// The table's rows, for one frame (items < 0: one walk record, the content's checksum behind the rows', no item column) and for a batch
+// of `items` frames (a walk record per item, each row's item).
+inline Lz4fTables lz4f_tables(Carver& c, int64_t max_blocks, int64_t items = -1)
 {
     Lz4fTables t;
     t.max_blocks = max_blocks;
-    t.walk = c.take_as<int64_t>(8 * kLz4fWalkSlots);
+    t.walk = c.take_as<int64_t>(8 * kLz4fWalkSlots * (items < 0 ? 1 : items));
     t.src_off = c.take_as<int64_t>(8 * max_blocks);
     t.hdr_off = c.take_as<int64_t>(8 * max_blocks);
     t.dst_off = c.take_as<int64_t>(8 * (max_blocks + 1));
@@ -1710,11 +1730,65 @@ inline Lz4fTables lz4f_tables(Carver& c, int64_t max_blocks)
     t.dec_len = c.take_as<int32_t>(4 * max_blocks);
     t.sum_len = c.take_as<int32_t>(4 * max_blocks);
     t.result = c.take_as<int32_t>(4 * max_blocks);
-    t.sums = c.take_as<uint32_t>(4 * (max_blocks + 1));
+    t.sums = c.take_as<uint32_t>(4 * (max_blocks + (items < 0 ? 1 : 0)));
     t.row = c.take_as<uint8_t>(max_blocks);
     t.plan = c.take_as<int32_t>(4 * max_blocks);
+    t.item = items < 0 ? nullptr : c.take_as<int32_t>(4 * max_blocks);
     return t;
 }
+
+// Both decodes of LZ4 frames over such a table.  Before the walk: the columns a row past the walks' count is read from are those of an
+// empty block that belongs to item 0.
+template <class B>
+int lz4f_tables_init(B& be, const Lz4fTables& t)
+{
+    const int64_t n = t.max_blocks;
+    LZ4HIP_FRAMING_TRY(be.fill(t.src_off, 0, (size_t)(8 * n)));
+    LZ4HIP_FRAMING_TRY(be.fill(t.stored, 0, (size_t)(4 * n)));
+    LZ4HIP_FRAMING_TRY(be.fill(t.dec_len, 0, (size_t)(4 * n)));
+    LZ4HIP_FRAMING_TRY(be.fill(t.sum_len, 0, (size_t)(4 * n)));
+    if (t.item) LZ4HIP_FRAMING_TRY(be.fill(t.item, 0, (size_t)(4 * n)));
+    return be.fill(t.row, 0, (size_t)n);
+}
+
+// After the walk: the block checksums if asked for, the state block, the linked rows' plan if accepted, the compact decode's rounds
+// over ALL max_blocks rows with the frames' own sizes step and pack layout (p.b is the table: its src_off, dec_len and result columns
+// and its dst_off as p.dst_off), the linked items' decode.  `total` and `base` are the batch's (nullptr: one frame), `item_bad` every
+// item's lowest bad row: for one frame the state block's kPackedBad slot.
+template <class B>
+int lz4f_rows_run(B& be, const PackedPlan& p, const Lz4fTables& t, unsigned flags, int64_t items, const int64_t* base, const int64_t* total,
+                  unsigned long long* item_bad)
+{
+    const uint8_t* src = (const uint8_t*)p.b.src;
+    if (flags & kLz4fVerifyBlocks) {
+        const XxhRows rows = { src, t.src_off, 0, t.sum_len, nullptr, 0, 0u, t.sums, t.max_blocks };
+        LZ4HIP_FRAMING_TRY(xxh32_rows_run(be, rows));
+        be.launch(lz4f_verify_kernel, stream_grid(t.max_blocks), kStreamThreads, src, t, total);
+    }
+    LZ4HIP_FRAMING_TRY(packed_state_init(be, p.l));
+    const Lz4fLinked linked = { src, p.dst, p.dst_cap, items, t.max_blocks, t.walk, base, total, t.src_off, t.stored, t.dst_off, t.row, t.plan, item_bad };
+    if (flags & kLz4fAcceptLinked) LZ4HIP_FRAMING_TRY(lz4f_linked_plan_run(be, linked));
+    const auto round = [&](const PackedRound& a) {
+        const int64_t f = a.first;
+        return Lz4fRound{ a, src, t.src_off + f, t.stored + f, t.row + f, t.plan + f, t.item ? t.item + f : nullptr, t.walk, item_bad };
+    };
+    LZ4HIP_FRAMING_TRY(packed_rounds(be, p, [&](const lz4hip_batch_t* rb) { return be.decode(rb, 0); },
+                                     [&](const PackedRound& a, Grid grid) { be.launch(lz4f_round_sizes_kernel, grid, kStreamThreads, round(a)); },
+                                     [&](const PackedRound& a, Grid grid) { be.launch(lz4f_round_pack_kernel, grid, kStreamThreads, Lz4fRoundLayout{ round(a) }, p.dst, p.dst_cap); }));
+    if (flags & kLz4fAcceptLinked) LZ4HIP_FRAMING_TRY(lz4f_linked_decode_run(be, linked));
+    return 0;
+}
+
+// the rounds' plan over a table: the table IS the batch, every row at its offset in the source, decoded at its dec_len
+inline PackedPlan lz4f_rounds_plan(const uint8_t* src, const Lz4fTables& t, const PackedScratch& l, int32_t slot_bytes, int64_t round_blocks, uint8_t* dst, int64_t dst_cap)
+{
+    PackedPlan p = {};
+    p.b.src = src; p.b.src_off = t.src_off; p.b.src_len = t.dec_len; p.b.result = t.result; p.b.n_blocks = t.max_blocks;
+    p.n = t.max_blocks; p.round = packed_round(t.max_blocks, round_blocks); p.slot = packed_slot(slot_bytes); p.limit = slot_bytes; p.l = l;
+    p.dst = dst; p.dst_cap = dst_cap; p.dst_off = t.dst_off;
+    return p;
+}
+
 struct Lz4fDecodeScratch { Lz4fTables t; PackedScratch l; int64_t bytes; };
 inline Lz4fDecodeScratch lz4f_decode_scratch(void* scratch, int32_t slot, int64_t max_blocks, int64_t round_blocks)
 {
@@ -1732,64 +1806,27 @@ inline int64_t lz4f_decode_scratch_bytes(int32_t slot_bytes, int64_t max_blocks,
 }
 
 struct Lz4fDecodePlan {
-    const uint8_t* src; int64_t src_len; int32_t slot_bytes; unsigned flags; Lz4fTables t; PackedScratch l; int64_t round, slot;
-    uint8_t* dst; int64_t dst_cap; Lz4fInfo* info;
+    const uint8_t* src; int64_t src_len; int32_t slot_bytes; unsigned flags; Lz4fTables t; PackedPlan rounds; Lz4fInfo* info;
 };
 
-// The walk, the block checksums, then packed_rounds_run's rounds over ALL max_blocks rows of the table with the twin sizes step and pack
-// layout (the rows past the walk's count are empty blocks, which decode to nothing), the record, the content checksum.  Nothing is
+// The walk, then what both decodes of LZ4 frames share (lz4f_rows_run: the block checksums and the rounds over ALL max_blocks rows of the
+// table; the rows past the walk's count are empty blocks, which decode to nothing), the record, the content checksum.  Nothing is
 // read on the host between the steps.  The decoders are handed the table's dec_len column through the round's sanitised copy: a raw
 // row and a row with a bad checksum arrive as empty blocks, and so does every row of a frame with linked blocks, which a caller who
-// accepts them (kLz4fAcceptLinked) gets sized before the rounds and decoded after them, as the batch of one item.
+// accepts them (kLz4fAcceptLinked) gets sized before the rounds and decoded after them.  The frame is the batch of one item, whose
+// lowest bad row is the state block's lowest failed index.
 template <class B>
 int lz4f_decode_run(B& be, const Lz4fDecodePlan& p)
 {
     const Lz4fTables& t = p.t;
-    const int64_t n = t.max_blocks;
-    LZ4HIP_FRAMING_TRY(be.fill(t.src_off, 0, (size_t)(8 * n)));
-    LZ4HIP_FRAMING_TRY(be.fill(t.stored, 0, (size_t)(4 * n)));
-    LZ4HIP_FRAMING_TRY(be.fill(t.dec_len, 0, (size_t)(4 * n)));
-    LZ4HIP_FRAMING_TRY(be.fill(t.sum_len, 0, (size_t)(4 * n)));
-    LZ4HIP_FRAMING_TRY(be.fill(t.row, 0, (size_t)n));
+    unsigned long long* const bad = (unsigned long long*)(p.rounds.l.state + kPackedBad);
+    LZ4HIP_FRAMING_TRY(lz4f_tables_init(be, t));
     be.launch(lz4f_walk_kernel, fixed_grid(1), 64, p.src, p.src_len, p.slot_bytes, p.flags, t);
     LZ4HIP_FRAMING_TRY(be.last_error());
-    if (p.flags & kLz4fVerifyBlocks) {
-        const XxhRows rows = { p.src, t.src_off, 0, t.sum_len, nullptr, 0, 0u, t.sums, n };
-        LZ4HIP_FRAMING_TRY(xxh32_rows_run(be, rows));
-        be.launch(lz4f_verify_kernel, stream_grid(n), kStreamThreads, p.src, t);
-    }
-    LZ4HIP_FRAMING_TRY(be.fill(p.l.state, 0, (size_t)kPackedStateBytes));
-    LZ4HIP_FRAMING_TRY(be.fill(p.l.state + kPackedBad, 0xFF, 8));      // the lowest bad block = none
-    const Lz4fLinked linked = { p.src, p.dst, p.dst_cap, 1, n, t.walk, nullptr, nullptr, t.src_off, t.stored, t.dst_off, t.row, t.plan,
-                                (unsigned long long*)(p.l.state + kPackedBad) };
-    if (p.flags & kLz4fAcceptLinked) LZ4HIP_FRAMING_TRY(lz4f_linked_plan_run(be, linked));
-    const Grid pack_grid = copy_grid(p.round * p.slot);
-    int32_t parity = 0;
-    for (int64_t first = 0; first < n; first += p.round, parity ^= 1) {
-        PackedRound a;
-        a.first = first; a.cnt = n - first < p.round ? n - first : p.round; a.slot = p.slot; a.limit = p.slot_bytes; a.parity = parity;
-        a.cap_in = nullptr; a.caps = p.l.caps; a.result = t.result + first;
-        a.len_in = t.dec_len + first; a.lens_enc = p.l.lens;
-        a.ring = p.l.ring; a.offs = t.dst_off + first; a.lens = nullptr; a.state = p.l.state;
-        be.launch(packed_caps_kernel, stream_grid(a.cnt), kStreamThreads, a);
-        LZ4HIP_FRAMING_TRY(be.last_error());
-        lz4hip_batch_t rb = {};
-        rb.src = p.src; rb.src_off = t.src_off + first; rb.src_len = p.l.lens;
-        rb.dst = p.l.ring; rb.dst_stride = p.slot; rb.dst_cap = p.l.caps;
-        rb.result = a.result; rb.n_blocks = a.cnt;
-        LZ4HIP_FRAMING_TRY(be.decode(&rb, 0));
-        const Lz4fRound r = { a, p.src, t.src_off + first, t.stored + first, t.row + first, t.walk, t.plan + first };
-        be.launch(lz4f_round_sizes_kernel, stream_grid(a.cnt), kStreamThreads, r);
-        launch_scan(be, a.offs, a.cnt, p.l.partial, p.l.state + kPackedTotal);
-        be.launch(packed_rebase_kernel, stream_grid(a.cnt), kStreamThreads, a);
-        Lz4fRoundLayout layout = { r };
-        be.launch(lz4f_round_pack_kernel, pack_grid, kStreamThreads, layout, p.dst, p.dst_cap);
-        LZ4HIP_FRAMING_TRY(be.last_error());
-    }
-    if (p.flags & kLz4fAcceptLinked) LZ4HIP_FRAMING_TRY(lz4f_linked_decode_run(be, linked));
-    be.launch(lz4f_info_kernel, fixed_grid(1), 64, t, (const int64_t*)(p.l.state + kPackedBad), p.flags, p.dst_cap, p.info);
+    LZ4HIP_FRAMING_TRY(lz4f_rows_run(be, p.rounds, t, p.flags, 1, nullptr, nullptr, bad));
+    be.launch(lz4f_info_kernel, fixed_grid(1), 64, t, (const unsigned long long*)bad, p.flags, p.rounds.dst_cap, p.info);
     if (p.flags & kLz4fVerifyContent) {
-        const XxhRows content = { p.dst, nullptr, 0, nullptr, t.walk + kLz4fWalkContentLen, 0, 0u, t.sums + n, 1 };
+        const XxhRows content = { p.rounds.dst, nullptr, 0, nullptr, t.walk + kLz4fWalkContentLen, 0, 0u, t.sums + t.max_blocks, 1 };
         LZ4HIP_FRAMING_TRY(xxh32_rows_run(be, content));
         be.launch(lz4f_final_kernel, fixed_grid(1), 64, p.src, t, p.info);
     }
@@ -1809,9 +1846,9 @@ int lz4f_decode_plan(B& be, const void* src, int64_t src_len, int32_t slot_bytes
     const Lz4fDecodeScratch d = lz4f_decode_scratch(scratch, p.slot_bytes, max_blocks, round_blocks);
     if (scratch_bytes < d.bytes) return be.fail(LZ4HIP_E_ARGUMENT, "lz4f decode: scratch_bytes < lz4hip_lz4f_decode_scratch_bytes");
     // (an empty source's rows are all empty: any address will do for them)
-    p.src = src ? (const uint8_t*)src : (const uint8_t*)scratch; p.src_len = src_len; p.flags = flags; p.t = d.t; p.l = d.l;
-    p.round = packed_round(max_blocks, round_blocks); p.slot = packed_slot(p.slot_bytes);
-    p.dst = (uint8_t*)dst; p.dst_cap = dst_cap; p.info = (Lz4fInfo*)info;
+    p.src = src ? (const uint8_t*)src : (const uint8_t*)scratch; p.src_len = src_len; p.flags = flags; p.t = d.t;
+    p.rounds = lz4f_rounds_plan(p.src, d.t, d.l, p.slot_bytes, round_blocks, (uint8_t*)dst, dst_cap);
+    p.info = (Lz4fInfo*)info;
     return 0;
 }
 
@@ -1958,27 +1995,16 @@ int lz4f_batch_encode(B& be, const void* src, int64_t src_len, const int64_t* sr
 inline Lz4fBatchTables lz4f_batch_tables(Carver& c, int64_t n, int64_t max_blocks)
 {
     Lz4fBatchTables t;
-    t.max_blocks = max_blocks; t.n = n;
+    t.n = n;
     t.total = c.take_as<int64_t>(256);
     t.min_bad = (unsigned long long*)t.total + 1;
-    t.walk = c.take_as<int64_t>(8 * kLz4fWalkSlots * n);
     t.item_at = c.take_as<int64_t>(8 * n);
     t.base = c.take_as<int64_t>(8 * n);
     t.item_bad = c.take_as<unsigned long long>(8 * n);
     t.content_off = c.take_as<int64_t>(8 * n);
     t.content_len = c.take_as<int64_t>(8 * n);
     t.content_sums = c.take_as<uint32_t>(4 * n);
-    t.src_off = c.take_as<int64_t>(8 * max_blocks);
-    t.hdr_off = c.take_as<int64_t>(8 * max_blocks);
-    t.dst_off = c.take_as<int64_t>(8 * (max_blocks + 1));
-    t.stored = c.take_as<int32_t>(4 * max_blocks);
-    t.dec_len = c.take_as<int32_t>(4 * max_blocks);
-    t.sum_len = c.take_as<int32_t>(4 * max_blocks);
-    t.result = c.take_as<int32_t>(4 * max_blocks);
-    t.item = c.take_as<int32_t>(4 * max_blocks);
-    t.sums = c.take_as<uint32_t>(4 * max_blocks);
-    t.row = c.take_as<uint8_t>(max_blocks);
-    t.plan = c.take_as<int32_t>(4 * max_blocks);
+    t.rows = lz4f_tables(c, max_blocks, n);
     return t;
 }
 struct Lz4fBatchDecodeScratch { Lz4fBatchTables t; int64_t* partial; PackedScratch l; int64_t bytes; };
@@ -1999,31 +2025,24 @@ inline int64_t lz4f_batch_decode_scratch_bytes(int64_t n, int32_t slot_bytes, in
 }
 
 struct Lz4fBatchDecodePlan {
-    Lz4fBatchDecodeArgs a; Lz4fBatchTables t; int64_t* partial; PackedScratch l; int64_t round, slot; uint8_t* dst; Lz4fBatchInfo* info;
+    Lz4fBatchDecodeArgs a; Lz4fBatchTables t; int64_t* partial; PackedPlan rounds; Lz4fBatchInfo* info;
 };
 
-// The two walks around their scan, the block checksums, then lz4f_decode_run's rounds over ALL max_blocks rows of the table with the
-// batch's sizes step and pack layout, the items' records, their content checksums as n rows of one launch, the batch's record.
-// With kLz4fAcceptLinked the linked items' rows are sized before the rounds and decoded after them (lz4hip_lz4f_linked.hpp).
-// Nothing is read on the host between the steps.
+// The two walks around their scan, then what both decodes of LZ4 frames share (lz4f_rows_run: the block checksums and the rounds over ALL
+// max_blocks rows of the table, a linked item's rows sized before them and decoded after them), the items' records, their content
+// checksums as n rows of one launch, the batch's record.  Nothing is read on the host between the steps.
 template <class B>
 int lz4f_batch_decode_run(B& be, const Lz4fBatchDecodePlan& p)
 {
     const Lz4fBatchDecodeArgs& a = p.a;
     const Lz4fBatchTables& t = p.t;
-    const int64_t m = t.max_blocks;
     LZ4HIP_FRAMING_TRY(be.fill(a.written_items, 0, sizeof(int64_t)));
     if (a.n == 0) {
         LZ4HIP_FRAMING_TRY(be.fill(a.dst_off, 0, sizeof(int64_t)));
         be.launch(lz4f_batch_empty_record_kernel, fixed_grid(1), 64, p.info);
         return be.last_error();
     }
-    LZ4HIP_FRAMING_TRY(be.fill(t.src_off, 0, (size_t)(8 * m)));
-    LZ4HIP_FRAMING_TRY(be.fill(t.stored, 0, (size_t)(4 * m)));
-    LZ4HIP_FRAMING_TRY(be.fill(t.dec_len, 0, (size_t)(4 * m)));
-    LZ4HIP_FRAMING_TRY(be.fill(t.sum_len, 0, (size_t)(4 * m)));
-    LZ4HIP_FRAMING_TRY(be.fill(t.item, 0, (size_t)(4 * m)));
-    LZ4HIP_FRAMING_TRY(be.fill(t.row, 0, (size_t)m));
+    LZ4HIP_FRAMING_TRY(lz4f_tables_init(be, t.rows));
     LZ4HIP_FRAMING_TRY(be.fill(t.total, 0, 8));
     LZ4HIP_FRAMING_TRY(be.fill(t.min_bad, 0xFF, 8));                   // the lowest failing item = none
     LZ4HIP_FRAMING_TRY(be.fill(t.item_bad, 0xFF, (size_t)(8 * a.n)));  // every item's lowest bad row = none
@@ -2031,43 +2050,11 @@ int lz4f_batch_decode_run(B& be, const Lz4fBatchDecodePlan& p)
     launch_scan(be, t.base, a.n, p.partial, t.total);
     be.launch(lz4f_batch_walk_kernel<true>, walk_grid(a.n), 64, a, t);
     LZ4HIP_FRAMING_TRY(be.last_error());
-    if (a.flags & kLz4fVerifyBlocks) {
-        const XxhRows rows = { a.src, t.src_off, 0, t.sum_len, nullptr, 0, 0u, t.sums, m };
-        LZ4HIP_FRAMING_TRY(xxh32_rows_run(be, rows));
-        be.launch(lz4f_batch_verify_kernel, stream_grid(m), kStreamThreads, a.src, t);
-    }
-    LZ4HIP_FRAMING_TRY(be.fill(p.l.state, 0, (size_t)kPackedStateBytes));
-    LZ4HIP_FRAMING_TRY(be.fill(p.l.state + kPackedBad, 0xFF, 8));
-    const Lz4fLinked linked = { a.src, p.dst, a.dst_cap, a.n, m, t.walk, t.base, t.total, t.src_off, t.stored, t.dst_off, t.row, t.plan, t.item_bad };
-    if (a.flags & kLz4fAcceptLinked) LZ4HIP_FRAMING_TRY(lz4f_linked_plan_run(be, linked));
-    const Grid pack_grid = copy_grid(p.round * p.slot);
-    int32_t parity = 0;
-    for (int64_t first = 0; first < m; first += p.round, parity ^= 1) {
-        PackedRound r;
-        r.first = first; r.cnt = m - first < p.round ? m - first : p.round; r.slot = p.slot; r.limit = a.slot_bytes; r.parity = parity;
-        r.cap_in = nullptr; r.caps = p.l.caps; r.result = t.result + first;
-        r.len_in = t.dec_len + first; r.lens_enc = p.l.lens;
-        r.ring = p.l.ring; r.offs = t.dst_off + first; r.lens = nullptr; r.state = p.l.state;
-        be.launch(packed_caps_kernel, stream_grid(r.cnt), kStreamThreads, r);
-        LZ4HIP_FRAMING_TRY(be.last_error());
-        lz4hip_batch_t rb = {};
-        rb.src = a.src; rb.src_off = t.src_off + first; rb.src_len = p.l.lens;
-        rb.dst = p.l.ring; rb.dst_stride = p.slot; rb.dst_cap = p.l.caps;
-        rb.result = r.result; rb.n_blocks = r.cnt;
-        LZ4HIP_FRAMING_TRY(be.decode(&rb, 0));
-        const Lz4fBatchRound br = { r, a.src, t.src_off + first, t.stored + first, t.row + first, t.item + first, t.walk, t.item_bad, t.plan + first };
-        be.launch(lz4f_batch_round_sizes_kernel, stream_grid(r.cnt), kStreamThreads, br);
-        launch_scan(be, r.offs, r.cnt, p.l.partial, p.l.state + kPackedTotal);
-        be.launch(packed_rebase_kernel, stream_grid(r.cnt), kStreamThreads, r);
-        Lz4fBatchRoundLayout layout = { br };
-        be.launch(lz4f_batch_round_pack_kernel, pack_grid, kStreamThreads, layout, p.dst, a.dst_cap);
-        LZ4HIP_FRAMING_TRY(be.last_error());
-    }
-    if (a.flags & kLz4fAcceptLinked) LZ4HIP_FRAMING_TRY(lz4f_linked_decode_run(be, linked));
+    LZ4HIP_FRAMING_TRY(lz4f_rows_run(be, p.rounds, t.rows, a.flags, a.n, t.base, t.total, t.item_bad));
     be.launch(lz4f_batch_offsets_out_kernel, stream_grid(a.n + 1), kStreamThreads, a, t);
     be.launch(lz4f_batch_info_kernel, stream_grid(a.n), kStreamThreads, a, t);
     if (a.flags & kLz4fVerifyContent) {
-        const XxhRows content = { p.dst, t.content_off, 0, nullptr, t.content_len, 0, 0u, t.content_sums, a.n };
+        const XxhRows content = { p.rounds.dst, t.content_off, 0, nullptr, t.content_len, 0, 0u, t.content_sums, a.n };
         LZ4HIP_FRAMING_TRY(xxh32_rows_run(be, content));
         be.launch(lz4f_batch_final_kernel, stream_grid(a.n), kStreamThreads, a, t);
     }
@@ -2094,8 +2081,8 @@ int lz4f_batch_decode_plan(B& be, const void* src, int64_t src_len, const int64_
     // (an empty source's rows are all empty: any address will do for them)
     a.src = src ? (const uint8_t*)src : (const uint8_t*)scratch; a.off = src_off; a.src_len = src_len; a.n = n; a.slot_bytes = slot; a.flags = flags;
     a.dst_cap = dst_cap; a.dst_off = dst_off; a.item_info = (Lz4fInfo*)item_info; a.written_items = written_items;
-    p.t = d.t; p.partial = d.partial; p.l = d.l; p.round = packed_round(max_blocks, round_blocks); p.slot = packed_slot(slot);
-    p.dst = (uint8_t*)dst; p.info = (Lz4fBatchInfo*)info;
+    p.t = d.t; p.partial = d.partial; p.rounds = lz4f_rounds_plan(a.src, d.t.rows, d.l, slot, round_blocks, (uint8_t*)dst, dst_cap);
+    p.info = (Lz4fBatchInfo*)info;
     return 0;
 }
 

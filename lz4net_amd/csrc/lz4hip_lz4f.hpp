@@ -22,6 +22,9 @@
 //             its payload the SOURCE, not the ring; the decoder sees it as an empty row -> lz4f_info_kernel -> [xxh32_rows_kernel, one
 //             row over the output] -> lz4f_final_kernel
 //
+// The decode is the batch of frames' (lz4hip_lz4f_batch.hpp) with one item: from the block checksums' verdict to the item's record,
+// everything but the walk is written here once for both, over one Lz4fTables whose rows name their item (or none: one item).
+//
 // The encoder's blocks are always independent (FLG.5) and use no dictionary; the decoder refuses dictionaries, and linked blocks unless
 // the caller accepts them (kLz4fAcceptLinked): each decodes only against the 64 KiB before it, in order, so a linked frame is one
 // serial chain -- lz4hip_lz4f_linked.hpp runs it on one wavefront, after the rounds, which see its rows as holes.  Every kernel here
@@ -352,17 +355,22 @@ constexpr int kLz4fWalkBlocks = 0, kLz4fWalkError = 1, kLz4fWalkErrorOff = 2, kL
 
 // The index: one table in caller scratch, max_blocks rows laid out as the arrays of a lz4hip_batch_t (src_off / dec_len / dst_off /
 // result) plus each block's size field offset, its stored length, the length its checksum covers (0 without block checksums) and
-// its raw / bad checksum bits.
+// its raw / bad checksum bits.  One frame's table and the table of a batch of frames (lz4hip_lz4f_batch.hpp) are this struct: the one
+// frame is the batch of one item, whose rows all belong to item 0 (item = nullptr) and whose walk record starts at walk[0].  In a
+// batch src_off is absolute and hdr_off stays relative to the row's item.
 struct Lz4fTables {
     int64_t max_blocks;
     int64_t* src_off; int64_t* hdr_off;
     int64_t* dst_off;                                                  // max_blocks + 1 entries: the compact decode's offsets
     int32_t* stored; int32_t* dec_len; int32_t* sum_len; int32_t* result;
-    uint32_t* sums;                                                    // max_blocks block checksums as computed, then the content's
+    uint32_t* sums;                                                    // max_blocks block checksums as computed; one frame: then the content's
     uint8_t* row;                                                      // kLz4fRow* bits
-    int64_t* walk;                                                     // kLz4fWalk* slots
     int32_t* plan;                                                     // a linked row's size, known before the rounds (lz4hip_lz4f_linked.hpp)
+    int32_t* item;                                                     // each row's item; nullptr: one item
+    int64_t* walk;                                                     // kLz4fWalk* slots per item
 };
+
+LZ4HIP_DEVICE int64_t lz4f_row_item(const int32_t* item, int64_t k) { return item ? item[k] : 0; }
 
 // what one walk found: the kLz4fWalk* slots before they are stored
 struct Lz4fWalk {
@@ -470,28 +478,33 @@ __global__ void __launch_bounds__(64) lz4f_walk_kernel(const uint8_t* src, int64
 }
 
 // after xxh32_rows_kernel over the rows' stored bytes: a row whose checksum does not match is a bad block, and the decoder is handed an
-// empty row in its place
-__global__ void __launch_bounds__(kStreamThreads) lz4f_verify_kernel(const uint8_t* src, Lz4fTables t)
+// empty row in its place.  The rows that were tabled: total[0] of them, none if they did not all fit; total == nullptr: one frame, tabled
+// while the table had rows.  Whether a row's frame carries block checksums is its item's FLG.4.
+__global__ void __launch_bounds__(kStreamThreads) lz4f_verify_kernel(const uint8_t* src, Lz4fTables t, const int64_t* total)
 {
-    const int64_t n = t.walk[kLz4fWalkBlocks] < t.max_blocks ? t.walk[kLz4fWalkBlocks] : t.max_blocks;
-    if (!(t.walk[kLz4fWalkFlg] & 0x10)) return;
-    for (int64_t k = (int64_t)blockIdx.x * kStreamThreads + threadIdx.x; k < n; k += (int64_t)gridDim.x * kStreamThreads)
+    const int64_t rows = total ? total[0] : t.walk[kLz4fWalkBlocks];
+    const int64_t n = rows <= t.max_blocks ? rows : (total ? 0 : t.max_blocks);
+    for (int64_t k = (int64_t)blockIdx.x * kStreamThreads + threadIdx.x; k < n; k += (int64_t)gridDim.x * kStreamThreads) {
+        if (!(t.walk[lz4f_row_item(t.item, k) * kLz4fWalkSlots + kLz4fWalkFlg] & 0x10)) continue;
         if (t.sums[k] != load_u32(src + t.src_off[k] + t.stored[k])) { t.row[k] |= kLz4fRowBadSum; t.dec_len[k] = 0; }
+    }
 }
 
-// One round of the compact decode (PackedRound: its caps, scan, rebase and state block are the packed paths') with what the twin steps
-// look at: the source, and the table's columns at row 0 of the round.
+// One round of the compact decode (PackedRound: its caps, scan, rebase and state block are the packed paths') with what its own sizes
+// step and pack layout look at: the source, the table's columns at row 0 of the round, and the per-item arrays whole.
 struct Lz4fRound {
     PackedRound a;
     const uint8_t* src;
     const int64_t* src_off; const int32_t* stored; const uint8_t* row;
-    const int64_t* walk;
     const int32_t* plan;
+    const int32_t* item;                                               // nullptr: one item
+    const int64_t* walk;
+    unsigned long long* item_bad;                                      // per item: its lowest bad row (~0: none); one frame: the state block's kPackedBad
 };
 
 // The bytes row k of the round takes, or -1 for a bad block: a row with a bad checksum; a raw row its stored size; a compressed row the
-// decoder's result, if it is one and within the FRAME's block maximum (it fits the slot either way).  A linked row takes its planned
-// size (0 for a dead one; its item's bad block is the plan's to report).
+// decoder's result, if it is one and within the block maximum of the ROW's frame (it fits the slot either way).  A linked row takes
+// its planned size (0 for a dead one; its item's bad block is the plan's to report).
 LZ4HIP_DEVICE int32_t lz4f_row_bytes(const Lz4fRound& r, int64_t k)
 {
     const uint8_t bits = r.row[k];
@@ -499,21 +512,22 @@ LZ4HIP_DEVICE int32_t lz4f_row_bytes(const Lz4fRound& r, int64_t k)
     if (bits & kLz4fRowBadSum) return -1;
     if (bits & kLz4fRowRaw) return r.stored[k];
     const int32_t res = r.a.result[k];
-    return res < 0 || res > (int32_t)r.walk[kLz4fWalkBlockMax] || res > r.a.limit ? -1 : res;
+    return res < 0 || res > (int32_t)r.walk[lz4f_row_item(r.item, k) * kLz4fWalkSlots + kLz4fWalkBlockMax] || res > r.a.limit ? -1 : res;
 }
 
-// compact_sizes_kernel's twin
+// The rounds' sizes step, in compact_sizes_kernel's place: the lowest bad row is kept PER ITEM (a round may begin and end in the middle
+// of one)
 __global__ void __launch_bounds__(kStreamThreads) lz4f_round_sizes_kernel(Lz4fRound r)
 {
     for (int64_t k = (int64_t)blockIdx.x * kStreamThreads + threadIdx.x; k < r.a.cnt; k += (int64_t)gridDim.x * kStreamThreads) {
         const int32_t len = lz4f_row_bytes(r, k);
         r.a.offs[k] = len < 0 ? 0 : len;
-        if (len < 0) atomicMin((unsigned long long*)(r.a.state + kPackedBad), (unsigned long long)(r.a.first + k));
+        if (len < 0) atomicMin(&r.item_bad[lz4f_row_item(r.item, k)], (unsigned long long)(r.a.first + k));
     }
 }
 
-// PackedLayout's twin: a raw row's payload lies in the source; a linked row has none (its bytes up to the next row's start are the
-// linked decode's to write)
+// The rounds' pack layout, in PackedLayout's place: a raw row's payload lies in the source; a linked row has none (its bytes up to the
+// next row's start are the linked decode's to write)
 struct Lz4fRoundLayout {
     Lz4fRound r;
     LZ4HIP_DEVICE int64_t count() const { return r.a.cnt; }
@@ -537,19 +551,17 @@ __global__ void __launch_bounds__(kStreamThreads) lz4f_round_pack_kernel(Lz4fRou
     copy_spans_from(L, dst, begin, end < cap ? end : cap);
 }
 
-// The record after the rounds, all but the content checksum's verdict.  Precedence, as a sequential reader meets them: a table too
-// small; a descriptor error (no block was walked); the lowest bad block; the walk's error (it lies after every tabled block); the
-// content size.  It also sets the length of the content checksum's row: the decoded total when that checksum is there, asked for, and
-// everything was written without an error; else 0.
-__global__ void __launch_bounds__(64) lz4f_info_kernel(Lz4fTables t, const int64_t* bad_slot, unsigned flags, int64_t dst_cap, Lz4fInfo* info)
+// One item's record after the rounds, all but the content checksum's verdict, from its walk slots w, its lowest bad row and its bytes
+// [begin, end) of the output; every offset in it is relative to the item.  Precedence, as a sequential reader meets them: a table too
+// small (`full`: error_offset -1, which the one-frame call replaces); a descriptor error (no block was walked); the lowest bad block;
+// the walk's error (it lies after every tabled block); the content size.  Returns whether the content checksum's row is to be summed:
+// that checksum is there, asked for, and the item was wholly written without an error.
+LZ4HIP_DEVICE bool lz4f_item_record(Lz4fInfo& r, const int64_t* w, unsigned long long bad, const Lz4fTables& t, bool full, int64_t begin, int64_t end,
+                                    unsigned flags, int64_t dst_cap)
 {
-    if (threadIdx.x != 0) return;
-    const int64_t* w = t.walk;
-    const unsigned long long bad = (unsigned long long)*bad_slot;
     const int flg = (int)w[kLz4fWalkFlg];
-    Lz4fInfo r;
     r.blocks = w[kLz4fWalkBlocks];
-    r.decoded_bytes = r.good_bytes = t.dst_off[t.max_blocks];
+    r.decoded_bytes = r.good_bytes = end - begin;
     r.error = (int32_t)w[kLz4fWalkError];
     r.error_offset = w[kLz4fWalkErrorOff];
     r.content_size = w[kLz4fWalkContentSize];
@@ -558,33 +570,52 @@ __global__ void __launch_bounds__(64) lz4f_info_kernel(Lz4fTables t, const int64
     r.block_max = (int32_t)w[kLz4fWalkBlockMax];
     r.flg = flg; r.bd = (int32_t)w[kLz4fWalkBd];
     r.checks = 0;
-    if (r.blocks > t.max_blocks) {
+    if (full) {
         r.error = kLz4fTableFull;
-        r.error_offset = w[kLz4fWalkFullOff];
+        r.error_offset = -1;
     } else if (bad != ~0ull) {
         r.error = (t.row[bad] & kLz4fRowBadSum) ? kLz4fBlockChecksumError : kLz4fCorruptBlock;
         r.error_offset = t.hdr_off[bad];
-        r.good_bytes = t.dst_off[bad];
+        r.good_bytes = t.dst_off[bad] - begin;
     } else if (r.error == kLz4fOk && r.kind == kLz4fKindFrame && r.content_size >= 0 && r.content_size != r.decoded_bytes) {
         r.error = kLz4fContentSizeError;
         r.error_offset = 6;
     }
-    const bool content = r.error == kLz4fOk && (flg & 0x04) && (flags & kLz4fVerifyContent) && r.decoded_bytes <= dst_cap;
+    const bool content = r.error == kLz4fOk && (flg & 0x04) && (flags & kLz4fVerifyContent) && end <= dst_cap;
     if (r.block_max > 0) {                                             // (a descriptor that parsed)
         r.checks = (flg & 0x10) ? ((flags & kLz4fVerifyBlocks) ? kLz4fCheckVerified : kLz4fCheckSkipped) : kLz4fCheckAbsent;
         r.checks |= ((flg & 0x04) ? (content ? kLz4fCheckVerified : kLz4fCheckSkipped) : kLz4fCheckAbsent) << 2;
     }
+    return content;
+}
+
+// The one frame's record: the item at [0, the decoded total); a table too small is reported at the size field of the first block that
+// did not fit.  It also sets the length of the content checksum's row: the decoded total, or 0 if it is not to be summed.
+__global__ void __launch_bounds__(64) lz4f_info_kernel(Lz4fTables t, const unsigned long long* bad, unsigned flags, int64_t dst_cap, Lz4fInfo* info)
+{
+    if (threadIdx.x != 0) return;
+    const bool full = t.walk[kLz4fWalkBlocks] > t.max_blocks;
+    Lz4fInfo r;
+    const bool content = lz4f_item_record(r, t.walk, *bad, t, full, 0, t.dst_off[t.max_blocks], flags, dst_cap);
+    if (full) r.error_offset = t.walk[kLz4fWalkFullOff];
     t.walk[kLz4fWalkContentLen] = content ? r.decoded_bytes : 0;
     *info = r;
+}
+
+// The content checksum's verdict, after its row was summed: `sum` against the four bytes at frame[trailer].  True if it turned the
+// record into an error.
+LZ4HIP_DEVICE bool lz4f_content_verdict(Lz4fInfo* info, uint32_t sum, const uint8_t* frame, int64_t trailer)
+{
+    if (((info->checks >> 2) & 3) != kLz4fCheckVerified || sum == load_u32(frame + trailer)) return false;
+    info->error = kLz4fContentChecksumError;
+    info->error_offset = trailer;
+    return true;
 }
 
 // after the content's row: the last verdict
 __global__ void __launch_bounds__(64) lz4f_final_kernel(const uint8_t* src, Lz4fTables t, Lz4fInfo* info)
 {
-    if (threadIdx.x != 0) return;
-    if (((info->checks >> 2) & 3) != kLz4fCheckVerified) return;
-    const int64_t at = t.walk[kLz4fWalkTrailer];
-    if (t.sums[t.max_blocks] != load_u32(src + at)) { info->error = kLz4fContentChecksumError; info->error_offset = at; }
+    if (threadIdx.x == 0) lz4f_content_verdict(info, t.sums[t.max_blocks], src, t.walk[kLz4fWalkTrailer]);
 }
 
 }  // namespace lz4hip

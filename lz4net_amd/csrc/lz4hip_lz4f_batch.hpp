@@ -14,12 +14,17 @@
 //   decode: lz4f_batch_walk_kernel<false> (ONE WAVEFRONT PER ITEM runs lz4f_walk_frame: the item's record and its block count) ->
 //           stream_scan_* (the first row of every item, the row total) -> lz4f_batch_walk_kernel<true> (the same walk again, writing
 //           rows at the item's base with absolute source offsets and the item's index) -> [xxh32_rows_kernel over all rows +
-//           lz4f_batch_verify_kernel] -> the compact decode's rounds over ALL max_blocks rows (packed_caps_kernel, the block decoder,
-//           lz4f_batch_round_sizes_kernel, the scan, packed_rebase_kernel, lz4f_batch_round_pack_kernel): a round may begin and end in
-//           the middle of an item; the lowest bad row is kept PER ITEM -> [the linked items, each on one wavefront:
+//           lz4f_verify_kernel] -> the one-frame decode's rounds over ALL max_blocks rows, the SAME kernels (packed_caps_kernel, the
+//           block decoder, lz4f_round_sizes_kernel, the scan, packed_rebase_kernel, lz4f_round_pack_kernel): a round may begin and
+//           end in the middle of an item; the lowest bad row is kept PER ITEM -> [the linked items, each on one wavefront:
 //           lz4hip_lz4f_linked.hpp, which also sizes their rows before the rounds] -> lz4f_batch_offsets_out_kernel (dst_off) ->
-//           lz4f_batch_info_kernel (one thread per item: lz4f_info_kernel's precedence, the item's content row) -> xxh32_rows_kernel
-//           (n rows of the output) -> lz4f_batch_final_kernel -> lz4f_batch_record_kernel
+//           lz4f_batch_info_kernel (one thread per item: lz4f_item_record, the item's content row) -> xxh32_rows_kernel (n rows of
+//           the output) -> lz4f_batch_final_kernel -> lz4f_batch_record_kernel
+//
+// The one-frame decode is the batch of one item: the table's rows (Lz4fTables), the round view, the sizes step, the pack layout, the
+// block checksum verdict, the item record and the content checksum's verdict are lz4hip_lz4f.hpp's, written once for both.  The walks
+// stay two kernels: the batch needs a count pass, a scan and a fill pass, and running a lone large frame's walk twice would double a
+// serial chain of dependent loads.
 //
 // A lane-per-item walk is the alternative should the walk dominate a measured profile; it is not built.
 // Every kernel here is launch-only work on the caller's stream over caller scratch; every table value is an ordinary store.
@@ -274,16 +279,11 @@ __global__ void __launch_bounds__(kStreamThreads) lz4f_batch_pack_kernel(Lz4fBat
 }
 
 // ---- decode ---------------------------------------------------------------------------------------------------------------------
-// The index of ALL items: Lz4fTables' columns with absolute source offsets (hdr_off stays relative to the row's item) and each row's
-// item, plus what is kept per item.
+// The index of ALL items: the rows of every item in one Lz4fTables (absolute source offsets, each row's item, kLz4fWalkSlots walk slots
+// per item), plus what is kept per item.
 struct Lz4fBatchTables {
-    int64_t max_blocks, n;
-    int64_t* src_off; int64_t* hdr_off;
-    int64_t* dst_off;                                                  // max_blocks + 1 entries: the compact decode's offsets
-    int32_t* stored; int32_t* dec_len; int32_t* sum_len; int32_t* result; int32_t* item;
-    uint32_t* sums;                                                    // max_blocks block checksums as computed
-    uint8_t* row;                                                      // kLz4fRow* bits
-    int64_t* walk;                                                     // kLz4fWalkSlots slots per item
+    Lz4fTables rows;
+    int64_t n;
     int64_t* item_at;                                                  // where the item starts in the source
     int64_t* base;                                                     // blocks per item, then (scanned in place) its first row
     int64_t* total;                                                    // [0]: the rows all items need
@@ -291,7 +291,6 @@ struct Lz4fBatchTables {
     unsigned long long* min_bad;                                       // the lowest failing item (~0: none)
     int64_t* content_off; int64_t* content_len;                        // the n rows of the content checksums in the output
     uint32_t* content_sums;
-    int32_t* plan;                                                     // a linked row's size, known before the rounds (lz4hip_lz4f_linked.hpp)
 };
 
 struct Lz4fBatchDecodeArgs {
@@ -306,7 +305,7 @@ struct Lz4fBatchDecodeArgs {
     int64_t* written_items;
 };
 
-LZ4HIP_DEVICE bool lz4f_batch_full(const Lz4fBatchTables& t) { return t.total[0] > t.max_blocks; }
+LZ4HIP_DEVICE bool lz4f_batch_full(const Lz4fBatchTables& t) { return t.total[0] > t.rows.max_blocks; }
 
 // One wavefront per item runs the one-frame walk on it.  The count pass (kFill = false) leaves the item's record and its block count;
 // the fill pass, after the scan, writes the item's rows at its base.  An item whose offsets decrease or leave [0, src_len] is not
@@ -323,11 +322,11 @@ __global__ void __launch_bounds__(64) lz4f_batch_walk_kernel(Lz4fBatchDecodeArgs
         Lz4fWalk r;
         if (valid) {
             r = lz4f_walk_frame(a.src + at, len, a.slot_bytes, a.flags, [&](int64_t k, int64_t pos, int32_t size, uint8_t bits, int32_t sum_bytes) {
-                if (kFill && lane == 0 && base + k < t.max_blocks) {
+                if (kFill && lane == 0 && base + k < t.rows.max_blocks) {
                     const int64_t j = base + k;
-                    t.src_off[j] = at + pos + 4; t.hdr_off[j] = pos; t.stored[j] = size;
-                    t.dec_len[j] = lz4f_row_dec_len(bits, size); t.sum_len[j] = sum_bytes ? size : 0;
-                    t.row[j] = bits; t.item[j] = (int32_t)i;
+                    t.rows.src_off[j] = at + pos + 4; t.rows.hdr_off[j] = pos; t.rows.stored[j] = size;
+                    t.rows.dec_len[j] = lz4f_row_dec_len(bits, size); t.rows.sum_len[j] = sum_bytes ? size : 0;
+                    t.rows.row[j] = bits; t.rows.item[j] = (int32_t)i;
                 }
             });
         } else {
@@ -335,124 +334,33 @@ __global__ void __launch_bounds__(64) lz4f_batch_walk_kernel(Lz4fBatchDecodeArgs
             r.err = kLz4fBatchBadOffsets; r.kind = kLz4fKindFrame; r.flg = r.bd = 0; r.block_max = 0;
         }
         if (!kFill && lane == 0) {
-            lz4f_walk_store(t.walk + i * kLz4fWalkSlots, r, -1);
+            lz4f_walk_store(t.rows.walk + i * kLz4fWalkSlots, r, -1);
             t.item_at[i] = at;
             t.base[i] = r.blocks;
         }
     }
 }
 
-// lz4f_verify_kernel over the rows of all items
-__global__ void __launch_bounds__(kStreamThreads) lz4f_batch_verify_kernel(const uint8_t* src, Lz4fBatchTables t)
-{
-    const int64_t n = lz4f_batch_full(t) ? 0 : t.total[0];
-    for (int64_t k = (int64_t)blockIdx.x * kStreamThreads + threadIdx.x; k < n; k += (int64_t)gridDim.x * kStreamThreads) {
-        if (!(t.walk[(int64_t)t.item[k] * kLz4fWalkSlots + kLz4fWalkFlg] & 0x10)) continue;
-        if (t.sums[k] != load_u32(src + t.src_off[k] + t.stored[k])) { t.row[k] |= kLz4fRowBadSum; t.dec_len[k] = 0; }
-    }
-}
-
-// Lz4fRound's twin: the columns at row 0 of the round, the per-item arrays whole
-struct Lz4fBatchRound {
-    PackedRound a;
-    const uint8_t* src;
-    const int64_t* src_off; const int32_t* stored; const uint8_t* row; const int32_t* item;
-    const int64_t* walk;
-    unsigned long long* item_bad;
-    const int32_t* plan;
-};
-
-// lz4f_row_bytes with the block maximum of the ROW's item
-LZ4HIP_DEVICE int32_t lz4f_batch_row_bytes(const Lz4fBatchRound& r, int64_t k)
-{
-    const uint8_t bits = r.row[k];
-    if (bits & kLz4fRowLinked) return r.plan[k];
-    if (bits & kLz4fRowBadSum) return -1;
-    if (bits & kLz4fRowRaw) return r.stored[k];
-    const int32_t res = r.a.result[k];
-    return res < 0 || res > (int32_t)r.walk[(int64_t)r.item[k] * kLz4fWalkSlots + kLz4fWalkBlockMax] || res > r.a.limit ? -1 : res;
-}
-
-// lz4f_round_sizes_kernel's twin: the lowest bad row per item (a round may begin and end in the middle of one)
-__global__ void __launch_bounds__(kStreamThreads) lz4f_batch_round_sizes_kernel(Lz4fBatchRound r)
-{
-    for (int64_t k = (int64_t)blockIdx.x * kStreamThreads + threadIdx.x; k < r.a.cnt; k += (int64_t)gridDim.x * kStreamThreads) {
-        const int32_t len = lz4f_batch_row_bytes(r, k);
-        r.a.offs[k] = len < 0 ? 0 : len;
-        if (len < 0) atomicMin(&r.item_bad[r.item[k]], (unsigned long long)(r.a.first + k));
-    }
-}
-
-struct Lz4fBatchRoundLayout {
-    Lz4fBatchRound r;
-    LZ4HIP_DEVICE int64_t count() const { return r.a.cnt; }
-    LZ4HIP_DEVICE int64_t start(int64_t k) const { return r.a.offs[k]; }
-    LZ4HIP_DEVICE CopySeg seg(int64_t k) const
-    {
-        CopySeg s;
-        const int32_t len = (r.row[k] & kLz4fRowLinked) ? 0 : lz4f_batch_row_bytes(r, k);   // (a linked row is a hole: Lz4fRoundLayout)
-        s.start = s.pbegin = r.a.offs[k];
-        s.pend = s.start + (len < 0 ? 0 : len);
-        s.payload = (r.row[k] & kLz4fRowRaw) ? r.src + r.src_off[k] : r.a.ring + k * r.a.slot;
-        s.flags = s.original = s.clen = 0;
-        return s;
-    }
-    LZ4HIP_DEVICE uint8_t head_byte(const CopySeg&, int64_t) const { return 0; }   // (no header bytes)
-};
-
-__global__ void __launch_bounds__(kStreamThreads) lz4f_batch_round_pack_kernel(Lz4fBatchRoundLayout L, uint8_t* dst, int64_t cap)
-{
-    const int64_t begin = L.r.a.offs[0], end = L.r.a.state[kPackedBase + (L.r.a.parity ^ 1)];
-    copy_spans_from(L, dst, begin, end < cap ? end : cap);
-}
-
 // dst_off[i] = the table's offset at the item's first row, dst_off[n] = the total
 __global__ void __launch_bounds__(kStreamThreads) lz4f_batch_offsets_out_kernel(Lz4fBatchDecodeArgs a, Lz4fBatchTables t)
 {
+    const int64_t m = t.rows.max_blocks;
     for (int64_t i = (int64_t)blockIdx.x * kStreamThreads + threadIdx.x; i <= a.n; i += (int64_t)gridDim.x * kStreamThreads) {
-        const int64_t k = i < a.n && !lz4f_batch_full(t) ? t.base[i] : t.max_blocks;
-        a.dst_off[i] = t.dst_off[k < t.max_blocks ? k : t.max_blocks];
+        const int64_t k = i < a.n && !lz4f_batch_full(t) ? t.base[i] : m;
+        a.dst_off[i] = t.rows.dst_off[k < m ? k : m];
     }
 }
 
-// One thread per item: lz4f_info_kernel's record and precedence with offsets relative to the item, the length of the item's content
-// row (non-zero only if the checksum is there, asked for, the item wholly written and without an error), the prefix of items that lie
-// wholly inside dst_cap, the lowest failing item.  With a table that is too small every item's outcome is LZ4HIP_LZ4F_TABLE_FULL.
+// One thread per item: its record (lz4f_item_record over its bytes of the output), the length of the item's content row, the prefix of
+// items that lie wholly inside dst_cap, the lowest failing item.  With a table that is too small every item's outcome is
+// LZ4HIP_LZ4F_TABLE_FULL.
 __global__ void __launch_bounds__(kStreamThreads) lz4f_batch_info_kernel(Lz4fBatchDecodeArgs a, Lz4fBatchTables t)
 {
     const bool full = lz4f_batch_full(t);
     for (int64_t i = (int64_t)blockIdx.x * kStreamThreads + threadIdx.x; i < a.n; i += (int64_t)gridDim.x * kStreamThreads) {
-        const int64_t* w = t.walk + i * kLz4fWalkSlots;
-        const unsigned long long bad = t.item_bad[i];
         const int64_t begin = a.dst_off[i], end = a.dst_off[i + 1];
-        const int flg = (int)w[kLz4fWalkFlg];
         Lz4fInfo r;
-        r.blocks = w[kLz4fWalkBlocks];
-        r.decoded_bytes = r.good_bytes = end - begin;
-        r.error = (int32_t)w[kLz4fWalkError];
-        r.error_offset = w[kLz4fWalkErrorOff];
-        r.content_size = w[kLz4fWalkContentSize];
-        r.frame_bytes = w[kLz4fWalkFrameBytes];
-        r.kind = (int32_t)w[kLz4fWalkKind];
-        r.block_max = (int32_t)w[kLz4fWalkBlockMax];
-        r.flg = flg; r.bd = (int32_t)w[kLz4fWalkBd];
-        r.checks = 0;
-        if (full) {
-            r.error = kLz4fTableFull;
-            r.error_offset = -1;
-        } else if (bad != ~0ull) {
-            r.error = (t.row[bad] & kLz4fRowBadSum) ? kLz4fBlockChecksumError : kLz4fCorruptBlock;
-            r.error_offset = t.hdr_off[bad];
-            r.good_bytes = t.dst_off[bad] - begin;
-        } else if (r.error == kLz4fOk && r.kind == kLz4fKindFrame && r.content_size >= 0 && r.content_size != r.decoded_bytes) {
-            r.error = kLz4fContentSizeError;
-            r.error_offset = 6;
-        }
-        const bool content = r.error == kLz4fOk && (flg & 0x04) && (a.flags & kLz4fVerifyContent) && end <= a.dst_cap;
-        if (r.block_max > 0) {                                         // (a descriptor that parsed)
-            r.checks = (flg & 0x10) ? ((a.flags & kLz4fVerifyBlocks) ? kLz4fCheckVerified : kLz4fCheckSkipped) : kLz4fCheckAbsent;
-            r.checks |= ((flg & 0x04) ? (content ? kLz4fCheckVerified : kLz4fCheckSkipped) : kLz4fCheckAbsent) << 2;
-        }
+        const bool content = lz4f_item_record(r, t.rows.walk + i * kLz4fWalkSlots, t.item_bad[i], t.rows, full, begin, end, a.flags, a.dst_cap);
         t.content_off[i] = begin;
         t.content_len[i] = content ? r.decoded_bytes : 0;
         a.item_info[i] = r;
@@ -465,16 +373,9 @@ __global__ void __launch_bounds__(kStreamThreads) lz4f_batch_info_kernel(Lz4fBat
 // after the content rows: the items' last verdict
 __global__ void __launch_bounds__(kStreamThreads) lz4f_batch_final_kernel(Lz4fBatchDecodeArgs a, Lz4fBatchTables t)
 {
-    for (int64_t i = (int64_t)blockIdx.x * kStreamThreads + threadIdx.x; i < a.n; i += (int64_t)gridDim.x * kStreamThreads) {
-        Lz4fInfo* info = a.item_info + i;
-        if (((info->checks >> 2) & 3) != kLz4fCheckVerified) continue;
-        const int64_t at = t.walk[i * kLz4fWalkSlots + kLz4fWalkTrailer];
-        if (t.content_sums[i] != load_u32(a.src + t.item_at[i] + at)) {
-            info->error = kLz4fContentChecksumError;
-            info->error_offset = at;
+    for (int64_t i = (int64_t)blockIdx.x * kStreamThreads + threadIdx.x; i < a.n; i += (int64_t)gridDim.x * kStreamThreads)
+        if (lz4f_content_verdict(a.item_info + i, t.content_sums[i], a.src + t.item_at[i], t.rows.walk[i * kLz4fWalkSlots + kLz4fWalkTrailer]))
             atomicMin(t.min_bad, (unsigned long long)i);
-        }
-    }
 }
 
 // The batch record: the counts, and the lowest failing item with its outcome (what a sequential loop over the items raises first); a
