@@ -56,6 +56,17 @@ namespace LZ4hip
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
         private static extern unsafe int lz4hip_decoded_sizes_host(Batch* b, long* dstOff, int* dstCap, SizesInfo* info);
 
+        // Block batches decoded against ONE shared dictionary (include/lz4hip.h, "block batches decoded against a shared dictionary"):
+        // K4os.Compression.LZ4's LZ4Codec.Decode(source, target, dictionary) for many blocks in one call.  Only the dictionary's last
+        // 65 535 bytes can be reached; dictLen = 0 (dict may be null) is the plain call.  One device, no _multi form.
+        // (Declarations only: not compiled or run by this repository's tests, tests/test_gpu_dict_decode.py calls the same symbols
+        // through ctypes.)
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        private static extern unsafe int lz4hip_decode_batch_dict_host(Batch* b, byte* dict, long dictLen, int knownOutputSize);
+
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        private static extern unsafe int lz4hip_decoded_sizes_dict_host(Batch* b, long dictLen, long* dstOff, int* dstCap, SizesInfo* info);
+
         // A batch encoded into ONE buffer of exactly the bytes produced (include/lz4hip.h, "a block batch encoded into one packed buffer"):
         // b's dst fields are ignored, b.dst_cap_all is the slot width (MaximumOutputLength of the longest block); dstOff[n + 1] and
         // packedLen[n] come back in the layout lz4hip_decoded_sizes_host and an offsets-form decode batch read.  dstCap may be anything
@@ -227,6 +238,40 @@ namespace LZ4hip
             for (int i = 0; i < n; i++)
             {
                 if (results[i] != lens[i])                                    // src/LZ4pn/LZ4Codec.Unsafe.cs:373-378
+                    throw new ArgumentException("LZ4 block is corrupted, or invalid length has been given.");
+                output[i] = new byte[outputLengths[i]];
+                Buffer.BlockCopy(dst, (int)dstOff[i], output[i], 0, outputLengths[i]);
+            }
+            return output;
+        }
+
+        /// <summary>Decompresses every block against one shared dictionary into a buffer of outputLengths[i] bytes
+        /// (LZ4_decompress_safe_usingDict per block, knownOutputLength: true semantics).</summary>
+        public static unsafe byte[][] DecodeWithDictionary(byte[][] blocks, int[] outputLengths, byte[] dictionary)
+        {
+            int n = blocks.Length;
+            long total = 0, outTotal = 0;
+            var srcOff = new long[n]; var dstOff = new long[n]; var lens = new int[n];
+            for (int i = 0; i < n; i++)
+            {
+                srcOff[i] = total; lens[i] = blocks[i].Length; total += lens[i];
+                dstOff[i] = outTotal; outTotal += outputLengths[i];
+            }
+            var src = new byte[Math.Max(total, 1)]; var dst = new byte[Math.Max(outTotal, 1)];
+            for (int i = 0; i < n; i++) Buffer.BlockCopy(blocks[i], 0, src, (int)srcOff[i], lens[i]);
+            var results = new int[n];
+            var dict = dictionary.Length > 0 ? dictionary : new byte[1];
+            fixed (byte* ps = src, pd = dst, pdict = dict)
+            fixed (long* so = srcOff, dof = dstOff)
+            fixed (int* sl = lens, dc = outputLengths, res = results)
+            {
+                var b = new Batch { src = ps, src_off = so, src_len = sl, dst = pd, dst_off = dof, dst_cap = dc, result = res, n_blocks = n };
+                Check(lz4hip_decode_batch_dict_host(&b, pdict, dictionary.Length, 1));
+            }
+            var output = new byte[n][];
+            for (int i = 0; i < n; i++)
+            {
+                if (results[i] != lens[i])
                     throw new ArgumentException("LZ4 block is corrupted, or invalid length has been given.");
                 output[i] = new byte[outputLengths[i]];
                 Buffer.BlockCopy(dst, (int)dstOff[i], output[i], 0, outputLengths[i]);

@@ -105,6 +105,32 @@ int lz4hip_decode_batch_device(const lz4hip_batch_t* b, int known_output_size, v
 int lz4hip_encode_batch_host(const lz4hip_batch_t* b, int mode);
 int lz4hip_decode_batch_host(const lz4hip_batch_t* b, int known_output_size);
 
+/* ---- block batches decoded against a shared dictionary -------------------------------------------------------------------------------
+ * LZ4_decompress_safe_usingDict in a loop (K4os.Compression.LZ4: LZ4Codec.Decode(source, target, dictionary)): every block of the batch
+ * shares ONE dictionary dict[0, dict_len).  Block i's result and bytes are what lz4hip_decode_batch_device gives for it, known_output_size
+ * 0 or 1, when the dictionary's bytes lie immediately in front of its dst: the return values and the rules are that call's.
+ *   - A match source at index s of the block's output with -dict_len <= s < 0 reads dict[dict_len + s].
+ *   - A source before that is the error a plain block gets for a source before the block, with the same return value.
+ *   - Only the last 65 535 bytes of the dictionary can ever be reached (an offset has 16 bits); the others are never read.
+ *   - Nothing outside [dict, dict + dict_len) is read, and nothing is written that the plain call would not write.
+ *   - dict_len == 0 (dict may then be NULL) is the plain call, result for result and byte for byte.
+ *   - The dictionary may have any alignment.  It is not copied: it must stay valid until the kernels have run.
+ * The device call carries the contract of lz4hip_decode_batch_device: device pointers of the current device -- dict included -- launch-only
+ * on `stream`, 0 or LZ4HIP_E_*; dict_len < 0, and dict == NULL with dict_len > 0, are LZ4HIP_E_ARGUMENT, checked before a device is looked
+ * for.  THE COST: these calls run the wavefront mapping (one wavefront per block) at every batch size -- lz4hip_dispatch_counts moves
+ * LZ4HIP_K_DECODE_WAVE only -- so a large dictionary batch decodes at that mapping's rate, not at the lane mapping's.  Each wavefront
+ * first copies the dictionary's last 4 096 bytes into its LDS mirror, so that runs of short sequences that copy out of the dictionary
+ * stay on the decoder's fast paths.
+ * The host call stages the blocks as lz4hip_decode_batch_host does; the dictionary's reachable bytes are uploaded once per call into
+ * per-thread grow-only device memory (freed by lz4hip_release_workspaces) and have landed before any slice's kernels start.
+ * The sizes calls are lz4hip_decoded_sizes_device / _host for such blocks: a match may start up to min(dict_len, 65 535) bytes before its
+ * block.  They need no byte of the dictionary; the scratch query is lz4hip_decoded_sizes_scratch_bytes.
+ * Out of scope: encoding against a dictionary (the reference has no such parse to be bit-exact to, and preloading the encoders' tables is
+ * a design of its own); LZ4 frames with a dictionary (below: they stay refused); a dictionary per block; the lane mapping; a _multi host
+ * form; the compact and packed decode forms. */
+int lz4hip_decode_batch_dict_device(const lz4hip_batch_t* b, const void* dict, int64_t dict_len, int known_output_size, void* stream);
+int lz4hip_decode_batch_dict_host(const lz4hip_batch_t* b, const void* dict, int64_t dict_len, int known_output_size);
+
 /* Host-resident batches sharded over several GPUs of the node: block i is processed by the (i mod N)-th device
  * selected by device_mask (bit d = HIP device d; 0 = every visible device) -- the round-robin partition of
  * SURVEY.md 8e.  One PERSISTENT worker thread and one staging pipeline per device (started on first use, reused by every
@@ -456,6 +482,10 @@ int lz4hip_decoded_sizes_device(const lz4hip_batch_t* b, int64_t* dst_off, int32
  * lz4hip_release_workspaces), runs the device call and synchronises; only result, dst_off, dst_cap and info travel back.  Returns 0
  * (block failures are in result and info) or LZ4HIP_E_*. */
 int lz4hip_decoded_sizes_host(const lz4hip_batch_t* b, int64_t* dst_off, int32_t* dst_cap, lz4hip_sizes_info_t* info);
+/* The same two calls for blocks that are decoded against a dictionary of dict_len >= 0 bytes (lz4hip_decode_batch_dict_*, above). */
+int lz4hip_decoded_sizes_dict_device(const lz4hip_batch_t* b, int64_t dict_len, int64_t* dst_off, int32_t* dst_cap,
+                                     void* scratch, int64_t scratch_bytes, lz4hip_sizes_info_t* info, void* stream);
+int lz4hip_decoded_sizes_dict_host(const lz4hip_batch_t* b, int64_t dict_len, int64_t* dst_off, int32_t* dst_cap, lz4hip_sizes_info_t* info);
 
 /* ---- a block batch encoded into one packed buffer ---------------------------------------------------
  * The pack step the framed encoders end in, for the plain block batch: n blocks are compressed as lz4hip_encode_batch_device compresses
@@ -684,7 +714,7 @@ int lz4hip_xxh32_rows_device(const void* data, const int64_t* off, int64_t strid
 #define LZ4HIP_LZ4F_VERIFY_CONTENT   2u   /* one serial row over dst[0, decoded_bytes): only when all of it was written and no block is bad */
 /* ... and an opt-in of the four decode calls (lz4hip_lz4f_decode_* and lz4hip_lz4f_batch_decode_*): frames whose blocks are LINKED
  * (FLG.5 clear -- the default of LZ4F_compressFrame, python-lz4 and Arrow's LZ4_FRAME codec for content above one block) are decoded
- * instead of refused with UNSUPPORTED_LINKED.  Without the flag every call is what it was; dictionaries stay refused either way.
+ * instead of refused with UNSUPPORTED_LINKED.  Without the flag every call is what it was; frames with a dictionary stay refused either way (block batches: lz4hip_decode_batch_dict_*).
  * COST: a linked frame is ONE serial chain and runs on ONE wavefront, so one large linked frame decodes far slower than on a host core
  * (INTEGRATION.md 4 has a lone wavefront's figures).  The flag pays only in batches of many items, one wavefront each.  With it:
  *  - an independent frame or item takes the path it always took: the same bytes, the same record;
@@ -712,7 +742,7 @@ int lz4hip_xxh32_rows_device(const void* data, const int64_t* off, int64_t strid
 #define LZ4HIP_LZ4F_BAD_HEADER             2   /* version, a reserved bit, or a block size id below 4 */
 #define LZ4HIP_LZ4F_HEADER_CHECKSUM        3
 #define LZ4HIP_LZ4F_UNSUPPORTED_LINKED     4   /* FLG.5 clear: linked blocks decode only in order, each against the 64 KiB before it (LZ4HIP_LZ4F_ACCEPT_LINKED takes them) */
-#define LZ4HIP_LZ4F_UNSUPPORTED_DICT       5   /* FLG.0 set */
+#define LZ4HIP_LZ4F_UNSUPPORTED_DICT       5   /* FLG.0 set: frames with a dictionary stay refused (block batches: lz4hip_decode_batch_dict_*) */
 #define LZ4HIP_LZ4F_SLOT_TOO_SMALL         6   /* the frame's block maximum exceeds slot_bytes: call again with .block_max */
 #define LZ4HIP_LZ4F_TRUNCATED              7   /* the frame ends inside the descriptor, a size field, data, a checksum, or before its EndMark */
 #define LZ4HIP_LZ4F_BAD_BLOCK_SIZE         8   /* a size field above the frame's block maximum (tested before the truncation rule) */
@@ -771,7 +801,7 @@ int lz4hip_lz4f_decode_host(const void* src, int64_t src_len, unsigned flags, vo
  * launch-only on the caller's stream, no device value read on the host, no allocation, scratch from the caller (the *_scratch_bytes
  * queries), arguments checked before the device is looked for, 0 or LZ4HIP_E_* returned.
  *
- * Out of scope: frames with a dictionary (the item's outcome says so; frames with linked blocks are the caller's choice:
+ * Out of scope: frames with a dictionary (the item's outcome says so; block batches against one: lz4hip_decode_batch_dict_*; frames with linked blocks are the caller's choice:
  * LZ4HIP_LZ4F_ACCEPT_LINKED); following appended frames inside one item (an
  * item is ONE frame, what lies behind it is left alone and shows only in frame_bytes); span forms (chosen items of an arena); a block
  * decoder for large blocks -- one wavefront still decodes one block.

@@ -120,6 +120,8 @@ SYMBOLS = [
     ("lz4hip_decode_batch_device", C.c_int, [C.POINTER(Batch), C.c_int, C.c_void_p]),
     ("lz4hip_encode_batch_host", C.c_int, [C.POINTER(Batch), C.c_int]),
     ("lz4hip_decode_batch_host", C.c_int, [C.POINTER(Batch), C.c_int]),
+    ("lz4hip_decode_batch_dict_device", C.c_int, [C.POINTER(Batch), C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
+    ("lz4hip_decode_batch_dict_host", C.c_int, [C.POINTER(Batch), C.c_void_p, C.c_int64, C.c_int]),
     ("lz4hip_encode_batch_host_multi", C.c_int, [C.POINTER(Batch), C.c_int, C.c_uint64]),
     ("lz4hip_decode_batch_host_multi", C.c_int, [C.POINTER(Batch), C.c_int, C.c_uint64]),
     ("lz4hip_synth_device", C.c_int, [C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]),
@@ -175,6 +177,8 @@ SYMBOLS = [
     ("lz4hip_decoded_sizes_scratch_bytes", C.c_int64, [C.c_int64]),
     ("lz4hip_decoded_sizes_device", C.c_int, [C.POINTER(Batch), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     ("lz4hip_decoded_sizes_host", C.c_int, [C.POINTER(Batch), C.c_void_p, C.c_void_p, C.POINTER(SizesInfo)]),
+    ("lz4hip_decoded_sizes_dict_device", C.c_int, [C.POINTER(Batch), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    ("lz4hip_decoded_sizes_dict_host", C.c_int, [C.POINTER(Batch), C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(SizesInfo)]),
     ("lz4hip_encode_packed_scratch_bytes", C.c_int64, [C.c_int64, C.c_int32, C.c_int64]),
     ("lz4hip_encode_packed_device", C.c_int, [C.POINTER(Batch), C.c_int, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                               C.c_void_p, C.c_void_p]),

@@ -78,6 +78,32 @@ def decode(src: torch.Tensor, src_len, dst: torch.Tensor, out_size, known_output
     return result
 
 
+def _dictionary(dictionary, like):
+    """(pointer, length, the tensor to keep alive) of the dictionary a batch shares: a 1-D uint8 CUDA tensor on the blocks' device; None
+    and an empty one are no dictionary"""
+    if dictionary is None:
+        return 0, 0, None
+    if not _p.is_device_vector(dictionary, "uint8"):
+        raise _p.ArgumentException("the dictionary must be a 1-D uint8 CUDA tensor")
+    if dictionary.device != like.device:
+        raise _p.ArgumentException("the dictionary must be on the blocks' device")
+    d = dictionary.contiguous()
+    return (d.data_ptr() if d.numel() else 0), d.numel(), d
+
+
+def decode_dict(src: torch.Tensor, src_len, dst: torch.Tensor, out_size, dictionary: torch.Tensor | None, known_output_size: bool = True,
+                result: torch.Tensor | None = None) -> torch.Tensor:
+    """decode() with ONE dictionary shared by every block (lz4hip_decode_batch_dict_device, LZ4_decompress_safe_usingDict in a loop):
+    a match may start in `dictionary` (1-D uint8, on the device), whose bytes count as lying in front of each block's output; only its
+    last 65 535 can be reached.  Results and rules are decode()'s.  The wavefront mapping decodes these batches at every size."""
+    ptr, n_dict, keep_dict = _dictionary(dictionary, src)
+    if result is None:
+        result = torch.empty(src.shape[0], dtype=torch.int32, device=src.device)
+    b, keep = _make_batch(src, src_len, dst, out_size, result)
+    _lib.check(_lib.lib().lz4hip_decode_batch_dict_device(C.byref(b), ptr, n_dict, 1 if known_output_size else 0, _stream()))
+    return result
+
+
 def synth(dist: int, seed: int, first_block: int, n_blocks: int, length: int = BLOCK, stride: int | None = None,
           out: torch.Tensor | None = None, device=None, block_step: int = 1) -> torch.Tensor:
     """Synthetic blocks generated on the device (bit-identical to oracle/synth.c); row i is synthetic block
@@ -131,12 +157,46 @@ def read_sizes_info(info: torch.Tensor) -> _lib.SizesInfo:
     return _p.read_record(info, _lib.SizesInfo)
 
 
+def _dict_len(dict_len) -> int:
+    if isinstance(dict_len, bool) or not isinstance(dict_len, int) or dict_len < 0:
+        raise _p.ArgumentException("dict_len must be an int >= 0")
+    return dict_len
+
+
+def decoded_sizes_dict(src: torch.Tensor, src_len, dict_len: int, src_off: torch.Tensor | None = None, result: torch.Tensor | None = None):
+    """decoded_sizes() for blocks that are decoded against a dictionary of dict_len bytes (lz4hip_decoded_sizes_dict_device): a match may
+    start up to min(dict_len, 65 535) bytes before its block.  The walk needs the dictionary's length, not its bytes."""
+    return _decoded_sizes(src, src_len, src_off, result, _dict_len(dict_len))
+
+
+def decode_packed_dict(src: torch.Tensor, src_len, dictionary: torch.Tensor | None, src_off: torch.Tensor | None = None):
+    """decode_packed() against a shared dictionary: decoded_sizes_dict, ONE synchronisation, then lz4hip_decode_batch_dict_device
+    (unknown size) on the offsets and capacities the query wrote.  Returns (dst, offsets, results) as decode_packed does."""
+    ptr, n_dict, keep_dict = _dictionary(dictionary, src)
+    n, b, keep = _source(src, src_len, src_off)
+    sizes, offsets, info = _decoded_sizes(src, src_len, src_off, None, n_dict)
+    total = read_sizes_info(info).decoded_bytes
+    dst = torch.empty(total, dtype=torch.uint8, device=src.device)
+    results = torch.empty(n, dtype=torch.int32, device=src.device)
+    if n == 0:
+        return dst, offsets, results
+    guard = dst if total > 0 else torch.empty(1, dtype=torch.uint8, device=src.device)      # (dst must be non-NULL even if nothing fits)
+    b.dst, b.dst_off, b.dst_cap, b.result = guard.data_ptr(), offsets.data_ptr(), sizes.data_ptr(), results.data_ptr()
+    _lib.check(_lib.lib().lz4hip_decode_batch_dict_device(C.byref(b), ptr, n_dict, 0, _stream()))
+    return dst, offsets, results
+
+
 def decoded_sizes(src: torch.Tensor, src_len, src_off: torch.Tensor | None = None, result: torch.Tensor | None = None):
     """What an unknown-size decode of every block would produce, without decoding it (lz4hip_decoded_sizes_device): block i is row i
     of a 2-D `src`, or src[src_off[i]:] of a 1-D one.  Returns (sizes, offsets, info), all on the device and not waited for:
     sizes[i] = max(result[i], 0) (int32), offsets (int64, n + 1) their exclusive scan -- the dst_cap and dst_off of a packed decode --
     and the lz4hip_sizes_info_t record as four int64 (read_sizes_info).  `result` (int32, n) receives the per-block results: bytes
     produced, or -(error position), as LZ4_uncompress_unknownOutputSize with an unbounded output."""
+    return _decoded_sizes(src, src_len, src_off, result, None)
+
+
+def _decoded_sizes(src, src_len, src_off, result, dict_len):
+    """decoded_sizes (dict_len None) and decoded_sizes_dict"""
     n, b, keep = _source(src, src_len, src_off)
     sizes = torch.empty(n, dtype=torch.int32, device=src.device)
     offsets = torch.empty(n + 1, dtype=torch.int64, device=src.device)
@@ -146,8 +206,12 @@ def decoded_sizes(src: torch.Tensor, src_len, src_off: torch.Tensor | None = Non
         b.result = result.data_ptr()
     need = _lib.lib().lz4hip_decoded_sizes_scratch_bytes(n)
     scratch = torch.empty(max(need, 1), dtype=torch.uint8, device=src.device)
-    _lib.check(_lib.lib().lz4hip_decoded_sizes_device(C.byref(b), offsets.data_ptr(), sizes.data_ptr(), scratch.data_ptr(), need,
-                                                      info.data_ptr(), _stream()))
+    if dict_len is None:
+        _lib.check(_lib.lib().lz4hip_decoded_sizes_device(C.byref(b), offsets.data_ptr(), sizes.data_ptr(), scratch.data_ptr(), need,
+                                                          info.data_ptr(), _stream()))
+    else:
+        _lib.check(_lib.lib().lz4hip_decoded_sizes_dict_device(C.byref(b), dict_len, offsets.data_ptr(), sizes.data_ptr(), scratch.data_ptr(), need,
+                                                               info.data_ptr(), _stream()))
     return sizes, offsets, info
 
 

@@ -238,6 +238,51 @@ class LZ4Codec(metaclass=_LZ4CodecMeta):
         cls._service.Decode(buf, inputOffset + 8, input_length, result, 0, output_length, True)
         return bytes(result)
 
+    # ---- many blocks against one dictionary: K4os.Compression.LZ4's LZ4Codec.Decode(source, target, dictionary), batched ------------
+    @classmethod
+    def decode_many_with_dictionary(cls, blocks, dictionary, out_sizes=None) -> list:
+        """[the bytes of block b decoded with `dictionary` in front of its output, for b in blocks], every block in ONE
+        lz4hip_decode_batch_dict_host call (LZ4_decompress_safe_usingDict in a loop).  out_sizes: the exact decoded size of every block
+        (the known-size decode: a block that does not decode to exactly that many bytes raises, as Decode does); None: the sizes are
+        walked first (lz4hip_decoded_sizes_dict_host) and the blocks decoded to what they produce.  A corrupt block raises
+        ArgumentException, as Decode does."""
+        if blocks is None:
+            raise ArgumentNullException("blocks")
+        if dictionary is None:
+            raise ArgumentNullException("dictionary")
+        bufs = [bytes(_as_bytes(b, "blocks")) for b in blocks]
+        dic = np.ascontiguousarray(_as_bytes(dictionary, "dictionary"))
+        n = len(bufs)
+        if out_sizes is not None:
+            out_sizes = [int(v) for v in out_sizes]
+            if len(out_sizes) != n or any(v < 0 or v > _INT_MAX for v in out_sizes):
+                raise ArgumentException("out_sizes must hold one size >= 0 per block")
+        if n == 0:
+            return []
+        src_len = np.array([len(b) for b in bufs], dtype=np.int32)
+        src_off = np.concatenate(([0], np.cumsum(src_len[:-1], dtype=np.int64))).astype(np.int64)
+        src = np.frombuffer(b"".join(bufs) or b"\0", dtype=np.uint8)
+        res = np.zeros(n, dtype=np.int32)
+        dict_ptr = dic.ctypes.data if dic.size else None
+        if out_sizes is None:
+            dst_len = np.zeros(n, dtype=np.int32)
+            dst_off = np.zeros(n + 1, dtype=np.int64)
+            info = _lib.SizesInfo()
+            b = _p.host_blocks(src, src_off, src_len, src, src_off, src_len, res)
+            _lib.check(_lib.lib().lz4hip_decoded_sizes_dict_host(C.byref(b), dic.size, dst_off.ctypes.data, dst_len.ctypes.data, C.byref(info)))
+            if info.first_error >= 0:
+                raise ArgumentException(_CORRUPT)
+            dst_off = dst_off[:n].copy()
+        else:
+            dst_len = np.array(out_sizes, dtype=np.int32)
+            dst_off = np.concatenate(([0], np.cumsum(dst_len[:-1], dtype=np.int64))).astype(np.int64)
+        dst = np.zeros(max(int(dst_len.astype(np.int64).sum()), 1), dtype=np.uint8)
+        b = _p.host_blocks(src, src_off, src_len, dst, dst_off, dst_len, res)
+        _lib.check(_lib.lib().lz4hip_decode_batch_dict_host(C.byref(b), dict_ptr, dic.size, 0 if out_sizes is None else 1))
+        if not (res == (dst_len if out_sizes is None else src_len)).all():     # (Decode64: produced / consumed is not what was promised)
+            raise ArgumentException(_CORRUPT)
+        return [dst[int(dst_off[i]):int(dst_off[i]) + int(dst_len[i])].tobytes() for i in range(n)]
+
     # ---- batched Wrap / Unwrap (SURVEY.md 8f-2): many messages, ONE GPU batch ---------------------------
     @classmethod
     def WrapMany(cls, messages, high_compression: bool = False) -> list:

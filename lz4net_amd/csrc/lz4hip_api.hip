@@ -920,6 +920,29 @@ int launch_decode(const lz4hip_batch_t* b, int known, hipStream_t stream)
     return 0;
 }
 
+// lz4hip_decode_batch_dict_*: every block against one dictionary in device memory, of which the kernel is given the bytes a match can
+// reach -- the last 65 535.  The wavefront mapping at every batch size: the lane mapping has no dictionary mode (include/lz4hip.h).
+int launch_decode_dict(const lz4hip_batch_t* b, const void* dict, int64_t dict_len, int known, hipStream_t stream)
+{
+    if (b->n_blocks == 0) return 0;
+    const Batch d = to_device_batch(*b);
+    const int reach = (int)hostbatch::dict_reach(dict_len);
+    const uint8_t* dict_end = reach > 0 ? (const uint8_t*)dict + dict_len : nullptr;
+    const unsigned waves = kWaveDecodeWavesPerGroup, grid = (unsigned)((d.n_blocks + waves - 1) / waves);
+    if (known) hipLaunchKernelGGL(decode_dict_kernel<true>, dim3(grid), dim3(64 * waves), 0, stream, d, dict_end, reach);
+    else       hipLaunchKernelGGL(decode_dict_kernel<false>, dim3(grid), dim3(64 * waves), 0, stream, d, dict_end, reach);
+    count_dispatch(LZ4HIP_K_DECODE_WAVE);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int check_dict(const void* dict, int64_t dict_len)
+{
+    if (dict_len < 0) return fail(LZ4HIP_E_ARGUMENT, "dictionary: dict_len < 0");
+    if (dict_len > 0 && !dict) return fail(LZ4HIP_E_ARGUMENT, "dictionary: dict is NULL and dict_len > 0");
+    return 0;
+}
+
 // Pinned (page-locked) host staging, grow-only, per calling thread: two slots so that the host can fill / drain
 // one slice while the device works on the other.
 struct Pinned {
@@ -971,6 +994,7 @@ struct HostPipe {
 // kernels of a slot on the slot's own stream, events between them.
 struct HostContext {
     Scratch scratch;
+    Scratch dict;                                                    // lz4hip_decode_batch_dict_host: the call's dictionary, apart from the slots' images (which move when they grow)
     Pinned pinned_in[kHostSlots], pinned_out[kHostSlots];
     HostPipe pipe;
     uint8_t* d_in[kHostSlots] = {};
@@ -990,6 +1014,17 @@ struct HostContext {
             d_in[k] = (uint8_t*)scratch.p + (size_t)k * (size_t)(in_bytes + out_bytes);
             d_out[k] = d_in[k] + in_bytes;
         }
+        return 0;
+    }
+    // (pageable host memory: the runtime stages it; the wait is what lets kernels on any stream, of any pipeline, read it)
+    int dict_upload(const uint8_t* from, int64_t bytes, uint8_t*& dev)
+    {
+        int rc = dict.reserve((size_t)bytes);
+        if (rc) return rc;
+        if ((rc = pipe.init())) return rc;
+        HIP_TRY(hipMemcpyAsync(dict.p, from, (size_t)bytes, hipMemcpyHostToDevice, pipe.s_in));
+        HIP_TRY(hipStreamSynchronize(pipe.s_in));
+        dev = (uint8_t*)dict.p;
         return 0;
     }
     uint8_t* pin_in(int slot) { return (uint8_t*)pinned_in[slot].p; }
@@ -1050,6 +1085,7 @@ void release_host_context(int dev)
 {
     if (HostContext* hc = host_context(dev, false)) {
         hc->scratch.release();
+        hc->dict.release();
         for (int k = 0; k < kHostSlots; k++) { hc->pinned_in[k].release(); hc->pinned_out[k].release(); }
     }
 }
@@ -1449,6 +1485,42 @@ int lz4hip_decode_batch_host(const lz4hip_batch_t* b, int known_output_size)
     return run_host_batch(b, !known_output_size, decoder_run(known_output_size));
 }
 
+int lz4hip_decode_batch_dict_device(const lz4hip_batch_t* b, const void* dict, int64_t dict_len, int known_output_size, void* stream)
+{
+    int rc = check_batch(b);
+    if (rc) return rc;
+    if ((rc = check_dict(dict, dict_len))) return rc;
+    if ((rc = ensure_device())) return rc;
+    return launch_decode_dict(b, dict, dict_len, known_output_size, (hipStream_t)stream);
+}
+
+// The dictionary goes up once, on the calling thread's context, and has landed before a slice is staged; the slices then travel as those of
+// lz4hip_decode_batch_host do -- as two pipelines from host_workers_for's size on, whose kernels read the one copy.
+int lz4hip_decode_batch_dict_host(const lz4hip_batch_t* b, const void* dict, int64_t dict_len, int known_output_size)
+{
+    int rc = check_batch(b);
+    if (rc) return rc;
+    if ((rc = check_dict(dict, dict_len))) return rc;
+    if (b->n_blocks == 0) return 0;
+    if ((rc = ensure_device())) return rc;
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    HostContext* hc = host_context(dev);
+    if (!hc) return fail(LZ4HIP_E_DEVICE, "device index out of range");
+    const int known = known_output_size;
+    auto make_run = [known](const uint8_t* d_dict, int64_t reach) {
+        return [=](const lz4hip_batch_t* db, hipStream_t s) { return launch_decode_dict(db, d_dict, reach, known, s); };
+    };
+    const int workers = host_workers_for(b, 0);
+    if (workers > 1) {
+        const uint8_t* d_dict = nullptr;
+        int64_t reach = 0;
+        if ((rc = hostbatch::upload_dictionary(*hc, dict, dict_len, d_dict, reach))) return rc;
+        return run_host_batch_multi(b, !known, 1ull << dev, make_run(d_dict, reach), 0, workers);
+    }
+    return hostbatch::run_host_batch_dict(*hc, b, dict, dict_len, !known, make_run, knob(kKnobHostSlices), knob(kKnobHostThreads));
+}
+
 int lz4hip_encode_batch_host_multi(const lz4hip_batch_t* b, int mode, uint64_t device_mask)
 {
     return run_host_batch_multi(b, true, device_mask, encoder_run(mode), mode == LZ4HIP_MODE_HC ? kHcHostSliceBlocks : 0);
@@ -1790,6 +1862,31 @@ int lz4hip_decoded_sizes_host(const lz4hip_batch_t* b, int64_t* dst_off, int32_t
     HipBackend be = {};
     if (int rc = stream_host_context(be)) return rc;
     return hostbatch::decoded_sizes_host(be, b, dst_off, dst_cap, info, knob(kKnobSizesGroups), knob(kKnobHostThreads));
+}
+
+// (the walk looks at no byte of the dictionary: its length is all these take)
+int lz4hip_decoded_sizes_dict_device(const lz4hip_batch_t* b, int64_t dict_len, int64_t* dst_off, int32_t* dst_cap, void* scratch, int64_t scratch_bytes,
+                                     lz4hip_sizes_info_t* info, void* stream)
+{
+    if (!b) return fail(LZ4HIP_E_ARGUMENT, "decoded sizes: batch descriptor is NULL");
+    if (b->n_blocks < 0) return fail(LZ4HIP_E_ARGUMENT, "decoded sizes: n_blocks < 0");
+    if (dict_len < 0) return fail(LZ4HIP_E_ARGUMENT, "dictionary: dict_len < 0");
+    if (scratch_bytes < sizes_scratch_bytes(b->n_blocks)) return fail(LZ4HIP_E_ARGUMENT, "decoded sizes: scratch_bytes < lz4hip_decoded_sizes_scratch_bytes");
+    if (b->n_blocks == 0 && !dst_off && !info) return 0;                // (nothing to write)
+    int rc = ensure_device();
+    if (rc) return rc;
+    HipBackend be = { (hipStream_t)stream };
+    return decoded_sizes(be, b, dst_off, dst_cap, scratch, scratch_bytes, info, knob(kKnobSizesGroups), dict_len);
+}
+
+int lz4hip_decoded_sizes_dict_host(const lz4hip_batch_t* b, int64_t dict_len, int64_t* dst_off, int32_t* dst_cap, lz4hip_sizes_info_t* info)
+{
+    if (!b) return fail(LZ4HIP_E_ARGUMENT, "decoded sizes: batch descriptor is NULL");
+    if (b->n_blocks < 0) return fail(LZ4HIP_E_ARGUMENT, "decoded sizes: n_blocks < 0");
+    if (dict_len < 0) return fail(LZ4HIP_E_ARGUMENT, "dictionary: dict_len < 0");
+    HipBackend be = {};
+    if (int rc = stream_host_context(be)) return rc;
+    return hostbatch::decoded_sizes_host(be, b, dst_off, dst_cap, info, knob(kKnobSizesGroups), knob(kKnobHostThreads), hostbatch::HostLimits(), dict_len);
 }
 
 int64_t lz4hip_encode_packed_scratch_bytes(int64_t n_blocks, int32_t slot_bytes, int64_t round_blocks)

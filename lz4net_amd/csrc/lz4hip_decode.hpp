@@ -45,6 +45,12 @@
 #ifndef LZ4HIP_STAT_PATH
 #define LZ4HIP_STAT_PATH(slot, cond) ((void)0)   /* slots 26 .. 34, which path a sequence took: only a build whose counter array has them defines it (tests/simt/emu_kernels.cpp) */
 #endif
+#ifndef LZ4HIP_DICT_PRELOAD
+#define LZ4HIP_DICT_PRELOAD kWaveRingBytes       /* bytes of the dictionary a wavefront copies into its LDS mirror first; 0 (tools/dict_decode_rate.py's A/B build only): none, every source before the block takes the general path -- slower, the same bytes */
+#endif
+#ifndef LZ4HIP_STAT_DICT
+#define LZ4HIP_STAT_DICT(slot, n) ((void)0)      /* where the bytes before the block came from in the DICT mode (tests/simt/emu_dict.cpp, DictStat below) */
+#endif
 // Section timers of the wavefront decoder (tools/dec_wave_sections.hip defines these to s_memtime accumulators; nothing in product builds).
 #ifndef LZ4HIP_DEC_T0
 #define LZ4HIP_DEC_DECL() ((void)0)
@@ -162,17 +168,49 @@ constexpr int kWaveLdsBytes = kWaveRingBytes + kWaveBurstRecBytes;
 // HISTORY: the `history` bytes before dst exist and a match may start in them (a linked block of an LZ4 frame: lz4hip_lz4f_linked.hpp).
 // Only the general path knows them: the burst and the short path leave a source before the block to it, as they leave an error, it
 // reads dst at indices below 0, and the LDS mirror never holds bytes before the block.  Without HISTORY the argument is not looked at.
-template <bool KNOWN, bool HISTORY = false>
-LZ4HIP_DEVICE int decode_block(const uint8_t* src, int src_len, uint8_t* dst, int out_size, unsigned char* ring, int history = 0)
+//
+// DICT: an external prefix, a dictionary shared by every block of a batch (decode_dict_kernel below).  Its dict_len bytes END at dict_end and
+// count as lying in front of the in-place history: index s of the block's output is dst[s] for s >= -history, and dict_end[s + history] for
+// -history - dict_len <= s < -history; anything before that is the error a source before the block is.  The caller passes at most the
+// 65 535 bytes a match can reach.  Before the first sequence the wavefront copies the last min(4 096, history + dict_len) of those bytes into
+// the LDS mirror, at the slots their negative indices have, and starts ring_from there: the burst and the short path then serve a source
+// before the block under the rule they serve any source by -- what the mirror still holds after the step -- and leave every other one to the
+// general path, which reads memory lane by lane and remains the definition; the long path copies a match's part in the dictionary with
+// wave_copy and the rest, whose sources all lie at -history or behind, with wave_match_copy at the same offset.  Nothing outside
+// [dict_end - dict_len, dict_end) is read.  Without DICT the two arguments are not looked at.
+enum DictStat { kDictPreload = 0, kDictBurstMirror, kDictShortMirror, kDictGeneralMemory, kDictGeneralMirror, kDictLongBytes, kDictLongCopies, kDictRefused, kDictStats };
+
+template <bool KNOWN, bool HISTORY = false, bool DICT = false>
+LZ4HIP_DEVICE int decode_block(const uint8_t* src, int src_len, uint8_t* dst, int out_size, unsigned char* ring, int history = 0,
+                               const uint8_t* dict_end = nullptr, int dict_len = 0)
 {
     const int lane = wv::lane();
     const int iend = src_len, oend = out_size;
     int ip = 0, op = 0;
     int ring_from = 0;                  // output bytes [max(ring_from, op - kWaveRingBytes), op) are in the ring
+    const int before = HISTORY ? history : 0;               // bytes in front of dst[0] that are dst's own
+    const int reach = before + (DICT ? dict_len : 0);       // ... and with the dictionary's: how far before the block a match may start
 
     if (!KNOWN && iend == 0) return 0;                      // original/lz4.c:946 returns -(0)
     SrcWindow win;
     win.init(src, src_len);
+    if (DICT) {
+        // the mirror's slot g holds index g - 4 096: 16 bytes per lane where a group lies wholly in the dictionary or wholly in dst
+        const int m = reach < LZ4HIP_DICT_PRELOAD ? reach : LZ4HIP_DICT_PRELOAD;
+        for (int g = lane * 16; g < kWaveRingBytes; g += 64 * 16) {
+            const int s = g - kWaveRingBytes;
+            if (s + 16 <= -m) continue;
+            if (s >= -m && (s + 16 <= -before || s >= -before)) {
+                store_v16(ring + g, load_v16(s < -before ? dict_end + (s + before) : dst + s));
+            } else {
+                for (int k = 0; k < 16; k++)
+                    if (s + k >= -m) ring[g + k] = s + k < -before ? dict_end[s + k + before] : dst[s + k];
+            }
+        }
+        wv::mem_sync();
+        ring_from = -m;
+        LZ4HIP_STAT_DICT(kDictPreload, lane == 0 ? m : 0);
+    }
 
     // A BURST: a run of short sequences in one step (round 4).  The two paths below handle one sequence per trip of this loop,
     // ~100 wave-instructions and ~940 cycles of dependent latency each -- which is what a batch too small for the lane mapping
@@ -261,10 +299,11 @@ LZ4HIP_DEVICE int decode_block(const uint8_t* src, int src_len, uint8_t* dst, in
                 const bool hist = live & !is_lit & (srel < 0);
                 const int habs = op + srel;
                 const int ring_lo = op - kWaveRingBytes > ring_from ? op - kWaveRingBytes : ring_from;
-                if (!wv::any(hist & ((habs < ring_lo) | (habs < 0)))) {          // (a source before the block is an error: lz4.c:863 / :980, general path)
+                if (!wv::any(hist & ((habs < ring_lo) | (DICT ? false : habs < 0)))) {   // (a source before the block is an error: lz4.c:863 / :980, general path; DICT: one the mirror holds is served)
                     uint32_t val = litb;
                     bool res = is_lit | !live;
                     if (hist) { val = ring[habs & (kWaveRingBytes - 1)]; res = true; }
+                    LZ4HIP_STAT_DICT(kDictBurstMirror, hist && habs < 0 ? 1 : 0);
                     // sources inside the burst: pull from the lane that produces the byte, until nothing is left
                     int rounds = 0;
                     while (wv::any(!res)) {
@@ -305,12 +344,13 @@ LZ4HIP_DEVICE int decode_block(const uint8_t* src, int src_len, uint8_t* dst, in
             if (tll <= 2 && tmlc != 15) {
                 const int t_lit_end = op + tll, t_ml = tmlc + kMinMatch;
                 const int t_off = (int)((t5 >> (8 + 8 * tll)) & 0xFFFFu);
-                if (t_off >= t_ml + tll && t_off <= t_lit_end) {
-                    const int t_ref = t_lit_end - t_off;
-                    // (the mirror serves what it is sure to hold AFTER this step, which stores at most 2 + 18 bytes: the slots of older bytes
-                    //  are the ones this step's store takes, and nothing orders a lane's read against another lane's store.  Such a source
-                    //  comes from memory.  A constant, not this sequence's own length: no instruction more than without it.)
-                    const int ring_lo = op - kWaveRingShortServed > ring_from ? op - kWaveRingShortServed : ring_from;
+                // (the mirror serves what it is sure to hold AFTER this step, which stores at most 2 + 18 bytes: the slots of older bytes
+                //  are the ones this step's store takes, and nothing orders a lane's read against another lane's store.  Such a source
+                //  comes from memory.  A constant, not this sequence's own length: no instruction more than without it.)
+                const int ring_lo = op - kWaveRingShortServed > ring_from ? op - kWaveRingShortServed : ring_from;
+                const int t_ref = t_lit_end - t_off;
+                // (DICT: a source before the block is this path's only where the mirror serves it)
+                if (t_off >= t_ml + tll && (t_off <= t_lit_end || (DICT && t_ref >= ring_lo))) {
                     const int sidx = t_ref + lane - tll;             // source of this lane's match byte (lanes >= tll)
                     const uint32_t lit = (uint32_t)(t5 >> 8) >> lane8;             // lanes < tll: their literal
                     // (two copies of the store on purpose: the one behind the LDS gather must not inherit the global
@@ -326,6 +366,7 @@ LZ4HIP_DEVICE int decode_block(const uint8_t* src, int src_len, uint8_t* dst, in
                     }
                     wv::mem_sync();
                     LZ4HIP_STAT(24, lane == 0); LZ4HIP_STAT_PATH(26, lane == 0 && t_ref >= ring_lo); LZ4HIP_STAT_PATH(27, lane == 0 && t_ref < ring_lo);
+                    LZ4HIP_STAT_DICT(kDictShortMirror, lane == 0 && t_ref < 0 ? 1 : 0);
                     ip += 3 + tll; op = t_lit_end + t_ml;
                     LZ4HIP_DEC_T(2);
                     continue;
@@ -367,7 +408,7 @@ LZ4HIP_DEVICE int decode_block(const uint8_t* src, int src_len, uint8_t* dst, in
         const int off = (int)(win.peek(p) | (win.peek(p + 1) << 8));
         p += 2;
         const int ref = lit_end - off;
-        if (ref < (HISTORY ? -history : 0)) return -p;
+        if (ref < -reach) { LZ4HIP_STAT_DICT(kDictRefused, lane == 0 ? 1 : 0); return -p; }
         int ml = (int)(token & 15);
         if (ml == 15) {
             if (KNOWN) {
@@ -395,9 +436,12 @@ LZ4HIP_DEVICE int decode_block(const uint8_t* src, int src_len, uint8_t* dst, in
             const uint32_t via_lit = wv::shuffle(lit_byte, from_lit < 0 ? 0 : from_lit);
             const int ring_lo = match_end - kWaveRingBytes > ring_from ? match_end - kWaveRingBytes : ring_from;   // (as in the short path: what the mirror holds after this step)
             uint32_t v = lit_byte;
-            if (in_match) v = from_lit >= 0 ? via_lit : (sidx >= ring_lo ? (uint32_t)ring[sidx & (kWaveRingBytes - 1)] : (uint32_t)dst[sidx]);
+            if (in_match) v = from_lit >= 0 ? via_lit : (sidx >= ring_lo ? (uint32_t)ring[sidx & (kWaveRingBytes - 1)]
+                                                                        : (uint32_t)(DICT && sidx < -before ? dict_end[sidx + before] : dst[sidx]));
             if (lane < ll || in_match) { dst[op + lane] = (uint8_t)v; ring[(op + lane) & (kWaveRingBytes - 1)] = (uint8_t)v; }
             LZ4HIP_STAT_PATH(28, in_match && from_lit >= 0); LZ4HIP_STAT_PATH(29, in_match && from_lit < 0 && sidx >= ring_lo); LZ4HIP_STAT_PATH(30, in_match && from_lit < 0 && sidx < ring_lo);
+            LZ4HIP_STAT_DICT(kDictGeneralMirror, in_match && sidx < 0 && sidx >= ring_lo ? 1 : 0);
+            LZ4HIP_STAT_DICT(kDictGeneralMemory, in_match && sidx < -before && sidx < ring_lo ? 1 : 0);
         } else {
             LZ4HIP_STAT_PATH(31, lane == 0);
             ring_from = match_end;                           // the long copies below bypass the ring
@@ -406,6 +450,14 @@ LZ4HIP_DEVICE int decode_block(const uint8_t* src, int src_len, uint8_t* dst, in
                 else wave_copy(dst + op, src + ip, ll);
                 wv::mem_sync();
             }
+            if (DICT && off != 0 && ref < -before) {
+                // the match starts in the dictionary: that part is a plain copy, and behind it every source lies at -before or later
+                const int nd = ml < -before - ref ? ml : -before - ref;
+                wave_copy(dst + lit_end, dict_end + (ref + before), nd);
+                wv::mem_sync();
+                LZ4HIP_STAT_DICT(kDictLongBytes, lane == 0 ? nd : 0); LZ4HIP_STAT_DICT(kDictLongCopies, lane == 0 ? 1 : 0);
+                if (ml > nd) wave_match_copy(dst, lit_end + nd, off, ml - nd);
+            } else
             if (off != 0) wave_match_copy(dst, lit_end, off, ml);
         }
         wv::mem_sync();
@@ -429,6 +481,22 @@ __global__ void __launch_bounds__(64 * kWaveDecodeWavesPerGroup) decode_kernel(B
     const uint8_t* src = batch_src(b, blk);
     uint8_t* dst = batch_dst(b, blk);
     const int r = decode_block<KNOWN>(src, src_len, dst, out_size, rings + wv::wave_in_block() * kWaveLdsBytes);
+    if (wv::lane() == 0) b.result[blk] = r;
+}
+
+// Every block of the batch against ONE dictionary, whose dict_len <= 65 535 bytes end at dict_end (lz4hip_decode_batch_dict_*): the same
+// grid, the same LDS and the same Batch as decode_kernel, every block on this mapping.
+template <bool KNOWN>
+__global__ void __launch_bounds__(64 * kWaveDecodeWavesPerGroup) decode_dict_kernel(Batch b, const uint8_t* dict_end, int dict_len)
+{
+    LZ4HIP_STATIC_LDS(rings, kWaveDecodeWavesPerGroup * kWaveLdsBytes);
+    const int64_t blk = (int64_t)blockIdx.x * (blockDim.x >> 6) + wv::wave_in_block();
+    if (blk >= b.n_blocks) return;
+    const int src_len = wv::uniform(batch_src_len(b, blk));
+    const int out_size = wv::uniform(batch_dst_cap(b, blk));
+    const uint8_t* src = batch_src(b, blk);
+    uint8_t* dst = batch_dst(b, blk);
+    const int r = decode_block<KNOWN, false, true>(src, src_len, dst, out_size, rings + wv::wave_in_block() * kWaveLdsBytes, 0, dict_end, dict_len);
     if (wv::lane() == 0) b.result[blk] = r;
 }
 

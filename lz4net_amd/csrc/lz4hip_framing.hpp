@@ -1211,19 +1211,22 @@ inline int64_t sizes_scratch_bytes(int64_t n) { return n <= 0 ? 0 : sizes_scratc
 
 // a.n > 0; a.offs has n + 1 entries and receives the offsets, a.offs[n] the total
 template <class B>
-int decoded_sizes_run(B& be, const SizesArgs& a, int64_t* partial, SizesInfo* info, int groups)
+int decoded_sizes_run(B& be, const SizesArgs& a, int64_t* partial, SizesInfo* info, int groups, int32_t history = -1)
 {
     LZ4HIP_FRAMING_TRY(be.fill(a.min_bad, 0xFF, 8));                   // min_bad = none
-    be.launch(sizes_walk_kernel, sizes_grid(a.n, groups), kSizesThreads, a);
+    if (history < 0) be.launch(sizes_walk_kernel, sizes_grid(a.n, groups), kSizesThreads, a);
+    else             be.launch(sizes_walk_dict_kernel, sizes_grid(a.n, groups), kSizesThreads, a, history);
     launch_scan(be, a.offs, a.n, partial, a.offs + a.n);
     if (info) be.launch(sizes_info_kernel, fixed_grid(1), 64, a, info);
     return be.last_error();
 }
 
-// reads b's src, src_off / src_stride, src_len / src_len_all, result and n_blocks; any of result, dst_off, dst_cap and info may be NULL
+// reads b's src, src_off / src_stride, src_len / src_len_all, result and n_blocks; any of result, dst_off, dst_cap and info may be NULL.
+// dict_len >= 0: the blocks are decoded against a dictionary of that many bytes (lz4hip_decoded_sizes_dict_*), whose last 65 535 a match
+// may reach; -1: blocks that stand alone.
 template <class B>
 int decoded_sizes(B& be, const lz4hip_batch_t* b, int64_t* dst_off, int32_t* dst_cap, void* scratch, int64_t scratch_bytes,
-                  lz4hip_sizes_info_t* info, int groups = 0)
+                  lz4hip_sizes_info_t* info, int groups = 0, int64_t dict_len = -1)
 {
     if (!b) return be.fail(LZ4HIP_E_ARGUMENT, "decoded sizes: batch descriptor is NULL");
     const int64_t n = b->n_blocks;
@@ -1241,7 +1244,7 @@ int decoded_sizes(B& be, const lz4hip_batch_t* b, int64_t* dst_off, int32_t* dst
     SizesArgs a;
     a.src = (const uint8_t*)b->src; a.src_off = b->src_off; a.src_stride = b->src_stride; a.src_len = b->src_len; a.src_len_all = b->src_len_all;
     a.n = n; a.result = b->result ? b->result : l.result; a.dst_cap = dst_cap; a.offs = dst_off ? dst_off : l.offs; a.min_bad = l.min_bad;
-    return decoded_sizes_run(be, a, l.partial, (SizesInfo*)info, groups);
+    return decoded_sizes_run(be, a, l.partial, (SizesInfo*)info, groups, dict_len < 0 ? -1 : (int32_t)(dict_len < 65535 ? dict_len : 65535));
 }
 
 // ---- a block batch encoded into one packed buffer (lz4hip_packed.hpp) -------------------------------------------------------------------

@@ -355,13 +355,47 @@ int run_host_batch(Stage& st, const lz4hip_batch_t* hb, bool dst_len_is_result, 
     return err;
 }
 
+// ---- a host-pointer batch decoded against one dictionary ------------------------------------------------------------------------------
+// lz4hip_decode_batch_dict_host: the bytes of the dictionary that a match can reach -- its last 65 535 -- are uploaded ONCE per call, into
+// staging of the stage's that is the dictionary's alone, and the upload is complete before the slice loop starts: whichever stream a
+// slice's kernels run on, and whichever pipeline they belong to, they find it there.  The stage has for this
+//
+//     int      dict_upload(from, bytes, dev)          reserves `bytes` of device memory (grow-only), copies the host bytes there, WAITS
+//                                                     for the copy, and gives the device address
+//
+// and make_run(device dictionary, its length) gives the `run` of the slices.
+inline int64_t dict_reach(int64_t dict_len) { return dict_len < 65535 ? dict_len : 65535; }
+
+template <class Stage>
+int upload_dictionary(Stage& st, const void* dict, int64_t dict_len, const uint8_t*& d_dict, int64_t& reach)
+{
+    reach = dict_reach(dict_len);
+    d_dict = nullptr;
+    if (reach == 0) return 0;
+    uint8_t* dev = nullptr;
+    if (int rc = st.dict_upload((const uint8_t*)dict + (dict_len - reach), reach, dev)) return rc;
+    d_dict = dev;
+    return 0;
+}
+
+template <class Stage, class MakeRun>
+int run_host_batch_dict(Stage& st, const lz4hip_batch_t* hb, const void* dict, int64_t dict_len, bool dst_len_is_result, MakeRun make_run,
+                        int slices_knob, int threads_knob, const HostLimits& limits = HostLimits())
+{
+    if (hb->n_blocks == 0) return 0;
+    const uint8_t* d_dict = nullptr;
+    int64_t reach = 0;
+    if (int rc = upload_dictionary(st, dict, dict_len, d_dict, reach)) return rc;
+    return run_host_batch(st, hb, dst_len_is_result, make_run(d_dict, reach), 0, slices_knob, threads_knob, limits);
+}
+
 // ---- the decoded sizes of a host-pointer batch ---------------------------------------------------------------------------------------
 // lz4hip_decoded_sizes_host: the rows are gathered back to back (the row work above), staged with their lengths in ONE device image of
 // the framing backend B, sized by the device call (framing::decoded_sizes), and only result, dst_off, dst_cap and info come back -- no
 // block payload travels in that direction.  Every row is needed before the offsets can be scanned, so there are no slices here.
 template <class B>
 int decoded_sizes_host(B& be, const lz4hip_batch_t* hb, int64_t* dst_off, int32_t* dst_cap, lz4hip_sizes_info_t* info, int groups, int threads_knob,
-                       const HostLimits& limits = HostLimits())
+                       const HostLimits& limits = HostLimits(), int64_t dict_len = -1)       // (dict_len: framing::decoded_sizes)
 {
     if (!hb) return be.fail(LZ4HIP_E_ARGUMENT, "decoded sizes: batch descriptor is NULL");
     const int64_t n = hb->n_blocks;
@@ -406,7 +440,7 @@ int decoded_sizes_host(B& be, const lz4hip_batch_t* hb, int64_t* dst_off, int32_
     lz4hip_batch_t db = {};
     db.src = im.d; db.src_off = im.i64(off_at); db.src_len = im.i32(len_at); db.result = im.i32(res_at); db.n_blocks = n;
     if (int rc = framing::decoded_sizes(be, &db, im.i64(doff_at), im.i32(cap_at), im.d + scratch_at, scratch_bytes,
-                                        (lz4hip_sizes_info_t*)(im.d + info_at), groups)) return rc;
+                                        (lz4hip_sizes_info_t*)(im.d + info_at), groups, dict_len)) return rc;
     if (hb->result) if (int rc = im.download(hb->result, res_at, 4 * n)) return rc;
     if (dst_off) if (int rc = im.download(dst_off, doff_at, 8 * (n + 1))) return rc;
     if (dst_cap) if (int rc = im.download(dst_cap, cap_at, 4 * n)) return rc;

@@ -172,6 +172,23 @@ __global__ void __launch_bounds__(kSizesThreads) sizes_walk_kernel(SizesArgs a)
     }
 }
 
+// the same walk for blocks that are decoded against a dictionary (lz4hip_decoded_sizes_dict_*): a match may start up to `history` bytes
+// before its block -- the dictionary's length, at most the format's 65 535; no byte of the dictionary is needed
+__global__ void __launch_bounds__(kSizesThreads) sizes_walk_dict_kernel(SizesArgs a, int32_t history)
+{
+    LZ4HIP_STATIC_LDS(lds_raw, kSizesLdsBytes);
+    uint32_t* const col = (uint32_t*)lds_raw + threadIdx.x;
+    for (int64_t i = (int64_t)blockIdx.x * kSizesThreads + threadIdx.x; i < a.n; i += (int64_t)gridDim.x * kSizesThreads) {
+        const uint8_t* src = a.src + (a.src_off ? a.src_off[i] : i * a.src_stride);
+        const int32_t r = decoded_size_block(src, a.src_len ? a.src_len[i] : a.src_len_all, col, history);
+        const int32_t cap = r < 0 ? 0 : r;
+        a.result[i] = r;
+        if (a.dst_cap) a.dst_cap[i] = cap;
+        a.offs[i] = cap;
+        if (r < 0) atomicMin(a.min_bad, (unsigned long long)i);
+    }
+}
+
 // after the scan: offs[n] is the total
 __global__ void __launch_bounds__(64) sizes_info_kernel(SizesArgs a, SizesInfo* info)
 {
