@@ -25,7 +25,63 @@
 #include "lz4hip_encode_lane.hpp"   // lane_copy, lane_put_length
 #include "lz4hip_hc.hpp"            // hash15
 
+#ifndef LZ4HIP_STAT_HC
+#define LZ4HIP_STAT_HC(slot, n) ((void)0)        /* which branch of the LZ4HC lane kernels a lane took (tests/simt/emu_kernels.cpp, HcStat below) */
+#endif
+
 namespace lz4hip {
+
+// What the emulator build counts per lane in the LZ4HC lane kernels and their table builders (tests/hc_lane_cases.py names the same
+// slots).  P: the parse (lz4hip_hc_parse.inc, for every kernel that includes it); the others: lz4hip_hc_lcp.hpp and its builders.
+enum HcStat {
+    // ---- the parse: one slot per branch that changes ip / ml / start2 / ml2 ----
+    kHcP_Ml2EqMl = 0,        // lz4hc.c:601   no wider match: emit
+    kHcP_Start0Restore,      // lz4hc.c:609   back to the match found first
+    kHcP_Start2Near,         // lz4hc.c:616   start2 - ip < 3: take the second match instead
+    kHcP_S3CorrOptimal,      // lz4hc.c:627   _Search3 shortens match 2, new_ml = min(ml, OPTIMAL_ML)
+    kHcP_S3CorrFit,          //               ... new_ml = what leaves match 2 its MINMATCH bytes
+    kHcP_S3NoSearch,         //               start2 + ml2 >= mflimit: no third search
+    kHcP_Ml3EqMl2Short,      // lz4hc.c:645   no third match, match 1 shortened to start2 - ip
+    kHcP_Ml3EqMl2Plain,      //               ... match 1 as it is
+    kHcP_Start3Near,         // lz4hc.c:656   start3 < ip + ml + 3
+    kHcP_Start3Far,          //               ... and not
+    kHcP_Start3Behind,       // lz4hc.c:658   start3 >= ip + ml: emit match 1, go on with match 3
+    kHcP_Start3Inside,       // lz4hc.c:684   start3 < ip + ml: match 3 replaces match 2
+    kHcP_Ml2Replaced,        // lz4hc.c:666   ml2 < MINMATCH after the correction: match 3 replaces match 2
+    kHcP_Lt15,               // lz4hc.c:694   start2 - ip < 15 (ML_MASK)
+    kHcP_Ge15,               // lz4hc.c:711   ... and its else: ml = start2 - ip
+    kHcP_Phase4,             // lz4hc.c:594   ip + ml >= mflimit: no wider search
+    kHcP_EmitRefuseLiterals, // lz4hc.c:529   the output limit, before the literals
+    kHcP_EmitRefuseMatch,    // lz4hc.c:541   ... before the match length
+    kHcP_EmitRefuseBytes,    //               ... the length bytes themselves (see lz4hip_hc.hpp)
+    // ---- lz4hip_hc_lcp.hpp: the walk (F(c') from F(c) and lcp[c]) ----
+    kHcW_Less,               // s_f < l
+    kHcW_Greater,            // s_f > l, l below the cap
+    kHcW_EqLimit,            // equal below the cap: s_ip + l >= matchlimit
+    kHcW_EqWinDiff,          // ... the byte is in the register window and differs from y
+    kHcW_EqWinSame,          // ... is in the window and equals y: compare on
+    kHcW_EqWinMiss,          // ... is not in the window: compare on
+    kHcW_BothCap,            // both 255 or more: compare on
+    kHcW_EndDistance, kHcW_EndStart, kHcW_EndAttempts,   // what ended the walk: the distance, the block's start (each that holds), the attempts alone
+    kHcH_Cap, kHcH_Below,    // the head: lcp[ip] at the cap (compare from 255) / below it
+    kHcR_Taken,              // + delta - 1 (four slots): the repeat test with s_f >= 4
+    kHcR_Short = kHcR_Taken + 4,   // + delta - 1 (four slots): a head within 4 bytes that shares fewer than 4
+    kHcC_WinHit = kHcR_Short + 4,  // a 16-byte compare step served from the window
+    kHcC_Fill,               // ... that refills the window
+    kHcC_MissNoFill,         // ... that misses it and may not refill it (f_a + 32 > n)
+    kHcC_Bytes,              // the byte loop before matchlimit
+    kHcF_Pass, kHcF_Fail,    // wider search: the filter byte answered from the common region
+    kHcF_ReadCached, kHcF_ReadLoaded,   // ... read, with the search position's byte cached / loaded
+    kHcF_Improved, kHcF_NotImproved,    // a candidate past the filter that improves s_len / does not
+    kHcB_Four4, kHcB_FourLess, kHcB_Byte,              // backward extension: a 4-byte step with k == 4 / k < 4, a byte step
+    kHcB_StopLimit, kHcB_StopStart, kHcB_StopMismatch, // ... what stopped it (byte steps; a 4-byte step stops by a mismatch)
+    kHcL_Store16, kHcL_Store1,          // repeat fill: 16-byte stores, single stores
+    kHcL_EntryCap, kHcL_EntryBelow,     // ... entries written with length 255 / below
+    // ---- the builders ----
+    kHcT_Leader, kHcT_Follower, kHcT_Late, kHcT_LeaderPast255,   // hc_lcp_fill_kernel: rows that count, rows served by their leader, served too late, leaders that counted past 255
+    kHcN_PrevLane, kHcN_PrevHead,       // hc_nat_chain_kernel: predecessor from a lower lane of the same step / from the head
+    kHcStats
+};
 
 constexpr int kHcLaneWavesPerCu = 16;   // one block takes a lane ~2 s of dependent memory round trips: throughput = lanes in flight (4: 1.8, 8: 3.0, 16: 4.8, 20: 4.8 GB/s)
 constexpr size_t kHcLaneSlab16 = 65536 + 131072;    // u16 heads + u16 chain

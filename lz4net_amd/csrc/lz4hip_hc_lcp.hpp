@@ -33,6 +33,9 @@
 #ifndef LZ4HIP_STAT_ADD
 #define LZ4HIP_STAT_ADD(slot, n) ((void)0)
 #endif
+#ifndef LZ4HIP_STAT_HC
+#define LZ4HIP_STAT_HC(slot, n) ((void)0)        /* the emulator build counts the branches taken (HcStat, lz4hip_hc_conv.hpp; tests/hc_lane_cases.py) */
+#endif
 
 namespace lz4hip {
 
@@ -142,6 +145,9 @@ __global__ void __launch_bounds__(kHcLcpFillThreads) hc_lcp_fill_kernel(Batch b,
             follower_rows |= follower ? 1u << u : 0u;
         }
         count_rows(leader_rows, p0, 63);
+        LZ4HIP_STAT_HC(kHcT_Leader, __builtin_popcount(leader_rows)); LZ4HIP_STAT_HC(kHcT_Follower, __builtin_popcount(follower_rows));
+#pragma unroll
+        for (int u = 0; u < U; u++) LZ4HIP_STAT_HC(kHcT_LeaderPast255, ((leader_rows >> u) & 1u) && r[u] > (uint32_t)kHcLcpCap ? 1 : 0);
 #pragma unroll
         for (int u = 0; u < U; u++) {
             const uint64_t leaders = wv::ballot(((follower_rows >> u) & 1u) == 0u);
@@ -153,6 +159,7 @@ __global__ void __launch_bounds__(kHcLcpFillThreads) hc_lcp_fill_kernel(Batch b,
             }
         }
         count_rows(late_rows, p0, 0);
+        LZ4HIP_STAT_HC(kHcT_Late, __builtin_popcount(late_rows));
 #pragma unroll
         for (int u = 0; u < U; u++) {
             const int p = p0 + u * kHcLcpFillThreads;
@@ -305,6 +312,7 @@ __global__ void __launch_bounds__(64) encode_hc_lcp_kernel(Batch b, long long fi
             s_ref = s_ip - (int)(v_e & 0xFFFFu);
             s_f = (int)((v_e >> 16) & 255u);
             s_first = 1;
+            LZ4HIP_STAT_HC(s_f >= kHcLcpCap ? kHcH_Cap : kHcH_Below, 1);
             if (s_f >= kHcLcpCap) { c_n = kHcLcpCap; st = kLsCmp; }
             else st = kLsHop;                                        // (blocks <= 64 KiB: the head is always within MAX_DISTANCE)
         }
@@ -314,6 +322,7 @@ __global__ void __launch_bounds__(64) encode_hc_lcp_kernel(Batch b, long long fi
         if (inC) {                                                   // common length of in[s_ip + c_n ..] and in[s_ref + c_n ..] up to matchlimit
             int add = 0;
             bool more = false;
+            LZ4HIP_STAT_HC(cmp16 ? (w_hit ? kHcC_WinHit : w_fill ? kHcC_Fill : kHcC_MissNoFill) : kHcC_Bytes, 1);
             if (cmp16) {
                 if (w_hit) v_x = win16(f_a - w_pos);
                 else if (w_fill) {
@@ -342,6 +351,7 @@ __global__ void __launch_bounds__(64) encode_hc_lcp_kernel(Batch b, long long fi
             s_link = (int)(v_e & 0xFFFFu); s_lcp = (int)((v_e >> 16) & 255u); s_y = v_e >> 24;
             if (phase == 0) {
                 if (s_first && s_ref >= s_ip - 4) {                  // lz4hc.c:411-421: not one of the attempts
+                    LZ4HIP_STAT_HC((s_f >= kMinMatch ? kHcR_Taken : kHcR_Short) + (s_ip - s_ref) - 1, 1);
                     if (s_f >= kMinMatch) { s_delta = (s_ip - s_ref) & 0xFFFF; s_repl = s_len = s_f; s_match = s_ref; }
                 } else {                                             // lz4hc.c:424-434
                     attempts--;
@@ -352,6 +362,7 @@ __global__ void __launch_bounds__(64) encode_hc_lcp_kernel(Batch b, long long fi
                 attempts--;
                 bool pass = false;
                 if (s_f >= kMinMatch) {
+                    LZ4HIP_STAT_HC(f_read ? (s_probe_ok ? kHcF_ReadCached : kHcF_ReadLoaded) : ((fj >= 0) & (fj < s_f)) ? kHcF_Pass : kHcF_Fail, 1);
                     if (f_read) {                                    // (kLsHop lanes only: the bytes were loaded above)
                         if (!s_probe_ok) { s_probe = v_pb; s_probe_ok = 1; }
                         pass = v_cb == s_probe;
@@ -367,13 +378,15 @@ __global__ void __launch_bounds__(64) encode_hc_lcp_kernel(Batch b, long long fi
                 const uint32_t d = v_w ^ v_w2;                       // bytes c_s-4 .. c_s-1 against c_r-4 .. c_r-1: count from the top
                 const int k = d == 0 ? 4 : (__builtin_clz(d) >> 3);
                 c_s -= k; c_r -= k; more = k == 4;
+                LZ4HIP_STAT_HC(k == 4 ? kHcB_Four4 : kHcB_FourLess, 1);
             } else {
                 for (int k = 0; k < 4; k++) {
-                    if (c_s > s_limit && c_r > 0 && in[c_s - 1] == in[c_r - 1]) { c_s--; c_r--; more = k == 3; }
-                    else { more = false; break; }
+                    if (c_s > s_limit && c_r > 0 && in[c_s - 1] == in[c_r - 1]) { c_s--; c_r--; more = k == 3; LZ4HIP_STAT_HC(kHcB_Byte, 1); }
+                    else { LZ4HIP_STAT_HC(c_s <= s_limit ? kHcB_StopLimit : c_r <= 0 ? kHcB_StopStart : kHcB_StopMismatch, 1); more = false; break; }
                 }
             }
             if (!more) {                                             // lz4hc.c:507-512
+                LZ4HIP_STAT_HC(c_fwd_end - c_s > s_len ? kHcF_Improved : kHcF_NotImproved, 1);
                 if (c_fwd_end - c_s > s_len) { s_len = c_fwd_end - c_s; s_match = c_r; s_start = c_s; s_probe_ok = 0; }
                 adv = true;
             }
@@ -384,9 +397,13 @@ __global__ void __launch_bounds__(64) encode_hc_lcp_kernel(Batch b, long long fi
             auto entry = [&](int at) -> uint32_t { const int l = c_fwd_end - at; return d | ((uint32_t)(l > kHcLcpCap ? kHcLcpCap : l) << 16); };
             if ((q & 3) == 0 && q + 4 <= c_r) {
                 store_v16((uint8_t*)(table + q), Vec16{ { entry(q), entry(q + 1), entry(q + 2), entry(q + 3) } });
+                LZ4HIP_STAT_HC(kHcL_Store16, 1);
+                for (int k = 0; k < 4; k++) LZ4HIP_STAT_HC(c_fwd_end - (q + k) >= kHcLcpCap ? kHcL_EntryCap : kHcL_EntryBelow, 1);
                 q += 4;
             } else {
                 table[q] = entry(q);
+                LZ4HIP_STAT_HC(kHcL_Store1, 1);
+                LZ4HIP_STAT_HC(c_fwd_end - q >= kHcLcpCap ? kHcL_EntryCap : kHcL_EntryBelow, 1);
                 q++;
             }
             c_s = q;
@@ -396,6 +413,7 @@ __global__ void __launch_bounds__(64) encode_hc_lcp_kernel(Batch b, long long fi
         if (adv) {
             const int c2 = s_ref - s_link;
             if (!(c2 >= s_ip - kMaxDistance && attempts > 0 && c2 >= 0)) {
+                LZ4HIP_STAT_HC(kHcW_EndDistance, c2 < s_ip - kMaxDistance ? 1 : 0); LZ4HIP_STAT_HC(kHcW_EndStart, c2 < 0 ? 1 : 0); LZ4HIP_STAT_HC(kHcW_EndAttempts, attempts <= 0 && c2 >= 0 && c2 >= s_ip - kMaxDistance ? 1 : 0);
                 st = (s_repl && phase == 0) ? (int)kLsRepl : (int)kLsCtrl;
                 // (what a bucket-contiguous table would need for this search: its own entry + the candidates' entries, four per 16-byte read)
                 LZ4HIP_STAT_ADD(12, 1); LZ4HIP_STAT_ADD(13, stat_hops); LZ4HIP_STAT_ADD(14, (stat_hops + 1 + 3) / 4); LZ4HIP_STAT_ADD(15, (stat_hops + 1 + 7) / 8);
@@ -405,6 +423,7 @@ __global__ void __launch_bounds__(64) encode_hc_lcp_kernel(Batch b, long long fi
                 const int l = s_lcp;
                 s_ref = c2; s_first = 0;
                 LZ4HIP_STAT(7, true);
+                LZ4HIP_STAT_HC(kHcW_Less, s_f < l ? 1 : 0); LZ4HIP_STAT_HC(kHcW_Greater, s_f > l && l < kHcLcpCap ? 1 : 0);
                 if (s_f < l) st = kLsHop;                                        // F(c') = F(c)
                 else if (s_f > l && l < kHcLcpCap) { s_f = l; st = kLsHop; }     // F(c') = lcp[c]
                 else {
@@ -417,6 +436,7 @@ __global__ void __launch_bounds__(64) encode_hc_lcp_kernel(Batch b, long long fi
                         if (pos >= matchlimit) exact = true;
                         else if ((pos >= w_pos) & (pos < w_pos + 32)) exact = win_byte(pos - w_pos) != s_y;
                     }
+                    LZ4HIP_STAT_HC(l >= kHcLcpCap ? kHcW_BothCap : pos >= matchlimit ? kHcW_EqLimit : !((pos >= w_pos) & (pos < w_pos + 32)) ? kHcW_EqWinMiss : exact ? kHcW_EqWinDiff : kHcW_EqWinSame, 1);
                     LZ4HIP_STAT(8, true); LZ4HIP_STAT(9, l < kHcLcpCap); LZ4HIP_STAT(10, (l < kHcLcpCap) & (pos >= w_pos) & (pos < w_pos + 32)); LZ4HIP_STAT(11, exact);
                     if (exact) st = kLsHop;                                      // F(c') = l = F(c)
                     else { c_n = l; st = kLsCmp; }                               // compare on

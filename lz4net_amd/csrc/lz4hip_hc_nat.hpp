@@ -29,6 +29,10 @@
 #pragma once
 #include "lz4hip_hc_conv.hpp"
 
+#ifndef LZ4HIP_STAT_HC
+#define LZ4HIP_STAT_HC(slot, n) ((void)0)        /* the emulator build counts the branches taken (HcStat, lz4hip_hc_conv.hpp) */
+#endif
+
 namespace lz4hip {
 
 constexpr size_t kHcNatChainBytes = 65536 * sizeof(uint16_t);   // per block
@@ -99,6 +103,7 @@ __global__ void __launch_bounds__(kHcNatChainThreads) hc_nat_chain_kernel(Batch 
             }
             const int prev = below ? base + (63 - __builtin_clzll(below)) : old;
             if (active) chain[p] = (EntryT)(p - prev);
+            LZ4HIP_STAT_HC(below ? kHcN_PrevLane : kHcN_PrevHead, active ? 1 : 0);
         }
 #pragma unroll
         for (int u = 0; u < U; u++) cur[u] = nxt[u];

@@ -67,8 +67,9 @@ def decode(comps, out_sizes, known=True, src_lens=None, waves_per_group=1, auto=
     return res, dst
 
 
-def encode(blocks, caps=None, hc=False, groups=2, lane=False, conv=False, nat=False, lcp=False, wg5=False):
-    src, sl = pack(blocks)
+def encode(blocks, caps=None, hc=False, groups=2, lane=False, conv=False, nat=False, lcp=False, wg5=False, pad=16):
+    """pad=0: a row of the greatest length ends directly in front of the next row's first byte"""
+    src, sl = pack(blocks, pad=pad)
     if caps is None:
         caps = [len(b) + len(b) // 255 + 16 for b in blocks]
     caps = np.array(caps, np.int32)
@@ -93,6 +94,21 @@ def encode(blocks, caps=None, hc=False, groups=2, lane=False, conv=False, nat=Fa
     else:
         lib().emu_encode_fast(*args)
     return res, dst
+
+
+def hc_stats(reset=True):
+    """lz4hip::HcStat: the branch counters of the LZ4HC lane kernels and their table builders since the last reset"""
+    st = (C.c_ulonglong * 96)()
+    n = lib().emu_hc_stats(st, int(reset))
+    return [int(x) for x in st[:n]]
+
+
+def hc_lcp_tables(blocks):
+    """(len(blocks), 65536) uint32: the tables hc_nat_chain_kernel<uint32_t> and hc_lcp_fill_kernel leave of poisoned memory"""
+    src, sl = pack(blocks)
+    tables = np.zeros((len(blocks), 65536), np.uint32)
+    lib().emu_hc_lcp_tables(_p(src), C.c_int64(src.shape[1]), _p(sl), C.c_int64(len(blocks)), _p(tables))
+    return tables
 
 
 def encode_hc_lane_static(blocks):

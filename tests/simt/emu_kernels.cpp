@@ -11,6 +11,8 @@ static unsigned long long g_stat[40];         // lane-iterations per state of th
 #define LZ4HIP_STAT(slot, cond) do { if (cond) g_stat[slot]++; } while (0)
 #define LZ4HIP_STAT_ADD(slot, n) do { g_stat[slot] += (unsigned long long)(n); } while (0)
 #define LZ4HIP_STAT_PATH(slot, cond) LZ4HIP_STAT(slot, cond)
+static unsigned long long g_hc_stat[96];      // lz4hip::HcStat: branches of the LZ4HC lane kernels and their table builders, per lane (tests/hc_lane_cases.py)
+#define LZ4HIP_STAT_HC(slot, n) do { g_hc_stat[slot] += (unsigned long long)(n); } while (0)
 
 #include "lz4hip_common.hpp"
 #include "lz4hip_decode.hpp"
@@ -295,6 +297,24 @@ void emu_encode_hc_lcp(const uint8_t* src, int64_t src_stride, const int32_t* sr
     simt::launch(dim3((unsigned)n), dim3(kHcNatChainThreads), kHcNatLdsBytes, [=] { hc_nat_chain_kernel<uint32_t>(b, 0, tables); });
     simt::launch(dim3((unsigned)n), dim3(kHcLcpFillThreads), kHcLcpFillLdsBytes, [=] { hc_lcp_fill_kernel(b, 0, tables); });
     simt::launch(dim3((unsigned)groups), dim3(64), 0, [=] { encode_hc_lcp_kernel(b, 0, (long long)n, counter, tables, kHcLcpCtrlEvery, kHcLcpCtrlLanes); });
+}
+#endif
+
+#ifdef LZ4HIP_HAVE_HC
+static_assert(kHcStats <= 96, "g_hc_stat");
+// the two table builders of lz4hip_hc_lcp.hpp alone: `tables` (n x 65536 entries) is poisoned here and handed back as they leave it
+void emu_hc_lcp_tables(const uint8_t* src, int64_t src_stride, const int32_t* src_len, int64_t n, uint32_t* tables)
+{
+    Batch b = make_batch(src, src_stride, src_len, nullptr, 0, nullptr, nullptr, n);
+    uint8_t* const t = (uint8_t*)tables;
+    memset(t, 0x5A, (size_t)n * kHcLcpTableBytes);
+    simt::launch(dim3((unsigned)n), dim3(kHcNatChainThreads), kHcNatLdsBytes, [=] { hc_nat_chain_kernel<uint32_t>(b, 0, t); });
+    simt::launch(dim3((unsigned)n), dim3(kHcLcpFillThreads), kHcLcpFillLdsBytes, [=] { hc_lcp_fill_kernel(b, 0, t); });
+}
+int emu_hc_stats(unsigned long long* out, int reset)
+{
+    for (int i = 0; i < kHcStats; i++) { out[i] = g_hc_stat[i]; if (reset) g_hc_stat[i] = 0; }
+    return kHcStats;
 }
 #endif
 
