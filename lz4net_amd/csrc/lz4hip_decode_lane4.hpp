@@ -37,6 +37,15 @@
 // are kept: the flush stores stay in front of T5, whose far fetch may only read what an EARLIER store instruction of this wavefront has written
 // (fl counts a unit from T2a on, but nothing between T2a and T2d reads memory through it), and nothing appends to the ring (B3 / B4) before the
 // helpers have read it (the wave-level fence behind T2d).  Vector-memory instructions per iteration, and their order, are unchanged (kVm).
+// CONDITIONAL ASSIGNMENTS ARE MOVES UNDER EXEC, not selects, in the kernels whose wavefronts share a SIMD (WAVES == 1): what the vector ALU charges
+// for at three wavefronts per SIMD is the ENCODING -- 4.5 SIMD-cycles for v_cndmask_b32_e64 like every 64-bit encoding, 2.8 for v_mov_b32, and
+// under EXEC with the region's two scalar instructions counted 3.1 - 3.3 per dword in regions of eight and four moves, 2.6 per dword as
+// v_pk_mov_b32 (profiles/lane_encodings/microbench_valu_rate.txt; a region of ONE move costs 9.5 and stays a select).  So: the window refill
+// (T1a: twenty dwords in three regions), the two in-place levels of the cursor tree (T1b: packed pairs, the last level in the shift-by-one-dword
+// form) and the source choice of the chunk (B3: two regions of four).  39 selects per iteration become 4 + 8 v_mov_b32 and 8 + 6 v_pk_mov_b32.  What
+// selects between two fresh values stays a select (the tree's first level, T4, T5), and so does what the compiler already folds into one
+// select per assignment (T4 under may_parse, which is a real branch; B4 under pgo).  Sections, their order, kVm and the hand-counted vmcnt are
+// untouched: the regions hold register moves only.
 // Everything else is generation 3's design: dword-interleaved output ring, appends by DS_MSKOR_B32 + v_perm_b32, cooperative
 // flush (four lanes per 64-byte line, or eight per 128-byte unit), far matches fetched from the lane's own output one and a
 // half iterations ahead, parse-ahead of one sequence, a byte-wise parser behind one wave-level branch, hand-counted vmcnt.
@@ -69,6 +78,47 @@
 #endif
 
 namespace lz4hip {
+
+// CONDITIONAL ASSIGNMENTS x = m ? a : x.  On the device they are moves under EXEC (wv::mov_mask, wv::mov2_mask, wv::shift_dword_mask: 32-bit
+// v_mov_b32, or two dwords per v_pk_mov_b32, up to eight dwords per EXEC region) instead of v_cndmask_b32_e64; everywhere else -- the host pass,
+// and the CPU emulation of the wave API, which builds this header as it stands -- they are the selects they replace, one per move and in the
+// same order.  (Only the kernels with kMoves use them, see lane4_decode_block.)
+#if defined(__HIP_DEVICE_COMPILE__)
+#define L4_MOV(...) wv::mov_mask(__VA_ARGS__)
+// eight dwords d[0..7] <- the four dwords of a and of b (two 16-byte registers), as four packed moves of register pairs
+#define L4_MOV8(m_, d_, a_, b_)                                                                                          \
+    do {                                                                                                                 \
+        wv::u32x2 p0_ = { (d_)[0], (d_)[1] }, p1_ = { (d_)[2], (d_)[3] }, p2_ = { (d_)[4], (d_)[5] }, p3_ = { (d_)[6], (d_)[7] }; \
+        wv::mov2_mask(m_, p0_, wv::u32x2{ (a_).x, (a_).y }, p1_, wv::u32x2{ (a_).z, (a_).w }, p2_, wv::u32x2{ (b_).x, (b_).y }, p3_, wv::u32x2{ (b_).z, (b_).w }); \
+        (d_)[0] = p0_.x; (d_)[1] = p0_.y; (d_)[2] = p1_.x; (d_)[3] = p1_.y; (d_)[4] = p2_.x; (d_)[5] = p2_.y; (d_)[6] = p3_.x; (d_)[7] = p3_.y; \
+    } while (0)
+// the two lowest levels of the cursor tree on t[0..7], in place: t[j] <- t[j + 2] (j < 6) under m2_, then t[j] <- t[j + 1] (j < 5) under m1_ --
+// three packed moves of register pairs each, the second level in the shift-by-one-dword form
+#define L4_TREE_LOW(m2_, m1_, t_)                                                                                        \
+    do {                                                                                                                 \
+        wv::u32x2 p0_ = { (t_)[0], (t_)[1] }, p1_ = { (t_)[2], (t_)[3] }, p2_ = { (t_)[4], (t_)[5] }, p3_ = { (t_)[6], (t_)[7] }; \
+        wv::mov2_mask(m2_, p0_, p1_, p1_, p2_, p2_, p3_);                                                                \
+        wv::shift_dword_mask(m1_, p0_, p1_, p2_);                                                                        \
+        (t_)[0] = p0_.x; (t_)[1] = p0_.y; (t_)[2] = p1_.x; (t_)[3] = p1_.y; (t_)[4] = p2_.x;                             \
+    } while (0)
+#else
+LZ4HIP_DEVICE void lane4_mov_sel(wv::mask_t) {}
+template <class T, class... REST>
+LZ4HIP_DEVICE void lane4_mov_sel(wv::mask_t m, T& d, T s, REST&&... rest)
+{
+    d = (T)wv::sel(m, (uint32_t)s, (uint32_t)d);
+    lane4_mov_sel(m, static_cast<REST&&>(rest)...);
+}
+#define L4_MOV(...) lane4_mov_sel(__VA_ARGS__)
+#define L4_MOV8(m_, d_, a_, b_)                                                                                          \
+    lane4_mov_sel(m_, (d_)[0], (uint32_t)(a_).x, (d_)[1], (uint32_t)(a_).y, (d_)[2], (uint32_t)(a_).z, (d_)[3], (uint32_t)(a_).w, \
+                      (d_)[4], (uint32_t)(b_).x, (d_)[5], (uint32_t)(b_).y, (d_)[6], (uint32_t)(b_).z, (d_)[7], (uint32_t)(b_).w)
+#define L4_TREE_LOW(m2_, m1_, t_)                                                                                        \
+    do {                                                                                                                 \
+        lane4_mov_sel(m2_, (t_)[0], (t_)[2], (t_)[1], (t_)[3], (t_)[2], (t_)[4], (t_)[3], (t_)[5], (t_)[4], (t_)[6], (t_)[5], (t_)[7]); \
+        lane4_mov_sel(m1_, (t_)[0], (t_)[1], (t_)[1], (t_)[2], (t_)[2], (t_)[3], (t_)[3], (t_)[4], (t_)[4], (t_)[5]);    \
+    } while (0)
+#endif
 
 #ifndef LZ4HIP_DEC4_FLUSH_RECS
 #define LZ4HIP_DEC4_FLUSH_RECS 0      /* 0 = all the two store instructions can carry; the emulator's 'starved' build: 4 */
@@ -129,6 +179,11 @@ LZ4HIP_DEVICE int lane4_decode_block(unsigned char* lds, int lane, bool active, 
     constexpr int kFlushRecs = (LZ4HIP_DEC4_FLUSH_RECS) ? (LZ4HIP_DEC4_FLUSH_RECS) : FS * RECS_PER_STORE;
     constexpr bool kLineNoWrap = R % 64 == 0;                        // a 64-byte line of the ring (16 rows from a multiple of 16) never wraps inside
     constexpr int kNearMax = R - 20;                                 // an append writes whole dwords, up to 19 bytes past its last byte
+    // Conditional assignments are moves under EXEC where wavefronts share a SIMD (WAVES == 1: three per SIMD in a large batch, and the other two
+    // issue their vector work beside a region's two scalar instructions).  The workgroups of four wavefronts run batches of at most one
+    // residency round, a wavefront ALONE on its SIMD, which pays for every instruction it issues: there the moves are slower (65 536 D2
+    // blocks: 7.99 ms with selects, 8.25 with moves, profiles/lane_encodings/ab.txt) and the select form stays, statement for statement.
+    constexpr bool kMoves = WAVES == 1;
     // vector-memory instructions per iteration: FS flush stores (if it flushes), far fetch, NL input loads (if it requests input)
     // Flush record i of this wavefront.  The 512 bytes of records per wavefront lie behind the ring as TWO halves, one in each of the first two
     // "rows" past the ring's end, at this wavefront's lanes' columns: an append's rows that run past the last ring row land in the storing
@@ -321,10 +376,20 @@ LZ4HIP_DEVICE int lane4_decode_block(unsigned char* lds, int lane, bool active, 
             const bool no_more = wb + 16 + P >= in_total;            // W holds the last piece of the source
             const bool cross = (d >= P) & ((lvalid != 0) | no_more);
             const wv::mask_t cm = wv::cond(d >= P) & (wv::cond(lvalid != 0) | wv::cond(no_more));   // (lane masks combined by scalar instructions)
+            if constexpr (LS && kMoves) {
+                // Twenty conditional assignments, none of them a select: three EXEC regions of moves.  W[0..3] <- W[8..11] comes first (it reads
+                // what the other two overwrite); the piece at wb + 16 + P is the low or the high half of the sector in L, so W[4..11] comes from
+                // L[0..1] under cm & ~hm or from L[2..3] under cm & hm, two dwords per move.  After the low half L stays valid.
+                const bool hi_half = ((wb + 16 + P) & 32) != 0;
+                const wv::mask_t hm = wv::cond(((wb + 16 + P) & 32) != 0);
+                L4_MOV(cm, W[0], W[8], W[1], W[9], W[2], W[10], W[3], W[11]);
+                L4_MOV8(cm & ~hm, W + 4, L[0], L[1]);
+                L4_MOV8(cm & hm, W + 4, L[2], L[3]);
+                lvalid = (cross & hi_half) ? 0 : lvalid;
+            } else if constexpr (LS) {
+                // (the select form) the piece at wb + 16 + P is the low or the high half of the sector in L; after the low half L stays valid
 #pragma unroll
-            for (int j = 0; j < 4; j++) W[j] = wv::sel(cm, W[P / 4 + j], W[j]);
-            if constexpr (LS) {
-                // the piece at wb + 16 + P is the low or the high half of the sector in L; after the low half L stays valid
+                for (int j = 0; j < 4; j++) W[j] = wv::sel(cm, W[P / 4 + j], W[j]);
                 const bool hi_half = ((wb + 16 + P) & 32) != 0;
                 const wv::mask_t hm = wv::cond(((wb + 16 + P) & 32) != 0);
 #pragma unroll
@@ -334,6 +399,9 @@ LZ4HIP_DEVICE int lane4_decode_block(unsigned char* lds, int lane, bool active, 
                 }
                 lvalid = (cross & hi_half) ? 0 : lvalid;
             } else {
+                // (the non-sector forms, P == 64 among them, are tuning builds: they keep their selects)
+#pragma unroll
+                for (int j = 0; j < 4; j++) W[j] = wv::sel(cm, W[P / 4 + j], W[j]);
 #pragma unroll
                 for (int j = 0; j < NL; j++) {
                     W[4 + 4 * j] = wv::sel(cm, L[j].x, W[4 + 4 * j]); W[5 + 4 * j] = wv::sel(cm, L[j].y, W[5 + 4 * j]);
@@ -352,16 +420,25 @@ LZ4HIP_DEVICE int lane4_decode_block(unsigned char* lds, int lane, bool active, 
             // W[k .. k + 4], k = d / 4, through a binary tree of selects; then the byte rotation
             const uint32_t k = (uint32_t)d >> 2;
             uint32_t t[NW];
+            if constexpr (kMoves && P == 32) {
+                // The first level reads W and writes t: selects.  The two levels below it work on t IN PLACE -- t[j] <- t[j + sh] going upwards reads
+                // every source before it is overwritten -- so they are conditional assignments: moves under the lane mask of their bit of k
+                const wv::mask_t m = wv::cond((k & 4u) != 0u);
 #pragma unroll
-            for (int j = 0; j < NW; j++) t[j] = W[j];
-            int n = NW;
+                for (int j = 0; j < 8; j++) t[j] = wv::sel(m, W[j + 4], W[j]);
+                L4_TREE_LOW(wv::cond((k & 2u) != 0u), wv::cond((k & 1u) != 0u), t);
+            } else {
 #pragma unroll
-            for (int sh = P / 8; sh >= 1; sh >>= 1) {
-                const wv::mask_t m = wv::cond((k & (uint32_t)sh) != 0u);
-                n -= sh;
+                for (int j = 0; j < NW; j++) t[j] = W[j];
+                int n = NW;
 #pragma unroll
-                for (int j = 0; j < NW; j++)
-                    if (j < n) t[j] = wv::sel(m, t[j + sh], t[j]);
+                for (int sh = P / 8; sh >= 1; sh >>= 1) {
+                    const wv::mask_t m = wv::cond((k & (uint32_t)sh) != 0u);
+                    n -= sh;
+#pragma unroll
+                    for (int j = 0; j < NW; j++)
+                        if (j < n) t[j] = wv::sel(m, t[j + sh], t[j]);
+                }
             }
             const uint32_t sx = L4_PHASE_SEL(d);
             x0 = wv::perm(t[1], t[0], sx); x1 = wv::perm(t[2], t[1], sx); x2 = wv::perm(t[3], t[2], sx); x3 = wv::perm(t[4], t[3], sx);
@@ -550,7 +627,8 @@ LZ4HIP_DEVICE int lane4_decode_block(unsigned char* lds, int lane, bool active, 
         LZ4HIP_SECTION("B1 wait");
         // ---- (B1) the loads of the PREVIOUS iteration have landed (this iteration's kVm accesses stay in flight) ----
         wv::vm_wait_list<kVm>(usF, L);
-        lvalid = us_pend ? 1 : lvalid;
+        if constexpr (kMoves) lvalid |= us_pend;                     // (both are 0 or 1: no select)
+        else lvalid = us_pend ? 1 : lvalid;
         us_pend = 0;
 
 #if defined(LZ4HIP_DEC4_BALLAST_VALU) || defined(LZ4HIP_DEC4_BALLAST_LDS)
@@ -567,11 +645,17 @@ LZ4HIP_DEVICE int lane4_decode_block(unsigned char* lds, int lane, bool active, 
         LZ4HIP_SECTION("B3 chunk append");
         // ---- (B3) append the chunk ----
         {
-            const bool far_src = kind == kK4Far;
-            v0 = lit ? x0 : (far_src ? usF.x : v0);
-            v1 = lit ? x1 : (far_src ? usF.y : v1);
-            v2 = lit ? x2 : (far_src ? usF.z : v2);
-            v3 = lit ? x3 : (far_src ? usF.w : v3);
+            // the source of the chunk: the near-match rows, unless it is literals or a far match
+            if constexpr (kMoves) {                                  // (two EXEC regions of four moves)
+                L4_MOV(wv::cond(kind == kK4Lit), v0, x0, v1, x1, v2, x2, v3, x3);
+                L4_MOV(wv::cond(kind == kK4Far), v0, (uint32_t)usF.x, v1, (uint32_t)usF.y, v2, (uint32_t)usF.z, v3, (uint32_t)usF.w);
+            } else {
+                const bool far_src = kind == kK4Far;
+                v0 = lit ? x0 : (far_src ? usF.x : v0);
+                v1 = lit ? x1 : (far_src ? usF.y : v1);
+                v2 = lit ? x2 : (far_src ? usF.z : v2);
+                v3 = lit ? x3 : (far_src ? usF.w : v3);
+            }
             if ((kind == kK4Zero) & (n > 0)) {                       // offset 0 (corrupt streams only): keep what dst holds, 8 bytes at a time
                 uint64_t acc = 0;
                 for (int b = 0; b < n; b++) acc |= (uint64_t)dst[op + b] << (8 * b);
@@ -595,6 +679,8 @@ LZ4HIP_DEVICE int lane4_decode_block(unsigned char* lds, int lane, bool active, 
             if (perr) {                                              // corrupt stream: this lane is finished, nothing more is stored
                 done = 1; final_seen = 1; final_run = 0; result = p_res;
             }
+            // (every assignment below is ONE select already -- the compiler folds pgo into the lane mask with scalar instructions -- so a region
+            //  of moves would add its moves to the selects of the new values: tried, +5 vector-ALU instructions per iteration)
             if (pgo) {
                 const bool streamed = p_st > 0;
                 rem = streamed ? p_st : p_ml;

@@ -209,6 +209,70 @@ LZ4HIP_DEVICE uint32_t sel(mask_t m, uint32_t a, uint32_t b)      // m ? a : b
     asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(r) : "v"(b), "v"(a), "s"(m.v));
     return r;
 }
+// ---- conditional assignments: moves under a lane mask (lz4hip_decode_lane4.hpp) ---------------------------------------------
+// x = m ? a : x needs no select.  It is v_mov_b32 x, a issued with EXEC = m: a 32-bit encoding, where v_cndmask_b32_e64 is a 64-bit
+// one, and at three wavefronts per SIMD the 64-bit encodings are what the issue rate charges for (tools/microbench_valu_rate.hip,
+// profiles/lane_encodings/microbench_valu_rate.txt).  One EXEC region (s_and_saveexec_b64 .. s_mov_b64 exec, as in vm_load16_mask)
+// carries four or eight moves that share the mask (fewer do not pay: 9.5 SIMD-cycles for a region of one move, 4.55 for the select; inline
+// assembly allows 30 operands, so eight is where one statement ends).
+// The moves are issued in the order given.  A destination MAY be the source of an EARLIER move of the same call (t0 <- t1, t1 <- t2:
+// a window shifting in place); a source may NOT be the destination of an earlier one (whether it then sees the old or the new value
+// would depend on the register the compiler picks for it).  T is any 32-bit type.  s_and_saveexec_b64 writes SCC, and the statements
+// say so: the compiler does keep a scalar compare live across an asm statement that does not (seen in tools/microbench_valu_rate.hip).
+#define LZ4HIP_MM_D(i) T& d##i, T s##i
+#define LZ4HIP_MM_I(i) "v_mov_b32 %[d" #i "], %[s" #i "]\n\t"
+#define LZ4HIP_MM_O(i) [d##i] "+v"(d##i)
+#define LZ4HIP_MM_S(i) [s##i] "v"(s##i)
+#define LZ4HIP_MM_ASM(INSTRS, OUTS, INS)                                                                                          \
+    static_assert(sizeof(T) == 4, "32-bit moves");                                                                                \
+    uint64_t saved;                                                                                                               \
+    asm volatile("s_and_saveexec_b64 %[sv], %[m]\n\t" INSTRS "s_mov_b64 exec, %[sv]" : OUTS, [sv] "=&s"(saved) : INS, [m] "s"(m.v) : "scc")
+#define LZ4HIP_C ,
+template <class T> LZ4HIP_DEVICE void mov_mask(mask_t m, LZ4HIP_MM_D(0), LZ4HIP_MM_D(1), LZ4HIP_MM_D(2), LZ4HIP_MM_D(3))
+{ LZ4HIP_MM_ASM(LZ4HIP_MM_I(0) LZ4HIP_MM_I(1) LZ4HIP_MM_I(2) LZ4HIP_MM_I(3), LZ4HIP_MM_O(0) LZ4HIP_C LZ4HIP_MM_O(1) LZ4HIP_C LZ4HIP_MM_O(2) LZ4HIP_C LZ4HIP_MM_O(3),
+                LZ4HIP_MM_S(0) LZ4HIP_C LZ4HIP_MM_S(1) LZ4HIP_C LZ4HIP_MM_S(2) LZ4HIP_C LZ4HIP_MM_S(3)); }
+template <class T> LZ4HIP_DEVICE void mov_mask(mask_t m, LZ4HIP_MM_D(0), LZ4HIP_MM_D(1), LZ4HIP_MM_D(2), LZ4HIP_MM_D(3), LZ4HIP_MM_D(4), LZ4HIP_MM_D(5), LZ4HIP_MM_D(6), LZ4HIP_MM_D(7))
+{ LZ4HIP_MM_ASM(LZ4HIP_MM_I(0) LZ4HIP_MM_I(1) LZ4HIP_MM_I(2) LZ4HIP_MM_I(3) LZ4HIP_MM_I(4) LZ4HIP_MM_I(5) LZ4HIP_MM_I(6) LZ4HIP_MM_I(7),
+                LZ4HIP_MM_O(0) LZ4HIP_C LZ4HIP_MM_O(1) LZ4HIP_C LZ4HIP_MM_O(2) LZ4HIP_C LZ4HIP_MM_O(3) LZ4HIP_C LZ4HIP_MM_O(4) LZ4HIP_C LZ4HIP_MM_O(5) LZ4HIP_C LZ4HIP_MM_O(6) LZ4HIP_C LZ4HIP_MM_O(7),
+                LZ4HIP_MM_S(0) LZ4HIP_C LZ4HIP_MM_S(1) LZ4HIP_C LZ4HIP_MM_S(2) LZ4HIP_C LZ4HIP_MM_S(3) LZ4HIP_C LZ4HIP_MM_S(4) LZ4HIP_C LZ4HIP_MM_S(5) LZ4HIP_C LZ4HIP_MM_S(6) LZ4HIP_C LZ4HIP_MM_S(7)); }
+// ... and of four register PAIRS: v_pk_mov_b32 moves two dwords per instruction (2.6 SIMD-cycles per dword under EXEC where v_mov_b32 takes
+// 3.1, same file).  Destinations and sources are aligned pairs; op_sel:[0,1] takes the low dword from the first source operand and the
+// high dword from the second, which here are the same pair.
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+LZ4HIP_DEVICE void mov2_mask(mask_t m, u32x2& d0, u32x2 s0, u32x2& d1, u32x2 s1, u32x2& d2, u32x2 s2, u32x2& d3, u32x2 s3)
+{
+    uint64_t saved;
+    asm volatile("s_and_saveexec_b64 %[sv], %[m]\n\t"
+                 "v_pk_mov_b32 %[d0], %[s0], %[s0] op_sel:[0,1]\n\tv_pk_mov_b32 %[d1], %[s1], %[s1] op_sel:[0,1]\n\t"
+                 "v_pk_mov_b32 %[d2], %[s2], %[s2] op_sel:[0,1]\n\tv_pk_mov_b32 %[d3], %[s3], %[s3] op_sel:[0,1]\n\t"
+                 "s_mov_b64 exec, %[sv]"
+                 : [d0] "+v"(d0), [d1] "+v"(d1), [d2] "+v"(d2), [d3] "+v"(d3), [sv] "=&s"(saved)
+                 : [s0] "v"(s0), [s1] "v"(s1), [s2] "v"(s2), [s3] "v"(s3), [m] "s"(m.v) : "scc");
+}
+LZ4HIP_DEVICE void mov2_mask(mask_t m, u32x2& d0, u32x2 s0, u32x2& d1, u32x2 s1, u32x2& d2, u32x2 s2)
+{
+    uint64_t saved;
+    asm volatile("s_and_saveexec_b64 %[sv], %[m]\n\t"
+                 "v_pk_mov_b32 %[d0], %[s0], %[s0] op_sel:[0,1]\n\tv_pk_mov_b32 %[d1], %[s1], %[s1] op_sel:[0,1]\n\tv_pk_mov_b32 %[d2], %[s2], %[s2] op_sel:[0,1]\n\t"
+                 "s_mov_b64 exec, %[sv]"
+                 : [d0] "+v"(d0), [d1] "+v"(d1), [d2] "+v"(d2), [sv] "=&s"(saved) : [s0] "v"(s0), [s1] "v"(s1), [s2] "v"(s2), [m] "s"(m.v) : "scc");
+}
+// The five dwords a.x a.y b.x b.y c.x become a.y b.x b.y c.x c.y -- a window of register pairs shifted down by ONE dword in place, under
+// the lane mask: op_sel:[1,0] takes the high dword of the first source operand and the low dword of the second.  (c.y holds the old c.x afterwards.)
+LZ4HIP_DEVICE void shift_dword_mask(mask_t m, u32x2& a, u32x2& b, u32x2& c)
+{
+    uint64_t saved;
+    asm volatile("s_and_saveexec_b64 %[sv], %[m]\n\t"
+                 "v_pk_mov_b32 %[a], %[a], %[b] op_sel:[1,0]\n\tv_pk_mov_b32 %[b], %[b], %[c] op_sel:[1,0]\n\tv_pk_mov_b32 %[c], %[c], %[c] op_sel:[1,0]\n\t"
+                 "s_mov_b64 exec, %[sv]"
+                 : [a] "+v"(a), [b] "+v"(b), [c] "+v"(c), [sv] "=&s"(saved) : [m] "s"(m.v) : "scc");
+}
+#undef LZ4HIP_C
+#undef LZ4HIP_MM_ASM
+#undef LZ4HIP_MM_S
+#undef LZ4HIP_MM_O
+#undef LZ4HIP_MM_I
+#undef LZ4HIP_MM_D
 // vm_load16_pred / vm_store16_pred with the lane mask given
 template <int POLICY = 0>
 LZ4HIP_DEVICE void vm_load16_mask(mask_t mk, uint64_t addr, u32x4& v)

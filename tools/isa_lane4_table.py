@@ -4,7 +4,7 @@ Builds lz4hip_api.hip with -DLZ4HIP_SECTION_MARKERS (every LZ4HIP_SECTION("...")
 the listing), walks the kernel's listing in layout order and attributes every instruction to the marker before it.  The loop body exists
 twice (the flushing iteration and the one that requests input), so every section appears twice; rare paths (the byte-wise parser, the end of
 a block, the exact tail) are sections of their own and are left out of the per-iteration sum.  Instructions are classified as
-  VOP3  vector-ALU, 64-bit encoding (v_cndmask_b32_e64, v_perm_b32, v_alignbyte_b32, v_lshl_add_u32, v_and_or_b32, v_add3_u32, v_bfe_u32, *_e64 ...)
+  VOP3  vector-ALU, 64-bit encoding (v_cndmask_b32_e64, v_perm_b32, v_alignbyte_b32, v_lshl_add_u32, v_and_or_b32, v_add3_u32, v_bfe_u32, *_e64, v_pk_* ...)
   VOP2  vector-ALU, 32-bit encoding (v_add_u32, v_and_b32, v_mov_b32, v_cmp_*_e32 ...)
   SALU / LDS / VMEM / WAIT
 usage: python tools/isa_lane4_table.py [out.txt]      (CPU only: hipcc cross-compiles)"""
@@ -20,7 +20,7 @@ KERNEL = "_ZN6lz4hip19decode_lane4_kernelILb1ELi192ELi32ELi128ELi2ELi2ELi2ELi16E
 VOP3_ONLY = ("v_perm_b32", "v_alignbyte_b32", "v_alignbit_b32", "v_lshl_add_u32", "v_add_lshl_u32", "v_and_or_b32", "v_or3_b32", "v_add3_u32", "v_bfe_u32", "v_bfe_i32",
              "v_bfi_b32", "v_lshl_or_b32", "v_mad_u32_u24", "v_mad_u64_u32", "v_mul_lo_u32", "v_mul_hi_u32", "v_lshlrev_b64", "v_lshrrev_b64", "v_ashrrev_i64",
              "v_lshl_add_u64", "v_mbcnt_lo_u32_b32", "v_mbcnt_hi_u32_b32", "v_readlane_b32", "v_writelane_b32", "v_min3_u32", "v_max3_u32", "v_med3_u32", "v_xad_u32",
-             "v_cmp_class", "v_sad_u32", "v_msad_u8")
+             "v_cmp_class", "v_sad_u32", "v_msad_u8", "v_pk_")
 
 
 def classify(op, text):

@@ -1,6 +1,11 @@
-// Issue rate of the integer VALU instructions the lane decoder is made of, per SIMD, at 1 / 2 / 4 wavefronts per SIMD.
+// Issue rate of the integer VALU instructions the lane decoder is made of, per SIMD, at 1 / 3 / 4 / 8 wavefronts per SIMD.
 // Each wavefront runs ITER x 32 independent instructions of one kind (8 accumulators); reports SIMD-cycles per
-// wavefront-instruction assuming 2.4 GHz.   hipcc --offload-arch=gfx950 -O3 tools/microbench_valu_rate.hip -o tools/microbench_valu_rate
+// wavefront-instruction assuming 2.4 GHz.
+// Kinds 20 .. 26 are the forms of a CONDITIONAL ASSIGNMENT x = m ? a : x that are not a select: v_mov_b32 inside an EXEC region
+// (s_and_saveexec_b64 .. s_mov_b64 exec; 1, 4 or 8 moves per region, the per-lane mask differs from region to region) and v_pk_mov_b32
+// (two dwords per instruction), alone and inside such a region.  Their ITER x 32 are MOVED DWORDS: the line gives SIMD-cycles per moved
+// dword with the two scalar instructions of each region included, next to what v_cndmask_b32_e64 (kind 10) costs per dword.
+//   hipcc --offload-arch=gfx950 -O3 tools/microbench_valu_rate.hip -o tools/microbench_valu_rate
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdint>
@@ -16,6 +21,37 @@ __global__ void __launch_bounds__(64) k(uint32_t* out, int iters, uint32_t s)
     for (int i = 0; i < iters; i++) {
 #pragma unroll
         for (int r = 0; r < 4; r++) {
+            if (KIND >= 20) {
+                // 8 moved dwords per trip of r, like the 8 instructions of the other kinds; the mask of a region depends on r and on its place
+                const uint64_t ma = m64 ^ (0x0123456789ABCDEFull * (uint64_t)(r + 1)), mb = ~ma ^ 0xF0F0F0F00F0F0F0Full;
+                uint64_t sv;                                         // (s_and_saveexec_b64 writes SCC: the statements say so, or the compiler keeps the loop's compare live across them)
+                uint64_t* const q = (uint64_t*)a;                    // a[0..7] as four register pairs
+#define MOV1(J) "v_mov_b32 %" #J ", %[b]\n\t"
+#define RGN(M, BODY) "s_and_saveexec_b64 %[sv], %[" M "]\n\t" BODY "s_mov_b64 exec, %[sv]\n\t"
+#define A8 "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(a[4]), "+v"(a[5]), "+v"(a[6]), "+v"(a[7]), [sv] "=&s"(sv)
+#define Q4 "+v"(q[0]), "+v"(q[1]), "+v"(q[2]), "+v"(q[3]), [sv] "=&s"(sv)
+                if (KIND == 20)                                      // one move per region
+                    asm volatile(RGN("ma", MOV1(0)) RGN("mb", MOV1(1)) RGN("ma", MOV1(2)) RGN("mb", MOV1(3)) RGN("ma", MOV1(4)) RGN("mb", MOV1(5)) RGN("ma", MOV1(6)) RGN("mb", MOV1(7))
+                                 : A8 : [b] "v"(b), [ma] "s"(ma), [mb] "s"(mb) : "scc");
+                if (KIND == 21)                                      // four moves per region
+                    asm volatile(RGN("ma", MOV1(0) MOV1(1) MOV1(2) MOV1(3)) RGN("mb", MOV1(4) MOV1(5) MOV1(6) MOV1(7)) : A8 : [b] "v"(b), [ma] "s"(ma), [mb] "s"(mb) : "scc");
+                if (KIND == 22)                                      // eight moves per region
+                    asm volatile(RGN("ma", MOV1(0) MOV1(1) MOV1(2) MOV1(3) MOV1(4) MOV1(5) MOV1(6) MOV1(7)) : A8 : [b] "v"(b), [ma] "s"(ma) : "scc");
+#define PK(J) "v_pk_mov_b32 %" #J ", %[p], %[p] op_sel:[0,1]\n\t"      /* d.lo = p.lo, d.hi = p.hi */
+#define PKS(J) "v_pk_mov_b32 %" #J ", %[p], %[p2] op_sel:[1,0]\n\t"    /* d.lo = p.hi, d.hi = p2.lo: a window shifted by one dword */
+                const uint64_t p = ((uint64_t)c << 32) | b, p2 = ((uint64_t)b << 32) | c;
+                if (KIND == 23) asm volatile(PK(0) PK(1) PK(2) PK(3) : "+v"(q[0]), "+v"(q[1]), "+v"(q[2]), "+v"(q[3]) : [p] "v"(p));
+                if (KIND == 24) asm volatile(RGN("ma", PK(0) PK(1) PK(2) PK(3)) : Q4 : [p] "v"(p), [ma] "s"(ma) : "scc");          // one region of four: 8 dwords
+                if (KIND == 25) asm volatile(PKS(0) PKS(1) PKS(2) PKS(3) : "+v"(q[0]), "+v"(q[1]), "+v"(q[2]), "+v"(q[3]) : [p] "v"(p), [p2] "v"(p2));
+                if (KIND == 26) asm volatile(RGN("ma", PKS(0) PKS(1) PKS(2) PKS(3)) : Q4 : [p] "v"(p), [p2] "v"(p2), [ma] "s"(ma) : "scc");
+#undef MOV1
+#undef RGN
+#undef A8
+#undef Q4
+#undef PK
+#undef PKS
+                continue;
+            }
 #pragma unroll
             for (int j = 0; j < 8; j++) {
                 if (KIND == 0) asm volatile("v_add_u32 %0, %0, %1" : "+v"(a[j]) : "v"(b));
@@ -50,7 +86,7 @@ template <int KIND>
 void run(const char* name, uint32_t* d, int cus)
 {
     const int iters = 20000;
-    for (int w : { 1, 3, 8 }) {
+    for (int w : { 1, 3, 4, 8 }) {
         const int grid = cus * 4 * w;
         hipEvent_t a, b; hipEventCreate(&a); hipEventCreate(&b);
         k<KIND><<<grid, 64>>>(d, 100, 1);
@@ -59,7 +95,8 @@ void run(const char* name, uint32_t* d, int cus)
         hipEventRecord(b); hipEventSynchronize(b);
         float ms; hipEventElapsedTime(&ms, a, b);
         const double cyc = ms * 1e-3 * 2.4e9 / ((double)iters * 32 * w);
-        printf("%-18s waves/SIMD %d: %.3f ms  %.2f SIMD-cycles per wavefront-instruction (at 2.4 GHz)\n", name, w, ms, cyc);
+        if (KIND >= 20) printf("%-34s waves/SIMD %d: %.3f ms  %.2f SIMD-cycles per moved dword of a wavefront (at 2.4 GHz)\n", name, w, ms, cyc);
+        else printf("%-18s waves/SIMD %d: %.3f ms  %.2f SIMD-cycles per wavefront-instruction (at 2.4 GHz)\n", name, w, ms, cyc);
     }
 }
 
@@ -75,5 +112,8 @@ int main()
     run<10>("v_cndmask_e64 sgpr", d, cus); run<11>("v_mov_b32", d, cus); run<12>("v_and_b32", d, cus); run<13>("v_lshlrev_b32", d, cus);
     run<14>("v_bfe_u32", d, cus); run<15>("v_cmp_e64 ->sgpr", d, cus); run<16>("v_cmp+v_cndmask vcc (x2)", d, cus); run<17>("v_add3_u32", d, cus);
     run<18>("v_sub_u32", d, cus); run<19>("v_add_u32 d=b+c", d, cus);
+    run<20>("v_mov under EXEC, 1 per region", d, cus); run<21>("v_mov under EXEC, 4 per region", d, cus); run<22>("v_mov under EXEC, 8 per region", d, cus);
+    run<23>("v_pk_mov_b32 [0,1]", d, cus); run<24>("v_pk_mov_b32 [0,1] under EXEC, 4", d, cus);
+    run<25>("v_pk_mov_b32 [1,0] (dword shift)", d, cus); run<26>("v_pk_mov_b32 [1,0] under EXEC, 4", d, cus);
     return 0;
 }
