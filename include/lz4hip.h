@@ -126,7 +126,7 @@ int lz4hip_decode_batch_host(const lz4hip_batch_t* b, int known_output_size);
  * The sizes calls are lz4hip_decoded_sizes_device / _host for such blocks: a match may start up to min(dict_len, 65 535) bytes before its
  * block.  They need no byte of the dictionary; the scratch query is lz4hip_decoded_sizes_scratch_bytes.
  * Out of scope: encoding against a dictionary (the reference has no such parse to be bit-exact to, and preloading the encoders' tables is
- * a design of its own); LZ4 frames with a dictionary (below: they stay refused); a dictionary per block; the lane mapping; a _multi host
+ * a design of its own); LZ4 frames with a dictionary (below: lz4hip_lz4f_*_dict_*); a dictionary per block; the lane mapping; a _multi host
  * form; the compact and packed decode forms. */
 int lz4hip_decode_batch_dict_device(const lz4hip_batch_t* b, const void* dict, int64_t dict_len, int known_output_size, void* stream);
 int lz4hip_decode_batch_dict_host(const lz4hip_batch_t* b, const void* dict, int64_t dict_len, int known_output_size);
@@ -714,7 +714,7 @@ int lz4hip_xxh32_rows_device(const void* data, const int64_t* off, int64_t strid
 #define LZ4HIP_LZ4F_VERIFY_CONTENT   2u   /* one serial row over dst[0, decoded_bytes): only when all of it was written and no block is bad */
 /* ... and an opt-in of the four decode calls (lz4hip_lz4f_decode_* and lz4hip_lz4f_batch_decode_*): frames whose blocks are LINKED
  * (FLG.5 clear -- the default of LZ4F_compressFrame, python-lz4 and Arrow's LZ4_FRAME codec for content above one block) are decoded
- * instead of refused with UNSUPPORTED_LINKED.  Without the flag every call is what it was; frames with a dictionary stay refused either way (block batches: lz4hip_decode_batch_dict_*).
+ * instead of refused with UNSUPPORTED_LINKED.  Without the flag every call is what it was; these four calls refuse frames with a dictionary ID either way (lz4hip_lz4f_*_dict_* take them).
  * COST: a linked frame is ONE serial chain and runs on ONE wavefront, so one large linked frame decodes far slower than on a host core
  * (INTEGRATION.md 4 has a lone wavefront's figures).  The flag pays only in batches of many items, one wavefront each.  With it:
  *  - an independent frame or item takes the path it always took: the same bytes, the same record;
@@ -742,7 +742,7 @@ int lz4hip_xxh32_rows_device(const void* data, const int64_t* off, int64_t strid
 #define LZ4HIP_LZ4F_BAD_HEADER             2   /* version, a reserved bit, or a block size id below 4 */
 #define LZ4HIP_LZ4F_HEADER_CHECKSUM        3
 #define LZ4HIP_LZ4F_UNSUPPORTED_LINKED     4   /* FLG.5 clear: linked blocks decode only in order, each against the 64 KiB before it (LZ4HIP_LZ4F_ACCEPT_LINKED takes them) */
-#define LZ4HIP_LZ4F_UNSUPPORTED_DICT       5   /* FLG.0 set: frames with a dictionary stay refused (block batches: lz4hip_decode_batch_dict_*) */
+#define LZ4HIP_LZ4F_UNSUPPORTED_DICT       5   /* FLG.0 set, in a call without a dictionary: lz4hip_lz4f_decode_dict_* and lz4hip_lz4f_batch_decode_dict_* take such frames */
 #define LZ4HIP_LZ4F_SLOT_TOO_SMALL         6   /* the frame's block maximum exceeds slot_bytes: call again with .block_max */
 #define LZ4HIP_LZ4F_TRUNCATED              7   /* the frame ends inside the descriptor, a size field, data, a checksum, or before its EndMark */
 #define LZ4HIP_LZ4F_BAD_BLOCK_SIZE         8   /* a size field above the frame's block maximum (tested before the truncation rule) */
@@ -751,6 +751,7 @@ int lz4hip_xxh32_rows_device(const void* data, const int64_t* off, int64_t strid
 #define LZ4HIP_LZ4F_CONTENT_SIZE_ERROR     11
 #define LZ4HIP_LZ4F_CONTENT_CHECKSUM_ERROR 12
 #define LZ4HIP_LZ4F_TABLE_FULL             13  /* more blocks than max_blocks; .blocks = the count needed */
+#define LZ4HIP_LZ4F_DICT_ID_MISMATCH       14  /* the dictionary calls: the descriptor's dictionary ID is not the non-zero dict_id of the call (a descriptor error, at the ID field) */
 #define LZ4HIP_LZ4F_KIND_FRAME     0
 #define LZ4HIP_LZ4F_KIND_SKIPPABLE 1           /* magic 0x184D2A50 .. 0x184D2A5F: frame_bytes = 8 + its size, no output */
 typedef struct lz4hip_lz4f_info {
@@ -794,6 +795,39 @@ int lz4hip_lz4f_decode_device(const void* src, int64_t src_len, int32_t slot_byt
 int lz4hip_lz4f_encode_host(const void* src, int64_t src_len, int block_size_id, int mode, unsigned flags, void* dst, int64_t dst_cap, int64_t* dst_len);
 int lz4hip_lz4f_decode_host(const void* src, int64_t src_len, unsigned flags, void* dst, int64_t dst_cap, lz4hip_lz4f_info_t* info);
 
+/* ---- LZ4 frames decoded with a dictionary ------------------------------------------------------------
+ * LZ4F_decompress_usingDict (frames of LZ4F_compressFrame_usingCDict, K4os streams with a dictionary): the four decode calls, argument
+ * for argument, with ONE dictionary dict[0, dict_len) per call and the ID the caller expects behind the source arguments.  The one-frame
+ * forms are here, the batch forms behind lz4hip_lz4f_batch_decode_host below.
+ *   - The dictionary's bytes count as lying immediately in front of the first output byte of EVERY frame of the call, whether or not
+ *     the frame's descriptor carries a dictionary ID (FLG.0).
+ *   - An INDEPENDENT frame (FLG.5 set): every block sees the dictionary and only the dictionary, never the block before it.  Block k's
+ *     result and bytes are what lz4hip_decode_batch_dict_device gives that block.
+ *   - A LINKED frame (it needs LZ4HIP_LZ4F_ACCEPT_LINKED, as ever): a match at item offset p with offset o > p reads
+ *     dict[dict_len - (o - p)], legal if and only if o - p <= dict_len.  A source before the dictionary's first byte is what a source
+ *     before the frame is in the plain calls: the decoder refuses that block, which keeps its planned place -- CORRUPT_BLOCK at its size
+ *     field, good_bytes the bytes before it.  Once 65 535 bytes of the item lie in front of a block the dictionary is out of reach.
+ *   - Only the dictionary's last 65 535 bytes are ever read, and nothing outside [dict, dict + dict_len).  Any alignment.  The device
+ *     calls do not copy it: it must stay valid until the kernels have run.  The host calls upload those last min(dict_len, 65 535)
+ *     bytes once per call, into staging apart from the call's image.
+ *   - dict_id == 0: no check.  Otherwise a frame whose descriptor carries a DIFFERENT ID gets LZ4HIP_LZ4F_DICT_ID_MISMATCH in the place
+ *     of UNSUPPORTED_DICT -- after the header checksum, before the linked check and the slot check; no block is walked; error_offset is
+ *     the ID field's (6, or 14 behind a content size).  A frame without an ID is accepted whatever dict_id is.
+ *   - dict_len == 0: dict may be NULL, dict_id is ignored and the call IS the plain call, record for record and byte for byte,
+ *     UNSUPPORTED_DICT for frames with an ID included.  dict_len < 0, or dict == NULL with dict_len > 0: LZ4HIP_E_ARGUMENT, checked
+ *     before a device is looked for.
+ *   - Scratch (the plain calls' *_decode_scratch_bytes queries), flags, the clipping, the size query, written_items, the checksum
+ *     verdicts and the precedence of outcomes are the plain calls'.
+ * COST: the rounds of a dictionary call decode EVERY compressed independent block with one wavefront per block at every batch size, as
+ * lz4hip_decode_batch_dict_device does (the lane mapping has no dictionary mode): lz4hip_dispatch_counts moves LZ4HIP_K_DECODE_WAVE only,
+ * and a large batch decodes at that mapping's rate.  Linked items run one wavefront each, as in the plain calls.
+ * Out of scope: encoding frames with a dictionary; a dictionary per item; the lane mapping for dictionary rows; span forms. */
+int lz4hip_lz4f_decode_dict_device(const void* src, int64_t src_len, const void* dict, int64_t dict_len, uint32_t dict_id, int32_t slot_bytes,
+                                   int64_t max_blocks, int64_t round_blocks, unsigned flags, void* scratch, int64_t scratch_bytes, void* dst, int64_t dst_cap,
+                                   lz4hip_lz4f_info_t* info, void* stream);
+int lz4hip_lz4f_decode_dict_host(const void* src, int64_t src_len, const void* dict, int64_t dict_len, uint32_t dict_id, unsigned flags, void* dst,
+                                 int64_t dst_cap, lz4hip_lz4f_info_t* info);
+
 /* ---- batches of LZ4 frames ---------------------------------------------------------------------------
  * Many independent frames per call, in the layout of the lz4hip_streams_* and lz4hip_wrap_* calls: one buffer src of src_len bytes plus
  * device offsets src_off[n + 1]; item i is src[src_off[i], src_off[i + 1]); outputs lie back to back in dst with dst_off[n + 1] (device),
@@ -801,8 +835,8 @@ int lz4hip_lz4f_decode_host(const void* src, int64_t src_len, unsigned flags, vo
  * launch-only on the caller's stream, no device value read on the host, no allocation, scratch from the caller (the *_scratch_bytes
  * queries), arguments checked before the device is looked for, 0 or LZ4HIP_E_* returned.
  *
- * Out of scope: frames with a dictionary (the item's outcome says so; block batches against one: lz4hip_decode_batch_dict_*; frames with linked blocks are the caller's choice:
- * LZ4HIP_LZ4F_ACCEPT_LINKED); following appended frames inside one item (an
+ * Out of scope: a dictionary per item (one per call: lz4hip_lz4f_batch_decode_dict_*; without one a frame with a dictionary ID is refused,
+ * the item's outcome says so; frames with linked blocks are the caller's choice: LZ4HIP_LZ4F_ACCEPT_LINKED); following appended frames inside one item (an
  * item is ONE frame, what lies behind it is left alone and shows only in frame_bytes); span forms (chosen items of an arena); a block
  * decoder for large blocks -- one wavefront still decodes one block.
  *
@@ -851,6 +885,15 @@ int lz4hip_lz4f_batch_encode_host(const void* src, int64_t src_len, const int64_
                                   void* dst, int64_t dst_cap, int64_t* dst_off);
 int lz4hip_lz4f_batch_decode_host(const void* src, int64_t src_len, const int64_t* src_off, int64_t n, unsigned flags, void* dst, int64_t dst_cap,
                                   int64_t* dst_off, lz4hip_lz4f_info_t* item_info, lz4hip_lz4f_batch_info_t* info);
+/* The batch decode with ONE dictionary for all items ("LZ4 frames decoded with a dictionary", above: the contract is there).  A
+ * DICT_ID_MISMATCH is the ITEM's outcome, as UNSUPPORTED_LINKED is. */
+int lz4hip_lz4f_batch_decode_dict_device(const void* src, int64_t src_len, const int64_t* src_off, int64_t n, const void* dict, int64_t dict_len,
+                                         uint32_t dict_id, int32_t slot_bytes, int64_t max_blocks, int64_t round_blocks, unsigned flags, void* scratch,
+                                         int64_t scratch_bytes, void* dst, int64_t dst_cap, int64_t* dst_off, lz4hip_lz4f_info_t* item_info,
+                                         lz4hip_lz4f_batch_info_t* info, int64_t* written_items, void* stream);
+int lz4hip_lz4f_batch_decode_dict_host(const void* src, int64_t src_len, const int64_t* src_off, int64_t n, const void* dict, int64_t dict_len, uint32_t dict_id,
+                                       unsigned flags, void* dst, int64_t dst_cap, int64_t* dst_off, lz4hip_lz4f_info_t* item_info,
+                                       lz4hip_lz4f_batch_info_t* info);
 
 /* ---- diagnostics ---------------------------------------------------------------------------------
  * Launch counters per kernel family since the library was loaded: which block->hardware mapping a call

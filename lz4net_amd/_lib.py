@@ -91,7 +91,7 @@ class Lz4fBatchInfo(C.Structure):
 
 (LZ4F_OK, LZ4F_BAD_MAGIC, LZ4F_BAD_HEADER, LZ4F_HEADER_CHECKSUM, LZ4F_UNSUPPORTED_LINKED, LZ4F_UNSUPPORTED_DICT, LZ4F_SLOT_TOO_SMALL,
  LZ4F_TRUNCATED, LZ4F_BAD_BLOCK_SIZE, LZ4F_CORRUPT_BLOCK, LZ4F_BLOCK_CHECKSUM_ERROR, LZ4F_CONTENT_SIZE_ERROR, LZ4F_CONTENT_CHECKSUM_ERROR,
- LZ4F_TABLE_FULL) = range(14)
+ LZ4F_TABLE_FULL, LZ4F_DICT_ID_MISMATCH) = range(15)
 LZ4F_BLOCK_CHECKSUM, LZ4F_CONTENT_CHECKSUM, LZ4F_CONTENT_SIZE = 1, 2, 4
 LZ4F_VERIFY_BLOCKS, LZ4F_VERIFY_CONTENT, LZ4F_ACCEPT_LINKED = 1, 2, 8
 LZ4F_KIND_FRAME, LZ4F_KIND_SKIPPABLE = 0, 1
@@ -218,6 +218,16 @@ SYMBOLS = [
     ("lz4hip_lz4f_batch_encode_host", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_uint, C.c_void_p, C.c_int64, C.c_void_p]),
     ("lz4hip_lz4f_batch_decode_host", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_uint, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                                 C.POINTER(Lz4fBatchInfo)]),
+    # ... with a dictionary: dict, dict_len, dict_id behind the source arguments
+    ("lz4hip_lz4f_decode_dict_device", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_uint32, C.c_int32, C.c_int64, C.c_int64, C.c_uint,
+                                                 C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    ("lz4hip_lz4f_decode_dict_host", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_uint32, C.c_uint, C.c_void_p, C.c_int64,
+                                               C.POINTER(Lz4fInfo)]),
+    ("lz4hip_lz4f_batch_decode_dict_device", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_uint32, C.c_int32, C.c_int64,
+                                                       C.c_int64, C.c_uint, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                       C.c_void_p, C.c_void_p]),
+    ("lz4hip_lz4f_batch_decode_dict_host", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_uint32, C.c_uint, C.c_void_p,
+                                                     C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(Lz4fBatchInfo)]),
 ]
 
 _lib = None

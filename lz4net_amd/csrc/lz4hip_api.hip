@@ -1277,6 +1277,9 @@ struct HipBackend {
     int fill(void* p, int byte, size_t bytes) { HIP_TRY(hipMemsetAsync(p, byte, bytes, stream)); return 0; }
     int encode(const lz4hip_batch_t* b, int mode) { return launch_encode(b, mode, stream); }
     int decode(const lz4hip_batch_t* b, int known) { return launch_decode(b, known, stream); }
+    // (the dictionary calls of LZ4 frames: `reach` <= 65 535 bytes that end at dict_end)
+    int decode_dict(const lz4hip_batch_t* b, const uint8_t* dict_end, int32_t reach, int known) { return launch_decode_dict(b, dict_end - reach, reach, known, stream); }
+    int dict_upload(const uint8_t* from, int64_t bytes, uint8_t*& dev) { return host->dict_upload(from, bytes, dev); }
     int last_error() { HIP_TRY(hipGetLastError()); return 0; }
     int fail(int code, const std::string& what) { return ::fail(code, what); }
     int reserve(size_t bytes, uint8_t*& base) { int rc = host->scratch.reserve(bytes); base = (uint8_t*)host->scratch.p; return rc; }
@@ -2053,6 +2056,29 @@ int lz4hip_lz4f_decode_device(const void* src, int64_t src_len, int32_t slot_byt
     return lz4f_decode_run(be, p);
 }
 
+// The dictionary calls: the plain call's plan behind the dictionary's check, then the sequence with the dictionary handed to the walk,
+// the rounds and the linked decode (lz4hip_framing.hpp); with dict_len == 0 the plain sequence.
+int lz4hip_lz4f_decode_dict_device(const void* src, int64_t src_len, const void* dict, int64_t dict_len, uint32_t dict_id, int32_t slot_bytes,
+                                   int64_t max_blocks, int64_t round_blocks, unsigned flags, void* scratch, int64_t scratch_bytes, void* dst, int64_t dst_cap,
+                                   lz4hip_lz4f_info_t* info, void* stream)
+{
+    HipBackend be = { (hipStream_t)stream };
+    Lz4fDecodePlan p;
+    if (int rc = lz4f_decode_dict_plan(be, src, src_len, dict, dict_len, slot_bytes, max_blocks, round_blocks, flags, scratch, scratch_bytes, dst, dst_cap, info, p))
+        return rc;
+    if (int rc = ensure_device()) return rc;
+    return lz4f_decode_dict_run(be, p, dict, dict_len, dict_id);
+}
+
+int lz4hip_lz4f_decode_dict_host(const void* src, int64_t src_len, const void* dict, int64_t dict_len, uint32_t dict_id, unsigned flags, void* dst,
+                                 int64_t dst_cap, lz4hip_lz4f_info_t* info)
+{
+    HipBackend be = {};
+    if (int rc = check_dict(dict, dict_len)) return rc;
+    if (int rc = stream_host_context(be)) return rc;
+    return lz4f_decode_dict_host(be, src, src_len, dict, dict_len, dict_id, flags, dst, dst_cap, info);
+}
+
 int lz4hip_lz4f_encode_host(const void* src, int64_t src_len, int block_size_id, int mode, unsigned flags, void* dst, int64_t dst_cap, int64_t* dst_len)
 {
     HipBackend be = {};
@@ -2101,6 +2127,29 @@ int lz4hip_lz4f_batch_decode_device(const void* src, int64_t src_len, const int6
                                         dst_off, item_info, info, written_items, p)) return rc;
     if (int rc = ensure_device()) return rc;
     return lz4f_batch_decode_run(be, p);
+}
+
+int lz4hip_lz4f_batch_decode_dict_device(const void* src, int64_t src_len, const int64_t* src_off, int64_t n, const void* dict, int64_t dict_len,
+                                         uint32_t dict_id, int32_t slot_bytes, int64_t max_blocks, int64_t round_blocks, unsigned flags, void* scratch,
+                                         int64_t scratch_bytes, void* dst, int64_t dst_cap, int64_t* dst_off, lz4hip_lz4f_info_t* item_info,
+                                         lz4hip_lz4f_batch_info_t* info, int64_t* written_items, void* stream)
+{
+    HipBackend be = { (hipStream_t)stream };
+    Lz4fBatchDecodePlan p;
+    if (int rc = lz4f_batch_decode_dict_plan(be, src, src_len, src_off, n, dict, dict_len, slot_bytes, max_blocks, round_blocks, flags, scratch, scratch_bytes, dst,
+                                             dst_cap, dst_off, item_info, info, written_items, p)) return rc;
+    if (int rc = ensure_device()) return rc;
+    return lz4f_batch_decode_dict_run(be, p, dict, dict_len, dict_id);
+}
+
+int lz4hip_lz4f_batch_decode_dict_host(const void* src, int64_t src_len, const int64_t* src_off, int64_t n, const void* dict, int64_t dict_len, uint32_t dict_id,
+                                       unsigned flags, void* dst, int64_t dst_cap, int64_t* dst_off, lz4hip_lz4f_info_t* item_info,
+                                       lz4hip_lz4f_batch_info_t* info)
+{
+    HipBackend be = {};
+    if (int rc = check_dict(dict, dict_len)) return rc;
+    if (int rc = stream_host_context(be)) return rc;
+    return lz4f_batch_decode_dict_host(be, src, src_len, src_off, n, dict, dict_len, dict_id, flags, dst, dst_cap, dst_off, item_info, info);
 }
 
 int lz4hip_lz4f_batch_encode_host(const void* src, int64_t src_len, const int64_t* src_off, int64_t n, int block_size_id, int mode, unsigned flags,

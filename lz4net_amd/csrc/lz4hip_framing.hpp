@@ -1540,7 +1540,7 @@ static_assert(kLz4fOk == LZ4HIP_LZ4F_OK && kLz4fBadMagic == LZ4HIP_LZ4F_BAD_MAGI
               kLz4fTruncated == LZ4HIP_LZ4F_TRUNCATED && kLz4fBadBlockSize == LZ4HIP_LZ4F_BAD_BLOCK_SIZE &&
               kLz4fCorruptBlock == LZ4HIP_LZ4F_CORRUPT_BLOCK && kLz4fBlockChecksumError == LZ4HIP_LZ4F_BLOCK_CHECKSUM_ERROR &&
               kLz4fContentSizeError == LZ4HIP_LZ4F_CONTENT_SIZE_ERROR && kLz4fContentChecksumError == LZ4HIP_LZ4F_CONTENT_CHECKSUM_ERROR &&
-              kLz4fTableFull == LZ4HIP_LZ4F_TABLE_FULL, "lz4f statuses");
+              kLz4fTableFull == LZ4HIP_LZ4F_TABLE_FULL && kLz4fDictIdMismatch == LZ4HIP_LZ4F_DICT_ID_MISMATCH, "lz4f statuses");
 static_assert(sizeof(Lz4fInfo) == sizeof(lz4hip_lz4f_info_t) && offsetof(Lz4fInfo, frame_bytes) == offsetof(lz4hip_lz4f_info_t, frame_bytes) &&
               offsetof(Lz4fInfo, error) == offsetof(lz4hip_lz4f_info_t, error) && offsetof(Lz4fInfo, checks) == offsetof(lz4hip_lz4f_info_t, checks),
               "Lz4fInfo must mirror lz4hip_lz4f_info_t");
@@ -1689,6 +1689,33 @@ int lz4f_encode(B& be, const void* src, int64_t src_len, int block_size_id, int 
 inline bool lz4f_slot_valid(int32_t slot_bytes) { return slot_bytes == 0 || slot_bytes == 65536 || slot_bytes == 262144 || slot_bytes == 1048576 || slot_bytes == 4194304; }
 inline int32_t lz4f_slot(int32_t slot_bytes) { return slot_bytes == 0 ? 4194304 : slot_bytes; }                    // (of a valid slot_bytes)
 constexpr unsigned kLz4fDecodeFlags = kLz4fVerifyBlocks | kLz4fVerifyContent | kLz4fAcceptLinked;
+static_assert(!(kLz4fDecodeFlags & kLz4fWithDict), "the walk's internal bit is no public flag");
+
+// ---- the dictionary of the dictionary calls (lz4hip_lz4f_*_dict_*), for both decode sequences below --------------------------------------
+// What a sequence is handed in its place: Lz4fNoDict by the plain calls, whose sequences are what they were, or the bytes of the call's
+// dictionary that a match can reach -- its last min(dict_len, 65 535), in device memory, which END at `end` -- and the ID a frame's must
+// equal (0: any).  The overloads below are all that differs: the walk's flag and ID, the rounds' block decoder (a backend needs
+// decode_dict only where a sequence is instantiated with a dictionary) and the linked decode's kernel.
+struct Lz4fNoDict {};
+struct Lz4fDict { const uint8_t* end; int32_t len; uint32_t id; };
+inline Lz4fDict lz4f_dict_of(const void* dict, int64_t dict_len, uint32_t dict_id)
+{
+    return { (const uint8_t*)dict + dict_len, (int32_t)(dict_len < kLz4fLinkedHistory ? dict_len : kLz4fLinkedHistory), dict_id };
+}
+inline unsigned lz4f_walk_flags(unsigned flags, Lz4fNoDict) { return flags; }
+inline unsigned lz4f_walk_flags(unsigned flags, const Lz4fDict&) { return flags | kLz4fWithDict; }
+inline uint32_t lz4f_walk_dict_id(Lz4fNoDict) { return 0; }
+inline uint32_t lz4f_walk_dict_id(const Lz4fDict& d) { return d.id; }
+template <class B> int lz4f_round_decode(B& be, const lz4hip_batch_t* rb, Lz4fNoDict) { return be.decode(rb, 0); }
+template <class B> int lz4f_round_decode(B& be, const lz4hip_batch_t* rb, const Lz4fDict& d) { return be.decode_dict(rb, d.end, d.len, 0); }
+// dict_len < 0, or no dictionary where there should be one
+template <class B>
+int lz4f_dict_check(B& be, const void* dict, int64_t dict_len)
+{
+    if (dict_len < 0) return be.fail(LZ4HIP_E_ARGUMENT, "dictionary: dict_len < 0");
+    if (dict_len > 0 && !dict) return be.fail(LZ4HIP_E_ARGUMENT, "dictionary: dict is NULL and dict_len > 0");
+    return 0;
+}
 
 // ---- frames with linked blocks (lz4hip_lz4f_linked.hpp), for both decode sequences below ------------------------------------------------
 // one lane per table row in single-wavefront workgroups; one wavefront per item in workgroups of kWaveDecodeWavesPerGroup: more rows
@@ -1713,9 +1740,15 @@ int lz4f_linked_plan_run(B& be, const Lz4fLinked& a)
 }
 // after the last round, before the records: the linked items, one wavefront each
 template <class B>
-int lz4f_linked_decode_run(B& be, const Lz4fLinked& a)
+int lz4f_linked_decode_run(B& be, const Lz4fLinked& a, Lz4fNoDict)
 {
     be.launch(lz4f_linked_decode_kernel, lz4f_linked_items_grid(a.n), 64 * kWaveDecodeWavesPerGroup, a);
+    return be.last_error();
+}
+template <class B>
+int lz4f_linked_decode_run(B& be, const Lz4fLinked& a, const Lz4fDict& d)
+{
+    be.launch(lz4f_linked_decode_dict_kernel, lz4f_linked_items_grid(a.n), 64 * kWaveDecodeWavesPerGroup, a, d.end, d.len);
     return be.last_error();
 }
 
@@ -1757,10 +1790,11 @@ int lz4f_tables_init(B& be, const Lz4fTables& t)
 // After the walk: the block checksums if asked for, the state block, the linked rows' plan if accepted, the compact decode's rounds
 // over ALL max_blocks rows with the frames' own sizes step and pack layout (p.b is the table: its src_off, dec_len and result columns
 // and its dst_off as p.dst_off), the linked items' decode.  `total` and `base` are the batch's (nullptr: one frame), `item_bad` every
-// item's lowest bad row: for one frame the state block's kPackedBad slot.
-template <class B>
+// item's lowest bad row: for one frame the state block's kPackedBad slot.  `dict`: Lz4fNoDict, or the call's dictionary, which every
+// compressed row of the rounds and every linked row then has in front of it.
+template <class B, class D>
 int lz4f_rows_run(B& be, const PackedPlan& p, const Lz4fTables& t, unsigned flags, int64_t items, const int64_t* base, const int64_t* total,
-                  unsigned long long* item_bad)
+                  unsigned long long* item_bad, const D& dict)
 {
     const uint8_t* src = (const uint8_t*)p.b.src;
     if (flags & kLz4fVerifyBlocks) {
@@ -1775,10 +1809,10 @@ int lz4f_rows_run(B& be, const PackedPlan& p, const Lz4fTables& t, unsigned flag
         const int64_t f = a.first;
         return Lz4fRound{ a, src, t.src_off + f, t.stored + f, t.row + f, t.plan + f, t.item ? t.item + f : nullptr, t.walk, item_bad };
     };
-    LZ4HIP_FRAMING_TRY(packed_rounds(be, p, [&](const lz4hip_batch_t* rb) { return be.decode(rb, 0); },
+    LZ4HIP_FRAMING_TRY(packed_rounds(be, p, [&](const lz4hip_batch_t* rb) { return lz4f_round_decode(be, rb, dict); },
                                      [&](const PackedRound& a, Grid grid) { be.launch(lz4f_round_sizes_kernel, grid, kStreamThreads, round(a)); },
                                      [&](const PackedRound& a, Grid grid) { be.launch(lz4f_round_pack_kernel, grid, kStreamThreads, Lz4fRoundLayout{ round(a) }, p.dst, p.dst_cap); }));
-    if (flags & kLz4fAcceptLinked) LZ4HIP_FRAMING_TRY(lz4f_linked_decode_run(be, linked));
+    if (flags & kLz4fAcceptLinked) LZ4HIP_FRAMING_TRY(lz4f_linked_decode_run(be, linked, dict));
     return 0;
 }
 
@@ -1817,16 +1851,16 @@ struct Lz4fDecodePlan {
 // read on the host between the steps.  The decoders are handed the table's dec_len column through the round's sanitised copy: a raw
 // row and a row with a bad checksum arrive as empty blocks, and so does every row of a frame with linked blocks, which a caller who
 // accepts them (kLz4fAcceptLinked) gets sized before the rounds and decoded after them.  The frame is the batch of one item, whose
-// lowest bad row is the state block's lowest failed index.
-template <class B>
-int lz4f_decode_run(B& be, const Lz4fDecodePlan& p)
+// lowest bad row is the state block's lowest failed index.  `dict`: as lz4f_rows_run's.
+template <class B, class D = Lz4fNoDict>
+int lz4f_decode_run(B& be, const Lz4fDecodePlan& p, const D& dict = D())
 {
     const Lz4fTables& t = p.t;
     unsigned long long* const bad = (unsigned long long*)(p.rounds.l.state + kPackedBad);
     LZ4HIP_FRAMING_TRY(lz4f_tables_init(be, t));
-    be.launch(lz4f_walk_kernel, fixed_grid(1), 64, p.src, p.src_len, p.slot_bytes, p.flags, t);
+    be.launch(lz4f_walk_kernel, fixed_grid(1), 64, p.src, p.src_len, p.slot_bytes, lz4f_walk_flags(p.flags, dict), t, lz4f_walk_dict_id(dict));
     LZ4HIP_FRAMING_TRY(be.last_error());
-    LZ4HIP_FRAMING_TRY(lz4f_rows_run(be, p.rounds, t, p.flags, 1, nullptr, nullptr, bad));
+    LZ4HIP_FRAMING_TRY(lz4f_rows_run(be, p.rounds, t, p.flags, 1, nullptr, nullptr, bad, dict));
     be.launch(lz4f_info_kernel, fixed_grid(1), 64, t, (const unsigned long long*)bad, p.flags, p.rounds.dst_cap, p.info);
     if (p.flags & kLz4fVerifyContent) {
         const XxhRows content = { p.rounds.dst, nullptr, 0, nullptr, t.walk + kLz4fWalkContentLen, 0, 0u, t.sums + t.max_blocks, 1 };
@@ -1855,13 +1889,29 @@ int lz4f_decode_plan(B& be, const void* src, int64_t src_len, int32_t slot_bytes
     return 0;
 }
 
-template <class B>
+template <class B, class D = Lz4fNoDict>
 int lz4f_decode(B& be, const void* src, int64_t src_len, int32_t slot_bytes, int64_t max_blocks, int64_t round_blocks, unsigned flags, void* scratch,
-                int64_t scratch_bytes, void* dst, int64_t dst_cap, lz4hip_lz4f_info_t* info)
+                int64_t scratch_bytes, void* dst, int64_t dst_cap, lz4hip_lz4f_info_t* info, const D& dict = D())
 {
     Lz4fDecodePlan p;
     LZ4HIP_FRAMING_TRY(lz4f_decode_plan(be, src, src_len, slot_bytes, max_blocks, round_blocks, flags, scratch, scratch_bytes, dst, dst_cap, info, p));
-    return lz4f_decode_run(be, p);
+    return lz4f_decode_run(be, p, dict);
+}
+
+// lz4hip_lz4f_decode_dict_device: the plain call's checks and plan behind the dictionary's own check; without a dictionary (dict_len
+// == 0) the plain sequence, which refuses a frame with a dictionary ID as ever
+template <class B>
+int lz4f_decode_dict_plan(B& be, const void* src, int64_t src_len, const void* dict, int64_t dict_len, int32_t slot_bytes, int64_t max_blocks,
+                          int64_t round_blocks, unsigned flags, void* scratch, int64_t scratch_bytes, void* dst, int64_t dst_cap, lz4hip_lz4f_info_t* info,
+                          Lz4fDecodePlan& p)
+{
+    LZ4HIP_FRAMING_TRY(lz4f_dict_check(be, dict, dict_len));
+    return lz4f_decode_plan(be, src, src_len, slot_bytes, max_blocks, round_blocks, flags, scratch, scratch_bytes, dst, dst_cap, info, p);
+}
+template <class B>
+int lz4f_decode_dict_run(B& be, const Lz4fDecodePlan& p, const void* dict, int64_t dict_len, uint32_t dict_id)
+{
+    return dict_len > 0 ? lz4f_decode_run(be, p, lz4f_dict_of(dict, dict_len, dict_id)) : lz4f_decode_run(be, p);
 }
 
 // ---- batches of LZ4 frames (lz4hip_lz4f_batch.hpp) --------------------------------------------------------------------------------------
@@ -2033,11 +2083,12 @@ struct Lz4fBatchDecodePlan {
 
 // The two walks around their scan, then what both decodes of LZ4 frames share (lz4f_rows_run: the block checksums and the rounds over ALL
 // max_blocks rows of the table, a linked item's rows sized before them and decoded after them), the items' records, their content
-// checksums as n rows of one launch, the batch's record.  Nothing is read on the host between the steps.
-template <class B>
-int lz4f_batch_decode_run(B& be, const Lz4fBatchDecodePlan& p)
+// checksums as n rows of one launch, the batch's record.  Nothing is read on the host between the steps.  `dict`: as lz4f_rows_run's.
+template <class B, class D = Lz4fNoDict>
+int lz4f_batch_decode_run(B& be, const Lz4fBatchDecodePlan& p, const D& dict = D())
 {
-    const Lz4fBatchDecodeArgs& a = p.a;
+    Lz4fBatchDecodeArgs a = p.a;
+    a.flags = lz4f_walk_flags(p.a.flags, dict); a.dict_id = lz4f_walk_dict_id(dict);
     const Lz4fBatchTables& t = p.t;
     LZ4HIP_FRAMING_TRY(be.fill(a.written_items, 0, sizeof(int64_t)));
     if (a.n == 0) {
@@ -2053,7 +2104,7 @@ int lz4f_batch_decode_run(B& be, const Lz4fBatchDecodePlan& p)
     launch_scan(be, t.base, a.n, p.partial, t.total);
     be.launch(lz4f_batch_walk_kernel<true>, walk_grid(a.n), 64, a, t);
     LZ4HIP_FRAMING_TRY(be.last_error());
-    LZ4HIP_FRAMING_TRY(lz4f_rows_run(be, p.rounds, t.rows, a.flags, a.n, t.base, t.total, t.item_bad));
+    LZ4HIP_FRAMING_TRY(lz4f_rows_run(be, p.rounds, t.rows, a.flags, a.n, t.base, t.total, t.item_bad, dict));
     be.launch(lz4f_batch_offsets_out_kernel, stream_grid(a.n + 1), kStreamThreads, a, t);
     be.launch(lz4f_batch_info_kernel, stream_grid(a.n), kStreamThreads, a, t);
     if (a.flags & kLz4fVerifyContent) {
@@ -2083,21 +2134,37 @@ int lz4f_batch_decode_plan(B& be, const void* src, int64_t src_len, const int64_
     Lz4fBatchDecodeArgs& a = p.a;
     // (an empty source's rows are all empty: any address will do for them)
     a.src = src ? (const uint8_t*)src : (const uint8_t*)scratch; a.off = src_off; a.src_len = src_len; a.n = n; a.slot_bytes = slot; a.flags = flags;
-    a.dst_cap = dst_cap; a.dst_off = dst_off; a.item_info = (Lz4fInfo*)item_info; a.written_items = written_items;
+    a.dst_cap = dst_cap; a.dst_off = dst_off; a.item_info = (Lz4fInfo*)item_info; a.written_items = written_items; a.dict_id = 0;
     p.t = d.t; p.partial = d.partial; p.rounds = lz4f_rounds_plan(a.src, d.t.rows, d.l, slot, round_blocks, (uint8_t*)dst, dst_cap);
     p.info = (Lz4fBatchInfo*)info;
     return 0;
 }
 
-template <class B>
+template <class B, class D = Lz4fNoDict>
 int lz4f_batch_decode(B& be, const void* src, int64_t src_len, const int64_t* src_off, int64_t n, int32_t slot_bytes, int64_t max_blocks, int64_t round_blocks,
                       unsigned flags, void* scratch, int64_t scratch_bytes, void* dst, int64_t dst_cap, int64_t* dst_off, lz4hip_lz4f_info_t* item_info,
-                      lz4hip_lz4f_batch_info_t* info, int64_t* written_items)
+                      lz4hip_lz4f_batch_info_t* info, int64_t* written_items, const D& dict = D())
 {
     Lz4fBatchDecodePlan p;
     LZ4HIP_FRAMING_TRY(lz4f_batch_decode_plan(be, src, src_len, src_off, n, slot_bytes, max_blocks, round_blocks, flags, scratch, scratch_bytes, dst, dst_cap,
                                               dst_off, item_info, info, written_items, p));
-    return lz4f_batch_decode_run(be, p);
+    return lz4f_batch_decode_run(be, p, dict);
+}
+
+// lz4hip_lz4f_batch_decode_dict_device, as lz4f_decode_dict_plan / lz4f_decode_dict_run are the one-frame call's
+template <class B>
+int lz4f_batch_decode_dict_plan(B& be, const void* src, int64_t src_len, const int64_t* src_off, int64_t n, const void* dict, int64_t dict_len, int32_t slot_bytes,
+                                int64_t max_blocks, int64_t round_blocks, unsigned flags, void* scratch, int64_t scratch_bytes, void* dst, int64_t dst_cap,
+                                int64_t* dst_off, lz4hip_lz4f_info_t* item_info, lz4hip_lz4f_batch_info_t* info, int64_t* written_items, Lz4fBatchDecodePlan& p)
+{
+    LZ4HIP_FRAMING_TRY(lz4f_dict_check(be, dict, dict_len));
+    return lz4f_batch_decode_plan(be, src, src_len, src_off, n, slot_bytes, max_blocks, round_blocks, flags, scratch, scratch_bytes, dst, dst_cap, dst_off,
+                                  item_info, info, written_items, p);
+}
+template <class B>
+int lz4f_batch_decode_dict_run(B& be, const Lz4fBatchDecodePlan& p, const void* dict, int64_t dict_len, uint32_t dict_id)
+{
+    return dict_len > 0 ? lz4f_batch_decode_run(be, p, lz4f_dict_of(dict, dict_len, dict_id)) : lz4f_batch_decode_run(be, p);
 }
 
 
@@ -2444,9 +2511,10 @@ int lz4f_encode_host(B& be, const void* src, int64_t src_len, int block_size_id,
 
 // The descriptor lies in host memory here: the block maximum sizes the slot, the content size (or four times the frame) the output's
 // piece of the image and the table.  A table that was too small or an output that has to grow is decoded again with what the record
-// reported, three passes at most.  On dst_cap < decoded_bytes only *info is filled (a size query: dst_cap = 0).
-template <class B>
-int lz4f_decode_host(B& be, const void* src, int64_t src_len, unsigned flags, void* dst, int64_t dst_cap, lz4hip_lz4f_info_t* info)
+// reported, three passes at most.  On dst_cap < decoded_bytes only *info is filled (a size query: dst_cap = 0).  `dict`: Lz4fNoDict,
+// or the call's dictionary ALREADY in device memory, in staging that is not the image's (lz4f_dict_stage).
+template <class B, class D = Lz4fNoDict>
+int lz4f_decode_host(B& be, const void* src, int64_t src_len, unsigned flags, void* dst, int64_t dst_cap, lz4hip_lz4f_info_t* info, const D& dict = D())
 {
     if (src_len < 0 || dst_cap < 0 || !info || (src_len > 0 && !src)) return be.fail(LZ4HIP_E_ARGUMENT, "lz4f decode: negative size or NULL pointer");
     if (flags & ~kLz4fDecodeFlags) return be.fail(LZ4HIP_E_ARGUMENT, "lz4f decode: unknown flag");
@@ -2471,7 +2539,7 @@ int lz4f_decode_host(B& be, const void* src, int64_t src_len, unsigned flags, vo
         LZ4HIP_FRAMING_TRY(im.reserve(c.at));
         LZ4HIP_FRAMING_TRY(im.upload_source(src, src_len));
         LZ4HIP_FRAMING_TRY(lz4f_decode(be, im.d, src_len, slot, max_blocks, 0, flags, im.d + scratch_at, scratch_bytes, im.d + out_at, out_bytes,
-                                       (lz4hip_lz4f_info_t*)(im.d + info_at)));
+                                       (lz4hip_lz4f_info_t*)(im.d + info_at), dict));
         LZ4HIP_FRAMING_TRY(im.download(&h, info_at, sizeof h));
         LZ4HIP_FRAMING_TRY(be.sync());
         if (attempt >= 2) break;
@@ -2487,6 +2555,33 @@ int lz4f_decode_host(B& be, const void* src, int64_t src_len, unsigned flags, vo
     if (h.decoded_bytes > 0) LZ4HIP_FRAMING_TRY(im.download(dst, out_at, h.decoded_bytes));
     LZ4HIP_FRAMING_TRY(be.sync());
     return info->error;
+}
+
+// The dictionary of a host-pointer dictionary call: the bytes a match can reach -- its last min(dict_len, 65 535) -- go up ONCE per call,
+// before the first pass, into staging of the backend's that is the dictionary's alone (be.dict_upload, which has landed when it returns:
+// hostbatch::upload_dictionary's contract).  The image of a later pass may grow and move; the dictionary stays where it is.
+template <class B>
+int lz4f_dict_stage(B& be, const void* dict, int64_t dict_len, uint32_t dict_id, Lz4fDict& d)
+{
+    const int64_t reach = dict_len < kLz4fLinkedHistory ? dict_len : kLz4fLinkedHistory;
+    uint8_t* dev = nullptr;
+    LZ4HIP_FRAMING_TRY(be.dict_upload((const uint8_t*)dict + (dict_len - reach), reach, dev));
+    d = lz4f_dict_of(dev, reach, dict_id);
+    return 0;
+}
+
+// lz4hip_lz4f_decode_dict_host; the dictionary's check comes first (the API repeats it before it looks for a device)
+template <class B>
+int lz4f_decode_dict_host(B& be, const void* src, int64_t src_len, const void* dict, int64_t dict_len, uint32_t dict_id, unsigned flags, void* dst,
+                          int64_t dst_cap, lz4hip_lz4f_info_t* info)
+{
+    LZ4HIP_FRAMING_TRY(lz4f_dict_check(be, dict, dict_len));
+    if (dict_len == 0) return lz4f_decode_host(be, src, src_len, flags, dst, dst_cap, info);
+    if (src_len < 0 || dst_cap < 0 || !info || (src_len > 0 && !src)) return be.fail(LZ4HIP_E_ARGUMENT, "lz4f decode: negative size or NULL pointer");
+    if (flags & ~kLz4fDecodeFlags) return be.fail(LZ4HIP_E_ARGUMENT, "lz4f decode: unknown flag");
+    Lz4fDict d;
+    LZ4HIP_FRAMING_TRY(lz4f_dict_stage(be, dict, dict_len, dict_id, d));
+    return lz4f_decode_host(be, src, src_len, flags, dst, dst_cap, info, d);
 }
 
 // A batch of frames staged the way streams_encode_host stages a batch of streams; the offsets are host memory here, so bad ones are
@@ -2523,10 +2618,11 @@ int lz4f_batch_encode_host(B& be, const void* src, int64_t src_len, const int64_
 // The descriptors lie in host memory here: the largest block maximum among them sizes the slots.  The table and the output's piece of
 // the image start as guesses; a table that was too small or an output that has to grow is decoded again with what the record reported,
 // three passes at most.  The rounds are bounded (a ring of 256 MiB, at least 64 slots), so the image does not grow with the table.
-// On dst_cap < decoded_bytes the offsets and the items' records are the caller's with the info (a size query: dst_cap = 0).
-template <class B>
+// On dst_cap < decoded_bytes the offsets and the items' records are the caller's with the info (a size query: dst_cap = 0).  `dict`: as
+// lz4f_decode_host's.
+template <class B, class D = Lz4fNoDict>
 int lz4f_batch_decode_host(B& be, const void* src, int64_t src_len, const int64_t* src_off, int64_t n, unsigned flags, void* dst, int64_t dst_cap,
-                           int64_t* dst_off, lz4hip_lz4f_info_t* item_info, lz4hip_lz4f_batch_info_t* info)
+                           int64_t* dst_off, lz4hip_lz4f_info_t* item_info, lz4hip_lz4f_batch_info_t* info, const D& dict = D())
 {
     if (src_len < 0 || n < 0 || dst_cap < 0 || !dst_off || !info || (n > 0 && (!src_off || !item_info)) || (src_len > 0 && n > 0 && !src))
         return be.fail(LZ4HIP_E_ARGUMENT, "lz4f batch decode: negative size or NULL pointer");
@@ -2559,7 +2655,7 @@ int lz4f_batch_decode_host(B& be, const void* src, int64_t src_len, const int64_
         LZ4HIP_FRAMING_TRY(im.upload_source(src, src_len, src_off, n, off_at));
         LZ4HIP_FRAMING_TRY(lz4f_batch_decode(be, im.d, src_len, im.i64(off_at), n, slot, max_blocks, round_blocks, flags, im.d + scratch_at, scratch_bytes,
                                              im.d + out_at, out_bytes, im.i64(doff_at), (lz4hip_lz4f_info_t*)(im.d + rec_at),
-                                             (lz4hip_lz4f_batch_info_t*)(im.d + info_at), im.i64(written_at)));
+                                             (lz4hip_lz4f_batch_info_t*)(im.d + info_at), im.i64(written_at), dict));
         LZ4HIP_FRAMING_TRY(im.download(&h, info_at, sizeof h));
         LZ4HIP_FRAMING_TRY(be.sync());
         if (attempt >= 2) break;
@@ -2579,6 +2675,25 @@ int lz4f_batch_decode_host(B& be, const void* src, int64_t src_len, const int64_
     if (h.decoded_bytes > 0) LZ4HIP_FRAMING_TRY(im.download(dst, out_at, h.decoded_bytes));
     LZ4HIP_FRAMING_TRY(be.sync());
     return info->error;
+}
+
+// lz4hip_lz4f_batch_decode_dict_host: the front checks that come before the staging are repeated here, so that a call that is refused
+// uploads nothing
+template <class B>
+int lz4f_batch_decode_dict_host(B& be, const void* src, int64_t src_len, const int64_t* src_off, int64_t n, const void* dict, int64_t dict_len, uint32_t dict_id,
+                                unsigned flags, void* dst, int64_t dst_cap, int64_t* dst_off, lz4hip_lz4f_info_t* item_info, lz4hip_lz4f_batch_info_t* info)
+{
+    LZ4HIP_FRAMING_TRY(lz4f_dict_check(be, dict, dict_len));
+    if (dict_len == 0 || n <= 0) return lz4f_batch_decode_host(be, src, src_len, src_off, n, flags, dst, dst_cap, dst_off, item_info, info);
+    if (src_len < 0 || dst_cap < 0 || !dst_off || !info || !src_off || !item_info || (src_len > 0 && !src))
+        return be.fail(LZ4HIP_E_ARGUMENT, "lz4f batch decode: negative size or NULL pointer");
+    if (flags & ~kLz4fDecodeFlags) return be.fail(LZ4HIP_E_ARGUMENT, "lz4f batch decode: unknown flag");
+    for (int64_t i = 0; i < n; i++)
+        if (src_off[i] < 0 || src_off[i + 1] < src_off[i] || src_off[i + 1] > src_len)
+            return be.fail(LZ4HIP_E_ARGUMENT, "lz4f batch decode: offsets decrease or fall outside [0, src_len]");
+    Lz4fDict d;
+    LZ4HIP_FRAMING_TRY(lz4f_dict_stage(be, dict, dict_len, dict_id, d));
+    return lz4f_batch_decode_host(be, src, src_len, src_off, n, flags, dst, dst_cap, dst_off, item_info, info, d);
 }
 
 #undef LZ4HIP_FRAMING_TRY

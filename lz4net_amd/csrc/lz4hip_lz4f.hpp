@@ -25,10 +25,12 @@
 // The decode is the batch of frames' (lz4hip_lz4f_batch.hpp) with one item: from the block checksums' verdict to the item's record,
 // everything but the walk is written here once for both, over one Lz4fTables whose rows name their item (or none: one item).
 //
-// The encoder's blocks are always independent (FLG.5) and use no dictionary; the decoder refuses dictionaries, and linked blocks unless
-// the caller accepts them (kLz4fAcceptLinked): each decodes only against the 64 KiB before it, in order, so a linked frame is one
-// serial chain -- lz4hip_lz4f_linked.hpp runs it on one wavefront, after the rounds, which see its rows as holes.  Every kernel here
-// is launch-only work on the caller's stream over caller scratch.
+// The encoder's blocks are always independent (FLG.5) and use no dictionary; the decoder refuses linked blocks unless the caller accepts
+// them (kLz4fAcceptLinked): each decodes only against the 64 KiB before it, in order, so a linked frame is one serial chain --
+// lz4hip_lz4f_linked.hpp runs it on one wavefront, after the rounds, which see its rows as holes.  A frame with a dictionary ID is
+// refused by the plain calls; the dictionary calls (lz4hip_lz4f_*_dict_*) hand the walk kLz4fWithDict and the ID they expect, the rounds
+// the dictionary decode (decode_dict_kernel) and the linked decode its dictionary form.  Every kernel here is launch-only work on the
+// caller's stream over caller scratch.
 #pragma once
 #include "lz4hip_packed.hpp"
 
@@ -333,9 +335,10 @@ __global__ void __launch_bounds__(kStreamThreads) lz4f_pack_kernel(Lz4fLayout L,
 // ---- decode ---------------------------------------------------------------------------------------------------------------------
 constexpr int kLz4fOk = 0, kLz4fBadMagic = 1, kLz4fBadHeader = 2, kLz4fHeaderChecksum = 3, kLz4fUnsupportedLinked = 4, kLz4fUnsupportedDict = 5,
               kLz4fSlotTooSmall = 6, kLz4fTruncated = 7, kLz4fBadBlockSize = 8, kLz4fCorruptBlock = 9, kLz4fBlockChecksumError = 10,
-              kLz4fContentSizeError = 11, kLz4fContentChecksumError = 12, kLz4fTableFull = 13;
+              kLz4fContentSizeError = 11, kLz4fContentChecksumError = 12, kLz4fTableFull = 13, kLz4fDictIdMismatch = 14;
 constexpr unsigned kLz4fVerifyBlocks = 1, kLz4fVerifyContent = 2;       // LZ4HIP_LZ4F_VERIFY_* (include/lz4hip.h)
 constexpr unsigned kLz4fAcceptLinked = 8;                               // LZ4HIP_LZ4F_ACCEPT_LINKED
+constexpr unsigned kLz4fWithDict = 0x100;                               // internal: the call has a dictionary (no public call lets the bit through)
 constexpr int kLz4fKindFrame = 0, kLz4fKindSkippable = 1;
 constexpr int kLz4fCheckAbsent = 0, kLz4fCheckVerified = 1, kLz4fCheckSkipped = 2;   // info.checks: bits 0-1 the blocks', bits 2-3 the content's
 constexpr uint8_t kLz4fRowRaw = 1, kLz4fRowBadSum = 2;
@@ -389,10 +392,11 @@ LZ4HIP_DEVICE int32_t lz4f_row_dec_len(uint8_t bits, int32_t size) { return bits
 // (lz4hip_lz4f_batch.hpp) are this walk with their own rows.  The descriptor's checks come in
 // the order a sequential reader applies them: version, reserved bits and block size id; the descriptor's length against the frame's;
 // HC; then what this decoder does not take (a dictionary ID, linked blocks unless `flags` has kLz4fAcceptLinked, a block maximum above
-// the caller's slot).  With a descriptor error no block is walked.  Per size field: the EndMark (and the content checksum behind it),
+// the caller's slot).  With kLz4fWithDict a dictionary ID is taken, and compared in the same place: a frame whose ID is not `dict_id`
+// (0: any) is kLz4fDictIdMismatch at the ID field.  With a descriptor error no block is walked.  Per size field: the EndMark (and the content checksum behind it),
 // the size against the frame's block maximum, then the data and its checksum against the end of the frame.
 template <class Row>
-LZ4HIP_DEVICE Lz4fWalk lz4f_walk_frame(const uint8_t* src, int64_t src_len, int32_t slot_bytes, unsigned flags, Row row)
+LZ4HIP_DEVICE Lz4fWalk lz4f_walk_frame(const uint8_t* src, int64_t src_len, int32_t slot_bytes, unsigned flags, Row row, uint32_t dict_id = 0)
 {
     int64_t pos = 0, blocks = 0, err_off = -1, content_size = -1, trailer = -1;
     int err = kLz4fOk, kind = kLz4fKindFrame, flg = 0, bd = 0;
@@ -417,7 +421,8 @@ LZ4HIP_DEVICE Lz4fWalk lz4f_walk_frame(const uint8_t* src, int64_t src_len, int3
         else {
             block_max = lz4f_block_bytes(id);
             if (flg & 0x08) content_size = (int64_t)wv::uniform(load_u64(src + 6));
-            if (flg & 0x01) { err = kLz4fUnsupportedDict; err_off = 4; }
+            if ((flg & 0x01) && !(flags & kLz4fWithDict)) { err = kLz4fUnsupportedDict; err_off = 4; }
+            else if ((flg & 0x01) && dict_id != 0 && wv::uniform(load_u32(src + 4 + dlen - 5)) != dict_id) { err = kLz4fDictIdMismatch; err_off = 4 + dlen - 5; }
             else if (!(flg & 0x20) && !(flags & kLz4fAcceptLinked)) { err = kLz4fUnsupportedLinked; err_off = 4; }
             else if (block_max > slot_bytes) { err = kLz4fSlotTooSmall; err_off = 5; }
             pos = 4 + dlen;
@@ -459,7 +464,7 @@ LZ4HIP_DEVICE void lz4f_walk_store(int64_t* w, const Lz4fWalk& r, int64_t full_o
 
 // One wavefront; every lane runs the same walk on the same (wave-uniform) position and lane 0 writes: row k of the table for block k
 // while the table has rows, the record at the end.
-__global__ void __launch_bounds__(64) lz4f_walk_kernel(const uint8_t* src, int64_t src_len, int32_t slot_bytes, unsigned flags, Lz4fTables t)
+__global__ void __launch_bounds__(64) lz4f_walk_kernel(const uint8_t* src, int64_t src_len, int32_t slot_bytes, unsigned flags, Lz4fTables t, uint32_t dict_id)
 {
     const int lane = wv::lane();
     int64_t full_off = -1;
@@ -473,7 +478,7 @@ __global__ void __launch_bounds__(64) lz4f_walk_kernel(const uint8_t* src, int64
         } else if (k == t.max_blocks) {
             full_off = pos;
         }
-    });
+    }, dict_id);
     if (lane == 0) lz4f_walk_store(t.walk, r, full_off);
 }
 

@@ -303,6 +303,7 @@ struct Lz4fBatchDecodeArgs {
     int64_t* dst_off;                                                  // n + 1
     Lz4fInfo* item_info;                                               // n
     int64_t* written_items;
+    uint32_t dict_id;                                                  // with kLz4fWithDict in flags: the ID a frame's must equal (0: any)
 };
 
 LZ4HIP_DEVICE bool lz4f_batch_full(const Lz4fBatchTables& t) { return t.total[0] > t.rows.max_blocks; }
@@ -328,7 +329,7 @@ __global__ void __launch_bounds__(64) lz4f_batch_walk_kernel(Lz4fBatchDecodeArgs
                     t.rows.dec_len[j] = lz4f_row_dec_len(bits, size); t.rows.sum_len[j] = sum_bytes ? size : 0;
                     t.rows.row[j] = bits; t.rows.item[j] = (int32_t)i;
                 }
-            });
+            }, a.dict_id);
         } else {
             r.pos = r.blocks = 0; r.err_off = r.content_size = r.trailer = -1;
             r.err = kLz4fBatchBadOffsets; r.kind = kLz4fKindFrame; r.flg = r.bd = 0; r.block_max = 0;

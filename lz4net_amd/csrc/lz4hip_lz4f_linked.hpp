@@ -21,6 +21,9 @@
 //
 // A linked frame is a serial chain on ONE wavefront: a lone large frame decodes far slower than on a host core (INTEGRATION.md 4 has a
 // lone wavefront's figures).  This path pays only in batches of many items.
+//
+// The dictionary calls (lz4hip_lz4f_*_dict_*) run the same three kernels, the last in its dictionary form: the size walk already allows
+// every row 65 535 bytes in front of it, so the plan is the same, and the decoder is where a source before the dictionary is refused.
 #pragma once
 #include "lz4hip_decode.hpp"
 #include "lz4hip_sizes.hpp"
@@ -97,11 +100,13 @@ __global__ void __launch_bounds__(kStreamThreads) lz4f_linked_plan_kernel(Lz4fLi
 // mem_sync between rows: the next row reads what this one stored, through global memory.  Rows that do not lie wholly inside dst_cap
 // end the item (the clip of a linked item is at a block boundary), and so does a row the decoder refuses, which becomes the item's
 // lowest bad row.  Nothing is written outside the planned bytes of the item's rows, and nothing at or past dst_cap.
-__global__ void __launch_bounds__(64 * kWaveDecodeWavesPerGroup) lz4f_linked_decode_kernel(Lz4fLinked a)
+// DICT (the dictionary calls, lz4hip_lz4f_*_dict_*): the call's dictionary, whose dict_len <= 65 535 bytes end at dict_end, counts as
+// lying in front of EVERY item's first byte.  A row with `history` bytes of its item in front of it reaches the dictionary's last
+// min(dict_len, 65 535 - history) bytes behind them: a source before those is what a source before the frame is without a dictionary.
+// The plain form is the instantiation without it, whose code does not know the two arguments.
+template <bool DICT>
+LZ4HIP_DEVICE void lz4f_linked_decode_items(const Lz4fLinked& a, unsigned char* const ring, const uint8_t* dict_end, int32_t dict_len)
 {
-    LZ4HIP_STATIC_LDS(rings, kWaveDecodeWavesPerGroup * kWaveLdsBytes);
-    unsigned char* const ring = rings + wv::wave_in_block() * kWaveLdsBytes;
-    if (lz4f_linked_full(a)) return;
     const int64_t waves = (int64_t)gridDim.x * kWaveDecodeWavesPerGroup;
     for (int64_t i = (int64_t)blockIdx.x * kWaveDecodeWavesPerGroup + wv::wave_in_block(); i < a.n; i += waves) {
         int64_t first, count;
@@ -120,7 +125,8 @@ __global__ void __launch_bounds__(64 * kWaveDecodeWavesPerGroup) lz4f_linked_dec
             } else {
                 const int64_t before = at - begin;
                 const int history = before < kLz4fLinkedHistory ? (int)before : kLz4fLinkedHistory;
-                const int r = decode_block<false, true>(in, stored, a.dst + at, size, ring, history);
+                const int dict_reach = dict_len < kLz4fLinkedHistory - history ? dict_len : kLz4fLinkedHistory - history;
+                const int r = decode_block<false, true, DICT>(in, stored, a.dst + at, size, ring, history, dict_end, dict_reach);
                 if (r != size) {
                     if (wv::lane() == 0) atomicMin(&a.item_bad[i], (unsigned long long)k);
                     break;
@@ -129,6 +135,22 @@ __global__ void __launch_bounds__(64 * kWaveDecodeWavesPerGroup) lz4f_linked_dec
             wv::mem_sync();
         }
     }
+}
+
+__global__ void __launch_bounds__(64 * kWaveDecodeWavesPerGroup) lz4f_linked_decode_kernel(Lz4fLinked a)
+{
+    LZ4HIP_STATIC_LDS(rings, kWaveDecodeWavesPerGroup * kWaveLdsBytes);
+    unsigned char* const ring = rings + wv::wave_in_block() * kWaveLdsBytes;
+    if (lz4f_linked_full(a)) return;
+    lz4f_linked_decode_items<false>(a, ring, nullptr, 0);
+}
+
+__global__ void __launch_bounds__(64 * kWaveDecodeWavesPerGroup) lz4f_linked_decode_dict_kernel(Lz4fLinked a, const uint8_t* dict_end, int32_t dict_len)
+{
+    LZ4HIP_STATIC_LDS(rings, kWaveDecodeWavesPerGroup * kWaveLdsBytes);
+    unsigned char* const ring = rings + wv::wave_in_block() * kWaveLdsBytes;
+    if (lz4f_linked_full(a)) return;
+    lz4f_linked_decode_items<true>(a, ring, dict_end, dict_len);
 }
 
 }  // namespace lz4hip

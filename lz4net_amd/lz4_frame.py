@@ -6,9 +6,10 @@ K4os.Compression.LZ4.Streams and python-lz4 write and read.
     LE32 0 (EndMark)   [LE32 xxh32(content) if FLG.2]
 
 The blocks are the block format the library encodes and decodes anyway; the framing, the xxHash32 checksums and the packing run on
-the device (lz4hip_lz4f_* of include/lz4hip.h).  Frames written here hold independent blocks and no dictionary; frames with a
-dictionary ID are refused with a clear message, not decoded wrongly, and so are frames with linked blocks (FLG.5 clear) unless the
-caller passes accept_linked=True.  Skippable frames (magic 0x184D2A50 .. 0x184D2A5F) are skipped, appended frames decoded one after
+the device (lz4hip_lz4f_* of include/lz4hip.h).  Frames written here hold independent blocks and no dictionary.  The decoders take
+dictionary=..., dict_id=... (LZ4F_decompress_usingDict: ONE dictionary per call, in front of every frame's first byte); without one,
+frames with a dictionary ID are refused with a clear message, not decoded wrongly, and so are frames with linked blocks (FLG.5 clear)
+unless the caller passes accept_linked=True.  Skippable frames (magic 0x184D2A50 .. 0x184D2A5F) are skipped, appended frames decoded one after
 the other.
 
 Many frames at once -- the buffers of an Arrow IPC stream, the record batches of a Kafka log, a service's pickled messages -- go
@@ -42,12 +43,15 @@ _TEXT = {
     _lib.LZ4F_CONTENT_SIZE_ERROR: "decoded size differs from the frame's content size",
     _lib.LZ4F_CONTENT_CHECKSUM_ERROR: "content checksum mismatch",
 }
+# ... and of a call with a dictionary, the only ones that know the outcome
+_DICT_TEXT = dict(_TEXT)
+_DICT_TEXT[_lib.LZ4F_DICT_ID_MISMATCH] = "the frame's dictionary ID is not the one the caller expects"
 
 
-def _frame_error(status: int, error_offset: int = -1):
+def _frame_error(status: int, error_offset: int = -1, texts=_TEXT):
     """The exception the decoders raise for an LZ4HIP_LZ4F_* outcome, with where it was met in .error_offset and the code in .status."""
     status = int(status)
-    e = ArgumentException(_TEXT[status]) if status in _TEXT else _lib.Lz4HipError(f"lz4 frame decode: unexpected outcome {status}")
+    e = ArgumentException(texts[status]) if status in texts else _lib.Lz4HipError(f"lz4 frame decode: unexpected outcome {status}")
     e.error_offset, e.status = int(error_offset), status
     return e
 
@@ -123,6 +127,33 @@ def _decode_flags(verify, accept_linked) -> int:
     return ((_lib.LZ4F_VERIFY_BLOCKS | _lib.LZ4F_VERIFY_CONTENT) if verify else 0) | (_lib.LZ4F_ACCEPT_LINKED if accept_linked else 0)
 
 
+def _device_dictionary(dictionary, like, dict_id):
+    """(pointer, length, ID, the tensor to keep alive) of a device call's dictionary: a 1-D uint8 CUDA tensor on the frames' device; None and
+    an empty one are no dictionary"""
+    if dictionary is None:
+        return 0, 0, 0, None
+    if not _p.is_device_vector(dictionary, "uint8"):
+        raise ArgumentException("the dictionary must be a 1-D uint8 CUDA tensor")
+    if dictionary.device != like.device:
+        raise ArgumentException("the dictionary must be on the frames' device")
+    d = dictionary.contiguous()
+    return (d.data_ptr() if d.numel() else 0), d.numel(), _dict_id(dict_id), d
+
+
+def _host_dictionary(dictionary, dict_id):
+    """(pointer, length, ID, the array to keep alive) of a host call's dictionary: bytes-like; None and an empty one are no dictionary"""
+    if dictionary is None:
+        return 0, 0, 0, None
+    d = _p.host_bytes(dictionary)
+    return (d.ctypes.data if d.size else 0), d.size, _dict_id(dict_id), d
+
+
+def _dict_id(dict_id) -> int:
+    if not 0 <= int(dict_id) <= 0xFFFFFFFF:
+        raise ArgumentException("dict_id must be 0 (no check) .. 2^32 - 1")
+    return int(dict_id)
+
+
 def compress_frame_device(t, block_size: int = 65536, high_compression: bool = False, block_checksum: bool = False,
                           content_checksum: bool = False, content_size: bool = True):
     """One LZ4 frame of a 1-D uint8 CUDA tensor, entirely on the device, on torch's current stream, returned as a 1-D uint8 CUDA tensor:
@@ -140,7 +171,7 @@ def compress_frame_device(t, block_size: int = 65536, high_compression: bool = F
         return out[:int(out_len.item())]
 
 
-def decompress_frame_device(t, verify: bool = True, round_blocks: int = 0, accept_linked: bool = False):
+def decompress_frame_device(t, verify: bool = True, round_blocks: int = 0, accept_linked: bool = False, dictionary=None, dict_id: int = 0):
     """The content of the LZ4 frames in a 1-D uint8 CUDA tensor -- appended frames one after the other, skippable frames skipped -- as a
     1-D uint8 CUDA tensor, decoded on the device on torch's current stream.  Per frame the host reads the first 19 bytes back (the block
     maximum sizes the decoder's slots, the content size the output and the table), calls lz4hip_lz4f_decode_device once and reads its
@@ -150,11 +181,14 @@ def decompress_frame_device(t, verify: bool = True, round_blocks: int = 0, accep
     device (DESIGN.md 7 records the measured single-row rate, or says that it has not been measured yet) -- so verify=False is worth it for large frames whose
     integrity is known.  round_blocks = K > 0 decodes K blocks at a time through a ring of K slots.  accept_linked=True decodes frames
     with linked blocks (LZ4HIP_LZ4F_ACCEPT_LINKED) instead of refusing them: such a frame is one serial chain on ONE wavefront, far
-    slower for one large frame than a host core -- it pays in decompress_frames_device, many frames at once.  Raises ArgumentException
-    with the outcome's text."""
+    slower for one large frame than a host core -- it pays in decompress_frames_device, many frames at once.  dictionary: a 1-D
+    uint8 CUDA tensor on t's device whose bytes count as lying in front of EVERY frame's first byte (lz4hip_lz4f_decode_dict_device,
+    LZ4F_decompress_usingDict); dict_id != 0 refuses a frame whose descriptor carries another ID.  None or empty: no dictionary, and a
+    frame with a dictionary ID is refused.  Raises ArgumentException with the outcome's text."""
     import torch
     t = _p.check_device_bytes(t, "t")
     flags = _decode_flags(verify, accept_linked)
+    dict_ptr, dict_len, dict_id, keep_dict = _device_dictionary(dictionary, t, dict_id)
     with _p.DeviceCall(t) as d:
         info_dev = d.record(_lib.Lz4fInfo)
         parts, pos, n = [], 0, t.numel()
@@ -177,8 +211,13 @@ def decompress_frame_device(t, verify: bool = True, round_blocks: int = 0, accep
                 max_blocks, out_bytes = guess
                 need = _lib.check(d.lib.lz4hip_lz4f_decode_scratch_bytes(head["block_max"], max_blocks, round_blocks))
                 scratch, out = d.u8(need), d.u8(out_bytes)
-                _lib.check(d.lib.lz4hip_lz4f_decode_device(t.data_ptr() + pos, rest, head["block_max"], max_blocks, round_blocks, flags,
-                                                           scratch.data_ptr(), need, out.data_ptr(), out_bytes, info_dev.data_ptr(), d.stream))
+                if dict_len:
+                    _lib.check(d.lib.lz4hip_lz4f_decode_dict_device(t.data_ptr() + pos, rest, dict_ptr, dict_len, dict_id, head["block_max"], max_blocks,
+                                                                    round_blocks, flags, scratch.data_ptr(), need, out.data_ptr(), out_bytes,
+                                                                    info_dev.data_ptr(), d.stream))
+                else:
+                    _lib.check(d.lib.lz4hip_lz4f_decode_device(t.data_ptr() + pos, rest, head["block_max"], max_blocks, round_blocks, flags,
+                                                               scratch.data_ptr(), need, out.data_ptr(), out_bytes, info_dev.data_ptr(), d.stream))
                 info = _p.read_record(info_dev, _lib.Lz4fInfo)
                 return (out, info), _p.table_or_output(info, "blocks", _lib.LZ4F_TABLE_FULL, guess)
 
@@ -189,7 +228,7 @@ def decompress_frame_device(t, verify: bool = True, round_blocks: int = 0, accep
             if info.error == _lib.LZ4F_TABLE_FULL or info.decoded_bytes > out_bytes:
                 raise _lib.Lz4HipError("lz4 frame decode: the size field walk did not settle")
             if info.error != _lib.LZ4F_OK:
-                raise _frame_error(info.error, pos + info.error_offset if info.error_offset >= 0 else -1)
+                raise _frame_error(info.error, pos + info.error_offset if info.error_offset >= 0 else -1, _DICT_TEXT if dict_len else _TEXT)
             parts.append(out[:int(info.decoded_bytes)])
             pos += int(info.frame_bytes)
         if not parts:                                                 # (skippable frames only)
@@ -211,12 +250,13 @@ def compress_frame_host(data, block_size: int = 65536, high_compression: bool = 
     return out[:out_len.value].tobytes()
 
 
-def decompress_frame_host(frame, verify: bool = True, accept_linked: bool = False) -> bytes:
+def decompress_frame_host(frame, verify: bool = True, accept_linked: bool = False, dictionary=None, dict_id: int = 0) -> bytes:
     """decompress_frame_device for host bytes, through lz4hip_lz4f_decode_host: per frame a size query (dst_cap = 0), then the call that
-    decodes into exactly that size.  Appended frames follow each other; skippable frames are skipped.  accept_linked as in
-    decompress_frame_device."""
+    decodes into exactly that size.  Appended frames follow each other; skippable frames are skipped.  accept_linked, dictionary
+    (bytes-like here, through lz4hip_lz4f_decode_dict_host) and dict_id as in decompress_frame_device."""
     buf = _p.host_bytes(frame)
     flags = _decode_flags(verify, accept_linked)
+    dict_ptr, dict_len, dict_id, keep_dict = _host_dictionary(dictionary, dict_id)
     L = _lib.lib()
     parts, pos = [], 0
     if buf.size == 0:
@@ -224,10 +264,13 @@ def decompress_frame_host(frame, verify: bool = True, accept_linked: bool = Fals
     while pos < buf.size:
         info = _lib.Lz4fInfo()
         at, rest = buf.ctypes.data + pos, buf.size - pos
-        out = _p.sized_decode_host(lambda dst, dst_cap: L.lz4hip_lz4f_decode_host(at, rest, flags, dst, dst_cap, C.byref(info)), info,
-                                   after_e_argument_only=True)
+        if dict_len:
+            call = lambda dst, dst_cap: L.lz4hip_lz4f_decode_dict_host(at, rest, dict_ptr, dict_len, dict_id, flags, dst, dst_cap, C.byref(info))
+        else:
+            call = lambda dst, dst_cap: L.lz4hip_lz4f_decode_host(at, rest, flags, dst, dst_cap, C.byref(info))
+        out = _p.sized_decode_host(call, info, after_e_argument_only=True)
         if info.error != _lib.LZ4F_OK:
-            raise _frame_error(info.error, pos + info.error_offset if info.error_offset >= 0 else -1)
+            raise _frame_error(info.error, pos + info.error_offset if info.error_offset >= 0 else -1, _DICT_TEXT if dict_len else _TEXT)
         parts.append(out.tobytes())
         pos += int(info.frame_bytes)
     return b"".join(parts)
@@ -250,14 +293,14 @@ def xxh32_rows_device(data, off, lens, seed: int = 0):
 
 # ---- batches of frames: one buffer, offsets[n + 1], one frame per item ---------------------------------------------------------------------
 
-def _item_error(batch):
+def _item_error(batch, texts=_TEXT):
     """the exception of the first failing item of a batch record (lz4hip_lz4f_batch_info_t), with the item's index in .item"""
     i = int(batch.first_error)
     if batch.error == _lib.E_ARGUMENT:
         e = ArgumentException(_p.BAD_OFFSETS)
         e.error_offset, e.status = -1, int(batch.error)
     else:
-        e = _frame_error(batch.error, batch.error_offset)
+        e = _frame_error(batch.error, batch.error_offset, texts)
     e.item = i
     return e
 
@@ -287,7 +330,7 @@ def compress_frames_device(t, offsets, block_size: int = 65536, high_compression
 
 
 def decompress_frames_device(t, offsets, slot_bytes: int = 65536, verify: bool = True, round_blocks: int = 0, max_blocks=None,
-                             accept_linked: bool = False):
+                             accept_linked: bool = False, dictionary=None, dict_id: int = 0):
     """[decompress_frame_device(item) for item in items] for items of ONE frame each, t[offsets[i]:offsets[i + 1]] of a 1-D uint8 CUDA
     tensor, in one call on the device, on torch's current stream -> (data, data_offsets).  Every item's size fields are walked by a
     wavefront of its own, the blocks of all items are one table of the block decoder, the content checksums n rows of one launch.
@@ -297,10 +340,12 @@ def decompress_frames_device(t, offsets, slot_bytes: int = 65536, verify: bool =
     item gives no bytes; what lies behind an item's frame is left alone.  round_blocks = K > 0 decodes K blocks at a time through a
     ring of K slots instead of one slot per table row.  accept_linked=True decodes items whose blocks are linked (the default of
     LZ4F_compressFrame, python-lz4 and Arrow's LZ4_FRAME codec above one block) instead of failing them: each such item is decoded in
-    order by ONE wavefront, so the flag pays in batches of many items.  Raises the first failing item's ArgumentException, its index in
-    .item."""
+    order by ONE wavefront, so the flag pays in batches of many items.  dictionary and dict_id as in decompress_frame_device: ONE
+    dictionary for all items (lz4hip_lz4f_batch_decode_dict_device); with it every compressed block decodes on the wavefront mapping.
+    Raises the first failing item's ArgumentException, its index in .item."""
     t, offsets = _p.check_device_batch(t, offsets)
     flags = _decode_flags(verify, accept_linked)
+    dict_ptr, dict_len, dict_id, keep_dict = _device_dictionary(dictionary, t, dict_id)
     if int(slot_bytes) not in BLOCK_SIZES:
         raise ArgumentException("slot_bytes must be 65536, 262144, 1048576 or 4194304")
     with _p.DeviceCall(t) as d:
@@ -312,9 +357,15 @@ def decompress_frames_device(t, offsets, slot_bytes: int = 65536, verify: bool =
             rows, out_bytes = guess
             need = _lib.check(d.lib.lz4hip_lz4f_batch_decode_scratch_bytes(n, slot_bytes, rows, round_blocks))
             scratch, out = d.u8(max(need, 1)), d.u8(out_bytes)
-            _lib.check(d.lib.lz4hip_lz4f_batch_decode_device(t.data_ptr(), t.numel(), offsets.data_ptr(), n, slot_bytes, rows, round_blocks, flags,
-                                                             scratch.data_ptr(), need, out.data_ptr(), out_bytes, out_off.data_ptr(),
-                                                             items_dev.data_ptr(), info_dev.data_ptr(), written.data_ptr(), d.stream))
+            if dict_len:
+                _lib.check(d.lib.lz4hip_lz4f_batch_decode_dict_device(t.data_ptr(), t.numel(), offsets.data_ptr(), n, dict_ptr, dict_len, dict_id, slot_bytes,
+                                                                      rows, round_blocks, flags, scratch.data_ptr(), need, out.data_ptr(), out_bytes,
+                                                                      out_off.data_ptr(), items_dev.data_ptr(), info_dev.data_ptr(), written.data_ptr(),
+                                                                      d.stream))
+            else:
+                _lib.check(d.lib.lz4hip_lz4f_batch_decode_device(t.data_ptr(), t.numel(), offsets.data_ptr(), n, slot_bytes, rows, round_blocks, flags,
+                                                                 scratch.data_ptr(), need, out.data_ptr(), out_bytes, out_off.data_ptr(),
+                                                                 items_dev.data_ptr(), info_dev.data_ptr(), written.data_ptr(), d.stream))
             info = _p.read_record(info_dev, _lib.Lz4fBatchInfo)
             return (out, info), _p.table_or_output(info, "blocks", _lib.LZ4F_TABLE_FULL, guess)
 
@@ -323,7 +374,7 @@ def decompress_frames_device(t, offsets, slot_bytes: int = 65536, verify: bool =
         if info.error == _lib.LZ4F_TABLE_FULL or info.decoded_bytes > out_bytes:
             raise _lib.Lz4HipError("lz4 frame batch decode: the size field walks did not settle")
         if info.first_error >= 0:
-            raise _item_error(info)
+            raise _item_error(info, _DICT_TEXT if dict_len else _TEXT)
         return out[:int(info.decoded_bytes)], out_off
 
 
@@ -344,22 +395,27 @@ def compress_frames_host(buf, offsets, block_size: int = 65536, high_compression
     return out[:int(out_off[n])], out_off
 
 
-def decompress_frames_host(packed, offsets, verify: bool = True, accept_linked: bool = False):
+def decompress_frames_host(packed, offsets, verify: bool = True, accept_linked: bool = False, dictionary=None, dict_id: int = 0):
     """decompress_frames_device for host arrays, through lz4hip_lz4f_batch_decode_host: a size query (dst_cap = 0), then the call that
     decodes into exactly that size -> (data, data_offsets) as numpy arrays.  The slots take the largest block maximum among the items'
-    descriptors.  accept_linked as in decompress_frames_device.  Raises the first failing item's ArgumentException, its index in .item."""
+    descriptors.  accept_linked, dictionary (bytes-like here) and dict_id as in decompress_frames_device.  Raises the first failing item's ArgumentException, its index in .item."""
     packed, offsets = _p.check_host_batch(packed, offsets)
     n = offsets.size - 1
     if n and ((np.diff(offsets) < 0).any() or offsets[0] < 0 or offsets[-1] > packed.size):
         raise ArgumentException(_p.BAD_OFFSETS)
     flags = _decode_flags(verify, accept_linked)
+    dict_ptr, dict_len, dict_id, keep_dict = _host_dictionary(dictionary, dict_id)
     L = _lib.lib()
     out_off = np.zeros(n + 1, np.int64)
     items = (_lib.Lz4fInfo * max(n, 1))()
     info = _lib.Lz4fBatchInfo()
-    out = _p.sized_decode_host(lambda dst, dst_cap: L.lz4hip_lz4f_batch_decode_host(
-        packed.ctypes.data, packed.size, offsets.ctypes.data, n, flags, dst, dst_cap, out_off.ctypes.data, items, C.byref(info)), info,
-        after_e_argument_only=True)
+    if dict_len:
+        call = lambda dst, dst_cap: L.lz4hip_lz4f_batch_decode_dict_host(
+            packed.ctypes.data, packed.size, offsets.ctypes.data, n, dict_ptr, dict_len, dict_id, flags, dst, dst_cap, out_off.ctypes.data, items, C.byref(info))
+    else:
+        call = lambda dst, dst_cap: L.lz4hip_lz4f_batch_decode_host(
+            packed.ctypes.data, packed.size, offsets.ctypes.data, n, flags, dst, dst_cap, out_off.ctypes.data, items, C.byref(info))
+    out = _p.sized_decode_host(call, info, after_e_argument_only=True)
     if info.first_error >= 0:
-        raise _item_error(info)
+        raise _item_error(info, _DICT_TEXT if dict_len else _TEXT)
     return out, out_off
