@@ -1,5 +1,6 @@
-// lz4f_batch_asan_main.cpp -- TEST INFRASTRUCTURE ONLY: a stand-alone program over the emulator translation unit of the batch of LZ4
-// frames (tests/simt/emu_lz4f_batch.cpp), for a sanitizer run of the kernels, the launch sequences and the fronts on the CPU:
+// lz4f_batch_asan_main.cpp -- TEST INFRASTRUCTURE ONLY: a stand-alone program over the framing emulator's translation unit, for the batch
+// of LZ4 frames (tests/simt/emu_framing.cpp, its part emu_lz4f_batch.inc): a sanitizer run of the kernels, the launch sequences and the
+// fronts on the CPU:
 //
 //     g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=undefined -pthread -Itests/simt -Ilz4net_amd/csrc \
 //         tests/cpp/lz4f_batch_asan_main.cpp -o lz4f_batch_asan && ./lz4f_batch_asan
@@ -7,17 +8,12 @@
 // It runs every outcome once in ONE batch (each fault as an item between good items) and 4 100 one-block items of 1 .. 40 bytes, every
 // buffer a heap block of exactly its size, at the library's grids and at grids forced to 1 and 3.  There is no block codec here: a
 // "compressed" block is len / 2 opaque bytes that the stand-in decoder answers with the source's bytes, which is all the framing sees of one.
-#include "../simt/emu_lz4f_batch.cpp"
-
-#include <cstdio>
-#include <cstdlib>
-#include <vector>
+#include "../simt/emu_framing.cpp"
+#include "built_frames.hpp"
 
 namespace {
 
-typedef std::vector<uint8_t> Bytes;
-
-#define CHECK(cond) do { if (!(cond)) { fprintf(stderr, "%s:%d: CHECK failed: %s\n", __FILE__, __LINE__, #cond); exit(1); } } while (0)
+using namespace built_frames;
 
 struct Batch { Bytes bytes; std::vector<int64_t> off; };
 
@@ -69,8 +65,6 @@ std::vector<Bytes> encode(const std::vector<Bytes>& items, unsigned flags, int g
 }
 
 struct Row { int32_t result, len; Bytes bytes; };                          // what the stand-in decoder holds for one table row
-
-struct Decoded { std::vector<lz4hip_lz4f_info_t> recs; lz4hip_lz4f_batch_info_t info; std::vector<int64_t> off; Bytes out; int64_t written; };
 
 Decoded decode(const std::vector<Bytes>& frames, const std::vector<Row>& rows, int64_t out_bytes, int64_t round_blocks, int grid)
 {

@@ -1,6 +1,6 @@
-// lz4f_dict_asan_main.cpp -- TEST INFRASTRUCTURE ONLY: a stand-alone program over the emulator translation unit of the decode of LZ4
-// frames with a dictionary (tests/simt/emu_lz4f_dict.cpp), for a sanitizer run of the kernels, the launch sequences and the fronts on
-// the CPU:
+// lz4f_dict_asan_main.cpp -- TEST INFRASTRUCTURE ONLY: a stand-alone program over the framing emulator's translation unit, for the
+// decode of LZ4 frames with a dictionary (tests/simt/emu_framing.cpp, its part emu_lz4f_dict.inc): a sanitizer run of the kernels, the
+// launch sequences and the fronts on the CPU:
 //
 //     g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=undefined -pthread -Itests/simt -Ilz4net_amd/csrc \
 //         tests/cpp/lz4f_dict_asan_main.cpp -o lz4f_dict_asan && ./lz4f_dict_asan
@@ -13,87 +13,13 @@
 // byte; 40 short sequences out of the dictionary and a long copy (the mirror's preload and the long path's two copies) -- with
 // dictionaries of 1, 13, 4 095, 4 097, 65 535 and 70 000 bytes, of which only the last 65 535 may be touched: the program hands the
 // kernels the WHOLE allocation but poisons nothing, so for 70 000 the check is the result.  Also the host calls, whose staging holds
-// exactly the reachable bytes.  The frames are built by hand here as tests/lz4f_dict_ref.py builds them.
-#include "../simt/emu_lz4f_dict.cpp"
-
-#include <cstdio>
-#include <cstdlib>
-#include <vector>
+// exactly the reachable bytes.  The frames are built by hand (built_frames.hpp) as tests/lz4f_dict_ref.py builds them.
+#include "../simt/emu_framing.cpp"
+#include "built_frames.hpp"
 
 namespace {
 
-typedef std::vector<uint8_t> Bytes;
-
-#define CHECK(cond) do { if (!(cond)) { fprintf(stderr, "%s:%d: CHECK failed: %s\n", __FILE__, __LINE__, #cond); exit(1); } } while (0)
-
-Bytes noise(size_t n, uint32_t seed)
-{
-    Bytes b(n);
-    uint32_t x = seed * 2654435761u + 1u;
-    for (size_t i = 0; i < n; i++) { x = x * 1664525u + 1013904223u; b[i] = (uint8_t)(x >> 24); }
-    return b;
-}
-
-void put32(Bytes& b, uint32_t v) { for (int k = 0; k < 4; k++) b.push_back((uint8_t)(v >> (8 * k))); }
-void append(Bytes& b, const Bytes& a) { b.insert(b.end(), a.begin(), a.end()); }
-void put_length(Bytes& b, size_t n) { for (; n >= 255; n -= 255) b.push_back(255); b.push_back((uint8_t)n); }
-
-// token, literal length bytes, literals [, offset, match length bytes]; match == 0: a block's last sequence
-void sequence(Bytes& b, const Bytes& literals, unsigned offset, size_t match)
-{
-    const size_t ll = literals.size(), ml = match ? match - 4 : 0;
-    b.push_back((uint8_t)((ll < 15 ? ll : 15) << 4 | (ml < 15 ? ml : 15)));
-    if (ll >= 15) put_length(b, ll - 15);
-    append(b, literals);
-    if (match) {
-        b.push_back((uint8_t)offset); b.push_back((uint8_t)(offset >> 8));
-        if (ml >= 15) put_length(b, ml - 15);
-    }
-}
-
-struct Block { Bytes data; bool raw; };
-struct Part { Bytes literals; unsigned offset; size_t match; };
-
-// the frame under construction and the bytes it decodes to: a block may copy from the dictionary and, in a linked frame, from the
-// frame's bytes so far
-struct Content {
-    Bytes dict, out;
-    bool linked;
-    Block raw(const Bytes& data) { append(out, data); return { data, true }; }
-    Block block(const std::vector<Part>& parts, const Bytes& tail)
-    {
-        Block b = { Bytes(), false };
-        Bytes window = dict;
-        if (linked) append(window, out);
-        const size_t base = window.size();
-        for (const Part& p : parts) {
-            sequence(b.data, p.literals, p.offset, p.match);
-            append(window, p.literals);
-            CHECK(p.offset >= 1 && p.offset <= window.size() && p.offset <= 65535);
-            for (size_t k = 0; k < p.match; k++) window.push_back(window[window.size() - p.offset]);
-        }
-        CHECK(tail.size() >= 12);
-        sequence(b.data, tail, 0, 0);
-        append(window, tail);
-        out.insert(out.end(), window.begin() + (long)base, window.end());
-        return b;
-    }
-};
-
-Bytes frame_of(const std::vector<Block>& blocks, bool linked, uint32_t dict_id)
-{
-    Bytes f;
-    put32(f, kLz4fMagic);
-    f.push_back((uint8_t)(0x40 | (linked ? 0 : 0x20) | (dict_id ? 0x01 : 0)));
-    f.push_back(0x40);
-    if (dict_id) put32(f, dict_id);
-    f.push_back((uint8_t)(xxh32_serial(f.data() + 4, (int64_t)f.size() - 4, 0) >> 8));
-    for (const Block& b : blocks) { put32(f, (uint32_t)b.data.size() | (b.raw ? kLz4fRawBit : 0u)); append(f, b.data); }
-    put32(f, 0);
-    return f;
-}
-
-struct Decoded { std::vector<lz4hip_lz4f_info_t> recs; lz4hip_lz4f_batch_info_t info; std::vector<int64_t> off; Bytes out; int64_t written; };
+using namespace built_frames;
 
 // every buffer a heap block of exactly its size; the dictionary at offset `odd` of a block of exactly its size + odd
 Decoded decode(const std::vector<Bytes>& frames, const Bytes& dict, uint32_t dict_id, int odd, int64_t rows, int64_t out_bytes, int64_t round_blocks, int grid,
@@ -125,8 +51,6 @@ Decoded decode(const std::vector<Bytes>& frames, const Bytes& dict, uint32_t dic
     CHECK(run.plain_calls == 0 && run.dict_calls > 0);
     return d;
 }
-
-const Bytes kTail = { 100, 101, 102, 103, 104, 105, 106, 107, 108, 109, 110, 111 };
 
 struct Case { Bytes frame, content; int64_t blocks; int64_t refused_good; };           // refused_good >= 0: block 1 is refused behind that many bytes
 

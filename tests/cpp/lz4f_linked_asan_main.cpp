@@ -1,6 +1,6 @@
-// lz4f_linked_asan_main.cpp -- TEST INFRASTRUCTURE ONLY: a stand-alone program over the emulator translation unit of the decode of LZ4
-// frames with linked blocks (tests/simt/emu_lz4f_linked.cpp), for a sanitizer run of the kernels, the launch sequences and the fronts
-// on the CPU:
+// lz4f_linked_asan_main.cpp -- TEST INFRASTRUCTURE ONLY: a stand-alone program over the framing emulator's translation unit, for the
+// decode of LZ4 frames with linked blocks (tests/simt/emu_framing.cpp, the linked entry points of its part emu_lz4f_batch.inc): a
+// sanitizer run of the kernels, the launch sequences and the fronts on the CPU:
 //
 //     g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=undefined -pthread -Itests/simt -Ilz4net_amd/csrc \
 //         tests/cpp/lz4f_linked_asan_main.cpp -o lz4f_linked_asan && ./lz4f_linked_asan
@@ -9,83 +9,14 @@
 // its item 0 at the very start of an allocation of exactly the decoded size: a match that starts at the frame's first byte (a), one
 // byte before it (a': it must be refused, not read), a source that crosses a raw block and overlaps itself (c), the run fill out of the
 // history (d), and the mixed batch of tests/test_simt_lz4f_linked.py with its clips, at the library's grids and at grids forced to 1
-// and 3.  The frames are built by hand here as tests/lz4f_linked_ref.py builds them; the independent items hold raw blocks only, so
-// the stand-in block codec is handed nothing but empty rows.
-#include "../simt/emu_lz4f_linked.cpp"
-
-#include <cstdio>
-#include <cstdlib>
-#include <vector>
+// and 3.  The frames are built by hand (built_frames.hpp) as tests/lz4f_linked_ref.py builds them; the independent items hold raw blocks
+// only, so the stand-in block codec is handed nothing but empty rows.
+#include "../simt/emu_framing.cpp"
+#include "built_frames.hpp"
 
 namespace {
 
-typedef std::vector<uint8_t> Bytes;
-
-#define CHECK(cond) do { if (!(cond)) { fprintf(stderr, "%s:%d: CHECK failed: %s\n", __FILE__, __LINE__, #cond); exit(1); } } while (0)
-
-Bytes noise(size_t n, uint32_t seed)
-{
-    Bytes b(n);
-    uint32_t x = seed * 2654435761u + 1u;
-    for (size_t i = 0; i < n; i++) { x = x * 1664525u + 1013904223u; b[i] = (uint8_t)(x >> 24); }
-    return b;
-}
-
-void put32(Bytes& b, uint32_t v) { for (int k = 0; k < 4; k++) b.push_back((uint8_t)(v >> (8 * k))); }
-void append(Bytes& b, const Bytes& a) { b.insert(b.end(), a.begin(), a.end()); }
-
-void put_length(Bytes& b, size_t n) { for (; n >= 255; n -= 255) b.push_back(255); b.push_back((uint8_t)n); }
-
-// token, literal length bytes, literals [, offset, match length bytes]; match == 0: a block's last sequence
-void sequence(Bytes& b, const Bytes& literals, unsigned offset, size_t match)
-{
-    const size_t ll = literals.size(), ml = match ? match - 4 : 0;
-    b.push_back((uint8_t)((ll < 15 ? ll : 15) << 4 | (ml < 15 ? ml : 15)));
-    if (ll >= 15) put_length(b, ll - 15);
-    append(b, literals);
-    if (match) {
-        b.push_back((uint8_t)offset); b.push_back((uint8_t)(offset >> 8));
-        if (ml >= 15) put_length(b, ml - 15);
-    }
-}
-
-struct Block { Bytes data; bool raw; };
-struct Part { Bytes literals; unsigned offset; size_t match; };
-
-// the frame under construction and the bytes it decodes to
-struct Content {
-    Bytes out;
-    Block raw(const Bytes& data) { append(out, data); return { data, true }; }
-    Block block(const std::vector<Part>& parts, const Bytes& tail)
-    {
-        Block b = { Bytes(), false };
-        for (const Part& p : parts) {
-            sequence(b.data, p.literals, p.offset, p.match);
-            append(out, p.literals);
-            CHECK(p.offset >= 1 && p.offset <= out.size());
-            for (size_t k = 0; k < p.match; k++) out.push_back(out[out.size() - p.offset]);
-        }
-        CHECK(tail.size() >= 12);
-        sequence(b.data, tail, 0, 0);
-        append(out, tail);
-        return b;
-    }
-};
-
-Bytes frame_of(const std::vector<Block>& blocks, bool linked, bool dict = false)
-{
-    Bytes f;
-    put32(f, kLz4fMagic);
-    f.push_back((uint8_t)(0x40 | (linked ? 0 : 0x20) | (dict ? 0x01 : 0)));
-    f.push_back(0x40);
-    if (dict) put32(f, 7);
-    f.push_back((uint8_t)(xxh32_serial(f.data() + 4, (int64_t)f.size() - 4, 0) >> 8));
-    for (const Block& b : blocks) { put32(f, (uint32_t)b.data.size() | (b.raw ? kLz4fRawBit : 0u)); append(f, b.data); }
-    put32(f, 0);
-    return f;
-}
-
-struct Decoded { std::vector<lz4hip_lz4f_info_t> recs; lz4hip_lz4f_batch_info_t info; std::vector<int64_t> off; Bytes out; int64_t written; };
+using namespace built_frames;
 
 // every buffer a heap block of exactly its size; the table holds `rows` rows, all of them empty rows to the stand-in codec
 Decoded decode(const std::vector<Bytes>& frames, int64_t rows, int64_t out_bytes, int64_t round_blocks, int grid, unsigned flags = 3 | kLz4fAcceptLinked)
@@ -110,28 +41,26 @@ Decoded decode(const std::vector<Bytes>& frames, int64_t rows, int64_t out_bytes
     return d;
 }
 
-const Bytes kTail = { 100, 101, 102, 103, 104, 105, 106, 107, 108, 109, 110, 111 };
-
 Block full_block(Content& c, uint32_t seed) { return c.block({ { noise(32762, seed), 32762, 32762 } }, kTail); }
 
 struct Case { Bytes frame, content; int64_t blocks; };
 
 Case case_a(unsigned offset)
 {
-    Content c;
+    Content c = { Bytes(), Bytes(), true };
     std::vector<Block> blocks = { c.raw(noise(1000, 1)), c.block({ { Bytes(), 1000, 20 } }, kTail) };
     blocks[1].data[1] = (uint8_t)offset; blocks[1].data[2] = (uint8_t)(offset >> 8);
     return { frame_of(blocks, true), c.out, 2 };
 }
 Case case_c()
 {
-    Content c;
+    Content c = { Bytes(), Bytes(), true };
     const std::vector<Block> blocks = { full_block(c, 3), c.raw(noise(10, 4)), c.block({ { Bytes(), 20, 40 }, { Bytes{ 'x', 'y' }, 65535, 5 } }, kTail) };
     return { frame_of(blocks, true), c.out, 3 };
 }
 Case case_d()
 {
-    Content c;
+    Content c = { Bytes(), Bytes(), true };
     const std::vector<Block> blocks = { c.block({}, noise(50, 5)), c.block({ { Bytes(), 1, 1000 } }, kTail) };
     return { frame_of(blocks, true), c.out, 2 };
 }
@@ -161,7 +90,7 @@ void mixed_batch(int grid)
     const std::vector<Bytes> frames = {
         frame_of({ { one_src, true } }, false), two.frame, skippable, three.frame,
         frame_of({ { Bytes(two_src.begin(), two_src.begin() + 65536), true }, { Bytes(two_src.begin() + 65536, two_src.end()), true } }, false),
-        frame_of({}, false), frame_of({ { Bytes{ '0', '1', '2' }, true } }, true, true),
+        frame_of({}, false), frame_of({ { Bytes{ '0', '1', '2' }, true } }, true, 7),
     };
     const std::vector<Bytes> contents = { one_src, two.content, Bytes(), three.content, two_src, Bytes(), Bytes() };
     Bytes want;

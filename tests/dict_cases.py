@@ -20,6 +20,7 @@ import os
 
 import numpy as np
 
+import emu_lib
 import lz4f_linked_ref as linked
 from lane_flush_cases import TAIL, emit, far_block, length_block
 from wave_decode_cases import short_run
@@ -367,27 +368,7 @@ def plain_blocks():
 
 
 # ---- the emulator library -------------------------------------------------------------------------------------------------------------------
-_lib = None
-
-
-def emu():
-    """libsimt_dict.so (tests/simt/emu_dict.cpp), built once"""
-    global _lib
-    if _lib is None:
-        import glob
-        import sys
-        simt = os.path.join(os.path.dirname(os.path.abspath(__file__)), "simt")
-        sys.path.insert(0, simt)
-        import build_emu
-        deps = [p for pat in (os.path.join(build_emu.AB, "*.hpp"), os.path.join(build_emu.CSRC, "*.hpp"), os.path.join(build_emu.CSRC, "*.inc"),
-                              os.path.join(simt, "*.hpp"), os.path.join(simt, "emu_kernels.cpp")) for p in glob.glob(pat)]
-        flags = ["-I" + build_emu.AB, "-pthread"] + (["-DLZ4HIP_HAVE_HC", "-DLZ4HIP_TUNING_BUILD"] if os.path.exists(os.path.join(build_emu.CSRC, "lz4hip_hc.hpp")) else [])
-        L = C.CDLL(build_emu._build(os.path.join(simt, "libsimt_dict.so"), "emu_dict.cpp", deps, flags))
-        L.emu_dict_sizeof.restype = C.c_int64
-        L.emu_dict_sizes_scratch_bytes.restype = C.c_int64
-        L.emu_dict_sizes_scratch_bytes.argtypes = [C.c_int64]
-        _lib = L
-    return _lib
+emu = emu_lib.dict_kernels    # libsimt_dict.so (tests/simt/emu_dict.cpp), built once
 
 
 # ---- the fixture: records compressed by liblz4 against a dictionary ---------------------------------------------------------------------------

@@ -1,5 +1,6 @@
-"""TEST INFRASTRUCTURE: the two emulator libraries of tests/simt/build_emu.py, each built and loaded once for every test file, the
-ctypes aliases the tests type their entry points with, the twins of the records every framing run record shares
+"""TEST INFRASTRUCTURE: the emulator libraries of tests/simt/build_emu.py -- three builds of the kernels' source (libsimt_kernels.so,
+its 'starved' variant, and libsimt_dict.so with the dictionary mode's counters) and the one of the framing source
+(libsimt_framing.so) -- each built and loaded once for every test file, the ctypes aliases the tests type their entry points with, the twins of the records every framing run record shares
 (tests/simt/emu_framing.hpp: EmuCounters, EmuHostRun), and what every emulator test file shares: the argument error, the forced grids
 and the guarded buffer."""
 import ctypes as C
@@ -12,7 +13,7 @@ import numpy as np
 from lz4net_amd._lib import E_ARGUMENT  # noqa: F401  (the tests take it from here)
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "simt"))
-from build_emu import build, build_framing  # noqa: E402
+from build_emu import build, build_dict, build_framing  # noqa: E402
 
 P, I64, I32, U32 = C.c_void_p, C.c_int64, C.c_int32, C.c_uint32
 GRIDS = (0, 1, 3)                               # the library's own grids, and grids forced to 1 and 3 workgroups
@@ -57,6 +58,15 @@ def kernels(starved=False):
     L = C.CDLL(build(starved=starved))
     L.emu_compare.restype = C.c_ulonglong
     L.emu_steps.restype = C.c_ulonglong
+    return L
+
+
+@functools.lru_cache(maxsize=None)
+def dict_kernels():
+    """libsimt_dict.so (tests/simt/emu_dict.cpp): the decode of block batches against a shared dictionary"""
+    L = C.CDLL(build_dict())
+    L.emu_dict_sizeof.restype = I64
+    L.emu_dict_sizes_scratch_bytes.argtypes, L.emu_dict_sizes_scratch_bytes.restype = [I64], I64
     return L
 
 

@@ -1,18 +1,16 @@
 """TEST INFRASTRUCTURE for the tests of batches of LZ4 frames -- tests/test_simt_lz4f_batch.py and tests/test_gpu_lz4f_batch.py: the
-emulator library of the batch path (tests/simt/emu_lz4f_batch.cpp, built here with build_emu._build as libsimt_lz4f_batch.so), the
+batch path's entry points in the framing emulator library (tests/simt/emu_lz4f_batch.inc, a part of libsimt_framing.so), the
 batches the tests are made of, and the emulator path checked against the one-frame path: encode against lz4f_cases.emu_encode of every
 item alone, decode against the from-the-spec twin tests/lz4f_ref.py on every item alone, with the twin's per-block results and bytes
 as the stand-in codec keyed by global table row."""
 import ctypes as C
 import functools
-import glob
 import os
 
 import numpy as np
 
 import emu_lib
 import lz4f_ref as ref
-from build_emu import CSRC, HERE as SIMT, _build
 from emu_lib import E_ARGUMENT, GUARD, Guarded, I32 as _I32, I64 as _I64, P as _P, u8
 from lz4f_cases import emu_encode, flip, mixed, sample
 from lz4net_amd._lib import Lz4fBatchInfo, Lz4fInfo
@@ -33,8 +31,7 @@ class EmuRun(C.Structure):
 
 @functools.lru_cache(maxsize=None)
 def emu():
-    deps = [f for p in ("*.hpp", "*.inc") for f in glob.glob(os.path.join(CSRC, p))] + glob.glob(os.path.join(SIMT, "*.hpp"))
-    L = C.CDLL(_build(os.path.join(SIMT, "libsimt_lz4f_batch.so"), "emu_lz4f_batch.cpp", deps, ["-pthread"]))
+    L = emu_lib.framing()
     L.emu_lz4f_batch_sizeof.restype = _I64
     assert L.emu_lz4f_batch_sizeof(0) == C.sizeof(Lz4fInfo) and L.emu_lz4f_batch_sizeof(1) == C.sizeof(EmuRun)
     assert L.emu_lz4f_batch_sizeof(2) == C.sizeof(Lz4fBatchInfo) and L.emu_lz4f_batch_sizeof(3) == C.sizeof(emu_lib.EmuCounters)

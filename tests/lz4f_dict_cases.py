@@ -1,12 +1,11 @@
 """TEST INFRASTRUCTURE for the tests of LZ4 frames with a dictionary -- tests/test_simt_lz4f_dict.py and tests/test_gpu_lz4f_dict.py:
-the emulator library (tests/simt/emu_lz4f_dict.cpp, built here with build_emu._build as libsimt_lz4f_dict.so), the frames and batches
-the tests are made of, what the twin (tests/lz4f_dict_ref.py) expects of a batch, and the emulator path checked against it field by
-field.  Every block runs the real wavefront decoder under the emulator: the rounds' rows decode_dict_kernel, the linked rows the
+the dictionary entry points of the framing emulator library (tests/simt/emu_lz4f_dict.inc, a part of libsimt_framing.so), the frames
+and batches the tests are made of, what the twin (tests/lz4f_dict_ref.py) expects of a batch, and the emulator path checked against it
+field by field.  Every block runs the real wavefront decoder under the emulator: the rounds' rows decode_dict_kernel, the linked rows the
 dictionary form of the ordered decode."""
 import base64
 import ctypes as C
 import functools
-import glob
 import json
 import os
 
@@ -15,7 +14,6 @@ import numpy as np
 import emu_lib
 import lz4f_dict_ref as dr
 import lz4f_ref as ref
-from build_emu import CSRC, HERE as SIMT, _build
 from emu_lib import GUARD, Guarded, I32 as _I32, I64 as _I64, P as _P, U32 as _U32, u8
 from lz4f_batch_cases import BATCH_FIELDS, INFO_FIELDS, expect_batch, offsets_of
 from lz4f_linked_cases import check_image, check_records, records_of
@@ -34,8 +32,7 @@ class EmuRun(C.Structure):
 
 @functools.lru_cache(maxsize=None)
 def emu():
-    deps = [f for p in ("*.hpp", "*.inc") for f in glob.glob(os.path.join(CSRC, p))] + glob.glob(os.path.join(SIMT, "*.hpp"))
-    L = C.CDLL(_build(os.path.join(SIMT, "libsimt_lz4f_dict.so"), "emu_lz4f_dict.cpp", deps, ["-pthread"]))
+    L = emu_lib.framing()
     L.emu_lz4f_dict_sizeof.restype = _I64
     assert L.emu_lz4f_dict_sizeof(0) == C.sizeof(Lz4fInfo) and L.emu_lz4f_dict_sizeof(1) == C.sizeof(EmuRun)
     assert L.emu_lz4f_dict_sizeof(2) == C.sizeof(Lz4fBatchInfo) and L.emu_lz4f_dict_sizeof(3) == C.sizeof(emu_lib.EmuCounters)

@@ -1,12 +1,11 @@
 """TEST INFRASTRUCTURE for the tests of LZ4 frames with linked blocks -- tests/test_simt_lz4f_linked.py and
-tests/test_gpu_lz4f_linked.py: the emulator library (tests/simt/emu_lz4f_linked.cpp, built here with build_emu._build as
-libsimt_lz4f_linked.so), the frames and batches the tests are made of, what the twin (tests/lz4f_linked_ref.py) expects of a batch, and
+tests/test_gpu_lz4f_linked.py: the linked entry points of the framing emulator library (tests/simt/emu_lz4f_batch.inc, a part of
+libsimt_framing.so), the frames and batches the tests are made of, what the twin (tests/lz4f_linked_ref.py) expects of a batch, and
 the emulator path checked against it field by field.  The linked rows run the real wavefront decoder under the emulator; the
 independent rows keep the stand-in codec of tests/lz4f_batch_cases.py, keyed by global table row."""
 import base64
 import ctypes as C
 import functools
-import glob
 import json
 import os
 
@@ -15,7 +14,6 @@ import numpy as np
 import emu_lib
 import lz4f_linked_ref as lk
 import lz4f_ref as ref
-from build_emu import CSRC, HERE as SIMT, _build
 from emu_lib import GUARD, Guarded, I32 as _I32, I64 as _I64, P as _P, u8
 from lz4f_batch_cases import BATCH_FIELDS, INFO_FIELDS, EmuRun, expect_batch, offsets_of, standin
 from lz4net_amd._lib import Lz4fBatchInfo, Lz4fInfo
@@ -26,9 +24,7 @@ GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "lz4
 
 @functools.lru_cache(maxsize=None)
 def emu():
-    deps = [f for p in ("*.hpp", "*.inc") for f in glob.glob(os.path.join(CSRC, p))] + glob.glob(os.path.join(SIMT, "*.hpp")) + \
-        [os.path.join(SIMT, "emu_lz4f_batch.cpp")]
-    L = C.CDLL(_build(os.path.join(SIMT, "libsimt_lz4f_linked.so"), "emu_lz4f_linked.cpp", deps, ["-pthread"]))
+    L = emu_lib.framing()
     L.emu_lz4f_batch_sizeof.restype = _I64
     assert L.emu_lz4f_batch_sizeof(0) == C.sizeof(Lz4fInfo) and L.emu_lz4f_batch_sizeof(1) == C.sizeof(EmuRun)
     assert L.emu_lz4f_batch_sizeof(2) == C.sizeof(Lz4fBatchInfo)

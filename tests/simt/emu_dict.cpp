@@ -3,8 +3,8 @@
 // lz4net_amd/csrc/lz4hip_decode.hpp, sizes_walk_dict_kernel through framing::decoded_sizes, and the host-pointer call's upload and slice
 // loop of lz4hip_hostbatch.hpp) compiled against the SIMT emulator, for tests/test_simt_dict_decode.py and
 // tests/cpp/dict_decode_asan_main.cpp.  It is emu_kernels.cpp -- its kernels, its counters, its EmuStage -- with the counters of the DICT
-// mode behind LZ4HIP_STAT_DICT, which expands to nothing in every other build.  Built with g++ by tests/dict_cases.py through
-// build_emu._build, never shipped.
+// mode behind LZ4HIP_STAT_DICT, which expands to nothing in every other build.  Built with g++ by build_emu.py (build_dict), never
+// shipped.
 static unsigned long long g_dict_stat[16];    // lz4hip::DictStat: where the bytes before the block came from, per lane
 #define LZ4HIP_STAT_DICT(slot, n) do { g_dict_stat[slot] += (unsigned long long)(n); } while (0)
 
@@ -24,16 +24,6 @@ namespace emu_dict {
 using namespace lz4hip;
 
 static_assert(kDictStats <= 16, "g_dict_stat");
-
-inline Batch device_batch(const lz4hip_batch_t* b)
-{
-    Batch d;
-    memset(&d, 0, sizeof d);
-    d.src = (const uint8_t*)b->src; d.src_off = b->src_off; d.src_stride = b->src_stride; d.src_len = b->src_len; d.src_len_all = b->src_len_all;
-    d.dst = (uint8_t*)b->dst; d.dst_off = b->dst_off; d.dst_stride = b->dst_stride; d.dst_cap = b->dst_cap; d.dst_cap_all = b->dst_cap_all;
-    d.result = b->result; d.n_blocks = b->n_blocks;
-    return d;
-}
 
 // the library's launch (launch_decode_dict of lz4hip_api.hip): the reachable bytes, the dictionary's end, four wavefronts a workgroup
 inline void launch(const Batch& d, const uint8_t* dict, int64_t dict_len, int known, unsigned wpg)
@@ -112,7 +102,7 @@ int emu_dict_host(const lz4hip_batch_t* hb, const uint8_t* dict, int64_t dict_le
     r->error[0] = 0;
     const unsigned wpg = (unsigned)waves_per_group;
     auto make_run = [known, wpg](const uint8_t* d_dict, int64_t reach) {
-        return [=](const lz4hip_batch_t* db, int64_t) { emu_dict::launch(emu_dict::device_batch(db), d_dict, reach, known, wpg); return 0; };
+        return [=](const lz4hip_batch_t* db, int64_t) { emu_dict::launch(emu_framing::device_batch(db), d_dict, reach, known, wpg); return 0; };
     };
     const int rc = hostbatch::run_host_batch_dict(st, hb, dict, dict_len, !known, make_run, r->slices_knob, 1, emu_hostbatch::limits_of(*r));
     r->intact = st.intact();

@@ -17,6 +17,9 @@ using emu_framing::EmuBackend;
 using emu_framing::backend;
 using emu_framing::finish;
 using emu_framing::kJunk;
+using emu_framing::kWaveDecodeLdsBytes;
+using emu_framing::device_batch;
+using emu_framing::same_kernel;
 
 #include "emu_stream.inc"    // LZ4Stream, Wrap and batches of streams: single kernels, sequences, fronts, host-pointer calls
 #include "emu_frame.inc"     // the legacy frame
@@ -25,4 +28,6 @@ using emu_framing::kJunk;
 #include "emu_sizes.inc"     // the size query of a block batch
 #include "emu_packed.inc"    // the packed encode of a block batch
 #include "emu_compact.inc"   // the compact decode of a block batch and of a legacy frame
-#include "emu_lz4f.inc"      // xxHash32 rows and the LZ4 frame
+#include "emu_lz4f.inc"      // xxHash32 rows and the LZ4 frame, with the stand-in decoder keyed by global table row ...
+#include "emu_lz4f_batch.inc"  // ... the batch of LZ4 frames over the same stand-in, and frames with linked blocks
+#include "emu_lz4f_dict.inc"   // LZ4 frames with a dictionary, every block through the real decoder

@@ -34,6 +34,21 @@ using namespace lz4hip::framing;
 
 constexpr uint8_t kJunk = 0xBD;                              // what a stand-in codec may leave inside a row's capacity
 
+// what a workgroup of the wavefront decoder has on the device: the LDS of the calls that run the real decoder (linked blocks, dictionaries)
+constexpr size_t kWaveDecodeLdsBytes = (size_t)kWaveDecodeWavesPerGroup * kWaveLdsBytes;
+static_assert(kWaveDecodeLdsBytes >= kSizesLdsBytes && kWaveDecodeLdsBytes >= kStreamThreads * 8, "one LDS size serves every kernel of the sequences");
+
+// the kernels' view of a batch of the C interface (to_device_batch of lz4hip_api.hip)
+inline Batch device_batch(const lz4hip_batch_t* b)
+{
+    Batch d;
+    memset(&d, 0, sizeof d);
+    d.src = (const uint8_t*)b->src; d.src_off = b->src_off; d.src_stride = b->src_stride; d.src_len = b->src_len; d.src_len_all = b->src_len_all;
+    d.dst = (uint8_t*)b->dst; d.dst_off = b->dst_off; d.dst_stride = b->dst_stride; d.dst_cap = b->dst_cap; d.dst_cap_all = b->dst_cap_all;
+    d.result = b->result; d.n_blocks = b->n_blocks;
+    return d;
+}
+
 // a kernel and its arguments, as the closure simt::launch runs in every lane
 template <class... P>
 struct KernelCall {

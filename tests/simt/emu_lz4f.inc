@@ -22,25 +22,14 @@ struct Lz4fEmuRun {
 
 namespace {
 
-struct Lz4fBackend : EmuBackend {
-    Lz4fEmuRun* r = nullptr;
+// The stand-in block decoder keyed by global table row, of this part's backend and of the batch's (emu_lz4f_batch.inc): `Run` is the
+// run record, of which it reads dec_results, dec_len, dec_at, dec_bytes and dec_rows and counts calls and shape_errors.  It is what
+// decides whether a decode sequence kept its promises, so it is written once.
+template <class Run>
+struct RowKeyedDecoder : EmuBackend {
+    Run* r = nullptr;
     int64_t done = 0, walk = 0;  // rows the decoder was given since walk number `walk` (EmuBackend::passes)
 
-    // LZ4_compress_limitedOutput per block at length - 1: the batch must be the frame's blocks, each with its own length (the last one
-    // ragged) and one byte less of room; the results and bytes are the test's
-    int encode(const lz4hip_batch_t* b, int)
-    {
-        if (!b->src_len || !b->dst_cap || !b->result || !b->dst || b->src_off || b->dst_off) { r->shape_errors++; return 0; }
-        for (int64_t j = 0; j < b->n_blocks; j++) {
-            const int32_t len = b->src_len[j], cap = b->dst_cap[j];
-            if (len != r->enc_len[j] || cap != len - 1 || cap > b->dst_stride || len > b->src_stride) { r->shape_errors++; b->result[j] = 0; continue; }
-            const int32_t res = r->enc_results[j];
-            if (res > cap) { r->shape_errors++; b->result[j] = 0; continue; }
-            if (res > 0) memcpy((uint8_t*)b->dst + j * b->dst_stride, r->enc_bytes + j * b->dst_stride, (size_t)res);
-            b->result[j] = res;
-        }
-        return 0;
-    }
     int decode(const lz4hip_batch_t* b, int known)
     {
         r->calls++;
@@ -60,6 +49,24 @@ struct Lz4fBackend : EmuBackend {
             b->result[j] = res;
         }
         done += b->n_blocks;
+        return 0;
+    }
+};
+
+struct Lz4fBackend : RowKeyedDecoder<Lz4fEmuRun> {
+    // LZ4_compress_limitedOutput per block at length - 1: the batch must be the frame's blocks, each with its own length (the last one
+    // ragged) and one byte less of room; the results and bytes are the test's
+    int encode(const lz4hip_batch_t* b, int)
+    {
+        if (!b->src_len || !b->dst_cap || !b->result || !b->dst || b->src_off || b->dst_off) { r->shape_errors++; return 0; }
+        for (int64_t j = 0; j < b->n_blocks; j++) {
+            const int32_t len = b->src_len[j], cap = b->dst_cap[j];
+            if (len != r->enc_len[j] || cap != len - 1 || cap > b->dst_stride || len > b->src_stride) { r->shape_errors++; b->result[j] = 0; continue; }
+            const int32_t res = r->enc_results[j];
+            if (res > cap) { r->shape_errors++; b->result[j] = 0; continue; }
+            if (res > 0) memcpy((uint8_t*)b->dst + j * b->dst_stride, r->enc_bytes + j * b->dst_stride, (size_t)res);
+            b->result[j] = res;
+        }
         return 0;
     }
 };

@@ -1,25 +1,11 @@
-// emu_lz4f_batch.cpp -- TEST INFRASTRUCTURE ONLY.
-// libsimt_lz4f_batch.so: the batch of LZ4 frames (lz4net_amd/csrc/lz4hip_lz4f_batch.hpp and its host code in lz4hip_framing.hpp:
-// lz4f_batch_encode, lz4f_batch_decode and the host-pointer calls lz4f_batch_encode_host / lz4f_batch_decode_host) compiled against the
-// SIMT emulator over the emulated device of emu_framing.hpp, for tests/test_simt_lz4f_batch.py and tests/cpp/lz4f_batch_asan_main.cpp.
-// A translation unit and library of its own beside libsimt_framing.so (folding it in as a part of emu_framing.cpp is a follow-up); the
-// prelude is that file's.  The block codec is a stand-in, as in emu_lz4f.inc: results and bytes the test computed with the oracle, keyed
-// by GLOBAL table row -- the encoder's table spans all items, and the decode sequence hands the decoder one round's rows at a time.
-// Built with g++ by tests/lz4f_batch_cases.py through build_emu._build, never shipped.
-#include "simt_wave.hpp"
-
-#include "lz4hip_common.hpp"
-
-using namespace lz4hip;
-
-#include "emu_framing.hpp"
-#include "lz4hip_hostbatch.hpp"
-
-using emu_framing::EmuBackend;
-using emu_framing::backend;
-using emu_framing::finish;
-using emu_framing::kJunk;
-using emu_framing::same_kernel;
+// emu_lz4f_batch.inc -- TEST INFRASTRUCTURE ONLY, a part of emu_framing.cpp.
+// The batch of LZ4 frames (lz4net_amd/csrc/lz4hip_lz4f_batch.hpp and its host code in lz4hip_framing.hpp: lz4f_batch_encode,
+// lz4f_batch_decode and the host-pointer calls lz4f_batch_encode_host / lz4f_batch_decode_host) under the SIMT emulator, for
+// tests/test_simt_lz4f_batch.py and tests/cpp/lz4f_batch_asan_main.cpp, and the decode of frames with linked blocks
+// (lz4net_amd/csrc/lz4hip_lz4f_linked.hpp inside the sequences lz4f_decode and lz4f_batch_decode) over the same backend, for
+// tests/test_simt_lz4f_linked.py and tests/cpp/lz4f_linked_asan_main.cpp.  The block codec is a stand-in, as in emu_lz4f.inc: results
+// and bytes the test computed with the oracle, keyed by GLOBAL table row -- the encoder's table spans all items, and the decoder is
+// emu_lz4f.inc's RowKeyedDecoder.
 
 // what the emulated device is to do, and what it did
 struct Lz4fBatchEmuRun {
@@ -41,10 +27,7 @@ struct Lz4fBatchEmuRun {
 
 namespace {
 
-struct Lz4fBatchBackend : EmuBackend {
-    Lz4fBatchEmuRun* r = nullptr;
-    int64_t done = 0, walk = 0;  // rows the decoder was given since walk number `walk`
-
+struct Lz4fBatchBackend : RowKeyedDecoder<Lz4fBatchEmuRun> {
     template <class... P, class... A>
     void launch(void (*kernel)(P...), framing::Grid grid, unsigned threads, A&&... a)
     {
@@ -69,33 +52,22 @@ struct Lz4fBatchBackend : EmuBackend {
         }
         return 0;
     }
-    int decode(const lz4hip_batch_t* b, int known)
-    {
-        r->calls++;
-        if (walk != passes) { walk = passes; done = 0; }                     // (a host call that decodes again starts at row 0 again)
-        if (known || !b->dst_cap || !b->result || !b->dst || b->dst_off || !b->src_off || !b->src_len || b->dst_stride % 16 != 0) { r->shape_errors++; return 0; }
-        for (int64_t j = 0; j < b->n_blocks; j++) {
-            const int64_t g = done + j;
-            const int32_t len = b->src_len[j], cap = b->dst_cap[j];
-            uint8_t* out = (uint8_t*)b->dst + j * b->dst_stride;
-            if (len == 0) { b->result[j] = 0; continue; }                    // an empty block decodes to nothing
-            if (g >= r->dec_rows || len != r->dec_len[g] || cap < 0 || cap > b->dst_stride) { r->shape_errors++; b->result[j] = -1; continue; }
-            const int32_t res = r->dec_results[g];
-            const int64_t wrote = res > 0 ? res : 0, junk = wrote + 64 < cap ? wrote + 64 : cap;
-            if (wrote > cap) { r->shape_errors++; b->result[j] = -1; continue; }
-            memset(out, kJunk, (size_t)junk);
-            memcpy(out, r->dec_bytes + r->dec_at[g], (size_t)wrote);
-            b->result[j] = res;
-        }
-        done += b->n_blocks;
-        return 0;
-    }
 };
 
 Lz4fBatchBackend backend_of(Lz4fBatchEmuRun* r)
 {
     Lz4fBatchBackend be = backend<Lz4fBatchBackend>(r->grid, r->grid, r->grid);
     be.r = r;
+    return be;
+}
+
+// The linked decode needs what the plain launches do not have: a workgroup's LDS as large as the wavefront decoder's rings.  The linked
+// rows are decoded by the real decode_block under the emulator; the stand-in sees them as the empty rows the sequence promises, and the
+// INDEPENDENT rows keep it.
+Lz4fBatchBackend linked_backend_of(Lz4fBatchEmuRun* r)
+{
+    Lz4fBatchBackend be = backend_of(r);
+    be.lds_bytes = kWaveDecodeLdsBytes;
     return be;
 }
 
@@ -154,6 +126,41 @@ int emu_lz4f_batch_decode_host(const void* src, int64_t src_len, const int64_t* 
                                int64_t* dst_off, lz4hip_lz4f_info_t* item_info, lz4hip_lz4f_batch_info_t* info, Lz4fBatchEmuRun* r)
 {
     Lz4fBatchBackend be = backend_of(r);
+    return finish(be, framing::lz4f_batch_decode_host(be, src, src_len, src_off, n, flags, dst, dst_cap, dst_off, item_info, info), &r->counters);
+}
+
+// ---- frames with linked blocks: the one-frame and the batch decode with the wavefront decoder's LDS -------------------------------------
+int64_t emu_lz4f_linked_decode_scratch_bytes(int32_t slot_bytes, int64_t max_blocks, int64_t round_blocks)
+{
+    return framing::lz4f_decode_scratch_bytes(slot_bytes, max_blocks, round_blocks);
+}
+
+int emu_lz4f_linked_decode(const void* src, int64_t src_len, int32_t slot_bytes, int64_t max_blocks, int64_t round_blocks, unsigned flags, void* scratch,
+                           int64_t scratch_bytes, void* dst, int64_t dst_cap, lz4hip_lz4f_info_t* info, Lz4fBatchEmuRun* r)
+{
+    Lz4fBatchBackend be = linked_backend_of(r);
+    return finish(be, framing::lz4f_decode(be, src, src_len, slot_bytes, max_blocks, round_blocks, flags, scratch, scratch_bytes, dst, dst_cap, info), &r->counters);
+}
+
+int emu_lz4f_linked_decode_host(const void* src, int64_t src_len, unsigned flags, void* dst, int64_t dst_cap, lz4hip_lz4f_info_t* info, Lz4fBatchEmuRun* r)
+{
+    Lz4fBatchBackend be = linked_backend_of(r);
+    return finish(be, framing::lz4f_decode_host(be, src, src_len, flags, dst, dst_cap, info), &r->counters);
+}
+
+int emu_lz4f_linked_batch_decode(const void* src, int64_t src_len, const int64_t* src_off, int64_t n, int32_t slot_bytes, int64_t max_blocks,
+                                 int64_t round_blocks, unsigned flags, void* scratch, int64_t scratch_bytes, void* dst, int64_t dst_cap, int64_t* dst_off,
+                                 lz4hip_lz4f_info_t* item_info, lz4hip_lz4f_batch_info_t* info, int64_t* written_items, Lz4fBatchEmuRun* r)
+{
+    Lz4fBatchBackend be = linked_backend_of(r);
+    return finish(be, framing::lz4f_batch_decode(be, src, src_len, src_off, n, slot_bytes, max_blocks, round_blocks, flags, scratch, scratch_bytes, dst, dst_cap,
+                                                 dst_off, item_info, info, written_items), &r->counters);
+}
+
+int emu_lz4f_linked_batch_decode_host(const void* src, int64_t src_len, const int64_t* src_off, int64_t n, unsigned flags, void* dst, int64_t dst_cap,
+                                      int64_t* dst_off, lz4hip_lz4f_info_t* item_info, lz4hip_lz4f_batch_info_t* info, Lz4fBatchEmuRun* r)
+{
+    Lz4fBatchBackend be = linked_backend_of(r);
     return finish(be, framing::lz4f_batch_decode_host(be, src, src_len, src_off, n, flags, dst, dst_cap, dst_off, item_info, info), &r->counters);
 }
 

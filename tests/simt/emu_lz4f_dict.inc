@@ -1,23 +1,10 @@
-// emu_lz4f_dict.cpp -- TEST INFRASTRUCTURE ONLY.
-// libsimt_lz4f_dict.so: the decode of LZ4 frames with a dictionary (lz4hip_lz4f_decode_dict_* and lz4hip_lz4f_batch_decode_dict_*: the
-// dictionary forms of lz4hip_framing.hpp's sequences lz4f_decode and lz4f_batch_decode, the walk's dictionary ID, the linked decode's
-// dictionary form of lz4hip_lz4f_linked.hpp, and the host-pointer calls with the dictionary's staging) compiled against the SIMT
-// emulator, for tests/test_simt_lz4f_dict.py and tests/cpp/lz4f_dict_asan_main.cpp.  The emulated device is emu_framing.hpp's; the
-// block codec of the rounds is NO stand-in here: decode_dict runs the real decode_dict_kernel under the emulator, as the library's
-// launch does, and decode (the plain sequences, which a call without a dictionary is) the real decode_kernel.  Built with g++ by
-// tests/lz4f_dict_cases.py through build_emu._build, never shipped.
-#include "simt_wave.hpp"
-
-#include "lz4hip_common.hpp"
-
-using namespace lz4hip;
-
-#include "emu_framing.hpp"
-#include "lz4hip_hostbatch.hpp"
-
-using emu_framing::EmuBackend;
-using emu_framing::backend;
-using emu_framing::finish;
+// emu_lz4f_dict.inc -- TEST INFRASTRUCTURE ONLY, a part of emu_framing.cpp.
+// The decode of LZ4 frames with a dictionary (lz4hip_lz4f_decode_dict_* and lz4hip_lz4f_batch_decode_dict_*: the dictionary forms of
+// lz4hip_framing.hpp's sequences lz4f_decode and lz4f_batch_decode, the walk's dictionary ID, the linked decode's dictionary form of
+// lz4hip_lz4f_linked.hpp, and the host-pointer calls with the dictionary's staging) under the SIMT emulator, for
+// tests/test_simt_lz4f_dict.py and tests/cpp/lz4f_dict_asan_main.cpp.  The block codec of the rounds is NO stand-in here: decode_dict
+// runs the real decode_dict_kernel under the emulator, as the library's launch does, and decode (the plain sequences, which a call
+// without a dictionary is) the real decode_kernel.
 
 // what the emulated device is to do, and what it did
 struct Lz4fDictEmuRun {
@@ -32,23 +19,11 @@ struct Lz4fDictEmuRun {
 
 namespace {
 
-static_assert(kWaveDecodeWavesPerGroup * kWaveLdsBytes >= kSizesLdsBytes && kWaveDecodeWavesPerGroup * kWaveLdsBytes >= kStreamThreads * 8,
-              "one LDS size serves every kernel of the sequences");
-
 struct Lz4fDictBackend : EmuBackend {
     Lz4fDictEmuRun* r = nullptr;
     const uint8_t* caller_dict = nullptr;
     std::vector<uint8_t> dict_store;
 
-    static Batch device_batch(const lz4hip_batch_t* b)
-    {
-        Batch d;
-        memset(&d, 0, sizeof d);
-        d.src = (const uint8_t*)b->src; d.src_off = b->src_off; d.src_stride = b->src_stride; d.src_len = b->src_len; d.src_len_all = b->src_len_all;
-        d.dst = (uint8_t*)b->dst; d.dst_off = b->dst_off; d.dst_stride = b->dst_stride; d.dst_cap = b->dst_cap; d.dst_cap_all = b->dst_cap_all;
-        d.result = b->result; d.n_blocks = b->n_blocks;
-        return d;
-    }
     // the library's launches (launch_decode with the wavefront mapping, launch_decode_dict): four wavefronts a workgroup
     int decode(const lz4hip_batch_t* b, int known)
     {
@@ -57,8 +32,8 @@ struct Lz4fDictBackend : EmuBackend {
         const Batch d = device_batch(b);
         const unsigned wpg = kWaveDecodeWavesPerGroup;
         dim3 grid((unsigned)((d.n_blocks + wpg - 1) / wpg)), block(64 * wpg);
-        if (known) simt::launch(grid, block, (size_t)wpg * kWaveLdsBytes, [=] { decode_kernel<true>(d, kAllBlocks); });
-        else       simt::launch(grid, block, (size_t)wpg * kWaveLdsBytes, [=] { decode_kernel<false>(d, kAllBlocks); });
+        if (known) simt::launch(grid, block, kWaveDecodeLdsBytes, [=] { decode_kernel<true>(d, kAllBlocks); });
+        else       simt::launch(grid, block, kWaveDecodeLdsBytes, [=] { decode_kernel<false>(d, kAllBlocks); });
         return 0;
     }
     int decode_dict(const lz4hip_batch_t* b, const uint8_t* dict_end, int32_t reach, int known)
@@ -68,8 +43,8 @@ struct Lz4fDictBackend : EmuBackend {
         const Batch d = device_batch(b);
         const unsigned wpg = kWaveDecodeWavesPerGroup;
         dim3 grid((unsigned)((d.n_blocks + wpg - 1) / wpg)), block(64 * wpg);
-        if (known) simt::launch(grid, block, (size_t)wpg * kWaveLdsBytes, [=] { decode_dict_kernel<true>(d, dict_end, reach); });
-        else       simt::launch(grid, block, (size_t)wpg * kWaveLdsBytes, [=] { decode_dict_kernel<false>(d, dict_end, reach); });
+        if (known) simt::launch(grid, block, kWaveDecodeLdsBytes, [=] { decode_dict_kernel<true>(d, dict_end, reach); });
+        else       simt::launch(grid, block, kWaveDecodeLdsBytes, [=] { decode_dict_kernel<false>(d, dict_end, reach); });
         return 0;
     }
     // the dictionary's staging: exactly the bytes asked for between guard bytes, apart from the image
@@ -93,7 +68,7 @@ Lz4fDictBackend backend_of(Lz4fDictEmuRun* r, const void* dict)
 {
     Lz4fDictBackend be = backend<Lz4fDictBackend>(r->grid, r->grid, r->grid);
     be.r = r; be.caller_dict = (const uint8_t*)dict;
-    be.lds_bytes = (size_t)kWaveDecodeWavesPerGroup * kWaveLdsBytes;
+    be.lds_bytes = kWaveDecodeLdsBytes;
     r->plain_calls = r->dict_calls = r->dict_uploads = r->dict_bytes = r->dict_first_byte = r->uploads_before_dict = 0;
     return be;
 }

@@ -2,7 +2,7 @@
 liblz4's LZ4F_compressFrame_usingCDict (tests/golden/make_lz4f_dict_golden.py) and are read by the emulator path in
 tests/test_simt_lz4f_dict.py; that test never skips.  Here, where liblz4 is installed (found with ctypes.util.find_library; nothing is
 downloaded), the same 24 shapes and a 150 000-byte source are written FRESH -- 32 combinations -- and go through the twin and the
-emulator path (the library's kernels and sequences, tests/simt/emu_lz4f_dict.cpp); these tests, and only these, skip where the library
+emulator path (the library's kernels and sequences, tests/simt/emu_lz4f_dict.inc); these tests, and only these, skip where the library
 or its dictionary calls are absent."""
 import os
 

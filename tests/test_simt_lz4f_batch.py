@@ -1,5 +1,5 @@
 """CPU-only: batches of LZ4 frames (lz4net_amd/csrc/lz4hip_lz4f_batch.hpp and its host code in lz4hip_framing.hpp) under the SIMT
-emulator (tests/simt/emu_lz4f_batch.cpp): the real kernels, the library's fronts, launch sequences and host-pointer calls, with the
+emulator (tests/simt/emu_lz4f_batch.inc): the real kernels, the library's fronts, launch sequences and host-pointer calls, with the
 block codec replaced by results and bytes computed here with the oracle.  The reference is the one-frame path: the frame the one-frame
 emulator path writes for every item alone, and the from-the-spec twin reader (tests/lz4f_ref.py) on every item alone."""
 import ctypes as C

@@ -124,14 +124,8 @@ def rows_of(blocks, pick):
 
 def emulator_shares(blocks, dic, preload):
     """share of sequences per path of the wavefront decoder under the emulator (LZ4HIP_STAT 21, 24, 25 and LZ4HIP_STAT_PATH 31)"""
-    import glob
-    simt = os.path.join(ROOT, "tests", "simt")
-    sys.path.insert(0, simt)
-    import build_emu
-    deps = [p for pat in (os.path.join(build_emu.CSRC, "*.hpp"), os.path.join(simt, "*.hpp"), os.path.join(simt, "emu_kernels.cpp")) for p in glob.glob(pat)]
-    flags = ["-I" + build_emu.AB, "-pthread", "-DLZ4HIP_HAVE_HC", "-DLZ4HIP_TUNING_BUILD"] + ([] if preload else ["-DLZ4HIP_DICT_PRELOAD=0"])
-    so = os.path.join(simt, "libsimt_dict.so" if preload else "libsimt_dict_no_preload.so")
-    L = C.CDLL(build_emu._build(so, "emu_dict.cpp", deps, flags))
+    from emu_lib import build_dict
+    L = C.CDLL(build_dict() if preload else build_dict(["-DLZ4HIP_DICT_PRELOAD=0"], "libsimt_dict_no_preload.so"))
     n = len(blocks)
     width = max(len(b) for b in blocks) + 16
     src = np.zeros((n, width), np.uint8)
