@@ -1,6 +1,6 @@
 // built_frames.hpp -- TEST INFRASTRUCTURE ONLY: what the stand-alone sanitizer programs over the framing emulator unit share
 // (lz4f_batch_asan_main.cpp, lz4f_linked_asan_main.cpp, lz4f_dict_asan_main.cpp): LZ4 blocks and frames built by hand, sequence by
-// sequence, as tests/lz4f_linked_ref.py and tests/lz4f_dict_ref.py build them, and the record of a decoded batch.  Included behind
+// sequence, as tests/lz4f_built.py builds them, and the record of a decoded batch.  Included behind
 // ../simt/emu_framing.cpp, whose names (the frame format's constants, xxh32_serial, the C interface's records) it uses.
 #pragma once
 

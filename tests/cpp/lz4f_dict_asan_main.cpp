@@ -13,7 +13,7 @@
 // byte; 40 short sequences out of the dictionary and a long copy (the mirror's preload and the long path's two copies) -- with
 // dictionaries of 1, 13, 4 095, 4 097, 65 535 and 70 000 bytes, of which only the last 65 535 may be touched: the program hands the
 // kernels the WHOLE allocation but poisons nothing, so for 70 000 the check is the result.  Also the host calls, whose staging holds
-// exactly the reachable bytes.  The frames are built by hand (built_frames.hpp) as tests/lz4f_dict_ref.py builds them.
+// exactly the reachable bytes.  The frames are built by hand (built_frames.hpp) as tests/lz4f_built.py builds them.
 #include "../simt/emu_framing.cpp"
 #include "built_frames.hpp"
 

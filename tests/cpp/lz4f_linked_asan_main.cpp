@@ -9,7 +9,7 @@
 // its item 0 at the very start of an allocation of exactly the decoded size: a match that starts at the frame's first byte (a), one
 // byte before it (a': it must be refused, not read), a source that crosses a raw block and overlaps itself (c), the run fill out of the
 // history (d), and the mixed batch of tests/test_simt_lz4f_linked.py with its clips, at the library's grids and at grids forced to 1
-// and 3.  The frames are built by hand (built_frames.hpp) as tests/lz4f_linked_ref.py builds them; the independent items hold raw blocks
+// and 3.  The frames are built by hand (built_frames.hpp) as tests/lz4f_built.py builds them; the independent items hold raw blocks
 // only, so the stand-in block codec is handed nothing but empty rows.
 #include "../simt/emu_framing.cpp"
 #include "built_frames.hpp"

@@ -1,13 +1,13 @@
 """TEST INFRASTRUCTURE for tests/test_simt_dict_decode.py and tests/test_gpu_dict_decode.py, which are one design: LZ4 blocks decoded against
 a SHARED DICTIONARY (lz4hip_decode_batch_dict_*, decode_block's DICT mode in lz4hip_decode.hpp), BUILT sequence by sequence
-(lz4f_linked_ref.sequence, lane_flush_cases.emit) so that every path of the wavefront decoder meets a source before the block on both
+(lz4f_built.sequence, lane_flush_cases.emit) so that every path of the wavefront decoder meets a source before the block on both
 sides of its edges: how far a match may reach, matches that begin in the dictionary and end in the block, the LDS mirror's preload and
 what each path takes from it, and what must come from memory after a long copy.  Every block decodes to at most 12 KiB.
 
 TRUTH.  The CPU oracle has no dictionary form, so truth comes from SPLICING: for a block B and the prefix P -- the dictionary's reachable
 tail, its last 65 535 bytes -- the plain block B' is B with P in front of its first sequence's literals.  The oracle's two decoders on B'
 give P + (what B decodes to against the dictionary), and their return values are B's shifted by len(B') - len(B) (a count of output
-bytes: by len(P)).  The twin decoder lz4f_linked_ref.decode_block(B, cap, history=P) is asserted against that on every case, and where
+bytes: by len(P)).  The twin decoder lz4f_ref.decode_block(B, cap, history=P) is asserted against that on every case, and where
 liblz4 is installed LZ4_decompress_safe_usingDict on the valid ones: all on the CPU, before a kernel sees a case.  Damaged blocks (two
 per family: cut inside the last literals, the last token changed) expect what the oracle says of their spliced form.
 
@@ -21,8 +21,9 @@ import os
 import numpy as np
 
 import emu_lib
-import lz4f_linked_ref as linked
+import lz4f_ref
 from lane_flush_cases import TAIL, emit, far_block, length_block
+from lz4f_built import sequence
 from wave_decode_cases import short_run
 
 RING = 4096                  # kWaveRingBytes
@@ -60,7 +61,7 @@ class Case:
 
     def __init__(self, seqs, tail, dict_len, valid=True, note=""):
         self.seqs, self.tail, self.dict_len, self.note = seqs, tail, dict_len, note
-        self.block = b"".join(linked.sequence(*s) for s in seqs) + linked.sequence(tail)
+        self.block = b"".join(sequence(*s) for s in seqs) + sequence(tail)
         self.cap = sum(len(lit) + ml for lit, _, ml in seqs) + len(tail)
         self.raw = None
         if valid:
@@ -81,7 +82,7 @@ class Case:
         n, lit0 = self._head()
         p = prefix_of(self.dict_len)
         assert bytes(block[:n + len(lit0)]) == self.block[:n + len(lit0)]
-        head = linked.sequence(p + lit0, 1, 4)[:-2]                 # token, length bytes, literals; the match nibble is the block's own
+        head = sequence(p + lit0, 1, 4)[:-2]                 # token, length bytes, literals; the match nibble is the block's own
         head = bytes([head[0] & 0xF0 | block[0] & 0x0F]) + head[1:]
         return head + bytes(block[n + len(lit0):])
 
@@ -93,7 +94,7 @@ class Case:
         if k == 0:
             b = b[:len(b) - 7]
         else:
-            b[len(b) - len(linked.sequence(self.tail))] ^= 0x5F
+            b[len(b) - len(sequence(self.tail))] ^= 0x5F
         assert len(b) >= sum(self._head()[:1]) + len(self._head()[1]) + 3
         c.block, c.raw, c.note = bytes(b), None, self.note + " damaged %d" % k
         return c
@@ -313,7 +314,7 @@ def expected(oracle, name, known):
                 r, o = oracle.uncompress_unknown_raw(sp, sp.size, c.cap + EXTRA + len(p))
                 want = r - len(p) if r >= 0 else r + shift
                 # the twin with a history, on every case
-                tr, tb = linked.decode_block(c.block, c.cap + EXTRA, history=p)
+                tr, tb = lz4f_ref.decode_block(c.block, c.cap + EXTRA, history=p)
                 assert tr == want, (name, i, c.note, "twin", tr, want)
                 if want >= 0:
                     assert tb == bytes(o[len(p):len(p) + want]), (name, i, c.note, "twin's bytes")

@@ -1,55 +1,20 @@
 """TEST INFRASTRUCTURE for the tests of batches of LZ4 frames -- tests/test_simt_lz4f_batch.py and tests/test_gpu_lz4f_batch.py: the
-batch path's entry points in the framing emulator library (tests/simt/emu_lz4f_batch.inc, a part of libsimt_framing.so), the
-batches the tests are made of, and the emulator path checked against the one-frame path: encode against lz4f_cases.emu_encode of every
-item alone, decode against the from-the-spec twin tests/lz4f_ref.py on every item alone, with the twin's per-block results and bytes
-as the stand-in codec keyed by global table row."""
+batches the tests are made of, and the emulator's batch encode checked against the one-frame path: lz4f_cases.emu_encode of every item
+alone.  (The decode harness is tests/lz4f_cases.py's, against the twin tests/lz4f_ref.py on every item alone.)"""
 import ctypes as C
 import functools
 import os
 
 import numpy as np
 
-import emu_lib
 import lz4f_ref as ref
-from emu_lib import E_ARGUMENT, GUARD, Guarded, I32 as _I32, I64 as _I64, P as _P, u8
-from lz4f_cases import emu_encode, flip, mixed, sample
-from lz4net_amd._lib import Lz4fBatchInfo, Lz4fInfo
+from emu_lib import GUARD, Guarded, u8
+from lz4f_cases import BatchRun, emu, emu_encode, flip, mixed, offsets_of, sample, spans
 
-INFO_FIELDS = [f for f, _ in Lz4fInfo._fields_]
-BATCH_FIELDS = [f for f, _ in Lz4fBatchInfo._fields_]
 ITEM_LENGTHS = (0, 1, 13, 65535, 65536, 65537, 3 * 65536 + 5)
-BAD_ITEM = dict(blocks=0, decoded_bytes=0, good_bytes=0, error_offset=-1, content_size=-1, frame_bytes=0, error=E_ARGUMENT, kind=0, block_max=0,
-                flg=0, bd=0, checks=0)
-
-
-class EmuRun(C.Structure):
-    _anonymous_ = ("counters",)
-    _fields_ = [("enc_results", _P), ("enc_bytes", _P), ("enc_at", _P), ("enc_len", _P), ("enc_src", _P), ("enc_rows", _I64),
-                ("dec_results", _P), ("dec_len", _P), ("dec_at", _P), ("dec_bytes", _P), ("dec_rows", _I64),
-                ("grid", _I32), ("pad", _I32), ("calls", _I64), ("shape_errors", _I64), ("counters", emu_lib.EmuCounters)]
-
-
-@functools.lru_cache(maxsize=None)
-def emu():
-    L = emu_lib.framing()
-    L.emu_lz4f_batch_sizeof.restype = _I64
-    assert L.emu_lz4f_batch_sizeof(0) == C.sizeof(Lz4fInfo) and L.emu_lz4f_batch_sizeof(1) == C.sizeof(EmuRun)
-    assert L.emu_lz4f_batch_sizeof(2) == C.sizeof(Lz4fBatchInfo) and L.emu_lz4f_batch_sizeof(3) == C.sizeof(emu_lib.EmuCounters)
-    L.emu_lz4f_batch_bound.argtypes, L.emu_lz4f_batch_bound.restype = [_I64, _I64, C.c_int, C.c_uint], _I64
-    L.emu_lz4f_batch_encode_scratch_bytes.argtypes, L.emu_lz4f_batch_encode_scratch_bytes.restype = [_I64, _I64, C.c_int], _I64
-    L.emu_lz4f_batch_decode_scratch_bytes.argtypes, L.emu_lz4f_batch_decode_scratch_bytes.restype = [_I64, _I32, _I64, _I64], _I64
-    L.emu_lz4f_batch_encode.argtypes = [_P, _I64, _P, _I64, C.c_int, C.c_int, C.c_uint, _P, _I64, _P, _P, _I64, _P]
-    L.emu_lz4f_batch_decode.argtypes = [_P, _I64, _P, _I64, _I32, _I64, _I64, C.c_uint, _P, _I64, _P, _I64, _P, _P, _P, _P, _P]
-    L.emu_lz4f_batch_encode_host.argtypes = [_P, _I64, _P, _I64, C.c_int, C.c_int, C.c_uint, _P, _I64, _P, _P]
-    L.emu_lz4f_batch_decode_host.argtypes = [_P, _I64, _P, _I64, C.c_uint, _P, _I64, _P, _P, _P, _P]
-    return L
 
 
 # ---- batches -------------------------------------------------------------------------------------------------------------------------
-def offsets_of(items):
-    return np.cumsum([0] + [len(b) for b in items]).astype(np.int64)
-
-
 @functools.lru_cache(maxsize=None)
 def _sources(oracle):
     return tuple(sample(oracle, 2 + (k & 1), n) for k, n in enumerate(ITEM_LENGTHS))
@@ -58,14 +23,6 @@ def _sources(oracle):
 def sources(oracle):
     """items of 0, 1, 13, 65535, 65536, 65537 and 3 * 65536 + 5 bytes, D2 and D3 in turn"""
     return list(_sources(oracle))
-
-
-def spans(src, off):
-    """item i of the batch, or None for offsets that decrease or leave the buffer"""
-    out = []
-    for a, b in zip(off[:-1], off[1:]):
-        out.append(bytes(src[a:b]) if 0 <= a <= b <= len(src) else None)
-    return out
 
 
 @functools.lru_cache(maxsize=None)
@@ -115,7 +72,7 @@ def emu_encode_batch(oracle, src, off, block_id=4, hc=False, flags=0, grid=0, ho
             lens.append(min(len(it) - j * ref.block_bytes(bid), ref.block_bytes(bid)))
             where.append(int(off[i]) + j * ref.block_bytes(bid))
     arrs = [np.array(rets + [0], np.int32), u8(blob + b"\0"), np.array(at + [0], np.int64), np.array(lens + [0], np.int32), np.array(where + [0], np.int64)]
-    run = EmuRun(enc_results=arrs[0].ctypes.data, enc_bytes=arrs[1].ctypes.data, enc_at=arrs[2].ctypes.data, enc_len=arrs[3].ctypes.data,
+    run = BatchRun(enc_results=arrs[0].ctypes.data, enc_bytes=arrs[1].ctypes.data, enc_at=arrs[2].ctypes.data, enc_len=arrs[3].ctypes.data,
                  enc_src=arrs[4].ctypes.data, enc_rows=len(rets), grid=grid)
     bound = L.emu_lz4f_batch_bound(n, len(src), block_id, flags)
     assert bound >= sum(len(w) for w in want)
@@ -141,93 +98,6 @@ def emu_encode_batch(oracle, src, off, block_id=4, hc=False, flags=0, grid=0, ho
     for i, w in enumerate(want):
         assert got[got_off[i]:got_off[i + 1]] == w, (i, "not the frame of the item alone")
     return got, got_off.copy()
-
-
-def expect_items(oracle, items, slot_bytes, verify, dst_cap=None):
-    """what the one-frame decode gives for every item alone -> (records, contents, rows of all items, prefix sums of the contents)"""
-    recs, outs, rows = [], [], []
-    for it in items:
-        if it is None:
-            recs.append(dict(BAD_ITEM))
-            outs.append(b"")
-            continue
-        info, out, r = ref.read_frame(oracle, it, slot_bytes, 1 << 30, verify)
-        recs.append(info)
-        outs.append(out)
-        rows += r
-    ends = offsets_of(outs)
-    if dst_cap is not None:                                            # an item not wholly written: its content checksum is not looked at
-        for i, it in enumerate(items):
-            if it is not None and ends[i + 1] > dst_cap:
-                recs[i] = ref.read_frame(oracle, it, slot_bytes, 1 << 30, verify, -1)[0]
-    return recs, outs, rows, ends
-
-
-def expect_batch(recs, ends):
-    bad = [i for i, r in enumerate(recs) if r["error"] != ref.OK]
-    want = dict(items=len(recs), blocks=sum(r["blocks"] for r in recs), decoded_bytes=int(ends[-1]), first_error=-1, error_offset=-1, error=0, reserved=0)
-    if bad:
-        want.update(first_error=bad[0], error_offset=recs[bad[0]]["error_offset"], error=recs[bad[0]]["error"])
-    return want
-
-
-def standin(rows, count):
-    """the stand-in decoder's arrays for `count` table rows"""
-    dec_results, dec_len, dec_at, blob = np.zeros(count + 1, np.int32), np.zeros(count + 1, np.int32), np.zeros(count + 1, np.int64), []
-    at = 0
-    for k, (_, size, raw, badsum, res, data) in enumerate(rows[:count]):
-        dec_results[k], dec_len[k], dec_at[k] = res, 0 if raw or badsum else size, at
-        blob.append(data)
-        at += len(data)
-    return dec_results, dec_len, dec_at, u8(b"".join(blob) + b"\0")
-
-
-def check_decode_batch(oracle, src, off, slot=0, max_blocks=None, round_blocks=0, verify=3, dst_cap=None, grid=0):
-    """the emulator path on the batch against the twin reader on every item alone: every record field by field, the batch's record,
-    dst_off, written_items, the output bytes, nothing written outside them -> (records, contents, batch record)"""
-    src, off = bytes(src), np.ascontiguousarray(off, np.int64)
-    L, n = emu(), len(off) - 1
-    slot_bytes = slot or (4 << 20)
-    items = spans(src, off)
-    recs, outs, rows, ends = expect_items(oracle, items, slot_bytes, verify, dst_cap)
-    want = expect_batch(recs, ends)
-    if max_blocks is None:
-        max_blocks = max(len(rows), 1)
-    full = len(rows) > max_blocks
-    cap = int(ends[-1]) if dst_cap is None else dst_cap
-    arrs = standin(rows, max_blocks)
-    run = EmuRun(dec_results=arrs[0].ctypes.data, dec_len=arrs[1].ctypes.data, dec_at=arrs[2].ctypes.data, dec_bytes=arrs[3].ctypes.data,
-                 dec_rows=max_blocks, grid=grid)
-    a = Guarded(len(src))
-    a.a[:] = u8(src)
-    scratch = Guarded(L.emu_lz4f_batch_decode_scratch_bytes(n, slot, max_blocks, round_blocks))
-    dst, dst_off, item_info, written = Guarded(cap), Guarded(8 * (n + 1)), Guarded(C.sizeof(Lz4fInfo) * n), Guarded(8)
-    info = Lz4fBatchInfo()
-    rc = L.emu_lz4f_batch_decode(a.ptr, len(src), off.ctypes.data, n, slot, max_blocks, round_blocks, verify, scratch.ptr, scratch.n, dst.ptr, cap,
-                                 dst_off.ptr, item_info.ptr, C.byref(info), written.ptr, C.byref(run))
-    assert rc == 0, run.error
-    rounds = (max_blocks + (round_blocks or max_blocks) - 1) // (round_blocks or max_blocks)
-    assert run.shape_errors == 0 and run.calls == (rounds if n else 0)
-    assert scratch.intact() and dst.intact() and a.intact() and dst_off.intact() and item_info.intact() and written.intact()
-    got = {f: int(getattr(info, f)) for f in BATCH_FIELDS}
-    got_off = dst_off.a.view(np.int64)
-    if full:
-        assert got == dict(want, first_error=-1, error_offset=-1, error=ref.TABLE_FULL, decoded_bytes=0), got
-        assert (dst.a == GUARD).all() and (got_off == 0).all() and int(written.a.view(np.int64)[0]) == 0
-        got_recs = (Lz4fInfo * n).from_buffer_copy(item_info.a.tobytes())
-        assert all(r.error == ref.TABLE_FULL for r in got_recs)
-        return recs, outs, got
-    assert got == want, {f: (got[f], want[f]) for f in BATCH_FIELDS if got[f] != want[f]}
-    assert list(got_off) == list(ends)
-    got_recs = (Lz4fInfo * n).from_buffer_copy(item_info.a.tobytes()) if n else []
-    for i, (g, w) in enumerate(zip(got_recs, recs)):
-        g = {f: int(getattr(g, f)) for f in INFO_FIELDS}
-        assert g == w, (i, {f: (g[f], w[f]) for f in INFO_FIELDS if g[f] != w[f]})
-    content = b"".join(outs)[:cap]
-    assert dst.a[:len(content)].tobytes() == content
-    assert (dst.a[len(content):] == GUARD).all(), "bytes past the decoded ones were written"
-    assert int(written.a.view(np.int64)[0]) == sum(1 for e in ends[1:] if e <= cap), "written_items: the prefix of items wholly inside dst_cap"
-    return recs, outs, got
 
 
 # ---- every fault of test_gpu_lz4f.test_every_outcome_once, as items ------------------------------------------------------------------

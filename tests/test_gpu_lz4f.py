@@ -4,7 +4,6 @@ and lz4hip_lz4f_* of include/lz4hip.h): the checksum's row set against a from-th
 (tests/lz4f_ref.py) and compared byte for byte with the emulator path's, every outcome once, and one large frame.  The broken inputs
 only have bytes flipped or cut: the kernels answer with statuses."""
 import base64
-import ctypes as C
 import json
 import os
 
@@ -14,7 +13,8 @@ import pytest
 import lz4f_ref as ref
 from gpu_helpers import dev, host
 from lz4f_cases import LENGTHS, emu_encode, flip, mixed, sample
-from lz4net_amd import _lib, batch, lz4_frame as lz
+from lz4f_gpu import frame_call
+from lz4net_amd import batch, lz4_frame as lz
 from lz4net_amd.codec import ArgumentException
 
 pytestmark = pytest.mark.gpu
@@ -84,7 +84,7 @@ def test_round_trips_every_flag_combination(oracle, flags):
         src = sample(oracle, 2, n)
         frame = host(lz.compress_frame_device(dev(src), **opts))
         assert frame == ref.write_frame(oracle, src, 4, False, flags)[0], (n, "not the twin writer's frame")
-        info, out, _ = ref.read_frame(oracle, frame)
+        info, out, _, _ = ref.read_frame(oracle, frame)
         assert info["error"] == ref.OK and out == src and info["frame_bytes"] == len(frame)
         assert host(lz.decompress_frame_device(dev(frame))) == src
         assert lz.compress_frame_host(src, **opts) == frame and lz.decompress_frame_host(frame) == src
@@ -111,30 +111,12 @@ def test_block_sizes_mixed_blocks_and_the_emulator_path_s_bytes(oracle, block_si
     assert host(lz.decompress_frame_device(dev(frame))) == src and lz.decompress_frame_host(frame) == src
 
 
-def decode_call(frame, slot=0, max_blocks=8, round_blocks=0, flags=3, dst_cap=None, room=1 << 19):
-    """lz4hip_lz4f_decode_device -> (info, the output buffer's first dst_cap bytes); asserts nothing past dst_cap was written"""
-    import torch
-    L = _lib.lib()
-    t = dev(frame) if len(frame) else torch.empty(0, dtype=torch.uint8, device="cuda")
-    cap = room if dst_cap is None else dst_cap
-    need = L.lz4hip_lz4f_decode_scratch_bytes(slot, max_blocks, round_blocks)
-    assert need > 0
-    scratch = torch.empty(need, dtype=torch.uint8, device="cuda")
-    out = torch.full((cap + 64,), 0xA7, dtype=torch.uint8, device="cuda")
-    info_dev = torch.zeros(C.sizeof(_lib.Lz4fInfo), dtype=torch.uint8, device="cuda")
-    assert L.lz4hip_lz4f_decode_device(t.data_ptr(), t.numel(), slot, max_blocks, round_blocks, flags, scratch.data_ptr(), need, out.data_ptr(), cap,
-                                       info_dev.data_ptr(), torch.cuda.current_stream().cuda_stream) == 0
-    info = _lib.Lz4fInfo.from_buffer_copy(host(info_dev))
-    raw = host(out)
-    assert raw[cap:] == b"\xA7" * 64, "bytes past dst_cap were written"
-    return info, raw[:cap]
-
-
-def check_against_twin(oracle, frame, **kw):
-    info, raw = decode_call(frame, **kw)
-    want, out, _ = ref.read_frame(oracle, frame, kw.get("slot", 0) or 4 << 20, kw.get("max_blocks", 8), kw.get("flags", 3), kw.get("dst_cap"))
-    got = {f: int(getattr(info, f)) for f, _ in _lib.Lz4fInfo._fields_}
+def check_against_twin(oracle, frame, slot=0, max_blocks=8, round_blocks=0, flags=3, dst_cap=None, room=1 << 19):
+    """lz4hip_lz4f_decode_device against the twin: the record field by field, the bytes, and the 0xA7 fill behind them and past dst_cap"""
+    got, dst = frame_call(frame, slot, flags, room if dst_cap is None else dst_cap, max_blocks, round_blocks)
+    want, out, _, _ = ref.read_frame(oracle, frame, slot or 4 << 20, max_blocks, flags, dst_cap)
     assert got == want, {f: (got[f], want[f]) for f in got if got[f] != want[f]}
+    raw = dst.tobytes()
     assert raw[:len(out)] == out and raw[len(out):] == b"\xA7" * (len(raw) - len(out))
     return want
 

@@ -4,26 +4,23 @@ byte for byte against compress_frame_device of every item alone, batch decode fi
 every item alone, at the small shapes of tests/test_simt_lz4f_batch.py; then the frames liblz4 wrote as one batch, 4 100 tiny items and
 one round trip of 1 024 items of 64 KiB.  The broken inputs only have bytes flipped or cut: the kernels answer with statuses."""
 import ctypes as C
+import types
 
 import numpy as np
 import pytest
 
+import lz4f_gpu as gpu
 import lz4f_ref as ref
 from gpu_helpers import dev, host, i64, s0
-from lz4f_batch_cases import golden_batch, offsets_of, outcome_items, sources, tiny_items
-from lz4f_cases import sample
+from lz4f_batch_cases import golden_batch, outcome_items, sources, tiny_items
+from lz4f_cases import INFO_FIELDS, offsets_of, sample
+from lz4f_gpu import dev_bytes
 from lz4net_amd import _lib, batch, lz4_frame as lz
 from lz4net_amd.codec import ArgumentException
 
 pytestmark = pytest.mark.gpu
 
-INFO_FIELDS = [f for f, _ in _lib.Lz4fInfo._fields_]
 E_ARGUMENT = _lib.E_ARGUMENT
-
-
-def dev_bytes(b):
-    import torch
-    return dev(b) if len(b) else torch.empty(0, dtype=torch.uint8, device="cuda")
 
 
 def options(flags):
@@ -48,46 +45,21 @@ def encode_call(src, off, block_id=4, mode=0, flags=0):
     return raw[:int(got_off[n])], got_off
 
 
-def frame_call(frame, slot, flags=3, max_blocks=8):
+def item_alone(frame, slot, flags=3, max_blocks=8):
     """lz4hip_lz4f_decode_device on one item alone, with a table and a dst_cap that hold it -> (record as a dict, its bytes)"""
-    import torch
-    L = _lib.lib()
-    t = dev_bytes(frame)
-    cap = 1 << 19
-    need = L.lz4hip_lz4f_decode_scratch_bytes(slot, max_blocks, 0)
-    scratch = torch.empty(need, dtype=torch.uint8, device="cuda")
-    out = torch.empty(cap, dtype=torch.uint8, device="cuda")
-    info_dev = torch.zeros(C.sizeof(_lib.Lz4fInfo), dtype=torch.uint8, device="cuda")
-    assert L.lz4hip_lz4f_decode_device(t.data_ptr(), t.numel(), slot, max_blocks, 0, flags, scratch.data_ptr(), need, out.data_ptr(), cap, info_dev.data_ptr(),
-                                       s0()) == 0
-    info = _lib.Lz4fInfo.from_buffer_copy(host(info_dev))
-    assert info.error != ref.TABLE_FULL and info.decoded_bytes <= cap
-    return {f: int(getattr(info, f)) for f in INFO_FIELDS}, host(out[:int(info.decoded_bytes)])
+    info, dst = gpu.frame_call(frame, slot, flags, 1 << 19, max_blocks)
+    assert info["error"] != ref.TABLE_FULL and info["decoded_bytes"] <= 1 << 19
+    return info, dst[:info["decoded_bytes"]].tobytes()
 
 
 def decode_call(blob, off, slot=65536, max_blocks=64, round_blocks=0, flags=3, dst_cap=None, room=1 << 21):
     """lz4hip_lz4f_batch_decode_device -> (records as dicts, batch record, dst_off, written_items, the first dst_cap bytes of the
     output); asserts that the 0xA7 fill past dst_cap is intact"""
-    import torch
-    L = _lib.lib()
-    n = len(off) - 1
-    t, o = dev_bytes(blob), i64(off)
     cap = room if dst_cap is None else dst_cap
-    need = L.lz4hip_lz4f_batch_decode_scratch_bytes(n, slot, max_blocks, round_blocks)
-    assert need > 0
-    scratch = torch.empty(need, dtype=torch.uint8, device="cuda")
-    out = torch.full((cap + 64,), 0xA7, dtype=torch.uint8, device="cuda")
-    out_off = torch.zeros(n + 1, dtype=torch.int64, device="cuda")
-    recs_dev = torch.zeros(C.sizeof(_lib.Lz4fInfo) * max(n, 1), dtype=torch.uint8, device="cuda")
-    info_dev = torch.zeros(C.sizeof(_lib.Lz4fBatchInfo), dtype=torch.uint8, device="cuda")
-    written = torch.full((1,), -1, dtype=torch.int64, device="cuda")
-    assert L.lz4hip_lz4f_batch_decode_device(t.data_ptr(), len(blob), o.data_ptr(), n, slot, max_blocks, round_blocks, flags, scratch.data_ptr(), need,
-                                             out.data_ptr(), cap, out_off.data_ptr(), recs_dev.data_ptr(), info_dev.data_ptr(), written.data_ptr(), s0()) == 0
-    info = _lib.Lz4fBatchInfo.from_buffer_copy(host(info_dev))
-    recs = (_lib.Lz4fInfo * max(n, 1)).from_buffer_copy(host(recs_dev))
-    raw = host(out)
-    assert raw[cap:] == b"\xA7" * 64, "bytes past dst_cap were written"
-    return [{f: int(getattr(r, f)) for f in INFO_FIELDS} for r in recs[:n]], info, out_off.cpu().numpy(), int(written.item()), raw[:cap]
+    info, recs, dst_off, dst, written = gpu.batch_call(blob, slot, max_blocks, round_blocks, flags, cap, off=off)
+    raw = dst.tobytes()
+    assert raw[cap:] == b"\xA7" * gpu.PAD, "bytes past dst_cap were written"
+    return recs, types.SimpleNamespace(**info), dst_off, written, raw[:cap]
 
 
 def check_against_one_frame_calls(items, slot=65536, one_frame_blocks=8, **kw):
@@ -97,7 +69,7 @@ def check_against_one_frame_calls(items, slot=65536, one_frame_blocks=8, **kw):
     flags, cap = kw.get("flags", 3), len(raw)                        # (dst_cap, or the room the call was given)
     outs = []
     for i, item in enumerate(items):
-        want, out = frame_call(item, slot, flags, one_frame_blocks)
+        want, out = item_alone(item, slot, flags, one_frame_blocks)
         if dst_off[i + 1] > cap and (want["checks"] >> 2) == ref.VERIFIED:      # not wholly written: present but not checked
             want = dict(want, checks=(want["checks"] & 3) | ref.SKIPPED << 2)
             if want["error"] == ref.CONTENT_CHECKSUM:
@@ -253,7 +225,7 @@ def test_4100_tiny_items():
     frames, frame_off = lz.compress_frames_device(dev(src), i64(off), block_checksum=True, content_checksum=True)
     f, fo = host(frames), frame_off.cpu().numpy()
     for i in (0, 1, 4095, 4096, 4099):
-        want, out = frame_call(f[fo[i]:fo[i + 1]], 65536)
+        want, out = item_alone(f[fo[i]:fo[i + 1]], 65536)
         assert want["error"] == 0 and out == items[i] and want["checks"] == 5
     data, data_off = lz.decompress_frames_device(frames, frame_off, max_blocks=len(items))
     assert host(data) == src and bool(torch.equal(data_off.cpu(), torch.from_numpy(off)))

@@ -1,103 +1,33 @@
 """GPU: LZ4 frames with a dictionary decoded on the device (lz4hip_lz4f_decode_dict_* and lz4hip_lz4f_batch_decode_dict_* of
 include/lz4hip.h, dictionary=... on the Python calls of lz4net_amd/lz4_frame.py), with the real block decoders, against the twin
-tests/lz4f_dict_ref.py field by field: the hand-built frames, the frames liblz4 wrote with LZ4F_compressFrame_usingCDict, the mixed
+tests/lz4f_ref.py field by field: the hand-built frames, the frames liblz4 wrote with LZ4F_compressFrame_usingCDict, the mixed
 batch of tests/test_simt_lz4f_dict.py, and one batch in which many wavefronts run the ordered decode at once.  Every output buffer is
 filled with 0xA7 first and starts at the very start of its allocation, and what the call was not to write is still 0xA7 afterwards; the
 dictionary lies between guard bytes, at an even or an odd address."""
 import ctypes as C
+import functools
 
 import numpy as np
 import pytest
 
-import lz4f_dict_ref as dr
+import lz4f_built as built
+import lz4f_cases as cases
+import lz4f_gpu as gpu
 import lz4f_ref as ref
-from gpu_helpers import FILL as DICT_FILL, GUARD as DICT_GUARD, dev, guarded, host, i64, s0
-from lz4f_batch_cases import BATCH_FIELDS, INFO_FIELDS, expect_batch, offsets_of
-from lz4f_dict_cases import (ACCEPT, GOLDEN_DICT_ID, check_image, check_records, dictionary, expect, golden, golden_dictionary, hand_built, mixed_batch,
-                             records_of)
+from gpu_helpers import dev, host, i64
+from lz4f_cases import ACCEPT, INFO_FIELDS, check_image, offsets_of
+from lz4f_dict_cases import GOLDEN_DICT_ID, dictionary, golden, golden_dictionary, hand_built, mixed_batch
+from lz4f_gpu import FILL, PAD, DeviceDict, batch_call, frame_call
 from lz4net_amd import _lib, lz4_frame as lz
 from lz4net_amd.codec import ArgumentException
 
 pytestmark = pytest.mark.gpu
 
-FILL, PAD = 0xA7, 64
-
-
-class DeviceDict:
-    """the dictionary between guard bytes on the device, at an even (odd = 0) or odd address"""
-    def __init__(self, d, odd=0):
-        import torch
-        self.raw = guarded(len(d) + 1)
-        self.at, self.n = DICT_GUARD + odd, len(d)
-        self.raw[self.at:self.at + self.n] = torch.from_numpy(np.frombuffer(bytes(d), np.uint8).copy()).cuda()
-        self.tensor = self.raw[self.at:self.at + self.n]
-        self.ptr = self.raw.data_ptr() + self.at
-
-    def intact(self):
-        raw, end = host(self.raw), self.at + self.n
-        return raw[:self.at] == bytes([DICT_FILL]) * self.at and raw[end:] == bytes([DICT_FILL]) * (len(raw) - end)
-
-
-def batch_call(frames, dd, dict_id, slot=65536, max_blocks=64, round_blocks=0, flags=3 | ACCEPT, cap=0, plain=False):
-    """lz4hip_lz4f_batch_decode_dict_device (plain: lz4hip_lz4f_batch_decode_device) -> (batch record, item records, dst_off, cap + PAD
-    bytes of dst, written_items)"""
-    import torch
-    L = _lib.lib()
-    n = len(frames)
-    blob = b"".join(frames)
-    t, o = dev(blob), i64(offsets_of(frames))
-    need = L.lz4hip_lz4f_batch_decode_scratch_bytes(n, slot, max_blocks, round_blocks)
-    assert need > 0
-    scratch = torch.empty(need, dtype=torch.uint8, device="cuda")
-    out = torch.full((cap + PAD,), FILL, dtype=torch.uint8, device="cuda")
-    out_off = torch.zeros(n + 1, dtype=torch.int64, device="cuda")
-    recs_dev = torch.zeros(C.sizeof(_lib.Lz4fInfo) * n, dtype=torch.uint8, device="cuda")
-    info_dev = torch.zeros(C.sizeof(_lib.Lz4fBatchInfo), dtype=torch.uint8, device="cuda")
-    written = torch.full((1,), -1, dtype=torch.int64, device="cuda")
-    if plain:
-        rc = L.lz4hip_lz4f_batch_decode_device(t.data_ptr(), len(blob), o.data_ptr(), n, slot, max_blocks, round_blocks, flags, scratch.data_ptr(), need,
-                                               out.data_ptr(), cap, out_off.data_ptr(), recs_dev.data_ptr(), info_dev.data_ptr(), written.data_ptr(), s0())
-    else:
-        rc = L.lz4hip_lz4f_batch_decode_dict_device(t.data_ptr(), len(blob), o.data_ptr(), n, dd.ptr if dd else None, dd.n if dd else 0, dict_id, slot,
-                                                    max_blocks, round_blocks, flags, scratch.data_ptr(), need, out.data_ptr(), cap, out_off.data_ptr(),
-                                                    recs_dev.data_ptr(), info_dev.data_ptr(), written.data_ptr(), s0())
-    assert rc == 0, L.lz4hip_last_error()
-    info = _lib.Lz4fBatchInfo.from_buffer_copy(host(info_dev))
-    assert dd is None or dd.intact()
-    return ({f: int(getattr(info, f)) for f in BATCH_FIELDS}, records_of(host(recs_dev), n), out_off.cpu().numpy(), out.cpu().numpy(), int(written.item()))
-
-
-def check_batch(frames, d, dict_id=0, slot=65536, round_blocks=0, verify=3, dst_cap=None, odd=0):
-    """the device call against the twin -> (records, batch record)"""
-    frames = list(frames)
-    recs, outs, ends, cap = expect(frames, d, dict_id, slot, verify, dst_cap)
-    got, got_recs, got_off, dst, written = batch_call(frames, DeviceDict(d, odd), dict_id, slot, max(sum(r["blocks"] for r in recs), 1) + 3, round_blocks,
-                                                      verify | ACCEPT, cap)
-    want = expect_batch(recs, ends)
-    assert got == want, {f: (got[f], want[f]) for f in BATCH_FIELDS if got[f] != want[f]}
-    assert list(got_off) == list(ends)
-    check_records(got_recs, recs)
-    check_image(dst, outs, ends, cap, FILL)
-    assert written == sum(1 for e in ends[1:] if e <= cap)
-    return recs, got
-
-
-def frame_call(frame, dd, dict_id, slot, flags, cap, max_blocks=16):
-    """lz4hip_lz4f_decode_dict_device -> (record, cap + PAD bytes of dst)"""
-    import torch
-    L = _lib.lib()
-    t = dev(frame)
-    need = L.lz4hip_lz4f_decode_scratch_bytes(slot, max_blocks, 0)
-    scratch = torch.empty(need, dtype=torch.uint8, device="cuda")
-    out = torch.full((cap + PAD,), FILL, dtype=torch.uint8, device="cuda")
-    info_dev = torch.zeros(C.sizeof(_lib.Lz4fInfo), dtype=torch.uint8, device="cuda")
-    assert L.lz4hip_lz4f_decode_dict_device(t.data_ptr(), t.numel(), dd.ptr if dd else None, dd.n if dd else 0, dict_id, slot, max_blocks, 0, flags,
-                                            scratch.data_ptr(), need, out.data_ptr(), cap, info_dev.data_ptr(), s0()) == 0
-    return records_of(host(info_dev), 1)[0], out.cpu().numpy()
+check_batch = functools.partial(gpu.check_batch, None)                # the _dict_ call: no codec, every block is the twin's own to decode
 
 
 @pytest.mark.parametrize("odd", [0, 1])
-@pytest.mark.parametrize("n", dr.DICT_LENGTHS)
+@pytest.mark.parametrize("n", built.DICT_LENGTHS)
 def test_hand_built_frames_through_the_batch_call(n, odd):
     """every case the dictionary's length allows, each once as item 0 (at the very start of the output's allocation), then all as one batch"""
     cases, d = hand_built(n), dictionary(n)
@@ -108,15 +38,15 @@ def test_hand_built_frames_through_the_batch_call(n, odd):
         assert (recs[0]["error"] == ref.OK) == (content is not None), name
         if content is None:
             assert recs[0]["error"] == ref.CORRUPT_BLOCK and recs[0]["good_bytes"] == (1000 if name.startswith("l") else 100), name
-    recs, got = check_batch([dr.front_item()] + [cases[k][0] for k in names] + [dr.front_item()], d, odd=odd, round_blocks=3)
+    recs, got = check_batch([built.front_item()] + [cases[k][0] for k in names] + [built.front_item()], d, odd=odd, round_blocks=3)
     assert [r["error"] == ref.OK for r in recs[1:-1]] == [cases[k][1] is not None for k in names] and recs[0]["error"] == recs[-1]["error"] == ref.OK
 
 
-@pytest.mark.parametrize("dict_id,frame_id,error", [(7, 7, ref.OK), (7, 8, dr.DICT_ID_MISMATCH), (0, 8, ref.OK), (7, None, ref.OK)])
+@pytest.mark.parametrize("dict_id,frame_id,error", [(7, 7, ref.OK), (7, 8, ref.DICT_ID_MISMATCH), (0, 8, ref.OK), (7, None, ref.OK)])
 def test_the_dictionary_id(dict_id, frame_id, error):
     d = dictionary(13)
     frames = [hand_built(13, frame_id)[name][0] for name in ("i_into_the_block", "l_run_fill")]
-    frames.append(dr.lk.frame_of([(b"0123456789", True)], linked=False, flags=ref.F_CONTENT_SIZE, content=b"0123456789", dict_id=frame_id))
+    frames.append(built.frame_of([(b"0123456789", True)], linked=False, flags=ref.F_CONTENT_SIZE, content=b"0123456789", dict_id=frame_id))
     recs, _ = check_batch(frames, d, dict_id)
     assert [r["error"] for r in recs] == [error] * 3
     if error:
@@ -133,10 +63,10 @@ def test_golden_frames_as_one_batch(round_blocks):
 @pytest.mark.parametrize("round_blocks", [0, 2])
 def test_mixed_batch_whole_and_clipped(round_blocks):
     frames, d, dict_id, linked = mixed_batch()
-    _, _, ends, total = expect(list(frames), d, dict_id)
+    _, _, _, ends, total = cases.expect(None, list(frames), 65536, 3, accept=True, dictionary=d, dict_id=dict_id)
     for cap in (total, 0, int(ends[linked]) + 10 + 30, int(ends[linked]) + 10 + 54):   # ... inside, and at the end of, the linked item's second block
         recs, got = check_batch(frames, d, dict_id, round_blocks=round_blocks, dst_cap=cap, odd=1)
-        assert [r["error"] for r in recs] == [0, 0, 0, 0, dr.DICT_ID_MISMATCH] and got["first_error"] == 4
+        assert [r["error"] for r in recs] == [0, 0, 0, 0, ref.DICT_ID_MISMATCH] and got["first_error"] == 4
 
 
 def test_the_one_frame_call_the_host_calls_and_the_python_calls_on_every_golden_frame():
@@ -144,8 +74,8 @@ def test_the_one_frame_call_the_host_calls_and_the_python_calls_on_every_golden_
     d = golden_dictionary()
     dd = DeviceDict(d, 1)
     for rec, frame, src in zip(golden_recs, frames, srcs):
-        want, out, unspecified = dr.read_frame_dict(frame, d, GOLDEN_DICT_ID)
-        got, dst = frame_call(frame, dd, GOLDEN_DICT_ID, 65536, 3 | ACCEPT, len(src))
+        want, out, unspecified, _ = ref.read_frame(None, frame, 65536, accept_linked=True, dictionary=d, dict_id=GOLDEN_DICT_ID)
+        got, dst = frame_call(frame, 65536, 3 | ACCEPT, len(src), dd=dd, dict_id=GOLDEN_DICT_ID)
         assert got == want, {f: (got[f], want[f]) for f in INFO_FIELDS if got[f] != want[f]}
         check_image(dst, [(out, unspecified)], [0, len(src)], len(src), FILL)
         assert out == src
@@ -189,13 +119,13 @@ def test_many_wavefronts_run_the_ordered_decode_at_once():
 
 def test_without_a_dictionary_the_call_is_the_plain_call():
     frames, d, _, _ = mixed_batch()
-    frames = [dr.front_item()] + list(frames)
+    frames = [built.front_item()] + list(frames)
     for flags in (3, 3 | ACCEPT):
-        plain = batch_call(frames, None, 0, max_blocks=16, round_blocks=2, flags=flags, cap=4096, plain=True)
-        none = batch_call(frames, None, 99, max_blocks=16, round_blocks=2, flags=flags, cap=4096)
+        plain = batch_call(frames, max_blocks=16, round_blocks=2, flags=flags, cap=4096)
+        none = batch_call(frames, max_blocks=16, round_blocks=2, flags=flags, cap=4096, dict_id=99, dict_call=True)
         assert plain[:2] == none[:2] and list(plain[2]) == list(none[2]) and (plain[3] == none[3]).all() and plain[4] == none[4]
         assert plain[1][1]["error"] == ref.UNSUPPORTED_DICT
-    got, dst = frame_call(frames[1], None, 5, 65536, 3, 64)
+    got, dst = frame_call(frames[1], 65536, 3, 64, dict_id=5, dict_call=True)
     assert got["error"] == ref.UNSUPPORTED_DICT and got["error_offset"] == 4 and (dst == FILL).all()
     L = _lib.lib()
     info = _lib.Lz4fInfo()
@@ -206,9 +136,9 @@ def test_without_a_dictionary_the_call_is_the_plain_call():
 
 def test_the_existing_calls_still_refuse_a_frame_with_a_dictionary_id():
     frames, d, _, _ = mixed_batch()
-    got, recs, off, dst, written = batch_call([dr.front_item(), frames[0]], None, 0, flags=3 | ACCEPT, cap=4096, plain=True)
+    got, recs, off, dst, written = batch_call([built.front_item(), frames[0]], flags=3 | ACCEPT, cap=4096)
     assert got["error"] == ref.UNSUPPORTED_DICT and got["first_error"] == 1 and list(off) == [0, 37, 37]
-    assert dst[:37].tobytes() == dr.FRONT and (dst[37:] == FILL).all()
+    assert dst[:37].tobytes() == built.FRONT and (dst[37:] == FILL).all()
     with pytest.raises(ArgumentException, match="frames with a dictionary ID are not supported"):
         lz.decompress_frame_device(dev(frames[0]))
     with pytest.raises(ArgumentException, match="frames with a dictionary ID are not supported"):

@@ -1,81 +1,35 @@
 """GPU: LZ4 frames with linked blocks decoded on the device (LZ4HIP_LZ4F_ACCEPT_LINKED on the lz4hip_lz4f_decode_* and
 lz4hip_lz4f_batch_decode_* calls of include/lz4hip.h, accept_linked=True on the Python calls of lz4net_amd/lz4_frame.py), with the real
-block codecs, against the twin tests/lz4f_linked_ref.py field by field: the hand-built frames, the frames liblz4 wrote, the mixed batch
+block codecs, against the twin tests/lz4f_ref.py field by field: the hand-built frames, the frames liblz4 wrote, the mixed batch
 of tests/test_simt_lz4f_linked.py, and one batch in which many wavefronts run the ordered decode at once.  Every output buffer is
 filled with 0xA7 first, and what the call was not to write is still 0xA7 afterwards."""
 import ctypes as C
+import functools
 
 import numpy as np
 import pytest
 
-import lz4f_linked_ref as lk
+import lz4f_built as built
+import lz4f_cases as cases
 import lz4f_ref as ref
-from gpu_helpers import dev, host, i64, s0
-from lz4f_batch_cases import BATCH_FIELDS, INFO_FIELDS, expect_batch, offsets_of
-from lz4f_linked_cases import ACCEPT, check_image, check_records, expect, golden, hand_built, mixed_batch, records_of
+from gpu_helpers import dev, host, i64
+from lz4f_cases import ACCEPT, INFO_FIELDS, check_image, check_records, offsets_of, records_of
+from lz4f_gpu import FILL, PAD, batch_call, check_batch, frame_call
+from lz4f_linked_cases import golden, hand_built, mixed_batch
 from lz4net_amd import _lib, lz4_frame as lz
 from lz4net_amd.codec import ArgumentException
 
 pytestmark = pytest.mark.gpu
 
-FILL, PAD = 0xA7, 64
+expect = functools.partial(cases.expect, accept=True)                 # what the twin says of a batch decoded with the flag
 
 
-def batch_call(frames, slot=65536, max_blocks=64, round_blocks=0, flags=3 | ACCEPT, cap=0):
-    """lz4hip_lz4f_batch_decode_device -> (batch record, item records, dst_off, cap + PAD bytes of dst, written_items)"""
-    import torch
-    L = _lib.lib()
-    n = len(frames)
-    blob = b"".join(frames)
-    t, o = dev(blob), i64(offsets_of(frames))
-    need = L.lz4hip_lz4f_batch_decode_scratch_bytes(n, slot, max_blocks, round_blocks)
-    assert need > 0
-    scratch = torch.empty(need, dtype=torch.uint8, device="cuda")
-    out = torch.full((cap + PAD,), FILL, dtype=torch.uint8, device="cuda")
-    out_off = torch.zeros(n + 1, dtype=torch.int64, device="cuda")
-    recs_dev = torch.zeros(C.sizeof(_lib.Lz4fInfo) * n, dtype=torch.uint8, device="cuda")
-    info_dev = torch.zeros(C.sizeof(_lib.Lz4fBatchInfo), dtype=torch.uint8, device="cuda")
-    written = torch.full((1,), -1, dtype=torch.int64, device="cuda")
-    assert L.lz4hip_lz4f_batch_decode_device(t.data_ptr(), len(blob), o.data_ptr(), n, slot, max_blocks, round_blocks, flags, scratch.data_ptr(), need,
-                                             out.data_ptr(), cap, out_off.data_ptr(), recs_dev.data_ptr(), info_dev.data_ptr(), written.data_ptr(), s0()) == 0
-    info = _lib.Lz4fBatchInfo.from_buffer_copy(host(info_dev))
-    return ({f: int(getattr(info, f)) for f in BATCH_FIELDS}, records_of(host(recs_dev), n), out_off.cpu().numpy(), out.cpu().numpy(), int(written.item()))
-
-
-def check_batch(oracle, frames, slot=65536, round_blocks=0, verify=3, dst_cap=None):
-    """the device call with the flag against the twin -> (records, batch record)"""
-    frames = list(frames)
-    recs, outs, rows, ends, cap = expect(oracle, frames, slot, verify, dst_cap)
-    got, got_recs, got_off, dst, written = batch_call(frames, slot, max(len(rows), 1) + 3, round_blocks, verify | ACCEPT, cap)
-    want = expect_batch(recs, ends)
-    assert got == want, {f: (got[f], want[f]) for f in BATCH_FIELDS if got[f] != want[f]}
-    assert list(got_off) == list(ends)
-    check_records(got_recs, recs)
-    check_image(dst, outs, ends, cap, FILL)
-    assert written == sum(1 for e in ends[1:] if e <= cap)
-    return recs, got
-
-
-def frame_call(frame, slot, flags, cap, max_blocks=16):
-    """lz4hip_lz4f_decode_device -> (record, cap + PAD bytes of dst)"""
-    import torch
-    L = _lib.lib()
-    t = dev(frame)
-    need = L.lz4hip_lz4f_decode_scratch_bytes(slot, max_blocks, 0)
-    scratch = torch.empty(need, dtype=torch.uint8, device="cuda")
-    out = torch.full((cap + PAD,), FILL, dtype=torch.uint8, device="cuda")
-    info_dev = torch.zeros(C.sizeof(_lib.Lz4fInfo), dtype=torch.uint8, device="cuda")
-    assert L.lz4hip_lz4f_decode_device(t.data_ptr(), t.numel(), slot, max_blocks, 0, flags, scratch.data_ptr(), need, out.data_ptr(), cap, info_dev.data_ptr(),
-                                       s0()) == 0
-    return records_of(host(info_dev), 1)[0], out.cpu().numpy()
-
-
-@pytest.mark.parametrize("name", sorted(lk.hand_built()))
+@pytest.mark.parametrize("name", sorted(hand_built()))
 def test_hand_built_frames_alone_and_behind_another_item(oracle, name):
     frame, content, bad = hand_built()[name]
     recs, _ = check_batch(oracle, [frame])
     assert (recs[0]["error"] == ref.OK) == (content is not None)
-    recs, got = check_batch(oracle, [lk.front_item(), frame, lk.front_item()], round_blocks=2)
+    recs, got = check_batch(oracle, [built.front_item(), frame, built.front_item()], round_blocks=2)
     assert recs[0]["error"] == recs[2]["error"] == ref.OK and got["first_error"] == (-1 if content is not None else 1)
 
 
@@ -99,7 +53,7 @@ def test_the_one_frame_call_and_the_python_calls_on_every_golden_frame(oracle):
     names, golden_recs, frames, srcs = golden(oracle)
     for rec, frame, src in zip(golden_recs, frames, srcs):
         slot = ref.block_bytes(rec["block_id"])
-        want, out, unspecified, _ = lk.read_frame_linked(oracle, frame, slot)
+        want, out, unspecified, _ = ref.read_frame(oracle, frame, slot, accept_linked=True)
         got, dst = frame_call(frame, slot, 3 | ACCEPT, len(src))
         assert got == want, {f: (got[f], want[f]) for f in INFO_FIELDS if got[f] != want[f]}
         check_image(dst, [(out, unspecified)], [0, len(src)], len(src), FILL)
@@ -148,9 +102,9 @@ def test_without_the_flag_a_linked_frame_is_still_refused(oracle):
     frame = golden(oracle)[2][0]
     got, dst = frame_call(frame, 262144, 3, 1 << 17)
     assert got["error"] == ref.UNSUPPORTED_LINKED and got["decoded_bytes"] == 0 and (dst == FILL).all()
-    got, recs, off, dst, written = batch_call([lk.front_item(), frame], flags=3, cap=4096)
+    got, recs, off, dst, written = batch_call([built.front_item(), frame], flags=3, cap=4096)
     assert got["error"] == ref.UNSUPPORTED_LINKED and got["first_error"] == 1 and list(off) == [0, 37, 37]
-    assert dst[:37].tobytes() == lk.FRONT and (dst[37:] == FILL).all()
+    assert dst[:37].tobytes() == built.FRONT and (dst[37:] == FILL).all()
     with pytest.raises(ArgumentException, match="frames with linked blocks are not supported"):
         lz.decompress_frame_device(dev(frame))
     with pytest.raises(ArgumentException, match="frames with linked blocks are not supported"):

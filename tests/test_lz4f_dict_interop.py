@@ -4,14 +4,18 @@ tests/test_simt_lz4f_dict.py; that test never skips.  Here, where liblz4 is inst
 downloaded), the same 24 shapes and a 150 000-byte source are written FRESH -- 32 combinations -- and go through the twin and the
 emulator path (the library's kernels and sequences, tests/simt/emu_lz4f_dict.inc); these tests, and only these, skip where the library
 or its dictionary calls are absent."""
+import functools
 import os
 
 import pytest
 
 import lz4f_dict_lib
 import lz4f_ref as ref
-from lz4f_dict_cases import GOLDEN, GOLDEN_DICT_ID, check_frame, golden, golden_dictionary, golden_source
+from lz4f_cases import DICT, check_frame
+from lz4f_dict_cases import GOLDEN, GOLDEN_DICT_ID, golden, golden_dictionary, golden_source
 from lz4net_amd import lz4_frame
+
+check_frame = functools.partial(check_frame, DICT, None, accept=True)
 
 needs_liblz4 = pytest.mark.skipif(lz4f_dict_lib.load() is None, reason="liblz4 >= 1.8.0 with LZ4F_compressFrame_usingCDict is not installed")
 

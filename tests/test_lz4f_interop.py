@@ -5,6 +5,7 @@ ctypes.util.find_library; nothing is downloaded) fresh frames at levels 0 and 9 
 path's frames go through LZ4F_decompress, which must consume every byte, and the descriptors are compared; those tests, and only those,
 skip where the library is absent."""
 import base64
+import functools
 import json
 import os
 
@@ -12,8 +13,10 @@ import pytest
 
 import lz4f_lib
 import lz4f_ref as ref
-from lz4f_cases import check_decode, emu_encode, mixed, sample
+from lz4f_cases import PLAIN, check_frame, emu_encode, mixed, sample
 from lz4net_amd import lz4_frame
+
+check_decode = functools.partial(check_frame, PLAIN, slot=0, max_blocks=8)   # the plain one-frame call, a table of 8 rows
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "lz4f_frames.json")
 with open(GOLDEN) as _f:

@@ -136,7 +136,7 @@ def test_dict_len_zero_is_the_plain_call(oracle):
 def test_sizes_walk_with_the_dictionary_length(oracle, name):
     """lz4hip_decoded_sizes_dict_device's sequence: a block's size is what its unknown-size decode against the dictionary produces with
     room to spare, or the walk's refusal of a source before the dictionary"""
-    import lz4f_linked_ref as linked
+    import lz4f_ref
     f = cases.family(name)
     L = cases.emu()
     for dict_len, idx in sorted(cases.groups(f).items()):
@@ -154,7 +154,7 @@ def test_sizes_walk_with_the_dictionary_length(oracle, name):
         rc = L.emu_dict_sizes(C.byref(b), C.c_int64(dict_len), C.c_void_p(offs.ctypes.data), C.c_void_p(caps.ctypes.data), C.c_void_p(scratch.ctypes.data),
                               C.c_int64(need), C.byref(info), 1, err)
         assert rc == 0, err.value
-        want = [linked.size_block(bytes(r), history=min(dict_len, cases.REACH)) for r in rows]
+        want = [lz4f_ref.size_block(bytes(r), history=min(dict_len, cases.REACH)) for r in rows]
         assert list(res) == want, (name, dict_len)
         assert list(caps) == [max(w, 0) for w in want] and list(offs) == list(np.concatenate(([0], np.cumsum([max(w, 0) for w in want]))))
         for j, w in zip(idx, want):
@@ -218,12 +218,12 @@ def test_host_call_uploads_the_dictionary_once(oracle, dict_len, slices, known):
 def test_fixture_blocks_decode_to_their_records():
     """tests/golden/dict_blocks.json (LZ4_loadDict + LZ4_compress_fast_continue) under the emulator, known and unknown size, against the
     records' plain text; the twin first, and a live liblz4 where there is one"""
-    import lz4f_linked_ref as linked
+    import lz4f_ref
     dic, records, header = cases.load_fixture()
     assert len(records) >= 40 and max(len(p) for p, _ in records) <= 4096 and header["dictionary"]["length"] == dic.size
     lz4 = cases.liblz4()
     for plain, block in records:
-        assert linked.decode_block(block, len(plain), history=dic.tobytes()[-cases.REACH:]) == (len(plain), plain)
+        assert lz4f_ref.decode_block(block, len(plain), history=dic.tobytes()[-cases.REACH:]) == (len(plain), plain)
         if lz4 is not None:
             assert cases.using_dict(lz4, block, len(plain), dic) == (len(plain), plain)
     comps = [np.frombuffer(b, np.uint8) for _, b in records]

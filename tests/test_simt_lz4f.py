@@ -3,6 +3,7 @@ under the SIMT emulator (tests/simt/emu_lz4f.inc): the real kernels, the library
 the block codec replaced by results and bytes computed here with the oracle.  The reference is the test-side twin tests/lz4f_ref.py: a
 from-the-spec xxh32, a frame writer and a frame reader over the oracle's block codec."""
 import ctypes as C
+import functools
 import mmap
 
 import numpy as np
@@ -10,8 +11,10 @@ import pytest
 
 import lz4f_ref as ref
 from emu_lib import E_ARGUMENT, Guarded, P as _P, u8
-from lz4f_cases import LENGTHS, EmuRun, check_decode, emu, emu_encode, flip, mixed, sample
+from lz4f_cases import LENGTHS, PLAIN, FrameRun as EmuRun, check_frame, emu, emu_encode, flip, mixed, sample
 from lz4net_amd._lib import Lz4fInfo
+
+check_decode = functools.partial(check_frame, PLAIN, slot=0, max_blocks=8)   # the plain one-frame call, a table of 8 rows
 
 
 # ---- xxHash32 -------------------------------------------------------------------------------------------------------------------
@@ -132,7 +135,7 @@ def test_encode_block_size_ids_and_mixed_blocks(oracle, block_id):
     frame = emu_encode(oracle, src, block_id=block_id, flags=7)
     assert frame[5] == (block_id or 4) << 4
     if block_id in (0, 4):
-        fields = [int.from_bytes(frame[at - 4:at], "little") >> 31 for at, *_ in ref.read_frame(oracle, frame)[2]]
+        fields = [int.from_bytes(frame[at - 4:at], "little") >> 31 for at, *_ in ref.read_frame(oracle, frame)[3]]
         assert fields == [1, 0, 0, 0, 1], "raw and compressed blocks were to mix"
 
 
@@ -314,7 +317,7 @@ def test_decode_arguments_and_host_call(oracle):
         args[at] = bad
         assert L.emu_lz4f_decode(*args, C.byref(run)) == E_ARGUMENT, at
     # the host-pointer call: a size query, then the decode; the stand-in codec is keyed by table row
-    _, _, rows = ref.read_frame(oracle, frame)
+    _, _, _, rows = ref.read_frame(oracle, frame)
     n = len(frame) // 65536 + 64
     dec_results, dec_len, dec_at, blob = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int64), b""
     for k, (at, size, raw, badsum, res, data) in enumerate(rows):

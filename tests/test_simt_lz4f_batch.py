@@ -10,9 +10,8 @@ import pytest
 import lz4f_lib
 import lz4f_ref as ref
 from emu_lib import E_ARGUMENT, GRIDS, Guarded, u8
-from lz4f_batch_cases import (EmuRun, check_decode_batch, emu, emu_encode_batch, expect_items, frames_alone, golden_batch, offsets_of, outcome_items,
-                              sources, standin, tiny_items)
-from lz4f_cases import sample
+from lz4f_batch_cases import emu_encode_batch, frames_alone, golden_batch, outcome_items, sources, tiny_items
+from lz4f_cases import PLAIN, BatchRun as EmuRun, check_batch, emu, expect, offsets_of, sample, standin
 from lz4net_amd._lib import Lz4fBatchInfo, Lz4fInfo
 
 
@@ -50,7 +49,7 @@ def test_decode_is_the_decode_of_every_item_alone(oracle, flags, grid):
     items = sources(oracle)
     frames = frames_alone(oracle, items, 4, False, flags)
     for verify in (3, 0):
-        recs, outs, info = check_decode_batch(oracle, b"".join(frames), offsets_of(frames), slot=65536, verify=verify, grid=grid)
+        recs, outs, info = check_batch(PLAIN, oracle, frames, slot=65536, verify=verify, grid=grid)
         assert outs == items and info["error"] == ref.OK and all(r["frame_bytes"] == len(f) for r, f in zip(recs, frames))
 
 
@@ -62,7 +61,7 @@ def test_every_outcome_in_one_batch(oracle, grid):
     for _, bad, _ in faults:
         items += [bad, good]
     items += frames_alone(oracle, sources(oracle)[2:4], 4, False, 7)
-    recs, outs, info = check_decode_batch(oracle, b"".join(items), offsets_of(items), slot=65536, round_blocks=3, grid=grid)
+    recs, outs, info = check_batch(PLAIN, oracle, items, slot=65536, round_blocks=3, grid=grid)
     assert [r["error"] for r in recs] == [ref.OK] + [c for _, _, code in faults for c in (code, ref.OK)] + [ref.OK, ref.OK]
     assert info["first_error"] == 1 and info["error"] == ref.BAD_MAGIC, "the lowest failing item, as a sequential loop raises it"
     # the neighbours are byte-identical to the fault-free batch's
@@ -72,7 +71,7 @@ def test_every_outcome_in_one_batch(oracle, grid):
     assert by_name["sum_and_content"]["error"] == ref.BLOCK_CHECKSUM and by_name["sum_and_cut"]["error"] == ref.BLOCK_CHECKSUM
     assert by_name["sum_and_cut"]["error_offset"] == by_name["block_sum"]["error_offset"]
     # unverified, the flipped byte is the decoder's to find
-    recs, _, _ = check_decode_batch(oracle, b"".join(items), offsets_of(items), slot=65536, verify=2, grid=grid)
+    recs, _, _ = check_batch(PLAIN, oracle, items, slot=65536, verify=2, grid=grid)
     assert recs[2 * [name for name, _, _ in faults].index("block_sum") + 1]["error"] == ref.CORRUPT_BLOCK
 
 
@@ -80,11 +79,11 @@ def test_every_outcome_in_one_batch(oracle, grid):
 def test_decode_an_item_with_bad_offsets(oracle, grid):
     frames = frames_alone(oracle, sources(oracle)[1:4], 4, False, 7)
     blob, off = with_a_bad_item(frames, 1)
-    recs, outs, info = check_decode_batch(oracle, blob, off, slot=65536, grid=grid)
+    recs, outs, info = check_batch(PLAIN, oracle, blob, off=off, slot=65536, grid=grid)
     assert recs[1]["error"] == E_ARGUMENT and outs[1] == b"" and recs[0]["error"] == ref.OK and info["first_error"] == 1
     off = offsets_of(frames)
     off[3] += 1                                                         # the last item leaves the buffer
-    recs, outs, info = check_decode_batch(oracle, b"".join(frames), off, slot=65536, grid=grid)
+    recs, outs, info = check_batch(PLAIN, oracle, b"".join(frames), off=off, slot=65536, grid=grid)
     assert [r["error"] for r in recs] == [ref.OK, ref.OK, E_ARGUMENT] and info["first_error"] == 2 and info["error"] == E_ARGUMENT
 
 
@@ -98,11 +97,11 @@ def mixed_batch(oracle):
 def test_table_exact_and_one_row_short(oracle, grid):
     frames, items = mixed_batch(oracle)
     blob, off = b"".join(frames), offsets_of(frames)
-    rows = len(expect_items(oracle, frames, 262144, 3)[2])
+    rows = len(expect(oracle, frames, 262144, 3)[2])
     assert rows == 1 + 1 + 1 + 1 + 2 + 4 + 1 + 1 + 1 + 1
-    _, outs, info = check_decode_batch(oracle, blob, off, slot=262144, max_blocks=rows, grid=grid)
+    _, outs, info = check_batch(PLAIN, oracle, blob, off=off, slot=262144, max_blocks=rows, grid=grid)
     assert outs == items and info["blocks"] == rows and info["error"] == ref.OK
-    _, _, info = check_decode_batch(oracle, blob, off, slot=262144, max_blocks=rows - 1, grid=grid)
+    _, _, info = check_batch(PLAIN, oracle, blob, off=off, slot=262144, max_blocks=rows - 1, grid=grid)
     assert info["error"] == ref.TABLE_FULL and info["blocks"] == rows, "the count needed"
 
 
@@ -110,7 +109,7 @@ def test_table_exact_and_one_row_short(oracle, grid):
 @pytest.mark.parametrize("round_blocks", [1, 2])
 def test_rounds_that_start_inside_an_item(oracle, round_blocks, grid):
     frames, items = mixed_batch(oracle)
-    _, outs, info = check_decode_batch(oracle, b"".join(frames), offsets_of(frames), slot=262144, max_blocks=17, round_blocks=round_blocks, grid=grid)
+    _, outs, info = check_batch(PLAIN, oracle, frames, slot=262144, max_blocks=17, round_blocks=round_blocks, grid=grid)
     assert outs == items and info["error"] == ref.OK
 
 
@@ -119,7 +118,7 @@ def test_block_ids_together_and_a_slot_too_small_for_one_item(oracle, grid):
     frames, items = mixed_batch(oracle)
     big = frames_alone(oracle, [items[5]], 6, False, 7)
     frames, items = frames[:3] + big + frames[3:], items[:3] + [b""] + items[3:]
-    recs, outs, info = check_decode_batch(oracle, b"".join(frames), offsets_of(frames), slot=262144, grid=grid)
+    recs, outs, info = check_batch(PLAIN, oracle, frames, slot=262144, grid=grid)
     assert [r["error"] for r in recs] == [ref.OK] * 3 + [ref.SLOT_TOO_SMALL] + [ref.OK] * (len(recs) - 4)
     assert outs == items and info["first_error"] == 3 and recs[3]["block_max"] == 1 << 20
     assert {r["block_max"] for r in recs} == {65536, 262144, 1 << 20}
@@ -131,7 +130,7 @@ def test_clipping_by_position(oracle, grid):
     blob, off = b"".join(frames), offsets_of(frames)
     ends = offsets_of(items)
     for cap in (0, int(ends[5]), int(ends[5]) - 1, int(ends[6]) + 70000):
-        recs, _, info = check_decode_batch(oracle, blob, off, slot=262144, round_blocks=2, dst_cap=cap, grid=grid)
+        recs, _, info = check_batch(PLAIN, oracle, blob, off=off, slot=262144, round_blocks=2, dst_cap=cap, grid=grid)
         assert info["decoded_bytes"] == ends[-1] and info["error"] == ref.OK
         for i, r in enumerate(recs):
             assert (r["checks"] >> 2) == (ref.VERIFIED if ends[i + 1] <= cap else ref.SKIPPED), (cap, i)
@@ -146,7 +145,7 @@ def test_item_counts_around_the_checksum_kernel_s_rows(oracle, n):
     src, off = b"".join(items), offsets_of(items)
     for grid in GRIDS:
         got, got_off = emu_encode_batch(oracle, src, off, 4, False, 7, grid)
-        recs, outs, _ = check_decode_batch(oracle, got, got_off, slot=65536, grid=grid)
+        recs, outs, _ = check_batch(PLAIN, oracle, got, off=got_off, slot=65536, grid=grid)
         assert outs == items and all((r["checks"] >> 2) == ref.VERIFIED for r in recs)
 
 
@@ -156,11 +155,11 @@ def test_4100_tiny_items_cross_a_scan_tile(oracle):
     assert emu().emu_lz4f_batch_sizeof(100) == 4096 < len(items)
     src, off = b"".join(items), offsets_of(items)
     got, got_off = emu_encode_batch(oracle, src, off, 4, False, 7)
-    recs, outs, info = check_decode_batch(oracle, got, got_off, slot=65536, round_blocks=4099)
+    recs, outs, info = check_batch(PLAIN, oracle, got, off=got_off, slot=65536, round_blocks=4099)
     assert outs == items and info["blocks"] == len(items) and info["error"] == ref.OK
     bad = bytearray(got)
     bad[got_off[4097] + 15 + 4] ^= 0xFF                                 # the first data byte of item 4097's only block
-    recs, outs, info = check_decode_batch(oracle, bytes(bad), got_off, slot=65536)
+    recs, outs, info = check_batch(PLAIN, oracle, bytes(bad), off=got_off, slot=65536)
     assert info["first_error"] == 4097 and info["error"] == ref.BLOCK_CHECKSUM and [i for i, r in enumerate(recs) if r["error"]] == [4097]
 
 
@@ -170,11 +169,11 @@ def test_skippable_trailing_bytes_empty_item_and_no_item(oracle, grid):
     src = sample(oracle, 3, 70000)
     frame = frames_alone(oracle, [src], 4, False, 7)[0]
     items = [frame, ref.skippable(b"user data", 3), frame + frame[:40], b"", frame]
-    recs, outs, info = check_decode_batch(oracle, b"".join(items), offsets_of(items), slot=65536, grid=grid)
+    recs, outs, info = check_batch(PLAIN, oracle, items, slot=65536, grid=grid)
     assert [r["error"] for r in recs] == [ref.OK, ref.OK, ref.OK, ref.BAD_MAGIC, ref.OK] and info["first_error"] == 3
     assert recs[1]["kind"] == 1 and recs[1]["frame_bytes"] == 17 and outs[1] == b""
     assert recs[2]["frame_bytes"] == len(frame) and outs[2] == src, "what lies behind the frame is left alone"
-    _, _, info = check_decode_batch(oracle, b"", np.zeros(1, np.int64), slot=65536, grid=grid)
+    _, _, info = check_batch(PLAIN, oracle, b"", off=np.zeros(1, np.int64), slot=65536, grid=grid)
     assert info == dict(items=0, blocks=0, decoded_bytes=0, first_error=-1, error_offset=-1, error=0, reserved=0)
     got, got_off = emu_encode_batch(oracle, b"", np.zeros(1, np.int64), grid=grid)
     assert got == b"" and list(got_off) == [0]
@@ -186,7 +185,7 @@ def test_skippable_trailing_bytes_empty_item_and_no_item(oracle, grid):
 @pytest.mark.parametrize("grid", GRIDS)
 def test_golden_frames_as_one_batch(oracle, grid):
     names, recs_json, frames, srcs = golden_batch(oracle)
-    recs, outs, info = check_decode_batch(oracle, b"".join(frames), offsets_of(frames), slot=0, round_blocks=5, grid=grid)
+    recs, outs, info = check_batch(PLAIN, oracle, frames, slot=0, round_blocks=5, grid=grid)
     for name, j, r, out, src in zip(names, recs_json, recs, outs, srcs):
         if j["linked"]:
             assert r["error"] == ref.UNSUPPORTED_LINKED and out == b"", name
@@ -217,7 +216,7 @@ def test_host_pointer_calls(oracle, grid):
     device, device_off = emu_encode_batch(oracle, src, off, 4, False, 7, grid)
     staged, staged_off = emu_encode_batch(oracle, src, off, 4, False, 7, grid, host=True)
     assert staged == device and list(staged_off) == list(device_off), "the same bytes as the device front"
-    recs, outs, rows, ends = expect_items(oracle, [staged[a:b] for a, b in zip(staged_off[:-1], staged_off[1:])], 65536, 3)
+    recs, outs, rows, ends, _ = expect(oracle, [staged[a:b] for a, b in zip(staged_off[:-1], staged_off[1:])], 65536, 3)
     n = len(items)
     table = len(staged) // 4096 + n + 16
     arrs = standin(rows, table)

@@ -1,58 +1,30 @@
 """CPU-only: the decode of ONE LZ4 frame is the decode of a batch of one (both run the same round kernels, sizes step, pack layout,
 checksum verdicts and item record: lz4net_amd/csrc/lz4hip_lz4f.hpp), compared emulator against emulator; and every scratch query of
 the paths that share the round loop of lz4hip_framing.hpp returns a recorded value."""
-import ctypes as C
 import itertools
 
-import numpy as np
 import pytest
 
 import lz4f_batch_cases as batch
 import lz4f_cases as one
 import lz4f_ref as ref
-from emu_lib import E_ARGUMENT, GRIDS, I32, I64, Guarded, u8
-from lz4net_amd._lib import Lz4fBatchInfo, Lz4fInfo
+from emu_lib import E_ARGUMENT, GRIDS, I32, I64
 
 SLOT, MAX_BLOCKS = 65536, 8
 
 
-def _standin(oracle, frame, verify):
-    """the twin's per-block results and bytes as the stand-in decoder of either run record, and the bytes the frame decodes to"""
-    want, out, rows = ref.read_frame(oracle, frame, SLOT, MAX_BLOCKS, verify)
-    arrs = batch.standin(rows, MAX_BLOCKS)
-    fields = dict(dec_results=arrs[0].ctypes.data, dec_len=arrs[1].ctypes.data, dec_at=arrs[2].ctypes.data, dec_bytes=arrs[3].ctypes.data, dec_rows=MAX_BLOCKS)
-    return fields, arrs, want["decoded_bytes"]
-
-
 def decode_one(oracle, frame, round_blocks, verify, grid):
     """the one-frame emulator call -> (record, the whole output buffer)"""
-    L = one.emu()
-    fields, keep, cap = _standin(oracle, frame, verify)
-    run = one.EmuRun(grid=grid, **fields)
-    a, dst, info = Guarded(len(frame)), Guarded(cap), Lz4fInfo()
-    a.a[:] = u8(frame)
-    scratch = Guarded(L.emu_lz4f_decode_scratch_bytes(SLOT, MAX_BLOCKS, round_blocks))
-    rc = L.emu_lz4f_decode(a.ptr, len(frame), SLOT, MAX_BLOCKS, round_blocks, verify, scratch.ptr, scratch.n, dst.ptr, cap, C.byref(info), C.byref(run))
-    assert rc == 0 and run.shape_errors == 0, run.error
-    assert scratch.intact() and dst.intact() and a.intact()
-    return {f: int(getattr(info, f)) for f in one.INFO_FIELDS}, dst.a.tobytes()
+    want, _, _, rows = ref.read_frame(oracle, frame, SLOT, MAX_BLOCKS, verify)
+    rec, dst, _ = one.run_frame(one.PLAIN, frame, rows, b"", 0, SLOT, MAX_BLOCKS, round_blocks, verify, want["decoded_bytes"], grid)
+    return rec, dst.tobytes()
 
 
 def decode_batch_of_one(oracle, frame, round_blocks, verify, grid):
     """the batch emulator call with n = 1 -> (the item's record, the whole output buffer)"""
-    L = batch.emu()
-    fields, keep, cap = _standin(oracle, frame, verify)
-    run = batch.EmuRun(grid=grid, **fields)
-    off = np.array([0, len(frame)], np.int64)
-    a, dst, dst_off, item_info, written, info = Guarded(len(frame)), Guarded(cap), Guarded(16), Guarded(C.sizeof(Lz4fInfo)), Guarded(8), Lz4fBatchInfo()
-    a.a[:] = u8(frame)
-    scratch = Guarded(L.emu_lz4f_batch_decode_scratch_bytes(1, SLOT, MAX_BLOCKS, round_blocks))
-    rc = L.emu_lz4f_batch_decode(a.ptr, len(frame), off.ctypes.data, 1, SLOT, MAX_BLOCKS, round_blocks, verify, scratch.ptr, scratch.n, dst.ptr, cap,
-                                 dst_off.ptr, item_info.ptr, C.byref(info), written.ptr, C.byref(run))
-    assert rc == 0 and run.shape_errors == 0, run.error
-    assert scratch.intact() and dst.intact() and a.intact() and dst_off.intact() and item_info.intact() and written.intact()
-    rec = Lz4fInfo.from_buffer_copy(item_info.a.tobytes())
-    return {f: int(getattr(rec, f)) for f in one.INFO_FIELDS}, dst.a.tobytes()
+    want, _, _, rows = ref.read_frame(oracle, frame, SLOT, MAX_BLOCKS, verify)
+    _, recs, _, dst, _, _ = one.run_batch(one.PLAIN, [frame], rows, b"", 0, SLOT, MAX_BLOCKS, round_blocks, verify, want["decoded_bytes"], grid)
+    return recs[0], dst.tobytes()
 
 
 # ---- 1. one frame = a batch of one ------------------------------------------------------------------------------------------------------
@@ -118,7 +90,7 @@ def test_lz4f_decode_scratch_bytes_are_the_recorded_ones():
 
 
 def test_lz4f_batch_decode_scratch_bytes_are_the_recorded_ones():
-    L = batch.emu()
+    L = one.emu()
     for (n, slot, m, r), want in LZ4F_BATCH.items():
         assert L.emu_lz4f_batch_decode_scratch_bytes(n, slot, m, r) == want, (n, slot, m, r)
     assert L.emu_lz4f_batch_decode_scratch_bytes(-1, SLOT, 1, 0) == E_ARGUMENT
