@@ -62,6 +62,9 @@
 #ifndef LZ4HIP_STAT
 #define LZ4HIP_STAT(slot, cond) ((void)0)   /* the emulator build counts lane-iterations per state (tools/emu_decoder_stats.py) */
 #endif
+#ifndef LZ4HIP_STAT_L4
+#define LZ4HIP_STAT_L4(slot, cond) ((void)0)   /* the emulator build counts which way the parser, the promotion and the ring went (L4Stat below, tests/lane_decode_cases.py) */
+#endif
 // Section markers for the per-section instruction table of the compiled kernel (tools/isa_lane4_table.py builds with
 // -DLZ4HIP_SECTION_MARKERS: each marker becomes a comment line in the assembly listing; volatile asm statements -- most of this kernel's
 // selects, loads and stores -- keep their order relative to the markers).  Nothing in product builds.
@@ -135,6 +138,13 @@ struct NoNext {
     LZ4HIP_DEVICE bool operator()(int, const uint8_t*&, int&, uint8_t*&, int&) const { return false; }
 };
 
+// Slots of LZ4HIP_STAT_L4, counted per lane: the parser's way (T4 / T4x) and each reason for the trap, what a parsed-ahead sequence was promoted
+// to (B4), the steps of a doubling near match (B3), near-match source rows that wrap the ring (T1c), the bytes of a block's last partial dword (B5)
+enum L4Stat { kL4Fast = 0, kL4TrapToken, kL4TrapHeader, kL4WhyInputEnd, kL4WhyLitByte255, kL4WhyLitPastInput, kL4WhyMatchByte255, kL4WhyOffset,
+              kL4WhyMatchEnd, kL4WhyLastRunKnown, kL4WhyLastRunOutput, kL4WhyLastRunInput, kL4WhyMatchByteInput, kL4ToNear, kL4ToFar, kL4ToZero,
+              kL4ToLit, kL4Doubling, kL4NearWrap, kL4Tail0, kL4Tail1, kL4Tail2, kL4Tail3,
+              kL4RoomBelow, kL4RoomLast, kL4RoomNone,   // a copy in progress meets op - fl one below, at and one above the last value with room, in an iteration that does not flush (T3)
+              kL4Stats };
 enum L4Kind { kK4None = 0, kK4Near = 1, kK4Far = 2, kK4Lit = 3, kK4Zero = 4 };
 enum L4Flag { kF4Final = 1, kF4Err = 2, kF4Header = 4 };   // pending sequence: final literal run / corrupt stream / no match yet (its header follows the literals)
 
@@ -369,6 +379,7 @@ LZ4HIP_DEVICE int lane4_decode_block(unsigned char* lds, int lane, bool active, 
             else { const uint32_t t = oa - back, u = t + kRingBytes; sa = u < t ? u : t; }
             r0 = L4_RING(sa); r1 = L4_RING(ring_add(sa, kRow)); r2 = L4_RING(ring_add(sa, 2 * kRow));
             r3 = L4_RING(ring_add(sa, 3 * kRow)); r4 = L4_RING(ring_add(sa, 4 * kRow));
+            LZ4HIP_STAT_L4(kL4NearWrap, (done == 0) & (kind == kK4Near) & (rem > 0) & (sa + 4u * kRow >= kRingBytes));
         }
         LZ4HIP_SECTION("T1a window refill");
         int d = ip + skew - wb;                                      // byte offset of the cursor in W: 0 .. 16 + P (+ 16 while a piece is awaited)
@@ -460,6 +471,8 @@ LZ4HIP_DEVICE int lane4_decode_block(unsigned char* lds, int lane, bool active, 
         n = ((kind == kK4Zero) & (n > 8)) ? 8 : n;
         LZ4HIP_STAT(5, (done == 0) & (rem > 0)); LZ4HIP_STAT(6, (done == 0) & (rem > 0) & (n == 0)); LZ4HIP_STAT(7, (done == 0) & (rem > 0) & !room);
         LZ4HIP_STAT(8, (done == 0) & (rem > 0) & (kind == kK4Far) & (gready == 0)); LZ4HIP_STAT(9, (done == 0) & (rem > n));
+        LZ4HIP_STAT_L4(kL4RoomBelow, (done == 0) & !FLUSH & (rem > 0) & (op - fl == R - 47)); LZ4HIP_STAT_L4(kL4RoomLast, (done == 0) & !FLUSH & (rem > 0) & (op - fl == R - 46));
+        LZ4HIP_STAT_L4(kL4RoomNone, (done == 0) & !FLUSH & (rem > 0) & (op - fl == R - 45));
         const int rem_after = rem - n;
         const int op_end = op + rem;                                 // where the current copy ends = where the parsed-ahead sequence's literals go
 
@@ -510,6 +523,16 @@ LZ4HIP_DEVICE int lane4_decode_block(unsigned char* lds, int lane, bool active, 
             trap |= in_win & ((e2 & (extb == 255u)) | (vo > lit_end) | ((uint32_t)lit_end + (uint32_t)ml > out_limit));   // (lit_end < 2^31 + 270, ml <= 274: no wrap)
             if (KNOWN) trap |= (hdr == 0) & (lit_end > oend - 8);
             else       trap |= ((hdr == 0) & ((lit_end > oend - kMfLimit) | (ip + 1 + (e1 ? 1 : 0) + ll > iend - 8))) | (in_win & e2 & !(p_after < iend - (kLastLiterals + 1)));
+            LZ4HIP_STAT_L4(kL4Fast, !trap); LZ4HIP_STAT_L4(kL4TrapToken, trap & (hdr == 0)); LZ4HIP_STAT_L4(kL4TrapHeader, trap & (hdr != 0));
+            LZ4HIP_STAT_L4(kL4WhyInputEnd, ip + 16 > iend); LZ4HIP_STAT_L4(kL4WhyLitByte255, e1 & (b1 == 255u)); LZ4HIP_STAT_L4(kL4WhyLitPastInput, ip + 1 + (e1 ? 1 : 0) + ll > iend);
+            // (the three tests of a match header are counted where the literals are no last run: behind a block's last token there is no header)
+#define L4_HAS_HEADER_ (in_win & !((hdr == 0) & (KNOWN ? lit_end > oend - 8 : ((lit_end > oend - kMfLimit) | (ip + 1 + (e1 ? 1 : 0) + ll > iend - 8)))))
+            LZ4HIP_STAT_L4(kL4WhyMatchByte255, L4_HAS_HEADER_ & e2 & (extb == 255u)); LZ4HIP_STAT_L4(kL4WhyOffset, L4_HAS_HEADER_ & (vo > lit_end));
+            LZ4HIP_STAT_L4(kL4WhyMatchEnd, L4_HAS_HEADER_ & ((uint32_t)lit_end + (uint32_t)ml > out_limit));
+#undef L4_HAS_HEADER_
+            LZ4HIP_STAT_L4(kL4WhyLastRunKnown, KNOWN & (hdr == 0) & (lit_end > oend - 8)); LZ4HIP_STAT_L4(kL4WhyLastRunOutput, !KNOWN & (hdr == 0) & (lit_end > oend - kMfLimit));
+            LZ4HIP_STAT_L4(kL4WhyLastRunInput, !KNOWN & (hdr == 0) & (ip + 1 + (e1 ? 1 : 0) + ll > iend - 8));
+            LZ4HIP_STAT_L4(kL4WhyMatchByteInput, !KNOWN & in_win & e2 & !(p_after < iend - (kLastLiterals + 1)));
             p_l0 = wv::alignbyte(x1, x0, 1); p_l1 = wv::alignbyte(x2, x1, 1); p_l2 = wv::alignbyte(x3, x2, 1);
             token = tok;
             p_ll = in_win ? ll : 0;
@@ -664,6 +687,7 @@ LZ4HIP_DEVICE int lane4_decode_block(unsigned char* lds, int lane, bool active, 
             ip += lit ? n : 0;
             L4_APPEND(v0, v1, v2, v3, n, true);
             rem = rem_after;
+            LZ4HIP_STAT_L4(kL4Doubling, near & (off < 16) & (n > 0));
             off = (near & (off < 16) & (n > 0)) ? off * 2 : off;
             kind = rem == 0 ? (int)kK4None : kind;
         }
@@ -688,6 +712,7 @@ LZ4HIP_DEVICE int lane4_decode_block(unsigned char* lds, int lane, bool active, 
                 kind = streamed ? (int)kK4Lit : (p_ml == 0 ? (int)kK4None : (p_off == 0 ? (int)kK4Zero : (p_off <= kNearMax ? (int)kK4Near : (int)kK4Far)));
                 final_run = (p_flags & kF4Final) ? 1 : final_run;
                 result = (p_flags & kF4Final) ? p_res : result;
+                LZ4HIP_STAT_L4(kL4ToNear, kind == kK4Near); LZ4HIP_STAT_L4(kL4ToFar, kind == kK4Far); LZ4HIP_STAT_L4(kL4ToZero, kind == kK4Zero); LZ4HIP_STAT_L4(kL4ToLit, kind == kK4Lit);
             }
             pv = promote ? 0 : pv;
         }
@@ -697,6 +722,7 @@ LZ4HIP_DEVICE int lane4_decode_block(unsigned char* lds, int lane, bool active, 
         if (final_run && rem == 0 && !pv && !done) {
             uint32_t qa = ring_add(oa, kRingBytes - ((((uint32_t)(op - fl)) << 6) & ~0xFFu) * (uint32_t)WAVES);
             while (op - fl >= 4) { const uint32_t qd = L4_RING(qa); __builtin_memcpy(dst + fl, &qd, 4); fl += 4; qa = ring_add(qa, kRow); }
+            LZ4HIP_STAT_L4(kL4Tail0 + (op - fl), true);
             if (fl < op) {
                 const uint32_t qd = L4_RING(qa);
                 for (int b = 0; fl + b < op; b++) dst[fl + b] = (uint8_t)(qd >> (8 * b));

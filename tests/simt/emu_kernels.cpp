@@ -13,6 +13,8 @@ static unsigned long long g_stat[40];         // lane-iterations per state of th
 #define LZ4HIP_STAT_PATH(slot, cond) LZ4HIP_STAT(slot, cond)
 static unsigned long long g_hc_stat[96];      // lz4hip::HcStat: branches of the LZ4HC lane kernels and their table builders, per lane (tests/hc_lane_cases.py)
 #define LZ4HIP_STAT_HC(slot, n) do { g_hc_stat[slot] += (unsigned long long)(n); } while (0)
+static unsigned long long g_l4_stat[32];      // lz4hip::L4Stat: the parser, the promotion and the ring of the fourth-generation lane decoder, per lane (tests/lane_decode_cases.py)
+#define LZ4HIP_STAT_L4(slot, cond) do { if (cond) g_l4_stat[slot]++; } while (0)
 
 #include "lz4hip_common.hpp"
 #include "lz4hip_decode.hpp"
@@ -341,6 +343,12 @@ unsigned long long emu_compare(const uint8_t* x, int64_t xs, const uint8_t* y, i
 
 unsigned long long emu_steps() { return simt::rt().steps; }
 void emu_stats(unsigned long long* out, int reset) { for (int i = 0; i < 40; i++) { out[i] = g_stat[i]; if (reset) g_stat[i] = 0; } }
+static_assert(kL4Stats <= 32, "g_l4_stat");
+int emu_l4_stats(unsigned long long* out, int reset)
+{
+    for (int i = 0; i < kL4Stats; i++) { out[i] = g_l4_stat[i]; if (reset) g_l4_stat[i] = 0; }
+    return kL4Stats;
+}
 unsigned long long emu_iterations(int reset) { const unsigned long long v = g_iterations; if (reset) g_iterations = 0; return v; }
 }
 
