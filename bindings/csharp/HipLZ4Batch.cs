@@ -63,6 +63,8 @@ namespace LZ4hip
         // through ctypes.)
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
         private static extern unsafe int lz4hip_decode_batch_dict_host(Batch* b, byte* dict, long dictLen, int knownOutputSize);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        private static extern unsafe int lz4hip_encode_batch_dict_host(Batch* b, byte* dict, long dictLen);
 
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
         private static extern unsafe int lz4hip_decoded_sizes_dict_host(Batch* b, long dictLen, long* dstOff, int* dstCap, SizesInfo* info);
@@ -275,6 +277,41 @@ namespace LZ4hip
                     throw new ArgumentException("LZ4 block is corrupted, or invalid length has been given.");
                 output[i] = new byte[outputLengths[i]];
                 Buffer.BlockCopy(dst, (int)dstOff[i], output[i], 0, outputLengths[i]);
+            }
+            return output;
+        }
+
+        /// <summary>Compresses every block against one shared dictionary (fast mode; K4os's LZ4Codec.Encode(source, target, dictionary)
+        /// per block, the parse of include/lz4hip.h).  Each result decodes with DecodeWithDictionary and the same dictionary.</summary>
+        public static unsafe byte[][] EncodeWithDictionary(byte[][] blocks, byte[] dictionary)
+        {
+            int n = blocks.Length;
+            long total = 0, outTotal = 0;
+            var srcOff = new long[n]; var dstOff = new long[n]; var lens = new int[n]; var caps = new int[n];
+            for (int i = 0; i < n; i++)
+            {
+                srcOff[i] = total; lens[i] = blocks[i].Length; total += lens[i];
+                caps[i] = lens[i] + lens[i] / 255 + 16;
+                dstOff[i] = outTotal; outTotal += caps[i];
+            }
+            var src = new byte[Math.Max(total, 1)]; var dst = new byte[Math.Max(outTotal, 1)];
+            for (int i = 0; i < n; i++) Buffer.BlockCopy(blocks[i], 0, src, (int)srcOff[i], lens[i]);
+            var results = new int[n];
+            var dict = dictionary.Length > 0 ? dictionary : new byte[1];
+            fixed (byte* ps = src, pd = dst, pdict = dict)
+            fixed (long* so = srcOff, dof = dstOff)
+            fixed (int* sl = lens, dc = caps, res = results)
+            {
+                var b = new Batch { src = ps, src_off = so, src_len = sl, dst = pd, dst_off = dof, dst_cap = dc, result = res, n_blocks = n };
+                Check(lz4hip_encode_batch_dict_host(&b, pdict, dictionary.Length));
+            }
+            var output = new byte[n][];
+            for (int i = 0; i < n; i++)
+            {
+                if (results[i] <= 0)
+                    throw new InvalidOperationException("Compression has been corrupted");
+                output[i] = new byte[results[i]];
+                Buffer.BlockCopy(dst, (int)dstOff[i], output[i], 0, results[i]);
             }
             return output;
         }

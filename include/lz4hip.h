@@ -125,11 +125,45 @@ int lz4hip_decode_batch_host(const lz4hip_batch_t* b, int known_output_size);
  * per-thread grow-only device memory (freed by lz4hip_release_workspaces) and have landed before any slice's kernels start.
  * The sizes calls are lz4hip_decoded_sizes_device / _host for such blocks: a match may start up to min(dict_len, 65 535) bytes before its
  * block.  They need no byte of the dictionary; the scratch query is lz4hip_decoded_sizes_scratch_bytes.
- * Out of scope: encoding against a dictionary (the reference has no such parse to be bit-exact to, and preloading the encoders' tables is
- * a design of its own); LZ4 frames with a dictionary (below: lz4hip_lz4f_*_dict_*); a dictionary per block; the lane mapping; a _multi host
- * form; the compact and packed decode forms. */
+ * Out of scope: LZ4 frames with a dictionary (below: lz4hip_lz4f_*_dict_*); a dictionary per block; the lane mapping; a _multi host
+ * form; the compact and packed decode forms.  (Encoding against a dictionary: lz4hip_encode_batch_dict_*, next.) */
 int lz4hip_decode_batch_dict_device(const lz4hip_batch_t* b, const void* dict, int64_t dict_len, int known_output_size, void* stream);
 int lz4hip_decode_batch_dict_host(const lz4hip_batch_t* b, const void* dict, int64_t dict_len, int known_output_size);
+
+/* ---- block batches encoded against a shared dictionary -------------------------------------------------------------------------------
+ * K4os.Compression.LZ4's LZ4Codec.Encode(source, target, dictionary) in a loop: every block of the batch shares ONE dictionary
+ * dict[0, dict_len).  FAST MODE ONLY.  result[i], dst_cap and the returned 0 when a block does not fit are those of
+ * lz4hip_encode_batch_device; nothing is written at or past a block's dst_cap.  A block's bytes are legal input for
+ * lz4hip_decode_batch_dict_device and for LZ4_decompress_safe_usingDict with the same dictionary.
+ * The reference has no such parse to be bit-exact to, so the bytes are DEFINED here: they are what the reference's generic
+ * encoder (LZ4_compressCtx: U32[4096] table, hash shift 20) writes when it runs over the dictionary's last T = min(dict_len, 65 535) bytes
+ * followed by the block, starts at the block's first byte -- anchor and first table insert there, first probe one byte later -- and finds
+ * its table primed: bucket h holds the highest position p <= T - 4 of the dictionary's tail whose four bytes hash to h, and position 0
+ * where there is none.  Matches may start in the dictionary and run on into the block; literals are the block's; offsets are <= 65 535.
+ * A block of fewer than 13 bytes is literals only.  They are not the bytes liblz4's LZ4_compress_fast_continue writes, but of the
+ * same kind and, on 4 KiB text records against a 64 KiB dictionary, the same size.
+ *   - Only the last 65 535 bytes of the dictionary are read, and nothing outside [dict, dict + dict_len).
+ *   - dict_len == 0 (dict and scratch may then be NULL) IS lz4hip_encode_batch_device(b, LZ4HIP_MODE_FAST, stream), result for result
+ *     and byte for byte -- that call's choice of the 64k variant for blocks below 65 547 bytes and its two mappings included.
+ *   - The dictionary may have any alignment.  It is not copied: it must stay valid until the kernels have run.
+ *   - A block of more than 0x7E000000 bytes (LZ4_MAX_INPUT_SIZE) gets the result 0.
+ * The device call carries the contract of lz4hip_decode_batch_dict_device: device pointers of the current device -- dict and scratch
+ * included -- launch-only on `stream`, nothing allocated, 0 or LZ4HIP_E_*; dict_len < 0, and dict == NULL with dict_len > 0, are
+ * LZ4HIP_E_ARGUMENT, checked before a device is looked for, and so are, with dict_len > 0, a NULL scratch, one that is not 16-byte
+ * aligned and scratch_bytes below lz4hip_encode_dict_scratch_bytes(dict_len).  The scratch holds the primed table (16 KiB), which a
+ * one-workgroup kernel builds from the dictionary at the start of every call; the blocks only read it.
+ * THE COST: these calls run the wavefront mapping (one wavefront per block, the table in 16 KiB of LDS, workgroups of one or five blocks
+ * as lz4hip_encode_batch_device picks them) at every batch size -- lz4hip_dispatch_counts moves LZ4HIP_K_ENCODE_WAVE only.  There is no
+ * lane mapping and no hand-over to it, so a large batch of sequence-dense blocks encodes at the wavefront mapping's rate.  Each wavefront
+ * first copies the primed table into its LDS, in place of the plain encoder's zero fill.
+ * The host call stages the blocks as lz4hip_encode_batch_host does (one pipeline, that call's slices); the dictionary's reachable bytes
+ * are uploaded once per call and its table is primed once per call, both into per-thread grow-only device memory (freed by
+ * lz4hip_release_workspaces), and both have landed before any slice's kernels start.
+ * Out of scope: LZ4 frames with a dictionary on the ENCODE side (the next step: LZ4F_compressFrame_usingCDict is this call under the
+ * frame rounds); LZ4HC against a dictionary; a dictionary per block; the lane mapping; a _multi host form; the packed encode form. */
+int64_t lz4hip_encode_dict_scratch_bytes(int64_t dict_len);
+int lz4hip_encode_batch_dict_device(const lz4hip_batch_t* b, const void* dict, int64_t dict_len, void* scratch, int64_t scratch_bytes, void* stream);
+int lz4hip_encode_batch_dict_host(const lz4hip_batch_t* b, const void* dict, int64_t dict_len);
 
 /* Host-resident batches sharded over several GPUs of the node: block i is processed by the (i mod N)-th device
  * selected by device_mask (bit d = HIP device d; 0 = every visible device) -- the round-robin partition of

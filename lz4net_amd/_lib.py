@@ -122,6 +122,9 @@ SYMBOLS = [
     ("lz4hip_decode_batch_host", C.c_int, [C.POINTER(Batch), C.c_int]),
     ("lz4hip_decode_batch_dict_device", C.c_int, [C.POINTER(Batch), C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
     ("lz4hip_decode_batch_dict_host", C.c_int, [C.POINTER(Batch), C.c_void_p, C.c_int64, C.c_int]),
+    ("lz4hip_encode_dict_scratch_bytes", C.c_int64, [C.c_int64]),
+    ("lz4hip_encode_batch_dict_device", C.c_int, [C.POINTER(Batch), C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
+    ("lz4hip_encode_batch_dict_host", C.c_int, [C.POINTER(Batch), C.c_void_p, C.c_int64]),
     ("lz4hip_encode_batch_host_multi", C.c_int, [C.POINTER(Batch), C.c_int, C.c_uint64]),
     ("lz4hip_decode_batch_host_multi", C.c_int, [C.POINTER(Batch), C.c_int, C.c_uint64]),
     ("lz4hip_synth_device", C.c_int, [C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]),

@@ -104,6 +104,23 @@ def decode_dict(src: torch.Tensor, src_len, dst: torch.Tensor, out_size, diction
     return result
 
 
+def encode_dict(src: torch.Tensor, src_len, dst: torch.Tensor, dst_cap, dictionary: torch.Tensor | None,
+                result: torch.Tensor | None = None) -> torch.Tensor:
+    """encode() in fast mode with ONE dictionary shared by every block (lz4hip_encode_batch_dict_device, K4os's
+    LZ4Codec.Encode(source, target, dictionary) in a loop): a match may start in `dictionary` (1-D uint8, on the device), of which only
+    the last 65 535 bytes can be reached.  Results are encode()'s; the bytes decode with decode_dict() and the same dictionary.  No
+    dictionary, or an empty one, is encode().  The wavefront mapping encodes these batches at every size; the call allocates its 16 KiB
+    of scratch (the dictionary's primed table) itself."""
+    ptr, n_dict, keep_dict = _dictionary(dictionary, src)
+    if result is None:
+        result = torch.empty(src.shape[0], dtype=torch.int32, device=src.device)
+    b, keep = _make_batch(src, src_len, dst, dst_cap, result)
+    need = _lib.lib().lz4hip_encode_dict_scratch_bytes(n_dict)
+    scratch = torch.empty(need, dtype=torch.uint8, device=src.device) if need else None   # (the caching allocator keeps it until the stream has passed)
+    _lib.check(_lib.lib().lz4hip_encode_batch_dict_device(C.byref(b), ptr, n_dict, _ptr(scratch), need, _stream()))
+    return result
+
+
 def synth(dist: int, seed: int, first_block: int, n_blocks: int, length: int = BLOCK, stride: int | None = None,
           out: torch.Tensor | None = None, device=None, block_step: int = 1) -> torch.Tensor:
     """Synthetic blocks generated on the device (bit-identical to oracle/synth.c); row i is synthetic block

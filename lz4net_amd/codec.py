@@ -283,6 +283,34 @@ class LZ4Codec(metaclass=_LZ4CodecMeta):
             raise ArgumentException(_CORRUPT)
         return [dst[int(dst_off[i]):int(dst_off[i]) + int(dst_len[i])].tobytes() for i in range(n)]
 
+    # ---- ... and K4os's LZ4Codec.Encode(source, target, dictionary), batched ----------------------------------------------------------
+    @classmethod
+    def encode_many_with_dictionary(cls, blocks, dictionary) -> list:
+        """[block b compressed against `dictionary`, for b in blocks], every block in ONE lz4hip_encode_batch_dict_host call (fast mode;
+        the parse of include/lz4hip.h).  Each result decodes with decode_many_with_dictionary and the same dictionary, and with
+        LZ4_decompress_safe_usingDict.  Every block gets MaximumOutputLength of room, so none fails to fit."""
+        if blocks is None:
+            raise ArgumentNullException("blocks")
+        if dictionary is None:
+            raise ArgumentNullException("dictionary")
+        bufs = [bytes(_as_bytes(b, "blocks")) for b in blocks]
+        dic = np.ascontiguousarray(_as_bytes(dictionary, "dictionary"))
+        n = len(bufs)
+        if n == 0:
+            return []
+        src_len = np.array([len(b) for b in bufs], dtype=np.int32)
+        src_off = np.concatenate(([0], np.cumsum(src_len[:-1], dtype=np.int64))).astype(np.int64)
+        src = np.frombuffer(b"".join(bufs) or b"\0", dtype=np.uint8)
+        dst_cap = np.array([cls.MaximumOutputLength(len(b)) for b in bufs], dtype=np.int32)
+        dst_off = np.concatenate(([0], np.cumsum(dst_cap[:-1], dtype=np.int64))).astype(np.int64)
+        dst = np.zeros(int(dst_cap.astype(np.int64).sum()), dtype=np.uint8)
+        res = np.zeros(n, dtype=np.int32)
+        b = _p.host_blocks(src, src_off, src_len, dst, dst_off, dst_cap, res)
+        _lib.check(_lib.lib().lz4hip_encode_batch_dict_host(C.byref(b), dic.ctypes.data if dic.size else None, dic.size))
+        if (res <= 0).any():
+            raise InvalidOperationException("Compression has been corrupted")
+        return [dst[int(dst_off[i]):int(dst_off[i]) + int(res[i])].tobytes() for i in range(n)]
+
     # ---- batched Wrap / Unwrap (SURVEY.md 8f-2): many messages, ONE GPU batch ---------------------------
     @classmethod
     def WrapMany(cls, messages, high_compression: bool = False) -> list:

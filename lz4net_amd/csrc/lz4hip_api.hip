@@ -14,6 +14,7 @@
 #include "../../tools/ab/lz4hip_hc_nat_lane.hpp"
 #endif
 #include "lz4hip_encode.hpp"
+#include "lz4hip_encode_dict.hpp"
 #include "lz4hip_encode_lane.hpp"
 #include "lz4hip_hc.hpp"
 #include "lz4hip_hc_conv.hpp"
@@ -406,7 +407,7 @@ struct DeviceState {
     CounterRing counter_ring;
     std::atomic<int> lds_drop{ 0 };             // lds_drop_confirmed(): 0 not probed yet, 1 confirmed, 2 not confirmed (or the probe could not run)
     std::mutex lds_drop_mu;
-    std::atomic<int> lds_encode_five{ 0 }, lds_hc_lcp_fill{ 0 }, lds_encode_hc{ 0 };   // allow_dynamic_lds()
+    std::atomic<int> lds_encode_five{ 0 }, lds_encode_dict_five{ 0 }, lds_hc_lcp_fill{ 0 }, lds_encode_hc{ 0 };   // allow_dynamic_lds()
     std::atomic<int> persist_per_cu{ 0 };       // residency of the persistent lane decoder (0: not known yet)
 };
 DeviceState g_device[kMaxDevices];
@@ -936,6 +937,39 @@ int launch_decode_dict(const lz4hip_batch_t* b, const void* dict, int64_t dict_l
     return 0;
 }
 
+// lz4hip_encode_batch_dict_*: the primed table of the dictionary's reachable bytes into `primed` (16 KiB), once per call ...
+int launch_encode_dict_prime(const void* dict, int64_t dict_len, void* primed, hipStream_t stream)
+{
+    const int reach = (int)hostbatch::dict_reach(dict_len);
+    hipLaunchKernelGGL(encode_dict_prime_kernel, dim3(1), dim3(kEncDictPrimeThreads), 0, stream, (const uint8_t*)dict + dict_len, reach, (uint8_t*)primed);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// ... and every block against it: the wavefront mapping at every batch size (no lane mapping, no hand-over), in workgroups of five
+// blocks wherever launch_encode would pick them.  dict_len > 0.
+int launch_encode_dict(const lz4hip_batch_t* b, const void* dict, int64_t dict_len, const void* primed, hipStream_t stream)
+{
+    if (b->n_blocks == 0) return 0;
+    const Batch d = to_device_batch(*b);
+    DeviceState* ds = nullptr;
+    int rc = current_device(ds);
+    if (rc) return rc;
+    const int reach = (int)hostbatch::dict_reach(dict_len);
+    const uint8_t* dict_end = (const uint8_t*)dict + dict_len;
+    bool five = encoder_five_blocks_per_workgroup(d.n_blocks);
+    five = five && allow_dynamic_lds(ds->lds_encode_dict_five, (const void*)(encode_dict_kernel<kEncodeBlocksPerGroup>),
+                                     kEncodeBlocksPerGroup * kFastTableBytes, true) == hipSuccess;
+    if (five)
+        hipLaunchKernelGGL((encode_dict_kernel<kEncodeBlocksPerGroup>), dim3((unsigned)((d.n_blocks + kEncodeBlocksPerGroup - 1) / kEncodeBlocksPerGroup)),
+                           dim3(64 * kEncodeBlocksPerGroup), kEncodeBlocksPerGroup * kFastTableBytes, stream, d, dict_end, reach, (const uint8_t*)primed);
+    else
+        hipLaunchKernelGGL(encode_dict_kernel<1>, dim3((unsigned)d.n_blocks), dim3(64), kFastTableBytes, stream, d, dict_end, reach, (const uint8_t*)primed);
+    HIP_TRY(hipGetLastError());
+    count_dispatch(LZ4HIP_K_ENCODE_WAVE);
+    return 0;
+}
+
 int check_dict(const void* dict, int64_t dict_len)
 {
     if (dict_len < 0) return fail(LZ4HIP_E_ARGUMENT, "dictionary: dict_len < 0");
@@ -995,6 +1029,7 @@ struct HostPipe {
 struct HostContext {
     Scratch scratch;
     Scratch dict;                                                    // lz4hip_decode_batch_dict_host: the call's dictionary, apart from the slots' images (which move when they grow)
+    Scratch primed;                                                  // lz4hip_encode_batch_dict_host: the dictionary's primed table
     Pinned pinned_in[kHostSlots], pinned_out[kHostSlots];
     HostPipe pipe;
     uint8_t* d_in[kHostSlots] = {};
@@ -1025,6 +1060,17 @@ struct HostContext {
         HIP_TRY(hipMemcpyAsync(dict.p, from, (size_t)bytes, hipMemcpyHostToDevice, pipe.s_in));
         HIP_TRY(hipStreamSynchronize(pipe.s_in));
         dev = (uint8_t*)dict.p;
+        return 0;
+    }
+    // lz4hip_encode_batch_dict_host: the primed table of the uploaded dictionary, built and WAITED for, as the upload is
+    int dict_prime(const uint8_t* d_dict, int64_t reach, uint8_t*& table)
+    {
+        int rc = primed.reserve((size_t)kFastTableBytes);
+        if (rc) return rc;
+        if ((rc = pipe.init())) return rc;
+        if ((rc = launch_encode_dict_prime(d_dict, reach, primed.p, pipe.s_in))) return rc;
+        HIP_TRY(hipStreamSynchronize(pipe.s_in));
+        table = (uint8_t*)primed.p;
         return 0;
     }
     uint8_t* pin_in(int slot) { return (uint8_t*)pinned_in[slot].p; }
@@ -1086,6 +1132,7 @@ void release_host_context(int dev)
     if (HostContext* hc = host_context(dev, false)) {
         hc->scratch.release();
         hc->dict.release();
+        hc->primed.release();
         for (int k = 0; k < kHostSlots; k++) { hc->pinned_in[k].release(); hc->pinned_out[k].release(); }
     }
 }
@@ -1522,6 +1569,42 @@ int lz4hip_decode_batch_dict_host(const lz4hip_batch_t* b, const void* dict, int
         return run_host_batch_multi(b, !known, 1ull << dev, make_run(d_dict, reach), 0, workers);
     }
     return hostbatch::run_host_batch_dict(*hc, b, dict, dict_len, !known, make_run, knob(kKnobHostSlices), knob(kKnobHostThreads));
+}
+
+int64_t lz4hip_encode_dict_scratch_bytes(int64_t dict_len) { return dict_len > 0 ? kFastTableBytes : 0; }
+
+int lz4hip_encode_batch_dict_device(const lz4hip_batch_t* b, const void* dict, int64_t dict_len, void* scratch, int64_t scratch_bytes, void* stream)
+{
+    int rc = check_batch(b);
+    if (rc) return rc;
+    if ((rc = check_dict(dict, dict_len))) return rc;
+    if (dict_len > 0 && !scratch) return fail(LZ4HIP_E_ARGUMENT, "encode with dictionary: scratch is NULL");
+    if (dict_len > 0 && scratch_bytes < kFastTableBytes) return fail(LZ4HIP_E_ARGUMENT, "encode with dictionary: scratch_bytes is less than lz4hip_encode_dict_scratch_bytes gives");
+    if (dict_len > 0 && (uintptr_t)scratch % 16) return fail(LZ4HIP_E_ARGUMENT, "encode with dictionary: scratch is not 16-byte aligned");
+    if ((rc = ensure_device())) return rc;
+    if (dict_len == 0) return launch_encode(b, LZ4HIP_MODE_FAST, (hipStream_t)stream);   // IS the plain call
+    if (b->n_blocks == 0) return 0;
+    if ((rc = launch_encode_dict_prime(dict, dict_len, scratch, (hipStream_t)stream))) return rc;
+    return launch_encode_dict(b, dict, dict_len, scratch, (hipStream_t)stream);
+}
+
+// The dictionary goes up once and its table is primed once, on the calling thread's context, and both have landed before a slice is
+// staged; the slices are those of lz4hip_encode_batch_host's one pipeline.
+int lz4hip_encode_batch_dict_host(const lz4hip_batch_t* b, const void* dict, int64_t dict_len)
+{
+    int rc = check_batch(b);
+    if (rc) return rc;
+    if ((rc = check_dict(dict, dict_len))) return rc;
+    if (dict_len == 0) return lz4hip_encode_batch_host(b, LZ4HIP_MODE_FAST);              // IS the plain call
+    if (b->n_blocks == 0) return 0;
+    if ((rc = ensure_device())) return rc;
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    HostContext* hc = host_context(dev);
+    if (!hc) return fail(LZ4HIP_E_DEVICE, "device index out of range");
+    return hostbatch::run_host_batch_encode_dict(*hc, b, dict, dict_len, [](const uint8_t* d_dict, int64_t reach, const uint8_t* table) {
+        return [=](const lz4hip_batch_t* db, hipStream_t s) { return launch_encode_dict(db, d_dict, reach, table, s); };
+    }, encode_host_slice_blocks(b, LZ4HIP_MODE_FAST), knob(kKnobHostSlices), knob(kKnobHostThreads));
 }
 
 int lz4hip_encode_batch_host_multi(const lz4hip_batch_t* b, int mode, uint64_t device_mask)

@@ -14,7 +14,12 @@
 // lane (256 bytes per step), literal copies at 16 B per lane, and length-byte fills.
 #pragma once
 #include "lz4hip_common.hpp"
+#include <type_traits>
 
+// Counters of encode_fast_block's DICT mode (lz4hip_encode_dict.hpp, EncDictStat; tests/simt/emu_dict_encode.cpp): nothing in every other build.
+#ifndef LZ4HIP_STAT_ENCDICT
+#define LZ4HIP_STAT_ENCDICT(slot, n) ((void)0)
+#endif
 // Section timers of the wavefront encoder (tools/enc_wave_sections.hip defines these to s_memtime accumulators; nothing in product builds).
 #ifndef LZ4HIP_ENC_T0
 #define LZ4HIP_ENC_DECL() ((void)0)
@@ -26,6 +31,22 @@
 
 namespace lz4hip {
 
+// what a case of tests/dict_encode_cases.py reached, per lane
+enum EncDictStat {
+    kEncDictWordInDict = 0,       // a dword read wholly inside the dictionary
+    kEncDictWordStraddles,        // a dword assembled from both segments
+    kEncDictByteInDict,           // a byte of the catch-up read inside the dictionary
+    kEncDictCandidate,            // a search ended at a candidate inside the dictionary
+    kEncDictCandidateZero,        // ... at position 0 of V
+    kEncDictReprobe,              // the zero-literal re-probe hit a candidate inside the dictionary
+    kEncDictCatchUpInto,          // the catch-up stepped the ref side from the block back into the dictionary
+    kEncDictCatchUpAtZero,        // the catch-up ended at V[0] with bytes of its own side left
+    kEncDictCountCrossesFirst,    // a forward count started in the dictionary and crossed T in its first 256-byte round
+    kEncDictCountCrossesLater,    // ... in a later round
+    kEncDictBlocks,               // blocks that ran the parse (n >= 13)
+    kEncDictStats
+};
+
 template <bool GENERIC> struct FastTable;
 template <> struct FastTable<false> {   // 64k variant: U16 HashTable[8192], hash shift 19 (lz4.c:567-570,583)
     typedef uint16_t entry;
@@ -36,12 +57,19 @@ template <> struct FastTable<true> {    // generic variant: U32 HashTable[4096],
     static LZ4HIP_DEVICE uint32_t hash(uint32_t word) { return (word * kGolden) >> 20; }
 };
 
+// The input of the search, the count and the catch-up is a type In: `const uint8_t*`, or the two-segment view of a dictionary and a block
+// (lz4hip_encode_dict.hpp, DictInput), which brings its own in + p, in[p], load_u32, load_u64 and wave_copy, and these two:
+LZ4HIP_DEVICE int input_start(const uint8_t*) { return 0; }          // where the block begins in the input
+LZ4HIP_DEVICE void fast_table_init(const uint8_t*, unsigned char*) {}   // what the table starts out as, where not zeroes
+
 // wave-uniform unaligned dword of the input at wave-uniform position p
-LZ4HIP_DEVICE uint32_t input_word(const uint8_t* in, int p) { return wv::uniform(load_u32(in + p)); }
+template <class In>
+LZ4HIP_DEVICE uint32_t input_word(In in, int p) { return wv::uniform(load_u32(in + p)); }
 
 // One lane's share of a 256-byte round of the count below: XOR of its dwords at in[a + off + 4*lane] and in[b + ...],
 // with a sentinel at the first byte that must not be counted (1 = "differs at byte 0" where nothing may be counted).
-LZ4HIP_DEVICE uint32_t common_length_round(const uint8_t* in, int a, int b, int limit, int off)
+template <class In>
+LZ4HIP_DEVICE uint32_t common_length_round(In in, int a, int b, int limit, int off)
 {
     const int pa = a + off + wv::lane() * 4;
     int valid = limit - pa;                           // bytes of this lane's dword that may be counted
@@ -58,7 +86,8 @@ LZ4HIP_DEVICE uint32_t common_length_round(const uint8_t* in, int a, int b, int 
 // Equals the reference's 8-byte XOR/ctz loop plus its 4/2/1-byte tails (lz4.c:698-721).
 // `first_round`: common_length_round(in, a, b, limit, 0), which the caller may have requested earlier (its loads then
 // travel together with those of the catch-up instead of costing a round trip of their own).
-LZ4HIP_DEVICE int wave_common_length(const uint8_t* in, int a, int b, int limit, uint32_t first_round)
+template <class In>
+LZ4HIP_DEVICE int wave_common_length(In in, int a, int b, int limit, uint32_t first_round)
 {
     int total = 0;
     uint32_t diff = first_round;
@@ -74,13 +103,15 @@ LZ4HIP_DEVICE int wave_common_length(const uint8_t* in, int a, int b, int limit,
     }
 }
 
-LZ4HIP_DEVICE int wave_common_length(const uint8_t* in, int a, int b, int limit)
+template <class In>
+LZ4HIP_DEVICE int wave_common_length(In in, int a, int b, int limit)
 {
     return wave_common_length(in, a, b, limit, common_length_round(in, a, b, limit, 0));
 }
 
 // Number of bytes the match can be extended backwards: in[ip-1-i] == in[ref-1-i], i < bound.
-LZ4HIP_DEVICE int wave_catch_up(const uint8_t* in, int ip, int ref, int bound)
+template <class In>
+LZ4HIP_DEVICE int wave_catch_up(In in, int ip, int ref, int bound)
 {
     const int lane = wv::lane();
     int total = 0;
@@ -126,8 +157,8 @@ LZ4HIP_DEVICE int first_probe_offset(int lane) { return lane < 61 ? lane : 2 * l
 // One 64-probe step.  ALLV: every lane's probe is known to be inside the input (the caller tested the last lane's), so nothing of the step
 // runs under a lane mask -- a guarded load or table access is a saveexec / restore pair and a branch each, a dozen of them per step.
 // Returns 0: 64 probes without a match (ip = next probe position), 1: match (ip, ref), 2: ran out of input.
-template <bool GENERIC, bool ALLV>
-LZ4HIP_DEVICE int wave_find_step(const uint8_t* in, typename FastTable<GENERIC>::entry* table, int& ip, int& ref, int mflimit, int attempts,
+template <bool GENERIC, bool ALLV, class In>
+LZ4HIP_DEVICE int wave_find_step(In in, typename FastTable<GENERIC>::entry* table, int& ip, int& ref, int mflimit, int attempts,
                                  bool have_words, uint32_t words)
 {
     typedef FastTable<GENERIC> T;
@@ -187,8 +218,8 @@ LZ4HIP_DEVICE int wave_find_step(const uint8_t* in, typename FastTable<GENERIC>:
     return 0;
 }
 
-template <bool GENERIC>
-LZ4HIP_DEVICE bool wave_find_match(const uint8_t* in, typename FastTable<GENERIC>::entry* table, int& ip, int& ref, int mflimit,
+template <bool GENERIC, class In>
+LZ4HIP_DEVICE bool wave_find_match(In in, typename FastTable<GENERIC>::entry* table, int& ip, int& ref, int mflimit,
                                    bool have_first = false, uint32_t first_words = 0)
 {
     int attempts = 67;
@@ -206,35 +237,43 @@ LZ4HIP_DEVICE bool wave_find_match(const uint8_t* in, typename FastTable<GENERIC
     }
 }
 
-template <bool GENERIC>
-LZ4HIP_DEVICE int encode_fast_block(const uint8_t* in, int n, uint8_t* out, int cap, unsigned char* table_bytes, bool may_defer = false)
+// In = DictInput is the DICT mode (lz4hip_encode_dict.hpp): `in` is the view of V = tail || block, n its length T + n, the block begins at
+// input_start(in) = T and the table starts out primed.  With In = const uint8_t* the start is the constant 0 and the counters are nothing.
+template <bool GENERIC, class In = const uint8_t*>
+LZ4HIP_DEVICE int encode_fast_block(In in, int n, uint8_t* out, int cap, unsigned char* table_bytes, bool may_defer = false)
 {
     typedef FastTable<GENERIC> T;
     typedef typename T::entry entry;
     entry* table = (entry*)table_bytes;
     const int lane = wv::lane();
     const int mflimit = n - kMfLimit, matchlimit = n - kLastLiterals;
-    int ip = 0, anchor = 0, op = 0;
+    const int start = input_start(in);
+    int ip = start, anchor = start, op = 0;
     int sequences = 0, checked_at = 0;                                // (hand-over rule, see kDeferredResult)
 
-    if (n >= kMinLength) {                                            // lz4.c:615
-        // fresh zeroed table per block (lz4.c:583 / `new ushort[8192]`, Unsafe.cs:283)
-        for (int k = lane * 16; k < kFastTableBytes; k += 64 * 16) {
-            Vec16 z = { { 0, 0, 0, 0 } };
-            *(Vec16*)(table_bytes + k) = z;
-        }
+    if (n - start >= kMinLength) {                                    // lz4.c:615
+        if (std::is_pointer<In>::value) {
+            // fresh zeroed table per block (lz4.c:583 / `new ushort[8192]`, Unsafe.cs:283).  (The fill stays HERE: as a function of its own it
+            // changed encode_fast_kernel's listing, profiles/dict_encode/listing_parent_vs_new.txt.)
+            for (int k = lane * 16; k < kFastTableBytes; k += 64 * 16) {
+                Vec16 z = { { 0, 0, 0, 0 } };
+                *(Vec16*)(table_bytes + k) = z;
+            }
+        } else fast_table_init(in, table_bytes);
         wv::mem_sync();
 
         if (GENERIC) {                                                // lz4.c:403: position 0 is inserted
-            const uint32_t h0 = T::hash(input_word(in, 0));           // (a no-op on a zeroed table; kept for clarity)
-            if (lane == 0) table[h0] = 0;
+            const uint32_t h0 = T::hash(input_word(in, start));       // (a no-op on a zeroed table; kept for clarity)
+            if (lane == 0) table[h0] = (entry)start;
         }
-        ip = 1;                                                       // lz4.c:631: position 0 is never probed
+        ip = start + 1;                                               // lz4.c:631: position 0 is never probed
         for (;;) {
             // ---- find a match: lz4.c:642-654, 64 probes of the skip schedule per step ----
             int ref = 0;
             uint32_t cur_word;
             if (!wave_find_match<GENERIC>(in, table, ip, ref, mflimit)) break;
+            LZ4HIP_STAT_ENCDICT(kEncDictCandidate, lane == 0 && ref < start ? 1 : 0);
+            LZ4HIP_STAT_ENCDICT(kEncDictCandidateZero, lane == 0 && ref == 0 && start > 0 ? 1 : 0);
 
             // ---- catch up: lz4.c:657 ----
             // (the first 256 bytes of the forward count are requested before it: the bytes a catch-up adds in front lie
@@ -244,6 +283,8 @@ LZ4HIP_DEVICE int encode_fast_block(const uint8_t* in, int n, uint8_t* out, int 
             {
                 const int room = ip - anchor, bound = room < ref ? room : ref;
                 const int back = bound > 0 ? wave_catch_up(in, ip, ref, bound) : 0;
+                LZ4HIP_STAT_ENCDICT(kEncDictCatchUpInto, lane == 0 && ref >= start && ref - back < start ? 1 : 0);
+                LZ4HIP_STAT_ENCDICT(kEncDictCatchUpAtZero, lane == 0 && start > 0 && back > 0 && back == ref && back < room ? 1 : 0);
                 ip -= back; ref -= back; caught_up = back;
             }
 
@@ -268,6 +309,8 @@ LZ4HIP_DEVICE int encode_fast_block(const uint8_t* in, int n, uint8_t* out, int 
                 ip += kMinMatch; ref += kMinMatch; anchor = ip;
                 // (first sequence of a search: counted from the probe position, `caught_up` bytes further on)
                 ip += caught_up + wave_common_length(in, ip + caught_up, ref + caught_up, matchlimit, fwd_round);
+                LZ4HIP_STAT_ENCDICT(kEncDictCountCrossesFirst, lane == 0 && ref + caught_up < start && ref + (ip - anchor) > start && start - (ref + caught_up) < 256 ? 1 : 0);
+                LZ4HIP_STAT_ENCDICT(kEncDictCountCrossesLater, lane == 0 && ref + caught_up < start && ref + (ip - anchor) > start && start - (ref + caught_up) >= 256 ? 1 : 0);
                 caught_up = 0;
                 const int extra = ip - anchor;
                 if (op + (extra >> 8) > cap - 6) return 0;           // lz4.c:728
@@ -296,6 +339,7 @@ LZ4HIP_DEVICE int encode_fast_block(const uint8_t* in, int n, uint8_t* out, int 
                 }
                 const bool in_range = !GENERIC || ref > ip - (kMaxDistance + 1);   // lz4.c:538
                 if (!(in_range && input_word(in, ref) == cur_word)) break;
+                LZ4HIP_STAT_ENCDICT(kEncDictReprobe, lane == 0 && ref < start ? 1 : 0);
                 token_at = op++;                                      // zero-literal sequence (lz4.c:751)
                 token = 0;
                 fwd_round = common_length_round(in, ip + kMinMatch, ref + kMinMatch, matchlimit, 0);

@@ -389,6 +389,27 @@ int run_host_batch_dict(Stage& st, const lz4hip_batch_t* hb, const void* dict, i
     return run_host_batch(st, hb, dst_len_is_result, make_run(d_dict, reach), 0, slices_knob, threads_knob, limits);
 }
 
+// lz4hip_encode_batch_dict_host (dict_len > 0): the same upload, then the dictionary's primed table (lz4hip_encode_dict.hpp) ONCE per
+// call, into staging of its own, complete before the slice loop starts as the upload is.  The stage has for this
+//
+//     int      dict_prime(device dictionary, bytes, table)   reserves the table's 16 KiB (grow-only), builds it from the uploaded bytes,
+//                                                            WAITS for that, and gives its device address
+//
+// make_run(device dictionary, its length, the table) gives the `run` of the slices, which are the plain encode's (slice_hint:
+// encode_host_slice_blocks).
+template <class Stage, class MakeRun>
+int run_host_batch_encode_dict(Stage& st, const lz4hip_batch_t* hb, const void* dict, int64_t dict_len, MakeRun make_run, int64_t slice_hint,
+                               int slices_knob, int threads_knob, const HostLimits& limits = HostLimits())
+{
+    if (hb->n_blocks == 0) return 0;
+    const uint8_t* d_dict = nullptr;
+    int64_t reach = 0;
+    if (int rc = upload_dictionary(st, dict, dict_len, d_dict, reach)) return rc;
+    uint8_t* table = nullptr;
+    if (int rc = st.dict_prime(d_dict, reach, table)) return rc;
+    return run_host_batch(st, hb, true, make_run(d_dict, reach, (const uint8_t*)table), slice_hint, slices_knob, threads_knob, limits);
+}
+
 // ---- the decoded sizes of a host-pointer batch ---------------------------------------------------------------------------------------
 // lz4hip_decoded_sizes_host: the rows are gathered back to back (the row work above), staged with their lengths in ONE device image of
 // the framing backend B, sized by the device call (framing::decoded_sizes), and only result, dst_off, dst_cap and info come back -- no
