@@ -46,6 +46,17 @@
 // selects between two fresh values stays a select (the tree's first level, T4, T5), and so does what the compiler already folds into one
 // select per assignment (T4 under may_parse, which is a real branch; B4 under pgo).  Sections, their order, kVm and the hand-counted vmcnt are
 // untouched: the regions hold register moves only.
+// A PREDICATE IS ONE COMPARE PER ITERATION in the same kernels (profiles/lane_compares/): priced by class instead of by encoding
+// (tools/isa_lane4_table.py), the vector compares were the largest single class of an iteration -- 57.5 of 264 instructions at 5.5 SIMD-cycles,
+// 4.2 in the middle of other vector work -- and a good part of them asked what the iteration already knew: `kind == k` in T3 and `kind != k` in
+// T5, `rem > 0` beside `rem < 1`, `rem_after == 0` in T5 and again in B3, `hdr == 0` beside `hdr != 0`, the half of the sector as a bool and as a
+// mask, and in B4 an `& flag` on a materialised bool.  Written through plain conditions the compiler canonicalises each use on its own; so each
+// predicate's lane mask is made ONCE and kept (L4_COND = wv::cond_keep), its negation and conjunctions are scalar instructions, and L4_LANE
+// (wv::lane_of) gives the mask back to a branch or a select.  What B4 and T5 ask of the parsed-ahead sequence -- p_st > 0, p_ml == 0,
+// p_off == 0, p_off <= kNearMax, the flags: thirteen compares with pv's -- T4 knows as values when it parses: it leaves a CLASS WORD in `pv`
+// (L4Class: the kind the copy becomes, streamed, final, error; never 0) and the length of that copy in p_len, and B4 / T5 ask the word five times.  Two
+// tests against the end of the source are one (T4).  All of it is per-lane state in vector registers and masks that live inside one
+// iteration; sections, their order, kVm and the vmcnt are untouched, and the kernels with four wavefronts keep the statements they had.
 // Everything else is generation 3's design: dword-interleaved output ring, appends by DS_MSKOR_B32 + v_perm_b32, cooperative
 // flush (four lanes per 64-byte line, or eight per 128-byte unit), far matches fetched from the lane's own output one and a
 // half iterations ahead, parse-ahead of one sequence, a byte-wise parser behind one wave-level branch, hand-counted vmcnt.
@@ -86,6 +97,17 @@ namespace lz4hip {
 // v_mov_b32, or two dwords per v_pk_mov_b32, up to eight dwords per EXEC region) instead of v_cndmask_b32_e64; everywhere else -- the host pass,
 // and the CPU emulation of the wave API, which builds this header as it stands -- they are the selects they replace, one per move and in the
 // same order.  (Only the kernels with kMoves use them, see lane4_decode_block.)
+// A PREDICATE OF THE ITERATION IS ONE COMPARE (the kernels with kMoves): L4_COND is the lane mask of a simple comparison, made once per
+// iteration and kept (wv::cond_keep); everything derived from it -- its negation, its conjunctions with other masks, the same predicate in a
+// later section -- is scalar mask algebra, and L4_LANE hands this lane's bit of a mask to a branch or a select (wv::lane_of).  Everywhere
+// else both are the plain conditions they stand for.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define L4_COND(p_) wv::cond_keep(p_)
+#define L4_LANE(m_) wv::lane_of(m_)
+#else
+#define L4_COND(p_) wv::cond(p_)
+#define L4_LANE(m_) (wv::sel((m_), 1u, 0u) != 0u)
+#endif
 #if defined(__HIP_DEVICE_COMPILE__)
 #define L4_MOV(...) wv::mov_mask(__VA_ARGS__)
 // eight dwords d[0..7] <- the four dwords of a and of b (two 16-byte registers), as four packed moves of register pairs
@@ -147,6 +169,10 @@ enum L4Stat { kL4Fast = 0, kL4TrapToken, kL4TrapHeader, kL4WhyInputEnd, kL4WhyLi
               kL4Stats };
 enum L4Kind { kK4None = 0, kK4Near = 1, kK4Far = 2, kK4Lit = 3, kK4Zero = 4 };
 enum L4Flag { kF4Final = 1, kF4Err = 2, kF4Header = 4 };   // pending sequence: final literal run / corrupt stream / no match yet (its header follows the literals)
+// The CLASS WORD of the parsed-ahead sequence (the kernels with kMoves keep it in `pv`, never 0 while a sequence is pending): the L4Kind its
+// copy becomes in B4 in the low three bits, and what B4 and T5 otherwise ask of p_st, p_ml, p_off and p_flags one compare each: its copy is
+// a literal run (p_st > 0), it is a block's final run, the stream is corrupt.  A far match that is neither is the bare value kK4Far.
+enum L4Class { kC4Kind = 7, kC4Final = 8, kC4Header = 16, kC4Streamed = 64, kC4Err = 128 };
 
 // All 64 lanes of the wavefront call this together and stay in the loop until the last one is done.
 //   R      bytes of output ring per lane (multiple of 16)
@@ -232,6 +258,7 @@ LZ4HIP_DEVICE int lane4_decode_block(unsigned char* lds, int lane, bool active, 
     int gready = 0;              // kK4Far: the 16 bytes fetched in the previous iteration are this lane's next chunk
     // parsed-ahead sequence
     int pv = 0, p_ll = 0, p_st = 0, p_ml = 0, p_off = 0, p_flags = 0, p_res = 0;
+    int p_len = 0;               // (kMoves) length of the copy it becomes: p_st if that is a literal run, else p_ml
     uint32_t p_l0 = 0, p_l1 = 0, p_l2 = 0;
     int hdr = 0;                 // the cursor is at a sequence's offset field (its literals were streamed)
     uint32_t token = 0;
@@ -256,7 +283,7 @@ LZ4HIP_DEVICE int lane4_decode_block(unsigned char* lds, int lane, bool active, 
         out_limit = oend > kLastLiterals ? (uint32_t)(oend - kLastLiterals) : 0u;
         ip = 0; wb = -16 - P; lvalid = 0; pend_a = 0; pend_b = 0; op = 0; fl = 0; oa = lane4;
         kind = kK4None; rem = 0; off = 8; gready = 0;
-        pv = 0; p_ll = 0; p_st = 0; p_ml = 0; p_off = 0; p_flags = 0; p_res = 0; hdr = 0; token = 0;
+        pv = 0; p_ll = 0; p_st = 0; p_ml = 0; p_off = 0; p_flags = 0; p_res = 0; p_len = 0; hdr = 0; token = 0;
         final_seen = 0; final_run = 0; result = 0; done = 0;
         if (!act || (!KNOWN && iend == 0)) { done = 1; final_seen = 1; }   // lz4.c:946 returns -(0)
     };
@@ -369,7 +396,10 @@ LZ4HIP_DEVICE int lane4_decode_block(unsigned char* lds, int lane, bool active, 
         //      cursor; the 16 bytes at the source of the current near match (its ring rows are asked for first: they depend on nothing
         //      the window does, and the window's selects cover their way back) ----
         LZ4HIP_SECTION("T1c near-match reads");
-        const uint32_t offn = kind == kK4Near ? (uint32_t)off : 4u;  // (any other kind: some valid row)
+        // (kMoves: the kinds' lane masks, one compare each for the whole iteration -- `kind` changes in B3 and B4 only, behind their last use)
+        wv::mask_t m_near = {}, m_lit = {}, m_far = {}, m_zero = {};
+        if constexpr (kMoves) { m_near = L4_COND(kind == kK4Near); m_lit = L4_COND(kind == kK4Lit); m_far = L4_COND(kind == kK4Far); m_zero = L4_COND(kind == kK4Zero); }
+        const uint32_t offn = (kMoves ? L4_LANE(m_near) : kind == kK4Near) ? (uint32_t)off : 4u;  // (any other kind: some valid row)
         uint32_t r0, r1, r2, r3, r4;
         {
             // row of output byte op - off: (op >> 2) - ((off - (op & 3) + 3) >> 2) rows back from oa
@@ -385,18 +415,18 @@ LZ4HIP_DEVICE int lane4_decode_block(unsigned char* lds, int lane, bool active, 
         int d = ip + skew - wb;                                      // byte offset of the cursor in W: 0 .. 16 + P (+ 16 while a piece is awaited)
         {
             const bool no_more = wb + 16 + P >= in_total;            // W holds the last piece of the source
-            const bool cross = (d >= P) & ((lvalid != 0) | no_more);
-            const wv::mask_t cm = wv::cond(d >= P) & (wv::cond(lvalid != 0) | wv::cond(no_more));   // (lane masks combined by scalar instructions)
+            const wv::mask_t cm = kMoves ? L4_COND(d >= P) & (L4_COND(lvalid != 0) | L4_COND(no_more))
+                                         : wv::cond(d >= P) & (wv::cond(lvalid != 0) | wv::cond(no_more));   // (lane masks combined by scalar instructions)
+            const bool cross = kMoves ? L4_LANE(cm) : (d >= P) & ((lvalid != 0) | no_more);
             if constexpr (LS && kMoves) {
                 // Twenty conditional assignments, none of them a select: three EXEC regions of moves.  W[0..3] <- W[8..11] comes first (it reads
                 // what the other two overwrite); the piece at wb + 16 + P is the low or the high half of the sector in L, so W[4..11] comes from
                 // L[0..1] under cm & ~hm or from L[2..3] under cm & hm, two dwords per move.  After the low half L stays valid.
-                const bool hi_half = ((wb + 16 + P) & 32) != 0;
-                const wv::mask_t hm = wv::cond(((wb + 16 + P) & 32) != 0);
+                const wv::mask_t hm = L4_COND(((wb + 16 + P) & 32) != 0);
                 L4_MOV(cm, W[0], W[8], W[1], W[9], W[2], W[10], W[3], W[11]);
                 L4_MOV8(cm & ~hm, W + 4, L[0], L[1]);
                 L4_MOV8(cm & hm, W + 4, L[2], L[3]);
-                lvalid = (cross & hi_half) ? 0 : lvalid;
+                lvalid = L4_LANE(cm & hm) ? 0 : lvalid;
             } else if constexpr (LS) {
                 // (the select form) the piece at wb + 16 + P is the low or the high half of the sector in L; after the low half L stays valid
 #pragma unroll
@@ -424,7 +454,9 @@ LZ4HIP_DEVICE int lane4_decode_block(unsigned char* lds, int lane, bool active, 
             d -= cross ? P : 0;
         }
         LZ4HIP_SECTION("T1b cursor view (select tree + rotation)");
-        const bool staged16 = d < P;                                 // the 16 bytes at the cursor lie in W (what lies past the source is never used)
+        wv::mask_t m_staged = {};
+        if constexpr (kMoves) m_staged = L4_COND(d < P);
+        const bool staged16 = kMoves ? L4_LANE(m_staged) : d < P;    // the 16 bytes at the cursor lie in W (what lies past the source is never used)
         LZ4HIP_STAT(0, true); LZ4HIP_STAT(1, done == 0); LZ4HIP_STAT(2, (done == 0) & !staged16);
         uint32_t x0, x1, x2, x3;
         {
@@ -463,17 +495,29 @@ LZ4HIP_DEVICE int lane4_decode_block(unsigned char* lds, int lane, bool active, 
 
         LZ4HIP_SECTION("T3 chunk size");
         // ---- (T3) size of this iteration's chunk of the current copy (appended at the bottom) ----
-        const bool room = op - fl <= R - 46;                         // this iteration's appends (<= 16 + 11 bytes + 19 of overshoot) stay clear of unflushed output
-        const bool near = kind == kK4Near, lit = kind == kK4Lit;
-        const bool can = room & (rem > 0) & !((kind == kK4Far) & (gready == 0)) & !(lit & !staged16);
-        const int stride = (near & (off < 16)) ? off : 16;          // a near match whose source would overlap the chunk copies `off` bytes and doubles off
+        // (kMoves: every predicate below is ONE compare of this iteration -- its mask is kept and T4, T5, B3 and B4 combine the masks; the
+        //  other kernels compare where they use, as they did)
+        wv::mask_t m_room = {}, m_rem = {}, m_can = {}, m_dbl = {};
+        if constexpr (kMoves) {
+            m_room = L4_COND(op - fl <= R - 46);
+            m_rem = L4_COND(rem > 0);
+            m_can = m_room & m_rem & ~(m_far & L4_COND(gready == 0)) & ~(m_lit & ~m_staged);
+            m_dbl = m_near & L4_COND(off < 16);
+        }
+        const bool room = kMoves ? L4_LANE(m_room) : op - fl <= R - 46;   // this iteration's appends (<= 16 + 11 bytes + 19 of overshoot) stay clear of unflushed output
+        const bool near = kMoves ? L4_LANE(m_near) : kind == kK4Near, lit = kMoves ? L4_LANE(m_lit) : kind == kK4Lit;
+        const bool can = kMoves ? L4_LANE(m_can) : room & (rem > 0) & !((kind == kK4Far) & (gready == 0)) & !(lit & !staged16);
+        const int stride = (kMoves ? L4_LANE(m_dbl) : near & (off < 16)) ? off : 16;   // a near match whose source would overlap the chunk copies `off` bytes and doubles off
         int n = can ? (rem < stride ? rem : stride) : 0;
-        n = ((kind == kK4Zero) & (n > 8)) ? 8 : n;
+        if constexpr (kMoves) n = L4_LANE(m_zero) ? (n < 8 ? n : 8) : n;
+        else n = ((kind == kK4Zero) & (n > 8)) ? 8 : n;
         LZ4HIP_STAT(5, (done == 0) & (rem > 0)); LZ4HIP_STAT(6, (done == 0) & (rem > 0) & (n == 0)); LZ4HIP_STAT(7, (done == 0) & (rem > 0) & !room);
         LZ4HIP_STAT(8, (done == 0) & (rem > 0) & (kind == kK4Far) & (gready == 0)); LZ4HIP_STAT(9, (done == 0) & (rem > n));
         LZ4HIP_STAT_L4(kL4RoomBelow, (done == 0) & !FLUSH & (rem > 0) & (op - fl == R - 47)); LZ4HIP_STAT_L4(kL4RoomLast, (done == 0) & !FLUSH & (rem > 0) & (op - fl == R - 46));
         LZ4HIP_STAT_L4(kL4RoomNone, (done == 0) & !FLUSH & (rem > 0) & (op - fl == R - 45));
         const int rem_after = rem - n;
+        wv::mask_t m_rem0 = {};                                         // (kMoves) the current copy ends in this iteration, or there is none: T5, B3 and B4 ask
+        if constexpr (kMoves) m_rem0 = L4_COND(rem_after == 0);
         const int op_end = op + rem;                                 // where the current copy ends = where the parsed-ahead sequence's literals go
 
         LZ4HIP_SECTION("T2c ring rows");
@@ -494,20 +538,27 @@ LZ4HIP_DEVICE int lane4_decode_block(unsigned char* lds, int lane, bool active, 
 
         LZ4HIP_SECTION("T4 parse ahead");
         // ---- (T4) parse ahead: the next sequence's header (needs only the cursor) ----
-        const bool may_parse = (pv == 0) & (final_seen == 0) & !(lit & (rem > 0)) & staged16;
+        const bool may_parse = kMoves ? L4_LANE(L4_COND((pv | final_seen) == 0) & ~(m_lit & m_rem) & m_staged)
+                                      : (pv == 0) & (final_seen == 0) & !(lit & (rem > 0)) & staged16;
         LZ4HIP_STAT(10, may_parse); LZ4HIP_STAT(11, (done == 0) & (pv != 0));
         if (may_parse) {
-            const uint32_t tok = hdr ? token : (x0 & 255u);
+            wv::mask_t m_h0 = {};                                     // (kMoves: hdr == 0 and hdr != 0 are one compare)
+            if constexpr (kMoves) m_h0 = L4_COND(hdr == 0);
+#define L4_H0_ (kMoves ? L4_LANE(m_h0) : hdr == 0)
+#define L4_HN_ (kMoves ? L4_LANE(~m_h0) : hdr != 0)
+            const uint32_t tok = L4_HN_ ? token : (x0 & 255u);
             const uint32_t t4 = tok >> 4, b1 = (x0 >> 8) & 255u, mlc = tok & 15u;
-            const bool e1 = (hdr == 0) & (t4 == 15u), e2 = mlc == 15u;
-            const int ll = hdr ? 0 : (int)t4 + (e1 ? (int)b1 : 0);
-            const bool in_win = (hdr != 0) | (t4 <= 11u);             // literals (<= 11, no length byte), offset and first match-length byte are within 16 bytes
-            const int o = hdr ? 0 : 1 + (int)t4;                      // position of the offset field when in_win (0 .. 12)
+            const bool e1 = L4_H0_ & (t4 == 15u), e2 = mlc == 15u;
+            const int ll = L4_HN_ ? 0 : (int)t4 + (e1 ? (int)b1 : 0);
+            const bool in_win = L4_HN_ | (t4 <= 11u);                 // literals (<= 11, no length byte), offset and first match-length byte are within 16 bytes
+            const int o = L4_HN_ ? 0 : 1 + (int)t4;                   // position of the offset field when in_win (0 .. 12)
             // offset + first match-length byte: bytes o .. o + 2 of the 16-byte view
             uint32_t ot;
             {
                 const uint32_t q = (uint32_t)o >> 2;
-                const wv::mask_t m1 = wv::cond((q & 1u) != 0u), m2 = wv::cond((q & 2u) != 0u);
+                // (kMoves: bit 1 of q as a range test on the token -- o >= 8 is t4 >= 7 -- instead of a bit field and a compare; a token of
+                //  0xF0 and more, where o = 16 has the bit clear, is not in_win and ot is not used)
+                const wv::mask_t m1 = wv::cond((q & 1u) != 0u), m2 = kMoves ? m_h0 & L4_COND(tok >= 0x70u) : wv::cond((q & 2u) != 0u);
                 const uint32_t lo = wv::sel(m2, wv::sel(m1, x3, x2), wv::sel(m1, x1, x0));
                 const uint32_t hi = wv::sel(m2, x3, wv::sel(m1, x2, x1));     // (q == 3: o == 12, byte phase 0, hi is not used)
                 ot = wv::alignbyte(hi, lo, (uint32_t)o & 3u);
@@ -519,10 +570,13 @@ LZ4HIP_DEVICE int lane4_decode_block(unsigned char* lds, int lane, bool active, 
             const int p_after = ip + o + 2;                          // after the offset field
             // what the 16-byte view cannot decide goes to the byte-wise parser: the end of the source, length bytes of 255,
             // the final literal run (lz4.c:851 / :965), every error (lz4.c:863,893 / :980,1024)
-            bool trap = (ip + 16 > iend) | (e1 & (b1 == 255u)) | (ip + 1 + (e1 ? 1 : 0) + ll > iend);
+            // (kMoves: the 16-byte view and the literals against the end of the source in ONE compare.  Without a length byte ll <= 14 and
+            //  ip + 1 + ll > iend implies ip + 16 > iend; with one, ip + 2 + ll = ip + 17 + b1 > iend is implied by ip + 16 > iend)
+            bool trap = kMoves ? (ip + 16 + (e1 ? 1 + (int)b1 : 0) > iend) | (e1 & (b1 == 255u))
+                               : (ip + 16 > iend) | (e1 & (b1 == 255u)) | (ip + 1 + (e1 ? 1 : 0) + ll > iend);
             trap |= in_win & ((e2 & (extb == 255u)) | (vo > lit_end) | ((uint32_t)lit_end + (uint32_t)ml > out_limit));   // (lit_end < 2^31 + 270, ml <= 274: no wrap)
-            if (KNOWN) trap |= (hdr == 0) & (lit_end > oend - 8);
-            else       trap |= ((hdr == 0) & ((lit_end > oend - kMfLimit) | (ip + 1 + (e1 ? 1 : 0) + ll > iend - 8))) | (in_win & e2 & !(p_after < iend - (kLastLiterals + 1)));
+            if (KNOWN) trap |= L4_H0_ & (lit_end > oend - 8);
+            else       trap |= (L4_H0_ & ((lit_end > oend - kMfLimit) | (ip + 1 + (e1 ? 1 : 0) + ll > iend - 8))) | (in_win & e2 & !(p_after < iend - (kLastLiterals + 1)));
             LZ4HIP_STAT_L4(kL4Fast, !trap); LZ4HIP_STAT_L4(kL4TrapToken, trap & (hdr == 0)); LZ4HIP_STAT_L4(kL4TrapHeader, trap & (hdr != 0));
             LZ4HIP_STAT_L4(kL4WhyInputEnd, ip + 16 > iend); LZ4HIP_STAT_L4(kL4WhyLitByte255, e1 & (b1 == 255u)); LZ4HIP_STAT_L4(kL4WhyLitPastInput, ip + 1 + (e1 ? 1 : 0) + ll > iend);
             // (the three tests of a match header are counted where the literals are no last run: behind a block's last token there is no header)
@@ -540,6 +594,13 @@ LZ4HIP_DEVICE int lane4_decode_block(unsigned char* lds, int lane, bool active, 
             p_ml = in_win ? ml : 0;
             p_off = vo;
             p_flags = in_win ? 0 : (int)kF4Header;
+            // (kMoves) the class word and the length of the copy: in the view a sequence has a match (ml >= 4) and its kind is its offset's;
+            // outside it has twelve literals or more and they are streamed.  T4x writes its own.
+            int cls = 1;
+            if constexpr (kMoves) {
+                p_len = in_win ? ml : ll;
+                cls = in_win ? (vo == 0 ? (int)kK4Zero : (vo > kNearMax ? (int)kK4Far : (int)kK4Near)) : (int)kK4Lit | kC4Streamed | kC4Header;
+            }
             const int ip_fast = in_win ? p_after + (e2 ? 1 : 0) : ip + 1 + (e1 ? 1 : 0);
             if (trap) {
                 LZ4HIP_SECTION("T4x byte-wise parser (trap)");
@@ -594,12 +655,20 @@ LZ4HIP_DEVICE int lane4_decode_block(unsigned char* lds, int lane, bool active, 
                 }
                 if (err != 0) { p_flags = kF4Err; p_res = err; }
                 hdr = (p_flags & kF4Header) ? 1 : 0;
+                if constexpr (kMoves) {                              // (what B4 makes of p_st, p_ml, p_off and p_flags in the other kernels)
+                    const bool streamed = p_st > 0;
+                    p_len = streamed ? p_st : p_ml;
+                    cls = (streamed ? (int)kK4Lit | kC4Streamed : (p_ml == 0 ? (int)kK4None : (p_off == 0 ? (int)kK4Zero : (p_off <= kNearMax ? (int)kK4Near : (int)kK4Far))))
+                        | ((p_flags & kF4Final) ? (int)kC4Final : 0) | ((p_flags & kF4Header) ? (int)kC4Header : 0) | ((p_flags & kF4Err) ? (int)kC4Err : 0);
+                }
             } else {
                 ip = ip_fast;
                 hdr = in_win ? 0 : 1;
             }
+#undef L4_H0_
+#undef L4_HN_
             LZ4HIP_SECTION("T4 parse ahead");
-            pv = 1;
+            pv = cls;                                                // (1, or with kMoves the class word: never 0)
         }
 
         LZ4HIP_SECTION("T2d flush stores");
@@ -618,9 +687,11 @@ LZ4HIP_DEVICE int lane4_decode_block(unsigned char* lds, int lane, bool active, 
         // what it holds simply fetches the same bytes again)
         {
             // (the lane masks of the simple comparisons, combined by scalar instructions)
-            const wv::mask_t m_rem0 = wv::cond(rem_after == 0);
-            const wv::mask_t f_cont = wv::cond(kind == kK4Far) & ~m_rem0;
-            const wv::mask_t f_first = m_rem0 & wv::cond(op - fl <= R - 46) & wv::cond(pv != 0) & wv::cond(p_ml != 0) & wv::cond(p_flags == 0) & wv::cond(p_off > kNearMax);
+            // (kMoves: a pending far match without a flag is the class word kK4Far, and no class word is 0)
+            const wv::mask_t m_end = kMoves ? m_rem0 : wv::cond(rem_after == 0);
+            const wv::mask_t f_cont = (kMoves ? m_far : wv::cond(kind == kK4Far)) & ~m_end;
+            const wv::mask_t f_first = kMoves ? m_end & m_room & L4_COND(pv == (int)kK4Far)
+                                              : m_end & wv::cond(op - fl <= R - 46) & wv::cond(pv != 0) & wv::cond(p_ml != 0) & wv::cond(p_flags == 0) & wv::cond(p_off > kNearMax);
             const int f_pos = (int)wv::sel(f_cont, (uint32_t)(op + n - off), (uint32_t)(op_end + p_ll - p_off));
             const wv::mask_t f_want = f_cont | f_first;
             const wv::mask_t f_do = f_want & wv::cond(f_pos + 16 <= fl);
@@ -670,8 +741,8 @@ LZ4HIP_DEVICE int lane4_decode_block(unsigned char* lds, int lane, bool active, 
         {
             // the source of the chunk: the near-match rows, unless it is literals or a far match
             if constexpr (kMoves) {                                  // (two EXEC regions of four moves)
-                L4_MOV(wv::cond(kind == kK4Lit), v0, x0, v1, x1, v2, x2, v3, x3);
-                L4_MOV(wv::cond(kind == kK4Far), v0, (uint32_t)usF.x, v1, (uint32_t)usF.y, v2, (uint32_t)usF.z, v3, (uint32_t)usF.w);
+                L4_MOV(m_lit, v0, x0, v1, x1, v2, x2, v3, x3);
+                L4_MOV(m_far, v0, (uint32_t)usF.x, v1, (uint32_t)usF.y, v2, (uint32_t)usF.z, v3, (uint32_t)usF.w);
             } else {
                 const bool far_src = kind == kK4Far;
                 v0 = lit ? x0 : (far_src ? usF.x : v0);
@@ -679,7 +750,8 @@ LZ4HIP_DEVICE int lane4_decode_block(unsigned char* lds, int lane, bool active, 
                 v2 = lit ? x2 : (far_src ? usF.z : v2);
                 v3 = lit ? x3 : (far_src ? usF.w : v3);
             }
-            if ((kind == kK4Zero) & (n > 0)) {                       // offset 0 (corrupt streams only): keep what dst holds, 8 bytes at a time
+            // (kMoves: n > 0 is `can` -- rem > 0 and a stride of at least 1)
+            if (kMoves ? L4_LANE(m_zero & m_can) : (kind == kK4Zero) & (n > 0)) {   // offset 0 (corrupt streams only): keep what dst holds, 8 bytes at a time
                 uint64_t acc = 0;
                 for (int b = 0; b < n; b++) acc |= (uint64_t)dst[op + b] << (8 * b);
                 v0 = (uint32_t)acc; v1 = (uint32_t)(acc >> 32);
@@ -687,25 +759,40 @@ LZ4HIP_DEVICE int lane4_decode_block(unsigned char* lds, int lane, bool active, 
             ip += lit ? n : 0;
             L4_APPEND(v0, v1, v2, v3, n, true);
             rem = rem_after;
-            LZ4HIP_STAT_L4(kL4Doubling, near & (off < 16) & (n > 0));
-            off = (near & (off < 16) & (n > 0)) ? off * 2 : off;
-            kind = rem == 0 ? (int)kK4None : kind;
+            const bool dbl = kMoves ? L4_LANE(m_dbl & m_can) : near & (off < 16) & (n > 0);
+            LZ4HIP_STAT_L4(kL4Doubling, dbl);
+            off = dbl ? off * 2 : off;
+            kind = (kMoves ? L4_LANE(m_rem0) : rem == 0) ? (int)kK4None : kind;
         }
 
         LZ4HIP_SECTION("B4 promote + literal append");
         // ---- (B4) promote the parsed-ahead sequence: its inline literals, then its copy becomes the current one ----
         {
-            const bool promote = (rem == 0) & (pv != 0) & room;
+            wv::mask_t m_prom = {}, m_pgo = {};                     // (kMoves: the class word says what the other kernels ask p_flags, p_st, p_ml and p_off)
+            if constexpr (kMoves) {
+                m_prom = m_rem0 & m_room & L4_COND(pv != 0);
+                m_pgo = m_prom & ~L4_COND(pv >= (int)kC4Err);
+            }
+            const bool promote = kMoves ? L4_LANE(m_prom) : (rem == 0) & (pv != 0) & room;
             LZ4HIP_STAT(12, promote); LZ4HIP_STAT(13, (done == 0) & (rem == 0) & (pv != 0) & !room); LZ4HIP_STAT(14, (done == 0) & (rem == 0) & (pv == 0));
-            const bool perr = promote & ((p_flags & kF4Err) != 0);
-            const bool pgo = promote & !perr;
+            const bool perr = kMoves ? L4_LANE(m_prom & ~m_pgo) : promote & ((p_flags & kF4Err) != 0);
+            const bool pgo = kMoves ? L4_LANE(m_pgo) : promote & !perr;
             L4_APPEND(p_l0, p_l1, p_l2, 0u, pgo ? p_ll : 0, false);
             if (perr) {                                              // corrupt stream: this lane is finished, nothing more is stored
                 done = 1; final_seen = 1; final_run = 0; result = p_res;
             }
             // (every assignment below is ONE select already -- the compiler folds pgo into the lane mask with scalar instructions -- so a region
             //  of moves would add its moves to the selects of the new values: tried, +5 vector-ALU instructions per iteration)
-            if (pgo) {
+            if constexpr (kMoves) {
+                // (five selects under masks: with an error out of the way, a class word of kC4Streamed and more is a literal run)
+                const wv::mask_t m_fin = m_pgo & L4_COND((pv & kC4Final) != 0);
+                rem = L4_LANE(m_pgo) ? p_len : rem;
+                off = L4_LANE(m_pgo & ~L4_COND(pv >= (int)kC4Streamed)) ? p_off : off;
+                kind = L4_LANE(m_pgo) ? (pv & kC4Kind) : kind;
+                final_run = L4_LANE(m_fin) ? 1 : final_run;
+                result = L4_LANE(m_fin) ? p_res : result;
+                LZ4HIP_STAT_L4(kL4ToNear, pgo & (kind == kK4Near)); LZ4HIP_STAT_L4(kL4ToFar, pgo & (kind == kK4Far)); LZ4HIP_STAT_L4(kL4ToZero, pgo & (kind == kK4Zero)); LZ4HIP_STAT_L4(kL4ToLit, pgo & (kind == kK4Lit));
+            } else if (pgo) {
                 const bool streamed = p_st > 0;
                 rem = streamed ? p_st : p_ml;
                 off = streamed ? off : p_off;

@@ -209,6 +209,18 @@ LZ4HIP_DEVICE uint32_t sel(mask_t m, uint32_t a, uint32_t b)      // m ? a : b
     asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(r) : "v"(b), "v"(a), "s"(m.v));
     return r;
 }
+// A lane mask the compiler KEEPS: one compare, written once, whose SGPR pair every later use reads -- `m`, `~m`, or this lane's bit of a
+// combination of masks (lane_of).  Through cond() alone the compiler sees the comparison behind the mask and canonicalises each use on its
+// own: `x == k` here and `x != k` there, or a mask and the bool it came from, are then TWO vector compares, and a compare is the dearest
+// vector-ALU instruction the lane decoder issues (tools/microbench_valu_rate.hip).  The empty asm statement is no instruction.
+LZ4HIP_DEVICE mask_t cond_keep(bool p)
+{
+    mask_t m = cond(p);
+    asm("" : "+s"(m.v));
+    return m;
+}
+// this lane's bit of a mask, as the condition of a branch or of a select: no instruction either
+LZ4HIP_DEVICE bool lane_of(mask_t m) { return __builtin_amdgcn_inverse_ballot_w64(m.v); }
 // ---- conditional assignments: moves under a lane mask (lz4hip_decode_lane4.hpp) ---------------------------------------------
 // x = m ? a : x needs no select.  It is v_mov_b32 x, a issued with EXEC = m: a 32-bit encoding, where v_cndmask_b32_e64 is a 64-bit
 // one, and at three wavefronts per SIMD the 64-bit encodings are what the issue rate charges for (tools/microbench_valu_rate.hip,
