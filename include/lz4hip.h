@@ -159,8 +159,9 @@ int lz4hip_decode_batch_dict_host(const lz4hip_batch_t* b, const void* dict, int
  * The host call stages the blocks as lz4hip_encode_batch_host does (one pipeline, that call's slices); the dictionary's reachable bytes
  * are uploaded once per call and its table is primed once per call, both into per-thread grow-only device memory (freed by
  * lz4hip_release_workspaces), and both have landed before any slice's kernels start.
- * Out of scope: LZ4 frames with a dictionary on the ENCODE side (the next step: LZ4F_compressFrame_usingCDict is this call under the
- * frame rounds); LZ4HC against a dictionary; a dictionary per block; the lane mapping; a _multi host form; the packed encode form. */
+ * Out of scope: LZ4HC against a dictionary; a dictionary per block; the lane mapping; a _multi host form; the packed encode form.
+ * (LZ4 frames with a dictionary on the encode side -- LZ4F_compressFrame_usingCDict -- are this call under the frame rounds:
+ * lz4hip_lz4f_encode_dict_* and lz4hip_lz4f_batch_encode_dict_*, "LZ4 frames encoded with a dictionary" below.) */
 int64_t lz4hip_encode_dict_scratch_bytes(int64_t dict_len);
 int lz4hip_encode_batch_dict_device(const lz4hip_batch_t* b, const void* dict, int64_t dict_len, void* scratch, int64_t scratch_bytes, void* stream);
 int lz4hip_encode_batch_dict_host(const lz4hip_batch_t* b, const void* dict, int64_t dict_len);
@@ -855,7 +856,8 @@ int lz4hip_lz4f_decode_host(const void* src, int64_t src_len, unsigned flags, vo
  * COST: the rounds of a dictionary call decode EVERY compressed independent block with one wavefront per block at every batch size, as
  * lz4hip_decode_batch_dict_device does (the lane mapping has no dictionary mode): lz4hip_dispatch_counts moves LZ4HIP_K_DECODE_WAVE only,
  * and a large batch decodes at that mapping's rate.  Linked items run one wavefront each, as in the plain calls.
- * Out of scope: encoding frames with a dictionary; a dictionary per item; the lane mapping for dictionary rows; span forms. */
+ * Out of scope: a dictionary per item; the lane mapping for dictionary rows; span forms.  (Encoding frames with a dictionary:
+ * lz4hip_lz4f_encode_dict_* and lz4hip_lz4f_batch_encode_dict_*, below.) */
 int lz4hip_lz4f_decode_dict_device(const void* src, int64_t src_len, const void* dict, int64_t dict_len, uint32_t dict_id, int32_t slot_bytes,
                                    int64_t max_blocks, int64_t round_blocks, unsigned flags, void* scratch, int64_t scratch_bytes, void* dst, int64_t dst_cap,
                                    lz4hip_lz4f_info_t* info, void* stream);
@@ -928,6 +930,51 @@ int lz4hip_lz4f_batch_decode_dict_device(const void* src, int64_t src_len, const
 int lz4hip_lz4f_batch_decode_dict_host(const void* src, int64_t src_len, const int64_t* src_off, int64_t n, const void* dict, int64_t dict_len, uint32_t dict_id,
                                        unsigned flags, void* dst, int64_t dst_cap, int64_t* dst_off, lz4hip_lz4f_info_t* item_info,
                                        lz4hip_lz4f_batch_info_t* info);
+
+/* ---- LZ4 frames encoded with a dictionary -----------------------------------------------------------------
+ * LZ4F_compressFrame_usingCDict with independent blocks, and K4os' streams with a dictionary: lz4hip_encode_batch_dict_device under the
+ * frame rounds.  The argument order mirrors the decode side: dict, dict_len, dict_id go behind the source arguments.
+ *   MODE: fast mode only -- there is no `mode` argument.  LZ4HC against a dictionary is out of scope.
+ *   BLOCKS: independent (FLG.5 is set).  Every block is encoded against the SAME dictionary and never sees the block before it, which is
+ * what LZ4F_compressFrame_usingCDict does with independent blocks.  The raw-store rule is the plain frame encoder's: the block encoder
+ * gets length - 1 bytes of room, and a result of 0 stores the block raw.
+ *   BLOCK BYTES: block k's bytes are exactly what lz4hip_encode_batch_dict_device writes for that block with dst_cap = len - 1 and the
+ * same dictionary -- the parse that call's section defines.  The frame therefore decodes with lz4hip_lz4f_decode_dict_* and with
+ * LZ4F_decompress_usingDict.
+ *   dict_id != 0: FLG.0 is set and the 4-byte little-endian ID sits behind the content size (behind BD when there is no size); the HC
+ * byte is computed over it; the descriptor is 4 bytes longer, 11 or 19 bytes.  dict_id == 0: no ID is written, as liblz4 does for
+ * dictID = 0; the dictionary is still used.
+ *   DICTIONARY: only its last 65 535 bytes are read, and nothing outside [dict, dict + dict_len); any alignment; the device calls do not
+ * copy it.  dict_len == 0: dict may be NULL, dict_id is ignored, and the call IS lz4hip_lz4f_encode_device /
+ * lz4hip_lz4f_batch_encode_device with LZ4HIP_MODE_FAST, byte for byte; the two bounds and the two scratch queries return the plain
+ * queries' values.
+ *   ARGUMENTS: dict_len < 0, dict == NULL with dict_len > 0, an unknown flag, a bad block_size_id, dst_cap below the bound and scratch
+ * below the query return LZ4HIP_E_ARGUMENT, checked before a device is looked for.
+ *   DEVICE CALLS: launch-only on `stream`; they read no device value on the host and allocate nothing.  The 16 KiB primed table lives in
+ * the caller's scratch (the query includes it when dict_len > 0) and is built once per call by encode_dict_prime_kernel, before the block
+ * encoder runs (a one-frame call with an empty source has no block and primes nothing).
+ *   BATCH: item i's frame is byte for byte what the one-frame dictionary call writes for that item alone; an empty item carries no
+ * content size; an item with bad offsets takes 0 bytes; one dictionary and one ID serve the whole call; ONE block encoder launch runs over
+ * the blocks of all items.
+ *   HOST FORMS: the dictionary's reachable tail goes up once per call, into staging apart from the image; the table is primed once; the
+ * device sequence runs over one image.  Offsets that decrease or leave [0, src_len] are refused, as in lz4hip_lz4f_batch_encode_host.
+ *   COST: as lz4hip_encode_batch_dict_device -- the wavefront mapping at every batch size, in workgroups of one or five blocks;
+ * lz4hip_dispatch_counts moves LZ4HIP_K_ENCODE_WAVE only; there is no lane mapping.
+ * Out of scope: LZ4HC with a dictionary; linked-block frames on the encode side; a dictionary per item; a _multi host form; the packed
+ * encode form with a dictionary; the lane mapping for dictionary rows. */
+int64_t lz4hip_lz4f_dict_bound(int64_t src_len, int block_size_id, unsigned flags, int64_t dict_len, uint32_t dict_id);
+int64_t lz4hip_lz4f_encode_dict_scratch_bytes(int64_t src_len, int block_size_id, int64_t dict_len);
+int lz4hip_lz4f_encode_dict_device(const void* src, int64_t src_len, const void* dict, int64_t dict_len, uint32_t dict_id, int block_size_id, unsigned flags,
+                                   void* dst, int64_t dst_cap, int64_t* dst_len, void* scratch, int64_t scratch_bytes, void* stream);
+int lz4hip_lz4f_encode_dict_host(const void* src, int64_t src_len, const void* dict, int64_t dict_len, uint32_t dict_id, int block_size_id, unsigned flags,
+                                 void* dst, int64_t dst_cap, int64_t* dst_len);
+int64_t lz4hip_lz4f_batch_dict_bound(int64_t n, int64_t src_len, int block_size_id, unsigned flags, int64_t dict_len, uint32_t dict_id);
+int64_t lz4hip_lz4f_batch_encode_dict_scratch_bytes(int64_t n, int64_t src_len, int block_size_id, int64_t dict_len);
+int lz4hip_lz4f_batch_encode_dict_device(const void* src, int64_t src_len, const int64_t* src_off, int64_t n, const void* dict, int64_t dict_len, uint32_t dict_id,
+                                         int block_size_id, unsigned flags, void* dst, int64_t dst_cap, int64_t* dst_off, void* scratch, int64_t scratch_bytes,
+                                         void* stream);
+int lz4hip_lz4f_batch_encode_dict_host(const void* src, int64_t src_len, const int64_t* src_off, int64_t n, const void* dict, int64_t dict_len, uint32_t dict_id,
+                                       int block_size_id, unsigned flags, void* dst, int64_t dst_cap, int64_t* dst_off);
 
 /* ---- diagnostics ---------------------------------------------------------------------------------
  * Launch counters per kernel family since the library was loaded: which block->hardware mapping a call

@@ -231,6 +231,19 @@ SYMBOLS = [
                                                        C.c_void_p, C.c_void_p]),
     ("lz4hip_lz4f_batch_decode_dict_host", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_uint32, C.c_uint, C.c_void_p,
                                                      C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(Lz4fBatchInfo)]),
+    # the encode with a dictionary (fast mode only: no mode argument)
+    ("lz4hip_lz4f_dict_bound", C.c_int64, [C.c_int64, C.c_int, C.c_uint, C.c_int64, C.c_uint32]),
+    ("lz4hip_lz4f_encode_dict_scratch_bytes", C.c_int64, [C.c_int64, C.c_int, C.c_int64]),
+    ("lz4hip_lz4f_encode_dict_device", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_uint32, C.c_int, C.c_uint, C.c_void_p, C.c_int64, C.c_void_p,
+                                                 C.c_void_p, C.c_int64, C.c_void_p]),
+    ("lz4hip_lz4f_encode_dict_host", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_uint32, C.c_int, C.c_uint, C.c_void_p, C.c_int64,
+                                               C.POINTER(C.c_int64)]),
+    ("lz4hip_lz4f_batch_dict_bound", C.c_int64, [C.c_int64, C.c_int64, C.c_int, C.c_uint, C.c_int64, C.c_uint32]),
+    ("lz4hip_lz4f_batch_encode_dict_scratch_bytes", C.c_int64, [C.c_int64, C.c_int64, C.c_int, C.c_int64]),
+    ("lz4hip_lz4f_batch_encode_dict_device", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_uint32, C.c_int, C.c_uint,
+                                                       C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    ("lz4hip_lz4f_batch_encode_dict_host", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_uint32, C.c_int, C.c_uint,
+                                                     C.c_void_p, C.c_int64, C.c_void_p]),
 ]
 
 _lib = None

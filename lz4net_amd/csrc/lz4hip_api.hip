@@ -1326,6 +1326,8 @@ struct HipBackend {
     int decode(const lz4hip_batch_t* b, int known) { return launch_decode(b, known, stream); }
     // (the dictionary calls of LZ4 frames: `reach` <= 65 535 bytes that end at dict_end)
     int decode_dict(const lz4hip_batch_t* b, const uint8_t* dict_end, int32_t reach, int known) { return launch_decode_dict(b, dict_end - reach, reach, known, stream); }
+    int encode_dict_prime(const uint8_t* dict_end, int32_t reach, uint8_t* primed) { return launch_encode_dict_prime(dict_end - reach, reach, primed, stream); }
+    int encode_dict(const lz4hip_batch_t* b, const uint8_t* dict_end, int32_t reach, const uint8_t* primed) { return launch_encode_dict(b, dict_end - reach, reach, primed, stream); }
     int dict_upload(const uint8_t* from, int64_t bytes, uint8_t*& dev) { return host->dict_upload(from, bytes, dev); }
     int last_error() { HIP_TRY(hipGetLastError()); return 0; }
     int fail(int code, const std::string& what) { return ::fail(code, what); }
@@ -2162,6 +2164,44 @@ int lz4hip_lz4f_decode_dict_host(const void* src, int64_t src_len, const void* d
     return lz4f_decode_dict_host(be, src, src_len, dict, dict_len, dict_id, flags, dst, dst_cap, info);
 }
 
+// The dictionary encode: the plain call's plan in fast mode behind the dictionary's check, with the dictionary's bound, scratch and head
+// length, then the sequence with the dictionary handed to the block encoder and the head kernel (lz4hip_framing.hpp); with dict_len == 0
+// the plain sequence.
+int64_t lz4hip_lz4f_dict_bound(int64_t src_len, int block_size_id, unsigned flags, int64_t dict_len, uint32_t dict_id)
+{
+    return lz4f_dict_bound(src_len, block_size_id, flags, dict_len, dict_id);
+}
+
+int64_t lz4hip_lz4f_encode_dict_scratch_bytes(int64_t src_len, int block_size_id, int64_t dict_len)
+{
+    if (dict_len < 0) return fail(LZ4HIP_E_ARGUMENT, "dictionary: dict_len < 0");
+    if (!lz4f_id_valid(block_size_id)) return fail(LZ4HIP_E_ARGUMENT, "lz4f encode: block_size_id must be 0 (64 KiB) or 4 .. 7");
+    return lz4f_encode_scratch(nullptr, src_len < 0 ? 0 : src_len, lz4f_block_bytes(lz4f_id(block_size_id)), dict_len).bytes;
+}
+
+int lz4hip_lz4f_encode_dict_device(const void* src, int64_t src_len, const void* dict, int64_t dict_len, uint32_t dict_id, int block_size_id, unsigned flags,
+                                   void* dst, int64_t dst_cap, int64_t* dst_len, void* scratch, int64_t scratch_bytes, void* stream)
+{
+    HipBackend be = { (hipStream_t)stream };
+    Lz4fEncodePlan p;
+    Lz4fDict d;
+    if (int rc = lz4f_encode_dict_plan(be, src, src_len, dict, dict_len, dict_id, block_size_id, flags, dst, dst_cap, dst_len, scratch, scratch_bytes, p, d)) return rc;
+    if (int rc = ensure_device()) return rc;
+    return lz4f_encode_dict_run(be, p, d);
+}
+
+int lz4hip_lz4f_encode_dict_host(const void* src, int64_t src_len, const void* dict, int64_t dict_len, uint32_t dict_id, int block_size_id, unsigned flags,
+                                 void* dst, int64_t dst_cap, int64_t* dst_len)
+{
+    HipBackend be = {};
+    if (int rc = check_dict(dict, dict_len)) return rc;
+    if (src_len < 0 || !dst_len || !dst || (src_len > 0 && !src)) return fail(LZ4HIP_E_ARGUMENT, "lz4f encode: negative size or NULL pointer");
+    if (!lz4f_id_valid(block_size_id) || (flags & ~kLz4fEncodeFlags)) return fail(LZ4HIP_E_ARGUMENT, "lz4f encode: block_size_id must be 0 or 4 .. 7, flags known");
+    if (dst_cap < lz4f_dict_bound(src_len, block_size_id, flags, dict_len, dict_id)) return fail(LZ4HIP_E_ARGUMENT, "lz4f encode: dst_cap < lz4hip_lz4f_dict_bound");
+    if (int rc = stream_host_context(be)) return rc;
+    return lz4f_encode_dict_host(be, src, src_len, dict, dict_len, dict_id, block_size_id, flags, dst, dst_cap, dst_len);
+}
+
 int lz4hip_lz4f_encode_host(const void* src, int64_t src_len, int block_size_id, int mode, unsigned flags, void* dst, int64_t dst_cap, int64_t* dst_len)
 {
     HipBackend be = {};
@@ -2233,6 +2273,45 @@ int lz4hip_lz4f_batch_decode_dict_host(const void* src, int64_t src_len, const i
     if (int rc = check_dict(dict, dict_len)) return rc;
     if (int rc = stream_host_context(be)) return rc;
     return lz4f_batch_decode_dict_host(be, src, src_len, src_off, n, dict, dict_len, dict_id, flags, dst, dst_cap, dst_off, item_info, info);
+}
+
+int64_t lz4hip_lz4f_batch_dict_bound(int64_t n, int64_t src_len, int block_size_id, unsigned flags, int64_t dict_len, uint32_t dict_id)
+{
+    return lz4f_batch_dict_bound(n, src_len, block_size_id, flags, dict_len, dict_id);
+}
+
+int64_t lz4hip_lz4f_batch_encode_dict_scratch_bytes(int64_t n, int64_t src_len, int block_size_id, int64_t dict_len)
+{
+    if (dict_len < 0) return fail(LZ4HIP_E_ARGUMENT, "dictionary: dict_len < 0");
+    if (!lz4f_id_valid(block_size_id)) return fail(LZ4HIP_E_ARGUMENT, "lz4f batch encode: block_size_id must be 0 (64 KiB) or 4 .. 7");
+    return n <= 0 ? 0 : lz4f_batch_encode_scratch(nullptr, n, src_len < 0 ? 0 : src_len, lz4f_block_bytes(lz4f_id(block_size_id)), dict_len).bytes;
+}
+
+int lz4hip_lz4f_batch_encode_dict_device(const void* src, int64_t src_len, const int64_t* src_off, int64_t n, const void* dict, int64_t dict_len, uint32_t dict_id,
+                                         int block_size_id, unsigned flags, void* dst, int64_t dst_cap, int64_t* dst_off, void* scratch, int64_t scratch_bytes,
+                                         void* stream)
+{
+    HipBackend be = { (hipStream_t)stream };
+    Lz4fBatchEncodePlan p;
+    Lz4fDict d;
+    if (int rc = lz4f_batch_encode_dict_plan(be, src, src_len, src_off, n, dict, dict_len, dict_id, block_size_id, flags, dst, dst_cap, dst_off, scratch,
+                                             scratch_bytes, p, d)) return rc;
+    if (int rc = ensure_device()) return rc;
+    return lz4f_batch_encode_dict_run(be, p, d);
+}
+
+int lz4hip_lz4f_batch_encode_dict_host(const void* src, int64_t src_len, const int64_t* src_off, int64_t n, const void* dict, int64_t dict_len, uint32_t dict_id,
+                                       int block_size_id, unsigned flags, void* dst, int64_t dst_cap, int64_t* dst_off)
+{
+    HipBackend be = {};
+    if (int rc = check_dict(dict, dict_len)) return rc;
+    if (src_len < 0 || n < 0 || !dst_off || (n > 0 && (!src_off || !dst)) || (src_len > 0 && n > 0 && !src))
+        return fail(LZ4HIP_E_ARGUMENT, "lz4f batch encode: negative size or NULL pointer");
+    if (!lz4f_id_valid(block_size_id) || (flags & ~kLz4fEncodeFlags)) return fail(LZ4HIP_E_ARGUMENT, "lz4f batch encode: block_size_id must be 0 or 4 .. 7, flags known");
+    if (n > 0 && dst_cap < lz4f_batch_dict_bound(n, src_len, block_size_id, flags, dict_len, dict_id))
+        return fail(LZ4HIP_E_ARGUMENT, "lz4f batch encode: dst_cap < lz4hip_lz4f_batch_dict_bound");
+    if (int rc = stream_host_context(be)) return rc;
+    return lz4f_batch_encode_dict_host(be, src, src_len, src_off, n, dict, dict_len, dict_id, block_size_id, flags, dst, dst_cap, dst_off);
 }
 
 int lz4hip_lz4f_batch_encode_host(const void* src, int64_t src_len, const int64_t* src_off, int64_t n, int block_size_id, int mode, unsigned flags,

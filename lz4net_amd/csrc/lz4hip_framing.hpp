@@ -9,6 +9,8 @@
 //     int  fill(p, byte, bytes)                      device bytes set to a value, in stream order
 //     int  encode(const lz4hip_batch_t*, mode)       the block encoder / decoder over a batch (launch_encode / launch_decode)
 //     int  decode(const lz4hip_batch_t*, known)
+//     int  encode_dict_prime(dict_end, reach, primed), encode_dict(batch, dict_end, reach, primed), decode_dict(batch, dict_end, reach, known)
+//                                                    the dictionary forms, only where a sequence is instantiated with a dictionary
 //     int  last_error()                              0, or the failure of a launch since the last look
 //     int  fail(code, text)                          records the text, returns the code
 //
@@ -1569,21 +1571,67 @@ int xxh32_rows_check(B& be, const void* data, const int64_t* off, int64_t stride
     return 0;
 }
 
+// ---- the dictionary of the dictionary calls (lz4hip_lz4f_*_dict_*), for the encode and decode sequences below -----------------------------
+// What a sequence is handed in its place: Lz4fNoDict by the plain calls, whose sequences are what they were, or the bytes of the call's
+// dictionary that a match can reach -- its last min(dict_len, 65 535), in device memory, which END at `end` -- and the ID a frame's must
+// equal (0: any).  The overloads below are all that differs: the walk's flag and ID, the rounds' block decoder (a backend needs
+// decode_dict only where a sequence is instantiated with a dictionary) and the linked decode's kernel.  To the encode sequences `id` is
+// the ID to write (0: none) and `primed` the 16 KiB of the call's scratch that hold the encoder's primed table; what differs there are
+// the block encoder (be.encode_dict_prime once, then be.encode_dict in be.encode's place), the head kernel and the head's length.
+struct Lz4fNoDict {};
+struct Lz4fDict { const uint8_t* end; int32_t len; uint32_t id; uint8_t* primed; };
+inline Lz4fDict lz4f_dict_of(const void* dict, int64_t dict_len, uint32_t dict_id)
+{
+    return { (const uint8_t*)dict + dict_len, (int32_t)(dict_len < kLz4fLinkedHistory ? dict_len : kLz4fLinkedHistory), dict_id, nullptr };
+}
+inline unsigned lz4f_walk_flags(unsigned flags, Lz4fNoDict) { return flags; }
+inline unsigned lz4f_walk_flags(unsigned flags, const Lz4fDict&) { return flags | kLz4fWithDict; }
+inline uint32_t lz4f_walk_dict_id(Lz4fNoDict) { return 0; }
+inline uint32_t lz4f_walk_dict_id(const Lz4fDict& d) { return d.id; }
+template <class B> int lz4f_round_decode(B& be, const lz4hip_batch_t* rb, Lz4fNoDict) { return be.decode(rb, 0); }
+template <class B> int lz4f_round_decode(B& be, const lz4hip_batch_t* rb, const Lz4fDict& d) { return be.decode_dict(rb, d.end, d.len, 0); }
+// the encode sequences' block call: the primed table first, once per call
+template <class B> int lz4f_blocks_encode(B& be, const lz4hip_batch_t* b, int mode, Lz4fNoDict) { return be.encode(b, mode); }
+template <class B> int lz4f_blocks_encode(B& be, const lz4hip_batch_t* b, int, const Lz4fDict& d)
+{
+    if (int rc = be.encode_dict_prime(d.end, d.len, d.primed)) return rc;
+    return be.encode_dict(b, d.end, d.len, d.primed);
+}
+inline Lz4fPlainHead lz4f_head_of(Lz4fNoDict) { return {}; }
+inline Lz4fDictHead lz4f_head_of(const Lz4fDict& d) { return { d.id }; }
+inline int64_t lz4f_dict_reach(Lz4fNoDict) { return 0; }
+inline int64_t lz4f_dict_reach(const Lz4fDict& d) { return d.len; }
+// dict_len < 0, or no dictionary where there should be one
+template <class B>
+int lz4f_dict_check(B& be, const void* dict, int64_t dict_len)
+{
+    if (dict_len < 0) return be.fail(LZ4HIP_E_ARGUMENT, "dictionary: dict_len < 0");
+    if (dict_len > 0 && !dict) return be.fail(LZ4HIP_E_ARGUMENT, "dictionary: dict is NULL and dict_len > 0");
+    return 0;
+}
+
 inline bool lz4f_id_valid(int block_size_id) { return block_size_id == 0 || (block_size_id >= 4 && block_size_id <= 7); }
 inline int lz4f_id(int block_size_id) { return block_size_id == 0 ? 4 : block_size_id; }                        // (of a valid id)
 constexpr unsigned kLz4fEncodeFlags = kLz4fBlockChecksum | kLz4fContentChecksum | kLz4fContentSize;
 // an empty source carries no content size: 0 means "unknown" to the format library, which writes none
 inline unsigned lz4f_flags(int64_t src_len, unsigned flags) { return src_len > 0 ? flags : flags & ~kLz4fContentSize; }
-inline int32_t lz4f_head_len(unsigned flags) { return 7 + ((flags & kLz4fContentSize) ? 8 : 0); }
+// the descriptor's length: the plain calls', or with `dict_id` != 0 (the dictionary encode) the four bytes of the ID more
+inline int32_t lz4f_head_len(unsigned flags, uint32_t dict_id = 0) { return Lz4fDictHead{ dict_id }.len(flags); }
 
 // the descriptor, every block stored raw behind its size field (and before its checksum), the EndMark and the content checksum
-inline int64_t lz4f_bound(int64_t src_len, int block_size_id, unsigned flags)
+inline int64_t lz4f_bound(int64_t src_len, int block_size_id, unsigned flags, uint32_t dict_id = 0)
 {
     if (!lz4f_id_valid(block_size_id) || (flags & ~kLz4fEncodeFlags)) return LZ4HIP_E_ARGUMENT;
     if (src_len < 0) src_len = 0;
     flags = lz4f_flags(src_len, flags);
     const int64_t n = stream_chunks(src_len, lz4f_block_bytes(lz4f_id(block_size_id)));
-    return lz4f_head_len(flags) + src_len + n * (4 + ((flags & kLz4fBlockChecksum) ? 4 : 0)) + 4 + ((flags & kLz4fContentChecksum) ? 4 : 0);
+    return lz4f_head_len(flags, dict_id) + src_len + n * (4 + ((flags & kLz4fBlockChecksum) ? 4 : 0)) + 4 + ((flags & kLz4fContentChecksum) ? 4 : 0);
+}
+// lz4hip_lz4f_dict_bound: without a dictionary the plain bound, whatever the ID
+inline int64_t lz4f_dict_bound(int64_t src_len, int block_size_id, unsigned flags, int64_t dict_len, uint32_t dict_id)
+{
+    if (dict_len < 0) return LZ4HIP_E_ARGUMENT;
+    return lz4f_bound(src_len, block_size_id, flags, dict_len > 0 ? dict_id : 0);
 }
 
 // the encoder's slot per block: a block is given one byte less than its length
@@ -1591,11 +1639,12 @@ inline int64_t lz4f_stride(int64_t src_len, int64_t block) { return src_len < bl
 
 // lz4f encode: the encoder's output (block k at k * stride), block lengths, capacities, results, the checksum rows, the n + 1 checksums,
 // the descriptor, the n + 2 sizes / offsets, tile sums
+// With a dictionary (dict_len > 0) the plain layout, then the descriptor's kLz4fDictHeadMax bytes and the 16 KiB primed table.
 struct Lz4fEncodeScratch {
     uint8_t* comp; int32_t* lens; int32_t* caps; int32_t* result; int64_t* row_off; int32_t* row_len; uint32_t* sums; uint8_t* head; int64_t* offs;
-    int64_t* partial; int64_t bytes;
+    int64_t* partial; uint8_t* primed; int64_t bytes;
 };
-inline Lz4fEncodeScratch lz4f_encode_scratch(void* scratch, int64_t src_len, int64_t block)
+inline Lz4fEncodeScratch lz4f_encode_scratch(void* scratch, int64_t src_len, int64_t block, int64_t dict_len = 0)
 {
     const int64_t n = stream_chunks(src_len, block);
     Carver c(scratch);
@@ -1610,6 +1659,11 @@ inline Lz4fEncodeScratch lz4f_encode_scratch(void* scratch, int64_t src_len, int
     l.head = c.take_as<uint8_t>(kLz4fHeadMax);
     l.offs = c.take_as<int64_t>(8 * (n + 2));
     l.partial = c.take_as<int64_t>(8 * scan_tiles(n + 2));
+    l.primed = nullptr;
+    if (dict_len > 0) {
+        l.head = c.take_as<uint8_t>(kLz4fDictHeadMax);
+        l.primed = c.take_as<uint8_t>(kFastTableBytes);
+    }
     l.bytes = c.at;
     return l;
 }
@@ -1619,9 +1673,13 @@ struct Lz4fEncodePlan {
     int64_t* dst_len; int64_t bound;
 };
 
+template <class B> void lz4f_head_launch(B& be, const Lz4fEncodeArgs& a, Lz4fNoDict) { be.launch(lz4f_head_kernel, fixed_grid(1), 64, a); }
+template <class B> void lz4f_head_launch(B& be, const Lz4fEncodeArgs& a, const Lz4fDict& d) { be.launch(lz4f_dict_head_kernel, fixed_grid(1), 64, a, lz4f_head_of(d)); }
+
 // p.a.comp and p.a.result are the block encoder's to write: block k at k * p.a.stride.  An empty source is a descriptor and an EndMark.
-template <class B>
-int lz4f_encode_run(B& be, const Lz4fEncodePlan& p)
+// `dict`: Lz4fNoDict, or the call's dictionary in device memory (the fast mode's dictionary encoder, whatever p.mode).
+template <class B, class D = Lz4fNoDict>
+int lz4f_encode_run(B& be, const Lz4fEncodePlan& p, const D& dict = D())
 {
     const Lz4fEncodeArgs& a = p.a;
     if (a.n > 0) {
@@ -1631,7 +1689,7 @@ int lz4f_encode_run(B& be, const Lz4fEncodePlan& p)
         b.src = a.src; b.src_stride = a.block; b.src_len = p.lens;
         b.dst = (void*)a.comp; b.dst_stride = a.stride; b.dst_cap = p.caps;
         b.src_len_all = a.block; b.result = (int32_t*)a.result; b.n_blocks = a.n;
-        LZ4HIP_FRAMING_TRY(be.encode(&b, p.mode));
+        LZ4HIP_FRAMING_TRY(lz4f_blocks_encode(be, &b, p.mode, dict));
         if (a.flags & kLz4fBlockChecksum) {
             be.launch(lz4f_rows_kernel, stream_grid(a.n), kStreamThreads, a, p.row_off, p.row_len);
             const XxhRows rows = { a.src, p.row_off, 0, p.row_len, nullptr, 0, 0u, a.sums, a.n };
@@ -1642,7 +1700,7 @@ int lz4f_encode_run(B& be, const Lz4fEncodePlan& p)
         const XxhRows content = { a.src, nullptr, 0, nullptr, nullptr, a.src_len, 0u, a.sums + a.n, 1 };
         LZ4HIP_FRAMING_TRY(xxh32_rows_run(be, content));
     }
-    be.launch(lz4f_head_kernel, fixed_grid(1), 64, a);
+    lz4f_head_launch(be, a, dict);
     be.launch(lz4f_sizes_kernel, stream_grid(a.n + 2), kStreamThreads, a);
     launch_scan(be, a.offs, a.n + 2, p.partial, p.dst_len);
     Lz4fLayout layout = { a };
@@ -1652,7 +1710,7 @@ int lz4f_encode_run(B& be, const Lz4fEncodePlan& p)
 
 template <class B>
 int lz4f_encode_plan(B& be, const void* src, int64_t src_len, int block_size_id, int mode, unsigned flags, void* dst, int64_t dst_cap, int64_t* dst_len,
-                     void* scratch, int64_t scratch_bytes, Lz4fEncodePlan& p)
+                     void* scratch, int64_t scratch_bytes, Lz4fEncodePlan& p, int64_t dict_len = 0, uint32_t dict_id = 0, uint8_t** primed = nullptr)
 {
     if (src_len < 0 || !dst_len) return be.fail(LZ4HIP_E_ARGUMENT, "lz4f encode: src_len < 0 or dst_len is NULL");
     if (!lz4f_id_valid(block_size_id)) return be.fail(LZ4HIP_E_ARGUMENT, "lz4f encode: block_size_id must be 0 (64 KiB) or 4 .. 7");
@@ -1661,17 +1719,20 @@ int lz4f_encode_plan(B& be, const void* src, int64_t src_len, int block_size_id,
     const int id = lz4f_id(block_size_id);
     const int64_t block = lz4f_block_bytes(id), n = stream_chunks(src_len, block);
     if (n >= 0x7FFFFFFF) return be.fail(LZ4HIP_E_ARGUMENT, "lz4f encode: more than 2^31 - 2 blocks");
-    p.bound = lz4f_bound(src_len, block_size_id, flags);
-    if (dst_cap < p.bound) return be.fail(LZ4HIP_E_ARGUMENT, "lz4f encode: dst_cap < lz4hip_lz4f_bound");
-    const Lz4fEncodeScratch l = lz4f_encode_scratch(scratch, src_len, block);
-    if (scratch_bytes < l.bytes) return be.fail(LZ4HIP_E_ARGUMENT, "lz4f encode: scratch_bytes < lz4hip_lz4f_encode_scratch_bytes");
+    p.bound = lz4f_bound(src_len, block_size_id, flags, dict_id);
+    if (dst_cap < p.bound) return be.fail(LZ4HIP_E_ARGUMENT, dict_len > 0 ? "lz4f encode: dst_cap < lz4hip_lz4f_dict_bound" : "lz4f encode: dst_cap < lz4hip_lz4f_bound");
+    const Lz4fEncodeScratch l = lz4f_encode_scratch(scratch, src_len, block, dict_len);
+    if (scratch_bytes < l.bytes)
+        return be.fail(LZ4HIP_E_ARGUMENT, dict_len > 0 ? "lz4f encode: scratch_bytes < lz4hip_lz4f_encode_dict_scratch_bytes"
+                                                       : "lz4f encode: scratch_bytes < lz4hip_lz4f_encode_scratch_bytes");
     if ((n > 0 && !src) || !dst || !scratch) return be.fail(LZ4HIP_E_ARGUMENT, "lz4f encode: src, dst and scratch must be non-NULL");
     Lz4fEncodeArgs& a = p.a;
     a.src = (const uint8_t*)src; a.comp = l.comp; a.src_len = src_len; a.n = n; a.stride = lz4f_stride(src_len, block); a.block = (int32_t)block;
-    a.block_id = id; a.flags = lz4f_flags(src_len, flags); a.head_len = lz4f_head_len(a.flags);
+    a.block_id = id; a.flags = lz4f_flags(src_len, flags); a.head_len = lz4f_head_len(a.flags, dict_id);
     a.result = l.result; a.sums = l.sums; a.head = l.head; a.offs = l.offs;
     p.mode = mode; p.lens = l.lens; p.caps = l.caps; p.row_off = l.row_off; p.row_len = l.row_len; p.partial = l.partial;
     p.dst = (uint8_t*)dst; p.dst_cap = dst_cap; p.dst_len = dst_len;
+    if (primed) *primed = l.primed;
     return 0;
 }
 
@@ -1684,38 +1745,35 @@ int lz4f_encode(B& be, const void* src, int64_t src_len, int block_size_id, int 
     return lz4f_encode_run(be, p);
 }
 
+// lz4hip_lz4f_encode_dict_device: the dictionary's check, then the plain call's plan in fast mode with the dictionary's bound, scratch
+// and head length; `d` is what the sequence is handed (d.len == 0: no dictionary, the plain sequence).  `dict` is device memory.
+template <class B>
+int lz4f_encode_dict_plan(B& be, const void* src, int64_t src_len, const void* dict, int64_t dict_len, uint32_t dict_id, int block_size_id, unsigned flags,
+                          void* dst, int64_t dst_cap, int64_t* dst_len, void* scratch, int64_t scratch_bytes, Lz4fEncodePlan& p, Lz4fDict& d)
+{
+    LZ4HIP_FRAMING_TRY(lz4f_dict_check(be, dict, dict_len));
+    d = lz4f_dict_of(dict, dict_len, dict_len > 0 ? dict_id : 0);
+    return lz4f_encode_plan(be, src, src_len, block_size_id, LZ4HIP_MODE_FAST, flags, dst, dst_cap, dst_len, scratch, scratch_bytes, p, dict_len, d.id, &d.primed);
+}
+template <class B>
+int lz4f_encode_dict_run(B& be, const Lz4fEncodePlan& p, const Lz4fDict& d) { return d.len > 0 ? lz4f_encode_run(be, p, d) : lz4f_encode_run(be, p); }
+
+template <class B>
+int lz4f_encode_dict(B& be, const void* src, int64_t src_len, const void* dict, int64_t dict_len, uint32_t dict_id, int block_size_id, unsigned flags, void* dst,
+                     int64_t dst_cap, int64_t* dst_len, void* scratch, int64_t scratch_bytes)
+{
+    Lz4fEncodePlan p;
+    Lz4fDict d;
+    LZ4HIP_FRAMING_TRY(lz4f_encode_dict_plan(be, src, src_len, dict, dict_len, dict_id, block_size_id, flags, dst, dst_cap, dst_len, scratch, scratch_bytes, p, d));
+    return lz4f_encode_dict_run(be, p, d);
+}
+
 // lz4f decode: the table of max_blocks rows (the n + 1 checksums and what the walk found with it), then the compact decode's scratch for
 // max_blocks rows of slot_bytes
 inline bool lz4f_slot_valid(int32_t slot_bytes) { return slot_bytes == 0 || slot_bytes == 65536 || slot_bytes == 262144 || slot_bytes == 1048576 || slot_bytes == 4194304; }
 inline int32_t lz4f_slot(int32_t slot_bytes) { return slot_bytes == 0 ? 4194304 : slot_bytes; }                    // (of a valid slot_bytes)
 constexpr unsigned kLz4fDecodeFlags = kLz4fVerifyBlocks | kLz4fVerifyContent | kLz4fAcceptLinked;
 static_assert(!(kLz4fDecodeFlags & kLz4fWithDict), "the walk's internal bit is no public flag");
-
-// ---- the dictionary of the dictionary calls (lz4hip_lz4f_*_dict_*), for both decode sequences below --------------------------------------
-// What a sequence is handed in its place: Lz4fNoDict by the plain calls, whose sequences are what they were, or the bytes of the call's
-// dictionary that a match can reach -- its last min(dict_len, 65 535), in device memory, which END at `end` -- and the ID a frame's must
-// equal (0: any).  The overloads below are all that differs: the walk's flag and ID, the rounds' block decoder (a backend needs
-// decode_dict only where a sequence is instantiated with a dictionary) and the linked decode's kernel.
-struct Lz4fNoDict {};
-struct Lz4fDict { const uint8_t* end; int32_t len; uint32_t id; };
-inline Lz4fDict lz4f_dict_of(const void* dict, int64_t dict_len, uint32_t dict_id)
-{
-    return { (const uint8_t*)dict + dict_len, (int32_t)(dict_len < kLz4fLinkedHistory ? dict_len : kLz4fLinkedHistory), dict_id };
-}
-inline unsigned lz4f_walk_flags(unsigned flags, Lz4fNoDict) { return flags; }
-inline unsigned lz4f_walk_flags(unsigned flags, const Lz4fDict&) { return flags | kLz4fWithDict; }
-inline uint32_t lz4f_walk_dict_id(Lz4fNoDict) { return 0; }
-inline uint32_t lz4f_walk_dict_id(const Lz4fDict& d) { return d.id; }
-template <class B> int lz4f_round_decode(B& be, const lz4hip_batch_t* rb, Lz4fNoDict) { return be.decode(rb, 0); }
-template <class B> int lz4f_round_decode(B& be, const lz4hip_batch_t* rb, const Lz4fDict& d) { return be.decode_dict(rb, d.end, d.len, 0); }
-// dict_len < 0, or no dictionary where there should be one
-template <class B>
-int lz4f_dict_check(B& be, const void* dict, int64_t dict_len)
-{
-    if (dict_len < 0) return be.fail(LZ4HIP_E_ARGUMENT, "dictionary: dict_len < 0");
-    if (dict_len > 0 && !dict) return be.fail(LZ4HIP_E_ARGUMENT, "dictionary: dict is NULL and dict_len > 0");
-    return 0;
-}
 
 // ---- frames with linked blocks (lz4hip_lz4f_linked.hpp), for both decode sequences below ------------------------------------------------
 // one lane per table row in single-wavefront workgroups; one wavefront per item in workgroups of kWaveDecodeWavesPerGroup: more rows
@@ -1925,13 +1983,18 @@ static_assert(kLz4fBatchBadOffsets == LZ4HIP_E_ARGUMENT, "lz4f batch statuses");
 inline int64_t lz4f_batch_cap(int64_t n, int64_t src_len, int64_t block) { return src_len / block + n; }
 
 // n descriptors, EndMarks and content checksums, and every row of the block table stored raw behind its size field
-inline int64_t lz4f_batch_bound(int64_t n, int64_t src_len, int block_size_id, unsigned flags)
+inline int64_t lz4f_batch_bound(int64_t n, int64_t src_len, int block_size_id, unsigned flags, uint32_t dict_id = 0)
 {
     if (!lz4f_id_valid(block_size_id) || (flags & ~kLz4fEncodeFlags)) return LZ4HIP_E_ARGUMENT;
     if (n < 0) n = 0;
     if (src_len < 0) src_len = 0;
     const int64_t cap = lz4f_batch_cap(n, src_len, lz4f_block_bytes(lz4f_id(block_size_id)));
-    return n * (lz4f_head_len(flags) + 4 + ((flags & kLz4fContentChecksum) ? 4 : 0)) + src_len + cap * (4 + ((flags & kLz4fBlockChecksum) ? 4 : 0));
+    return n * (lz4f_head_len(flags, dict_id) + 4 + ((flags & kLz4fContentChecksum) ? 4 : 0)) + src_len + cap * (4 + ((flags & kLz4fBlockChecksum) ? 4 : 0));
+}
+inline int64_t lz4f_batch_dict_bound(int64_t n, int64_t src_len, int block_size_id, unsigned flags, int64_t dict_len, uint32_t dict_id)
+{
+    if (dict_len < 0) return LZ4HIP_E_ARGUMENT;
+    return lz4f_batch_bound(n, src_len, block_size_id, flags, dict_len > 0 ? dict_id : 0);
 }
 
 // lz4f batch encode: the encoder's output (every block at its own source position), the items' spans and first blocks, the block total,
@@ -1939,9 +2002,10 @@ inline int64_t lz4f_batch_bound(int64_t n, int64_t src_len, int block_size_id, u
 // sizes / offsets + the total, the scans' tile sums
 struct Lz4fBatchEncodeScratch {
     uint8_t* comp; int64_t* item_at; int64_t* item_len; int64_t* first; int64_t* total; int64_t* c_at; int32_t* c_len; int32_t* c_cap; int32_t* result;
-    int64_t* row_off; int32_t* row_len; uint32_t* sums; uint8_t* head; int32_t* seg_item; int64_t* offs; int64_t* partial; int64_t bytes;
+    int64_t* row_off; int32_t* row_len; uint32_t* sums; uint8_t* head; int32_t* seg_item; int64_t* offs; int64_t* partial; uint8_t* primed; int64_t bytes;
 };
-inline Lz4fBatchEncodeScratch lz4f_batch_encode_scratch(void* scratch, int64_t n, int64_t src_len, int64_t block)
+// With a dictionary (dict_len > 0) the plain layout, then the n descriptors' kLz4fDictHeadMax bytes each and the 16 KiB primed table.
+inline Lz4fBatchEncodeScratch lz4f_batch_encode_scratch(void* scratch, int64_t n, int64_t src_len, int64_t block, int64_t dict_len = 0)
 {
     const int64_t cap = lz4f_batch_cap(n, src_len, block), segs = cap + 2 * n;
     Carver c(scratch);
@@ -1962,6 +2026,11 @@ inline Lz4fBatchEncodeScratch lz4f_batch_encode_scratch(void* scratch, int64_t n
     l.seg_item = c.take_as<int32_t>(4 * segs);
     l.offs = c.take_as<int64_t>(8 * (segs + 1));
     l.partial = c.take_as<int64_t>(8 * scan_tiles(segs));              // (segs >= n: both scans fit)
+    l.primed = nullptr;
+    if (dict_len > 0) {
+        l.head = c.take_as<uint8_t>(kLz4fDictHeadMax * n);
+        l.primed = c.take_as<uint8_t>(kFastTableBytes);
+    }
     l.bytes = c.at;
     return l;
 }
@@ -1972,9 +2041,30 @@ struct Lz4fBatchEncodePlan {
 };
 
 // a.comp and a.result are the block encoder's to write, every block at its own source position.  Rows past the blocks' count are
-// empty blocks, which read and write nothing.
-template <class B>
-int lz4f_batch_encode_run(B& be, const Lz4fBatchEncodePlan& p)
+// empty blocks, which read and write nothing.  `dict`: as lz4f_encode_run's.
+template <class B> void lz4f_batch_head_launch(B& be, const Lz4fBatchEncodeArgs& a, int64_t segs, Lz4fNoDict)
+{
+    be.launch(lz4f_batch_head_kernel, stream_grid(a.n), kStreamThreads, a);
+    be.launch(lz4f_batch_sizes_kernel, stream_grid(segs), kStreamThreads, a);
+}
+template <class B> void lz4f_batch_head_launch(B& be, const Lz4fBatchEncodeArgs& a, int64_t segs, const Lz4fDict& d)
+{
+    be.launch(lz4f_batch_dict_head_kernel, stream_grid(a.n), kStreamThreads, a, lz4f_head_of(d));
+    be.launch(lz4f_batch_dict_sizes_kernel, stream_grid(segs), kStreamThreads, a, lz4f_head_of(d));
+}
+template <class B> void lz4f_batch_pack_launch(B& be, const Lz4fBatchEncodePlan& p, Lz4fNoDict)
+{
+    Lz4fBatchLayout layout = { p.a };
+    be.launch(lz4f_batch_pack_kernel, copy_grid(p.bound), kStreamThreads, layout, p.dst, p.dst_cap);
+}
+template <class B> void lz4f_batch_pack_launch(B& be, const Lz4fBatchEncodePlan& p, const Lz4fDict& d)
+{
+    Lz4fBatchDictLayout layout = { p.a, lz4f_head_of(d) };
+    be.launch(lz4f_batch_dict_pack_kernel, copy_grid(p.bound), kStreamThreads, layout, p.dst, p.dst_cap);
+}
+
+template <class B, class D = Lz4fNoDict>
+int lz4f_batch_encode_run(B& be, const Lz4fBatchEncodePlan& p, const D& dict = D())
 {
     const Lz4fBatchEncodeArgs& a = p.a;
     if (a.n == 0) return be.fill(p.dst_off, 0, sizeof(int64_t));
@@ -1987,7 +2077,7 @@ int lz4f_batch_encode_run(B& be, const Lz4fBatchEncodePlan& p)
     b.src = a.src; b.src_off = a.c_at; b.src_len = a.c_len;
     b.dst = (void*)a.comp; b.dst_off = a.c_at; b.dst_cap = a.c_cap;
     b.src_len_all = a.block; b.result = p.result; b.n_blocks = a.cap;
-    LZ4HIP_FRAMING_TRY(be.encode(&b, p.mode));
+    LZ4HIP_FRAMING_TRY(lz4f_blocks_encode(be, &b, p.mode, dict));
     if (a.flags & kLz4fBlockChecksum) {
         be.launch(lz4f_batch_rows_kernel, stream_grid(a.cap), kStreamThreads, a, p.row_off, p.row_len);
         const XxhRows rows = { a.src, p.row_off, 0, p.row_len, nullptr, 0, 0u, a.sums, a.cap };
@@ -1997,18 +2087,17 @@ int lz4f_batch_encode_run(B& be, const Lz4fBatchEncodePlan& p)
         const XxhRows content = { a.src, a.item_at, 0, nullptr, a.item_len, 0, 0u, a.sums + a.cap, a.n };
         LZ4HIP_FRAMING_TRY(xxh32_rows_run(be, content));
     }
-    be.launch(lz4f_batch_head_kernel, stream_grid(a.n), kStreamThreads, a);
-    be.launch(lz4f_batch_sizes_kernel, stream_grid(segs), kStreamThreads, a);
+    lz4f_batch_head_launch(be, a, segs, dict);
     launch_scan(be, a.offs, segs, p.partial, a.offs + segs);
     be.launch(lz4f_batch_offsets_kernel, stream_grid(a.n + 1), kStreamThreads, a, p.dst_off);
-    Lz4fBatchLayout layout = { a };
-    be.launch(lz4f_batch_pack_kernel, copy_grid(p.bound), kStreamThreads, layout, p.dst, p.dst_cap);
+    lz4f_batch_pack_launch(be, p, dict);
     return be.last_error();
 }
 
 template <class B>
 int lz4f_batch_encode_plan(B& be, const void* src, int64_t src_len, const int64_t* src_off, int64_t n, int block_size_id, int mode, unsigned flags,
-                           void* dst, int64_t dst_cap, int64_t* dst_off, void* scratch, int64_t scratch_bytes, Lz4fBatchEncodePlan& p)
+                           void* dst, int64_t dst_cap, int64_t* dst_off, void* scratch, int64_t scratch_bytes, Lz4fBatchEncodePlan& p, int64_t dict_len = 0,
+                           uint32_t dict_id = 0, uint8_t** primed = nullptr)
 {
     if (src_len < 0 || n < 0 || !dst_off) return be.fail(LZ4HIP_E_ARGUMENT, "lz4f batch encode: src_len < 0, n < 0 or dst_off is NULL");
     if (!lz4f_id_valid(block_size_id)) return be.fail(LZ4HIP_E_ARGUMENT, "lz4f batch encode: block_size_id must be 0 (64 KiB) or 4 .. 7");
@@ -2017,10 +2106,13 @@ int lz4f_batch_encode_plan(B& be, const void* src, int64_t src_len, const int64_
     const int id = lz4f_id(block_size_id);
     const int64_t block = lz4f_block_bytes(id), cap = lz4f_batch_cap(n, src_len, block);
     if (n > 0x3FFFFFFF || cap > 0x3FFFFFFF) return be.fail(LZ4HIP_E_ARGUMENT, "lz4f batch encode: more than 2^30 - 1 items or blocks");
-    p.bound = lz4f_batch_bound(n, src_len, block_size_id, flags);
-    if (n > 0 && dst_cap < p.bound) return be.fail(LZ4HIP_E_ARGUMENT, "lz4f batch encode: dst_cap < lz4hip_lz4f_batch_bound");
-    const Lz4fBatchEncodeScratch l = lz4f_batch_encode_scratch(scratch, n, src_len, block);
-    if (n > 0 && scratch_bytes < l.bytes) return be.fail(LZ4HIP_E_ARGUMENT, "lz4f batch encode: scratch_bytes < lz4hip_lz4f_batch_encode_scratch_bytes");
+    p.bound = lz4f_batch_bound(n, src_len, block_size_id, flags, dict_id);
+    if (n > 0 && dst_cap < p.bound)
+        return be.fail(LZ4HIP_E_ARGUMENT, dict_len > 0 ? "lz4f batch encode: dst_cap < lz4hip_lz4f_batch_dict_bound" : "lz4f batch encode: dst_cap < lz4hip_lz4f_batch_bound");
+    const Lz4fBatchEncodeScratch l = lz4f_batch_encode_scratch(scratch, n, src_len, block, dict_len);
+    if (n > 0 && scratch_bytes < l.bytes)
+        return be.fail(LZ4HIP_E_ARGUMENT, dict_len > 0 ? "lz4f batch encode: scratch_bytes < lz4hip_lz4f_batch_encode_dict_scratch_bytes"
+                                                       : "lz4f batch encode: scratch_bytes < lz4hip_lz4f_batch_encode_scratch_bytes");
     if (n > 0 && ((src_len > 0 && !src) || !src_off || !dst || !scratch))
         return be.fail(LZ4HIP_E_ARGUMENT, "lz4f batch encode: src, src_off, dst and scratch must be non-NULL");
     Lz4fBatchEncodeArgs& a = p.a;
@@ -2031,6 +2123,7 @@ int lz4f_batch_encode_plan(B& be, const void* src, int64_t src_len, const int64_
     a.result = l.result; a.sums = l.sums; a.head = l.head; a.seg_item = l.seg_item; a.offs = l.offs;
     p.mode = mode; p.result = l.result; p.row_off = l.row_off; p.row_len = l.row_len; p.partial = l.partial;
     p.dst = (uint8_t*)dst; p.dst_cap = dst_cap; p.dst_off = dst_off;
+    if (primed) *primed = l.primed;
     return 0;
 }
 
@@ -2041,6 +2134,34 @@ int lz4f_batch_encode(B& be, const void* src, int64_t src_len, const int64_t* sr
     Lz4fBatchEncodePlan p;
     LZ4HIP_FRAMING_TRY(lz4f_batch_encode_plan(be, src, src_len, src_off, n, block_size_id, mode, flags, dst, dst_cap, dst_off, scratch, scratch_bytes, p));
     return lz4f_batch_encode_run(be, p);
+}
+
+// lz4hip_lz4f_batch_encode_dict_device, as lz4f_encode_dict_plan / _run: one dictionary and one ID for every item
+template <class B>
+int lz4f_batch_encode_dict_plan(B& be, const void* src, int64_t src_len, const int64_t* src_off, int64_t n, const void* dict, int64_t dict_len, uint32_t dict_id,
+                                int block_size_id, unsigned flags, void* dst, int64_t dst_cap, int64_t* dst_off, void* scratch, int64_t scratch_bytes,
+                                Lz4fBatchEncodePlan& p, Lz4fDict& d)
+{
+    LZ4HIP_FRAMING_TRY(lz4f_dict_check(be, dict, dict_len));
+    d = lz4f_dict_of(dict, dict_len, dict_len > 0 ? dict_id : 0);
+    return lz4f_batch_encode_plan(be, src, src_len, src_off, n, block_size_id, LZ4HIP_MODE_FAST, flags, dst, dst_cap, dst_off, scratch, scratch_bytes, p, dict_len,
+                                  d.id, &d.primed);
+}
+template <class B>
+int lz4f_batch_encode_dict_run(B& be, const Lz4fBatchEncodePlan& p, const Lz4fDict& d)
+{
+    return d.len > 0 ? lz4f_batch_encode_run(be, p, d) : lz4f_batch_encode_run(be, p);
+}
+
+template <class B>
+int lz4f_batch_encode_dict(B& be, const void* src, int64_t src_len, const int64_t* src_off, int64_t n, const void* dict, int64_t dict_len, uint32_t dict_id,
+                           int block_size_id, unsigned flags, void* dst, int64_t dst_cap, int64_t* dst_off, void* scratch, int64_t scratch_bytes)
+{
+    Lz4fBatchEncodePlan p;
+    Lz4fDict d;
+    LZ4HIP_FRAMING_TRY(lz4f_batch_encode_dict_plan(be, src, src_len, src_off, n, dict, dict_len, dict_id, block_size_id, flags, dst, dst_cap, dst_off, scratch,
+                                                   scratch_bytes, p, d));
+    return lz4f_batch_encode_dict_run(be, p, d);
 }
 
 // lz4f batch decode: what is kept per item (the walk's records, spans, first rows, lowest bad rows, content rows), the totals, the
@@ -2484,23 +2605,40 @@ int frame_decode_host(B& be, const void* src, int64_t src_len, int32_t chunk_siz
     return info->error;
 }
 
-// The LZ4 frame's encoder staged the way frame_encode_host stages the legacy frame's.
+// the device call of the host-pointer encoders over their image: the plain call, or the dictionary call in its place
 template <class B>
-int lz4f_encode_host(B& be, const void* src, int64_t src_len, int block_size_id, int mode, unsigned flags, void* dst, int64_t dst_cap, int64_t* dst_len)
+int lz4f_encode_image(B& be, const void* src, int64_t src_len, int block_size_id, int mode, unsigned flags, void* dst, int64_t dst_cap, int64_t* dst_len,
+                      void* scratch, int64_t scratch_bytes, Lz4fNoDict)
 {
+    return lz4f_encode(be, src, src_len, block_size_id, mode, flags, dst, dst_cap, dst_len, scratch, scratch_bytes);
+}
+template <class B>
+int lz4f_encode_image(B& be, const void* src, int64_t src_len, int block_size_id, int, unsigned flags, void* dst, int64_t dst_cap, int64_t* dst_len,
+                      void* scratch, int64_t scratch_bytes, const Lz4fDict& d)
+{
+    return lz4f_encode_dict(be, src, src_len, d.end - d.len, d.len, d.id, block_size_id, flags, dst, dst_cap, dst_len, scratch, scratch_bytes);
+}
+
+// The LZ4 frame's encoder staged the way frame_encode_host stages the legacy frame's.  `dict`: Lz4fNoDict, or the call's dictionary ALREADY
+// in device memory, in staging that is not the image's (lz4f_dict_stage); its primed table lies in the image's scratch.
+template <class B, class D = Lz4fNoDict>
+int lz4f_encode_host(B& be, const void* src, int64_t src_len, int block_size_id, int mode, unsigned flags, void* dst, int64_t dst_cap, int64_t* dst_len,
+                     const D& dict = D())
+{
+    const int64_t reach = lz4f_dict_reach(dict);
     if (src_len < 0 || !dst_len || !dst || (src_len > 0 && !src)) return be.fail(LZ4HIP_E_ARGUMENT, "lz4f encode: negative size or NULL pointer");
     if (!lz4f_id_valid(block_size_id) || (flags & ~kLz4fEncodeFlags)) return be.fail(LZ4HIP_E_ARGUMENT, "lz4f encode: block_size_id must be 0 or 4 .. 7, flags known");
-    const int64_t bound = lz4f_bound(src_len, block_size_id, flags);
-    if (dst_cap < bound) return be.fail(LZ4HIP_E_ARGUMENT, "lz4f encode: dst_cap < lz4hip_lz4f_bound");
+    const int64_t bound = lz4f_bound(src_len, block_size_id, flags, lz4f_walk_dict_id(dict));
+    if (dst_cap < bound) return be.fail(LZ4HIP_E_ARGUMENT, reach ? "lz4f encode: dst_cap < lz4hip_lz4f_dict_bound" : "lz4f encode: dst_cap < lz4hip_lz4f_bound");
     // device image: [source | frame | scratch | length]
-    const int64_t scratch_bytes = lz4f_encode_scratch(nullptr, src_len, lz4f_block_bytes(lz4f_id(block_size_id))).bytes;
+    const int64_t scratch_bytes = lz4f_encode_scratch(nullptr, src_len, lz4f_block_bytes(lz4f_id(block_size_id)), reach).bytes;
     Carver c;
     c.take(src_len);
     const int64_t out_at = c.take(bound), scratch_at = c.take(scratch_bytes), len_at = c.take(256);
     Image<B> im = { be };
     LZ4HIP_FRAMING_TRY(im.reserve(c.at));
     LZ4HIP_FRAMING_TRY(im.upload_source(src, src_len));
-    LZ4HIP_FRAMING_TRY(lz4f_encode(be, im.d, src_len, block_size_id, mode, flags, im.d + out_at, bound, im.i64(len_at), im.d + scratch_at, scratch_bytes));
+    LZ4HIP_FRAMING_TRY(lz4f_encode_image(be, im.d, src_len, block_size_id, mode, flags, im.d + out_at, bound, im.i64(len_at), im.d + scratch_at, scratch_bytes, dict));
     int64_t total = 0;
     LZ4HIP_FRAMING_TRY(im.download(&total, len_at, sizeof total));
     LZ4HIP_FRAMING_TRY(be.sync());
@@ -2584,12 +2722,43 @@ int lz4f_decode_dict_host(B& be, const void* src, int64_t src_len, const void* d
     return lz4f_decode_host(be, src, src_len, flags, dst, dst_cap, info, d);
 }
 
-// A batch of frames staged the way streams_encode_host stages a batch of streams; the offsets are host memory here, so bad ones are
-// refused instead of encoded as items of no bytes.
+// lz4hip_lz4f_encode_dict_host: three phases -- the dictionary's reachable tail goes up once (lz4f_dict_stage), its table is primed once
+// and the device sequence runs over one image (both inside lz4f_encode_dict).  The front checks that come before the staging are
+// repeated here, so that a call that is refused uploads nothing.
 template <class B>
-int lz4f_batch_encode_host(B& be, const void* src, int64_t src_len, const int64_t* src_off, int64_t n, int block_size_id, int mode, unsigned flags,
-                           void* dst, int64_t dst_cap, int64_t* dst_off)
+int lz4f_encode_dict_host(B& be, const void* src, int64_t src_len, const void* dict, int64_t dict_len, uint32_t dict_id, int block_size_id, unsigned flags,
+                          void* dst, int64_t dst_cap, int64_t* dst_len)
 {
+    LZ4HIP_FRAMING_TRY(lz4f_dict_check(be, dict, dict_len));
+    if (dict_len == 0) return lz4f_encode_host(be, src, src_len, block_size_id, LZ4HIP_MODE_FAST, flags, dst, dst_cap, dst_len);
+    if (src_len < 0 || !dst_len || !dst || (src_len > 0 && !src)) return be.fail(LZ4HIP_E_ARGUMENT, "lz4f encode: negative size or NULL pointer");
+    if (!lz4f_id_valid(block_size_id) || (flags & ~kLz4fEncodeFlags)) return be.fail(LZ4HIP_E_ARGUMENT, "lz4f encode: block_size_id must be 0 or 4 .. 7, flags known");
+    if (dst_cap < lz4f_bound(src_len, block_size_id, flags, dict_id)) return be.fail(LZ4HIP_E_ARGUMENT, "lz4f encode: dst_cap < lz4hip_lz4f_dict_bound");
+    Lz4fDict d;
+    LZ4HIP_FRAMING_TRY(lz4f_dict_stage(be, dict, dict_len, dict_id, d));
+    return lz4f_encode_host(be, src, src_len, block_size_id, LZ4HIP_MODE_FAST, flags, dst, dst_cap, dst_len, d);
+}
+
+// A batch of frames staged the way streams_encode_host stages a batch of streams; the offsets are host memory here, so bad ones are
+// refused instead of encoded as items of no bytes.  `dict`: as lz4f_encode_host's.
+template <class B>
+int lz4f_batch_encode_image(B& be, const void* src, int64_t src_len, const int64_t* src_off, int64_t n, int block_size_id, int mode, unsigned flags, void* dst,
+                            int64_t dst_cap, int64_t* dst_off, void* scratch, int64_t scratch_bytes, Lz4fNoDict)
+{
+    return lz4f_batch_encode(be, src, src_len, src_off, n, block_size_id, mode, flags, dst, dst_cap, dst_off, scratch, scratch_bytes);
+}
+template <class B>
+int lz4f_batch_encode_image(B& be, const void* src, int64_t src_len, const int64_t* src_off, int64_t n, int block_size_id, int, unsigned flags, void* dst,
+                            int64_t dst_cap, int64_t* dst_off, void* scratch, int64_t scratch_bytes, const Lz4fDict& d)
+{
+    return lz4f_batch_encode_dict(be, src, src_len, src_off, n, d.end - d.len, d.len, d.id, block_size_id, flags, dst, dst_cap, dst_off, scratch, scratch_bytes);
+}
+
+template <class B, class D = Lz4fNoDict>
+int lz4f_batch_encode_host(B& be, const void* src, int64_t src_len, const int64_t* src_off, int64_t n, int block_size_id, int mode, unsigned flags,
+                           void* dst, int64_t dst_cap, int64_t* dst_off, const D& dict = D())
+{
+    const int64_t reach = lz4f_dict_reach(dict);
     if (src_len < 0 || n < 0 || !dst_off || (n > 0 && (!src_off || !dst)) || (src_len > 0 && n > 0 && !src))
         return be.fail(LZ4HIP_E_ARGUMENT, "lz4f batch encode: negative size or NULL pointer");
     if (!lz4f_id_valid(block_size_id) || (flags & ~kLz4fEncodeFlags)) return be.fail(LZ4HIP_E_ARGUMENT, "lz4f batch encode: block_size_id must be 0 or 4 .. 7, flags known");
@@ -2597,22 +2766,41 @@ int lz4f_batch_encode_host(B& be, const void* src, int64_t src_len, const int64_
     for (int64_t i = 0; i < n; i++)
         if (src_off[i] < 0 || src_off[i + 1] < src_off[i] || src_off[i + 1] > src_len)
             return be.fail(LZ4HIP_E_ARGUMENT, "lz4f batch encode: offsets decrease or fall outside [0, src_len]");
-    const int64_t bound = lz4f_batch_bound(n, src_len, block_size_id, flags);
-    if (n > 0 && dst_cap < bound) return be.fail(LZ4HIP_E_ARGUMENT, "lz4f batch encode: dst_cap < lz4hip_lz4f_batch_bound");
+    const int64_t bound = lz4f_batch_bound(n, src_len, block_size_id, flags, lz4f_walk_dict_id(dict));
+    if (n > 0 && dst_cap < bound)
+        return be.fail(LZ4HIP_E_ARGUMENT, reach ? "lz4f batch encode: dst_cap < lz4hip_lz4f_batch_dict_bound" : "lz4f batch encode: dst_cap < lz4hip_lz4f_batch_bound");
     if (n == 0) { dst_off[0] = 0; return 0; }
     // device image: [source | offsets | output | output offsets | scratch]
-    const int64_t scratch_bytes = lz4f_batch_encode_scratch(nullptr, n, src_len, lz4f_block_bytes(lz4f_id(block_size_id))).bytes;
+    const int64_t scratch_bytes = lz4f_batch_encode_scratch(nullptr, n, src_len, lz4f_block_bytes(lz4f_id(block_size_id)), reach).bytes;
     Carver c;
     c.take(src_len);
     const int64_t off_at = c.take(8 * (n + 1)), out_at = c.take(bound), doff_at = c.take(8 * (n + 1)), scratch_at = c.take(scratch_bytes);
     Image<B> im = { be };
     LZ4HIP_FRAMING_TRY(im.reserve(c.at));
     LZ4HIP_FRAMING_TRY(im.upload_source(src, src_len, src_off, n, off_at));
-    LZ4HIP_FRAMING_TRY(lz4f_batch_encode(be, im.d, src_len, im.i64(off_at), n, block_size_id, mode, flags, im.d + out_at, bound, im.i64(doff_at),
-                                         im.d + scratch_at, scratch_bytes));
+    LZ4HIP_FRAMING_TRY(lz4f_batch_encode_image(be, im.d, src_len, im.i64(off_at), n, block_size_id, mode, flags, im.d + out_at, bound, im.i64(doff_at),
+                                               im.d + scratch_at, scratch_bytes, dict));
     LZ4HIP_FRAMING_TRY(im.download_items({ n, dst_off, doff_at, nullptr, 0, nullptr, 0 }));
     LZ4HIP_FRAMING_TRY(be.sync());
     return im.download_encoded(dst, out_at, dst_off[n] < dst_cap ? dst_off[n] : dst_cap);
+}
+
+// lz4hip_lz4f_batch_encode_dict_host, as lz4f_encode_dict_host: a call that is refused, or has no items, uploads nothing
+template <class B>
+int lz4f_batch_encode_dict_host(B& be, const void* src, int64_t src_len, const int64_t* src_off, int64_t n, const void* dict, int64_t dict_len, uint32_t dict_id,
+                                int block_size_id, unsigned flags, void* dst, int64_t dst_cap, int64_t* dst_off)
+{
+    LZ4HIP_FRAMING_TRY(lz4f_dict_check(be, dict, dict_len));
+    if (dict_len == 0 || n <= 0) return lz4f_batch_encode_host(be, src, src_len, src_off, n, block_size_id, LZ4HIP_MODE_FAST, flags, dst, dst_cap, dst_off);
+    if (src_len < 0 || !dst_off || !src_off || !dst || (src_len > 0 && !src)) return be.fail(LZ4HIP_E_ARGUMENT, "lz4f batch encode: negative size or NULL pointer");
+    if (!lz4f_id_valid(block_size_id) || (flags & ~kLz4fEncodeFlags)) return be.fail(LZ4HIP_E_ARGUMENT, "lz4f batch encode: block_size_id must be 0 or 4 .. 7, flags known");
+    for (int64_t i = 0; i < n; i++)
+        if (src_off[i] < 0 || src_off[i + 1] < src_off[i] || src_off[i + 1] > src_len)
+            return be.fail(LZ4HIP_E_ARGUMENT, "lz4f batch encode: offsets decrease or fall outside [0, src_len]");
+    if (dst_cap < lz4f_batch_bound(n, src_len, block_size_id, flags, dict_id)) return be.fail(LZ4HIP_E_ARGUMENT, "lz4f batch encode: dst_cap < lz4hip_lz4f_batch_dict_bound");
+    Lz4fDict d;
+    LZ4HIP_FRAMING_TRY(lz4f_dict_stage(be, dict, dict_len, dict_id, d));
+    return lz4f_batch_encode_host(be, src, src_len, src_off, n, block_size_id, LZ4HIP_MODE_FAST, flags, dst, dst_cap, dst_off, d);
 }
 
 // The descriptors lie in host memory here: the largest block maximum among them sizes the slots.  The table and the output's piece of

@@ -25,7 +25,9 @@
 // The decode is the batch of frames' (lz4hip_lz4f_batch.hpp) with one item: from the block checksums' verdict to the item's record,
 // everything but the walk is written here once for both, over one Lz4fTables whose rows name their item (or none: one item).
 //
-// The encoder's blocks are always independent (FLG.5) and use no dictionary; the decoder refuses linked blocks unless the caller accepts
+// The encoder's blocks are always independent (FLG.5); the dictionary calls (lz4hip_lz4f_*encode_dict_*) hand the block round to the
+// dictionary encoder (lz4hip_encode_dict.hpp) and write the descriptor with lz4f_dict_head_kernel, which knows the dictionary ID: the
+// rest of the sequence is the plain one.  The decoder refuses linked blocks unless the caller accepts
 // them (kLz4fAcceptLinked): each decodes only against the 64 KiB before it, in order, so a linked frame is one serial chain --
 // lz4hip_lz4f_linked.hpp runs it on one wavefront, after the rounds, which see its rows as holes.  A frame with a dictionary ID is
 // refused by the plain calls; the dictionary calls (lz4hip_lz4f_*_dict_*) hand the walk kLz4fWithDict and the ID they expect, the rounds
@@ -262,6 +264,90 @@ __global__ void __launch_bounds__(64) lz4f_head_kernel(Lz4fEncodeArgs a)
     h[at] = (uint8_t)(xxh32_serial(h + 4, at - 4, 0) >> 8);
     at++;
     for (int b = 0; b < at; b++) a.head[b] = h[b];
+}
+
+// ---- the descriptor of the dictionary encode (lz4hip_lz4f_*encode_dict_*) ----------------------------------------------------------------
+// What the kernels that lay out a descriptor are handed: nothing by the plain calls (Lz4fPlainHead: kLz4fHeadMax bytes of storage, two
+// words), or the call's dictionary ID (Lz4fDictHead: FLG.0 and the ID behind the content size when it is not 0, 4 bytes more, so 24 bytes
+// of storage, three words).
+constexpr int kLz4fDictHeadMax = 24;                                    // magic + FLG + BD + content size + dictID + HC = 19
+struct Lz4fPlainHead {
+    static constexpr int kBytes = kLz4fHeadMax;
+    __host__ __device__ int32_t len(uint32_t flags) const { return 7 + ((flags & kLz4fContentSize) ? 8 : 0); }
+};
+struct Lz4fDictHead {
+    uint32_t dict_id;                                                   // 0: no ID is written
+    static constexpr int kBytes = kLz4fDictHeadMax;
+    __host__ __device__ int32_t len(uint32_t flags) const { return 7 + ((flags & kLz4fContentSize) ? 8 : 0) + (dict_id ? 4 : 0); }
+};
+
+// The descriptor's HC byte, the second byte of xxh32 (seed 0) over FLG, BD and the content size if there is one: 2 or 10 bytes, in
+// registers (xxh32_serial reads memory, and a descriptor built in a local array would live in scratch).
+LZ4HIP_DEVICE uint32_t lz4f_batch_hc(uint32_t flg, uint32_t bd, bool sized, uint64_t size)
+{
+    uint32_t h = kXxhP5 + (sized ? 10u : 2u);
+    if (sized) {
+        h = xxh_rotl(h + (flg | bd << 8 | (uint32_t)(size & 0xFFFFu) << 16) * kXxhP3, 17) * kXxhP4;
+        h = xxh_rotl(h + (uint32_t)(size >> 16) * kXxhP3, 17) * kXxhP4;
+        h = xxh_rotl(h + (uint32_t)((size >> 48) & 0xFFu) * kXxhP5, 11) * kXxhP1;
+        h = xxh_rotl(h + (uint32_t)(size >> 56) * kXxhP5, 11) * kXxhP1;
+    } else {
+        h = xxh_rotl(h + flg * kXxhP5, 11) * kXxhP1;
+        h = xxh_rotl(h + bd * kXxhP5, 11) * kXxhP1;
+    }
+    h ^= h >> 15; h *= kXxhP2;
+    h ^= h >> 13; h *= kXxhP3;
+    h ^= h >> 16;
+    return (h >> 8) & 0xFFu;
+}
+
+// The HC byte of a descriptor with a dictionary ID: xxh32 (seed 0) over FLG, BD, the content size if there is one and the ID -- 6 bytes (one
+// 4-byte lane, two tail bytes) or 14 (three lanes, two tail bytes) -- in registers, as lz4f_batch_hc (lz4hip_lz4f_batch.hpp) has the 2 and 10.
+LZ4HIP_DEVICE uint32_t lz4f_dict_hc(uint32_t flg, uint32_t bd, bool sized, uint64_t size, uint32_t id)
+{
+    uint32_t h = kXxhP5 + (sized ? 14u : 6u);
+    if (sized) {
+        h = xxh_rotl(h + (flg | bd << 8 | (uint32_t)(size & 0xFFFFu) << 16) * kXxhP3, 17) * kXxhP4;
+        h = xxh_rotl(h + (uint32_t)(size >> 16) * kXxhP3, 17) * kXxhP4;
+        h = xxh_rotl(h + ((uint32_t)(size >> 48) | (id & 0xFFFFu) << 16) * kXxhP3, 17) * kXxhP4;
+    } else {
+        h = xxh_rotl(h + (flg | bd << 8 | (id & 0xFFFFu) << 16) * kXxhP3, 17) * kXxhP4;
+    }
+    h = xxh_rotl(h + ((id >> 16) & 0xFFu) * kXxhP5, 11) * kXxhP1;
+    h = xxh_rotl(h + (id >> 24) * kXxhP5, 11) * kXxhP1;
+    h ^= h >> 15; h *= kXxhP2;
+    h ^= h >> 13; h *= kXxhP3;
+    h ^= h >> 16;
+    return (h >> 8) & 0xFFu;
+}
+
+// The descriptor of the dictionary encode as the three little-endian words of its kLz4fDictHeadMax bytes: with the ID `id` != 0, 11 bytes
+// or 19 with the content size; without one the plain descriptor, 7 or 15.  `size` counts only with kLz4fContentSize in flags.
+LZ4HIP_DEVICE void lz4f_dict_head_words(uint64_t* head, uint32_t flags, int32_t block_id, uint64_t size, uint32_t id)
+{
+    const bool sized = (flags & kLz4fContentSize) != 0;
+    const uint32_t flg = 0x60u | (id ? 0x01u : 0u) | ((flags & kLz4fBlockChecksum) ? 0x10u : 0u) | (sized ? 0x08u : 0u) | ((flags & kLz4fContentChecksum) ? 0x04u : 0u);
+    const uint32_t bd = (uint32_t)block_id << 4;
+    const uint64_t front = (uint64_t)kLz4fMagic | (uint64_t)flg << 32 | (uint64_t)bd << 40;
+    if (!sized) size = 0;
+    if (id) {
+        const uint64_t hc = lz4f_dict_hc(flg, bd, sized, size, id);
+        head[0] = front | (sized ? size << 48 : (uint64_t)(id & 0xFFFFu) << 48);
+        head[1] = sized ? (size >> 16 | (uint64_t)(id & 0xFFFFu) << 48) : ((uint64_t)(id >> 16) | hc << 16);
+        head[2] = sized ? ((uint64_t)(id >> 16) | hc << 16) : 0;
+    } else {
+        const uint64_t hc = lz4f_batch_hc(flg, bd, sized, size);
+        head[0] = front | (sized ? size << 48 : hc << 48);
+        head[1] = sized ? (size >> 16 | hc << 48) : 0;
+        head[2] = 0;
+    }
+}
+
+// lz4f_head_kernel of the dictionary encode: a.head has kLz4fDictHeadMax bytes (at a multiple of 256), written as words (a descriptor
+// built in a local array, as lz4f_head_kernel has it, would live in scratch memory)
+__global__ void __launch_bounds__(64) lz4f_dict_head_kernel(Lz4fEncodeArgs a, Lz4fDictHead d)
+{
+    if (threadIdx.x == 0) lz4f_dict_head_words((uint64_t*)a.head, a.flags, a.block_id, (uint64_t)a.src_len, d.dict_id);
 }
 
 // The frame as n + 2 segments of the copy routine.  A block's checksum FOLLOWS its data, and a segment's header bytes come before its

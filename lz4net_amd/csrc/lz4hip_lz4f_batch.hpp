@@ -10,6 +10,9 @@
 //           block) -> xxh32_rows_kernel (n rows: the items' contents) -> lz4f_batch_head_kernel (n descriptors) -> lz4f_batch_sizes_kernel
 //           (every segment's item and size) -> stream_scan_* (ONE scan: the frames are concatenated, so the global layout is each item's
 //           local one) -> lz4f_batch_offsets_kernel (dst_off) -> lz4f_batch_pack_kernel (copy_spans over Lz4fBatchLayout)
+//           With a dictionary (lz4hip_lz4f_batch_encode_dict_*) the block call is launch_encode_dict_prime + launch_encode_dict, and
+//           the three kernels that know a descriptor's length are lz4f_batch_dict_head_kernel, lz4f_batch_dict_sizes_kernel and
+//           lz4f_batch_dict_pack_kernel (Lz4fDictHead: the dictionary ID, 24 bytes of storage per item); everything else is the same.
 //
 //   decode: lz4f_batch_walk_kernel<false> (ONE WAVEFRONT PER ITEM runs lz4f_walk_frame: the item's record and its block count) ->
 //           stream_scan_* (the first row of every item, the row total) -> lz4f_batch_walk_kernel<true> (the same walk again, writing
@@ -63,7 +66,7 @@ struct Lz4fBatchEncodeArgs {
     int32_t* c_cap;
     const int32_t* result;
     uint32_t* sums;              // cap block checksums, then n content checksums
-    uint8_t* head;               // kLz4fHeadMax bytes per item
+    uint8_t* head;               // kLz4fHeadMax bytes per item (the dictionary encode: kLz4fDictHeadMax)
     int32_t* seg_item;           // per segment: its item, -1 for padding
     int64_t* offs;               // cap + 2 n segment sizes, scanned in place to their offsets; offs[cap + 2 n] = the total
 };
@@ -71,7 +74,6 @@ struct Lz4fBatchEncodeArgs {
 LZ4HIP_DEVICE int64_t lz4f_batch_segments(const Lz4fBatchEncodeArgs& a) { return a.cap + 2 * a.n; }
 LZ4HIP_DEVICE int64_t lz4f_batch_blocks(const Lz4fBatchEncodeArgs& a) { return *a.total < a.cap ? *a.total : a.cap; }
 LZ4HIP_DEVICE uint32_t lz4f_batch_item_flags(const Lz4fBatchEncodeArgs& a, int64_t i) { return a.item_len[i] > 0 ? a.flags : a.flags & ~kLz4fContentSize; }
-LZ4HIP_DEVICE int32_t lz4f_batch_head_len(uint32_t flags) { return 7 + ((flags & kLz4fContentSize) ? 8 : 0); }
 // blocks of item i that lie in the table (offsets that decrease can make K exceed it: the blocks past it are dropped)
 LZ4HIP_DEVICE int64_t lz4f_batch_item_blocks(const Lz4fBatchEncodeArgs& a, int64_t i)
 {
@@ -127,26 +129,6 @@ __global__ void __launch_bounds__(kStreamThreads) lz4f_batch_rows_kernel(Lz4fBat
     }
 }
 
-// The descriptor's HC byte, the second byte of xxh32 (seed 0) over FLG, BD and the content size if there is one: 2 or 10 bytes, in
-// registers (xxh32_serial reads memory, and a descriptor built in a local array would live in scratch).
-LZ4HIP_DEVICE uint32_t lz4f_batch_hc(uint32_t flg, uint32_t bd, bool sized, uint64_t size)
-{
-    uint32_t h = kXxhP5 + (sized ? 10u : 2u);
-    if (sized) {
-        h = xxh_rotl(h + (flg | bd << 8 | (uint32_t)(size & 0xFFFFu) << 16) * kXxhP3, 17) * kXxhP4;
-        h = xxh_rotl(h + (uint32_t)(size >> 16) * kXxhP3, 17) * kXxhP4;
-        h = xxh_rotl(h + (uint32_t)((size >> 48) & 0xFFu) * kXxhP5, 11) * kXxhP1;
-        h = xxh_rotl(h + (uint32_t)(size >> 56) * kXxhP5, 11) * kXxhP1;
-    } else {
-        h = xxh_rotl(h + flg * kXxhP5, 11) * kXxhP1;
-        h = xxh_rotl(h + bd * kXxhP5, 11) * kXxhP1;
-    }
-    h ^= h >> 15; h *= kXxhP2;
-    h ^= h >> 13; h *= kXxhP3;
-    h ^= h >> 16;
-    return (h >> 8) & 0xFFu;
-}
-
 // lz4f_head_kernel per item, one thread each: the magic, FLG, BD, the content size if asked for (not for an empty item) and HC, as the
 // two little-endian words of the item's kLz4fHeadMax bytes
 __global__ void __launch_bounds__(kStreamThreads) lz4f_batch_head_kernel(Lz4fBatchEncodeArgs a)
@@ -165,6 +147,15 @@ __global__ void __launch_bounds__(kStreamThreads) lz4f_batch_head_kernel(Lz4fBat
     }
 }
 
+// ... and of the dictionary encode: three words of the item's kLz4fDictHeadMax bytes; without an ID the plain descriptor
+__global__ void __launch_bounds__(kStreamThreads) lz4f_batch_dict_head_kernel(Lz4fBatchEncodeArgs a, Lz4fDictHead d)
+{
+    static_assert(kLz4fDictHeadMax == 24, "three 64-bit words per descriptor");
+    // (the descriptors start at a multiple of 256 bytes)
+    for (int64_t i = (int64_t)blockIdx.x * kStreamThreads + threadIdx.x; i < a.n; i += (int64_t)gridDim.x * kStreamThreads)
+        lz4f_dict_head_words((uint64_t*)(a.head + i * kLz4fDictHeadMax), lz4f_batch_item_flags(a, i), a.block_id, (uint64_t)a.item_len[i], d.dict_id);
+}
+
 // One segment: whose it is and which of the item's it is (0: the descriptor, 1 .. blocks: a block, blocks + 1: the tail).
 struct Lz4fBatchSeg { int64_t item, local, blocks, row; };              // row: the block's table row (for the tail: one past the item's last)
 
@@ -179,11 +170,12 @@ LZ4HIP_DEVICE Lz4fBatchSeg lz4f_batch_seg_of(const Lz4fBatchEncodeArgs& a, int64
 }
 
 // the segment's bytes; lead: the checksum of the block before it opens a segment (a block's checksum FOLLOWS its data)
-LZ4HIP_DEVICE int64_t lz4f_batch_seg_bytes(const Lz4fBatchEncodeArgs& a, const Lz4fBatchSeg& g)
+template <class H = Lz4fPlainHead>
+LZ4HIP_DEVICE int64_t lz4f_batch_seg_bytes(const Lz4fBatchEncodeArgs& a, const Lz4fBatchSeg& g, const H& head = H())
 {
     if (a.item_len[g.item] < 0 || g.local < 0 || g.local > g.blocks + 1) return 0;
     const uint32_t flags = lz4f_batch_item_flags(a, g.item);
-    if (g.local == 0) return lz4f_batch_head_len(flags);
+    if (g.local == 0) return head.len(flags);
     int64_t bytes = (g.local >= 2 && (flags & kLz4fBlockChecksum) ? 4 : 0) + 4;
     if (g.local <= g.blocks) bytes += lz4f_batch_stored_len(a, g.row);
     else if (flags & kLz4fContentChecksum) bytes += 4;
@@ -211,6 +203,28 @@ __global__ void __launch_bounds__(kStreamThreads) lz4f_batch_sizes_kernel(Lz4fBa
     }
 }
 
+// ... with the dictionary encode's descriptors (the loop is written twice: as one function of both kernels it changed the plain kernel's
+// listing, profiles/lz4f_dict_encode/listing_parent_vs_new.txt)
+__global__ void __launch_bounds__(kStreamThreads) lz4f_batch_dict_sizes_kernel(Lz4fBatchEncodeArgs a, Lz4fDictHead d)
+{
+    const int64_t S = lz4f_batch_segments(a), used = lz4f_batch_blocks(a) + 2 * a.n;
+    for (int64_t s = (int64_t)blockIdx.x * kStreamThreads + threadIdx.x; s < S; s += (int64_t)gridDim.x * kStreamThreads) {
+        int64_t bytes = 0;
+        int32_t item = -1;
+        if (s < used) {
+            int64_t lo = 0, hi = a.n - 1;
+            while (lo < hi) {
+                const int64_t mid = hi - (hi - lo) / 2;
+                if (a.first[mid] + 2 * mid <= s) lo = mid; else hi = mid - 1;
+            }
+            item = (int32_t)lo;
+            bytes = lz4f_batch_seg_bytes(a, lz4f_batch_seg_of(a, s, lo), d);
+        }
+        a.seg_item[s] = item;
+        a.offs[s] = bytes;
+    }
+}
+
 // dst_off[i] = the offset of item i's descriptor, dst_off[n] = the total
 __global__ void __launch_bounds__(kStreamThreads) lz4f_batch_offsets_kernel(Lz4fBatchEncodeArgs a, int64_t* dst_off)
 {
@@ -223,56 +237,73 @@ __global__ void __launch_bounds__(kStreamThreads) lz4f_batch_offsets_kernel(Lz4f
 
 // Lz4fLayout's twin over the segments of all items.  flags: 1 = the checksum that opens the segment is there (in `original`), 4 = a
 // descriptor, whose bytes are the payload pointer's; a tail's content checksum lies behind the payload pointer too.
+template <class H>
+LZ4HIP_DEVICE CopySeg lz4f_batch_layout_seg(const Lz4fBatchEncodeArgs& a, int64_t k, const H& head)
+{
+    CopySeg s;
+    s.start = s.pbegin = s.pend = a.offs[k];
+    s.flags = 0; s.original = s.clen = 0;
+    s.payload = a.src;
+    const int32_t item = a.seg_item[k];
+    if (item < 0) return s;
+    const Lz4fBatchSeg g = lz4f_batch_seg_of(a, k, item);
+    if (lz4f_batch_seg_bytes(a, g, head) == 0) return s;
+    const uint32_t flags = lz4f_batch_item_flags(a, item);
+    if (g.local == 0) {
+        s.flags = 4;
+        s.payload = a.head + (int64_t)item * H::kBytes;
+        s.pbegin = s.pend = s.start + head.len(flags);
+        return s;
+    }
+    if (g.local >= 2 && (flags & kLz4fBlockChecksum)) { s.flags = 1; s.original = a.sums[g.row - 1]; }
+    s.pbegin = s.start + (s.flags ? 8 : 4);
+    if (g.local > g.blocks) {
+        s.payload = (const uint8_t*)(a.sums + a.cap + item);
+        s.pbegin += (flags & kLz4fContentChecksum) ? 4 : 0;
+        s.pend = s.pbegin;
+        return s;
+    }
+    const int32_t stored = lz4f_batch_stored_len(a, g.row);
+    s.clen = (uint32_t)stored | (lz4f_batch_compressed(a, g.row) ? 0u : kLz4fRawBit);
+    s.pend = s.pbegin + stored;
+    s.payload = lz4f_batch_stored(a, g.row);
+    return s;
+}
+LZ4HIP_DEVICE uint8_t lz4f_batch_layout_head_byte(const CopySeg& s, int64_t x)
+{
+    int i = (int)(x - s.start);
+    if (s.flags & 4) return s.payload[i];
+    if (s.flags & 1) {
+        if (i < 4) return (uint8_t)(s.original >> (8 * i));
+        i -= 4;
+    }
+    if (i < 4) return (uint8_t)(s.clen >> (8 * i));
+    return s.payload[i - 4];                                        // (only a tail has header bytes here: its content checksum)
+}
 struct Lz4fBatchLayout {
     Lz4fBatchEncodeArgs a;
     LZ4HIP_DEVICE int64_t count() const { return lz4f_batch_segments(a); }
     LZ4HIP_DEVICE int64_t start(int64_t k) const { return a.offs[k]; }
-    LZ4HIP_DEVICE CopySeg seg(int64_t k) const
-    {
-        CopySeg s;
-        s.start = s.pbegin = s.pend = a.offs[k];
-        s.flags = 0; s.original = s.clen = 0;
-        s.payload = a.src;
-        const int32_t item = a.seg_item[k];
-        if (item < 0) return s;
-        const Lz4fBatchSeg g = lz4f_batch_seg_of(a, k, item);
-        if (lz4f_batch_seg_bytes(a, g) == 0) return s;
-        const uint32_t flags = lz4f_batch_item_flags(a, item);
-        if (g.local == 0) {
-            s.flags = 4;
-            s.payload = a.head + (int64_t)item * kLz4fHeadMax;
-            s.pbegin = s.pend = s.start + lz4f_batch_head_len(flags);
-            return s;
-        }
-        if (g.local >= 2 && (flags & kLz4fBlockChecksum)) { s.flags = 1; s.original = a.sums[g.row - 1]; }
-        s.pbegin = s.start + (s.flags ? 8 : 4);
-        if (g.local > g.blocks) {
-            s.payload = (const uint8_t*)(a.sums + a.cap + item);
-            s.pbegin += (flags & kLz4fContentChecksum) ? 4 : 0;
-            s.pend = s.pbegin;
-            return s;
-        }
-        const int32_t stored = lz4f_batch_stored_len(a, g.row);
-        s.clen = (uint32_t)stored | (lz4f_batch_compressed(a, g.row) ? 0u : kLz4fRawBit);
-        s.pend = s.pbegin + stored;
-        s.payload = lz4f_batch_stored(a, g.row);
-        return s;
-    }
-    LZ4HIP_DEVICE uint8_t head_byte(const CopySeg& s, int64_t x) const
-    {
-        int i = (int)(x - s.start);
-        if (s.flags & 4) return s.payload[i];
-        if (s.flags & 1) {
-            if (i < 4) return (uint8_t)(s.original >> (8 * i));
-            i -= 4;
-        }
-        if (i < 4) return (uint8_t)(s.clen >> (8 * i));
-        return s.payload[i - 4];                                        // (only a tail has header bytes here: its content checksum)
-    }
+    LZ4HIP_DEVICE CopySeg seg(int64_t k) const { return lz4f_batch_layout_seg(a, k, Lz4fPlainHead()); }
+    LZ4HIP_DEVICE uint8_t head_byte(const CopySeg& s, int64_t x) const { return lz4f_batch_layout_head_byte(s, x); }
+};
+// ... of the dictionary encode: the descriptors are Lz4fDictHead's
+struct Lz4fBatchDictLayout {
+    Lz4fBatchEncodeArgs a;
+    Lz4fDictHead d;
+    LZ4HIP_DEVICE int64_t count() const { return lz4f_batch_segments(a); }
+    LZ4HIP_DEVICE int64_t start(int64_t k) const { return a.offs[k]; }
+    LZ4HIP_DEVICE CopySeg seg(int64_t k) const { return lz4f_batch_layout_seg(a, k, d); }
+    LZ4HIP_DEVICE uint8_t head_byte(const CopySeg& s, int64_t x) const { return lz4f_batch_layout_head_byte(s, x); }
 };
 
 // output bytes [0, min(total, cap)): the total exceeds the bound only for offsets that decrease, and nothing past cap is written
 __global__ void __launch_bounds__(kStreamThreads) lz4f_batch_pack_kernel(Lz4fBatchLayout L, uint8_t* dst, int64_t cap)
+{
+    const int64_t total = L.a.offs[lz4f_batch_segments(L.a)];
+    copy_spans(L, dst, total < cap ? total : cap);
+}
+__global__ void __launch_bounds__(kStreamThreads) lz4f_batch_dict_pack_kernel(Lz4fBatchDictLayout L, uint8_t* dst, int64_t cap)
 {
     const int64_t total = L.a.offs[lz4f_batch_segments(L.a)];
     copy_spans(L, dst, total < cap ? total : cap);

@@ -6,7 +6,9 @@ K4os.Compression.LZ4.Streams and python-lz4 write and read.
     LE32 0 (EndMark)   [LE32 xxh32(content) if FLG.2]
 
 The blocks are the block format the library encodes and decodes anyway; the framing, the xxHash32 checksums and the packing run on
-the device (lz4hip_lz4f_* of include/lz4hip.h).  Frames written here hold independent blocks and no dictionary.  The decoders take
+the device (lz4hip_lz4f_* of include/lz4hip.h).  Frames written here hold independent blocks.  The encoders take dictionary=...,
+dict_id=... (LZ4F_compressFrame_usingCDict with independent blocks: every block is encoded against the same dictionary, in fast mode;
+dict_id != 0 is written into the descriptor), and the decoders take
 dictionary=..., dict_id=... (LZ4F_decompress_usingDict: ONE dictionary per call, in front of every frame's first byte); without one,
 frames with a dictionary ID are refused with a clear message, not decoded wrongly, and so are frames with linked blocks (FLG.5 clear)
 unless the caller passes accept_linked=True.  Skippable frames (magic 0x184D2A50 .. 0x184D2A5F) are skipped, appended frames decoded one after
@@ -148,6 +150,11 @@ def _host_dictionary(dictionary, dict_id):
     return (d.ctypes.data if d.size else 0), d.size, _dict_id(dict_id), d
 
 
+def _no_hc_with_dictionary(high_compression, dict_len):
+    if high_compression and dict_len:
+        raise ArgumentException("high_compression with a dictionary is not supported: the dictionary encoder has the fast mode only")
+
+
 def _dict_id(dict_id) -> int:
     if not 0 <= int(dict_id) <= 0xFFFFFFFF:
         raise ArgumentException("dict_id must be 0 (no check) .. 2^32 - 1")
@@ -155,14 +162,26 @@ def _dict_id(dict_id) -> int:
 
 
 def compress_frame_device(t, block_size: int = 65536, high_compression: bool = False, block_checksum: bool = False,
-                          content_checksum: bool = False, content_size: bool = True):
+                          content_checksum: bool = False, content_size: bool = True, dictionary=None, dict_id: int = 0):
     """One LZ4 frame of a 1-D uint8 CUDA tensor, entirely on the device, on torch's current stream, returned as a 1-D uint8 CUDA tensor:
     independent blocks of block_size bytes, a block that does not shrink stored raw.  The content checksum is ONE serial row of the
-    checksum kernel over the whole source.  Waits for the device once, to learn the frame's length."""
+    checksum kernel over the whole source.  Waits for the device once, to learn the frame's length.  dictionary: a 1-D uint8 CUDA tensor
+    on t's device against which EVERY block is encoded (lz4hip_lz4f_encode_dict_device, LZ4F_compressFrame_usingCDict with independent
+    blocks; fast mode only: with high_compression=True it raises ArgumentException); dict_id != 0 is written into the descriptor.  None
+    or empty: no dictionary, the plain call."""
     t = _p.check_device_bytes(t, "t")
     bid, flags = _block_id(block_size), _encode_flags(block_checksum, content_checksum, content_size)
+    dict_ptr, dict_len, dict_id, keep_dict = _device_dictionary(dictionary, t, dict_id)
+    _no_hc_with_dictionary(high_compression, dict_len)
     with _p.DeviceCall(t) as d:
         n = t.numel()
+        if dict_len:
+            out = d.u8(_lib.check(d.lib.lz4hip_lz4f_dict_bound(n, bid, flags, dict_len, dict_id)))
+            scratch = d.u8(_lib.check(d.lib.lz4hip_lz4f_encode_dict_scratch_bytes(n, bid, dict_len)))
+            out_len = d.i64(1)
+            _lib.check(d.lib.lz4hip_lz4f_encode_dict_device(t.data_ptr(), n, dict_ptr, dict_len, dict_id, bid, flags, out.data_ptr(), out.numel(),
+                                                            out_len.data_ptr(), scratch.data_ptr(), scratch.numel(), d.stream))
+            return out[:int(out_len.item())]
         out = d.u8(d.lib.lz4hip_lz4f_bound(n, bid, flags))
         scratch = d.u8(max(d.lib.lz4hip_lz4f_encode_scratch_bytes(n, bid), 1))
         out_len = d.i64(1)
@@ -237,11 +256,20 @@ def decompress_frame_device(t, verify: bool = True, round_blocks: int = 0, accep
 
 
 def compress_frame_host(data, block_size: int = 65536, high_compression: bool = False, block_checksum: bool = False,
-                        content_checksum: bool = False, content_size: bool = True) -> bytes:
-    """compress_frame_device for host bytes, through lz4hip_lz4f_encode_host: one staged call, the frame packed on the device."""
+                        content_checksum: bool = False, content_size: bool = True, dictionary=None, dict_id: int = 0) -> bytes:
+    """compress_frame_device for host bytes, through lz4hip_lz4f_encode_host: one staged call, the frame packed on the device.  dictionary
+    (bytes-like here, through lz4hip_lz4f_encode_dict_host) and dict_id as in compress_frame_device."""
     raw = _p.host_bytes(data)
     bid, flags = _block_id(block_size), _encode_flags(block_checksum, content_checksum, content_size)
+    dict_ptr, dict_len, dict_id, keep_dict = _host_dictionary(dictionary, dict_id)
+    _no_hc_with_dictionary(high_compression, dict_len)
     L = _lib.lib()
+    if dict_len:
+        bound = _lib.check(L.lz4hip_lz4f_dict_bound(raw.size, bid, flags, dict_len, dict_id))
+        out = np.empty(bound, np.uint8)
+        out_len = C.c_int64(0)
+        _lib.check(L.lz4hip_lz4f_encode_dict_host(raw.ctypes.data, raw.size, dict_ptr, dict_len, dict_id, bid, flags, out.ctypes.data, bound, C.byref(out_len)))
+        return out[:out_len.value].tobytes()
     bound = L.lz4hip_lz4f_bound(raw.size, bid, flags)
     out = np.empty(bound, np.uint8)
     out_len = C.c_int64(0)
@@ -306,22 +334,32 @@ def _item_error(batch, texts=_TEXT):
 
 
 def compress_frames_device(t, offsets, block_size: int = 65536, high_compression: bool = False, block_checksum: bool = False,
-                           content_checksum: bool = False, content_size: bool = True):
+                           content_checksum: bool = False, content_size: bool = True, dictionary=None, dict_id: int = 0):
     """[compress_frame_device(item) for item in items] for the items t[offsets[i]:offsets[i + 1]] of a 1-D uint8 CUDA tensor, in one
     call on the device, on torch's current stream -> (frames, frame_offsets): item i's frame is frames[frame_offsets[i]:
     frame_offsets[i + 1]], byte for byte the frame of that item alone.  The blocks of all items are one batch of the block encoder,
     the block checksums rows of one checksum launch, the n content checksums n rows of another.  Waits for the device once, to learn
-    the total."""
+    the total.  dictionary and dict_id as in compress_frame_device: ONE dictionary and one ID for all items
+    (lz4hip_lz4f_batch_encode_dict_device); with it every block is encoded on the wavefront mapping."""
     import torch
     t, offsets = _p.check_device_batch(t, offsets)
     bid, flags = _block_id(block_size), _encode_flags(block_checksum, content_checksum, content_size)
+    dict_ptr, dict_len, dict_id, keep_dict = _device_dictionary(dictionary, t, dict_id)
+    _no_hc_with_dictionary(high_compression, dict_len)
     with _p.DeviceCall(t) as d:
         n = offsets.numel() - 1
-        bound = d.lib.lz4hip_lz4f_batch_bound(n, t.numel(), bid, flags)
-        out, out_off = d.u8(bound), d.i64(n + 1)
-        scratch = d.u8(max(d.lib.lz4hip_lz4f_batch_encode_scratch_bytes(n, t.numel(), bid), 1))
-        _lib.check(d.lib.lz4hip_lz4f_batch_encode_device(t.data_ptr(), t.numel(), offsets.data_ptr(), n, bid, _p.mode(high_compression), flags,
-                                                         out.data_ptr(), bound, out_off.data_ptr(), scratch.data_ptr(), scratch.numel(), d.stream))
+        if dict_len:
+            bound = _lib.check(d.lib.lz4hip_lz4f_batch_dict_bound(n, t.numel(), bid, flags, dict_len, dict_id))
+            out, out_off = d.u8(bound), d.i64(n + 1)
+            scratch = d.u8(max(_lib.check(d.lib.lz4hip_lz4f_batch_encode_dict_scratch_bytes(n, t.numel(), bid, dict_len)), 1))
+            _lib.check(d.lib.lz4hip_lz4f_batch_encode_dict_device(t.data_ptr(), t.numel(), offsets.data_ptr(), n, dict_ptr, dict_len, dict_id, bid, flags,
+                                                                  out.data_ptr(), bound, out_off.data_ptr(), scratch.data_ptr(), scratch.numel(), d.stream))
+        else:
+            bound = d.lib.lz4hip_lz4f_batch_bound(n, t.numel(), bid, flags)
+            out, out_off = d.u8(bound), d.i64(n + 1)
+            scratch = d.u8(max(d.lib.lz4hip_lz4f_batch_encode_scratch_bytes(n, t.numel(), bid), 1))
+            _lib.check(d.lib.lz4hip_lz4f_batch_encode_device(t.data_ptr(), t.numel(), offsets.data_ptr(), n, bid, _p.mode(high_compression), flags,
+                                                             out.data_ptr(), bound, out_off.data_ptr(), scratch.data_ptr(), scratch.numel(), d.stream))
         bad = ((offsets[1:] < offsets[:-1]).any() | (offsets[0] < 0) | (offsets[-1] > t.numel())).to(torch.int64).reshape(1)
         total, bad = torch.cat([out_off[n:], bad]).tolist()
         if bad:
@@ -379,14 +417,24 @@ def decompress_frames_device(t, offsets, slot_bytes: int = 65536, verify: bool =
 
 
 def compress_frames_host(buf, offsets, block_size: int = 65536, high_compression: bool = False, block_checksum: bool = False,
-                         content_checksum: bool = False, content_size: bool = True):
-    """compress_frames_device for host arrays, through lz4hip_lz4f_batch_encode_host -> (frames, frame_offsets) as numpy arrays."""
+                         content_checksum: bool = False, content_size: bool = True, dictionary=None, dict_id: int = 0):
+    """compress_frames_device for host arrays, through lz4hip_lz4f_batch_encode_host -> (frames, frame_offsets) as numpy arrays.
+    dictionary (bytes-like here, through lz4hip_lz4f_batch_encode_dict_host) and dict_id as in compress_frame_device."""
     buf, offsets = _p.check_host_batch(buf, offsets)
     bid, flags = _block_id(block_size), _encode_flags(block_checksum, content_checksum, content_size)
+    dict_ptr, dict_len, dict_id, keep_dict = _host_dictionary(dictionary, dict_id)
+    _no_hc_with_dictionary(high_compression, dict_len)
     n = offsets.size - 1
     if n and ((np.diff(offsets) < 0).any() or offsets[0] < 0 or offsets[-1] > buf.size):
         raise ArgumentException(_p.BAD_OFFSETS)
     L = _lib.lib()
+    if dict_len:
+        bound = _lib.check(L.lz4hip_lz4f_batch_dict_bound(n, buf.size, bid, flags, dict_len, dict_id))
+        out = np.empty(max(bound, 1), np.uint8)
+        out_off = np.empty(n + 1, np.int64)
+        _lib.check(L.lz4hip_lz4f_batch_encode_dict_host(buf.ctypes.data, buf.size, offsets.ctypes.data, n, dict_ptr, dict_len, dict_id, bid, flags,
+                                                        out.ctypes.data, bound, out_off.ctypes.data))
+        return out[:int(out_off[n])], out_off
     bound = L.lz4hip_lz4f_batch_bound(n, buf.size, bid, flags)
     out = np.empty(max(bound, 1), np.uint8)
     out_off = np.empty(n + 1, np.int64)
