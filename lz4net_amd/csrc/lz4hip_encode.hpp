@@ -20,6 +20,12 @@
 #ifndef LZ4HIP_STAT_ENCDICT
 #define LZ4HIP_STAT_ENCDICT(slot, n) ((void)0)
 #endif
+// Counters of the wavefront fast encoder's branches (EncStat below; tests/simt/emu_kernels.cpp, tests/wave_encode_cases.py): nothing in every other
+// build.  LZ4HIP_STAT_ENC_LOCAL(code) is a statement that exists only where the counters do (a local the counters need).
+#ifndef LZ4HIP_STAT_ENC
+#define LZ4HIP_STAT_ENC(slot, n) ((void)0)
+#define LZ4HIP_STAT_ENC_LOCAL(code)
+#endif
 // Section timers of the wavefront encoder (tools/enc_wave_sections.hip defines these to s_memtime accumulators; nothing in product builds).
 #ifndef LZ4HIP_ENC_T0
 #define LZ4HIP_ENC_DECL() ((void)0)
@@ -45,6 +51,64 @@ enum EncDictStat {
     kEncDictCountCrossesLater,    // ... in a later round
     kEncDictBlocks,               // blocks that ran the parse (n >= 13)
     kEncDictStats
+};
+
+// what a block of tests/wave_encode_cases.py reached in the wavefront fast encoder, per wavefront (a bucket's slots: per bucket, counted by its lowest lane)
+// (one list for the enum and for the names the emulator hands to the tests: emu_enc_stat_name)
+#define LZ4HIP_ENC_STATS(X) \
+    X(StepMatchAllv)          /* a 64-probe step, by outcome and mask form: a match, every lane inside the input (ALLV) */ \
+    X(StepMissAllv)           /* ... 64 misses, ALLV */ \
+    X(StepMatchMasked)        /* ... a match in a step that runs under the lane mask */ \
+    X(StepMissMasked)         /* ... 64 misses under the lane mask: never moves (such a step's last lane is outside the input and stops it) */ \
+    X(StepOutMasked)          /* ... ran out of input (an ALLV step cannot) */ \
+    X(Rounds0)                /* shared-bucket rounds of a step: none */ \
+    X(Rounds1)                /* ... one */ \
+    X(Rounds2)                /* ... two or more */ \
+    X(Bucket2)                /* a shared bucket of two lanes */ \
+    X(Bucket3)                /* ... three */ \
+    X(Bucket4)                /* ... four or more */ \
+    X(CandLower)              /* the winner's candidate is the next lower lane of its bucket */ \
+    X(CandGathered)           /* ... the gathered table entry (the winner alone in its bucket, or the lowest lane of a shared one: WinHasHigher) */ \
+    X(WinHasLower)            /* the winner sits in a shared bucket with a lower member (and none higher) */ \
+    X(WinHasHigher)           /* ... with a higher member (and none lower) */ \
+    X(WinHasBoth)             /* ... with both */ \
+    X(BucketAboveWinner)      /* a shared bucket all of whose lanes lie above the winner: it comes back as it was */ \
+    X(BucketSplitByWinner)    /* a shared bucket with lanes below and above a winner that is not one of them */ \
+    X(BucketBelowWinner)      /* a shared bucket all of whose lanes lie below the winner */ \
+    X(RestoreLive)            /* a shared bucket restored to a non-zero old entry */ \
+    X(RestoreLiveKept)        /* ... which it keeps: all its lanes lie above the winner */ \
+    X(RestoreIntoDict)        /* ... restored to an entry in front of input_start: a position inside the dictionary */ \
+    X(GenericRefusal)         /* generic variant: a lane of a shared bucket whose candidate has its word and is past the distance limit */ \
+    X(WinStep1)               /* a search won in its first step */ \
+    X(WinStep2)               /* ... second */ \
+    X(WinStep3)               /* ... third or later */ \
+    X(FirstWords)             /* a first step fed from first_words */ \
+    X(WindowRebase)           /* test-next-position: the register window re-based */ \
+    X(WindowServed)           /* ... served from the window as it stood */ \
+    X(TestWide)               /* test-next-position: test and count in one 256-byte round */ \
+    X(TestBytewise)           /* ... the word test, then the count */ \
+    X(TestHit)                \
+    X(TestMiss)               \
+    X(TestHit256)             /* a hit of 256 bytes and more */ \
+    X(AfterCombined)          /* after a search: catch-up and count requested together */ \
+    X(AfterGuarded)           /* ... the guarded rounds near the end of the block */ \
+    X(Back0)                  /* after a search: no byte caught up */ \
+    X(Back1To63)              \
+    X(Back64)                 /* 64 bytes and more with bound == 64 (64 is all there is) */ \
+    X(Back64Continued)        /* 64 bytes and more with bound > 64: in the combined path the continuation ran */ \
+    X(EmitOne)                /* emit: the one-store form */ \
+    X(EmitOneRefused)         /* ... refused by its limit test */ \
+    X(EmitGeneral)            \
+    X(DeferPassed)            /* hand-over rule: check passed */ \
+    X(Deferred)               /* ... block handed over */ \
+    X(Pos0Search)             /* 64k variant: a search won with the candidate at position 0 (the empty bucket) */ \
+    X(Pos0Test)               /* ... a test-next-position hit at position 0 */ \
+    /* end */
+enum EncStat {
+#define LZ4HIP_ENC_STAT_ENUM(name) kEnc##name,
+    LZ4HIP_ENC_STATS(LZ4HIP_ENC_STAT_ENUM)
+#undef LZ4HIP_ENC_STAT_ENUM
+    kEncStats
 };
 
 template <bool GENERIC> struct FastTable;
@@ -183,12 +247,16 @@ LZ4HIP_DEVICE int wave_find_step(In in, typename FastTable<GENERIC>::entry* tabl
     uint64_t shared = wv::ballot(valid && (int)table[h] != lane);
     wv::mem_sync();
     uint64_t bucket = 0;                                             // the lanes of this lane's bucket (0: alone)
+    LZ4HIP_STAT_ENC_LOCAL(int stat_rounds = 0;)
     while (shared) {                                                 // rare: one round per shared bucket
         const uint32_t hb = wv::readlane(h, wv::ctz64(shared));
         const uint64_t g = wv::ballot(valid && h == hb);
         if (valid && h == hb) bucket = g;
         shared &= ~g;
+        LZ4HIP_STAT_ENC_LOCAL(stat_rounds++;)
+        LZ4HIP_STAT_ENC(__builtin_popcountll(g) >= 4 ? kEncBucket4 : __builtin_popcountll(g) == 3 ? kEncBucket3 : kEncBucket2, lane == 0);
     }
+    LZ4HIP_STAT_ENC(stat_rounds >= 2 ? kEncRounds2 : stat_rounds == 1 ? kEncRounds1 : kEncRounds0, lane == 0);
     const uint64_t lower = bucket & below_me;
     const int prev = lower ? 63 - __builtin_clzll(lower) : lane;
     const uint32_t pw = wv::shuffle(w, prev);
@@ -197,6 +265,19 @@ LZ4HIP_DEVICE int wave_find_step(In in, typename FastTable<GENERIC>::entry* tabl
     const bool cand = valid && (!GENERIC || cref >= p - kMaxDistance) && (lower ? pw : rw) == w;   // lz4.c:427 / :654
     const uint64_t stop = wv::ballot(cand || !valid);
     const int m = stop ? wv::ctz64(stop) : 63;                       // the last lane of this step that probes (if valid)
+    LZ4HIP_STAT_ENC(kEncGenericRefusal, GENERIC && valid && bucket != 0 && cref < p - kMaxDistance && (lower ? pw : rw) == w);
+    LZ4HIP_STAT_ENC(kEncCandLower, lane == m && cand && lower != 0);
+    LZ4HIP_STAT_ENC(kEncCandGathered, lane == m && cand && lower == 0);
+    LZ4HIP_STAT_ENC(kEncWinHasLower, lane == m && cand && lower != 0 && (bucket >> lane) == 1);
+    LZ4HIP_STAT_ENC(kEncWinHasHigher, lane == m && cand && bucket != 0 && lower == 0);
+    LZ4HIP_STAT_ENC(kEncWinHasBoth, lane == m && cand && lower != 0 && (bucket >> lane) > 1);
+    LZ4HIP_STAT_ENC(kEncBucketAboveWinner, stop != 0 && bucket != 0 && lower == 0 && lane > m);
+    LZ4HIP_STAT_ENC(kEncBucketSplitByWinner, stop != 0 && bucket != 0 && lower == 0 && lane < m && !((bucket >> m) & 1) && (bucket >> m) != 0);
+    LZ4HIP_STAT_ENC(kEncBucketBelowWinner, stop != 0 && bucket != 0 && lower == 0 && (bucket >> m) == 0);
+    LZ4HIP_STAT_ENC(kEncRestoreLive, bucket != 0 && lower == 0 && r != 0);
+    LZ4HIP_STAT_ENC(kEncRestoreIntoDict, bucket != 0 && lower == 0 && r > 0 && r < input_start(in));
+    LZ4HIP_STAT_ENC(kEncRestoreLiveKept, stop != 0 && bucket != 0 && lower == 0 && r != 0 && lane > m);
+    LZ4HIP_STAT_ENC(kEncPos0Search, !GENERIC && lane == m && cand && cref == 0);
     // table: lanes after the winner restore their bucket, of the others the highest lane of each bucket writes
     if (wv::any(bucket != 0)) {
         if (valid) table[h] = (entry)r;                              // (lanes of one bucket hold the same old entry)
@@ -209,11 +290,13 @@ LZ4HIP_DEVICE int wave_find_step(In in, typename FastTable<GENERIC>::entry* tabl
     }
     wv::mem_sync();
     if (stop) {
-        if (!ALLV && !wv::readlane((uint32_t)valid, m)) return 2;
+        if (!ALLV && !wv::readlane((uint32_t)valid, m)) { LZ4HIP_STAT_ENC(kEncStepOutMasked, lane == 0); return 2; }
+        LZ4HIP_STAT_ENC(ALLV ? kEncStepMatchAllv : kEncStepMatchMasked, lane == 0);
         ip = (int)wv::readlane((uint32_t)p, m);
         ref = (int)wv::readlane((uint32_t)cref, m);
         return 1;
     }
+    LZ4HIP_STAT_ENC(ALLV ? kEncStepMissAllv : kEncStepMissMasked, lane == 0);
     ip = (int)wv::readlane((uint32_t)p_next, 63);                    // 64 probes without a match
     return 0;
 }
@@ -228,9 +311,10 @@ LZ4HIP_DEVICE bool wave_find_match(In in, typename FastTable<GENERIC>::entry* ta
         const int a63 = attempts + 63;
         const bool all_valid = ip + skip_sum(a63) - skip_sum(attempts) + (a63 >> 6) <= mflimit;
         const bool hw = have_first && attempts == 67;
+        LZ4HIP_STAT_ENC(kEncFirstWords, hw && wv::lane() == 0);
         const int st = all_valid ? wave_find_step<GENERIC, true>(in, table, ip, ref, mflimit, attempts, hw, first_words)
                                  : wave_find_step<GENERIC, false>(in, table, ip, ref, mflimit, attempts, hw, first_words);
-        if (st == 1) return true;
+        if (st == 1) { LZ4HIP_STAT_ENC(attempts == 67 ? kEncWinStep1 : attempts == 131 ? kEncWinStep2 : kEncWinStep3, wv::lane() == 0); return true; }
         if (st == 2) return false;
         attempts += 64;
         LZ4HIP_ENC_COUNT(4, 1);
@@ -265,6 +349,7 @@ LZ4HIP_DEVICE int encode_fast_block(In in, int n, uint8_t* out, int cap, unsigne
         if (GENERIC) {                                                // lz4.c:403: position 0 is inserted
             const uint32_t h0 = T::hash(input_word(in, start));       // (a no-op on a zeroed table; kept for clarity)
             if (lane == 0) table[h0] = (entry)start;
+            wv::mem_sync();                                           // (the first step's lanes gather this entry: with a dictionary it is T, not the fill's 0)
         }
         ip = start + 1;                                               // lz4.c:631: position 0 is never probed
         for (;;) {
@@ -385,7 +470,8 @@ LZ4HIP_DEVICE FastSeq emit_fast_sequence(const uint8_t* in, uint8_t* out, int ca
     if (ll < 15 && extra < 15) {
         // token, literals, offset: ll + 3 <= 17 bytes, lane j writes byte j.  (lz4.c:663: op + 1 + ll + (ll >> 8) > cap - 8 fails; what
         // :728 tests afterwards, op + 3 + ll > cap - 6, is the same inequality for these lengths.)
-        if (op + 1 + ll > cap - 8) return FastSeq{ 0, false };
+        if (op + 1 + ll > cap - 8) { LZ4HIP_STAT_ENC(kEncEmitOneRefused, lane == 0); return FastSeq{ 0, false }; }
+        LZ4HIP_STAT_ENC(kEncEmitOne, lane == 0);
         const uint32_t tok = ((uint32_t)ll << 4) | (uint32_t)extra;
         if (lane < ll + 3) {
             uint32_t v = tok;
@@ -395,6 +481,7 @@ LZ4HIP_DEVICE FastSeq emit_fast_sequence(const uint8_t* in, uint8_t* out, int ca
         }
         return FastSeq{ op + ll + 3, true };
     }
+    LZ4HIP_STAT_ENC(kEncEmitGeneral, lane == 0);
     int token_at = op++;
     if (op + ll + (ll >> 8) > cap - 8) return FastSeq{ 0, false };                  // lz4.c:663
     if (ll >= 15 && op + (ll - 15) / 255 + 1 + ll > cap) return FastSeq{ 0, false };
@@ -455,11 +542,13 @@ LZ4HIP_DEVICE int encode_fast_block64k(const uint8_t* in, int n, uint8_t* out, i
                 int mlen;
                 const int room = ip - anchor, bound = room < ref ? room : ref;
                 if (ip + kMinMatch + 256 <= matchlimit) {
+                    LZ4HIP_STAT_ENC(kEncAfterCombined, lane == 0);
                     const int ia = ip - 1 - lane, ib = ref - 1 - lane;
                     const uint32_t ca = in[ia > 0 ? ia : 0], cb = in[ib > 0 ? ib : 0];
                     const uint32_t diff = load_u32(in + ip + kMinMatch + 4 * lane) ^ load_u32(in + ref + kMinMatch + 4 * lane);
                     const uint64_t differs = wv::ballot(lane >= bound || ca != cb);
                     int back = differs ? wv::ctz64(differs) : 64;
+                    LZ4HIP_STAT_ENC(back == 0 ? kEncBack0 : back < 64 ? kEncBack1To63 : bound > 64 ? kEncBack64Continued : kEncBack64, lane == 0);
                     if (back == 64 && bound > 64) back = 64 + wave_catch_up(in, ip - 64, ref - 64, bound - 64);
                     const uint64_t stop = wv::ballot(diff != 0);
                     int fwd;
@@ -468,8 +557,10 @@ LZ4HIP_DEVICE int encode_fast_block64k(const uint8_t* in, int n, uint8_t* out, i
                     ip -= back; ref -= back;
                     mlen = kMinMatch + back + fwd;
                 } else {
+                    LZ4HIP_STAT_ENC(kEncAfterGuarded, lane == 0);
                     const uint32_t fwd_round = common_length_round(in, ip + kMinMatch, ref + kMinMatch, matchlimit, 0);
                     const int back = bound > 0 ? wave_catch_up(in, ip, ref, bound) : 0;
+                    LZ4HIP_STAT_ENC(back == 0 ? kEncBack0 : back < 64 ? kEncBack1To63 : bound > 64 ? kEncBack64Continued : kEncBack64, lane == 0);
                     ip -= back; ref -= back;
                     mlen = kMinMatch + back + wave_common_length(in, ip + kMinMatch + back, ref + kMinMatch + back, matchlimit, fwd_round);
                 }
@@ -483,7 +574,8 @@ LZ4HIP_DEVICE int encode_fast_block64k(const uint8_t* in, int n, uint8_t* out, i
             for (;;) {
                 LZ4HIP_ENC_T0();
                 if (may_defer && (++sequences % kDeferCheckSequences) == 0) {
-                    if (ip - checked_at < kDeferCheckSequences * kDeferBytesPerSequence) return kDeferredResult;
+                    if (ip - checked_at < kDeferCheckSequences * kDeferBytesPerSequence) { LZ4HIP_STAT_ENC(kEncDeferred, lane == 0); return kDeferredResult; }
+                    LZ4HIP_STAT_ENC(kEncDeferPassed, lane == 0);
                     checked_at = ip;
                 }
                 if (ip > mflimit) { anchor = ip; goto tail; }        // lz4.c:736
@@ -497,7 +589,8 @@ LZ4HIP_DEVICE int encode_fast_block64k(const uint8_t* in, int n, uint8_t* out, i
                     win = pos + 4 <= n ? load_u32(in + pos) : 0u;
                     wv::wait_vector_memory();
                     LZ4HIP_KEEP(win);
-                }
+                    LZ4HIP_STAT_ENC(kEncWindowRebase, lane == 0);
+                } else LZ4HIP_STAT_ENC(kEncWindowServed, lane == 0);
                 const bool wide = ip + 256 <= matchlimit;             // 256 bytes from ip may be read and counted (wave-uniform)
                 // Both loads are issued in EVERY iteration, from addresses clamped to the block (n >= 13 here): a load under a condition
                 // needs its register zeroed first, and that write has to wait for whatever load into the same register is still in
@@ -522,10 +615,11 @@ LZ4HIP_DEVICE int encode_fast_block64k(const uint8_t* in, int n, uint8_t* out, i
                 table[h] = (uint16_t)ip;
                 LZ4HIP_ENC_T(5);
                 int mlen;
+                LZ4HIP_STAT_ENC(wide ? kEncTestWide : kEncTestBytewise, lane == 0);
                 if (wide) {
                     const uint32_t diff = a4 ^ load_u32(in + ref2 + 4 * lane);
                     const uint64_t stop = wv::ballot(diff != 0);
-                    if (stop & 1ull) { LZ4HIP_ENC_T(3); break; }      // A32(ref) != A32(ip)
+                    if (stop & 1ull) { LZ4HIP_STAT_ENC(kEncTestMiss, lane == 0); LZ4HIP_ENC_T(3); break; }      // A32(ref) != A32(ip)
                     if (stop) {
                         const int first = wv::ctz64(stop);
                         mlen = first * 4 + (__builtin_ctz(wv::readlane(diff, first)) >> 3);
@@ -533,10 +627,13 @@ LZ4HIP_DEVICE int encode_fast_block64k(const uint8_t* in, int n, uint8_t* out, i
                         mlen = 256 + wave_common_length(in, ip + 256, ref2 + 256, matchlimit);
                     }
                 } else {
-                    if (input_word(in, ref2) != cur_word) { LZ4HIP_ENC_T(3); break; }
+                    if (input_word(in, ref2) != cur_word) { LZ4HIP_STAT_ENC(kEncTestMiss, lane == 0); LZ4HIP_ENC_T(3); break; }
                     mlen = kMinMatch + wave_common_length(in, ip + kMinMatch, ref2 + kMinMatch, matchlimit);
                 }
                 LZ4HIP_ENC_T(6);
+                LZ4HIP_STAT_ENC(kEncTestHit, lane == 0);
+                LZ4HIP_STAT_ENC(kEncTestHit256, lane == 0 && mlen >= 256);
+                LZ4HIP_STAT_ENC(kEncPos0Test, lane == 0 && ref2 == 0);
                 const FastSeq e = emit_fast_sequence(in, out, cap, op, ip, 0, (uint32_t)(ip - ref2) & 0xFFFFu, mlen);   // zero-literal sequence (lz4.c:751)
                 if (!e.ok) return 0;
                 op = e.op;

@@ -103,6 +103,28 @@ def hc_stats(reset=True):
     return [int(x) for x in st[:n]]
 
 
+def enc_stats(reset=True, library=None):
+    """lz4hip::EncStat: the branch counters of the wavefront fast encoder since the last reset (library: another build of emu_kernels.cpp)"""
+    st = (C.c_ulonglong * 64)()
+    n = (library or lib()).emu_enc_stats(st, int(reset))
+    return [int(x) for x in st[:n]]
+
+
+class descending_lanes:
+    """with emu.descending_lanes(): the scheduler runs the live lanes of a wavefront from the highest down between two rendezvous, so of
+    several stores to one address the LOWEST lane's lands last (tests/simt/simt.hpp)"""
+
+    def __init__(self, library=None):
+        self.lib = library
+
+    def __enter__(self):
+        (self.lib or lib()).emu_lane_order(1)
+
+    def __exit__(self, *a):
+        (self.lib or lib()).emu_lane_order(0)
+        return False
+
+
 def hc_lcp_tables(blocks):
     """(len(blocks), 65536) uint32: the tables hc_nat_chain_kernel<uint32_t> and hc_lcp_fill_kernel leave of poisoned memory"""
     src, sl = pack(blocks)

@@ -15,6 +15,9 @@ static unsigned long long g_hc_stat[96];      // lz4hip::HcStat: branches of the
 #define LZ4HIP_STAT_HC(slot, n) do { g_hc_stat[slot] += (unsigned long long)(n); } while (0)
 static unsigned long long g_l4_stat[32];      // lz4hip::L4Stat: the parser, the promotion and the ring of the fourth-generation lane decoder, per lane (tests/lane_decode_cases.py)
 #define LZ4HIP_STAT_L4(slot, cond) do { if (cond) g_l4_stat[slot]++; } while (0)
+static unsigned long long g_enc_stat[64];     // lz4hip::EncStat: the branches of the wavefront fast encoder, per wavefront (tests/wave_encode_cases.py)
+#define LZ4HIP_STAT_ENC(slot, n) do { g_enc_stat[slot] += (unsigned long long)(n); } while (0)
+#define LZ4HIP_STAT_ENC_LOCAL(code) code
 
 #include "lz4hip_common.hpp"
 #include "lz4hip_decode.hpp"
@@ -349,6 +352,21 @@ int emu_l4_stats(unsigned long long* out, int reset)
     for (int i = 0; i < kL4Stats; i++) { out[i] = g_l4_stat[i]; if (reset) g_l4_stat[i] = 0; }
     return kL4Stats;
 }
+static_assert(kEncStats <= 64, "g_enc_stat");
+int emu_enc_stats(unsigned long long* out, int reset)
+{
+    for (int i = 0; i < kEncStats; i++) { out[i] = g_enc_stat[i]; if (reset) g_enc_stat[i] = 0; }
+    return kEncStats;
+}
+const char* emu_enc_stat_name(int slot)
+{
+#define EMU_ENC_STAT_NAME(name) #name,
+    static const char* const names[] = { LZ4HIP_ENC_STATS(EMU_ENC_STAT_NAME) };
+#undef EMU_ENC_STAT_NAME
+    return slot >= 0 && slot < kEncStats ? names[slot] : "";
+}
+// 1: the scheduler runs the live lanes of a wavefront in DESCENDING order between two rendezvous (simt.hpp); 0: ascending, the default
+void emu_lane_order(int descending) { simt::rt().descending = descending != 0; }
 unsigned long long emu_iterations(int reset) { const unsigned long long v = g_iterations; if (reset) g_iterations = 0; return v; }
 }
 

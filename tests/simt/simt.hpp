@@ -109,6 +109,7 @@ struct Runtime {
     std::vector<unsigned char> lds;
     std::function<void()> body;
     uint64_t steps = 0;
+    bool descending = false;   // run the live lanes of a wave from the highest down: of several stores to one address the LOWEST lane's lands last
 };
 
 inline Runtime& rt()
@@ -175,8 +176,8 @@ inline void run_block(size_t lds_bytes)
             any_live = true;
             if (at_barrier[(size_t)w]) continue;
             all_blocked = false;
-            for (int t = lo; t < hi; t++) {
-                Lane& l = r.lanes[(size_t)t];
+            for (int k = lo; k < hi; k++) {
+                Lane& l = r.lanes[(size_t)(r.descending ? lo + hi - 1 - k : k)];
                 if (l.done) continue;
                 r.cur = &l;
                 fiber_switch(&r.sched, &l.ctx);
