@@ -110,6 +110,13 @@ def enc_stats(reset=True, library=None):
     return [int(x) for x in st[:n]]
 
 
+def lane_enc_stats(reset=True):
+    """lz4hip::LaneEncStat: the branch counters of the fast lane encoder since the last reset"""
+    st = (C.c_ulonglong * 96)()
+    n = lib().emu_lane_enc_stats(st, int(reset))
+    return [int(x) for x in st[:n]]
+
+
 class descending_lanes:
     """with emu.descending_lanes(): the scheduler runs the live lanes of a wavefront from the highest down between two rendezvous, so of
     several stores to one address the LOWEST lane's lands last (tests/simt/simt.hpp)"""

@@ -18,6 +18,9 @@ static unsigned long long g_l4_stat[32];      // lz4hip::L4Stat: the parser, the
 static unsigned long long g_enc_stat[64];     // lz4hip::EncStat: the branches of the wavefront fast encoder, per wavefront (tests/wave_encode_cases.py)
 #define LZ4HIP_STAT_ENC(slot, n) do { g_enc_stat[slot] += (unsigned long long)(n); } while (0)
 #define LZ4HIP_STAT_ENC_LOCAL(code) code
+static unsigned long long g_lane_enc_stat[96]; // lz4hip::LaneEncStat: the branches of the fast lane encoder, per lane (tests/lane_encode_cases.py)
+#define LZ4HIP_STAT_LANE(slot, cond) ((cond) ? (void)g_lane_enc_stat[(unsigned)(slot) < 96u ? (unsigned)(slot) : 95u]++ : (void)0)
+#define LZ4HIP_STAT_LANE_LOCAL(code) code
 
 #include "lz4hip_common.hpp"
 #include "lz4hip_decode.hpp"
@@ -364,6 +367,20 @@ const char* emu_enc_stat_name(int slot)
     static const char* const names[] = { LZ4HIP_ENC_STATS(EMU_ENC_STAT_NAME) };
 #undef EMU_ENC_STAT_NAME
     return slot >= 0 && slot < kEncStats ? names[slot] : "";
+}
+static_assert(kLaneEncStats < 96, "g_lane_enc_stat (the last slot takes what is out of range)");
+int emu_lane_enc_stats(unsigned long long* out, int reset)
+{
+    if (g_lane_enc_stat[95]) abort();                                // a slot computed out of range
+    for (int i = 0; i < kLaneEncStats; i++) { out[i] = g_lane_enc_stat[i]; if (reset) g_lane_enc_stat[i] = 0; }
+    return kLaneEncStats;
+}
+const char* emu_lane_enc_stat_name(int slot)
+{
+#define EMU_LANE_ENC_STAT_NAME(name) #name,
+    static const char* const names[] = { LZ4HIP_LANE_ENC_STATS(EMU_LANE_ENC_STAT_NAME) };
+#undef EMU_LANE_ENC_STAT_NAME
+    return slot >= 0 && slot < kLaneEncStats ? names[slot] : "";
 }
 // 1: the scheduler runs the live lanes of a wavefront in DESCENDING order between two rendezvous (simt.hpp); 0: ascending, the default
 void emu_lane_order(int descending) { simt::rt().descending = descending != 0; }

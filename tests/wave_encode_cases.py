@@ -49,6 +49,19 @@ def bucket(word, generic=False):
     return ((np.asarray(word, np.uint64) * np.uint64(GOLDEN)) & np.uint64(0xFFFFFFFF)) >> np.uint64(20 if generic else 19)
 
 
+GOLDEN_INVERSE = pow(GOLDEN, -1, 1 << 32)
+
+
+def product(word):
+    """the 32-bit hash product of a little-endian word: bucket = product >> 19 (64k variant), the lane encoder's tag = product >> 4 & 0x3FF"""
+    return int(word) * GOLDEN & 0xFFFFFFFF
+
+
+def word_of(prod):
+    """the four bytes whose hash product is prod"""
+    return int(int(prod) * GOLDEN_INVERSE & 0xFFFFFFFF).to_bytes(4, "little")
+
+
 def _b(values):
     return bytes(bytearray(int(x) for x in values))
 
@@ -168,6 +181,24 @@ class Build:
                 self.used.add(target >> 1 if not self.wide else target)
                 return [bytes([x & 255, x >> 8 & 255, x >> 16 & 255, x >> 24]) for x in ws[:k]]
         raise Retry("no colliding words")
+
+    def tagged(self, like, same_tag, k=1):
+        """k different words (bytes 1..255) in the bucket of the word `like` whose tag -- bits 4 .. 13 of the hash product, which the lane
+        encoder keeps next to a position -- is `like`'s (same_tag) or another.  The multiplier is odd: the word of a chosen product is the
+        product times the multiplier's inverse mod 2^32.  The bucket is bits 19 .. 31; bits 0 .. 3 and 14 .. 18 are free."""
+        prod = product(le(like))
+        out = []
+        for _ in range(4000):
+            free = int(self.rng.integers(0, 1 << 9))
+            tag = prod >> 4 & 0x3FF if same_tag else int(self.rng.integers(0, 1 << 10))
+            if not same_tag and tag == prod >> 4 & 0x3FF:
+                continue
+            w = word_of(prod & 0xFFF80000 | (free >> 4) << 14 | tag << 4 | free & 15)
+            if 0 not in w and w != bytes(like) and w not in out:
+                out.append(w)
+                if len(out) == k:
+                    return out
+        raise Retry("no tagged words")
 
     def finish(self):
         a = np.frombuffer(bytes(self.b), np.uint8).astype(np.uint64)
@@ -1174,13 +1205,14 @@ def check_dict(encode, cases, want, what):
         assert (dst[i, max(wr, 0):] == 0xA5).all(), (what, name, "wrote past the result")
 
 
-def assert_moves(f, st):
+def assert_moves(f, st, slots=S):
+    """slots: slot name -> index, of the kernel the counters st are of"""
     for slot in f.moves:
-        assert st[S[slot]] > 0, (f.name, "counter never moved", slot)
+        assert st[slots[slot]] > 0, (f.name, "counter never moved", slot)
 
 
-def assert_pairs(f, alone):
+def assert_pairs(f, alone, slots=S):
     """alone: case index -> counters of that case encoded alone"""
     for a, b, slot in f.pairs:
-        x, y = alone[a][S[slot]], alone[b][S[slot]]
+        x, y = alone[a][slots[slot]], alone[b][slots[slot]]
         assert x < y, (f.name, "pair not in the declared direction", f.cases[a][0], f.cases[b][0], slot, x, y)
